@@ -8,7 +8,7 @@ reference's fixtures and KNN application use), inputs and keys already resident 
 replicated keys (weak scaling, no data-path collective -- SURVEY.md section 8e); rank 0 prints ONE
 JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--set SK-128] [--batch 4096] [--mode replicated|party] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--set SK-128] [--batch 4096] [--mode replicated|party] [--no-cpu-baseline] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no launcher (WORLD_SIZE unset): this process starts the N ranks ITSELF, as child processes and before
@@ -31,6 +31,23 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "torus-fhe_amd"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much, .npy headers included
+
+
+def dump_outputs(directory, name, out):
+    """--dump-outputs: the records the timed path handed back in its last step, as DIR/<name>.npy in float64 (int32 torus words convert
+    exactly).  A batch larger than DUMP_BYTES keeps a fixed, seeded sample of its rows, in order, and their indices go to DIR/<name>_rows.npy."""
+    os.makedirs(directory, exist_ok=True)
+    rows = out.shape[0]
+    keep = min(rows, (DUMP_BYTES - 256) // (8 * out[0].size + 8))   # 256: two .npy headers; + 8: the row index of a sampled row
+    rows_path = os.path.join(directory, f"{name}_rows.npy")
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(0x5EED00D0).choice(rows, keep, replace=False))
+        np.save(rows_path, idx.astype(np.float64))
+        out = out[idx]
+    elif os.path.exists(rows_path):   # left by an earlier, sampled dump into the same directory
+        os.remove(rows_path)
+    np.save(os.path.join(directory, f"{name}.npy"), out.astype(np.float64))
 
 
 def algorithmic_bytes(p, rotations=1):
@@ -141,7 +158,7 @@ def dist_setup(n_gpus):
         else:
             dist.init_process_group("gloo", rank=rank, world_size=world)
             dev = torch.device("cpu")
-            dist.barrier()
+            dist.all_reduce(torch.zeros(1))   # rendezvous: a CPU all-reduce, as in barrier() below
     except Exception as e:
         print(f"[bench] rank {rank}: {backend} backend failed to initialise: {e!r}", file=sys.stderr, flush=True)
         os._exit(3)   # non-zero on this rank; the launcher tears the others down
@@ -153,7 +170,11 @@ def dist_setup(n_gpus):
     def barrier():
         if dev.type == "cuda":
             torch.cuda.synchronize()
-        dist.barrier()
+            dist.barrier()
+        else:
+            # gloo: an all-reduce of a CPU tensor.  dist.barrier() asks torch for the accelerator, which starts the HIP runtime and opens
+            # the GPU in every rank -- also in the --dry-topology ranks, which must not touch it
+            dist.all_reduce(torch.zeros(1))
 
     def max_reduce(x):
         t = torch.tensor([float(x)], dtype=torch.float64, device=dev)
@@ -349,6 +370,8 @@ def run_party(args, p, rank, world, barrier, max_reduce, backend, device):
     ranks = gather_objects(rank_record(rank, device, B * args.steps / topo["group_size"], mine))   # a rank's share of its group's gates
     rot_ms = [a.elapsed_time(b) for a, b in be.timing]
     got = out.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "nand_out", got)
     errors = int((K.decrypt(got) != ~(bits_a.astype(bool) & bits_b.astype(bool))).sum())
     if errors:
         raise RuntimeError(f"rank {rank}: {errors} of {B} bootstrapped NAND outputs decrypt wrongly")
@@ -403,9 +426,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-per-thread", type=int, default=None, help="gates per host thread in the exact-oracle sample of the CPU baseline (default 8; 1 for multi-key sets; the FFT-engine sample is 8x that)")
     ap.add_argument("--dry-topology", action="store_true", help="rank start-up + rendezvous + barrier only (no GPU): rehearsal of --gpus N")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's output records of the last step to DIR/nand_out.npy (float64, at most 64 MB: a seeded row sample beyond that)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("[bench] --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("[bench] --steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))   # nothing above has touched torch, HIP or the GPU
@@ -473,6 +500,8 @@ def main():
     ranks = gather_objects(rank_record(rank, device, B * args.steps, mine))
 
     out = do.download((B, words))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "nand_out", out)
     errors = int((K.decrypt(out) != ~(bits_a.astype(bool) & bits_b.astype(bool))).sum())
     if errors:
         raise RuntimeError(f"rank {rank}: {errors} of {B} bootstrapped NAND outputs decrypt wrongly")
