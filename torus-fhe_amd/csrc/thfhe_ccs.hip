@@ -19,12 +19,14 @@
 // LDS: T1 8 + acc 36 + v 36 + slots 64 = 144 KiB (sized for P <= 8).
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include "../../include/thfhe_hip.h"
 #include "thfhe_common.h"
+#include "thfhe_devctx.h"
 #include "thfhe_lane.h"
 #include "thfhe_mk_shared.h"
 
@@ -340,60 +342,51 @@ __global__ __launch_bounds__(512, 2) void ccs_blind_rotate_wide_kernel(CCSArgs a
 
 }  // namespace
 
-struct thfhe_ccs_ctx {
+struct THFHE_INTERNAL thfhe_ccs_ctx : DevCtx {
     thfhe_params p;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    cplx *d_bk = nullptr, *d_pk = nullptr, *d_crs = nullptr, *d_tw = nullptr;
-    int32_t *d_ksk = nullptr;
+    DevBuf d_bk, d_pk, d_crs, d_tw;
+    DevBuf d_ksk;
     int row_words = 0, w_pad = 0, words = 0;
-    size_t cap = 0;
-    int32_t *d_bara = nullptr, *d_barb = nullptr, *d_u = nullptr, *d_in[2] = {nullptr, nullptr}, *d_out = nullptr;
-    int32_t *d_v = nullptr;   // wide shape (more than 8 parties or 8 levels): the v polynomials of a step, int32[jobs][P+1][1024]
+    DevBuf d_bara, d_barb, d_u, d_in[2], d_out;
+    DevBuf d_v;   // wide shape (more than 8 parties or 8 levels): the v polynomials of a step, int32[jobs][P+1][1024]
     bool wide = false;
-    std::mutex mu;
 };
 
 namespace {
 int ccs_ensure(thfhe_ccs_ctx *c, size_t jobs) {
-    if (jobs <= c->cap) return THFHE_OK;
-    for (int32_t **q : {&c->d_bara, &c->d_barb, &c->d_u, &c->d_in[0], &c->d_in[1], &c->d_out, &c->d_v}) {
-        (void)hipFree(*q);
-        *q = nullptr;
-    }
-    c->cap = 0;
     const size_t rec = (size_t)c->words + 1;
-    THFHE_HIP(hipMalloc(&c->d_bara, jobs * c->w_pad * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_barb, jobs * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_u, jobs * ((size_t)c->p.parties * 1024 + 1) * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_in[0], jobs * rec * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_in[1], jobs * rec * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_out, jobs * rec * sizeof(int32_t)));
-    if (c->wide) THFHE_HIP(hipMalloc(&c->d_v, jobs * ((size_t)c->p.parties + 1) * 1024 * sizeof(int32_t)));
-    c->cap = jobs;
-    return THFHE_OK;
+    int rc = c->d_bara.grow(jobs * c->w_pad * sizeof(int32_t));
+    if (!rc) rc = c->d_barb.grow(jobs * sizeof(int32_t));
+    if (!rc) rc = c->d_u.grow(jobs * ((size_t)c->p.parties * 1024 + 1) * sizeof(int32_t));
+    if (!rc) rc = c->d_in[0].grow(jobs * rec * sizeof(int32_t));
+    if (!rc) rc = c->d_in[1].grow(jobs * rec * sizeof(int32_t));
+    if (!rc) rc = c->d_out.grow(jobs * rec * sizeof(int32_t));
+    if (!rc && c->wide) rc = c->d_v.grow(jobs * ((size_t)c->p.parties + 1) * 1024 * sizeof(int32_t));
+    return rc;
 }
 
 int ccs_run(thfhe_ccs_ctx *c, MKLin L, const int32_t *in0, const int32_t *in1, int32_t mu, int32_t *out, size_t count) {
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     int rc = ccs_ensure(c, count);
     if (rc) return rc;
+    int32_t *const d_in0 = c->d_in[0].as<int32_t>(), *const d_in1 = c->d_in[1].as<int32_t>(), *const d_out = c->d_out.as<int32_t>();
+    int32_t *const d_bara = c->d_bara.as<int32_t>(), *const d_barb = c->d_barb.as<int32_t>(), *const d_u = c->d_u.as<int32_t>();
     const size_t rec = (size_t)c->words + 1, bytes = count * rec * sizeof(int32_t);
-    THFHE_HIP(hipMemcpyAsync(c->d_in[0], in0, bytes, hipMemcpyHostToDevice, c->stream));
-    if (in1) THFHE_HIP(hipMemcpyAsync(c->d_in[1], in1, bytes, hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(d_in0, in0, bytes, hipMemcpyHostToDevice, c->stream));
+    if (in1) THFHE_HIP(hipMemcpyAsync(d_in1, in1, bytes, hipMemcpyHostToDevice, c->stream));
     dim3 pg((unsigned)((c->words + 1 + 255) / 256), (unsigned)count);
-    hipLaunchKernelGGL(mk_prologue_kernel, pg, dim3(256), 0, c->stream, c->d_in[0], in1 ? c->d_in[1] : c->d_in[0], c->d_in[0], L, L, (const int32_t *)nullptr, 1,
-                       c->words, c->w_pad, 11, (long)count, c->d_bara, c->d_barb);
-    CCSArgs a{c->d_bk, c->d_pk, c->d_crs, c->d_tw, c->d_bara, c->d_barb, c->d_u, (long)count, c->p.parties, c->p.n, c->p.l, c->w_pad, c->p.Bgbit, mu};
-    if (c->wide) hipLaunchKernelGGL(ccs_blind_rotate_wide_kernel, dim3((unsigned)count), dim3(512), 0, c->stream, a, c->d_v);
+    hipLaunchKernelGGL(mk_prologue_kernel, pg, dim3(256), 0, c->stream, d_in0, in1 ? d_in1 : d_in0, d_in0, L, L, (const int32_t *)nullptr, 1,
+                       c->words, c->w_pad, 11, (long)count, d_bara, d_barb);
+    CCSArgs a{c->d_bk.as<cplx>(), c->d_pk.as<cplx>(), c->d_crs.as<cplx>(), c->d_tw.as<cplx>(), d_bara, d_barb, d_u, (long)count, c->p.parties, c->p.n, c->p.l, c->w_pad, c->p.Bgbit, mu};
+    if (c->wide) hipLaunchKernelGGL(ccs_blind_rotate_wide_kernel, dim3((unsigned)count), dim3(512), 0, c->stream, a, c->d_v.as<int32_t>());
     else hipLaunchKernelGGL(ccs_blind_rotate_kernel, dim3((unsigned)count), dim3(512), 0, c->stream, a);
-    MKKSArgs k{c->d_ksk, c->d_u, c->d_out, (long)count, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, 1024, c->p.parties * 1024 + 1, 1024};
+    MKKSArgs k{c->d_ksk.as<int32_t>(), d_u, d_out, (long)count, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, 1024, c->p.parties * 1024 + 1, 1024};
     const int nsplit = count * c->p.parties <= 64 ? 16 : (count * c->p.parties <= 256 ? 4 : 1);
-    THFHE_HIP(hipMemsetAsync(c->d_out, 0, bytes, c->stream));
+    THFHE_HIP(hipMemsetAsync(d_out, 0, bytes, c->stream));
     mk_launch_keyswitch(k, nsplit, c->stream);
     THFHE_HIP(hipGetLastError());
-    THFHE_HIP(hipMemcpyAsync(out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }
@@ -414,70 +407,42 @@ int thfhe_ccs_ctx_create(const thfhe_params *p, const int32_t *bk, const int32_t
         return thfhe_fail(THFHE_E_UNSUPPORTED, "(parties+1) * l * 2^(Bgbit-1) exceeds the FP64 exactness bound of the stage-2 sums");
     if (p->n < 1 || p->n > 767) return thfhe_fail(THFHE_E_UNSUPPORTED, "need 1 <= n <= 767");
     if (p->ks_t < 1 || p->ks_basebit < 1 || p->ks_t * p->ks_basebit > 31) return thfhe_fail(THFHE_E_INVALID, "bad key-switch parameters");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return thfhe_fail(THFHE_E_NO_DEVICE, "no usable HIP device (this library has no CPU fallback)");
-    THFHE_HIP(hipSetDevice(device));
-    thfhe_ccs_ctx *c = new (std::nothrow) thfhe_ccs_ctx;
+    std::unique_ptr<thfhe_ccs_ctx> c(new (std::nothrow) thfhe_ccs_ctx);
     if (!c) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
+    THFHE_TRY(c->open(device, false));
     c->p = *p;
-    c->device = device;
     c->wide = p->parties > kCcsMaxParties || p->l > 8;   // the 16-party shape: ccs_blind_rotate_wide_kernel
     c->words = p->parties * p->n;
     c->w_pad = (c->words + 3) & ~3;
     c->row_words = 128 * ((p->n + 1 + 127) / 128);
-    int32_t *d_coeff = nullptr, *d_raw = nullptr;  // upload staging, freed on every path
-    auto fail = [&](int code) {
-        (void)hipFree(d_coeff);
-        (void)hipFree(d_raw);
-        thfhe_ccs_ctx_destroy(c);
-        return code;
-    };
-#define CK(expr)                                                      \
-    do {                                                              \
-        hipError_t e_ = (expr);                                       \
-        if (e_ != hipSuccess) return fail(thfhe_fail_hip(e_, #expr)); \
-    } while (0)
-    CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     std::vector<cplx> tw(576);
     make_twiddles_1024(tw.data(), tw.data() + 512);
-    CK(hipMalloc(&c->d_tw, tw.size() * sizeof(cplx)));
-    CK(hipMemcpyAsync(c->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
-    struct Tab { const int32_t *src; long npolys; cplx **dst; };
+    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
+    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
+    struct Tab { const int32_t *src; long npolys; DevBuf *dst; };
     const Tab tabs[3] = {{bk, (long)p->parties * p->n * 3 * p->l, &c->d_bk}, {pk, (long)p->parties * p->l, &c->d_pk}, {crs, (long)p->l, &c->d_crs}};
     for (const Tab &t : tabs) {
-        CK(hipMalloc(&d_coeff, (size_t)t.npolys * 1024 * sizeof(int32_t)));
-        CK(hipMemcpyAsync(d_coeff, t.src, (size_t)t.npolys * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        CK(hipMalloc(t.dst, (size_t)t.npolys * 1024 * sizeof(cplx)));
-        hipLaunchKernelGGL(ccs_key_transform_kernel, dim3((unsigned)((t.npolys + 3) / 4)), dim3(256), 0, c->stream, d_coeff, t.npolys, c->d_tw, *t.dst);
-        CK(hipGetLastError());
-        CK(hipStreamSynchronize(c->stream));
-        (void)hipFree(d_coeff);
-        d_coeff = nullptr;
+        DevBuf coeff;  // upload staging
+        THFHE_TRY(coeff.grow((size_t)t.npolys * 1024 * sizeof(int32_t)));
+        THFHE_HIP(hipMemcpyAsync(coeff.as<int32_t>(), t.src, (size_t)t.npolys * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        THFHE_TRY(t.dst->grow((size_t)t.npolys * 1024 * sizeof(cplx)));
+        hipLaunchKernelGGL(ccs_key_transform_kernel, dim3((unsigned)((t.npolys + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int32_t>(), t.npolys, c->d_tw.as<cplx>(), t.dst->as<cplx>());
+        THFHE_HIP(hipGetLastError());
+        THFHE_HIP(hipStreamSynchronize(c->stream));
     }
     const long rows = (long)p->parties * 1024 * p->ks_t * ((1 << p->ks_basebit) - 1);
-    CK(hipMalloc(&d_raw, (size_t)rows * (p->n + 1) * sizeof(int32_t)));
-    CK(hipMemcpyAsync(d_raw, ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    CK(hipMalloc(&c->d_ksk, (size_t)rows * c->row_words * sizeof(int32_t)));
-    hipLaunchKernelGGL(mk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, d_raw, rows, p->n, c->row_words, c->d_ksk);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_raw);
-#undef CK
-    *out = c;
+    DevBuf raw;  // upload staging
+    THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));
+    THFHE_HIP(hipMemcpyAsync(raw.as<int32_t>(), ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->d_ksk.grow((size_t)rows * c->row_words * sizeof(int32_t)));
+    hipLaunchKernelGGL(mk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, raw.as<int32_t>(), rows, p->n, c->row_words, c->d_ksk.as<int32_t>());
+    THFHE_HIP(hipGetLastError());
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    *out = c.release();
     return THFHE_OK;
 }
 
-void thfhe_ccs_ctx_destroy(thfhe_ccs_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void *q : {(void *)c->d_bk, (void *)c->d_pk, (void *)c->d_crs, (void *)c->d_tw, (void *)c->d_ksk, (void *)c->d_bara, (void *)c->d_barb, (void *)c->d_u,
-                    (void *)c->d_in[0], (void *)c->d_in[1], (void *)c->d_out, (void *)c->d_v})
-        (void)hipFree(q);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
+void thfhe_ccs_ctx_destroy(thfhe_ccs_ctx *c) { ctx_destroy(c); }
 
 int thfhe_ccs_gates(thfhe_ccs_ctx *c, int op, const int32_t *in0, const int32_t *in1, int32_t *out, size_t count) {
     if (!c || !in0 || !in1 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");

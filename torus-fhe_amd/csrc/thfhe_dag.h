@@ -11,6 +11,7 @@
 
 #include "../../include/thfhe_hip.h"
 #include "thfhe_common.h"
+#include "thfhe_devctx.h"
 
 namespace {
 using namespace thfhe;
@@ -127,20 +128,7 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
 
 // Device buffers of the executor (grow-only, owned by the engine's context and reused by every run on it).
 struct DagBuffers {
-    size_t cap_wires = 0, cap_tab = 0, cap_ops = 0, cap_pack = 0;   // bytes
-    int32_t *d_wires = nullptr, *d_tab = nullptr, *d_ops = nullptr, *d_pack = nullptr;
-    static hipError_t grow(int32_t *&p, size_t &cap, size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        (void)hipFree(p);
-        p = nullptr, cap = 0;
-        const hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    void release() {
-        for (int32_t **p : {&d_wires, &d_tab, &d_ops, &d_pack}) (void)hipFree(*p), *p = nullptr;
-        cap_wires = cap_tab = cap_ops = cap_pack = 0;
-    }
+    DevBuf wires, tab, ops, pack;
 };
 
 // Device-resident executor.  Level by level, each class of a level as slices of at most `slice_cap` gates over ALL instances: gather ->
@@ -163,12 +151,14 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
     int rc = ensure(slice ? slice : 1, stage_in, &stage_out);
     if (rc) return rc;
     const size_t rec = (size_t)words * sizeof(int32_t);
-    hipError_t e = DagBuffers::grow(B.d_wires, B.cap_wires, instances * n_wires * rec);
-    if (e == hipSuccess) e = DagBuffers::grow(B.d_tab, B.cap_tab, (plan.tab.size() + n_sel) * sizeof(int32_t));
-    if (e == hipSuccess) e = DagBuffers::grow(B.d_ops, B.cap_ops, (slice ? slice : 1) * sizeof(int32_t));
-    if (e == hipSuccess && h_sel) e = DagBuffers::grow(B.d_pack, B.cap_pack, instances * n_sel * rec);
-    if (e != hipSuccess) return thfhe_fail_hip(e, "gate-DAG executor: device tables");
-    int32_t *const d_wires = B.d_wires, *const d_tab = B.d_tab, *const d_sel = B.d_tab + plan.tab.size();
+    rc = B.wires.grow(instances * n_wires * rec);
+    if (!rc) rc = B.tab.grow((plan.tab.size() + n_sel) * sizeof(int32_t));
+    if (!rc) rc = B.ops.grow((slice ? slice : 1) * sizeof(int32_t));
+    if (!rc && h_sel) rc = B.pack.grow(instances * n_sel * rec);
+    if (rc) return rc;
+    int32_t *const d_wires = B.wires.as<int32_t>(), *const d_tab = B.tab.as<int32_t>(), *const d_sel = d_tab + plan.tab.size();
+    int32_t *const d_ops = B.ops.as<int32_t>(), *const d_pack = B.pack.as<int32_t>();
+    hipError_t e = hipSuccess;
     if (n_inputs) e = hipMemcpy2DAsync(d_wires, n_wires * rec, h_inputs, n_inputs * rec, n_inputs * rec, instances, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_tab, plan.tab.data(), plan.tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && n_sel) e = hipMemcpyAsync(d_sel, h_sel, n_sel * sizeof(int32_t), hipMemcpyHostToDevice, stream);
@@ -186,10 +176,10 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
         for (long first = 0; first < all && rc == THFHE_OK; first += (long)slice) {
             const long n = all - first < (long)slice ? all - first : (long)slice;
             const dim3 grid((unsigned)n, wb);
-            hipLaunchKernelGGL(dag_gather_kernel, grid, block, 0, stream, d_wires, t0, stage_in[0], first, n, cnt, n_wires, words, t_ops, B.d_ops);
+            hipLaunchKernelGGL(dag_gather_kernel, grid, block, 0, stream, d_wires, t0, stage_in[0], first, n, cnt, n_wires, words, t_ops, d_ops);
             hipLaunchKernelGGL(dag_gather_kernel, grid, block, 0, stream, d_wires, t1, stage_in[1], first, n, cnt, n_wires, words, nullptr, nullptr);
             if (cls != 0) hipLaunchKernelGGL(dag_gather_kernel, grid, block, 0, stream, d_wires, t2, stage_in[2], first, n, cnt, n_wires, words, nullptr, nullptr);
-            rc = run(cls, B.d_ops, (size_t)n);
+            rc = run(cls, d_ops, (size_t)n);
             if (!rc) hipLaunchKernelGGL(dag_scatter_kernel, grid, block, 0, stream, stage_out, t_out, d_wires, first, n, cnt, n_wires, words);
         }
     }
@@ -197,9 +187,9 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
         e = hipGetLastError();
         if (e == hipSuccess && h_sel && n_sel) {
             const long all = (long)(n_sel * instances);
-            hipLaunchKernelGGL(dag_gather_kernel, dim3((unsigned)all, wb), block, 0, stream, d_wires, d_sel, B.d_pack, 0L, all, (long)n_sel, n_wires, words, nullptr, nullptr);
+            hipLaunchKernelGGL(dag_gather_kernel, dim3((unsigned)all, wb), block, 0, stream, d_wires, d_sel, d_pack, 0L, all, (long)n_sel, n_wires, words, nullptr, nullptr);
             e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(h_out, B.d_pack, instances * n_sel * rec, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_pack, instances * n_sel * rec, hipMemcpyDeviceToHost, stream);
         } else if (e == hipSuccess && !h_sel) {
             e = hipMemcpy2DAsync(h_out, n_gates * rec, d_wires + n_inputs * (size_t)words, n_wires * rec, n_gates * rec, instances, hipMemcpyDeviceToHost, stream);
         }

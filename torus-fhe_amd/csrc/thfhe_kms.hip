@@ -20,12 +20,14 @@
 #include <deque>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include "../../include/thfhe_hip.h"
 #include "thfhe_common.h"
+#include "thfhe_devctx.h"
 #include "thfhe_lane.h"
 #include "thfhe_mk_shared.h"
 
@@ -117,48 +119,30 @@ __global__ __launch_bounds__(256) void kms_rlwe_split_kernel(const int64_t *__re
 }
 }  // namespace
 
-struct thfhe_kms_ctx {
+struct THFHE_INTERNAL thfhe_kms_ctx : DevCtx {
     thfhe_kms_params p;
-    int device = 0;
-    hipStream_t stream = nullptr;      // the stream every call enqueues on
-    hipStream_t own_stream = nullptr;  // created with the context; `stream` differs only after thfhe_kms_set_stream
-    cplx *d_tw = nullptr;
-    Rot2kPark park;              // two jobs per workgroup: partial spectra between row-part batches (thfhe_rot2k.h)
+    DevBuf d_tw;
+    DevBuf park;                 // two jobs per workgroup: partial spectra between row-part batches (thfhe_rot2k.h)
     long pair_threshold = 256;   // launches of more TLev / RLWE rotations than this (one per CU) run two jobs per workgroup
-    cplx *d_bk = nullptr;       // [party][j][row part][o][h][half][512]
-    int32_t *d_ksk = nullptr;
+    DevBuf d_bk;                 // [party][j][row part][o][h][half][512]
+    DevBuf d_ksk;
     int parts = 1, lo_bits = 1, row_words = 0;
     size_t party_stride = 0;    // complex elements per party in d_bk
-    void *d_buf[3] = {nullptr, nullptr, nullptr};
-    size_t cap[3] = {0, 0, 0};
+    DevBuf d_buf[3];
     // relinearisation keys as limb spectra: [party][d | f0 | f1][l_uni], then pk [P][l_uni], then crs [l_uni]   (thfhe_kms_set_relin_keys)
-    cplx *d_relin = nullptr;
-    int *d_flag = nullptr;
+    DevBuf d_relin;
+    DevBuf d_flag;
     enum { W_X, W_Y, W_BARA, W_ACCUM, W_LEV, W_LEVSPEC, W_SMALL, W_EF, W_R, W_V, W_W01, W_TERMS, W_FIRST, W_INDEX, W_U, W_OUT, W_ACC1, W_COUNT };
-    void *d_w[W_COUNT] = {};
-    size_t cap_w[W_COUNT] = {};
+    DevBuf d_w[W_COUNT];
     // device-resident copies of the relinearisation index tables (terms / first of thfhe_pm_mac, decompose index lists, assemble positions):
     // they depend only on (table kind, party, gates per call, route), so a steady stream of equally sized calls uploads them once
     struct DevTab {
-        int32_t *d = nullptr;
+        DevBuf d;
         size_t words = 0;
     };
     std::map<uint64_t, DevTab> tabs;
     size_t tab_bytes = 0;
-    std::mutex mu;
 };
-
-namespace {
-int kms_ensure(thfhe_kms_ctx *c, int slot, size_t bytes) {
-    if (bytes <= c->cap[slot]) return THFHE_OK;
-    (void)hipFree(c->d_buf[slot]);
-    c->d_buf[slot] = nullptr;
-    c->cap[slot] = 0;
-    THFHE_HIP(hipMalloc(&c->d_buf[slot], bytes));
-    c->cap[slot] = bytes;
-    return THFHE_OK;
-}
-}  // namespace
 
 extern "C" {
 
@@ -171,14 +155,10 @@ int thfhe_kms_ctx_create(const thfhe_kms_params *p, const int64_t *gsw, const in
         return thfhe_fail(THFHE_E_UNSUPPORTED, "gsw gadget: need 1 <= l <= 8, 2 <= Bgbit <= 14, l * Bgbit <= 64");
     if (p->l_lev < 1 || p->l_lev > 8 || p->bg_lev < 1 || p->l_lev * p->bg_lev > 64) return thfhe_fail(THFHE_E_UNSUPPORTED, "bad lev gadget");
     if (p->ks_t < 1 || p->ks_basebit < 1 || p->ks_t * p->ks_basebit > 31) return thfhe_fail(THFHE_E_INVALID, "bad key-switch parameters");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return thfhe_fail(THFHE_E_NO_DEVICE, "no usable HIP device (this library has no CPU fallback)");
-    THFHE_HIP(hipSetDevice(device));
-    thfhe_kms_ctx *c = new (std::nothrow) thfhe_kms_ctx;
+    std::unique_ptr<thfhe_kms_ctx> c(new (std::nothrow) thfhe_kms_ctx);
     if (!c) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
+    THFHE_TRY(c->open(device, false));
     c->p = *p;
-    c->device = device;
     // exactness: RP * N * 2^(part width - 1) * 2^15 must stay below 2^37 (N = 2048 bound of DESIGN.md section 4.3).  Digits are cut in two
     // balanced parts when they are wider than 10 bit OR when the whole-digit sum would leave the bound (many rows: the 16-party set's
     // l = 5, Bgbit 9 gives 2^37.3)
@@ -189,37 +169,21 @@ int thfhe_kms_ctx_create(const thfhe_kms_params *p, const int64_t *gsw, const in
     c->row_words = 128 * ((p->n + 1 + 127) / 128);
     const int RP = 2 * p->l_gsw * c->parts;
     const int part_bits = c->parts == 2 ? c->lo_bits : p->bg_gsw;
-    if (sum_bound(c->parts, part_bits) > 137438953472.0 /* 2^37 */) {
-        delete c;
+    if (sum_bound(c->parts, part_bits) > 137438953472.0 /* 2^37 */)
         return thfhe_fail(THFHE_E_UNSUPPORTED, "gsw gadget outside the FP64 exactness bound of the N = 2048 transform");
-    }
-    int64_t *d_coeff = nullptr;
-    int32_t *d_raw = nullptr;
-    auto fail = [&](int code) {
-        (void)hipFree(d_coeff);
-        (void)hipFree(d_raw);
-        thfhe_kms_ctx_destroy(c);
-        return code;
-    };
-#define CK(expr)                                                      \
-    do {                                                              \
-        hipError_t e_ = (expr);                                       \
-        if (e_ != hipSuccess) return fail(thfhe_fail_hip(e_, #expr)); \
-    } while (0)
-    CK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    c->stream = c->own_stream;
+    DevBuf coeff, raw;  // upload staging
     std::vector<cplx> tw(1216 + 64), unused(512);   // T1 (twist 1), T1 (twist 5), T2; [1216..): pass-1 ratio of the table-free transforms
     make_lane_ratio_2048(tw.data() + 1216);
     make_twiddles_2048(tw.data(), tw.data() + 512);
     make_twiddles_1024(unused.data(), tw.data() + 1024);
-    CK(hipMalloc(&c->d_tw, tw.size() * sizeof(cplx)));
-    CK(hipMemcpyAsync(c->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
+    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
     // key table: per party and key bit the 2 l rows x 2 columns of the TGSW sample; with two-part digits every row is followed by its copy
     // shifted left by lo_bits (wrapping): d (*) K = d_lo (*) K + d_hi (*) (K << lo_bits)
     const size_t polys_per_party = (size_t)p->n * RP * 2;
     c->party_stride = polys_per_party * 4 * 1024;
-    CK(hipMalloc(&c->d_bk, (size_t)p->parties * c->party_stride * sizeof(cplx)));
-    CK(hipMalloc(&d_coeff, polys_per_party * N * sizeof(int64_t)));
+    THFHE_TRY(c->d_bk.grow((size_t)p->parties * c->party_stride * sizeof(cplx)));
+    THFHE_TRY(coeff.grow(polys_per_party * N * sizeof(int64_t)));
     std::vector<int64_t> host(polys_per_party * N);
     for (int q = 0; q < p->parties; q++) {
         for (int j = 0; j < p->n; j++)
@@ -231,61 +195,43 @@ int thfhe_kms_ctx_create(const thfhe_kms_params *p, const int64_t *gsw, const in
                         const int sh = part * c->lo_bits;
                         for (int t = 0; t < N; t++) dst[t] = (int64_t)((uint64_t)src[t] << sh);
                     }
-        CK(hipMemcpyAsync(d_coeff, host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(kms_key_transform_kernel, dim3((unsigned)((polys_per_party * 4 + 3) / 4)), dim3(256), 0, c->stream, d_coeff, (long)polys_per_party,
-                           c->d_tw, c->d_bk + (size_t)q * c->party_stride);
-        CK(hipGetLastError());
-        CK(hipStreamSynchronize(c->stream));   // `host` is reused for the next party
+        THFHE_HIP(hipMemcpyAsync(coeff.as<int64_t>(), host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(kms_key_transform_kernel, dim3((unsigned)((polys_per_party * 4 + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int64_t>(), (long)polys_per_party,
+                           c->d_tw.as<cplx>(), c->d_bk.as<cplx>() + (size_t)q * c->party_stride);
+        THFHE_HIP(hipGetLastError());
+        THFHE_HIP(hipStreamSynchronize(c->stream));   // `host` is reused for the next party
     }
     const long rows = (long)p->parties * N * p->ks_t * ((1 << p->ks_basebit) - 1);
-    CK(hipMalloc(&d_raw, (size_t)rows * (p->n + 1) * sizeof(int32_t)));
-    CK(hipMemcpyAsync(d_raw, ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    CK(hipMalloc(&c->d_ksk, (size_t)rows * c->row_words * sizeof(int32_t)));
-    hipLaunchKernelGGL(mk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, d_raw, rows, p->n, c->row_words, c->d_ksk);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_coeff);
-    (void)hipFree(d_raw);
-#undef CK
-    *out = c;
+    THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));
+    THFHE_HIP(hipMemcpyAsync(raw.as<int32_t>(), ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->d_ksk.grow((size_t)rows * c->row_words * sizeof(int32_t)));
+    hipLaunchKernelGGL(mk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, raw.as<int32_t>(), rows, p->n, c->row_words, c->d_ksk.as<int32_t>());
+    THFHE_HIP(hipGetLastError());
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    *out = c.release();
     return THFHE_OK;
 }
 
-void thfhe_kms_ctx_destroy(thfhe_kms_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    (void)hipFree(c->d_tw);
-    (void)hipFree(c->park.buf);
-    (void)hipFree(c->d_bk);
-    (void)hipFree(c->d_ksk);
-    for (auto &q : c->d_buf) (void)hipFree(q);
-    for (auto &q : c->d_w) (void)hipFree(q);
-    for (auto &kv : c->tabs) (void)hipFree(kv.second.d);
-    (void)hipFree(c->d_relin);
-    (void)hipFree(c->d_flag);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
-}
+void thfhe_kms_ctx_destroy(thfhe_kms_ctx *c) { ctx_destroy(c); }
 
 int thfhe_kms_tlev_rotate(thfhe_kms_ctx *c, int party, const int32_t *bara, int64_t *lev, size_t count) {
     if (!c || !bara || !lev) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (party < 0 || party >= c->p.parties) return thfhe_fail(THFHE_E_INVALID, "party out of range");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     const size_t jobs = count * c->p.l_lev;
-    int rc = kms_ensure(c, 0, count * c->p.n * sizeof(int32_t));
-    if (!rc) rc = kms_ensure(c, 1, jobs * 4096 * sizeof(int64_t));
+    int rc = c->d_buf[0].grow(count * c->p.n * sizeof(int32_t));
+    if (!rc) rc = c->d_buf[1].grow(jobs * 4096 * sizeof(int64_t));
     if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_buf[0], bara, count * c->p.n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    KmsBRArgs a{c->d_bk + (size_t)party * c->party_stride, c->d_tw, (const int32_t *)c->d_buf[0], (int64_t *)c->d_buf[1], nullptr, (long)jobs,
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[0].as<void>(), bara, count * c->p.n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    KmsBRArgs a{c->d_bk.as<cplx>() + (size_t)party * c->party_stride, c->d_tw.as<cplx>(), c->d_buf[0].as<int32_t>(), c->d_buf[1].as<int64_t>(), nullptr, (long)jobs,
                 c->p.n, c->p.l_gsw, c->p.bg_gsw, c->parts, c->lo_bits, c->p.l_lev, c->p.bg_lev, c->p.n};
     {
         int rc2 = rot2k_launch(a, c->stream, c->pair_threshold, c->park);
         if (rc2) return rc2;
     }
-    THFHE_HIP(hipMemcpyAsync(lev, c->d_buf[1], jobs * 4096 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(lev, c->d_buf[1].as<void>(), jobs * 4096 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }
@@ -294,20 +240,20 @@ int thfhe_kms_rlwe_rotate(thfhe_kms_ctx *c, int party, const int32_t *bara, int6
     if (!c || !bara || !acc) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (party < 0 || party >= c->p.parties) return thfhe_fail(THFHE_E_INVALID, "party out of range");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
-    int rc = kms_ensure(c, 0, count * c->p.n * sizeof(int32_t));
-    if (!rc) rc = kms_ensure(c, 1, count * 4096 * sizeof(int64_t));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    int rc = c->d_buf[0].grow(count * c->p.n * sizeof(int32_t));
+    if (!rc) rc = c->d_buf[1].grow(count * 4096 * sizeof(int64_t));
     if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_buf[0], bara, count * c->p.n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_buf[1], acc, count * 4096 * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    KmsBRArgs a{c->d_bk + (size_t)party * c->party_stride, c->d_tw, (const int32_t *)c->d_buf[0], (int64_t *)c->d_buf[1], (const int64_t *)c->d_buf[1],
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[0].as<void>(), bara, count * c->p.n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[1].as<void>(), acc, count * 4096 * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    KmsBRArgs a{c->d_bk.as<cplx>() + (size_t)party * c->party_stride, c->d_tw.as<cplx>(), c->d_buf[0].as<int32_t>(), c->d_buf[1].as<int64_t>(), c->d_buf[1].as<int64_t>(),
                 (long)count, c->p.n, c->p.l_gsw, c->p.bg_gsw, c->parts, c->lo_bits, 1, c->p.bg_lev, c->p.n};   // in place: a workgroup reads its sample before it writes it
     {
         int rc2 = rot2k_launch(a, c->stream, c->pair_threshold, c->park);
         if (rc2) return rc2;
     }
-    THFHE_HIP(hipMemcpyAsync(acc, c->d_buf[1], count * 4096 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(acc, c->d_buf[1].as<void>(), count * 4096 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }
@@ -315,20 +261,20 @@ int thfhe_kms_rlwe_rotate(thfhe_kms_ctx *c, int party, const int32_t *bara, int6
 int thfhe_kms_keyswitch(thfhe_kms_ctx *c, const int32_t *u, int32_t *out, size_t count) {
     if (!c || !u || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     const int P = c->p.parties, N = c->p.N, n = c->p.n;
     const size_t in_words = count * ((size_t)P * N + 1), out_words = count * ((size_t)P * n + 1);
-    int rc = kms_ensure(c, 1, in_words * sizeof(int32_t));
-    if (!rc) rc = kms_ensure(c, 2, out_words * sizeof(int32_t));
+    int rc = c->d_buf[1].grow(in_words * sizeof(int32_t));
+    if (!rc) rc = c->d_buf[2].grow(out_words * sizeof(int32_t));
     if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_buf[1], u, in_words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemsetAsync(c->d_buf[2], 0, out_words * sizeof(int32_t), c->stream));
-    MKKSArgs k{c->d_ksk, (const int32_t *)c->d_buf[1], (int32_t *)c->d_buf[2], (long)count, n, c->p.ks_t, c->p.ks_basebit, P, c->row_words, N, P * N + 1, N};
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[1].as<void>(), u, in_words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemsetAsync(c->d_buf[2].as<void>(), 0, out_words * sizeof(int32_t), c->stream));
+    MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_buf[1].as<int32_t>(), c->d_buf[2].as<int32_t>(), (long)count, n, c->p.ks_t, c->p.ks_basebit, P, c->row_words, N, P * N + 1, N};
     const int nsplit = count <= 64 ? 8 : 2;
     mk_launch_keyswitch(k, nsplit, c->stream);
     THFHE_HIP(hipGetLastError());
-    THFHE_HIP(hipMemcpyAsync(out, c->d_buf[2], out_words * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(out, c->d_buf[2].as<void>(), out_words * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }
@@ -336,15 +282,6 @@ int thfhe_kms_keyswitch(thfhe_kms_ctx *c, const int32_t *u, int32_t *out, size_t
 }  // extern "C"
 
 namespace {
-int kms_w(thfhe_kms_ctx *c, int slot, size_t bytes) {
-    if (bytes <= c->cap_w[slot]) return THFHE_OK;
-    (void)hipFree(c->d_w[slot]);
-    c->d_w[slot] = nullptr;
-    c->cap_w[slot] = 0;
-    THFHE_HIP(hipMalloc(&c->d_w[slot], bytes));
-    c->cap_w[slot] = bytes;
-    return THFHE_OK;
-}
 // host-built tables of one call stay alive until the stream has been synchronised (asynchronous copies read them)
 struct KmsTables {
     std::deque<std::vector<int32_t>> keep;   // a deque: references to earlier tables stay valid when one is added
@@ -365,18 +302,17 @@ int kms_tab(thfhe_kms_ctx *c, KmsTables &tabs, uint64_t key, const std::function
         build(host);
         if (c->tab_bytes + host.size() * 4 > (size_t)256 << 20) {
             THFHE_HIP(hipStreamSynchronize(c->stream));
-            for (auto &kv : c->tabs) (void)hipFree(kv.second.d);
             c->tabs.clear();
             c->tab_bytes = 0;
         }
         thfhe_kms_ctx::DevTab t;
         t.words = host.size();
-        THFHE_HIP(hipMalloc(&t.d, (t.words ? t.words : 1) * 4));
-        if (t.words) THFHE_HIP(hipMemcpyAsync(t.d, host.data(), t.words * 4, hipMemcpyHostToDevice, c->stream));
+        THFHE_TRY(t.d.grow((t.words ? t.words : 1) * 4));
+        if (t.words) THFHE_HIP(hipMemcpyAsync(t.d.as<int32_t>(), host.data(), t.words * 4, hipMemcpyHostToDevice, c->stream));
         c->tab_bytes += t.words * 4;
-        it = c->tabs.emplace(key, t).first;
+        it = c->tabs.emplace(key, std::move(t)).first;
     }
-    *d_out = it->second.d;
+    *d_out = it->second.d.as<int32_t>();
     if (words_out) *words_out = it->second.words;
     return THFHE_OK;
 }
@@ -396,15 +332,15 @@ int kms_mac(thfhe_kms_ctx *c, KmsTables &tabs, uint64_t key, const int32_t *d_sm
     }, &d_tab, &words);
     if (rc) return rc;
     const size_t n_terms = (words - (n_out + 1)) / 4;
-    PMArgs a{d_small, d_spec, d_tab, d_tab + 4 * n_terms, d_addend, d_out, c->d_tw, (long)n_out, c->d_flag};
+    PMArgs a{d_small, d_spec, d_tab, d_tab + 4 * n_terms, d_addend, d_out, c->d_tw.as<cplx>(), (long)n_out, c->d_flag.as<int>()};
     hipLaunchKernelGGL((pm_mac_kernel<2048, 64>), dim3((unsigned)((n_out + 3) / 4)), dim3(256), 0, c->stream, a);
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
 int kms_decompose(thfhe_kms_ctx *c, const int64_t *d_polys, const int32_t *d_index, size_t n, int l, int bg) {
-    int rc = kms_w(c, thfhe_kms_ctx::W_SMALL, n * l * 2048 * sizeof(int32_t));
+    int rc = c->d_w[thfhe_kms_ctx::W_SMALL].grow(n * l * 2048 * sizeof(int32_t));
     if (rc) return rc;
-    hipLaunchKernelGGL(kms_decompose_kernel, dim3((unsigned)n, 8), dim3(256), 0, c->stream, d_polys, d_index, (long)n, l, bg, (int32_t *)c->d_w[thfhe_kms_ctx::W_SMALL]);
+    hipLaunchKernelGGL(kms_decompose_kernel, dim3((unsigned)n, 8), dim3(256), 0, c->stream, d_polys, d_index, (long)n, l, bg, c->d_w[thfhe_kms_ctx::W_SMALL].as<int32_t>());
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
@@ -415,26 +351,26 @@ int kms_relin_core(thfhe_kms_ctx *c, KmsTables &tabs, int party, size_t G, const
     typedef thfhe_kms_ctx K;
     const int P = c->p.parties, lu = c->p.l_uni, ns = (int)src.size();
     const size_t N = 2048;
-    const int64_t *d_e = (const int64_t *)c->d_w[K::W_EF], *d_f = d_e + G * ns * N;
+    const int64_t *d_e = c->d_w[K::W_EF].as<int64_t>(), *d_f = d_e + G * ns * N;
     auto T_D = [&](int l) { return (party * 3 + 0) * lu + l; };
     auto T_F = [&](int w, int l) { return (party * 3 + 1 + w) * lu + l; };
     auto T_PK = [&](int i, int l) { return P * 3 * lu + i * lu + l; };
     auto T_A = [&](int l) { return P * 3 * lu + P * lu + l; };
     int rc = kms_decompose(c, d_e, nullptr, G * ns, lu, c->p.bg_uni);
-    if (!rc) rc = kms_w(c, K::W_R, G * ns * N * 8);
-    if (!rc) rc = kms_w(c, K::W_V, G * N * 8);
-    if (!rc) rc = kms_w(c, K::W_W01, G * 2 * N * 8);
+    if (!rc) rc = c->d_w[K::W_R].grow(G * ns * N * 8);
+    if (!rc) rc = c->d_w[K::W_V].grow(G * N * 8);
+    if (!rc) rc = c->d_w[K::W_W01].grow(G * 2 * N * 8);
     if (rc) return rc;
-    const int32_t *d_small = (const int32_t *)c->d_w[K::W_SMALL];
-    rc = kms_mac(c, tabs, kms_key(1, party, G, route), d_small, c->d_relin, [&](std::vector<int32_t> &t) {
+    const int32_t *d_small = c->d_w[K::W_SMALL].as<int32_t>();
+    rc = kms_mac(c, tabs, kms_key(1, party, G, route), d_small, c->d_relin.as<cplx>(), [&](std::vector<int32_t> &t) {
         for (size_t g = 0; g < G; g++)
             for (int q = 0; q < ns; q++)
                 for (int l = 0; l < lu; l++) {
                     const int32_t j = (int32_t)(g * ns + q);
                     t.insert(t.end(), {j, j * lu + l, T_D(l), -1});          // (f - u)_q = f_q - sum_l dec(e_q)[l] (*) d[l]
                 }
-    }, G * ns, d_f, c->d_w[K::W_R]);
-    if (!rc) rc = kms_mac(c, tabs, kms_key(2, party, G, route), d_small, c->d_relin, [&](std::vector<int32_t> &t) {
+    }, G * ns, d_f, c->d_w[K::W_R].as<void>());
+    if (!rc) rc = kms_mac(c, tabs, kms_key(2, party, G, route), d_small, c->d_relin.as<cplx>(), [&](std::vector<int32_t> &t) {
         for (size_t g = 0; g < G; g++)
             for (int q = 0; q < ns; q++)
                 for (int l = 0; l < lu; l++) {
@@ -442,14 +378,14 @@ int kms_relin_core(thfhe_kms_ctx *c, KmsTables &tabs, int party, size_t G, const
                     if (src[q] < P) t.insert(t.end(), {(int32_t)g, sm, T_PK(src[q], l), 1});   // v = sum_i <dec(e_i), pk_i> - <dec(e_b), crs>
                     else t.insert(t.end(), {(int32_t)g, sm, T_A(l), -1});
                 }
-    }, G, nullptr, c->d_w[K::W_V]);
-    if (!rc) rc = kms_decompose(c, (const int64_t *)c->d_w[K::W_V], nullptr, G, lu, c->p.bg_uni);   // stream order: after the two products read W_SMALL
+    }, G, nullptr, c->d_w[K::W_V].as<void>());
+    if (!rc) rc = kms_decompose(c, c->d_w[K::W_V].as<int64_t>(), nullptr, G, lu, c->p.bg_uni);   // stream order: after the two products read W_SMALL
     if (rc) return rc;
-    rc = kms_mac(c, tabs, kms_key(3, party, G, 0), (const int32_t *)c->d_w[K::W_SMALL], c->d_relin, [&](std::vector<int32_t> &t) {
+    rc = kms_mac(c, tabs, kms_key(3, party, G, 0), c->d_w[K::W_SMALL].as<int32_t>(), c->d_relin.as<cplx>(), [&](std::vector<int32_t> &t) {
         for (size_t g = 0; g < G; g++)
             for (int w = 0; w < 2; w++)
                 for (int l = 0; l < lu; l++) t.insert(t.end(), {(int32_t)(g * 2 + w), (int32_t)(g * lu + l), T_F(w, l), 1});   // w0 = <dec(v), f0>, w1 = <dec(v), f1>
-    }, G * 2, nullptr, c->d_w[K::W_W01]);
+    }, G * 2, nullptr, c->d_w[K::W_W01].as<void>());
     if (rc) return rc;
     const int32_t *d_pos = nullptr;
     rc = kms_tab(c, tabs, kms_key(4, party, 0, route), [&](std::vector<int32_t> &pos) {
@@ -457,8 +393,8 @@ int kms_relin_core(thfhe_kms_ctx *c, KmsTables &tabs, int party, size_t G, const
         for (int q = 0; q < ns; q++) pos[src[q]] = q;
     }, &d_pos, nullptr);
     if (rc) return rc;
-    hipLaunchKernelGGL(kms_assemble_kernel, dim3((unsigned)G, (unsigned)(P + 1)), dim3(256), 0, c->stream, (const int64_t *)c->d_w[K::W_R],
-                       (const int64_t *)c->d_w[K::W_W01], d_pos, ns, party, P, d_accum);
+    hipLaunchKernelGGL(kms_assemble_kernel, dim3((unsigned)G, (unsigned)(P + 1)), dim3(256), 0, c->stream, c->d_w[K::W_R].as<int64_t>(),
+                       c->d_w[K::W_W01].as<int64_t>(), d_pos, ns, party, P, d_accum);
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
@@ -477,30 +413,30 @@ int kms_lev_rlwe_mul_dev(thfhe_kms_ctx *c, KmsTables &tabs, int party, size_t G,
             for (int q = 0; q < ns; q++) index.push_back((int32_t)(g * (P + 1) + src[q]));
     }, &d_index, nullptr);
     if (!rc) rc = kms_decompose(c, d_accum, d_index, G * ns, lv, c->p.bg_lev);
-    if (!rc) rc = kms_w(c, K::W_LEVSPEC, G * lv * 2 * 4 * 1024 * sizeof(cplx));
-    if (!rc) rc = kms_w(c, K::W_EF, 2 * G * ns * N * 8);
+    if (!rc) rc = c->d_w[K::W_LEVSPEC].grow(G * lv * 2 * 4 * 1024 * sizeof(cplx));
+    if (!rc) rc = c->d_w[K::W_EF].grow(2 * G * ns * N * 8);
     if (rc) return rc;
     hipLaunchKernelGGL((pm_torus_transform_kernel<2048, 64>), dim3((unsigned)((G * lv * 2 * 4 + 3) / 4)), dim3(256), 0, c->stream, (const void *)d_lev,
-                       (long)(G * lv * 2), c->d_tw, (cplx *)c->d_w[K::W_LEVSPEC]);
+                       (long)(G * lv * 2), c->d_tw.as<cplx>(), c->d_w[K::W_LEVSPEC].as<cplx>());
     THFHE_HIP(hipGetLastError());
-    rc = kms_mac(c, tabs, kms_key(6, party, G, 0), (const int32_t *)c->d_w[K::W_SMALL], (const cplx *)c->d_w[K::W_LEVSPEC], [&](std::vector<int32_t> &t1) {
+    rc = kms_mac(c, tabs, kms_key(6, party, G, 0), c->d_w[K::W_SMALL].as<int32_t>(), c->d_w[K::W_LEVSPEC].as<cplx>(), [&](std::vector<int32_t> &t1) {
         for (int w = 0; w < 2; w++)   // e block (w = 0: masks of the TLev samples), then f block (w = 1: bodies)
             for (size_t g = 0; g < G; g++)
                 for (int q = 0; q < ns; q++)
                     for (int s = 0; s < lv; s++)
                         t1.insert(t1.end(), {(int32_t)((w * G + g) * ns + q), (int32_t)((g * ns + q) * lv + s), (int32_t)((g * lv + s) * 2 + w), 1});
-    }, 2 * G * ns, nullptr, c->d_w[K::W_EF]);
+    }, 2 * G * ns, nullptr, c->d_w[K::W_EF].as<void>());
     if (rc) return rc;
     return kms_relin_core(c, tabs, party, G, src, d_accum, 0);
 }
 int kms_launch_rotation(thfhe_kms_ctx *c, int party, const int32_t *d_bara, int64_t *d_out, const int64_t *d_in, size_t gates, int l_lev) {
-    KmsBRArgs a{c->d_bk + (size_t)party * c->party_stride, c->d_tw, d_bara, d_out, d_in, (long)(gates * l_lev),
+    KmsBRArgs a{c->d_bk.as<cplx>() + (size_t)party * c->party_stride, c->d_tw.as<cplx>(), d_bara, d_out, d_in, (long)(gates * l_lev),
                 c->p.n, c->p.l_gsw, c->p.bg_gsw, c->parts, c->lo_bits, l_lev, c->p.bg_lev, c->p.n};
     return rot2k_launch(a, c->stream, c->pair_threshold, c->park);
 }
 int kms_finish(thfhe_kms_ctx *c) {
     int flag = 0;
-    THFHE_HIP(hipMemcpyAsync(&flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(&flag, c->d_flag.as<int>(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     if (flag) return thfhe_fail(THFHE_E_UNSUPPORTED, "a gadget digit left [-4096, 4096] (outside the FP64 exactness bound of the relinearisation products)");
     return THFHE_OK;
@@ -509,56 +445,56 @@ int kms_finish(thfhe_kms_ctx *c) {
 int kms_bootstrap_body(thfhe_kms_ctx *c, KmsTables &tabs, int32_t cb, int32_t cx, int32_t cy, int64_t mu, const int32_t *x, const int32_t *y, int32_t *u_out,
                        int32_t *out, size_t G, int fast_boot) {
     typedef thfhe_kms_ctx K;
-    if (!c->d_relin) return thfhe_fail(THFHE_E_INVALID, "thfhe_kms_set_relin_keys has not been called on this context");
+    if (!c->d_relin.bytes()) return thfhe_fail(THFHE_E_INVALID, "thfhe_kms_set_relin_keys has not been called on this context");
     const int P = c->p.parties, n = c->p.n, lv = c->p.l_lev;
     const size_t N = 2048, words = (size_t)P * n + 1, uw = (size_t)P * N + 1;
     THFHE_HIP(hipSetDevice(c->device));
-    int rc = kms_w(c, K::W_X, G * words * 4);
-    if (!rc && y) rc = kms_w(c, K::W_Y, G * words * 4);
-    if (!rc) rc = kms_w(c, K::W_BARA, (size_t)P * G * n * 4);
-    if (!rc) rc = kms_w(c, K::W_ACCUM, G * (P + 1) * N * 8);
-    if (!rc) rc = kms_w(c, K::W_LEV, G * lv * 2 * N * 8);
-    if (!rc) rc = kms_w(c, K::W_U, G * uw * 4);
-    if (!rc) rc = kms_w(c, K::W_OUT, G * words * 4);
+    int rc = c->d_w[K::W_X].grow(G * words * 4);
+    if (!rc && y) rc = c->d_w[K::W_Y].grow(G * words * 4);
+    if (!rc) rc = c->d_w[K::W_BARA].grow((size_t)P * G * n * 4);
+    if (!rc) rc = c->d_w[K::W_ACCUM].grow(G * (P + 1) * N * 8);
+    if (!rc) rc = c->d_w[K::W_LEV].grow(G * lv * 2 * N * 8);
+    if (!rc) rc = c->d_w[K::W_U].grow(G * uw * 4);
+    if (!rc) rc = c->d_w[K::W_OUT].grow(G * words * 4);
     if (rc) return rc;
-    THFHE_HIP(hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_w[K::W_X], x, G * words * 4, hipMemcpyHostToDevice, c->stream));
-    if (y) THFHE_HIP(hipMemcpyAsync(c->d_w[K::W_Y], y, G * words * 4, hipMemcpyHostToDevice, c->stream));
-    int64_t *d_accum = (int64_t *)c->d_w[K::W_ACCUM];
-    const int32_t *d_bara = (const int32_t *)c->d_w[K::W_BARA];
-    hipLaunchKernelGGL(kms_prologue_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, (const int32_t *)c->d_w[K::W_X], y ? (const int32_t *)c->d_w[K::W_Y] : nullptr,
-                       cb, cx, cy, n, P, (long)G, mu, (int32_t *)c->d_w[K::W_BARA], d_accum);
+    THFHE_HIP(hipMemsetAsync(c->d_flag.as<int>(), 0, sizeof(int), c->stream));
+    THFHE_HIP(hipMemcpyAsync(c->d_w[K::W_X].as<void>(), x, G * words * 4, hipMemcpyHostToDevice, c->stream));
+    if (y) THFHE_HIP(hipMemcpyAsync(c->d_w[K::W_Y].as<void>(), y, G * words * 4, hipMemcpyHostToDevice, c->stream));
+    int64_t *d_accum = c->d_w[K::W_ACCUM].as<int64_t>();
+    const int32_t *d_bara = c->d_w[K::W_BARA].as<int32_t>();
+    hipLaunchKernelGGL(kms_prologue_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, c->d_w[K::W_X].as<int32_t>(), y ? c->d_w[K::W_Y].as<int32_t>() : nullptr,
+                       cb, cx, cy, n, P, (long)G, mu, c->d_w[K::W_BARA].as<int32_t>(), d_accum);
     THFHE_HIP(hipGetLastError());
     int first = 0;
     if (fast_boot) {   // mk_blind_rotate_new_v2 (J/new_mk_internals.jl:255-269)
-        rc = kms_w(c, K::W_ACC1, G * 2 * N * 8);
-        if (!rc) rc = kms_w(c, K::W_EF, 2 * G * N * 8);
+        rc = c->d_w[K::W_ACC1].grow(G * 2 * N * 8);
+        if (!rc) rc = c->d_w[K::W_EF].grow(2 * G * N * 8);
         if (rc) return rc;
-        hipLaunchKernelGGL(kms_rlwe_init_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, (const int64_t *)d_accum, P, (int64_t *)c->d_w[K::W_ACC1]);
-        rc = kms_launch_rotation(c, 0, d_bara, (int64_t *)c->d_w[K::W_ACC1], (const int64_t *)c->d_w[K::W_ACC1], G, 1);
+        hipLaunchKernelGGL(kms_rlwe_init_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, (const int64_t *)d_accum, P, c->d_w[K::W_ACC1].as<int64_t>());
+        rc = kms_launch_rotation(c, 0, d_bara, c->d_w[K::W_ACC1].as<int64_t>(), c->d_w[K::W_ACC1].as<int64_t>(), G, 1);
         if (rc) return rc;
-        hipLaunchKernelGGL(kms_rlwe_split_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, (const int64_t *)c->d_w[K::W_ACC1], (long)G, (int64_t *)c->d_w[K::W_EF]);
+        hipLaunchKernelGGL(kms_rlwe_split_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, c->d_w[K::W_ACC1].as<int64_t>(), (long)G, c->d_w[K::W_EF].as<int64_t>());
         THFHE_HIP(hipGetLastError());
         rc = kms_relin_core(c, tabs, 0, G, std::vector<int>{P}, d_accum, 1);
         if (rc) return rc;
         first = 1;
     }
     for (int party = first; party < P; party++) {
-        rc = kms_launch_rotation(c, party, d_bara + (size_t)party * G * n, (int64_t *)c->d_w[K::W_LEV], nullptr, G, lv);
-        if (!rc) rc = kms_lev_rlwe_mul_dev(c, tabs, party, G, d_accum, (const int64_t *)c->d_w[K::W_LEV]);
+        rc = kms_launch_rotation(c, party, d_bara + (size_t)party * G * n, c->d_w[K::W_LEV].as<int64_t>(), nullptr, G, lv);
+        if (!rc) rc = kms_lev_rlwe_mul_dev(c, tabs, party, G, d_accum, c->d_w[K::W_LEV].as<int64_t>());
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(kms_extract_kernel, dim3((unsigned)G, (unsigned)(P + 1)), dim3(256), 0, c->stream, (const int64_t *)d_accum, P, (int32_t *)c->d_w[K::W_U]);
+    hipLaunchKernelGGL(kms_extract_kernel, dim3((unsigned)G, (unsigned)(P + 1)), dim3(256), 0, c->stream, (const int64_t *)d_accum, P, c->d_w[K::W_U].as<int32_t>());
     THFHE_HIP(hipGetLastError());
-    if (u_out) THFHE_HIP(hipMemcpyAsync(u_out, c->d_w[K::W_U], G * uw * 4, hipMemcpyDeviceToHost, c->stream));
+    if (u_out) THFHE_HIP(hipMemcpyAsync(u_out, c->d_w[K::W_U].as<void>(), G * uw * 4, hipMemcpyDeviceToHost, c->stream));
     if (out) {
-        THFHE_HIP(hipMemsetAsync(c->d_w[K::W_OUT], 0, G * words * 4, c->stream));
-        MKKSArgs k{c->d_ksk, (const int32_t *)c->d_w[K::W_U], (int32_t *)c->d_w[K::W_OUT], (long)G, n, c->p.ks_t, c->p.ks_basebit, P, c->row_words, (int)N,
+        THFHE_HIP(hipMemsetAsync(c->d_w[K::W_OUT].as<void>(), 0, G * words * 4, c->stream));
+        MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_w[K::W_U].as<int32_t>(), c->d_w[K::W_OUT].as<int32_t>(), (long)G, n, c->p.ks_t, c->p.ks_basebit, P, c->row_words, (int)N,
                    (int)uw, (int)N};
         const int nsplit = G <= 64 ? 8 : 2;
         mk_launch_keyswitch(k, nsplit, c->stream);
         THFHE_HIP(hipGetLastError());
-        THFHE_HIP(hipMemcpyAsync(out, c->d_w[K::W_OUT], G * words * 4, hipMemcpyDeviceToHost, c->stream));
+        THFHE_HIP(hipMemcpyAsync(out, c->d_w[K::W_OUT].as<void>(), G * words * 4, hipMemcpyDeviceToHost, c->stream));
     }
     return kms_finish(c);
 }
@@ -574,18 +510,18 @@ int kms_bootstrap_impl(thfhe_kms_ctx *c, int32_t cb, int32_t cx, int32_t cy, int
 }
 int kms_lev_rlwe_mul_body(thfhe_kms_ctx *c, KmsTables &tabs, int party, int64_t *accum, const int64_t *lev, size_t count) {
     typedef thfhe_kms_ctx K;
-    if (!c->d_relin) return thfhe_fail(THFHE_E_INVALID, "thfhe_kms_set_relin_keys has not been called on this context");
+    if (!c->d_relin.bytes()) return thfhe_fail(THFHE_E_INVALID, "thfhe_kms_set_relin_keys has not been called on this context");
     THFHE_HIP(hipSetDevice(c->device));
     const size_t N = 2048, ab = count * (c->p.parties + 1) * N * 8, lb = count * c->p.l_lev * 2 * N * 8;
-    int rc = kms_w(c, K::W_ACCUM, ab);
-    if (!rc) rc = kms_w(c, K::W_LEV, lb);
+    int rc = c->d_w[K::W_ACCUM].grow(ab);
+    if (!rc) rc = c->d_w[K::W_LEV].grow(lb);
     if (rc) return rc;
-    THFHE_HIP(hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_w[K::W_ACCUM], accum, ab, hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_w[K::W_LEV], lev, lb, hipMemcpyHostToDevice, c->stream));
-    rc = kms_lev_rlwe_mul_dev(c, tabs, party, count, (int64_t *)c->d_w[K::W_ACCUM], (const int64_t *)c->d_w[K::W_LEV]);
+    THFHE_HIP(hipMemsetAsync(c->d_flag.as<int>(), 0, sizeof(int), c->stream));
+    THFHE_HIP(hipMemcpyAsync(c->d_w[K::W_ACCUM].as<void>(), accum, ab, hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(c->d_w[K::W_LEV].as<void>(), lev, lb, hipMemcpyHostToDevice, c->stream));
+    rc = kms_lev_rlwe_mul_dev(c, tabs, party, count, c->d_w[K::W_ACCUM].as<int64_t>(), c->d_w[K::W_LEV].as<int64_t>());
     if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(accum, c->d_w[K::W_ACCUM], ab, hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(accum, c->d_w[K::W_ACCUM].as<void>(), ab, hipMemcpyDeviceToHost, c->stream));
     return kms_finish(c);
 }
 }  // namespace
@@ -596,25 +532,22 @@ int thfhe_kms_set_relin_keys(thfhe_kms_ctx *c, const int64_t *uni, const int64_t
     if (!c || !uni || !pk || !crs) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (c->p.l_uni < 1 || c->p.l_uni > 16 || c->p.bg_uni < 1 || c->p.bg_uni > 13 || c->p.l_uni * c->p.bg_uni > 64 || c->p.bg_lev > 13 || c->p.parties > 62)
         return thfhe_fail(THFHE_E_UNSUPPORTED, "relinearisation gadgets: need Bgbit <= 13 (digits inside [-4096, 4096]), l_uni <= 16, l * Bgbit <= 64");
-    std::lock_guard<std::mutex> lock(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     const int P = c->p.parties, lu = c->p.l_uni;
     const size_t N = 2048, n_polys = (size_t)P * 3 * lu + (size_t)P * lu + lu;
-    void *d_raw = nullptr;
-    THFHE_HIP(hipMalloc(&d_raw, n_polys * N * 8));
-    hipError_t e = hipMemcpyAsync(d_raw, uni, (size_t)P * 3 * lu * N * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync((char *)d_raw + (size_t)P * 3 * lu * N * 8, pk, (size_t)P * lu * N * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync((char *)d_raw + (size_t)P * 4 * lu * N * 8, crs, (size_t)lu * N * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && !c->d_relin) e = hipMalloc(&c->d_relin, n_polys * 4 * 1024 * sizeof(cplx));
-    if (e == hipSuccess && !c->d_flag) e = hipMalloc(&c->d_flag, sizeof(int));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((pm_torus_transform_kernel<2048, 64>), dim3((unsigned)((n_polys * 4 + 3) / 4)), dim3(256), 0, c->stream, (const void *)d_raw, (long)n_polys,
-                           c->d_tw, c->d_relin);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_raw);
-    if (e != hipSuccess) return thfhe_fail_hip(e, "thfhe_kms_set_relin_keys");
+    DevBuf raw;  // upload staging
+    THFHE_TRY(raw.grow(n_polys * N * 8));
+    char *const d_raw = raw.as<char>();
+    THFHE_HIP(hipMemcpyAsync(d_raw, uni, (size_t)P * 3 * lu * N * 8, hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(d_raw + (size_t)P * 3 * lu * N * 8, pk, (size_t)P * lu * N * 8, hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(d_raw + (size_t)P * 4 * lu * N * 8, crs, (size_t)lu * N * 8, hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->d_relin.grow(n_polys * 4 * 1024 * sizeof(cplx)));
+    THFHE_TRY(c->d_flag.grow(sizeof(int)));
+    hipLaunchKernelGGL((pm_torus_transform_kernel<2048, 64>), dim3((unsigned)((n_polys * 4 + 3) / 4)), dim3(256), 0, c->stream, (const void *)d_raw, (long)n_polys,
+                       c->d_tw.as<cplx>(), c->d_relin.as<cplx>());
+    THFHE_HIP(hipGetLastError());
+    THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }
 
@@ -670,18 +603,18 @@ int thfhe_kms_rotate_parties_dev(thfhe_kms_ctx *c, int op, const int32_t *d_x, c
     if (cy != 0 && !d_y) return thfhe_fail(THFHE_E_INVALID, "null operand");
     if (first_party < 0 || n_parties < 0 || first_party + n_parties > c->p.parties) return thfhe_fail(THFHE_E_INVALID, "party block out of range");
     if (count == 0 || n_parties == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     const int P = c->p.parties, n = c->p.n, lv = c->p.l_lev;
     const size_t G = count, N = 2048;
-    rc = kms_w(c, K::W_BARA, (size_t)P * G * n * 4);
-    if (!rc) rc = kms_w(c, K::W_ACCUM, G * (P + 1) * N * 8);
+    rc = c->d_w[K::W_BARA].grow((size_t)P * G * n * 4);
+    if (!rc) rc = c->d_w[K::W_ACCUM].grow(G * (P + 1) * N * 8);
     if (rc) return rc;
     hipLaunchKernelGGL(kms_prologue_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, d_x, cy != 0 ? d_y : nullptr, cb, cx, cy, n, P, (long)G, (int64_t)1 << 61,
-                       (int32_t *)c->d_w[K::W_BARA], (int64_t *)c->d_w[K::W_ACCUM]);
+                       c->d_w[K::W_BARA].as<int32_t>(), c->d_w[K::W_ACCUM].as<int64_t>());
     THFHE_HIP(hipGetLastError());
     for (int q = 0; q < n_parties && !rc; q++)
-        rc = kms_launch_rotation(c, first_party + q, (const int32_t *)c->d_w[K::W_BARA] + (size_t)(first_party + q) * G * n, d_lev + (size_t)q * G * lv * 2 * N, nullptr, G, lv);
+        rc = kms_launch_rotation(c, first_party + q, c->d_w[K::W_BARA].as<int32_t>() + (size_t)(first_party + q) * G * n, d_lev + (size_t)q * G * lv * 2 * N, nullptr, G, lv);
     return rc;
 }
 // phase 2: accum = X^{-barb} mu (trivial), then mk_lev_rlwe_mul for p = 0 .. P-1 with d_lev_all int64[P][count][l_lev][2][N] (sequential by construction,
@@ -695,29 +628,29 @@ int thfhe_kms_finish_dev(thfhe_kms_ctx *c, int op, const int32_t *d_x, const int
     if (cy != 0 && !d_y) return thfhe_fail(THFHE_E_INVALID, "null operand");
     if (count == 0) return THFHE_OK;
     std::lock_guard<std::mutex> lock(c->mu);
-    if (!c->d_relin) return thfhe_fail(THFHE_E_INVALID, "thfhe_kms_set_relin_keys has not been called on this context");
+    if (!c->d_relin.bytes()) return thfhe_fail(THFHE_E_INVALID, "thfhe_kms_set_relin_keys has not been called on this context");
     THFHE_HIP(hipSetDevice(c->device));
     KmsTables tabs;
     const int P = c->p.parties, n = c->p.n, lv = c->p.l_lev;
     const size_t G = count, N = 2048, words = (size_t)P * n + 1, uw = (size_t)P * N + 1;
     auto body = [&]() -> int {
-        int r = kms_w(c, K::W_BARA, (size_t)P * G * n * 4);
-        if (!r) r = kms_w(c, K::W_ACCUM, G * (P + 1) * N * 8);
-        if (!r) r = kms_w(c, K::W_U, G * uw * 4);
+        int r = c->d_w[K::W_BARA].grow((size_t)P * G * n * 4);
+        if (!r) r = c->d_w[K::W_ACCUM].grow(G * (P + 1) * N * 8);
+        if (!r) r = c->d_w[K::W_U].grow(G * uw * 4);
         if (r) return r;
-        THFHE_HIP(hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
-        int64_t *d_accum = (int64_t *)c->d_w[K::W_ACCUM];
+        THFHE_HIP(hipMemsetAsync(c->d_flag.as<int>(), 0, sizeof(int), c->stream));
+        int64_t *d_accum = c->d_w[K::W_ACCUM].as<int64_t>();
         hipLaunchKernelGGL(kms_prologue_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, d_x, cy != 0 ? d_y : nullptr, cb, cx, cy, n, P, (long)G, (int64_t)1 << 61,
-                           (int32_t *)c->d_w[K::W_BARA], d_accum);
+                           c->d_w[K::W_BARA].as<int32_t>(), d_accum);
         THFHE_HIP(hipGetLastError());
         for (int party = 0; party < P; party++) {
             r = kms_lev_rlwe_mul_dev(c, tabs, party, G, d_accum, d_lev_all + (size_t)party * G * lv * 2 * N);
             if (r) return r;
         }
-        hipLaunchKernelGGL(kms_extract_kernel, dim3((unsigned)G, (unsigned)(P + 1)), dim3(256), 0, c->stream, (const int64_t *)d_accum, P, (int32_t *)c->d_w[K::W_U]);
+        hipLaunchKernelGGL(kms_extract_kernel, dim3((unsigned)G, (unsigned)(P + 1)), dim3(256), 0, c->stream, (const int64_t *)d_accum, P, c->d_w[K::W_U].as<int32_t>());
         THFHE_HIP(hipGetLastError());
         THFHE_HIP(hipMemsetAsync(d_out, 0, G * words * 4, c->stream));
-        MKKSArgs k{c->d_ksk, (const int32_t *)c->d_w[K::W_U], d_out, (long)G, n, c->p.ks_t, c->p.ks_basebit, P, c->row_words, (int)N, (int)uw, (int)N};
+        MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_w[K::W_U].as<int32_t>(), d_out, (long)G, n, c->p.ks_t, c->p.ks_basebit, P, c->row_words, (int)N, (int)uw, (int)N};
         const int nsplit = G <= 64 ? 8 : 2;
         mk_launch_keyswitch(k, nsplit, c->stream);
         THFHE_HIP(hipGetLastError());

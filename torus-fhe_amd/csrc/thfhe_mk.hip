@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -920,63 +921,29 @@ __global__ __launch_bounds__(256) void mk_mux_combine_kernel(const int32_t *__re
 
 }  // namespace
 
-struct thfhe_mk_ctx {
+struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     thfhe_params p;
-    int device = 0;
-    hipStream_t stream = nullptr;      // the stream every call enqueues on
-    hipStream_t own_stream = nullptr;  // created with the context; `stream` differs only after thfhe_mk_set_stream
-    cplx *d_bk = nullptr;
-    int32_t *d_ksk = nullptr;
-    cplx *d_tw = nullptr;
+    DevBuf d_bk, d_ksk, d_tw;
     int row_words = 0, w_pad = 0, words = 0, log2_2n = 11;
-    Rot2kPark park;              // batched N = 2048 rotation, two jobs per workgroup: partial spectra between row-part batches
+    DevBuf park;                 // batched N = 2048 rotation, two jobs per workgroup: partial spectra between row-part batches (thfhe_rot2k.h)
     long pair_threshold = 256;  // batches of more rotations than this run two gates per workgroup (mk_blind_rotate_pair_kernel)
     bool batched = false;       // N = 2048 with l x digit parts > 3: thfhe_rot2k.h (row parts through the LDS in batches), key table in its layout
-    int64_t *d_acc = nullptr;   // batched path: accumulators in global memory, int64[jobs][2][2048]
-    size_t cap_acc = 0;
+    DevBuf d_acc;               // batched path: accumulators in global memory, int64[jobs][2][2048]
     int parts = 1, pw = 0;      // N = 2048 with a wide gadget base: digit parts and their width (MKBRArgs)
-    size_t cap_jobs = 0;
-    int32_t *d_bara = nullptr, *d_barb = nullptr, *d_u = nullptr, *d_tmp = nullptr;
-    size_t cap_stage = 0;
+    DevBuf d_bara, d_barb, d_u, d_tmp;
+    Stage stage;
     DagBuffers dag;   // gate-DAG executor tables (thfhe_dag.h)
     size_t dag_slice = 8192;  // gates per launch of a DAG level
-    int32_t *d_in[3] = {nullptr, nullptr, nullptr};
-    int32_t *d_out = nullptr;
-    bool profiling = false, ev_valid = false;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::mutex mu;
 };
 
 namespace {
 
 int mk_ensure_workspace(thfhe_mk_ctx *c, size_t jobs) {
-    if (jobs <= c->cap_jobs) return THFHE_OK;
-    (void)hipFree(c->d_bara);
-    (void)hipFree(c->d_barb);
-    (void)hipFree(c->d_u);
-    (void)hipFree(c->d_tmp);
-    c->d_bara = c->d_barb = c->d_u = c->d_tmp = nullptr;
-    c->cap_jobs = 0;
-    THFHE_HIP(hipMalloc(&c->d_bara, jobs * c->w_pad * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_barb, jobs * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_u, jobs * ((size_t)c->p.N + 1) * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_tmp, jobs * (c->words + 1) * sizeof(int32_t)));
-    c->cap_jobs = jobs;
-    return THFHE_OK;
-}
-int mk_ensure_stage(thfhe_mk_ctx *c, size_t words) {
-    if (words <= c->cap_stage) return THFHE_OK;
-    for (auto &p : c->d_in) {
-        (void)hipFree(p);
-        p = nullptr;
-    }
-    (void)hipFree(c->d_out);
-    c->d_out = nullptr;
-    c->cap_stage = 0;
-    for (auto &p : c->d_in) THFHE_HIP(hipMalloc(&p, words * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_out, words * sizeof(int32_t)));
-    c->cap_stage = words;
-    return THFHE_OK;
+    int rc = c->d_bara.grow(jobs * c->w_pad * sizeof(int32_t));
+    if (!rc) rc = c->d_barb.grow(jobs * sizeof(int32_t));
+    if (!rc) rc = c->d_u.grow(jobs * ((size_t)c->p.N + 1) * sizeof(int32_t));
+    if (!rc) rc = c->d_tmp.grow(jobs * (c->words + 1) * sizeof(int32_t));
+    return rc;
 }
 
 __global__ void mk_extract_kernel(const int64_t *__restrict__ acc, int32_t *__restrict__ out, long jobs, int N);
@@ -988,15 +955,15 @@ int mk_enqueue_bootstraps(thfhe_mk_ctx *c, const int32_t *d0, const int32_t *d1,
     const size_t jobs = gates * rot;
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
     dim3 pg((unsigned)((c->words + 1 + 255) / 256), (unsigned)jobs);
-    hipLaunchKernelGGL(mk_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, L0, L1, d_ops, rot, c->words, c->w_pad, c->log2_2n, (long)jobs, c->d_bara, c->d_barb);
+    hipLaunchKernelGGL(mk_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, L0, L1, d_ops, rot, c->words, c->w_pad, c->log2_2n, (long)jobs, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
-    MKBRArgs a{c->d_bk, c->d_tw, c->d_bara, c->d_barb, c->d_u, (long)jobs, c->p.parties * c->p.n, c->w_pad, c->p.Bgbit, mu};
+    MKBRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, c->p.parties * c->p.n, c->w_pad, c->p.Bgbit, mu};
     {
         int rc = mk_launch_rotation(c, a);
         if (rc) return rc;
     }
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
-    MKKSArgs k{c->d_ksk, c->d_u, d_dst, (long)jobs, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, c->p.N, c->p.N + 1, 0};
+    MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_u.as<int32_t>(), d_dst, (long)jobs, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, c->p.N, c->p.N + 1, 0};
     const int nsplit = jobs * c->p.parties <= 64 ? 16 : (jobs * c->p.parties <= 256 ? 4 : (c->p.N > 2048 ? 2 : 1));  // fill the chip at small batch sizes; a block holds <= 2048 mask words
     THFHE_HIP(hipMemsetAsync(d_dst, 0, jobs * ((size_t)c->words + 1) * sizeof(int32_t), c->stream));
     mk_launch_keyswitch(k, nsplit, c->stream);
@@ -1014,27 +981,18 @@ int mk_launch_rotation(thfhe_mk_ctx *c, const MKBRArgs &a) {
         // ring of degree 4096: accumulators in global memory, rotated in place by r4k_rotate_kernel (thfhe_rot4k.h)
         int64_t *acc = a.acc_out;
         if (!acc) {
-            if ((size_t)a.jobs * 2 > c->cap_acc) {   // cap_acc counts 4096-word accumulators
-                (void)hipFree(c->d_acc);
-                c->d_acc = nullptr;
-                c->cap_acc = 0;
-                THFHE_HIP(hipMalloc(&c->d_acc, (size_t)a.jobs * 8192 * sizeof(int64_t)));
-                c->cap_acc = (size_t)a.jobs * 2;
-            }
-            acc = c->d_acc;
+            THFHE_TRY(c->d_acc.grow((size_t)a.jobs * 8192 * sizeof(int64_t)));
+            acc = c->d_acc.as<int64_t>();
         }
         if (!a.acc_in) hipLaunchKernelGGL(mk_acc_init_2k_kernel, dim3((unsigned)a.jobs), dim3(256), 0, c->stream, a.barb, a.mu, a.jobs, acc, 4096);
         else if (a.acc_in != acc) THFHE_HIP(hipMemcpyAsync(acc, a.acc_in, (size_t)a.jobs * 8192 * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream));
-        R4KArgs k{c->d_bk, c->d_tw, a.bara, acc, a.jobs, a.pn, c->p.l, c->p.Bgbit, c->parts, c->pw, a.w_pad};
-        if ((size_t)a.jobs > c->park.cap_wgs) {   // 128 KiB per workgroup for the parked partial spectra (thfhe_rot4k.h)
+        R4KArgs k{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), a.bara, acc, a.jobs, a.pn, c->p.l, c->p.Bgbit, c->parts, c->pw, a.w_pad};
+        const size_t park_bytes = (size_t)a.jobs * 8 * 2 * 512 * sizeof(cplx);   // 128 KiB per workgroup for the parked partial spectra (thfhe_rot4k.h)
+        if (park_bytes > c->park.bytes()) {
             THFHE_HIP(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->park.buf);
-            c->park.buf = nullptr;
-            c->park.cap_wgs = 0;
-            THFHE_HIP(hipMalloc(&c->park.buf, (size_t)a.jobs * 8 * 2 * 512 * sizeof(cplx)));
-            c->park.cap_wgs = (size_t)a.jobs;
+            THFHE_TRY(c->park.grow(park_bytes));
         }
-        hipLaunchKernelGGL(r4k_rotate_kernel, grid, block, 0, c->stream, k, c->park.buf);
+        hipLaunchKernelGGL(r4k_rotate_kernel, grid, block, 0, c->stream, k, c->park.as<cplx>());
         if (!a.acc_out) hipLaunchKernelGGL(mk_extract_kernel, grid, dim3(256), 0, c->stream, (const int64_t *)acc, a.out, a.jobs, 4096);
         THFHE_HIP(hipGetLastError());
         return THFHE_OK;
@@ -1044,17 +1002,11 @@ int mk_launch_rotation(thfhe_mk_ctx *c, const MKBRArgs &a) {
         // the accumulator itself)
         int64_t *acc = a.acc_out;
         if (!acc) {
-            if ((size_t)a.jobs > c->cap_acc) {
-                (void)hipFree(c->d_acc);
-                c->d_acc = nullptr;
-                c->cap_acc = 0;
-                THFHE_HIP(hipMalloc(&c->d_acc, (size_t)a.jobs * 4096 * sizeof(int64_t)));
-                c->cap_acc = (size_t)a.jobs;
-            }
-            acc = c->d_acc;
+            THFHE_TRY(c->d_acc.grow((size_t)a.jobs * 4096 * sizeof(int64_t)));
+            acc = c->d_acc.as<int64_t>();
         }
         if (!a.acc_in) hipLaunchKernelGGL(mk_acc_init_2k_kernel, dim3((unsigned)a.jobs), dim3(256), 0, c->stream, a.barb, a.mu, a.jobs, acc);
-        KmsBRArgs k{c->d_bk, c->d_tw, a.bara, acc, a.acc_in ? a.acc_in : acc, a.jobs, a.pn, c->p.l, c->p.Bgbit, c->parts, c->pw, 1, 1, a.w_pad};
+        KmsBRArgs k{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), a.bara, acc, a.acc_in ? a.acc_in : acc, a.jobs, a.pn, c->p.l, c->p.Bgbit, c->parts, c->pw, 1, 1, a.w_pad};
         {
             int rc = rot2k_launch(k, c->stream, c->pair_threshold, c->park);
             if (rc) return rc;
@@ -1162,10 +1114,10 @@ int mk_gates_dev_locked(thfhe_mk_ctx *c, int op, const int32_t *d0, const int32_
     // MUX: t1 = AND(x, y), t2 = AND(-x, z) as two full bootstraps, then (0, 1/8) + t1 + t2 without bootstrapping
     int rc = mk_ensure_workspace(c, 2 * count);
     if (rc) return rc;
-    rc = mk_enqueue_bootstraps(c, d0, d1, d2, L0, L1, 2, count, MU, c->d_tmp);  // job 2g: AND(x,y); job 2g+1: AND(-x,z)
+    rc = mk_enqueue_bootstraps(c, d0, d1, d2, L0, L1, 2, count, MU, c->d_tmp.as<int32_t>());  // job 2g: AND(x,y); job 2g+1: AND(-x,z)
     if (rc) return rc;
     // d_tmp holds [t1_0, t2_0, t1_1, t2_1, ...]: out = (0, 1/8) + t1 + t2            J/3gen_mk_gates.jl:144-147
-    hipLaunchKernelGGL(mk_mux_combine_kernel, dim3(lb), dim3(256), 0, c->stream, c->d_tmp, dout, words, rec);
+    hipLaunchKernelGGL(mk_mux_combine_kernel, dim3(lb), dim3(256), 0, c->stream, c->d_tmp.as<int32_t>(), dout, words, rec);
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
@@ -1196,14 +1148,10 @@ int thfhe_mk_ctx_create(const thfhe_params *p, const int64_t *bk_coeff, const in
         return thfhe_fail(THFHE_E_UNSUPPORTED, "need 1 <= l <= 4, l*Bgbit <= 32 (64 on the batched path), and Bgbit <= 10 (FP64 exactness bound) unless N = 2048 with l x ceil(Bgbit / 9) <= 3 or two-part digits");
     if (p->n < 1 || p->n > 767) return thfhe_fail(THFHE_E_UNSUPPORTED, "need 1 <= n <= 767");
     if (p->ks_t < 1 || p->ks_basebit < 1 || p->ks_t * p->ks_basebit > 31) return thfhe_fail(THFHE_E_INVALID, "bad key-switch parameters");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return thfhe_fail(THFHE_E_NO_DEVICE, "no usable HIP device (this library has no CPU fallback)");
-    THFHE_HIP(hipSetDevice(device));
-    thfhe_mk_ctx *c = new (std::nothrow) thfhe_mk_ctx;
+    std::unique_ptr<thfhe_mk_ctx> c(new (std::nothrow) thfhe_mk_ctx);
     if (!c) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
+    THFHE_TRY(c->open(device, true));
     c->p = *p;
-    c->device = device;
     c->words = p->parties * p->n;
     c->w_pad = (c->words + 3) & ~3;
     c->row_words = 128 * ((p->n + 1 + 127) / 128);
@@ -1211,23 +1159,7 @@ int thfhe_mk_ctx_create(const thfhe_params *p, const int64_t *bk_coeff, const in
     c->parts = parts;
     c->pw = pw;
     c->batched = batched;
-    int64_t *d_coeff = nullptr, *d_exp = nullptr;  // upload staging, freed on every path
-    int32_t *d_raw = nullptr;
-    auto fail = [&](int code) {
-        (void)hipFree(d_coeff);
-        (void)hipFree(d_exp);
-        (void)hipFree(d_raw);
-        thfhe_mk_ctx_destroy(c);
-        return code;
-    };
-#define CK(expr)                                                      \
-    do {                                                              \
-        hipError_t e_ = (expr);                                       \
-        if (e_ != hipSuccess) return fail(thfhe_fail_hip(e_, #expr)); \
-    } while (0)
-    CK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    c->stream = c->own_stream;
-    for (auto &e : c->ev) CK(hipEventCreate(&e));
+    DevBuf coeff, raw;  // upload staging
     std::vector<cplx> tw(1088 + 128 + 64 + 256);   // [1280..): per-lane roots of the four quarter twists (N = 4096)
     make_lane_roots_4096(tw.data() + 1280);
     // N = 1024: T1[512] T2[64]; N = 2048: T1(twist 1)[512] T1(twist 5)[512] T2[64]; [1088..): per-lane roots (N = 1024); [1216..): pass-1 ratio (N = 2048)
@@ -1240,15 +1172,15 @@ int thfhe_mk_ctx_create(const thfhe_params *p, const int64_t *bk_coeff, const in
         make_twiddles_1024(tw.data(), tw.data() + 512);
     }
     make_lane_roots_1024(tw.data() + 1088);
-    CK(hipMalloc(&c->d_tw, tw.size() * sizeof(cplx)));
-    CK(hipMemcpyAsync(c->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
+    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
     if (ring4k) {
         // key table of thfhe_rot4k.h: [party * n + i][row part rp = (j l + level) parts + part][output o][limb][quarter][512]; row part (j, level, part)
         // of output o is part_{mk_part_index(j, o)}[level] shifted left by part * pw bits (wrapping).  Staged party by party.
         const int RP = 2 * p->l * parts, N = 4096;
         const size_t polys_per_party = (size_t)p->n * RP * 2;
-        CK(hipMalloc(&c->d_bk, (size_t)p->parties * polys_per_party * 4 * 2048 * sizeof(cplx)));
-        CK(hipMalloc(&d_coeff, polys_per_party * N * sizeof(int64_t)));
+        THFHE_TRY(c->d_bk.grow((size_t)p->parties * polys_per_party * 4 * 2048 * sizeof(cplx)));
+        THFHE_TRY(coeff.grow(polys_per_party * N * sizeof(int64_t)));
         std::vector<int64_t> host(polys_per_party * N);
         for (int q = 0; q < p->parties; q++) {
             for (int i = 0; i < p->n; i++)
@@ -1262,22 +1194,21 @@ int thfhe_mk_ctx_create(const thfhe_params *p, const int64_t *bk_coeff, const in
                                 const int sh = part * pw;
                                 for (int t = 0; t < N; t++) dst[t] = (int64_t)((uint64_t)src[t] << sh);
                             }
-            CK(hipMemcpyAsync(d_coeff, host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(r4k_key_transform_kernel, dim3((unsigned)((polys_per_party * 4 + 3) / 4)), dim3(256), 0, c->stream, d_coeff, (long)polys_per_party,
-                               c->d_tw, c->d_bk + (size_t)q * polys_per_party * 4 * 2048);
-            CK(hipGetLastError());
-            CK(hipStreamSynchronize(c->stream));   // `host` is reused for the next party
+            THFHE_HIP(hipMemcpyAsync(coeff.as<int64_t>(), host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(r4k_key_transform_kernel, dim3((unsigned)((polys_per_party * 4 + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int64_t>(), (long)polys_per_party,
+                               c->d_tw.as<cplx>(), c->d_bk.as<cplx>() + (size_t)q * polys_per_party * 4 * 2048);
+            THFHE_HIP(hipGetLastError());
+            THFHE_HIP(hipStreamSynchronize(c->stream));   // `host` is reused for the next party
         }
-        (void)hipFree(d_coeff);
-        d_coeff = nullptr;
+        coeff = DevBuf();
     } else if (batched) {
         // key table of thfhe_rot2k.h: [party * n + i][row part rp = (j l + level) parts + part][output o][limb][half][512]; row part (j, level,
         // part) of output o is part_{mk_part_index(j, o)}[level] shifted left by part * pw bits (wrapping): d (*) K = d_lo (*) K + d_hi (*) (K << pw).
         // Staged party by party (the 256-party set: 194 MB of coefficients per party, 185 GB of spectra in all).
         const int RP = 2 * p->l * parts, N = 2048;
         const size_t polys_per_party = (size_t)p->n * RP * 2;
-        CK(hipMalloc(&c->d_bk, (size_t)p->parties * polys_per_party * 4 * 1024 * sizeof(cplx)));
-        CK(hipMalloc(&d_coeff, polys_per_party * N * sizeof(int64_t)));
+        THFHE_TRY(c->d_bk.grow((size_t)p->parties * polys_per_party * 4 * 1024 * sizeof(cplx)));
+        THFHE_TRY(coeff.grow(polys_per_party * N * sizeof(int64_t)));
         std::vector<int64_t> host(polys_per_party * N);
         for (int q = 0; q < p->parties; q++) {
             for (int i = 0; i < p->n; i++)
@@ -1291,130 +1222,65 @@ int thfhe_mk_ctx_create(const thfhe_params *p, const int64_t *bk_coeff, const in
                                 const int sh = part * pw;
                                 for (int t = 0; t < N; t++) dst[t] = (int64_t)((uint64_t)src[t] << sh);
                             }
-            CK(hipMemcpyAsync(d_coeff, host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(kms_key_transform_kernel, dim3((unsigned)((polys_per_party * 4 + 3) / 4)), dim3(256), 0, c->stream, d_coeff, (long)polys_per_party,
-                               c->d_tw, c->d_bk + (size_t)q * polys_per_party * 4 * 1024);
-            CK(hipGetLastError());
-            CK(hipStreamSynchronize(c->stream));   // `host` is reused for the next party
+            THFHE_HIP(hipMemcpyAsync(coeff.as<int64_t>(), host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(kms_key_transform_kernel, dim3((unsigned)((polys_per_party * 4 + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int64_t>(), (long)polys_per_party,
+                               c->d_tw.as<cplx>(), c->d_bk.as<cplx>() + (size_t)q * polys_per_party * 4 * 1024);
+            THFHE_HIP(hipGetLastError());
+            THFHE_HIP(hipStreamSynchronize(c->stream));   // `host` is reused for the next party
         }
-        (void)hipFree(d_coeff);
-        d_coeff = nullptr;
+        coeff = DevBuf();
     } else {
     const long PN = (long)p->parties * p->n;
     const size_t coeff_words = (size_t)PN * 4 * p->l * p->N;
-    CK(hipMalloc(&d_coeff, coeff_words * sizeof(int64_t)));
-    CK(hipMemcpyAsync(d_coeff, bk_coeff, coeff_words * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(coeff.grow(coeff_words * sizeof(int64_t)));
+    THFHE_HIP(hipMemcpyAsync(coeff.as<int64_t>(), bk_coeff, coeff_words * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     const int le = p->l * parts;
     const size_t chunks = (size_t)PN * 2 * le * 8;
-    CK(hipMalloc(&c->d_bk, chunks * (p->N / 2) * sizeof(cplx)));
+    THFHE_TRY(c->d_bk.grow(chunks * (p->N / 2) * sizeof(cplx)));
     if (p->N == 2048) {
         if (parts > 1) {   // key rows followed by their copies shifted left by pw, 2 pw bits (wrapping): d (*) K = sum_w d_w (*) (K << pw w)
-            CK(hipMalloc(&d_exp, coeff_words * parts * sizeof(int64_t)));
+            DevBuf exp;
+            THFHE_TRY(exp.grow(coeff_words * parts * sizeof(int64_t)));
             const long polys = PN * 4 * p->l;
-            hipLaunchKernelGGL(mk_expand_parts_kernel, dim3((unsigned)polys, (unsigned)parts), dim3(256), 0, c->stream, d_coeff, d_exp, p->l, parts, pw);
-            CK(hipGetLastError());
-            CK(hipStreamSynchronize(c->stream));
-            (void)hipFree(d_coeff);
-            d_coeff = d_exp;
-            d_exp = nullptr;
+            hipLaunchKernelGGL(mk_expand_parts_kernel, dim3((unsigned)polys, (unsigned)parts), dim3(256), 0, c->stream, coeff.as<int64_t>(), exp.as<int64_t>(), p->l, parts, pw);
+            THFHE_HIP(hipGetLastError());
+            THFHE_HIP(hipStreamSynchronize(c->stream));
+            coeff = std::move(exp);
         }
         const long items = PN * 2 * le * 8;
-        hipLaunchKernelGGL(mk_key_transform_2k_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, c->stream, d_coeff, PN, le, c->d_tw, c->d_bk);
+        hipLaunchKernelGGL(mk_key_transform_2k_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int64_t>(), PN, le, c->d_tw.as<cplx>(), c->d_bk.as<cplx>());
     } else {
         const long items = PN * 2 * p->l * 2;
-        hipLaunchKernelGGL(mk_key_transform_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, c->stream, d_coeff, PN, p->l, c->d_tw, c->d_bk);
+        hipLaunchKernelGGL(mk_key_transform_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int64_t>(), PN, p->l, c->d_tw.as<cplx>(), c->d_bk.as<cplx>());
     }
-    CK(hipGetLastError());
+    THFHE_HIP(hipGetLastError());
     }
     const long rows = (long)p->parties * p->N * p->ks_t * ((1 << p->ks_basebit) - 1);
-    CK(hipMalloc(&d_raw, (size_t)rows * (p->n + 1) * sizeof(int32_t)));
-    CK(hipMemcpyAsync(d_raw, ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    CK(hipMalloc(&c->d_ksk, (size_t)rows * c->row_words * sizeof(int32_t)));
-    hipLaunchKernelGGL(mk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, d_raw, rows, p->n, c->row_words, c->d_ksk);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_coeff);
-    (void)hipFree(d_raw);
-#undef CK
-    *out = c;
+    THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));
+    THFHE_HIP(hipMemcpyAsync(raw.as<int32_t>(), ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->d_ksk.grow((size_t)rows * c->row_words * sizeof(int32_t)));
+    hipLaunchKernelGGL(mk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, raw.as<int32_t>(), rows, p->n, c->row_words, c->d_ksk.as<int32_t>());
+    THFHE_HIP(hipGetLastError());
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    *out = c.release();
     return THFHE_OK;
 }
 
-void thfhe_mk_ctx_destroy(thfhe_mk_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    (void)hipFree(c->d_bk);
-    (void)hipFree(c->d_ksk);
-    (void)hipFree(c->d_tw);
-    (void)hipFree(c->park.buf);
-    (void)hipFree(c->d_bara);
-    (void)hipFree(c->d_barb);
-    (void)hipFree(c->d_u);
-    (void)hipFree(c->d_tmp);
-    (void)hipFree(c->d_acc);
-    for (auto &p : c->d_in) (void)hipFree(p);
-    (void)hipFree(c->d_out);
-    c->dag.release();
-    for (auto &e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
-}
+void thfhe_mk_ctx_destroy(thfhe_mk_ctx *c) { ctx_destroy(c); }
 
-void *thfhe_mk_dev_alloc(thfhe_mk_ctx *c, size_t bytes) {
-    if (!c) return nullptr;
-    void *p = nullptr;
-    if (hipSetDevice(c->device) != hipSuccess || hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    return p;
-}
-void thfhe_mk_dev_free(thfhe_mk_ctx *c, void *p) {
-    if (c) (void)hipSetDevice(c->device);
-    (void)hipFree(p);
-}
-int thfhe_mk_copy_h2d(thfhe_mk_ctx *c, void *dst, const void *src, size_t bytes) {
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    THFHE_HIP(hipSetDevice(c->device));
-    THFHE_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
-}
-int thfhe_mk_copy_d2h(thfhe_mk_ctx *c, void *dst, const void *src, size_t bytes) {
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    THFHE_HIP(hipSetDevice(c->device));
-    THFHE_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
-}
+void *thfhe_mk_dev_alloc(thfhe_mk_ctx *c, size_t bytes) { return ctx_dev_alloc(c, bytes); }
+void thfhe_mk_dev_free(thfhe_mk_ctx *c, void *p) { ctx_dev_free(c, p); }
+int thfhe_mk_copy_h2d(thfhe_mk_ctx *c, void *dst, const void *src, size_t bytes) { return ctx_copy(c, dst, src, bytes, hipMemcpyHostToDevice); }
+int thfhe_mk_copy_d2h(thfhe_mk_ctx *c, void *dst, const void *src, size_t bytes) { return ctx_copy(c, dst, src, bytes, hipMemcpyDeviceToHost); }
 int thfhe_mk_reserve(thfhe_mk_ctx *c, size_t max_count) {
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     return mk_ensure_workspace(c, max_count * 2);
 }
-int thfhe_mk_sync(thfhe_mk_ctx *c) {
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
-}
-int thfhe_mk_set_profiling(thfhe_mk_ctx *c, int enabled) {
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    std::lock_guard<std::mutex> g(c->mu);
-    c->profiling = enabled != 0;
-    c->ev_valid = false;
-    return THFHE_OK;
-}
-int thfhe_mk_last_timings(thfhe_mk_ctx *c, float ms[4]) {
-    if (!c || !ms) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->ev_valid) return thfhe_fail(THFHE_E_INVALID, "no profiled call recorded");
-    THFHE_HIP(hipEventSynchronize(c->ev[3]));
-    THFHE_HIP(hipEventElapsedTime(&ms[0], c->ev[0], c->ev[1]));
-    THFHE_HIP(hipEventElapsedTime(&ms[1], c->ev[1], c->ev[2]));
-    THFHE_HIP(hipEventElapsedTime(&ms[2], c->ev[2], c->ev[3]));
-    THFHE_HIP(hipEventElapsedTime(&ms[3], c->ev[0], c->ev[3]));
-    return THFHE_OK;
-}
+int thfhe_mk_sync(thfhe_mk_ctx *c) { return ctx_sync(c); }
+int thfhe_mk_set_profiling(thfhe_mk_ctx *c, int enabled) { return ctx_set_profiling(c, enabled); }
+int thfhe_mk_last_timings(thfhe_mk_ctx *c, float ms[4]) { return ctx_last_timings(c, ms); }
 
 int thfhe_mk_gates_dev(thfhe_mk_ctx *c, int op, const int32_t *d0, const int32_t *d1, const int32_t *d2, int32_t *dout, size_t count) {
     if (!c || !d0 || !dout) return thfhe_fail(THFHE_E_INVALID, "null argument");
@@ -1425,19 +1291,10 @@ int thfhe_mk_gates_dev(thfhe_mk_ctx *c, int op, const int32_t *d0, const int32_t
 int thfhe_mk_gates(thfhe_mk_ctx *c, int op, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count) {
     if (!c || !in0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
     const size_t words = count * ((size_t)c->words + 1), bytes = words * sizeof(int32_t);
-    int rc = mk_ensure_stage(c, words);
-    if (rc) return rc;
-    const int32_t *src[3] = {in0, in1, in2};
-    for (int q = 0; q < 3; q++)
-        if (src[q]) THFHE_HIP(hipMemcpyAsync(c->d_in[q], src[q], bytes, hipMemcpyHostToDevice, c->stream));
-    rc = mk_gates_dev_locked(c, op, c->d_in[0], in1 ? c->d_in[1] : nullptr, in2 ? c->d_in[2] : nullptr, c->d_out, count);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
+    return ctx_staged(c, words, {in0, in1, in2}, {bytes, bytes, bytes}, [&] {
+        return mk_gates_dev_locked(c, op, c->stage.in_ptr(0), in1 ? c->stage.in_ptr(1) : nullptr, in2 ? c->stage.in_ptr(2) : nullptr, c->stage.out_ptr(), count);
+    }, c->stage.out, out, bytes);
 }
 
 // Gate-DAG evaluation for the 3-gen scheme: the reference's integer circuits (mk_add_3gen ... mk_int_mul_3gen, J/3gen_mk_gates.jl:183-362) as
@@ -1455,8 +1312,8 @@ int thfhe_mk_dag_run_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inpu
                       plan);
     if (rc) return rc;
     if (stats) plan.fill_stats(stats);
-    std::lock_guard<std::mutex> lk(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     const int words = c->words + 1;
     MKLin L;
     mk_gate_lin(THFHE_NAND, 0, L);
@@ -1464,22 +1321,17 @@ int thfhe_mk_dag_run_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inpu
         plan, c->dag, c->stream, words, n_inputs, n_gates, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) {
             int r = mk_ensure_workspace(c, 2 * max_gates);
-            if (!r) r = mk_ensure_stage(c, max_gates * words);
-            in[0] = c->d_in[0], in[1] = c->d_in[1], in[2] = c->d_in[2], *out = c->d_out;
+            if (!r) r = c->stage.grow(max_gates * words);
+            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
             return r;
         },
         [&](int cls, const int32_t *d_ops, size_t n) {
-            if (cls == 0) return mk_enqueue_bootstraps(c, c->d_in[0], c->d_in[1], nullptr, L, L, 1, n, (int64_t)1 << 61, c->d_out, d_ops);
-            return mk_gates_dev_locked(c, cls == 1 ? THFHE_MUX : THFHE_AND3, c->d_in[0], c->d_in[1], c->d_in[2], c->d_out, n);
+            if (cls == 0) return mk_enqueue_bootstraps(c, c->stage.in_ptr(0), c->stage.in_ptr(1), nullptr, L, L, 1, n, (int64_t)1 << 61, c->stage.out_ptr(), d_ops);
+            return mk_gates_dev_locked(c, cls == 1 ? THFHE_MUX : THFHE_AND3, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), c->stage.out_ptr(), n);
         });
 }
 
-int thfhe_mk_set_dag_slice(thfhe_mk_ctx *c, size_t max_gates) {
-    if (!c || max_gates < 1 || max_gates > 32767) return thfhe_fail(THFHE_E_INVALID, "slice must be 1 .. 32767 gates");
-    std::lock_guard<std::mutex> g(c->mu);
-    c->dag_slice = max_gates;
-    return THFHE_OK;
-}
+int thfhe_mk_set_dag_slice(thfhe_mk_ctx *c, size_t max_gates) { return ctx_set_dag_slice(c, max_gates); }
 
 int thfhe_mk_dag_run(thfhe_mk_ctx *c, int32_t *wires, size_t n_inputs, const int32_t *gates, size_t n_gates, int64_t *stats) {
     if (!wires) return thfhe_fail(THFHE_E_INVALID, "null argument");
@@ -1492,23 +1344,13 @@ int thfhe_mk_gates_mixed(thfhe_mk_ctx *c, const int32_t *ops, const int32_t *in0
     for (size_t g = 0; g < count; g++)
         if (!(ops[g] == THFHE_NAND || ops[g] == THFHE_OR || ops[g] == THFHE_AND || ops[g] == THFHE_XOR))
             return thfhe_fail(THFHE_E_INVALID, "thfhe_mk_gates_mixed takes the two-input 3-gen gates NAND / OR / AND / XOR only");
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
     const size_t words = count * ((size_t)c->words + 1), bytes = words * sizeof(int32_t);
-    int rc = mk_ensure_stage(c, words);
-    if (rc) return rc;
-    rc = mk_ensure_workspace(c, count);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_in[0], in0, bytes, hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_in[1], in1, bytes, hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_in[2], ops, count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     MKLin L;
     mk_gate_lin(THFHE_NAND, 0, L);
-    rc = mk_enqueue_bootstraps(c, c->d_in[0], c->d_in[1], nullptr, L, L, 1, count, (int64_t)1 << 61, c->d_out, c->d_in[2]);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
+    return ctx_staged(c, words, {in0, in1, ops}, {bytes, bytes, count * sizeof(int32_t)}, [&] {   // staging buffer 2 holds the opcodes
+        int rc = mk_ensure_workspace(c, count);
+        return rc ? rc : mk_enqueue_bootstraps(c, c->stage.in_ptr(0), c->stage.in_ptr(1), nullptr, L, L, 1, count, (int64_t)1 << 61, c->stage.out_ptr(), c->stage.in_ptr(2));
+    }, c->stage.out, out, bytes);
 }
 
 // ---- party-sharded building blocks (device pointers; see include/thfhe_hip.h and thfhe/party_sharded.py) -------------------
@@ -1516,9 +1358,9 @@ int thfhe_mk_rotate_partial_dev(thfhe_mk_ctx *c, const int32_t *d_bara, const in
                                 int64_t *d_acc_out, size_t count) {
     if (!c || !d_bara || !d_acc_out || (!d_acc_in && !d_barb)) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
-    MKBRArgs a{c->d_bk, c->d_tw, d_bara, d_barb, nullptr, (long)count, c->p.parties * c->p.n, c->words, c->p.Bgbit, mu, d_acc_in, d_acc_out};
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    MKBRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), d_bara, d_barb, nullptr, (long)count, c->p.parties * c->p.n, c->words, c->p.Bgbit, mu, d_acc_in, d_acc_out};
     return mk_launch_rotation(c, a);
 }
 int thfhe_mk_prologue_dev(thfhe_mk_ctx *c, int op, int which, const int32_t *d0, const int32_t *d1, const int32_t *d2, int rec_words,
@@ -1531,8 +1373,8 @@ int thfhe_mk_prologue_dev(thfhe_mk_ctx *c, int op, int which, const int32_t *d0,
     if ((L.cy != 0 && !d1) || (L.cz != 0 && !d2)) return thfhe_fail(THFHE_E_INVALID, "null operand");
     const int nw = c->words;  // this context's parties are contiguous in the record: parties * n mask words
     if (first_word < 0 || first_word + nw > rec_words - 1) return thfhe_fail(THFHE_E_INVALID, "party slice outside the record");
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     const dim3 grid((unsigned)((nw + 1 + 255) / 256), (unsigned)count);
     hipLaunchKernelGGL(mk_prologue_slice_kernel, grid, dim3(256), 0, c->stream, d0, d1, d2, L, rec_words, first_word, nw, c->log2_2n, (long)count, d_bara, d_barb);
     THFHE_HIP(hipGetLastError());
@@ -1559,8 +1401,8 @@ int thfhe_mk_set_stream(thfhe_mk_ctx *c, void *hip_stream) {
 int thfhe_mk_extract_dev(thfhe_mk_ctx *c, const int64_t *d_acc, int32_t *d_u, size_t count) {
     if (!c || !d_acc || !d_u) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     hipLaunchKernelGGL(mk_extract_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, d_acc, d_u, (long)count, c->p.N);
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
@@ -1568,9 +1410,9 @@ int thfhe_mk_extract_dev(thfhe_mk_ctx *c, const int64_t *d_acc, int32_t *d_u, si
 int thfhe_mk_keyswitch_dev(thfhe_mk_ctx *c, const int32_t *d_u, int32_t *d_out, size_t count) {
     if (!c || !d_u || !d_out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
-    MKKSArgs k{c->d_ksk, d_u, d_out, (long)count, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, c->p.N, c->p.N + 1, 0};
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    MKKSArgs k{c->d_ksk.as<int32_t>(), d_u, d_out, (long)count, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, c->p.N, c->p.N + 1, 0};
     const int nsplit = count * c->p.parties <= 64 ? 16 : (count * c->p.parties <= 256 ? 4 : (c->p.N > 2048 ? 2 : 1));
     THFHE_HIP(hipMemsetAsync(d_out, 0, count * ((size_t)c->words + 1) * sizeof(int32_t), c->stream));
     mk_launch_keyswitch(k, nsplit, c->stream);
@@ -1581,21 +1423,13 @@ int thfhe_mk_keyswitch_dev(thfhe_mk_ctx *c, const int32_t *d_u, int32_t *d_out, 
 int thfhe_mk_bootstrap(thfhe_mk_ctx *c, int64_t mu, const int32_t *x, int32_t *out, size_t count) {
     if (!c || !x || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
     const size_t words = count * ((size_t)c->words + 1), bytes = words * sizeof(int32_t);
-    int rc = mk_ensure_stage(c, words);
-    if (rc) return rc;
-    rc = mk_ensure_workspace(c, count);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_in[0], x, bytes, hipMemcpyHostToDevice, c->stream));
     MKLin L;
     mk_gate_lin(kOpIdentity, 0, L);
-    rc = mk_enqueue_bootstraps(c, c->d_in[0], c->d_in[0], c->d_in[0], L, L, 1, count, mu, c->d_out);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
+    return ctx_staged(c, words, {x, nullptr, nullptr}, {bytes, 0, 0}, [&] {
+        int rc = mk_ensure_workspace(c, count);
+        return rc ? rc : mk_enqueue_bootstraps(c, c->stage.in_ptr(0), c->stage.in_ptr(0), c->stage.in_ptr(0), L, L, 1, count, mu, c->stage.out_ptr());
+    }, c->stage.out, out, bytes);
 }
 
 }  // extern "C"

@@ -479,23 +479,15 @@ __global__ __launch_bounds__(512, 2) void kms_tlev_rotate_pair_kernel(KmsBRArgs 
 
 // launch: one job per workgroup up to `pair_threshold` jobs (one per CU), two above; the park buffer (128 KiB per workgroup) is only
 // needed when the row parts do not fit one batch
-struct Rot2kPark {
-    cplx *buf = nullptr;
-    size_t cap_wgs = 0;
-};
-inline int rot2k_launch(const KmsBRArgs &a, hipStream_t stream, long pair_threshold, Rot2kPark &park) {
+inline int rot2k_launch(const KmsBRArgs &a, hipStream_t stream, long pair_threshold, DevBuf &park) {
     if (a.jobs > pair_threshold) {
-        const size_t wgs = ((size_t)a.jobs + 1) / 2;
+        const size_t wgs = ((size_t)a.jobs + 1) / 2, park_bytes = wgs * 8 * 2 * 512 * sizeof(cplx);
         const bool need_park = 2 * a.lg * a.parts > 6;
-        if (need_park && wgs > park.cap_wgs) {
+        if (need_park && park_bytes > park.bytes()) {
             THFHE_HIP(hipStreamSynchronize(stream));
-            (void)hipFree(park.buf);
-            park.buf = nullptr;
-            park.cap_wgs = 0;
-            THFHE_HIP(hipMalloc(&park.buf, wgs * 8 * 2 * 512 * sizeof(cplx)));
-            park.cap_wgs = wgs;
+            THFHE_TRY(park.grow(park_bytes));
         }
-        hipLaunchKernelGGL(kms_tlev_rotate_pair_kernel, dim3((unsigned)wgs), dim3(512), 0, stream, a, need_park ? park.buf : (cplx *)nullptr);
+        hipLaunchKernelGGL(kms_tlev_rotate_pair_kernel, dim3((unsigned)wgs), dim3(512), 0, stream, a, need_park ? park.as<cplx>() : (cplx *)nullptr);
     } else {
         hipLaunchKernelGGL(kms_tlev_rotate_kernel, dim3((unsigned)a.jobs), dim3(512), 0, stream, a);
     }

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -23,6 +24,7 @@
 #include "../../include/thfhe_hip.h"
 #include "thfhe_common.h"
 #include "thfhe_dag.h"
+#include "thfhe_devctx.h"
 #include "thfhe_lane.h"
 
 using namespace thfhe;
@@ -795,66 +797,34 @@ __global__ __launch_bounds__(256) void sk_linear_kernel(const int32_t *__restric
 // ======================================================================================================
 // host side
 // ======================================================================================================
-struct thfhe_ctx {
+struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     thfhe_params p;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    cplx *d_bk = nullptr;     // spectral key
-    int32_t *d_ksk = nullptr; // padded rows
+    DevBuf d_bk;              // spectral key
+    DevBuf d_ksk;             // padded rows
     int ks_w = 0;             // words per lane of a padded KSK row
     long ks_multi_min_gates = 1024;  // batches of at least this many gates use sk_keyswitch_multi_kernel (rows shared by the gates of a workgroup)
     long ks_staged_min_gates = 192;  // (measured: 128 gates 0.146 ms one gate per workgroup / 0.184 staged, 256 gates 0.381 / 0.201)
     // ... and, where its shape allows, batches from this size on sk_keyswitch_staged_kernel (rows staged in LDS, the digit selects an address)
     int coop_max_jobs = 768;    // remainders (batch mod 2048) up to this many rotations use the cooperative (latency) kernel
     int ring4_max_jobs = 1024;  // ... above it and up to this many, the four-wave ring kernel (launch_br)
-    cplx *d_tw = nullptr;
+    DevBuf d_tw;
     // workspace
-    size_t cap_jobs = 0;
     int n_pad = 0;
-    int32_t *d_bara = nullptr, *d_barb = nullptr, *d_u = nullptr;
+    DevBuf d_bara, d_barb, d_u;
     // staging for the host-buffer API
-    size_t cap_stage = 0;
-    int32_t *d_in[3] = {nullptr, nullptr, nullptr};
-    int32_t *d_out = nullptr;
+    Stage stage;
     // gate-DAG executor: wire table and index tables (grow-only, reused by every thfhe_dag_run on this context)
     DagBuffers dag;
     size_t dag_slice = 28672;  // gates per launch of a DAG level: 14 x 2048, so that a MUX slice (2 rotations per gate) stays under the 65 535 limit of the prologue's grid
-    // profiling
-    bool profiling = false;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool ev_valid = false;
-    std::mutex mu;
 };
 
 namespace {
 
 int ensure_workspace(thfhe_ctx *c, size_t jobs) {
-    if (jobs <= c->cap_jobs) return THFHE_OK;
-    (void)hipFree(c->d_bara);
-    (void)hipFree(c->d_barb);
-    (void)hipFree(c->d_u);
-    c->d_bara = c->d_barb = c->d_u = nullptr;
-    c->cap_jobs = 0;
-    THFHE_HIP(hipMalloc(&c->d_bara, jobs * c->n_pad * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_barb, jobs * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_u, jobs * 1025 * sizeof(int32_t)));
-    c->cap_jobs = jobs;
-    return THFHE_OK;
-}
-
-int ensure_stage(thfhe_ctx *c, size_t words) {
-    if (words <= c->cap_stage) return THFHE_OK;
-    for (auto &p : c->d_in) {
-        (void)hipFree(p);
-        p = nullptr;
-    }
-    (void)hipFree(c->d_out);
-    c->d_out = nullptr;
-    c->cap_stage = 0;
-    for (auto &p : c->d_in) THFHE_HIP(hipMalloc(&p, words * sizeof(int32_t)));
-    THFHE_HIP(hipMalloc(&c->d_out, words * sizeof(int32_t)));
-    c->cap_stage = words;
-    return THFHE_OK;
+    int rc = c->d_bara.grow(jobs * c->n_pad * sizeof(int32_t));
+    if (!rc) rc = c->d_barb.grow(jobs * sizeof(int32_t));
+    if (!rc) rc = c->d_u.grow(jobs * 1025 * sizeof(int32_t));
+    return rc;
 }
 
 // One launch of `a.jobs` rotations on one kernel shape.
@@ -920,9 +890,9 @@ int enqueue_rotations(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
     dim3 pg((unsigned)((n + 1 + 255) / 256), (unsigned)jobs);
     hipLaunchKernelGGL(sk_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, op, d_ops, rot_per_gate, n, c->n_pad,
-                       ilog2(2 * c->p.N), (long)jobs, c->d_bara, c->d_barb);
+                       ilog2(2 * c->p.N), (long)jobs, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
-    BRArgs a{c->d_bk, c->d_tw, c->d_bara, c->d_barb, c->d_u, (long)jobs, n, c->n_pad, c->p.Bgbit, mu};
+    BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, n, c->n_pad, c->p.Bgbit, mu};
     switch (c->p.l) {
     case 1: launch_br<1>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
     case 2: launch_br<2>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
@@ -943,7 +913,7 @@ int enqueue_keyswitch(thfhe_ctx *c, const int32_t *d_u, int32_t *d_out, size_t g
         // into 16 ranges (8 from 2 048 gates on: measured) whose partial sums meet in the zeroed output: 1 024 workgroups at 4 096 gates, 512 at 1 024.
         // Measured on MI355X, n = 630: 4 096 gates 1.01 ms (one gate per workgroup 2.57, branch-selected rows 1.69), 1 024 gates 0.34 (0.58),
         // 512 gates 0.24 (0.43), 256 gates 0.20 (0.38).
-        KSArgs k{c->d_ksk, d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, 2, gates >= 2048 ? 8 : 16};
+        KSArgs k{c->d_ksk.as<int32_t>(), d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, 2, gates >= 2048 ? 8 : 16};
         THFHE_HIP(hipMemsetAsync(d_out, 0, gates * (size_t)(c->p.n + 1) * sizeof(int32_t), c->stream));
         const dim3 sgrid((unsigned)((gates + 31) / 32), (unsigned)k.nsplit), sblock(512);
         if (c->ks_w == 8) hipLaunchKernelGGL((sk_keyswitch_staged_kernel<8, 4>), sgrid, sblock, 0, c->stream, k);
@@ -961,7 +931,7 @@ int enqueue_keyswitch(thfhe_ctx *c, const int32_t *d_u, int32_t *d_out, size_t g
         // staged kernel does not take (t not a multiple of its stage depth).  The coordinate range is cut in four so that 2048+ workgroups keep
         // ~12 waves per CU in flight.
         constexpr int kSplit = 4;
-        KSArgs k{c->d_ksk, d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, 2, kSplit};
+        KSArgs k{c->d_ksk.as<int32_t>(), d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, 2, kSplit};
         THFHE_HIP(hipMemsetAsync(d_out, 0, gates * (size_t)(c->p.n + 1) * sizeof(int32_t), c->stream));
         const dim3 block(256);
         if (c->ks_w == 8) hipLaunchKernelGGL((sk_keyswitch_multi_kernel<2, 0, 8>), dim3((unsigned)((gates + 7) / 8), kSplit), block, 0, c->stream, k);
@@ -975,7 +945,7 @@ int enqueue_keyswitch(thfhe_ctx *c, const int32_t *d_u, int32_t *d_out, size_t g
         return THFHE_OK;
     }
     const int nsplit = gates <= 32 ? 16 : (gates <= 128 ? 8 : (gates <= 512 ? 2 : 1));  // fill the chip at small batch sizes
-    KSArgs k{c->d_ksk, d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, c->p.ks_basebit, nsplit};
+    KSArgs k{c->d_ksk.as<int32_t>(), d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, c->p.ks_basebit, nsplit};
     if (nsplit > 1) THFHE_HIP(hipMemsetAsync(d_out, 0, gates * (size_t)(c->p.n + 1) * sizeof(int32_t), c->stream));
     const dim3 grid((unsigned)gates, (unsigned)nsplit), block(256);
     switch (c->ks_w) {
@@ -1012,7 +982,7 @@ int gates_dev_locked(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1,
     const int rot = op == THFHE_MUX ? 2 : 1;
     int rc = enqueue_rotations(c, op, d0, d1, d2, count, rot, 1 << 29);
     if (rc) return rc;
-    return enqueue_keyswitch(c, c->d_u, dout, count, rot, true);
+    return enqueue_keyswitch(c, c->d_u.as<int32_t>(), dout, count, rot, true);
 }
 
 }  // namespace
@@ -1040,78 +1010,40 @@ int thfhe_ctx_create(const thfhe_params *p, const int32_t *bk_coeff, const int32
         return thfhe_fail(THFHE_E_UNSUPPORTED, "need 1 <= l <= 4, Bgbit <= 10 (FP64 exactness bound), l*Bgbit <= 32");
     if (p->n < 1 || p->n > 1407) return thfhe_fail(THFHE_E_UNSUPPORTED, "need 1 <= n <= 1407");
     if (p->ks_t < 1 || p->ks_basebit < 1 || p->ks_t * p->ks_basebit > 31) return thfhe_fail(THFHE_E_INVALID, "bad key-switch parameters");
-    if (thfhe_device_count() <= device || device < 0) return thfhe_fail(THFHE_E_NO_DEVICE, "no usable HIP device (this library has no CPU fallback)");
-    THFHE_HIP(hipSetDevice(device));
-    thfhe_ctx *c = new (std::nothrow) thfhe_ctx;
+    std::unique_ptr<thfhe_ctx> c(new (std::nothrow) thfhe_ctx);
     if (!c) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
+    THFHE_TRY(c->open(device, true));
     c->p = *p;
-    c->device = device;
     c->n_pad = (p->n + 3) & ~3;
     c->ks_w = ks_words_per_lane(p->n);
     const int row_words = 64 * c->ks_w;
-    int32_t *d_coeff = nullptr, *d_raw = nullptr;  // upload staging, freed on every path
-    auto fail = [&](int code) {
-        (void)hipFree(d_coeff);
-        (void)hipFree(d_raw);
-        thfhe_ctx_destroy(c);
-        return code;
-    };
-#define CK(expr)                                                   \
-    do {                                                           \
-        hipError_t e_ = (expr);                                    \
-        if (e_ != hipSuccess) return fail(thfhe_fail_hip(e_, #expr)); \
-    } while (0)
-    CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (auto &e : c->ev) CK(hipEventCreate(&e));
     // twiddles
     std::vector<cplx> tw(576 + 128);  // T1[512] T2[64] lane roots[128]
     make_twiddles_1024(tw.data(), tw.data() + 512);
     make_lane_roots_1024(tw.data() + 576);
-    CK(hipMalloc(&c->d_tw, tw.size() * sizeof(cplx)));
-    CK(hipMemcpyAsync(c->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
+    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
     // bootstrapping key: upload coefficients, transform on device
+    DevBuf coeff, raw;  // upload staging
     const long npolys = (long)p->n * 2 * p->l * 2;
-    CK(hipMalloc(&d_coeff, (size_t)npolys * 1024 * sizeof(int32_t)));
-    CK(hipMemcpyAsync(d_coeff, bk_coeff, (size_t)npolys * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    CK(hipMalloc(&c->d_bk, (size_t)npolys * 1024 * sizeof(cplx)));
-    hipLaunchKernelGGL(sk_key_transform_kernel, dim3((unsigned)((npolys + 3) / 4)), dim3(256), 0, c->stream, d_coeff, npolys, c->d_tw, c->d_bk);
-    CK(hipGetLastError());
+    THFHE_TRY(coeff.grow((size_t)npolys * 1024 * sizeof(int32_t)));
+    THFHE_HIP(hipMemcpyAsync(coeff.as<int32_t>(), bk_coeff, (size_t)npolys * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->d_bk.grow((size_t)npolys * 1024 * sizeof(cplx)));
+    hipLaunchKernelGGL(sk_key_transform_kernel, dim3((unsigned)((npolys + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int32_t>(), npolys, c->d_tw.as<cplx>(), c->d_bk.as<cplx>());
+    THFHE_HIP(hipGetLastError());
     // key-switching key: pad rows to 640 words
     const long rows = (long)p->N * p->ks_t * ((1 << p->ks_basebit) - 1);
-    CK(hipMalloc(&d_raw, (size_t)rows * (p->n + 1) * sizeof(int32_t)));
-    CK(hipMemcpyAsync(d_raw, ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    CK(hipMalloc(&c->d_ksk, (size_t)rows * row_words * sizeof(int32_t)));
-    hipLaunchKernelGGL(sk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, d_raw, rows, p->n, row_words, c->d_ksk);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_coeff);
-    (void)hipFree(d_raw);
-#undef CK
-    *out = c;
+    THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));
+    THFHE_HIP(hipMemcpyAsync(raw.as<int32_t>(), ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->d_ksk.grow((size_t)rows * row_words * sizeof(int32_t)));
+    hipLaunchKernelGGL(sk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, raw.as<int32_t>(), rows, p->n, row_words, c->d_ksk.as<int32_t>());
+    THFHE_HIP(hipGetLastError());
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    *out = c.release();
     return THFHE_OK;
 }
 
-void thfhe_ctx_destroy(thfhe_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    {
-        std::lock_guard<std::mutex> g(c->mu);  // a call still running on another thread finishes first
-        if (c->stream) (void)hipStreamSynchronize(c->stream);
-    }
-    (void)hipFree(c->d_bk);
-    (void)hipFree(c->d_ksk);
-    (void)hipFree(c->d_tw);
-    (void)hipFree(c->d_bara);
-    (void)hipFree(c->d_barb);
-    (void)hipFree(c->d_u);
-    for (auto &p : c->d_in) (void)hipFree(p);
-    (void)hipFree(c->d_out);
-    c->dag.release();
-    for (auto &e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
+void thfhe_ctx_destroy(thfhe_ctx *c) { ctx_destroy(c); }
 
 int thfhe_ctx_params(const thfhe_ctx *c, thfhe_params *out) {
     if (!c || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
@@ -1119,41 +1051,17 @@ int thfhe_ctx_params(const thfhe_ctx *c, thfhe_params *out) {
     return THFHE_OK;
 }
 
-void *thfhe_dev_alloc(thfhe_ctx *c, size_t bytes) {
-    if (!c) return nullptr;
-    void *p = nullptr;
-    if (hipSetDevice(c->device) != hipSuccess || hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    return p;
-}
-void thfhe_dev_free(thfhe_ctx *c, void *p) {
-    if (c) (void)hipSetDevice(c->device);
-    (void)hipFree(p);
-}
-int thfhe_copy_h2d(thfhe_ctx *c, void *dst, const void *src, size_t bytes) {
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    THFHE_HIP(hipSetDevice(c->device));
-    THFHE_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
-}
-int thfhe_copy_d2h(thfhe_ctx *c, void *dst, const void *src, size_t bytes) {
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    THFHE_HIP(hipSetDevice(c->device));
-    THFHE_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
-}
+void *thfhe_dev_alloc(thfhe_ctx *c, size_t bytes) { return ctx_dev_alloc(c, bytes); }
+void thfhe_dev_free(thfhe_ctx *c, void *p) { ctx_dev_free(c, p); }
+int thfhe_copy_h2d(thfhe_ctx *c, void *dst, const void *src, size_t bytes) { return ctx_copy(c, dst, src, bytes, hipMemcpyHostToDevice); }
+int thfhe_copy_d2h(thfhe_ctx *c, void *dst, const void *src, size_t bytes) { return ctx_copy(c, dst, src, bytes, hipMemcpyDeviceToHost); }
 int thfhe_reserve(thfhe_ctx *c, size_t max_count) {
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     return ensure_workspace(c, max_count * 2);
 }
-int thfhe_sync(thfhe_ctx *c) {
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
-}
+int thfhe_sync(thfhe_ctx *c) { return ctx_sync(c); }
 #ifdef THFHE_STAMPS
 int thfhe_debug_read_stamps(unsigned long long *dst, size_t count) {
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), count * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
@@ -1171,24 +1079,8 @@ int thfhe_set_ring4_threshold(thfhe_ctx *c, int max_jobs) {
     c->ring4_max_jobs = max_jobs;
     return THFHE_OK;
 }
-int thfhe_set_profiling(thfhe_ctx *c, int enabled) {
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    std::lock_guard<std::mutex> g(c->mu);
-    c->profiling = enabled != 0;
-    c->ev_valid = false;
-    return THFHE_OK;
-}
-int thfhe_last_timings(thfhe_ctx *c, float ms[4]) {
-    if (!c || !ms) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!c->ev_valid) return thfhe_fail(THFHE_E_INVALID, "no profiled call recorded");
-    THFHE_HIP(hipEventSynchronize(c->ev[3]));
-    THFHE_HIP(hipEventElapsedTime(&ms[0], c->ev[0], c->ev[1]));
-    THFHE_HIP(hipEventElapsedTime(&ms[1], c->ev[1], c->ev[2]));
-    THFHE_HIP(hipEventElapsedTime(&ms[2], c->ev[2], c->ev[3]));
-    THFHE_HIP(hipEventElapsedTime(&ms[3], c->ev[0], c->ev[3]));
-    return THFHE_OK;
-}
+int thfhe_set_profiling(thfhe_ctx *c, int enabled) { return ctx_set_profiling(c, enabled); }
+int thfhe_last_timings(thfhe_ctx *c, float ms[4]) { return ctx_last_timings(c, ms); }
 
 int thfhe_gates_dev(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1, const int32_t *d2, int32_t *dout, size_t count) {
     if (!c || !d0 || !dout) return thfhe_fail(THFHE_E_INVALID, "null argument");
@@ -1199,19 +1091,10 @@ int thfhe_gates_dev(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1, 
 int thfhe_gates(thfhe_ctx *c, int op, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count) {
     if (!c || !in0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
     const size_t words = count * (c->p.n + 1), bytes = words * sizeof(int32_t);
-    int rc = ensure_stage(c, words);
-    if (rc) return rc;
-    const int32_t *src[3] = {in0, in1, in2};
-    for (int q = 0; q < 3; q++)
-        if (src[q]) THFHE_HIP(hipMemcpyAsync(c->d_in[q], src[q], bytes, hipMemcpyHostToDevice, c->stream));
-    rc = gates_dev_locked(c, op, c->d_in[0], in1 ? c->d_in[1] : nullptr, in2 ? c->d_in[2] : nullptr, c->d_out, count);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));  // after all input copies: aliasing-safe
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
+    return ctx_staged(c, words, {in0, in1, in2}, {bytes, bytes, bytes}, [&] {
+        return gates_dev_locked(c, op, c->stage.in_ptr(0), in1 ? c->stage.in_ptr(1) : nullptr, in2 ? c->stage.in_ptr(2) : nullptr, c->stage.out_ptr(), count);
+    }, c->stage.out, out, bytes);
 }
 
 int thfhe_gates_mixed(thfhe_ctx *c, const int32_t *ops, const int32_t *in0, const int32_t *in1, int32_t *out, size_t count) {
@@ -1219,21 +1102,11 @@ int thfhe_gates_mixed(thfhe_ctx *c, const int32_t *ops, const int32_t *in0, cons
     if (count == 0) return THFHE_OK;
     for (size_t g = 0; g < count; g++)
         if (ops[g] < THFHE_NAND || ops[g] > THFHE_ORYN) return thfhe_fail(THFHE_E_INVALID, "thfhe_gates_mixed takes two-input bootstrapped gates only");
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
     const size_t words = count * (c->p.n + 1), bytes = words * sizeof(int32_t);
-    int rc = ensure_stage(c, words);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_in[0], in0, bytes, hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_in[1], in1, bytes, hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_in[2], ops, count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));  // staging buffer 2 holds the opcodes
-    rc = enqueue_rotations(c, THFHE_NAND, c->d_in[0], c->d_in[1], nullptr, count, 1, 1 << 29, c->d_in[2]);
-    if (rc) return rc;
-    rc = enqueue_keyswitch(c, c->d_u, c->d_out, count, 1, true);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
+    return ctx_staged(c, words, {in0, in1, ops}, {bytes, bytes, count * sizeof(int32_t)}, [&] {   // staging buffer 2 holds the opcodes
+        int rc = enqueue_rotations(c, THFHE_NAND, c->stage.in_ptr(0), c->stage.in_ptr(1), nullptr, count, 1, 1 << 29, c->stage.in_ptr(2));
+        return rc ? rc : enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), count, 1, true);
+    }, c->stage.out, out, bytes);
 }
 
 // Gate-DAG evaluation: ASAP levelising scheduler (thfhe_dag.h) + device-resident executor.  The reference's
@@ -1248,32 +1121,27 @@ int thfhe_dag_run_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs, co
                       plan);
     if (rc) return rc;
     if (stats) plan.fill_stats(stats);
-    std::lock_guard<std::mutex> lk(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     const int words = c->p.n + 1;
     return dag_execute(
         plan, c->dag, c->stream, words, n_inputs, n_gates, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) {
             int r = ensure_workspace(c, 2 * max_gates);
-            if (!r) r = ensure_stage(c, max_gates * words);
-            in[0] = c->d_in[0], in[1] = c->d_in[1], in[2] = c->d_in[2], *out = c->d_out;
+            if (!r) r = c->stage.grow(max_gates * words);
+            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
             return r;
         },
         [&](int cls, const int32_t *d_ops, size_t n) {
             const bool is_mux = cls == 1;
-            int r = enqueue_rotations(c, is_mux ? THFHE_MUX : THFHE_NAND, c->d_in[0], c->d_in[1], is_mux ? c->d_in[2] : nullptr, n, is_mux ? 2 : 1, 1 << 29,
+            int r = enqueue_rotations(c, is_mux ? THFHE_MUX : THFHE_NAND, c->stage.in_ptr(0), c->stage.in_ptr(1), is_mux ? c->stage.in_ptr(2) : nullptr, n, is_mux ? 2 : 1, 1 << 29,
                                       is_mux ? nullptr : d_ops);
-            if (!r) r = enqueue_keyswitch(c, c->d_u, c->d_out, n, is_mux ? 2 : 1, false);
+            if (!r) r = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), n, is_mux ? 2 : 1, false);
             return r;
         });
 }
 
-int thfhe_set_dag_slice(thfhe_ctx *c, size_t max_gates) {
-    if (!c || max_gates < 1 || max_gates > 32767) return thfhe_fail(THFHE_E_INVALID, "slice must be 1 .. 32767 gates");
-    std::lock_guard<std::mutex> g(c->mu);
-    c->dag_slice = max_gates;
-    return THFHE_OK;
-}
+int thfhe_set_dag_slice(thfhe_ctx *c, size_t max_gates) { return ctx_set_dag_slice(c, max_gates); }
 
 int thfhe_dag_run(thfhe_ctx *c, int32_t *wires, size_t n_inputs, const int32_t *gates, size_t n_gates, int64_t *stats) {
     if (!wires) return thfhe_fail(THFHE_E_INVALID, "null argument");
@@ -1283,50 +1151,35 @@ int thfhe_dag_run(thfhe_ctx *c, int32_t *wires, size_t n_inputs, const int32_t *
 int thfhe_bootstrap_wo_keyswitch(thfhe_ctx *c, int32_t mu, const int32_t *x, int32_t *out_N1, size_t count) {
     if (!c || !x || !out_N1) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
     const size_t words = count * (c->p.n + 1);
-    int rc = ensure_stage(c, words);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_in[0], x, words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    rc = enqueue_rotations(c, kOpIdentity, c->d_in[0], c->d_in[0], nullptr, count, 1, mu);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(out_N1, c->d_u, count * 1025 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
+    return ctx_staged(c, words, {x, nullptr, nullptr}, {words * sizeof(int32_t), 0, 0}, [&] {
+        return enqueue_rotations(c, kOpIdentity, c->stage.in_ptr(0), c->stage.in_ptr(0), nullptr, count, 1, mu);
+    }, c->d_u, out_N1, count * 1025 * sizeof(int32_t));
 }
 
 int thfhe_bootstrap(thfhe_ctx *c, int32_t mu, const int32_t *x, int32_t *out, size_t count) {
     if (!c || !x || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
     const size_t words = count * (c->p.n + 1);
-    int rc = ensure_stage(c, words);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_in[0], x, words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    rc = enqueue_rotations(c, kOpIdentity, c->d_in[0], c->d_in[0], nullptr, count, 1, mu);
-    if (rc) return rc;
-    rc = enqueue_keyswitch(c, c->d_u, c->d_out, count, 1, false);
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(out, c->d_out, words * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
+    return ctx_staged(c, words, {x, nullptr, nullptr}, {words * sizeof(int32_t), 0, 0}, [&] {
+        int rc = enqueue_rotations(c, kOpIdentity, c->stage.in_ptr(0), c->stage.in_ptr(0), nullptr, count, 1, mu);
+        return rc ? rc : enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), count, 1, false);
+    }, c->stage.out, out, words * sizeof(int32_t));
 }
 
 int thfhe_keyswitch(thfhe_ctx *c, const int32_t *in_N1, int32_t *out, size_t count) {
     if (!c || !in_N1 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     int rc = ensure_workspace(c, count);
     if (rc) return rc;
-    rc = ensure_stage(c, count * (c->p.n + 1));
+    rc = c->stage.grow(count * (c->p.n + 1));
     if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_u, in_N1, count * 1025 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    rc = enqueue_keyswitch(c, c->d_u, c->d_out, count, 1, false);
+    THFHE_HIP(hipMemcpyAsync(c->d_u.as<int32_t>(), in_N1, count * 1025 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    rc = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), count, 1, false);
     if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(out, c->d_out, count * (c->p.n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(out, c->stage.out_ptr(), count * (c->p.n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }

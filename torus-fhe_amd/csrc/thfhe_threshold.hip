@@ -9,12 +9,14 @@
 // (two forward, two inverse transforms per ciphertext, one wave each).  |sum| <= N 2^9 2^15 = 2^34: inside the exactness bound.
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include "../../include/thfhe_hip.h"
 #include "thfhe_common.h"
+#include "thfhe_devctx.h"
 #include "thfhe_lane.h"
 
 using namespace thfhe;
@@ -110,27 +112,10 @@ __global__ __launch_bounds__(256) void final_decrypt_kernel(const int32_t *__res
 
 }  // namespace
 
-struct thfhe_poly_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    cplx *d_tw = nullptr, *d_spec = nullptr;
-    int *d_flag = nullptr;
-    void *d_buf[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t cap[4] = {0, 0, 0, 0};
-    std::mutex mu;
+struct THFHE_INTERNAL thfhe_poly_ctx : DevCtx {
+    DevBuf d_tw, d_spec, d_flag;
+    DevBuf d_buf[4];
 };
-
-namespace {
-int ensure(thfhe_poly_ctx *c, int slot, size_t bytes) {
-    if (bytes <= c->cap[slot]) return THFHE_OK;
-    (void)hipFree(c->d_buf[slot]);
-    c->d_buf[slot] = nullptr;
-    c->cap[slot] = 0;
-    THFHE_HIP(hipMalloc(&c->d_buf[slot], bytes));
-    c->cap[slot] = bytes;
-    return THFHE_OK;
-}
-}  // namespace
 
 extern "C" {
 
@@ -138,56 +123,37 @@ int thfhe_poly_ctx_create(int device, int N, thfhe_poly_ctx **out) {
     if (!out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     *out = nullptr;
     if (N != 1024) return thfhe_fail(THFHE_E_UNSUPPORTED, "only N = 1024 (k = 1) is implemented");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return thfhe_fail(THFHE_E_NO_DEVICE, "no usable HIP device (this library has no CPU fallback)");
-    THFHE_HIP(hipSetDevice(device));
-    thfhe_poly_ctx *c = new (std::nothrow) thfhe_poly_ctx;
+    std::unique_ptr<thfhe_poly_ctx> c(new (std::nothrow) thfhe_poly_ctx);
     if (!c) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
-    c->device = device;
+    THFHE_TRY(c->open(device, false));
     std::vector<cplx> tw(576);
     make_twiddles_1024(tw.data(), tw.data() + 512);
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&c->d_tw, tw.size() * sizeof(cplx));
-    if (e == hipSuccess) e = hipMalloc(&c->d_spec, 512 * sizeof(cplx));
-    if (e == hipSuccess) e = hipMalloc(&c->d_flag, sizeof(int));
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        thfhe_poly_ctx_destroy(c);
-        return thfhe_fail_hip(e, "thfhe_poly_ctx_create");
-    }
-    *out = c;
+    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
+    THFHE_TRY(c->d_spec.grow(512 * sizeof(cplx)));
+    THFHE_TRY(c->d_flag.grow(sizeof(int)));
+    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    *out = c.release();
     return THFHE_OK;
 }
 
-void thfhe_poly_ctx_destroy(thfhe_poly_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->d_tw);
-    (void)hipFree(c->d_spec);
-    (void)hipFree(c->d_flag);
-    for (auto &p : c->d_buf) (void)hipFree(p);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
+void thfhe_poly_ctx_destroy(thfhe_poly_ctx *c) { ctx_destroy(c); }
 
 int thfhe_tlwe_from_lwe(thfhe_poly_ctx *c, const int32_t *lwe, int32_t *tlwe_a, int32_t *tlwe_b, size_t count) {
     if (!c || !lwe || !tlwe_a || !tlwe_b) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
-    int rc = ensure(c, 0, count * 1025 * 4);
-    if (!rc) rc = ensure(c, 1, count * 1024 * 4);
-    if (!rc) rc = ensure(c, 2, count * 1024 * 4);
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    int rc = c->d_buf[0].grow(count * 1025 * 4);
+    if (!rc) rc = c->d_buf[1].grow(count * 1024 * 4);
+    if (!rc) rc = c->d_buf[2].grow(count * 1024 * 4);
     if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_buf[0], lwe, count * 1025 * 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(tlwe_from_lwe_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, (const int32_t *)c->d_buf[0], (int32_t *)c->d_buf[1],
-                       (int32_t *)c->d_buf[2], (long)count);
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[0].as<void>(), lwe, count * 1025 * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(tlwe_from_lwe_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, c->d_buf[0].as<int32_t>(), c->d_buf[1].as<int32_t>(),
+                       c->d_buf[2].as<int32_t>(), (long)count);
     THFHE_HIP(hipGetLastError());
-    THFHE_HIP(hipMemcpyAsync(tlwe_a, c->d_buf[1], count * 1024 * 4, hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipMemcpyAsync(tlwe_b, c->d_buf[2], count * 1024 * 4, hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(tlwe_a, c->d_buf[1].as<void>(), count * 1024 * 4, hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(tlwe_b, c->d_buf[2].as<void>(), count * 1024 * 4, hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }
@@ -195,25 +161,25 @@ int thfhe_tlwe_from_lwe(thfhe_poly_ctx *c, const int32_t *lwe, int32_t *tlwe_a, 
 int thfhe_partial_decrypt(thfhe_poly_ctx *c, const int32_t *key_share, const int32_t *tlwe_a, const int32_t *noise, int32_t *partial, size_t count) {
     if (!c || !key_share || !tlwe_a || !partial) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     const size_t bytes = count * 1024 * 4;
-    int rc = ensure(c, 0, bytes);
-    if (!rc) rc = ensure(c, 1, bytes);
-    if (!rc) rc = ensure(c, 2, bytes);
-    if (!rc) rc = ensure(c, 3, 1024 * 4);
+    int rc = c->d_buf[0].grow(bytes);
+    if (!rc) rc = c->d_buf[1].grow(bytes);
+    if (!rc) rc = c->d_buf[2].grow(bytes);
+    if (!rc) rc = c->d_buf[3].grow(1024 * 4);
     if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_buf[3], key_share, 1024 * 4, hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_buf[0], tlwe_a, bytes, hipMemcpyHostToDevice, c->stream));
-    if (noise) THFHE_HIP(hipMemcpyAsync(c->d_buf[1], noise, bytes, hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(share_transform_kernel, dim3(1), dim3(64), 0, c->stream, (const int32_t *)c->d_buf[3], c->d_tw, c->d_spec, c->d_flag);
-    hipLaunchKernelGGL(partial_decrypt_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, c->stream, (const int32_t *)c->d_buf[0],
-                       noise ? (const int32_t *)c->d_buf[1] : nullptr, c->d_spec, c->d_tw, (int32_t *)c->d_buf[2], (long)count);
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[3].as<void>(), key_share, 1024 * 4, hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[0].as<void>(), tlwe_a, bytes, hipMemcpyHostToDevice, c->stream));
+    if (noise) THFHE_HIP(hipMemcpyAsync(c->d_buf[1].as<void>(), noise, bytes, hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemsetAsync(c->d_flag.as<int>(), 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(share_transform_kernel, dim3(1), dim3(64), 0, c->stream, c->d_buf[3].as<int32_t>(), c->d_tw.as<cplx>(), c->d_spec.as<cplx>(), c->d_flag.as<int>());
+    hipLaunchKernelGGL(partial_decrypt_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, c->stream, c->d_buf[0].as<int32_t>(),
+                       noise ? c->d_buf[1].as<int32_t>() : nullptr, c->d_spec.as<cplx>(), c->d_tw.as<cplx>(), c->d_buf[2].as<int32_t>(), (long)count);
     THFHE_HIP(hipGetLastError());
     int flag = 0;
-    THFHE_HIP(hipMemcpyAsync(&flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipMemcpyAsync(partial, c->d_buf[2], bytes, hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(&flag, c->d_flag.as<int>(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(partial, c->d_buf[2].as<void>(), bytes, hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     if (flag) return thfhe_fail(THFHE_E_UNSUPPORTED, "key-share coefficients must satisfy |s| <= 512 (FP64 exactness bound)");
     return THFHE_OK;
@@ -222,21 +188,21 @@ int thfhe_partial_decrypt(thfhe_poly_ctx *c, const int32_t *key_share, const int
 int thfhe_final_decrypt(thfhe_poly_ctx *c, const int32_t *tlwe_b, const int32_t *partials, int t, int32_t *result, int32_t *bits, size_t count) {
     if (!c || !tlwe_b || !partials || !bits || t < 1) return thfhe_fail(THFHE_E_INVALID, "bad argument");
     if (count == 0) return THFHE_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    THFHE_HIP(hipSetDevice(c->device));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
     const size_t bytes = count * 1024 * 4;
-    int rc = ensure(c, 0, bytes);
-    if (!rc) rc = ensure(c, 1, bytes * t);
-    if (!rc) rc = ensure(c, 2, bytes);
-    if (!rc) rc = ensure(c, 3, count * 4 > 4096 ? count * 4 : 4096);
+    int rc = c->d_buf[0].grow(bytes);
+    if (!rc) rc = c->d_buf[1].grow(bytes * t);
+    if (!rc) rc = c->d_buf[2].grow(bytes);
+    if (!rc) rc = c->d_buf[3].grow(count * 4 > 4096 ? count * 4 : 4096);
     if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_buf[0], tlwe_b, bytes, hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_buf[1], partials, bytes * t, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(final_decrypt_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, (const int32_t *)c->d_buf[0], (const int32_t *)c->d_buf[1], t,
-                       (long)count, result ? (int32_t *)c->d_buf[2] : nullptr, (int32_t *)c->d_buf[3]);
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[0].as<void>(), tlwe_b, bytes, hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[1].as<void>(), partials, bytes * t, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(final_decrypt_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, c->d_buf[0].as<int32_t>(), c->d_buf[1].as<int32_t>(), t,
+                       (long)count, result ? c->d_buf[2].as<int32_t>() : nullptr, c->d_buf[3].as<int32_t>());
     THFHE_HIP(hipGetLastError());
-    if (result) THFHE_HIP(hipMemcpyAsync(result, c->d_buf[2], bytes, hipMemcpyDeviceToHost, c->stream));
-    THFHE_HIP(hipMemcpyAsync(bits, c->d_buf[3], count * 4, hipMemcpyDeviceToHost, c->stream));
+    if (result) THFHE_HIP(hipMemcpyAsync(result, c->d_buf[2].as<void>(), bytes, hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(bits, c->d_buf[3].as<void>(), count * 4, hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }

@@ -300,27 +300,134 @@ class DeviceBuffer:
             self.ptr = None
 
 
-def _dag_run_batch(fn, h, words, input_records, gates, out_wires):
-    """Shared body of CloudKey.dag_run_batch / MKCloudKey.dag_run_batch."""
-    x = np.ascontiguousarray(input_records, np.int32)
-    if x.ndim != 3 or x.shape[2] != words:
-        raise ValueError("dag_run_batch: input records must be int32[instances][n_inputs][%d]" % words)
-    g = np.ascontiguousarray(gates, np.int32).reshape(-1, 4)
-    q, n_in = x.shape[0], x.shape[1]
-    sel = None if out_wires is None else np.ascontiguousarray(out_wires, np.int32).reshape(-1)
-    out = np.zeros((q, g.shape[0] if sel is None else sel.shape[0], words), np.int32)
-    st = np.zeros(4, np.int64)
-    _check(fn(h, _p32(x), n_in, _p32(g), g.shape[0], q, _p32(sel), 0 if sel is None else sel.shape[0], _p32(out), st.ctypes.data_as(_i64p)))
-    return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
+class _Handle:
+    """Owner of one native context handle: close() destroys it once; garbage collection closes it too."""
+
+    h = None
+    _destroy = None
+
+    def _own(self, h, destroy):
+        self.h, self._destroy = h, destroy
+
+    def close(self):
+        h, self.h = self.h, None
+        if h and self._destroy is not None:
+            self._destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter teardown
+            pass
 
 
+class _EvalKey(_Handle):
+    """What CloudKey and MKCloudKey share: the same calls under the C symbol prefix `_prefix` (thfhe_ / thfhe_mk_)."""
 
-class CloudKey:
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(lib(), self._prefix + name)
+
+    # -- host-buffer calls -------------------------------------------------------------------------
+    def gates(self, op, x, y=None, z=None):
+        x = _rec(x, self.words)
+        y = _rec(y, self.words) if y is not None else None
+        z = _rec(z, self.words) if z is not None else None
+        _same_count(x, y, z)
+        out = np.empty_like(x)
+        _check(self._fn("gates")(self.h, op, _p32(x), _p32(y), _p32(z), _p32(out), x.shape[0]))
+        return out
+
+    def gates_mixed(self, ops, x, y):
+        """One launch for a DAG level: gate g applies ops[g] (a two-input bootstrapped gate) to (x[g], y[g])."""
+        x, y = _rec(x, self.words), _rec(y, self.words)
+        ops = np.ascontiguousarray(ops, np.int32)
+        _same_count(x, y, ops)
+        out = np.empty_like(x)
+        _check(self._fn("gates_mixed")(self.h, _p32(ops), _p32(x), _p32(y), _p32(out), x.shape[0]))
+        return out
+
+    def dag_run(self, input_records, gates):
+        """Native levelising scheduler + device-resident executor.  gates: int32[n_gates][4] = (op, in0, in1, in2).
+        Returns (wires int32[n_inputs + n_gates][words], stats dict)."""
+        x = _rec(input_records, self.words)
+        g = np.ascontiguousarray(gates, np.int32).reshape(-1, 4)
+        wires = np.zeros((x.shape[0] + g.shape[0], self.words), np.int32)
+        wires[:x.shape[0]] = x
+        st = np.zeros(4, np.int64)
+        _check(self._fn("dag_run")(self.h, _p32(wires), x.shape[0], _p32(g), g.shape[0], st.ctypes.data_as(_i64p)))
+        return wires, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]), widest_level=int(st[3]))
+
+    def dag_run_batch(self, input_records, gates, out_wires=None):
+        """`instances` evaluations of one gate list side by side (the reference's loop over test records,
+        src/KNN_medical_data.cpp:676-691).  input_records: int32[instances][n_inputs][words]; out_wires: wire ids to return (None = every
+        gate wire).  Returns (int32[instances][len(out_wires) or n_gates][words], stats)."""
+        words = self.words
+        x = np.ascontiguousarray(input_records, np.int32)
+        if x.ndim != 3 or x.shape[2] != words:
+            raise ValueError("dag_run_batch: input records must be int32[instances][n_inputs][%d]" % words)
+        g = np.ascontiguousarray(gates, np.int32).reshape(-1, 4)
+        q, n_in = x.shape[0], x.shape[1]
+        sel = None if out_wires is None else np.ascontiguousarray(out_wires, np.int32).reshape(-1)
+        out = np.zeros((q, g.shape[0] if sel is None else sel.shape[0], words), np.int32)
+        st = np.zeros(4, np.int64)
+        _check(self._fn("dag_run_batch")(self.h, _p32(x), n_in, _p32(g), g.shape[0], q, _p32(sel), 0 if sel is None else sel.shape[0], _p32(out),
+                                         st.ctypes.data_as(_i64p)))
+        return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
+
+    def _bootstrap(self, x, mu):
+        x = _rec(x, self.words)
+        out = np.empty_like(x)
+        _check(self._fn("bootstrap")(self.h, mu, _p32(x), _p32(out), x.shape[0]))
+        return out
+
+    # -- device-buffer calls -----------------------------------------------------------------------
+    def _alloc(self, n):
+        return self._fn("dev_alloc")(self.h, n)
+
+    def _free(self, p):
+        self._fn("dev_free")(self.h, p)
+
+    def _h2d(self, dptr, arr):
+        _check(self._fn("copy_h2d")(self.h, dptr, arr.ctypes.data_as(_vp), arr.nbytes))
+
+    def _d2h(self, arr, dptr):
+        _check(self._fn("copy_d2h")(self.h, arr.ctypes.data_as(_vp), dptr, arr.nbytes))
+
+    def device_records(self, count):
+        return DeviceBuffer(self, count * self.words * 4)
+
+    def reserve(self, max_count):
+        _check(self._fn("reserve")(self.h, max_count))
+
+    def gates_dev(self, op, dx, dy, dz, dout, count):
+        _check(self._fn("gates_dev")(self.h, op, dx.ptr, dy.ptr if dy else None, dz.ptr if dz else None, dout.ptr, count))
+
+    def sync(self):
+        _check(self._fn("sync")(self.h))
+
+    def set_dag_slice(self, max_gates):
+        """Gates per launch of a DAG level (dag_run_batch cuts wider levels into slices)."""
+        _check(self._fn("set_dag_slice")(self.h, int(max_gates)))
+
+    def set_profiling(self, on):
+        _check(self._fn("set_profiling")(self.h, int(bool(on))))
+
+    def last_timings(self):
+        ms = (C.c_float * 4)()
+        _check(self._fn("last_timings")(self.h, ms))
+        return dict(prologue_ms=ms[0], blind_rotate_ms=ms[1], keyswitch_ms=ms[2], total_ms=ms[3])
+
+
+class CloudKey(_EvalKey):
     """Single-key evaluation context = the reference's CloudKey (api.jl:215-231): bootstrap key + keyswitch key,
     held on one MI355X in the engine's transformed layout.
 
     bk_coeff: int32[n][(k+1)l][k+1][N] coefficient-domain TGSW rows; ksk: int32[N][t][base-1][n+1].
     """
+
+    _prefix = "thfhe_"
 
     def __init__(self, params, bk_coeff, ksk, device=0):
         self.params = params
@@ -333,61 +440,11 @@ class CloudKey:
             raise ValueError("ksk has the wrong size for these parameters")
         h = _vp()
         _check(lib().thfhe_ctx_create(C.byref(p), _p32(bk), _p32(ks), device, C.byref(h)))
-        self.h, self._destroy = h, lib().thfhe_ctx_destroy
+        self._own(h, lib().thfhe_ctx_destroy)
         self.words = p.n + 1
 
-    def close(self):
-        h, self.h = getattr(self, "h", None), None
-        if h and getattr(self, "_destroy", None) is not None:
-            self._destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter teardown
-            pass
-
-    # -- host-buffer calls -------------------------------------------------------------------------
-    def gates(self, op, x, y=None, z=None):
-        x = _rec(x, self.words)
-        y = _rec(y, self.words) if y is not None else None
-        z = _rec(z, self.words) if z is not None else None
-        _same_count(x, y, z)
-        out = np.empty_like(x)
-        _check(lib().thfhe_gates(self.h, op, _p32(x), _p32(y), _p32(z), _p32(out), x.shape[0]))
-        return out
-
-    def gates_mixed(self, ops, x, y):
-        """One launch for a DAG level: gate g applies ops[g] (two-input bootstrapped gates) to (x[g], y[g])."""
-        x, y = _rec(x, self.words), _rec(y, self.words)
-        ops = np.ascontiguousarray(ops, np.int32)
-        _same_count(x, y, ops)
-        out = np.empty_like(x)
-        _check(lib().thfhe_gates_mixed(self.h, _p32(ops), _p32(x), _p32(y), _p32(out), x.shape[0]))
-        return out
-
-    def dag_run(self, input_records, gates):
-        """Native levelising scheduler + device-resident executor.  gates: int32[n_gates][4] = (op, in0, in1, in2).
-        Returns (wires int32[n_inputs + n_gates][n+1], stats dict)."""
-        x = _rec(input_records, self.words)
-        g = np.ascontiguousarray(gates, np.int32).reshape(-1, 4)
-        wires = np.zeros((x.shape[0] + g.shape[0], self.words), np.int32)
-        wires[:x.shape[0]] = x
-        st = np.zeros(4, np.int64)
-        _check(lib().thfhe_dag_run(self.h, _p32(wires), x.shape[0], _p32(g), g.shape[0], st.ctypes.data_as(_i64p)))
-        return wires, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]), widest_level=int(st[3]))
-
-    def dag_run_batch(self, input_records, gates, out_wires=None):
-        """`instances` evaluations of one gate list side by side (thfhe_dag_run_batch; the reference's loop over test records,
-        src/KNN_medical_data.cpp:676-691).  input_records: int32[instances][n_inputs][n+1]; out_wires: wire ids to return (None = every gate
-        wire).  Returns (int32[instances][len(out_wires) or n_gates][n+1], stats)."""
-        return _dag_run_batch(lib().thfhe_dag_run_batch, self.h, self.words, input_records, gates, out_wires)
-
     def bootstrap(self, x, mu=MU8):
-        x = _rec(x, self.words)
-        out = np.empty_like(x)
-        _check(lib().thfhe_bootstrap(self.h, mu, _p32(x), _p32(out), x.shape[0]))
-        return out
+        return self._bootstrap(x, mu)
 
     def bootstrap_wo_keyswitch(self, x, mu=MU8):
         x = _rec(x, self.words)
@@ -400,35 +457,6 @@ class CloudKey:
         out = np.empty((u.shape[0], self.words), np.int32)
         _check(lib().thfhe_keyswitch(self.h, _p32(u), _p32(out), u.shape[0]))
         return out
-
-    # -- device-buffer calls -----------------------------------------------------------------------
-    def _alloc(self, n):
-        return lib().thfhe_dev_alloc(self.h, n)
-
-    def _free(self, p):
-        lib().thfhe_dev_free(self.h, p)
-
-    def _h2d(self, dptr, arr):
-        _check(lib().thfhe_copy_h2d(self.h, dptr, arr.ctypes.data_as(_vp), arr.nbytes))
-
-    def _d2h(self, arr, dptr):
-        _check(lib().thfhe_copy_d2h(self.h, arr.ctypes.data_as(_vp), dptr, arr.nbytes))
-
-    def device_records(self, count):
-        return DeviceBuffer(self, count * self.words * 4)
-
-    def reserve(self, max_count):
-        _check(lib().thfhe_reserve(self.h, max_count))
-
-    def gates_dev(self, op, dx, dy, dz, dout, count):
-        _check(lib().thfhe_gates_dev(self.h, op, dx.ptr, dy.ptr if dy else None, dz.ptr if dz else None, dout.ptr, count))
-
-    def sync(self):
-        _check(lib().thfhe_sync(self.h))
-
-    def set_dag_slice(self, max_gates):
-        """Gates per launch of a DAG level (dag_run_batch cuts wider levels into slices)."""
-        _check(lib().thfhe_set_dag_slice(self.h, int(max_gates)))
 
     def set_ring4_threshold(self, max_jobs):
         """Remainders (batch mod 2048) above the cooperative threshold and <= max_jobs rotations use the four-wave ring kernel; 0 disables it."""
@@ -450,14 +478,6 @@ class CloudKey:
         if r <= coop:
             return f"sk_blind_rotate_coop_kernel<{l}>"
         return f"sk_blind_rotate_ring_kernel<{l}, 4 waves>" if r <= ring4 + min(coop, 256) and ring4 else f"sk_blind_rotate_ring_kernel<{l}>"
-
-    def set_profiling(self, on):
-        _check(lib().thfhe_set_profiling(self.h, int(bool(on))))
-
-    def last_timings(self):
-        ms = (C.c_float * 4)()
-        _check(lib().thfhe_last_timings(self.h, ms))
-        return dict(prologue_ms=ms[0], blind_rotate_ms=ms[1], keyswitch_ms=ms[2], total_ms=ms[3])
 
 
 # ---- the reference's single-key gate API (gates.jl:15-177), batched over the leading axis -------------
@@ -488,13 +508,15 @@ def keyswitch(ck, u): return ck.keyswitch(u)                                    
 
 
 # ---- 3-gen multi-key -------------------------------------------------------------------------------------
-class MKCloudKey:
+class MKCloudKey(_EvalKey):
     """Evaluation context of the 3rd-generation multi-key scheme: the parties' TransformedBootstrapKeyPart_3gen
     (3gen_mk_internals.jl:45-56) and KeyswitchKey tables on one MI355X.
 
     bk_coeff: int64[P][n][4][l][N] (part_1..part_4 of every TGswSample_3gen, coefficient domain);
     ksk: int32[P][N][t][base-1][n+1].  Records are int32[P*n+1] = a[p*n+i], b (MKLweSample, mk_internals.jl:23-37).
     """
+
+    _prefix = "thfhe_mk_"
 
     def __init__(self, params, bk_coeff, ksk, device=0):
         self.params = p = params
@@ -506,87 +528,11 @@ class MKCloudKey:
             raise ValueError("ksk has the wrong size for these parameters")
         h = _vp()
         _check(lib().thfhe_mk_ctx_create(C.byref(p), bk.ctypes.data_as(_i64p), _p32(ks), device, C.byref(h)))
-        self.h, self._destroy = h, lib().thfhe_mk_ctx_destroy
+        self._own(h, lib().thfhe_mk_ctx_destroy)
         self.words = p.parties * p.n + 1
 
-    def close(self):
-        h, self.h = getattr(self, "h", None), None
-        if h and getattr(self, "_destroy", None) is not None:
-            self._destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def gates(self, op, x, y=None, z=None):
-        x = _rec(x, self.words)
-        y = _rec(y, self.words) if y is not None else None
-        z = _rec(z, self.words) if z is not None else None
-        _same_count(x, y, z)
-        out = np.empty_like(x)
-        _check(lib().thfhe_mk_gates(self.h, op, _p32(x), _p32(y), _p32(z), _p32(out), x.shape[0]))
-        return out
-
-    def gates_mixed(self, ops, x, y):
-        """One launch for a DAG level of two-input 3-gen gates with per-gate opcodes."""
-        x, y = _rec(x, self.words), _rec(y, self.words)
-        ops = np.ascontiguousarray(ops, np.int32)
-        _same_count(x, y, ops)
-        out = np.empty_like(x)
-        _check(lib().thfhe_mk_gates_mixed(self.h, _p32(ops), _p32(x), _p32(y), _p32(out), x.shape[0]))
-        return out
-
-    def dag_run(self, input_records, gates):
-        """Native levelising scheduler + device-resident executor for 3-gen circuits (thfhe_mk_dag_run)."""
-        x = _rec(input_records, self.words)
-        g = np.ascontiguousarray(gates, np.int32).reshape(-1, 4)
-        wires = np.zeros((x.shape[0] + g.shape[0], self.words), np.int32)
-        wires[:x.shape[0]] = x
-        st = np.zeros(4, np.int64)
-        _check(lib().thfhe_mk_dag_run(self.h, _p32(wires), x.shape[0], _p32(g), g.shape[0], st.ctypes.data_as(_i64p)))
-        return wires, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]), widest_level=int(st[3]))
-
-    def dag_run_batch(self, input_records, gates, out_wires=None):
-        """`instances` evaluations of one 3-gen gate list side by side (thfhe_mk_dag_run_batch)."""
-        return _dag_run_batch(lib().thfhe_mk_dag_run_batch, self.h, self.words, input_records, gates, out_wires)
-
     def bootstrap(self, x, mu=MU8_64):
-        x = _rec(x, self.words)
-        out = np.empty_like(x)
-        _check(lib().thfhe_mk_bootstrap(self.h, mu, _p32(x), _p32(out), x.shape[0]))
-        return out
-
-    def _alloc(self, n):
-        return lib().thfhe_mk_dev_alloc(self.h, n)
-
-    def _free(self, p):
-        lib().thfhe_mk_dev_free(self.h, p)
-
-    def _h2d(self, dptr, arr):
-        _check(lib().thfhe_mk_copy_h2d(self.h, dptr, arr.ctypes.data_as(_vp), arr.nbytes))
-
-    def _d2h(self, arr, dptr):
-        _check(lib().thfhe_mk_copy_d2h(self.h, arr.ctypes.data_as(_vp), dptr, arr.nbytes))
-
-    def device_records(self, count):
-        return DeviceBuffer(self, count * self.words * 4)
-
-    def reserve(self, max_count):
-        _check(lib().thfhe_mk_reserve(self.h, max_count))
-
-    def gates_dev(self, op, dx, dy, dz, dout, count):
-        _check(lib().thfhe_mk_gates_dev(self.h, op, dx.ptr, dy.ptr if dy else None, dz.ptr if dz else None, dout.ptr, count))
-
-    def sync(self):
-        _check(lib().thfhe_mk_sync(self.h))
-
-    def set_profiling(self, on):
-        _check(lib().thfhe_mk_set_profiling(self.h, int(bool(on))))
-
-    def set_dag_slice(self, max_gates):
-        _check(lib().thfhe_mk_set_dag_slice(self.h, int(max_gates)))
+        return self._bootstrap(x, mu)
 
     def set_pair_threshold(self, max_single_jobs):
         """Batches of <= max_single_jobs rotations run one gate per workgroup; larger ones two gates per workgroup."""
@@ -607,30 +553,15 @@ class MKCloudKey:
         pair = p.l <= 3 and rotations > getattr(self, "_pair_threshold", 256)
         return f"mk_blind_rotate_{'pair' if pair else 'coop'}_kernel<{p.l}>"
 
-    def last_timings(self):
-        ms = (C.c_float * 4)()
-        _check(lib().thfhe_mk_last_timings(self.h, ms))
-        return dict(prologue_ms=ms[0], blind_rotate_ms=ms[1], keyswitch_ms=ms[2], total_ms=ms[3])
 
-
-class PolyMac:
+class PolyMac(_Handle):
     """Device engine for the key-generation products (thfhe_pm_mac): out[j] = addend[j] + sum_terms sign * small[s] (*) torus[t], exact."""
 
     def __init__(self, N, torus_bits, device=0):
         h = _vp()
         _check(lib().thfhe_pm_ctx_create(device, N, torus_bits, C.byref(h)))
-        self.h, self._destroy, self.N, self.dtype = h, lib().thfhe_pm_ctx_destroy, N, (np.int32 if torus_bits == 32 else np.int64)
-
-    def close(self):
-        h, self.h = getattr(self, "h", None), None
-        if h and getattr(self, "_destroy", None) is not None:
-            self._destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._own(h, lib().thfhe_pm_ctx_destroy)
+        self.N, self.dtype = N, (np.int32 if torus_bits == 32 else np.int64)
 
     def mac(self, small, torus, terms, n_out, addend=None):
         small = np.ascontiguousarray(small, np.int32).reshape(-1, self.N)
@@ -644,7 +575,7 @@ class PolyMac:
         return out
 
 
-class CCSCloudKey:
+class CCSCloudKey(_Handle):
     """MKCloudKey of the CCS scheme (mk_api.jl:392-408): MKBootstrapKey (uni-encrypted key bits, public keys, shared key) and the
     parties' KeyswitchKeys on one MI355X.  bk int32[P][n][3][l][N] (d1, f0, f1), pk int32[P][l][N], crs int32[l][N], ksk as MKCloudKey."""
 
@@ -656,19 +587,8 @@ class CCSCloudKey:
             raise ValueError("key table has the wrong size for these parameters")
         h = _vp()
         _check(lib().thfhe_ccs_ctx_create(C.byref(p), *[_p32(a) for a in arrs], device, C.byref(h)))
-        self.h, self._destroy = h, lib().thfhe_ccs_ctx_destroy
+        self._own(h, lib().thfhe_ccs_ctx_destroy)
         self.words = p.parties * p.n + 1
-
-    def close(self):
-        h, self.h = getattr(self, "h", None), None
-        if h and getattr(self, "_destroy", None) is not None:
-            self._destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def gates(self, op, x, y):
         x, y = _rec(x, self.words), _rec(y, self.words)

@@ -14,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import MU8_64, NAND, ThfheError, _check, _i64p, _p32, _rec, _same_count, _vp, lib
+from . import MU8_64, NAND, ThfheError, _check, _Handle, _i64p, _p32, _rec, _same_count, _vp, lib
 
 _TWO_INPUT = range(10)   # opcodes NAND .. ORYN (gates.jl:15-161)
 
@@ -33,7 +33,7 @@ def modswitch(x, N):
     return (y >> (32 - lg)).astype(np.int32)
 
 
-class KMSCloudKey:
+class KMSCloudKey(_Handle):
     """MKCloudKey_new (mk_api.jl:440-455): the parties' TGSW bootstrapping keys, key-switch keys, uni-encryptions, public keys and the
     shared key on one MI355X (all as limb spectra).  Tables as produced by thfhe.keygen.KMSSecretKeySet."""
 
@@ -50,20 +50,9 @@ class KMSCloudKey:
             raise ValueError("uni / pk / crs have the wrong size for these parameters")
         h = _vp()
         _check(lib().thfhe_kms_ctx_create(C.byref(p), gsw.ctypes.data_as(_i64p), _p32(ksk), device, C.byref(h)))
-        self.h, self._destroy = h, lib().thfhe_kms_ctx_destroy
+        self._own(h, lib().thfhe_kms_ctx_destroy)
         _check(lib().thfhe_kms_set_relin_keys(h, uni.ctypes.data_as(_i64p), pk.ctypes.data_as(_i64p), crs.ctypes.data_as(_i64p)))
         self.words = p.parties * p.n + 1
-
-    def close(self):
-        h, self.h = getattr(self, "h", None), None
-        if h and getattr(self, "_destroy", None) is not None:
-            self._destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_pair_threshold(self, max_single_jobs):
         """Launches of <= max_single_jobs rotations run one job per workgroup; larger ones two jobs per workgroup (shared key chunks)."""

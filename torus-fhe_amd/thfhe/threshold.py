@@ -5,28 +5,17 @@ import ctypes as C
 
 import numpy as np
 
-from . import ThfheError, _check, _p32, _vp, lib
+from . import ThfheError, _check, _Handle, _p32, _vp, lib
 
 
-class PolyContext:
+class PolyContext(_Handle):
     """Device context for the ring operations (N = 1024, k = 1)."""
 
     def __init__(self, device=0, N=1024):
         self.N = N
         h = _vp()
         _check(lib().thfhe_poly_ctx_create(device, N, C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().thfhe_poly_ctx_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._own(h, lib().thfhe_poly_ctx_destroy)
 
 
 def TLweFromLwe(ctx, cipher):
