@@ -122,9 +122,9 @@ struct WaveQS {  // multi-key kernels: first transpose in registers, second thro
 
 extern "C" {
 
-// coefficient-domain key polynomials -> spectral layout [poly][limb][m][lane], scaled by 1/512
+// coefficient-domain key polynomials -> spectral layout [poly][limb][m][lane], scaled by 1/512, in the swizzled form of torus_transform_kernel
 void emu_transform_key_polys(const int32_t *polys, int64_t npolys, double *spec /* npolys*2*512*2 doubles */) {
-    Wave w;
+    WaveS w;
     static cplx zlo[64][8], zhi[64][8];
     for (int64_t q = 0; q < npolys; q++) {
         for (int l = 0; l < 64; l++) key_limbs_to_z(l, polys + q * 1024, zlo[l], zhi[l]);
@@ -275,7 +275,7 @@ double emu_variant_crosscheck(const int32_t *small, const int32_t *b, int32_t *o
     Wave w;
     WaveS ws;
     std::vector<double> spec(2 * 512 * 2);
-    emu_transform_key_polys(b, 1, spec.data());   // key transformed by the padded variant
+    emu_transform_key_polys(b, 1, spec.data());   // key transformed by the swizzled variant (as torus_transform_kernel does)
     const cplx *B = reinterpret_cast<const cplx *>(spec.data());
     static cplx z[64][8], z2[64][8], slo[64][8], shi[64][8];
     for (int l = 0; l < 64; l++)
@@ -310,7 +310,7 @@ static double variant_crosscheck(const int32_t *small, const int32_t *b, int32_t
     Wave w;
     WV wr;
     std::vector<double> spec(2 * 512 * 2);
-    emu_transform_key_polys(b, 1, spec.data());   // key transformed by the table variant (as sk_key_transform_kernel does)
+    emu_transform_key_polys(b, 1, spec.data());   // key transformed by the swizzled variant (as torus_transform_kernel does)
     const cplx *B = reinterpret_cast<const cplx *>(spec.data());
     static cplx z[64][8], z2[64][8], slo[64][8], shi[64][8];
     for (int l = 0; l < 64; l++)
@@ -423,12 +423,12 @@ void emu_mk_extract(const int64_t *acc, int32_t *out) {
 // ---- N = 2048: radix-2 split + two twisted 512-point transforms (thfhe_lane.h, "N = 2048" section) ---------------------------
 namespace {
 struct Wave2K {
-    cplx T1a[512], T1b[512], T2[64], scratch[512];
+    cplx T1a[512], T1b[512], T2[64];
     cplx xbuf[512];
     W64 w[64];
     Wave2K() {
         make_twiddles_2048(T1a, T1b);
-        make_twiddles_1024(scratch, T2);
+        make_twiddles_t2(T2);
         for (int l = 0; l < 64; l++) w[l] = W64{T2[1 * 8 + (l & 7)]};
     }
     template <int T>
@@ -551,12 +551,12 @@ void emu_mk_extract_2k(const int64_t *acc, int32_t *out) {
 // ---- table-free twisted transforms ("tq" form: N = 2048 two-gate kernels) and the ring of degree 4096 (four twisted quarters) -----------
 namespace {
 struct WaveTQ {
-    cplx T1a[512], T1b[512], T2[64], scratch[512], ratio[64], roots4k[256];
+    cplx T1a[512], T1b[512], T2[64], ratio[64], roots4k[256];
     cplx xbuf[512];
     W64 w[64];
     WaveTQ() {
         make_twiddles_2048(T1a, T1b);
-        make_twiddles_1024(scratch, T2);
+        make_twiddles_t2(T2);
         make_lane_ratio_2048(ratio);
         make_lane_roots_4096(roots4k);
         for (int l = 0; l < 64; l++) w[l] = W64{T2[1 * 8 + (l & 7)]};

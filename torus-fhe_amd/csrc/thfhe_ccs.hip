@@ -36,28 +36,7 @@ namespace {
 
 constexpr int kCcsMaxParties = 8;
 
-// coefficient-domain Torus32 polynomials -> two-limb spectra [poly][limb][slot m][lane], scaled by 1/512
-__global__ __launch_bounds__(256) void ccs_key_transform_kernel(const int32_t *__restrict__ polys, long npolys, const cplx *__restrict__ tw,
-                                                                 cplx *__restrict__ spec) {
-    __shared__ cplx sT1[512];
-    __shared__ cplx sX[4][512];
-    for (int t = threadIdx.x; t < 512; t += 256) sT1[t] = tw[t];
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const W64 w64{tw[512 + 1 * 8 + (lane & 7)]};
-    const long q = (long)blockIdx.x * 4 + wave;
-    if (q >= npolys) return;
-    cplx zlo[8], zhi[8];
-    key_limbs_to_z(lane, polys + q * 1024, zlo, zhi);
-    wave_fft_fwd_s(lane, zlo, sX[wave], sT1, w64);
-    wave_fft_fwd_s(lane, zhi, sX[wave], sT1, w64);
-    cplx *dst = spec + q * 1024;
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-        dst[m * 64 + lane] = cplx{zlo[m].re * (1.0 / 512), zlo[m].im * (1.0 / 512)};
-        dst[512 + m * 64 + lane] = cplx{zhi[m].re * (1.0 / 512), zhi[m].im * (1.0 / 512)};
-    }
-}
+#include "thfhe_transform.h"
 
 struct CCSArgs {
     const cplx *bk;   // [(party*n + j)][3: d, f0, f1][l][limb][512]
@@ -89,7 +68,7 @@ __global__ __launch_bounds__(512, 2) void ccs_blind_rotate_kernel(CCSArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     sT1[threadIdx.x] = a.tw[threadIdx.x];
-    const W64 w64{a.tw[512 + 1 * 8 + (lane & 7)]};
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
     const long job = blockIdx.x;
     const int P = a.parties, L = a.l, Bgbit = a.Bgbit;
     const int G = 8 / L < 4 ? 8 / L : 4;  // polynomial groups per batch: G*L <= 8 forward transforms, 4*G <= 16 stage-1 output tasks
@@ -224,7 +203,7 @@ __global__ __launch_bounds__(512, 2) void ccs_blind_rotate_wide_kernel(CCSArgs a
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     sT1[threadIdx.x] = a.tw[threadIdx.x];
-    const W64 w64{a.tw[512 + 1 * 8 + (lane & 7)]};
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
     const long job = blockIdx.x;
     const int P = a.parties, L = a.l, Bgbit = a.Bgbit;
     const uniform_i32_ptr bara = as_uniform(a.bara + job * a.w_pad);
@@ -344,7 +323,7 @@ __global__ __launch_bounds__(512, 2) void ccs_blind_rotate_wide_kernel(CCSArgs a
 
 struct THFHE_INTERNAL thfhe_ccs_ctx : DevCtx {
     thfhe_params p;
-    DevBuf d_bk, d_pk, d_crs, d_tw;
+    DevBuf d_bk, d_pk, d_crs;
     DevBuf d_ksk;
     int row_words = 0, w_pad = 0, words = 0;
     DevBuf d_bara, d_barb, d_u, d_in[2], d_out;
@@ -415,10 +394,7 @@ int thfhe_ccs_ctx_create(const thfhe_params *p, const int32_t *bk, const int32_t
     c->words = p->parties * p->n;
     c->w_pad = (c->words + 3) & ~3;
     c->row_words = 128 * ((p->n + 1 + 127) / 128);
-    std::vector<cplx> tw(576);
-    make_twiddles_1024(tw.data(), tw.data() + 512);
-    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
-    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->upload_twiddles(1024));
     struct Tab { const int32_t *src; long npolys; DevBuf *dst; };
     const Tab tabs[3] = {{bk, (long)p->parties * p->n * 3 * p->l, &c->d_bk}, {pk, (long)p->parties * p->l, &c->d_pk}, {crs, (long)p->l, &c->d_crs}};
     for (const Tab &t : tabs) {
@@ -426,8 +402,7 @@ int thfhe_ccs_ctx_create(const thfhe_params *p, const int32_t *bk, const int32_t
         THFHE_TRY(coeff.grow((size_t)t.npolys * 1024 * sizeof(int32_t)));
         THFHE_HIP(hipMemcpyAsync(coeff.as<int32_t>(), t.src, (size_t)t.npolys * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         THFHE_TRY(t.dst->grow((size_t)t.npolys * 1024 * sizeof(cplx)));
-        hipLaunchKernelGGL(ccs_key_transform_kernel, dim3((unsigned)((t.npolys + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int32_t>(), t.npolys, c->d_tw.as<cplx>(), t.dst->as<cplx>());
-        THFHE_HIP(hipGetLastError());
+        THFHE_TRY((launch_torus_transform<1024, 32>(c->stream, coeff.as<int32_t>(), t.npolys, c->d_tw.as<cplx>(), t.dst->as<cplx>())));
         THFHE_HIP(hipStreamSynchronize(c->stream));
     }
     const long rows = (long)p->parties * 1024 * p->ks_t * ((1 << p->ks_basebit) - 1);

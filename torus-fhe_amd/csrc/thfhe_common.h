@@ -67,25 +67,6 @@ __device__ __forceinline__ int opaque_lane(int lane) {
     asm volatile("" : "+v"(lane));
     return lane;
 }
-// forward / inverse folded negacyclic transform of the 8 points each lane holds (see thfhe_lane.h)
-__device__ __forceinline__ void wave_fft_fwd(int lane, cplx (&z)[8], cplx *xb, const cplx *T1, const cplx *T2) {
-    wave_sync();
-    fwd_seg1(lane, z, xb, T1);
-    wave_sync();
-    fwd_seg2_ld(lane, z, xb);
-    fwd_seg2_st(lane, z, xb, T2);
-    wave_sync();
-    fwd_seg3(lane, z, xb);
-}
-__device__ __forceinline__ void wave_fft_inv(int lane, cplx (&z)[8], cplx *xb, const cplx *T1, const cplx *T2) {
-    wave_sync();
-    inv_seg1(lane, z, xb, T2);
-    wave_sync();
-    inv_seg2_ld(lane, z, xb);
-    inv_seg2_st(lane, z, xb);
-    wave_sync();
-    inv_seg3(lane, z, xb, T1);
-}
 // Wave-uniform words that no kernel of the launch writes (the mod-switched mask words a rotation walks: written by the prologue kernel before it):
 // read through the constant address space, i.e. with s_load_dword into an SGPR.  As plain global loads they were global_load_dword + s_waitcnt vmcnt(0)
 // at the top of every CMux -- a vector-memory round trip on the sequential chain, and a vmcnt(0) that also waits for whatever the wave has in flight.

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <mutex>
+#include <vector>
 
 #include "thfhe_common.h"
 
@@ -74,8 +75,9 @@ struct Stage {
     int32_t *out_ptr() const { return out.as<int32_t>(); }
 };
 
-// What every engine context holds: its device, its stream (created non-blocking by open()), the profiling events and the mutex that
-// serialises calls on the context.  `stream` is where calls enqueue; it differs from `own_stream` only after an engine's set_stream.
+// What every engine context holds: its device, its stream (created non-blocking by open()), the profiling events, the mutex that
+// serialises calls on the context and the twiddle table of its ring degree.  `stream` is where calls enqueue; it differs from
+// `own_stream` only after an engine's set_stream.
 struct DevCtx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -83,6 +85,7 @@ struct DevCtx {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool profiling = false, ev_valid = false;
     std::mutex mu;
+    DevBuf d_tw;   // make_twiddle_table(N) (thfhe_lane.h), filled by upload_twiddles
 
     DevCtx() = default;
     DevCtx(const DevCtx &) = delete;
@@ -102,6 +105,14 @@ struct DevCtx {
         stream = own_stream;
         if (with_events)
             for (hipEvent_t &e : ev) THFHE_HIP(hipEventCreate(&e));
+        return THFHE_OK;
+    }
+    // build the twiddle table of ring degree N and copy it to d_tw; returns when the copy is done
+    int upload_twiddles(int N) {
+        const std::vector<cplx> tw = make_twiddle_table(N);
+        THFHE_TRY(d_tw.grow(tw.size() * sizeof(cplx)));
+        THFHE_HIP(hipMemcpyAsync(d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, stream));
+        THFHE_HIP(hipStreamSynchronize(stream));
         return THFHE_OK;
     }
 };

@@ -39,6 +39,7 @@ THFHE_STAMP_STORAGE
 
 #include "thfhe_rot2k.h"
 
+#include "thfhe_transform.h"
 #include "thfhe_pm_kernels.h"
 
 // ---- device-resident mk_bootstrap_new: everything between the gate's linear part and the key switch stays in HBM -----------------
@@ -121,7 +122,6 @@ __global__ __launch_bounds__(256) void kms_rlwe_split_kernel(const int64_t *__re
 
 struct THFHE_INTERNAL thfhe_kms_ctx : DevCtx {
     thfhe_kms_params p;
-    DevBuf d_tw;
     DevBuf park;                 // two jobs per workgroup: partial spectra between row-part batches (thfhe_rot2k.h)
     long pair_threshold = 256;   // launches of more TLev / RLWE rotations than this (one per CU) run two jobs per workgroup
     DevBuf d_bk;                 // [party][j][row part][o][h][half][512]
@@ -171,36 +171,14 @@ int thfhe_kms_ctx_create(const thfhe_kms_params *p, const int64_t *gsw, const in
     const int part_bits = c->parts == 2 ? c->lo_bits : p->bg_gsw;
     if (sum_bound(c->parts, part_bits) > 137438953472.0 /* 2^37 */)
         return thfhe_fail(THFHE_E_UNSUPPORTED, "gsw gadget outside the FP64 exactness bound of the N = 2048 transform");
-    DevBuf coeff, raw;  // upload staging
-    std::vector<cplx> tw(1216 + 64), unused(512);   // T1 (twist 1), T1 (twist 5), T2; [1216..): pass-1 ratio of the table-free transforms
-    make_lane_ratio_2048(tw.data() + 1216);
-    make_twiddles_2048(tw.data(), tw.data() + 512);
-    make_twiddles_1024(unused.data(), tw.data() + 1024);
-    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
-    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->upload_twiddles(N));
     // key table: per party and key bit the 2 l rows x 2 columns of the TGSW sample; with two-part digits every row is followed by its copy
     // shifted left by lo_bits (wrapping): d (*) K = d_lo (*) K + d_hi (*) (K << lo_bits)
-    const size_t polys_per_party = (size_t)p->n * RP * 2;
-    c->party_stride = polys_per_party * 4 * 1024;
-    THFHE_TRY(c->d_bk.grow((size_t)p->parties * c->party_stride * sizeof(cplx)));
-    THFHE_TRY(coeff.grow(polys_per_party * N * sizeof(int64_t)));
-    std::vector<int64_t> host(polys_per_party * N);
-    for (int q = 0; q < p->parties; q++) {
-        for (int j = 0; j < p->n; j++)
-            for (int r = 0; r < 2 * p->l_gsw; r++)
-                for (int part = 0; part < c->parts; part++)
-                    for (int col = 0; col < 2; col++) {
-                        const int64_t *src = gsw + ((((size_t)q * p->n + j) * 2 * p->l_gsw + r) * 2 + col) * N;
-                        int64_t *dst = host.data() + ((((size_t)j * RP + (size_t)r * c->parts + part) * 2) + col) * N;
-                        const int sh = part * c->lo_bits;
-                        for (int t = 0; t < N; t++) dst[t] = (int64_t)((uint64_t)src[t] << sh);
-                    }
-        THFHE_HIP(hipMemcpyAsync(coeff.as<int64_t>(), host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(kms_key_transform_kernel, dim3((unsigned)((polys_per_party * 4 + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int64_t>(), (long)polys_per_party,
-                           c->d_tw.as<cplx>(), c->d_bk.as<cplx>() + (size_t)q * c->party_stride);
-        THFHE_HIP(hipGetLastError());
-        THFHE_HIP(hipStreamSynchronize(c->stream));   // `host` is reused for the next party
-    }
+    c->party_stride = (size_t)p->n * RP * 2 * 4 * 1024;
+    THFHE_TRY(stage_party_keys<N>(*c, c->d_bk, p->parties, p->n, 2 * p->l_gsw, c->parts, c->lo_bits, [&](int q, int j, int r, int col) {
+        return gsw + ((((size_t)q * p->n + j) * 2 * p->l_gsw + r) * 2 + col) * N;
+    }));
+    DevBuf raw;  // upload staging
     const long rows = (long)p->parties * N * p->ks_t * ((1 << p->ks_basebit) - 1);
     THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));
     THFHE_HIP(hipMemcpyAsync(raw.as<int32_t>(), ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
@@ -416,9 +394,7 @@ int kms_lev_rlwe_mul_dev(thfhe_kms_ctx *c, KmsTables &tabs, int party, size_t G,
     if (!rc) rc = c->d_w[K::W_LEVSPEC].grow(G * lv * 2 * 4 * 1024 * sizeof(cplx));
     if (!rc) rc = c->d_w[K::W_EF].grow(2 * G * ns * N * 8);
     if (rc) return rc;
-    hipLaunchKernelGGL((pm_torus_transform_kernel<2048, 64>), dim3((unsigned)((G * lv * 2 * 4 + 3) / 4)), dim3(256), 0, c->stream, (const void *)d_lev,
-                       (long)(G * lv * 2), c->d_tw.as<cplx>(), c->d_w[K::W_LEVSPEC].as<cplx>());
-    THFHE_HIP(hipGetLastError());
+    THFHE_TRY((launch_torus_transform<2048, 64>(c->stream, d_lev, (long)(G * lv * 2), c->d_tw.as<cplx>(), c->d_w[K::W_LEVSPEC].as<cplx>())));
     rc = kms_mac(c, tabs, kms_key(6, party, G, 0), c->d_w[K::W_SMALL].as<int32_t>(), c->d_w[K::W_LEVSPEC].as<cplx>(), [&](std::vector<int32_t> &t1) {
         for (int w = 0; w < 2; w++)   // e block (w = 0: masks of the TLev samples), then f block (w = 1: bodies)
             for (size_t g = 0; g < G; g++)
@@ -544,9 +520,7 @@ int thfhe_kms_set_relin_keys(thfhe_kms_ctx *c, const int64_t *uni, const int64_t
     THFHE_HIP(hipMemcpyAsync(d_raw + (size_t)P * 4 * lu * N * 8, crs, (size_t)lu * N * 8, hipMemcpyHostToDevice, c->stream));
     THFHE_TRY(c->d_relin.grow(n_polys * 4 * 1024 * sizeof(cplx)));
     THFHE_TRY(c->d_flag.grow(sizeof(int)));
-    hipLaunchKernelGGL((pm_torus_transform_kernel<2048, 64>), dim3((unsigned)((n_polys * 4 + 3) / 4)), dim3(256), 0, c->stream, (const void *)d_raw, (long)n_polys,
-                       c->d_tw.as<cplx>(), c->d_relin.as<cplx>());
-    THFHE_HIP(hipGetLastError());
+    THFHE_TRY((launch_torus_transform<2048, 64>(c->stream, d_raw, (long)n_polys, c->d_tw.as<cplx>(), c->d_relin.as<cplx>())));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }

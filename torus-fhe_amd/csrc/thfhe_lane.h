@@ -96,6 +96,8 @@ THFHE_FN int xs_c(int k1, int lane) { return (lane >> 3) * 72 + k1 * 9 + (lane &
 THFHE_FN int xs_d(int j0, int lane) { return (lane >> 3) * 72 + (lane & 7) * 9 + j0; }      // lane = k1 + 8 k0
 
 // ---- forward transform, three segments -------------------------------------------------------------
+// This table form (padded buffer, T1 and T2 read from tables) runs in no product kernel: tests/emu/lane_emu.cpp keeps it as the
+// reference that the "s", "r", "q" and N = 2048 forms below are checked against.
 // z[m] on entry: folded coefficients (p[lane + 64 m], p[lane + 64 m + 512])
 THFHE_FN void fwd_seg1(int lane, cplx (&z)[8], cplx *xbuf, const cplx *T1) {
 #pragma unroll
@@ -633,7 +635,7 @@ THFHE_FN void extract16(int lane, const int32_t *acc_mask, const int32_t *acc_bo
     }
     if (lane == 0) out[1024] = acc_body[0];
 }
-// folded limb inputs of a key polynomial for the key transform
+// folded two-limb inputs of a Torus32 polynomial (the ciphertext masks of the threshold partial decryption)
 THFHE_FN void key_limbs_to_z(int lane, const int32_t *poly, cplx (&zlo)[8], cplx (&zhi)[8]) {
 #pragma unroll
     for (int m = 0; m < 8; m++) {
@@ -683,15 +685,35 @@ THFHE_FN void split_limbs64(int64_t v, double (&l)[4]) {
     }
     l[3] = (double)v;
 }
+// limb h (balanced, 16 bit) of the two coefficients q0, q1 of a Torus32 (TB = 32) or Torus64 (TB = 64) polynomial that a lane folds
+// into one complex point of the key transform
+template <int TB>
+THFHE_FN cplx limb_pair(const void *poly, int q0, int q1, int h) {
+    if (TB == 32) {
+        const int32_t *p = static_cast<const int32_t *>(poly);
+        double l0, h0, l1, h1;
+        split_limbs32(p[q0], l0, h0);
+        split_limbs32(p[q1], l1, h1);
+        return h == 0 ? cplx{l0, l1} : cplx{h0, h1};
+    } else {
+        const int64_t *p = static_cast<const int64_t *>(poly);
+        double a[4], b[4];
+        split_limbs64(p[q0], a);
+        split_limbs64(p[q1], b);
+        return cplx{a[h], b[h]};
+    }
+}
+// the limb inputs of a Torus64 key polynomial as the key transform reads them: all four limbs of a degree-1024 polynomial, limb h of a
+// degree-2048 one
 THFHE_FN void key_limbs64_to_z(int lane, const int64_t *poly, cplx (&z)[4][8]) {
 #pragma unroll
-    for (int m = 0; m < 8; m++) {
-        double a[4], b[4];
-        split_limbs64(poly[lane + 64 * m], a);
-        split_limbs64(poly[lane + 64 * m + 512], b);
+    for (int h = 0; h < 4; h++)
 #pragma unroll
-        for (int q = 0; q < 4; q++) z[q][m] = cplx{a[q], b[q]};
-    }
+        for (int m = 0; m < 8; m++) z[h][m] = limb_pair<64>(poly, lane + 64 * m, lane + 64 * m + 512, h);
+}
+THFHE_FN void key_limbs64_to_z16(int lane, const int64_t *poly, int h, cplx (&z)[16]) {
+#pragma unroll
+    for (int m = 0; m < 16; m++) z[m] = limb_pair<64>(poly, lane + 64 * m, lane + 64 * m + 1024, h);
 }
 // round-to-nearest of x (|x| < 2^51) as int64
 THFHE_FN int64_t round_i64(double x) {
@@ -920,15 +942,6 @@ THFHE_FN void digits_to_z16(const uint32_t (&t)[32], int p, int Bgbit, cplx (&z)
 #pragma unroll
     for (int m = 0; m < 16; m++) z[m] = cplx{digit32(t[m], shift, mask, half), digit32(t[m + 16], shift, mask, half)};
 }
-THFHE_FN void key_limbs64_to_z16(int lane, const int64_t *poly, int h, cplx (&z)[16]) {  // limb h of a degree-2048 key polynomial
-#pragma unroll
-    for (int m = 0; m < 16; m++) {
-        double a[4], b[4];
-        split_limbs64(poly[lane + 64 * m], a);
-        split_limbs64(poly[lane + 64 * m + 1024], b);
-        z[m] = cplx{a[h], b[h]};
-    }
-}
 template <int NN>
 THFHE_FN void acc_init_64_n(int lane, int64_t *acc_mask, int64_t *acc_body, int barb, int64_t mu) {
 #pragma unroll
@@ -951,12 +964,43 @@ THFHE_FN void extract_64_n(int lane, const int64_t *acc_mask, const int64_t *acc
 // spectral key stream for N = 2048: [party*n + i][row r][limb h][output o][half][slot m][lane], 16 KiB per (pi, r, h, o)
 THFHE_FN size_t mk_chunk_index_2k(long pi, int r, int h, int o, int rows) { return mk_chunk_index(pi, r, h, o, rows) * 2; }  // * 512 complex
 
+// ---- twiddle tables: one per ring degree, indexed only through these offsets (in complex entries) ---------------------------
+// N = 1024
+struct TwRing1k {
+    static constexpr int T1 = 0;       // [512] T1[k0*64 + lane]
+    static constexpr int T2 = 512;     // [64]  T2[k1*8 + j0]; the W64 root of a lane is T2[1*8 + (lane & 7)]
+    static constexpr int ROOTS = 576;  // [128] per-lane roots of variant "r"
+    static constexpr int SIZE = 704;
+};
+// N = 2048 and N = 4096
+struct TwRing2k {
+    static constexpr int T1_TWIST1 = 0;   // [512] T1 of the twist-1 half (b_T of the "qs" form: its first 64 entries)
+    static constexpr int T1_TWIST5 = 512; // [512] T1 of the twist-5 half
+    static constexpr int T2 = 1024;       // [64]  as TwRing1k::T2
+    static constexpr int RATIO = 1088;    // [64]  pass-1 ratio of the table-free transforms
+    static constexpr int ROOTS4K = 1152;  // [256] per-lane roots of the four quarter twists (N = 4096)
+    static constexpr int SIZE = 1408;
+};
+template <int NN>
+THFHE_FN constexpr int tw_t2() { return NN == 1024 ? TwRing1k::T2 : TwRing2k::T2; }
+
 }  // namespace thfhe
 
 // ---- host-side twiddle table (double precision from long double; identical bytes on device) ---------
 #include <cmath>
+#include <vector>
+#pragma GCC visibility push(hidden)   // library-internal: not part of the exported C ABI
 namespace thfhe {
-// T1[k0*64 + lane] = exp(i pi lane (4 k0 + 1) / 1024), T2[k1*8 + j0] = exp(2 pi i j0 k1 / 64)
+// T2[k1*8 + j0] = exp(2 pi i j0 k1 / 64)
+inline void make_twiddles_t2(cplx *T2 /*64*/) {
+    const long double PI = 3.14159265358979323846264338327950288L;
+    for (int k1 = 0; k1 < 8; k1++)
+        for (int j0 = 0; j0 < 8; j0++) {
+            long double ang = 2.0L * PI * (long double)(j0 * k1) / 64.0L;
+            T2[k1 * 8 + j0] = cplx{(double)cosl(ang), (double)sinl(ang)};
+        }
+}
+// T1[k0*64 + lane] = exp(i pi lane (4 k0 + 1) / 1024), T2 as above
 inline void make_twiddles_1024(cplx *T1 /*512*/, cplx *T2 /*64*/) {
     const long double PI = 3.14159265358979323846264338327950288L;
     for (int k0 = 0; k0 < 8; k0++)
@@ -964,11 +1008,7 @@ inline void make_twiddles_1024(cplx *T1 /*512*/, cplx *T2 /*64*/) {
             long double ang = PI * (long double)(lane * (4 * k0 + 1)) / 1024.0L;
             T1[k0 * 64 + lane] = cplx{(double)cosl(ang), (double)sinl(ang)};
         }
-    for (int k1 = 0; k1 < 8; k1++)
-        for (int j0 = 0; j0 < 8; j0++) {
-            long double ang = 2.0L * PI * (long double)(j0 * k1) / 64.0L;
-            T2[k1 * 8 + j0] = cplx{(double)cosl(ang), (double)sinl(ang)};
-        }
+    make_twiddles_t2(T2);
 }
 // per-lane roots of variant "r": roots[2*lane] = exp(i pi lane / 1024), roots[2*lane + 1] = exp(i pi 4 lane / 1024)
 inline void make_lane_roots_1024(cplx *roots /*128*/) {
@@ -1006,6 +1046,22 @@ inline void make_twiddles_2048(cplx *T1a /*512, T = 1*/, cplx *T1b /*512, T = 5*
             T1b[k0 * 64 + lane] = cplx{(double)cosl(a5), (double)sinl(a5)};
         }
 }
+// the twiddle table of ring degree N: the TwRing1k layout for N = 1024, the TwRing2k layout for N = 2048 and 4096
+inline std::vector<cplx> make_twiddle_table(int N) {
+    if (N == 1024) {
+        std::vector<cplx> tw(TwRing1k::SIZE);
+        make_twiddles_1024(tw.data() + TwRing1k::T1, tw.data() + TwRing1k::T2);
+        make_lane_roots_1024(tw.data() + TwRing1k::ROOTS);
+        return tw;
+    }
+    std::vector<cplx> tw(TwRing2k::SIZE);
+    make_twiddles_2048(tw.data() + TwRing2k::T1_TWIST1, tw.data() + TwRing2k::T1_TWIST5);
+    make_twiddles_t2(tw.data() + TwRing2k::T2);
+    make_lane_ratio_2048(tw.data() + TwRing2k::RATIO);
+    make_lane_roots_4096(tw.data() + TwRing2k::ROOTS4K);
+    return tw;
+}
 }  // namespace thfhe
+#pragma GCC visibility pop
 
 #endif  // THFHE_LANE_H

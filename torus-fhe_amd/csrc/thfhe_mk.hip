@@ -7,8 +7,8 @@
 //   + mk_keyswitch_3gen (J/mk_internals.jl:730-744): one key switch per party, b = b' + sum of the parts' b.
 //
 // Kernels:
-//   mk_key_transform_kernel   TransformedBootstrapKeyPart_3gen (J/3gen_mk_internals.jl:45-56): int64 coefficient
-//                             polynomials -> four balanced 16-bit limbs -> FP64 spectra in streaming order
+//   torus_transform_kernel    TransformedBootstrapKeyPart_3gen (J/3gen_mk_internals.jl:45-56): int64 coefficient
+//   (thfhe_transform.h)       polynomials -> four balanced 16-bit limbs -> FP64 spectra in streaming order
 //   mk_prologue_kernel        gate linear part + mod-switch of the (n, P) mask matrix and of b
 //   mk_blind_rotate_coop_kernel / _pair_kernel   one 512-thread workgroup per gate / per two gates: the eight (output polynomial, limb) spectra on
 //                             eight waves; _coop2k / _pair2k on the ring of degree 2048 (two twisted half transforms per polynomial);
@@ -33,35 +33,21 @@ using namespace thfhe;
 
 namespace {
 
-// ------------------------------------------------------------------------------------------------------
-// key transform: one wave per (pi, row, output) key polynomial, four limb spectra each
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mk_key_transform_kernel(const int64_t *__restrict__ bk, long PN, int l,
-                                                                const cplx *__restrict__ tw, cplx *__restrict__ spec) {
-    __shared__ cplx sT1[512];
-    __shared__ cplx sX[4][512];
-    for (int t = threadIdx.x; t < 512; t += 256) sT1[t] = tw[t];
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const W64 w64{tw[512 + 1 * 8 + (lane & 7)]};
-    const int rows = 2 * l;
-    const long item = (long)blockIdx.x * 4 + wave;  // (pi, r, o)
-    if (item >= PN * rows * 2) return;
-    const int o = (int)(item & 1);
-    const int r = (int)((item >> 1) % rows);
-    const long pi = (item >> 1) / rows;
-    const int j = r / l, lv = r % l;
-    const int64_t *poly = bk + (((size_t)pi * 4 + mk_part_index(j, o)) * l + lv) * 1024;
-    cplx z[4][8];
-    key_limbs64_to_z(lane, poly, z);
-#pragma unroll
-    for (int h = 0; h < 4; h++) {
-        wave_fft_fwd_s(lane, z[h], sX[wave], sT1, w64);
-        cplx *dst = spec + mk_chunk_index(pi, r, h, o, rows) * 512;
-#pragma unroll
-        for (int m = 0; m < 8; m++) dst[m * 64 + lane] = cplx{z[h][m].re * (1.0 / 512), z[h][m].im * (1.0 / 512)};
+#include "thfhe_transform.h"
+
+// torus_transform_kernel on the resident key tables (N = 1024 / 2048): polynomial p = (pi, row r, output o) is part_{mk_part_index(j, o)}[level]
+// of row r = j l + level of key pi; its limb spectra go to the chunks of the streaming order (mk_chunk_index)
+struct MkResidentMap {
+    int l;
+    __device__ long src(long p) const {
+        const int rows = 2 * l, o = (int)(p & 1), r = (int)((p >> 1) % rows);
+        return (((p >> 1) / rows) * 4 + mk_part_index(r / l, o)) * l + r % l;
     }
-}
+    __device__ size_t dst(long p, int h, int) const {
+        const int rows = 2 * l;
+        return mk_chunk_index((p >> 1) / rows, (int)((p >> 1) % rows), h, (int)(p & 1), rows);
+    }
+};
 
 // wide gadget base: src [poly = (pi, part_q, level)][2048] -> dst [(pi, part_q, level * parts + w)][2048] = src << (pw w)
 __global__ __launch_bounds__(256) void mk_expand_parts_kernel(const int64_t *__restrict__ src, int64_t *__restrict__ dst, int l, int parts, int pw) {
@@ -71,36 +57,6 @@ __global__ __launch_bounds__(256) void mk_expand_parts_kernel(const int64_t *__r
     const int64_t *s = src + poly * 2048;
     int64_t *d = dst + ((head * l + level) * parts + w) * 2048;
     for (int t = threadIdx.x; t < 2048; t += 256) d[t] = (int64_t)((uint64_t)s[t] << (pw * w));
-}
-
-// N = 2048: one wave per (pi, row, output, limb); two twisted 512-point spectra (even / odd outputs) per item, scaled by 1/1024
-__global__ __launch_bounds__(256) void mk_key_transform_2k_kernel(const int64_t *__restrict__ bk, long PN, int l,
-                                                                   const cplx *__restrict__ tw, cplx *__restrict__ spec) {
-    __shared__ cplx sT1[2][512];
-    __shared__ cplx sX[4][512];
-    for (int t = threadIdx.x; t < 1024; t += 256) (&sT1[0][0])[t] = tw[t];
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const W64 w64{tw[1024 + 1 * 8 + (lane & 7)]};
-    const int rows = 2 * l;
-    const long item = (long)blockIdx.x * 4 + wave;  // (pi, r, o, h)
-    if (item >= PN * rows * 8) return;
-    const int h = (int)(item & 3), o = (int)((item >> 2) & 1);
-    const int r = (int)((item >> 3) % rows);
-    const long pi = (item >> 3) / rows;
-    const int j = r / l, lv = r % l;
-    const int64_t *poly = bk + (((size_t)pi * 4 + mk_part_index(j, o)) * l + lv) * 2048;
-    cplx z[16], y0[8], y1[8];
-    key_limbs64_to_z16(lane, poly, h, z);
-    split2048(z, y0, y1);
-    wave_fft_fwd_t<1>(lane, y0, sX[wave], sT1[0], w64);
-    wave_fft_fwd_t<5>(lane, y1, sX[wave], sT1[1], w64);
-    cplx *dst = spec + mk_chunk_index_2k(pi, r, h, o, rows) * 512;
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-        dst[m * 64 + lane] = cplx{y0[m].re * (1.0 / 1024), y0[m].im * (1.0 / 1024)};
-        dst[512 + m * 64 + lane] = cplx{y1[m].re * (1.0 / 1024), y1[m].im * (1.0 / 1024)};
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -147,7 +103,7 @@ __global__ __launch_bounds__(512, 2) void mk_blind_rotate_coop_kernel(MKBRArgs a
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     sT1[threadIdx.x] = a.tw[threadIdx.x];
-    const W64 w64{a.tw[512 + 1 * 8 + (lane & 7)]};
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
     const long job = blockIdx.x;
     const int32_t *bara = a.bara + job * a.w_pad;
     const int Bgbit = a.Bgbit;
@@ -268,8 +224,8 @@ __global__ __launch_bounds__(512, 2) void mk_blind_rotate_pair_kernel(MKBRArgs a
     __shared__ cplx sSpec[SPEC_SLOTS];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    const W64 w64{a.tw[512 + 1 * 8 + (lane & 7)]};
-    const LaneRoots roots0{a.tw[1088 + 2 * lane], a.tw[1088 + 2 * lane + 1]};
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
+    const LaneRoots roots0{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
     const MK_ROOTS roots = mk_make_roots(roots0);
     const long job0 = 2 * (long)blockIdx.x;
     const bool has1 = job0 + 1 < a.jobs;
@@ -415,9 +371,9 @@ __global__ __launch_bounds__(512, 2) void mk_blind_rotate_coop2k_kernel(MKBRArgs
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     // per-lane transform constants are phase-local (L1 / L2 hits at the start of a transform phase), not 10 VGPRs alive across the multiply
-    auto tw_w64 = [&](int ln) { return W64{a.tw[1024 + 1 * 8 + (ln & 7)]}; };
-    auto tw_roots1 = [&](int ln) { return LaneRoots{opaque_cplx(a.tw[ln]), opaque_cplx(a.tw[1216 + ln])}; };   // b_T = T1_T[0][lane], pass-1 ratio
-    auto tw_roots5 = [&](int ln) { return LaneRoots{opaque_cplx(a.tw[512 + ln]), opaque_cplx(a.tw[1216 + ln])}; };
+    auto tw_w64 = [&](int ln) { return W64{a.tw[TwRing2k::T2 + 1 * 8 + (ln & 7)]}; };
+    auto tw_roots1 = [&](int ln) { return LaneRoots{opaque_cplx(a.tw[TwRing2k::T1_TWIST1 + ln]), opaque_cplx(a.tw[TwRing2k::RATIO + ln])}; };   // b_T = T1_T[0][lane], pass-1 ratio
+    auto tw_roots5 = [&](int ln) { return LaneRoots{opaque_cplx(a.tw[TwRing2k::T1_TWIST5 + ln]), opaque_cplx(a.tw[TwRing2k::RATIO + ln])}; };
     const long job = blockIdx.x;
     const int32_t *bara = a.bara + job * a.w_pad;
     const int Bgbit = a.Bgbit;
@@ -684,9 +640,9 @@ __global__ __launch_bounds__(512, 2) void mk_blind_rotate_pair2k_kernel(MKBRArgs
     // per-lane transform constants are phase-local: fetched again (L1 / L2 hits) at the start of every transform phase instead of living in
     // 16 VGPRs across the multiply phases, where the four partial spectra, two key chunks and a digit spectrum leave no room (the allocator
     // spilled them to scratch and reloaded them in front of every use)
-    auto tw_w64 = [&](int ln) { return W64{a.tw[1024 + 1 * 8 + (ln & 7)]}; };
-    auto tw_roots1 = [&](int ln) { return LaneRoots{a.tw[ln], a.tw[1216 + ln]}; };         // b_T = T1_T[0][lane], ratio
-    auto tw_roots5 = [&](int ln) { return LaneRoots{a.tw[512 + ln], a.tw[1216 + ln]}; };
+    auto tw_w64 = [&](int ln) { return W64{a.tw[TwRing2k::T2 + 1 * 8 + (ln & 7)]}; };
+    auto tw_roots1 = [&](int ln) { return LaneRoots{a.tw[TwRing2k::T1_TWIST1 + ln], a.tw[TwRing2k::RATIO + ln]}; };         // b_T = T1_T[0][lane], ratio
+    auto tw_roots5 = [&](int ln) { return LaneRoots{a.tw[TwRing2k::T1_TWIST5 + ln], a.tw[TwRing2k::RATIO + ln]}; };
     P2KDigits dg;
     dg.parts = a.parts > 1 ? a.parts : 1;
     dg.pw = a.pw;
@@ -923,7 +879,7 @@ __global__ __launch_bounds__(256) void mk_mux_combine_kernel(const int32_t *__re
 
 struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     thfhe_params p;
-    DevBuf d_bk, d_ksk, d_tw;
+    DevBuf d_bk, d_ksk;
     int row_words = 0, w_pad = 0, words = 0, log2_2n = 11;
     DevBuf park;                 // batched N = 2048 rotation, two jobs per workgroup: partial spectra between row-part batches (thfhe_rot2k.h)
     long pair_threshold = 256;  // batches of more rotations than this run two gates per workgroup (mk_blind_rotate_pair_kernel)
@@ -1159,102 +1115,40 @@ int thfhe_mk_ctx_create(const thfhe_params *p, const int64_t *bk_coeff, const in
     c->parts = parts;
     c->pw = pw;
     c->batched = batched;
-    DevBuf coeff, raw;  // upload staging
-    std::vector<cplx> tw(1088 + 128 + 64 + 256);   // [1280..): per-lane roots of the four quarter twists (N = 4096)
-    make_lane_roots_4096(tw.data() + 1280);
-    // N = 1024: T1[512] T2[64]; N = 2048: T1(twist 1)[512] T1(twist 5)[512] T2[64]; [1088..): per-lane roots (N = 1024); [1216..): pass-1 ratio (N = 2048)
-    make_lane_ratio_2048(tw.data() + 1216);
-    if (p->N >= 2048) {   // (N = 4096 reads only T2, the ratio and its own roots: the table-free transforms)
-        std::vector<cplx> unused(512);
-        make_twiddles_2048(tw.data(), tw.data() + 512);
-        make_twiddles_1024(unused.data(), tw.data() + 1024);
+    THFHE_TRY(c->upload_twiddles(p->N));
+    if (ring4k || batched) {
+        // key table of thfhe_rot4k.h / thfhe_rot2k.h, staged party by party: row part (j l + level) parts + part of output o is
+        // part_{mk_part_index(j, o)}[level] shifted left by part * pw bits
+        const int l = p->l;
+        auto src = [&](int q, int i, int r, int o) { return bk_coeff + ((((size_t)q * p->n + i) * 4 + mk_part_index(r / l, o)) * l + r % l) * p->N; };
+        THFHE_TRY(ring4k ? stage_party_keys<4096>(*c, c->d_bk, p->parties, p->n, 2 * l, parts, pw, src)
+                         : stage_party_keys<2048>(*c, c->d_bk, p->parties, p->n, 2 * l, parts, pw, src));
     } else {
-        make_twiddles_1024(tw.data(), tw.data() + 512);
-    }
-    make_lane_roots_1024(tw.data() + 1088);
-    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
-    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
-    if (ring4k) {
-        // key table of thfhe_rot4k.h: [party * n + i][row part rp = (j l + level) parts + part][output o][limb][quarter][512]; row part (j, level, part)
-        // of output o is part_{mk_part_index(j, o)}[level] shifted left by part * pw bits (wrapping).  Staged party by party.
-        const int RP = 2 * p->l * parts, N = 4096;
-        const size_t polys_per_party = (size_t)p->n * RP * 2;
-        THFHE_TRY(c->d_bk.grow((size_t)p->parties * polys_per_party * 4 * 2048 * sizeof(cplx)));
-        THFHE_TRY(coeff.grow(polys_per_party * N * sizeof(int64_t)));
-        std::vector<int64_t> host(polys_per_party * N);
-        for (int q = 0; q < p->parties; q++) {
-            for (int i = 0; i < p->n; i++)
-                for (int j = 0; j < 2; j++)
-                    for (int lv = 0; lv < p->l; lv++)
-                        for (int part = 0; part < parts; part++)
-                            for (int o = 0; o < 2; o++) {
-                                const int64_t *src = bk_coeff + ((((size_t)q * p->n + i) * 4 + mk_part_index(j, o)) * p->l + lv) * N;
-                                const int rp = (j * p->l + lv) * parts + part;
-                                int64_t *dst = host.data() + (((size_t)i * RP + rp) * 2 + o) * N;
-                                const int sh = part * pw;
-                                for (int t = 0; t < N; t++) dst[t] = (int64_t)((uint64_t)src[t] << sh);
-                            }
-            THFHE_HIP(hipMemcpyAsync(coeff.as<int64_t>(), host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(r4k_key_transform_kernel, dim3((unsigned)((polys_per_party * 4 + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int64_t>(), (long)polys_per_party,
-                               c->d_tw.as<cplx>(), c->d_bk.as<cplx>() + (size_t)q * polys_per_party * 4 * 2048);
-            THFHE_HIP(hipGetLastError());
-            THFHE_HIP(hipStreamSynchronize(c->stream));   // `host` is reused for the next party
+        const long PN = (long)p->parties * p->n;
+        const size_t coeff_words = (size_t)PN * 4 * p->l * p->N;
+        DevBuf coeff;  // upload staging
+        THFHE_TRY(coeff.grow(coeff_words * sizeof(int64_t)));
+        THFHE_HIP(hipMemcpyAsync(coeff.as<int64_t>(), bk_coeff, coeff_words * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        const int le = p->l * parts;
+        const long npolys = PN * 2 * le * 2;   // (pi, row, output)
+        THFHE_TRY(c->d_bk.grow((size_t)npolys * 4 * (p->N / 2) * sizeof(cplx)));
+        if (p->N == 2048) {
+            if (parts > 1) {   // key rows followed by their copies shifted left by pw, 2 pw bits (wrapping): d (*) K = sum_w d_w (*) (K << pw w)
+                DevBuf exp;
+                THFHE_TRY(exp.grow(coeff_words * parts * sizeof(int64_t)));
+                const long polys = PN * 4 * p->l;
+                hipLaunchKernelGGL(mk_expand_parts_kernel, dim3((unsigned)polys, (unsigned)parts), dim3(256), 0, c->stream, coeff.as<int64_t>(), exp.as<int64_t>(), p->l, parts, pw);
+                THFHE_HIP(hipGetLastError());
+                THFHE_HIP(hipStreamSynchronize(c->stream));
+                coeff = std::move(exp);
+            }
+            THFHE_TRY((launch_torus_transform<2048, 64>(c->stream, coeff.as<int64_t>(), npolys, c->d_tw.as<cplx>(), c->d_bk.as<cplx>(), MkResidentMap{le})));
+        } else {
+            THFHE_TRY((launch_torus_transform<1024, 64>(c->stream, coeff.as<int64_t>(), npolys, c->d_tw.as<cplx>(), c->d_bk.as<cplx>(), MkResidentMap{le})));
         }
-        coeff = DevBuf();
-    } else if (batched) {
-        // key table of thfhe_rot2k.h: [party * n + i][row part rp = (j l + level) parts + part][output o][limb][half][512]; row part (j, level,
-        // part) of output o is part_{mk_part_index(j, o)}[level] shifted left by part * pw bits (wrapping): d (*) K = d_lo (*) K + d_hi (*) (K << pw).
-        // Staged party by party (the 256-party set: 194 MB of coefficients per party, 185 GB of spectra in all).
-        const int RP = 2 * p->l * parts, N = 2048;
-        const size_t polys_per_party = (size_t)p->n * RP * 2;
-        THFHE_TRY(c->d_bk.grow((size_t)p->parties * polys_per_party * 4 * 1024 * sizeof(cplx)));
-        THFHE_TRY(coeff.grow(polys_per_party * N * sizeof(int64_t)));
-        std::vector<int64_t> host(polys_per_party * N);
-        for (int q = 0; q < p->parties; q++) {
-            for (int i = 0; i < p->n; i++)
-                for (int j = 0; j < 2; j++)
-                    for (int lv = 0; lv < p->l; lv++)
-                        for (int part = 0; part < parts; part++)
-                            for (int o = 0; o < 2; o++) {
-                                const int64_t *src = bk_coeff + ((((size_t)q * p->n + i) * 4 + mk_part_index(j, o)) * p->l + lv) * N;
-                                const int rp = (j * p->l + lv) * parts + part;
-                                int64_t *dst = host.data() + (((size_t)i * RP + rp) * 2 + o) * N;
-                                const int sh = part * pw;
-                                for (int t = 0; t < N; t++) dst[t] = (int64_t)((uint64_t)src[t] << sh);
-                            }
-            THFHE_HIP(hipMemcpyAsync(coeff.as<int64_t>(), host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(kms_key_transform_kernel, dim3((unsigned)((polys_per_party * 4 + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int64_t>(), (long)polys_per_party,
-                               c->d_tw.as<cplx>(), c->d_bk.as<cplx>() + (size_t)q * polys_per_party * 4 * 1024);
-            THFHE_HIP(hipGetLastError());
-            THFHE_HIP(hipStreamSynchronize(c->stream));   // `host` is reused for the next party
-        }
-        coeff = DevBuf();
-    } else {
-    const long PN = (long)p->parties * p->n;
-    const size_t coeff_words = (size_t)PN * 4 * p->l * p->N;
-    THFHE_TRY(coeff.grow(coeff_words * sizeof(int64_t)));
-    THFHE_HIP(hipMemcpyAsync(coeff.as<int64_t>(), bk_coeff, coeff_words * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    const int le = p->l * parts;
-    const size_t chunks = (size_t)PN * 2 * le * 8;
-    THFHE_TRY(c->d_bk.grow(chunks * (p->N / 2) * sizeof(cplx)));
-    if (p->N == 2048) {
-        if (parts > 1) {   // key rows followed by their copies shifted left by pw, 2 pw bits (wrapping): d (*) K = sum_w d_w (*) (K << pw w)
-            DevBuf exp;
-            THFHE_TRY(exp.grow(coeff_words * parts * sizeof(int64_t)));
-            const long polys = PN * 4 * p->l;
-            hipLaunchKernelGGL(mk_expand_parts_kernel, dim3((unsigned)polys, (unsigned)parts), dim3(256), 0, c->stream, coeff.as<int64_t>(), exp.as<int64_t>(), p->l, parts, pw);
-            THFHE_HIP(hipGetLastError());
-            THFHE_HIP(hipStreamSynchronize(c->stream));
-            coeff = std::move(exp);
-        }
-        const long items = PN * 2 * le * 8;
-        hipLaunchKernelGGL(mk_key_transform_2k_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int64_t>(), PN, le, c->d_tw.as<cplx>(), c->d_bk.as<cplx>());
-    } else {
-        const long items = PN * 2 * p->l * 2;
-        hipLaunchKernelGGL(mk_key_transform_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int64_t>(), PN, p->l, c->d_tw.as<cplx>(), c->d_bk.as<cplx>());
+        THFHE_HIP(hipStreamSynchronize(c->stream));   // before `coeff` is freed
     }
-    THFHE_HIP(hipGetLastError());
-    }
+    DevBuf raw;  // upload staging
     const long rows = (long)p->parties * p->N * p->ks_t * ((1 << p->ks_basebit) - 1);
     THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));
     THFHE_HIP(hipMemcpyAsync(raw.as<int32_t>(), ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));

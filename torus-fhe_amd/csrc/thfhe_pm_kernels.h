@@ -1,68 +1,13 @@
-// thfhe_pm_kernels.h -- the exact small x torus polynomial multiply-accumulate kernels (see thfhe_polymac.hip for the method).
-// Included INSIDE the anonymous namespace of a translation unit (thfhe_polymac.hip: the thfhe_pm_* entry points; thfhe_kms.hip: the
-// device-resident relinearisation of the KMS scheme), so that every unit has its own internal-linkage copies of the kernels.
+// thfhe_pm_kernels.h -- the exact small x torus polynomial multiply-accumulate kernel (see thfhe_polymac.hip for the method); its torus
+// operands are limb spectra of torus_transform_kernel (thfhe_transform.h).  Included INSIDE the anonymous namespace of a translation unit
+// (thfhe_polymac.hip: the thfhe_pm_* entry points; thfhe_kms.hip: the device-resident relinearisation of the KMS scheme), so that every
+// unit has its own internal-linkage copies of the kernels.
 #ifndef THFHE_PM_KERNELS_H
 #define THFHE_PM_KERNELS_H
 
-// limb h (balanced, 16 bit) of the two coefficients a lane folds into one complex point
-template <int TB>
-__device__ __forceinline__ cplx limb_pair(const void *poly, int q0, int q1, int h) {
-    if (TB == 32) {
-        const int32_t *p = static_cast<const int32_t *>(poly);
-        double l0, h0, l1, h1;
-        split_limbs32(p[q0], l0, h0);
-        split_limbs32(p[q1], l1, h1);
-        return h == 0 ? cplx{l0, l1} : cplx{h0, h1};
-    } else {
-        const int64_t *p = static_cast<const int64_t *>(poly);
-        double a[4], b[4];
-        split_limbs64(p[q0], a);
-        split_limbs64(p[q1], b);
-        return cplx{a[h], b[h]};
-    }
-}
-
-// torus polynomials -> limb spectra [poly][limb][half][512], scaled by 1/(NN/2); one wave per (poly, limb)
-template <int NN, int TB>
-__global__ __launch_bounds__(256) void pm_torus_transform_kernel(const void *__restrict__ torus, long npolys, const cplx *__restrict__ tw,
-                                                                  cplx *__restrict__ spec) {
-    constexpr int LIMBS = TB / 16, HALVES = NN / 1024;
-    __shared__ cplx sT1[HALVES][512];
-    __shared__ cplx sX[4][512];
-    for (int t = threadIdx.x; t < HALVES * 512; t += 256) (&sT1[0][0])[t] = tw[t];
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const W64 w64{tw[HALVES * 512 + 1 * 8 + (lane & 7)]};
-    const long item = (long)blockIdx.x * 4 + wave;
-    if (item >= npolys * LIMBS) return;
-    const int h = (int)(item % LIMBS);
-    const char *poly = static_cast<const char *>(torus) + (size_t)(item / LIMBS) * NN * (TB / 8);
-    cplx *dst = spec + (size_t)item * HALVES * 512;
-    if (NN == 1024) {
-        cplx z[8];
-#pragma unroll
-        for (int m = 0; m < 8; m++) z[m] = limb_pair<TB>(poly, lane + 64 * m, lane + 64 * m + 512, h);
-        wave_fft_fwd_s(lane, z, sX[wave], sT1[0], w64);
-#pragma unroll
-        for (int m = 0; m < 8; m++) dst[m * 64 + lane] = cplx{z[m].re * (1.0 / 512), z[m].im * (1.0 / 512)};
-    } else {
-        cplx z[16], y0[8], y1[8];
-#pragma unroll
-        for (int m = 0; m < 16; m++) z[m] = limb_pair<TB>(poly, lane + 64 * m, lane + 64 * m + 1024, h);
-        split2048(z, y0, y1);
-        wave_fft_fwd_t<1>(lane, y0, sX[wave], sT1[0], w64);
-        wave_fft_fwd_t<5>(lane, y1, sX[wave], sT1[HALVES - 1], w64);
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-            dst[m * 64 + lane] = cplx{y0[m].re * (1.0 / 1024), y0[m].im * (1.0 / 1024)};
-            dst[512 + m * 64 + lane] = cplx{y1[m].re * (1.0 / 1024), y1[m].im * (1.0 / 1024)};
-        }
-    }
-}
-
 struct PMArgs {
     const int32_t *small;   // [n_small][NN]
-    const cplx *spec;       // limb spectra of the torus polynomials
+    const cplx *spec;       // limb spectra of the torus polynomials [poly][limb][NN/2]
     const int32_t *terms;   // [n_terms][4] = (out, small, torus, sign), grouped by `out`
     const int32_t *first;   // [n_out + 1]: terms of output j are first[j] .. first[j+1]-1
     const void *addend;     // [n_out][NN] or null
@@ -81,7 +26,7 @@ __global__ __launch_bounds__(256) void pm_mac_kernel(PMArgs a) {
     for (int t = threadIdx.x; t < HALVES * 512; t += 256) (&sT1[0][0])[t] = a.tw[t];
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const W64 w64{a.tw[HALVES * 512 + 1 * 8 + (lane & 7)]};
+    const W64 w64{a.tw[tw_t2<NN>() + 1 * 8 + (lane & 7)]};
     const long j = (long)blockIdx.x * 4 + wave;
     if (j >= a.n_out) return;
     word r[PER];   // coefficient lane + 64 m

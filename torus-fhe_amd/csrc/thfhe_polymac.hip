@@ -5,7 +5,7 @@
 // r (*) a_i, s (*) f1_i) -- with the randomness handed in as arrays, so that the GPU result equals the host (numpy) key generation
 // bit for bit (thfhe/keygen.py, tests/test_gpu_keygen.py).
 // Method: the engine's split-limb FP64 transform (thfhe_lane.h).  Every torus polynomial is split into balanced 16-bit limbs and
-// transformed once (pm_torus_transform_kernel); one wave per output transforms each small operand once, multiplies it into the
+// transformed once (torus_transform_kernel); one wave per output transforms each small operand once, multiplies it into the
 // limb spectra of its partner and inverse-transforms every limb product separately: |product| <= N 2^(sb-1) 2^15 with |small| < 2^(sb-1),
 // sb <= 13 -- at most 2^38 for N = 2048, inside the exactness bound.  Ring degrees 1024 and 2048 (radix-2 split
 // + two twisted 512-point transforms), Torus32 (N = 1024) and Torus64.
@@ -26,21 +26,21 @@ using namespace thfhe;
 
 namespace {
 
+#include "thfhe_transform.h"
 #include "thfhe_pm_kernels.h"
 
 }  // namespace
 
 struct THFHE_INTERNAL thfhe_pm_ctx : DevCtx {
     int N = 1024, torus_bits = 32;
-    DevBuf d_tw, d_flag;
+    DevBuf d_flag;
     DevBuf d_buf[7];  // small, torus, spec, terms, first, addend, out
 };
 
 namespace {
 template <int NN, int TB>
 int pm_run(thfhe_pm_ctx *c, size_t n_torus, const PMArgs &a) {
-    hipLaunchKernelGGL((pm_torus_transform_kernel<NN, TB>), dim3((unsigned)((n_torus * (TB / 16) + 3) / 4)), dim3(256), 0, c->stream, c->d_buf[1].as<void>(), (long)n_torus,
-                       c->d_tw.as<cplx>(), c->d_buf[2].as<cplx>());
+    THFHE_TRY((launch_torus_transform<NN, TB>(c->stream, c->d_buf[1].as<void>(), (long)n_torus, c->d_tw.as<cplx>(), c->d_buf[2].as<cplx>())));
     hipLaunchKernelGGL((pm_mac_kernel<NN, TB>), dim3((unsigned)((a.n_out + 3) / 4)), dim3(256), 0, c->stream, a);
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
@@ -58,18 +58,8 @@ int thfhe_pm_ctx_create(int device, int N, int torus_bits, thfhe_pm_ctx **out) {
     if (!c) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
     THFHE_TRY(c->open(device, false));
     c->N = N, c->torus_bits = torus_bits;
-    std::vector<cplx> tw(1088);  // N = 1024: T1[512] T2[64]; N = 2048: T1(twist 1)[512] T1(twist 5)[512] T2[64]
-    if (N == 2048) {
-        std::vector<cplx> unused(512);
-        make_twiddles_2048(tw.data(), tw.data() + 512);
-        make_twiddles_1024(unused.data(), tw.data() + 1024);
-    } else {
-        make_twiddles_1024(tw.data(), tw.data() + 512);
-    }
-    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
+    THFHE_TRY(c->upload_twiddles(N));
     THFHE_TRY(c->d_flag.grow(sizeof(int)));
-    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
     *out = c.release();
     return THFHE_OK;
 }

@@ -8,30 +8,6 @@
 
 __device__ __forceinline__ void kms_pin() { asm volatile("" ::: "memory"); }
 
-// torus polynomials int64[npolys][2048] -> limb spectra [poly][limb h][half][512], scaled by 1/1024 (one wave per (poly, limb))
-__global__ __launch_bounds__(256) void kms_key_transform_kernel(const int64_t *__restrict__ polys, long npolys, const cplx *__restrict__ tw,
-                                                                 cplx *__restrict__ spec) {
-    __shared__ cplx sT1[2][512];
-    __shared__ cplx sX[4][512];
-    for (int t = threadIdx.x; t < 1024; t += 256) (&sT1[0][0])[t] = tw[t];
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const W64 w64{tw[1024 + 1 * 8 + (lane & 7)]};
-    const long item = (long)blockIdx.x * 4 + wave;
-    if (item >= npolys * 4) return;
-    cplx z[16], y0[8], y1[8];
-    key_limbs64_to_z16(lane, polys + (item >> 2) * 2048, (int)(item & 3), z);
-    split2048(z, y0, y1);
-    wave_fft_fwd_t<1>(lane, y0, sX[wave], sT1[0], w64);
-    wave_fft_fwd_t<5>(lane, y1, sX[wave], sT1[1], w64);
-    cplx *dst = spec + (size_t)item * 1024;
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-        dst[m * 64 + lane] = cplx{y0[m].re * (1.0 / 1024), y0[m].im * (1.0 / 1024)};
-        dst[512 + m * 64 + lane] = cplx{y1[m].re * (1.0 / 1024), y1[m].im * (1.0 / 1024)};
-    }
-}
-
 struct KmsBRArgs {
     const cplx *bk;       // the party's key spectra [j][row part][column o][limb h][half][512]
     const cplx *tw;
@@ -51,7 +27,7 @@ __global__ __launch_bounds__(512, 2) void kms_tlev_rotate_kernel(KmsBRArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     for (int t = threadIdx.x; t < 1024; t += 512) (&sT1[0][0])[t] = a.tw[t];
-    const W64 w64{a.tw[1024 + 1 * 8 + (lane & 7)]};
+    const W64 w64{a.tw[TwRing2k::T2 + 1 * 8 + (lane & 7)]};
     const long job = blockIdx.x;
     const long gate = job / a.l_lev;
     const int sample = (int)(job % a.l_lev);
@@ -336,9 +312,9 @@ __global__ __launch_bounds__(512, 2) void kms_tlev_rotate_pair_kernel(KmsBRArgs 
     __shared__ cplx sSpec[2 * BATCH * 512];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    auto tw_w64 = [&](int ln) { return W64{a.tw[1024 + 1 * 8 + (ln & 7)]}; };             // phase-local constants: see mk_blind_rotate_pair2k_kernel
-    auto tw_roots1 = [&](int ln) { return LaneRoots{a.tw[ln], a.tw[1216 + ln]}; };
-    auto tw_roots5 = [&](int ln) { return LaneRoots{a.tw[512 + ln], a.tw[1216 + ln]}; };
+    auto tw_w64 = [&](int ln) { return W64{a.tw[TwRing2k::T2 + 1 * 8 + (ln & 7)]}; };             // phase-local constants: see mk_blind_rotate_pair2k_kernel
+    auto tw_roots1 = [&](int ln) { return LaneRoots{a.tw[TwRing2k::T1_TWIST1 + ln], a.tw[TwRing2k::RATIO + ln]}; };
+    auto tw_roots5 = [&](int ln) { return LaneRoots{a.tw[TwRing2k::T1_TWIST5 + ln], a.tw[TwRing2k::RATIO + ln]}; };
     const long job0 = 2 * (long)blockIdx.x;
     const bool has1 = job0 + 1 < a.jobs;
     const int32_t *bara0 = a.bara + (job0 / a.l_lev) * a.bara_stride;

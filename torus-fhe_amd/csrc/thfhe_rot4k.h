@@ -14,45 +14,6 @@
 #define R4K_EARLY_KEY 0
 #endif
 
-// torus polynomials int64[npolys][4096] -> limb spectra [poly][limb h][quarter][512], scaled by 1/2048 (one wave per (poly, limb))
-__global__ __launch_bounds__(256) void r4k_key_transform_kernel(const int64_t *__restrict__ polys, long npolys, const cplx *__restrict__ tw,
-                                                                 cplx *__restrict__ spec) {
-    __shared__ cplx sX[4][512];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long item = (long)blockIdx.x * 4 + wave;
-    if (item >= npolys * 4) return;
-    const W64 w64{tw[1024 + 1 * 8 + (lane & 7)]};
-    const cplx ratio = tw[1216 + lane];
-    const int64_t *poly = polys + (item >> 2) * 4096;
-    const int h = (int)(item & 3);
-    cplx *dst = spec + (size_t)item * 2048;
-#pragma unroll
-    for (int qt = 0; qt < 4; qt++) {
-        cplx y[8];
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-            cplx u[4];
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                double a[4], b[4];
-                split_limbs64(poly[lane + 64 * m + 512 * s], a);
-                split_limbs64(poly[lane + 64 * m + 512 * s + 2048], b);
-                u[s] = cplx{a[h], b[h]};
-            }
-            pre4096(u);
-            y[m] = qt == 0 ? comb4096<0>(u) : qt == 1 ? comb4096<1>(u) : qt == 2 ? comb4096<2>(u) : comb4096<3>(u);
-        }
-        const LaneRoots roots{tw[1280 + qt * 64 + lane], ratio};
-        if (qt == 0) wave_fft_fwd_tq<1, 64>(lane, y, sX[wave], roots, w64);
-        if (qt == 1) wave_fft_fwd_tq<5, 64>(lane, y, sX[wave], roots, w64);
-        if (qt == 2) wave_fft_fwd_tq<9, 64>(lane, y, sX[wave], roots, w64);
-        if (qt == 3) wave_fft_fwd_tq<13, 64>(lane, y, sX[wave], roots, w64);
-        wave_sync();
-#pragma unroll
-        for (int m = 0; m < 8; m++) dst[qt * 512 + m * 64 + lane] = cplx{y[m].re * (1.0 / 2048), y[m].im * (1.0 / 2048)};
-    }
-}
-
 struct R4KArgs {
     const cplx *bk;       // key spectra [step][row part][output o][limb h][quarter][512]
     const cplx *tw;
@@ -164,11 +125,11 @@ __global__ __launch_bounds__(512, 2) void r4k_rotate_kernel(R4KArgs a, cplx *__r
 #endif
             {
                 const int ln = opaque_lane(lane);
-                const W64 w64{a.tw[1024 + 1 * 8 + (ln & 7)]};
-                const cplx ratio = a.tw[1216 + ln];
+                const W64 w64{a.tw[TwRing2k::T2 + 1 * 8 + (ln & 7)]};
+                const cplx ratio = a.tw[TwRing2k::RATIO + ln];
                 auto transform = [&](int qt, int slot, cplx (&y)[8]) {
                     cplx *xb = sSpec + slot * 512;
-                    const LaneRoots roots{a.tw[1280 + (2 * P + qt) * 64 + ln], ratio};
+                    const LaneRoots roots{a.tw[TwRing2k::ROOTS4K + (2 * P + qt) * 64 + ln], ratio};
                     if (P == 0 && qt == 0) wave_fft_fwd_tq<1, 64>(ln, y, xb, roots, w64);
                     if (P == 0 && qt == 1) wave_fft_fwd_tq<5, 64>(ln, y, xb, roots, w64);
                     if (P == 1 && qt == 0) wave_fft_fwd_tq<9, 64>(ln, y, xb, roots, w64);
@@ -226,17 +187,17 @@ __global__ __launch_bounds__(512, 2) void r4k_rotate_kernel(R4KArgs a, cplx *__r
         {
             cplx *xb = sSpec + wave * 512;
             const int ln = opaque_lane(lane);
-            const W64 w64{a.tw[1024 + 1 * 8 + (ln & 7)]};
-            const cplx ratio = a.tw[1216 + ln];
+            const W64 w64{a.tw[TwRing2k::T2 + 1 * 8 + (ln & 7)]};
+            const cplx ratio = a.tw[TwRing2k::RATIO + ln];
             cplx Sa[8], Sb[8];
             kms_pin();
             load8(ln, Sa, mypark);         // requested ahead of the two transforms that do not need them
             load8(ln, Sb, mypark + 512);
             kms_pin();
-            wave_fft_inv_tq<9, 64>(ln, S[0], xb, LaneRoots{a.tw[1280 + 128 + ln], ratio}, w64);
-            wave_fft_inv_tq<13, 64>(ln, S[1], xb, LaneRoots{a.tw[1280 + 192 + ln], ratio}, w64);
-            wave_fft_inv_tq<1, 64>(ln, Sa, xb, LaneRoots{a.tw[1280 + ln], ratio}, w64);
-            wave_fft_inv_tq<5, 64>(ln, Sb, xb, LaneRoots{a.tw[1280 + 64 + ln], ratio}, w64);
+            wave_fft_inv_tq<9, 64>(ln, S[0], xb, LaneRoots{a.tw[TwRing2k::ROOTS4K + 128 + ln], ratio}, w64);
+            wave_fft_inv_tq<13, 64>(ln, S[1], xb, LaneRoots{a.tw[TwRing2k::ROOTS4K + 192 + ln], ratio}, w64);
+            wave_fft_inv_tq<1, 64>(ln, Sa, xb, LaneRoots{a.tw[TwRing2k::ROOTS4K + ln], ratio}, w64);
+            wave_fft_inv_tq<5, 64>(ln, Sb, xb, LaneRoots{a.tw[TwRing2k::ROOTS4K + 64 + ln], ratio}, w64);
 #pragma unroll
             for (int m = 0; m < 8; m++) {
                 cplx z[4];

@@ -1,8 +1,8 @@
 // thfhe_sk.hip -- single-key (Torus32) gate bootstrapping on gfx950: kernels + C ABI.
 //
 // Kernels (one HIP stream per context, no host sync inside a call):
-//   sk_key_transform_kernel   BootstrapKey forward_transform step (J/bootstrap.jl:11-12): coefficient-domain TGSW
-//                             rows -> two-limb FP64 spectra in the blind-rotate kernel's register order
+//   torus_transform_kernel    BootstrapKey forward_transform step (J/bootstrap.jl:11-12): coefficient-domain TGSW
+//   (thfhe_transform.h)       rows -> two-limb FP64 spectra in the blind-rotate kernel's register order
 //   sk_prologue_kernel        gate linear part (J/gates.jl:15-177) + mod-switch decode_message(.,2N)
 //                             (J/bootstrap.jl:80-81) -> bara[job][n], barb[job]
 //   sk_blind_rotate_ring_kernel / sk_blind_rotate_coop_kernel   blind_rotate_and_extract (J/bootstrap.jl:38-65): accumulator in
@@ -31,32 +31,7 @@ using namespace thfhe;
 
 namespace {
 
-// ------------------------------------------------------------------------------------------------------
-// key transform
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sk_key_transform_kernel(const int32_t *__restrict__ polys, long npolys,
-                                                                const cplx *__restrict__ tw, cplx *__restrict__ spec) {
-    __shared__ cplx sT1[512];
-    __shared__ cplx sT2[64];
-    __shared__ cplx sX[4][kXbufSlots];
-    for (int t = threadIdx.x; t < 512; t += 256) sT1[t] = tw[t];
-    if (threadIdx.x < 64) sT2[threadIdx.x] = tw[512 + threadIdx.x];
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long q = (long)blockIdx.x * 4 + wave;
-    if (q >= npolys) return;
-    cplx zlo[8], zhi[8];
-    key_limbs_to_z(lane, polys + q * 1024, zlo, zhi);
-    cplx *xb = sX[wave];
-    wave_fft_fwd(lane, zlo, xb, sT1, sT2);
-    wave_fft_fwd(lane, zhi, xb, sT1, sT2);
-    cplx *out = spec + q * 1024;
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-        out[m * 64 + lane] = cplx{zlo[m].re * (1.0 / 512), zlo[m].im * (1.0 / 512)};
-        out[512 + m * 64 + lane] = cplx{zhi[m].re * (1.0 / 512), zhi[m].im * (1.0 / 512)};
-    }
-}
+#include "thfhe_transform.h"
 
 // ------------------------------------------------------------------------------------------------------
 // prologue: tmp = (0, cb) + cx * x + cy * y ; bara = decode_message(tmp.a, 2N) ; barb likewise
@@ -175,8 +150,8 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
     constexpr int DPC = 8 / W;   // ring DMAs per wave and chunk
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    const W64 w64{a.tw[512 + 1 * 8 + (lane & 7)]};
-    const LaneRoots roots{a.tw[576 + 2 * lane], a.tw[576 + 2 * lane + 1]};
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
+    const LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
     const LaneTw tw = make_lane_tw(roots);
     const long job = (long)blockIdx.x * W + wave;
     const bool has_job = job < a.jobs;
@@ -339,8 +314,8 @@ __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) 
     __shared__ cplx sX[8][kXbufSlots];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    const W64 w64{a.tw[512 + 1 * 8 + (lane & 7)]};
-    const LaneRoots roots{a.tw[576 + 2 * lane], a.tw[576 + 2 * lane + 1]};
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
+    const LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
     const long job = blockIdx.x;
     const uniform_i32_ptr bara = as_uniform(a.bara + job * a.n_pad);
     const int Bgbit = a.Bgbit;
@@ -807,7 +782,6 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     // ... and, where its shape allows, batches from this size on sk_keyswitch_staged_kernel (rows staged in LDS, the digit selects an address)
     int coop_max_jobs = 768;    // remainders (batch mod 2048) up to this many rotations use the cooperative (latency) kernel
     int ring4_max_jobs = 1024;  // ... above it and up to this many, the four-wave ring kernel (launch_br)
-    DevBuf d_tw;
     // workspace
     int n_pad = 0;
     DevBuf d_bara, d_barb, d_u;
@@ -1017,20 +991,14 @@ int thfhe_ctx_create(const thfhe_params *p, const int32_t *bk_coeff, const int32
     c->n_pad = (p->n + 3) & ~3;
     c->ks_w = ks_words_per_lane(p->n);
     const int row_words = 64 * c->ks_w;
-    // twiddles
-    std::vector<cplx> tw(576 + 128);  // T1[512] T2[64] lane roots[128]
-    make_twiddles_1024(tw.data(), tw.data() + 512);
-    make_lane_roots_1024(tw.data() + 576);
-    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
-    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(c->upload_twiddles(1024));
     // bootstrapping key: upload coefficients, transform on device
     DevBuf coeff, raw;  // upload staging
     const long npolys = (long)p->n * 2 * p->l * 2;
     THFHE_TRY(coeff.grow((size_t)npolys * 1024 * sizeof(int32_t)));
     THFHE_HIP(hipMemcpyAsync(coeff.as<int32_t>(), bk_coeff, (size_t)npolys * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     THFHE_TRY(c->d_bk.grow((size_t)npolys * 1024 * sizeof(cplx)));
-    hipLaunchKernelGGL(sk_key_transform_kernel, dim3((unsigned)((npolys + 3) / 4)), dim3(256), 0, c->stream, coeff.as<int32_t>(), npolys, c->d_tw.as<cplx>(), c->d_bk.as<cplx>());
-    THFHE_HIP(hipGetLastError());
+    THFHE_TRY((launch_torus_transform<1024, 32>(c->stream, coeff.as<int32_t>(), npolys, c->d_tw.as<cplx>(), c->d_bk.as<cplx>())));
     // key-switching key: pad rows to 640 words
     const long rows = (long)p->N * p->ks_t * ((1 << p->ks_basebit) - 1);
     THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));

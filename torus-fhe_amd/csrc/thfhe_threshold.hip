@@ -30,7 +30,7 @@ __global__ __launch_bounds__(64) void share_transform_kernel(const int32_t *__re
     const int lane = threadIdx.x;
     for (int t = lane; t < 512; t += 64) sT1[t] = tw[t];
     __syncthreads();
-    const W64 w64{tw[512 + 1 * 8 + (lane & 7)]};
+    const W64 w64{tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
     cplx z[8];
     int big = 0;
 #pragma unroll
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void partial_decrypt_kernel(const int32_t *__r
     for (int t = threadIdx.x; t < 512; t += 256) sT1[t] = tw[t];
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const W64 w64{tw[512 + 1 * 8 + (lane & 7)]};
+    const W64 w64{tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
     const long c = (long)blockIdx.x * 4 + wave;
     if (c >= count) return;
     cplx zlo[8], zhi[8], S[8];
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void final_decrypt_kernel(const int32_t *__res
 }  // namespace
 
 struct THFHE_INTERNAL thfhe_poly_ctx : DevCtx {
-    DevBuf d_tw, d_spec, d_flag;
+    DevBuf d_spec, d_flag;
     DevBuf d_buf[4];
 };
 
@@ -126,13 +126,9 @@ int thfhe_poly_ctx_create(int device, int N, thfhe_poly_ctx **out) {
     std::unique_ptr<thfhe_poly_ctx> c(new (std::nothrow) thfhe_poly_ctx);
     if (!c) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
     THFHE_TRY(c->open(device, false));
-    std::vector<cplx> tw(576);
-    make_twiddles_1024(tw.data(), tw.data() + 512);
-    THFHE_TRY(c->d_tw.grow(tw.size() * sizeof(cplx)));
+    THFHE_TRY(c->upload_twiddles(1024));
     THFHE_TRY(c->d_spec.grow(512 * sizeof(cplx)));
     THFHE_TRY(c->d_flag.grow(sizeof(int)));
-    THFHE_HIP(hipMemcpyAsync(c->d_tw.as<cplx>(), tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipStreamSynchronize(c->stream));
     *out = c.release();
     return THFHE_OK;
 }
