@@ -111,6 +111,38 @@ int thfhe_bootstrap(thfhe_ctx *ctx, int32_t mu, const int32_t *x, int32_t *out, 
 int thfhe_bootstrap_wo_keyswitch(thfhe_ctx *ctx, int32_t mu, const int32_t *x, int32_t *out_N1, size_t count);
 int thfhe_keyswitch(thfhe_ctx *ctx, const int32_t *in_N1, int32_t *out, size_t count);
 
+/* ---- programmable bootstrapping (PBS): a lookup table on a small encrypted integer, evaluated during the blind rotation.
+ *
+ * Integer encoding (padding bit): m in [0, p), p a power of two, is the Torus32 word m * 2^32 / (2p); the phase stays in [0, 1/2) and
+ * the negacyclic wrap never inverts a valid input.
+ * Prologue: x = w0*in0 + w1*in1 + w2*in2 + (0, ..., 0, bias), word-wise mod 2^32 over the first n_inputs inputs; the bias is added to the
+ *   body only.  With w = (p_b, 1) a two-input function f(a, b) is a one-input table on p_b*a + b.
+ * Mod-switch with theta outputs (many-LUT), theta in {1, 2, 4}: every word of x is rounded to a multiple of theta in Z_2N,
+ *   bar = modswitch_{2N/theta}(word) * theta  (theta = 1: the mod-switch of thfhe_bootstrap, bit for bit).
+ * Accumulator: (0, X^{-barb} * tv), tv = the sample's test vector of N Torus32 words; the blind rotation is the one of thfhe_bootstrap
+ *   (same CMux chain, same skip of mask words with bara == 0).
+ * Extraction: for every j < theta, coefficient j of the accumulator becomes an LWE(N) record: a'_i = a_{j-i} for i <= j,
+ *   a'_i = -a_{N+j-i} for i > j, b' = body_j.  thfhe_lut_bootstrap then key-switches the count*theta records.
+ * Test-vector layout (built on the host, e.g. thfhe.lut.test_vector): message m occupies the box of N/p coefficients centred on m*N/p;
+ *   inside the box entry i holds f_{i mod theta}(m); the lower half-box of m = 0 wraps to the top of tv with its sign negated.
+ *   tv = (mu, ..., mu), theta = 1, w = (1), bias = 0 is exactly thfhe_bootstrap(mu).
+ * tv: HOST int32[n_luts][N], 1 <= n_luts <= 1024.  lut_index: HOST int32[count] table of each sample, or NULL (every sample uses table 0).
+ * in0/in1/in2: HOST records int32[count][n+1] (in1, in2 may be NULL when n_inputs does not name them).
+ * out: HOST int32[count][theta][n+1] (thfhe_lut_bootstrap) or int32[count][theta][N+1] (thfhe_lut_bootstrap_wo_keyswitch).
+ * Arguments are checked on the host before any device work (THFHE_E_INVALID): null pointers, n_inputs outside 1..3, theta not in
+ * {1, 2, 4}, n_luts outside 1..1024, any lut_index entry outside 0..n_luts-1.  count 0 returns THFHE_OK.  Single key, N = 1024. */
+typedef struct thfhe_lut_spec {
+    int32_t n_inputs;   /* 1..3 */
+    int32_t weights[3]; /* integer weights of in0, in1, in2 */
+    int32_t bias;       /* Torus32 constant added to the body */
+    int32_t theta;      /* outputs per rotation: 1, 2 or 4 */
+} thfhe_lut_spec;
+
+int thfhe_lut_bootstrap(thfhe_ctx *ctx, const thfhe_lut_spec *spec, const int32_t *tv, int n_luts, const int32_t *lut_index,
+                        const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count);
+int thfhe_lut_bootstrap_wo_keyswitch(thfhe_ctx *ctx, const thfhe_lut_spec *spec, const int32_t *tv, int n_luts, const int32_t *lut_index,
+                                     const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1, size_t count);
+
 /* ---- device-buffer API: records already resident in HBM (what bench.py times).  Pointers come from
  * thfhe_dev_alloc (or any hipMalloc in this process).  Calls enqueue on the context's stream and
  * return; thfhe_sync waits. */

@@ -635,6 +635,27 @@ THFHE_FN void extract16(int lane, const int32_t *acc_mask, const int32_t *acc_bo
     }
     if (lane == 0) out[1024] = acc_body[0];
 }
+// programmable bootstrap: acc = (0, X^{-barb} * tv), tv = N = 1024 Torus32 words in global memory (read once, from L2)
+THFHE_FN void acc_init_tv16(int lane, int32_t *acc_mask, int32_t *acc_body, int barb, const int32_t *tv) {
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        int q = lane + 64 * m;
+        int e = (q + barb) & 2047;
+        const int32_t v = tv[e & 1023];
+        acc_mask[q] = 0;
+        acc_body[q] = (e & 1024) ? (int32_t)(0u - (uint32_t)v) : v;
+    }
+}
+// sample extraction at coefficient j (0 <= j < N): a'_i = a_{j-i} for i <= j, a'_i = -a_{N+j-i} for i > j, b = body_j
+THFHE_FN void extract_at16(int lane, const int32_t *acc_mask, const int32_t *acc_body, int j, int32_t *out) {
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        int q = lane + 64 * m;
+        const int32_t v = acc_mask[(j - q) & 1023];
+        out[q] = q <= j ? v : (int32_t)(0u - (uint32_t)v);
+    }
+    if (lane == 0) out[1024] = acc_body[j];
+}
 // folded two-limb inputs of a Torus32 polynomial (the ciphertext masks of the threshold partial decryption)
 THFHE_FN void key_limbs_to_z(int lane, const int32_t *poly, cplx (&zlo)[8], cplx (&zhi)[8]) {
 #pragma unroll

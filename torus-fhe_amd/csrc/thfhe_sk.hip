@@ -5,6 +5,8 @@
 //   (thfhe_transform.h)       rows -> two-limb FP64 spectra in the blind-rotate kernel's register order
 //   sk_prologue_kernel        gate linear part (J/gates.jl:15-177) + mod-switch decode_message(.,2N)
 //                             (J/bootstrap.jl:80-81) -> bara[job][n], barb[job]
+//   sk_lut_prologue_kernel    programmable bootstrap (thfhe_lut_bootstrap): weighted sum of 1-3 inputs + bias, mod-switch to multiples of theta;
+//                             the blind-rotate kernels' LUT instantiations start from a test vector and extract theta coefficients
 //   sk_blind_rotate_ring_kernel / sk_blind_rotate_coop_kernel   blind_rotate_and_extract (J/bootstrap.jl:38-65): accumulator in
 //                             LDS for all n CMuxes; throughput (8 gates per workgroup, key through an LDS-DMA ring) and latency
 //                             (one workgroup per gate) variants
@@ -81,6 +83,28 @@ __global__ __launch_bounds__(256) void sk_prologue_kernel(const int32_t *__restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// programmable-bootstrap prologue: x = w0 in0 + w1 in1 + w2 in2 + (0, ..., 0, bias) word-wise mod 2^32, then every word rounded to a
+// multiple of theta in Z_2N: bar = modswitch_{2N/theta}(word) * theta (theta = 1: modswitch2n).  grid.y strides over the jobs.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sk_lut_prologue_kernel(const int32_t *__restrict__ in0, const int32_t *__restrict__ in1,
+                                                               const int32_t *__restrict__ in2, int n_inputs, int32_t w0, int32_t w1, int32_t w2,
+                                                               int32_t bias, int log2_theta, int n, int n_pad, int log2_2n, long jobs,
+                                                               int32_t *__restrict__ bara, int32_t *__restrict__ barb) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    for (long job = blockIdx.y; job < jobs; job += gridDim.y) {
+        const size_t off = (size_t)job * (n + 1) + i;
+        uint32_t v = (uint32_t)w0 * (uint32_t)in0[off];
+        if (n_inputs > 1) v += (uint32_t)w1 * (uint32_t)in1[off];
+        if (n_inputs > 2) v += (uint32_t)w2 * (uint32_t)in2[off];
+        if (i == n) v += (uint32_t)bias;
+        const int32_t bar = (int32_t)((uint32_t)modswitch2n((int32_t)v, log2_2n - log2_theta) << log2_theta);
+        if (i == n) barb[job] = bar;
+        else bara[job * n_pad + i] = bar;
+    }
+}
+
 THFHE_STAMP_STORAGE
 
 // arguments of the blind-rotate kernels
@@ -89,10 +113,14 @@ struct BRArgs {
     const cplx *tw;        // T1[512] ++ T2[64]
     const int32_t *bara;   // [jobs][n_pad]
     const int32_t *barb;   // [jobs]
-    int32_t *out;          // [jobs][N+1]
+    int32_t *out;          // [jobs][N+1]; LUT kernels: [jobs][theta][N+1]
     long jobs;
     int n, n_pad, Bgbit;
     int32_t mu;
+    // LUT kernels only (programmable bootstrap): accumulator X^{-barb} * tv, coefficients 0 .. theta-1 extracted
+    const int32_t *tv;       // [n_luts][N]
+    const int32_t *lut_idx;  // [jobs] test vector of each job, or null: table 0
+    int theta;               // 1, 2 or 4
 };
 
 // ------------------------------------------------------------------------------------------------------
@@ -141,7 +169,8 @@ struct BRArgs {
 // W = waves (= jobs) per workgroup.  W = 8 is the throughput shape described above.  W = 4 (one wave per SIMD, 92 KiB of LDS, each wave
 // brings TWO slices of a chunk) is the shape for batches that cannot give every CU eight jobs (<= 1024 rotations): a wave alone on its
 // SIMD issues at ~87 % of what a pair reaches together (tools/probes/issue_probe.hip), so four jobs finish much sooner than eight.
-template <int L, int V = 1, int W = 8>
+// LUT = programmable bootstrap: the accumulator starts from a test vector and theta coefficients are extracted; the CMux loop is the same code.
+template <int L, int V = 1, int W = 8, bool LUT = false>
 __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_kernel(BRArgs a) {
     __shared__ __attribute__((aligned(4096))) int32_t sAcc[W][2048];   // rotated_digits_z ORs byte offsets into the polynomial base
     __shared__ cplx sX[W][kXbufSlots];
@@ -159,7 +188,10 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
     cplx *xb = sX[wave];
     const uniform_i32_ptr bara = as_uniform(a.bara + (has_job ? job : 0) * a.n_pad);   // job is wave-uniform: scalar loads
     const int Bgbit = a.Bgbit;
-    if (has_job) acc_init16(lane, acc, acc + 1024, a.barb[job], a.mu);
+    if (has_job) {
+        if constexpr (LUT) acc_init_tv16(lane, acc, acc + 1024, a.barb[job], a.tv + (a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0));
+        else acc_init16(lane, acc, acc + 1024, a.barb[job], a.mu);
+    }
 
     const long total_chunks = (long)a.n * ROWS * 4;
     const cplx *gsrc = a.bk + wave * (64 * DPC) + lane;
@@ -281,7 +313,13 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
     }
     STAMP_FLUSH(blockIdx.x, wave);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (has_job) extract16(lane, acc, acc + 1024, a.out + job * 1025);
+    if (has_job) {
+        if constexpr (LUT) {
+            for (int j = 0; j < a.theta; j++) extract_at16(lane, acc, acc + 1024, j, a.out + (job * a.theta + j) * 1025);
+        } else {
+            extract16(lane, acc, acc + 1024, a.out + job * 1025);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -306,7 +344,7 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
 __device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ void pin() { asm volatile("" ::: "memory"); }  // memory operations do not move across this point
 
-template <int L, int PACE = 1>
+template <int L, int PACE = 1, bool LUT = false>
 __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) {
     constexpr int ROWS = 2 * L;
     __shared__ __attribute__((aligned(4096))) int32_t sAcc[2048];
@@ -319,7 +357,10 @@ __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) 
     const long job = blockIdx.x;
     const uniform_i32_ptr bara = as_uniform(a.bara + job * a.n_pad);
     const int Bgbit = a.Bgbit;
-    if (wave == 0) acc_init16(lane, sAcc, sAcc + 1024, a.barb[job], a.mu);
+    if (wave == 0) {
+        if constexpr (LUT) acc_init_tv16(lane, sAcc, sAcc + 1024, a.barb[job], a.tv + (a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0));
+        else acc_init16(lane, sAcc, sAcc + 1024, a.barb[job], a.mu);
+    }
     const int c = (wave >> 1) & 1, h = wave & 1, half = wave >> 2, r0 = half * L;  // role in M: rows r0 .. r0+L-1 of (column c, limb h)
     unsigned int *ap = reinterpret_cast<unsigned int *>(sAcc) + c * 1024;
     cplx *xb = sX[wave];
@@ -422,7 +463,11 @@ __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) 
         i = inext;
     }
     STAMP_FLUSH(blockIdx.x, wave);
-    if (wave == 0) extract16(lane, sAcc, sAcc + 1024, a.out + job * 1025);
+    if constexpr (LUT) {
+        if (wave < a.theta) extract_at16(lane, sAcc, sAcc + 1024, wave, a.out + (job * a.theta + wave) * 1025);   // one wave per output
+    } else {
+        if (wave == 0) extract16(lane, sAcc, sAcc + 1024, a.out + job * 1025);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -785,6 +830,7 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     // workspace
     int n_pad = 0;
     DevBuf d_bara, d_barb, d_u;
+    DevBuf d_tv, d_lut_idx;   // programmable bootstrap: test-vector table and per-sample table index (grow-only)
     // staging for the host-buffer API
     Stage stage;
     // gate-DAG executor: wire table and index tables (grow-only, reused by every thfhe_dag_run on this context)
@@ -801,30 +847,30 @@ int ensure_workspace(thfhe_ctx *c, size_t jobs) {
     return rc;
 }
 
-// One launch of `a.jobs` rotations on one kernel shape.
-template <int L>
+// One launch of `a.jobs` rotations on one kernel shape.  LUT: the programmable-bootstrap instantiation (the developer variants are gate-only).
+template <int L, bool LUT>
 void launch_coop(const BRArgs &a, hipStream_t s) {
 #ifdef THFHE_VARIANTS
     static const int pace = std::getenv("THFHE_COOP_PACE") ? std::atoi(std::getenv("THFHE_COOP_PACE")) : 1;
-    if (pace == 0) { hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 0>), dim3((unsigned)a.jobs), dim3(512), 0, s, a); return; }
-    if (pace == 2) { hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 2>), dim3((unsigned)a.jobs), dim3(512), 0, s, a); return; }
-    if (pace == 4) { hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 4>), dim3((unsigned)a.jobs), dim3(512), 0, s, a); return; }
+    if (!LUT && pace == 0) { hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 0>), dim3((unsigned)a.jobs), dim3(512), 0, s, a); return; }
+    if (!LUT && pace == 2) { hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 2>), dim3((unsigned)a.jobs), dim3(512), 0, s, a); return; }
+    if (!LUT && pace == 4) { hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 4>), dim3((unsigned)a.jobs), dim3(512), 0, s, a); return; }
 #endif
-    hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 1>), dim3((unsigned)a.jobs), dim3(512), 0, s, a);
+    hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 1, LUT>), dim3((unsigned)a.jobs), dim3(512), 0, s, a);
 }
-template <int L>
+template <int L, bool LUT>
 void launch_ring4(const BRArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 1, 4>), dim3((unsigned)((a.jobs + 3) / 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 1, 4, LUT>), dim3((unsigned)((a.jobs + 3) / 4)), dim3(256), 0, s, a);
 }
-template <int L>
+template <int L, bool LUT>
 void launch_ring8(const BRArgs &a, hipStream_t s) {
     const dim3 grid((unsigned)((a.jobs + 7) / 8)), block(512);
 #ifdef THFHE_VARIANTS  // developer A/B builds only: 8 = first transpose through the LDS (variant "r")
     static const int variant = std::getenv("THFHE_RING_VARIANT") ? std::atoi(std::getenv("THFHE_RING_VARIANT")) : 0;
-    if (variant == 8) { hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 0>), grid, block, 0, s, a); return; }
-    if (variant == 3) { hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 3>), grid, block, 0, s, a); return; }   // forward in registers, inverse through the LDS
+    if (!LUT && variant == 8) { hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 0>), grid, block, 0, s, a); return; }
+    if (!LUT && variant == 3) { hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 3>), grid, block, 0, s, a); return; }   // forward in registers, inverse through the LDS
 #endif
-    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 1>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 1, 8, LUT>), grid, block, 0, s, a);
 }
 
 // Kernel choice for a batch of rotations.  Measured on one MI355X (256 CUs, SK-128; profiles/r04_time_batch.txt): a round of the
@@ -834,24 +880,39 @@ void launch_ring8(const BRArgs &a, hipStream_t s) {
 // ring4_max (1 024), four-wave ring + one cooperative round up to ring4_max + 256 (12.9 ms), else one more eight-wave round.
 // (3 072 rotations: 30.1 ms as one launch of 384 eight-wave workgroups, 24.8 ms as 2 048 + 1 024.)  The pieces are independent jobs
 // on disjoint slices of the same arrays, launched back to back on the context's stream.
-template <int L>
+template <int L, bool LUT>
 void launch_br(const BRArgs &a, hipStream_t s, int coop_max, int ring4_max) {
     auto piece = [&](long first, long count) {
         BRArgs b = a;
-        b.bara += first * a.n_pad, b.barb += first, b.out += first * 1025, b.jobs = count;
+        b.bara += first * a.n_pad, b.barb += first, b.jobs = count;
+        b.out += first * (LUT ? a.theta : 1) * 1025;
+        if (LUT && b.lut_idx) b.lut_idx += first;
         return b;
     };
     constexpr long kRound = 2048;   // 256 CUs x 8 jobs
     const long full = (coop_max > 0 || ring4_max > 0) ? a.jobs / kRound * kRound : a.jobs;   // both thresholds 0: everything on the eight-wave kernel
-    if (full > 0) launch_ring8<L>(piece(0, full), s);
+    if (full > 0) launch_ring8<L, LUT>(piece(0, full), s);
     const long r = a.jobs - full;
     if (r == 0) return;
-    if (r <= coop_max) launch_coop<L>(piece(full, r), s);
-    else if (r <= ring4_max) launch_ring4<L>(piece(full, r), s);
+    if (r <= coop_max) launch_coop<L, LUT>(piece(full, r), s);
+    else if (r <= ring4_max) launch_ring4<L, LUT>(piece(full, r), s);
     else if (ring4_max > 0 && coop_max > 0 && r <= ring4_max + (coop_max < 256 ? coop_max : 256)) {
-        launch_ring4<L>(piece(full, ring4_max), s);
-        launch_coop<L>(piece(full + ring4_max, r - ring4_max), s);
-    } else launch_ring8<L>(piece(full, r), s);
+        launch_ring4<L, LUT>(piece(full, ring4_max), s);
+        launch_coop<L, LUT>(piece(full + ring4_max, r - ring4_max), s);
+    } else launch_ring8<L, LUT>(piece(full, r), s);
+}
+
+// the blind rotations of `a` on the kernel shapes of launch_br, for the context's decomposition length
+template <bool LUT>
+int launch_rotations(thfhe_ctx *c, const BRArgs &a) {
+    switch (c->p.l) {
+    case 1: launch_br<1, LUT>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
+    case 2: launch_br<2, LUT>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
+    case 3: launch_br<3, LUT>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
+    case 4: launch_br<4, LUT>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
+    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
+    }
+    return THFHE_OK;
 }
 
 // rotations (prologue + blind rotate) of `jobs` = gates * rot_per_gate jobs into c->d_u
@@ -867,13 +928,29 @@ int enqueue_rotations(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1
                        ilog2(2 * c->p.N), (long)jobs, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
     BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, n, c->n_pad, c->p.Bgbit, mu};
-    switch (c->p.l) {
-    case 1: launch_br<1>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
-    case 2: launch_br<2>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
-    case 3: launch_br<3>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
-    case 4: launch_br<4>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
-    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
-    }
+    rc = launch_rotations<false>(c, a);
+    if (rc) return rc;
+    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
+    THFHE_HIP(hipGetLastError());
+    return THFHE_OK;
+}
+
+// programmable bootstrap of `count` samples (lut prologue + LUT blind rotations) into c->d_u: count x theta records of N+1 words
+int enqueue_lut_rotations(thfhe_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0, const int32_t *d1, const int32_t *d2, size_t count,
+                          const int32_t *d_tv, const int32_t *d_idx) {
+    int rc = ensure_workspace(c, count);
+    if (!rc) rc = c->d_u.grow(count * sp.theta * 1025 * sizeof(int32_t));
+    if (rc) return rc;
+    const int n = c->p.n;
+    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
+    dim3 pg((unsigned)((n + 1 + 255) / 256), (unsigned)(count < 65535 ? count : 65535));
+    hipLaunchKernelGGL(sk_lut_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, sp.n_inputs, sp.weights[0], sp.weights[1], sp.weights[2],
+                       sp.bias, ilog2(sp.theta), n, c->n_pad, ilog2(2 * c->p.N), (long)count, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
+    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
+    BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)count, n, c->n_pad, c->p.Bgbit,
+             0, d_tv, d_idx, sp.theta};
+    rc = launch_rotations<true>(c, a);
+    if (rc) return rc;
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
@@ -957,6 +1034,46 @@ int gates_dev_locked(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1,
     int rc = enqueue_rotations(c, op, d0, d1, d2, count, rot, 1 << 29);
     if (rc) return rc;
     return enqueue_keyswitch(c, c->d_u.as<int32_t>(), dout, count, rot, true);
+}
+
+// Host-side checks of a programmable-bootstrap call, before any device work: null pointers first (no context needed), then the spec and
+// every lut_index entry (the kernel cannot report an index out of range).
+int lut_validate(const thfhe_lut_spec *sp, const int32_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0, const int32_t *in1,
+                 const int32_t *in2, const int32_t *out, size_t count) {
+    if (!sp || !tv || !in0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (sp->n_inputs < 1 || sp->n_inputs > 3) return thfhe_fail(THFHE_E_INVALID, "lut spec: n_inputs must be 1, 2 or 3");
+    if ((sp->n_inputs > 1 && !in1) || (sp->n_inputs > 2 && !in2)) return thfhe_fail(THFHE_E_INVALID, "null operand: the spec names more inputs");
+    if (sp->theta != 1 && sp->theta != 2 && sp->theta != 4) return thfhe_fail(THFHE_E_INVALID, "lut spec: theta must be 1, 2 or 4");
+    if (n_luts < 1 || n_luts > 1024) return thfhe_fail(THFHE_E_INVALID, "n_luts must be 1 .. 1024");
+    if (count > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "count too large");
+    if (lut_index)
+        for (size_t g = 0; g < count; g++)
+            if (lut_index[g] < 0 || lut_index[g] >= n_luts) return thfhe_fail(THFHE_E_INVALID, "lut_index out of range (0 .. n_luts-1)");
+    return THFHE_OK;
+}
+
+// thfhe_lut_bootstrap (keyswitch) / thfhe_lut_bootstrap_wo_keyswitch: out = count x theta records of n+1 (resp. N+1) words
+int lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
+                  const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch) {
+    int rc = lut_validate(sp, tv, n_luts, lut_index, in0, in1, in2, out, count);
+    if (rc) return rc;
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (count == 0) return THFHE_OK;
+    const thfhe_lut_spec s = *sp;
+    const size_t in_words = count * (c->p.n + 1), outs = count * s.theta;
+    const size_t in_bytes = in_words * sizeof(int32_t);
+    const size_t out_bytes = outs * (keyswitch ? c->p.n + 1 : c->p.N + 1) * sizeof(int32_t);
+    const size_t stage_words = keyswitch ? outs * (c->p.n + 1) : in_words;   // the key switch writes count x theta records into stage.out
+    return ctx_staged(c, stage_words, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, {in_bytes, in_bytes, in_bytes}, [&] {
+        int r = c->d_tv.grow((size_t)n_luts * 1024 * sizeof(int32_t));
+        if (!r && lut_index) r = c->d_lut_idx.grow(count * sizeof(int32_t));
+        if (r) return r;
+        THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if (lut_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), lut_index, count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        r = enqueue_lut_rotations(c, s, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), count, c->d_tv.as<int32_t>(),
+                                  lut_index ? c->d_lut_idx.as<int32_t>() : nullptr);
+        return r || !keyswitch ? r : enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), outs, 1, true);
+    }, keyswitch ? c->stage.out : c->d_u, out, out_bytes);
 }
 
 }  // namespace
@@ -1133,6 +1250,16 @@ int thfhe_bootstrap(thfhe_ctx *c, int32_t mu, const int32_t *x, int32_t *out, si
         int rc = enqueue_rotations(c, kOpIdentity, c->stage.in_ptr(0), c->stage.in_ptr(0), nullptr, count, 1, mu);
         return rc ? rc : enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), count, 1, false);
     }, c->stage.out, out, words * sizeof(int32_t));
+}
+
+int thfhe_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *spec, const int32_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
+                        const int32_t *in1, const int32_t *in2, int32_t *out, size_t count) {
+    return lut_bootstrap(c, spec, tv, n_luts, lut_index, in0, in1, in2, out, count, true);
+}
+
+int thfhe_lut_bootstrap_wo_keyswitch(thfhe_ctx *c, const thfhe_lut_spec *spec, const int32_t *tv, int n_luts, const int32_t *lut_index,
+                                     const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1, size_t count) {
+    return lut_bootstrap(c, spec, tv, n_luts, lut_index, in0, in1, in2, out_N1, count, false);
 }
 
 int thfhe_keyswitch(thfhe_ctx *c, const int32_t *in_N1, int32_t *out, size_t count) {

@@ -130,6 +130,11 @@ def make_params(name=None, **kw):
     return Params(**d)
 
 
+class LutSpec(C.Structure):
+    """thfhe_lut_spec (include/thfhe_hip.h): prologue x = sum w_q in_q + (0, bias) over n_inputs inputs, theta outputs per rotation."""
+    _fields_ = [("n_inputs", C.c_int32), ("weights", C.c_int32 * 3), ("bias", C.c_int32), ("theta", C.c_int32)]
+
+
 _lib = None
 
 _i32p = C.POINTER(C.c_int32)
@@ -153,6 +158,8 @@ SIGNATURES = {
     "thfhe_bootstrap": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_keyswitch": (C.c_int, [_vp, _i32p, _i32p, C.c_size_t]),
+    "thfhe_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.POINTER(LutSpec), _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_dev_alloc": (_vp, [_vp, C.c_size_t]),
     "thfhe_dev_free": (None, [_vp, _vp]),
     "thfhe_copy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
@@ -257,6 +264,12 @@ def _check(rc):
 
 def _p32(a):
     return a.ctypes.data_as(_i32p) if a is not None else None
+
+
+def _wrap32(v):
+    """An integer taken mod 2^32 as a signed int32 (weights and Torus32 constants)."""
+    v = int(v) & 0xFFFFFFFF
+    return v - (1 << 32) if v >= 1 << 31 else v
 
 
 def _rec(a, words):
@@ -456,6 +469,38 @@ class CloudKey(_EvalKey):
         u = _rec(u, self.params.N + 1)
         out = np.empty((u.shape[0], self.words), np.int32)
         _check(lib().thfhe_keyswitch(self.h, _p32(u), _p32(out), u.shape[0]))
+        return out
+
+    def lut_bootstrap(self, tv, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
+        """Programmable bootstrap (include/thfhe_hip.h, thfhe_lut_bootstrap): sample g evaluates test vector tv[lut_index[g]] (table 0 without
+        an index) on x = sum_q weights[q] * (x, y, z)[q] + (0, bias), theta outputs per rotation.  tv: int32[n_luts][N] (thfhe.lut.test_vector).
+        Returns int32[count, theta, n+1]."""
+        return self._lut(tv, x, y, z, weights, bias, theta, lut_index, True)
+
+    def lut_bootstrap_wo_keyswitch(self, tv, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
+        """lut_bootstrap without the key switch: int32[count, theta, N+1] records under the ring key."""
+        return self._lut(tv, x, y, z, weights, bias, theta, lut_index, False)
+
+    def _lut(self, tv, x, y, z, weights, bias, theta, lut_index, keyswitch):
+        given = [v for v in (x, y, z) if v is not None]
+        if any(v is None for v in (x, y, z)[:len(given)]) or len(given) != len(weights):
+            raise ValueError("give the inputs in order (x, then y, then z) and one weight per input")
+        ins = [_rec(v, self.words) for v in given]
+        _same_count(*ins)
+        tv = np.ascontiguousarray(tv, np.int32).reshape(-1, self.params.N)
+        count = ins[0].shape[0]
+        idx = None
+        if lut_index is not None:
+            idx = np.ascontiguousarray(lut_index, np.int32).reshape(-1)
+            if idx.shape[0] != count:
+                raise ValueError(f"lut_index holds {idx.shape[0]} entries for {count} samples")
+        w = list(weights) + [0] * (3 - len(weights))
+        spec = LutSpec(len(ins), (C.c_int32 * 3)(*[_wrap32(v) for v in w]), _wrap32(bias), int(theta))
+        words = self.words if keyswitch else self.params.N + 1
+        out = np.empty((count, int(theta) if theta in (1, 2, 4) else 1, words), np.int32)
+        fn = lib().thfhe_lut_bootstrap if keyswitch else lib().thfhe_lut_bootstrap_wo_keyswitch
+        p = [_p32(v) for v in ins] + [None] * (3 - len(ins))
+        _check(fn(self.h, C.byref(spec), _p32(tv), tv.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
         return out
 
     def set_ring4_threshold(self, max_jobs):

@@ -1,0 +1,70 @@
+"""Host helpers of programmable bootstrapping (include/thfhe_hip.h, thfhe_lut_bootstrap): the padding-bit integer encoding and the
+test-vector layout the blind rotation expects.
+
+A message m in [0, p), p a power of two, is the Torus32 word m * 2^32 / (2p): its phase stays in [0, 1/2), so the negacyclic wrap never
+inverts a valid input.  In a test vector of N words, message m owns the box of N/p coefficients centred on m*N/p; entry i of the box holds
+f_{i mod theta}(m), and the lower half-box of m = 0 wraps to the top of the vector with its sign negated.  A rotation by a phase inside
+m's box, rounded to a multiple of theta, then brings f_0(m) .. f_{theta-1}(m) to coefficients 0 .. theta-1.
+"""
+import numpy as np
+
+MU8 = 1 << 29  # the boolean encoding of the gates: true = +2^29, false = -2^29
+
+
+def _check_p(p):
+    if p < 2 or p & (p - 1):
+        raise ValueError(f"p must be a power of two >= 2, got {p}")
+
+
+def _to_i32(v):
+    return (np.asarray(v, np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def encode(m, p):
+    """Torus32 words of the messages m in [0, p) (padding bit): m * 2^32 / (2p)."""
+    _check_p(p)
+    m = np.asarray(m, np.int64)
+    if np.any((m < 0) | (m >= p)):
+        raise ValueError(f"messages must lie in [0, {p})")
+    return _to_i32(m * ((1 << 32) // (2 * p)))
+
+
+def decode(phase_words, p):
+    """Nearest message of each phase: round(phase * 2p / 2^32) mod 2p.  A valid result lies in [0, p); p .. 2p-1 means the phase left [0, 1/2)."""
+    _check_p(p)
+    u = np.asarray(phase_words, np.int64) & 0xFFFFFFFF
+    step = (1 << 32) // (2 * p)
+    return ((u + step // 2) // step) % (2 * p)
+
+
+def test_vector(tables, p, theta=1, N=1024):
+    """int32[N] test vector: tables = theta arrays of p Torus32 output words (tables[j][m] = f_j(m)); with theta = 1 one array of p words will do."""
+    _check_p(p)
+    if theta not in (1, 2, 4):
+        raise ValueError("theta must be 1, 2 or 4")
+    T = np.asarray(tables, np.int64)
+    if T.ndim == 1 and theta == 1:
+        T = T[None]
+    if T.shape != (theta, p):
+        raise ValueError(f"expected {theta} tables of {p} words, got shape {T.shape}")
+    box = N // p
+    if box < 2 or (box // 2) % theta:
+        raise ValueError(f"p = {p} leaves half-boxes of {box // 2} coefficients: not a multiple of theta = {theta}")
+    i = np.arange(N)
+    m = (i + box // 2) // box          # 0 .. p; p = the lower half-box of m = 0, wrapped to the top
+    wrap = m == p
+    v = T[i % theta, np.where(wrap, 0, m)]
+    return _to_i32(np.where(wrap, -v, v))
+
+
+def int_outputs(f, p_out, p=None):
+    """Table of integer outputs: encode(f(m), p_out) for m in [0, p) (p defaults to p_out); f(m) is taken mod p_out."""
+    p = p_out if p is None else p
+    _check_p(p)
+    return encode(np.array([int(f(m)) % p_out for m in range(p)], np.int64), p_out)
+
+
+def bool_outputs(f, p):
+    """Table of boolean outputs in the gates' encoding (+2^29 if f(m) else -2^29): LUT results that feed thfhe's gates."""
+    _check_p(p)
+    return _to_i32(np.array([MU8 if f(m) else -MU8 for m in range(p)], np.int64))
