@@ -122,6 +122,14 @@ struct WaveQS {  // multi-key kernels: first transpose in registers, second thro
 
 extern "C" {
 
+// the balanced limb splits themselves, for the Python restatement in tests/bound_inputs.py
+void emu_split_limbs32(int32_t v, double *out /* 2 */) { split_limbs32(v, out[0], out[1]); }
+void emu_split_limbs64(int64_t v, double *out /* 4 */) {
+    double l[4];
+    split_limbs64(v, l);
+    for (int h = 0; h < 4; h++) out[h] = l[h];
+}
+
 // coefficient-domain key polynomials -> spectral layout [poly][limb][m][lane], scaled by 1/512, in the swizzled form of torus_transform_kernel
 void emu_transform_key_polys(const int32_t *polys, int64_t npolys, double *spec /* npolys*2*512*2 doubles */) {
     WaveS w;
@@ -175,7 +183,8 @@ double emu_polymul(const int32_t *small, const int32_t *b, int32_t *out) {
 
 // one CMux on acc[2][1024] with the spectral key of index i (bk_spec laid out by emu_transform_key_polys over
 // the coefficient table [n][2l][2][1024], i.e. poly index ((i*2l + r)*2 + c)).   Mirrors blind_rotate_kernel.
-void emu_mux_rotate(const double *bk_spec, int l_levels, int Bgbit, int i, int barai, int32_t *acc) {
+// Returns the worst distance of an inverse-transform output from an integer (exactness margin of the 2l-row sum).
+double emu_mux_rotate(const double *bk_spec, int l_levels, int Bgbit, int i, int barai, int32_t *acc) {
     Wave w;
     const cplx *BK = reinterpret_cast<const cplx *>(bk_spec);
     const int rows = 2 * l_levels;
@@ -184,6 +193,7 @@ void emu_mux_rotate(const double *bk_spec, int l_levels, int Bgbit, int i, int b
     static cplx S[64][2][2][8], z[64][8];
     static uint32_t t[64][16];
     memset(S, 0, sizeof(S));
+    double worst = 0;
     for (int j = 0; j < 2; j++) {
         for (int l = 0; l < 64; l++) load_rotated16(l, acc + j * 1024, a2n, offset, t[l]);
         for (int p = 1; p <= l_levels; p++) {
@@ -203,8 +213,13 @@ void emu_mux_rotate(const double *bk_spec, int l_levels, int Bgbit, int i, int b
         }
         w.inv(lo);
         w.inv(hi);
-        for (int l = 0; l < 64; l++) acc_update16(l, acc + c * 1024, lo[l], hi[l]);
+        for (int l = 0; l < 64; l++) {
+            for (int m = 0; m < 8; m++)
+                for (double v : {lo[l][m].re, lo[l][m].im, hi[l][m].re, hi[l][m].im}) worst = __builtin_fmax(worst, __builtin_fabs(v - __builtin_rint(v)));
+            acc_update16(l, acc + c * 1024, lo[l], hi[l]);
+        }
     }
+    return worst;
 }
 
 // whole blind rotation + extraction of one job (bara[n], barb given), mirrors the kernel's control flow

@@ -1,0 +1,127 @@
+"""CPU checks of the bound-level input recipe (tests/bound_inputs.py): the extreme key words and digit words decompose as claimed for every
+parameter set and swept shape, the crafted bootstraps reach the limb sum they are meant to reach, and the oracle's schoolbook and NTT
+paths agree on them, so the GPU comparison in test_gpu_exactness_bound.py is against exact values."""
+import numpy as np
+import pytest
+
+import bound_inputs as B
+from test_gpu_param_sweep import MK_SHAPES, SK_SHAPES
+
+
+def _gadgets(O):
+    """(torus bits, l, Bgbit) of every parameter set in oracle_lib and every shape of the GPU parameter sweep; the KMS gadgets too."""
+    import thfhe
+    out = {(p["torus_bits"], p["l"], p["Bgbit"]) for p in O.PARAM_SETS.values()}
+    out |= {(32, l, bg) for _, l, bg, _, _ in SK_SHAPES} | {(64, l, bg) for _, _, l, bg, _, _ in MK_SHAPES}
+    for k in thfhe.KMS_PARAM_SETS.values():
+        out |= {(64, k["l_gsw"], k["bg_gsw"]), (64, k["l_lev"], k["bg_lev"]), (64, k["l_uni"], k["bg_uni"])}
+    return sorted(out)
+
+
+def test_extreme_key_words():
+    assert B.extreme_key_word(32) == 0x7FFF8000
+    assert B.split_limbs32(B.extreme_key_word(32)) == (-2**15, 2**15)
+    assert B.extreme_key_word(64) == 0x7FFF7FFF7FFF8000
+    assert B.split_limbs64(B.extreme_key_word(64)) == [-2**15, -2**15, -2**15, 2**15]
+
+
+def test_digit_words_decompose_to_extreme_digits(O):
+    for bits, l, Bgbit in _gadgets(O):
+        x = B.digit_word(bits, l, Bgbit)
+        d = B.decompose(np.full(4, x), bits, l, Bgbit)
+        e = B.extreme_digit(Bgbit)
+        assert np.all(d == e), (bits, l, Bgbit)
+        parts, pw = B.digit_parts(Bgbit)
+        cut = B.cut_parts(e, parts, pw)
+        assert sum(v << (pw * w) for w, v in enumerate(cut)) == e
+        if parts == 1:
+            assert e == -2**(Bgbit - 1)
+        else:   # every lower part at -2^(pw-1); the top part as low as the digit range allows
+            assert cut[:-1] == [-2**(pw - 1)] * (parts - 1)
+            assert e - 2**(pw * (parts - 1)) < -2**(Bgbit - 1) <= e
+        # the bootstrap reaches it: body mu, X^N acc - acc = -2 mu
+        assert B.wrap(-2 * B.crafted_mu(bits, l, Bgbit), bits) == x
+    assert B.crafted_mu(32, 3, 7) == 0x40810000
+    # a lone -2^25 is not extreme for the three 9-bit parts of a 26-bit digit
+    assert B.cut_parts(-2**25, 3, 9) == [0, 0, -128]
+
+
+@pytest.mark.parametrize("l, Bgbit", [(2, 10), (3, 7), (3, 10), (1, 8), (2, 7), (3, 6)])
+def test_single_key_recipe_reaches_the_bound(O, l, Bgbit):
+    p = O.make_params("SK-128", n=4, l=l, Bgbit=Bgbit)
+    K = O.SKKeys(p, 0xB0 + l, 2.0**-25, 2.0**-15)
+    for full in (True, False):
+        bk, x, mu, step = B.sk_case(p, K.bk, full)
+        orc = O.Oracle(p, bk, K.ksk)
+        assert B.sk_reached(orc, p, bk, x, mu, step) == B.bound(2 * l, p.N, Bgbit) // (1 if full else 2)
+        acc = B.sk_acc_before(orc, p, x, mu, step)
+        assert np.all(acc[1] == mu) and np.all(acc[0] == (mu if full else 0))   # full: step 0 copied the body into the mask
+        assert np.array_equal(orc.bootstrap_wo_keyswitch(x, mu), orc.bootstrap_wo_keyswitch(x, mu, schoolbook=True))
+    # l Bgbit = 32: only the half recipe
+    p = O.make_params("SK-128", n=2, l=4, Bgbit=8)
+    K = O.SKKeys(p, 5, 2.0**-25, 2.0**-15)
+    bk, x, mu, step = B.sk_case(p, K.bk, False)
+    orc = O.Oracle(p, bk, K.ksk)
+    assert B.sk_reached(orc, p, bk, x, mu, step) == B.bound(8, p.N, 8) // 2
+
+
+@pytest.mark.parametrize("name, frac", [("MK2", 1.0), ("MK8", 1.0), ("MK4-N2048", 1.0), ("MK16", 0.83), ("MK128", 0.83), ("MK256", 0.99),
+                                        ("MK64-fft", 0.99)])
+def test_multi_key_recipe_reaches_the_bound(O, name, frac):
+    p = O.make_params(name, n=2, parties=2)
+    K = O.MKKeys(p, 0xB1, 2.0**-30.70, 2.0**-13.52)
+    bk, x, mu = B.mk_case(p, K.bk, [0, 1], full=True)
+    orc = O.MKOracle(p, bk, K.ksk)
+    bd = B.bound(2 * p.l, p.N, p.Bgbit)
+    for k in range(2):
+        acc, steps = B.mk_rotate(orc, p, bk, x[k], mu)
+        assert len(steps) == 1 and frac * bd <= steps[0][2] <= bd, (steps, bd)
+        assert frac < 1.0 or steps[0][2] == bd
+        assert np.array_equal(orc.bootstrap_wo_keyswitch(x[k], mu), orc.bootstrap_wo_keyswitch(x[k], mu, schoolbook=True))
+
+
+def test_ccs_oracle_exact_on_extreme_keys(O):
+    # the CCS products with every bootstrap-key, public-key and common-key word at 0x7FFF8000 on a mask word of 2^31: schoolbook == NTT
+    p = O.make_params("CCS2", n=2)
+    s = O.SIGMAS["CCS2"]
+    K = O.CCSKeys(p, 7, s["bk"], s["ks"])
+    for a in (K.bk, K.pk, K.crs):
+        a[...] = B.extreme_key_word(32)
+    orc = O.CCSOracle(p, K)
+    x = np.zeros(p.parties * p.n + 1, np.int32)
+    x[0] = x[p.n + 1] = -2**31
+    mu = B.crafted_mu(32, p.l, p.Bgbit)
+    assert np.array_equal(orc.bootstrap_wo_keyswitch(x, mu), orc.bootstrap_wo_keyswitch(x, mu, schoolbook=True))
+
+
+def test_ccs_recipe_reaches_the_stage2_bound(O):
+    # (P + 1) l 2^(Bgbit-1) = 3072: the largest stage-2 sum thfhe_ccs_ctx_create admits, reached exactly
+    p = O.make_params("CCS2", n=3, parties=3)
+    s = O.SIGMAS["CCS2"]
+    K = O.CCSKeys(p, 0xB2, s["bk"], s["ks"])
+    bk, pk, crs, x, mu, step = B.ccs_case(p, K.bk, K.pk, K.crs)
+    K.bk[...], K.pk[...], K.crs[...] = bk, pk, crs
+    orc = O.CCSOracle(p, K)
+    s1, s2 = B.ccs_reached(orc, p, bk, pk, crs, x, mu, step)
+    assert s1 == B.bound(p.l, p.N, p.Bgbit) and s2 == B.bound(12, p.N, p.Bgbit) == 3072 * p.N * 2**15
+    assert np.array_equal(orc.bootstrap_wo_keyswitch(x, mu), orc.bootstrap_wo_keyswitch(x, mu, schoolbook=True))
+
+
+def test_kms_recipes_reach_the_bound(O):
+    import thfhe
+    from thfhe import keygen
+    p = thfhe.make_kms_params("KMS4", n=3, parties=2)
+    K = keygen.KMSSecretKeySet(p, seed=11)
+    bd = B.bound(2 * p.l_gsw, p.N, p.bg_gsw)
+    gsw, bara, acc = B.kms_rlwe_case(p, K.gsw, 1)
+    assert B.gsw_reached(acc, p.N, gsw[1, 0], p.l_gsw, p.bg_gsw) == bd
+    orc = O.KMSOracle(p, gsw, K.uni, K.pk, K.crs, K.ksk)
+    assert np.array_equal(orc.rlwe_rotate(1, bara, acc), orc.rlwe_rotate(1, bara, acc, schoolbook=True))
+    gsw, bara = B.kms_tlev_case(p, K.gsw, 0)
+    orc = O.KMSOracle(p, gsw, K.uni, K.pk, K.crs, K.ksk)
+    init = np.zeros((2, p.N), np.int64)
+    init[1, 0] = 1 << (64 - p.bg_lev)
+    acc = orc.rlwe_rotate(0, np.where(np.arange(p.n) == 0, bara, 0).astype(np.int32), init)
+    assert np.all(acc[0] == B.crafted_mu(64, p.l_gsw, p.bg_gsw))
+    assert 0.999 * bd <= B.gsw_reached(acc, p.N, gsw[0, 1], p.l_gsw, p.bg_gsw) < bd
+    assert np.array_equal(orc.tlev_rotate(0, bara), orc.tlev_rotate(0, bara, schoolbook=True))

@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import bound_inputs as B
+
 pytestmark = pytest.mark.gpu
 
 
@@ -41,6 +43,12 @@ def test_polymac_equals_schoolbook(O, N, bits):
     # no addend, an output without terms
     got = pm.mac(small, torus, [(1, 1, 0, 1)], 2)
     assert not got[0].any() and np.array_equal(got[1], schoolbook(O, small[1], torus[0], bits))
+    # coherent: constant +-4096 against a constant word whose limbs all have magnitude 2^15 -- the limb sums at coefficient N - 1 are
+    # N 2^12 2^15, the largest the 13-bit bound admits (random words leave them 5 - 6 bits lower)
+    ext = np.full((1, N), B.extreme_key_word(bits), dt)
+    for d in (4096, -4096):
+        sm = np.full((1, N), d, np.int32)
+        assert np.array_equal(pm.mac(sm, ext, [(0, 0, 0, 1)], 1)[0], schoolbook(O, sm[0], ext[0], bits)), d
     # a coefficient outside the bound is refused, not silently mis-multiplied
     bad = small.copy(); bad[0, 5] = 5000
     with pytest.raises(thfhe.ThfheError):

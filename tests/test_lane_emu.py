@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import bound_inputs as B
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -57,8 +59,8 @@ def test_polymul_exact_with_margin(E, O, case):
         a = rng.integers(-64, 64, N); b = rng.integers(-2**31, 2**31, N)
     elif case == "random10":
         a = rng.integers(-512, 512, N); b = rng.integers(-2**31, 2**31, N)
-    elif case == "worst_neg":
-        a = np.full(N, -512); b = np.full(N, -2**31)
+    elif case == "worst_neg":   # coherent: both limbs of every key word at magnitude 2^15, every digit at -2^9
+        a = np.full(N, -512); b = np.full(N, B.extreme_key_word(32))
     else:
         a = 511 * (-1) ** np.arange(N); b = np.full(N, 2**31 - 1)
     a = a.astype(np.int32); b = b.astype(np.int32)
@@ -106,8 +108,8 @@ def test_swizzled_variant_matches_padded(E, O):
 @pytest.mark.parametrize("case", ["random", "adversarial"])
 def test_roots_variant_exact_with_margin(E, O, case, fn):
     # second-generation ring kernel: pass-1 twiddles rebuilt from two per-lane roots (b * s^k0) instead of the T1 table.  The
-    # products must stay exact with a wide margin, on random digits and on the worst case of the SK-80 shape (|digit| = 512,
-    # every key word at +-2^31) where the limb sums are largest.
+    # products must stay exact with a wide margin, on random digits and on the worst case of the SK-80 shape where the limb sums are
+    # largest: every digit -512, every key word 0x7FFF8000 (both limbs at magnitude 2^15), so the sum at coefficient N - 1 is coherent.
     # (second variant: the same with the first transpose modelled as the in-register lane exchange of the third-generation kernel;
     # third: that exchange followed by the XOR-swizzled second transpose, the combination the multi-key kernels use)
     getattr(E, fn).restype = C.c_double
@@ -115,7 +117,7 @@ def test_roots_variant_exact_with_margin(E, O, case, fn):
     if case == "random":
         a = rng.integers(-512, 512, 1024).astype(np.int32); b = rng.integers(-2**31, 2**31, 1024).astype(np.int32)
     else:
-        a = (rng.integers(0, 2, 1024) * 1023 - 512).astype(np.int32); b = np.where(rng.integers(0, 2, 1024) == 1, 2**31 - 1, -2**31).astype(np.int32)
+        a = np.full(1024, -512, np.int32); b = np.full(1024, B.extreme_key_word(32), np.int32)
     ref, got = np.zeros(1024, np.int32), np.zeros(1024, np.int32)
     O.lib().oracle_polymul_schoolbook32(O.p32(a), O.p32(b), 1024, O.p32(ref))
     dmax = C.c_double(0)
@@ -235,12 +237,13 @@ def test_table_free_twisted_transforms_equal_the_table_form(E):
 def test_ring_4096_product_exact_with_margin(E, O):
     # the arithmetic of r4k_rotate_kernel (radix-4 split, four twisted 512-point quarter transforms, four 16-bit limbs, 1/2048 in the key
     # spectra): digits of the 9-bit parts (|d| <= 256) times a Torus64 polynomial == the exact negacyclic convolution mod 2^64, and every
-    # inverse output within 1e-3 of an integer on an adversarial input (all digits +-256, key words +-2^63 pattern) as well as a random one
+    # inverse output within 1e-3 of an integer on an adversarial input (every digit -256, every key word with all four limbs at magnitude
+    # 2^15: the coherent sum 4096 * 2^8 * 2^15 at coefficient N - 1) as well as a random one
     E.emu_polymul_4k.restype = C.c_double
     rng = np.random.default_rng(6)
     N = 4096
     cases = [(rng.integers(-256, 257, N).astype(np.int32), rng.integers(-2**63, 2**63, N, dtype=np.int64)),
-             (np.where(rng.integers(0, 2, N) == 1, 256, -256).astype(np.int32), np.where(rng.integers(0, 2, N) == 1, 2**63 - 1, -2**63).astype(np.int64))]
+             (np.full(N, -256, np.int32), np.full(N, B.extreme_key_word(64), np.int64))]
     for d, k in cases:
         out = np.zeros(N, np.int64)
         margin = E.emu_polymul_4k(O.p32(d), O.p64(k), O.p64(out))
@@ -250,3 +253,72 @@ def test_ring_4096_product_exact_with_margin(E, O):
         O.lib().oracle_polymul_schoolbook64(O.p64(d.astype(np.int64)), O.p64(k), N, O.p64(ref))
         assert np.array_equal(out, ref)
         assert margin < 1e-3, margin
+
+
+def test_limb_split_restatement_matches_the_lane_code(E):
+    # tests/bound_inputs.py restates split_limbs32 / split_limbs64; the extreme words must really split into limbs of magnitude 2^15
+    E.emu_split_limbs32.argtypes = [C.c_int32, C.POINTER(C.c_double)]
+    E.emu_split_limbs64.argtypes = [C.c_int64, C.POINTER(C.c_double)]
+    rng = np.random.default_rng(40)
+    w32 = [0, 1, -1, 2**31 - 1, -2**31, 0x7FFF8000, -0x8000, 0x8000, 0x7FFF, -0x7FFF8000] + rng.integers(-2**31, 2**31, 300).tolist()
+    w64 = [0, 1, -1, 2**63 - 1, -2**63, 0x7FFF7FFF7FFF8000, -0x8000] + rng.integers(-2**63, 2**63, 300, dtype=np.int64).tolist()
+    out = np.zeros(4)
+    for v in w32:
+        E.emu_split_limbs32(int(v), dptr(out))
+        assert tuple(out[:2]) == B.split_limbs32(v), v
+        lo, hi = B.split_limbs32(v)
+        assert lo + 65536 * hi == v and -2**15 <= lo < 2**15
+    for v in w64:
+        E.emu_split_limbs64(int(v), dptr(out))
+        assert list(out) == B.split_limbs64(v), v
+        assert B.wrap(sum(x << (16 * h) for h, x in enumerate(B.split_limbs64(v))), 64) == v
+    assert B.extreme_key_word(32) == 0x7FFF8000 and B.split_limbs32(0x7FFF8000) == (-2**15, 2**15)
+    assert B.split_limbs64(B.extreme_key_word(64)) == [-2**15, -2**15, -2**15, 2**15]
+    # the words the older margin cases used leave the low limbs near zero
+    assert B.split_limbs32(-2**31) == (0, -2**15) and B.split_limbs32(2**31 - 1) == (-1, 2**15)
+
+
+@pytest.mark.parametrize("l, Bgbit", [(2, 10), (3, 10), (3, 7)])
+def test_cmux_at_the_full_bound(E, O, l, Bgbit):
+    # one CMux with all 2l digit rows at -2^(Bgbit-1) on every coefficient against a key whose every word is 0x7FFF8000: the 2l products
+    # are summed in the spectrum as in the kernels, the limb sum at coefficient N - 1 is exactly 2l N 2^(Bgbit-1) 2^15 (2^36.6 for
+    # l = 3, Bgbit = 10); every output word equals the oracle's schoolbook CMux and every inverse output is within 1e-3 of an integer
+    E.emu_mux_rotate.restype = C.c_double
+    p = O.make_params("SK-128", n=2, l=l, Bgbit=Bgbit)
+    K = O.SKKeys(p, 21, 2.0**-25, 2.0**-15)
+    bk = K.bk.copy()
+    bk[1] = B.extreme_key_word(32)
+    orc = O.Oracle(p, bk, K.ksk)
+    npolys = bk.size // 1024
+    spec = np.zeros(npolys * 2 * 512 * 2, np.float64)
+    E.emu_transform_key_polys(O.p32(bk), C.c_int64(npolys), dptr(spec))
+    acc = np.full((2, 1024), B.crafted_mu(32, l, Bgbit), np.int32)
+    rows = B.step_digit_rows(acc, 1024, 32, l, Bgbit)
+    assert len(rows) == 2 * l and all(np.all(d == -2**(Bgbit - 1)) for _, _, d in rows)
+    assert B.peak_limb_sum([(d, bk[1, r, 0]) for r, _, d in rows], 32) == B.bound(2 * l, 1024, Bgbit)
+    ref = orc.mux_rotate(1, 1024, acc, schoolbook=True)
+    got = acc.copy()
+    margin = E.emu_mux_rotate(dptr(spec), l, Bgbit, 1, 1024, O.p32(got))
+    assert np.array_equal(ref, got)
+    assert margin < 1e-3, margin
+
+
+def test_mk_cmux_2048_at_the_full_bound(E, O):
+    # the N = 2048 Torus64 CMux (MK4-N2048 shape) with all 2l digit rows at -2^5 and every key word 0x7FFF7FFF7FFF8000 in all four parts
+    E.emu_mk_mux_rotate_2k.restype = C.c_double
+    p = O.make_params("MK4-N2048", n=2, parties=2)
+    K = O.MKKeys(p, 3, 2.0**-30.70, 2.0**-13.52)
+    bk = K.bk.copy()
+    bk[1, 1] = B.extreme_key_word(64)
+    orc = O.MKOracle(p, bk, K.ksk)
+    PN = p.parties * p.n
+    spec = np.zeros(PN * 2 * p.l * 8 * 1024 * 2, np.float64)
+    E.emu_mk_transform_key_2k(O.p64(bk), C.c_long(PN), p.l, dptr(spec))
+    acc = np.full((2, 2048), B.crafted_mu(64, p.l, p.Bgbit), np.int64)
+    rows = B.step_digit_rows(acc, 2048, 64, p.l, p.Bgbit)
+    assert B.peak_limb_sum([(d, bk[1, 1, 0, 0]) for _, _, d in rows], 64) == B.bound(2 * p.l, 2048, p.Bgbit)
+    ref = orc.mux_rotate(1, 1, 2048, acc, schoolbook=True)
+    got = acc.copy()
+    margin = E.emu_mk_mux_rotate_2k(dptr(spec), p.l, p.Bgbit, C.c_long(1 * p.n + 1), 2048, O.p64(got))
+    assert np.array_equal(ref, got)
+    assert margin < 1e-3, margin

@@ -5,6 +5,8 @@ against the oracle, and the reference's application flow gate -> conversion -> p
 import numpy as np
 import pytest
 
+import bound_inputs as B
+
 N = 1024
 
 
@@ -82,12 +84,14 @@ def test_gpu_threshold_ops_bit_exact(O):
             e = np.ascontiguousarray(noise[c]) if noise is not None else None
             L.oracle_partial_decrypt(O.p32(share), O.p32(np.ascontiguousarray(ta[c])), O.p32(e), N, O.p32(ref[c]))
         assert np.array_equal(got, ref), name
-    worst_a = np.full((2, N), -2**31, np.int32)       # largest limbs everywhere
     share = np.full(N, -512, np.int32)
-    ref = np.zeros_like(worst_a)
-    for c in range(2):
-        L.oracle_partial_decrypt(O.p32(share), O.p32(worst_a[c]), None, N, O.p32(ref[c]))
-    assert np.array_equal(T.PartialDecrypt(ctx, share, worst_a), ref)
+    # -2^31 splits to limbs (0, -2^15); 0x7FFF8000 to (-2^15, 2^15): both limbs extreme, the sums at coefficient N - 1 coherent
+    for word in (-2**31, B.extreme_key_word(32)):
+        worst_a = np.full((2, N), word, np.int32)
+        ref = np.zeros_like(worst_a)
+        for c in range(2):
+            L.oracle_partial_decrypt(O.p32(share), O.p32(worst_a[c]), None, N, O.p32(ref[c]))
+        assert np.array_equal(T.PartialDecrypt(ctx, share, worst_a), ref), word
     parts = rng.integers(-2**31, 2**31, size=(4, cnt, N), dtype=np.int64).astype(np.int32)
     bits, res = T.finalDecrypt(ctx, tb, parts, want_result=True)
     for c in range(cnt):

@@ -648,6 +648,10 @@ class CCSCloudKey(_Handle):
         _check(lib().thfhe_ccs_bootstrap(self.h, mu, _p32(x), _p32(out), x.shape[0]))
         return out
 
+    def rotation_kernel_name(self):
+        """The blind-rotation kernel of this context (thfhe_ccs_ctx_create: more than 8 parties or 8 levels take the wide kernel)."""
+        return "ccs_blind_rotate_wide_kernel" if self.params.parties > 8 or self.params.l > 8 else "ccs_blind_rotate_kernel"
+
 
 def mk_gate_nand(ck, x, y): return ck.gates(NAND, x, y)          # mk_gates.jl:7-13 (CCS scheme)
 def mk_bootstrap(ck, mu, x): return ck.bootstrap(x, mu)         # mk_internals.jl:855-858
