@@ -192,6 +192,19 @@ int thfhe_mk_dag_run_batch(thfhe_mk_ctx *ctx, const int32_t *inputs, size_t n_in
                            const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats);
 int thfhe_mk_set_dag_slice(thfhe_mk_ctx *ctx, size_t max_gates); /* default 8 192 */
 int thfhe_mk_bootstrap(thfhe_mk_ctx *ctx, int64_t mu, const int32_t *x, int32_t *out, size_t count);
+/* Multi-key programmable bootstrap: the contract of thfhe_lut_bootstrap on the 3-gen scheme, every parameter family.
+ * in0/in1/in2: HOST records int32[count][P*n+1] (padding-bit encoding m * 2^32 / (2p)).  The prologue and the theta-rounded mod-switch
+ *   run over all P*n+1 words; the CMux chain is mk_bootstrap_3gen's (party-major, mask words with bara == 0 skipped).
+ * tv: HOST int64[n_luts][N] Torus64 test vectors (N = the context's ring degree; layout of thfhe_lut_bootstrap, e.g.
+ *   thfhe.lut.test_vector(..., torus_bits=64)).  Accumulator (0, X^{-barb} * tv[lut_index[s]]); record j < theta of sample s is
+ *   coefficient j extracted with t64tot32: a'_i = t64tot32(a_{j-i}) (i <= j), t64tot32(-a_{N+j-i}) (i > j), b' = t64tot32(body_j).
+ *   tv = (mu, ..., mu), theta = 1, w = (1), bias = 0 is exactly thfhe_mk_bootstrap(mu).
+ * out: HOST int32[count][theta][P*n+1] (key-switched) or int32[count][theta][N+1] (_wo_keyswitch).
+ * Argument checks as thfhe_lut_bootstrap, on the host before any device work and before the context is looked at. */
+int thfhe_mk_lut_bootstrap(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec, const int64_t *tv, int n_luts, const int32_t *lut_index,
+                           const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count);
+int thfhe_mk_lut_bootstrap_wo_keyswitch(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec, const int64_t *tv, int n_luts, const int32_t *lut_index,
+                                        const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1, size_t count);
 /* Party-sharded building blocks (optional mode: a rank holds only the keys of a contiguous block of m
  * parties, i.e. a context created with parties = m from those parties' key parts; m = 1 is one rank per party).  Below
  * nb = m * n (the block's mask words) and P = the key set's total party count.  All pointers are DEVICE pointers; calls enqueue

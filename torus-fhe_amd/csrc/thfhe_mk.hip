@@ -15,6 +15,9 @@
 //                             thfhe_rot2k.h (any number of digit row parts, N = 2048) and thfhe_rot4k.h (N = 4096) for the large-party sets
 //   mk_keyswitch_kernel / mk_keyswitch_staged_kernel (thfhe_mk_shared.h)   P key switches of the extracted sample + the cross-party combine
 //                             of b: one workgroup per (sample, party, range), or from 192 samples on the rows staged in LDS for 32 samples
+//   mk_lut_prologue_kernel / mk_lut_acc_init_kernel / mk_extract_at_kernel   programmable bootstrap (thfhe_mk_lut_bootstrap): weighted
+//                             sum + mod-switch to multiples of theta, accumulator X^{-barb} * tv in global memory, the rotation kernels above
+//                             through acc_in / acc_out, extraction of theta coefficients
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -852,6 +855,67 @@ __global__ __launch_bounds__(256) void mk_acc_init_2k_kernel(const int32_t *__re
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// programmable bootstrap (thfhe_mk_lut_bootstrap): only the two ends of the rotation are new; the rotation kernels take the
+// accumulator from global memory and return it there (MKBRArgs::acc_in / acc_out).
+// ------------------------------------------------------------------------------------------------------
+// prologue: x = w0 in0 + w1 in1 + w2 in2 + (0, ..., 0, bias) word-wise mod 2^32 over the P n + 1 record words, then every word rounded to a
+// multiple of theta in Z_2N: bar = modswitch_{2N/theta}(word) * theta (theta = 1: mk_prologue_kernel's mod-switch).  One thread per word,
+// grid.y strides over the samples.
+__global__ __launch_bounds__(256) void mk_lut_prologue_kernel(const int32_t *__restrict__ in0, const int32_t *__restrict__ in1,
+                                                               const int32_t *__restrict__ in2, int n_inputs, int32_t w0, int32_t w1, int32_t w2,
+                                                               int32_t bias, int log2_theta, int words, int w_pad, int log2_2n, long jobs,
+                                                               int32_t *__restrict__ bara, int32_t *__restrict__ barb) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > words) return;
+    for (long job = blockIdx.y; job < jobs; job += gridDim.y) {
+        const size_t off = (size_t)job * (words + 1) + i;
+        uint32_t v = (uint32_t)w0 * (uint32_t)in0[off];
+        if (n_inputs > 1) v += (uint32_t)w1 * (uint32_t)in1[off];
+        if (n_inputs > 2) v += (uint32_t)w2 * (uint32_t)in2[off];
+        if (i == words) v += (uint32_t)bias;
+        const int32_t bar = (int32_t)((uint32_t)modswitch2n((int32_t)v, log2_2n - log2_theta) << log2_theta);
+        if (i == words) barb[job] = bar;
+        else bara[job * w_pad + i] = bar;
+    }
+}
+
+// accumulator start acc[job] = (0, X^{-barb} * tv[lut_idx[job]]) over Torus64 (oracle_mul_by_monomial64): coefficient q is tv[(q + barb) mod N],
+// negated when (q + barb) mod 2N >= N.  mk_acc_init_2k_kernel with a per-sample table instead of a constant; N = 1024, 2048 or 4096.
+__global__ __launch_bounds__(256) void mk_lut_acc_init_kernel(const int32_t *__restrict__ barb, const int64_t *__restrict__ tv,
+                                                               const int32_t *__restrict__ lut_idx, long jobs, int N, int64_t *__restrict__ acc) {
+    const long job = blockIdx.x;
+    if (job >= jobs) return;
+    const int b = barb[job];
+    const int64_t *t = tv + (lut_idx ? (size_t)lut_idx[job] * N : 0);
+    int64_t *ap = acc + job * 2 * N;
+    for (int q = threadIdx.x; q < N; q += 256) {
+        const int e = (q + b) & (2 * N - 1);
+        const int64_t v = t[e & (N - 1)];
+        ap[q] = 0;
+        ap[N + q] = (e & N) ? (int64_t)(0ull - (uint64_t)v) : v;
+    }
+}
+
+// extraction of coefficients j = blockIdx.y < theta: record (job theta + j) of N + 1 words, a'_i = t64tot32(a_{j-i}) for i <= j,
+// t64tot32(-a_{N+j-i}) for i > j (negated mod 2^64 before the conversion), b' = t64tot32(body_j).  j = 0 is mk_extract_kernel.
+__global__ __launch_bounds__(256) void mk_extract_at_kernel(const int64_t *__restrict__ acc, int32_t *__restrict__ out, long jobs, int N, int theta) {
+    const long job = blockIdx.x;
+    const int j = blockIdx.y;
+    if (job >= jobs || j >= theta) return;
+    const int64_t *ap = acc + job * 2 * N;
+    int32_t *o = out + (job * theta + j) * (N + 1);
+    for (int q = threadIdx.x; q <= N; q += 256) {
+        int64_t v;
+        if (q == N) v = ap[N + j];
+        else {
+            v = ap[(j - q) & (N - 1)];
+            if (q > j) v = (int64_t)(0ull - (uint64_t)v);
+        }
+        o[q] = t64tot32(v);
+    }
+}
+
 __global__ __launch_bounds__(256) void mk_linear_kernel(const int32_t *__restrict__ x, const int32_t *__restrict__ y, int32_t *__restrict__ out,
                                                          size_t words, size_t rec, int mode) {
     // mode 0: copy, 1: negate, 2: (0, 1/8) + x + y   (the 3-gen MUX epilogue, J/3gen_mk_gates.jl:144-147)
@@ -887,6 +951,7 @@ struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     DevBuf d_acc;               // batched path: accumulators in global memory, int64[jobs][2][2048]
     int parts = 1, pw = 0;      // N = 2048 with a wide gadget base: digit parts and their width (MKBRArgs)
     DevBuf d_bara, d_barb, d_u, d_tmp;
+    DevBuf d_tv, d_lut_idx;     // programmable bootstrap: Torus64 test-vector table and per-sample table index (grow-only)
     Stage stage;
     DagBuffers dag;   // gate-DAG executor tables (thfhe_dag.h)
     size_t dag_slice = 8192;  // gates per launch of a DAG level
@@ -923,6 +988,49 @@ int mk_enqueue_bootstraps(thfhe_mk_ctx *c, const int32_t *d0, const int32_t *d1,
     const int nsplit = jobs * c->p.parties <= 64 ? 16 : (jobs * c->p.parties <= 256 ? 4 : (c->p.N > 2048 ? 2 : 1));  // fill the chip at small batch sizes; a block holds <= 2048 mask words
     THFHE_HIP(hipMemsetAsync(d_dst, 0, jobs * ((size_t)c->words + 1) * sizeof(int32_t), c->stream));
     mk_launch_keyswitch(k, nsplit, c->stream);
+    if (c->profiling) {
+        THFHE_HIP(hipEventRecord(c->ev[3], c->stream));
+        c->ev_valid = true;
+    }
+    THFHE_HIP(hipGetLastError());
+    return THFHE_OK;
+}
+
+// programmable bootstrap of `count` samples: lut prologue + accumulator start, the rotation of mk_bootstrap_3gen, extraction of
+// theta coefficients into d_u [count][theta][N+1]; then, if d_dst is given, the key switch of the count x theta records into d_dst.  The
+// profiling events sit on the boundaries of mk_enqueue_bootstraps: prologue | rotation + extraction | key switch.
+int mk_enqueue_lut(thfhe_mk_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0, const int32_t *d1, const int32_t *d2, size_t count,
+                   const int64_t *d_tv, const int32_t *d_idx, int32_t *d_dst) {
+    const int N = c->p.N;
+    const size_t recs = count * sp.theta;
+    int rc = mk_ensure_workspace(c, count);
+    if (!rc) rc = c->d_u.grow(recs * ((size_t)N + 1) * sizeof(int32_t));
+    if (!rc) rc = c->d_acc.grow(count * 2 * (size_t)N * sizeof(int64_t));
+    if (rc) return rc;
+    int64_t *acc = c->d_acc.as<int64_t>();
+    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
+    dim3 pg((unsigned)((c->words + 1 + 255) / 256), (unsigned)(count < 65535 ? count : 65535));
+    hipLaunchKernelGGL(mk_lut_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, sp.n_inputs, sp.weights[0], sp.weights[1], sp.weights[2],
+                       sp.bias, ilog2(sp.theta), c->words, c->w_pad, c->log2_2n, (long)count, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
+    hipLaunchKernelGGL(mk_lut_acc_init_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, c->d_barb.as<int32_t>(), d_tv, d_idx, (long)count, N, acc);
+    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
+    // acc_in == acc_out == d_acc: every rotation shape may run in place.  The N = 1024 / 2048 coop and pair kernels copy their job's
+    // accumulator(s) into LDS before the first barrier and write them back only after the last CMux, and no workgroup touches another job's
+    // slot; the batched two-level path (c->batched) always rotates the global accumulator in place; the N = 4096 path skips its copy when
+    // acc_in is the accumulator it rotates.  barb is not read when acc_in is given: the start above already applied X^{-barb}.
+    MKBRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), nullptr, (long)count, c->p.parties * c->p.n,
+               c->w_pad, c->p.Bgbit, 0, acc, acc};
+    rc = mk_launch_rotation(c, a);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mk_extract_at_kernel, dim3((unsigned)count, (unsigned)sp.theta), dim3(256), 0, c->stream, (const int64_t *)acc, c->d_u.as<int32_t>(),
+                       (long)count, N, sp.theta);
+    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
+    if (d_dst) {
+        MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_u.as<int32_t>(), d_dst, (long)recs, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, N, N + 1, 0};
+        const int nsplit = recs * c->p.parties <= 64 ? 16 : (recs * c->p.parties <= 256 ? 4 : (N > 2048 ? 2 : 1));   // as mk_enqueue_bootstraps
+        THFHE_HIP(hipMemsetAsync(d_dst, 0, recs * ((size_t)c->words + 1) * sizeof(int32_t), c->stream));
+        mk_launch_keyswitch(k, nsplit, c->stream);
+    }
     if (c->profiling) {
         THFHE_HIP(hipEventRecord(c->ev[3], c->stream));
         c->ev_valid = true;
@@ -1076,6 +1184,29 @@ int mk_gates_dev_locked(thfhe_mk_ctx *c, int op, const int32_t *d0, const int32_
     hipLaunchKernelGGL(mk_mux_combine_kernel, dim3(lb), dim3(256), 0, c->stream, c->d_tmp.as<int32_t>(), dout, words, rec);
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
+}
+
+// thfhe_mk_lut_bootstrap (keyswitch) / thfhe_mk_lut_bootstrap_wo_keyswitch: out = count x theta records of P n + 1 (resp. N + 1) words
+int mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
+                     const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch) {
+    int rc = lut_validate(sp, tv, n_luts, lut_index, in0, in1, in2, out, count);
+    if (rc) return rc;
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (count == 0) return THFHE_OK;
+    const thfhe_lut_spec s = *sp;
+    const size_t rec = (size_t)c->words + 1, in_words = count * rec, outs = count * s.theta, N = c->p.N;
+    const size_t in_bytes = in_words * sizeof(int32_t);
+    const size_t out_bytes = outs * (keyswitch ? rec : N + 1) * sizeof(int32_t);
+    const size_t stage_words = keyswitch ? outs * rec : in_words;   // the key switch writes count x theta records into stage.out
+    return ctx_staged(c, stage_words, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, {in_bytes, in_bytes, in_bytes}, [&] {
+        int r = c->d_tv.grow((size_t)n_luts * N * sizeof(int64_t));
+        if (!r && lut_index) r = c->d_lut_idx.grow(count * sizeof(int32_t));
+        if (r) return r;
+        THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv, (size_t)n_luts * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        if (lut_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), lut_index, count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        return mk_enqueue_lut(c, s, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), count, c->d_tv.as<int64_t>(),
+                              lut_index ? c->d_lut_idx.as<int32_t>() : nullptr, keyswitch ? c->stage.out_ptr() : nullptr);
+    }, keyswitch ? c->stage.out : c->d_u, out, out_bytes);
 }
 
 }  // namespace
@@ -1324,6 +1455,16 @@ int thfhe_mk_bootstrap(thfhe_mk_ctx *c, int64_t mu, const int32_t *x, int32_t *o
         int rc = mk_ensure_workspace(c, count);
         return rc ? rc : mk_enqueue_bootstraps(c, c->stage.in_ptr(0), c->stage.in_ptr(0), c->stage.in_ptr(0), L, L, 1, count, mu, c->stage.out_ptr());
     }, c->stage.out, out, bytes);
+}
+
+int thfhe_mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const int64_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
+                           const int32_t *in1, const int32_t *in2, int32_t *out, size_t count) {
+    return mk_lut_bootstrap(c, spec, tv, n_luts, lut_index, in0, in1, in2, out, count, true);
+}
+
+int thfhe_mk_lut_bootstrap_wo_keyswitch(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const int64_t *tv, int n_luts, const int32_t *lut_index,
+                                        const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1, size_t count) {
+    return mk_lut_bootstrap(c, spec, tv, n_luts, lut_index, in0, in1, in2, out_N1, count, false);
 }
 
 }  // extern "C"

@@ -203,6 +203,8 @@ SIGNATURES = {
     "thfhe_mk_dag_run": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, _i64p]),
     "thfhe_mk_dag_run_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_mk_bootstrap": (C.c_int, [_vp, C.c_int64, _i32p, _i32p, C.c_size_t]),
+    "thfhe_mk_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_mk_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_prologue_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t]),
     "thfhe_mk_set_stream": (C.c_int, [_vp, _vp]),
     "thfhe_mk_set_pair_threshold": (C.c_int, [_vp, C.c_long]),
@@ -395,6 +397,43 @@ class _EvalKey(_Handle):
         _check(self._fn("bootstrap")(self.h, mu, _p32(x), _p32(out), x.shape[0]))
         return out
 
+    # -- programmable bootstrap (thfhe_lut_bootstrap / thfhe_mk_lut_bootstrap) ---------------------------------------------------
+    def lut_bootstrap(self, tv, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
+        """Programmable bootstrap (include/thfhe_hip.h, thfhe_lut_bootstrap / thfhe_mk_lut_bootstrap): sample g evaluates test vector
+        tv[lut_index[g]] (table 0 without an index) on x = sum_q weights[q] * (x, y, z)[q] + (0, bias), theta outputs per rotation.
+        tv: [n_luts][N] test vectors of the ring's torus (thfhe.lut.test_vector): int32 for CloudKey, int64 (torus_bits=64) for MKCloudKey.
+        Returns int32[count, theta, words] (words = n+1, or P*n+1 for the multi-key scheme)."""
+        return self._lut(tv, x, y, z, weights, bias, theta, lut_index, True)
+
+    def lut_bootstrap_wo_keyswitch(self, tv, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
+        """lut_bootstrap without the key switch: int32[count, theta, N+1] records under the ring key."""
+        return self._lut(tv, x, y, z, weights, bias, theta, lut_index, False)
+
+    _tv_dtype = np.int32   # the ring's torus: Torus32 test vectors (MKCloudKey: Torus64)
+
+    def _lut(self, tv, x, y, z, weights, bias, theta, lut_index, keyswitch):
+        given = [v for v in (x, y, z) if v is not None]
+        if any(v is None for v in (x, y, z)[:len(given)]) or len(given) != len(weights):
+            raise ValueError("give the inputs in order (x, then y, then z) and one weight per input")
+        ins = [_rec(v, self.words) for v in given]
+        _same_count(*ins)
+        tv = np.ascontiguousarray(tv, self._tv_dtype).reshape(-1, self.params.N)
+        count = ins[0].shape[0]
+        idx = None
+        if lut_index is not None:
+            idx = np.ascontiguousarray(lut_index, np.int32).reshape(-1)
+            if idx.shape[0] != count:
+                raise ValueError(f"lut_index holds {idx.shape[0]} entries for {count} samples")
+        w = list(weights) + [0] * (3 - len(weights))
+        spec = LutSpec(len(ins), (C.c_int32 * 3)(*[_wrap32(v) for v in w]), _wrap32(bias), int(theta))
+        words = self.words if keyswitch else self.params.N + 1
+        out = np.empty((count, int(theta) if theta in (1, 2, 4) else 1, words), np.int32)
+        fn = self._fn("lut_bootstrap" if keyswitch else "lut_bootstrap_wo_keyswitch")
+        p = [_p32(v) for v in ins] + [None] * (3 - len(ins))
+        ptv = tv.ctypes.data_as(_i64p if self._tv_dtype == np.int64 else _i32p)
+        _check(fn(self.h, C.byref(spec), ptv, tv.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
+        return out
+
     # -- device-buffer calls -----------------------------------------------------------------------
     def _alloc(self, n):
         return self._fn("dev_alloc")(self.h, n)
@@ -471,38 +510,6 @@ class CloudKey(_EvalKey):
         _check(lib().thfhe_keyswitch(self.h, _p32(u), _p32(out), u.shape[0]))
         return out
 
-    def lut_bootstrap(self, tv, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
-        """Programmable bootstrap (include/thfhe_hip.h, thfhe_lut_bootstrap): sample g evaluates test vector tv[lut_index[g]] (table 0 without
-        an index) on x = sum_q weights[q] * (x, y, z)[q] + (0, bias), theta outputs per rotation.  tv: int32[n_luts][N] (thfhe.lut.test_vector).
-        Returns int32[count, theta, n+1]."""
-        return self._lut(tv, x, y, z, weights, bias, theta, lut_index, True)
-
-    def lut_bootstrap_wo_keyswitch(self, tv, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
-        """lut_bootstrap without the key switch: int32[count, theta, N+1] records under the ring key."""
-        return self._lut(tv, x, y, z, weights, bias, theta, lut_index, False)
-
-    def _lut(self, tv, x, y, z, weights, bias, theta, lut_index, keyswitch):
-        given = [v for v in (x, y, z) if v is not None]
-        if any(v is None for v in (x, y, z)[:len(given)]) or len(given) != len(weights):
-            raise ValueError("give the inputs in order (x, then y, then z) and one weight per input")
-        ins = [_rec(v, self.words) for v in given]
-        _same_count(*ins)
-        tv = np.ascontiguousarray(tv, np.int32).reshape(-1, self.params.N)
-        count = ins[0].shape[0]
-        idx = None
-        if lut_index is not None:
-            idx = np.ascontiguousarray(lut_index, np.int32).reshape(-1)
-            if idx.shape[0] != count:
-                raise ValueError(f"lut_index holds {idx.shape[0]} entries for {count} samples")
-        w = list(weights) + [0] * (3 - len(weights))
-        spec = LutSpec(len(ins), (C.c_int32 * 3)(*[_wrap32(v) for v in w]), _wrap32(bias), int(theta))
-        words = self.words if keyswitch else self.params.N + 1
-        out = np.empty((count, int(theta) if theta in (1, 2, 4) else 1, words), np.int32)
-        fn = lib().thfhe_lut_bootstrap if keyswitch else lib().thfhe_lut_bootstrap_wo_keyswitch
-        p = [_p32(v) for v in ins] + [None] * (3 - len(ins))
-        _check(fn(self.h, C.byref(spec), _p32(tv), tv.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
-        return out
-
     def set_ring4_threshold(self, max_jobs):
         """Remainders (batch mod 2048) above the cooperative threshold and <= max_jobs rotations use the four-wave ring kernel; 0 disables it."""
         _check(lib().thfhe_set_ring4_threshold(self.h, int(max_jobs)))
@@ -562,6 +569,7 @@ class MKCloudKey(_EvalKey):
     """
 
     _prefix = "thfhe_mk_"
+    _tv_dtype = np.int64   # the 3-gen accumulator is Torus64
 
     def __init__(self, params, bk_coeff, ksk, device=0):
         self.params = p = params

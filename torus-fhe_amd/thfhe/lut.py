@@ -5,10 +5,14 @@ A message m in [0, p), p a power of two, is the Torus32 word m * 2^32 / (2p): it
 inverts a valid input.  In a test vector of N words, message m owns the box of N/p coefficients centred on m*N/p; entry i of the box holds
 f_{i mod theta}(m), and the lower half-box of m = 0 wraps to the top of the vector with its sign negated.  A rotation by a phase inside
 m's box, rounded to a multiple of theta, then brings f_0(m) .. f_{theta-1}(m) to coefficients 0 .. theta-1.
+
+The 3-gen multi-key engine (MKCloudKey.lut_bootstrap, thfhe_mk_lut_bootstrap) rotates a Torus64 accumulator: its test vectors and output
+words take torus_bits=64 (m * 2^64 / (2p); booleans +-2^61, the 3-gen gate encoding).  The inputs stay Torus32 records (encode) either way.
 """
 import numpy as np
 
 MU8 = 1 << 29  # the boolean encoding of the gates: true = +2^29, false = -2^29
+MU8_64 = 1 << 61  # the same on Torus64 (the 3-gen gates)
 
 
 def _check_p(p):
@@ -18,6 +22,16 @@ def _check_p(p):
 
 def _to_i32(v):
     return (np.asarray(v, np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def _check_bits(torus_bits):
+    if torus_bits not in (32, 64):
+        raise ValueError(f"torus_bits must be 32 or 64, got {torus_bits}")
+
+
+def _to_i64(v):
+    """Python integers taken mod 2^64 as int64 words."""
+    return np.array([int(x) % (1 << 64) for x in np.ravel(v)], np.uint64).view(np.int64).reshape(np.shape(v))
 
 
 def encode(m, p):
@@ -37,9 +51,11 @@ def decode(phase_words, p):
     return ((u + step // 2) // step) % (2 * p)
 
 
-def test_vector(tables, p, theta=1, N=1024):
-    """int32[N] test vector: tables = theta arrays of p Torus32 output words (tables[j][m] = f_j(m)); with theta = 1 one array of p words will do."""
+def test_vector(tables, p, theta=1, N=1024, torus_bits=32):
+    """int32[N] test vector: tables = theta arrays of p Torus32 output words (tables[j][m] = f_j(m)); with theta = 1 one array of p words will do.
+    torus_bits=64: int64[N] from Torus64 output words (the multi-key engine)."""
     _check_p(p)
+    _check_bits(torus_bits)
     if theta not in (1, 2, 4):
         raise ValueError("theta must be 1, 2 or 4")
     T = np.asarray(tables, np.int64)
@@ -54,17 +70,28 @@ def test_vector(tables, p, theta=1, N=1024):
     m = (i + box // 2) // box          # 0 .. p; p = the lower half-box of m = 0, wrapped to the top
     wrap = m == p
     v = T[i % theta, np.where(wrap, 0, m)]
+    if torus_bits == 64:
+        return np.where(wrap, -v, v)   # int64 negation wraps mod 2^64
     return _to_i32(np.where(wrap, -v, v))
 
 
-def int_outputs(f, p_out, p=None):
-    """Table of integer outputs: encode(f(m), p_out) for m in [0, p) (p defaults to p_out); f(m) is taken mod p_out."""
+def int_outputs(f, p_out, p=None, torus_bits=32):
+    """Table of integer outputs: encode(f(m), p_out) for m in [0, p) (p defaults to p_out); f(m) is taken mod p_out.
+    torus_bits=64: the Torus64 words f(m) * 2^64 / (2 p_out) as int64."""
     p = p_out if p is None else p
     _check_p(p)
+    _check_bits(torus_bits)
+    if torus_bits == 64:
+        _check_p(p_out)
+        return _to_i64([(int(f(m)) % p_out) * ((1 << 64) // (2 * p_out)) for m in range(p)])
     return encode(np.array([int(f(m)) % p_out for m in range(p)], np.int64), p_out)
 
 
-def bool_outputs(f, p):
-    """Table of boolean outputs in the gates' encoding (+2^29 if f(m) else -2^29): LUT results that feed thfhe's gates."""
+def bool_outputs(f, p, torus_bits=32):
+    """Table of boolean outputs in the gates' encoding (+2^29 if f(m) else -2^29): LUT results that feed thfhe's gates.
+    torus_bits=64: +-2^61 as int64, the encoding of the 3-gen multi-key gates."""
     _check_p(p)
+    _check_bits(torus_bits)
+    if torus_bits == 64:
+        return np.array([MU8_64 if f(m) else -MU8_64 for m in range(p)], np.int64)
     return _to_i32(np.array([MU8 if f(m) else -MU8 for m in range(p)], np.int64))
