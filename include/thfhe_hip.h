@@ -56,7 +56,9 @@ typedef struct thfhe_params {
 enum thfhe_gate {
     THFHE_NAND = 0, THFHE_OR = 1, THFHE_AND = 2, THFHE_XOR = 3, THFHE_XNOR = 4, THFHE_NOR = 5,
     THFHE_ANDNY = 6, THFHE_ANDYN = 7, THFHE_ORNY = 8, THFHE_ORYN = 9, THFHE_MUX = 10,
-    THFHE_NOT = 11, THFHE_COPY = 12, THFHE_AND3 = 13
+    THFHE_NOT = 11, THFHE_COPY = 12, THFHE_AND3 = 13,
+    THFHE_LUT = 14,     /* gate-DAG node: programmable bootstrap, output 0 (thfhe_dag_run_lut_batch only) */
+    THFHE_LUT_OUT = 15  /* output j > 0 of the LUT node j rows above (thfhe_dag_run_lut_batch only) */
 };
 
 enum thfhe_error {
@@ -143,6 +145,27 @@ int thfhe_lut_bootstrap(thfhe_ctx *ctx, const thfhe_lut_spec *spec, const int32_
 int thfhe_lut_bootstrap_wo_keyswitch(thfhe_ctx *ctx, const thfhe_lut_spec *spec, const int32_t *tv, int n_luts, const int32_t *lut_index,
                                      const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1, size_t count);
 
+/* ---- LUT nodes in the gate-DAG executor: thfhe_dag_run_batch with programmable bootstraps among the gates.
+ * nodes: HOST int32[n_nodes][6] = (opcode, in0, in1, in2, spec, lut); row g defines wire n_inputs + g, topological order.
+ *   Gate row:  an opcode of thfhe_dag_run_batch, spec = lut = -1.
+ *   LUT node:  (THFHE_LUT, in0, in1, in2, spec, lut): specs[spec] gives n_inputs, weights, bias and theta; operands beyond n_inputs are -1;
+ *              tv[lut] is the node's test vector.  It is followed by exactly theta - 1 rows (THFHE_LUT_OUT, head, -1, -1, -1, -1), head =
+ *              the LUT row's wire id; wire head + j holds output j, the record thfhe_lut_bootstrap(specs[spec], tv[lut], operands) returns
+ *              at [0][j], bit for bit (key switch included).
+ * specs: HOST thfhe_lut_spec[n_specs], 1 <= n_specs <= 1024; tv: HOST int32[n_luts][N], 1 <= n_luts <= 1024.  Every instance shares them;
+ *   they are uploaded once per call.
+ * Scheduling: a LUT node costs one level, like a bootstrapped gate; the LUT nodes of a level run as one launch group per theta (the spec and
+ *   the table vary per node).  LUT_OUT wires sit on their head's level, so NOT / COPY may read them at once.
+ * stats: a LUT node counts one rotation whatever its theta, a LUT_OUT row nothing; launches counts each LUT launch group.
+ * inputs / instances / out_wires / outputs / stats: the contract of thfhe_dag_run_batch.
+ * Checks, on the host before any device work and before the context is looked at (THFHE_E_INVALID): null pointers, n_specs / n_luts out of
+ *   range, an invalid spec (the rules of thfhe_lut_bootstrap), a spec or table index out of range, operands that do not match the spec's
+ *   n_inputs, a missing, extra or misplaced LUT_OUT row or one naming the wrong head, spec / lut not -1 on a gate row, operands that are not
+ *   earlier wires, opcodes the engine does not define.  thfhe_dag_run(_batch) and thfhe_mk_dag_run(_batch) reject THFHE_LUT and THFHE_LUT_OUT. */
+int thfhe_dag_run_lut_batch(thfhe_ctx *ctx, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs,
+                            int n_specs, const int32_t *tv, int n_luts, size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs,
+                            int64_t *stats);
+
 /* ---- device-buffer API: records already resident in HBM (what bench.py times).  Pointers come from
  * thfhe_dev_alloc (or any hipMalloc in this process).  Calls enqueue on the context's stream and
  * return; thfhe_sync waits. */
@@ -205,6 +228,11 @@ int thfhe_mk_lut_bootstrap(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec, const 
                            const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count);
 int thfhe_mk_lut_bootstrap_wo_keyswitch(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec, const int64_t *tv, int n_luts, const int32_t *lut_index,
                                         const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1, size_t count);
+/* LUT nodes in the 3-gen gate-DAG executor: the contract of thfhe_dag_run_lut_batch with the gate opcodes of thfhe_mk_dag_run_batch, records of
+ * P*n+1 words and Torus64 tables tv: HOST int64[n_luts][N] (N = the context's ring degree).  A LUT node equals thfhe_mk_lut_bootstrap bit for bit. */
+int thfhe_mk_dag_run_lut_batch(thfhe_mk_ctx *ctx, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                               const thfhe_lut_spec *specs, int n_specs, const int64_t *tv, int n_luts, size_t instances, const int32_t *out_wires,
+                               size_t n_out, int32_t *outputs, int64_t *stats);
 /* Party-sharded building blocks (optional mode: a rank holds only the keys of a contiguous block of m
  * parties, i.e. a context created with parties = m from those parties' key parts; m = 1 is one rank per party).  Below
  * nb = m * n (the block's mask words) and P = the key set's total party count.  All pointers are DEVICE pointers; calls enqueue

@@ -37,6 +37,13 @@ inline int lut_validate(const thfhe_lut_spec *sp, const void *tv, int n_luts, co
     return THFHE_OK;
 }
 
+// The spec rules of lut_validate on their own (the gate-DAG LUT nodes, thfhe_dag.h): n_inputs 1 .. 3, theta 1, 2 or 4.
+inline int lut_spec_check(const thfhe_lut_spec &sp) {
+    if (sp.n_inputs < 1 || sp.n_inputs > 3) return thfhe_fail(THFHE_E_INVALID, "lut spec: n_inputs must be 1, 2 or 3");
+    if (sp.theta != 1 && sp.theta != 2 && sp.theta != 4) return thfhe_fail(THFHE_E_INVALID, "lut spec: theta must be 1, 2 or 4");
+    return THFHE_OK;
+}
+
 #define THFHE_HIP(expr)                                                    \
     do {                                                                   \
         hipError_t thfhe_e_ = (expr);                                      \

@@ -1,12 +1,15 @@
 // thfhe_dag.h -- the gate-DAG front end shared by the single-key and the 3-gen multi-key engines:
 // an ASAP levelising scheduler for the reference's circuits (src/KNN_medical_data.cpp:127-489, J/3gen_mk_gates.jl:183-362), and the
-// gather / scatter kernels of the device-resident executor.
+// gather / scatter kernels of the device-resident executor.  LUT nodes (thfhe_dag_run_lut_batch): programmable bootstraps among the
+// gates, fed by a fused prologue that reads their operands from the wire table, their theta outputs scattered into consecutive wires.
 #ifndef THFHE_DAG_H
 #define THFHE_DAG_H
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/thfhe_hip.h"
@@ -50,17 +53,67 @@ __global__ __launch_bounds__(256) void dag_wire_linear_kernel(int32_t *__restric
     const uint32_t v = (uint32_t)wires[(base + in_idx[g]) * words + i];
     wires[(base + out_idx[g]) * words + i] = (int32_t)(ops[g] == THFHE_NOT ? 0u - v : v);
 }
+// Fused prologue of a LUT launch group: job j of the slice is node g of instance q (G = first + j = q cnt + g).  Its 1-3 operands come straight
+// from the wire table, weighted by its spec, the bias added to the body, every word rounded to a multiple of theta in Z_2N -- the arithmetic of
+// sk_lut_prologue_kernel / mk_lut_prologue_kernel word for word -- and the node's table index goes to lut_idx[j] for the rotation.
+// n = mask words of a record (n, or P n on the 3-gen scheme), pad = row stride of bara.  One thread per word; grid.y strides over the jobs.
+__global__ __launch_bounds__(256) void dag_lut_prologue_kernel(const int32_t *__restrict__ wires, const int32_t *__restrict__ t0, const int32_t *__restrict__ t1,
+                                                               const int32_t *__restrict__ t2, const int32_t *__restrict__ t_spec,
+                                                               const int32_t *__restrict__ t_lut, const thfhe_lut_spec *__restrict__ specs, long first,
+                                                               long total, long cnt, size_t n_wires, int n, int pad, int log2_2n, int32_t *__restrict__ bara,
+                                                               int32_t *__restrict__ barb, int32_t *__restrict__ lut_idx) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    const size_t words = (size_t)n + 1;
+    for (long j = blockIdx.y; j < total; j += gridDim.y) {
+        const long G = first + j, q = G / cnt, g = G - q * cnt;
+        const thfhe_lut_spec sp = specs[t_spec[g]];
+        const int32_t *rec = wires + (size_t)q * n_wires * words + i;
+        uint32_t v = (uint32_t)sp.weights[0] * (uint32_t)rec[(size_t)t0[g] * words];
+        if (sp.n_inputs > 1) v += (uint32_t)sp.weights[1] * (uint32_t)rec[(size_t)t1[g] * words];
+        if (sp.n_inputs > 2) v += (uint32_t)sp.weights[2] * (uint32_t)rec[(size_t)t2[g] * words];
+        if (i == n) v += (uint32_t)sp.bias;
+        const int log2_theta = sp.theta == 4 ? 2 : sp.theta >> 1;
+        const int32_t bar = (int32_t)((uint32_t)modswitch2n((int32_t)v, log2_2n - log2_theta) << log2_theta);
+        if (i == n) {
+            barb[j] = bar;
+            lut_idx[j] = t_lut[g];
+        } else {
+            bara[j * pad + i] = bar;
+        }
+    }
+}
+// theta-record scatter of a LUT launch group: key-switched record r = j theta + t of the slice -> wire idx[g] + t of instance q
+__global__ __launch_bounds__(256) void dag_scatter_theta_kernel(const int32_t *__restrict__ src, const int32_t *__restrict__ idx, int32_t *__restrict__ wires,
+                                                                long first, long total, long cnt, size_t n_wires, int words, int theta) {
+    const long r = blockIdx.x;
+    const int i = blockIdx.y * 256 + threadIdx.x;
+    if (r >= total * theta || i >= words) return;
+    const long j = r / theta, t = r - j * theta, G = first + j, q = G / cnt, g = G - q * cnt;
+    wires[((size_t)q * n_wires + idx[g] + t) * words + i] = src[r * words + i];
+}
 
 
 // One launch group of the schedule: `count` gates of one class whose operands are all available.
 struct DagBatch {
-    int32_t depth, sub, cls;  // cls: engine-defined gate class; 2 = NOT / COPY (no bootstrap)
-    size_t off, count;        // index table slice: [ops | in0 | in1 | in2 | out], `count` entries each, at tab[off]
+    int32_t depth, sub, cls;  // cls: engine-defined gate class; 2 = NOT / COPY (no bootstrap); 4 / 5 / 6 = LUT nodes of theta 1 / 2 / 4
+    size_t off, count;        // index table slice: [ops | in0 | in1 | in2 | out], LUT classes + [spec | lut], `count` entries each, at tab[off]
 };
+constexpr int kDagLutOut = 7;                // LUT_OUT row: no launch, its wire is written by its head's scatter
+inline int dag_lut_class(int theta) { return theta == 1 ? 4 : (theta == 2 ? 5 : 6); }
+inline int dag_lut_theta(int cls) { return cls == 4 ? 1 : (cls == 5 ? 2 : 4); }
+
+// The LUT side of a run (thfhe_dag_run_lut_batch): node rows of 6 words, the run's specs and its table count.
+struct DagLuts {
+    const thfhe_lut_spec *specs;
+    int n_specs, n_luts;
+};
+
 struct DagPlan {
     std::vector<DagBatch> batches;
     std::vector<int32_t> tab;
     size_t max_width = 0, max_rot = 0;
+    int max_theta = 1;   // most records per node of any launch group (LUT groups: theta); sizes staging and workspace
     int64_t rotations = 0;
     int32_t max_depth = 0;
     void fill_stats(int64_t *stats) const {
@@ -72,21 +125,48 @@ struct DagPlan {
 // ASAP schedule.  gates: int32[n_gates][4] = (opcode, in0, in1, in2) in topological order; gate g defines wire n_inputs + g.
 // classify(op) -> class id (0 = two-input bootstrapped gate, 1 = MUX, 2 = NOT / COPY, 3 = three-input bootstrapped gate) or -1.
 // Bootstrapped gates add one level; NOT / COPY ride on their operand's level as sub-levels (a NOT may read a NOT of the same depth).
+// luts (thfhe_dag_run_lut_batch): rows of 6 words (opcode, in0, in1, in2, spec, lut); a THFHE_LUT node adds one level like a bootstrapped
+// gate and joins the launch group of its theta; its theta - 1 THFHE_LUT_OUT rows take its depth with sub-level 0 and launch nothing.
 template <typename Classify>
-int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify classify, DagPlan &plan) {
-    const size_t n_wires = n_inputs + n_gates;
+int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify classify, DagPlan &plan, const DagLuts *luts = nullptr) {
+    const size_t n_wires = n_inputs + n_gates, stride = luts ? 6 : 4;
     if (n_wires > (size_t)INT32_MAX / 2) return thfhe_fail(THFHE_E_INVALID, "too many wires");
     std::vector<int32_t> depth(n_wires, 0), sub(n_wires, 0), cls(n_gates, 0);
     int32_t max_depth = 0;
+    int32_t head = -1, pending = 0;   // the LUT node whose LUT_OUT rows are still due, and how many
     for (size_t g = 0; g < n_gates; g++) {
-        const int32_t op = gates[4 * g], w = (int32_t)(n_inputs + g);
-        const int k = classify(op);
-        if (k < 0) return thfhe_fail(THFHE_E_INVALID, "gate opcode not defined for this engine");
+        const int32_t *row = gates + stride * g;
+        const int32_t op = row[0], w = (int32_t)(n_inputs + g);
+        if (luts && op == THFHE_LUT_OUT) {
+            if (pending == 0) return thfhe_fail(THFHE_E_INVALID, "LUT_OUT row without a LUT node before it (extra or misplaced LUT_OUT row)");
+            if (row[1] != head) return thfhe_fail(THFHE_E_INVALID, "LUT_OUT row names the wrong head (it must name its LUT node's wire)");
+            if (row[2] != -1 || row[3] != -1 || row[4] != -1 || row[5] != -1) return thfhe_fail(THFHE_E_INVALID, "LUT_OUT row: fields after the head must be -1");
+            pending--;
+            cls[g] = kDagLutOut;
+            depth[w] = depth[head], sub[w] = 0;
+            continue;
+        }
+        if (pending) return thfhe_fail(THFHE_E_INVALID, "LUT node: missing LUT_OUT row (theta - 1 of them must follow it)");
+        int k, nin;
+        if (luts && op == THFHE_LUT) {
+            if (row[4] < 0 || row[4] >= luts->n_specs) return thfhe_fail(THFHE_E_INVALID, "LUT node: spec index out of range (0 .. n_specs-1)");
+            if (row[5] < 0 || row[5] >= luts->n_luts) return thfhe_fail(THFHE_E_INVALID, "LUT node: table index out of range (0 .. n_luts-1)");
+            const thfhe_lut_spec &sp = luts->specs[row[4]];
+            nin = sp.n_inputs;
+            for (int q = 0; q < 3; q++)
+                if ((q < nin) != (row[1 + q] != -1)) return thfhe_fail(THFHE_E_INVALID, "LUT node: operands do not match the spec's n_inputs (unused ones are -1)");
+            k = dag_lut_class(sp.theta);
+            head = w, pending = sp.theta - 1;
+        } else {
+            k = classify(op);
+            if (k < 0) return thfhe_fail(THFHE_E_INVALID, "gate opcode not defined for this engine");
+            if (luts && (row[4] != -1 || row[5] != -1)) return thfhe_fail(THFHE_E_INVALID, "gate row: spec and lut must be -1");
+            nin = k == 2 ? 1 : (k == 0 ? 2 : 3);
+        }
         cls[g] = k;
-        const int nin = k == 2 ? 1 : (k == 0 ? 2 : 3);
         int32_t d = 0, s = 0;
         for (int q = 0; q < nin; q++) {
-            const int32_t in = gates[4 * g + 1 + q];
+            const int32_t in = row[1 + q];
             if (in < 0 || in >= w) return thfhe_fail(THFHE_E_INVALID, "gate operand is not an earlier wire (gates must be in topological order)");
             if (depth[in] > d || (depth[in] == d && sub[in] > s)) d = depth[in], s = sub[in];
         }
@@ -94,11 +174,13 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
         depth[w] = d, sub[w] = s;
         if (d > max_depth) max_depth = d;
     }
+    if (pending) return thfhe_fail(THFHE_E_INVALID, "LUT node: missing LUT_OUT row (theta - 1 of them must follow it)");
     plan.max_depth = max_depth;
     // bucket: (depth, sub, class); bootstrapped classes first (sub 0), then the linear sub-levels in order
-    std::vector<std::vector<std::vector<int32_t>>> boot(max_depth + 1, std::vector<std::vector<int32_t>>(4)), lin(max_depth + 1);
+    std::vector<std::vector<std::vector<int32_t>>> boot(max_depth + 1, std::vector<std::vector<int32_t>>(7)), lin(max_depth + 1);
     for (size_t g = 0; g < n_gates; g++) {
         const int32_t w = (int32_t)(n_inputs + g);
+        if (cls[g] == kDagLutOut) continue;
         if (cls[g] == 2) {
             auto &L = lin[depth[w]];
             if ((int)L.size() < sub[w]) L.resize(sub[w]);
@@ -111,24 +193,56 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
     auto emit = [&](int32_t d, int32_t s, int32_t k, const std::vector<int32_t> &G) {
         if (G.empty()) return;
         DagBatch b{d, s, k, plan.tab.size(), G.size()};
-        for (int col = 0; col < 5; col++)
-            for (int32_t g : G) plan.tab.push_back(col == 4 ? (int32_t)(n_inputs + g) : (col == 0 ? gates[4 * g] : (gates[4 * g + col] < 0 ? 0 : gates[4 * g + col])));
+        const int cols = k >= 4 ? 7 : 5;   // LUT groups: + spec, lut
+        for (int col = 0; col < cols; col++)
+            for (int32_t g : G) {
+                const int32_t *row = gates + stride * g;   // columns 5, 6 = row fields 4, 5 (spec, lut)
+                plan.tab.push_back(col == 4 ? (int32_t)(n_inputs + g) : (col == 0 ? row[0] : (row[col < 4 ? col : col - 1] < 0 ? 0 : row[col < 4 ? col : col - 1])));
+            }
         plan.batches.push_back(b);
         if (G.size() > plan.max_width) plan.max_width = G.size();
         const size_t rot = k == 2 ? 0 : (k == 1 ? 2 * G.size() : G.size());
         if (rot > plan.max_rot) plan.max_rot = rot;
+        if (k >= 4 && dag_lut_theta(k) > plan.max_theta) plan.max_theta = dag_lut_theta(k);
         plan.rotations += (int64_t)rot;
     };
     for (int32_t d = 0; d <= max_depth; d++) {
-        for (int32_t k : {0, 3, 1}) emit(d, 0, k, boot[d][k]);
+        for (int32_t k : {0, 3, 1, 4, 5, 6}) emit(d, 0, k, boot[d][k]);
         for (size_t q = 0; q < lin[d].size(); q++) emit(d, (int32_t)q + 1, 2, lin[d][q]);
     }
     return THFHE_OK;
 }
 
+// Host-side checks and plan of thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch, before any device work and before the context is looked
+// at: null pointers, the spec and table counts, every spec (the rules of lut_validate), the output wire ids, then dag_plan's row checks.
+template <typename Classify>
+int dag_lut_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs, int n_specs, const void *tv,
+                 int n_luts, const int32_t *out_wires, size_t n_out, const int32_t *outputs, Classify classify, DagPlan &plan) {
+    if ((!inputs && n_inputs) || (!nodes && n_nodes) || (!outputs && n_nodes) || (!out_wires && n_out) || !specs || !tv)
+        return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (n_specs < 1 || n_specs > 1024) return thfhe_fail(THFHE_E_INVALID, "n_specs must be 1 .. 1024");
+    if (n_luts < 1 || n_luts > 1024) return thfhe_fail(THFHE_E_INVALID, "n_luts must be 1 .. 1024");
+    for (int s = 0; s < n_specs; s++)
+        THFHE_TRY(lut_spec_check(specs[s]));
+    for (size_t s = 0; s < n_out; s++)
+        if (out_wires[s] < 0 || (size_t)out_wires[s] >= n_inputs + n_nodes) return thfhe_fail(THFHE_E_INVALID, "output wire id out of range");
+    const DagLuts luts{specs, n_specs, n_luts};
+    return dag_plan(nodes, n_inputs, n_nodes, classify, plan, &luts);
+}
+
 // Device buffers of the executor (grow-only, owned by the engine's context and reused by every run on it).
 struct DagBuffers {
     DevBuf wires, tab, ops, pack;
+    DevBuf specs;   // thfhe_lut_spec[n_specs] of a LUT run
+};
+
+// The slice of a LUT launch group that DagExecute hands to the engine: wire table, the group's index columns, jobs [first, first + total) of
+// cnt nodes per instance.  The engine runs dag_lut_prologue_kernel, its LUT rotation and the key switch of total x theta records into its
+// staging output.
+struct DagLutSlice {
+    const int32_t *wires, *t0, *t1, *t2, *t_spec, *t_lut;
+    long first, total, cnt;
+    size_t n_wires;
 };
 
 // Device-resident executor.  Level by level, each class of a level as slices of at most `slice_cap` gates over ALL instances: gather ->
@@ -138,9 +252,13 @@ struct DagBuffers {
 //   h_sel     wire ids to return (n_sel of them) or null = every gate wire [n_inputs, n_wires)
 //   h_out     int32[instances][n_sel or n_gates][words]
 // ensure(max_gates_per_slice) sizes the engine's workspace and staging and returns its staging pointers through the out-parameters.
-template <typename Ensure, typename Run>
+// LUT launch groups (plans of thfhe_dag_run_lut_batch): run_lut(theta, DagLutSlice) -> fused prologue + LUT rotation + key switch of the
+// slice's nodes x theta records into the staging output, then the theta-record scatter into wires out[g] + j.  ensure sizes for
+// plan.max_theta records per node.
+template <typename Ensure, typename Run, typename RunLut = std::nullptr_t>
 int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int words, size_t n_inputs, size_t n_gates, size_t instances,
-                const int32_t *h_inputs, const int32_t *h_sel, size_t n_sel, int32_t *h_out, size_t slice_cap, Ensure ensure, Run run) {
+                const int32_t *h_inputs, const int32_t *h_sel, size_t n_sel, int32_t *h_out, size_t slice_cap, Ensure ensure, Run run,
+                RunLut run_lut = nullptr) {
     const size_t n_wires = n_inputs + n_gates;
     if (instances == 0 || n_gates == 0) return THFHE_OK;
     if (n_wires * instances > ((size_t)1 << 40) / (size_t)words) return thfhe_fail(THFHE_E_INVALID, "wire table too large");
@@ -171,6 +289,22 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
         const int32_t *t_ops = d_tab + plan.batches[b].off, *t0 = t_ops + cnt, *t1 = t0 + cnt, *t2 = t1 + cnt, *t_out = t2 + cnt;
         if (cls == 2) {
             hipLaunchKernelGGL(dag_wire_linear_kernel, dim3((unsigned)all, wb), block, 0, stream, d_wires, t0, t_out, t_ops, all, cnt, n_wires, words);
+            continue;
+        }
+        if (cls >= 4) {
+            if constexpr (std::is_same_v<RunLut, std::nullptr_t>) {
+                rc = thfhe_fail(THFHE_E_INVALID, "LUT node in a gate-only run");
+            } else {
+                const int theta = dag_lut_theta(cls);
+                const int32_t *t_spec = t_out + cnt, *t_lut = t_spec + cnt;
+                for (long first = 0; first < all && rc == THFHE_OK; first += (long)slice) {
+                    const long n = all - first < (long)slice ? all - first : (long)slice;
+                    rc = run_lut(theta, DagLutSlice{d_wires, t0, t1, t2, t_spec, t_lut, first, n, cnt, n_wires});
+                    if (!rc)
+                        hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(n * theta), wb), block, 0, stream, stage_out, t_out, d_wires, first, n, cnt,
+                                           n_wires, words, theta);
+                }
+            }
             continue;
         }
         for (long first = 0; first < all && rc == THFHE_OK; first += (long)slice) {

@@ -17,7 +17,8 @@
 //                             of b: one workgroup per (sample, party, range), or from 192 samples on the rows staged in LDS for 32 samples
 //   mk_lut_prologue_kernel / mk_lut_acc_init_kernel / mk_extract_at_kernel   programmable bootstrap (thfhe_mk_lut_bootstrap): weighted
 //                             sum + mod-switch to multiples of theta, accumulator X^{-barb} * tv in global memory, the rotation kernels above
-//                             through acc_in / acc_out, extraction of theta coefficients
+//                             through acc_in / acc_out, extraction of theta coefficients; behind dag_lut_prologue_kernel (thfhe_dag.h) they
+//                             run the LUT nodes of the gate DAG (thfhe_mk_dag_run_lut_batch)
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -996,22 +997,21 @@ int mk_enqueue_bootstraps(thfhe_mk_ctx *c, const int32_t *d0, const int32_t *d1,
     return THFHE_OK;
 }
 
-// programmable bootstrap of `count` samples: lut prologue + accumulator start, the rotation of mk_bootstrap_3gen, extraction of
-// theta coefficients into d_u [count][theta][N+1]; then, if d_dst is given, the key switch of the count x theta records into d_dst.  The
-// profiling events sit on the boundaries of mk_enqueue_bootstraps: prologue | rotation + extraction | key switch.
-int mk_enqueue_lut(thfhe_mk_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0, const int32_t *d1, const int32_t *d2, size_t count,
-                   const int64_t *d_tv, const int32_t *d_idx, int32_t *d_dst) {
-    const int N = c->p.N;
-    const size_t recs = count * sp.theta;
+// workspace of a programmable bootstrap of `count` samples with theta outputs each: bara / barb, count x theta extracted records, accumulators
+int mk_lut_workspace(thfhe_mk_ctx *c, size_t count, int theta) {
     int rc = mk_ensure_workspace(c, count);
-    if (!rc) rc = c->d_u.grow(recs * ((size_t)N + 1) * sizeof(int32_t));
-    if (!rc) rc = c->d_acc.grow(count * 2 * (size_t)N * sizeof(int64_t));
-    if (rc) return rc;
+    if (!rc) rc = c->d_u.grow(count * theta * ((size_t)c->p.N + 1) * sizeof(int32_t));
+    if (!rc) rc = c->d_acc.grow(count * 2 * (size_t)c->p.N * sizeof(int64_t));
+    return rc;
+}
+
+// the rotation side of a programmable bootstrap of `count` samples whose bara / barb are in the workspace: accumulator start from the
+// sample's table, the rotation of mk_bootstrap_3gen, extraction of theta coefficients into d_u [count][theta][N+1]; then, if d_dst is given,
+// the key switch of the count x theta records into d_dst.  Shared by mk_enqueue_lut and the gate-DAG LUT nodes (thfhe_mk_dag_run_lut_batch).
+int mk_enqueue_lut_rotation(thfhe_mk_ctx *c, int theta, size_t count, const int64_t *d_tv, const int32_t *d_idx, int32_t *d_dst) {
+    const int N = c->p.N;
+    const size_t recs = count * theta;
     int64_t *acc = c->d_acc.as<int64_t>();
-    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
-    dim3 pg((unsigned)((c->words + 1 + 255) / 256), (unsigned)(count < 65535 ? count : 65535));
-    hipLaunchKernelGGL(mk_lut_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, sp.n_inputs, sp.weights[0], sp.weights[1], sp.weights[2],
-                       sp.bias, ilog2(sp.theta), c->words, c->w_pad, c->log2_2n, (long)count, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
     hipLaunchKernelGGL(mk_lut_acc_init_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, c->d_barb.as<int32_t>(), d_tv, d_idx, (long)count, N, acc);
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
     // acc_in == acc_out == d_acc: every rotation shape may run in place.  The N = 1024 / 2048 coop and pair kernels copy their job's
@@ -1020,10 +1020,10 @@ int mk_enqueue_lut(thfhe_mk_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0,
     // acc_in is the accumulator it rotates.  barb is not read when acc_in is given: the start above already applied X^{-barb}.
     MKBRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), nullptr, (long)count, c->p.parties * c->p.n,
                c->w_pad, c->p.Bgbit, 0, acc, acc};
-    rc = mk_launch_rotation(c, a);
+    int rc = mk_launch_rotation(c, a);
     if (rc) return rc;
-    hipLaunchKernelGGL(mk_extract_at_kernel, dim3((unsigned)count, (unsigned)sp.theta), dim3(256), 0, c->stream, (const int64_t *)acc, c->d_u.as<int32_t>(),
-                       (long)count, N, sp.theta);
+    hipLaunchKernelGGL(mk_extract_at_kernel, dim3((unsigned)count, (unsigned)theta), dim3(256), 0, c->stream, (const int64_t *)acc, c->d_u.as<int32_t>(),
+                       (long)count, N, theta);
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
     if (d_dst) {
         MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_u.as<int32_t>(), d_dst, (long)recs, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, N, N + 1, 0};
@@ -1037,6 +1037,19 @@ int mk_enqueue_lut(thfhe_mk_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0,
     }
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
+}
+
+// programmable bootstrap of `count` samples: lut prologue, then mk_enqueue_lut_rotation.  The profiling events sit on the
+// boundaries of mk_enqueue_bootstraps: prologue | rotation + extraction | key switch.
+int mk_enqueue_lut(thfhe_mk_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0, const int32_t *d1, const int32_t *d2, size_t count,
+                   const int64_t *d_tv, const int32_t *d_idx, int32_t *d_dst) {
+    int rc = mk_lut_workspace(c, count, sp.theta);
+    if (rc) return rc;
+    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
+    dim3 pg((unsigned)((c->words + 1 + 255) / 256), (unsigned)(count < 65535 ? count : 65535));
+    hipLaunchKernelGGL(mk_lut_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, sp.n_inputs, sp.weights[0], sp.weights[1], sp.weights[2],
+                       sp.bias, ilog2(sp.theta), c->words, c->w_pad, c->log2_2n, (long)count, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
+    return mk_enqueue_lut_rotation(c, sp.theta, count, d_tv, d_idx, d_dst);
 }
 
 int mk_launch_rotation(thfhe_mk_ctx *c, const MKBRArgs &a) {
@@ -1186,6 +1199,20 @@ int mk_gates_dev_locked(thfhe_mk_ctx *c, int op, const int32_t *d0, const int32_
     return THFHE_OK;
 }
 
+// gate classes of the 3-gen gate DAG (thfhe_dag.h): two-input gates NAND / OR / AND / XOR, MUX, NOT / COPY, AND3
+int mk_dag_classify(int op) {
+    return op == THFHE_NOT || op == THFHE_COPY ? 2 : (op == THFHE_MUX ? 1 : (op == THFHE_AND3 ? 3 : (op == THFHE_NAND || op == THFHE_OR || op == THFHE_AND || op == THFHE_XOR ? 0 : -1)));
+}
+
+// one launch of a gate-DAG gate class from the staging arrays into stage.out (dag_execute's run): two-input gates with per-gate opcodes, MUX
+// or AND3
+int mk_dag_gate_class(thfhe_mk_ctx *c, int cls, const int32_t *d_ops, size_t n) {
+    MKLin L;
+    mk_gate_lin(THFHE_NAND, 0, L);
+    if (cls == 0) return mk_enqueue_bootstraps(c, c->stage.in_ptr(0), c->stage.in_ptr(1), nullptr, L, L, 1, n, (int64_t)1 << 61, c->stage.out_ptr(), d_ops);
+    return mk_gates_dev_locked(c, cls == 1 ? THFHE_MUX : THFHE_AND3, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), c->stage.out_ptr(), n);
+}
+
 // thfhe_mk_lut_bootstrap (keyswitch) / thfhe_mk_lut_bootstrap_wo_keyswitch: out = count x theta records of P n + 1 (resp. N + 1) words
 int mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
                      const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch) {
@@ -1330,18 +1357,12 @@ int thfhe_mk_dag_run_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inpu
                            const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
     if (!c || (!inputs && n_inputs) || (!gates && n_gates) || (!outputs && n_gates) || (!out_wires && n_out)) return thfhe_fail(THFHE_E_INVALID, "null argument");
     DagPlan plan;
-    int rc = dag_plan(gates, n_inputs, n_gates,
-                      [](int op) {
-                          return op == THFHE_NOT || op == THFHE_COPY ? 2 : (op == THFHE_MUX ? 1 : (op == THFHE_AND3 ? 3 : (op == THFHE_NAND || op == THFHE_OR || op == THFHE_AND || op == THFHE_XOR ? 0 : -1)));
-                      },
-                      plan);
+    int rc = dag_plan(gates, n_inputs, n_gates, mk_dag_classify, plan);
     if (rc) return rc;
     if (stats) plan.fill_stats(stats);
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
     const int words = c->words + 1;
-    MKLin L;
-    mk_gate_lin(THFHE_NAND, 0, L);
     return dag_execute(
         plan, c->dag, c->stream, words, n_inputs, n_gates, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) {
@@ -1350,9 +1371,46 @@ int thfhe_mk_dag_run_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inpu
             in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
             return r;
         },
-        [&](int cls, const int32_t *d_ops, size_t n) {
-            if (cls == 0) return mk_enqueue_bootstraps(c, c->stage.in_ptr(0), c->stage.in_ptr(1), nullptr, L, L, 1, n, (int64_t)1 << 61, c->stage.out_ptr(), d_ops);
-            return mk_gates_dev_locked(c, cls == 1 ? THFHE_MUX : THFHE_AND3, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), c->stage.out_ptr(), n);
+        [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); });
+}
+
+// LUT nodes among the 3-gen gates: the gate classes run as in thfhe_mk_dag_run_batch; a LUT launch group runs the fused
+// prologue (dag_lut_prologue_kernel over the P n + 1 record words), then mk_enqueue_lut_rotation with the key switch into the staging output.
+int thfhe_mk_dag_run_lut_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                               const thfhe_lut_spec *specs, int n_specs, const int64_t *tv, int n_luts, size_t instances, const int32_t *out_wires,
+                               size_t n_out, int32_t *outputs, int64_t *stats) {
+    DagPlan plan;
+    int rc = dag_lut_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, out_wires, n_out, outputs, mk_dag_classify, plan);
+    if (rc) return rc;
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (stats) plan.fill_stats(stats);
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const int words = c->words + 1, theta_max = plan.max_theta;
+    const size_t N = c->p.N;
+    rc = c->d_tv.grow((size_t)n_luts * N * sizeof(int64_t));
+    if (!rc) rc = c->dag.specs.grow((size_t)n_specs * sizeof(thfhe_lut_spec));
+    if (rc) return rc;
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv, (size_t)n_luts * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(c->dag.specs.as<thfhe_lut_spec>(), specs, (size_t)n_specs * sizeof(thfhe_lut_spec), hipMemcpyHostToDevice, c->stream));
+    return dag_execute(
+        plan, c->dag, c->stream, words, n_inputs, n_nodes, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
+        [&](size_t max_gates, int32_t **in, int32_t **out) {
+            int r = mk_ensure_workspace(c, 2 * max_gates);
+            if (!r) r = mk_lut_workspace(c, max_gates, theta_max);
+            if (!r) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
+            if (!r) r = c->stage.grow(max_gates * words);
+            if (!r) r = c->stage.out.grow(theta_max * max_gates * words * sizeof(int32_t));   // key switch of nodes x theta records
+            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
+            return r;
+        },
+        [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); },
+        [&](int theta, const DagLutSlice &s) {
+            const dim3 pg((unsigned)((c->words + 1 + 255) / 256), (unsigned)(s.total < 65535 ? s.total : 65535));
+            hipLaunchKernelGGL(dag_lut_prologue_kernel, pg, dim3(256), 0, c->stream, s.wires, s.t0, s.t1, s.t2, s.t_spec, s.t_lut,
+                               (const thfhe_lut_spec *)c->dag.specs.as<thfhe_lut_spec>(), s.first, s.total, s.cnt, s.n_wires, c->words, c->w_pad, c->log2_2n,
+                               c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
+            return mk_enqueue_lut_rotation(c, theta, (size_t)s.total, c->d_tv.as<int64_t>(), c->d_lut_idx.as<int32_t>(), c->stage.out_ptr());
         });
 }
 

@@ -6,7 +6,8 @@
 //   sk_prologue_kernel        gate linear part (J/gates.jl:15-177) + mod-switch decode_message(.,2N)
 //                             (J/bootstrap.jl:80-81) -> bara[job][n], barb[job]
 //   sk_lut_prologue_kernel    programmable bootstrap (thfhe_lut_bootstrap): weighted sum of 1-3 inputs + bias, mod-switch to multiples of theta;
-//                             the blind-rotate kernels' LUT instantiations start from a test vector and extract theta coefficients
+//                             the blind-rotate kernels' LUT instantiations start from a test vector and extract theta coefficients;
+//                             LUT nodes of the gate DAG (thfhe_dag_run_lut_batch) use them behind dag_lut_prologue_kernel (thfhe_dag.h)
 //   sk_blind_rotate_ring_kernel / sk_blind_rotate_coop_kernel   blind_rotate_and_extract (J/bootstrap.jl:38-65): accumulator in
 //                             LDS for all n CMuxes; throughput (8 gates per workgroup, key through an LDS-DMA ring) and latency
 //                             (one workgroup per gate) variants
@@ -1036,6 +1037,16 @@ int gates_dev_locked(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1,
     return enqueue_keyswitch(c, c->d_u.as<int32_t>(), dout, count, rot, true);
 }
 
+// one launch of a gate-DAG gate class from the staging arrays into stage.out (thfhe_dag.h, dag_execute's run): two-input gates with per-gate
+// opcodes, or MUX
+int dag_gate_class(thfhe_ctx *c, int cls, const int32_t *d_ops, size_t n) {
+    const bool is_mux = cls == 1;
+    int r = enqueue_rotations(c, is_mux ? THFHE_MUX : THFHE_NAND, c->stage.in_ptr(0), c->stage.in_ptr(1), is_mux ? c->stage.in_ptr(2) : nullptr, n, is_mux ? 2 : 1, 1 << 29,
+                              is_mux ? nullptr : d_ops);
+    if (!r) r = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), n, is_mux ? 2 : 1, false);
+    return r;
+}
+
 // thfhe_lut_bootstrap (keyswitch) / thfhe_lut_bootstrap_wo_keyswitch: out = count x theta records of n+1 (resp. N+1) words
 int lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
                   const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch) {
@@ -1201,11 +1212,53 @@ int thfhe_dag_run_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs, co
             in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
             return r;
         },
-        [&](int cls, const int32_t *d_ops, size_t n) {
-            const bool is_mux = cls == 1;
-            int r = enqueue_rotations(c, is_mux ? THFHE_MUX : THFHE_NAND, c->stage.in_ptr(0), c->stage.in_ptr(1), is_mux ? c->stage.in_ptr(2) : nullptr, n, is_mux ? 2 : 1, 1 << 29,
-                                      is_mux ? nullptr : d_ops);
-            if (!r) r = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), n, is_mux ? 2 : 1, false);
+        [&](int cls, const int32_t *d_ops, size_t n) { return dag_gate_class(c, cls, d_ops, n); });
+}
+
+// LUT nodes among the gates: the gate classes run as in thfhe_dag_run_batch; a LUT launch group runs the fused prologue
+// (dag_lut_prologue_kernel: operands straight from the wire table), the LUT instantiations of the blind-rotate kernels on the shapes of
+// launch_br, and the key switch of its nodes x theta records.
+int thfhe_dag_run_lut_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs,
+                            int n_specs, const int32_t *tv, int n_luts, size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs,
+                            int64_t *stats) {
+    DagPlan plan;
+    int rc = dag_lut_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, out_wires, n_out, outputs,
+                          [](int op) { return op == THFHE_NOT || op == THFHE_COPY ? 2 : (op == THFHE_MUX ? 1 : (op >= THFHE_NAND && op <= THFHE_ORYN ? 0 : -1)); },
+                          plan);
+    if (rc) return rc;
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (stats) plan.fill_stats(stats);
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const int words = c->p.n + 1, theta_max = plan.max_theta;
+    // the run's tables and specs, once per call
+    rc = c->d_tv.grow((size_t)n_luts * 1024 * sizeof(int32_t));
+    if (!rc) rc = c->dag.specs.grow((size_t)n_specs * sizeof(thfhe_lut_spec));
+    if (rc) return rc;
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(c->dag.specs.as<thfhe_lut_spec>(), specs, (size_t)n_specs * sizeof(thfhe_lut_spec), hipMemcpyHostToDevice, c->stream));
+    return dag_execute(
+        plan, c->dag, c->stream, words, n_inputs, n_nodes, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
+        [&](size_t max_gates, int32_t **in, int32_t **out) {
+            int r = ensure_workspace(c, 2 * max_gates);
+            if (!r) r = c->d_u.grow(theta_max * max_gates * 1025 * sizeof(int32_t));
+            if (!r) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
+            if (!r) r = c->stage.grow(max_gates * words);
+            if (!r) r = c->stage.out.grow(theta_max * max_gates * words * sizeof(int32_t));   // key switch of nodes x theta records
+            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
+            return r;
+        },
+        [&](int cls, const int32_t *d_ops, size_t n) { return dag_gate_class(c, cls, d_ops, n); },
+        [&](int theta, const DagLutSlice &s) {
+            const int n = c->p.n;
+            const dim3 pg((unsigned)((n + 1 + 255) / 256), (unsigned)(s.total < 65535 ? s.total : 65535));
+            hipLaunchKernelGGL(dag_lut_prologue_kernel, pg, dim3(256), 0, c->stream, s.wires, s.t0, s.t1, s.t2, s.t_spec, s.t_lut,
+                               (const thfhe_lut_spec *)c->dag.specs.as<thfhe_lut_spec>(), s.first, s.total, s.cnt, s.n_wires, n, c->n_pad, ilog2(2 * c->p.N),
+                               c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
+            BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), s.total, n, c->n_pad,
+                     c->p.Bgbit, 0, c->d_tv.as<int32_t>(), c->d_lut_idx.as<int32_t>(), theta};
+            int r = launch_rotations<true>(c, a);
+            if (!r) r = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), (size_t)s.total * theta, 1, false);
             return r;
         });
 }

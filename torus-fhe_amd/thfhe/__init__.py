@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("THFHE_HIP_LIB", os.path.join(os.path.dirname(_HERE), 
 
 # gate opcodes (include/thfhe_hip.h enum thfhe_gate)
 NAND, OR, AND, XOR, XNOR, NOR, ANDNY, ANDYN, ORNY, ORYN, MUX, NOT, COPY, AND3 = range(14)
+LUT, LUT_OUT = 14, 15   # gate-DAG LUT node and its outputs j > 0 (dag_run_lut_batch only)
 
 MU8 = 1 << 29     # encode_message(1, 8), Torus32      (numeric-functions.jl:86-89)
 MU8_64 = 1 << 61  # encode_message64(1, 8), Torus64    (numeric-functions.jl:92-95)
@@ -155,6 +156,8 @@ SIGNATURES = {
     "thfhe_set_dag_slice": (C.c_int, [_vp, C.c_size_t]),
     "thfhe_mk_set_dag_slice": (C.c_int, [_vp, C.c_size_t]),
     "thfhe_dag_run_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
+    "thfhe_dag_run_lut_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, C.c_size_t, _i32p,
+                                          C.c_size_t, _i32p, _i64p]),
     "thfhe_bootstrap": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_keyswitch": (C.c_int, [_vp, _i32p, _i32p, C.c_size_t]),
@@ -202,6 +205,8 @@ SIGNATURES = {
     "thfhe_mk_gates_mixed": (C.c_int, [_vp, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_dag_run": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, _i64p]),
     "thfhe_mk_dag_run_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
+    "thfhe_mk_dag_run_lut_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, C.c_size_t,
+                                             _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_mk_bootstrap": (C.c_int, [_vp, C.c_int64, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
@@ -389,6 +394,28 @@ class _EvalKey(_Handle):
         st = np.zeros(4, np.int64)
         _check(self._fn("dag_run_batch")(self.h, _p32(x), n_in, _p32(g), g.shape[0], q, _p32(sel), 0 if sel is None else sel.shape[0], _p32(out),
                                          st.ctypes.data_as(_i64p)))
+        return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
+
+    def dag_run_lut_batch(self, input_records, nodes, specs, tv, out_wires=None):
+        """dag_run_batch with LUT nodes (thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch).  nodes: int32[n_nodes][6] =
+        (op, in0, in1, in2, spec, lut); specs: (n_inputs, (w0, w1, w2), bias, theta) tuples or LutSpec; tv: [n_luts][N] test vectors of the
+        ring's torus (int32 for CloudKey, int64 for MKCloudKey).  Returns (int32[instances][len(out_wires) or n_nodes][words], stats)."""
+        words = self.words
+        x = np.ascontiguousarray(input_records, np.int32)
+        if x.ndim != 3 or x.shape[2] != words:
+            raise ValueError("dag_run_lut_batch: input records must be int32[instances][n_inputs][%d]" % words)
+        g = np.ascontiguousarray(nodes, np.int32).reshape(-1, 6)
+        sp = (LutSpec * len(specs))(*[s if isinstance(s, LutSpec) else
+                                      LutSpec(int(s[0]), (C.c_int32 * 3)(*[_wrap32(w) for w in (list(s[1]) + [0, 0, 0])[:3]]), _wrap32(s[2]), int(s[3]))
+                                      for s in specs])
+        tv = np.ascontiguousarray(tv, self._tv_dtype).reshape(-1, self.params.N)
+        q, n_in = x.shape[0], x.shape[1]
+        sel = None if out_wires is None else np.ascontiguousarray(out_wires, np.int32).reshape(-1)
+        out = np.zeros((q, g.shape[0] if sel is None else sel.shape[0], words), np.int32)
+        st = np.zeros(4, np.int64)
+        ptv = tv.ctypes.data_as(_i64p if self._tv_dtype == np.int64 else _i32p)
+        _check(self._fn("dag_run_lut_batch")(self.h, _p32(x), n_in, _p32(g), g.shape[0], sp, len(specs), ptv, tv.shape[0], q, _p32(sel),
+                                             0 if sel is None else sel.shape[0], _p32(out), st.ctypes.data_as(_i64p)))
         return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
 
     def _bootstrap(self, x, mu):

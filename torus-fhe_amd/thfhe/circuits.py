@@ -8,12 +8,16 @@ independent gates of a level -- and of independent sub-circuits placed in the sa
 
 Bit vectors are MSB-first lists of wire ids, as in the reference (index nbits-1 = least significant bit,
 src/bootstrap_modules.cpp:95).
+
+LUT nodes (Circuit.lut): a programmable bootstrap among the gates -- one rotation, one level, theta outputs on consecutive wires
+(a THFHE_LUT row, then theta - 1 THFHE_LUT_OUT rows).  Circuits that hold them run on thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch;
+lut_ripple_add, from_gate_bit and to_gate_bit build integer arithmetic from them.
 """
 import time
 
 import numpy as np
 
-from . import AND, COPY, MUX, NOT, OR, XOR
+from . import AND, COPY, LUT, LUT_OUT, MUX, NOT, OR, XOR, _wrap32
 
 
 class Circuit:
@@ -23,6 +27,10 @@ class Circuit:
         self.n_inputs = 0
         self.gates = []   # (op, a, b, c) ; c = -1 unless MUX ; output wire id = n_inputs + index
         self.outputs = {}
+        self.tables = []      # test vectors of the LUT nodes (table ids index this list)
+        self.specs = []       # (n_inputs, (w0, w1, w2), bias, theta) of the LUT nodes, deduplicated
+        self.lut_rows = {}    # gate index of a LUT node -> (spec id, table id)
+        self._ids = {}
 
     def inputs(self, count):
         assert not self.gates, "declare all inputs before the first gate"
@@ -34,17 +42,58 @@ class Circuit:
         self.gates.append((op, a, b, c))
         return self.n_inputs + len(self.gates) - 1
 
+    def table(self, tv):
+        """Register a test vector (thfhe.lut.test_vector: int32[N] for the single-key engine, int64[N] with torus_bits=64 for the 3-gen one);
+        returns its table id.  Equal tables share one id."""
+        tv = np.ascontiguousarray(tv)
+        key = ("table", tv.dtype.str, tv.tobytes())
+        if key not in self._ids:
+            self._ids[key] = len(self.tables)
+            self.tables.append(tv)
+        return self._ids[key]
+
+    def lut(self, table_id, inputs, weights=(1,), bias=0, theta=1):
+        """A LUT node: programmable bootstrap of x = sum_q weights[q] * inputs[q] + (0, bias) through table `table_id`, theta outputs from one
+        rotation.  Returns the theta output wire ids (consecutive: the node's row, then theta - 1 LUT_OUT rows)."""
+        inputs = list(inputs)
+        if not 1 <= len(inputs) <= 3 or len(weights) != len(inputs):
+            raise ValueError("a LUT node takes 1 to 3 inputs and one weight per input")
+        if theta not in (1, 2, 4):
+            raise ValueError("theta must be 1, 2 or 4")
+        if not 0 <= table_id < len(self.tables):
+            raise ValueError(f"unknown table id {table_id}")
+        spec = (len(inputs), tuple(_wrap32(w) for w in list(weights) + [0] * (3 - len(weights))), _wrap32(bias), int(theta))
+        key = ("spec",) + spec
+        if key not in self._ids:
+            self._ids[key] = len(self.specs)
+            self.specs.append(spec)
+        head = self.gate(LUT, *(inputs + [-1] * (3 - len(inputs))))
+        self.lut_rows[len(self.gates) - 1] = (self._ids[key], int(table_id))
+        return [head] + [self.gate(LUT_OUT, head) for _ in range(theta - 1)]
+
+    def has_luts(self):
+        return bool(self.lut_rows)
+
+    def nodes(self):
+        """int32[n_gates][6] = (op, in0, in1, in2, spec, lut): the rows of thfhe_dag_run_lut_batch (spec = lut = -1 on gate rows)."""
+        rows = [tuple(g) + self.lut_rows.get(i, (-1, -1)) for i, g in enumerate(self.gates)]
+        return np.array(rows, np.int32).reshape(-1, 6)
+
     def n_wires(self):
         return self.n_inputs + len(self.gates)
 
     def levels(self):
-        """ASAP schedule: list of lists of gate indices; NOT costs no level (it is not bootstrapped, gates.jl:76-79)."""
+        """ASAP schedule: list of lists of gate indices; NOT costs no level (it is not bootstrapped, gates.jl:76-79).  A LUT node costs one
+        level; its LUT_OUT rows join its level."""
         depth = np.zeros(self.n_wires(), np.int64)
         lv = {}
         for gi, (op, a, b, c) in enumerate(self.gates):
-            d = max(depth[w] for w in (a, b, c) if w >= 0)
-            if op not in (NOT, COPY):
-                d += 1
+            if op == LUT_OUT:
+                d = depth[a]
+            else:
+                d = max(depth[w] for w in (a, b, c) if w >= 0)
+                if op not in (NOT, COPY):
+                    d += 1
             depth[self.n_inputs + gi] = d
             lv.setdefault((int(d), op in (NOT, COPY)), []).append(gi)
         keys = sorted(lv)  # (depth, is_not): bootstrapped gates of depth d first, then the free NOTs that read them
@@ -52,9 +101,12 @@ class Circuit:
 
     def census(self):
         ops = [g[0] for g in self.gates]
-        boot = sum(1 for o in ops if o not in (NOT, COPY))
-        return dict(gates=len(ops), bootstrapped=boot, mux=ops.count(MUX), rotations=boot + ops.count(MUX),
-                    depth=len([l for l in self.levels() if self.gates[l[0]][0] not in (NOT, COPY)]))
+        boot = sum(1 for o in ops if o not in (NOT, COPY, LUT_OUT))
+        c = dict(gates=len(ops), bootstrapped=boot, mux=ops.count(MUX), rotations=boot + ops.count(MUX),
+                 depth=len([l for l in self.levels() if self.gates[l[0]][0] not in (NOT, COPY)]))
+        if self.lut_rows:
+            c["luts"] = ops.count(LUT)
+        return c
 
 
 # ---- the reference's building blocks (src/KNN_medical_data.cpp) ---------------------------------------------------
@@ -397,6 +449,51 @@ def mk_int_mul_3gen(cir, a, b, zero):
     return [cp(result[i]) for i in range(W)]
 
 
+# ---- integer arithmetic from LUT nodes -------------------------------------------------------------------------------------
+# Integer bits use the padding-bit encoding of thfhe.lut at p = 4 (bit m = m * 2^32 / 8); gate bits are the gates' +-1/8.  Tables are built
+# for the ring of degree N, Torus32 (single key) or torus_bits=64 (3-gen multi-key), unless a table id is given.
+def adder_table(N=1024, torus_bits=32):
+    """theta = 2 test vector of a full-adder bit at p = 4: output 0 = parity (sum), output 1 = majority (carry) of a + b + c."""
+    from . import lut
+    return lut.test_vector([lut.int_outputs(lambda m: m & 1, 4, torus_bits=torus_bits), lut.int_outputs(lambda m: m >= 2, 4, torus_bits=torus_bits)],
+                           4, theta=2, N=N, torus_bits=torus_bits)
+
+
+def lut_ripple_add(cir, a_bits, b_bits, table_id=None, carry_in=None, N=1024, torus_bits=32):
+    """a + b on LSB-first p = 4 integer bits: one theta = 2 LUT node per bit (the node of bit i reads a_i, b_i and the carry of bit i-1).
+    Returns (sum bits LSB-first, carry out).  table_id: an adder_table registered in cir (None: registered here)."""
+    if table_id is None:
+        table_id = cir.table(adder_table(N, torus_bits))
+    carry, sums = carry_in, []
+    for a, b in zip(a_bits, b_bits):
+        if carry is None:
+            s, carry = cir.lut(table_id, [a, b], weights=(1, 1), theta=2)
+        else:
+            s, carry = cir.lut(table_id, [a, b, carry], weights=(1, 1, 1), theta=2)
+        sums.append(s)
+    return sums, carry
+
+
+def from_gate_bit(cir, w, table_id=None, N=1024, torus_bits=32):
+    """Gate bit (+-1/8) -> p = 4 integer bit, one theta = 1 LUT node: with weight 1 and bias +1/8 the gate bit is the p = 2 message 0 or 1."""
+    from . import lut
+    if table_id is None:
+        table_id = cir.table(lut.test_vector(lut.int_outputs(lambda m: m, 4, p=2, torus_bits=torus_bits), 2, N=N, torus_bits=torus_bits))
+    return cir.lut(table_id, [w], weights=(1,), bias=1 << 29)[0]
+
+
+def to_gate_bit(cir, w, table_id=None, N=1024, torus_bits=32):
+    """p = 4 integer bit -> gate bit (+-1/8 on Torus32; the 3-gen gates read the same Torus32 records), one theta = 1 LUT node."""
+    from . import lut
+    if table_id is None:
+        table_id = cir.table(lut.test_vector(lut.bool_outputs(lambda m: m & 1, 4, torus_bits=torus_bits), 4, N=N, torus_bits=torus_bits))
+    return cir.lut(table_id, [w])[0]
+
+
+def _tables(ck, cir):
+    return np.stack([np.asarray(t, ck._tv_dtype).reshape(ck.params.N) for t in cir.tables])
+
+
 def simulate(cir, input_bits):
     """Plaintext evaluation of the DAG (wiring check): bool[n_inputs] -> bool[n_wires]."""
     from . import ANDNY, ANDYN, NAND, NOR, ORNY, ORYN, XNOR
@@ -444,7 +541,14 @@ def simulate_mk(cir, input_bits):
 def evaluate(ck, cir, input_records, stats=None):
     """Run the DAG on the engine.  input_records: int32[n_inputs][n+1].  Returns int32[n_wires][n+1].
     Single-key contexts use the native scheduler / executor (thfhe_dag_run: wires stay in HBM, no host round trip per level);
-    multi-key contexts go level by level through thfhe_mk_gates_mixed (evaluate_levels)."""
+    multi-key contexts go level by level through thfhe_mk_gates_mixed (evaluate_levels).  Circuits with LUT nodes run on
+    thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch."""
+    if cir.has_luts():
+        x = np.ascontiguousarray(input_records, np.int32).reshape(1, cir.n_inputs, ck.words)
+        out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir))
+        if stats is not None:
+            stats.update(cir.census(), **st)
+        return np.concatenate([x[0], out[0]])
     if hasattr(ck, "dag_run"):
         vals, st = ck.dag_run(input_records, np.array(cir.gates, np.int32).reshape(-1, 4))
         if stats is not None:
@@ -456,14 +560,17 @@ def evaluate(ck, cir, input_records, stats=None):
 def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None):
     """`instances` evaluations of one DAG side by side.  input_records: int32[instances][n_inputs][words]; out_wires: wire ids to return
     (None: every wire).  Returns int32[instances][len(out_wires) or n_wires][words].  Contexts with the native executor use
-    thfhe_dag_run_batch / thfhe_mk_dag_run_batch (wire tables stay in HBM); others are driven level by level from the host, a level's
-    call holding the gates of all instances."""
+    thfhe_dag_run_batch / thfhe_mk_dag_run_batch (wire tables stay in HBM), circuits with LUT nodes thfhe_dag_run_lut_batch /
+    thfhe_mk_dag_run_lut_batch; others are driven level by level from the host, a level's call holding the gates of all instances."""
     x = np.ascontiguousarray(input_records, np.int32)
     Q, n_in, words = x.shape
     assert n_in == cir.n_inputs
-    if hasattr(ck, "dag_run_batch"):
+    if cir.has_luts() or hasattr(ck, "dag_run_batch"):
         sel = None if out_wires is None else np.asarray(out_wires, np.int32)
-        out, st = ck.dag_run_batch(x, np.array(cir.gates, np.int32).reshape(-1, 4), sel)
+        if cir.has_luts():
+            out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir), sel)
+        else:
+            out, st = ck.dag_run_batch(x, np.array(cir.gates, np.int32).reshape(-1, 4), sel)
         if stats is not None:
             stats.update(cir.census(), **st)
         return out if out_wires is not None else np.concatenate([x, out], axis=1)
@@ -495,7 +602,8 @@ def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None):
 
 
 def evaluate_levels(ck, cir, input_records, stats=None):
-    """The same schedule driven from the host: one host-buffer call per level (works for single-key and multi-key contexts)."""
+    """The same schedule driven from the host: one host-buffer call per level (works for single-key and multi-key contexts).  LUT nodes go
+    through ck.lut_bootstrap, one call per (theta, spec) of a level: the yardstick of the native LUT-node executor."""
     from . import AND3 as _AND3
     words = ck.words
     vals = np.zeros((cir.n_wires(), words), np.int32)
@@ -510,7 +618,22 @@ def evaluate_levels(ck, cir, input_records, stats=None):
                 src = vals[gates[g][1]]
                 vals[base + g] = (0 - src.astype(np.int64)).astype(np.int32) if gates[g][0] == NOT else src
             continue
-        two = [g for g in level if gates[g][0] not in (MUX, _AND3)]
+        luts = [g for g in level if gates[g][0] == LUT]
+        if luts:
+            # LUT nodes grouped by (theta, spec): one lut_bootstrap per group, each node's table through lut_index
+            tvs = _tables(ck, cir)
+            groups = {}
+            for g in luts:
+                sp = cir.specs[cir.lut_rows[g][0]]
+                groups.setdefault((sp[3], cir.lut_rows[g][0]), []).append(g)
+            for (theta, si), G in sorted(groups.items()):
+                nin, w, bias, _ = cir.specs[si]
+                ins = [vals[[gates[g][1 + q] for g in G]] for q in range(nin)]
+                r = ck.lut_bootstrap(tvs, *ins, weights=w[:nin], bias=bias, theta=theta, lut_index=[cir.lut_rows[g][1] for g in G])
+                for j in range(theta):
+                    vals[base + np.array(G) + j] = r[:, j]
+                launches += 1
+        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT)]
         mux = [g for g in level if gates[g][0] == MUX]
         and3 = [g for g in level if gates[g][0] == _AND3]   # 3-gen three-input AND: its own gate class (thfhe_mk_gates)
         if and3:
