@@ -836,7 +836,7 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     Stage stage;
     // gate-DAG executor: wire table and index tables (grow-only, reused by every thfhe_dag_run on this context)
     DagBuffers dag;
-    size_t dag_slice = 28672;  // gates per launch of a DAG level: 14 x 2048, so that a MUX slice (2 rotations per gate) stays under the 65 535 limit of the prologue's grid
+    size_t dag_slice = 28672;  // gates per launch of a DAG level: 14 x 2048 (a MUX slice is 57 344 rotations); it sizes the staging arrays, not the prologue's grid: the runtime runs grid.y > 65 535 (66 636 rotations in one call, tests/test_gpu_large_batch.py)
 };
 
 namespace {
