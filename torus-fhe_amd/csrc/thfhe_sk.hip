@@ -806,6 +806,160 @@ __global__ __launch_bounds__(512) void sk_keyswitch_staged_kernel(KSArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// key switch on the matrix cores (ks_basebit == 2, t = 4 or 8, large batches).  The key switch is an exact integer GEMM:
+//   out[g] = (0, .., 0, b) - sum_k A[g][k] B[k],   k = (i, j, v): coordinate i < N, level j < t, digit value v < 4,
+// A one-hot (A[g][(i, j, v)] = [digit j of coordinate i of gate g == v]) and B[(i, j, v)] = KS[i][j][v - 1], with a row of zeros for v = 0.
+// Every 32-bit key word is split into four balanced signed bytes, w = sum_p beta_p 2^(8p) (mod 2^32), beta_p in [-128, 127], so B becomes four
+// int8 planes and C_p = A B_p is a v_mfma_i32_32x32x32_i8 product: |C_p| <= N t 128 = 2^20, and out = b - sum_p C_p << 8p, all mod 2^32.
+// Integer sums commute, so tiling, split-K and the atomics cannot change a bit.
+//
+// K chunks of 32 = 8 (i, j) slots x 4 values: slot s = 8 kc + 4 h + q of the chunk kc is held by the lanes of half h = lane >> 5 in the
+// fragment dword q, value v in byte v.  A and B fragments use that one convention, and an MFMA pairs element e of lane half h of A with
+// element e of the same lane half of B, so the product is the sum over the chunk whatever order the hardware gives the 32 k of a chunk.
+// Planes: [word tile wt][chunk kc][plane p][lane][4 dwords], a 1 KB B fragment per (wt, kc, p); lane r + 32 h holds word 32 wt + r.
+// ------------------------------------------------------------------------------------------------------
+typedef int32_t ks_i32x4 __attribute__((ext_vector_type(4)));
+typedef int32_t ks_i32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ uint32_t ks_balanced_byte(uint32_t w, int p) {   // beta_p of w, as a byte
+    for (int k = 0; k < p; k++) w = (w - (uint32_t)(int32_t)(int8_t)(w & 0xFFu)) >> 8;
+    return w & 0xFFu;
+}
+
+__global__ __launch_bounds__(256) void sk_ksk_planes_kernel(const int32_t *__restrict__ ksk, int row_words, int t, long kchunks, long total,
+                                                             uint32_t *__restrict__ planes) {
+    const long x = (long)blockIdx.x * 256 + threadIdx.x;   // one dword of the planes
+    if (x >= total) return;
+    const int q = (int)(x & 3), lane = (int)((x >> 2) & 63), p = (int)((x >> 8) & 3);
+    const long kc = (x >> 10) % kchunks, wt = (x >> 10) / kchunks;
+    const long s = 8 * kc + 4 * (lane >> 5) + q, i = s / t, j = s % t;
+    const int32_t *row = ksk + ((i * t + j) * 3) * row_words + 32 * wt + (lane & 31);
+    uint32_t dw = 0;
+    for (int v = 1; v < 4; v++) dw |= ks_balanced_byte((uint32_t)row[(v - 1) * row_words], p) << (8 * v);
+    planes[x] = dw;
+}
+
+struct KSMArgs {
+    const ks_i32x4 *planes;   // [wtiles][kchunks][4][64]
+    const int32_t *u;         // [jobs][N+1]
+    int32_t *out;             // [gates][n+1]
+    long gates;
+    int rot_per_gate;         // 1, or 2 for MUX: input = (0, 2^29) + u1 + u2
+    int n, t;
+    int kchunks;              // N t / 8
+    int wtiles;               // 32-word tiles of a padded row
+    int gtiles;               // 256-gate tiles
+    int nsplit;               // > 1: the chunks are cut in nsplit ranges whose partial sums meet in the zeroed output with atomics
+};
+
+// One workgroup: 256 gates (4 waves x 2 tiles of 32) x one 32-word tile (4 planes) x one chunk range.  The planes of KS_S chunks (32 KB) are
+// staged in LDS per step (double buffered through registers) and read by all four waves; each wave builds its A fragments from the digits of
+// its gates, and keeps 2 x 4 accumulators of 32 x 32 int32.
+template <int T, int ROT>   // key-switch depth: 4 or 8; rotations per gate: 1, or 2 for MUX (a.rot_per_gate)
+__global__ __launch_bounds__(256) void sk_keyswitch_mfma_kernel(KSMArgs a) {
+    static_assert(T == 4 || T == 8, "a lane half's four slots are four levels of one coordinate");
+    constexpr int S = 8;                  // chunks per stage
+    constexpr int NLD = S * 4 * 64 / 256; // 16-byte pieces per thread and stage
+    __shared__ ks_i32x4 sB[2][S * 4 * 64];
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int r = lane & 31, h = lane >> 5;
+    // workgroups are dealt round-robin over the 8 XCDs: renumber them so that the gate tiles of one (word tile, chunk range) share an XCD's L2
+    long L = blockIdx.x;
+    const long nblk = gridDim.x;
+    if (nblk % 8 == 0) L = (L % 8) * (nblk / 8) + L / 8;
+    const int gt = (int)(L % a.gtiles), wt = (int)(L / a.gtiles % a.wtiles), sp = (int)(L / a.gtiles / a.wtiles);
+    const int kper = a.kchunks / a.nsplit, kc0 = sp * kper, NS = kper / S;
+    const ks_i32x4 *src = a.planes + ((size_t)wt * a.kchunks + kc0) * 256;
+    const uint32_t prec_offset = 1u << (32 - (1 + 2 * T));
+    // the lane's A rows: gates g0 + 32 m + r
+    const long g0 = (long)gt * 256 + wave * 64;
+    // (rows past the batch read the last gate's digits and store nothing: no branch around the loads, whose waits would serialise them)
+    const int32_t *urow[2];
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+        const long g = g0 + 32 * m + r;
+        urow[m] = a.u + (size_t)(g < a.gates ? g : a.gates - 1) * ROT * 1025;
+    }
+    // chunk kc: the lane's four slots 8 kc + 4 h + q are levels j0 .. j0 + 3 of one coordinate (t is a multiple of 4)
+    auto coord = [&](int kc) { return T == 8 ? kc : 2 * kc + h; };
+    const int j0 = T == 8 ? 4 * h : 0;
+    ks_i32x4 pre[NLD];
+    uint32_t uw[2][S], un[2][S];
+    auto load = [&](int st) {
+        const ks_i32x4 *p_ = src + (size_t)st * (S * 256) + tid;
+#pragma unroll
+        for (int k = 0; k < NLD; k++) pre[k] = p_[256 * k];
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+            for (int c = 0; c < S; c++) {
+                const int i = coord(kc0 + st * S + c);
+                un[m][c] = (uint32_t)urow[m][i];
+                if (ROT == 2) un[m][c] += (uint32_t)urow[m][1025 + i];
+            }
+    };
+    auto store = [&](int buf) {
+#pragma unroll
+        for (int k = 0; k < NLD; k++) sB[buf][tid + 256 * k] = pre[k];
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+            for (int c = 0; c < S; c++) uw[m][c] = un[m][c] + prec_offset;   // (here, not in load(): the add would wait for the loads)
+    };
+    load(0);
+    store(0);
+    __syncthreads();
+    ks_i32x16 acc[2][4];
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int p = 0; p < 4; p++) acc[m][p] = ks_i32x16{0};
+    for (int st = 0; st < NS; st++) {
+        if (st + 1 < NS) load(st + 1);
+        const ks_i32x4 *b = sB[st & 1] + lane;
+        ks_i32x4 bf[2][4];   // the B fragments of chunk c + 1 are read while chunk c's MFMAs run
+#pragma unroll
+        for (int p = 0; p < 4; p++) bf[0][p] = b[p * 64];
+#pragma unroll
+        for (int c = 0; c < S; c++) {
+            if (c + 1 < S)
+#pragma unroll
+                for (int p = 0; p < 4; p++) bf[(c + 1) & 1][p] = b[((c + 1) * 4 + p) * 64];
+            ks_i32x4 af[2];
+#pragma unroll
+            for (int m = 0; m < 2; m++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) af[m][q] = (int32_t)(1u << (8 * ((uw[m][c] >> (30 - 2 * (j0 + q))) & 3u)));   // digit 0: the zero row
+#pragma unroll
+            for (int m = 0; m < 2; m++)
+#pragma unroll
+                for (int p = 0; p < 4; p++) acc[m][p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[m], bf[c & 1][p], acc[m][p], 0, 0, 0);
+        }
+        if (st + 1 < NS) store((st + 1) & 1);
+        __syncthreads();
+    }
+    // C/D: lane r + 32 h, register e holds row (e & 3) + 8 (e >> 2) + 4 h, column r
+    const int col = 32 * wt + r;
+    if (col > a.n) return;
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const long g = g0 + 32 * m + (e & 3) + 8 * (e >> 2) + 4 * h;
+            if (g >= a.gates) continue;
+            uint32_t v = 0u - ((uint32_t)acc[m][0][e] + ((uint32_t)acc[m][1][e] << 8) + ((uint32_t)acc[m][2][e] << 16) + ((uint32_t)acc[m][3][e] << 24));
+            if (col == a.n && sp == 0) {
+                const int32_t *u1 = a.u + (size_t)g * ROT * 1025;
+                v += (uint32_t)u1[1024];
+                if (ROT == 2) v += (uint32_t)u1[1025 + 1024] + (1u << 29);
+            }
+            unsigned int *o = reinterpret_cast<unsigned int *>(a.out) + (size_t)g * (a.n + 1) + col;
+            if (a.nsplit == 1) *o = v;
+            else atomicAdd(o, v);
+        }
+}
+
 inline int ks_words_per_lane(int n) { return (((n + 1 + 63) / 64) + 1) & ~1; }
 
 __global__ __launch_bounds__(256) void sk_linear_kernel(const int32_t *__restrict__ in0, int32_t *__restrict__ out, size_t words, int negate) {
@@ -822,7 +976,9 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     thfhe_params p;
     DevBuf d_bk;              // spectral key
     DevBuf d_ksk;             // padded rows
+    DevBuf d_ksk_planes;      // the padded rows as four balanced int8 planes in MFMA fragment order (sk_keyswitch_mfma_kernel; empty: shape not taken)
     int ks_w = 0;             // words per lane of a padded KSK row
+    long ks_mfma_min_gates = 512;    // batches of at least this many gates use sk_keyswitch_mfma_kernel where its shape allows
     long ks_multi_min_gates = 1024;  // batches of at least this many gates use sk_keyswitch_multi_kernel (rows shared by the gates of a workgroup)
     long ks_staged_min_gates = 192;  // (measured: 128 gates 0.146 ms one gate per workgroup / 0.184 staged, 256 gates 0.381 / 0.201)
     // ... and, where its shape allows, batches from this size on sk_keyswitch_staged_kernel (rows staged in LDS, the digit selects an address)
@@ -957,7 +1113,32 @@ int enqueue_lut_rotations(thfhe_ctx *c, const thfhe_lut_spec &sp, const int32_t 
     return THFHE_OK;
 }
 
+// the shapes sk_keyswitch_mfma_kernel takes: 2-bit digits, t = 4 or 8 (four levels of one coordinate per lane half), N = 1024
+inline bool ks_mfma_shape(const thfhe_params &p) { return p.ks_basebit == 2 && (p.ks_t == 4 || p.ks_t == 8) && p.N == 1024; }
+
 int enqueue_keyswitch(thfhe_ctx *c, const int32_t *d_u, int32_t *d_out, size_t gates, int rot_per_gate, bool timed) {
+    if (c->d_ksk_planes.bytes() && (long)gates >= c->ks_mfma_min_gates) {
+        // the key switch as an int8 GEMM on the matrix cores (sk_keyswitch_mfma_kernel): 256-gate x 32-word tiles; the chunks are cut into
+        // nsplit ranges until the grid has at least 1 024 workgroups (4 096 gates, n = 630: 16 x 20 x 4).
+        KSMArgs k{c->d_ksk_planes.as<ks_i32x4>(), d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, c->p.N * c->p.ks_t / 8, 2 * c->ks_w,
+                  (int)((gates + 255) / 256), 1};
+        while (k.nsplit < 8 && (long)k.gtiles * k.wtiles * k.nsplit < 1024) k.nsplit *= 2;
+        if (k.nsplit > 1) THFHE_HIP(hipMemsetAsync(d_out, 0, gates * (size_t)(c->p.n + 1) * sizeof(int32_t), c->stream));
+        const dim3 grid((unsigned)((long)k.gtiles * k.wtiles * k.nsplit)), block(256);
+        if (c->p.ks_t == 8) {
+            if (rot_per_gate == 1) hipLaunchKernelGGL((sk_keyswitch_mfma_kernel<8, 1>), grid, block, 0, c->stream, k);
+            else hipLaunchKernelGGL((sk_keyswitch_mfma_kernel<8, 2>), grid, block, 0, c->stream, k);
+        } else {
+            if (rot_per_gate == 1) hipLaunchKernelGGL((sk_keyswitch_mfma_kernel<4, 1>), grid, block, 0, c->stream, k);
+            else hipLaunchKernelGGL((sk_keyswitch_mfma_kernel<4, 2>), grid, block, 0, c->stream, k);
+        }
+        if (timed && c->profiling) {
+            THFHE_HIP(hipEventRecord(c->ev[3], c->stream));
+            c->ev_valid = true;
+        }
+        THFHE_HIP(hipGetLastError());
+        return THFHE_OK;
+    }
     const bool staged_shape = c->p.ks_basebit == 2 && c->p.ks_t <= 8 &&
                               (((c->ks_w == 8 || c->ks_w == 10) && c->p.ks_t % 4 == 0) || (c->ks_w == 18 && c->p.ks_t % 2 == 0));
     if (staged_shape && (long)gates >= c->ks_staged_min_gates) {
@@ -1118,6 +1299,14 @@ int thfhe_ctx_create(const thfhe_params *p, const int32_t *bk_coeff, const int32
     THFHE_TRY(c->d_ksk.grow((size_t)rows * row_words * sizeof(int32_t)));
     hipLaunchKernelGGL(sk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, raw.as<int32_t>(), rows, p->n, row_words, c->d_ksk.as<int32_t>());
     THFHE_HIP(hipGetLastError());
+    if (ks_mfma_shape(*p)) {
+        // ... and as int8 planes for the matrix-core kernel: 4 bytes per (word, coordinate, level, digit value): 80 MiB at n = 630, t = 8
+        const long kchunks = (long)p->N * p->ks_t / 8, total = (long)(row_words / 32) * kchunks * 4 * 64 * 4;
+        THFHE_TRY(c->d_ksk_planes.grow((size_t)total * sizeof(uint32_t)));
+        hipLaunchKernelGGL(sk_ksk_planes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->d_ksk.as<int32_t>(), row_words,
+                           p->ks_t, kchunks, total, c->d_ksk_planes.as<uint32_t>());
+        THFHE_HIP(hipGetLastError());
+    }
     THFHE_HIP(hipStreamSynchronize(c->stream));
     *out = c.release();
     return THFHE_OK;
