@@ -58,7 +58,7 @@ def test_ccs_2party_full_size_like_runtests(O):
     dev = np.abs(np.abs(K.phases(out) / 2.0**32) - 0.125)
     assert dev.max() < 0.125 and dev.mean() < 0.04     # the 2-party CCS set is noisy by design (about 0.03 rms after one bootstrap)
     assert np.array_equal(out[:2], orc.gates(O.NAND, c1[:2], c2[:2]))
-    # 200 gates: the key switch (ks 8/2, one mask per party) goes through the staged kernel; a ragged last workgroup
+    # 200 gates: the key switch (ks 8/2, one mask per party) goes through ks_staged_kernel; a ragged last workgroup
     B2 = 200
     m1, m2 = rng.integers(0, 2, B2), rng.integers(0, 2, B2)
     c1, c2 = K.encrypt_bits(m1, s["lwe"], 43), K.encrypt_bits(m2, s["lwe"], 44)

@@ -1,6 +1,7 @@
 """Parameter sets at the reference's FULL size on the MI355X (pytest -m gpu), through the checks of tests/full_size_checks.py: MK32 (32 parties,
 n = 620, N = 2048: the three-part-digit pair kernel behind the MK32 ... MK128 numbers) as gates and as a lookup table, KMS2 at n = 560, CCS4.
-Every check returns its record; the asserts are on the words compared with the CPU oracle and on the decryptions."""
+Every check returns its record; the asserts are on the words compared with the CPU oracle and on the decryptions.  The key switches
+(thfhe_keyswitch.h) run ks_staged_kernel from 192 samples on (the 512 MK32 gates) and ks_plain_kernel below."""
 import pytest
 
 import full_size_checks as F

@@ -6,8 +6,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-MFMA_MIN_GATES = 512   # thfhe_ctx::ks_mfma_min_gates
-SMALL = 200            # batches of this size stay on the staged kernel
+MFMA_MIN_GATES = 512   # kKsMfmaMinSamples (thfhe_keyswitch.h)
+SMALL = 200            # batches of this size stay on ks_staged_kernel
 
 
 def _inputs(p, batch, seed):

@@ -79,8 +79,8 @@ def test_kms2_truth_table_larger_n(O):
 
 
 def test_kms2_keyswitch_full_n_both_kernels(O):
-    # mk_keyswitch (mk_internals.jl:714-728) at the reference's n = 560 (640-word rows): 100 samples one workgroup per (sample, party), 260 through
-    # the staged kernel; P N + 1 = 4097-word extracted samples with one mask per party
+    # mk_keyswitch (mk_internals.jl:714-728) at the reference's n = 560 (640-word rows): 100 samples through ks_plain_kernel (one workgroup per
+    # sample, party and coordinate range), 260 through ks_staged_kernel; P N + 1 = 4097-word extracted samples with one mask per party
     p, K, orc, ck = setup(O, "KMS2", 560, seed=10)
     rng = np.random.default_rng(14)
     for count in (100, 260):

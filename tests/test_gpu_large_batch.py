@@ -3,7 +3,8 @@ ring kernel plus 1 100 = 1 024 on the four-wave ring and 76 on the cooperative k
 prologues launch more than 65 535 grid rows (grid.y = jobs), and the LUT prologues, which clamp grid.y to 65 535, take a second pass of their
 stride loop.  Job 65 536 is the first past that line and the first of the remainder.  Every output word must equal the same engine on the same
 records cut into calls of 4 096 gates (the size the rest of the suite compares with the oracle), and the rows around each boundary must equal
-the CPU oracle word for word.  Inputs are random records: the oracle evaluates any record, and so does the engine."""
+the CPU oracle word for word.  Inputs are random records: the oracle evaluates any record, and so does the engine.  The key switches
+(thfhe_keyswitch.h) run sk_keyswitch_mfma_kernel on the single key and ks_staged_kernel on the multi key, in the one call and in the chunks."""
 import numpy as np
 import pytest
 

@@ -61,8 +61,8 @@ def test_multi_key_shapes(O, shape, monkeypatch):
 
 @pytest.mark.parametrize("name", ["SK-80", "SK-128", "SK-lib"])
 def test_multi_gate_keyswitch_kernel(O, name):
-    # sk_keyswitch_multi_kernel (batches >= 1024 gates, basebit 2; 8 / 4 gates per workgroup share every row load, coordinate range
-    # cut in four, atomics): every output word against the oracle for a ragged batch, and the MUX combine (two rotations per gate)
+    # sk_keyswitch_mfma_kernel (from 512 gates on; t = 8, 2-bit digits: every named single-key set) on a ragged batch of 1 033 gates (the
+    # last 256-gate tile holds 9) and on 1 024 MUX gates (two rotations per gate): sampled output words against the oracle
     import thfhe
     p = O.make_params(name)
     s = O.SIGMAS[name]

@@ -193,9 +193,10 @@ def _check_keyswitch(O, ck, orc, p, batch, seed):
 
 
 def test_every_keyswitch_kernel_bit_exact(O, sk128, gpu128):
-    """keyswitch (J/keyswitch.jl:45-80) through all three kernels: one gate per workgroup (< 192 gates), rows staged in LDS for 32 gates with the
-    digit selecting an address (from 192 gates on; 16 coordinate ranges, 8 from 2 048 gates on), also with a ragged last workgroup, and the
-    two-rotation input of the MUX epilogue (J/gates.jl:172-176) at a staged batch size."""
+    """keyswitch (J/keyswitch.jl:45-80) through all three kernels of thfhe_keyswitch.h: ks_plain_kernel, one gate per workgroup (1 and 191
+    gates), ks_staged_kernel, rows staged in LDS for 32 gates with the digit selecting an address (192 and 223 gates: 16 coordinate ranges, a
+    ragged last workgroup), and sk_keyswitch_mfma_kernel (1 000 and 2 051 gates); then the two-rotation input of the MUX epilogue
+    (J/gates.jl:172-176) through ks_staged_kernel (200 gates)."""
     import thfhe
     p, K, orc = sk128
     for batch, seed in ((1, 1), (191, 2), (192, 3), (223, 4), (1000, 5), (2051, 6)):
@@ -211,8 +212,9 @@ def test_every_keyswitch_kernel_bit_exact(O, sk128, gpu128):
 
 @pytest.mark.parametrize("name,kw", [("SK-80", {}), ("SK-128", dict(ks_t=4)), ("SK-128", dict(ks_t=6)), ("SK-lib", {})])
 def test_keyswitch_shapes(O, name, kw):
-    """the staged kernel's other row length (n = 500: 8 words per lane), a key-switch depth of 4, and the shapes it hands to the other kernels
-    (t = 6: not a multiple of 4; n = 1024: 18 words per lane)"""
+    """37 gates through ks_plain_kernel and 230 through ks_staged_kernel at its other row lengths (n = 500: 512 words; n = 1024: 1 152 words,
+    two (i, j) per stage), a key-switch depth of 4 and one of 6 (stages straddle coordinates); 1 030 gates through sk_keyswitch_mfma_kernel,
+    except t = 6, which the matrix cores do not take: ks_staged_kernel again"""
     import thfhe
     p = O.make_params(name, **kw)
     s = O.SIGMAS[name]
@@ -221,6 +223,27 @@ def test_keyswitch_shapes(O, name, kw):
     ck = thfhe.CloudKey(thfhe.make_params(name, **kw), K.bk, K.ksk, device=0)
     for batch, seed in ((37, 11), (230, 12), (1030, 13)):
         _check_keyswitch(O, ck, orc, p, batch, seed)
+    ck.close()
+
+
+def test_staged_keyswitch_straddling_stages_and_mux(O):
+    """ks_staged_kernel with stages that straddle a coordinate (SK-128 with t = 6: four (i, j) per stage) and the two-rotation input of MUX
+    ((0, 2^29) + u1 + u2, J/gates.jl:172-176): a raw key switch and MUX gates at 230 (16 coordinate ranges) and 1 030 gates, against the oracle"""
+    import thfhe
+    p = O.make_params("SK-128", ks_t=6)
+    s = O.SIGMAS["SK-128"]
+    K = O.SKKeys(p, 85, s["bk"], s["ks"])
+    orc = O.Oracle(p, K.bk, K.ksk)
+    ck = thfhe.CloudKey(thfhe.make_params("SK-128", ks_t=6), K.bk, K.ksk, device=0)
+    rng = np.random.default_rng(16)
+    for batch, seed in ((230, 14), (1030, 15)):
+        _check_keyswitch(O, ck, orc, p, batch, seed)
+        bits = rng.integers(0, 2, (3, batch))
+        cx, cy, cz = (K.encrypt_bits(bits[q], s["lwe"], 600 + 3 * seed + q) for q in range(3))
+        got = ck.gates(O.MUX, cx, cy, cz)
+        assert np.array_equal(K.decrypt_bits(got), np.where(bits[0] == 1, bits[1], bits[2]).astype(bool))
+        pick = [0, 1, 31, 32, batch // 2, batch - 2, batch - 1]
+        assert np.array_equal(got[pick], orc.gates(O.MUX, cx[pick], cy[pick], cz[pick])), batch
     ck.close()
 
 

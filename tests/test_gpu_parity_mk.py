@@ -17,8 +17,9 @@ def mk2gpu(O):
 
 
 def check_mk_keyswitch(ck, orc, p, counts, seed):
-    """mk_keyswitch_3gen (J/mk_internals.jl:730-744) of random extracted samples through thfhe_mk_keyswitch_dev: below 192 samples one workgroup
-    per (sample, party), from 192 on the staged kernel (rows in LDS, the digit selects an address); sampled rows against the oracle."""
+    """mk_keyswitch_3gen (J/mk_internals.jl:730-744) of random extracted samples through thfhe_mk_keyswitch_dev: below 192 samples
+    ks_plain_kernel (one workgroup per sample, party and coordinate range), from 192 on ks_staged_kernel (rows in LDS, the digit selects an
+    address); sampled rows against the oracle."""
     import thfhe
     rng = np.random.default_rng(seed)
     for count in counts:

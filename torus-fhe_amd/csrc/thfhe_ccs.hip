@@ -324,8 +324,8 @@ __global__ __launch_bounds__(512, 2) void ccs_blind_rotate_wide_kernel(CCSArgs a
 struct THFHE_INTERNAL thfhe_ccs_ctx : DevCtx {
     thfhe_params p;
     DevBuf d_bk, d_pk, d_crs;
-    DevBuf d_ksk;
-    int row_words = 0, w_pad = 0, words = 0;
+    KsKey ksk;
+    int w_pad = 0, words = 0;
     DevBuf d_bara, d_barb, d_u, d_in[2], d_out;
     DevBuf d_v;   // wide shape (more than 8 parties or 8 levels): the v polynomials of a step, int32[jobs][P+1][1024]
     bool wide = false;
@@ -360,11 +360,9 @@ int ccs_run(thfhe_ccs_ctx *c, MKLin L, const int32_t *in0, const int32_t *in1, i
     CCSArgs a{c->d_bk.as<cplx>(), c->d_pk.as<cplx>(), c->d_crs.as<cplx>(), c->d_tw.as<cplx>(), d_bara, d_barb, d_u, (long)count, c->p.parties, c->p.n, c->p.l, c->w_pad, c->p.Bgbit, mu};
     if (c->wide) hipLaunchKernelGGL(ccs_blind_rotate_wide_kernel, dim3((unsigned)count), dim3(512), 0, c->stream, a, c->d_v.as<int32_t>());
     else hipLaunchKernelGGL(ccs_blind_rotate_kernel, dim3((unsigned)count), dim3(512), 0, c->stream, a);
-    MKKSArgs k{c->d_ksk.as<int32_t>(), d_u, d_out, (long)count, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, 1024, c->p.parties * 1024 + 1, 1024};
-    const int nsplit = count * c->p.parties <= 64 ? 16 : (count * c->p.parties <= 256 ? 4 : 1);
-    THFHE_HIP(hipMemsetAsync(d_out, 0, bytes, c->stream));
-    mk_launch_keyswitch(k, nsplit, c->stream);
-    THFHE_HIP(hipGetLastError());
+    KsArgs k = c->ksk.args(d_u, d_out, (long)count);
+    k.u_rec = c->p.parties * 1024 + 1, k.u_pstride = 1024;   // one mask per party
+    THFHE_TRY(ks_enqueue(c->ksk, k, count * c->p.parties <= 64 ? 16 : (count * c->p.parties <= 256 ? 4 : 1), c->stream));
     THFHE_HIP(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
@@ -393,7 +391,6 @@ int thfhe_ccs_ctx_create(const thfhe_params *p, const int32_t *bk, const int32_t
     c->wide = p->parties > kCcsMaxParties || p->l > 8;   // the 16-party shape: ccs_blind_rotate_wide_kernel
     c->words = p->parties * p->n;
     c->w_pad = (c->words + 3) & ~3;
-    c->row_words = 128 * ((p->n + 1 + 127) / 128);
     THFHE_TRY(c->upload_twiddles(1024));
     struct Tab { const int32_t *src; long npolys; DevBuf *dst; };
     const Tab tabs[3] = {{bk, (long)p->parties * p->n * 3 * p->l, &c->d_bk}, {pk, (long)p->parties * p->l, &c->d_pk}, {crs, (long)p->l, &c->d_crs}};
@@ -405,14 +402,7 @@ int thfhe_ccs_ctx_create(const thfhe_params *p, const int32_t *bk, const int32_t
         THFHE_TRY((launch_torus_transform<1024, 32>(c->stream, coeff.as<int32_t>(), t.npolys, c->d_tw.as<cplx>(), t.dst->as<cplx>())));
         THFHE_HIP(hipStreamSynchronize(c->stream));
     }
-    const long rows = (long)p->parties * 1024 * p->ks_t * ((1 << p->ks_basebit) - 1);
-    DevBuf raw;  // upload staging
-    THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));
-    THFHE_HIP(hipMemcpyAsync(raw.as<int32_t>(), ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_TRY(c->d_ksk.grow((size_t)rows * c->row_words * sizeof(int32_t)));
-    hipLaunchKernelGGL(mk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, raw.as<int32_t>(), rows, p->n, c->row_words, c->d_ksk.as<int32_t>());
-    THFHE_HIP(hipGetLastError());
-    THFHE_HIP(hipStreamSynchronize(c->stream));
+    THFHE_TRY(c->ksk.upload(ksk, p->parties, 1024, p->n, p->ks_t, p->ks_basebit, false, c->stream));
     *out = c.release();
     return THFHE_OK;
 }

@@ -125,8 +125,8 @@ struct THFHE_INTERNAL thfhe_kms_ctx : DevCtx {
     DevBuf park;                 // two jobs per workgroup: partial spectra between row-part batches (thfhe_rot2k.h)
     long pair_threshold = 256;   // launches of more TLev / RLWE rotations than this (one per CU) run two jobs per workgroup
     DevBuf d_bk;                 // [party][j][row part][o][h][half][512]
-    DevBuf d_ksk;
-    int parts = 1, lo_bits = 1, row_words = 0;
+    KsKey ksk;
+    int parts = 1, lo_bits = 1;
     size_t party_stride = 0;    // complex elements per party in d_bk
     DevBuf d_buf[3];
     // relinearisation keys as limb spectra: [party][d | f0 | f1][l_uni], then pk [P][l_uni], then crs [l_uni]   (thfhe_kms_set_relin_keys)
@@ -143,6 +143,15 @@ struct THFHE_INTERNAL thfhe_kms_ctx : DevCtx {
     std::map<uint64_t, DevTab> tabs;
     size_t tab_bytes = 0;
 };
+
+namespace {
+// the key switch of `count` extracted samples of P N + 1 words (one mask per party) into d_out
+int kms_keyswitch(thfhe_kms_ctx *c, const int32_t *d_u, int32_t *d_out, size_t count) {
+    KsArgs k = c->ksk.args(d_u, d_out, (long)count);
+    k.u_rec = c->p.parties * c->p.N + 1, k.u_pstride = c->p.N;
+    return ks_enqueue(c->ksk, k, count <= 64 ? 8 : 2, c->stream);
+}
+}  // namespace
 
 extern "C" {
 
@@ -166,7 +175,6 @@ int thfhe_kms_ctx_create(const thfhe_kms_params *p, const int64_t *gsw, const in
     auto sum_bound = [&](int parts, int bits) { return (double)(2 * p->l_gsw * parts) * N * (double)(1 << (bits - 1)) * 32768.0; };
     c->lo_bits = (p->bg_gsw + 1) / 2;
     c->parts = (p->bg_gsw > 10 || sum_bound(1, p->bg_gsw) > 137438953472.0) ? 2 : 1;
-    c->row_words = 128 * ((p->n + 1 + 127) / 128);
     const int RP = 2 * p->l_gsw * c->parts;
     const int part_bits = c->parts == 2 ? c->lo_bits : p->bg_gsw;
     if (sum_bound(c->parts, part_bits) > 137438953472.0 /* 2^37 */)
@@ -178,14 +186,7 @@ int thfhe_kms_ctx_create(const thfhe_kms_params *p, const int64_t *gsw, const in
     THFHE_TRY(stage_party_keys<N>(*c, c->d_bk, p->parties, p->n, 2 * p->l_gsw, c->parts, c->lo_bits, [&](int q, int j, int r, int col) {
         return gsw + ((((size_t)q * p->n + j) * 2 * p->l_gsw + r) * 2 + col) * N;
     }));
-    DevBuf raw;  // upload staging
-    const long rows = (long)p->parties * N * p->ks_t * ((1 << p->ks_basebit) - 1);
-    THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));
-    THFHE_HIP(hipMemcpyAsync(raw.as<int32_t>(), ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_TRY(c->d_ksk.grow((size_t)rows * c->row_words * sizeof(int32_t)));
-    hipLaunchKernelGGL(mk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, raw.as<int32_t>(), rows, p->n, c->row_words, c->d_ksk.as<int32_t>());
-    THFHE_HIP(hipGetLastError());
-    THFHE_HIP(hipStreamSynchronize(c->stream));
+    THFHE_TRY(c->ksk.upload(ksk, p->parties, N, p->n, p->ks_t, p->ks_basebit, false, c->stream));
     *out = c.release();
     return THFHE_OK;
 }
@@ -247,11 +248,7 @@ int thfhe_kms_keyswitch(thfhe_kms_ctx *c, const int32_t *u, int32_t *out, size_t
     if (!rc) rc = c->d_buf[2].grow(out_words * sizeof(int32_t));
     if (rc) return rc;
     THFHE_HIP(hipMemcpyAsync(c->d_buf[1].as<void>(), u, in_words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemsetAsync(c->d_buf[2].as<void>(), 0, out_words * sizeof(int32_t), c->stream));
-    MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_buf[1].as<int32_t>(), c->d_buf[2].as<int32_t>(), (long)count, n, c->p.ks_t, c->p.ks_basebit, P, c->row_words, N, P * N + 1, N};
-    const int nsplit = count <= 64 ? 8 : 2;
-    mk_launch_keyswitch(k, nsplit, c->stream);
-    THFHE_HIP(hipGetLastError());
+    THFHE_TRY(kms_keyswitch(c, c->d_buf[1].as<int32_t>(), c->d_buf[2].as<int32_t>(), count));
     THFHE_HIP(hipMemcpyAsync(out, c->d_buf[2].as<void>(), out_words * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
@@ -464,12 +461,7 @@ int kms_bootstrap_body(thfhe_kms_ctx *c, KmsTables &tabs, int32_t cb, int32_t cx
     THFHE_HIP(hipGetLastError());
     if (u_out) THFHE_HIP(hipMemcpyAsync(u_out, c->d_w[K::W_U].as<void>(), G * uw * 4, hipMemcpyDeviceToHost, c->stream));
     if (out) {
-        THFHE_HIP(hipMemsetAsync(c->d_w[K::W_OUT].as<void>(), 0, G * words * 4, c->stream));
-        MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_w[K::W_U].as<int32_t>(), c->d_w[K::W_OUT].as<int32_t>(), (long)G, n, c->p.ks_t, c->p.ks_basebit, P, c->row_words, (int)N,
-                   (int)uw, (int)N};
-        const int nsplit = G <= 64 ? 8 : 2;
-        mk_launch_keyswitch(k, nsplit, c->stream);
-        THFHE_HIP(hipGetLastError());
+        THFHE_TRY(kms_keyswitch(c, c->d_w[K::W_U].as<int32_t>(), c->d_w[K::W_OUT].as<int32_t>(), G));
         THFHE_HIP(hipMemcpyAsync(out, c->d_w[K::W_OUT].as<void>(), G * words * 4, hipMemcpyDeviceToHost, c->stream));
     }
     return kms_finish(c);
@@ -606,7 +598,7 @@ int thfhe_kms_finish_dev(thfhe_kms_ctx *c, int op, const int32_t *d_x, const int
     THFHE_HIP(hipSetDevice(c->device));
     KmsTables tabs;
     const int P = c->p.parties, n = c->p.n, lv = c->p.l_lev;
-    const size_t G = count, N = 2048, words = (size_t)P * n + 1, uw = (size_t)P * N + 1;
+    const size_t G = count, N = 2048, uw = (size_t)P * N + 1;
     auto body = [&]() -> int {
         int r = c->d_w[K::W_BARA].grow((size_t)P * G * n * 4);
         if (!r) r = c->d_w[K::W_ACCUM].grow(G * (P + 1) * N * 8);
@@ -623,11 +615,7 @@ int thfhe_kms_finish_dev(thfhe_kms_ctx *c, int op, const int32_t *d_x, const int
         }
         hipLaunchKernelGGL(kms_extract_kernel, dim3((unsigned)G, (unsigned)(P + 1)), dim3(256), 0, c->stream, (const int64_t *)d_accum, P, c->d_w[K::W_U].as<int32_t>());
         THFHE_HIP(hipGetLastError());
-        THFHE_HIP(hipMemsetAsync(d_out, 0, G * words * 4, c->stream));
-        MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_w[K::W_U].as<int32_t>(), d_out, (long)G, n, c->p.ks_t, c->p.ks_basebit, P, c->row_words, (int)N, (int)uw, (int)N};
-        const int nsplit = G <= 64 ? 8 : 2;
-        mk_launch_keyswitch(k, nsplit, c->stream);
-        THFHE_HIP(hipGetLastError());
+        THFHE_TRY(kms_keyswitch(c, c->d_w[K::W_U].as<int32_t>(), d_out, G));
         return kms_finish(c);
     };
     rc = body();

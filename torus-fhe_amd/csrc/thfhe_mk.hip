@@ -13,8 +13,8 @@
 //   mk_blind_rotate_coop_kernel / _pair_kernel   one 512-thread workgroup per gate / per two gates: the eight (output polynomial, limb) spectra on
 //                             eight waves; _coop2k / _pair2k on the ring of degree 2048 (two twisted half transforms per polynomial);
 //                             thfhe_rot2k.h (any number of digit row parts, N = 2048) and thfhe_rot4k.h (N = 4096) for the large-party sets
-//   mk_keyswitch_kernel / mk_keyswitch_staged_kernel (thfhe_mk_shared.h)   P key switches of the extracted sample + the cross-party combine
-//                             of b: one workgroup per (sample, party, range), or from 192 samples on the rows staged in LDS for 32 samples
+//   ks_plain_kernel / ks_staged_kernel (thfhe_keyswitch.h)   P key switches of the extracted sample + the cross-party combine of b:
+//                             one workgroup per (sample, party, range), or from 192 samples on the rows staged in LDS for 32 samples
 //   mk_lut_prologue_kernel / mk_lut_acc_init_kernel / mk_extract_at_kernel   programmable bootstrap (thfhe_mk_lut_bootstrap): weighted
 //                             sum + mod-switch to multiples of theta, accumulator X^{-barb} * tv in global memory, the rotation kernels above
 //                             through acc_in / acc_out, extraction of theta coefficients; behind dag_lut_prologue_kernel (thfhe_dag.h) they
@@ -944,8 +944,9 @@ __global__ __launch_bounds__(256) void mk_mux_combine_kernel(const int32_t *__re
 
 struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     thfhe_params p;
-    DevBuf d_bk, d_ksk;
-    int row_words = 0, w_pad = 0, words = 0, log2_2n = 11;
+    DevBuf d_bk;
+    KsKey ksk;
+    int w_pad = 0, words = 0, log2_2n = 11;
     DevBuf park;                 // batched N = 2048 rotation, two jobs per workgroup: partial spectra between row-part batches (thfhe_rot2k.h)
     long pair_threshold = 256;  // batches of more rotations than this run two gates per workgroup (mk_blind_rotate_pair_kernel)
     bool batched = false;       // N = 2048 with l x digit parts > 3: thfhe_rot2k.h (row parts through the LDS in batches), key table in its layout
@@ -972,6 +973,14 @@ __global__ void mk_extract_kernel(const int64_t *__restrict__ acc, int32_t *__re
 int mk_launch_rotation(thfhe_mk_ctx *c, const MKBRArgs &a);
 
 // bootstrap (prologue + blind rotate + key switch) of `jobs` = gates * rot jobs; results to d_dst[jobs][P*n+1]
+// the key switch of `count` extracted records of N + 1 words (one mask for all parties) into d_out; the plain kernel's coordinate ranges
+// fill the chip at small batch sizes, and a block holds <= 2048 mask words
+int mk_keyswitch(thfhe_mk_ctx *c, const int32_t *d_u, int32_t *d_out, size_t count) {
+    const size_t s = count * c->p.parties;
+    const int nsplit = s <= 64 ? 16 : (s <= 256 ? 4 : (c->p.N > 2048 ? 2 : 1));
+    return ks_enqueue(c->ksk, c->ksk.args(d_u, d_out, (long)count), nsplit, c->stream);
+}
+
 int mk_enqueue_bootstraps(thfhe_mk_ctx *c, const int32_t *d0, const int32_t *d1, const int32_t *d2, MKLin L0, MKLin L1, int rot,
                           size_t gates, int64_t mu, int32_t *d_dst, const int32_t *d_ops = nullptr) {
     const size_t jobs = gates * rot;
@@ -985,15 +994,11 @@ int mk_enqueue_bootstraps(thfhe_mk_ctx *c, const int32_t *d0, const int32_t *d1,
         if (rc) return rc;
     }
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
-    MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_u.as<int32_t>(), d_dst, (long)jobs, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, c->p.N, c->p.N + 1, 0};
-    const int nsplit = jobs * c->p.parties <= 64 ? 16 : (jobs * c->p.parties <= 256 ? 4 : (c->p.N > 2048 ? 2 : 1));  // fill the chip at small batch sizes; a block holds <= 2048 mask words
-    THFHE_HIP(hipMemsetAsync(d_dst, 0, jobs * ((size_t)c->words + 1) * sizeof(int32_t), c->stream));
-    mk_launch_keyswitch(k, nsplit, c->stream);
+    THFHE_TRY(mk_keyswitch(c, c->d_u.as<int32_t>(), d_dst, jobs));
     if (c->profiling) {
         THFHE_HIP(hipEventRecord(c->ev[3], c->stream));
         c->ev_valid = true;
     }
-    THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
 
@@ -1025,12 +1030,7 @@ int mk_enqueue_lut_rotation(thfhe_mk_ctx *c, int theta, size_t count, const int6
     hipLaunchKernelGGL(mk_extract_at_kernel, dim3((unsigned)count, (unsigned)theta), dim3(256), 0, c->stream, (const int64_t *)acc, c->d_u.as<int32_t>(),
                        (long)count, N, theta);
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
-    if (d_dst) {
-        MKKSArgs k{c->d_ksk.as<int32_t>(), c->d_u.as<int32_t>(), d_dst, (long)recs, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, N, N + 1, 0};
-        const int nsplit = recs * c->p.parties <= 64 ? 16 : (recs * c->p.parties <= 256 ? 4 : (N > 2048 ? 2 : 1));   // as mk_enqueue_bootstraps
-        THFHE_HIP(hipMemsetAsync(d_dst, 0, recs * ((size_t)c->words + 1) * sizeof(int32_t), c->stream));
-        mk_launch_keyswitch(k, nsplit, c->stream);
-    }
+    if (d_dst) THFHE_TRY(mk_keyswitch(c, c->d_u.as<int32_t>(), d_dst, recs));
     if (c->profiling) {
         THFHE_HIP(hipEventRecord(c->ev[3], c->stream));
         c->ev_valid = true;
@@ -1268,7 +1268,6 @@ int thfhe_mk_ctx_create(const thfhe_params *p, const int64_t *bk_coeff, const in
     c->p = *p;
     c->words = p->parties * p->n;
     c->w_pad = (c->words + 3) & ~3;
-    c->row_words = 128 * ((p->n + 1 + 127) / 128);
     c->log2_2n = ilog2(2 * p->N);
     c->parts = parts;
     c->pw = pw;
@@ -1306,14 +1305,7 @@ int thfhe_mk_ctx_create(const thfhe_params *p, const int64_t *bk_coeff, const in
         }
         THFHE_HIP(hipStreamSynchronize(c->stream));   // before `coeff` is freed
     }
-    DevBuf raw;  // upload staging
-    const long rows = (long)p->parties * p->N * p->ks_t * ((1 << p->ks_basebit) - 1);
-    THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));
-    THFHE_HIP(hipMemcpyAsync(raw.as<int32_t>(), ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_TRY(c->d_ksk.grow((size_t)rows * c->row_words * sizeof(int32_t)));
-    hipLaunchKernelGGL(mk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, raw.as<int32_t>(), rows, p->n, c->row_words, c->d_ksk.as<int32_t>());
-    THFHE_HIP(hipGetLastError());
-    THFHE_HIP(hipStreamSynchronize(c->stream));
+    THFHE_TRY(c->ksk.upload(ksk, p->parties, p->N, p->n, p->ks_t, p->ks_basebit, false, c->stream));
     *out = c.release();
     return THFHE_OK;
 }
@@ -1495,12 +1487,7 @@ int thfhe_mk_keyswitch_dev(thfhe_mk_ctx *c, const int32_t *d_u, int32_t *d_out, 
     if (count == 0) return THFHE_OK;
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
-    MKKSArgs k{c->d_ksk.as<int32_t>(), d_u, d_out, (long)count, c->p.n, c->p.ks_t, c->p.ks_basebit, c->p.parties, c->row_words, c->p.N, c->p.N + 1, 0};
-    const int nsplit = count * c->p.parties <= 64 ? 16 : (count * c->p.parties <= 256 ? 4 : (c->p.N > 2048 ? 2 : 1));
-    THFHE_HIP(hipMemsetAsync(d_out, 0, count * ((size_t)c->words + 1) * sizeof(int32_t), c->stream));
-    mk_launch_keyswitch(k, nsplit, c->stream);
-    THFHE_HIP(hipGetLastError());
-    return THFHE_OK;
+    return mk_keyswitch(c, d_u, d_out, count);
 }
 
 int thfhe_mk_bootstrap(thfhe_mk_ctx *c, int64_t mu, const int32_t *x, int32_t *out, size_t count) {

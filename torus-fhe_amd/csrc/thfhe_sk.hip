@@ -11,9 +11,9 @@
 //   sk_blind_rotate_ring_kernel / sk_blind_rotate_coop_kernel   blind_rotate_and_extract (J/bootstrap.jl:38-65): accumulator in
 //                             LDS for all n CMuxes; throughput (8 gates per workgroup, key through an LDS-DMA ring) and latency
 //                             (one workgroup per gate) variants
-//   sk_keyswitch_kernel / sk_keyswitch_staged_kernel / sk_keyswitch_multi_kernel   keyswitch (J/keyswitch.jl:45-80) (+ the MUX combine of
-//                             J/gates.jl:172-176): one gate per workgroup (small batches); from 192 gates on the rows of a few (i, j) staged in
-//                             LDS for 32 gates, the digit selecting an address; rows in registers selected by branches for the remaining shapes
+//   ks_plain_kernel / ks_staged_kernel / sk_keyswitch_mfma_kernel   keyswitch (J/keyswitch.jl:45-80) (+ the MUX combine of J/gates.jl:172-176),
+//   (thfhe_keyswitch.h, shared with the multi-key engines): one gate per workgroup (small batches); from 192 gates on the rows of a few
+//                             (i, j) staged in LDS for 32 gates, the digit selecting an address; from 512 gates on an int8 GEMM on the matrix cores
 //   sk_linear_kernel          NOT / COPY (J/gates.jl:76-79)
 #include <hip/hip_runtime.h>
 
@@ -28,6 +28,7 @@
 #include "thfhe_common.h"
 #include "thfhe_dag.h"
 #include "thfhe_devctx.h"
+#include "thfhe_keyswitch.h"
 #include "thfhe_lane.h"
 
 using namespace thfhe;
@@ -471,497 +472,6 @@ __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) 
     }
 }
 
-// ------------------------------------------------------------------------------------------------------
-// key switch.  One workgroup (4 waves) per gate; wave w takes input coordinates i = w (mod 4); every lane keeps
-// its 4*NX4 + 2*NX2 words of the padded output row in registers.  KSK rows are padded to 64*(4*NX4+2*NX2) words
-// (n = 630: 640 words = 2560 B, 16-B aligned): per row each lane issues NX4 16-byte and NX2 8-byte loads.
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sk_ksk_pad_kernel(const int32_t *__restrict__ src, long rows, int n, int row_words,
-                                                          int32_t *__restrict__ dst) {
-    const long r = blockIdx.x;
-    if (r >= rows) return;
-    for (int q = threadIdx.x; q < row_words; q += 256) dst[r * row_words + q] = q <= n ? src[r * (n + 1) + q] : 0;
-}
-
-struct KSArgs {
-    const int32_t *ksk;  // [N][t][base-1][row_words]
-    const int32_t *u;    // [jobs][N+1]
-    int32_t *out;        // [gates][n+1]
-    long gates;
-    int rot_per_gate;    // 1, or 2 for MUX: input = (0, 2^29) + u1 + u2     (J/gates.jl:172-176)
-    int n, t, basebit;
-    int nsplit;          // > 1: grid.y workgroups share one gate (small batches) and accumulate into a zeroed output with atomics
-};
-
-template <int NX4, int NX2>
-__global__ __launch_bounds__(256) void sk_keyswitch_kernel(KSArgs a) {
-    constexpr int ROW = 64 * (4 * NX4 + 2 * NX2);
-    __shared__ uint32_t sA[1024];
-    __shared__ uint32_t sRed[3][ROW];
-    const long g = blockIdx.x;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint32_t prec_offset = 1u << (32 - (1 + a.basebit * a.t));
-    const int32_t *u1 = a.u + (size_t)g * a.rot_per_gate * 1025;
-    for (int q = tid; q < 1024; q += 256) {
-        uint32_t v = (uint32_t)u1[q];
-        if (a.rot_per_gate == 2) v += (uint32_t)u1[1025 + q];
-        sA[q] = v + prec_offset;
-    }
-    __syncthreads();
-    const int base1 = (1 << a.basebit) - 1;
-    const uint32_t mask = (uint32_t)base1;
-    uint32_t r4[NX4 > 0 ? NX4 : 1][4];
-    uint32_t r2[NX2 > 0 ? NX2 : 1][2];
-#pragma unroll
-    for (int c = 0; c < NX4; c++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) r4[c][q] = 0;
-    r2[0][0] = r2[0][1] = 0;
-    const int i_lo = (int)blockIdx.y * (1024 / a.nsplit), i_hi = i_lo + 1024 / a.nsplit;
-    for (int i = i_lo + wave; i < i_hi; i += 4) {
-        const uint32_t ai = sA[i];
-        const int32_t *rowi = a.ksk + (size_t)i * a.t * base1 * ROW;
-        for (int j = 0; j < a.t; j++) {
-            const uint32_t d = (ai >> (32 - (j + 1) * a.basebit)) & mask;
-            if (d == 0) continue;  // wave-uniform
-            const int32_t *row = rowi + ((size_t)j * base1 + (d - 1)) * ROW;
-#pragma unroll
-            for (int c = 0; c < NX4; c++) {
-                const uint4 x = *reinterpret_cast<const uint4 *>(row + c * 256 + 4 * lane);
-                r4[c][0] -= x.x; r4[c][1] -= x.y; r4[c][2] -= x.z; r4[c][3] -= x.w;
-            }
-            if (NX2 > 0) {
-                const uint2 x = *reinterpret_cast<const uint2 *>(row + NX4 * 256 + 2 * lane);
-                r2[0][0] -= x.x; r2[0][1] -= x.y;
-            }
-        }
-    }
-    if (wave > 0) {
-        uint32_t *red = sRed[wave - 1];
-#pragma unroll
-        for (int c = 0; c < NX4; c++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) red[c * 256 + 4 * lane + q] = r4[c][q];
-        if (NX2 > 0) {
-            red[NX4 * 256 + 2 * lane] = r2[0][0];
-            red[NX4 * 256 + 2 * lane + 1] = r2[0][1];
-        }
-    }
-    __syncthreads();
-    if (wave == 0) {
-        uint32_t b = (uint32_t)u1[1024];
-        if (a.rot_per_gate == 2) b += (uint32_t)u1[1025 + 1024] + (1u << 29);
-        int32_t *out = a.out + (size_t)g * (a.n + 1);
-        auto emit = [&](int q, uint32_t v) {
-            v += sRed[0][q] + sRed[1][q] + sRed[2][q];
-            if (q == a.n && blockIdx.y == 0) v += b;
-            if (q > a.n) return;
-            if (a.nsplit == 1) out[q] = (int32_t)v;
-            else atomicAdd(reinterpret_cast<unsigned int *>(out) + q, v);  // integer adds commute: still bit-exact
-        };
-#pragma unroll
-        for (int c = 0; c < NX4; c++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) emit(c * 256 + 4 * lane + q, r4[c][q]);
-        if (NX2 > 0) {
-            emit(NX4 * 256 + 2 * lane, r2[0][0]);
-            emit(NX4 * 256 + 2 * lane + 1, r2[0][1]);
-        }
-    }
-}
-
-// words per lane of a padded KSK row: smallest even W with 64*W >= n+1
-// ------------------------------------------------------------------------------------------------------
-// key switch, throughput variant (ks_basebit == 2, large batches).  sk_keyswitch_kernel reads 0.75 rows per gate and (i, j) out of
-// L2 -- 15.7 MB per gate, 64 GB per 4096-gate launch: it is bound by L2 bandwidth, not by its subtractions.  Here one workgroup
-// takes G gates and walks (i, j) once for all of them: the three rows KS[i][j][1..3] are loaded ONCE into registers (3 x W words per
-// lane) and every gate subtracts the row its wave-uniform digit selects (or nothing), so a launch pulls 3/G rows per gate and (i, j)
-// (G = 16: 4x less).  Wave w takes coordinates i = w (mod 4); the four partial sums per gate are combined with integer atomics into the
-// zeroed output (adds commute: bit-exact).
-// ------------------------------------------------------------------------------------------------------
-template <int NX4, int NX2, int G>
-__global__ __launch_bounds__(256) void sk_keyswitch_multi_kernel(KSArgs a) {
-    constexpr int W = 4 * NX4 + 2 * NX2;  // words per lane of a padded row
-    constexpr int ROW = 64 * W;
-    __shared__ uint32_t sA[G][1024];
-    const long g0 = (long)blockIdx.x * G;
-    const int ng = (a.gates - g0) < G ? (int)(a.gates - g0) : G;
-    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const uint32_t prec_offset = 1u << (32 - (1 + 2 * a.t));
-    const int span = 1024 / a.nsplit, first = (int)blockIdx.y * span;
-    for (int q = tid; q < G * span; q += 256) {
-        const int g = q / span, i = first + q % span;
-        uint32_t v = 0;
-        if (g < ng) {
-            const int32_t *u1 = a.u + (size_t)(g0 + g) * a.rot_per_gate * 1025;
-            v = (uint32_t)u1[i];
-            if (a.rot_per_gate == 2) v += (uint32_t)u1[1025 + i];
-            v += prec_offset;
-        }
-        sA[g][i] = v;  // absent gates: all digits zero
-    }
-    __syncthreads();
-    uint32_t r[G][W];
-#pragma unroll
-    for (int g = 0; g < G; g++)
-#pragma unroll
-        for (int q = 0; q < W; q++) r[g][q] = 0;
-    const int i_lo = (int)blockIdx.y * (1024 / a.nsplit), i_hi = i_lo + 1024 / a.nsplit;
-    for (int i = i_lo + wave; i < i_hi; i += 4) {
-        uint32_t ai[G];
-#pragma unroll
-        for (int g = 0; g < G; g++) ai[g] = __builtin_amdgcn_readfirstlane(sA[g][i]);
-        const int32_t *rowi = a.ksk + (size_t)i * a.t * 3 * ROW;
-        for (int j = 0; j < a.t; j++) {
-            const int sh = 32 - 2 * (j + 1);
-            uint32_t x[3][W];
-#pragma unroll
-            for (int d = 0; d < 3; d++) {
-                const int32_t *row = rowi + ((size_t)j * 3 + d) * ROW;
-#pragma unroll
-                for (int c = 0; c < NX4; c++) {
-                    const uint4 v = *reinterpret_cast<const uint4 *>(row + c * 256 + 4 * lane);
-                    x[d][4 * c] = v.x, x[d][4 * c + 1] = v.y, x[d][4 * c + 2] = v.z, x[d][4 * c + 3] = v.w;
-                }
-                if (NX2 > 0) {
-                    const uint2 v = *reinterpret_cast<const uint2 *>(row + NX4 * 256 + 2 * lane);
-                    x[d][4 * NX4] = v.x, x[d][4 * NX4 + 1] = v.y;
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < G; g++) {
-                const uint32_t d = (ai[g] >> sh) & 3u;  // wave-uniform
-                if (d == 1) {
-#pragma unroll
-                    for (int q = 0; q < W; q++) r[g][q] -= x[0][q];
-                } else if (d == 2) {
-#pragma unroll
-                    for (int q = 0; q < W; q++) r[g][q] -= x[1][q];
-                } else if (d == 3) {
-#pragma unroll
-                    for (int q = 0; q < W; q++) r[g][q] -= x[2][q];
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-        if (g < ng) {  // (no `break`: the loop must unroll completely so that r[][] stays in registers)
-            const int32_t *u1 = a.u + (size_t)(g0 + g) * a.rot_per_gate * 1025;
-            unsigned int *out = reinterpret_cast<unsigned int *>(a.out) + (size_t)(g0 + g) * (a.n + 1);
-            uint32_t b = 0;
-            if (wave == 0 && blockIdx.y == 0) {
-                b = (uint32_t)u1[1024];
-                if (a.rot_per_gate == 2) b += (uint32_t)u1[1025 + 1024] + (1u << 29);
-            }
-#pragma unroll
-            for (int q = 0; q < W; q++) {
-                const int col = q < 4 * NX4 ? (q >> 2) * 256 + 4 * lane + (q & 3) : NX4 * 256 + 2 * lane + (q - 4 * NX4);
-                uint32_t v = r[g][q];
-                if (col == a.n) v += b;
-                if (col <= a.n) atomicAdd(out + col, v);
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// key switch, staged variant (ks_basebit == 2, t <= 8 and a multiple of the stage depth, rows of 512 / 640 / 1152 words, >= 192 gates).  The kernel above selects a row per gate with
-// wave-uniform branches; the compiler turns that chain into flag-guarded blocks with subtract-into-a-copy + moves, and the loop runs at a
-// quarter of its subtraction rate.  Here the digit selects an ADDRESS: a workgroup of eight waves copies the rows KS[i][j][1..3] of four
-// (i, j) at a time into LDS (twelve contiguous rows in global memory; double buffered through registers), and a lane reads its part of the
-// row its gate's digit names -- digit 0 names a row of zeros -- with ds_read_b128: no branch, no select, 3/32 rows per gate and (i, j)
-// out of L2.  A wave takes FOUR gates, one per 16-lane group of the LDS hardware ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32
-// serve one ds_read_b128 cycle each): the 16 lanes of a group read 16 consecutive pieces of ONE row = all 64 banks once, whatever the four
-// digits are (eight lanes per gate met other gates' rows in their group: two-way conflicts, 1.3 ms per 4096 gates).  Partial sums of the
-// coordinate ranges meet in the zeroed output with integer atomics (adds commute: bit-exact).
-// ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ks_sub(uint32_t &r, uint32_t x) { asm("v_sub_u32 %0, %0, %1" : "+v"(r) : "v"(x)); }   // in place, never re-associated
-template <int W, int SJ>   // W: 16-byte pieces per lane (row of 64 W words); SJ: (i, j) pairs per stage (4; 2 for the long rows of n = 1024)
-__global__ __launch_bounds__(512) void sk_keyswitch_staged_kernel(KSArgs a) {
-    constexpr int ROW4 = 16 * W;             // 16-byte pieces of a padded row
-    constexpr int Q = W;                     // pieces per lane: sixteen lanes share a row
-    constexpr int GW = 32;                   // gates per workgroup
-    constexpr int KS_CHUNK = 3;              // reads in flight behind the ones being subtracted (measured: 3 <= 5 < 10; SJ = 2 loses 4 %)
-    constexpr int STAGE4 = SJ * 3 * ROW4;
-    constexpr int NLD = (STAGE4 + 511) / 512;
-    static_assert(NLD <= 4, "a stage is at most four rounds of 512 pieces");
-    __shared__ uint4 sL[ROW4 + 2 * STAGE4];     // [row of zeros][stage 0][stage 1]
-    __shared__ uint16_t sDig[GW][256];          // the t <= 8 digits of every coordinate of this workgroup's range: top 16 bits of u + offset
-    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int q5 = lane & 31;
-    const int gl = 2 * (lane >> 5) + (int)((0xF00F0FF0u >> q5) & 1u);   // the lane's ds_read_b128 group = its gate within the wave
-    const int c = q5 < 4 ? q5 : q5 < 12 ? q5 - 4 : q5 < 20 ? q5 - 8 : q5 < 28 ? q5 - 12 : q5 - 16;   // position in the group: 0 .. 15
-    const long g0 = (long)blockIdx.x * GW;
-    const int span = 1024 / a.nsplit, first = (int)blockIdx.y * span;   // span <= 256
-    const uint32_t prec_offset = 1u << (32 - (1 + 2 * a.t));
-    for (int q = tid; q < GW * span; q += 512) {
-        const int g = q / span, ii = q % span;
-        uint32_t v = 0;
-        if (g0 + g < a.gates) {
-            const int32_t *u1 = a.u + (size_t)(g0 + g) * a.rot_per_gate * 1025;
-            v = (uint32_t)u1[first + ii];
-            if (a.rot_per_gate == 2) v += (uint32_t)u1[1025 + first + ii];
-            v += prec_offset;
-        }
-        sDig[g][ii] = (uint16_t)(v >> 16);  // absent gates: all digits zero
-    }
-    for (int q = tid; q < ROW4; q += 512) sL[q] = uint4{0u, 0u, 0u, 0u};
-    const uint4 *src = reinterpret_cast<const uint4 *>(a.ksk) + (size_t)first * a.t * 3 * ROW4;
-    const int NS = span * a.t / SJ;
-    // stage st of the key: twelve contiguous rows; thread tid moves pieces tid + 512 k (a partial last round reads a clamped index and stores nothing).
-    // Named scalars: as arrays behind an unrolled loop the pieces stayed in scratch memory.
-    uint4 pre0, pre1 = uint4{0u, 0u, 0u, 0u}, pre2 = pre1, pre3 = pre1;
-    const bool last_ok = 512 * NLD <= STAGE4 || tid + 512 * (NLD - 1) < STAGE4;
-    const int last_idx = last_ok ? tid + 512 * (NLD - 1) : STAGE4 - 1;
-#define KS_GLOAD(st)                                              \
-    {                                                             \
-        const uint4 *p_ = src + (size_t)(st) * STAGE4;            \
-        pre0 = p_[NLD == 1 ? last_idx : tid];                     \
-        if (NLD > 1) pre1 = p_[NLD == 2 ? last_idx : tid + 512];  \
-        if (NLD > 2) pre2 = p_[NLD == 3 ? last_idx : tid + 1024]; \
-        if (NLD > 3) pre3 = p_[last_idx];                         \
-    }
-#define KS_LSTORE(buf)                                                    \
-    {                                                                     \
-        uint4 *d_ = sL + ROW4 + (buf) * STAGE4 + tid;                     \
-        if (NLD > 1 || last_ok) d_[0] = pre0;                             \
-        if (NLD > 2 || (NLD == 2 && last_ok)) d_[512] = pre1;             \
-        if (NLD > 3 || (NLD == 3 && last_ok)) d_[1024] = pre2;            \
-        if (NLD == 4 && last_ok) d_[1536] = pre3;                         \
-    }
-    KS_GLOAD(0)
-    KS_LSTORE(0)
-    __syncthreads();
-    uint4 acc[Q];
-#pragma unroll
-    for (int k = 0; k < Q; k++) acc[k] = uint4{0u, 0u, 0u, 0u};
-    const uint16_t *dig = sDig[wave * 4 + gl];
-    for (int st = 0; st < NS; st++) {
-        if (st + 1 < NS) {
-            KS_GLOAD(st + 1)
-        }
-        const int p0 = st * SJ, ii = p0 / a.t, j0 = p0 % a.t;   // t is a multiple of SJ: the pairs of a stage belong to one coordinate
-        const uint32_t hi = dig[ii];
-        const uint4 *row[SJ];
-#pragma unroll
-        for (int pp = 0; pp < SJ; pp++) {
-            const uint32_t d = (hi >> (14 - 2 * (j0 + pp))) & 3u;
-            row[pp] = sL + (d ? ROW4 + (st & 1) * STAGE4 + (pp * 3 + (int)d - 1) * ROW4 : 0) + c;
-        }
-        // KS_CHUNK reads in flight behind the KS_CHUNK being subtracted -- not all of a stage: the memory fence stops the optimiser, the
-        // scheduling barrier the instruction scheduler from clustering them
-        constexpr int NCH = (Q + KS_CHUNK - 1) / KS_CHUNK;
-        uint4 x[2][KS_CHUNK];
-        auto reads = [&](int ch) {   // ch < SJ * NCH, compile-time after unrolling
-            const uint4 *r = row[ch / NCH];
-            const int k0 = (ch % NCH) * KS_CHUNK;
-#pragma unroll
-            for (int k = 0; k < KS_CHUNK; k++)
-                if (k0 + k < Q) x[ch & 1][k] = r[16 * (k0 + k)];
-        };
-        reads(0);
-#pragma unroll
-        for (int ch = 0; ch < SJ * NCH; ch++) {
-            if (ch + 1 < SJ * NCH) reads(ch + 1);
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            const int k0 = (ch % NCH) * KS_CHUNK;
-#pragma unroll
-            for (int k = 0; k < KS_CHUNK; k++)
-                if (k0 + k < Q) {
-                    uint4 &t = acc[k0 + k];
-                    const uint4 v = x[ch & 1][k];
-                    ks_sub(t.x, v.x), ks_sub(t.y, v.y), ks_sub(t.z, v.z), ks_sub(t.w, v.w);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (st + 1 < NS) {
-            KS_LSTORE((st + 1) & 1)
-        }
-        __syncthreads();
-    }
-#undef KS_GLOAD
-#undef KS_LSTORE
-    const long g = g0 + wave * 4 + gl;
-    if (g < a.gates) {
-        const int32_t *u1 = a.u + (size_t)g * a.rot_per_gate * 1025;
-        unsigned int *out = reinterpret_cast<unsigned int *>(a.out) + (size_t)g * (a.n + 1);
-        uint32_t b = 0;
-        if (blockIdx.y == 0) {
-            b = (uint32_t)u1[1024];
-            if (a.rot_per_gate == 2) b += (uint32_t)u1[1025 + 1024] + (1u << 29);
-        }
-#pragma unroll
-        for (int k = 0; k < Q; k++) {
-            const uint32_t v4[4] = {acc[k].x, acc[k].y, acc[k].z, acc[k].w};
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int col = 4 * (c + 16 * k) + e;
-                uint32_t v = v4[e];
-                if (col == a.n) v += b;
-                if (col <= a.n) atomicAdd(out + col, v);
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// key switch on the matrix cores (ks_basebit == 2, t = 4 or 8, large batches).  The key switch is an exact integer GEMM:
-//   out[g] = (0, .., 0, b) - sum_k A[g][k] B[k],   k = (i, j, v): coordinate i < N, level j < t, digit value v < 4,
-// A one-hot (A[g][(i, j, v)] = [digit j of coordinate i of gate g == v]) and B[(i, j, v)] = KS[i][j][v - 1], with a row of zeros for v = 0.
-// Every 32-bit key word is split into four balanced signed bytes, w = sum_p beta_p 2^(8p) (mod 2^32), beta_p in [-128, 127], so B becomes four
-// int8 planes and C_p = A B_p is a v_mfma_i32_32x32x32_i8 product: |C_p| <= N t 128 = 2^20, and out = b - sum_p C_p << 8p, all mod 2^32.
-// Integer sums commute, so tiling, split-K and the atomics cannot change a bit.
-//
-// K chunks of 32 = 8 (i, j) slots x 4 values: slot s = 8 kc + 4 h + q of the chunk kc is held by the lanes of half h = lane >> 5 in the
-// fragment dword q, value v in byte v.  A and B fragments use that one convention, and an MFMA pairs element e of lane half h of A with
-// element e of the same lane half of B, so the product is the sum over the chunk whatever order the hardware gives the 32 k of a chunk.
-// Planes: [word tile wt][chunk kc][plane p][lane][4 dwords], a 1 KB B fragment per (wt, kc, p); lane r + 32 h holds word 32 wt + r.
-// ------------------------------------------------------------------------------------------------------
-typedef int32_t ks_i32x4 __attribute__((ext_vector_type(4)));
-typedef int32_t ks_i32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ uint32_t ks_balanced_byte(uint32_t w, int p) {   // beta_p of w, as a byte
-    for (int k = 0; k < p; k++) w = (w - (uint32_t)(int32_t)(int8_t)(w & 0xFFu)) >> 8;
-    return w & 0xFFu;
-}
-
-__global__ __launch_bounds__(256) void sk_ksk_planes_kernel(const int32_t *__restrict__ ksk, int row_words, int t, long kchunks, long total,
-                                                             uint32_t *__restrict__ planes) {
-    const long x = (long)blockIdx.x * 256 + threadIdx.x;   // one dword of the planes
-    if (x >= total) return;
-    const int q = (int)(x & 3), lane = (int)((x >> 2) & 63), p = (int)((x >> 8) & 3);
-    const long kc = (x >> 10) % kchunks, wt = (x >> 10) / kchunks;
-    const long s = 8 * kc + 4 * (lane >> 5) + q, i = s / t, j = s % t;
-    const int32_t *row = ksk + ((i * t + j) * 3) * row_words + 32 * wt + (lane & 31);
-    uint32_t dw = 0;
-    for (int v = 1; v < 4; v++) dw |= ks_balanced_byte((uint32_t)row[(v - 1) * row_words], p) << (8 * v);
-    planes[x] = dw;
-}
-
-struct KSMArgs {
-    const ks_i32x4 *planes;   // [wtiles][kchunks][4][64]
-    const int32_t *u;         // [jobs][N+1]
-    int32_t *out;             // [gates][n+1]
-    long gates;
-    int rot_per_gate;         // 1, or 2 for MUX: input = (0, 2^29) + u1 + u2
-    int n, t;
-    int kchunks;              // N t / 8
-    int wtiles;               // 32-word tiles of a padded row
-    int gtiles;               // 256-gate tiles
-    int nsplit;               // > 1: the chunks are cut in nsplit ranges whose partial sums meet in the zeroed output with atomics
-};
-
-// One workgroup: 256 gates (4 waves x 2 tiles of 32) x one 32-word tile (4 planes) x one chunk range.  The planes of KS_S chunks (32 KB) are
-// staged in LDS per step (double buffered through registers) and read by all four waves; each wave builds its A fragments from the digits of
-// its gates, and keeps 2 x 4 accumulators of 32 x 32 int32.
-template <int T, int ROT>   // key-switch depth: 4 or 8; rotations per gate: 1, or 2 for MUX (a.rot_per_gate)
-__global__ __launch_bounds__(256) void sk_keyswitch_mfma_kernel(KSMArgs a) {
-    static_assert(T == 4 || T == 8, "a lane half's four slots are four levels of one coordinate");
-    constexpr int S = 8;                  // chunks per stage
-    constexpr int NLD = S * 4 * 64 / 256; // 16-byte pieces per thread and stage
-    __shared__ ks_i32x4 sB[2][S * 4 * 64];
-    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int r = lane & 31, h = lane >> 5;
-    // workgroups are dealt round-robin over the 8 XCDs: renumber them so that the gate tiles of one (word tile, chunk range) share an XCD's L2
-    long L = blockIdx.x;
-    const long nblk = gridDim.x;
-    if (nblk % 8 == 0) L = (L % 8) * (nblk / 8) + L / 8;
-    const int gt = (int)(L % a.gtiles), wt = (int)(L / a.gtiles % a.wtiles), sp = (int)(L / a.gtiles / a.wtiles);
-    const int kper = a.kchunks / a.nsplit, kc0 = sp * kper, NS = kper / S;
-    const ks_i32x4 *src = a.planes + ((size_t)wt * a.kchunks + kc0) * 256;
-    const uint32_t prec_offset = 1u << (32 - (1 + 2 * T));
-    // the lane's A rows: gates g0 + 32 m + r
-    const long g0 = (long)gt * 256 + wave * 64;
-    // (rows past the batch read the last gate's digits and store nothing: no branch around the loads, whose waits would serialise them)
-    const int32_t *urow[2];
-#pragma unroll
-    for (int m = 0; m < 2; m++) {
-        const long g = g0 + 32 * m + r;
-        urow[m] = a.u + (size_t)(g < a.gates ? g : a.gates - 1) * ROT * 1025;
-    }
-    // chunk kc: the lane's four slots 8 kc + 4 h + q are levels j0 .. j0 + 3 of one coordinate (t is a multiple of 4)
-    auto coord = [&](int kc) { return T == 8 ? kc : 2 * kc + h; };
-    const int j0 = T == 8 ? 4 * h : 0;
-    ks_i32x4 pre[NLD];
-    uint32_t uw[2][S], un[2][S];
-    auto load = [&](int st) {
-        const ks_i32x4 *p_ = src + (size_t)st * (S * 256) + tid;
-#pragma unroll
-        for (int k = 0; k < NLD; k++) pre[k] = p_[256 * k];
-#pragma unroll
-        for (int m = 0; m < 2; m++)
-#pragma unroll
-            for (int c = 0; c < S; c++) {
-                const int i = coord(kc0 + st * S + c);
-                un[m][c] = (uint32_t)urow[m][i];
-                if (ROT == 2) un[m][c] += (uint32_t)urow[m][1025 + i];
-            }
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int k = 0; k < NLD; k++) sB[buf][tid + 256 * k] = pre[k];
-#pragma unroll
-        for (int m = 0; m < 2; m++)
-#pragma unroll
-            for (int c = 0; c < S; c++) uw[m][c] = un[m][c] + prec_offset;   // (here, not in load(): the add would wait for the loads)
-    };
-    load(0);
-    store(0);
-    __syncthreads();
-    ks_i32x16 acc[2][4];
-#pragma unroll
-    for (int m = 0; m < 2; m++)
-#pragma unroll
-        for (int p = 0; p < 4; p++) acc[m][p] = ks_i32x16{0};
-    for (int st = 0; st < NS; st++) {
-        if (st + 1 < NS) load(st + 1);
-        const ks_i32x4 *b = sB[st & 1] + lane;
-        ks_i32x4 bf[2][4];   // the B fragments of chunk c + 1 are read while chunk c's MFMAs run
-#pragma unroll
-        for (int p = 0; p < 4; p++) bf[0][p] = b[p * 64];
-#pragma unroll
-        for (int c = 0; c < S; c++) {
-            if (c + 1 < S)
-#pragma unroll
-                for (int p = 0; p < 4; p++) bf[(c + 1) & 1][p] = b[((c + 1) * 4 + p) * 64];
-            ks_i32x4 af[2];
-#pragma unroll
-            for (int m = 0; m < 2; m++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) af[m][q] = (int32_t)(1u << (8 * ((uw[m][c] >> (30 - 2 * (j0 + q))) & 3u)));   // digit 0: the zero row
-#pragma unroll
-            for (int m = 0; m < 2; m++)
-#pragma unroll
-                for (int p = 0; p < 4; p++) acc[m][p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[m], bf[c & 1][p], acc[m][p], 0, 0, 0);
-        }
-        if (st + 1 < NS) store((st + 1) & 1);
-        __syncthreads();
-    }
-    // C/D: lane r + 32 h, register e holds row (e & 3) + 8 (e >> 2) + 4 h, column r
-    const int col = 32 * wt + r;
-    if (col > a.n) return;
-#pragma unroll
-    for (int m = 0; m < 2; m++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-            const long g = g0 + 32 * m + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (g >= a.gates) continue;
-            uint32_t v = 0u - ((uint32_t)acc[m][0][e] + ((uint32_t)acc[m][1][e] << 8) + ((uint32_t)acc[m][2][e] << 16) + ((uint32_t)acc[m][3][e] << 24));
-            if (col == a.n && sp == 0) {
-                const int32_t *u1 = a.u + (size_t)g * ROT * 1025;
-                v += (uint32_t)u1[1024];
-                if (ROT == 2) v += (uint32_t)u1[1025 + 1024] + (1u << 29);
-            }
-            unsigned int *o = reinterpret_cast<unsigned int *>(a.out) + (size_t)g * (a.n + 1) + col;
-            if (a.nsplit == 1) *o = v;
-            else atomicAdd(o, v);
-        }
-}
-
-inline int ks_words_per_lane(int n) { return (((n + 1 + 63) / 64) + 1) & ~1; }
-
 __global__ __launch_bounds__(256) void sk_linear_kernel(const int32_t *__restrict__ in0, int32_t *__restrict__ out, size_t words, int negate) {
     const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (q < words) out[q] = negate ? (int32_t)(0u - (uint32_t)in0[q]) : in0[q];
@@ -975,13 +485,7 @@ __global__ __launch_bounds__(256) void sk_linear_kernel(const int32_t *__restric
 struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     thfhe_params p;
     DevBuf d_bk;              // spectral key
-    DevBuf d_ksk;             // padded rows
-    DevBuf d_ksk_planes;      // the padded rows as four balanced int8 planes in MFMA fragment order (sk_keyswitch_mfma_kernel; empty: shape not taken)
-    int ks_w = 0;             // words per lane of a padded KSK row
-    long ks_mfma_min_gates = 512;    // batches of at least this many gates use sk_keyswitch_mfma_kernel where its shape allows
-    long ks_multi_min_gates = 1024;  // batches of at least this many gates use sk_keyswitch_multi_kernel (rows shared by the gates of a workgroup)
-    long ks_staged_min_gates = 192;  // (measured: 128 gates 0.146 ms one gate per workgroup / 0.184 staged, 256 gates 0.381 / 0.201)
-    // ... and, where its shape allows, batches from this size on sk_keyswitch_staged_kernel (rows staged in LDS, the digit selects an address)
+    KsKey ksk;                // padded rows (+ the matrix-core planes)
     int coop_max_jobs = 768;    // remainders (batch mod 2048) up to this many rotations use the cooperative (latency) kernel
     int ring4_max_jobs = 1024;  // ... above it and up to this many, the four-wave ring kernel (launch_br)
     // workspace
@@ -1113,91 +617,17 @@ int enqueue_lut_rotations(thfhe_ctx *c, const thfhe_lut_spec &sp, const int32_t 
     return THFHE_OK;
 }
 
-// the shapes sk_keyswitch_mfma_kernel takes: 2-bit digits, t = 4 or 8 (four levels of one coordinate per lane half), N = 1024
-inline bool ks_mfma_shape(const thfhe_params &p) { return p.ks_basebit == 2 && (p.ks_t == 4 || p.ks_t == 8) && p.N == 1024; }
-
 int enqueue_keyswitch(thfhe_ctx *c, const int32_t *d_u, int32_t *d_out, size_t gates, int rot_per_gate, bool timed) {
-    if (c->d_ksk_planes.bytes() && (long)gates >= c->ks_mfma_min_gates) {
-        // the key switch as an int8 GEMM on the matrix cores (sk_keyswitch_mfma_kernel): 256-gate x 32-word tiles; the chunks are cut into
-        // nsplit ranges until the grid has at least 1 024 workgroups (4 096 gates, n = 630: 16 x 20 x 4).
-        KSMArgs k{c->d_ksk_planes.as<ks_i32x4>(), d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, c->p.N * c->p.ks_t / 8, 2 * c->ks_w,
-                  (int)((gates + 255) / 256), 1};
-        while (k.nsplit < 8 && (long)k.gtiles * k.wtiles * k.nsplit < 1024) k.nsplit *= 2;
-        if (k.nsplit > 1) THFHE_HIP(hipMemsetAsync(d_out, 0, gates * (size_t)(c->p.n + 1) * sizeof(int32_t), c->stream));
-        const dim3 grid((unsigned)((long)k.gtiles * k.wtiles * k.nsplit)), block(256);
-        if (c->p.ks_t == 8) {
-            if (rot_per_gate == 1) hipLaunchKernelGGL((sk_keyswitch_mfma_kernel<8, 1>), grid, block, 0, c->stream, k);
-            else hipLaunchKernelGGL((sk_keyswitch_mfma_kernel<8, 2>), grid, block, 0, c->stream, k);
-        } else {
-            if (rot_per_gate == 1) hipLaunchKernelGGL((sk_keyswitch_mfma_kernel<4, 1>), grid, block, 0, c->stream, k);
-            else hipLaunchKernelGGL((sk_keyswitch_mfma_kernel<4, 2>), grid, block, 0, c->stream, k);
-        }
-        if (timed && c->profiling) {
-            THFHE_HIP(hipEventRecord(c->ev[3], c->stream));
-            c->ev_valid = true;
-        }
-        THFHE_HIP(hipGetLastError());
-        return THFHE_OK;
-    }
-    const bool staged_shape = c->p.ks_basebit == 2 && c->p.ks_t <= 8 &&
-                              (((c->ks_w == 8 || c->ks_w == 10) && c->p.ks_t % 4 == 0) || (c->ks_w == 18 && c->p.ks_t % 2 == 0));
-    if (staged_shape && (long)gates >= c->ks_staged_min_gates) {
-        // throughput variant: rows staged in LDS for 32 gates, the digit selects an address (sk_keyswitch_staged_kernel).  The coordinates are cut
-        // into 16 ranges (8 from 2 048 gates on: measured) whose partial sums meet in the zeroed output: 1 024 workgroups at 4 096 gates, 512 at 1 024.
-        // Measured on MI355X, n = 630: 4 096 gates 1.01 ms (one gate per workgroup 2.57, branch-selected rows 1.69), 1 024 gates 0.34 (0.58),
-        // 512 gates 0.24 (0.43), 256 gates 0.20 (0.38).
-        KSArgs k{c->d_ksk.as<int32_t>(), d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, 2, gates >= 2048 ? 8 : 16};
-        THFHE_HIP(hipMemsetAsync(d_out, 0, gates * (size_t)(c->p.n + 1) * sizeof(int32_t), c->stream));
-        const dim3 sgrid((unsigned)((gates + 31) / 32), (unsigned)k.nsplit), sblock(512);
-        if (c->ks_w == 8) hipLaunchKernelGGL((sk_keyswitch_staged_kernel<8, 4>), sgrid, sblock, 0, c->stream, k);
-        else if (c->ks_w == 10) hipLaunchKernelGGL((sk_keyswitch_staged_kernel<10, 4>), sgrid, sblock, 0, c->stream, k);
-        else hipLaunchKernelGGL((sk_keyswitch_staged_kernel<18, 2>), sgrid, sblock, 0, c->stream, k);
-        if (timed && c->profiling) {
-            THFHE_HIP(hipEventRecord(c->ev[3], c->stream));
-            c->ev_valid = true;
-        }
-        THFHE_HIP(hipGetLastError());
-        return THFHE_OK;
-    }
-    if (c->p.ks_basebit == 2 && (long)gates >= c->ks_multi_min_gates && (c->ks_w == 8 || c->ks_w == 10 || c->ks_w == 18)) {
-        // the rows of an (i, j) loaded once into registers for the gates of a workgroup, selected per gate by wave-uniform branches: the shapes the
-        // staged kernel does not take (t not a multiple of its stage depth).  The coordinate range is cut in four so that 2048+ workgroups keep
-        // ~12 waves per CU in flight.
-        constexpr int kSplit = 4;
-        KSArgs k{c->d_ksk.as<int32_t>(), d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, 2, kSplit};
-        THFHE_HIP(hipMemsetAsync(d_out, 0, gates * (size_t)(c->p.n + 1) * sizeof(int32_t), c->stream));
-        const dim3 block(256);
-        if (c->ks_w == 8) hipLaunchKernelGGL((sk_keyswitch_multi_kernel<2, 0, 8>), dim3((unsigned)((gates + 7) / 8), kSplit), block, 0, c->stream, k);
-        else if (c->ks_w == 10) hipLaunchKernelGGL((sk_keyswitch_multi_kernel<2, 1, 8>), dim3((unsigned)((gates + 7) / 8), kSplit), block, 0, c->stream, k);
-        else hipLaunchKernelGGL((sk_keyswitch_multi_kernel<4, 1, 4>), dim3((unsigned)((gates + 3) / 4), kSplit), block, 0, c->stream, k);
-        if (timed && c->profiling) {
-            THFHE_HIP(hipEventRecord(c->ev[3], c->stream));
-            c->ev_valid = true;
-        }
-        THFHE_HIP(hipGetLastError());
-        return THFHE_OK;
-    }
+    KsArgs k = c->ksk.args(d_u, d_out, (long)gates);
+    k.rot_per_gate = rot_per_gate;
     const int nsplit = gates <= 32 ? 16 : (gates <= 128 ? 8 : (gates <= 512 ? 2 : 1));  // fill the chip at small batch sizes
-    KSArgs k{c->d_ksk.as<int32_t>(), d_u, d_out, (long)gates, rot_per_gate, c->p.n, c->p.ks_t, c->p.ks_basebit, nsplit};
-    if (nsplit > 1) THFHE_HIP(hipMemsetAsync(d_out, 0, gates * (size_t)(c->p.n + 1) * sizeof(int32_t), c->stream));
-    const dim3 grid((unsigned)gates, (unsigned)nsplit), block(256);
-    switch (c->ks_w) {
-#define THFHE_KS_CASE(W, X4, X2) \
-    case W: hipLaunchKernelGGL((sk_keyswitch_kernel<X4, X2>), grid, block, 0, c->stream, k); break;
-        THFHE_KS_CASE(2, 0, 1) THFHE_KS_CASE(4, 1, 0) THFHE_KS_CASE(6, 1, 1) THFHE_KS_CASE(8, 2, 0) THFHE_KS_CASE(10, 2, 1)
-        THFHE_KS_CASE(12, 3, 0) THFHE_KS_CASE(14, 3, 1) THFHE_KS_CASE(16, 4, 0) THFHE_KS_CASE(18, 4, 1) THFHE_KS_CASE(20, 5, 0)
-        THFHE_KS_CASE(22, 5, 1)
-#undef THFHE_KS_CASE
-    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "LWE dimension n too large for the key-switch kernel (n <= 1407)");
-    }
+    THFHE_TRY(ks_enqueue(c->ksk, k, nsplit, c->stream));
     if (timed && c->profiling) {
         THFHE_HIP(hipEventRecord(c->ev[3], c->stream));
         c->ev_valid = true;
     }
-    THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
-
 int gates_dev_locked(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1, const int32_t *d2, int32_t *dout, size_t count) {
     if (count == 0) return THFHE_OK;
     if (count > (size_t)INT32_MAX / 4) return thfhe_fail(THFHE_E_INVALID, "count too large");
@@ -1282,32 +712,15 @@ int thfhe_ctx_create(const thfhe_params *p, const int32_t *bk_coeff, const int32
     THFHE_TRY(c->open(device, true));
     c->p = *p;
     c->n_pad = (p->n + 3) & ~3;
-    c->ks_w = ks_words_per_lane(p->n);
-    const int row_words = 64 * c->ks_w;
     THFHE_TRY(c->upload_twiddles(1024));
     // bootstrapping key: upload coefficients, transform on device
-    DevBuf coeff, raw;  // upload staging
+    DevBuf coeff;  // upload staging
     const long npolys = (long)p->n * 2 * p->l * 2;
     THFHE_TRY(coeff.grow((size_t)npolys * 1024 * sizeof(int32_t)));
     THFHE_HIP(hipMemcpyAsync(coeff.as<int32_t>(), bk_coeff, (size_t)npolys * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     THFHE_TRY(c->d_bk.grow((size_t)npolys * 1024 * sizeof(cplx)));
     THFHE_TRY((launch_torus_transform<1024, 32>(c->stream, coeff.as<int32_t>(), npolys, c->d_tw.as<cplx>(), c->d_bk.as<cplx>())));
-    // key-switching key: pad rows to 640 words
-    const long rows = (long)p->N * p->ks_t * ((1 << p->ks_basebit) - 1);
-    THFHE_TRY(raw.grow((size_t)rows * (p->n + 1) * sizeof(int32_t)));
-    THFHE_HIP(hipMemcpyAsync(raw.as<int32_t>(), ksk, (size_t)rows * (p->n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_TRY(c->d_ksk.grow((size_t)rows * row_words * sizeof(int32_t)));
-    hipLaunchKernelGGL(sk_ksk_pad_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, raw.as<int32_t>(), rows, p->n, row_words, c->d_ksk.as<int32_t>());
-    THFHE_HIP(hipGetLastError());
-    if (ks_mfma_shape(*p)) {
-        // ... and as int8 planes for the matrix-core kernel: 4 bytes per (word, coordinate, level, digit value): 80 MiB at n = 630, t = 8
-        const long kchunks = (long)p->N * p->ks_t / 8, total = (long)(row_words / 32) * kchunks * 4 * 64 * 4;
-        THFHE_TRY(c->d_ksk_planes.grow((size_t)total * sizeof(uint32_t)));
-        hipLaunchKernelGGL(sk_ksk_planes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->d_ksk.as<int32_t>(), row_words,
-                           p->ks_t, kchunks, total, c->d_ksk_planes.as<uint32_t>());
-        THFHE_HIP(hipGetLastError());
-    }
-    THFHE_HIP(hipStreamSynchronize(c->stream));
+    THFHE_TRY(c->ksk.upload(ksk, 1, p->N, p->n, p->ks_t, p->ks_basebit, true, c->stream));   // (synchronises: the transform is done too)
     *out = c.release();
     return THFHE_OK;
 }
