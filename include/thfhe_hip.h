@@ -287,7 +287,17 @@ int thfhe_ccs_bootstrap(thfhe_ccs_ctx *ctx, int32_t mu, const int32_t *x, int32_
  *                              partial[c] = key_share (*) tlwe_a[c] + noise[c]; (*) exact negacyclic product mod 2^32 (torusPolynomialAddMulR);
  *                              key_share int32[N] with |s| <= 512; noise (the caller's smudging Gaussian) may be NULL
  *   thfhe_final_decrypt     <- finalDecrypt                                          src/libthfhe.cpp:296-315
- *                              result[c] = tlwe_b[c] - partials[0][c] + sum_{i>=1} partials[i][c]; bits[c] = result[c][0] > 0; result may be NULL */
+ *                              result[c] = tlwe_b[c] - partials[0][c] + sum_{i>=1} partials[i][c]; bits[c] = result[c][0] > 0; result may be NULL
+ *   thfhe_pack_key_set      the LWE -> TLWE packing key (the reference's TODO at src/Convert.cpp:103):
+ *                              pk int32[n][t][2^basebit - 1][2][N], row (j, p, v) a TLWE sample (alpha, beta) under the ring key z with
+ *                              beta = alpha (*) z + e + v s_j 2^(32 - (p+1) basebit) on the constant coefficient.  Uploads it (with the
+ *                              matrix-core planes for basebit 2, t = 4 or 8) and replaces any earlier key.  THFHE_E_INVALID for n < 1, t < 1
+ *                              or t basebit > 32; THFHE_E_UNSUPPORTED for basebit > 4 or n > 2048; an allocation failure leaves no key set
+ *   thfhe_pack_lwe          lwe int32[count][n+1] -> tlwe_a, tlwe_b int32[ceil(count / slots)][N]: sample g slots + i is key-switched
+ *                              with its LWE key switch's digits into T = (0, b X^0) - sum PK[j][p][digit - 1] and lands at X^i:
+ *                              output g = sum_i X^i T_{g slots + i} mod X^N + 1.  Coefficient i of its phase (b - a (*) z) is sample i's
+ *                              phase plus rounding and key noise; the output feeds thfhe_partial_decrypt / thfhe_final_decrypt unchanged.
+ *                              THFHE_E_INVALID without a key or for slots outside 1 .. N.  Bit-exact: integer sums mod 2^32 */
 typedef struct thfhe_poly_ctx thfhe_poly_ctx;
 int thfhe_poly_ctx_create(int device, int N, thfhe_poly_ctx **out);
 void thfhe_poly_ctx_destroy(thfhe_poly_ctx *ctx);
@@ -295,6 +305,8 @@ int thfhe_tlwe_from_lwe(thfhe_poly_ctx *ctx, const int32_t *lwe, int32_t *tlwe_a
 int thfhe_partial_decrypt(thfhe_poly_ctx *ctx, const int32_t *key_share, const int32_t *tlwe_a, const int32_t *noise, int32_t *partial, size_t count);
 int thfhe_final_decrypt(thfhe_poly_ctx *ctx, const int32_t *tlwe_b, const int32_t *partials /*[t][count][N]*/, int t, int32_t *result, int32_t *bits,
                         size_t count);
+int thfhe_pack_key_set(thfhe_poly_ctx *ctx, const int32_t *pk, int n, int t, int basebit);
+int thfhe_pack_lwe(thfhe_poly_ctx *ctx, const int32_t *lwe /*[count][n+1]*/, size_t count, int slots, int32_t *tlwe_a, int32_t *tlwe_b /*[ceil(count/slots)][N]*/);
 
 /* ---- multi-key KEY GENERATION arithmetic on the device --------------------------------------------------------------
  * Exact multiply-accumulate of small-coefficient polynomials with torus polynomials, the only non-trivial arithmetic of

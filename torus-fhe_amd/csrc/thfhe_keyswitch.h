@@ -8,6 +8,9 @@
 //   sk_keyswitch_mfma_kernel   single key, 2-bit digits, t = 4 or 8: the key switch as an int8 GEMM on the matrix cores (from 512 samples on);
 //   sk_ksk_planes_kernel       its key planes
 //
+// The LWE -> TLWE packing key switch (thfhe_threshold.hip) runs on the same kernels: its key rows are TLWE samples of 2N words, b lands
+// at word N of the output record (KsArgs::b_col, ::out_rec), and its coordinates are padded to a multiple of 128 (KsKey::upload_pack).
+//
 // Every sample's output is the sum of per-(party, coordinate range) partial sums: integer adds commute, so atomics into a zeroed output
 // are bit-exact.  ks_enqueue picks the kernel and zeroes the output where the kernel accumulates.
 #ifndef THFHE_KEYSWITCH_H
@@ -35,6 +38,8 @@ struct KsArgs {
     int N;  // ring degree = dimension of the extracted sample
     int u_rec, u_pstride;
     int rot_per_gate;
+    int out_rec;  // words per output record: parties * n + 1; the packing key: 2N
+    int b_col;    // output column that receives b: n (its own word after the parties' masks); the packing key: N (inside the row)
 };
 
 constexpr long kKsMfmaMinSamples = 512;    // batches from this size on run sk_keyswitch_mfma_kernel where its shape allows
@@ -52,13 +57,15 @@ __device__ __forceinline__ uint32_t ks_b(const KsArgs &a, long g) {   // b of sa
     if (a.rot_per_gate == 2) b += (uint32_t)u[a.u_rec] + (1u << 29);
     return b;
 }
-// word `col` of sample g's partial sum for party p into the zeroed output; the first coordinate range of party 0 adds b
+// rounding offset of the digits: 2^(32 - (1 + basebit t)), 0 when the digits cover all 32 bits
+__device__ __forceinline__ uint32_t ks_prec_offset(int bt) { return bt >= 32 ? 0u : 1u << (31 - bt); }
+// word `col` of sample g's partial sum for party p into the zeroed output; the first coordinate range of party 0 adds b at column b_col
 __device__ __forceinline__ void ks_emit(const KsArgs &a, long g, int p, bool first, int col, uint32_t v) {
-    unsigned int *out = reinterpret_cast<unsigned int *>(a.out) + (size_t)g * ((size_t)a.parties * a.n + 1);
+    unsigned int *out = reinterpret_cast<unsigned int *>(a.out) + (size_t)g * a.out_rec;
+    if (col == a.b_col && p == 0 && first) v += ks_b(a, g);
     if (col < a.n) {
         atomicAdd(out + (size_t)p * a.n + col, v);
     } else if (col == a.n) {
-        if (p == 0 && first) v += ks_b(a, g);
         atomicAdd(out + (size_t)a.parties * a.n, v);
     }
 }
@@ -82,7 +89,7 @@ __global__ __launch_bounds__(256) void ks_plain_kernel(KsArgs a, int nsplit) {
     const long g = blockIdx.x;
     const int p = blockIdx.y;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint32_t prec_offset = 1u << (32 - (1 + a.basebit * a.t));
+    const uint32_t prec_offset = ks_prec_offset(a.basebit * a.t);
     const int span = a.N / nsplit, i_lo = (int)blockIdx.z * span, i_hi = i_lo + span;
     for (int q = tid; q < span; q += 256) sA[q] = ks_mask_word(a, g, p, i_lo + q) + prec_offset;
     __syncthreads();
@@ -305,9 +312,10 @@ __global__ __launch_bounds__(256) void sk_ksk_planes_kernel(const int32_t *__res
 
 struct KSMArgs {
     const ks_i32x4 *planes;   // [wtiles][kchunks][4][64]
-    const int32_t *u;         // [jobs][N+1]
-    int32_t *out;             // [gates][n+1]
+    const int32_t *u;         // [jobs][u_rec]: N mask words, b last
+    int32_t *out;             // [gates][out_rec]
     long gates;
+    int u_rec, out_rec, b_col;   // KsArgs::u_rec, ::out_rec, ::b_col
     int rot_per_gate;         // 1, or 2 for MUX: input = (0, 2^29) + u1 + u2
     int n, t;
     int kchunks;              // N t / 8
@@ -342,7 +350,7 @@ __global__ __launch_bounds__(256) void sk_keyswitch_mfma_kernel(KSMArgs a) {
 #pragma unroll
     for (int m = 0; m < 2; m++) {
         const long g = g0 + 32 * m + r;
-        urow[m] = a.u + (size_t)(g < a.gates ? g : a.gates - 1) * ROT * 1025;
+        urow[m] = a.u + (size_t)(g < a.gates ? g : a.gates - 1) * ROT * a.u_rec;
     }
     // chunk kc: the lane's four slots 8 kc + 4 h + q are levels j0 .. j0 + 3 of one coordinate (t is a multiple of 4)
     auto coord = [&](int kc) { return T == 8 ? kc : 2 * kc + h; };
@@ -359,7 +367,7 @@ __global__ __launch_bounds__(256) void sk_keyswitch_mfma_kernel(KSMArgs a) {
             for (int c = 0; c < S; c++) {
                 const int i = coord(kc0 + st * S + c);
                 un[m][c] = (uint32_t)urow[m][i];
-                if (ROT == 2) un[m][c] += (uint32_t)urow[m][1025 + i];
+                if (ROT == 2) un[m][c] += (uint32_t)urow[m][a.u_rec + i];
             }
     };
     auto store = [&](int buf) {
@@ -404,7 +412,7 @@ __global__ __launch_bounds__(256) void sk_keyswitch_mfma_kernel(KSMArgs a) {
     }
     // C/D: lane r + 32 h, register e holds row (e & 3) + 8 (e >> 2) + 4 h, column r
     const int col = 32 * wt + r;
-    if (col > a.n) return;
+    if (col >= a.out_rec) return;
 #pragma unroll
     for (int m = 0; m < 2; m++)
 #pragma unroll
@@ -412,12 +420,12 @@ __global__ __launch_bounds__(256) void sk_keyswitch_mfma_kernel(KSMArgs a) {
             const long g = g0 + 32 * m + (e & 3) + 8 * (e >> 2) + 4 * h;
             if (g >= a.gates) continue;
             uint32_t v = 0u - ((uint32_t)acc[m][0][e] + ((uint32_t)acc[m][1][e] << 8) + ((uint32_t)acc[m][2][e] << 16) + ((uint32_t)acc[m][3][e] << 24));
-            if (col == a.n && sp == 0) {
-                const int32_t *u1 = a.u + (size_t)g * ROT * 1025;
-                v += (uint32_t)u1[1024];
-                if (ROT == 2) v += (uint32_t)u1[1025 + 1024] + (1u << 29);
+            if (col == a.b_col && sp == 0) {
+                const int32_t *u1 = a.u + (size_t)g * ROT * a.u_rec;
+                v += (uint32_t)u1[a.u_rec - 1];
+                if (ROT == 2) v += (uint32_t)u1[2 * a.u_rec - 1] + (1u << 29);
             }
-            unsigned int *o = reinterpret_cast<unsigned int *>(a.out) + (size_t)g * (a.n + 1) + col;
+            unsigned int *o = reinterpret_cast<unsigned int *>(a.out) + (size_t)g * a.out_rec + col;
             if (a.nsplit == 1) *o = v;
             else atomicAdd(o, v);
         }
@@ -446,31 +454,58 @@ struct KsKey {
         THFHE_TRY(rows.grow((size_t)nrows * row_words * sizeof(int32_t)));
         hipLaunchKernelGGL(ks_pad_kernel, dim3((unsigned)nrows), dim3(256), 0, s, raw.as<int32_t>(), nrows, n, row_words, rows.as<int32_t>());
         THFHE_HIP(hipGetLastError());
-        if (single && basebit == 2 && (t == 4 || t == 8) && N == 1024) {   // the shapes sk_keyswitch_mfma_kernel takes
-            const long kchunks = (long)N * t / 8, total = (long)(row_words / 32) * kchunks * 4 * 64 * 4;
-            THFHE_TRY(planes.grow((size_t)total * sizeof(uint32_t)));
-            hipLaunchKernelGGL(sk_ksk_planes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rows.as<int32_t>(), row_words, t, kchunks,
-                               total, planes.as<uint32_t>());
-            THFHE_HIP(hipGetLastError());
-        }
+        if (single && basebit == 2 && (t == 4 || t == 8) && N == 1024) THFHE_TRY(build_planes(s));   // the shapes sk_keyswitch_mfma_kernel takes
         THFHE_HIP(hipStreamSynchronize(s));   // before `raw` is freed
         return THFHE_OK;
     }
 
-    // the arguments of a key switch of `samples` records of N + 1 words, one rotation each; CCS / KMS layouts and the MUX combine set their fields
+    // The LWE -> TLWE packing key ([n_lwe][t][base-1][2 N_ring] words: TLWE samples (alpha, beta)) as a single-key table: rows of
+    // row_words = 2 N_ring, output "dimension" n = 2 N_ring (b is added at word N_ring: KsArgs::b_col), input coordinates padded with rows
+    // of zeros to N = n_pad, a multiple of 128 -- the matrix-core kernel's chunking (and the plain kernel's coordinate ranges) need it, and a
+    // zero mask word past n_lwe has only zero digits.  Planes for 2-bit digits, t = 4 or 8.  Replaces any earlier key; on failure the key
+    // is left empty (n = 0).
+    int upload_pack(const int32_t *pk, int n_lwe, int t_, int basebit_, int N_ring, hipStream_t s) {
+        n = 0;
+        planes = DevBuf();
+        const int n_pad = 128 * ((n_lwe + 127) / 128);
+        const size_t per_coord = (size_t)t_ * ((1 << basebit_) - 1) * 2 * N_ring;   // words of one coordinate's rows
+        THFHE_TRY(rows.grow((size_t)n_pad * per_coord * sizeof(int32_t)));
+        THFHE_HIP(hipMemcpyAsync(rows.as<int32_t>(), pk, (size_t)n_lwe * per_coord * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (n_pad > n_lwe)
+            THFHE_HIP(hipMemsetAsync(rows.as<int32_t>() + (size_t)n_lwe * per_coord, 0, (size_t)(n_pad - n_lwe) * per_coord * sizeof(int32_t), s));
+        t = t_, basebit = basebit_, parties = 1, N = n_pad, row_words = 2 * N_ring, single = true;
+        if (basebit == 2 && (t == 4 || t == 8)) THFHE_TRY(build_planes(s));
+        THFHE_HIP(hipStreamSynchronize(s));   // before the caller's host key may go
+        n = 2 * N_ring;
+        return THFHE_OK;
+    }
+
+    // the int8 planes of sk_keyswitch_mfma_kernel from the padded rows (N t / 8 chunks: a multiple of 64 for N = 1024 and for N % 128 == 0)
+    int build_planes(hipStream_t s) {
+        const long kchunks = (long)N * t / 8, total = (long)(row_words / 32) * kchunks * 4 * 64 * 4;
+        THFHE_TRY(planes.grow((size_t)total * sizeof(uint32_t)));
+        hipLaunchKernelGGL(sk_ksk_planes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rows.as<int32_t>(), row_words, t, kchunks,
+                           total, planes.as<uint32_t>());
+        THFHE_HIP(hipGetLastError());
+        return THFHE_OK;
+    }
+
+    // the arguments of a key switch of `samples` records of N + 1 words, one rotation each; CCS / KMS layouts, the MUX combine and the
+    // packing key set their fields
     KsArgs args(const int32_t *u, int32_t *out, long samples) const {
-        return KsArgs{rows.as<int32_t>(), u, out, samples, n, t, basebit, parties, row_words, N, N + 1, 0, 1};
+        return KsArgs{rows.as<int32_t>(), u, out, samples, n, t, basebit, parties, row_words, N, N + 1, 0, 1, parties * n + 1, n};
     }
 };
 
-// the key switch of a.samples samples into a.out: matrix cores where the key has planes, else the staged kernel where its shape allows,
-// else the plain kernel with the coordinates cut into nsplit_plain ranges (N / nsplit_plain <= 2048).  Zeroes a.out where the kernel
-// accumulates into it.
-inline int ks_enqueue(const KsKey &key, const KsArgs &a, int nsplit_plain, hipStream_t stream) {
-    const size_t out_bytes = (size_t)a.samples * ((size_t)a.parties * a.n + 1) * sizeof(int32_t);
-    if (key.planes.bytes() && a.samples >= kKsMfmaMinSamples) {
+// the key switch of a.samples samples into a.out: matrix cores where the key has planes (from mfma_min samples on), else the staged
+// kernel where its shape allows, else the plain kernel with the coordinates cut into nsplit_plain ranges (N / nsplit_plain <= 2048).
+// Zeroes a.out where the kernel accumulates into it.
+inline int ks_enqueue(const KsKey &key, const KsArgs &a, int nsplit_plain, hipStream_t stream, long mfma_min = kKsMfmaMinSamples) {
+    const size_t out_bytes = (size_t)a.samples * a.out_rec * sizeof(int32_t);
+    if (key.planes.bytes() && a.samples >= mfma_min) {
         // 256-gate x 32-word tiles; the chunks are cut into nsplit ranges until the grid has at least 1 024 workgroups (4 096 gates, n = 630: 16 x 20 x 4)
-        KSMArgs k{key.planes.as<ks_i32x4>(), a.u, a.out, a.samples, a.rot_per_gate, a.n, a.t, a.N * a.t / 8, a.row_words / 32, (int)((a.samples + 255) / 256), 1};
+        KSMArgs k{key.planes.as<ks_i32x4>(), a.u, a.out, a.samples, a.u_rec, a.out_rec, a.b_col, a.rot_per_gate, a.n, a.t, a.N * a.t / 8, a.row_words / 32,
+                  (int)((a.samples + 255) / 256), 1};
         while (k.nsplit < 8 && (long)k.gtiles * k.wtiles * k.nsplit < 1024) k.nsplit *= 2;
         if (k.nsplit > 1) THFHE_HIP(hipMemsetAsync(a.out, 0, out_bytes, stream));
         const dim3 grid((unsigned)((long)k.gtiles * k.wtiles * k.nsplit)), block(256);
@@ -516,7 +551,7 @@ inline int ks_enqueue(const KsKey &key, const KsArgs &a, int nsplit_plain, hipSt
     case W: hipLaunchKernelGGL((ks_plain_kernel<X4, X2>), grid, block, 0, stream, a, nsplit_plain); break;
         THFHE_KS_CASE(2, 0, 1) THFHE_KS_CASE(4, 1, 0) THFHE_KS_CASE(6, 1, 1) THFHE_KS_CASE(8, 2, 0) THFHE_KS_CASE(10, 2, 1)
         THFHE_KS_CASE(12, 3, 0) THFHE_KS_CASE(14, 3, 1) THFHE_KS_CASE(16, 4, 0) THFHE_KS_CASE(18, 4, 1) THFHE_KS_CASE(20, 5, 0)
-        THFHE_KS_CASE(22, 5, 1)
+        THFHE_KS_CASE(22, 5, 1) THFHE_KS_CASE(32, 8, 0)   // 32: the packing key's rows of 2N = 2048 words
 #undef THFHE_KS_CASE
     default: return thfhe_fail(THFHE_E_UNSUPPORTED, "LWE dimension n too large for the key-switch kernel (n <= 1407)");
     }

@@ -7,6 +7,10 @@
 // The product is the blind-rotate engine's split-limb FP64 transform with the roles swapped: the small integer polynomial
 // (the key share, |s| <= 2^9) is transformed once per call, every ciphertext mask is split into two balanced 16-bit limbs
 // (two forward, two inverse transforms per ciphertext, one wave each).  |sum| <= N 2^9 2^15 = 2^34: inside the exactness bound.
+//   PackLwe               the LWE -> TLWE packing key switch (the reference's TODO at src/Convert.cpp:103):
+//                         m <= N LWE samples of any dimension n -> ONE ring sample whose coefficient i holds sample i's phase.
+//                         Phase 1 is the shared key switch (thfhe_keyswitch.h) with the packing key's 2N-word TLWE rows into
+//                         per-sample T_i; phase 2 (pack_rotate_sum_kernel) sums X^i T_i mod X^N + 1 in integers.
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -17,6 +21,7 @@
 #include "../../include/thfhe_hip.h"
 #include "thfhe_common.h"
 #include "thfhe_devctx.h"
+#include "thfhe_keyswitch.h"
 #include "thfhe_lane.h"
 
 using namespace thfhe;
@@ -110,11 +115,56 @@ __global__ __launch_bounds__(256) void final_decrypt_kernel(const int32_t *__res
     }
 }
 
+// LWE records [count][n + 1] -> [count][n_pad + 1]: the mask padded with zeros (zero digits: no key row), b last
+__global__ __launch_bounds__(256) void pack_pad_lwe_kernel(const int32_t *__restrict__ lwe, int n, int n_pad, long count, int32_t *__restrict__ out) {
+    const long c = blockIdx.x;
+    if (c >= count) return;
+    for (int q = threadIdx.x; q <= n_pad; q += 256)
+        out[c * (n_pad + 1) + q] = q < n ? lwe[c * (n + 1) + q] : q == n_pad ? lwe[c * (n + 1) + n] : 0;
+}
+
+// P_g = sum_{i < m_g} X^i T_{g m + i} mod X^N + 1 for both polynomials of the 2N-word records T (alpha: words [0, N), beta: [N, 2N)).
+// grid = (outputs, 2N / 64): block (g, w) owns words [64 w, 64 w + 64) of output g; its 16 waves take the rows i = wave (mod 16), lane
+// = coefficient, and meet in LDS.  Coefficient c of X^i f is f[c - i] for c >= i and -f[c - i + N] below: integer sums, no atomics.
+__global__ __launch_bounds__(1024) void pack_rotate_sum_kernel(const int32_t *__restrict__ T, long count, int m, int N, int32_t *__restrict__ out_a,
+                                                               int32_t *__restrict__ out_b) {
+    __shared__ uint32_t sRed[16][64];
+    const long g = blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int word = (int)blockIdx.y * 64 + lane;
+    const int poly = word >= N, c = word - poly * N;
+    const long row0 = g * m;
+    const int mg = (int)(count - row0 < m ? count - row0 : m);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(T) + (size_t)row0 * 2 * N + (size_t)poly * N;
+    uint32_t acc = 0;
+#pragma unroll 8
+    for (int i = wave; i < mg; i += 16) {
+        const uint32_t *row = src + (size_t)i * 2 * N;
+        acc += c >= i ? row[c - i] : 0u - row[c - i + N];
+    }
+    sRed[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int w = 0; w < 16; w++) v += sRed[w][lane];
+        (poly ? out_b : out_a)[g * N + c] = (int32_t)v;
+    }
+}
+
+// below this many samples the packing key switch runs the plain kernel (rows of 2N words, coordinates in ranges of 64); from here on the
+// matrix cores, whose cost up to 256 samples is about one pass over the planes (measured, SK-128, whole calls: 4 samples 0.096 ms plain /
+// 0.095 matrix cores, 8 0.107 / 0.103, 16 0.120 / 0.103, 31 0.176 / 0.108)
+constexpr long kPackMfmaMinSamples = 8;
+
 }  // namespace
 
 struct THFHE_INTERNAL thfhe_poly_ctx : DevCtx {
     DevBuf d_spec, d_flag;
     DevBuf d_buf[4];
+    KsKey pk;        // the packing key (thfhe_pack_key_set)
+    int pk_n = 0;    // its LWE dimension; 0: no key
+    DevBuf d_pin, d_pt;   // padded LWE input, per-sample T_i
 };
 
 extern "C" {
@@ -199,6 +249,50 @@ int thfhe_final_decrypt(thfhe_poly_ctx *c, const int32_t *tlwe_b, const int32_t 
     THFHE_HIP(hipGetLastError());
     if (result) THFHE_HIP(hipMemcpyAsync(result, c->d_buf[2].as<void>(), bytes, hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipMemcpyAsync(bits, c->d_buf[3].as<void>(), count * 4, hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    return THFHE_OK;
+}
+
+int thfhe_pack_key_set(thfhe_poly_ctx *c, const int32_t *pk, int n, int t, int basebit) {
+    if (!c || !pk) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (n < 1 || t < 1 || basebit < 1 || (long)t * basebit > 32) return thfhe_fail(THFHE_E_INVALID, "packing key: need n >= 1, t >= 1, basebit >= 1, t basebit <= 32");
+    if (basebit > 4) return thfhe_fail(THFHE_E_UNSUPPORTED, "packing key: basebit <= 4");
+    if (n > 2048) return thfhe_fail(THFHE_E_UNSUPPORTED, "packing key: LWE dimension n <= 2048");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    c->pk_n = 0;
+    THFHE_TRY(c->pk.upload_pack(pk, n, t, basebit, 1024, c->stream));
+    c->pk_n = n;
+    return THFHE_OK;
+}
+
+int thfhe_pack_lwe(thfhe_poly_ctx *c, const int32_t *lwe, size_t count, int slots, int32_t *tlwe_a, int32_t *tlwe_b) {
+    if (!c || !lwe || !tlwe_a || !tlwe_b) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (slots < 1 || slots > 1024) return thfhe_fail(THFHE_E_INVALID, "slots must be in 1 .. N");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    if (!c->pk_n) return thfhe_fail(THFHE_E_INVALID, "no packing key set (thfhe_pack_key_set)");
+    if (count == 0) return THFHE_OK;
+    const int n = c->pk_n, n_pad = c->pk.N, N = 1024;
+    const size_t outs = (count + slots - 1) / slots;
+    int rc = c->d_buf[0].grow(count * (n + 1) * 4);
+    if (!rc) rc = c->d_pin.grow(count * (n_pad + 1) * 4);
+    if (!rc) rc = c->d_pt.grow(count * 2 * N * 4);
+    if (!rc) rc = c->d_buf[1].grow(outs * N * 4);
+    if (!rc) rc = c->d_buf[2].grow(outs * N * 4);
+    if (rc) return rc;
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[0].as<void>(), lwe, count * (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(pack_pad_lwe_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, c->d_buf[0].as<int32_t>(), n, n_pad, (long)count,
+                       c->d_pin.as<int32_t>());
+    THFHE_HIP(hipGetLastError());
+    KsArgs k = c->pk.args(c->d_pin.as<int32_t>(), c->d_pt.as<int32_t>(), (long)count);
+    k.out_rec = 2 * N, k.b_col = N;   // (u_rec = n_pad + 1: args' default)
+    THFHE_TRY(ks_enqueue(c->pk, k, n_pad / 64, c->stream, kPackMfmaMinSamples));
+    hipLaunchKernelGGL(pack_rotate_sum_kernel, dim3((unsigned)outs, (unsigned)(2 * N / 64)), dim3(1024), 0, c->stream, c->d_pt.as<int32_t>(), (long)count,
+                       slots, N, c->d_buf[1].as<int32_t>(), c->d_buf[2].as<int32_t>());
+    THFHE_HIP(hipGetLastError());
+    THFHE_HIP(hipMemcpyAsync(tlwe_a, c->d_buf[1].as<void>(), outs * N * 4, hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(tlwe_b, c->d_buf[2].as<void>(), outs * N * 4, hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }

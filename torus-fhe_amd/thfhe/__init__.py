@@ -183,6 +183,8 @@ SIGNATURES = {
     "thfhe_tlwe_from_lwe": (C.c_int, [_vp, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_partial_decrypt": (C.c_int, [_vp, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_final_decrypt": (C.c_int, [_vp, _i32p, _i32p, C.c_int, _i32p, _i32p, C.c_size_t]),
+    "thfhe_pack_key_set": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_int]),
+    "thfhe_pack_lwe": (C.c_int, [_vp, _i32p, C.c_size_t, C.c_int, _i32p, _i32p]),
     "thfhe_kms_ctx_create": (C.c_int, [_vp, _i64p, _i32p, C.c_int, C.POINTER(_vp)]),
     "thfhe_kms_ctx_destroy": (None, [_vp]),
     "thfhe_kms_tlev_rotate": (C.c_int, [_vp, C.c_int, _i32p, _i64p, C.c_size_t]),

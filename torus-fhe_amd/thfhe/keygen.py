@@ -75,6 +75,32 @@ def gen_keyswitch_key(rng, in_key, out_key, t, basebit, sigma):
     return ksk
 
 
+def gen_pack_key(rng, lwe_key, tlwe_key, t, basebit, sigma, chunk=2048):
+    """The LWE -> TLWE packing key -> int32[n][t][2^basebit - 1][2][N]: row (j, p, v) is the TLWE sample
+    (alpha, beta) under the ring key z = tlwe_key with alpha uniform and beta = alpha (*) z + e + v s_j 2^(32 - (p+1) basebit) on the
+    constant coefficient, e Gaussian of standard deviation `sigma` on all N coefficients.  The key noise reaches every packed slot
+    m n t times: use the ring's bootstrapping-key sigma (SIGMAS[set]["bk"]), not the LWE key switch's.  Exact products through
+    polymul_small32, `chunk` rows at a time."""
+    s = np.asarray(lwe_key, np.int64)
+    z = np.asarray(tlwe_key, np.int32)
+    n, N, R = s.shape[0], z.shape[0], (1 << basebit) - 1
+    assert t * basebit <= 32
+    rows = n * t * R
+    pk = np.empty((rows, 2, N), np.int32)
+    j = np.repeat(np.arange(n), t * R)
+    p = np.tile(np.repeat(np.arange(t), R), n)
+    v = np.tile(np.arange(1, R + 1), n * t)
+    msg = (v * s[j]) << (32 - (p + 1) * basebit)
+    for r0 in range(0, rows, chunk):
+        r1 = min(rows, r0 + chunk)
+        alpha = rng.integers(-2**31, 2**31, size=(r1 - r0, N), dtype=np.int64).astype(np.int32)
+        beta = polymul_small32(alpha, z).astype(np.int64) + dtot32(rng.standard_normal((r1 - r0, N)) * sigma)
+        beta[:, 0] += msg[r0:r1]
+        pk[r0:r1, 0] = alpha
+        pk[r0:r1, 1] = beta.astype(np.uint32).view(np.int32)
+    return pk.reshape(n, t, R, 2, N)
+
+
 def seed_seq_generate(seeds, count):
     """std::seed_seq(seeds).generate: `count` 32-bit words ([rand.util.seedseq], as libstdc++ implements it)."""
     v = [int(x) & 0xFFFFFFFF for x in seeds]
