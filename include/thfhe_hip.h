@@ -308,6 +308,52 @@ int thfhe_final_decrypt(thfhe_poly_ctx *ctx, const int32_t *tlwe_b, const int32_
 int thfhe_pack_key_set(thfhe_poly_ctx *ctx, const int32_t *pk, int n, int t, int basebit);
 int thfhe_pack_lwe(thfhe_poly_ctx *ctx, const int32_t *lwe /*[count][n+1]*/, size_t count, int slots, int32_t *tlwe_a, int32_t *tlwe_b /*[ceil(count/slots)][N]*/);
 
+/* ---- encrypted lookup tables and two-digit tree PBS (single key, N = 1024, k = 1).  Phase convention everywhere: beta - alpha (*) z.
+ *
+ * thfhe_lut_bootstrap_enc(_wo_keyswitch): the contract of thfhe_lut_bootstrap(_wo_keyswitch) with ENCRYPTED tables.  Table t is a TLWE sample
+ *   (tv_a[t], tv_b[t]) under the context's bootstrapping ring key, whose phase is a test vector in the layout of thfhe_lut_bootstrap (e.g.
+ *   thfhe.lut.encrypt_table, or an output of thfhe_pack_boxes).  tv_a, tv_b: HOST int32[n_luts][N], 1 <= n_luts <= 262 144 (every sample may bring
+ *   its own table).  Accumulator (X^{-barb} * tv_a[t], X^{-barb} * tv_b[t]), t = lut_index[s], or table 0 when lut_index is NULL.  Prologue, theta in
+ *   {1, 2, 4}, the theta-rounded mod-switch, the skip of mask words with bara == 0, extraction at coefficients 0 .. theta-1, the key switch, the
+ *   output shapes and the argument checks (on the host, before the context is looked at) are those of thfhe_lut_bootstrap.  tv_a = 0, tv_b = tv gives
+ *   the words of thfhe_lut_bootstrap(tv).  The table's noise adds to the output's.
+ *
+ * thfhe_pack_boxes: p LWE samples -> ONE encrypted test vector.  lwe: HOST int32[count][n+1] (n = the packing key's dimension), p a power of two,
+ *   2 <= p <= N/2, count a multiple of p -> tlwe_a, tlwe_b HOST int32[count / p][N].  With T_i the per-sample key-switch result of thfhe_pack_lwe,
+ *   output g = U(X) * sum_{i < p} X^(i N/p) T_(g p + i) mod X^N + 1 on both polynomials, U(X) = X^(-N/(2p)) (1 + X + ... + X^(N/p - 1)): candidate i
+ *   fills the N/p coefficients centred on i N/p, the lower half-box of candidate 0 wraps to the top negated -- the layout of thfhe.lut.test_vector at
+ *   theta = 1.  Noiseless trivial inputs (a = 0, b = v_i) under an all-zero key give exactly (0, test_vector(v, p)).  Bit-exact: integer sums mod 2^32.
+ *   THFHE_E_INVALID without a key, for a bad p, or a count that is not a multiple of p.
+ *
+ * thfhe_tree_lut_bootstrap: out[s] = f_table[s](hi, lo) for two encrypted digits, as level-1 many-LUT rotations on `lo`, box packing, and one
+ *   rotation of the packed (encrypted) table on `hi`; nothing between the stages visits the host.
+ *   spec_lo: 1 .. 3 weighted inputs lo0..2, theta1 in {1, 2, 4}.  spec_hi: inputs hi0..2, theta must be 1.  p_hi: a power of two, 2 <= p_hi <= N/2,
+ *   theta1 | p_hi; R = p_hi / theta1.  tv1: HOST int32[n_tables][R][N], row r = the many-LUT test vector of f(r theta1 + j, .), j < theta1 (e.g.
+ *   thfhe.lut.tree_test_vectors); 1 <= n_tables, n_tables R <= 262 144.  table_index: HOST int32[count] or NULL (table 0).  lo*, hi*: HOST records
+ *   int32[count][n+1]; out: HOST int32[count][n+1], which must not alias an input.
+ *   The result equals, word for word, thfhe_lut_bootstrap(spec_lo, tv1 rows, lut_index = table R + r) on every sample's inputs repeated R times ->
+ *   thfhe_pack_boxes(p = p_hi) -> thfhe_lut_bootstrap_enc(spec_hi, table s for sample s).
+ *   ctx_pack must hold a packing key (thfhe_pack_key_set) from the gate key set's LWE key to its BOOTSTRAPPING RING key -- the key the encrypted
+ *   table must be under for the second rotation (thfhe.keygen.gen_pack_key(rng, K.lwe_key, K.rlwe_key, t, basebit, sigma_bk)).  The library cannot
+ *   check which ring key a packing key targets: with any other key the call succeeds and the results do not decrypt.
+ *   THFHE_E_INVALID, before any device work: null pointers, an invalid spec, spec_hi theta != 1, a bad p_hi, theta1 not dividing p_hi, n_tables or a
+ *   table_index entry out of range (these on the host, before the contexts are looked at); then the two contexts on different devices, no packing
+ *   key, a packing key whose n differs from the gate context's.
+ *   The batch runs in slices of at most max_candidates / p_hi samples (thfhe_set_tree_slice, default 65 536 candidates, 1 .. 2^20): the packing
+ *   scratch is 8 KiB per candidate.  All work of a call is enqueued on the gate context's stream while both contexts are locked; the packing
+ *   context's own stream is drained first.  With profiling on, thfhe_last_timings gives ms[0] = level 1, ms[1] = packing, ms[2] = level 2 of the
+ *   LAST slice and ms[3] = the whole call. */
+int thfhe_lut_bootstrap_enc(thfhe_ctx *ctx, const thfhe_lut_spec *spec, const int32_t *tv_a, const int32_t *tv_b, int n_luts, const int32_t *lut_index,
+                            const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count);
+int thfhe_lut_bootstrap_enc_wo_keyswitch(thfhe_ctx *ctx, const thfhe_lut_spec *spec, const int32_t *tv_a, const int32_t *tv_b, int n_luts,
+                                         const int32_t *lut_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1,
+                                         size_t count);
+int thfhe_pack_boxes(thfhe_poly_ctx *ctx, const int32_t *lwe /*[count][n+1]*/, size_t count, int p, int32_t *tlwe_a, int32_t *tlwe_b /*[count/p][N]*/);
+int thfhe_tree_lut_bootstrap(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi,
+                             const int32_t *tv1, int n_tables, const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2,
+                             const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count);
+int thfhe_set_tree_slice(thfhe_ctx *ctx, size_t max_candidates);
+
 /* ---- multi-key KEY GENERATION arithmetic on the device --------------------------------------------------------------
  * Exact multiply-accumulate of small-coefficient polynomials with torus polynomials, the only non-trivial arithmetic of
  *   tgsw_encrypt_3gen                3-gen-mk-tfhe/src/tgsw_3gen.jl:41-95     part_1..4 = r1 (*) B, r2 (*) B, r2 (*) A, r1 (*) A  (+ m g + e)

@@ -22,14 +22,14 @@ inline int ilog2(int x) {
 
 // Host-side checks of a programmable-bootstrap call, before any device work: null pointers first (no context needed), then the spec and
 // every lut_index entry (the kernel cannot report an index out of range).  Shared by thfhe_lut_bootstrap (tv int32) and
-// thfhe_mk_lut_bootstrap (tv int64).
+// thfhe_mk_lut_bootstrap (tv int64); thfhe_lut_bootstrap_enc raises the table cap (max_luts).
 inline int lut_validate(const thfhe_lut_spec *sp, const void *tv, int n_luts, const int32_t *lut_index, const int32_t *in0, const int32_t *in1,
-                        const int32_t *in2, const int32_t *out, size_t count) {
+                        const int32_t *in2, const int32_t *out, size_t count, int max_luts = 1024) {
     if (!sp || !tv || !in0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (sp->n_inputs < 1 || sp->n_inputs > 3) return thfhe_fail(THFHE_E_INVALID, "lut spec: n_inputs must be 1, 2 or 3");
     if ((sp->n_inputs > 1 && !in1) || (sp->n_inputs > 2 && !in2)) return thfhe_fail(THFHE_E_INVALID, "null operand: the spec names more inputs");
     if (sp->theta != 1 && sp->theta != 2 && sp->theta != 4) return thfhe_fail(THFHE_E_INVALID, "lut spec: theta must be 1, 2 or 4");
-    if (n_luts < 1 || n_luts > 1024) return thfhe_fail(THFHE_E_INVALID, "n_luts must be 1 .. 1024");
+    if (n_luts < 1 || n_luts > max_luts) return thfhe_fail(THFHE_E_INVALID, max_luts == 1024 ? "n_luts must be 1 .. 1024" : "n_luts must be 1 .. 262144");
     if (count > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "count too large");
     if (lut_index)
         for (size_t g = 0; g < count; g++)

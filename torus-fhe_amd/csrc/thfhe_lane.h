@@ -646,6 +646,18 @@ THFHE_FN void acc_init_tv16(int lane, int32_t *acc_mask, int32_t *acc_body, int 
         acc_body[q] = (e & 1024) ? (int32_t)(0u - (uint32_t)v) : v;
     }
 }
+// encrypted test vector: acc = (X^{-barb} * tv_a, X^{-barb} * tv_b), a TLWE sample of 2 x N = 1024 Torus32 words in global
+// memory (8 KiB, read once, from L2); the index and sign map of acc_init_tv16 on both polynomials
+THFHE_FN void acc_init_tlwe16(int lane, int32_t *acc_mask, int32_t *acc_body, int barb, const int32_t *tv_a, const int32_t *tv_b) {
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        int q = lane + 64 * m;
+        int e = (q + barb) & 2047;
+        const int32_t va = tv_a[e & 1023], vb = tv_b[e & 1023];
+        acc_mask[q] = (e & 1024) ? (int32_t)(0u - (uint32_t)va) : va;
+        acc_body[q] = (e & 1024) ? (int32_t)(0u - (uint32_t)vb) : vb;
+    }
+}
 // sample extraction at coefficient j (0 <= j < N): a'_i = a_{j-i} for i <= j, a'_i = -a_{N+j-i} for i > j, b = body_j
 THFHE_FN void extract_at16(int lane, const int32_t *acc_mask, const int32_t *acc_body, int j, int32_t *out) {
 #pragma unroll

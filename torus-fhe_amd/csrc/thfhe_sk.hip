@@ -17,6 +17,7 @@
 //   sk_linear_kernel          NOT / COPY (J/gates.jl:76-79)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <memory>
 #include <mutex>
@@ -30,6 +31,7 @@
 #include "thfhe_devctx.h"
 #include "thfhe_keyswitch.h"
 #include "thfhe_lane.h"
+#include "thfhe_pack.h"
 
 using namespace thfhe;
 
@@ -107,6 +109,34 @@ __global__ __launch_bounds__(256) void sk_lut_prologue_kernel(const int32_t *__r
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// tree-PBS prologue (thfhe_tree_lut_bootstrap): sk_lut_prologue_kernel with every sample's record serving `reps` jobs.  Job
+// s * reps + r reads sample s and looks up table base(s) * reps + r, base(s) = table_index[s], or s (identity: level 2, the sample's own
+// packed table), or 0.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sk_tree_prologue_kernel(const int32_t *__restrict__ in0, const int32_t *__restrict__ in1,
+                                                                const int32_t *__restrict__ in2, int n_inputs, int32_t w0, int32_t w1, int32_t w2,
+                                                                int32_t bias, int log2_theta, int n, int n_pad, int log2_2n, long jobs, int reps,
+                                                                const int32_t *__restrict__ table_index, int identity, int32_t *__restrict__ bara,
+                                                                int32_t *__restrict__ barb, int32_t *__restrict__ lut_idx) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    for (long job = blockIdx.y; job < jobs; job += gridDim.y) {
+        const long s = job / reps;
+        const size_t off = (size_t)s * (n + 1) + i;
+        uint32_t v = (uint32_t)w0 * (uint32_t)in0[off];
+        if (n_inputs > 1) v += (uint32_t)w1 * (uint32_t)in1[off];
+        if (n_inputs > 2) v += (uint32_t)w2 * (uint32_t)in2[off];
+        if (i == n) v += (uint32_t)bias;
+        const int32_t bar = (int32_t)((uint32_t)modswitch2n((int32_t)v, log2_2n - log2_theta) << log2_theta);
+        if (i == n) {
+            barb[job] = bar;
+            const long base = table_index ? table_index[s] : (identity ? s : 0);
+            lut_idx[job] = (int32_t)(base * reps + (job - s * reps));
+        } else bara[job * n_pad + i] = bar;
+    }
+}
+
 THFHE_STAMP_STORAGE
 
 // arguments of the blind-rotate kernels
@@ -123,7 +153,12 @@ struct BRArgs {
     const int32_t *tv;       // [n_luts][N]
     const int32_t *lut_idx;  // [jobs] test vector of each job, or null: table 0
     int theta;               // 1, 2 or 4
+    // encrypted-table kernels only (LUT == kLutEnc): the tables are TLWE samples (tv_a, tv) under the ring key, accumulator X^{-barb} * (tv_a, tv)
+    const int32_t *tv_a;     // [n_luts][N] masks; `tv` holds the bodies
 };
+
+// what a blind-rotate instantiation starts from: the gates' constant test vector, a plaintext table, an encrypted table (4.11)
+constexpr int kGate = 0, kLut = 1, kLutEnc = 2;
 
 // ------------------------------------------------------------------------------------------------------
 // blind rotate + extract, throughput kernel ("LDS ring", second generation).
@@ -171,8 +206,9 @@ struct BRArgs {
 // W = waves (= jobs) per workgroup.  W = 8 is the throughput shape described above.  W = 4 (one wave per SIMD, 92 KiB of LDS, each wave
 // brings TWO slices of a chunk) is the shape for batches that cannot give every CU eight jobs (<= 1024 rotations): a wave alone on its
 // SIMD issues at ~87 % of what a pair reaches together (tools/probes/issue_probe.hip), so four jobs finish much sooner than eight.
-// LUT = programmable bootstrap: the accumulator starts from a test vector and theta coefficients are extracted; the CMux loop is the same code.
-template <int L, int V = 1, int W = 8, bool LUT = false>
+// LUT = kLut, kLutEnc: programmable bootstrap, the accumulator starts from a test vector (kLutEnc: from a TLWE sample, mask included) and theta
+// coefficients are extracted; the CMux loop is the same code.
+template <int L, int V = 1, int W = 8, int LUT = kGate>
 __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_kernel(BRArgs a) {
     __shared__ __attribute__((aligned(4096))) int32_t sAcc[W][2048];   // rotated_digits_z ORs byte offsets into the polynomial base
     __shared__ cplx sX[W][kXbufSlots];
@@ -191,7 +227,10 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
     const uniform_i32_ptr bara = as_uniform(a.bara + (has_job ? job : 0) * a.n_pad);   // job is wave-uniform: scalar loads
     const int Bgbit = a.Bgbit;
     if (has_job) {
-        if constexpr (LUT) acc_init_tv16(lane, acc, acc + 1024, a.barb[job], a.tv + (a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0));
+        if constexpr (LUT == kLutEnc) {
+            const size_t t = a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0;
+            acc_init_tlwe16(lane, acc, acc + 1024, a.barb[job], a.tv_a + t, a.tv + t);
+        } else if constexpr (LUT) acc_init_tv16(lane, acc, acc + 1024, a.barb[job], a.tv + (a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0));
         else acc_init16(lane, acc, acc + 1024, a.barb[job], a.mu);
     }
 
@@ -346,7 +385,7 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
 __device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ void pin() { asm volatile("" ::: "memory"); }  // memory operations do not move across this point
 
-template <int L, int PACE = 1, bool LUT = false>
+template <int L, int PACE = 1, int LUT = kGate>
 __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) {
     constexpr int ROWS = 2 * L;
     __shared__ __attribute__((aligned(4096))) int32_t sAcc[2048];
@@ -360,7 +399,10 @@ __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) 
     const uniform_i32_ptr bara = as_uniform(a.bara + job * a.n_pad);
     const int Bgbit = a.Bgbit;
     if (wave == 0) {
-        if constexpr (LUT) acc_init_tv16(lane, sAcc, sAcc + 1024, a.barb[job], a.tv + (a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0));
+        if constexpr (LUT == kLutEnc) {
+            const size_t t = a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0;
+            acc_init_tlwe16(lane, sAcc, sAcc + 1024, a.barb[job], a.tv_a + t, a.tv + t);
+        } else if constexpr (LUT) acc_init_tv16(lane, sAcc, sAcc + 1024, a.barb[job], a.tv + (a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0));
         else acc_init16(lane, sAcc, sAcc + 1024, a.barb[job], a.mu);
     }
     const int c = (wave >> 1) & 1, h = wave & 1, half = wave >> 2, r0 = half * L;  // role in M: rows r0 .. r0+L-1 of (column c, limb h)
@@ -492,6 +534,10 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     int n_pad = 0;
     DevBuf d_bara, d_barb, d_u;
     DevBuf d_tv, d_lut_idx;   // programmable bootstrap: test-vector table and per-sample table index (grow-only)
+    DevBuf d_tva;             // encrypted tables (thfhe_lut_bootstrap_enc): the masks; d_tv holds the bodies
+    // tree PBS (thfhe_tree_lut_bootstrap): a slice's table indices, key-switched level-1 candidates and packed tables (mask, body)
+    DevBuf d_tree_tab, d_tree_lwe, d_tree_a, d_tree_b;
+    size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate)
     // staging for the host-buffer API
     Stage stage;
     // gate-DAG executor: wire table and index tables (grow-only, reused by every thfhe_dag_run on this context)
@@ -501,6 +547,8 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
 
 namespace {
 
+constexpr int kMaxEncLuts = 1 << 18;   // encrypted tables per call (2 GiB of TLWE samples): every sample may bring its own
+
 int ensure_workspace(thfhe_ctx *c, size_t jobs) {
     int rc = c->d_bara.grow(jobs * c->n_pad * sizeof(int32_t));
     if (!rc) rc = c->d_barb.grow(jobs * sizeof(int32_t));
@@ -508,8 +556,8 @@ int ensure_workspace(thfhe_ctx *c, size_t jobs) {
     return rc;
 }
 
-// One launch of `a.jobs` rotations on one kernel shape.  LUT: the programmable-bootstrap instantiation (the developer variants are gate-only).
-template <int L, bool LUT>
+// One launch of `a.jobs` rotations on one kernel shape.  LUT: kGate, or a programmable-bootstrap instantiation (the developer variants are gate-only).
+template <int L, int LUT>
 void launch_coop(const BRArgs &a, hipStream_t s) {
 #ifdef THFHE_VARIANTS
     static const int pace = std::getenv("THFHE_COOP_PACE") ? std::atoi(std::getenv("THFHE_COOP_PACE")) : 1;
@@ -519,11 +567,11 @@ void launch_coop(const BRArgs &a, hipStream_t s) {
 #endif
     hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 1, LUT>), dim3((unsigned)a.jobs), dim3(512), 0, s, a);
 }
-template <int L, bool LUT>
+template <int L, int LUT>
 void launch_ring4(const BRArgs &a, hipStream_t s) {
     hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 1, 4, LUT>), dim3((unsigned)((a.jobs + 3) / 4)), dim3(256), 0, s, a);
 }
-template <int L, bool LUT>
+template <int L, int LUT>
 void launch_ring8(const BRArgs &a, hipStream_t s) {
     const dim3 grid((unsigned)((a.jobs + 7) / 8)), block(512);
 #ifdef THFHE_VARIANTS  // developer A/B builds only: 8 = first transpose through the LDS (variant "r")
@@ -541,7 +589,7 @@ void launch_ring8(const BRArgs &a, hipStream_t s) {
 // ring4_max (1 024), four-wave ring + one cooperative round up to ring4_max + 256 (12.9 ms), else one more eight-wave round.
 // (3 072 rotations: 30.1 ms as one launch of 384 eight-wave workgroups, 24.8 ms as 2 048 + 1 024.)  The pieces are independent jobs
 // on disjoint slices of the same arrays, launched back to back on the context's stream.
-template <int L, bool LUT>
+template <int L, int LUT>
 void launch_br(const BRArgs &a, hipStream_t s, int coop_max, int ring4_max) {
     auto piece = [&](long first, long count) {
         BRArgs b = a;
@@ -564,7 +612,7 @@ void launch_br(const BRArgs &a, hipStream_t s, int coop_max, int ring4_max) {
 }
 
 // the blind rotations of `a` on the kernel shapes of launch_br, for the context's decomposition length
-template <bool LUT>
+template <int LUT>
 int launch_rotations(thfhe_ctx *c, const BRArgs &a) {
     switch (c->p.l) {
     case 1: launch_br<1, LUT>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
@@ -589,16 +637,17 @@ int enqueue_rotations(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1
                        ilog2(2 * c->p.N), (long)jobs, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
     BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, n, c->n_pad, c->p.Bgbit, mu};
-    rc = launch_rotations<false>(c, a);
+    rc = launch_rotations<kGate>(c, a);
     if (rc) return rc;
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
 
-// programmable bootstrap of `count` samples (lut prologue + LUT blind rotations) into c->d_u: count x theta records of N+1 words
+// programmable bootstrap of `count` samples (lut prologue + LUT blind rotations) into c->d_u: count x theta records of N+1 words;
+// d_tva: the masks of encrypted tables (d_tv their bodies), or null: plaintext tables
 int enqueue_lut_rotations(thfhe_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0, const int32_t *d1, const int32_t *d2, size_t count,
-                          const int32_t *d_tv, const int32_t *d_idx) {
+                          const int32_t *d_tv, const int32_t *d_idx, const int32_t *d_tva = nullptr) {
     int rc = ensure_workspace(c, count);
     if (!rc) rc = c->d_u.grow(count * sp.theta * 1025 * sizeof(int32_t));
     if (rc) return rc;
@@ -609,8 +658,8 @@ int enqueue_lut_rotations(thfhe_ctx *c, const thfhe_lut_spec &sp, const int32_t 
                        sp.bias, ilog2(sp.theta), n, c->n_pad, ilog2(2 * c->p.N), (long)count, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
     BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)count, n, c->n_pad, c->p.Bgbit,
-             0, d_tv, d_idx, sp.theta};
-    rc = launch_rotations<true>(c, a);
+             0, d_tv, d_idx, sp.theta, d_tva};
+    rc = d_tva ? launch_rotations<kLutEnc>(c, a) : launch_rotations<kLut>(c, a);
     if (rc) return rc;
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
     THFHE_HIP(hipGetLastError());
@@ -658,10 +707,12 @@ int dag_gate_class(thfhe_ctx *c, int cls, const int32_t *d_ops, size_t n) {
     return r;
 }
 
-// thfhe_lut_bootstrap (keyswitch) / thfhe_lut_bootstrap_wo_keyswitch: out = count x theta records of n+1 (resp. N+1) words
+// thfhe_lut_bootstrap (keyswitch) / thfhe_lut_bootstrap_wo_keyswitch: out = count x theta records of n+1 (resp. N+1) words.
+// enc: thfhe_lut_bootstrap_enc(_wo_keyswitch), the tables are TLWE samples (tv_a, tv) and up to kMaxEncLuts of them
 int lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
-                  const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch) {
-    int rc = lut_validate(sp, tv, n_luts, lut_index, in0, in1, in2, out, count);
+                  const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch, bool enc = false, const int32_t *tv_a = nullptr) {
+    if (enc && !tv_a) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    int rc = lut_validate(sp, tv, n_luts, lut_index, in0, in1, in2, out, count, enc ? kMaxEncLuts : 1024);
     if (rc) return rc;
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     if (count == 0) return THFHE_OK;
@@ -672,12 +723,14 @@ int lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv, int
     const size_t stage_words = keyswitch ? outs * (c->p.n + 1) : in_words;   // the key switch writes count x theta records into stage.out
     return ctx_staged(c, stage_words, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, {in_bytes, in_bytes, in_bytes}, [&] {
         int r = c->d_tv.grow((size_t)n_luts * 1024 * sizeof(int32_t));
+        if (!r && enc) r = c->d_tva.grow((size_t)n_luts * 1024 * sizeof(int32_t));
         if (!r && lut_index) r = c->d_lut_idx.grow(count * sizeof(int32_t));
         if (r) return r;
         THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if (enc) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int32_t>(), tv_a, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         if (lut_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), lut_index, count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         r = enqueue_lut_rotations(c, s, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), count, c->d_tv.as<int32_t>(),
-                                  lut_index ? c->d_lut_idx.as<int32_t>() : nullptr);
+                                  lut_index ? c->d_lut_idx.as<int32_t>() : nullptr, enc ? c->d_tva.as<int32_t>() : nullptr);
         return r || !keyswitch ? r : enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), outs, 1, true);
     }, keyswitch ? c->stage.out : c->d_u, out, out_bytes);
 }
@@ -859,7 +912,7 @@ int thfhe_dag_run_lut_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs
                                c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
             BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), s.total, n, c->n_pad,
                      c->p.Bgbit, 0, c->d_tv.as<int32_t>(), c->d_lut_idx.as<int32_t>(), theta};
-            int r = launch_rotations<true>(c, a);
+            int r = launch_rotations<kLut>(c, a);
             if (!r) r = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), (size_t)s.total * theta, 1, false);
             return r;
         });
@@ -899,6 +952,115 @@ int thfhe_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *spec, const int32_t 
 int thfhe_lut_bootstrap_wo_keyswitch(thfhe_ctx *c, const thfhe_lut_spec *spec, const int32_t *tv, int n_luts, const int32_t *lut_index,
                                      const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1, size_t count) {
     return lut_bootstrap(c, spec, tv, n_luts, lut_index, in0, in1, in2, out_N1, count, false);
+}
+
+int thfhe_lut_bootstrap_enc(thfhe_ctx *c, const thfhe_lut_spec *spec, const int32_t *tv_a, const int32_t *tv_b, int n_luts, const int32_t *lut_index,
+                            const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count) {
+    return lut_bootstrap(c, spec, tv_b, n_luts, lut_index, in0, in1, in2, out, count, true, true, tv_a);
+}
+
+int thfhe_lut_bootstrap_enc_wo_keyswitch(thfhe_ctx *c, const thfhe_lut_spec *spec, const int32_t *tv_a, const int32_t *tv_b, int n_luts,
+                                         const int32_t *lut_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1,
+                                         size_t count) {
+    return lut_bootstrap(c, spec, tv_b, n_luts, lut_index, in0, in1, in2, out_N1, count, false, true, tv_a);
+}
+
+int thfhe_set_tree_slice(thfhe_ctx *c, size_t max_candidates) {
+    if (!c || max_candidates < 1 || max_candidates > ((size_t)1 << 20)) return thfhe_fail(THFHE_E_INVALID, "slice must be 1 .. 2^20 candidates");
+    std::lock_guard<std::mutex> g(c->mu);
+    c->tree_slice = max_candidates;
+    return THFHE_OK;
+}
+
+// Two-digit tree PBS.  Per slice of S samples, everything on the gate context's stream: level 1 = S R rotations of the plaintext
+// rows tv1[table[s]][r] on the `lo` prologue and the key switch of their S p_hi candidates; the packing context's box packing of the candidates
+// into S encrypted test vectors (pack_boxes_enqueue: it enqueues on the stream it is given); level 2 = S rotations of those tables on the `hi`
+// prologue, extraction at coefficient 0, key switch.  Only the inputs of a slice go up and its S results come down.
+int thfhe_tree_lut_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, const int32_t *tv1,
+                             int n_tables, const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
+                             const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
+    // host checks, before either context is looked at
+    if (!spec_lo || !spec_hi || !tv1 || !lo0 || !hi0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    THFHE_TRY(lut_spec_check(*spec_lo));
+    THFHE_TRY(lut_spec_check(*spec_hi));
+    if ((spec_lo->n_inputs > 1 && !lo1) || (spec_lo->n_inputs > 2 && !lo2) || (spec_hi->n_inputs > 1 && !hi1) || (spec_hi->n_inputs > 2 && !hi2))
+        return thfhe_fail(THFHE_E_INVALID, "null operand: the spec names more inputs");
+    if (spec_hi->theta != 1) return thfhe_fail(THFHE_E_INVALID, "tree: spec_hi theta must be 1 (the packed table holds one function)");
+    if (p_hi < 2 || p_hi > 512 || (p_hi & (p_hi - 1))) return thfhe_fail(THFHE_E_INVALID, "tree: p_hi must be a power of two in 2 .. N/2");
+    if (p_hi % spec_lo->theta) return thfhe_fail(THFHE_E_INVALID, "tree: spec_lo theta must divide p_hi");
+    const int theta1 = spec_lo->theta, R = p_hi / theta1;
+    if (n_tables < 1 || (long)n_tables * R > kMaxEncLuts) return thfhe_fail(THFHE_E_INVALID, "tree: n_tables must be 1 .. 262144 / (p_hi / theta)");
+    if (count > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "count too large");
+    if (table_index)
+        for (size_t g = 0; g < count; g++)
+            if (table_index[g] < 0 || table_index[g] >= n_tables) return thfhe_fail(THFHE_E_INVALID, "table_index out of range (0 .. n_tables-1)");
+    if (!c || !pc) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (pack_ctx_device(pc) != c->device) return thfhe_fail(THFHE_E_INVALID, "tree: the gate context and the packing context must be on the same device");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    std::lock_guard<std::mutex> pg(pack_ctx_mutex(pc));   // always after the gate context's: nothing else takes both
+    const int n = c->p.n, words = n + 1;
+    if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
+    if (pack_key_n(pc) != n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
+    if (count == 0) return THFHE_OK;
+    const thfhe_lut_spec lo = *spec_lo, hi = *spec_hi;
+    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / p_hi));
+    int rc = c->d_tv.grow((size_t)n_tables * R * 1024 * sizeof(int32_t));
+    if (!rc) rc = ensure_workspace(c, S_max * R);
+    if (!rc) rc = c->d_u.grow(S_max * p_hi * 1025 * sizeof(int32_t));
+    if (!rc) rc = c->d_lut_idx.grow(S_max * R * sizeof(int32_t));
+    if (!rc) rc = c->stage.grow(S_max * words);
+    if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_lwe.grow(S_max * p_hi * words * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_a.grow(S_max * 1024 * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_b.grow(S_max * 1024 * sizeof(int32_t));
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle (its calls drain it); from here on its buffers are used on `st`
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv1, (size_t)n_tables * R * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const int log2_2n = ilog2(2 * c->p.N);
+    const int32_t *lo_in[3] = {lo0, lo.n_inputs > 1 ? lo1 : nullptr, lo.n_inputs > 2 ? lo2 : nullptr};
+    const int32_t *hi_in[3] = {hi0, hi.n_inputs > 1 ? hi1 : nullptr, hi.n_inputs > 2 ? hi2 : nullptr};
+    auto prologue = [&](const thfhe_lut_spec &sp, size_t jobs, int reps, const int32_t *d_tab, int identity) {
+        const dim3 pg((unsigned)((n + 1 + 255) / 256), (unsigned)(jobs < 65535 ? jobs : 65535));
+        hipLaunchKernelGGL(sk_tree_prologue_kernel, pg, dim3(256), 0, st, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), sp.n_inputs, sp.weights[0],
+                           sp.weights[1], sp.weights[2], sp.bias, ilog2(sp.theta), n, c->n_pad, log2_2n, (long)jobs, reps, d_tab, identity, c->d_bara.as<int32_t>(),
+                           c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
+    };
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0), J1 = S * R, C = S * p_hi, in_bytes = S * words * sizeof(int32_t);
+        const bool first = s0 == 0, last = s0 + S == count;
+        // ---- level 1 ----
+        for (int q = 0; q < 3; q++)
+            if (lo_in[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), lo_in[q] + s0 * words, in_bytes, hipMemcpyHostToDevice, st));
+        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_tree_tab.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (c->profiling && first) THFHE_HIP(hipEventRecord(c->ev[0], st));
+        prologue(lo, J1, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr, 0);
+        BRArgs a1{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)J1, n, c->n_pad, c->p.Bgbit,
+                  0, c->d_tv.as<int32_t>(), c->d_lut_idx.as<int32_t>(), theta1, nullptr};
+        THFHE_TRY(launch_rotations<kLut>(c, a1));
+        THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->d_tree_lwe.as<int32_t>(), C, 1, false));
+        if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[1], st));
+        // ---- packing: candidate r theta1 + j of sample s is record s p_hi + r theta1 + j, the order the rotations wrote them in ----
+        THFHE_TRY(pack_boxes_enqueue(pc, c->d_tree_lwe.as<int32_t>(), C, p_hi, c->d_tree_a.as<int32_t>(), c->d_tree_b.as<int32_t>(), st));
+        if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[2], st));
+        // ---- level 2: sample s rotates its own packed table ----
+        for (int q = 0; q < 3; q++)
+            if (hi_in[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), hi_in[q] + s0 * words, in_bytes, hipMemcpyHostToDevice, st));
+        prologue(hi, S, 1, nullptr, 1);
+        BRArgs a2{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)S, n, c->n_pad, c->p.Bgbit,
+                  0, c->d_tree_b.as<int32_t>(), c->d_lut_idx.as<int32_t>(), 1, c->d_tree_a.as<int32_t>()};
+        THFHE_TRY(launch_rotations<kLutEnc>(c, a2));
+        THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), S, 1, false));
+        if (c->profiling && last) {
+            THFHE_HIP(hipEventRecord(c->ev[3], st));
+            c->ev_valid = true;
+        }
+        THFHE_HIP(hipGetLastError());
+        THFHE_HIP(hipMemcpyAsync(out + s0 * words, c->stage.out_ptr(), in_bytes, hipMemcpyDeviceToHost, st));
+    }
+    THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
 }
 
 int thfhe_keyswitch(thfhe_ctx *c, const int32_t *in_N1, int32_t *out, size_t count) {

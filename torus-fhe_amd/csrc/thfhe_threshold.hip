@@ -11,6 +11,9 @@
 //                         m <= N LWE samples of any dimension n -> ONE ring sample whose coefficient i holds sample i's phase.
 //                         Phase 1 is the shared key switch (thfhe_keyswitch.h) with the packing key's 2N-word TLWE rows into
 //                         per-sample T_i; phase 2 (pack_rotate_sum_kernel) sums X^i T_i mod X^N + 1 in integers.
+//   PackBoxes             the same key switch into the box layout of a test vector: p samples -> ONE ring sample
+//                         whose box i (the N/p coefficients centred on i N/p) holds sample i's phase on every coefficient -- an
+//                         encrypted test vector for thfhe_lut_bootstrap_enc.  Phase 2 is pack_boxes_kernel.
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -23,6 +26,7 @@
 #include "thfhe_devctx.h"
 #include "thfhe_keyswitch.h"
 #include "thfhe_lane.h"
+#include "thfhe_pack.h"
 
 using namespace thfhe;
 
@@ -152,6 +156,43 @@ __global__ __launch_bounds__(1024) void pack_rotate_sum_kernel(const int32_t *__
     }
 }
 
+// Box packing: output g = U(X) * sum_{i < p} X^{i B} T_{g p + i} mod X^N + 1, B = N / p, U = X^{-B/2} (1 + X + ... + X^{B-1}), N = 1024.
+// grid = (outputs, 2): block (g, poly) owns one polynomial (alpha: words [0, N) of the 2N-word records T, beta: [N, 2N)), thread = coefficient c.
+//   strided rotate-sum   S[c] = sum_i (X^{i B} T_i)[c]: T_i[c - i B], negated where c < i B -- every word of the p records is read once
+//   window sum           (U S)[c] = sum over the negacyclic extension E of S (E[j + N] = -E[j]) of E[j], c - B/2 < j <= c + B/2.  With the
+//                        inclusive prefix sums Pre of S (Hillis-Steele scan in LDS) and Tot = Pre[N - 1], the prefix of E up to j is
+//                        Pre[j] inside [0, N) and Tot - Pre[j mod N] one period below or above; the window is a difference of two.
+// Integer sums mod 2^32, no atomics; 64-bit offsets into T.
+__global__ __launch_bounds__(1024) void pack_boxes_kernel(const int32_t *__restrict__ T, int p, int32_t *__restrict__ out_a, int32_t *__restrict__ out_b) {
+    __shared__ uint32_t sP[2][1024];
+    const size_t g = blockIdx.x;
+    const int poly = blockIdx.y, c = threadIdx.x;
+    const int B = 1024 / p;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(T) + g * p * 2048 + (size_t)poly * 1024;
+    uint32_t acc = 0;
+#pragma unroll 8
+    for (int i = 0; i < p; i++) {
+        const int e = c - i * B;   // in (-N, N)
+        const uint32_t v = src[(size_t)i * 2048 + (e & 1023)];
+        acc += e < 0 ? 0u - v : v;
+    }
+    int cur = 0;
+    sP[0][c] = acc;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        uint32_t v = sP[cur][c];
+        if (c >= d) v += sP[cur][c - d];
+        sP[cur ^ 1][c] = v;
+        __syncthreads();
+        cur ^= 1;
+    }
+    const uint32_t tot = sP[cur][1023];
+    const int hi = c + B / 2, lo = c - B / 2;   // hi < 2N, lo >= -N
+    const uint32_t ph = hi < 1024 ? sP[cur][hi] : tot - sP[cur][hi & 1023];
+    const uint32_t pl = lo >= 0 ? sP[cur][lo] : tot - sP[cur][lo & 1023];
+    (poly ? out_b : out_a)[g * 1024 + c] = (int32_t)(ph - pl);
+}
+
 // below this many samples the packing key switch runs the plain kernel (rows of 2N words, coordinates in ranges of 64); from here on the
 // matrix cores, whose cost up to 256 samples is about one pass over the planes (measured, SK-128, whole calls: 4 samples 0.096 ms plain /
 // 0.095 matrix cores, 8 0.107 / 0.103, 16 0.120 / 0.103, 31 0.176 / 0.108)
@@ -166,6 +207,39 @@ struct THFHE_INTERNAL thfhe_poly_ctx : DevCtx {
     int pk_n = 0;    // its LWE dimension; 0: no key
     DevBuf d_pin, d_pt;   // padded LWE input, per-sample T_i
 };
+
+namespace {
+
+// phase 1 of thfhe_pack_lwe / thfhe_pack_boxes on device records: pad the masks, key-switch with the packing key into c->d_pt [count][2N]
+int pack_per_sample(thfhe_poly_ctx *c, const int32_t *d_lwe, size_t count, hipStream_t stream) {
+    const int n = c->pk_n, n_pad = c->pk.N, N = 1024;
+    int rc = c->d_pin.grow(count * (n_pad + 1) * 4);
+    if (!rc) rc = c->d_pt.grow(count * 2 * N * 4);
+    if (rc) return rc;
+    hipLaunchKernelGGL(pack_pad_lwe_kernel, dim3((unsigned)count), dim3(256), 0, stream, d_lwe, n, n_pad, (long)count, c->d_pin.as<int32_t>());
+    THFHE_HIP(hipGetLastError());
+    KsArgs k = c->pk.args(c->d_pin.as<int32_t>(), c->d_pt.as<int32_t>(), (long)count);
+    k.out_rec = 2 * N, k.b_col = N;   // (u_rec = n_pad + 1: args' default)
+    return ks_enqueue(c->pk, k, n_pad / 64, stream, kPackMfmaMinSamples);
+}
+
+}  // namespace
+
+namespace thfhe {
+
+int pack_ctx_device(thfhe_poly_ctx *c) { return c->device; }
+hipStream_t pack_ctx_stream(thfhe_poly_ctx *c) { return c->stream; }
+std::mutex &pack_ctx_mutex(thfhe_poly_ctx *c) { return c->mu; }
+int pack_key_n(thfhe_poly_ctx *c) { return c->pk_n; }
+
+int pack_boxes_enqueue(thfhe_poly_ctx *c, const int32_t *d_lwe, size_t count, int p, int32_t *d_a, int32_t *d_b, hipStream_t stream) {
+    THFHE_TRY(pack_per_sample(c, d_lwe, count, stream));
+    hipLaunchKernelGGL(pack_boxes_kernel, dim3((unsigned)(count / p), 2), dim3(1024), 0, stream, c->d_pt.as<int32_t>(), p, d_a, d_b);
+    THFHE_HIP(hipGetLastError());
+    return THFHE_OK;
+}
+
+}  // namespace thfhe
 
 extern "C" {
 
@@ -273,24 +347,39 @@ int thfhe_pack_lwe(thfhe_poly_ctx *c, const int32_t *lwe, size_t count, int slot
     if (lk.rc) return lk.rc;
     if (!c->pk_n) return thfhe_fail(THFHE_E_INVALID, "no packing key set (thfhe_pack_key_set)");
     if (count == 0) return THFHE_OK;
-    const int n = c->pk_n, n_pad = c->pk.N, N = 1024;
+    const int n = c->pk_n, N = 1024;
     const size_t outs = (count + slots - 1) / slots;
     int rc = c->d_buf[0].grow(count * (n + 1) * 4);
-    if (!rc) rc = c->d_pin.grow(count * (n_pad + 1) * 4);
-    if (!rc) rc = c->d_pt.grow(count * 2 * N * 4);
     if (!rc) rc = c->d_buf[1].grow(outs * N * 4);
     if (!rc) rc = c->d_buf[2].grow(outs * N * 4);
     if (rc) return rc;
     THFHE_HIP(hipMemcpyAsync(c->d_buf[0].as<void>(), lwe, count * (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(pack_pad_lwe_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, c->d_buf[0].as<int32_t>(), n, n_pad, (long)count,
-                       c->d_pin.as<int32_t>());
-    THFHE_HIP(hipGetLastError());
-    KsArgs k = c->pk.args(c->d_pin.as<int32_t>(), c->d_pt.as<int32_t>(), (long)count);
-    k.out_rec = 2 * N, k.b_col = N;   // (u_rec = n_pad + 1: args' default)
-    THFHE_TRY(ks_enqueue(c->pk, k, n_pad / 64, c->stream, kPackMfmaMinSamples));
+    THFHE_TRY(pack_per_sample(c, c->d_buf[0].as<int32_t>(), count, c->stream));
     hipLaunchKernelGGL(pack_rotate_sum_kernel, dim3((unsigned)outs, (unsigned)(2 * N / 64)), dim3(1024), 0, c->stream, c->d_pt.as<int32_t>(), (long)count,
                        slots, N, c->d_buf[1].as<int32_t>(), c->d_buf[2].as<int32_t>());
     THFHE_HIP(hipGetLastError());
+    THFHE_HIP(hipMemcpyAsync(tlwe_a, c->d_buf[1].as<void>(), outs * N * 4, hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(tlwe_b, c->d_buf[2].as<void>(), outs * N * 4, hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    return THFHE_OK;
+}
+
+int thfhe_pack_boxes(thfhe_poly_ctx *c, const int32_t *lwe, size_t count, int p, int32_t *tlwe_a, int32_t *tlwe_b) {
+    if (!c || !lwe || !tlwe_a || !tlwe_b) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (p < 2 || p > 512 || (p & (p - 1))) return thfhe_fail(THFHE_E_INVALID, "p must be a power of two in 2 .. N/2");
+    if (count % p) return thfhe_fail(THFHE_E_INVALID, "count must be a multiple of p");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    if (!c->pk_n) return thfhe_fail(THFHE_E_INVALID, "no packing key set (thfhe_pack_key_set)");
+    if (count == 0) return THFHE_OK;
+    const int n = c->pk_n, N = 1024;
+    const size_t outs = count / p;
+    int rc = c->d_buf[0].grow(count * (n + 1) * 4);
+    if (!rc) rc = c->d_buf[1].grow(outs * N * 4);
+    if (!rc) rc = c->d_buf[2].grow(outs * N * 4);
+    if (rc) return rc;
+    THFHE_HIP(hipMemcpyAsync(c->d_buf[0].as<void>(), lwe, count * (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    THFHE_TRY(pack_boxes_enqueue(c, c->d_buf[0].as<int32_t>(), count, p, c->d_buf[1].as<int32_t>(), c->d_buf[2].as<int32_t>(), c->stream));
     THFHE_HIP(hipMemcpyAsync(tlwe_a, c->d_buf[1].as<void>(), outs * N * 4, hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipMemcpyAsync(tlwe_b, c->d_buf[2].as<void>(), outs * N * 4, hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));

@@ -163,6 +163,11 @@ SIGNATURES = {
     "thfhe_keyswitch": (C.c_int, [_vp, _i32p, _i32p, C.c_size_t]),
     "thfhe_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.POINTER(LutSpec), _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_lut_bootstrap_enc": (C.c_int, [_vp, C.POINTER(LutSpec), _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_lut_bootstrap_enc_wo_keyswitch": (C.c_int, [_vp, C.POINTER(LutSpec), _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_tree_lut_bootstrap": (C.c_int, [_vp, _vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p,
+                                           _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_set_tree_slice": (C.c_int, [_vp, C.c_size_t]),
     "thfhe_dev_alloc": (_vp, [_vp, C.c_size_t]),
     "thfhe_dev_free": (None, [_vp, _vp]),
     "thfhe_copy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
@@ -185,6 +190,7 @@ SIGNATURES = {
     "thfhe_final_decrypt": (C.c_int, [_vp, _i32p, _i32p, C.c_int, _i32p, _i32p, C.c_size_t]),
     "thfhe_pack_key_set": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_int]),
     "thfhe_pack_lwe": (C.c_int, [_vp, _i32p, C.c_size_t, C.c_int, _i32p, _i32p]),
+    "thfhe_pack_boxes": (C.c_int, [_vp, _i32p, C.c_size_t, C.c_int, _i32p, _i32p]),
     "thfhe_kms_ctx_create": (C.c_int, [_vp, _i64p, _i32p, C.c_int, C.POINTER(_vp)]),
     "thfhe_kms_ctx_destroy": (None, [_vp]),
     "thfhe_kms_tlev_rotate": (C.c_int, [_vp, C.c_int, _i32p, _i64p, C.c_size_t]),
@@ -538,6 +544,71 @@ class CloudKey(_EvalKey):
         out = np.empty((u.shape[0], self.words), np.int32)
         _check(lib().thfhe_keyswitch(self.h, _p32(u), _p32(out), u.shape[0]))
         return out
+
+    # -- encrypted tables and the two-digit tree (thfhe_lut_bootstrap_enc, thfhe_tree_lut_bootstrap) ------------------------
+    def lut_bootstrap_enc(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
+        """lut_bootstrap with ENCRYPTED tables: table t is the TLWE sample (tv_a[t], tv_b[t]) under the bootstrapping ring key
+        (thfhe.lut.encrypt_table, or PackBoxes' output); up to 262 144 tables, so every sample may bring its own.  int32[count, theta, n+1]."""
+        return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, True)
+
+    def lut_bootstrap_enc_wo_keyswitch(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
+        """lut_bootstrap_enc without the key switch: int32[count, theta, N+1] records under the ring key."""
+        return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, False)
+
+    def _lut_args(self, ins, weights, bias, theta, what):
+        given = [v for v in ins if v is not None]
+        if any(v is None for v in ins[:len(given)]) or len(given) != len(weights):
+            raise ValueError(f"{what}: give the inputs in order and one weight per input")
+        recs = [_rec(v, self.words) for v in given]
+        _same_count(*recs)
+        w = list(weights) + [0] * (3 - len(weights))
+        spec = LutSpec(len(recs), (C.c_int32 * 3)(*[_wrap32(v) for v in w]), _wrap32(bias), int(theta))
+        return recs, spec, [_p32(v) for v in recs] + [None] * (3 - len(recs))
+
+    def _lut_enc(self, tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, keyswitch):
+        ins, spec, p = self._lut_args((x, y, z), weights, bias, theta, "lut_bootstrap_enc")
+        N = self.params.N
+        tv_a = np.ascontiguousarray(tv_a, np.int32).reshape(-1, N)
+        tv_b = np.ascontiguousarray(tv_b, np.int32).reshape(-1, N)
+        if tv_a.shape != tv_b.shape:
+            raise ValueError(f"tv_a and tv_b differ in shape: {tv_a.shape} vs {tv_b.shape}")
+        count = ins[0].shape[0]
+        idx = None
+        if lut_index is not None:
+            idx = np.ascontiguousarray(lut_index, np.int32).reshape(-1)
+            if idx.shape[0] != count:
+                raise ValueError(f"lut_index holds {idx.shape[0]} entries for {count} samples")
+        out = np.empty((count, int(theta) if theta in (1, 2, 4) else 1, self.words if keyswitch else N + 1), np.int32)
+        fn = lib().thfhe_lut_bootstrap_enc if keyswitch else lib().thfhe_lut_bootstrap_enc_wo_keyswitch
+        _check(fn(self.h, C.byref(spec), _p32(tv_a), _p32(tv_b), tv_a.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
+        return out
+
+    def tree_lut_bootstrap(self, poly_ctx, tv1, lo, hi, *, p_hi, weights_lo=(1,), bias_lo=0, theta=1, weights_hi=(1,), bias_hi=0, table_index=None):
+        """Two-digit tree PBS (thfhe_tree_lut_bootstrap): sample s gets f_table[s](hi, lo) as one record int32[count, n+1].  lo, hi: one record
+        array or a tuple of 1 .. 3 (weighted by weights_lo / weights_hi); tv1: int32[n_tables][p_hi / theta][N] (thfhe.lut.tree_test_vectors);
+        poly_ctx: a threshold.PolyContext holding the packing key from this key set's LWE key to its bootstrapping ring key."""
+        as_tuple = lambda v: tuple(v) + (None,) * (3 - len(v)) if isinstance(v, (tuple, list)) else (v, None, None)
+        lo_r, spec_lo, plo = self._lut_args(as_tuple(lo), weights_lo, bias_lo, theta, "tree_lut_bootstrap (lo)")
+        hi_r, spec_hi, phi = self._lut_args(as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap (hi)")
+        _same_count(lo_r[0], hi_r[0])
+        count = lo_r[0].shape[0]
+        R = int(p_hi) // int(theta) if theta in (1, 2, 4) else 1
+        tv1 = np.ascontiguousarray(tv1, np.int32)
+        if R < 1 or tv1.size == 0 or tv1.size % (R * self.params.N):
+            raise ValueError(f"tv1: expected int32[n_tables][{R}][{self.params.N}]")
+        idx = None
+        if table_index is not None:
+            idx = np.ascontiguousarray(table_index, np.int32).reshape(-1)
+            if idx.shape[0] != count:
+                raise ValueError(f"table_index holds {idx.shape[0]} entries for {count} samples")
+        out = np.empty((count, self.words), np.int32)
+        _check(lib().thfhe_tree_lut_bootstrap(self.h, poly_ctx.h, C.byref(spec_lo), C.byref(spec_hi), int(p_hi), _p32(tv1), tv1.size // (R * self.params.N),
+                                              _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
+        return out
+
+    def set_tree_slice(self, max_candidates):
+        """Level-1 candidates (samples x p_hi) per slice of tree_lut_bootstrap: bounds its workspace (8 KiB of packing scratch per candidate)."""
+        _check(lib().thfhe_set_tree_slice(self.h, int(max_candidates)))
 
     def set_ring4_threshold(self, max_jobs):
         """Remainders (batch mod 2048) above the cooperative threshold and <= max_jobs rotations use the four-wave ring kernel; 0 disables it."""

@@ -95,3 +95,25 @@ def bool_outputs(f, p, torus_bits=32):
     if torus_bits == 64:
         return np.array([MU8_64 if f(m) else -MU8_64 for m in range(p)], np.int64)
     return _to_i32(np.array([MU8 if f(m) else -MU8 for m in range(p)], np.int64))
+
+
+def tree_test_vectors(f, p_hi, p_lo, p_out, theta=1, N=1024):
+    """Level-1 test vectors of the two-digit tree (thfhe_tree_lut_bootstrap) for f(hi, lo), taken mod p_out: int32[p_hi / theta][N],
+    row r = test_vector of the theta functions lo -> f(r theta + j, lo), j < theta, at modulus p_lo."""
+    _check_p(p_hi)
+    if theta not in (1, 2, 4) or p_hi % theta:
+        raise ValueError("theta must be 1, 2 or 4 and divide p_hi")
+    return np.stack([test_vector([int_outputs(lambda lo, h=r * theta + j: f(h, lo), p_out, p_lo) for j in range(theta)], p_lo, theta, N)
+                     for r in range(p_hi // theta)])
+
+
+def encrypt_table(rlwe_key, tv, sigma, rng):
+    """The client side of an encrypted table (thfhe_lut_bootstrap_enc): a fresh TLWE sample (tv_a, tv_b) of the test vector(s) tv int32[..., N]
+    under the bootstrapping ring key: tv_a uniform, tv_b = tv_a (*) z + tv + e, e Gaussian of standard deviation sigma; exact product."""
+    from .keygen import dtot32, polymul_small32
+    z = np.asarray(rlwe_key, np.int32).reshape(-1)
+    tv = np.ascontiguousarray(tv, np.int32)
+    flat = tv.reshape(-1, z.shape[0])
+    a = rng.integers(-2**31, 2**31, size=flat.shape, dtype=np.int64).astype(np.int32)
+    b = polymul_small32(a, z).astype(np.int64) + flat.astype(np.int64) + dtot32(rng.standard_normal(flat.shape) * sigma).astype(np.int64)
+    return a.reshape(tv.shape), _to_i32(b).reshape(tv.shape)

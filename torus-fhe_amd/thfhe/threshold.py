@@ -75,6 +75,20 @@ def PackLwe(ctx, cipher, slots=None):
     return a, b
 
 
+def PackBoxes(ctx, cipher, p):
+    """thfhe_pack_boxes: LWE records int32[count][n+1], count a multiple of p -> (a, b) int32[count / p][N], one encrypted
+    test vector per p samples: candidate i fills the N/p coefficients centred on i N/p (the layout of thfhe.lut.test_vector at theta = 1), ready
+    for CloudKey.lut_bootstrap_enc when the packing key targets the bootstrapping ring key."""
+    p = int(p)
+    if ctx.pack_n is None:
+        raise ThfheError("no packing key set (PolyContext.set_pack_key)")
+    x = np.ascontiguousarray(cipher, np.int32).reshape(-1, ctx.pack_n + 1)
+    outs = x.shape[0] // p if p > 0 else 0
+    a, b = np.empty((outs, ctx.N), np.int32), np.empty((outs, ctx.N), np.int32)
+    _check(lib().thfhe_pack_boxes(ctx.h, _p32(x), x.shape[0], p, _p32(a), _p32(b)))
+    return a, b
+
+
 def packed_bits(result, count, slots=None):
     """The message bits of `count` packed samples from finalDecrypt(..., want_result=True)'s result: coefficient i of output g is
     sample g slots + i, and its bit is that coefficient > 0."""
