@@ -58,7 +58,10 @@ enum thfhe_gate {
     THFHE_ANDNY = 6, THFHE_ANDYN = 7, THFHE_ORNY = 8, THFHE_ORYN = 9, THFHE_MUX = 10,
     THFHE_NOT = 11, THFHE_COPY = 12, THFHE_AND3 = 13,
     THFHE_LUT = 14,     /* gate-DAG node: programmable bootstrap, output 0 (thfhe_dag_run_lut_batch only) */
-    THFHE_LUT_OUT = 15  /* output j > 0 of the LUT node j rows above (thfhe_dag_run_lut_batch only) */
+    THFHE_LUT_OUT = 15, /* output j > 0 of the LUT node j rows above (thfhe_dag_run_lut_batch, thfhe_dag_run_tree_batch) */
+    THFHE_LUT_ENC = 16, /* gate-DAG node: programmable bootstrap of an ENCRYPTED table (thfhe_dag_run_tree_batch only) */
+    THFHE_SELECT = 17,  /* gate-DAG node: oblivious pick among p consecutive earlier wires (thfhe_dag_run_tree_batch only) */
+    THFHE_TREE = 18     /* gate-DAG node: two-digit tree PBS (thfhe_dag_run_tree_batch only) */
 };
 
 enum thfhe_error {
@@ -353,6 +356,43 @@ int thfhe_tree_lut_bootstrap(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const thf
                              const int32_t *tv1, int n_tables, const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2,
                              const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count);
 int thfhe_set_tree_slice(thfhe_ctx *ctx, size_t max_candidates);
+
+/* ---- encrypted-table, select and tree nodes in the gate-DAG executor (single key): thfhe_dag_run_lut_batch with three more node
+ * kinds, so that a circuit needing a private table, an oblivious pick or a 6-bit -> 3-bit function does not leave the device-resident wire table.
+ * nodes: HOST int32[n_nodes][6] = (opcode, in0, in1, in2, x, y); row g defines wire n_inputs + g.  Gate rows, THFHE_LUT and THFHE_LUT_OUT rows mean
+ *   exactly what they mean in thfhe_dag_run_lut_batch.  New rows:
+ *   (THFHE_LUT_ENC, in0, in1, in2, spec, etab), followed by theta - 1 THFHE_LUT_OUT rows: wire head + j is the record
+ *       thfhe_lut_bootstrap_enc(specs[spec], enc_a[etab], enc_b[etab], operands) returns at [0][j], word for word.
+ *   (THFHE_SELECT, in0, in1, in2, tree, first): the candidate among the p = trees[tree].p_hi consecutive EARLIER wires first .. first + p - 1 that the
+ *       encrypted digit trees[tree].hi forms from the operands points at: thfhe_pack_boxes(candidate records, p) then
+ *       thfhe_lut_bootstrap_enc(trees[tree].hi, that table), word for word.  trees[tree].lo is ignored.  The outputs of a many-LUT node (its row and
+ *       its LUT_OUT rows) are consecutive wires and serve as candidates directly.
+ *   (THFHE_TREE, op0, op1, op2, tree, row0): the first lo.n_inputs operands belong to trees[tree].lo, the next hi.n_inputs to .hi, at most three
+ *       together, unused fields -1; level-1 rows tv1[row0 .. row0 + R - 1].  The result is thfhe_tree_lut_bootstrap(ctx, ctx_pack, &lo, &hi, p_hi,
+ *       tv1 + row0 N, 1, NULL, operands ...), word for word.
+ * specs / tv (as thfhe_dag_run_lut_batch) may both be absent (NULL, 0); enc_a, enc_b: HOST int32[n_enc][N] encrypted tables or NULL, 0, shared by all
+ *   instances and uploaded once per call; trees: HOST thfhe_tree_spec[n_trees] (at most 1024); tv1: HOST int32[n_tv1_rows][N] or NULL, 0.
+ * Scheduling: every new node costs one level (a SELECT's depth counts its candidates too).  A level's LUT_ENC nodes run as one launch group per
+ *   theta, its SELECT and its TREE nodes as one group per distinct trees[] index, after the gate and LUT groups.  A TREE group runs its whole chain
+ *   -- level-1 rotations, key switch, box packing, selection rotation, key switch, scatter -- inside its level on the gate context's stream.  A group
+ *   is cut into slices of at most thfhe_set_dag_slice nodes over all instances, SELECT / TREE groups also of at most thfhe_set_tree_slice / p_hi.
+ * stats: a TREE node counts R + 1 rotations and its group two launches, a LUT_ENC or SELECT node one rotation, their groups one launch.
+ * Checks, on the host before any device work and before either context is looked at (THFHE_E_INVALID): those of thfhe_dag_run_lut_batch; etab, tree
+ *   or row0 + R out of range; n_enc outside 1 .. 262 144 with a LUT_ENC row present; a tree spec thfhe_tree_lut_bootstrap would refuse; operand counts
+ *   that do not match the specs or exceed three; SELECT candidates that are not all earlier wires; a table family that is NULL while a row refers to
+ *   it.  Then, when the plan holds a SELECT or TREE node, the context checks of thfhe_tree_lut_bootstrap (same device, a packing key, its n equal to
+ *   the gate context's); ctx_pack may be NULL otherwise.  thfhe_dag_run(_batch), thfhe_dag_run_lut_batch and every thfhe_mk_dag_* entry reject the
+ *   three opcodes. */
+typedef struct thfhe_tree_spec {
+    thfhe_lut_spec lo;   /* level 1 (TREE only): 1..3 inputs, theta1 in {1,2,4} */
+    thfhe_lut_spec hi;   /* selection rotation: theta must be 1 */
+    int32_t p_hi;        /* power of two, 2..N/2; TREE: theta1 | p_hi, R = p_hi / theta1 */
+} thfhe_tree_spec;
+
+int thfhe_dag_run_tree_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                             const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
+                             const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, size_t instances, const int32_t *out_wires,
+                             size_t n_out, int32_t *outputs, int64_t *stats);
 
 /* ---- multi-key KEY GENERATION arithmetic on the device --------------------------------------------------------------
  * Exact multiply-accumulate of small-coefficient polynomials with torus polynomials, the only non-trivial arithmetic of

@@ -2,6 +2,7 @@
 // an ASAP levelising scheduler for the reference's circuits (src/KNN_medical_data.cpp:127-489, J/3gen_mk_gates.jl:183-362), and the
 // gather / scatter kernels of the device-resident executor.  LUT nodes (thfhe_dag_run_lut_batch): programmable bootstraps among the
 // gates, fed by a fused prologue that reads their operands from the wire table, their theta outputs scattered into consecutive wires.
+// Encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch, DESIGN 4.12, single key): three more node kinds, planned here, run by the engine.
 #ifndef THFHE_DAG_H
 #define THFHE_DAG_H
 
@@ -9,6 +10,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <map>
 #include <type_traits>
 #include <vector>
 
@@ -92,21 +94,95 @@ __global__ __launch_bounds__(256) void dag_scatter_theta_kernel(const int32_t *_
     const long j = r / theta, t = r - j * theta, G = first + j, q = G / cnt, g = G - q * cnt;
     wires[((size_t)q * n_wires + idx[g] + t) * words + i] = src[r * words + i];
 }
+// Tree prologue (TREE launch group): node j of the slice (G = first + j = q cnt + g) reads its `lo` operands from the wire table ONCE
+// and serves its R level-1 jobs j R + r: the same bara / barb for each, table index row0[g] + r.  sk_tree_prologue_kernel's arithmetic over
+// dag_lut_prologue_kernel's addressing, the theta-rounded mod-switch included; the group's spec comes by value (one trees[] entry per group).
+__global__ __launch_bounds__(256) void dag_tree_prologue_kernel(const int32_t *__restrict__ wires, const int32_t *__restrict__ t0, const int32_t *__restrict__ t1,
+                                                                const int32_t *__restrict__ t2, const int32_t *__restrict__ t_row0, thfhe_lut_spec sp, int reps,
+                                                                long first, long total, long cnt, size_t n_wires, int n, int pad, int log2_2n,
+                                                                int32_t *__restrict__ bara, int32_t *__restrict__ barb, int32_t *__restrict__ lut_idx) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    const size_t words = (size_t)n + 1;
+    const int log2_theta = sp.theta == 4 ? 2 : sp.theta >> 1;
+    for (long j = blockIdx.y; j < total; j += gridDim.y) {
+        const long G = first + j, q = G / cnt, g = G - q * cnt;
+        const int32_t *rec = wires + (size_t)q * n_wires * words + i;
+        uint32_t v = (uint32_t)sp.weights[0] * (uint32_t)rec[(size_t)t0[g] * words];
+        if (sp.n_inputs > 1) v += (uint32_t)sp.weights[1] * (uint32_t)rec[(size_t)t1[g] * words];
+        if (sp.n_inputs > 2) v += (uint32_t)sp.weights[2] * (uint32_t)rec[(size_t)t2[g] * words];
+        if (i == n) v += (uint32_t)sp.bias;
+        const int32_t bar = (int32_t)((uint32_t)modswitch2n((int32_t)v, log2_2n - log2_theta) << log2_theta);
+        const size_t job0 = (size_t)j * reps;
+        if (i == n) {
+            const int32_t row0 = t_row0[g];
+            for (int r = 0; r < reps; r++) barb[job0 + r] = bar, lut_idx[job0 + r] = row0 + r;
+        } else {
+            for (int r = 0; r < reps; r++) bara[(job0 + r) * pad + i] = bar;
+        }
+    }
+}
+// Selection prologue (SELECT groups, level 2 of TREE groups): the index operands of node j from the wire table for the one-table-per-job rotation of
+// its own packed table: lut_idx[j] = j.  theta = 1: the plain mod-switch.
+__global__ __launch_bounds__(256) void dag_select_prologue_kernel(const int32_t *__restrict__ wires, const int32_t *__restrict__ t0, const int32_t *__restrict__ t1,
+                                                                  const int32_t *__restrict__ t2, thfhe_lut_spec sp, long first, long total, long cnt,
+                                                                  size_t n_wires, int n, int pad, int log2_2n, int32_t *__restrict__ bara,
+                                                                  int32_t *__restrict__ barb, int32_t *__restrict__ lut_idx) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    const size_t words = (size_t)n + 1;
+    for (long j = blockIdx.y; j < total; j += gridDim.y) {
+        const long G = first + j, q = G / cnt, g = G - q * cnt;
+        const int32_t *rec = wires + (size_t)q * n_wires * words + i;
+        uint32_t v = (uint32_t)sp.weights[0] * (uint32_t)rec[(size_t)t0[g] * words];
+        if (sp.n_inputs > 1) v += (uint32_t)sp.weights[1] * (uint32_t)rec[(size_t)t1[g] * words];
+        if (sp.n_inputs > 2) v += (uint32_t)sp.weights[2] * (uint32_t)rec[(size_t)t2[g] * words];
+        if (i == n) v += (uint32_t)sp.bias;
+        const int32_t bar = modswitch2n((int32_t)v, log2_2n);
+        if (i == n) {
+            barb[j] = bar;
+            lut_idx[j] = (int32_t)j;
+        } else {
+            bara[(size_t)j * pad + i] = bar;
+        }
+    }
+}
+// Candidate gather of a SELECT group: candidate r = j p + k of the slice is wire t_first[g] + k of instance q -> dst[r], the [jobs p][words] buffer
+// the box packing reads.  grid.y strides over the candidates.
+__global__ __launch_bounds__(256) void dag_select_gather_kernel(const int32_t *__restrict__ wires, const int32_t *__restrict__ t_first, int32_t *__restrict__ dst,
+                                                                long first, long total, long cnt, size_t n_wires, int words, int p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= words) return;
+    for (long r = blockIdx.y; r < total * p; r += gridDim.y) {
+        const long j = r / p, k = r - j * p, G = first + j, q = G / cnt, g = G - q * cnt;
+        dst[(size_t)r * words + i] = wires[((size_t)q * n_wires + t_first[g] + k) * words + i];
+    }
+}
 
 
 // One launch group of the schedule: `count` gates of one class whose operands are all available.
 struct DagBatch {
     int32_t depth, sub, cls;  // cls: engine-defined gate class; 2 = NOT / COPY (no bootstrap); 4 / 5 / 6 = LUT nodes of theta 1 / 2 / 4
     size_t off, count;        // index table slice: [ops | in0 | in1 | in2 | out], LUT classes + [spec | lut], `count` entries each, at tab[off]
+    int32_t tree = -1;        // SELECT / TREE groups: the trees[] entry the whole group shares
 };
 constexpr int kDagLutOut = 7;                // LUT_OUT row: no launch, its wire is written by its head's scatter
 inline int dag_lut_class(int theta) { return theta == 1 ? 4 : (theta == 2 ? 5 : 6); }
 inline int dag_lut_theta(int cls) { return cls == 4 ? 1 : (cls == 5 ? 2 : 4); }
+// thfhe_dag_run_tree_batch: LUT_ENC nodes of theta 1 / 2 / 4 = 8 / 9 / 10 (index columns as the LUT classes: [spec | etab]); SELECT groups = 11
+// ([tree | first]), TREE groups = 12 ([tree | row0]), one group per trees[] entry
+constexpr int kDagEnc = 8, kDagSelect = 11, kDagTree = 12;
+inline int dag_enc_theta(int cls) { return cls == 8 ? 1 : (cls == 9 ? 2 : 4); }
 
 // The LUT side of a run (thfhe_dag_run_lut_batch): node rows of 6 words, the run's specs and its table count.
 struct DagLuts {
     const thfhe_lut_spec *specs;
     int n_specs, n_luts;
+    // thfhe_dag_run_tree_batch only (ext): the encrypted-table count, the tree specs and the level-1 row count
+    bool ext = false;
+    int n_enc = 0;
+    const thfhe_tree_spec *trees = nullptr;
+    int n_trees = 0, n_tv1_rows = 0;
 };
 
 struct DagPlan {
@@ -118,7 +194,12 @@ struct DagPlan {
     int32_t max_depth = 0;
     void fill_stats(int64_t *stats) const {
         stats[0] = max_depth, stats[1] = 0, stats[2] = rotations, stats[3] = (int64_t)max_width;
-        for (const auto &b : batches) stats[1] += b.cls != 2;
+        for (const auto &b : batches) stats[1] += b.cls == kDagTree ? 2 : (b.cls != 2);   // a TREE group: level-1 and selection launch
+    }
+    bool has_tree_groups() const {
+        for (const auto &b : batches)
+            if (b.cls == kDagSelect || b.cls == kDagTree) return true;
+        return false;
     }
 };
 
@@ -127,11 +208,15 @@ struct DagPlan {
 // Bootstrapped gates add one level; NOT / COPY ride on their operand's level as sub-levels (a NOT may read a NOT of the same depth).
 // luts (thfhe_dag_run_lut_batch): rows of 6 words (opcode, in0, in1, in2, spec, lut); a THFHE_LUT node adds one level like a bootstrapped
 // gate and joins the launch group of its theta; its theta - 1 THFHE_LUT_OUT rows take its depth with sub-level 0 and launch nothing.
+// luts->ext (thfhe_dag_run_tree_batch): THFHE_LUT_ENC rows are LUT rows over the encrypted tables (classes 8 / 9 / 10); THFHE_SELECT and THFHE_TREE
+// rows add one level above their operands (a SELECT's candidates included) and form one group per trees[] entry, emitted after the other classes.
 template <typename Classify>
 int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify classify, DagPlan &plan, const DagLuts *luts = nullptr) {
     const size_t n_wires = n_inputs + n_gates, stride = luts ? 6 : 4;
     if (n_wires > (size_t)INT32_MAX / 2) return thfhe_fail(THFHE_E_INVALID, "too many wires");
     std::vector<int32_t> depth(n_wires, 0), sub(n_wires, 0), cls(n_gates, 0);
+    const bool ext = luts && luts->ext;
+    std::vector<char> tree_lo_ok(ext ? (size_t)luts->n_trees : 0, 0);   // trees[] entries whose `lo` half a TREE row has had checked
     int32_t max_depth = 0;
     int32_t head = -1, pending = 0;   // the LUT node whose LUT_OUT rows are still due, and how many
     for (size_t g = 0; g < n_gates; g++) {
@@ -148,15 +233,48 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
         }
         if (pending) return thfhe_fail(THFHE_E_INVALID, "LUT node: missing LUT_OUT row (theta - 1 of them must follow it)");
         int k, nin;
-        if (luts && op == THFHE_LUT) {
+        int32_t cand_first = 0, cand_count = 0;   // SELECT: its candidate wires
+        if (luts && (op == THFHE_LUT || (ext && op == THFHE_LUT_ENC))) {
+            const bool enc = op == THFHE_LUT_ENC;
+            if (ext && (!luts->specs || (!enc && luts->n_luts == 0)))
+                return thfhe_fail(THFHE_E_INVALID, enc ? "LUT_ENC node: no specs given (null table family)" : "LUT node: no specs or no tables given (null table family)");
+            if (enc && luts->n_enc < 1) return thfhe_fail(THFHE_E_INVALID, "LUT_ENC node: n_enc must be 1 .. 262144 (null table family)");
             if (row[4] < 0 || row[4] >= luts->n_specs) return thfhe_fail(THFHE_E_INVALID, "LUT node: spec index out of range (0 .. n_specs-1)");
-            if (row[5] < 0 || row[5] >= luts->n_luts) return thfhe_fail(THFHE_E_INVALID, "LUT node: table index out of range (0 .. n_luts-1)");
+            if (!enc && (row[5] < 0 || row[5] >= luts->n_luts)) return thfhe_fail(THFHE_E_INVALID, "LUT node: table index out of range (0 .. n_luts-1)");
+            if (enc && (row[5] < 0 || row[5] >= luts->n_enc)) return thfhe_fail(THFHE_E_INVALID, "LUT_ENC node: etab out of range (0 .. n_enc-1)");
             const thfhe_lut_spec &sp = luts->specs[row[4]];
             nin = sp.n_inputs;
             for (int q = 0; q < 3; q++)
                 if ((q < nin) != (row[1 + q] != -1)) return thfhe_fail(THFHE_E_INVALID, "LUT node: operands do not match the spec's n_inputs (unused ones are -1)");
-            k = dag_lut_class(sp.theta);
+            k = enc ? kDagEnc + (dag_lut_class(sp.theta) - 4) : dag_lut_class(sp.theta);
             head = w, pending = sp.theta - 1;
+        } else if (ext && (op == THFHE_SELECT || op == THFHE_TREE)) {
+            const bool is_tree = op == THFHE_TREE;
+            if (!luts->trees) return thfhe_fail(THFHE_E_INVALID, "SELECT / TREE node: no tree specs given (null table family)");
+            if (row[4] < 0 || row[4] >= luts->n_trees) return thfhe_fail(THFHE_E_INVALID, "SELECT / TREE node: tree index out of range (0 .. n_trees-1)");
+            const thfhe_tree_spec &ts = luts->trees[row[4]];
+            nin = ts.hi.n_inputs;
+            if (is_tree) {
+                if (!tree_lo_ok[row[4]]) {
+                    THFHE_TRY(lut_spec_check(ts.lo));
+                    if (ts.p_hi % ts.lo.theta) return thfhe_fail(THFHE_E_INVALID, "tree: spec_lo theta must divide p_hi");
+                    tree_lo_ok[row[4]] = 1;
+                }
+                nin += ts.lo.n_inputs;
+                if (nin > 3) return thfhe_fail(THFHE_E_INVALID, "TREE node: lo and hi operands exceed three");
+                if (luts->n_tv1_rows < 1) return thfhe_fail(THFHE_E_INVALID, "TREE node: no level-1 rows given (null table family)");
+                if (row[5] < 0 || (long)row[5] + ts.p_hi / ts.lo.theta > luts->n_tv1_rows)
+                    return thfhe_fail(THFHE_E_INVALID, "TREE node: row0 + R out of range (0 .. n_tv1_rows)");
+            } else {
+                cand_first = row[5], cand_count = ts.p_hi;
+                if (cand_first < 0 || (long)cand_first + cand_count > (long)w)
+                    return thfhe_fail(THFHE_E_INVALID, "SELECT node: candidate is not an earlier wire (first .. first + p - 1 must all be defined above)");
+            }
+            for (int q = 0; q < 3; q++)
+                if ((q < nin) != (row[1 + q] != -1))
+                    return thfhe_fail(THFHE_E_INVALID, is_tree ? "TREE node: operands do not match lo.n_inputs + hi.n_inputs (unused ones are -1)"
+                                                               : "SELECT node: operands do not match hi.n_inputs (unused ones are -1)");
+            k = is_tree ? kDagTree : kDagSelect;
         } else {
             k = classify(op);
             if (k < 0) return thfhe_fail(THFHE_E_INVALID, "gate opcode not defined for this engine");
@@ -170,6 +288,8 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
             if (in < 0 || in >= w) return thfhe_fail(THFHE_E_INVALID, "gate operand is not an earlier wire (gates must be in topological order)");
             if (depth[in] > d || (depth[in] == d && sub[in] > s)) d = depth[in], s = sub[in];
         }
+        for (int32_t in = cand_first; in < cand_first + cand_count; in++)
+            if (depth[in] > d || (depth[in] == d && sub[in] > s)) d = depth[in], s = sub[in];
         if (k == 2) s += 1; else d += 1, s = 0;
         depth[w] = d, sub[w] = s;
         if (d > max_depth) max_depth = d;
@@ -177,11 +297,14 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
     if (pending) return thfhe_fail(THFHE_E_INVALID, "LUT node: missing LUT_OUT row (theta - 1 of them must follow it)");
     plan.max_depth = max_depth;
     // bucket: (depth, sub, class); bootstrapped classes first (sub 0), then the linear sub-levels in order
-    std::vector<std::vector<std::vector<int32_t>>> boot(max_depth + 1, std::vector<std::vector<int32_t>>(7)), lin(max_depth + 1);
+    std::vector<std::vector<std::vector<int32_t>>> boot(max_depth + 1, std::vector<std::vector<int32_t>>(kDagSelect)), lin(max_depth + 1);
+    std::vector<std::map<int32_t, std::vector<int32_t>>> sel(ext ? max_depth + 1 : 0), tre(ext ? max_depth + 1 : 0);   // per level, by trees[] index
     for (size_t g = 0; g < n_gates; g++) {
         const int32_t w = (int32_t)(n_inputs + g);
         if (cls[g] == kDagLutOut) continue;
-        if (cls[g] == 2) {
+        if (cls[g] == kDagSelect || cls[g] == kDagTree) {
+            (cls[g] == kDagTree ? tre : sel)[depth[w]][gates[stride * g + 4]].push_back((int32_t)g);
+        } else if (cls[g] == 2) {
             auto &L = lin[depth[w]];
             if ((int)L.size() < sub[w]) L.resize(sub[w]);
             L[sub[w] - 1].push_back((int32_t)g);
@@ -190,9 +313,9 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
         }
     }
     plan.tab.reserve(5 * n_gates);
-    auto emit = [&](int32_t d, int32_t s, int32_t k, const std::vector<int32_t> &G) {
+    auto emit = [&](int32_t d, int32_t s, int32_t k, const std::vector<int32_t> &G, int32_t tree = -1) {
         if (G.empty()) return;
-        DagBatch b{d, s, k, plan.tab.size(), G.size()};
+        DagBatch b{d, s, k, plan.tab.size(), G.size(), tree};
         const int cols = k >= 4 ? 7 : 5;   // LUT groups: + spec, lut
         for (int col = 0; col < cols; col++)
             for (int32_t g : G) {
@@ -201,13 +324,19 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
             }
         plan.batches.push_back(b);
         if (G.size() > plan.max_width) plan.max_width = G.size();
-        const size_t rot = k == 2 ? 0 : (k == 1 ? 2 * G.size() : G.size());
+        size_t rot = k == 2 ? 0 : (k == 1 ? 2 * G.size() : G.size());
+        if (k == kDagTree) rot = G.size() * (size_t)(luts->trees[tree].p_hi / luts->trees[tree].lo.theta + 1);   // R level-1 rotations + the selection
         if (rot > plan.max_rot) plan.max_rot = rot;
-        if (k >= 4 && dag_lut_theta(k) > plan.max_theta) plan.max_theta = dag_lut_theta(k);
+        if (k >= 4 && k < kDagSelect && dag_lut_theta(k < kDagEnc ? k : k - 4) > plan.max_theta) plan.max_theta = dag_lut_theta(k < kDagEnc ? k : k - 4);
         plan.rotations += (int64_t)rot;
     };
     for (int32_t d = 0; d <= max_depth; d++) {
         for (int32_t k : {0, 3, 1, 4, 5, 6}) emit(d, 0, k, boot[d][k]);
+        if (ext) {
+            for (int32_t k : {8, 9, 10}) emit(d, 0, k, boot[d][k]);
+            for (const auto &kv : sel[d]) emit(d, 0, kDagSelect, kv.second, kv.first);
+            for (const auto &kv : tre[d]) emit(d, 0, kDagTree, kv.second, kv.first);
+        }
         for (size_t q = 0; q < lin[d].size(); q++) emit(d, (int32_t)q + 1, 2, lin[d][q]);
     }
     return THFHE_OK;
@@ -230,6 +359,36 @@ int dag_lut_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, s
     return dag_plan(nodes, n_inputs, n_nodes, classify, plan, &luts);
 }
 
+// Host-side checks and plan of thfhe_dag_run_tree_batch, before any device work and before either context is looked at: what
+// dag_lut_plan checks (specs / tv may both be absent), the encrypted-table and level-1 row counts, every tree spec's `hi` half and p_hi (the rules of
+// thfhe_tree_lut_bootstrap; the `lo` half when a TREE row uses the entry), then dag_plan's row checks with the three node kinds.
+template <typename Classify>
+int dag_tree_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs, int n_specs, const int32_t *tv,
+                  int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc, const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1,
+                  int n_tv1_rows, const int32_t *out_wires, size_t n_out, const int32_t *outputs, Classify classify, DagPlan &plan) {
+    if ((!inputs && n_inputs) || (!nodes && n_nodes) || (!outputs && n_nodes) || (!out_wires && n_out)) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if ((!specs && n_specs) || (!tv && n_luts) || ((!enc_a || !enc_b) && n_enc) || (!trees && n_trees) || (!tv1 && n_tv1_rows))
+        return thfhe_fail(THFHE_E_INVALID, "null argument: a table family with a count but no pointer");
+    if (n_specs < 0 || n_specs > 1024 || (specs && n_specs < 1)) return thfhe_fail(THFHE_E_INVALID, "n_specs must be 1 .. 1024 (0 with specs = NULL)");
+    if (n_luts < 0 || n_luts > 1024 || (tv && n_luts < 1)) return thfhe_fail(THFHE_E_INVALID, "n_luts must be 1 .. 1024 (0 with tv = NULL)");
+    if (n_enc < 0 || n_enc > (1 << 18)) return thfhe_fail(THFHE_E_INVALID, "n_enc must be 1 .. 262144 (0 with enc_a = enc_b = NULL)");
+    if (n_trees < 0 || n_trees > 1024 || (trees && n_trees < 1)) return thfhe_fail(THFHE_E_INVALID, "n_trees must be 1 .. 1024 (0 with trees = NULL)");
+    if (n_tv1_rows < 0 || n_tv1_rows > (1 << 18) || (tv1 && n_tv1_rows < 1)) return thfhe_fail(THFHE_E_INVALID, "n_tv1_rows must be 1 .. 262144 (0 with tv1 = NULL)");
+    for (int s = 0; s < n_specs; s++)
+        THFHE_TRY(lut_spec_check(specs[s]));
+    for (int t = 0; t < n_trees; t++) {
+        THFHE_TRY(lut_spec_check(trees[t].hi));
+        if (trees[t].hi.theta != 1) return thfhe_fail(THFHE_E_INVALID, "tree: spec_hi theta must be 1 (the packed table holds one function)");
+        const int p_hi = trees[t].p_hi;
+        if (p_hi < 2 || p_hi > 512 || (p_hi & (p_hi - 1))) return thfhe_fail(THFHE_E_INVALID, "tree: p_hi must be a power of two in 2 .. N/2");
+    }
+    for (size_t s = 0; s < n_out; s++)
+        if (out_wires[s] < 0 || (size_t)out_wires[s] >= n_inputs + n_nodes) return thfhe_fail(THFHE_E_INVALID, "output wire id out of range");
+    DagLuts luts{specs, n_specs, n_luts};
+    luts.ext = true, luts.n_enc = enc_a ? n_enc : 0, luts.trees = trees, luts.n_trees = n_trees, luts.n_tv1_rows = tv1 ? n_tv1_rows : 0;
+    return dag_plan(nodes, n_inputs, n_nodes, classify, plan, &luts);
+}
+
 // Device buffers of the executor (grow-only, owned by the engine's context and reused by every run on it).
 struct DagBuffers {
     DevBuf wires, tab, ops, pack;
@@ -245,6 +404,17 @@ struct DagLutSlice {
     size_t n_wires;
 };
 
+// A LUT_ENC, SELECT or TREE launch group as DagExecute hands it to the engine (thfhe_dag_run_tree_batch): the wire table, the group's index columns
+// (t_x, t_y = [spec | etab], [tree | first] or [tree | row0]), `all` = cnt nodes x instances jobs.  The engine cuts it into slices, runs the chain of
+// each and scatters the results into the wires t_out.
+struct DagExtGroup {
+    int cls, tree;
+    int32_t *wires;
+    const int32_t *t0, *t1, *t2, *t_out, *t_x, *t_y;
+    long all, cnt;
+    size_t n_wires;
+};
+
 // Device-resident executor.  Level by level, each class of a level as slices of at most `slice_cap` gates over ALL instances: gather ->
 // run(cls, d_ops, n) (the engine's prologue + blind rotations + key switch from its staging arrays stage_in[0..2] into stage_out) ->
 // scatter.  Nothing synchronises with the host between levels.
@@ -254,11 +424,12 @@ struct DagLutSlice {
 // ensure(max_gates_per_slice) sizes the engine's workspace and staging and returns its staging pointers through the out-parameters.
 // LUT launch groups (plans of thfhe_dag_run_lut_batch): run_lut(theta, DagLutSlice) -> fused prologue + LUT rotation + key switch of the
 // slice's nodes x theta records into the staging output, then the theta-record scatter into wires out[g] + j.  ensure sizes for
-// plan.max_theta records per node.
-template <typename Ensure, typename Run, typename RunLut = std::nullptr_t>
+// plan.max_theta records per node.  LUT_ENC / SELECT / TREE groups (plans of thfhe_dag_run_tree_batch): run_ext(DagExtGroup) slices, runs and
+// scatters the whole group; ensure sizes the engine's buffers for them from the plan.
+template <typename Ensure, typename Run, typename RunLut = std::nullptr_t, typename RunExt = std::nullptr_t>
 int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int words, size_t n_inputs, size_t n_gates, size_t instances,
                 const int32_t *h_inputs, const int32_t *h_sel, size_t n_sel, int32_t *h_out, size_t slice_cap, Ensure ensure, Run run,
-                RunLut run_lut = nullptr) {
+                RunLut run_lut = nullptr, RunExt run_ext = nullptr) {
     const size_t n_wires = n_inputs + n_gates;
     if (instances == 0 || n_gates == 0) return THFHE_OK;
     if (n_wires * instances > ((size_t)1 << 40) / (size_t)words) return thfhe_fail(THFHE_E_INVALID, "wire table too large");
@@ -289,6 +460,14 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
         const int32_t *t_ops = d_tab + plan.batches[b].off, *t0 = t_ops + cnt, *t1 = t0 + cnt, *t2 = t1 + cnt, *t_out = t2 + cnt;
         if (cls == 2) {
             hipLaunchKernelGGL(dag_wire_linear_kernel, dim3((unsigned)all, wb), block, 0, stream, d_wires, t0, t_out, t_ops, all, cnt, n_wires, words);
+            continue;
+        }
+        if (cls >= kDagEnc) {
+            if constexpr (std::is_same_v<RunExt, std::nullptr_t>) {
+                rc = thfhe_fail(THFHE_E_INVALID, "encrypted-table, select or tree node in a run without them");
+            } else {
+                rc = run_ext(DagExtGroup{cls, plan.batches[b].tree, d_wires, t0, t1, t2, t_out, t_out + cnt, t_out + 2 * cnt, all, cnt, n_wires});
+            }
             continue;
         }
         if (cls >= 4) {

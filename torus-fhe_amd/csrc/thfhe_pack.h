@@ -1,4 +1,4 @@
-// thfhe_pack.h -- what the single-key engine (thfhe_sk.hip, thfhe_tree_lut_bootstrap) needs from the packing context of
+// thfhe_pack.h -- what the single-key engine (thfhe_sk.hip: thfhe_tree_lut_bootstrap, thfhe_dag_run_tree_batch) needs from the packing context of
 // thfhe_threshold.hip: host functions only, hidden from the library's dynamic symbol table.  thfhe_poly_ctx itself stays private to
 // thfhe_threshold.hip (it holds a KsKey, whose type lives in each translation unit's anonymous namespace).
 #ifndef THFHE_PACK_H
@@ -23,6 +23,9 @@ int pack_key_n(thfhe_poly_ctx *c);
 // power of two in 2 .. N/2) -> d_a, d_b int32[count / p][N].  The caller holds pack_ctx_mutex, has made the context's device current and has
 // checked the arguments; the context's padded-input and T_i scratch (8 KiB per record) grow as needed.
 int pack_boxes_enqueue(thfhe_poly_ctx *c, const int32_t *d_lwe, size_t count, int p, int32_t *d_a, int32_t *d_b, hipStream_t stream);
+// grow that scratch for `count` records now, so that no later pack_boxes_enqueue of up to `count` records allocates (the gate-DAG executor sizes
+// its workspaces once, when a run starts); the caller holds pack_ctx_mutex, a key is set
+int pack_boxes_reserve(thfhe_poly_ctx *c, size_t count);
 
 }  // namespace thfhe
 

@@ -7,7 +7,9 @@
 //                             (J/bootstrap.jl:80-81) -> bara[job][n], barb[job]
 //   sk_lut_prologue_kernel    programmable bootstrap (thfhe_lut_bootstrap): weighted sum of 1-3 inputs + bias, mod-switch to multiples of theta;
 //                             the blind-rotate kernels' LUT instantiations start from a test vector and extract theta coefficients;
-//                             LUT nodes of the gate DAG (thfhe_dag_run_lut_batch) use them behind dag_lut_prologue_kernel (thfhe_dag.h)
+//                             LUT nodes of the gate DAG (thfhe_dag_run_lut_batch) use them behind dag_lut_prologue_kernel (thfhe_dag.h);
+//                             encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch) behind dag_tree_prologue_kernel /
+//                             dag_select_prologue_kernel / dag_select_gather_kernel (thfhe_dag.h)
 //   sk_blind_rotate_ring_kernel / sk_blind_rotate_coop_kernel   blind_rotate_and_extract (J/bootstrap.jl:38-65): accumulator in
 //                             LDS for all n CMuxes; throughput (8 gates per workgroup, key through an LDS-DMA ring) and latency
 //                             (one workgroup per gate) variants
@@ -537,6 +539,8 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     DevBuf d_tva;             // encrypted tables (thfhe_lut_bootstrap_enc): the masks; d_tv holds the bodies
     // tree PBS (thfhe_tree_lut_bootstrap): a slice's table indices, key-switched level-1 candidates and packed tables (mask, body)
     DevBuf d_tree_tab, d_tree_lwe, d_tree_a, d_tree_b;
+    // encrypted-table and tree nodes of the gate DAG (thfhe_dag_run_tree_batch): the run's encrypted tables (masks, bodies) and level-1 rows
+    DevBuf d_dag_enc_a, d_dag_enc_b, d_dag_tv1;
     size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate)
     // staging for the host-buffer API
     Stage stage;
@@ -915,6 +919,152 @@ int thfhe_dag_run_lut_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs
             int r = launch_rotations<kLut>(c, a);
             if (!r) r = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), (size_t)s.total * theta, 1, false);
             return r;
+        });
+}
+
+// Encrypted-table, select and tree nodes among the gates and LUT nodes.  Gate classes and LUT groups run as in
+// thfhe_dag_run_lut_batch.  A LUT_ENC group is a LUT group on the kLutEnc instantiations with the run's shared encrypted tables.  A SELECT group
+// gathers its candidates into the buffer the box packing reads, packs them into one encrypted table per node and rotates that table by the index
+// digit (dag_select_prologue_kernel, lut_idx = job).  A TREE group runs the chain of thfhe_tree_lut_bootstrap with both prologues reading the wire
+// table: level-1 rotations (dag_tree_prologue_kernel), key switch into the packing buffer, box packing, selection rotation, key switch.  Everything
+// is enqueued on the gate context's stream; both contexts stay locked for the run.
+int thfhe_dag_run_tree_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                             const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
+                             const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, size_t instances, const int32_t *out_wires,
+                             size_t n_out, int32_t *outputs, int64_t *stats) {
+    DagPlan plan;
+    int rc = dag_tree_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, out_wires, n_out,
+                           outputs,
+                           [](int op) { return op == THFHE_NOT || op == THFHE_COPY ? 2 : (op == THFHE_MUX ? 1 : (op >= THFHE_NAND && op <= THFHE_ORYN ? 0 : -1)); },
+                           plan);
+    if (rc) return rc;
+    if (stats) plan.fill_stats(stats);   // the plan's figures need no device
+    const bool packs = plan.has_tree_groups();
+    if (!c || (packs && !pc)) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (packs && pack_ctx_device(pc) != c->device)
+        return thfhe_fail(THFHE_E_INVALID, "tree: the gate context and the packing context must be on the same device");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    std::unique_lock<std::mutex> pg;   // always after the gate context's: nothing else takes both
+    if (packs) pg = std::unique_lock<std::mutex>(pack_ctx_mutex(pc));
+    const int n = c->p.n, words = n + 1, theta_max = plan.max_theta, log2_2n = ilog2(2 * c->p.N);
+    if (packs) {
+        if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
+        if (pack_key_n(pc) != n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
+    }
+    if (instances == 0 || n_nodes == 0) return THFHE_OK;
+    if (instances > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "too many instances");
+    // a slice of a group: at most dag_slice nodes over all instances, SELECT / TREE groups also at most tree_slice / p_hi of them
+    const size_t dag_slice = c->dag_slice, tree_slice = c->tree_slice;
+    auto slice_of = [&](int cls, int tree, size_t all) {
+        size_t s = std::min(all, dag_slice);
+        if (cls >= kDagSelect) s = std::min(s, std::max<size_t>(1, tree_slice / (size_t)trees[tree].p_hi));
+        return s;
+    };
+    // workspaces, sized once from the plan: rotation jobs, extracted records, key-switched records, candidates, packed tables
+    size_t w_jobs = 0, w_u = 0, w_out = 0, w_cand = 0, w_tab = 0;
+    for (const DagBatch &b : plan.batches) {
+        if (b.cls < kDagEnc) continue;
+        const size_t S = slice_of(b.cls, b.tree, b.count * instances);
+        if (b.cls < kDagSelect) {
+            const size_t theta = (size_t)dag_enc_theta(b.cls);
+            w_jobs = std::max(w_jobs, S), w_u = std::max(w_u, S * theta), w_out = std::max(w_out, S * theta);
+        } else {
+            const size_t p = (size_t)trees[b.tree].p_hi, R = b.cls == kDagTree ? p / (size_t)trees[b.tree].lo.theta : 1;
+            w_jobs = std::max(w_jobs, S * R), w_u = std::max(w_u, b.cls == kDagTree ? S * p : S), w_out = std::max(w_out, S);
+            w_cand = std::max(w_cand, S * p), w_tab = std::max(w_tab, S);
+        }
+    }
+    // the run's tables and specs, once per call
+    if (n_luts) rc = c->d_tv.grow((size_t)n_luts * 1024 * sizeof(int32_t));
+    if (!rc && n_specs) rc = c->dag.specs.grow((size_t)n_specs * sizeof(thfhe_lut_spec));
+    if (!rc && n_enc) rc = c->d_dag_enc_a.grow((size_t)n_enc * 1024 * sizeof(int32_t));
+    if (!rc && n_enc) rc = c->d_dag_enc_b.grow((size_t)n_enc * 1024 * sizeof(int32_t));
+    if (!rc && n_tv1_rows) rc = c->d_dag_tv1.grow((size_t)n_tv1_rows * 1024 * sizeof(int32_t));
+    if (!rc && w_cand) rc = c->d_tree_lwe.grow(w_cand * words * sizeof(int32_t));
+    if (!rc && w_tab) rc = c->d_tree_a.grow(w_tab * 1024 * sizeof(int32_t));
+    if (!rc && w_tab) rc = c->d_tree_b.grow(w_tab * 1024 * sizeof(int32_t));
+    if (!rc && w_cand) rc = pack_boxes_reserve(pc, w_cand);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    if (packs) THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle; from here on its buffers are used on `st`
+    if (n_luts) THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (n_specs) THFHE_HIP(hipMemcpyAsync(c->dag.specs.as<thfhe_lut_spec>(), specs, (size_t)n_specs * sizeof(thfhe_lut_spec), hipMemcpyHostToDevice, st));
+    if (n_enc) {
+        THFHE_HIP(hipMemcpyAsync(c->d_dag_enc_a.as<int32_t>(), enc_a, (size_t)n_enc * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        THFHE_HIP(hipMemcpyAsync(c->d_dag_enc_b.as<int32_t>(), enc_b, (size_t)n_enc * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    if (n_tv1_rows) THFHE_HIP(hipMemcpyAsync(c->d_dag_tv1.as<int32_t>(), tv1, (size_t)n_tv1_rows * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const unsigned pgx = (unsigned)((n + 1 + 255) / 256), wb = (unsigned)((words + 255) / 256);
+    auto gy = [](size_t jobs) { return (unsigned)(jobs < 65535 ? jobs : 65535); };
+    auto br = [&](long jobs, const int32_t *tab_b, int theta, const int32_t *tab_a) {
+        return BRArgs{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), jobs, n, c->n_pad,
+                      c->p.Bgbit, 0, tab_b, c->d_lut_idx.as<int32_t>(), theta, tab_a};
+    };
+    return dag_execute(
+        plan, c->dag, st, words, n_inputs, n_nodes, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
+        [&](size_t max_gates, int32_t **in, int32_t **out) {
+            int r = ensure_workspace(c, std::max(2 * max_gates, w_jobs));
+            if (!r) r = c->d_u.grow(std::max(theta_max * max_gates, w_u) * 1025 * sizeof(int32_t));
+            if (!r) r = c->d_lut_idx.grow(std::max(max_gates, w_jobs) * sizeof(int32_t));
+            if (!r) r = c->stage.grow(max_gates * words);
+            if (!r) r = c->stage.out.grow(std::max(theta_max * max_gates, w_out) * words * sizeof(int32_t));   // key switch of nodes x theta records
+            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
+            return r;
+        },
+        [&](int cls, const int32_t *d_ops, size_t m) { return dag_gate_class(c, cls, d_ops, m); },
+        [&](int theta, const DagLutSlice &s) {
+            hipLaunchKernelGGL(dag_lut_prologue_kernel, dim3(pgx, gy((size_t)s.total)), dim3(256), 0, st, s.wires, s.t0, s.t1, s.t2, s.t_spec, s.t_lut,
+                               (const thfhe_lut_spec *)c->dag.specs.as<thfhe_lut_spec>(), s.first, s.total, s.cnt, s.n_wires, n, c->n_pad, log2_2n,
+                               c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
+            int r = launch_rotations<kLut>(c, br(s.total, c->d_tv.as<int32_t>(), theta, nullptr));
+            if (!r) r = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), (size_t)s.total * theta, 1, false);
+            return r;
+        },
+        [&](const DagExtGroup &g) {
+            const long slice = (long)slice_of(g.cls, g.tree, (size_t)g.all);
+            for (long first = 0; first < g.all; first += slice) {
+                const long S = std::min(slice, g.all - first);
+                if (g.cls < kDagSelect) {   // LUT_ENC: t_x = spec, t_y = etab
+                    const int theta = dag_enc_theta(g.cls);
+                    hipLaunchKernelGGL(dag_lut_prologue_kernel, dim3(pgx, gy((size_t)S)), dim3(256), 0, st, (const int32_t *)g.wires, g.t0, g.t1, g.t2, g.t_x, g.t_y,
+                                       (const thfhe_lut_spec *)c->dag.specs.as<thfhe_lut_spec>(), first, S, g.cnt, g.n_wires, n, c->n_pad, log2_2n,
+                                       c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
+                    THFHE_TRY(launch_rotations<kLutEnc>(c, br(S, c->d_dag_enc_b.as<int32_t>(), theta, c->d_dag_enc_a.as<int32_t>())));
+                    THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), (size_t)S * theta, 1, false));
+                    hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(S * theta), wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires,
+                                       first, S, g.cnt, g.n_wires, words, theta);
+                    THFHE_HIP(hipGetLastError());
+                    continue;
+                }
+                const thfhe_tree_spec ts = trees[g.tree];
+                const int p = ts.p_hi;
+                const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the index operands of a TREE node follow its lo.n_inputs level-1 operands
+                int hi0 = 0;
+                if (g.cls == kDagTree) {   // t_y = row0
+                    const int R = p / ts.lo.theta;
+                    hi0 = ts.lo.n_inputs;
+                    hipLaunchKernelGGL(dag_tree_prologue_kernel, dim3(pgx, gy((size_t)S)), dim3(256), 0, st, (const int32_t *)g.wires, g.t0, g.t1, g.t2, g.t_y, ts.lo, R,
+                                       first, S, g.cnt, g.n_wires, n, c->n_pad, log2_2n, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(),
+                                       c->d_lut_idx.as<int32_t>());
+                    THFHE_TRY(launch_rotations<kLut>(c, br(S * R, c->d_dag_tv1.as<int32_t>(), ts.lo.theta, nullptr)));
+                    THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->d_tree_lwe.as<int32_t>(), (size_t)S * p, 1, false));
+                } else {                   // SELECT: t_y = first candidate wire
+                    hipLaunchKernelGGL(dag_select_gather_kernel, dim3(wb, gy((size_t)S * p)), dim3(256), 0, st, (const int32_t *)g.wires, g.t_y,
+                                       c->d_tree_lwe.as<int32_t>(), first, S, g.cnt, g.n_wires, words, p);
+                }
+                // candidate k of node j is record j p + k: the order the level-1 key switch (or the gather) wrote them in
+                THFHE_TRY(pack_boxes_enqueue(pc, c->d_tree_lwe.as<int32_t>(), (size_t)S * p, p, c->d_tree_a.as<int32_t>(), c->d_tree_b.as<int32_t>(), st));
+                hipLaunchKernelGGL(dag_select_prologue_kernel, dim3(pgx, gy((size_t)S)), dim3(256), 0, st, (const int32_t *)g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2],
+                                   ts.hi, first, S, g.cnt, g.n_wires, n, c->n_pad, log2_2n, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(),
+                                   c->d_lut_idx.as<int32_t>());
+                THFHE_TRY(launch_rotations<kLutEnc>(c, br(S, c->d_tree_b.as<int32_t>(), 1, c->d_tree_a.as<int32_t>())));
+                THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), (size_t)S, 1, false));
+                hipLaunchKernelGGL(dag_scatter_kernel, dim3((unsigned)S, wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires, first, S, g.cnt,
+                                   g.n_wires, words);
+                THFHE_HIP(hipGetLastError());
+            }
+            return (int)THFHE_OK;
         });
 }
 

@@ -232,6 +232,11 @@ hipStream_t pack_ctx_stream(thfhe_poly_ctx *c) { return c->stream; }
 std::mutex &pack_ctx_mutex(thfhe_poly_ctx *c) { return c->mu; }
 int pack_key_n(thfhe_poly_ctx *c) { return c->pk_n; }
 
+int pack_boxes_reserve(thfhe_poly_ctx *c, size_t count) {
+    THFHE_TRY(c->d_pin.grow(count * (c->pk.N + 1) * 4));
+    return c->d_pt.grow(count * 2 * 1024 * 4);
+}
+
 int pack_boxes_enqueue(thfhe_poly_ctx *c, const int32_t *d_lwe, size_t count, int p, int32_t *d_a, int32_t *d_b, hipStream_t stream) {
     THFHE_TRY(pack_per_sample(c, d_lwe, count, stream));
     hipLaunchKernelGGL(pack_boxes_kernel, dim3((unsigned)(count / p), 2), dim3(1024), 0, stream, c->d_pt.as<int32_t>(), p, d_a, d_b);

@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("THFHE_HIP_LIB", os.path.join(os.path.dirname(_HERE), 
 
 # gate opcodes (include/thfhe_hip.h enum thfhe_gate)
 NAND, OR, AND, XOR, XNOR, NOR, ANDNY, ANDYN, ORNY, ORYN, MUX, NOT, COPY, AND3 = range(14)
-LUT, LUT_OUT = 14, 15   # gate-DAG LUT node and its outputs j > 0 (dag_run_lut_batch only)
+LUT, LUT_OUT = 14, 15   # gate-DAG LUT node and its outputs j > 0 (dag_run_lut_batch, dag_run_tree_batch)
+LUT_ENC, SELECT, TREE = 16, 17, 18   # gate-DAG encrypted-table, select and tree nodes (CloudKey.dag_run_tree_batch only)
 
 MU8 = 1 << 29     # encode_message(1, 8), Torus32      (numeric-functions.jl:86-89)
 MU8_64 = 1 << 61  # encode_message64(1, 8), Torus64    (numeric-functions.jl:92-95)
@@ -136,6 +137,19 @@ class LutSpec(C.Structure):
     _fields_ = [("n_inputs", C.c_int32), ("weights", C.c_int32 * 3), ("bias", C.c_int32), ("theta", C.c_int32)]
 
 
+class TreeSpec(C.Structure):
+    """thfhe_tree_spec (include/thfhe_hip.h): the `lo` (level 1, TREE nodes only) and `hi` (selection rotation) prologues and the digit modulus p_hi
+    of the SELECT / TREE nodes of one launch group."""
+    _fields_ = [("lo", LutSpec), ("hi", LutSpec), ("p_hi", C.c_int32)]
+
+
+def _lut_spec(s):
+    """LutSpec from a (n_inputs, (w0, w1, w2), bias, theta) tuple (or a LutSpec)."""
+    if isinstance(s, LutSpec):
+        return s
+    return LutSpec(int(s[0]), (C.c_int32 * 3)(*[_wrap32(w) for w in (list(s[1]) + [0, 0, 0])[:3]]), _wrap32(s[2]), int(s[3]))
+
+
 _lib = None
 
 _i32p = C.POINTER(C.c_int32)
@@ -158,6 +172,8 @@ SIGNATURES = {
     "thfhe_dag_run_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_dag_run_lut_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, C.c_size_t, _i32p,
                                           C.c_size_t, _i32p, _i64p]),
+    "thfhe_dag_run_tree_batch": (C.c_int, [_vp, _vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, _i32p, _i32p, C.c_int,
+                                           C.POINTER(TreeSpec), C.c_int, _i32p, C.c_int, C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_bootstrap": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_keyswitch": (C.c_int, [_vp, _i32p, _i32p, C.c_size_t]),
@@ -413,9 +429,7 @@ class _EvalKey(_Handle):
         if x.ndim != 3 or x.shape[2] != words:
             raise ValueError("dag_run_lut_batch: input records must be int32[instances][n_inputs][%d]" % words)
         g = np.ascontiguousarray(nodes, np.int32).reshape(-1, 6)
-        sp = (LutSpec * len(specs))(*[s if isinstance(s, LutSpec) else
-                                      LutSpec(int(s[0]), (C.c_int32 * 3)(*[_wrap32(w) for w in (list(s[1]) + [0, 0, 0])[:3]]), _wrap32(s[2]), int(s[3]))
-                                      for s in specs])
+        sp = (LutSpec * len(specs))(*[_lut_spec(s) for s in specs])
         tv = np.ascontiguousarray(tv, self._tv_dtype).reshape(-1, self.params.N)
         q, n_in = x.shape[0], x.shape[1]
         sel = None if out_wires is None else np.ascontiguousarray(out_wires, np.int32).reshape(-1)
@@ -605,6 +619,33 @@ class CloudKey(_EvalKey):
         _check(lib().thfhe_tree_lut_bootstrap(self.h, poly_ctx.h, C.byref(spec_lo), C.byref(spec_hi), int(p_hi), _p32(tv1), tv1.size // (R * self.params.N),
                                               _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
         return out
+
+    def dag_run_tree_batch(self, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, out_wires=None, pack=None):
+        """dag_run_lut_batch with encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch, DESIGN 4.12).  nodes: int32[n_nodes][6];
+        specs, tv: as dag_run_lut_batch, both may be absent; enc_a, enc_b: int32[n_enc][N] encrypted tables; trees: (lo, hi, p_hi) tuples of spec
+        tuples (lo may be None: SELECT only) or TreeSpec; tv1: int32[rows][N] level-1 rows; pack: the threshold.PolyContext holding the packing key
+        (needed when a SELECT or TREE node is present).  Returns (int32[instances][len(out_wires) or n_nodes][words], stats)."""
+        words, N = self.words, self.params.N
+        x = np.ascontiguousarray(input_records, np.int32)
+        if x.ndim != 3 or x.shape[2] != words:
+            raise ValueError("dag_run_tree_batch: input records must be int32[instances][n_inputs][%d]" % words)
+        g = np.ascontiguousarray(nodes, np.int32).reshape(-1, 6)
+        sp = (LutSpec * len(specs))(*[_lut_spec(s) for s in specs]) if len(specs) else None
+        none = (1, (0, 0, 0), 0, 1)
+        tr = (TreeSpec * len(trees))(*[t if isinstance(t, TreeSpec) else TreeSpec(_lut_spec(t[0] or none), _lut_spec(t[1]), int(t[2])) for t in trees]) if len(trees) else None
+        tab = lambda a: None if a is None else np.ascontiguousarray(a, np.int32).reshape(-1, N)
+        tv, enc_a, enc_b, tv1 = tab(tv), tab(enc_a), tab(enc_b), tab(tv1)
+        if (enc_a is None) != (enc_b is None) or (enc_a is not None and enc_a.shape != enc_b.shape):
+            raise ValueError("enc_a and enc_b must both be given, with the same shape")
+        rows = lambda a: 0 if a is None else a.shape[0]
+        q, n_in = x.shape[0], x.shape[1]
+        sel = None if out_wires is None else np.ascontiguousarray(out_wires, np.int32).reshape(-1)
+        out = np.zeros((q, g.shape[0] if sel is None else sel.shape[0], words), np.int32)
+        st = np.zeros(4, np.int64)
+        _check(lib().thfhe_dag_run_tree_batch(self.h, None if pack is None else pack.h, _p32(x), n_in, _p32(g), g.shape[0], sp, len(specs), _p32(tv), rows(tv),
+                                              _p32(enc_a), _p32(enc_b), rows(enc_a), tr, len(trees), _p32(tv1), rows(tv1), q, _p32(sel),
+                                              0 if sel is None else sel.shape[0], _p32(out), st.ctypes.data_as(_i64p)))
+        return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
 
     def set_tree_slice(self, max_candidates):
         """Level-1 candidates (samples x p_hi) per slice of tree_lut_bootstrap: bounds its workspace (8 KiB of packing scratch per candidate)."""

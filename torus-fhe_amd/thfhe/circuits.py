@@ -12,12 +12,16 @@ src/bootstrap_modules.cpp:95).
 LUT nodes (Circuit.lut): a programmable bootstrap among the gates -- one rotation, one level, theta outputs on consecutive wires
 (a THFHE_LUT row, then theta - 1 THFHE_LUT_OUT rows).  Circuits that hold them run on thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch;
 lut_ripple_add, from_gate_bit and to_gate_bit build integer arithmetic from them.
+
+Encrypted-table, select and tree nodes (Circuit.lut_enc / select / tree; single key): a programmable bootstrap of an encrypted
+table, an oblivious pick among p consecutive wires, and the two-digit tree PBS, each one level.  Circuits that hold them run on
+thfhe_dag_run_tree_batch with the packing context (`pack`); tree_mul_digits multiplies two 3-bit digits with two TREE nodes.
 """
 import time
 
 import numpy as np
 
-from . import AND, COPY, LUT, LUT_OUT, MUX, NOT, OR, XOR, _wrap32
+from . import AND, COPY, LUT, LUT_ENC, LUT_OUT, MUX, NOT, OR, SELECT, TREE, XOR, _wrap32
 
 
 class Circuit:
@@ -30,6 +34,10 @@ class Circuit:
         self.tables = []      # test vectors of the LUT nodes (table ids index this list)
         self.specs = []       # (n_inputs, (w0, w1, w2), bias, theta) of the LUT nodes, deduplicated
         self.lut_rows = {}    # gate index of a LUT node -> (spec id, table id)
+        self.enc_tables = []  # (tv_a, tv_b, plaintext test vector or None) of the LUT_ENC nodes (the plaintext serves simulate only)
+        self.tree_specs = []  # (lo spec or None, hi spec, p_hi) of the SELECT / TREE launch groups, deduplicated
+        self.tv1 = []         # level-1 rows int32[N] of the TREE nodes, blocks of R registered by tree_rows
+        self.ext_rows = {}    # gate index of a LUT_ENC / SELECT / TREE node -> (spec id, etab) / (tree id, first) / (tree id, row0)
         self._ids = {}
 
     def inputs(self, count):
@@ -71,12 +79,110 @@ class Circuit:
         self.lut_rows[len(self.gates) - 1] = (self._ids[key], int(table_id))
         return [head] + [self.gate(LUT_OUT, head) for _ in range(theta - 1)]
 
+    def _spec_id(self, n_in, weights, bias, theta):
+        spec = (n_in, tuple(_wrap32(w) for w in list(weights) + [0] * (3 - len(weights))), _wrap32(bias), int(theta))
+        key = ("spec",) + spec
+        if key not in self._ids:
+            self._ids[key] = len(self.specs)
+            self.specs.append(spec)
+        return self._ids[key]
+
+    def _tree_id(self, lo, hi, p):
+        if p < 2 or p > 512 or p & (p - 1):
+            raise ValueError("p must be a power of two in 2 .. 512")
+        key = ("tree", lo, hi, int(p))
+        if key not in self._ids:
+            self._ids[key] = len(self.tree_specs)
+            self.tree_specs.append((lo, hi, int(p)))
+        return self._ids[key]
+
+    def enc_table(self, tv_a, tv_b, plain=None):
+        """Register an encrypted table: the TLWE sample (tv_a, tv_b) int32[N] under the bootstrapping ring key (thfhe.lut.encrypt_table, or
+        PackBoxes' output); returns its id.  Equal samples share one id.  plain: its plaintext test vector, carried for simulate only."""
+        a, b = np.ascontiguousarray(tv_a, np.int32).reshape(-1), np.ascontiguousarray(tv_b, np.int32).reshape(-1)
+        if a.shape != b.shape:
+            raise ValueError("tv_a and tv_b differ in shape")
+        key = ("enc", a.tobytes(), b.tobytes())
+        if key not in self._ids:
+            self._ids[key] = len(self.enc_tables)
+            self.enc_tables.append((a, b, None if plain is None else np.ascontiguousarray(plain, np.int32).reshape(-1)))
+        return self._ids[key]
+
+    def lut_enc(self, etab, inputs, weights=(1,), bias=0, theta=1):
+        """A LUT_ENC node: Circuit.lut on the encrypted table `etab` (enc_table).  Returns the theta output wire ids (consecutive)."""
+        inputs = list(inputs)
+        if not 1 <= len(inputs) <= 3 or len(weights) != len(inputs):
+            raise ValueError("a LUT_ENC node takes 1 to 3 inputs and one weight per input")
+        if theta not in (1, 2, 4):
+            raise ValueError("theta must be 1, 2 or 4")
+        if not 0 <= etab < len(self.enc_tables):
+            raise ValueError(f"unknown encrypted table id {etab}")
+        si = self._spec_id(len(inputs), weights, bias, theta)
+        head = self.gate(LUT_ENC, *(inputs + [-1] * (3 - len(inputs))))
+        self.ext_rows[len(self.gates) - 1] = (si, int(etab))
+        return [head] + [self.gate(LUT_OUT, head) for _ in range(theta - 1)]
+
+    def tree_rows(self, rows):
+        """Register the R level-1 rows int32[R][N] of a tree function (thfhe.lut.tree_test_vectors); returns row0, the index of the first.  Equal row
+        blocks share one row0."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        if rows.ndim != 2 or rows.shape[0] < 1:
+            raise ValueError("tree_rows: expected int32[R][N]")
+        key = ("tv1", rows.shape, rows.tobytes())
+        if key not in self._ids:
+            self._ids[key] = len(self.tv1)
+            self.tv1.extend(rows)
+        return self._ids[key]
+
+    def tree(self, row0, lo_inputs, hi_inputs, p_hi, lo_weights=None, hi_weights=None, lo_bias=0, hi_bias=0, theta1=1):
+        """A TREE node: f(hi, lo) of two encrypted digits by the two-digit tree PBS (R = p_hi / theta1 level-1 rotations of the rows row0 .. row0 + R - 1
+        on the `lo` digit, box packing, one rotation of the packed table on the `hi` digit), one level, one output wire.  lo_inputs and hi_inputs
+        number at most three together; the weights default to ones."""
+        lo_inputs, hi_inputs = list(lo_inputs), list(hi_inputs)
+        lo_weights = (1,) * len(lo_inputs) if lo_weights is None else tuple(lo_weights)
+        hi_weights = (1,) * len(hi_inputs) if hi_weights is None else tuple(hi_weights)
+        if not lo_inputs or not hi_inputs or len(lo_inputs) + len(hi_inputs) > 3:
+            raise ValueError("a TREE node takes at least one lo and one hi input, at most three together")
+        if len(lo_weights) != len(lo_inputs) or len(hi_weights) != len(hi_inputs):
+            raise ValueError("one weight per input")
+        if theta1 not in (1, 2, 4) or p_hi % theta1:
+            raise ValueError("theta1 must be 1, 2 or 4 and divide p_hi")
+        if not 0 <= row0 or row0 + p_hi // theta1 > len(self.tv1):
+            raise ValueError("row0 + R exceeds the registered level-1 rows (tree_rows)")
+        lo = (len(lo_inputs), tuple(_wrap32(w) for w in list(lo_weights) + [0] * (3 - len(lo_weights))), _wrap32(lo_bias), int(theta1))
+        hi = (len(hi_inputs), tuple(_wrap32(w) for w in list(hi_weights) + [0] * (3 - len(hi_weights))), _wrap32(hi_bias), 1)
+        ti = self._tree_id(lo, hi, p_hi)
+        ops = lo_inputs + hi_inputs
+        w = self.gate(TREE, *(ops + [-1] * (3 - len(ops))))
+        self.ext_rows[len(self.gates) - 1] = (ti, int(row0))
+        return w
+
+    def select(self, index_inputs, first, p, weights=None, bias=0):
+        """A SELECT node: the wire among first .. first + p - 1 (all defined above) that the encrypted digit sum_q weights[q] * index_inputs[q] + (0, bias)
+        points at, obliviously: box packing of the p candidates and one rotation of the packed table.  One level, one output wire."""
+        index_inputs = list(index_inputs)
+        weights = (1,) * len(index_inputs) if weights is None else tuple(weights)
+        if not 1 <= len(index_inputs) <= 3 or len(weights) != len(index_inputs):
+            raise ValueError("a SELECT node takes 1 to 3 index inputs and one weight per input")
+        hi = (len(index_inputs), tuple(_wrap32(w) for w in list(weights) + [0] * (3 - len(weights))), _wrap32(bias), 1)
+        if first < 0 or first + p > self.n_wires():
+            raise ValueError("the candidates first .. first + p - 1 must be wires defined above the node")
+        ti = self._tree_id(None, hi, p)
+        w = self.gate(SELECT, *(index_inputs + [-1] * (3 - len(index_inputs))))
+        self.ext_rows[len(self.gates) - 1] = (ti, int(first))
+        return w
+
     def has_luts(self):
         return bool(self.lut_rows)
 
+    def has_tree_nodes(self):
+        """Whether the circuit holds a LUT_ENC, SELECT or TREE node (it then runs on thfhe_dag_run_tree_batch)."""
+        return bool(self.ext_rows)
+
     def nodes(self):
-        """int32[n_gates][6] = (op, in0, in1, in2, spec, lut): the rows of thfhe_dag_run_lut_batch (spec = lut = -1 on gate rows)."""
-        rows = [tuple(g) + self.lut_rows.get(i, (-1, -1)) for i, g in enumerate(self.gates)]
+        """int32[n_gates][6] = (op, in0, in1, in2, spec, lut): the rows of thfhe_dag_run_lut_batch (spec = lut = -1 on gate rows); LUT_ENC, SELECT and
+        TREE rows (thfhe_dag_run_tree_batch) carry (spec, etab), (tree, first), (tree, row0)."""
+        rows = [tuple(g) + (self.lut_rows.get(i) or self.ext_rows.get(i, (-1, -1))) for i, g in enumerate(self.gates)]
         return np.array(rows, np.int32).reshape(-1, 6)
 
     def n_wires(self):
@@ -92,6 +198,9 @@ class Circuit:
                 d = depth[a]
             else:
                 d = max(depth[w] for w in (a, b, c) if w >= 0)
+                if op == SELECT:   # its candidates count too
+                    ti, first = self.ext_rows[gi]
+                    d = max(d, depth[first:first + self.tree_specs[ti][2]].max())
                 if op not in (NOT, COPY):
                     d += 1
             depth[self.n_inputs + gi] = d
@@ -106,6 +215,9 @@ class Circuit:
                  depth=len([l for l in self.levels() if self.gates[l[0]][0] not in (NOT, COPY)]))
         if self.lut_rows:
             c["luts"] = ops.count(LUT)
+        if self.ext_rows:   # a TREE node: R level-1 rotations + the selection rotation
+            extra = sum(self.tree_specs[self.ext_rows[i][0]][2] // self.tree_specs[self.ext_rows[i][0]][0][3] for i, o in enumerate(ops) if o == TREE)
+            c.update(rotations=c["rotations"] + extra, luts_enc=ops.count(LUT_ENC), selects=ops.count(SELECT), trees=ops.count(TREE))
         return c
 
 
@@ -490,13 +602,84 @@ def to_gate_bit(cir, w, table_id=None, N=1024, torus_bits=32):
     return cir.lut(table_id, [w])[0]
 
 
+def tree_mul_digits(cir, a, b, N=1024):
+    """The product of two 3-bit digits (p = 8 wires a, b) as its low and high 3-bit digits: two TREE nodes with p_hi = p_lo = p_out = 8 and
+    theta1 = 2 (4 + 1 rotations each; a shape of DESIGN 4.11's supported set), a on the level-1 digit, b on the selection digit.  Returns (low, high)."""
+    from . import lut
+    lo_rows = cir.tree_rows(lut.tree_test_vectors(lambda h, l: (h * l) % 8, 8, 8, 8, theta=2, N=N))
+    hi_rows = cir.tree_rows(lut.tree_test_vectors(lambda h, l: (h * l) // 8, 8, 8, 8, theta=2, N=N))
+    return cir.tree(lo_rows, [a], [b], 8, theta1=2), cir.tree(hi_rows, [a], [b], 8, theta1=2)
+
+
 def _tables(ck, cir):
     return np.stack([np.asarray(t, ck._tv_dtype).reshape(ck.params.N) for t in cir.tables])
 
 
+def _rotate_noiseless(x, tv, theta):
+    """Coefficients 0 .. theta-1 of X^{-bar} tv for the noiseless phase word x: what a programmable bootstrap of table tv returns on it."""
+    N = tv.shape[0]
+    steps = 2 * N // theta
+    shift = 32 - (steps.bit_length() - 1)
+    bar = ((((int(x) & 0xFFFFFFFF) + (1 << (shift - 1))) >> shift) % steps) * theta
+    out = []
+    for j in range(theta):
+        k = (bar + j) % (2 * N)
+        out.append(int(tv[k]) if k < N else -int(tv[k - N]))
+    return out
+
+
+def _simulate_words(cir, input_words):
+    """simulate for circuits with LUT-type nodes: noiseless Torus32 phase words in (thfhe.lut.encode of the digits; +-2^29 for gate bits), the
+    noiseless phase word of every wire out (thfhe.lut.decode gives the digits)."""
+    from . import lut
+    N = len(cir.tables[0]) if cir.tables else (len(cir.tv1[0]) if cir.tv1 else 1024)
+    v = np.zeros(cir.n_wires(), np.int64)
+    v[:cir.n_inputs] = np.asarray(input_words, np.int64)
+    wrap = lambda t: ((int(t) + (1 << 31)) % (1 << 32)) - (1 << 31)
+    lin = lambda spec, ws: wrap(sum(int(w) * int(v[i]) for w, i in zip(spec[1], ws)) + spec[2])
+    gates_only = Circuit()
+    for gi, (op, a, b, c) in enumerate(cir.gates):
+        o = cir.n_inputs + gi
+        if op == LUT_OUT:
+            continue
+        if op in (LUT, LUT_ENC):
+            si, ti = cir.lut_rows[gi] if op == LUT else cir.ext_rows[gi]
+            tv = cir.tables[ti] if op == LUT else cir.enc_tables[ti][2]
+            if tv is None:
+                raise ValueError("simulate: the encrypted table was registered without its plaintext")
+            spec = cir.specs[si]
+            outs = _rotate_noiseless(lin(spec, (a, b, c)[:spec[0]]), np.asarray(tv), spec[3])
+            v[o:o + spec[3]] = [wrap(t) for t in outs]
+        elif op == SELECT:
+            ti, first = cir.ext_rows[gi]
+            _, hi, p = cir.tree_specs[ti]
+            tv = lut.test_vector(lut._to_i32(v[first:first + p]), p, N=N)
+            v[o] = wrap(_rotate_noiseless(lin(hi, (a, b, c)[:hi[0]]), tv, 1)[0])
+        elif op == TREE:
+            ti, row0 = cir.ext_rows[gi]
+            lo, hi, p = cir.tree_specs[ti]
+            ops = (a, b, c)
+            x = lin(lo, ops[:lo[0]])
+            cands = [wrap(t) for r in range(p // lo[3]) for t in _rotate_noiseless(x, np.asarray(cir.tv1[row0 + r]), lo[3])]
+            tv = lut.test_vector(lut._to_i32(np.array(cands, np.int64)), p, N=N)
+            v[o] = wrap(_rotate_noiseless(lin(hi, ops[lo[0]:lo[0] + hi[0]]), tv, 1)[0])
+        elif op == NOT:
+            v[o] = wrap(-int(v[a]))
+        elif op == COPY:
+            v[o] = v[a]
+        else:   # a bootstrapped gate on the signs of its operands
+            gates_only.n_inputs, gates_only.gates = o, [(op, a, b, c)]
+            v[o] = (1 << 29) if simulate(gates_only, v[:o] > 0)[o] else -(1 << 29)
+    return lut._to_i32(v)
+
+
 def simulate(cir, input_bits):
-    """Plaintext evaluation of the DAG (wiring check): bool[n_inputs] -> bool[n_wires]."""
+    """Plaintext evaluation of the DAG (wiring check): bool[n_inputs] -> bool[n_wires].  Circuits with LUT, LUT_ENC, SELECT or TREE nodes work on
+    integer digits in their torus encoding: int32[n_inputs] noiseless phase words (thfhe.lut.encode(digit, p); +-2^29 for gate bits) -> the
+    noiseless phase word int32[n_wires] of every wire, which thfhe.lut.decode turns into digits."""
     from . import ANDNY, ANDYN, NAND, NOR, ORNY, ORYN, XNOR
+    if cir.lut_rows or cir.ext_rows:
+        return _simulate_words(cir, input_bits)
     v = np.zeros(cir.n_wires(), bool)
     v[:cir.n_inputs] = np.asarray(input_bits, bool)
     f = {NAND: lambda a, b: not (a and b), OR: lambda a, b: a or b, AND: lambda a, b: a and b, XOR: lambda a, b: a != b,
@@ -538,14 +721,25 @@ def simulate_mk(cir, input_bits):
 
 
 # ---- evaluator --------------------------------------------------------------------------------------------------------
-def evaluate(ck, cir, input_records, stats=None):
+def _run_tree_batch(ck, cir, x, sel, pack):
+    enc = cir.enc_tables
+    return ck.dag_run_tree_batch(x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None,
+                                 np.stack([e[0] for e in enc]) if enc else None, np.stack([e[1] for e in enc]) if enc else None,
+                                 cir.tree_specs, np.stack(cir.tv1) if cir.tv1 else None, sel, pack)
+
+
+def evaluate(ck, cir, input_records, stats=None, pack=None):
     """Run the DAG on the engine.  input_records: int32[n_inputs][n+1].  Returns int32[n_wires][n+1].
     Single-key contexts use the native scheduler / executor (thfhe_dag_run: wires stay in HBM, no host round trip per level);
     multi-key contexts go level by level through thfhe_mk_gates_mixed (evaluate_levels).  Circuits with LUT nodes run on
-    thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch."""
-    if cir.has_luts():
+    thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch, circuits with encrypted-table, select or tree nodes on thfhe_dag_run_tree_batch
+    (pack: the threshold.PolyContext holding the packing key)."""
+    if cir.has_luts() or cir.has_tree_nodes():
         x = np.ascontiguousarray(input_records, np.int32).reshape(1, cir.n_inputs, ck.words)
-        out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir))
+        if cir.has_tree_nodes():
+            out, st = _run_tree_batch(ck, cir, x, None, pack)
+        else:
+            out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir))
         if stats is not None:
             stats.update(cir.census(), **st)
         return np.concatenate([x[0], out[0]])
@@ -557,17 +751,20 @@ def evaluate(ck, cir, input_records, stats=None):
     return evaluate_levels(ck, cir, input_records, stats)
 
 
-def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None):
+def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None, pack=None):
     """`instances` evaluations of one DAG side by side.  input_records: int32[instances][n_inputs][words]; out_wires: wire ids to return
     (None: every wire).  Returns int32[instances][len(out_wires) or n_wires][words].  Contexts with the native executor use
     thfhe_dag_run_batch / thfhe_mk_dag_run_batch (wire tables stay in HBM), circuits with LUT nodes thfhe_dag_run_lut_batch /
-    thfhe_mk_dag_run_lut_batch; others are driven level by level from the host, a level's call holding the gates of all instances."""
+    thfhe_mk_dag_run_lut_batch, circuits with encrypted-table, select or tree nodes thfhe_dag_run_tree_batch (pack: the threshold.PolyContext
+    holding the packing key); others are driven level by level from the host, a level's call holding the gates of all instances."""
     x = np.ascontiguousarray(input_records, np.int32)
     Q, n_in, words = x.shape
     assert n_in == cir.n_inputs
-    if cir.has_luts() or hasattr(ck, "dag_run_batch"):
+    if cir.has_luts() or cir.has_tree_nodes() or hasattr(ck, "dag_run_batch"):
         sel = None if out_wires is None else np.asarray(out_wires, np.int32)
-        if cir.has_luts():
+        if cir.has_tree_nodes():
+            out, st = _run_tree_batch(ck, cir, x, sel, pack)
+        elif cir.has_luts():
             out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir), sel)
         else:
             out, st = ck.dag_run_batch(x, np.array(cir.gates, np.int32).reshape(-1, 4), sel)
@@ -601,9 +798,49 @@ def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None):
     return vals if out_wires is None else vals[:, np.asarray(out_wires, np.int64)]
 
 
-def evaluate_levels(ck, cir, input_records, stats=None):
+def _levels_ext(ck, cir, level, vals, pack):
+    """The LUT_ENC, SELECT and TREE nodes of one level through the public flat calls (lut_bootstrap_enc, PackBoxes, tree_lut_bootstrap); returns
+    the number of calls' groups."""
+    from .threshold import PackBoxes
+    gates, base, groups = cir.gates, cir.n_inputs, 0
+    by = {}
+    for g in level:
+        if gates[g][0] in (LUT_ENC, SELECT, TREE):
+            x, _ = cir.ext_rows[g]
+            by.setdefault((gates[g][0], cir.specs[x][3] if gates[g][0] == LUT_ENC else 0, x), []).append(g)
+    for (op, theta, x), G in sorted(by.items()):
+        groups += 1
+        out = base + np.array(G)
+        if op == LUT_ENC:
+            nin, w, bias, _ = cir.specs[x]
+            ins = [vals[[gates[g][1 + q] for g in G]] for q in range(nin)]
+            r = ck.lut_bootstrap_enc(np.stack([e[0] for e in cir.enc_tables]), np.stack([e[1] for e in cir.enc_tables]), *ins, weights=w[:nin], bias=bias,
+                                     theta=theta, lut_index=[cir.ext_rows[g][1] for g in G])
+            for j in range(theta):
+                vals[out + j] = r[:, j]
+            continue
+        lo, hi, p = cir.tree_specs[x]
+        if op == SELECT:
+            cands = vals[np.concatenate([cir.ext_rows[g][1] + np.arange(p) for g in G])]
+            a, b = PackBoxes(pack, cands, p)
+            ins = [vals[[gates[g][1 + q] for g in G]] for q in range(hi[0])]
+            vals[out] = ck.lut_bootstrap_enc(a, b, *ins, weights=hi[1][:hi[0]], bias=hi[2], lut_index=np.arange(len(G)))[:, 0]
+        else:
+            R = p // lo[3]
+            row0s = sorted({cir.ext_rows[g][1] for g in G})
+            tv1 = np.stack([np.stack(cir.tv1[r:r + R]) for r in row0s])
+            lo_in = tuple(vals[[gates[g][1 + q] for g in G]] for q in range(lo[0]))
+            hi_in = tuple(vals[[gates[g][1 + lo[0] + q] for g in G]] for q in range(hi[0]))
+            vals[out] = ck.tree_lut_bootstrap(pack, tv1, lo_in, hi_in, p_hi=p, weights_lo=lo[1][:lo[0]], bias_lo=lo[2], theta=lo[3], weights_hi=hi[1][:hi[0]],
+                                              bias_hi=hi[2], table_index=[row0s.index(cir.ext_rows[g][1]) for g in G])
+    return groups
+
+
+def evaluate_levels(ck, cir, input_records, stats=None, pack=None):
     """The same schedule driven from the host: one host-buffer call per level (works for single-key and multi-key contexts).  LUT nodes go
-    through ck.lut_bootstrap, one call per (theta, spec) of a level: the yardstick of the native LUT-node executor."""
+    through ck.lut_bootstrap, one call per (theta, spec) of a level: the yardstick of the native LUT-node executor.  LUT_ENC, SELECT and TREE nodes
+    go through lut_bootstrap_enc, PackBoxes + lut_bootstrap_enc and tree_lut_bootstrap (pack: the packing context): the yardstick of
+    thfhe_dag_run_tree_batch."""
     from . import AND3 as _AND3
     words = ck.words
     vals = np.zeros((cir.n_wires(), words), np.int32)
@@ -633,7 +870,9 @@ def evaluate_levels(ck, cir, input_records, stats=None):
                 for j in range(theta):
                     vals[base + np.array(G) + j] = r[:, j]
                 launches += 1
-        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT)]
+        if cir.ext_rows:
+            launches += _levels_ext(ck, cir, level, vals, pack)
+        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT, LUT_ENC, SELECT, TREE)]
         mux = [g for g in level if gates[g][0] == MUX]
         and3 = [g for g in level if gates[g][0] == _AND3]   # 3-gen three-input AND: its own gate class (thfhe_mk_gates)
         if and3:
