@@ -292,6 +292,27 @@ def test_tree_slices_and_table_index(sk128, ck, pack):
     assert np.array_equal(whole[picks], np.stack(pmap(lambda g: model(orc, pk, p, tv1[tab[g]], [xl], [xh], g, 1, 4), picks)))
 
 
+def test_tree_three_lo_and_three_hi_operands_in_slices(sk128, ck, pack):
+    # p_hi = 8, theta1 = 4 (R = 2), two tables chosen per sample, three weighted `lo` and three weighted `hi` operands with both biases, 10 samples
+    # in slices of 3 (24 candidates).  Random record and table words: every word of the output against the three-call composition.
+    p, K, orc = sk128
+    pc, pk = pack
+    rng = np.random.default_rng(90)
+    count = 10
+    word = lambda *shape: rng.integers(-2**31, 2**31, shape, dtype=np.int64).astype(np.int32)
+    tv1 = word(2, 2, N)
+    lo, hi = [word(count, p.n + 1) for _ in range(3)], [word(count, p.n + 1) for _ in range(3)]
+    tab = rng.integers(0, 2, count).astype(np.int32)
+    w_lo, w_hi, b_lo, b_hi = (3, -5, 7), (-2, 9, 1), 0x12345678, -0x0abcdef1
+    try:
+        ck.set_tree_slice(24)
+        got = ck.tree_lut_bootstrap(pc, tv1, tuple(lo), tuple(hi), p_hi=8, theta=4, weights_lo=w_lo, bias_lo=b_lo, weights_hi=w_hi, bias_hi=b_hi, table_index=tab)
+    finally:
+        ck.set_tree_slice(65536)
+    assert got.shape == (count, p.n + 1)
+    assert np.array_equal(got, compose(ck, pc, tv1, lo, hi, 8, 4, w_lo=w_lo, b_lo=b_lo, w_hi=w_hi, b_hi=b_hi, table_index=tab))
+
+
 def test_tree_131072_level1_jobs(sk128, ck, pack):
     # 8 192 samples x R = 16 (p = 16 digits, theta1 = 1, p_out = 8): 131 072 level-1 rotations in two slices of 65 536, 8 192 level-2 ones.
     # Decrypt-exact on all; the model on two samples (17 oracle rotations each, ~10 s per sample on one core)

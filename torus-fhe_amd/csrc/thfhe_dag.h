@@ -1,7 +1,8 @@
 // thfhe_dag.h -- the gate-DAG front end shared by the single-key and the 3-gen multi-key engines:
 // an ASAP levelising scheduler for the reference's circuits (src/KNN_medical_data.cpp:127-489, J/3gen_mk_gates.jl:183-362), and the
 // gather / scatter kernels of the device-resident executor.  LUT nodes (thfhe_dag_run_lut_batch): programmable bootstraps among the
-// gates, fed by a fused prologue that reads their operands from the wire table, their theta outputs scattered into consecutive wires.
+// gates, fed by the shared prologue reading their operands from the wire table (LutWireSrc, thfhe_lut_prologue.h), their theta outputs scattered
+// into consecutive wires.
 // Encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch, DESIGN 4.12, single key): three more node kinds, planned here, run by the engine.
 #ifndef THFHE_DAG_H
 #define THFHE_DAG_H
@@ -17,6 +18,7 @@
 #include "../../include/thfhe_hip.h"
 #include "thfhe_common.h"
 #include "thfhe_devctx.h"
+#include "thfhe_lut_prologue.h"
 
 namespace {
 using namespace thfhe;
@@ -55,36 +57,6 @@ __global__ __launch_bounds__(256) void dag_wire_linear_kernel(int32_t *__restric
     const uint32_t v = (uint32_t)wires[(base + in_idx[g]) * words + i];
     wires[(base + out_idx[g]) * words + i] = (int32_t)(ops[g] == THFHE_NOT ? 0u - v : v);
 }
-// Fused prologue of a LUT launch group: job j of the slice is node g of instance q (G = first + j = q cnt + g).  Its 1-3 operands come straight
-// from the wire table, weighted by its spec, the bias added to the body, every word rounded to a multiple of theta in Z_2N -- the arithmetic of
-// sk_lut_prologue_kernel / mk_lut_prologue_kernel word for word -- and the node's table index goes to lut_idx[j] for the rotation.
-// n = mask words of a record (n, or P n on the 3-gen scheme), pad = row stride of bara.  One thread per word; grid.y strides over the jobs.
-__global__ __launch_bounds__(256) void dag_lut_prologue_kernel(const int32_t *__restrict__ wires, const int32_t *__restrict__ t0, const int32_t *__restrict__ t1,
-                                                               const int32_t *__restrict__ t2, const int32_t *__restrict__ t_spec,
-                                                               const int32_t *__restrict__ t_lut, const thfhe_lut_spec *__restrict__ specs, long first,
-                                                               long total, long cnt, size_t n_wires, int n, int pad, int log2_2n, int32_t *__restrict__ bara,
-                                                               int32_t *__restrict__ barb, int32_t *__restrict__ lut_idx) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i > n) return;
-    const size_t words = (size_t)n + 1;
-    for (long j = blockIdx.y; j < total; j += gridDim.y) {
-        const long G = first + j, q = G / cnt, g = G - q * cnt;
-        const thfhe_lut_spec sp = specs[t_spec[g]];
-        const int32_t *rec = wires + (size_t)q * n_wires * words + i;
-        uint32_t v = (uint32_t)sp.weights[0] * (uint32_t)rec[(size_t)t0[g] * words];
-        if (sp.n_inputs > 1) v += (uint32_t)sp.weights[1] * (uint32_t)rec[(size_t)t1[g] * words];
-        if (sp.n_inputs > 2) v += (uint32_t)sp.weights[2] * (uint32_t)rec[(size_t)t2[g] * words];
-        if (i == n) v += (uint32_t)sp.bias;
-        const int log2_theta = sp.theta == 4 ? 2 : sp.theta >> 1;
-        const int32_t bar = (int32_t)((uint32_t)modswitch2n((int32_t)v, log2_2n - log2_theta) << log2_theta);
-        if (i == n) {
-            barb[j] = bar;
-            lut_idx[j] = t_lut[g];
-        } else {
-            bara[j * pad + i] = bar;
-        }
-    }
-}
 // theta-record scatter of a LUT launch group: key-switched record r = j theta + t of the slice -> wire idx[g] + t of instance q
 __global__ __launch_bounds__(256) void dag_scatter_theta_kernel(const int32_t *__restrict__ src, const int32_t *__restrict__ idx, int32_t *__restrict__ wires,
                                                                 long first, long total, long cnt, size_t n_wires, int words, int theta) {
@@ -93,59 +65,6 @@ __global__ __launch_bounds__(256) void dag_scatter_theta_kernel(const int32_t *_
     if (r >= total * theta || i >= words) return;
     const long j = r / theta, t = r - j * theta, G = first + j, q = G / cnt, g = G - q * cnt;
     wires[((size_t)q * n_wires + idx[g] + t) * words + i] = src[r * words + i];
-}
-// Tree prologue (TREE launch group): node j of the slice (G = first + j = q cnt + g) reads its `lo` operands from the wire table ONCE
-// and serves its R level-1 jobs j R + r: the same bara / barb for each, table index row0[g] + r.  sk_tree_prologue_kernel's arithmetic over
-// dag_lut_prologue_kernel's addressing, the theta-rounded mod-switch included; the group's spec comes by value (one trees[] entry per group).
-__global__ __launch_bounds__(256) void dag_tree_prologue_kernel(const int32_t *__restrict__ wires, const int32_t *__restrict__ t0, const int32_t *__restrict__ t1,
-                                                                const int32_t *__restrict__ t2, const int32_t *__restrict__ t_row0, thfhe_lut_spec sp, int reps,
-                                                                long first, long total, long cnt, size_t n_wires, int n, int pad, int log2_2n,
-                                                                int32_t *__restrict__ bara, int32_t *__restrict__ barb, int32_t *__restrict__ lut_idx) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i > n) return;
-    const size_t words = (size_t)n + 1;
-    const int log2_theta = sp.theta == 4 ? 2 : sp.theta >> 1;
-    for (long j = blockIdx.y; j < total; j += gridDim.y) {
-        const long G = first + j, q = G / cnt, g = G - q * cnt;
-        const int32_t *rec = wires + (size_t)q * n_wires * words + i;
-        uint32_t v = (uint32_t)sp.weights[0] * (uint32_t)rec[(size_t)t0[g] * words];
-        if (sp.n_inputs > 1) v += (uint32_t)sp.weights[1] * (uint32_t)rec[(size_t)t1[g] * words];
-        if (sp.n_inputs > 2) v += (uint32_t)sp.weights[2] * (uint32_t)rec[(size_t)t2[g] * words];
-        if (i == n) v += (uint32_t)sp.bias;
-        const int32_t bar = (int32_t)((uint32_t)modswitch2n((int32_t)v, log2_2n - log2_theta) << log2_theta);
-        const size_t job0 = (size_t)j * reps;
-        if (i == n) {
-            const int32_t row0 = t_row0[g];
-            for (int r = 0; r < reps; r++) barb[job0 + r] = bar, lut_idx[job0 + r] = row0 + r;
-        } else {
-            for (int r = 0; r < reps; r++) bara[(job0 + r) * pad + i] = bar;
-        }
-    }
-}
-// Selection prologue (SELECT groups, level 2 of TREE groups): the index operands of node j from the wire table for the one-table-per-job rotation of
-// its own packed table: lut_idx[j] = j.  theta = 1: the plain mod-switch.
-__global__ __launch_bounds__(256) void dag_select_prologue_kernel(const int32_t *__restrict__ wires, const int32_t *__restrict__ t0, const int32_t *__restrict__ t1,
-                                                                  const int32_t *__restrict__ t2, thfhe_lut_spec sp, long first, long total, long cnt,
-                                                                  size_t n_wires, int n, int pad, int log2_2n, int32_t *__restrict__ bara,
-                                                                  int32_t *__restrict__ barb, int32_t *__restrict__ lut_idx) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i > n) return;
-    const size_t words = (size_t)n + 1;
-    for (long j = blockIdx.y; j < total; j += gridDim.y) {
-        const long G = first + j, q = G / cnt, g = G - q * cnt;
-        const int32_t *rec = wires + (size_t)q * n_wires * words + i;
-        uint32_t v = (uint32_t)sp.weights[0] * (uint32_t)rec[(size_t)t0[g] * words];
-        if (sp.n_inputs > 1) v += (uint32_t)sp.weights[1] * (uint32_t)rec[(size_t)t1[g] * words];
-        if (sp.n_inputs > 2) v += (uint32_t)sp.weights[2] * (uint32_t)rec[(size_t)t2[g] * words];
-        if (i == n) v += (uint32_t)sp.bias;
-        const int32_t bar = modswitch2n((int32_t)v, log2_2n);
-        if (i == n) {
-            barb[j] = bar;
-            lut_idx[j] = (int32_t)j;
-        } else {
-            bara[(size_t)j * pad + i] = bar;
-        }
-    }
 }
 // Candidate gather of a SELECT group: candidate r = j p + k of the slice is wire t_first[g] + k of instance q -> dst[r], the [jobs p][words] buffer
 // the box packing reads.  grid.y strides over the candidates.
@@ -395,22 +314,26 @@ struct DagBuffers {
     DevBuf specs;   // thfhe_lut_spec[n_specs] of a LUT run
 };
 
-// The slice of a LUT launch group that DagExecute hands to the engine: wire table, the group's index columns, jobs [first, first + total) of
-// cnt nodes per instance.  The engine runs dag_lut_prologue_kernel, its LUT rotation and the key switch of total x theta records into its
-// staging output.
+// The slice of a LUT or LUT_ENC launch group that DagExecute hands to the engine: wire table, the group's index columns, jobs
+// [first, first + total) of cnt nodes per instance; enc: t_lut names the run's encrypted tables.  The engine runs the prologue on src(), its LUT
+// rotation and the key switch of total x theta records into its staging output.
 struct DagLutSlice {
     const int32_t *wires, *t0, *t1, *t2, *t_spec, *t_lut;
     long first, total, cnt;
     size_t n_wires;
+    bool enc;
+    LutWireSrc<LutSpecPerNode, LutIdx::table> src(const thfhe_lut_spec *d_specs) const {
+        return {wires, t0, t1, t2, {d_specs, t_spec}, t_lut, first, cnt, n_wires, 1};
+    }
 };
 
-// A LUT_ENC, SELECT or TREE launch group as DagExecute hands it to the engine (thfhe_dag_run_tree_batch): the wire table, the group's index columns
-// (t_x, t_y = [spec | etab], [tree | first] or [tree | row0]), `all` = cnt nodes x instances jobs.  The engine cuts it into slices, runs the chain of
+// A SELECT or TREE launch group as DagExecute hands it to the engine (thfhe_dag_run_tree_batch): the wire table, the group's index columns
+// (t_y = a SELECT's first candidate wire, a TREE's row0), `all` = cnt nodes x instances jobs.  The engine cuts it into slices, runs the chain of
 // each and scatters the results into the wires t_out.
 struct DagExtGroup {
     int cls, tree;
     int32_t *wires;
-    const int32_t *t0, *t1, *t2, *t_out, *t_x, *t_y;
+    const int32_t *t0, *t1, *t2, *t_out, *t_y;
     long all, cnt;
     size_t n_wires;
 };
@@ -422,10 +345,10 @@ struct DagExtGroup {
 //   h_sel     wire ids to return (n_sel of them) or null = every gate wire [n_inputs, n_wires)
 //   h_out     int32[instances][n_sel or n_gates][words]
 // ensure(max_gates_per_slice) sizes the engine's workspace and staging and returns its staging pointers through the out-parameters.
-// LUT launch groups (plans of thfhe_dag_run_lut_batch): run_lut(theta, DagLutSlice) -> fused prologue + LUT rotation + key switch of the
-// slice's nodes x theta records into the staging output, then the theta-record scatter into wires out[g] + j.  ensure sizes for
-// plan.max_theta records per node.  LUT_ENC / SELECT / TREE groups (plans of thfhe_dag_run_tree_batch): run_ext(DagExtGroup) slices, runs and
-// scatters the whole group; ensure sizes the engine's buffers for them from the plan.
+// LUT and LUT_ENC launch groups: run_lut(theta, DagLutSlice) -> prologue + LUT rotation + key switch of the slice's nodes x theta records into
+// the staging output, then the theta-record scatter into wires out[g] + j.  ensure sizes for plan.max_theta records per node.  SELECT / TREE
+// groups (plans of thfhe_dag_run_tree_batch): run_ext(DagExtGroup) slices, runs and scatters the whole group.  An engine without run_ext
+// rejects all three kinds.
 template <typename Ensure, typename Run, typename RunLut = std::nullptr_t, typename RunExt = std::nullptr_t>
 int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int words, size_t n_inputs, size_t n_gates, size_t instances,
                 const int32_t *h_inputs, const int32_t *h_sel, size_t n_sel, int32_t *h_out, size_t slice_cap, Ensure ensure, Run run,
@@ -462,23 +385,25 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
             hipLaunchKernelGGL(dag_wire_linear_kernel, dim3((unsigned)all, wb), block, 0, stream, d_wires, t0, t_out, t_ops, all, cnt, n_wires, words);
             continue;
         }
-        if (cls >= kDagEnc) {
-            if constexpr (std::is_same_v<RunExt, std::nullptr_t>) {
-                rc = thfhe_fail(THFHE_E_INVALID, "encrypted-table, select or tree node in a run without them");
-            } else {
-                rc = run_ext(DagExtGroup{cls, plan.batches[b].tree, d_wires, t0, t1, t2, t_out, t_out + cnt, t_out + 2 * cnt, all, cnt, n_wires});
-            }
+        if (cls >= kDagEnc && std::is_same_v<RunExt, std::nullptr_t>) {
+            rc = thfhe_fail(THFHE_E_INVALID, "encrypted-table, select or tree node in a run without them");
             continue;
         }
-        if (cls >= 4) {
+        if (cls >= kDagSelect) {
+            if constexpr (!std::is_same_v<RunExt, std::nullptr_t>)
+                rc = run_ext(DagExtGroup{cls, plan.batches[b].tree, d_wires, t0, t1, t2, t_out, t_out + 2 * cnt, all, cnt, n_wires});
+            continue;
+        }
+        if (cls >= 4) {   // LUT groups, and LUT_ENC groups over the run's encrypted tables
             if constexpr (std::is_same_v<RunLut, std::nullptr_t>) {
                 rc = thfhe_fail(THFHE_E_INVALID, "LUT node in a gate-only run");
             } else {
-                const int theta = dag_lut_theta(cls);
+                const bool enc = cls >= kDagEnc;
+                const int theta = enc ? dag_enc_theta(cls) : dag_lut_theta(cls);
                 const int32_t *t_spec = t_out + cnt, *t_lut = t_spec + cnt;
                 for (long first = 0; first < all && rc == THFHE_OK; first += (long)slice) {
                     const long n = all - first < (long)slice ? all - first : (long)slice;
-                    rc = run_lut(theta, DagLutSlice{d_wires, t0, t1, t2, t_spec, t_lut, first, n, cnt, n_wires});
+                    rc = run_lut(theta, DagLutSlice{d_wires, t0, t1, t2, t_spec, t_lut, first, n, cnt, n_wires, enc});
                     if (!rc)
                         hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(n * theta), wb), block, 0, stream, stage_out, t_out, d_wires, first, n, cnt,
                                            n_wires, words, theta);

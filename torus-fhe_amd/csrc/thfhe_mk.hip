@@ -15,10 +15,10 @@
 //                             thfhe_rot2k.h (any number of digit row parts, N = 2048) and thfhe_rot4k.h (N = 4096) for the large-party sets
 //   ks_plain_kernel / ks_staged_kernel (thfhe_keyswitch.h)   P key switches of the extracted sample + the cross-party combine of b:
 //                             one workgroup per (sample, party, range), or from 192 samples on the rows staged in LDS for 32 samples
-//   mk_lut_prologue_kernel / mk_lut_acc_init_kernel / mk_extract_at_kernel   programmable bootstrap (thfhe_mk_lut_bootstrap): weighted
-//                             sum + mod-switch to multiples of theta, accumulator X^{-barb} * tv in global memory, the rotation kernels above
-//                             through acc_in / acc_out, extraction of theta coefficients; behind dag_lut_prologue_kernel (thfhe_dag.h) they
-//                             run the LUT nodes of the gate DAG (thfhe_mk_dag_run_lut_batch)
+//   lut_prologue_kernel (thfhe_lut_prologue.h, shared with thfhe_sk.hip) / mk_lut_acc_init_kernel / mk_extract_at_kernel   programmable bootstrap
+//                             (thfhe_mk_lut_bootstrap): weighted sum + mod-switch to multiples of theta, accumulator X^{-barb} * tv in
+//                             global memory, the rotation kernels above through acc_in / acc_out, extraction of theta coefficients; with the
+//                             prologue reading the wire table they run the LUT nodes of the gate DAG (thfhe_mk_dag_run_lut_batch)
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -860,27 +860,7 @@ __global__ __launch_bounds__(256) void mk_acc_init_2k_kernel(const int32_t *__re
 // programmable bootstrap (thfhe_mk_lut_bootstrap): only the two ends of the rotation are new; the rotation kernels take the
 // accumulator from global memory and return it there (MKBRArgs::acc_in / acc_out).
 // ------------------------------------------------------------------------------------------------------
-// prologue: x = w0 in0 + w1 in1 + w2 in2 + (0, ..., 0, bias) word-wise mod 2^32 over the P n + 1 record words, then every word rounded to a
-// multiple of theta in Z_2N: bar = modswitch_{2N/theta}(word) * theta (theta = 1: mk_prologue_kernel's mod-switch).  One thread per word,
-// grid.y strides over the samples.
-__global__ __launch_bounds__(256) void mk_lut_prologue_kernel(const int32_t *__restrict__ in0, const int32_t *__restrict__ in1,
-                                                               const int32_t *__restrict__ in2, int n_inputs, int32_t w0, int32_t w1, int32_t w2,
-                                                               int32_t bias, int log2_theta, int words, int w_pad, int log2_2n, long jobs,
-                                                               int32_t *__restrict__ bara, int32_t *__restrict__ barb) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i > words) return;
-    for (long job = blockIdx.y; job < jobs; job += gridDim.y) {
-        const size_t off = (size_t)job * (words + 1) + i;
-        uint32_t v = (uint32_t)w0 * (uint32_t)in0[off];
-        if (n_inputs > 1) v += (uint32_t)w1 * (uint32_t)in1[off];
-        if (n_inputs > 2) v += (uint32_t)w2 * (uint32_t)in2[off];
-        if (i == words) v += (uint32_t)bias;
-        const int32_t bar = (int32_t)((uint32_t)modswitch2n((int32_t)v, log2_2n - log2_theta) << log2_theta);
-        if (i == words) barb[job] = bar;
-        else bara[job * w_pad + i] = bar;
-    }
-}
-
+// prologue: lut_prologue_kernel (thfhe_lut_prologue.h) over the P n + 1 record words.
 // accumulator start acc[job] = (0, X^{-barb} * tv[lut_idx[job]]) over Torus64 (oracle_mul_by_monomial64): coefficient q is tv[(q + barb) mod N],
 // negated when (q + barb) mod 2N >= N.  mk_acc_init_2k_kernel with a per-sample table instead of a constant; N = 1024, 2048 or 4096.
 __global__ __launch_bounds__(256) void mk_lut_acc_init_kernel(const int32_t *__restrict__ barb, const int64_t *__restrict__ tv,
@@ -1046,9 +1026,8 @@ int mk_enqueue_lut(thfhe_mk_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0,
     int rc = mk_lut_workspace(c, count, sp.theta);
     if (rc) return rc;
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
-    dim3 pg((unsigned)((c->words + 1 + 255) / 256), (unsigned)(count < 65535 ? count : 65535));
-    hipLaunchKernelGGL(mk_lut_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, sp.n_inputs, sp.weights[0], sp.weights[1], sp.weights[2],
-                       sp.bias, ilog2(sp.theta), c->words, c->w_pad, c->log2_2n, (long)count, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
+    lut_prologue_launch(LutFlatSrc<LutIdx::none>{d0, d1, d2, sp, 1, nullptr}, count, c->words, c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(),
+                        c->d_barb.as<int32_t>(), nullptr, c->stream);
     return mk_enqueue_lut_rotation(c, sp.theta, count, d_tv, d_idx, d_dst);
 }
 
@@ -1367,7 +1346,7 @@ int thfhe_mk_dag_run_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inpu
 }
 
 // LUT nodes among the 3-gen gates: the gate classes run as in thfhe_mk_dag_run_batch; a LUT launch group runs the fused
-// prologue (dag_lut_prologue_kernel over the P n + 1 record words), then mk_enqueue_lut_rotation with the key switch into the staging output.
+// prologue (lut_prologue_kernel on the wire table, over the P n + 1 record words), then mk_enqueue_lut_rotation with the key switch into the staging output.
 int thfhe_mk_dag_run_lut_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
                                const thfhe_lut_spec *specs, int n_specs, const int64_t *tv, int n_luts, size_t instances, const int32_t *out_wires,
                                size_t n_out, int32_t *outputs, int64_t *stats) {
@@ -1398,10 +1377,8 @@ int thfhe_mk_dag_run_lut_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_
         },
         [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); },
         [&](int theta, const DagLutSlice &s) {
-            const dim3 pg((unsigned)((c->words + 1 + 255) / 256), (unsigned)(s.total < 65535 ? s.total : 65535));
-            hipLaunchKernelGGL(dag_lut_prologue_kernel, pg, dim3(256), 0, c->stream, s.wires, s.t0, s.t1, s.t2, s.t_spec, s.t_lut,
-                               (const thfhe_lut_spec *)c->dag.specs.as<thfhe_lut_spec>(), s.first, s.total, s.cnt, s.n_wires, c->words, c->w_pad, c->log2_2n,
-                               c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
+            lut_prologue_launch(s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, c->words, c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(),
+                                c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>(), c->stream);
             return mk_enqueue_lut_rotation(c, theta, (size_t)s.total, c->d_tv.as<int64_t>(), c->d_lut_idx.as<int32_t>(), c->stage.out_ptr());
         });
 }

@@ -5,11 +5,11 @@
 //   (thfhe_transform.h)       rows -> two-limb FP64 spectra in the blind-rotate kernel's register order
 //   sk_prologue_kernel        gate linear part (J/gates.jl:15-177) + mod-switch decode_message(.,2N)
 //                             (J/bootstrap.jl:80-81) -> bara[job][n], barb[job]
-//   sk_lut_prologue_kernel    programmable bootstrap (thfhe_lut_bootstrap): weighted sum of 1-3 inputs + bias, mod-switch to multiples of theta;
-//                             the blind-rotate kernels' LUT instantiations start from a test vector and extract theta coefficients;
-//                             LUT nodes of the gate DAG (thfhe_dag_run_lut_batch) use them behind dag_lut_prologue_kernel (thfhe_dag.h);
-//                             encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch) behind dag_tree_prologue_kernel /
-//                             dag_select_prologue_kernel / dag_select_gather_kernel (thfhe_dag.h)
+//   lut_prologue_kernel       programmable bootstrap (thfhe_lut_bootstrap): weighted sum of 1-3 inputs + bias, mod-switch to multiples of theta
+//   (thfhe_lut_prologue.h,    (DESIGN 4.7); one kernel for every PBS front half, instantiated on where a job's operands live: contiguous arrays
+//   shared with thfhe_mk.hip) (the flat calls, both levels of thfhe_tree_lut_bootstrap) or the gate DAG's wire table (LUT, LUT_ENC,
+//                             SELECT and TREE nodes; dag_select_gather_kernel in thfhe_dag.h collects a SELECT's candidates).
+//                             The blind-rotate kernels' LUT instantiations start from a test vector and extract theta coefficients
 //   sk_blind_rotate_ring_kernel / sk_blind_rotate_coop_kernel   blind_rotate_and_extract (J/bootstrap.jl:38-65): accumulator in
 //                             LDS for all n CMuxes; throughput (8 gates per workgroup, key through an LDS-DMA ring) and latency
 //                             (one workgroup per gate) variants
@@ -86,56 +86,6 @@ __global__ __launch_bounds__(256) void sk_prologue_kernel(const int32_t *__restr
         barb[job] = modswitch2n((int32_t)v, log2_2n);
     } else {
         bara[job * n_pad + i] = modswitch2n((int32_t)v, log2_2n);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// programmable-bootstrap prologue: x = w0 in0 + w1 in1 + w2 in2 + (0, ..., 0, bias) word-wise mod 2^32, then every word rounded to a
-// multiple of theta in Z_2N: bar = modswitch_{2N/theta}(word) * theta (theta = 1: modswitch2n).  grid.y strides over the jobs.
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sk_lut_prologue_kernel(const int32_t *__restrict__ in0, const int32_t *__restrict__ in1,
-                                                               const int32_t *__restrict__ in2, int n_inputs, int32_t w0, int32_t w1, int32_t w2,
-                                                               int32_t bias, int log2_theta, int n, int n_pad, int log2_2n, long jobs,
-                                                               int32_t *__restrict__ bara, int32_t *__restrict__ barb) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i > n) return;
-    for (long job = blockIdx.y; job < jobs; job += gridDim.y) {
-        const size_t off = (size_t)job * (n + 1) + i;
-        uint32_t v = (uint32_t)w0 * (uint32_t)in0[off];
-        if (n_inputs > 1) v += (uint32_t)w1 * (uint32_t)in1[off];
-        if (n_inputs > 2) v += (uint32_t)w2 * (uint32_t)in2[off];
-        if (i == n) v += (uint32_t)bias;
-        const int32_t bar = (int32_t)((uint32_t)modswitch2n((int32_t)v, log2_2n - log2_theta) << log2_theta);
-        if (i == n) barb[job] = bar;
-        else bara[job * n_pad + i] = bar;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// tree-PBS prologue (thfhe_tree_lut_bootstrap): sk_lut_prologue_kernel with every sample's record serving `reps` jobs.  Job
-// s * reps + r reads sample s and looks up table base(s) * reps + r, base(s) = table_index[s], or s (identity: level 2, the sample's own
-// packed table), or 0.
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sk_tree_prologue_kernel(const int32_t *__restrict__ in0, const int32_t *__restrict__ in1,
-                                                                const int32_t *__restrict__ in2, int n_inputs, int32_t w0, int32_t w1, int32_t w2,
-                                                                int32_t bias, int log2_theta, int n, int n_pad, int log2_2n, long jobs, int reps,
-                                                                const int32_t *__restrict__ table_index, int identity, int32_t *__restrict__ bara,
-                                                                int32_t *__restrict__ barb, int32_t *__restrict__ lut_idx) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i > n) return;
-    for (long job = blockIdx.y; job < jobs; job += gridDim.y) {
-        const long s = job / reps;
-        const size_t off = (size_t)s * (n + 1) + i;
-        uint32_t v = (uint32_t)w0 * (uint32_t)in0[off];
-        if (n_inputs > 1) v += (uint32_t)w1 * (uint32_t)in1[off];
-        if (n_inputs > 2) v += (uint32_t)w2 * (uint32_t)in2[off];
-        if (i == n) v += (uint32_t)bias;
-        const int32_t bar = (int32_t)((uint32_t)modswitch2n((int32_t)v, log2_2n - log2_theta) << log2_theta);
-        if (i == n) {
-            barb[job] = bar;
-            const long base = table_index ? table_index[s] : (identity ? s : 0);
-            lut_idx[job] = (int32_t)(base * reps + (job - s * reps));
-        } else bara[job * n_pad + i] = bar;
     }
 }
 
@@ -648,28 +598,6 @@ int enqueue_rotations(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1
     return THFHE_OK;
 }
 
-// programmable bootstrap of `count` samples (lut prologue + LUT blind rotations) into c->d_u: count x theta records of N+1 words;
-// d_tva: the masks of encrypted tables (d_tv their bodies), or null: plaintext tables
-int enqueue_lut_rotations(thfhe_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0, const int32_t *d1, const int32_t *d2, size_t count,
-                          const int32_t *d_tv, const int32_t *d_idx, const int32_t *d_tva = nullptr) {
-    int rc = ensure_workspace(c, count);
-    if (!rc) rc = c->d_u.grow(count * sp.theta * 1025 * sizeof(int32_t));
-    if (rc) return rc;
-    const int n = c->p.n;
-    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
-    dim3 pg((unsigned)((n + 1 + 255) / 256), (unsigned)(count < 65535 ? count : 65535));
-    hipLaunchKernelGGL(sk_lut_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, sp.n_inputs, sp.weights[0], sp.weights[1], sp.weights[2],
-                       sp.bias, ilog2(sp.theta), n, c->n_pad, ilog2(2 * c->p.N), (long)count, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
-    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
-    BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)count, n, c->n_pad, c->p.Bgbit,
-             0, d_tv, d_idx, sp.theta, d_tva};
-    rc = d_tva ? launch_rotations<kLutEnc>(c, a) : launch_rotations<kLut>(c, a);
-    if (rc) return rc;
-    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
-    THFHE_HIP(hipGetLastError());
-    return THFHE_OK;
-}
-
 int enqueue_keyswitch(thfhe_ctx *c, const int32_t *d_u, int32_t *d_out, size_t gates, int rot_per_gate, bool timed) {
     KsArgs k = c->ksk.args(d_u, d_out, (long)gates);
     k.rot_per_gate = rot_per_gate;
@@ -681,6 +609,38 @@ int enqueue_keyswitch(thfhe_ctx *c, const int32_t *d_u, int32_t *d_out, size_t g
     }
     return THFHE_OK;
 }
+
+// One PBS stage on the context's stream, the workspace sized by the caller: the prologue of `jobs` jobs of `src`, their rotations on the plaintext
+// tables tv (kLut) or, with tv_a, on the encrypted tables (tv_a, tv) (kLutEnc), theta records each into c->d_u; then, with ks_dst, the key switch of
+// those jobs x theta records into it.  A source that writes no table index rotates on d_idx (null: table 0).  timed: the profiling events of a
+// flat call (prologue | rotations | key switch).
+template <typename Src>
+int enqueue_pbs(thfhe_ctx *c, const Src &src, size_t jobs, const int32_t *tv, const int32_t *tv_a, int theta, const int32_t *d_idx, int32_t *ks_dst,
+                bool timed = false) {
+    const int n = c->p.n;
+    const bool ev = timed && c->profiling;
+    int32_t *const idx = c->d_lut_idx.as<int32_t>();
+    if (ev) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
+    lut_prologue_launch(src, jobs, n, c->n_pad, ilog2(2 * c->p.N), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), idx, c->stream);
+    if (ev) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
+    BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, n, c->n_pad, c->p.Bgbit,
+             0, tv, Src::kIdx == LutIdx::none ? d_idx : idx, theta, tv_a};
+    THFHE_TRY(tv_a ? launch_rotations<kLutEnc>(c, a) : launch_rotations<kLut>(c, a));
+    if (ev) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
+    THFHE_HIP(hipGetLastError());
+    return ks_dst ? enqueue_keyswitch(c, c->d_u.as<int32_t>(), ks_dst, jobs * theta, 1, timed) : THFHE_OK;
+}
+
+// programmable bootstrap of `count` samples from contiguous operand arrays: count x theta records of N+1 words into c->d_u and, with ks_dst,
+// key-switched into it; d_tva: the masks of encrypted tables (d_tv their bodies), or null: plaintext tables
+int enqueue_lut_rotations(thfhe_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0, const int32_t *d1, const int32_t *d2, size_t count,
+                          const int32_t *d_tv, const int32_t *d_idx, const int32_t *d_tva, int32_t *ks_dst) {
+    int rc = ensure_workspace(c, count);
+    if (!rc) rc = c->d_u.grow(count * sp.theta * 1025 * sizeof(int32_t));
+    if (rc) return rc;
+    return enqueue_pbs(c, LutFlatSrc<LutIdx::none>{d0, d1, d2, sp, 1, nullptr}, count, d_tv, d_tva, sp.theta, d_idx, ks_dst, true);
+}
+
 int gates_dev_locked(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1, const int32_t *d2, int32_t *dout, size_t count) {
     if (count == 0) return THFHE_OK;
     if (count > (size_t)INT32_MAX / 4) return thfhe_fail(THFHE_E_INVALID, "count too large");
@@ -733,10 +693,138 @@ int lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv, int
         THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         if (enc) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int32_t>(), tv_a, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         if (lut_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), lut_index, count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        r = enqueue_lut_rotations(c, s, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), count, c->d_tv.as<int32_t>(),
-                                  lut_index ? c->d_lut_idx.as<int32_t>() : nullptr, enc ? c->d_tva.as<int32_t>() : nullptr);
-        return r || !keyswitch ? r : enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), outs, 1, true);
+        return enqueue_lut_rotations(c, s, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), count, c->d_tv.as<int32_t>(),
+                                     lut_index ? c->d_lut_idx.as<int32_t>() : nullptr, enc ? c->d_tva.as<int32_t>() : nullptr,
+                                     keyswitch ? c->stage.out_ptr() : nullptr);
     }, keyswitch ? c->stage.out : c->d_u, out, out_bytes);
+}
+
+// Grow-only workspace of one tree chain over S samples / nodes: S R level-1 jobs of theta_lo records each (a SELECT group, whose candidates are
+// gathered: R = theta_lo = 1, the selection rotation alone), their S p candidates, S packed tables.
+int tree_workspace(thfhe_ctx *c, size_t S, size_t p, size_t R, size_t theta_lo) {
+    int rc = ensure_workspace(c, S * R);
+    if (!rc) rc = c->d_u.grow(S * R * theta_lo * 1025 * sizeof(int32_t));
+    if (!rc) rc = c->d_lut_idx.grow(S * R * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_lwe.grow(S * p * (c->p.n + 1) * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_a.grow(S * 1024 * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_b.grow(S * 1024 * sizeof(int32_t));
+    return rc;
+}
+
+// One tree chain over S samples / nodes on the gate context's stream, the workspace sized by tree_workspace.  Level 1: S (p / theta_lo)
+// rotations of the plaintext rows d_tv1 on the `lo` source, key-switched into the candidate buffer -- candidate k of sample s is record s p + k, the
+// order the rotations write them in; lo = nullptr (SELECT): the caller has gathered the candidates there in that order.  Then the packing context's
+// box packing of the candidates into S encrypted tables (pack_boxes_enqueue enqueues on the stream it is given), and the selection: sample s rotates
+// its own packed table on the `hi` source, coefficient 0 key-switched into d_out.  seam(1) / seam(2) run after level 1 and after the packing: what
+// the caller has to put on the stream there.
+template <typename Lo, typename Hi, typename Seam>
+int enqueue_tree_chain(thfhe_ctx *c, thfhe_poly_ctx *pc, const Lo &lo, const int32_t *d_tv1, int theta_lo, const Hi &hi, size_t S, int p, int32_t *d_out,
+                       Seam seam) {
+    int32_t *const cand = c->d_tree_lwe.as<int32_t>(), *const tab_a = c->d_tree_a.as<int32_t>(), *const tab_b = c->d_tree_b.as<int32_t>();
+    if constexpr (!std::is_same_v<Lo, std::nullptr_t>) THFHE_TRY(enqueue_pbs(c, lo, S * (p / theta_lo), d_tv1, nullptr, theta_lo, nullptr, cand));
+    THFHE_TRY(seam(1));
+    THFHE_TRY(pack_boxes_enqueue(pc, cand, S * p, p, tab_a, tab_b, c->stream));
+    THFHE_TRY(seam(2));
+    return enqueue_pbs(c, hi, S, tab_b, tab_a, 1, nullptr, d_out);
+}
+
+// ---- gate-DAG entry points: what thfhe_dag_run_batch, thfhe_dag_run_lut_batch and thfhe_dag_run_tree_batch share ----
+int sk_dag_classify(int op) { return op == THFHE_NOT || op == THFHE_COPY ? 2 : (op == THFHE_MUX ? 1 : (op >= THFHE_NAND && op <= THFHE_ORYN ? 0 : -1)); }
+
+// dag_execute's ensure: workspace and staging for slices of max_gates gates; theta_max > 0: a run with LUT groups of up to theta_max records per node
+int sk_dag_ensure(thfhe_ctx *c, size_t max_gates, int theta_max, int32_t **in, int32_t **out) {
+    const size_t words = c->p.n + 1;
+    int r = ensure_workspace(c, 2 * max_gates);
+    if (!r && theta_max) r = c->d_u.grow(theta_max * max_gates * 1025 * sizeof(int32_t));
+    if (!r && theta_max) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
+    if (!r) r = c->stage.grow(max_gates * words);
+    if (!r && theta_max) r = c->stage.out.grow(theta_max * max_gates * words * sizeof(int32_t));   // key switch of nodes x theta records
+    in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
+    return r;
+}
+
+// The table families of a LUT / tree run (host pointers, checked by dag_lut_plan / dag_tree_plan; a family the run does not have is null / 0).
+struct SkDagTables {
+    const thfhe_lut_spec *specs;
+    int n_specs;
+    const int32_t *tv;
+    int n_luts;
+    const int32_t *enc_a = nullptr, *enc_b = nullptr;
+    int n_enc = 0;
+    const thfhe_tree_spec *trees = nullptr;
+    const int32_t *tv1 = nullptr;
+    int n_tv1_rows = 0;
+};
+
+// The device side of thfhe_dag_run_lut_batch and thfhe_dag_run_tree_batch, both contexts locked by the caller (pc: null in a run without SELECT /
+// TREE groups).  Gate classes run as in thfhe_dag_run_batch.  A LUT group is one PBS stage on the wire table over the run's plaintext tables
+// (DESIGN 4.9), a LUT_ENC group the same over its encrypted tables.  A SELECT group gathers its candidates into the buffer the box packing reads
+// and runs the tree chain from there; a TREE group runs the whole chain with both prologues reading the wire table.  Everything is
+// enqueued on the gate context's stream.
+int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const SkDagTables &T, const int32_t *inputs, size_t n_inputs, size_t n_nodes,
+                    size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs) {
+    const int words = c->p.n + 1;
+    hipStream_t st = c->stream;
+    // a slice of a SELECT / TREE group: at most dag_slice nodes over all instances and at most tree_slice / p_hi of them
+    const size_t dag_slice = c->dag_slice, tree_slice = c->tree_slice;
+    auto slice_of = [&](int tree, size_t all) { return std::min({all, dag_slice, std::max<size_t>(1, tree_slice / (size_t)T.trees[tree].p_hi)}); };
+    size_t w_cand = 0;
+    for (const DagBatch &b : plan.batches) {
+        if (b.cls < kDagSelect) continue;
+        const thfhe_tree_spec &ts = T.trees[b.tree];
+        const size_t S = slice_of(b.tree, b.count * instances), p = (size_t)ts.p_hi, theta_lo = b.cls == kDagTree ? (size_t)ts.lo.theta : 1;
+        THFHE_TRY(tree_workspace(c, S, p, b.cls == kDagTree ? p / theta_lo : 1, theta_lo));
+        w_cand = std::max(w_cand, S * p);
+    }
+    if (w_cand) {
+        THFHE_TRY(pack_boxes_reserve(pc, w_cand));
+        THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle; from here on its buffers are used on `st`
+    }
+    // the run's tables and specs, once per call
+    auto upload = [&](DevBuf &d, const void *h, size_t bytes) -> int {
+        if (!bytes) return THFHE_OK;
+        THFHE_TRY(d.grow(bytes));
+        THFHE_HIP(hipMemcpyAsync(d.as<void>(), h, bytes, hipMemcpyHostToDevice, st));
+        return THFHE_OK;
+    };
+    THFHE_TRY(upload(c->d_tv, T.tv, (size_t)T.n_luts * 1024 * sizeof(int32_t)));
+    THFHE_TRY(upload(c->dag.specs, T.specs, (size_t)T.n_specs * sizeof(thfhe_lut_spec)));
+    THFHE_TRY(upload(c->d_dag_enc_a, T.enc_a, (size_t)T.n_enc * 1024 * sizeof(int32_t)));
+    THFHE_TRY(upload(c->d_dag_enc_b, T.enc_b, (size_t)T.n_enc * 1024 * sizeof(int32_t)));
+    THFHE_TRY(upload(c->d_dag_tv1, T.tv1, (size_t)T.n_tv1_rows * 1024 * sizeof(int32_t)));
+    const unsigned wb = (unsigned)((words + 255) / 256);
+    return dag_execute(
+        plan, c->dag, st, words, n_inputs, n_nodes, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
+        [&](size_t max_gates, int32_t **in, int32_t **out) { return sk_dag_ensure(c, max_gates, plan.max_theta, in, out); },
+        [&](int cls, const int32_t *d_ops, size_t m) { return dag_gate_class(c, cls, d_ops, m); },
+        [&](int theta, const DagLutSlice &s) {
+            return enqueue_pbs(c, s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, (s.enc ? c->d_dag_enc_b : c->d_tv).as<int32_t>(),
+                               s.enc ? c->d_dag_enc_a.as<int32_t>() : nullptr, theta, nullptr, c->stage.out_ptr());
+        },
+        [&](const DagExtGroup &g) {
+            const thfhe_tree_spec ts = T.trees[g.tree];
+            const int p = ts.p_hi, hi0 = g.cls == kDagTree ? ts.lo.n_inputs : 0;
+            const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the index operands of a TREE node follow its lo.n_inputs level-1 operands
+            const long slice = (long)slice_of(g.tree, (size_t)g.all);
+            auto no_seam = [](int) { return (int)THFHE_OK; };
+            for (long first = 0; first < g.all; first += slice) {
+                const long S = std::min(slice, g.all - first);
+                const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
+                if (g.cls == kDagTree) {   // t_y = row0
+                    const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {ts.lo}, g.t_y, first, g.cnt, g.n_wires, p / ts.lo.theta};
+                    THFHE_TRY(enqueue_tree_chain(c, pc, lo, c->d_dag_tv1.as<int32_t>(), ts.lo.theta, hi, (size_t)S, p, c->stage.out_ptr(), no_seam));
+                } else {                   // SELECT: t_y = first candidate wire
+                    const unsigned gy = (unsigned)std::min<long>(S * p, 65535);
+                    hipLaunchKernelGGL(dag_select_gather_kernel, dim3(wb, gy), dim3(256), 0, st, (const int32_t *)g.wires, g.t_y, c->d_tree_lwe.as<int32_t>(), first, S,
+                                       g.cnt, g.n_wires, words, p);
+                    THFHE_TRY(enqueue_tree_chain(c, pc, nullptr, nullptr, 1, hi, (size_t)S, p, c->stage.out_ptr(), no_seam));
+                }
+                hipLaunchKernelGGL(dag_scatter_kernel, dim3((unsigned)S, wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires, first, S, g.cnt,
+                                   g.n_wires, words);
+                THFHE_HIP(hipGetLastError());
+            }
+            return (int)THFHE_OK;
+        });
 }
 
 }  // namespace
@@ -856,87 +944,40 @@ int thfhe_dag_run_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs, co
                         const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
     if (!c || (!inputs && n_inputs) || (!gates && n_gates) || (!outputs && n_gates) || (!out_wires && n_out)) return thfhe_fail(THFHE_E_INVALID, "null argument");
     DagPlan plan;
-    int rc = dag_plan(gates, n_inputs, n_gates, [](int op) { return op == THFHE_NOT || op == THFHE_COPY ? 2 : (op == THFHE_MUX ? 1 : (op >= THFHE_NAND && op <= THFHE_ORYN ? 0 : -1)); },
-                      plan);
+    int rc = dag_plan(gates, n_inputs, n_gates, sk_dag_classify, plan);
     if (rc) return rc;
     if (stats) plan.fill_stats(stats);
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
-    const int words = c->p.n + 1;
     return dag_execute(
-        plan, c->dag, c->stream, words, n_inputs, n_gates, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
-        [&](size_t max_gates, int32_t **in, int32_t **out) {
-            int r = ensure_workspace(c, 2 * max_gates);
-            if (!r) r = c->stage.grow(max_gates * words);
-            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
-            return r;
-        },
+        plan, c->dag, c->stream, c->p.n + 1, n_inputs, n_gates, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
+        [&](size_t max_gates, int32_t **in, int32_t **out) { return sk_dag_ensure(c, max_gates, 0, in, out); },
         [&](int cls, const int32_t *d_ops, size_t n) { return dag_gate_class(c, cls, d_ops, n); });
 }
 
-// LUT nodes among the gates: the gate classes run as in thfhe_dag_run_batch; a LUT launch group runs the fused prologue
-// (dag_lut_prologue_kernel: operands straight from the wire table), the LUT instantiations of the blind-rotate kernels on the shapes of
-// launch_br, and the key switch of its nodes x theta records.
+// LUT nodes among the gates: sk_dag_run_luts with plaintext tables only -- no encrypted tables, no trees, no packing context.
 int thfhe_dag_run_lut_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs,
                             int n_specs, const int32_t *tv, int n_luts, size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs,
                             int64_t *stats) {
     DagPlan plan;
-    int rc = dag_lut_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, out_wires, n_out, outputs,
-                          [](int op) { return op == THFHE_NOT || op == THFHE_COPY ? 2 : (op == THFHE_MUX ? 1 : (op >= THFHE_NAND && op <= THFHE_ORYN ? 0 : -1)); },
-                          plan);
+    int rc = dag_lut_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, out_wires, n_out, outputs, sk_dag_classify, plan);
     if (rc) return rc;
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     if (stats) plan.fill_stats(stats);
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
-    const int words = c->p.n + 1, theta_max = plan.max_theta;
-    // the run's tables and specs, once per call
-    rc = c->d_tv.grow((size_t)n_luts * 1024 * sizeof(int32_t));
-    if (!rc) rc = c->dag.specs.grow((size_t)n_specs * sizeof(thfhe_lut_spec));
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->dag.specs.as<thfhe_lut_spec>(), specs, (size_t)n_specs * sizeof(thfhe_lut_spec), hipMemcpyHostToDevice, c->stream));
-    return dag_execute(
-        plan, c->dag, c->stream, words, n_inputs, n_nodes, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
-        [&](size_t max_gates, int32_t **in, int32_t **out) {
-            int r = ensure_workspace(c, 2 * max_gates);
-            if (!r) r = c->d_u.grow(theta_max * max_gates * 1025 * sizeof(int32_t));
-            if (!r) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
-            if (!r) r = c->stage.grow(max_gates * words);
-            if (!r) r = c->stage.out.grow(theta_max * max_gates * words * sizeof(int32_t));   // key switch of nodes x theta records
-            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
-            return r;
-        },
-        [&](int cls, const int32_t *d_ops, size_t n) { return dag_gate_class(c, cls, d_ops, n); },
-        [&](int theta, const DagLutSlice &s) {
-            const int n = c->p.n;
-            const dim3 pg((unsigned)((n + 1 + 255) / 256), (unsigned)(s.total < 65535 ? s.total : 65535));
-            hipLaunchKernelGGL(dag_lut_prologue_kernel, pg, dim3(256), 0, c->stream, s.wires, s.t0, s.t1, s.t2, s.t_spec, s.t_lut,
-                               (const thfhe_lut_spec *)c->dag.specs.as<thfhe_lut_spec>(), s.first, s.total, s.cnt, s.n_wires, n, c->n_pad, ilog2(2 * c->p.N),
-                               c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
-            BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), s.total, n, c->n_pad,
-                     c->p.Bgbit, 0, c->d_tv.as<int32_t>(), c->d_lut_idx.as<int32_t>(), theta};
-            int r = launch_rotations<kLut>(c, a);
-            if (!r) r = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), (size_t)s.total * theta, 1, false);
-            return r;
-        });
+    return sk_dag_run_luts(c, nullptr, plan, SkDagTables{specs, n_specs, tv, n_luts}, inputs, n_inputs, n_nodes, instances, out_wires, n_out, outputs);
 }
 
-// Encrypted-table, select and tree nodes among the gates and LUT nodes.  Gate classes and LUT groups run as in
-// thfhe_dag_run_lut_batch.  A LUT_ENC group is a LUT group on the kLutEnc instantiations with the run's shared encrypted tables.  A SELECT group
-// gathers its candidates into the buffer the box packing reads, packs them into one encrypted table per node and rotates that table by the index
-// digit (dag_select_prologue_kernel, lut_idx = job).  A TREE group runs the chain of thfhe_tree_lut_bootstrap with both prologues reading the wire
-// table: level-1 rotations (dag_tree_prologue_kernel), key switch into the packing buffer, box packing, selection rotation, key switch.  Everything
-// is enqueued on the gate context's stream; both contexts stay locked for the run.
+// Encrypted-table, select and tree nodes among the gates and LUT nodes: the host checks and the two locks here, the run in
+// sk_dag_run_luts.  Both contexts stay locked for the run.
 int thfhe_dag_run_tree_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
                              const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
                              const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, size_t instances, const int32_t *out_wires,
                              size_t n_out, int32_t *outputs, int64_t *stats) {
     DagPlan plan;
     int rc = dag_tree_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, out_wires, n_out,
-                           outputs,
-                           [](int op) { return op == THFHE_NOT || op == THFHE_COPY ? 2 : (op == THFHE_MUX ? 1 : (op >= THFHE_NAND && op <= THFHE_ORYN ? 0 : -1)); },
-                           plan);
+                           outputs, sk_dag_classify, plan);
     if (rc) return rc;
     if (stats) plan.fill_stats(stats);   // the plan's figures need no device
     const bool packs = plan.has_tree_groups();
@@ -947,125 +988,14 @@ int thfhe_dag_run_tree_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *in
     if (lk.rc) return lk.rc;
     std::unique_lock<std::mutex> pg;   // always after the gate context's: nothing else takes both
     if (packs) pg = std::unique_lock<std::mutex>(pack_ctx_mutex(pc));
-    const int n = c->p.n, words = n + 1, theta_max = plan.max_theta, log2_2n = ilog2(2 * c->p.N);
     if (packs) {
         if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
-        if (pack_key_n(pc) != n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
+        if (pack_key_n(pc) != c->p.n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
     }
     if (instances == 0 || n_nodes == 0) return THFHE_OK;
     if (instances > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "too many instances");
-    // a slice of a group: at most dag_slice nodes over all instances, SELECT / TREE groups also at most tree_slice / p_hi of them
-    const size_t dag_slice = c->dag_slice, tree_slice = c->tree_slice;
-    auto slice_of = [&](int cls, int tree, size_t all) {
-        size_t s = std::min(all, dag_slice);
-        if (cls >= kDagSelect) s = std::min(s, std::max<size_t>(1, tree_slice / (size_t)trees[tree].p_hi));
-        return s;
-    };
-    // workspaces, sized once from the plan: rotation jobs, extracted records, key-switched records, candidates, packed tables
-    size_t w_jobs = 0, w_u = 0, w_out = 0, w_cand = 0, w_tab = 0;
-    for (const DagBatch &b : plan.batches) {
-        if (b.cls < kDagEnc) continue;
-        const size_t S = slice_of(b.cls, b.tree, b.count * instances);
-        if (b.cls < kDagSelect) {
-            const size_t theta = (size_t)dag_enc_theta(b.cls);
-            w_jobs = std::max(w_jobs, S), w_u = std::max(w_u, S * theta), w_out = std::max(w_out, S * theta);
-        } else {
-            const size_t p = (size_t)trees[b.tree].p_hi, R = b.cls == kDagTree ? p / (size_t)trees[b.tree].lo.theta : 1;
-            w_jobs = std::max(w_jobs, S * R), w_u = std::max(w_u, b.cls == kDagTree ? S * p : S), w_out = std::max(w_out, S);
-            w_cand = std::max(w_cand, S * p), w_tab = std::max(w_tab, S);
-        }
-    }
-    // the run's tables and specs, once per call
-    if (n_luts) rc = c->d_tv.grow((size_t)n_luts * 1024 * sizeof(int32_t));
-    if (!rc && n_specs) rc = c->dag.specs.grow((size_t)n_specs * sizeof(thfhe_lut_spec));
-    if (!rc && n_enc) rc = c->d_dag_enc_a.grow((size_t)n_enc * 1024 * sizeof(int32_t));
-    if (!rc && n_enc) rc = c->d_dag_enc_b.grow((size_t)n_enc * 1024 * sizeof(int32_t));
-    if (!rc && n_tv1_rows) rc = c->d_dag_tv1.grow((size_t)n_tv1_rows * 1024 * sizeof(int32_t));
-    if (!rc && w_cand) rc = c->d_tree_lwe.grow(w_cand * words * sizeof(int32_t));
-    if (!rc && w_tab) rc = c->d_tree_a.grow(w_tab * 1024 * sizeof(int32_t));
-    if (!rc && w_tab) rc = c->d_tree_b.grow(w_tab * 1024 * sizeof(int32_t));
-    if (!rc && w_cand) rc = pack_boxes_reserve(pc, w_cand);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    if (packs) THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle; from here on its buffers are used on `st`
-    if (n_luts) THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (n_specs) THFHE_HIP(hipMemcpyAsync(c->dag.specs.as<thfhe_lut_spec>(), specs, (size_t)n_specs * sizeof(thfhe_lut_spec), hipMemcpyHostToDevice, st));
-    if (n_enc) {
-        THFHE_HIP(hipMemcpyAsync(c->d_dag_enc_a.as<int32_t>(), enc_a, (size_t)n_enc * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        THFHE_HIP(hipMemcpyAsync(c->d_dag_enc_b.as<int32_t>(), enc_b, (size_t)n_enc * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-    if (n_tv1_rows) THFHE_HIP(hipMemcpyAsync(c->d_dag_tv1.as<int32_t>(), tv1, (size_t)n_tv1_rows * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const unsigned pgx = (unsigned)((n + 1 + 255) / 256), wb = (unsigned)((words + 255) / 256);
-    auto gy = [](size_t jobs) { return (unsigned)(jobs < 65535 ? jobs : 65535); };
-    auto br = [&](long jobs, const int32_t *tab_b, int theta, const int32_t *tab_a) {
-        return BRArgs{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), jobs, n, c->n_pad,
-                      c->p.Bgbit, 0, tab_b, c->d_lut_idx.as<int32_t>(), theta, tab_a};
-    };
-    return dag_execute(
-        plan, c->dag, st, words, n_inputs, n_nodes, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
-        [&](size_t max_gates, int32_t **in, int32_t **out) {
-            int r = ensure_workspace(c, std::max(2 * max_gates, w_jobs));
-            if (!r) r = c->d_u.grow(std::max(theta_max * max_gates, w_u) * 1025 * sizeof(int32_t));
-            if (!r) r = c->d_lut_idx.grow(std::max(max_gates, w_jobs) * sizeof(int32_t));
-            if (!r) r = c->stage.grow(max_gates * words);
-            if (!r) r = c->stage.out.grow(std::max(theta_max * max_gates, w_out) * words * sizeof(int32_t));   // key switch of nodes x theta records
-            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
-            return r;
-        },
-        [&](int cls, const int32_t *d_ops, size_t m) { return dag_gate_class(c, cls, d_ops, m); },
-        [&](int theta, const DagLutSlice &s) {
-            hipLaunchKernelGGL(dag_lut_prologue_kernel, dim3(pgx, gy((size_t)s.total)), dim3(256), 0, st, s.wires, s.t0, s.t1, s.t2, s.t_spec, s.t_lut,
-                               (const thfhe_lut_spec *)c->dag.specs.as<thfhe_lut_spec>(), s.first, s.total, s.cnt, s.n_wires, n, c->n_pad, log2_2n,
-                               c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
-            int r = launch_rotations<kLut>(c, br(s.total, c->d_tv.as<int32_t>(), theta, nullptr));
-            if (!r) r = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), (size_t)s.total * theta, 1, false);
-            return r;
-        },
-        [&](const DagExtGroup &g) {
-            const long slice = (long)slice_of(g.cls, g.tree, (size_t)g.all);
-            for (long first = 0; first < g.all; first += slice) {
-                const long S = std::min(slice, g.all - first);
-                if (g.cls < kDagSelect) {   // LUT_ENC: t_x = spec, t_y = etab
-                    const int theta = dag_enc_theta(g.cls);
-                    hipLaunchKernelGGL(dag_lut_prologue_kernel, dim3(pgx, gy((size_t)S)), dim3(256), 0, st, (const int32_t *)g.wires, g.t0, g.t1, g.t2, g.t_x, g.t_y,
-                                       (const thfhe_lut_spec *)c->dag.specs.as<thfhe_lut_spec>(), first, S, g.cnt, g.n_wires, n, c->n_pad, log2_2n,
-                                       c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
-                    THFHE_TRY(launch_rotations<kLutEnc>(c, br(S, c->d_dag_enc_b.as<int32_t>(), theta, c->d_dag_enc_a.as<int32_t>())));
-                    THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), (size_t)S * theta, 1, false));
-                    hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(S * theta), wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires,
-                                       first, S, g.cnt, g.n_wires, words, theta);
-                    THFHE_HIP(hipGetLastError());
-                    continue;
-                }
-                const thfhe_tree_spec ts = trees[g.tree];
-                const int p = ts.p_hi;
-                const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the index operands of a TREE node follow its lo.n_inputs level-1 operands
-                int hi0 = 0;
-                if (g.cls == kDagTree) {   // t_y = row0
-                    const int R = p / ts.lo.theta;
-                    hi0 = ts.lo.n_inputs;
-                    hipLaunchKernelGGL(dag_tree_prologue_kernel, dim3(pgx, gy((size_t)S)), dim3(256), 0, st, (const int32_t *)g.wires, g.t0, g.t1, g.t2, g.t_y, ts.lo, R,
-                                       first, S, g.cnt, g.n_wires, n, c->n_pad, log2_2n, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(),
-                                       c->d_lut_idx.as<int32_t>());
-                    THFHE_TRY(launch_rotations<kLut>(c, br(S * R, c->d_dag_tv1.as<int32_t>(), ts.lo.theta, nullptr)));
-                    THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->d_tree_lwe.as<int32_t>(), (size_t)S * p, 1, false));
-                } else {                   // SELECT: t_y = first candidate wire
-                    hipLaunchKernelGGL(dag_select_gather_kernel, dim3(wb, gy((size_t)S * p)), dim3(256), 0, st, (const int32_t *)g.wires, g.t_y,
-                                       c->d_tree_lwe.as<int32_t>(), first, S, g.cnt, g.n_wires, words, p);
-                }
-                // candidate k of node j is record j p + k: the order the level-1 key switch (or the gather) wrote them in
-                THFHE_TRY(pack_boxes_enqueue(pc, c->d_tree_lwe.as<int32_t>(), (size_t)S * p, p, c->d_tree_a.as<int32_t>(), c->d_tree_b.as<int32_t>(), st));
-                hipLaunchKernelGGL(dag_select_prologue_kernel, dim3(pgx, gy((size_t)S)), dim3(256), 0, st, (const int32_t *)g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2],
-                                   ts.hi, first, S, g.cnt, g.n_wires, n, c->n_pad, log2_2n, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(),
-                                   c->d_lut_idx.as<int32_t>());
-                THFHE_TRY(launch_rotations<kLutEnc>(c, br(S, c->d_tree_b.as<int32_t>(), 1, c->d_tree_a.as<int32_t>())));
-                THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), (size_t)S, 1, false));
-                hipLaunchKernelGGL(dag_scatter_kernel, dim3((unsigned)S, wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires, first, S, g.cnt,
-                                   g.n_wires, words);
-                THFHE_HIP(hipGetLastError());
-            }
-            return (int)THFHE_OK;
-        });
+    return sk_dag_run_luts(c, packs ? pc : nullptr, plan, SkDagTables{specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, tv1, n_tv1_rows},
+                           inputs, n_inputs, n_nodes, instances, out_wires, n_out, outputs);
 }
 
 int thfhe_set_dag_slice(thfhe_ctx *c, size_t max_gates) { return ctx_set_dag_slice(c, max_gates); }
@@ -1122,10 +1052,8 @@ int thfhe_set_tree_slice(thfhe_ctx *c, size_t max_candidates) {
     return THFHE_OK;
 }
 
-// Two-digit tree PBS.  Per slice of S samples, everything on the gate context's stream: level 1 = S R rotations of the plaintext
-// rows tv1[table[s]][r] on the `lo` prologue and the key switch of their S p_hi candidates; the packing context's box packing of the candidates
-// into S encrypted test vectors (pack_boxes_enqueue: it enqueues on the stream it is given); level 2 = S rotations of those tables on the `hi`
-// prologue, extraction at coefficient 0, key switch.  Only the inputs of a slice go up and its S results come down.
+// Two-digit tree PBS: per slice of S samples one enqueue_tree_chain on contiguous operands -- level 1 on the rows
+// tv1[table[s]][r] and the `lo` operands, the selection on the `hi` operands.  Only the inputs of a slice go up and its S results come down.
 int thfhe_tree_lut_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, const int32_t *tv1,
                              int n_tables, const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
                              const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
@@ -1156,57 +1084,38 @@ int thfhe_tree_lut_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_s
     const thfhe_lut_spec lo = *spec_lo, hi = *spec_hi;
     const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / p_hi));
     int rc = c->d_tv.grow((size_t)n_tables * R * 1024 * sizeof(int32_t));
-    if (!rc) rc = ensure_workspace(c, S_max * R);
-    if (!rc) rc = c->d_u.grow(S_max * p_hi * 1025 * sizeof(int32_t));
-    if (!rc) rc = c->d_lut_idx.grow(S_max * R * sizeof(int32_t));
+    if (!rc) rc = tree_workspace(c, S_max, p_hi, R, theta1);
     if (!rc) rc = c->stage.grow(S_max * words);
     if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
-    if (!rc) rc = c->d_tree_lwe.grow(S_max * p_hi * words * sizeof(int32_t));
-    if (!rc) rc = c->d_tree_a.grow(S_max * 1024 * sizeof(int32_t));
-    if (!rc) rc = c->d_tree_b.grow(S_max * 1024 * sizeof(int32_t));
     if (rc) return rc;
     hipStream_t st = c->stream;
     THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle (its calls drain it); from here on its buffers are used on `st`
     THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv1, (size_t)n_tables * R * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const int log2_2n = ilog2(2 * c->p.N);
     const int32_t *lo_in[3] = {lo0, lo.n_inputs > 1 ? lo1 : nullptr, lo.n_inputs > 2 ? lo2 : nullptr};
     const int32_t *hi_in[3] = {hi0, hi.n_inputs > 1 ? hi1 : nullptr, hi.n_inputs > 2 ? hi2 : nullptr};
-    auto prologue = [&](const thfhe_lut_spec &sp, size_t jobs, int reps, const int32_t *d_tab, int identity) {
-        const dim3 pg((unsigned)((n + 1 + 255) / 256), (unsigned)(jobs < 65535 ? jobs : 65535));
-        hipLaunchKernelGGL(sk_tree_prologue_kernel, pg, dim3(256), 0, st, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), sp.n_inputs, sp.weights[0],
-                           sp.weights[1], sp.weights[2], sp.bias, ilog2(sp.theta), n, c->n_pad, log2_2n, (long)jobs, reps, d_tab, identity, c->d_bara.as<int32_t>(),
-                           c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>());
-    };
+    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);   // `lo`, then `hi` operands of the slice
     for (size_t s0 = 0; s0 < count; s0 += S_max) {
-        const size_t S = std::min(S_max, count - s0), J1 = S * R, C = S * p_hi, in_bytes = S * words * sizeof(int32_t);
+        const size_t S = std::min(S_max, count - s0), in_bytes = S * words * sizeof(int32_t);
         const bool first = s0 == 0, last = s0 + S == count;
-        // ---- level 1 ----
-        for (int q = 0; q < 3; q++)
-            if (lo_in[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), lo_in[q] + s0 * words, in_bytes, hipMemcpyHostToDevice, st));
+        auto upload = [&](const int32_t *const *h) {
+            for (int q = 0; q < 3; q++)
+                if (h[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), h[q] + s0 * words, in_bytes, hipMemcpyHostToDevice, st));
+            return (int)THFHE_OK;
+        };
+        THFHE_TRY(upload(lo_in));
         if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_tree_tab.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
         if (c->profiling && first) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        prologue(lo, J1, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr, 0);
-        BRArgs a1{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)J1, n, c->n_pad, c->p.Bgbit,
-                  0, c->d_tv.as<int32_t>(), c->d_lut_idx.as<int32_t>(), theta1, nullptr};
-        THFHE_TRY(launch_rotations<kLut>(c, a1));
-        THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->d_tree_lwe.as<int32_t>(), C, 1, false));
-        if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[1], st));
-        // ---- packing: candidate r theta1 + j of sample s is record s p_hi + r theta1 + j, the order the rotations wrote them in ----
-        THFHE_TRY(pack_boxes_enqueue(pc, c->d_tree_lwe.as<int32_t>(), C, p_hi, c->d_tree_a.as<int32_t>(), c->d_tree_b.as<int32_t>(), st));
-        if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[2], st));
-        // ---- level 2: sample s rotates its own packed table ----
-        for (int q = 0; q < 3; q++)
-            if (hi_in[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), hi_in[q] + s0 * words, in_bytes, hipMemcpyHostToDevice, st));
-        prologue(hi, S, 1, nullptr, 1);
-        BRArgs a2{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)S, n, c->n_pad, c->p.Bgbit,
-                  0, c->d_tree_b.as<int32_t>(), c->d_lut_idx.as<int32_t>(), 1, c->d_tree_a.as<int32_t>()};
-        THFHE_TRY(launch_rotations<kLutEnc>(c, a2));
-        THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), S, 1, false));
+        // profiling, on the last slice: level 1 | packing | selection.  The `hi` operands replace the `lo` ones in the staging arrays once level 1 is enqueued.
+        auto seam = [&](int k) {
+            if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[k], st));
+            return k == 2 ? upload(hi_in) : (int)THFHE_OK;
+        };
+        THFHE_TRY(enqueue_tree_chain(c, pc, LutFlatSrc<LutIdx::table>{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr},
+                                     c->d_tv.as<int32_t>(), theta1, LutFlatSrc<LutIdx::job>{in0, in1, in2, hi, 1, nullptr}, S, p_hi, c->stage.out_ptr(), seam));
         if (c->profiling && last) {
             THFHE_HIP(hipEventRecord(c->ev[3], st));
             c->ev_valid = true;
         }
-        THFHE_HIP(hipGetLastError());
         THFHE_HIP(hipMemcpyAsync(out + s0 * words, c->stage.out_ptr(), in_bytes, hipMemcpyDeviceToHost, st));
     }
     THFHE_HIP(hipStreamSynchronize(st));
