@@ -357,6 +357,39 @@ int thfhe_tree_lut_bootstrap(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const thf
                              const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count);
 int thfhe_set_tree_slice(thfhe_ctx *ctx, size_t max_candidates);
 
+/* ---- multi-value bootstrapping with factored test vectors (single key, N = 1024): q functions of one encrypted digit from ONE
+ * blind rotation, whatever q is (Carpov - Izabachene - Mollimard; Guimaraes - Borin - Aranha).
+ *
+ * thfhe_mv_lut_bootstrap(_wo_keyswitch): spec must have theta 1; prologue, mod-switch, CMux chain and the skip of mask words with bara == 0 are
+ *   those of thfhe_lut_bootstrap at theta = 1.  tv0: HOST int32[N], any words: the accumulator starts at (0, X^{-barb} * tv0).
+ *   factors: HOST int32[n_tables][q][p], p a power of two, 2 <= p <= 64, 1 <= q <= 64, 1 <= n_tables <= 1024.  table_index: HOST int32[count], or
+ *   NULL (table 0).  With box = N/p and F_{t,j}(X) = sum_{k<p} factors[t][j][k] X^(box/2 + k box), output (s, j) is the extraction at coefficient 0
+ *   of ACC_s * F_{t,j} mod (X^N + 1, 2^32), t = table_index[s]: word-wise, - sum_k factors[t][j][k] * extract_at(ACC_s, N - box/2 - k box), an exact
+ *   integer combination of p extractions.  With tv0 = (u, ..., u), step = 2u, and factors c_k = f(k+1) - f(k) (k < p-1), c_{p-1} = -(f(0) + f(p-1))
+ *   (thfhe.lut.mv_base / mv_factors) tv0 * F is the test vector of the words f(m) * step: output j carries f_j(m) * step.  The rotation's noise
+ *   reaches output j multiplied by the 2-norm of its factor.
+ *   out: HOST int32[count][q][n+1] (thfhe_mv_lut_bootstrap) or int32[count][q][N+1] (_wo_keyswitch).
+ *   THFHE_E_INVALID on the host, before the context is looked at: the checks of thfhe_lut_bootstrap (tv0 and n_tables in the places of tv and
+ *   n_luts), a null factors, theta != 1, a bad p, q or n_tables, a table_index entry out of range.  count 0 returns THFHE_OK.  The batch runs in
+ *   slices of at most max_candidates (thfhe_set_tree_slice) output records, 4.1 KiB of workspace each.
+ *
+ * thfhe_tree_lut_bootstrap_mv: thfhe_tree_lut_bootstrap with level 1 replaced by one multi-value rotation per sample on `lo` (p = p_lo taps,
+ *   q = p_hi outputs: candidate h of sample s is output h), then the key switch of the count p_hi candidates, the box packing and the selection
+ *   rotation on `hi` as there: 1 + 1 rotations per sample.  factors: HOST int32[n_tables][p_hi][p_lo] (thfhe.lut.tree_mv_factors).  The result
+ *   equals, word for word, thfhe_mv_lut_bootstrap(spec_lo, q = p_hi) -> thfhe_pack_boxes(p = p_hi) -> thfhe_lut_bootstrap_enc(spec_hi, table s for
+ *   sample s).  Checks, contexts, locking, stream, slicing and timings are those of thfhe_tree_lut_bootstrap, plus the checks above (spec_lo theta
+ *   1, p_lo as p, p_hi as q: 2 .. 64). */
+int thfhe_mv_lut_bootstrap(thfhe_ctx *ctx, const thfhe_lut_spec *spec, const int32_t *tv0, const int32_t *factors /*[n_tables][q][p]*/, int p, int q,
+                           int n_tables, const int32_t *table_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out,
+                           size_t count);
+int thfhe_mv_lut_bootstrap_wo_keyswitch(thfhe_ctx *ctx, const thfhe_lut_spec *spec, const int32_t *tv0, const int32_t *factors /*[n_tables][q][p]*/,
+                                        int p, int q, int n_tables, const int32_t *table_index, const int32_t *in0, const int32_t *in1,
+                                        const int32_t *in2, int32_t *out_N1, size_t count);
+int thfhe_tree_lut_bootstrap_mv(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi,
+                                int p_lo, const int32_t *tv0, const int32_t *factors /*[n_tables][p_hi][p_lo]*/, int n_tables,
+                                const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
+                                const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count);
+
 /* ---- encrypted-table, select and tree nodes in the gate-DAG executor (single key): thfhe_dag_run_lut_batch with three more node
  * kinds, so that a circuit needing a private table, an oblivious pick or a 6-bit -> 3-bit function does not leave the device-resident wire table.
  * nodes: HOST int32[n_nodes][6] = (opcode, in0, in1, in2, x, y); row g defines wire n_inputs + g.  Gate rows, THFHE_LUT and THFHE_LUT_OUT rows mean

@@ -668,6 +668,34 @@ THFHE_FN void extract_at16(int lane, const int32_t *acc_mask, const int32_t *acc
     }
     if (lane == 0) out[1024] = acc_body[j];
 }
+// multi-value bootstrap: ONE output of a factored test vector, the LWE(N) record of coefficient 0 of ACC * F,
+// F = sum_{k < p} c[k] X^(box/2 + k box), box = N / p.  Coefficient 0 of X^pos * ACC is -(coefficient N - pos of ACC), mask included, so
+//     out = - sum_k c[k] * extract_at(ACC, J_k),   J_k = N - box/2 - k box  (box/2 <= J_k <= N - box/2),   word-wise mod 2^32,
+// straight from the accumulator in LDS: p reads and p multiply-adds for each of the lane's 16 mask words, nothing transformed.  The taps
+// c[k] are wave-uniform: WPtr is a uniform_i32_ptr in the kernels (one scalar load per tap), a plain pointer in host code.
+// LDS banks: the taps J_k lie odd multiples of box/2 apart (box/2 = 8 .. 256 words), so lanes that read DIFFERENT taps in one
+// instruction would meet on 64 / box banks (16-way at p = 64).  Here an instruction reads ONE tap for all lanes: lane q takes word
+// (J_k - q) mod N, 64 consecutive words on 64 distinct banks, conflict-free for every k, like extract_at16.  The body word body[J_k] is
+// one address for the whole wave (a broadcast read, no conflict); every lane forms the sum, lane 0 stores it.
+template <typename WPtr>
+THFHE_FN void extract_mv16(int lane, const int32_t *acc_mask, const int32_t *acc_body, WPtr c, int p, int box, int32_t *out) {
+    uint32_t s[16], sb = 0;
+#pragma unroll
+    for (int m = 0; m < 16; m++) s[m] = 0;
+    int J = 1024 - (box >> 1);
+    for (int k = 0; k < p; k++, J -= box) {
+        const uint32_t ck = (uint32_t)c[k], nck = 0u - ck;
+#pragma unroll
+        for (int m = 0; m < 16; m++) {
+            const int d = J - (lane + 64 * m);   // extract_at16 at j = J: a_{J-q} for q <= J, -a_{N+J-q} above; the leading minus folded into the tap
+            s[m] += (uint32_t)acc_mask[d & 1023] * (d >= 0 ? nck : ck);
+        }
+        sb += (uint32_t)acc_body[J] * nck;
+    }
+#pragma unroll
+    for (int m = 0; m < 16; m++) out[lane + 64 * m] = (int32_t)s[m];
+    if (lane == 0) out[1024] = (int32_t)sb;
+}
 // folded two-limb inputs of a Torus32 polynomial (the ciphertext masks of the threshold partial decryption)
 THFHE_FN void key_limbs_to_z(int lane, const int32_t *poly, cplx (&zlo)[8], cplx (&zhi)[8]) {
 #pragma unroll

@@ -97,20 +97,24 @@ struct BRArgs {
     const cplx *tw;        // T1[512] ++ T2[64]
     const int32_t *bara;   // [jobs][n_pad]
     const int32_t *barb;   // [jobs]
-    int32_t *out;          // [jobs][N+1]; LUT kernels: [jobs][theta][N+1]
+    int32_t *out;          // [jobs][N+1]; LUT kernels: [jobs][theta][N+1]; kLutMv: [jobs][q][N+1]
     long jobs;
     int n, n_pad, Bgbit;
     int32_t mu;
     // LUT kernels only (programmable bootstrap): accumulator X^{-barb} * tv, coefficients 0 .. theta-1 extracted
     const int32_t *tv;       // [n_luts][N]
     const int32_t *lut_idx;  // [jobs] test vector of each job, or null: table 0
-    int theta;               // 1, 2 or 4
+    int theta;               // records per job: 1, 2 or 4 coefficients extracted; kLutMv: its q outputs, 1 .. 64
     // encrypted-table kernels only (LUT == kLutEnc): the tables are TLWE samples (tv_a, tv) under the ring key, accumulator X^{-barb} * (tv_a, tv)
     const int32_t *tv_a;     // [n_luts][N] masks; `tv` holds the bodies
+    // multi-value kernels only (LUT == kLutMv): every job rotates tv[0 .. N); lut_idx picks its table of `theta` factors of mv_p taps
+    const int32_t *mv_w;     // [n_tables][theta][mv_p] taps; written before the launch, read as wave-uniform scalars
+    int mv_p, mv_box;        // taps per output (a power of two, 2 .. 64) and N / mv_p
 };
 
-// what a blind-rotate instantiation starts from: the gates' constant test vector, a plaintext table, an encrypted table (4.11)
-constexpr int kGate = 0, kLut = 1, kLutEnc = 2;
+// what a blind-rotate instantiation starts from: the gates' constant test vector, a plaintext table, an encrypted table (4.11);
+// kLutMv starts like kLut, from the one base vector of a multi-value bootstrap, and ends in extract_mv16 (4.13)
+constexpr int kGate = 0, kLut = 1, kLutEnc = 2, kLutMv = 3;
 
 // ------------------------------------------------------------------------------------------------------
 // blind rotate + extract, throughput kernel ("LDS ring", second generation).
@@ -159,7 +163,8 @@ constexpr int kGate = 0, kLut = 1, kLutEnc = 2;
 // brings TWO slices of a chunk) is the shape for batches that cannot give every CU eight jobs (<= 1024 rotations): a wave alone on its
 // SIMD issues at ~87 % of what a pair reaches together (tools/probes/issue_probe.hip), so four jobs finish much sooner than eight.
 // LUT = kLut, kLutEnc: programmable bootstrap, the accumulator starts from a test vector (kLutEnc: from a TLWE sample, mask included) and theta
-// coefficients are extracted; the CMux loop is the same code.
+// coefficients are extracted; kLutMv: multi-value bootstrap, the kLut start on one base vector and a.theta = q outputs, each a
+// p-tap combination of extractions (extract_mv16); the CMux loop is the same code.
 template <int L, int V = 1, int W = 8, int LUT = kGate>
 __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_kernel(BRArgs a) {
     __shared__ __attribute__((aligned(4096))) int32_t sAcc[W][2048];   // rotated_digits_z ORs byte offsets into the polynomial base
@@ -182,7 +187,8 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
         if constexpr (LUT == kLutEnc) {
             const size_t t = a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0;
             acc_init_tlwe16(lane, acc, acc + 1024, a.barb[job], a.tv_a + t, a.tv + t);
-        } else if constexpr (LUT) acc_init_tv16(lane, acc, acc + 1024, a.barb[job], a.tv + (a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0));
+        } else if constexpr (LUT == kLutMv) acc_init_tv16(lane, acc, acc + 1024, a.barb[job], a.tv);
+        else if constexpr (LUT) acc_init_tv16(lane, acc, acc + 1024, a.barb[job], a.tv + (a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0));
         else acc_init16(lane, acc, acc + 1024, a.barb[job], a.mu);
     }
 
@@ -307,7 +313,11 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
     STAMP_FLUSH(blockIdx.x, wave);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (has_job) {
-        if constexpr (LUT) {
+        if constexpr (LUT == kLutMv) {
+            // the job's factor table: job is wave-uniform, so the index and every tap are scalar loads
+            const uniform_i32_ptr w = as_uniform(a.mv_w) + (size_t)(a.lut_idx ? as_uniform(a.lut_idx)[job] : 0) * a.theta * a.mv_p;
+            for (int j = 0; j < a.theta; j++) extract_mv16(lane, acc, acc + 1024, w + j * a.mv_p, a.mv_p, a.mv_box, a.out + (job * a.theta + j) * 1025);
+        } else if constexpr (LUT) {
             for (int j = 0; j < a.theta; j++) extract_at16(lane, acc, acc + 1024, j, a.out + (job * a.theta + j) * 1025);
         } else {
             extract16(lane, acc, acc + 1024, a.out + job * 1025);
@@ -354,7 +364,8 @@ __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) 
         if constexpr (LUT == kLutEnc) {
             const size_t t = a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0;
             acc_init_tlwe16(lane, sAcc, sAcc + 1024, a.barb[job], a.tv_a + t, a.tv + t);
-        } else if constexpr (LUT) acc_init_tv16(lane, sAcc, sAcc + 1024, a.barb[job], a.tv + (a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0));
+        } else if constexpr (LUT == kLutMv) acc_init_tv16(lane, sAcc, sAcc + 1024, a.barb[job], a.tv);
+        else if constexpr (LUT) acc_init_tv16(lane, sAcc, sAcc + 1024, a.barb[job], a.tv + (a.lut_idx ? (size_t)a.lut_idx[job] * 1024 : 0));
         else acc_init16(lane, sAcc, sAcc + 1024, a.barb[job], a.mu);
     }
     const int c = (wave >> 1) & 1, h = wave & 1, half = wave >> 2, r0 = half * L;  // role in M: rows r0 .. r0+L-1 of (column c, limb h)
@@ -459,7 +470,11 @@ __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) 
         i = inext;
     }
     STAMP_FLUSH(blockIdx.x, wave);
-    if constexpr (LUT) {
+    if constexpr (LUT == kLutMv) {
+        const uniform_i32_ptr w = as_uniform(a.mv_w) + (size_t)(a.lut_idx ? as_uniform(a.lut_idx)[job] : 0) * a.theta * a.mv_p;
+        for (int j = wave; j < a.theta; j += 8)   // the q outputs dealt over the eight waves
+            extract_mv16(lane, sAcc, sAcc + 1024, w + j * a.mv_p, a.mv_p, a.mv_box, a.out + (job * a.theta + j) * 1025);
+    } else if constexpr (LUT) {
         if (wave < a.theta) extract_at16(lane, sAcc, sAcc + 1024, wave, a.out + (job * a.theta + wave) * 1025);   // one wave per output
     } else {
         if (wave == 0) extract16(lane, sAcc, sAcc + 1024, a.out + job * 1025);
@@ -487,11 +502,12 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     DevBuf d_bara, d_barb, d_u;
     DevBuf d_tv, d_lut_idx;   // programmable bootstrap: test-vector table and per-sample table index (grow-only)
     DevBuf d_tva;             // encrypted tables (thfhe_lut_bootstrap_enc): the masks; d_tv holds the bodies
+    DevBuf d_mv_w;            // multi-value bootstrap (thfhe_mv_lut_bootstrap, thfhe_tree_lut_bootstrap_mv): the factor tables; d_tv holds the base vector
     // tree PBS (thfhe_tree_lut_bootstrap): a slice's table indices, key-switched level-1 candidates and packed tables (mask, body)
     DevBuf d_tree_tab, d_tree_lwe, d_tree_a, d_tree_b;
     // encrypted-table and tree nodes of the gate DAG (thfhe_dag_run_tree_batch): the run's encrypted tables (masks, bodies) and level-1 rows
     DevBuf d_dag_enc_a, d_dag_enc_b, d_dag_tv1;
-    size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate)
+    size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate); also the output records (samples x q) per slice of thfhe_mv_lut_bootstrap
     // staging for the host-buffer API
     Stage stage;
     // gate-DAG executor: wire table and index tables (grow-only, reused by every thfhe_dag_run on this context)
@@ -610,13 +626,19 @@ int enqueue_keyswitch(thfhe_ctx *c, const int32_t *d_u, int32_t *d_out, size_t g
     return THFHE_OK;
 }
 
+// the device side of a multi-value rotation's factor tables: int32[n_tables][q][p] taps
+struct MvArgs {
+    const int32_t *w;
+    int p;
+};
+
 // One PBS stage on the context's stream, the workspace sized by the caller: the prologue of `jobs` jobs of `src`, their rotations on the plaintext
 // tables tv (kLut) or, with tv_a, on the encrypted tables (tv_a, tv) (kLutEnc), theta records each into c->d_u; then, with ks_dst, the key switch of
 // those jobs x theta records into it.  A source that writes no table index rotates on d_idx (null: table 0).  timed: the profiling events of a
-// flat call (prologue | rotations | key switch).
+// flat call (prologue | rotations | key switch).  mv: multi-value rotations (kLutMv) of the base vector tv, the index picks a table of theta = q factors.
 template <typename Src>
 int enqueue_pbs(thfhe_ctx *c, const Src &src, size_t jobs, const int32_t *tv, const int32_t *tv_a, int theta, const int32_t *d_idx, int32_t *ks_dst,
-                bool timed = false) {
+                bool timed = false, const MvArgs *mv = nullptr) {
     const int n = c->p.n;
     const bool ev = timed && c->profiling;
     int32_t *const idx = c->d_lut_idx.as<int32_t>();
@@ -625,7 +647,10 @@ int enqueue_pbs(thfhe_ctx *c, const Src &src, size_t jobs, const int32_t *tv, co
     if (ev) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
     BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, n, c->n_pad, c->p.Bgbit,
              0, tv, Src::kIdx == LutIdx::none ? d_idx : idx, theta, tv_a};
-    THFHE_TRY(tv_a ? launch_rotations<kLutEnc>(c, a) : launch_rotations<kLut>(c, a));
+    if (mv) {
+        a.mv_w = mv->w, a.mv_p = mv->p, a.mv_box = c->p.N / mv->p;
+        THFHE_TRY(launch_rotations<kLutMv>(c, a));
+    } else THFHE_TRY(tv_a ? launch_rotations<kLutEnc>(c, a) : launch_rotations<kLut>(c, a));
     if (ev) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
     THFHE_HIP(hipGetLastError());
     return ks_dst ? enqueue_keyswitch(c, c->d_u.as<int32_t>(), ks_dst, jobs * theta, 1, timed) : THFHE_OK;
@@ -716,12 +741,13 @@ int tree_workspace(thfhe_ctx *c, size_t S, size_t p, size_t R, size_t theta_lo) 
 // order the rotations write them in; lo = nullptr (SELECT): the caller has gathered the candidates there in that order.  Then the packing context's
 // box packing of the candidates into S encrypted tables (pack_boxes_enqueue enqueues on the stream it is given), and the selection: sample s rotates
 // its own packed table on the `hi` source, coefficient 0 key-switched into d_out.  seam(1) / seam(2) run after level 1 and after the packing: what
-// the caller has to put on the stream there.
+// the caller has to put on the stream there.  mv: level 1 is ONE multi-value rotation per sample of the base vector d_tv1 with
+// theta_lo = p outputs, the candidates in the same order.
 template <typename Lo, typename Hi, typename Seam>
 int enqueue_tree_chain(thfhe_ctx *c, thfhe_poly_ctx *pc, const Lo &lo, const int32_t *d_tv1, int theta_lo, const Hi &hi, size_t S, int p, int32_t *d_out,
-                       Seam seam) {
+                       Seam seam, const MvArgs *mv = nullptr) {
     int32_t *const cand = c->d_tree_lwe.as<int32_t>(), *const tab_a = c->d_tree_a.as<int32_t>(), *const tab_b = c->d_tree_b.as<int32_t>();
-    if constexpr (!std::is_same_v<Lo, std::nullptr_t>) THFHE_TRY(enqueue_pbs(c, lo, S * (p / theta_lo), d_tv1, nullptr, theta_lo, nullptr, cand));
+    if constexpr (!std::is_same_v<Lo, std::nullptr_t>) THFHE_TRY(enqueue_pbs(c, lo, S * (p / theta_lo), d_tv1, nullptr, theta_lo, nullptr, cand, false, mv));
     THFHE_TRY(seam(1));
     THFHE_TRY(pack_boxes_enqueue(pc, cand, S * p, p, tab_a, tab_b, c->stream));
     THFHE_TRY(seam(2));
@@ -825,6 +851,138 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
             }
             return (int)THFHE_OK;
         });
+}
+
+// ---- what thfhe_tree_lut_bootstrap and thfhe_tree_lut_bootstrap_mv share ----
+// host checks of a tree call that need no context: pointers, both specs, p_hi
+int tree_validate(const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, const int32_t *tv, const int32_t *lo0, const int32_t *lo1,
+                  const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, const int32_t *out) {
+    if (!spec_lo || !spec_hi || !tv || !lo0 || !hi0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    THFHE_TRY(lut_spec_check(*spec_lo));
+    THFHE_TRY(lut_spec_check(*spec_hi));
+    if ((spec_lo->n_inputs > 1 && !lo1) || (spec_lo->n_inputs > 2 && !lo2) || (spec_hi->n_inputs > 1 && !hi1) || (spec_hi->n_inputs > 2 && !hi2))
+        return thfhe_fail(THFHE_E_INVALID, "null operand: the spec names more inputs");
+    if (spec_hi->theta != 1) return thfhe_fail(THFHE_E_INVALID, "tree: spec_hi theta must be 1 (the packed table holds one function)");
+    if (p_hi < 2 || p_hi > 512 || (p_hi & (p_hi - 1))) return thfhe_fail(THFHE_E_INVALID, "tree: p_hi must be a power of two in 2 .. N/2");
+    return THFHE_OK;
+}
+int tree_validate_index(const int32_t *table_index, int n_tables, size_t count) {
+    if (count > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "count too large");
+    if (table_index)
+        for (size_t g = 0; g < count; g++)
+            if (table_index[g] < 0 || table_index[g] >= n_tables) return thfhe_fail(THFHE_E_INVALID, "table_index out of range (0 .. n_tables-1)");
+    return THFHE_OK;
+}
+// the rules a multi-value rotation adds to lut_validate's: theta 1, p taps, q outputs, the factor tables
+int mv_validate(const thfhe_lut_spec &sp, int p, int q, int n_tables) {
+    if (sp.theta != 1) return thfhe_fail(THFHE_E_INVALID, "multi-value: the spec's theta must be 1");
+    if (p < 2 || p > 64 || (p & (p - 1))) return thfhe_fail(THFHE_E_INVALID, "multi-value: p must be a power of two in 2 .. 64");
+    if (q < 1 || q > 64) return thfhe_fail(THFHE_E_INVALID, "multi-value: q must be 1 .. 64");
+    if (n_tables < 1 || n_tables > 1024) return thfhe_fail(THFHE_E_INVALID, "multi-value: n_tables must be 1 .. 1024");
+    return THFHE_OK;
+}
+
+// Two-digit tree PBS (DESIGN 4.11): per slice of S samples one enqueue_tree_chain on contiguous operands -- level 1 on the rows
+// tv[table[s]][r] (tv_rows rows of N words in all) and the `lo` operands, the selection on the `hi` operands.  Only the inputs of a slice go up and its
+// S results come down.  factors: level 1 is one multi-value rotation per sample of the base vector tv with the p_hi factors of mv_p taps
+// of table[s], int32[mv_tables][p_hi][mv_p].  The arguments have passed the entry's host checks.
+int tree_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec &lo, const thfhe_lut_spec &hi, int p_hi, const int32_t *tv, size_t tv_rows,
+                   const int32_t *factors, int mv_p, int mv_tables, const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2,
+                   const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
+    if (!c || !pc) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (pack_ctx_device(pc) != c->device) return thfhe_fail(THFHE_E_INVALID, "tree: the gate context and the packing context must be on the same device");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    std::lock_guard<std::mutex> pg(pack_ctx_mutex(pc));   // always after the gate context's: nothing else takes both
+    const int n = c->p.n, words = n + 1;
+    if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
+    if (pack_key_n(pc) != n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
+    if (count == 0) return THFHE_OK;
+    const int theta1 = factors ? p_hi : lo.theta, R = p_hi / theta1;   // level-1 records per rotation, rotations per sample
+    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / p_hi));
+    const size_t tv_bytes = tv_rows * 1024 * sizeof(int32_t), w_bytes = factors ? (size_t)mv_tables * p_hi * mv_p * sizeof(int32_t) : 0;
+    int rc = c->d_tv.grow(tv_bytes);
+    if (!rc && factors) rc = c->d_mv_w.grow(w_bytes);
+    if (!rc) rc = tree_workspace(c, S_max, p_hi, R, theta1);
+    if (!rc) rc = c->stage.grow(S_max * words);
+    if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle (its calls drain it); from here on its buffers are used on `st`
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, tv_bytes, hipMemcpyHostToDevice, st));
+    if (factors) THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
+    const MvArgs mv{c->d_mv_w.as<int32_t>(), mv_p};
+    const int32_t *lo_in[3] = {lo0, lo.n_inputs > 1 ? lo1 : nullptr, lo.n_inputs > 2 ? lo2 : nullptr};
+    const int32_t *hi_in[3] = {hi0, hi.n_inputs > 1 ? hi1 : nullptr, hi.n_inputs > 2 ? hi2 : nullptr};
+    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);   // `lo`, then `hi` operands of the slice
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0), in_bytes = S * words * sizeof(int32_t);
+        const bool first = s0 == 0, last = s0 + S == count;
+        auto upload = [&](const int32_t *const *h) {
+            for (int q = 0; q < 3; q++)
+                if (h[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), h[q] + s0 * words, in_bytes, hipMemcpyHostToDevice, st));
+            return (int)THFHE_OK;
+        };
+        THFHE_TRY(upload(lo_in));
+        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_tree_tab.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (c->profiling && first) THFHE_HIP(hipEventRecord(c->ev[0], st));
+        // profiling, on the last slice: level 1 | packing | selection.  The `hi` operands replace the `lo` ones in the staging arrays once level 1 is enqueued.
+        auto seam = [&](int k) {
+            if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[k], st));
+            return k == 2 ? upload(hi_in) : (int)THFHE_OK;
+        };
+        THFHE_TRY(enqueue_tree_chain(c, pc, LutFlatSrc<LutIdx::table>{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr},
+                                     c->d_tv.as<int32_t>(), theta1, LutFlatSrc<LutIdx::job>{in0, in1, in2, hi, 1, nullptr}, S, p_hi, c->stage.out_ptr(), seam,
+                                     factors ? &mv : nullptr));
+        if (c->profiling && last) {
+            THFHE_HIP(hipEventRecord(c->ev[3], st));
+            c->ev_valid = true;
+        }
+        THFHE_HIP(hipMemcpyAsync(out + s0 * words, c->stage.out_ptr(), in_bytes, hipMemcpyDeviceToHost, st));
+    }
+    THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
+}
+
+// thfhe_mv_lut_bootstrap (keyswitch) / thfhe_mv_lut_bootstrap_wo_keyswitch: out = count x q records of n+1 (resp. N+1) words, in slices
+// of at most tree_slice records: only a slice's inputs go up and its records come down.
+int mv_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv0, const int32_t *factors, int p, int q, int n_tables,
+                     const int32_t *table_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch) {
+    if (!factors) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    THFHE_TRY(lut_validate(sp, tv0, n_tables, table_index, in0, in1, in2, out, count));
+    THFHE_TRY(mv_validate(*sp, p, q, n_tables));
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (count == 0) return THFHE_OK;
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const thfhe_lut_spec s = *sp;
+    const size_t words = c->p.n + 1, rec = keyswitch ? words : (size_t)c->p.N + 1;
+    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / q));
+    const size_t w_bytes = (size_t)n_tables * q * p * sizeof(int32_t);
+    int rc = ensure_workspace(c, S_max);
+    if (!rc) rc = c->d_u.grow(S_max * q * 1025 * sizeof(int32_t));
+    if (!rc) rc = c->stage.grow(keyswitch ? S_max * q * words : S_max * words);   // the key switch writes S x q records into stage.out
+    if (!rc) rc = c->d_tv.grow(1024 * sizeof(int32_t));
+    if (!rc) rc = c->d_mv_w.grow(w_bytes);
+    if (!rc && table_index) rc = c->d_lut_idx.grow(S_max * sizeof(int32_t));
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv0, 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
+    const MvArgs mv{c->d_mv_w.as<int32_t>(), p};
+    const int32_t *in[3] = {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr};
+    int32_t *const res = keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>();
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0);
+        for (int k = 0; k < 3; k++)
+            if (in[k]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(k), in[k] + s0 * words, S * words * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        THFHE_TRY(enqueue_pbs(c, LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, S, c->d_tv.as<int32_t>(),
+                              nullptr, q, table_index ? c->d_lut_idx.as<int32_t>() : nullptr, keyswitch ? c->stage.out_ptr() : nullptr, s0 + S == count, &mv));
+        THFHE_HIP(hipMemcpyAsync(out + s0 * q * rec, res, S * q * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
 }
 
 }  // namespace
@@ -1052,74 +1210,39 @@ int thfhe_set_tree_slice(thfhe_ctx *c, size_t max_candidates) {
     return THFHE_OK;
 }
 
-// Two-digit tree PBS (DESIGN 4.11): per slice of S samples one enqueue_tree_chain on contiguous operands -- level 1 on the rows
-// tv1[table[s]][r] and the `lo` operands, the selection on the `hi` operands.  Only the inputs of a slice go up and its S results come down.
 int thfhe_tree_lut_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, const int32_t *tv1,
                              int n_tables, const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
                              const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
     // host checks, before either context is looked at
-    if (!spec_lo || !spec_hi || !tv1 || !lo0 || !hi0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    THFHE_TRY(lut_spec_check(*spec_lo));
-    THFHE_TRY(lut_spec_check(*spec_hi));
-    if ((spec_lo->n_inputs > 1 && !lo1) || (spec_lo->n_inputs > 2 && !lo2) || (spec_hi->n_inputs > 1 && !hi1) || (spec_hi->n_inputs > 2 && !hi2))
-        return thfhe_fail(THFHE_E_INVALID, "null operand: the spec names more inputs");
-    if (spec_hi->theta != 1) return thfhe_fail(THFHE_E_INVALID, "tree: spec_hi theta must be 1 (the packed table holds one function)");
-    if (p_hi < 2 || p_hi > 512 || (p_hi & (p_hi - 1))) return thfhe_fail(THFHE_E_INVALID, "tree: p_hi must be a power of two in 2 .. N/2");
+    THFHE_TRY(tree_validate(spec_lo, spec_hi, p_hi, tv1, lo0, lo1, lo2, hi0, hi1, hi2, out));
     if (p_hi % spec_lo->theta) return thfhe_fail(THFHE_E_INVALID, "tree: spec_lo theta must divide p_hi");
-    const int theta1 = spec_lo->theta, R = p_hi / theta1;
+    const int R = p_hi / spec_lo->theta;
     if (n_tables < 1 || (long)n_tables * R > kMaxEncLuts) return thfhe_fail(THFHE_E_INVALID, "tree: n_tables must be 1 .. 262144 / (p_hi / theta)");
-    if (count > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "count too large");
-    if (table_index)
-        for (size_t g = 0; g < count; g++)
-            if (table_index[g] < 0 || table_index[g] >= n_tables) return thfhe_fail(THFHE_E_INVALID, "table_index out of range (0 .. n_tables-1)");
-    if (!c || !pc) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (pack_ctx_device(pc) != c->device) return thfhe_fail(THFHE_E_INVALID, "tree: the gate context and the packing context must be on the same device");
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    std::lock_guard<std::mutex> pg(pack_ctx_mutex(pc));   // always after the gate context's: nothing else takes both
-    const int n = c->p.n, words = n + 1;
-    if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
-    if (pack_key_n(pc) != n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
-    if (count == 0) return THFHE_OK;
-    const thfhe_lut_spec lo = *spec_lo, hi = *spec_hi;
-    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / p_hi));
-    int rc = c->d_tv.grow((size_t)n_tables * R * 1024 * sizeof(int32_t));
-    if (!rc) rc = tree_workspace(c, S_max, p_hi, R, theta1);
-    if (!rc) rc = c->stage.grow(S_max * words);
-    if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle (its calls drain it); from here on its buffers are used on `st`
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv1, (size_t)n_tables * R * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const int32_t *lo_in[3] = {lo0, lo.n_inputs > 1 ? lo1 : nullptr, lo.n_inputs > 2 ? lo2 : nullptr};
-    const int32_t *hi_in[3] = {hi0, hi.n_inputs > 1 ? hi1 : nullptr, hi.n_inputs > 2 ? hi2 : nullptr};
-    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);   // `lo`, then `hi` operands of the slice
-    for (size_t s0 = 0; s0 < count; s0 += S_max) {
-        const size_t S = std::min(S_max, count - s0), in_bytes = S * words * sizeof(int32_t);
-        const bool first = s0 == 0, last = s0 + S == count;
-        auto upload = [&](const int32_t *const *h) {
-            for (int q = 0; q < 3; q++)
-                if (h[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), h[q] + s0 * words, in_bytes, hipMemcpyHostToDevice, st));
-            return (int)THFHE_OK;
-        };
-        THFHE_TRY(upload(lo_in));
-        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_tree_tab.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (c->profiling && first) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        // profiling, on the last slice: level 1 | packing | selection.  The `hi` operands replace the `lo` ones in the staging arrays once level 1 is enqueued.
-        auto seam = [&](int k) {
-            if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[k], st));
-            return k == 2 ? upload(hi_in) : (int)THFHE_OK;
-        };
-        THFHE_TRY(enqueue_tree_chain(c, pc, LutFlatSrc<LutIdx::table>{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr},
-                                     c->d_tv.as<int32_t>(), theta1, LutFlatSrc<LutIdx::job>{in0, in1, in2, hi, 1, nullptr}, S, p_hi, c->stage.out_ptr(), seam));
-        if (c->profiling && last) {
-            THFHE_HIP(hipEventRecord(c->ev[3], st));
-            c->ev_valid = true;
-        }
-        THFHE_HIP(hipMemcpyAsync(out + s0 * words, c->stage.out_ptr(), in_bytes, hipMemcpyDeviceToHost, st));
-    }
-    THFHE_HIP(hipStreamSynchronize(st));
-    return THFHE_OK;
+    THFHE_TRY(tree_validate_index(table_index, n_tables, count));
+    return tree_bootstrap(c, pc, *spec_lo, *spec_hi, p_hi, tv1, (size_t)n_tables * R, nullptr, 0, 0, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
+}
+
+int thfhe_mv_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *spec, const int32_t *tv0, const int32_t *factors, int p, int q, int n_tables,
+                           const int32_t *table_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count) {
+    return mv_lut_bootstrap(c, spec, tv0, factors, p, q, n_tables, table_index, in0, in1, in2, out, count, true);
+}
+
+int thfhe_mv_lut_bootstrap_wo_keyswitch(thfhe_ctx *c, const thfhe_lut_spec *spec, const int32_t *tv0, const int32_t *factors, int p, int q, int n_tables,
+                                        const int32_t *table_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1,
+                                        size_t count) {
+    return mv_lut_bootstrap(c, spec, tv0, factors, p, q, n_tables, table_index, in0, in1, in2, out_N1, count, false);
+}
+
+int thfhe_tree_lut_bootstrap_mv(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, int p_lo,
+                                const int32_t *tv0, const int32_t *factors, int n_tables, const int32_t *table_index, const int32_t *lo0,
+                                const int32_t *lo1, const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out,
+                                size_t count) {
+    // host checks, before either context is looked at
+    THFHE_TRY(tree_validate(spec_lo, spec_hi, p_hi, tv0, lo0, lo1, lo2, hi0, hi1, hi2, out));
+    if (!factors) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    THFHE_TRY(mv_validate(*spec_lo, p_lo, p_hi, n_tables));
+    THFHE_TRY(tree_validate_index(table_index, n_tables, count));
+    return tree_bootstrap(c, pc, *spec_lo, *spec_hi, p_hi, tv0, 1, factors, p_lo, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
 }
 
 int thfhe_keyswitch(thfhe_ctx *c, const int32_t *in_N1, int32_t *out, size_t count) {

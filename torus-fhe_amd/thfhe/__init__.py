@@ -184,6 +184,11 @@ SIGNATURES = {
     "thfhe_tree_lut_bootstrap": (C.c_int, [_vp, _vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p,
                                            _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_set_tree_slice": (C.c_int, [_vp, C.c_size_t]),
+    "thfhe_mv_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_mv_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.POINTER(LutSpec), _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p,
+                                                      C.c_size_t]),
+    "thfhe_tree_lut_bootstrap_mv": (C.c_int, [_vp, _vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p,
+                                              _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_dev_alloc": (_vp, [_vp, C.c_size_t]),
     "thfhe_dev_free": (None, [_vp, _vp]),
     "thfhe_copy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
@@ -620,6 +625,56 @@ class CloudKey(_EvalKey):
                                               _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
         return out
 
+    # -- multi-value bootstrapping with factored test vectors (thfhe_mv_lut_bootstrap, thfhe_tree_lut_bootstrap_mv) ---------
+    def mv_lut_bootstrap(self, factors, x, y=None, z=None, *, tv0, weights=(1,), bias=0, table_index=None):
+        """q functions of one encrypted digit from ONE blind rotation: the base vector tv0 int32[N] (thfhe.lut.mv_base) is rotated by
+        x = sum_q weights[q] * (x, y, z)[q] + (0, bias) at theta = 1, and output j of sample s is coefficient 0 of ACC_s * F_j, F_j built from the p
+        taps factors[table_index[s]][j] (thfhe.lut.mv_factors).  factors: int32[q][p] or int32[n_tables][q][p].  Returns int32[count, q, n+1]."""
+        return self._mv(factors, x, y, z, tv0, weights, bias, table_index, True)
+
+    def mv_lut_bootstrap_wo_keyswitch(self, factors, x, y=None, z=None, *, tv0, weights=(1,), bias=0, table_index=None):
+        """mv_lut_bootstrap without the key switch: int32[count, q, N+1] records under the ring key."""
+        return self._mv(factors, x, y, z, tv0, weights, bias, table_index, False)
+
+    def _mv_tables(self, factors, tv0, table_index, count):
+        w = np.ascontiguousarray(factors, np.int32)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.size == 0:
+            raise ValueError("factors: expected int32[q][p] or int32[n_tables][q][p]")
+        tv0 = np.ascontiguousarray(tv0, np.int32).reshape(-1)
+        if tv0.shape[0] != self.params.N:
+            raise ValueError(f"tv0: expected int32[{self.params.N}]")
+        idx = None
+        if table_index is not None:
+            idx = np.ascontiguousarray(table_index, np.int32).reshape(-1)
+            if idx.shape[0] != count:
+                raise ValueError(f"table_index holds {idx.shape[0]} entries for {count} samples")
+        return w, tv0, idx
+
+    def _mv(self, factors, x, y, z, tv0, weights, bias, table_index, keyswitch):
+        ins, spec, p = self._lut_args((x, y, z), weights, bias, 1, "mv_lut_bootstrap")
+        count = ins[0].shape[0]
+        w, tv0, idx = self._mv_tables(factors, tv0, table_index, count)
+        out = np.empty((count, w.shape[1], self.words if keyswitch else self.params.N + 1), np.int32)
+        fn = lib().thfhe_mv_lut_bootstrap if keyswitch else lib().thfhe_mv_lut_bootstrap_wo_keyswitch
+        _check(fn(self.h, C.byref(spec), _p32(tv0), _p32(w), w.shape[2], w.shape[1], w.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
+        return out
+
+    def tree_lut_bootstrap_mv(self, poly_ctx, factors, lo, hi, *, tv0, weights_lo=(1,), bias_lo=0, weights_hi=(1,), bias_hi=0, table_index=None):
+        """tree_lut_bootstrap with level 1 as ONE multi-value rotation per sample (thfhe_tree_lut_bootstrap_mv): 1 + 1 rotations whatever p_hi is.
+        tv0, factors int32[p_hi][p_lo] or int32[n_tables][p_hi][p_lo]: thfhe.lut.tree_mv_factors.  int32[count, n+1]."""
+        as_tuple = lambda v: tuple(v) + (None,) * (3 - len(v)) if isinstance(v, (tuple, list)) else (v, None, None)
+        lo_r, spec_lo, plo = self._lut_args(as_tuple(lo), weights_lo, bias_lo, 1, "tree_lut_bootstrap_mv (lo)")
+        hi_r, spec_hi, phi = self._lut_args(as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap_mv (hi)")
+        _same_count(lo_r[0], hi_r[0])
+        count = lo_r[0].shape[0]
+        w, tv0, idx = self._mv_tables(factors, tv0, table_index, count)
+        out = np.empty((count, self.words), np.int32)
+        _check(lib().thfhe_tree_lut_bootstrap_mv(self.h, poly_ctx.h, C.byref(spec_lo), C.byref(spec_hi), w.shape[1], w.shape[2], _p32(tv0), _p32(w), w.shape[0],
+                                                 _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
+        return out
+
     def dag_run_tree_batch(self, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, out_wires=None, pack=None):
         """dag_run_lut_batch with encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch, DESIGN 4.12).  nodes: int32[n_nodes][6];
         specs, tv: as dag_run_lut_batch, both may be absent; enc_a, enc_b: int32[n_enc][N] encrypted tables; trees: (lo, hi, p_hi) tuples of spec
@@ -648,7 +703,8 @@ class CloudKey(_EvalKey):
         return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
 
     def set_tree_slice(self, max_candidates):
-        """Level-1 candidates (samples x p_hi) per slice of tree_lut_bootstrap: bounds its workspace (8 KiB of packing scratch per candidate)."""
+        """Level-1 candidates (samples x p_hi) per slice of tree_lut_bootstrap(_mv): bounds its workspace (8 KiB of packing scratch per candidate);
+        also the output records (samples x q) per slice of mv_lut_bootstrap."""
         _check(lib().thfhe_set_tree_slice(self.h, int(max_candidates)))
 
     def set_ring4_threshold(self, max_jobs):

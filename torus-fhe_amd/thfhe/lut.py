@@ -107,6 +107,43 @@ def tree_test_vectors(f, p_hi, p_lo, p_out, theta=1, N=1024):
                      for r in range(p_hi // theta)])
 
 
+def mv_base(step, N=1024):
+    """Base vector of a multi-value bootstrap (thfhe_mv_lut_bootstrap): int32[N] = (step/2, ..., step/2).  Times the factor of an integer
+    table f (mv_factors) it is test_vector(f * step, p): output j of the rotation carries f_j(m) * step.  step: an even Torus32 word, e.g.
+    2^32 / (2 p_out) for outputs in the padding-bit encoding at modulus p_out."""
+    step = int(step)
+    if step % 2:
+        raise ValueError("step must be even (the base vector holds step / 2)")
+    return _to_i32(np.full(N, step // 2, np.int64))
+
+
+def mv_factors(int_tables, p):
+    """Factors int32[q][p] of q integer tables (int_tables[j][m] = f_j(m), m in [0, p)): c_k = f(k+1) - f(k) for k < p-1, c_{p-1} = -(f(0) + f(p-1)),
+    the coefficient of X^(N/(2p) + k N/p).  The integers are taken as given, not reduced: f and f + p_out give outputs half a torus apart.  The
+    rotation's noise reaches output j times the 2-norm of row j, so small differences between neighbouring entries are cheap."""
+    _check_p(p)
+    f = np.asarray(int_tables, np.int64)
+    if f.ndim == 1:
+        f = f[None]
+    if f.ndim != 2 or f.shape[1] != p:
+        raise ValueError(f"expected q tables of {p} integers, got shape {f.shape}")
+    c = np.empty_like(f)
+    c[:, :-1] = f[:, 1:] - f[:, :-1]
+    c[:, -1] = -(f[:, 0] + f[:, -1])
+    if np.any(np.abs(c) >= 1 << 31):
+        raise ValueError("factor out of the int32 range")
+    return c.astype(np.int32)
+
+
+def tree_mv_factors(f, p_hi, p_lo, p_out, N=1024):
+    """(tv0, factors) of thfhe_tree_lut_bootstrap_mv for f(hi, lo), taken mod p_out: the base vector at step 2^32 / (2 p_out) and int32[p_hi][p_lo],
+    row h = the factor of lo -> f(h, lo).  Candidate h of the one level-1 rotation then carries encode(f(h, lo), p_out)."""
+    _check_p(p_hi)
+    _check_p(p_out)
+    tab = [[int(f(h, lo)) % p_out for lo in range(p_lo)] for h in range(p_hi)]
+    return mv_base((1 << 32) // (2 * p_out), N), mv_factors(tab, p_lo)
+
+
 def encrypt_table(rlwe_key, tv, sigma, rng):
     """The client side of an encrypted table (thfhe_lut_bootstrap_enc): a fresh TLWE sample (tv_a, tv_b) of the test vector(s) tv int32[..., N]
     under the bootstrapping ring key: tv_a uniform, tv_b = tv_a (*) z + tv + e, e Gaussian of standard deviation sigma; exact product."""
