@@ -61,7 +61,9 @@ enum thfhe_gate {
     THFHE_LUT_OUT = 15, /* output j > 0 of the LUT node j rows above (thfhe_dag_run_lut_batch, thfhe_dag_run_tree_batch) */
     THFHE_LUT_ENC = 16, /* gate-DAG node: programmable bootstrap of an ENCRYPTED table (thfhe_dag_run_tree_batch only) */
     THFHE_SELECT = 17,  /* gate-DAG node: oblivious pick among p consecutive earlier wires (thfhe_dag_run_tree_batch only) */
-    THFHE_TREE = 18     /* gate-DAG node: two-digit tree PBS (thfhe_dag_run_tree_batch only) */
+    THFHE_TREE = 18,    /* gate-DAG node: two-digit tree PBS (thfhe_dag_run_tree_batch, thfhe_dag_run_mv_batch) */
+    THFHE_MV = 19,      /* gate-DAG node: multi-value bootstrap, q outputs of one rotation (thfhe_dag_run_mv_batch only) */
+    THFHE_TREE_MV = 20  /* gate-DAG node: two-digit tree with a multi-value level 1 and k outputs (thfhe_dag_run_mv_batch only) */
 };
 
 enum thfhe_error {
@@ -378,7 +380,20 @@ int thfhe_set_tree_slice(thfhe_ctx *ctx, size_t max_candidates);
  *   rotation on `hi` as there: 1 + 1 rotations per sample.  factors: HOST int32[n_tables][p_hi][p_lo] (thfhe.lut.tree_mv_factors).  The result
  *   equals, word for word, thfhe_mv_lut_bootstrap(spec_lo, q = p_hi) -> thfhe_pack_boxes(p = p_hi) -> thfhe_lut_bootstrap_enc(spec_hi, table s for
  *   sample s).  Checks, contexts, locking, stream, slicing and timings are those of thfhe_tree_lut_bootstrap, plus the checks above (spec_lo theta
- *   1, p_lo as p, p_hi as q: 2 .. 64). */
+ *   1, p_lo as p, p_hi as q: 2 .. 64).
+ *
+ * thfhe_tree_lut_bootstrap_mvk: thfhe_tree_lut_bootstrap_mv with k tables per sample, out[s][j] = f_{t,j}(hi_s, lo_s) for j < k, in
+ *   1 + k rotations per sample; nothing between the stages visits the host.  factors: HOST int32[n_tables][k][p_hi][p_lo] (thfhe.lut.tree_mvk_factors);
+ *   out: HOST int32[count][k][n+1].  p_lo and p_hi powers of two in 2 .. 64, 1 <= k, k p_hi <= 64 (the multi-value rotation's q limit), 1 <= n_tables
+ *   <= 1024, both specs' theta 1.  Per slice: one multi-value rotation per sample on `lo` with q = k p_hi outputs, output j p_hi + h = candidate h of
+ *   table j; the key switch of the S k p_hi candidates; the box packing (p = p_hi) into S k encrypted tables -- the candidate order makes table (s, j)
+ *   the packed sample s k + j; S k selection rotations, job s k + j on sample s's `hi` operands and its own table s k + j; the key switch into out.
+ *   The result equals, word for word, thfhe_mv_lut_bootstrap(spec_lo, q = k p_hi) -> thfhe_pack_boxes(p = p_hi) -> thfhe_lut_bootstrap_enc(spec_hi,
+ *   ...) with each sample's `hi` operands repeated k times and lut_index = 0 .. count k - 1; at k = 1 it equals thfhe_tree_lut_bootstrap_mv word for
+ *   word.  Host checks, before either context is looked at: those of thfhe_tree_lut_bootstrap_mv, then k and k p_hi; then the context checks of
+ *   thfhe_tree_lut_bootstrap; count 0 returns THFHE_OK once those have passed (with a NULL context it is THFHE_E_INVALID, as in the older tree entries).  A
+ *   slice is at most max(1, max_candidates / (k p_hi)) samples (thfhe_set_tree_slice).  Contexts, locking, the single stream, the drain of the packing
+ *   context's stream and the timing slots are those of thfhe_tree_lut_bootstrap. */
 int thfhe_mv_lut_bootstrap(thfhe_ctx *ctx, const thfhe_lut_spec *spec, const int32_t *tv0, const int32_t *factors /*[n_tables][q][p]*/, int p, int q,
                            int n_tables, const int32_t *table_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out,
                            size_t count);
@@ -389,6 +404,10 @@ int thfhe_tree_lut_bootstrap_mv(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const 
                                 int p_lo, const int32_t *tv0, const int32_t *factors /*[n_tables][p_hi][p_lo]*/, int n_tables,
                                 const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
                                 const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count);
+int thfhe_tree_lut_bootstrap_mvk(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi,
+                                 int p_lo, int k, const int32_t *tv0, const int32_t *factors /*[n_tables][k][p_hi][p_lo]*/, int n_tables,
+                                 const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
+                                 const int32_t *hi1, const int32_t *hi2, int32_t *out /*[count][k][n+1]*/, size_t count);
 
 /* ---- encrypted-table, select and tree nodes in the gate-DAG executor (single key): thfhe_dag_run_lut_batch with three more node
  * kinds, so that a circuit needing a private table, an oblivious pick or a 6-bit -> 3-bit function does not leave the device-resident wire table.
@@ -426,6 +445,44 @@ int thfhe_dag_run_tree_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const int
                              const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
                              const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, size_t instances, const int32_t *out_wires,
                              size_t n_out, int32_t *outputs, int64_t *stats);
+
+/* ---- multi-value nodes in the gate-DAG executor (single key): thfhe_dag_run_tree_batch with two more node kinds and their table
+ * families, so that a circuit can hold multi-value rotations.  Every row of thfhe_dag_run_tree_batch means what it means there.  New rows:
+ *   (THFHE_MV, in0, in1, in2, mv, t), followed by q - 1 THFHE_LUT_OUT rows (q = mvs[mv].q): wire head + j is the record
+ *       thfhe_mv_lut_bootstrap(mvs[mv].lo, mv_tv0[base], table t of the spec, p, q, operands) returns at [0][j], word for word.  The q wires are
+ *       consecutive: a later THFHE_SELECT takes them as its candidates directly.  mvs[mv].k must be 1, .hi is ignored.
+ *   (THFHE_TREE_MV, op0, op1, op2, mv, t), followed by k - 1 THFHE_LUT_OUT rows: the operands are split between .lo and .hi as a THFHE_TREE row
+ *       splits them, at most three together; wire head + j is thfhe_tree_lut_bootstrap_mvk(&lo, &hi, p_hi = q, p_lo = p, k, mv_tv0[base], table t,
+ *       operands)[0][j], word for word.
+ * mvs: HOST thfhe_mv_spec[n_mvs] (at most 1024) or NULL, 0; mv_tv0: HOST int32[n_bases][N] base vectors (at most 1024) or NULL, 0; mv_factors: HOST
+ *   int32[n_factor_words], the taps of every spec: table t of spec m starts at word factors_off + t k q p (k = 1 for MV).  All are uploaded once
+ *   per call.  With the three families absent the call is thfhe_dag_run_tree_batch.
+ * Scheduling: every new node costs one level.  A level's MV nodes run as one launch group per distinct mvs[] index (one rotation launch: p, q and
+ *   the base vector are per launch, the table per job), their outputs scattered q per node; its TREE_MV nodes as one group per mvs[] index, the whole
+ *   chain of thfhe_tree_lut_bootstrap_mvk with both prologues reading the wire table.  Slices: at most thfhe_set_dag_slice nodes over all instances;
+ *   MV groups also at most thfhe_set_tree_slice / q nodes, TREE_MV groups at most thfhe_set_tree_slice / (k q).
+ * stats: an MV node counts one rotation and its group one launch; a TREE_MV node 1 + k rotations and its group two launches.
+ * Checks, on the host before any device work and before either context is looked at (THFHE_E_INVALID): those of thfhe_dag_run_tree_batch; mv, t,
+ *   base or factors_off + n_tables k q p out of range; a spec the flat entries would refuse (theta != 1, p, q, k, k q > 64, n_tables; an MV row on
+ *   a spec with k != 1); a wrong number of LUT_OUT rows after a head; operand counts that do not match the specs or exceed three; a family that is
+ *   NULL while a row refers to it.  The context checks of thfhe_tree_lut_bootstrap apply when the plan holds a SELECT, TREE or TREE_MV node; ctx_pack
+ *   may be NULL otherwise.  Every other thfhe_dag_* and thfhe_mk_dag_* entry rejects the two opcodes. */
+typedef struct thfhe_mv_spec {
+    thfhe_lut_spec lo;      /* the multi-value rotation's inputs, theta 1 */
+    thfhe_lut_spec hi;      /* TREE_MV: selection inputs, theta 1; ignored by MV */
+    int32_t p;              /* taps (p_lo), power of two 2..64 */
+    int32_t q;              /* MV: outputs 1..64.  TREE_MV: p_hi, power of two 2..64 */
+    int32_t k;              /* TREE_MV: outputs, k q <= 64; MV: must be 1 */
+    int32_t base;           /* row of mv_tv0[n_bases][N] */
+    int32_t factors_off;    /* word offset of this spec's table 0 in mv_factors; table t at + t k q p */
+    int32_t n_tables;
+} thfhe_mv_spec;
+
+int thfhe_dag_run_mv_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                           const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
+                           const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs,
+                           const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, size_t instances,
+                           const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats);
 
 /* ---- multi-key KEY GENERATION arithmetic on the device --------------------------------------------------------------
  * Exact multiply-accumulate of small-coefficient polynomials with torus polynomials, the only non-trivial arithmetic of

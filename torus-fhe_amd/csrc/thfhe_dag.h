@@ -4,6 +4,7 @@
 // gates, fed by the shared prologue reading their operands from the wire table (LutWireSrc, thfhe_lut_prologue.h), their theta outputs scattered
 // into consecutive wires.
 // Encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch, DESIGN 4.12, single key): three more node kinds, planned here, run by the engine.
+// Multi-value nodes (thfhe_dag_run_mv_batch, DESIGN 4.14, single key): MV and TREE_MV rows, planned here next to them.
 #ifndef THFHE_DAG_H
 #define THFHE_DAG_H
 
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void dag_select_gather_kernel(const int32_t *_
 struct DagBatch {
     int32_t depth, sub, cls;  // cls: engine-defined gate class; 2 = NOT / COPY (no bootstrap); 4 / 5 / 6 = LUT nodes of theta 1 / 2 / 4
     size_t off, count;        // index table slice: [ops | in0 | in1 | in2 | out], LUT classes + [spec | lut], `count` entries each, at tab[off]
-    int32_t tree = -1;        // SELECT / TREE groups: the trees[] entry the whole group shares
+    int32_t tree = -1;        // SELECT / TREE groups: the trees[] entry the whole group shares; MV / TREE_MV groups: the mvs[] entry
 };
 constexpr int kDagLutOut = 7;                // LUT_OUT row: no launch, its wire is written by its head's scatter
 inline int dag_lut_class(int theta) { return theta == 1 ? 4 : (theta == 2 ? 5 : 6); }
@@ -92,6 +93,8 @@ inline int dag_lut_theta(int cls) { return cls == 4 ? 1 : (cls == 5 ? 2 : 4); }
 // ([tree | first]), TREE groups = 12 ([tree | row0]), one group per trees[] entry
 constexpr int kDagEnc = 8, kDagSelect = 11, kDagTree = 12;
 inline int dag_enc_theta(int cls) { return cls == 8 ? 1 : (cls == 9 ? 2 : 4); }
+// thfhe_dag_run_mv_batch: MV groups = 13, TREE_MV groups = 14 ([mv | t]), one group per mvs[] entry
+constexpr int kDagMv = 13, kDagTreeMv = 14;
 
 // The LUT side of a run (thfhe_dag_run_lut_batch): node rows of 6 words, the run's specs and its table count.
 struct DagLuts {
@@ -102,7 +105,48 @@ struct DagLuts {
     int n_enc = 0;
     const thfhe_tree_spec *trees = nullptr;
     int n_trees = 0, n_tv1_rows = 0;
+    // thfhe_dag_run_mv_batch only (mv): the multi-value specs, the base-vector count and the words of the factor array
+    bool mv = false;
+    const thfhe_mv_spec *mvs = nullptr;
+    int n_mvs = 0, n_bases = 0;
+    size_t n_factor_words = 0;
 };
+
+// the rules a multi-value rotation adds to lut_spec_check's: theta 1, p taps, q outputs, the table count (thfhe_mv_lut_bootstrap)
+inline int mv_validate(const thfhe_lut_spec &sp, int p, int q, int n_tables) {
+    if (sp.theta != 1) return thfhe_fail(THFHE_E_INVALID, "multi-value: the spec's theta must be 1");
+    if (p < 2 || p > 64 || (p & (p - 1))) return thfhe_fail(THFHE_E_INVALID, "multi-value: p must be a power of two in 2 .. 64");
+    if (q < 1 || q > 64) return thfhe_fail(THFHE_E_INVALID, "multi-value: q must be 1 .. 64");
+    if (n_tables < 1 || n_tables > 1024) return thfhe_fail(THFHE_E_INVALID, "multi-value: n_tables must be 1 .. 1024");
+    return THFHE_OK;
+}
+// ... and a k-output tree on it (thfhe_tree_lut_bootstrap_mvk): p_hi a power of two within the rotation's 64 outputs (the flat entry's
+// tree_validate and mv_validate have refused a bad one before; the DAG planner comes here first), k tables per sample, k p_hi outputs in all
+inline int mvk_validate(int p_hi, int k) {
+    if (p_hi < 2 || p_hi > 64 || (p_hi & (p_hi - 1))) return thfhe_fail(THFHE_E_INVALID, "multi-value tree: p_hi must be a power of two in 2 .. 64");
+    if (k < 1) return thfhe_fail(THFHE_E_INVALID, "multi-value tree: k must be at least 1");
+    if ((long)k * p_hi > 64) return thfhe_fail(THFHE_E_INVALID, "multi-value tree: k p_hi must be at most 64 (the outputs of one rotation)");
+    return THFHE_OK;
+}
+// One mvs[] entry as an MV row (tree = false) or a TREE_MV row uses it: the flat entries' rules, then its base row and its slice of the factor array.
+inline int dag_mv_spec_check(const DagLuts &L, const thfhe_mv_spec &m, bool tree) {
+    THFHE_TRY(lut_spec_check(m.lo));
+    if (tree) {
+        THFHE_TRY(lut_spec_check(m.hi));
+        if (m.hi.theta != 1) return thfhe_fail(THFHE_E_INVALID, "tree: spec_hi theta must be 1 (the packed table holds one function)");
+        THFHE_TRY(mvk_validate(m.q, m.k));
+        THFHE_TRY(mv_validate(m.lo, m.p, m.k * m.q, m.n_tables));
+    } else {
+        if (m.k != 1) return thfhe_fail(THFHE_E_INVALID, "MV node: the spec's k must be 1");
+        THFHE_TRY(mv_validate(m.lo, m.p, m.q, m.n_tables));
+    }
+    if (L.n_bases < 1) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: no base vectors given (null table family)");
+    if (m.base < 0 || m.base >= L.n_bases) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: base out of range (0 .. n_bases-1)");
+    if (L.n_factor_words < 1) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: no factors given (null table family)");
+    if (m.factors_off < 0 || (size_t)m.factors_off + (size_t)m.n_tables * m.k * m.q * m.p > L.n_factor_words)
+        return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: factors_off + n_tables k q p out of range (0 .. n_factor_words)");
+    return THFHE_OK;
+}
 
 struct DagPlan {
     std::vector<DagBatch> batches;
@@ -113,11 +157,11 @@ struct DagPlan {
     int32_t max_depth = 0;
     void fill_stats(int64_t *stats) const {
         stats[0] = max_depth, stats[1] = 0, stats[2] = rotations, stats[3] = (int64_t)max_width;
-        for (const auto &b : batches) stats[1] += b.cls == kDagTree ? 2 : (b.cls != 2);   // a TREE group: level-1 and selection launch
+        for (const auto &b : batches) stats[1] += b.cls == kDagTree || b.cls == kDagTreeMv ? 2 : (b.cls != 2);   // a TREE / TREE_MV group: level-1 and selection launch
     }
     bool has_tree_groups() const {
         for (const auto &b : batches)
-            if (b.cls == kDagSelect || b.cls == kDagTree) return true;
+            if (b.cls == kDagSelect || b.cls == kDagTree || b.cls == kDagTreeMv) return true;
         return false;
     }
 };
@@ -129,6 +173,8 @@ struct DagPlan {
 // gate and joins the launch group of its theta; its theta - 1 THFHE_LUT_OUT rows take its depth with sub-level 0 and launch nothing.
 // luts->ext (thfhe_dag_run_tree_batch): THFHE_LUT_ENC rows are LUT rows over the encrypted tables (classes 8 / 9 / 10); THFHE_SELECT and THFHE_TREE
 // rows add one level above their operands (a SELECT's candidates included) and form one group per trees[] entry, emitted after the other classes.
+// luts->mv (thfhe_dag_run_mv_batch): THFHE_MV and THFHE_TREE_MV rows (mv, t) add one level and form one group per mvs[] entry, emitted after those;
+// q - 1 (MV) or k - 1 (TREE_MV) LUT_OUT rows follow the head.
 template <typename Classify>
 int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify classify, DagPlan &plan, const DagLuts *luts = nullptr) {
     const size_t n_wires = n_inputs + n_gates, stride = luts ? 6 : 4;
@@ -136,6 +182,8 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
     std::vector<int32_t> depth(n_wires, 0), sub(n_wires, 0), cls(n_gates, 0);
     const bool ext = luts && luts->ext;
     std::vector<char> tree_lo_ok(ext ? (size_t)luts->n_trees : 0, 0);   // trees[] entries whose `lo` half a TREE row has had checked
+    const bool mvx = ext && luts->mv;
+    std::vector<char> mv_ok(mvx ? (size_t)luts->n_mvs : 0, 0);          // mvs[] entries checked as an MV (bit 0) / a TREE_MV (bit 1) row uses them
     int32_t max_depth = 0;
     int32_t head = -1, pending = 0;   // the LUT node whose LUT_OUT rows are still due, and how many
     for (size_t g = 0; g < n_gates; g++) {
@@ -194,6 +242,24 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
                     return thfhe_fail(THFHE_E_INVALID, is_tree ? "TREE node: operands do not match lo.n_inputs + hi.n_inputs (unused ones are -1)"
                                                                : "SELECT node: operands do not match hi.n_inputs (unused ones are -1)");
             k = is_tree ? kDagTree : kDagSelect;
+        } else if (mvx && (op == THFHE_MV || op == THFHE_TREE_MV)) {
+            const bool is_tree = op == THFHE_TREE_MV;
+            if (!luts->mvs) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: no multi-value specs given (null table family)");
+            if (row[4] < 0 || row[4] >= luts->n_mvs) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: mv index out of range (0 .. n_mvs-1)");
+            const thfhe_mv_spec &m = luts->mvs[row[4]];
+            if (!(mv_ok[row[4]] & (is_tree ? 2 : 1))) {
+                THFHE_TRY(dag_mv_spec_check(*luts, m, is_tree));
+                mv_ok[row[4]] |= is_tree ? 2 : 1;
+            }
+            if (row[5] < 0 || row[5] >= m.n_tables) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: table index out of range (0 .. n_tables-1)");
+            nin = m.lo.n_inputs + (is_tree ? m.hi.n_inputs : 0);
+            if (nin > 3) return thfhe_fail(THFHE_E_INVALID, "TREE_MV node: lo and hi operands exceed three");
+            for (int q = 0; q < 3; q++)
+                if ((q < nin) != (row[1 + q] != -1))
+                    return thfhe_fail(THFHE_E_INVALID, is_tree ? "TREE_MV node: operands do not match lo.n_inputs + hi.n_inputs (unused ones are -1)"
+                                                               : "MV node: operands do not match lo.n_inputs (unused ones are -1)");
+            k = is_tree ? kDagTreeMv : kDagMv;
+            head = w, pending = (is_tree ? m.k : m.q) - 1;
         } else {
             k = classify(op);
             if (k < 0) return thfhe_fail(THFHE_E_INVALID, "gate opcode not defined for this engine");
@@ -218,11 +284,14 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
     // bucket: (depth, sub, class); bootstrapped classes first (sub 0), then the linear sub-levels in order
     std::vector<std::vector<std::vector<int32_t>>> boot(max_depth + 1, std::vector<std::vector<int32_t>>(kDagSelect)), lin(max_depth + 1);
     std::vector<std::map<int32_t, std::vector<int32_t>>> sel(ext ? max_depth + 1 : 0), tre(ext ? max_depth + 1 : 0);   // per level, by trees[] index
+    std::vector<std::map<int32_t, std::vector<int32_t>>> mvn(mvx ? max_depth + 1 : 0), tmv(mvx ? max_depth + 1 : 0);   // per level, by mvs[] index
     for (size_t g = 0; g < n_gates; g++) {
         const int32_t w = (int32_t)(n_inputs + g);
         if (cls[g] == kDagLutOut) continue;
         if (cls[g] == kDagSelect || cls[g] == kDagTree) {
             (cls[g] == kDagTree ? tre : sel)[depth[w]][gates[stride * g + 4]].push_back((int32_t)g);
+        } else if (cls[g] == kDagMv || cls[g] == kDagTreeMv) {
+            (cls[g] == kDagTreeMv ? tmv : mvn)[depth[w]][gates[stride * g + 4]].push_back((int32_t)g);
         } else if (cls[g] == 2) {
             auto &L = lin[depth[w]];
             if ((int)L.size() < sub[w]) L.resize(sub[w]);
@@ -245,6 +314,7 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
         if (G.size() > plan.max_width) plan.max_width = G.size();
         size_t rot = k == 2 ? 0 : (k == 1 ? 2 * G.size() : G.size());
         if (k == kDagTree) rot = G.size() * (size_t)(luts->trees[tree].p_hi / luts->trees[tree].lo.theta + 1);   // R level-1 rotations + the selection
+        if (k == kDagTreeMv) rot = G.size() * (size_t)(1 + luts->mvs[tree].k);   // one multi-value rotation + k selections
         if (rot > plan.max_rot) plan.max_rot = rot;
         if (k >= 4 && k < kDagSelect && dag_lut_theta(k < kDagEnc ? k : k - 4) > plan.max_theta) plan.max_theta = dag_lut_theta(k < kDagEnc ? k : k - 4);
         plan.rotations += (int64_t)rot;
@@ -255,6 +325,10 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
             for (int32_t k : {8, 9, 10}) emit(d, 0, k, boot[d][k]);
             for (const auto &kv : sel[d]) emit(d, 0, kDagSelect, kv.second, kv.first);
             for (const auto &kv : tre[d]) emit(d, 0, kDagTree, kv.second, kv.first);
+        }
+        if (mvx) {
+            for (const auto &kv : mvn[d]) emit(d, 0, kDagMv, kv.second, kv.first);
+            for (const auto &kv : tmv[d]) emit(d, 0, kDagTreeMv, kv.second, kv.first);
         }
         for (size_t q = 0; q < lin[d].size(); q++) emit(d, (int32_t)q + 1, 2, lin[d][q]);
     }
@@ -281,10 +355,21 @@ int dag_lut_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, s
 // Host-side checks and plan of thfhe_dag_run_tree_batch, before any device work and before either context is looked at: what
 // dag_lut_plan checks (specs / tv may both be absent), the encrypted-table and level-1 row counts, every tree spec's `hi` half and p_hi (the rules of
 // thfhe_tree_lut_bootstrap; the `lo` half when a TREE row uses the entry), then dag_plan's row checks with the three node kinds.
+// mv (thfhe_dag_run_mv_batch): the multi-value families too -- their counts here, every mvs[] entry when a row uses it (dag_mv_spec_check);
+// null: a run without them, which rejects MV and TREE_MV rows as opcodes it does not define.
+struct DagMvFamilies {
+    const thfhe_mv_spec *mvs;
+    int n_mvs;
+    const int32_t *tv0;
+    int n_bases;
+    const int32_t *factors;
+    size_t n_factor_words;
+};
 template <typename Classify>
 int dag_tree_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs, int n_specs, const int32_t *tv,
                   int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc, const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1,
-                  int n_tv1_rows, const int32_t *out_wires, size_t n_out, const int32_t *outputs, Classify classify, DagPlan &plan) {
+                  int n_tv1_rows, const int32_t *out_wires, size_t n_out, const int32_t *outputs, Classify classify, DagPlan &plan,
+                  const DagMvFamilies *mv = nullptr) {
     if ((!inputs && n_inputs) || (!nodes && n_nodes) || (!outputs && n_nodes) || (!out_wires && n_out)) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if ((!specs && n_specs) || (!tv && n_luts) || ((!enc_a || !enc_b) && n_enc) || (!trees && n_trees) || (!tv1 && n_tv1_rows))
         return thfhe_fail(THFHE_E_INVALID, "null argument: a table family with a count but no pointer");
@@ -293,6 +378,14 @@ int dag_tree_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, 
     if (n_enc < 0 || n_enc > (1 << 18)) return thfhe_fail(THFHE_E_INVALID, "n_enc must be 1 .. 262144 (0 with enc_a = enc_b = NULL)");
     if (n_trees < 0 || n_trees > 1024 || (trees && n_trees < 1)) return thfhe_fail(THFHE_E_INVALID, "n_trees must be 1 .. 1024 (0 with trees = NULL)");
     if (n_tv1_rows < 0 || n_tv1_rows > (1 << 18) || (tv1 && n_tv1_rows < 1)) return thfhe_fail(THFHE_E_INVALID, "n_tv1_rows must be 1 .. 262144 (0 with tv1 = NULL)");
+    if (mv) {
+        if ((!mv->mvs && mv->n_mvs) || (!mv->tv0 && mv->n_bases) || (!mv->factors && mv->n_factor_words))
+            return thfhe_fail(THFHE_E_INVALID, "null argument: a table family with a count but no pointer");
+        if (mv->n_mvs < 0 || mv->n_mvs > 1024 || (mv->mvs && mv->n_mvs < 1)) return thfhe_fail(THFHE_E_INVALID, "n_mvs must be 1 .. 1024 (0 with mvs = NULL)");
+        if (mv->n_bases < 0 || mv->n_bases > 1024 || (mv->tv0 && mv->n_bases < 1)) return thfhe_fail(THFHE_E_INVALID, "n_bases must be 1 .. 1024 (0 with mv_tv0 = NULL)");
+        if (mv->n_factor_words > ((size_t)1 << 28) || (mv->factors && mv->n_factor_words < 1))
+            return thfhe_fail(THFHE_E_INVALID, "n_factor_words must be 1 .. 2^28 (0 with mv_factors = NULL)");
+    }
     for (int s = 0; s < n_specs; s++)
         THFHE_TRY(lut_spec_check(specs[s]));
     for (int t = 0; t < n_trees; t++) {
@@ -305,6 +398,10 @@ int dag_tree_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, 
         if (out_wires[s] < 0 || (size_t)out_wires[s] >= n_inputs + n_nodes) return thfhe_fail(THFHE_E_INVALID, "output wire id out of range");
     DagLuts luts{specs, n_specs, n_luts};
     luts.ext = true, luts.n_enc = enc_a ? n_enc : 0, luts.trees = trees, luts.n_trees = n_trees, luts.n_tv1_rows = tv1 ? n_tv1_rows : 0;
+    if (mv) {
+        luts.mv = true, luts.mvs = mv->mvs, luts.n_mvs = mv->mvs ? mv->n_mvs : 0, luts.n_bases = mv->tv0 ? mv->n_bases : 0;
+        luts.n_factor_words = mv->factors ? mv->n_factor_words : 0;
+    }
     return dag_plan(nodes, n_inputs, n_nodes, classify, plan, &luts);
 }
 
@@ -328,7 +425,8 @@ struct DagLutSlice {
 };
 
 // A SELECT or TREE launch group as DagExecute hands it to the engine (thfhe_dag_run_tree_batch): the wire table, the group's index columns
-// (t_y = a SELECT's first candidate wire, a TREE's row0), `all` = cnt nodes x instances jobs.  The engine cuts it into slices, runs the chain of
+// (t_y = a SELECT's first candidate wire, a TREE's row0), `all` = cnt nodes x instances jobs.  MV and TREE_MV groups (thfhe_dag_run_mv_batch): tree =
+// the group's mvs[] entry, t_y = each node's table t.  The engine cuts it into slices, runs the chain of
 // each and scatters the results into the wires t_out.
 struct DagExtGroup {
     int cls, tree;

@@ -507,6 +507,8 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     DevBuf d_tree_tab, d_tree_lwe, d_tree_a, d_tree_b;
     // encrypted-table and tree nodes of the gate DAG (thfhe_dag_run_tree_batch): the run's encrypted tables (masks, bodies) and level-1 rows
     DevBuf d_dag_enc_a, d_dag_enc_b, d_dag_tv1;
+    // multi-value nodes of the gate DAG (thfhe_dag_run_mv_batch): the run's base vectors and the factor array of all its specs
+    DevBuf d_dag_mv_tv0, d_dag_mv_w;
     size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate); also the output records (samples x q) per slice of thfhe_mv_lut_bootstrap
     // staging for the host-buffer API
     Stage stage;
@@ -725,14 +727,16 @@ int lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv, int
 }
 
 // Grow-only workspace of one tree chain over S samples / nodes: S R level-1 jobs of theta_lo records each (a SELECT group, whose candidates are
-// gathered: R = theta_lo = 1, the selection rotation alone), their S p candidates, S packed tables.
-int tree_workspace(thfhe_ctx *c, size_t S, size_t p, size_t R, size_t theta_lo) {
-    int rc = ensure_workspace(c, S * R);
-    if (!rc) rc = c->d_u.grow(S * R * theta_lo * 1025 * sizeof(int32_t));
-    if (!rc) rc = c->d_lut_idx.grow(S * R * sizeof(int32_t));
-    if (!rc) rc = c->d_tree_lwe.grow(S * p * (c->p.n + 1) * sizeof(int32_t));
-    if (!rc) rc = c->d_tree_a.grow(S * 1024 * sizeof(int32_t));
-    if (!rc) rc = c->d_tree_b.grow(S * 1024 * sizeof(int32_t));
+// gathered: R = theta_lo = 1, the selection rotation alone), their S k p candidates, S k packed tables and selection jobs (k tables per sample,
+// R = 1, theta_lo = k p).
+int tree_workspace(thfhe_ctx *c, size_t S, size_t p, size_t R, size_t theta_lo, size_t k = 1) {
+    const size_t jobs = S * std::max(R, k);
+    int rc = ensure_workspace(c, jobs);
+    if (!rc) rc = c->d_u.grow(std::max(S * R * theta_lo, S * k) * 1025 * sizeof(int32_t));
+    if (!rc) rc = c->d_lut_idx.grow(jobs * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_lwe.grow(S * k * p * (c->p.n + 1) * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_a.grow(S * k * 1024 * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_b.grow(S * k * 1024 * sizeof(int32_t));
     return rc;
 }
 
@@ -742,16 +746,18 @@ int tree_workspace(thfhe_ctx *c, size_t S, size_t p, size_t R, size_t theta_lo) 
 // box packing of the candidates into S encrypted tables (pack_boxes_enqueue enqueues on the stream it is given), and the selection: sample s rotates
 // its own packed table on the `hi` source, coefficient 0 key-switched into d_out.  seam(1) / seam(2) run after level 1 and after the packing: what
 // the caller has to put on the stream there.  mv: level 1 is ONE multi-value rotation per sample of the base vector d_tv1 with
-// theta_lo = p outputs, the candidates in the same order.
+// theta_lo = k p outputs, the candidates in the same order.  k > 1 (mv only): k tables per sample -- output j p + h of the rotation is
+// candidate h of table j, so the packed table of (s, j) is sample s k + j, and selection job s k + j rotates it on sample s's `hi` operands (the
+// `hi` source repeats every sample k times and numbers its jobs): S k records into d_out.
 template <typename Lo, typename Hi, typename Seam>
 int enqueue_tree_chain(thfhe_ctx *c, thfhe_poly_ctx *pc, const Lo &lo, const int32_t *d_tv1, int theta_lo, const Hi &hi, size_t S, int p, int32_t *d_out,
-                       Seam seam, const MvArgs *mv = nullptr) {
+                       Seam seam, const MvArgs *mv = nullptr, size_t k = 1) {
     int32_t *const cand = c->d_tree_lwe.as<int32_t>(), *const tab_a = c->d_tree_a.as<int32_t>(), *const tab_b = c->d_tree_b.as<int32_t>();
-    if constexpr (!std::is_same_v<Lo, std::nullptr_t>) THFHE_TRY(enqueue_pbs(c, lo, S * (p / theta_lo), d_tv1, nullptr, theta_lo, nullptr, cand, false, mv));
+    if constexpr (!std::is_same_v<Lo, std::nullptr_t>) THFHE_TRY(enqueue_pbs(c, lo, S * (k * p / theta_lo), d_tv1, nullptr, theta_lo, nullptr, cand, false, mv));
     THFHE_TRY(seam(1));
-    THFHE_TRY(pack_boxes_enqueue(pc, cand, S * p, p, tab_a, tab_b, c->stream));
+    THFHE_TRY(pack_boxes_enqueue(pc, cand, S * k * p, p, tab_a, tab_b, c->stream));
     THFHE_TRY(seam(2));
-    return enqueue_pbs(c, hi, S, tab_b, tab_a, 1, nullptr, d_out);
+    return enqueue_pbs(c, hi, S * k, tab_b, tab_a, 1, nullptr, d_out);
 }
 
 // ---- gate-DAG entry points: what thfhe_dag_run_batch, thfhe_dag_run_lut_batch and thfhe_dag_run_tree_batch share ----
@@ -780,13 +786,20 @@ struct SkDagTables {
     const thfhe_tree_spec *trees = nullptr;
     const int32_t *tv1 = nullptr;
     int n_tv1_rows = 0;
+    // thfhe_dag_run_mv_batch: the multi-value specs, base vectors int32[n_bases][N] and the factor array
+    const thfhe_mv_spec *mvs = nullptr;
+    const int32_t *mv_tv0 = nullptr;
+    int n_bases = 0;
+    const int32_t *mv_factors = nullptr;
+    size_t n_factor_words = 0;
 };
 
 // The device side of thfhe_dag_run_lut_batch and thfhe_dag_run_tree_batch, both contexts locked by the caller (pc: null in a run without SELECT /
 // TREE groups).  Gate classes run as in thfhe_dag_run_batch.  A LUT group is one PBS stage on the wire table over the run's plaintext tables
 // (DESIGN 4.9), a LUT_ENC group the same over its encrypted tables.  A SELECT group gathers its candidates into the buffer the box packing reads
-// and runs the tree chain from there; a TREE group runs the whole chain with both prologues reading the wire table.  Everything is
-// enqueued on the gate context's stream.
+// and runs the tree chain from there; a TREE group runs the whole chain with both prologues reading the wire table.  An MV group is
+// one multi-value PBS stage on the wire table, its q records per node scattered into consecutive wires; a TREE_MV group the k-table chain with both
+// prologues on the wire table.  Everything is enqueued on the gate context's stream.
 int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const SkDagTables &T, const int32_t *inputs, size_t n_inputs, size_t n_nodes,
                     size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs) {
     const int words = c->p.n + 1;
@@ -794,9 +807,25 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
     // a slice of a SELECT / TREE group: at most dag_slice nodes over all instances and at most tree_slice / p_hi of them
     const size_t dag_slice = c->dag_slice, tree_slice = c->tree_slice;
     auto slice_of = [&](int tree, size_t all) { return std::min({all, dag_slice, std::max<size_t>(1, tree_slice / (size_t)T.trees[tree].p_hi)}); };
+    // ... of an MV / TREE_MV group: at most tree_slice / q, resp. tree_slice / (k q) nodes -- the flat calls' workspace rules
+    auto mv_slice_of = [&](int mv, size_t all) { return std::min({all, dag_slice, std::max<size_t>(1, tree_slice / ((size_t)T.mvs[mv].k * T.mvs[mv].q))}); };
     size_t w_cand = 0;
     for (const DagBatch &b : plan.batches) {
         if (b.cls < kDagSelect) continue;
+        if (b.cls == kDagMv || b.cls == kDagTreeMv) {   // every buffer the group's slices use, the staging output included, before dag_execute takes pointers
+            const thfhe_mv_spec &m = T.mvs[b.tree];
+            const size_t S = mv_slice_of(b.tree, b.count * instances), k = (size_t)m.k, q = (size_t)m.q;
+            if (b.cls == kDagTreeMv) {
+                THFHE_TRY(tree_workspace(c, S, q, 1, k * q, k));
+                w_cand = std::max(w_cand, S * k * q);
+            } else {
+                THFHE_TRY(ensure_workspace(c, S));
+                THFHE_TRY(c->d_u.grow(S * q * 1025 * sizeof(int32_t)));
+                THFHE_TRY(c->d_lut_idx.grow(S * sizeof(int32_t)));
+            }
+            THFHE_TRY(c->stage.out.grow(S * (b.cls == kDagTreeMv ? k : q) * words * sizeof(int32_t)));
+            continue;
+        }
         const thfhe_tree_spec &ts = T.trees[b.tree];
         const size_t S = slice_of(b.tree, b.count * instances), p = (size_t)ts.p_hi, theta_lo = b.cls == kDagTree ? (size_t)ts.lo.theta : 1;
         THFHE_TRY(tree_workspace(c, S, p, b.cls == kDagTree ? p / theta_lo : 1, theta_lo));
@@ -818,6 +847,8 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
     THFHE_TRY(upload(c->d_dag_enc_a, T.enc_a, (size_t)T.n_enc * 1024 * sizeof(int32_t)));
     THFHE_TRY(upload(c->d_dag_enc_b, T.enc_b, (size_t)T.n_enc * 1024 * sizeof(int32_t)));
     THFHE_TRY(upload(c->d_dag_tv1, T.tv1, (size_t)T.n_tv1_rows * 1024 * sizeof(int32_t)));
+    THFHE_TRY(upload(c->d_dag_mv_tv0, T.mv_tv0, (size_t)T.n_bases * 1024 * sizeof(int32_t)));
+    THFHE_TRY(upload(c->d_dag_mv_w, T.mv_factors, T.n_factor_words * sizeof(int32_t)));
     const unsigned wb = (unsigned)((words + 255) / 256);
     return dag_execute(
         plan, c->dag, st, words, n_inputs, n_nodes, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
@@ -828,11 +859,34 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
                                s.enc ? c->d_dag_enc_a.as<int32_t>() : nullptr, theta, nullptr, c->stage.out_ptr());
         },
         [&](const DagExtGroup &g) {
+            auto no_seam = [](int) { return (int)THFHE_OK; };
+            if (g.cls == kDagMv || g.cls == kDagTreeMv) {   // t_y = each node's table
+                const thfhe_mv_spec m = T.mvs[g.tree];
+                const bool is_tree = g.cls == kDagTreeMv;
+                const int outs = is_tree ? m.k : m.q, hi0 = m.lo.n_inputs;
+                const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};
+                const int32_t *const tv0 = c->d_dag_mv_tv0.as<int32_t>() + (size_t)m.base * 1024;
+                const MvArgs mv{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p};
+                const long slice = (long)mv_slice_of(g.tree, (size_t)g.all);
+                for (long first = 0; first < g.all; first += slice) {
+                    const long S = std::min(slice, g.all - first);
+                    const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
+                    if (is_tree) {
+                        const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
+                        THFHE_TRY(enqueue_tree_chain(c, pc, lo, tv0, m.k * m.q, hi, (size_t)S, m.q, c->stage.out_ptr(), no_seam, &mv, (size_t)m.k));
+                    } else {
+                        THFHE_TRY(enqueue_pbs(c, lo, (size_t)S, tv0, nullptr, m.q, nullptr, c->stage.out_ptr(), false, &mv));
+                    }
+                    hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(S * outs), wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires,
+                                       first, S, g.cnt, g.n_wires, words, outs);
+                    THFHE_HIP(hipGetLastError());
+                }
+                return (int)THFHE_OK;
+            }
             const thfhe_tree_spec ts = T.trees[g.tree];
             const int p = ts.p_hi, hi0 = g.cls == kDagTree ? ts.lo.n_inputs : 0;
             const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the index operands of a TREE node follow its lo.n_inputs level-1 operands
             const long slice = (long)slice_of(g.tree, (size_t)g.all);
-            auto no_seam = [](int) { return (int)THFHE_OK; };
             for (long first = 0; first < g.all; first += slice) {
                 const long S = std::min(slice, g.all - first);
                 const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
@@ -873,22 +927,15 @@ int tree_validate_index(const int32_t *table_index, int n_tables, size_t count) 
             if (table_index[g] < 0 || table_index[g] >= n_tables) return thfhe_fail(THFHE_E_INVALID, "table_index out of range (0 .. n_tables-1)");
     return THFHE_OK;
 }
-// the rules a multi-value rotation adds to lut_validate's: theta 1, p taps, q outputs, the factor tables
-int mv_validate(const thfhe_lut_spec &sp, int p, int q, int n_tables) {
-    if (sp.theta != 1) return thfhe_fail(THFHE_E_INVALID, "multi-value: the spec's theta must be 1");
-    if (p < 2 || p > 64 || (p & (p - 1))) return thfhe_fail(THFHE_E_INVALID, "multi-value: p must be a power of two in 2 .. 64");
-    if (q < 1 || q > 64) return thfhe_fail(THFHE_E_INVALID, "multi-value: q must be 1 .. 64");
-    if (n_tables < 1 || n_tables > 1024) return thfhe_fail(THFHE_E_INVALID, "multi-value: n_tables must be 1 .. 1024");
-    return THFHE_OK;
-}
 
 // Two-digit tree PBS: per slice of S samples one enqueue_tree_chain on contiguous operands -- level 1 on the rows
 // tv[table[s]][r] (tv_rows rows of N words in all) and the `lo` operands, the selection on the `hi` operands.  Only the inputs of a slice go up and its
 // S results come down.  factors: level 1 is one multi-value rotation per sample of the base vector tv with the p_hi factors of mv_p taps
-// of table[s], int32[mv_tables][p_hi][mv_p].  The arguments have passed the entry's host checks.
+// of table[s], int32[mv_tables][p_hi][mv_p].  k (with factors only): k tables per sample from the one rotation, factors
+// int32[mv_tables][k][p_hi][mv_p], out int32[count][k][n+1].  The arguments have passed the entry's host checks.
 int tree_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec &lo, const thfhe_lut_spec &hi, int p_hi, const int32_t *tv, size_t tv_rows,
                    const int32_t *factors, int mv_p, int mv_tables, const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2,
-                   const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
+                   const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count, int k = 1) {
     if (!c || !pc) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     if (pack_ctx_device(pc) != c->device) return thfhe_fail(THFHE_E_INVALID, "tree: the gate context and the packing context must be on the same device");
     DevLock lk(*c);
@@ -898,13 +945,13 @@ int tree_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec &lo, c
     if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
     if (pack_key_n(pc) != n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
     if (count == 0) return THFHE_OK;
-    const int theta1 = factors ? p_hi : lo.theta, R = p_hi / theta1;   // level-1 records per rotation, rotations per sample
-    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / p_hi));
-    const size_t tv_bytes = tv_rows * 1024 * sizeof(int32_t), w_bytes = factors ? (size_t)mv_tables * p_hi * mv_p * sizeof(int32_t) : 0;
+    const int theta1 = factors ? k * p_hi : lo.theta, R = k * p_hi / theta1;   // level-1 records per rotation, rotations per sample
+    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / ((size_t)k * p_hi)));
+    const size_t tv_bytes = tv_rows * 1024 * sizeof(int32_t), w_bytes = factors ? (size_t)mv_tables * k * p_hi * mv_p * sizeof(int32_t) : 0;
     int rc = c->d_tv.grow(tv_bytes);
     if (!rc && factors) rc = c->d_mv_w.grow(w_bytes);
-    if (!rc) rc = tree_workspace(c, S_max, p_hi, R, theta1);
-    if (!rc) rc = c->stage.grow(S_max * words);
+    if (!rc) rc = tree_workspace(c, S_max, p_hi, R, theta1, k);
+    if (!rc) rc = c->stage.grow(S_max * k * words);
     if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
     if (rc) return rc;
     hipStream_t st = c->stream;
@@ -927,18 +974,18 @@ int tree_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec &lo, c
         if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_tree_tab.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
         if (c->profiling && first) THFHE_HIP(hipEventRecord(c->ev[0], st));
         // profiling, on the last slice: level 1 | packing | selection.  The `hi` operands replace the `lo` ones in the staging arrays once level 1 is enqueued.
-        auto seam = [&](int k) {
-            if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[k], st));
-            return k == 2 ? upload(hi_in) : (int)THFHE_OK;
+        auto seam = [&](int stage) {
+            if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[stage], st));
+            return stage == 2 ? upload(hi_in) : (int)THFHE_OK;
         };
         THFHE_TRY(enqueue_tree_chain(c, pc, LutFlatSrc<LutIdx::table>{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr},
-                                     c->d_tv.as<int32_t>(), theta1, LutFlatSrc<LutIdx::job>{in0, in1, in2, hi, 1, nullptr}, S, p_hi, c->stage.out_ptr(), seam,
-                                     factors ? &mv : nullptr));
+                                     c->d_tv.as<int32_t>(), theta1, LutFlatSrc<LutIdx::job>{in0, in1, in2, hi, k, nullptr}, S, p_hi, c->stage.out_ptr(), seam,
+                                     factors ? &mv : nullptr, (size_t)k));
         if (c->profiling && last) {
             THFHE_HIP(hipEventRecord(c->ev[3], st));
             c->ev_valid = true;
         }
-        THFHE_HIP(hipMemcpyAsync(out + s0 * words, c->stage.out_ptr(), in_bytes, hipMemcpyDeviceToHost, st));
+        THFHE_HIP(hipMemcpyAsync(out + s0 * k * words, c->stage.out_ptr(), in_bytes * k, hipMemcpyDeviceToHost, st));
     }
     THFHE_HIP(hipStreamSynchronize(st));
     return THFHE_OK;
@@ -983,6 +1030,37 @@ int mv_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv0,
     }
     THFHE_HIP(hipStreamSynchronize(st));
     return THFHE_OK;
+}
+
+// Encrypted-table, select and tree nodes among the gates and LUT nodes, and the multi-value nodes among those (mv null:
+// a run without their families, thfhe_dag_run_tree_batch): the host checks and the two locks here, the run in sk_dag_run_luts.  Both contexts stay
+// locked for the run.
+int sk_dag_run_ext_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                         const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
+                         const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const DagMvFamilies *mv, size_t instances,
+                         const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
+    DagPlan plan;
+    int rc = dag_tree_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, out_wires, n_out,
+                           outputs, sk_dag_classify, plan, mv);
+    if (rc) return rc;
+    if (stats) plan.fill_stats(stats);   // the plan's figures need no device
+    const bool packs = plan.has_tree_groups();
+    if (!c || (packs && !pc)) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (packs && pack_ctx_device(pc) != c->device)
+        return thfhe_fail(THFHE_E_INVALID, "tree: the gate context and the packing context must be on the same device");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    std::unique_lock<std::mutex> pg;   // always after the gate context's: nothing else takes both
+    if (packs) pg = std::unique_lock<std::mutex>(pack_ctx_mutex(pc));
+    if (packs) {
+        if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
+        if (pack_key_n(pc) != c->p.n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
+    }
+    if (instances == 0 || n_nodes == 0) return THFHE_OK;
+    if (instances > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "too many instances");
+    SkDagTables T{specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, tv1, n_tv1_rows};
+    if (mv) T.mvs = mv->mvs, T.mv_tv0 = mv->tv0, T.n_bases = mv->tv0 ? mv->n_bases : 0, T.mv_factors = mv->factors, T.n_factor_words = mv->factors ? mv->n_factor_words : 0;
+    return sk_dag_run_luts(c, packs ? pc : nullptr, plan, T, inputs, n_inputs, n_nodes, instances, out_wires, n_out, outputs);
 }
 
 }  // namespace
@@ -1127,33 +1205,23 @@ int thfhe_dag_run_lut_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs
     return sk_dag_run_luts(c, nullptr, plan, SkDagTables{specs, n_specs, tv, n_luts}, inputs, n_inputs, n_nodes, instances, out_wires, n_out, outputs);
 }
 
-// Encrypted-table, select and tree nodes among the gates and LUT nodes: the host checks and the two locks here, the run in
-// sk_dag_run_luts.  Both contexts stay locked for the run.
+// both entries are sk_dag_run_ext_batch, without and with the multi-value families.
 int thfhe_dag_run_tree_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
                              const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
                              const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, size_t instances, const int32_t *out_wires,
                              size_t n_out, int32_t *outputs, int64_t *stats) {
-    DagPlan plan;
-    int rc = dag_tree_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, out_wires, n_out,
-                           outputs, sk_dag_classify, plan);
-    if (rc) return rc;
-    if (stats) plan.fill_stats(stats);   // the plan's figures need no device
-    const bool packs = plan.has_tree_groups();
-    if (!c || (packs && !pc)) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (packs && pack_ctx_device(pc) != c->device)
-        return thfhe_fail(THFHE_E_INVALID, "tree: the gate context and the packing context must be on the same device");
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    std::unique_lock<std::mutex> pg;   // always after the gate context's: nothing else takes both
-    if (packs) pg = std::unique_lock<std::mutex>(pack_ctx_mutex(pc));
-    if (packs) {
-        if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
-        if (pack_key_n(pc) != c->p.n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
-    }
-    if (instances == 0 || n_nodes == 0) return THFHE_OK;
-    if (instances > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "too many instances");
-    return sk_dag_run_luts(c, packs ? pc : nullptr, plan, SkDagTables{specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, tv1, n_tv1_rows},
-                           inputs, n_inputs, n_nodes, instances, out_wires, n_out, outputs);
+    return sk_dag_run_ext_batch(c, pc, inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, nullptr,
+                                instances, out_wires, n_out, outputs, stats);
+}
+
+int thfhe_dag_run_mv_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                           const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
+                           const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs,
+                           const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, size_t instances, const int32_t *out_wires,
+                           size_t n_out, int32_t *outputs, int64_t *stats) {
+    const DagMvFamilies mv{mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words};
+    return sk_dag_run_ext_batch(c, pc, inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, &mv,
+                                instances, out_wires, n_out, outputs, stats);
 }
 
 int thfhe_set_dag_slice(thfhe_ctx *c, size_t max_gates) { return ctx_set_dag_slice(c, max_gates); }
@@ -1243,6 +1311,19 @@ int thfhe_tree_lut_bootstrap_mv(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lu
     THFHE_TRY(mv_validate(*spec_lo, p_lo, p_hi, n_tables));
     THFHE_TRY(tree_validate_index(table_index, n_tables, count));
     return tree_bootstrap(c, pc, *spec_lo, *spec_hi, p_hi, tv0, 1, factors, p_lo, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
+}
+
+int thfhe_tree_lut_bootstrap_mvk(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, int p_lo, int k,
+                                 const int32_t *tv0, const int32_t *factors, int n_tables, const int32_t *table_index, const int32_t *lo0,
+                                 const int32_t *lo1, const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out,
+                                 size_t count) {
+    // host checks, before either context is looked at: those of thfhe_tree_lut_bootstrap_mv, then k and k p_hi
+    THFHE_TRY(tree_validate(spec_lo, spec_hi, p_hi, tv0, lo0, lo1, lo2, hi0, hi1, hi2, out));
+    if (!factors) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    THFHE_TRY(mv_validate(*spec_lo, p_lo, p_hi, n_tables));
+    THFHE_TRY(tree_validate_index(table_index, n_tables, count));
+    THFHE_TRY(mvk_validate(p_hi, k));
+    return tree_bootstrap(c, pc, *spec_lo, *spec_hi, p_hi, tv0, 1, factors, p_lo, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count, k);
 }
 
 int thfhe_keyswitch(thfhe_ctx *c, const int32_t *in_N1, int32_t *out, size_t count) {

@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("THFHE_HIP_LIB", os.path.join(os.path.dirname(_HERE), 
 # gate opcodes (include/thfhe_hip.h enum thfhe_gate)
 NAND, OR, AND, XOR, XNOR, NOR, ANDNY, ANDYN, ORNY, ORYN, MUX, NOT, COPY, AND3 = range(14)
 LUT, LUT_OUT = 14, 15   # gate-DAG LUT node and its outputs j > 0 (dag_run_lut_batch, dag_run_tree_batch)
-LUT_ENC, SELECT, TREE = 16, 17, 18   # gate-DAG encrypted-table, select and tree nodes (CloudKey.dag_run_tree_batch only)
+LUT_ENC, SELECT, TREE = 16, 17, 18   # gate-DAG encrypted-table, select and tree nodes (CloudKey.dag_run_tree_batch, dag_run_mv_batch)
+MV, TREE_MV = 19, 20                 # gate-DAG multi-value and k-output multi-value tree nodes (CloudKey.dag_run_mv_batch only)
 
 MU8 = 1 << 29     # encode_message(1, 8), Torus32      (numeric-functions.jl:86-89)
 MU8_64 = 1 << 61  # encode_message64(1, 8), Torus64    (numeric-functions.jl:92-95)
@@ -143,6 +144,12 @@ class TreeSpec(C.Structure):
     _fields_ = [("lo", LutSpec), ("hi", LutSpec), ("p_hi", C.c_int32)]
 
 
+class MvSpec(C.Structure):
+    """thfhe_mv_spec (include/thfhe_hip.h): the prologues, shape (p taps, q outputs or p_hi, k tables per node), base vector and factor tables of the
+    MV / TREE_MV nodes of one launch group."""
+    _fields_ = [("lo", LutSpec), ("hi", LutSpec)] + [(f, C.c_int32) for f in ("p", "q", "k", "base", "factors_off", "n_tables")]
+
+
 def _lut_spec(s):
     """LutSpec from a (n_inputs, (w0, w1, w2), bias, theta) tuple (or a LutSpec)."""
     if isinstance(s, LutSpec):
@@ -174,6 +181,9 @@ SIGNATURES = {
                                           C.c_size_t, _i32p, _i64p]),
     "thfhe_dag_run_tree_batch": (C.c_int, [_vp, _vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, _i32p, _i32p, C.c_int,
                                            C.POINTER(TreeSpec), C.c_int, _i32p, C.c_int, C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
+    "thfhe_dag_run_mv_batch": (C.c_int, [_vp, _vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, _i32p, _i32p, C.c_int,
+                                         C.POINTER(TreeSpec), C.c_int, _i32p, C.c_int, C.POINTER(MvSpec), C.c_int, _i32p, C.c_int, _i32p, C.c_size_t,
+                                         C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_bootstrap": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_keyswitch": (C.c_int, [_vp, _i32p, _i32p, C.c_size_t]),
@@ -189,6 +199,8 @@ SIGNATURES = {
                                                       C.c_size_t]),
     "thfhe_tree_lut_bootstrap_mv": (C.c_int, [_vp, _vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p,
                                               _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_tree_lut_bootstrap_mvk": (C.c_int, [_vp, _vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p,
+                                               _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_dev_alloc": (_vp, [_vp, C.c_size_t]),
     "thfhe_dev_free": (None, [_vp, _vp]),
     "thfhe_copy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
@@ -675,15 +687,50 @@ class CloudKey(_EvalKey):
                                                  _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
         return out
 
+    def tree_lut_bootstrap_mvk(self, poly_ctx, factors, lo, hi, *, tv0, weights_lo=(1,), bias_lo=0, weights_hi=(1,), bias_hi=0, table_index=None):
+        """tree_lut_bootstrap_mv with k tables per sample (thfhe_tree_lut_bootstrap_mvk): out[s][j] = f_j(hi_s, lo_s) in 1 + k rotations.
+        tv0, factors int32[k][p_hi][p_lo] or int32[n_tables][k][p_hi][p_lo]: thfhe.lut.tree_mvk_factors; k p_hi <= 64.  int32[count, k, n+1]."""
+        as_tuple = lambda v: tuple(v) + (None,) * (3 - len(v)) if isinstance(v, (tuple, list)) else (v, None, None)
+        lo_r, spec_lo, plo = self._lut_args(as_tuple(lo), weights_lo, bias_lo, 1, "tree_lut_bootstrap_mvk (lo)")
+        hi_r, spec_hi, phi = self._lut_args(as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap_mvk (hi)")
+        _same_count(lo_r[0], hi_r[0])
+        count = lo_r[0].shape[0]
+        w = np.ascontiguousarray(factors, np.int32)
+        if w.ndim == 3:
+            w = w[None]
+        if w.ndim != 4 or w.size == 0:
+            raise ValueError("factors: expected int32[k][p_hi][p_lo] or int32[n_tables][k][p_hi][p_lo]")
+        _, tv0, idx = self._mv_tables(w[0], tv0, table_index, count)
+        out = np.empty((count, w.shape[1], self.words), np.int32)
+        _check(lib().thfhe_tree_lut_bootstrap_mvk(self.h, poly_ctx.h, C.byref(spec_lo), C.byref(spec_hi), w.shape[2], w.shape[3], w.shape[1], _p32(tv0), _p32(w),
+                                                  w.shape[0], _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
+        return out
+
+    def dag_run_mv_batch(self, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, mvs=(), mv_tv0=None, mv_factors=None,
+                         out_wires=None, pack=None):
+        """dag_run_tree_batch with multi-value nodes (thfhe_dag_run_mv_batch).  mvs: MvSpec or (lo, hi, p, q, k, base, factors_off, n_tables)
+        tuples (hi may be None: MV only); mv_tv0: int32[n_bases][N] base vectors; mv_factors: int32[words], the taps of every spec."""
+        none = (1, (0, 0, 0), 0, 1)
+        mv = (MvSpec * len(mvs))(*[m if isinstance(m, MvSpec) else MvSpec(_lut_spec(m[0]), _lut_spec(m[1] or none), *[int(v) for v in m[2:]]) for m in mvs]) if len(mvs) else None
+        tv0 = None if mv_tv0 is None else np.ascontiguousarray(mv_tv0, np.int32).reshape(-1, self.params.N)
+        fac = None if mv_factors is None else np.ascontiguousarray(mv_factors, np.int32).reshape(-1)
+        families = (mv, len(mvs), _p32(tv0), 0 if tv0 is None else tv0.shape[0], _p32(fac), 0 if fac is None else fac.shape[0])
+        return self._dag_run_ext(lib().thfhe_dag_run_mv_batch, families, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack)
+
     def dag_run_tree_batch(self, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, out_wires=None, pack=None):
         """dag_run_lut_batch with encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch, DESIGN 4.12).  nodes: int32[n_nodes][6];
         specs, tv: as dag_run_lut_batch, both may be absent; enc_a, enc_b: int32[n_enc][N] encrypted tables; trees: (lo, hi, p_hi) tuples of spec
         tuples (lo may be None: SELECT only) or TreeSpec; tv1: int32[rows][N] level-1 rows; pack: the threshold.PolyContext holding the packing key
         (needed when a SELECT or TREE node is present).  Returns (int32[instances][len(out_wires) or n_nodes][words], stats)."""
+        return self._dag_run_ext(lib().thfhe_dag_run_tree_batch, (), input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack)
+
+    def _dag_run_ext(self, fn, families, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack):
+        """What dag_run_tree_batch and dag_run_mv_batch share: fn(contexts, inputs, nodes, the earlier table families, `families` -- the multi-value
+        arguments of thfhe_dag_run_mv_batch, none for thfhe_dag_run_tree_batch --, instances, outputs, stats)."""
         words, N = self.words, self.params.N
         x = np.ascontiguousarray(input_records, np.int32)
         if x.ndim != 3 or x.shape[2] != words:
-            raise ValueError("dag_run_tree_batch: input records must be int32[instances][n_inputs][%d]" % words)
+            raise ValueError("dag_run_tree_batch / dag_run_mv_batch: input records must be int32[instances][n_inputs][%d]" % words)
         g = np.ascontiguousarray(nodes, np.int32).reshape(-1, 6)
         sp = (LutSpec * len(specs))(*[_lut_spec(s) for s in specs]) if len(specs) else None
         none = (1, (0, 0, 0), 0, 1)
@@ -697,13 +744,14 @@ class CloudKey(_EvalKey):
         sel = None if out_wires is None else np.ascontiguousarray(out_wires, np.int32).reshape(-1)
         out = np.zeros((q, g.shape[0] if sel is None else sel.shape[0], words), np.int32)
         st = np.zeros(4, np.int64)
-        _check(lib().thfhe_dag_run_tree_batch(self.h, None if pack is None else pack.h, _p32(x), n_in, _p32(g), g.shape[0], sp, len(specs), _p32(tv), rows(tv),
-                                              _p32(enc_a), _p32(enc_b), rows(enc_a), tr, len(trees), _p32(tv1), rows(tv1), q, _p32(sel),
-                                              0 if sel is None else sel.shape[0], _p32(out), st.ctypes.data_as(_i64p)))
+        head = (self.h, None if pack is None else pack.h, _p32(x), n_in, _p32(g), g.shape[0], sp, len(specs), _p32(tv), rows(tv), _p32(enc_a), _p32(enc_b),
+                rows(enc_a), tr, len(trees), _p32(tv1), rows(tv1))
+        tail = (q, _p32(sel), 0 if sel is None else sel.shape[0], _p32(out), st.ctypes.data_as(_i64p))
+        _check(fn(*head, *families, *tail))
         return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
 
     def set_tree_slice(self, max_candidates):
-        """Level-1 candidates (samples x p_hi) per slice of tree_lut_bootstrap(_mv): bounds its workspace (8 KiB of packing scratch per candidate);
+        """Level-1 candidates (samples x p_hi, x k for tree_lut_bootstrap_mvk) per slice of tree_lut_bootstrap(_mv, _mvk): bounds its workspace (8 KiB of packing scratch per candidate);
         also the output records (samples x q) per slice of mv_lut_bootstrap."""
         _check(lib().thfhe_set_tree_slice(self.h, int(max_candidates)))
 

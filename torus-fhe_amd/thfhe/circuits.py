@@ -16,12 +16,16 @@ lut_ripple_add, from_gate_bit and to_gate_bit build integer arithmetic from them
 Encrypted-table, select and tree nodes (Circuit.lut_enc / select / tree; single key): a programmable bootstrap of an encrypted
 table, an oblivious pick among p consecutive wires, and the two-digit tree PBS, each one level.  Circuits that hold them run on
 thfhe_dag_run_tree_batch with the packing context (`pack`); tree_mul_digits multiplies two 3-bit digits with two TREE nodes.
+
+Multi-value nodes (Circuit.mv / tree_mv; single key): q functions of one digit from one rotation on q consecutive wires, and k functions
+of two digits in 1 + k rotations on k consecutive wires, each one level.  Circuits that hold them run on thfhe_dag_run_mv_batch; sbox_digits looks a
+6-bit -> 4-bit table up in one TREE_MV node.
 """
 import time
 
 import numpy as np
 
-from . import AND, COPY, LUT, LUT_ENC, LUT_OUT, MUX, NOT, OR, SELECT, TREE, XOR, _wrap32
+from . import AND, COPY, LUT, LUT_ENC, LUT_OUT, MUX, MV, NOT, OR, SELECT, TREE, TREE_MV, XOR, _wrap32
 
 
 class Circuit:
@@ -38,6 +42,9 @@ class Circuit:
         self.tree_specs = []  # (lo spec or None, hi spec, p_hi) of the SELECT / TREE launch groups, deduplicated
         self.tv1 = []         # level-1 rows int32[N] of the TREE nodes, blocks of R registered by tree_rows
         self.ext_rows = {}    # gate index of a LUT_ENC / SELECT / TREE node -> (spec id, etab) / (tree id, first) / (tree id, row0)
+        self.mv_bases = []    # base vectors int32[N] of the MV / TREE_MV nodes
+        self.mv_specs = []    # [lo spec, hi spec or None, p, q, k, base id, [factor tables int32[k][q][p]]] of the MV / TREE_MV launch groups
+        self.mv_rows = {}     # gate index of an MV / TREE_MV node -> (mv id, table t of that spec)
         self._ids = {}
 
     def inputs(self, count):
@@ -172,6 +179,82 @@ class Circuit:
         self.ext_rows[len(self.gates) - 1] = (ti, int(first))
         return w
 
+    def mv_base(self, tv0):
+        """Register the base vector int32[N] of multi-value rotations (thfhe.lut.mv_base, or the first result of tree_mv_factors / tree_mvk_factors);
+        returns its id.  Equal vectors share one id."""
+        tv0 = np.ascontiguousarray(tv0, np.int32).reshape(-1)
+        key = ("mv_base", tv0.tobytes())
+        if key not in self._ids:
+            self._ids[key] = len(self.mv_bases)
+            self.mv_bases.append(tv0)
+        return self._ids[key]
+
+    def _mv_row(self, op, lo, hi, base, w, operands):
+        """An MV / TREE_MV row on the factor table w int32[k][q][p]: its launch group's spec (one per distinct prologues, shape and base) and the
+        table's index in it; the head wire and its LUT_OUT rows."""
+        k, q, p = w.shape
+        if not 0 <= base < len(self.mv_bases):
+            raise ValueError(f"unknown base vector id {base}")
+        if p < 2 or p > 64 or p & (p - 1) or k * q > 64:
+            raise ValueError("p must be a power of two in 2 .. 64 and the node's rotation has at most 64 outputs")
+        key = ("mv", lo, hi, p, q, k, int(base))
+        if key not in self._ids:
+            self._ids[key] = len(self.mv_specs)
+            self.mv_specs.append([lo, hi, p, q, k, int(base), []])
+        mi = self._ids[key]
+        tabs = self.mv_specs[mi][6]
+        t = next((i for i, x in enumerate(tabs) if np.array_equal(x, w)), len(tabs))
+        if t == len(tabs):
+            tabs.append(w)
+        head = self.gate(op, *(operands + [-1] * (3 - len(operands))))
+        self.mv_rows[len(self.gates) - 1] = (mi, t)
+        return [head] + [self.gate(LUT_OUT, head) for _ in range((k if op == TREE_MV else q) - 1)]
+
+    def mv(self, base, factors, inputs, weights=(1,), bias=0):
+        """An MV node: q functions of the digit x = sum_q weights[q] * inputs[q] + (0, bias) from ONE rotation of the base vector `base` (mv_base),
+        function j through the taps factors[j] (thfhe.lut.mv_factors: int32[q][p]).  Returns the q output wire ids (consecutive: a SELECT can take
+        them as its candidates)."""
+        inputs = list(inputs)
+        if not 1 <= len(inputs) <= 3 or len(weights) != len(inputs):
+            raise ValueError("an MV node takes 1 to 3 inputs and one weight per input")
+        w = np.ascontiguousarray(factors, np.int32)
+        if w.ndim != 2:
+            raise ValueError("factors: expected int32[q][p]")
+        lo = (len(inputs), tuple(_wrap32(v) for v in list(weights) + [0] * (3 - len(weights))), _wrap32(bias), 1)
+        return self._mv_row(MV, lo, None, base, w[None], inputs)
+
+    def tree_mv(self, base, factors, lo_inputs, hi_inputs, lo_weights=None, hi_weights=None, lo_bias=0, hi_bias=0):
+        """A TREE_MV node: k functions f_j(hi, lo) of two encrypted digits in 1 + k rotations (one multi-value rotation of the base vector `base` on
+        the `lo` digit with k p_hi outputs, box packing, k selection rotations on the `hi` digit), one level.  factors: int32[k][p_hi][p_lo]
+        (thfhe.lut.tree_mvk_factors).  lo_inputs and hi_inputs number at most three together.  Returns the k output wire ids (consecutive)."""
+        lo_inputs, hi_inputs = list(lo_inputs), list(hi_inputs)
+        lo_weights = (1,) * len(lo_inputs) if lo_weights is None else tuple(lo_weights)
+        hi_weights = (1,) * len(hi_inputs) if hi_weights is None else tuple(hi_weights)
+        if not lo_inputs or not hi_inputs or len(lo_inputs) + len(hi_inputs) > 3:
+            raise ValueError("a TREE_MV node takes at least one lo and one hi input, at most three together")
+        if len(lo_weights) != len(lo_inputs) or len(hi_weights) != len(hi_inputs):
+            raise ValueError("one weight per input")
+        w = np.ascontiguousarray(factors, np.int32)
+        if w.ndim != 3 or w.shape[1] < 2 or w.shape[1] & (w.shape[1] - 1):
+            raise ValueError("factors: expected int32[k][p_hi][p_lo], p_hi a power of two")
+        lo = (len(lo_inputs), tuple(_wrap32(v) for v in list(lo_weights) + [0] * (3 - len(lo_weights))), _wrap32(lo_bias), 1)
+        hi = (len(hi_inputs), tuple(_wrap32(v) for v in list(hi_weights) + [0] * (3 - len(hi_weights))), _wrap32(hi_bias), 1)
+        return self._mv_row(TREE_MV, lo, hi, base, w, lo_inputs + hi_inputs)
+
+    def has_mv_nodes(self):
+        """Whether the circuit holds an MV or TREE_MV node (it then runs on thfhe_dag_run_mv_batch)."""
+        return bool(self.mv_rows)
+
+    def mv_families(self):
+        """(mvs, mv_tv0, mv_factors) of thfhe_dag_run_mv_batch: (lo, hi, p, q, k, base, factors_off, n_tables) per spec, the base vectors
+        int32[n_bases][N] and the specs' tables laid end to end."""
+        mvs, words, off = [], [], 0
+        for lo, hi, p, q, k, base, tabs in self.mv_specs:
+            mvs.append((lo, hi, p, q, k, base, off, len(tabs)))
+            words += [t.reshape(-1) for t in tabs]
+            off += len(tabs) * k * q * p
+        return mvs, (np.stack(self.mv_bases) if self.mv_bases else None), (np.concatenate(words) if words else None)
+
     def has_luts(self):
         return bool(self.lut_rows)
 
@@ -181,8 +264,8 @@ class Circuit:
 
     def nodes(self):
         """int32[n_gates][6] = (op, in0, in1, in2, spec, lut): the rows of thfhe_dag_run_lut_batch (spec = lut = -1 on gate rows); LUT_ENC, SELECT and
-        TREE rows (thfhe_dag_run_tree_batch) carry (spec, etab), (tree, first), (tree, row0)."""
-        rows = [tuple(g) + (self.lut_rows.get(i) or self.ext_rows.get(i, (-1, -1))) for i, g in enumerate(self.gates)]
+        TREE rows (thfhe_dag_run_tree_batch) carry (spec, etab), (tree, first), (tree, row0); MV and TREE_MV rows (thfhe_dag_run_mv_batch) (mv, t)."""
+        rows = [tuple(g) + (self.lut_rows.get(i) or self.ext_rows.get(i) or self.mv_rows.get(i, (-1, -1))) for i, g in enumerate(self.gates)]
         return np.array(rows, np.int32).reshape(-1, 6)
 
     def n_wires(self):
@@ -218,6 +301,9 @@ class Circuit:
         if self.ext_rows:   # a TREE node: R level-1 rotations + the selection rotation
             extra = sum(self.tree_specs[self.ext_rows[i][0]][2] // self.tree_specs[self.ext_rows[i][0]][0][3] for i, o in enumerate(ops) if o == TREE)
             c.update(rotations=c["rotations"] + extra, luts_enc=ops.count(LUT_ENC), selects=ops.count(SELECT), trees=ops.count(TREE))
+        if self.mv_rows:    # a TREE_MV node: one multi-value rotation + k selection rotations
+            extra = sum(self.mv_specs[self.mv_rows[i][0]][4] for i, o in enumerate(ops) if o == TREE_MV)
+            c.update(rotations=c["rotations"] + extra, mvs=ops.count(MV), tree_mvs=ops.count(TREE_MV))
         return c
 
 
@@ -611,6 +697,18 @@ def tree_mul_digits(cir, a, b, N=1024):
     return cir.tree(lo_rows, [a], [b], 8, theta1=2), cir.tree(hi_rows, [a], [b], 8, theta1=2)
 
 
+def sbox_digits(cir, hi, lo, table, N=1024):
+    """A 64-entry table of 4-bit values (a DES S-box: table[8 hi + lo]) on two p = 8 digit wires, as its four bits LSB-first in the p_out = 2 encoding
+    of thfhe.lut: ONE TREE_MV node with k = 4, p_hi = p_lo = 8 (1 + 4 rotations; bit-valued outputs, the shape DESIGN 4.13's noise table supports on
+    the named parameter sets).  Returns the four bit wires."""
+    from . import lut
+    table = [int(v) for v in table]
+    if len(table) != 64 or any(not 0 <= v < 16 for v in table):
+        raise ValueError("sbox_digits: expected 64 values in 0 .. 15")
+    tv0, w = lut.tree_mvk_factors([lambda h, l, j=j: (table[8 * h + l] >> j) & 1 for j in range(4)], 8, 8, 2, N=N)
+    return cir.tree_mv(cir.mv_base(tv0), w, [lo], [hi])
+
+
 def _tables(ck, cir):
     return np.stack([np.asarray(t, ck._tv_dtype).reshape(ck.params.N) for t in cir.tables])
 
@@ -628,11 +726,24 @@ def _rotate_noiseless(x, tv, theta):
     return out
 
 
+def _mv_test_vector(tv0, taps):
+    """tv0 * F mod (X^N + 1, 2^32) for the factor F = sum_k taps[k] X^(box/2 + k box), box = N / p: the test vector a multi-value output equals a
+    plain rotation of (thfhe_mv_lut_bootstrap)."""
+    tv0 = np.asarray(tv0, np.int64)
+    N, p = tv0.shape[0], len(taps)
+    box = N // p
+    acc = np.zeros(N, np.int64)
+    for k, c in enumerate(taps):
+        e = box // 2 + k * box
+        acc += int(c) * np.concatenate([-tv0[N - e:], tv0[:N - e]])
+    return ((acc + (1 << 31)) % (1 << 32)) - (1 << 31)
+
+
 def _simulate_words(cir, input_words):
     """simulate for circuits with LUT-type nodes: noiseless Torus32 phase words in (thfhe.lut.encode of the digits; +-2^29 for gate bits), the
     noiseless phase word of every wire out (thfhe.lut.decode gives the digits)."""
     from . import lut
-    N = len(cir.tables[0]) if cir.tables else (len(cir.tv1[0]) if cir.tv1 else 1024)
+    N = len(cir.tables[0]) if cir.tables else (len(cir.tv1[0]) if cir.tv1 else (len(cir.mv_bases[0]) if cir.mv_bases else 1024))
     v = np.zeros(cir.n_wires(), np.int64)
     v[:cir.n_inputs] = np.asarray(input_words, np.int64)
     wrap = lambda t: ((int(t) + (1 << 31)) % (1 << 32)) - (1 << 31)
@@ -663,6 +774,17 @@ def _simulate_words(cir, input_words):
             cands = [wrap(t) for r in range(p // lo[3]) for t in _rotate_noiseless(x, np.asarray(cir.tv1[row0 + r]), lo[3])]
             tv = lut.test_vector(lut._to_i32(np.array(cands, np.int64)), p, N=N)
             v[o] = wrap(_rotate_noiseless(lin(hi, ops[lo[0]:lo[0] + hi[0]]), tv, 1)[0])
+        elif op in (MV, TREE_MV):
+            mi, t = cir.mv_rows[gi]
+            lo, hi, p, q, k, base, tabs = cir.mv_specs[mi]
+            ops = (a, b, c)
+            x = lin(lo, ops[:lo[0]])
+            outs = [[wrap(_rotate_noiseless(x, _mv_test_vector(cir.mv_bases[base], tabs[t][j][h]), 1)[0]) for h in range(q)] for j in range(k)]
+            if op == MV:
+                v[o:o + q] = outs[0]
+            else:
+                y = lin(hi, ops[lo[0]:lo[0] + hi[0]])
+                v[o:o + k] = [wrap(_rotate_noiseless(y, lut.test_vector(lut._to_i32(np.array(cands, np.int64)), q, N=N), 1)[0]) for cands in outs]
         elif op == NOT:
             v[o] = wrap(-int(v[a]))
         elif op == COPY:
@@ -678,7 +800,7 @@ def simulate(cir, input_bits):
     integer digits in their torus encoding: int32[n_inputs] noiseless phase words (thfhe.lut.encode(digit, p); +-2^29 for gate bits) -> the
     noiseless phase word int32[n_wires] of every wire, which thfhe.lut.decode turns into digits."""
     from . import ANDNY, ANDYN, NAND, NOR, ORNY, ORYN, XNOR
-    if cir.lut_rows or cir.ext_rows:
+    if cir.lut_rows or cir.ext_rows or cir.mv_rows:
         return _simulate_words(cir, input_bits)
     v = np.zeros(cir.n_wires(), bool)
     v[:cir.n_inputs] = np.asarray(input_bits, bool)
@@ -723,9 +845,11 @@ def simulate_mk(cir, input_bits):
 # ---- evaluator --------------------------------------------------------------------------------------------------------
 def _run_tree_batch(ck, cir, x, sel, pack):
     enc = cir.enc_tables
-    return ck.dag_run_tree_batch(x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None,
-                                 np.stack([e[0] for e in enc]) if enc else None, np.stack([e[1] for e in enc]) if enc else None,
-                                 cir.tree_specs, np.stack(cir.tv1) if cir.tv1 else None, sel, pack)
+    args = (x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None, np.stack([e[0] for e in enc]) if enc else None,
+            np.stack([e[1] for e in enc]) if enc else None, cir.tree_specs, np.stack(cir.tv1) if cir.tv1 else None)
+    if cir.has_mv_nodes():
+        return ck.dag_run_mv_batch(*args, *cir.mv_families(), sel, pack)
+    return ck.dag_run_tree_batch(*args, sel, pack)
 
 
 def evaluate(ck, cir, input_records, stats=None, pack=None):
@@ -734,9 +858,9 @@ def evaluate(ck, cir, input_records, stats=None, pack=None):
     multi-key contexts go level by level through thfhe_mk_gates_mixed (evaluate_levels).  Circuits with LUT nodes run on
     thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch, circuits with encrypted-table, select or tree nodes on thfhe_dag_run_tree_batch
     (pack: the threshold.PolyContext holding the packing key)."""
-    if cir.has_luts() or cir.has_tree_nodes():
+    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes():
         x = np.ascontiguousarray(input_records, np.int32).reshape(1, cir.n_inputs, ck.words)
-        if cir.has_tree_nodes():
+        if cir.has_tree_nodes() or cir.has_mv_nodes():
             out, st = _run_tree_batch(ck, cir, x, None, pack)
         else:
             out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir))
@@ -760,9 +884,9 @@ def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None, pack=None
     x = np.ascontiguousarray(input_records, np.int32)
     Q, n_in, words = x.shape
     assert n_in == cir.n_inputs
-    if cir.has_luts() or cir.has_tree_nodes() or hasattr(ck, "dag_run_batch"):
+    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or hasattr(ck, "dag_run_batch"):
         sel = None if out_wires is None else np.asarray(out_wires, np.int32)
-        if cir.has_tree_nodes():
+        if cir.has_tree_nodes() or cir.has_mv_nodes():
             out, st = _run_tree_batch(ck, cir, x, sel, pack)
         elif cir.has_luts():
             out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir), sel)
@@ -836,11 +960,34 @@ def _levels_ext(ck, cir, level, vals, pack):
     return groups
 
 
+def _levels_mv(ck, cir, level, vals, pack):
+    """The MV and TREE_MV nodes of one level through the public flat calls (mv_lut_bootstrap, tree_lut_bootstrap_mvk), one call per spec; returns
+    the number of calls."""
+    gates, base, by = cir.gates, cir.n_inputs, {}
+    for g in level:
+        if gates[g][0] in (MV, TREE_MV):
+            by.setdefault((gates[g][0], cir.mv_rows[g][0]), []).append(g)
+    for (op, mi), G in sorted(by.items()):
+        lo, hi, p, q, k, b, tabs = cir.mv_specs[mi]
+        out = base + np.array(G)
+        idx = [cir.mv_rows[g][1] for g in G]
+        lo_in = tuple(vals[[gates[g][1 + i] for g in G]] for i in range(lo[0]))
+        if op == MV:
+            r = ck.mv_lut_bootstrap(np.stack([t[0] for t in tabs]), *lo_in, tv0=cir.mv_bases[b], weights=lo[1][:lo[0]], bias=lo[2], table_index=idx)
+        else:
+            hi_in = tuple(vals[[gates[g][1 + lo[0] + i] for g in G]] for i in range(hi[0]))
+            r = ck.tree_lut_bootstrap_mvk(pack, np.stack(tabs), lo_in, hi_in, tv0=cir.mv_bases[b], weights_lo=lo[1][:lo[0]], bias_lo=lo[2],
+                                          weights_hi=hi[1][:hi[0]], bias_hi=hi[2], table_index=idx)
+        for j in range(r.shape[1]):
+            vals[out + j] = r[:, j]
+    return len(by)
+
+
 def evaluate_levels(ck, cir, input_records, stats=None, pack=None):
     """The same schedule driven from the host: one host-buffer call per level (works for single-key and multi-key contexts).  LUT nodes go
     through ck.lut_bootstrap, one call per (theta, spec) of a level: the yardstick of the native LUT-node executor.  LUT_ENC, SELECT and TREE nodes
     go through lut_bootstrap_enc, PackBoxes + lut_bootstrap_enc and tree_lut_bootstrap (pack: the packing context): the yardstick of
-    thfhe_dag_run_tree_batch."""
+    thfhe_dag_run_tree_batch.  MV and TREE_MV nodes go through mv_lut_bootstrap and tree_lut_bootstrap_mvk: the yardstick of thfhe_dag_run_mv_batch."""
     from . import AND3 as _AND3
     words = ck.words
     vals = np.zeros((cir.n_wires(), words), np.int32)
@@ -872,7 +1019,9 @@ def evaluate_levels(ck, cir, input_records, stats=None, pack=None):
                 launches += 1
         if cir.ext_rows:
             launches += _levels_ext(ck, cir, level, vals, pack)
-        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT, LUT_ENC, SELECT, TREE)]
+        if cir.mv_rows:
+            launches += _levels_mv(ck, cir, level, vals, pack)
+        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT, LUT_ENC, SELECT, TREE, MV, TREE_MV)]
         mux = [g for g in level if gates[g][0] == MUX]
         and3 = [g for g in level if gates[g][0] == _AND3]   # 3-gen three-input AND: its own gate class (thfhe_mk_gates)
         if and3:

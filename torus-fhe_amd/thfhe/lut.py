@@ -144,6 +144,17 @@ def tree_mv_factors(f, p_hi, p_lo, p_out, N=1024):
     return mv_base((1 << 32) // (2 * p_out), N), mv_factors(tab, p_lo)
 
 
+def tree_mvk_factors(fs, p_hi, p_lo, p_out=2, N=1024):
+    """(tv0, factors) of thfhe_tree_lut_bootstrap_mvk for the k functions fs[j](hi, lo), taken mod p_out: one base vector and
+    int32[k][p_hi][p_lo], block j = tree_mv_factors(fs[j]).  Output j p_hi + h of the one level-1 rotation is candidate h of function j.  p_out = 2
+    (bit-valued outputs) is what the named parameter sets carry through the two rotations; k p_hi <= 64."""
+    fs = list(fs)
+    if not fs or len(fs) * p_hi > 64:
+        raise ValueError("1 <= k and k * p_hi <= 64 (the outputs of one multi-value rotation)")
+    parts = [tree_mv_factors(f, p_hi, p_lo, p_out, N) for f in fs]
+    return parts[0][0], np.stack([w for _, w in parts])
+
+
 def encrypt_table(rlwe_key, tv, sigma, rng):
     """The client side of an encrypted table (thfhe_lut_bootstrap_enc): a fresh TLWE sample (tv_a, tv_b) of the test vector(s) tv int32[..., N]
     under the bootstrapping ring key: tv_a uniform, tv_b = tv_a (*) z + tv + e, e Gaussian of standard deviation sigma; exact product."""
