@@ -409,6 +409,41 @@ int thfhe_tree_lut_bootstrap_mvk(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const
                                  const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
                                  const int32_t *hi1, const int32_t *hi2, int32_t *out /*[count][k][n+1]*/, size_t count);
 
+/* ---- leveled table lookup on TGSW-encrypted address bits (single key, N = 1024): the external product TGSW (.) TLWE on user data.
+ * With the d address bits of a sample encrypted as TGSW samples under the ring key, a 2^d-entry table costs d CMuxes instead of a blind rotation.
+ *
+ * thfhe_tgsw_set_create: tgsw: HOST int32[count][d][2l][2][N], the layout of the bootstrapping key (thfhe.keygen.SecretKeySet.tgsw_encrypt): row
+ *   (j, level) of a sample is a TLWE encryption of zero plus bit * 2^(32 - (level+1) Bgbit) on coefficient 0 of polynomial j.  The samples are
+ *   uploaded in slices, transformed on the device and kept as spectra, count d 2l 32 KiB; that size is checked against the free device memory
+ *   before anything is allocated (THFHE_E_NOMEM), and a failed create leaves nothing behind.  1 <= d <= 16, 1 <= count <= 2^24.  The set belongs to
+ *   ctx: destroy it before the context.  thfhe_tgsw_set_destroy(NULL) is a no-op.
+ *
+ * thfhe_lhe_cmux: out[s] = d0[s] + C_(s,bit) (.) (d1[s] - d0[s]) for the samples s = 0 .. count-1 of the set: d1 where the bit is 1, d0 where it is
+ *   0.  d1_a, d1_b, d0_a, d0_b, out_a, out_b: HOST int32[count][N] (masks, bodies of TLWE samples under the ring key, phase b - a (*) z).  Exact
+ *   integers: every word equals the reference's decomposition and product.
+ *
+ * thfhe_lhe_lookup(_wo_keyswitch): samples first .. first+count-1 of the set; d_tree + d_rot must equal the set's d, 0 <= d_tree <= 6,
+ *   0 <= d_rot <= 10, box = N >> d_rot, theta in {1, 2, 4} and theta <= box.  Address bits 0 .. d_rot-1 are the low bits, bits d_rot .. d-1 pick the
+ *   polynomial.  tab_b: HOST int32[n_tables][2^d_tree][N]; tab_a: the masks, or NULL for a public table (trivial samples (0, tab_b)); n_tables
+ *   2^d_tree <= 262144.  table_index: HOST int32[count] or NULL (table 0).  Entry e of function j of a table sits at coefficient e * box + j of
+ *   polynomial e >> d_rot (thfhe.lut.lhe_table).  Per sample: a CMux tree over the 2^d_tree polynomials, level t pairing neighbours on bit d_rot + t;
+ *   then for i = 0 .. d_rot-1  ACC += C_(s,i) (.) (X^(2N - box 2^i) ACC - ACC); then the extraction of coefficients 0 .. theta-1.
+ *   out: HOST int32[count][theta][n+1] (key-switched) or int32[count][theta][N+1] (_wo_keyswitch).  The batch runs in slices of at most
+ *   max_candidates / 2^(d_tree-1) samples (thfhe_set_tree_slice; the tree workspace is 2^(d_tree-1) TLWE samples per sample) and 65 535 samples.
+ *
+ * All checks run on the host before the context is looked at (THFHE_E_INVALID): null pointers, the ranges above, a table_index entry out of range,
+ * samples outside the set; then a NULL context or a set of another context.  count 0 returns THFHE_OK once those have passed. */
+typedef struct thfhe_tgsw_set thfhe_tgsw_set;
+int thfhe_tgsw_set_create(thfhe_ctx *ctx, const int32_t *tgsw /*[count][d][2l][2][N]*/, size_t count, int d, thfhe_tgsw_set **out);
+void thfhe_tgsw_set_destroy(thfhe_tgsw_set *set);
+int thfhe_lhe_cmux(thfhe_ctx *ctx, const thfhe_tgsw_set *set, int bit, const int32_t *d1_a, const int32_t *d1_b, const int32_t *d0_a,
+                   const int32_t *d0_b /*[count][N]*/, int32_t *out_a, int32_t *out_b, size_t count);
+int thfhe_lhe_lookup(thfhe_ctx *ctx, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta, const int32_t *tab_a,
+                     const int32_t *tab_b /*[n_tables][2^d_tree][N]*/, int n_tables, const int32_t *table_index, int32_t *out);
+int thfhe_lhe_lookup_wo_keyswitch(thfhe_ctx *ctx, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta,
+                                  const int32_t *tab_a, const int32_t *tab_b /*[n_tables][2^d_tree][N]*/, int n_tables, const int32_t *table_index,
+                                  int32_t *out_N1);
+
 /* ---- encrypted-table, select and tree nodes in the gate-DAG executor (single key): thfhe_dag_run_lut_batch with three more node
  * kinds, so that a circuit needing a private table, an oblivious pick or a 6-bit -> 3-bit function does not leave the device-resident wire table.
  * nodes: HOST int32[n_nodes][6] = (opcode, in0, in1, in2, x, y); row g defines wire n_inputs + g.  Gate rows, THFHE_LUT and THFHE_LUT_OUT rows mean

@@ -506,6 +506,33 @@ THFHE_FN void rotated_digits_z(int lane, const int32_t *p, int a2n, int level, i
         z[m] = cplx{d[0], d[1]};
     }
 }
+// The digit extraction of rotated_digits_z on a plain difference (leveled CMux d0 + C (.) (d1 - d0)):
+// z[m] = (digit_p of (p1 - p0)[lane + 64 m], digit_p of ...[lane + 64 m + 512]), level p = 1..l.  No rotation, so no index or sign work: the
+// 32 reads first, then one subtraction, one addition of offset + half_p, one signed bit-field extract and one conversion per coefficient.
+THFHE_FN void diff_digits_z(int lane, const int32_t *p1, const int32_t *p0, int level, int l, int Bgbit, cplx (&z)[8]) {
+    const int shift = 32 - level * Bgbit;
+    const uint32_t off = decomp_offset32(l, Bgbit) + ((1u << (Bgbit - 1)) << shift);
+    uint32_t r[8][2], s[8][2];
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const int c = lane + 64 * m + 512 * q;
+            r[m][q] = (uint32_t)p1[c];
+            s[m][q] = (uint32_t)p0[c];
+        }
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+        double d[2];
+#pragma unroll
+        for (int q = 0; q < 2; q++) d[q] = (double)sbfe32(r[m][q] + (off - s[m][q]), shift, Bgbit);
+        z[m] = cplx{d[0], d[1]};
+    }
+}
 // Two-step form: index, sign and subtraction are done once per coefficient and polynomial, a level then costs one signed bit-field
 // extract and one conversion:   t = ((X^a acc - acc) + offset) ^ offset,  offset = sum_p (Bg/2) << (32 - p Bgbit).
 // XOR with Bg/2 inside a field is "+ Bg/2 mod Bg" without carries into the neighbouring fields, so the two's-complement reading of

@@ -1,0 +1,367 @@
+// thfhe_lhe.h -- leveled table lookup on TGSW-encrypted address bits (single key, N = 1024, k = 1): kernels and host side of
+// thfhe_tgsw_set_create, thfhe_lhe_cmux and thfhe_lhe_lookup(_wo_keyswitch).  Included by thfhe_sk.hip INSIDE its second anonymous namespace, after
+// thfhe_ctx, the cooperative blind-rotate kernel (whose barriers and phases it reuses) and enqueue_keyswitch.
+//
+// Data flow.  The blind-rotate kernels share ONE key stream among all jobs and give every job its own rotation amounts.  Here every job has its OWN
+// TGSW spectra (the address bits of its sample, 2l x 32 KiB per bit) and the rotation amounts are public: X^(2N - box 2^i) for address bit i.  Nothing
+// is shared between workgroups, so both kernels are the cooperative kernel's shape -- one job per 512-thread workgroup, accumulator and the 2l digit
+// spectra in LDS, the F / M / I phases of one CMux with the spectra of the step in registers -- and they are bound by streaming those spectra once.
+#ifndef THFHE_LHE_H
+#define THFHE_LHE_H
+
+constexpr int kLheMaxBits = 16, kLheMaxTree = 6, kLheMaxRot = 10;
+
+// One CMux ACC += C (.) D in the cooperative kernel's F / M / I phases (sk_blind_rotate_coop_kernel), C's chunks of this wave's role in B.
+//   ROT:  D = X^a2n ACC - ACC (rotated_digits_z);  else D = d1 - ACC, d1 in sD1 (diff_digits_z).
+//   PUB:  the mask of D is known to be zero (first tree level of a public table): its l digit polynomials are zero, so their transforms and the
+//         multiplies of waves 0 .. 3 (rows 0 .. l-1) are not issued.
+//   NEXT: `next` holds the spectra of the CMux that follows, requested where the cooperative kernel requests them (idle waves after the hand-off,
+//         transforming waves between the stages of the inverse); else nothing follows and B is left alone.  Three rows travel that way; at
+//         l = 4 the fourth would not fit the 256 registers next to the transform (the cooperative kernel spills there), so it is requested from
+//         `cur`, this step's own spectra, on entry and lands under the F phase.
+// Ends with the accumulator updated and a workgroup barrier.
+template <int L, bool ROT, bool PUB, bool NEXT>
+__device__ __forceinline__ void lhe_cmux_step(int lane, int wave, int32_t *sAcc, const int32_t *sD1, cplx (*sSpec)[512], cplx (*sX)[kXbufSlots],
+                                              cplx (&B)[L][8], const cplx *cur, const cplx *next, int a2n, int Bgbit, const LaneRoots &roots, const W64 &w64) {
+    constexpr int ROWS = 2 * L;
+    const int c = (wave >> 1) & 1, h = wave & 1, half = wave >> 2, r0 = half * L;  // role in M: rows r0 .. r0+L-1 of (column c, limb h)
+    unsigned int *ap = reinterpret_cast<unsigned int *>(sAcc) + c * 1024;
+    cplx *xb = sX[wave];
+    constexpr int PF = L < 3 ? L : 3;   // rows requested a step ahead
+    if constexpr (NEXT && L > PF) load8(lane, B[L - 1], cur + bk_spec_index(0, r0 + L - 1, c, h, ROWS));
+    // ---- F ----
+    if (wave < ROWS && !(PUB && wave < L)) {
+        cplx z[8];
+        if constexpr (ROT) rotated_digits_z(lane, sAcc + (wave / L) * 1024, a2n, (wave % L) + 1, L, Bgbit, z);
+        else diff_digits_z(lane, sD1 + (wave / L) * 1024, sAcc + (wave / L) * 1024, (wave % L) + 1, L, Bgbit, z);
+        wave_fft_fwd_q(lane, z, xb, roots, w64);
+#pragma unroll
+        for (int m = 0; m < 8; m++) sSpec[wave][m * 64 + lane] = z[m];
+    }
+    wg_barrier();  // spectra published; every read of the accumulator is done
+    // ---- M ----
+    cplx S[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) S[m] = cplx{0.0, 0.0};
+    if (!(PUB && half == 0)) {
+#pragma unroll
+        for (int r = 0; r < L; r++) {
+            cplx z[8];
+#pragma unroll
+            for (int m = 0; m < 8; m++) z[m] = sSpec[r0 + r][m * 64 + lane];
+            mac8r(S, z, B[r]);
+            pin();   // one row's spectrum in registers at a time
+        }
+    }
+    if (half == 1) {
+#pragma unroll
+        for (int m = 0; m < 8; m++) xb[m * 64 + lane] = S[m];   // hand-off to wave - 4
+        pin();
+        wg_barrier();
+        if constexpr (NEXT) {
+#pragma unroll
+            for (int r = 0; r < PF; r++) {
+                const cplx *src = next + bk_spec_index(0, r0 + r, c, h, ROWS);
+#pragma unroll
+                for (int m = 0; m < 8; m++) {
+                    B[r][m] = src[m * 64 + lane];
+                    pin();
+                    __builtin_amdgcn_s_sleep(1);   // paced: these waves have the whole inverse phase
+                }
+            }
+        }
+    } else {
+        if constexpr (NEXT) load8(lane, B[0], next + bk_spec_index(0, r0, c, h, ROWS));
+        pin();
+        wg_barrier();
+        // ---- I ----
+        const cplx *px = sX[wave + 4];
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            const cplx v = px[m * 64 + lane];
+            S[m].re += v.re;
+            S[m].im += v.im;
+        }
+        wave_sync();
+        invr_seg1(lane, S, xb, w64);
+        pin();
+        if constexpr (NEXT && L > 1) load8(lane, B[L > 1 ? 1 : 0], next + bk_spec_index(0, r0 + 1, c, h, ROWS));
+        pin();
+        wave_sync();
+        inv_seg2_ld(lane, S, xb);
+        dft8<-1>(S);
+        pin();
+        if constexpr (NEXT && L > 2) load8(lane, B[L > 2 ? 2 : 0], next + bk_spec_index(0, r0 + 2, c, h, ROWS));
+        pin();
+        wave_transpose_hi3(S);
+        invq_seg3(S, roots);
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            const int q = lane + 64 * m;
+            atomicAdd(ap + q, round_lo32(S[m].re) << (16 * h));
+            atomicAdd(ap + q + 512, round_lo32(S[m].im) << (16 * h));
+        }
+    }
+    wg_barrier();  // accumulator updated before anybody reads it again
+}
+
+// the chunks of one TGSW sample (at `key`) that this wave multiplies with
+template <int L, bool PUB>
+__device__ __forceinline__ void lhe_load_spectra(int lane, int wave, cplx (&B)[L][8], const cplx *key) {
+    const int c = (wave >> 1) & 1, h = wave & 1, half = wave >> 2;
+    if (PUB && half == 0) return;
+#pragma unroll
+    for (int r = 0; r < L; r++) load8(lane, B[r], key + bk_spec_index(0, half * L + r, c, h, 2 * L));
+}
+
+// arguments of sk_lhe_rotate_kernel: job s starts from the TLWE sample (src_a, src_b) + index(s) * src_stride words, index(s) = src_idx[s] or s
+// (src_a null: the trivial sample (0, src_b)), runs ACC += C_(s,i) (.) (X^(2N - box 2^i) ACC - ACC) for i = 0 .. d_rot-1 and extracts theta records
+struct LheRotArgs {
+    const cplx *spec;        // spectra of the set, at the first sample of the launch: [sample][d][2l][2][2][512]
+    const cplx *tw;
+    const int32_t *src_a, *src_b;
+    const int32_t *src_idx;  // [jobs] or null
+    size_t src_stride;       // words between the samples of consecutive indices (0: every job starts from index 0)
+    int32_t *out;            // [jobs][theta][N+1]
+    int d, d_rot, box, theta, Bgbit;
+};
+
+template <int L>
+__global__ __launch_bounds__(512, 2) void sk_lhe_rotate_kernel(LheRotArgs a) {
+    constexpr int ROWS = 2 * L;
+    __shared__ __attribute__((aligned(4096))) int32_t sAcc[2048];
+    __shared__ cplx sSpec[ROWS][512];
+    __shared__ cplx sX[8][kXbufSlots];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
+    const LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
+    const size_t job = blockIdx.x;
+    const size_t bit_stride = (size_t)ROWS * 2048;            // complex slots of one TGSW sample
+    const cplx *key = a.spec + job * a.d * bit_stride;        // the job's own address bits
+    if (wave == 0) {
+        const size_t t = (a.src_idx ? (size_t)a.src_idx[job] : job) * a.src_stride;
+        if (a.src_a) acc_init_tlwe16(lane, sAcc, sAcc + 1024, 0, a.src_a + t, a.src_b + t);
+        else acc_init_tv16(lane, sAcc, sAcc + 1024, 0, a.src_b + t);
+    }
+    cplx B[L][8];
+    if (a.d_rot > 0) lhe_load_spectra<L, false>(lane, wave, B, key);   // (l = 4: the step requests its fourth row again, a hit)
+    wg_barrier();
+    for (int i = 0; i < a.d_rot; i++) {   // public, wave-uniform steps: no step is skipped
+        const int a2n = 2048 - (a.box << i);
+        const int inl = i + 1 < a.d_rot ? i + 1 : i;   // the last step re-requests its own chunks: unconditional loads keep B one set of registers
+        lhe_cmux_step<L, true, false, true>(lane, wave, sAcc, nullptr, sSpec, sX, B, key + i * bit_stride, key + inl * bit_stride, a2n, a.Bgbit, roots, w64);
+    }
+    if (wave < a.theta) extract_at16(lane, sAcc, sAcc + 1024, wave, a.out + (job * a.theta + wave) * 1025);   // one wave per output
+}
+
+// arguments of sk_lhe_cmux_kernel, grid (pairs, samples): out(s, p) = d0(s, p) + C_(s,bit) (.) (d1(s, p) - d0(s, p)).  Word offsets: inputs at
+// index(s) * in_sample + p * in_pair, index(s) = in_idx[s] or s; output at s * out_sample + p * out_pair.  PUB: the masks are not read (zero).
+struct LheCmuxArgs {
+    const cplx *spec;   // spectra of the set, at the first sample of the launch
+    const cplx *tw;
+    const int32_t *d0_a, *d0_b, *d1_a, *d1_b;
+    int32_t *out_a, *out_b;
+    const int32_t *in_idx;   // [samples] or null
+    size_t in_sample, in_pair, out_sample, out_pair;
+    int d, bit, Bgbit;
+};
+
+template <int L, bool PUB>
+__global__ __launch_bounds__(512, 2) void sk_lhe_cmux_kernel(LheCmuxArgs a) {
+    constexpr int ROWS = 2 * L;
+    __shared__ __attribute__((aligned(4096))) int32_t sAcc[2048];
+    __shared__ int32_t sD1[2048];
+    __shared__ cplx sSpec[ROWS][512];
+    __shared__ cplx sX[8][kXbufSlots];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
+    const LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
+    const size_t s = blockIdx.y, pair = blockIdx.x;
+    const size_t in = (a.in_idx ? (size_t)a.in_idx[s] : s) * a.in_sample + pair * a.in_pair;
+    cplx B[L][8];
+    lhe_load_spectra<L, PUB>(lane, wave, B, a.spec + (s * a.d + a.bit) * ((size_t)ROWS * 2048));
+    for (int q = threadIdx.x; q < 1024; q += 512) {
+        sAcc[q] = PUB ? 0 : a.d0_a[in + q];
+        sD1[q] = PUB ? 0 : a.d1_a[in + q];
+        sAcc[1024 + q] = a.d0_b[in + q];
+        sD1[1024 + q] = a.d1_b[in + q];
+    }
+    wg_barrier();
+    lhe_cmux_step<L, false, PUB, false>(lane, wave, sAcc, sD1, sSpec, sX, B, nullptr, nullptr, 0, a.Bgbit, roots, w64);
+    const size_t o = s * a.out_sample + pair * a.out_pair;
+    for (int q = threadIdx.x; q < 1024; q += 512) {
+        a.out_a[o + q] = sAcc[q];
+        a.out_b[o + q] = sAcc[1024 + q];
+    }
+}
+
+template <int L>
+void launch_lhe_cmux_l(const LheCmuxArgs &a, size_t pairs, size_t samples, bool pub, hipStream_t s) {
+    const dim3 grid((unsigned)pairs, (unsigned)samples);
+    if (pub) hipLaunchKernelGGL((sk_lhe_cmux_kernel<L, true>), grid, dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((sk_lhe_cmux_kernel<L, false>), grid, dim3(512), 0, s, a);
+}
+int launch_lhe_cmux(thfhe_ctx *c, const LheCmuxArgs &a, size_t pairs, size_t samples, bool pub) {
+    switch (c->p.l) {
+    case 1: launch_lhe_cmux_l<1>(a, pairs, samples, pub, c->stream); break;
+    case 2: launch_lhe_cmux_l<2>(a, pairs, samples, pub, c->stream); break;
+    case 3: launch_lhe_cmux_l<3>(a, pairs, samples, pub, c->stream); break;
+    case 4: launch_lhe_cmux_l<4>(a, pairs, samples, pub, c->stream); break;
+    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
+    }
+    THFHE_HIP(hipGetLastError());
+    return THFHE_OK;
+}
+int launch_lhe_rotate(thfhe_ctx *c, const LheRotArgs &a, size_t jobs) {
+    const dim3 grid((unsigned)jobs), block(512);
+    switch (c->p.l) {
+    case 1: hipLaunchKernelGGL(sk_lhe_rotate_kernel<1>, grid, block, 0, c->stream, a); break;
+    case 2: hipLaunchKernelGGL(sk_lhe_rotate_kernel<2>, grid, block, 0, c->stream, a); break;
+    case 3: hipLaunchKernelGGL(sk_lhe_rotate_kernel<3>, grid, block, 0, c->stream, a); break;
+    case 4: hipLaunchKernelGGL(sk_lhe_rotate_kernel<4>, grid, block, 0, c->stream, a); break;
+    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
+    }
+    THFHE_HIP(hipGetLastError());
+    return THFHE_OK;
+}
+
+// complex slots of the spectra of one sample of a set (d bits of 2l rows x 2 columns x 2 limbs x 512)
+inline size_t lhe_sample_slots(const thfhe_ctx *c, int d) { return (size_t)d * 2 * c->p.l * 2048; }
+
+// thfhe_tgsw_set_create after its host checks: the size check, the allocation and the sliced upload + transform
+int tgsw_set_fill(thfhe_ctx *c, thfhe_tgsw_set *set, const int32_t *tgsw) {
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const size_t polys_per_bit = (size_t)2 * c->p.l * 2, bits = set->count * set->d;
+    const size_t bytes = bits * polys_per_bit * 1024 * sizeof(cplx);   // count d 2l 32 KiB
+    const size_t slice_bits = std::min<size_t>(bits, std::max<size_t>(1, ((size_t)64 << 20) / (polys_per_bit * 4096)));   // 64 MiB of coefficients at a time
+    const size_t stage_bytes = slice_bits * polys_per_bit * 4096;
+    size_t free_b = 0, total_b = 0;
+    THFHE_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (bytes + stage_bytes > free_b) return thfhe_fail(THFHE_E_NOMEM, "tgsw set: count d 2l 32 KiB of spectra exceed the free device memory");
+    DevBuf coeff;   // upload staging, freed on return
+    THFHE_TRY(coeff.grow(stage_bytes));
+    THFHE_TRY(set->spec.grow(bytes));
+    for (size_t b0 = 0; b0 < bits; b0 += slice_bits) {
+        const size_t nb = std::min(slice_bits, bits - b0), np = nb * polys_per_bit;
+        THFHE_HIP(hipMemcpyAsync(coeff.as<int32_t>(), tgsw + b0 * polys_per_bit * 1024, np * 4096, hipMemcpyHostToDevice, c->stream));
+        THFHE_TRY((launch_torus_transform<1024, 32>(c->stream, coeff.as<int32_t>(), (long)np, c->d_tw.as<cplx>(), set->spec.as<cplx>() + b0 * polys_per_bit * 1024)));
+        THFHE_HIP(hipStreamSynchronize(c->stream));   // the staging buffer is reused by the next slice
+    }
+    return THFHE_OK;
+}
+
+// host checks shared by thfhe_lhe_cmux and thfhe_lhe_lookup once the set is known to be non-null
+int lhe_validate_range(const thfhe_tgsw_set *set, size_t first, size_t count) {
+    if (first > set->count || count > set->count - first) return thfhe_fail(THFHE_E_INVALID, "lhe: samples first .. first+count-1 are not all in the set");
+    return THFHE_OK;
+}
+
+int lhe_cmux(thfhe_ctx *c, const thfhe_tgsw_set *set, int bit, const int32_t *d1_a, const int32_t *d1_b, const int32_t *d0_a, const int32_t *d0_b,
+             int32_t *out_a, int32_t *out_b, size_t count) {
+    if (!d1_a || !d1_b || !d0_a || !d0_b || !out_a || !out_b) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (bit < 0 || bit >= kLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "lhe_cmux: bit must be 0 .. d-1");
+    if (!set) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
+    if (bit >= set->d) return thfhe_fail(THFHE_E_INVALID, "lhe_cmux: bit must be 0 .. d-1");
+    THFHE_TRY(lhe_validate_range(set, 0, count));
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (c != set->ctx) return thfhe_fail(THFHE_E_INVALID, "lhe: the set belongs to another context");
+    if (count == 0) return THFHE_OK;
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const size_t S_max = std::min<size_t>(count, 32768), bytes = S_max * 4096;
+    for (DevBuf &b : c->d_lhe_in) THFHE_TRY(b.grow(bytes));
+    THFHE_TRY(c->d_lhe_a.grow(bytes));
+    THFHE_TRY(c->d_lhe_b.grow(bytes));
+    const int32_t *src[4] = {d0_a, d0_b, d1_a, d1_b};
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0);
+        for (int q = 0; q < 4; q++) THFHE_HIP(hipMemcpyAsync(c->d_lhe_in[q].as<int32_t>(), src[q] + s0 * 1024, S * 4096, hipMemcpyHostToDevice, c->stream));
+        LheCmuxArgs a{set->spec.as<cplx>() + s0 * lhe_sample_slots(c, set->d), c->d_tw.as<cplx>(), c->d_lhe_in[0].as<int32_t>(), c->d_lhe_in[1].as<int32_t>(),
+                      c->d_lhe_in[2].as<int32_t>(), c->d_lhe_in[3].as<int32_t>(), c->d_lhe_a.as<int32_t>(), c->d_lhe_b.as<int32_t>(), nullptr,
+                      1024, 0, 1024, 0, set->d, bit, c->p.Bgbit};
+        THFHE_TRY(launch_lhe_cmux(c, a, 1, S, false));
+        THFHE_HIP(hipMemcpyAsync(out_a + s0 * 1024, c->d_lhe_a.as<int32_t>(), S * 4096, hipMemcpyDeviceToHost, c->stream));
+        THFHE_HIP(hipMemcpyAsync(out_b + s0 * 1024, c->d_lhe_b.as<int32_t>(), S * 4096, hipMemcpyDeviceToHost, c->stream));
+    }
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    return THFHE_OK;
+}
+
+// thfhe_lhe_lookup (keyswitch) / thfhe_lhe_lookup_wo_keyswitch: out = count x theta records of n+1 (resp. N+1) words, in slices of at most
+// tree_slice / 2^(d_tree-1) samples (the tree workspace: 2^(d_tree-1) TLWE samples of 8 KiB per sample)
+int lhe_lookup(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta, const int32_t *tab_a,
+               const int32_t *tab_b, int n_tables, const int32_t *table_index, int32_t *out, bool keyswitch) {
+    // host checks, before the context is looked at
+    if (!tab_b || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (d_tree < 0 || d_tree > kLheMaxTree) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: d_tree must be 0 .. 6");
+    if (d_rot < 0 || d_rot > kLheMaxRot) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: d_rot must be 0 .. 10");
+    if (theta != 1 && theta != 2 && theta != 4) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: theta must be 1, 2 or 4");
+    if (theta > (1024 >> d_rot)) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: theta must not exceed box = N >> d_rot");
+    if (n_tables < 1 || ((long)n_tables << d_tree) > kMaxEncLuts) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: n_tables 2^d_tree must be 1 .. 262144");
+    THFHE_TRY(tree_validate_index(table_index, n_tables, count));
+    if (!set) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
+    if (d_tree + d_rot != set->d) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: d_tree + d_rot must equal the set's d");
+    THFHE_TRY(lhe_validate_range(set, first, count));
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (c != set->ctx) return thfhe_fail(THFHE_E_INVALID, "lhe: the set belongs to another context");
+    if (count == 0) return THFHE_OK;
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const size_t leaves = (size_t)1 << d_tree, ws = d_tree ? leaves / 2 : 0;   // TLWE samples of tree workspace per sample
+    const size_t S_max = std::min({count, (size_t)65535, std::max<size_t>(1, c->tree_slice / std::max<size_t>(ws, 1))});
+    const size_t words = c->p.n + 1, rec = keyswitch ? words : 1025, tab_bytes = (size_t)n_tables * leaves * 4096;
+    int rc = c->d_tv.grow(tab_bytes);
+    if (!rc && tab_a) rc = c->d_tva.grow(tab_bytes);
+    if (!rc && ws) rc = c->d_lhe_a.grow(S_max * ws * 4096);
+    if (!rc && ws) rc = c->d_lhe_b.grow(S_max * ws * 4096);
+    if (!rc) rc = c->d_u.grow(S_max * theta * 1025 * sizeof(int32_t));
+    if (!rc && keyswitch) rc = c->stage.grow(S_max * theta * words);
+    if (!rc && table_index) rc = c->d_lut_idx.grow(S_max * sizeof(int32_t));
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tab_b, tab_bytes, hipMemcpyHostToDevice, st));
+    if (tab_a) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int32_t>(), tab_a, tab_bytes, hipMemcpyHostToDevice, st));
+    const int32_t *const t_a = tab_a ? c->d_tva.as<int32_t>() : nullptr, *const t_b = c->d_tv.as<int32_t>();
+    const int32_t *const idx = table_index ? c->d_lut_idx.as<int32_t>() : nullptr;
+    int32_t *const w_a = c->d_lhe_a.as<int32_t>(), *const w_b = c->d_lhe_b.as<int32_t>();
+    int32_t *const res = keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>();
+    const size_t tab_stride = table_index ? leaves * 1024 : 0;   // without an index every sample reads table 0
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0);
+        const cplx *spec = set->spec.as<cplx>() + (first + s0) * lhe_sample_slots(c, set->d);
+        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[0], st));
+        // the tree: level t pairs neighbours on bit d_rot + t; level 0 reads the table, the later levels run in place on the workspace -- the result
+        // of pair p of level t lies at slot p 2^t of the sample, the slot of its own d0, which no other workgroup of the launch touches
+        for (int t = 0; t < d_tree; t++) {
+            LheCmuxArgs a{spec, c->d_tw.as<cplx>(), nullptr, nullptr, nullptr, nullptr, w_a, w_b, nullptr, 0, 0, ws * 1024, 0, set->d, d_rot + t, c->p.Bgbit};
+            if (t == 0) {
+                a.d0_a = t_a, a.d0_b = t_b, a.d1_a = t_a ? t_a + 1024 : nullptr, a.d1_b = t_b + 1024;
+                a.in_idx = idx, a.in_sample = tab_stride, a.in_pair = 2048, a.out_pair = 1024;
+            } else {
+                const size_t step = (size_t)1024 << t;   // words between the d0 slots of neighbouring pairs
+                a.d0_a = w_a, a.d0_b = w_b, a.d1_a = w_a + step / 2, a.d1_b = w_b + step / 2;
+                a.in_sample = ws * 1024, a.in_pair = step, a.out_pair = step;
+            }
+            THFHE_TRY(launch_lhe_cmux(c, a, leaves >> (t + 1), S, t == 0 && !tab_a));
+        }
+        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[1], st));
+        LheRotArgs r{spec, c->d_tw.as<cplx>(), d_tree ? w_a : t_a, d_tree ? w_b : t_b, d_tree ? nullptr : idx, d_tree ? ws * 1024 : (table_index ? 1024 : 0),
+                     c->d_u.as<int32_t>(), set->d, d_rot, 1024 >> d_rot, theta, c->p.Bgbit};
+        THFHE_TRY(launch_lhe_rotate(c, r, S));
+        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[2], st));
+        if (keyswitch) THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), S * theta, 1, false));
+        if (c->profiling && s0 == 0) {
+            THFHE_HIP(hipEventRecord(c->ev[3], st));
+            c->ev_valid = true;
+        }
+        THFHE_HIP(hipMemcpyAsync(out + s0 * theta * rec, res, S * theta * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
+}
+
+#endif  // THFHE_LHE_H

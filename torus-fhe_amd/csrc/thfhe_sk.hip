@@ -509,12 +509,23 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     DevBuf d_dag_enc_a, d_dag_enc_b, d_dag_tv1;
     // multi-value nodes of the gate DAG (thfhe_dag_run_mv_batch): the run's base vectors and the factor array of all its specs
     DevBuf d_dag_mv_tv0, d_dag_mv_w;
+    // leveled lookup (thfhe_lhe_cmux, thfhe_lhe_lookup): the CMux tree's workspace (masks, bodies) and the flat CMux's four operands
+    DevBuf d_lhe_a, d_lhe_b, d_lhe_in[4];
     size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate); also the output records (samples x q) per slice of thfhe_mv_lut_bootstrap
     // staging for the host-buffer API
     Stage stage;
     // gate-DAG executor: wire table and index tables (grow-only, reused by every thfhe_dag_run on this context)
     DagBuffers dag;
     size_t dag_slice = 28672;  // gates per launch of a DAG level: 14 x 2048 (a MUX slice is 57 344 rotations); it sizes the staging arrays, not the prologue's grid: the runtime runs grid.y > 65 535 (66 636 rotations in one call, tests/test_gpu_large_batch.py)
+};
+
+// Device-resident TGSW samples of thfhe_tgsw_set_create: the spectra of count x d address bits, laid out like the bootstrapping key's with
+// (sample d + bit) in the place of the key index.  Belongs to the context that made it and is destroyed before it.
+struct THFHE_INTERNAL thfhe_tgsw_set {
+    thfhe_ctx *ctx = nullptr;
+    DevBuf spec;
+    size_t count = 0;
+    int d = 0;
 };
 
 namespace {
@@ -1063,6 +1074,8 @@ int sk_dag_run_ext_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs
     return sk_dag_run_luts(c, packs ? pc : nullptr, plan, T, inputs, n_inputs, n_nodes, instances, out_wires, n_out, outputs);
 }
 
+#include "thfhe_lhe.h"
+
 }  // namespace
 
 extern "C" {
@@ -1341,6 +1354,49 @@ int thfhe_keyswitch(thfhe_ctx *c, const int32_t *in_N1, int32_t *out, size_t cou
     THFHE_HIP(hipMemcpyAsync(out, c->stage.out_ptr(), count * (c->p.n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
+}
+
+int thfhe_tgsw_set_create(thfhe_ctx *c, const int32_t *tgsw, size_t count, int d, thfhe_tgsw_set **out) {
+    if (!tgsw || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    *out = nullptr;
+    if (d < 1 || d > kLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "tgsw set: d must be 1 .. 16");
+    if (count < 1 || count > ((size_t)1 << 24)) return thfhe_fail(THFHE_E_INVALID, "tgsw set: count must be 1 .. 2^24");
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    std::unique_ptr<thfhe_tgsw_set> set(new (std::nothrow) thfhe_tgsw_set);
+    if (!set) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
+    set->ctx = c, set->count = count, set->d = d;
+    const int rc = tgsw_set_fill(c, set.get(), tgsw);
+    if (rc) {   // nothing is left behind: the spectra are freed on the context's device
+        (void)hipSetDevice(c->device);
+        return rc;
+    }
+    *out = set.release();
+    return THFHE_OK;
+}
+
+void thfhe_tgsw_set_destroy(thfhe_tgsw_set *set) {
+    if (!set) return;
+    {
+        std::lock_guard<std::mutex> g(set->ctx->mu);   // a call still running on another thread finishes first
+        (void)hipSetDevice(set->ctx->device);
+        (void)hipStreamSynchronize(set->ctx->stream);
+    }
+    delete set;
+}
+
+int thfhe_lhe_cmux(thfhe_ctx *c, const thfhe_tgsw_set *set, int bit, const int32_t *d1_a, const int32_t *d1_b, const int32_t *d0_a, const int32_t *d0_b,
+                   int32_t *out_a, int32_t *out_b, size_t count) {
+    return lhe_cmux(c, set, bit, d1_a, d1_b, d0_a, d0_b, out_a, out_b, count);
+}
+
+int thfhe_lhe_lookup(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta, const int32_t *tab_a,
+                     const int32_t *tab_b, int n_tables, const int32_t *table_index, int32_t *out) {
+    return lhe_lookup(c, set, first, count, d_tree, d_rot, theta, tab_a, tab_b, n_tables, table_index, out, true);
+}
+
+int thfhe_lhe_lookup_wo_keyswitch(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta,
+                                  const int32_t *tab_a, const int32_t *tab_b, int n_tables, const int32_t *table_index, int32_t *out_N1) {
+    return lhe_lookup(c, set, first, count, d_tree, d_rot, theta, tab_a, tab_b, n_tables, table_index, out_N1, false);
 }
 
 }  // extern "C"

@@ -201,6 +201,11 @@ SIGNATURES = {
                                               _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_tree_lut_bootstrap_mvk": (C.c_int, [_vp, _vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p,
                                                _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_tgsw_set_create": (C.c_int, [_vp, _i32p, C.c_size_t, C.c_int, C.POINTER(_vp)]),
+    "thfhe_tgsw_set_destroy": (None, [_vp]),
+    "thfhe_lhe_cmux": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_lhe_lookup": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p]),
+    "thfhe_lhe_lookup_wo_keyswitch": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p]),
     "thfhe_dev_alloc": (_vp, [_vp, C.c_size_t]),
     "thfhe_dev_free": (None, [_vp, _vp]),
     "thfhe_copy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
@@ -750,6 +755,58 @@ class CloudKey(_EvalKey):
         _check(fn(*head, *families, *tail))
         return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
 
+    # -- leveled table lookup on TGSW-encrypted address bits (thfhe_tgsw_set_create, thfhe_lhe_cmux, thfhe_lhe_lookup) ----------
+    def tgsw_set(self, samples, d):
+        """Device-resident address bits: samples int32[count * d][2l][2][N] (SecretKeySet.tgsw_encrypt of the bits, sample-major: bit i of sample s
+        is row s d + i), kept as spectra, count d 2l 32 KiB.  Returns a TgswSet: close() it (or use `with`) before this key is closed."""
+        return TgswSet(self, samples, d)
+
+    def lhe_cmux(self, tset, bit, d1_a, d1_b, d0_a, d0_b):
+        """(out_a, out_b) int32[count][N]: sample s gets d0[s] + C_(s,bit) (.) (d1[s] - d0[s]) -- d1 where its address bit `bit` is 1, else d0."""
+        N = self.params.N
+        arrs = [np.ascontiguousarray(v, np.int32).reshape(-1, N) for v in (d1_a, d1_b, d0_a, d0_b)]
+        _same_count(*arrs)
+        out_a, out_b = np.empty_like(arrs[0]), np.empty_like(arrs[0])
+        _check(lib().thfhe_lhe_cmux(self.h, tset.h, int(bit), *[_p32(v) for v in arrs], _p32(out_a), _p32(out_b), arrs[0].shape[0]))
+        return out_a, out_b
+
+    def lhe_lookup(self, tset, tab_b, *, d_tree, d_rot, theta=1, tab_a=None, table_index=None, first=0, count=None):
+        """Leveled lookup of samples first .. first+count-1 of the set (default: all from `first`) in the table tab_b int32[n_tables][2^d_tree][N]
+        (thfhe.lut.lhe_table; tab_a: the masks of an encrypted table, None: public): d_tree + d_rot CMuxes, theta functions per sample.
+        Returns key-switched records int32[count, theta, n+1]."""
+        return self._lhe_lookup(tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, True)
+
+    def lhe_lookup_wo_keyswitch(self, tset, tab_b, *, d_tree, d_rot, theta=1, tab_a=None, table_index=None, first=0, count=None):
+        """lhe_lookup without the key switch: int32[count, theta, N+1] records under the ring key."""
+        return self._lhe_lookup(tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, False)
+
+    def _lhe_lookup(self, tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, keyswitch):
+        N = self.params.N
+        if not 0 <= int(d_tree) <= 6:
+            raise ValueError("d_tree must be 0 .. 6")
+        leaves = 1 << int(d_tree)
+        tab_b = np.ascontiguousarray(tab_b, np.int32)
+        if tab_b.size == 0 or tab_b.size % (leaves * N):
+            raise ValueError(f"tab_b: expected int32[n_tables][{leaves}][{N}]")
+        if tab_a is not None:
+            tab_a = np.ascontiguousarray(tab_a, np.int32)
+            if tab_a.size != tab_b.size:
+                raise ValueError("tab_a and tab_b differ in size")
+        first = int(first)
+        count = tset.count - first if count is None else int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        idx = None
+        if table_index is not None:
+            idx = np.ascontiguousarray(table_index, np.int32).reshape(-1)
+            if idx.shape[0] != count:
+                raise ValueError(f"table_index holds {idx.shape[0]} entries for {count} samples")
+        out = np.empty((count, int(theta) if theta in (1, 2, 4) else 1, self.words if keyswitch else N + 1), np.int32)
+        fn = lib().thfhe_lhe_lookup if keyswitch else lib().thfhe_lhe_lookup_wo_keyswitch
+        _check(fn(self.h, tset.h, first, count, int(d_tree), int(d_rot), int(theta), _p32(tab_a), _p32(tab_b), tab_b.size // (leaves * N), _p32(idx),
+                  _p32(out)))
+        return out
+
     def set_tree_slice(self, max_candidates):
         """Level-1 candidates (samples x p_hi, x k for tree_lut_bootstrap_mvk) per slice of tree_lut_bootstrap(_mv, _mvk): bounds its workspace (8 KiB of packing scratch per candidate);
         also the output records (samples x q) per slice of mv_lut_bootstrap."""
@@ -778,6 +835,28 @@ class CloudKey(_EvalKey):
 
 
 # ---- the reference's single-key gate API (gates.jl:15-177), batched over the leading axis -------------
+class TgswSet(_Handle):
+    """TGSW samples resident on a CloudKey's device (thfhe_tgsw_set_create): the address bits of `count` samples, d bits each."""
+
+    def __init__(self, ck, samples, d):
+        p = ck.params
+        d = int(d)
+        a = np.ascontiguousarray(samples, np.int32)
+        per_bit = 2 * p.l * 2 * p.N
+        if d < 1 or a.size == 0 or a.size % (per_bit * d):
+            raise ValueError(f"samples: expected int32[count * d][{2 * p.l}][2][{p.N}] with d = {d}")
+        self.ck, self.d, self.count = ck, d, a.size // (per_bit * d)   # the key is kept alive for as long as the set
+        h = _vp()
+        _check(lib().thfhe_tgsw_set_create(ck.h, _p32(a), self.count, d, C.byref(h)))
+        self._own(h, lib().thfhe_tgsw_set_destroy)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def gate_nand(ck, x, y): return ck.gates(NAND, x, y)
 def gate_or(ck, x, y): return ck.gates(OR, x, y)
 def gate_and(ck, x, y): return ck.gates(AND, x, y)

@@ -709,6 +709,22 @@ def sbox_digits(cir, hi, lo, table, N=1024):
     return cir.tree_mv(cir.mv_base(tv0), w, [lo], [hi])
 
 
+def lhe_sbox(ck, tset, table, p_out=8):
+    """A 16-bit -> 4-bit S-box by leveled lookup (thfhe_lhe_lookup), not a circuit of gates: `table` holds 2^16 integers in [0, 16), `tset`
+    the TGSW samples of the 16 address bits of every sample (CloudKey.tgsw_set, d = 16).  A 16-bit address needs (d_tree, d_rot) = (6, 10), where
+    box = N >> 10 = 1 leaves room for ONE function per polynomial, so theta = 4 does not fit; the four output bits are four lookups at (6, 10, 1) on
+    the same set, 4 x 73 CMuxes per sample (about half a bootstrap).  The other layout the issue of four functions allows, theta = 4 at d_rot = 8,
+    serves 14-bit addresses only.  Returns int32[count, 4, n+1]: record j of a sample is bit j of its entry at modulus p_out (thfhe.lut.encode)."""
+    from . import lut
+    t = np.asarray(table, np.int64).reshape(-1)
+    if t.shape[0] != 1 << 16 or np.any((t < 0) | (t > 15)):
+        raise ValueError("table: expected 2^16 integers in [0, 16)")
+    if tset.d != 16:
+        raise ValueError("tset: expected 16 address bits per sample")
+    outs = [ck.lhe_lookup(tset, lut.lhe_table((t >> j) & 1, 6, 10, encode=lambda v: lut.encode(v, p_out)), d_tree=6, d_rot=10)[:, 0] for j in range(4)]
+    return np.stack(outs, axis=1)
+
+
 def _tables(ck, cir):
     return np.stack([np.asarray(t, ck._tv_dtype).reshape(ck.params.N) for t in cir.tables])
 

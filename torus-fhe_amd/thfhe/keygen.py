@@ -158,19 +158,43 @@ class SecretKeySet:
         self.lwe_key = (np.asarray(lwe_key, np.int32) if lwe_key is not None
                         else rng.integers(0, 2, p.n).astype(np.int32))          # LweKey: uniform binary
         self.rlwe_key = rng.integers(0, 2, p.N).astype(np.int32)                 # RLweKey: uniform binary
-        rows = 2 * p.l
+        self.sigma_bk = sigma_bk
+        self.bk = self._tgsw_encrypt(rng, self.lwe_key)
+        self.ksk = gen_keyswitch_key(rng, self.rlwe_key, self.lwe_key, p.ks_t, p.ks_basebit, sigma_ks)
+
+    def _tgsw_encrypt(self, rng, bits):
+        """tgsw_encrypt (tgsw.jl:88-101) of every bit under the ring key, on the generator `rng` -> int32[len(bits)][2l][2][N]."""
+        p = self.params
+        bits = np.asarray(bits, np.int64).reshape(-1)
+        m, rows = bits.shape[0], 2 * p.l
         # rlwe_encrypt_zero for every TGSW row: mask uniform, body = z (*) mask + gaussian
-        mask = rng.integers(-2**31, 2**31, size=(p.n * rows, p.N), dtype=np.int64).astype(np.int32)
-        body = polymul_small32(mask, self.rlwe_key).astype(np.int64) + dtot32(rng.standard_normal((p.n * rows, p.N)) * sigma_bk)
-        bk = np.empty((p.n, rows, 2, p.N), np.int64)
-        bk[:, :, 0, :] = mask.reshape(p.n, rows, p.N)
-        bk[:, :, 1, :] = body.reshape(p.n, rows, p.N)
+        mask = rng.integers(-2**31, 2**31, size=(m * rows, p.N), dtype=np.int64).astype(np.int32)
+        body = polymul_small32(mask, self.rlwe_key).astype(np.int64) + dtot32(rng.standard_normal((m * rows, p.N)) * self.sigma_bk)
+        out = np.empty((m, rows, 2, p.N), np.int64)
+        out[:, :, 0, :] = mask.reshape(m, rows, p.N)
+        out[:, :, 1, :] = body.reshape(m, rows, p.N)
         # + message * gadget on the constant coefficient of polynomial j of row (j, level)   tgsw.jl:65-85
         for j in range(2):
             for lv in range(p.l):
-                bk[:, j * p.l + lv, j, 0] += self.lwe_key.astype(np.int64) << (32 - (lv + 1) * p.Bgbit)
-        self.bk = bk.astype(np.uint32).view(np.int32)
-        self.ksk = gen_keyswitch_key(rng, self.rlwe_key, self.lwe_key, p.ks_t, p.ks_basebit, sigma_ks)
+                out[:, j * p.l + lv, j, 0] += bits << (32 - (lv + 1) * p.Bgbit)
+        return out.astype(np.uint32).view(np.int32)
+
+    def tgsw_encrypt(self, bits, seed=0x5EED0003):
+        """TGSW samples of `bits` under the ring key, the bootstrapping key's own code path and layout (bk == the samples of lwe_key on the same
+        generator state) -> int32[len(bits)][2l][2][N]: what CloudKey.tgsw_set takes as the address bits of a leveled lookup."""
+        return self._tgsw_encrypt(np.random.default_rng(seed), bits)
+
+    def tlwe_phase(self, a, b):
+        """b - a (*) z of TLWE samples under the ring key (masks a, bodies b: int32[..., N]) as wrapping int32."""
+        a = np.ascontiguousarray(a, np.int32)
+        az = polymul_small32(a.reshape(-1, self.params.N), self.rlwe_key).reshape(a.shape)
+        return (np.asarray(b, np.int64) - az.astype(np.int64)).astype(np.uint32).view(np.int32)
+
+    def ring_phase(self, recs):
+        """Phase of LWE(N) records (the _wo_keyswitch outputs) under the extracted ring key, as wrapping int32."""
+        recs = np.asarray(recs, np.int32).reshape(-1, self.params.N + 1).astype(np.int64)
+        ph = recs[:, -1] - (recs[:, :-1] * self.rlwe_key.astype(np.int64)).sum(axis=1)
+        return ph.astype(np.uint32).view(np.int32)
 
     def encrypt(self, bits, seed=0x5EED0002):
         """lwe_encrypt of +-1/8 per bit -> int32[len(bits)][n+1]."""

@@ -155,6 +155,39 @@ def tree_mvk_factors(fs, p_hi, p_lo, p_out=2, N=1024):
     return parts[0][0], np.stack([w for _, w in parts])
 
 
+def lhe_table(functions, d_tree, d_rot, theta=1, encode=None, N=1024):
+    """Table polynomials of a leveled lookup (thfhe_lhe_lookup): int32[2^d_tree][N] from theta integer tables of 2^(d_tree + d_rot)
+    entries (functions[j][e] = f_j(e); with theta = 1 one table will do).  Entry e of function j sits at coefficient (e mod 2^d_rot) * box + j of
+    polynomial e >> d_rot, box = N >> d_rot -- the many-LUT layout without the half-box offset: the address is exact, not a noisy phase.  The other
+    coefficients of a box are zero.  encode: integers -> Torus32 words (e.g. lambda v: lut.encode(v, 8)); None: the entries are the words."""
+    if not (0 <= d_tree <= 6 and 0 <= d_rot <= 10):
+        raise ValueError("d_tree must be 0 .. 6 and d_rot 0 .. 10")
+    box = N >> d_rot
+    if theta not in (1, 2, 4) or theta > box:
+        raise ValueError("theta must be 1, 2 or 4 and at most box = N >> d_rot")
+    F = np.asarray(functions, np.int64)
+    if F.ndim == 1 and theta == 1:
+        F = F[None]
+    entries = 1 << (d_tree + d_rot)
+    if F.shape != (theta, entries):
+        raise ValueError(f"expected {theta} tables of {entries} entries, got shape {F.shape}")
+    words = np.asarray(encode(F), np.int64) if encode is not None else F
+    tab = np.zeros((1 << d_tree, N), np.int64)
+    e = np.arange(entries)
+    for j in range(theta):
+        tab[e >> d_rot, (e & ((1 << d_rot) - 1)) * box + j] = words[j]
+    return _to_i32(tab)
+
+
+def lhe_address_bits(addresses, d):
+    """Bits of the addresses, low bit first, sample-major: int32[len(addresses) * d], bit i of address s at s d + i -- the order
+    SecretKeySet.tgsw_encrypt -> CloudKey.tgsw_set expects."""
+    a = np.asarray(addresses, np.int64).reshape(-1)
+    if not 1 <= d <= 16 or np.any((a < 0) | (a >= 1 << d)):
+        raise ValueError(f"addresses must lie in [0, 2^{d}), 1 <= d <= 16")
+    return ((a[:, None] >> np.arange(d)[None, :]) & 1).astype(np.int32).reshape(-1)
+
+
 def encrypt_table(rlwe_key, tv, sigma, rng):
     """The client side of an encrypted table (thfhe_lut_bootstrap_enc): a fresh TLWE sample (tv_a, tv_b) of the test vector(s) tv int32[..., N]
     under the bootstrapping ring key: tv_a uniform, tv_b = tv_a (*) z + tv + e, e Gaussian of standard deviation sigma; exact product."""
