@@ -8,7 +8,9 @@ below that; the recipe here reaches it through the public bootstrap calls:
 * every key coefficient of the crafted step = extreme_key_word(...): all 16-bit limbs at magnitude 2^15, so the sum at coefficient N - 1
   is coherent (l N 2^(Bgbit-1) 2^15 per limb from the body rows alone: half the bound);
 * full bound: one step earlier, a key whose only non-zero coefficient is w X^0 in the body row of level 1, mask column, makes the mask
-  equal to the body; the crafted step then has the extreme digit in all 2l rows.
+  equal to the body; the crafted step then has the extreme digit in all 2l rows;
+* the leveled calls (thfhe_lhe_cmux, thfhe_lhe_lookup) and the encrypted-table bootstrap take mask and body from the caller: all 2l rows are
+  loaded directly (lhe_cmux_case, lhe_rot_table, lut_enc_case), which reaches the full bound at l Bgbit = 32 too.
 
 These are not valid ciphertexts: the contract under test is word equality with the oracle.  reached(...) recomputes, with Python integers,
 the per-limb sum the crafted step really produces at its peak coefficient from the oracle's own decomposition."""
@@ -374,3 +376,69 @@ def kms_tlev_case(p, gsw, party):
     bara = np.zeros(p.n, np.int32)
     bara[:2] = N
     return gsw, bara
+
+
+# ---- leveled table lookup (thfhe_lhe_cmux / thfhe_lhe_lookup) ----------------------------------------------
+# The leveled calls take the TGSW words and both TLWE inputs from the caller, so all 2l rows are loaded directly -- no key step that copies the
+# body into the mask -- and l Bgbit = 32 reaches the full bound too.  A TLWE sample is int32[2N] = (mask, body) as in lhe_reference.py.
+def _i32(v):
+    return (np.asarray(v, np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def lhe_cmux_case(p):
+    """Crafted leveled CMux: (C int32[2l][2][N] with every word extreme_key_word, d1 int32[2N] with every word digit_word, d0 = 0): the
+    difference d1 - d0 decomposes to the extreme digit in all 2l rows at every coefficient."""
+    C = np.full((2 * p.l, 2, p.N), extreme_key_word(32), np.int32)
+    d1 = _i32(np.full(2 * p.N, digit_word(32, p.l, p.Bgbit), np.int64))
+    return C, d1, np.zeros(2 * p.N, np.int32)
+
+
+def lhe_rot_table(p, s):
+    """The table polynomial int32[N] whose rotation step by s = N / m has the difference digit_word everywhere: segment r (coefficients
+    r s .. (r + 1) s - 1) holds q_r = (r - m / 2) T.  X^(2N - s) ACC - ACC is q_(r+1) - q_r = T inside, and -q_0 - q_(m-1) = T in the last
+    segment (the wrap negates).  s = 512: (-T, 0); s = 256: (-2T, -T, 0, T)."""
+    m = p.N // s
+    assert m >= 2 and m * s == p.N
+    T = digit_word(32, p.l, p.Bgbit)
+    return _i32(np.repeat([(r - m // 2) * T for r in range(m)], s))
+
+
+def lhe_reached(p, C, diff):
+    """Exact peak limb sum of the external product C (.) diff (C int32[2l][2][N], diff int32[2N] = (mask, body)) over all 2l rows, the larger
+    of the two output columns."""
+    N, l = p.N, p.l
+    diff = np.asarray(diff, np.int32)
+    digits = np.concatenate([decompose(diff[:N], 32, l, p.Bgbit), decompose(diff[N:], 32, l, p.Bgbit)])
+    return max(peak_limb_sum([(digits[r], C[r][c]) for r in range(2 * l)], 32) for c in range(2))
+
+
+def lhe_rot_diff(tab_a, tab_b, shift):
+    """X^shift ACC - ACC of the accumulator (tab_a, tab_b) (tab_a None: zero mask) -> int32[2N], the difference a rotation step decomposes."""
+    N = len(tab_b)
+    out = np.zeros(2 * N, np.int32)
+    rot = np.zeros(N, np.int32)
+    for j, t in enumerate((tab_a, tab_b)):
+        if t is None:
+            continue
+        t = np.ascontiguousarray(t, np.int32)
+        O.lib().oracle_mul_by_monomial32(O.p32(t), int(shift), N, O.p32(rot))
+        out[j * N:(j + 1) * N] = _i32(rot.astype(np.int64) - t)
+    return out
+
+
+# ---- encrypted-table bootstrap (thfhe_lut_bootstrap_enc; DESIGN.md section 4.11) ---------------------------------------------------
+def lut_enc_case(p, bk):
+    """Crafted encrypted-table bootstrap: tables tv_a = tv_b = mu everywhere, a_0 = 2^31 (bara_0 = N at every theta), body 0, step-0 key all
+    extreme_key_word: the accumulator starts as (mu, mu), so step 0 itself has -2 mu = digit_word in mask and body -- all 2l rows, with no
+    key step before it.  Returns (bk', x, mu)."""
+    bk = np.array(bk, np.int32, copy=True)
+    bk[0] = extreme_key_word(32)
+    x = np.zeros(p.n + 1, np.int32)
+    x[0] = -2**31
+    return bk, x, crafted_mu(32, p.l, p.Bgbit)
+
+
+def lut_enc_reached(p, bk, mu):
+    """Exact peak limb sum of step 0 of lut_enc_case, largest over the two output columns."""
+    rows = step_digit_rows(np.full((2, p.N), mu, np.int32), p.N, 32, p.l, p.Bgbit)
+    return max(peak_limb_sum([(d, bk[0, r, c]) for r, _, d in rows], 32) for c in range(2))

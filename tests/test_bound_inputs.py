@@ -125,3 +125,82 @@ def test_kms_recipes_reach_the_bound(O):
     assert np.all(acc[0] == B.crafted_mu(64, p.l_gsw, p.bg_gsw))
     assert 0.999 * bd <= B.gsw_reached(acc, p.N, gsw[0, 1], p.l_gsw, p.bg_gsw) < bd
     assert np.array_equal(orc.tlev_rotate(0, bara), orc.tlev_rotate(0, bara, schoolbook=True))
+
+
+# ---- leveled table lookup and encrypted-table bootstrap (the crafting facts test_gpu_exactness_bound.py relies on) ------------------
+LHE_SHAPES = [(1, 8), (2, 10), (3, 7), (3, 10), (4, 8)]   # (l, Bgbit) of the leveled cases in test_gpu_exactness_bound.py
+
+
+def _lhe_params(O, l, Bgbit):
+    return O.make_params("SK-128", n=4, l=l, Bgbit=Bgbit)
+
+
+@pytest.mark.parametrize("l, Bgbit", LHE_SHAPES)
+def test_leveled_cmux_recipe_reaches_the_bound(O, l, Bgbit):
+    import lhe_reference as LR
+    p = _lhe_params(O, l, Bgbit)
+    N, T, e = p.N, B.digit_word(32, l, Bgbit), B.extreme_digit(Bgbit)
+    assert e == -2**(Bgbit - 1)
+    C, d1, d0 = B.lhe_cmux_case(p)
+    # fact 1: T at all N coefficients decomposes to e at every level
+    assert np.all(B.decompose(d1[:N], 32, l, Bgbit) == e) and np.all(B.decompose(d1[N:], 32, l, Bgbit) == e)
+    # fact 2: against the constant extreme key word the 2l rows give the bound exactly; the l body rows alone give half
+    assert np.all(C == B.extreme_key_word(32)) and not d0.any()
+    bd = B.bound(2 * l, N, Bgbit)
+    assert B.lhe_reached(p, C, LR._sub(d1, d0)) == bd
+    assert B.lhe_reached(p, C, np.concatenate([np.zeros(N, np.int32), d1[N:]])) == B.bound(l, N, Bgbit) == bd // 2
+    # ... and from non-zero operands with the same difference
+    w = np.random.default_rng(l * 100 + Bgbit).integers(-2**31, 2**31, 2 * N, dtype=np.int64).astype(np.int32)
+    assert np.array_equal(LR._sub(LR._add(w, d1), w), d1)
+    # (3, 10) is the largest of the five sums: 6 x 1024 x 2^9 x 2^15 = 2^36.6
+    assert bd <= 6 * 1024 * 2**9 * 2**15 and (bd == 6 * 1024 * 2**9 * 2**15) == ((l, Bgbit) == (3, 10))
+
+
+@pytest.mark.parametrize("l, Bgbit", LHE_SHAPES)
+def test_leveled_rotation_tables_reach_the_bound(O, l, Bgbit):
+    import lut_reference as R
+    p = _lhe_params(O, l, Bgbit)
+    N, T = p.N, B.digit_word(32, l, Bgbit)
+    C = np.full((2 * l, 2, N), B.extreme_key_word(32), np.int32)
+    assert B.lhe_rot_table(p, 512).tolist() == [B.wrap(-T, 32)] * 512 + [0] * 512
+    assert B.lhe_rot_table(p, 256)[::256].tolist() == [B.wrap(-2 * T, 32), B.wrap(-T, 32), 0, B.wrap(T, 32)]
+    for s in (512, 256, 128, 1):
+        tab = B.lhe_rot_table(p, s)
+        # fact 3: X^(2N - s) ACC - ACC equals T at all N coefficients (oracle_mul_by_monomial32)
+        rot = R.monomial(tab, 2 * N - s, N)
+        assert np.all(R.to_i32(rot.astype(np.int64) - tab) == B.wrap(T, 32)), s
+        diff = B.lhe_rot_diff(tab, tab, 2 * N - s)
+        assert np.all(diff == B.wrap(T, 32))
+        if s >= 256:
+            assert B.lhe_reached(p, C, diff) == B.bound(2 * l, N, Bgbit)
+            assert B.lhe_reached(p, C, B.lhe_rot_diff(None, tab, 2 * N - s)) == B.bound(2 * l, N, Bgbit) // 2   # public table: zero mask
+
+
+@pytest.mark.parametrize("l, Bgbit", LHE_SHAPES)
+def test_random_words_stay_far_below_the_leveled_bound(O, l, Bgbit):
+    # why test_gpu_lhe_shapes.py cannot stand in for the crafted cases: random TGSW words against random differences leave the peak limb sum
+    # more than 5 bits below the bound (a statement about the reference inputs; the sum is sqrt(2 l N) incoherent terms, not 2 l N coherent ones)
+    p = _lhe_params(O, l, Bgbit)
+    rng = np.random.default_rng(50 + l * 16 + Bgbit)
+    words = lambda *shape: rng.integers(-2**31, 2**31, size=shape, dtype=np.int64).astype(np.int32)
+    for _ in range(3):
+        assert B.lhe_reached(p, words(2 * l, 2, p.N), words(2 * p.N)) < B.bound(2 * l, p.N, Bgbit) // 32
+
+
+@pytest.mark.parametrize("l, Bgbit", [(2, 10), (3, 7), (3, 10), (4, 8)])
+def test_encrypted_table_recipe_reaches_the_bound_at_step_0(O, l, Bgbit):
+    import tree_lut_reference as TR
+    p = _lhe_params(O, l, Bgbit)
+    K = O.SKKeys(p, 0xB0 + l, 2.0**-25, 2.0**-15)
+    bk, x, mu = B.lut_enc_case(p, K.bk)
+    assert B.digit_word(32, l, Bgbit) % 2 == 0 and B.wrap(-2 * mu, 32) == B.digit_word(32, l, Bgbit)
+    for theta in (1, 2, 4):   # bara_0 = N (mod 2N) whatever theta is
+        assert (O.lib().oracle_modswitch(int(x[0]), p.N // theta) * theta) % (2 * p.N) == p.N
+    assert B.lut_enc_reached(p, bk, mu) == B.bound(2 * l, p.N, Bgbit)
+    orc = O.Oracle(p, bk, K.ksk)
+    tv = np.full(p.N, mu, np.int32)
+    u = TR.lut_enc_wo_keyswitch(orc, x, tv, tv, 4)
+    assert u.shape == (4, p.N + 1)
+    # the oracle's schoolbook path agrees on the crafted step: the accumulator (mu, mu) through CMux 0 at bara = N
+    acc = np.full((2, p.N), mu, np.int32)
+    assert np.array_equal(orc.mux_rotate(0, p.N, acc), orc.mux_rotate(0, p.N, acc, schoolbook=True))

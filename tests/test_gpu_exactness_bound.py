@@ -5,7 +5,8 @@ transform accuracy would pass every other GPU test.  Here tests/bound_inputs.py 
 extreme digit in every row at every coefficient against a key whose every word has all 16-bit limbs at magnitude 2^15: the limb sum at
 coefficient N - 1 is the bound itself (or the stated fraction of it).  Each case asserts the sum it reached, the kernel that ran, and
 every output word against the oracle.  The inputs are not valid ciphertexts; the contract is word equality.  n and the party count are
-reduced: the bound depends on neither."""
+reduced: the bound depends on neither.  The leveled CMux and rotation kernels (section 4.15) and the encrypted-table instantiations of the
+blind rotations (section 4.11) take mask and body from the caller, so their cases load all 2l rows directly -- l = 4, Bgbit = 8 at the full bound."""
 import numpy as np
 import pytest
 
@@ -232,5 +233,153 @@ def test_kms_rotations_at_the_bound(O, kms_keys, name, pair):
         u = ck.bootstrap_wo_keyswitch(np.stack([x, x]))
         for g in range(2):
             assert np.array_equal(u[g], ref_u), g
+    finally:
+        ck.close()
+
+
+# ---- leveled table lookup (sk_lhe_cmux_kernel<L, PUB>, sk_lhe_rotate_kernel<L>) and the kLutEnc blind rotations ----
+# The leveled calls take the TGSW words and both TLWE inputs from the caller: every word of C is extreme_key_word and the difference the CMux
+# decomposes is digit_word in mask and body, so all 2l rows are extreme with no key step before -- l = 4, Bgbit = 8 included.
+LHE_SHAPES = [(1, 8), (2, 10), (3, 7), (3, 10), (4, 8)]
+LHE_IDS = ["l1-Bg8", "SK-80", "SK-128", "l3-Bg10", "l4-Bg8-full"]
+BATCH = 12      # identical samples: more than one workgroup per CU pair, every one compared
+
+
+class _Lhe:
+    """One context of the shape (n = 4), its oracle and oracle parameters; close() in a finally."""
+
+    def __init__(self, O, l, Bgbit):
+        import thfhe
+        kw = dict(O.PARAM_SETS["SK-128"], n=4, l=l, Bgbit=Bgbit)
+        self.p = O.make_params(**kw)
+        K = O.SKKeys(self.p, 0xB0 + l, 2.0**-25, 2.0**-15)
+        self.K, self.orc = K, O.Oracle(self.p, K.bk, K.ksk)
+        self.ck = thfhe.CloudKey(thfhe.make_params(**kw), K.bk, K.ksk, device=0)
+
+    def close(self):
+        self.ck.close()
+
+
+def _same_as(got, ref, what):
+    """every sample of got (leading axis) equals the one model record set"""
+    for g in range(got.shape[0]):
+        assert np.array_equal(got[g], ref), (what, g, np.argwhere(got[g] != ref)[:8].tolist())
+
+
+def _words(rng, *shape):
+    return rng.integers(-2**31, 2**31, size=shape, dtype=np.int64).astype(np.int32)
+
+
+@pytest.mark.parametrize("l, Bgbit", LHE_SHAPES, ids=LHE_IDS)
+def test_lhe_cmux_at_the_bound(O, l, Bgbit):
+    # thfhe_lhe_cmux (sk_lhe_cmux_kernel<l, false>, diff_digits_z) with all 2l rows at the extreme digit against extreme key words: first from
+    # (d1, d0) = (T, 0), then from (w + T, w) with random words w -- the same digits out of non-zero operands, and an output that adds d0 = w
+    import lhe_reference as LR
+    E = _Lhe(O, l, Bgbit)
+    try:
+        p, N = E.p, E.p.N
+        C, d1, d0 = B.lhe_cmux_case(p)
+        w = _words(np.random.default_rng(0xC0 + l), 2 * N)
+        with E.ck.tgsw_set(np.tile(C, (BATCH, 1, 1, 1)), 1) as ts:
+            for what, (x1, x0) in (("zero d0", (d1, d0)), ("random d0", (LR._add(w, d1), w))):
+                assert B.lhe_reached(p, C, LR._sub(x1, x0)) == B.bound(2 * l, N, Bgbit)
+                ref = LR.cmux(p, C, x1, x0)
+                t1, t0 = np.tile(x1, (BATCH, 1)), np.tile(x0, (BATCH, 1))
+                a, b = E.ck.lhe_cmux(ts, 0, t1[:, :N], t1[:, N:], t0[:, :N], t0[:, N:])
+                _same_as(np.concatenate([a, b], axis=1), ref, what)
+    finally:
+        E.close()
+
+
+@pytest.mark.parametrize("l, Bgbit", LHE_SHAPES, ids=LHE_IDS)
+def test_lhe_rotate_at_the_bound(O, l, Bgbit):
+    # thfhe_lhe_lookup at d_tree = 0 (sk_lhe_rotate_kernel<l>, rotated_digits_z), theta = 4, the table in mask and body (full bound) and public
+    # (zero mask: half).  (a) d_rot 1: step 0 on the spectra loaded before the loop.  (b) d_rot 2, C_0 = 0: the crafted step is step 1, on
+    # spectra that arrived through the one-step-ahead requests of step 0 (at l = 4: the fourth row re-requested on entry).  (c) d_rot 2, crafted
+    # step 0, then a step on random words that reads the low bits the crafted one wrote.
+    import lhe_reference as LR
+    E = _Lhe(O, l, Bgbit)
+    try:
+        p, N = E.p, E.p.N
+        bd = B.bound(2 * l, N, Bgbit)
+        CK = np.full((2 * l, 2, N), B.extreme_key_word(32), np.int32)
+        rnd = _words(np.random.default_rng(0xD0 + l), 2 * l, 2, N)
+        cases = [  # (name, TGSW samples of the address bits, table shift s, crafted step)
+            ("rot1", np.stack([CK]), 512, 0),
+            ("rot2-step1", np.stack([np.zeros_like(CK), CK]), 512, 1),
+            ("rot2-step0-then-random", np.stack([CK, rnd]), 256, 0),
+        ]
+        ks_done = False
+        for name, Cs, s, step in cases:
+            d_rot = Cs.shape[0]
+            box = N >> d_rot
+            tab = B.lhe_rot_table(p, s)
+            assert box << step == s     # the crafted step rotates by the table's segment length, and the steps before it leave ACC alone
+            assert not Cs[:step].any()
+            kw = dict(d_tree=0, d_rot=d_rot, theta=4)
+            with E.ck.tgsw_set(np.tile(Cs, (BATCH, 1, 1, 1, 1)), d_rot) as ts:
+                for kind, tab_a, frac in (("enc", tab, 1), ("pub", None, 2)):
+                    assert B.lhe_reached(p, Cs[step], B.lhe_rot_diff(tab_a, tab, 2 * N - s)) == bd // frac
+                    ref = LR.lookup_wo_keyswitch(p, Cs, tab_a, tab, 0, d_rot, 4)
+                    u = E.ck.lhe_lookup_wo_keyswitch(ts, tab, tab_a=tab_a, **kw)
+                    assert u.shape == (BATCH, 4, N + 1)
+                    _same_as(u, ref, (name, kind))
+                    if not ks_done:   # the key-switched call once per shape
+                        ks_done = True
+                        _same_as(E.ck.lhe_lookup(ts, tab, tab_a=tab_a, **kw), np.stack([E.orc.keyswitch(r) for r in ref]), (name, kind, "keyswitch"))
+    finally:
+        E.close()
+
+
+@pytest.mark.parametrize("l, Bgbit", LHE_SHAPES, ids=LHE_IDS)
+def test_lhe_public_first_level_at_the_bound(O, l, Bgbit):
+    # thfhe_lhe_lookup at (d_tree 1, d_rot 0, theta 1).  Public table with leaves (0, T): sk_lhe_cmux_kernel<l, true>, which issues only the l
+    # body rows, all extreme -- l N 2^(Bgbit-1) 2^15.  Its encrypted twin, leaves (0, 0) and (T, T): sk_lhe_cmux_kernel<l, false> through the tree
+    # path's strides at the full 2l-row bound.  The N+1-word record carries every coefficient of the output mask column (the peak at coefficient
+    # N - 1 is observed there) but of the body coefficient 0 only.
+    import lhe_reference as LR
+    E = _Lhe(O, l, Bgbit)
+    try:
+        p, N = E.p, E.p.N
+        CK = np.full((1, 2 * l, 2, N), B.extreme_key_word(32), np.int32)
+        T = np.full(N, B.digit_word(32, l, Bgbit), np.int64).astype(np.uint32).view(np.int32)
+        tab = np.stack([np.zeros(N, np.int32), T])[None]      # [1 table][2 leaves][N]
+        with E.ck.tgsw_set(np.tile(CK, (BATCH, 1, 1, 1, 1)), 1) as ts:
+            for kind, tab_a, rows in (("pub", None, l), ("enc", tab, 2 * l)):
+                diff = np.concatenate([np.zeros(N, np.int32) if tab_a is None else T, T])     # leaf 1 - leaf 0
+                assert B.lhe_reached(p, CK[0], diff) == B.bound(rows, N, Bgbit)
+                ref = LR.lookup_wo_keyswitch(p, CK, None if tab_a is None else tab_a[0], tab[0], 1, 0, 1)
+                u = E.ck.lhe_lookup_wo_keyswitch(ts, tab, tab_a=tab_a, d_tree=1, d_rot=0, theta=1)
+                assert u.shape == (BATCH, 1, N + 1)
+                _same_as(u, ref, kind)
+    finally:
+        E.close()
+
+
+@pytest.mark.parametrize("l, Bgbit", LHE_SHAPES[1:], ids=LHE_IDS[1:])
+def test_encrypted_table_bootstrap_at_the_bound(O, l, Bgbit):
+    # thfhe_lut_bootstrap_enc (the kLutEnc instantiations of the ring, four-wave ring and cooperative kernels): the accumulator starts as the
+    # loaded table (mu, mu), so step 0 -- bara = N, key all extreme words -- has -2 mu = T in mask and body: the full 2l-row bound at step 0,
+    # l = 4, Bgbit = 8 included
+    import thfhe
+    import tree_lut_reference as TR
+    kw = dict(O.PARAM_SETS["SK-128"], n=4, l=l, Bgbit=Bgbit)
+    p = O.make_params(**kw)
+    K = O.SKKeys(p, 0xB0 + l, 2.0**-25, 2.0**-15)
+    bk, x, mu = B.lut_enc_case(p, K.bk)
+    assert B.lut_enc_reached(p, bk, mu) == B.bound(2 * l, p.N, Bgbit)
+    orc = O.Oracle(p, bk, K.ksk)
+    tv = np.full(p.N, mu, np.int32)
+    ref = TR.lut_enc_wo_keyswitch(orc, x, tv, tv, 4)
+    xs = np.tile(x, (BATCH, 1))
+    ck = thfhe.CloudKey(thfhe.make_params(**kw), bk, K.ksk, device=0)
+    try:
+        for coop, ring4, name in SK_KERNELS:
+            ck.set_coop_threshold(coop)
+            ck.set_ring4_threshold(ring4)
+            assert ck.rotation_kernel_name(len(xs)) == name.format(l=l)
+            u = ck.lut_bootstrap_enc_wo_keyswitch(tv, tv, xs, theta=4)
+            assert u.shape == (BATCH, 4, p.N + 1)
+            _same_as(u, ref, (coop, ring4))
     finally:
         ck.close()

@@ -4,7 +4,8 @@ pieces (lhe_reference.py).
 
   (1) 11 samples with random-word TGSW samples and random-word tables, encrypted and public: thfhe_lhe_cmux, and thfhe_lhe_lookup with and without
       the key switch at (d_tree, d_rot, theta) = (0, 1, 1), (1, 0, 1), (2, 3, 4), (6, 2, 1), (0, 10, 1); a per-sample table index over 3 tables;
-      a call cut into slices against the unsliced call;
+      a call cut into slices against the unsliced call; the same at d_tree = 0 -- (0, 3, 4) and (0, 10, 1) --, where the rotation kernel itself
+      picks the sample's table;
   (2) noiseless TGSW samples with a zero mask on ALL 1 024 addresses at (0, 10) and all 4 096 at (2, 10), against numpy alone: table words that
       the decomposition represents exactly come out exactly.  The 4 096 addresses go through four sets of 1 024 samples (a set of 4 096 x 12 bits
       is 2.4 .. 3.2 GB of host words at l = 3, 4), each read in two calls, the second with a non-zero `first`.
@@ -142,6 +143,45 @@ def test_per_sample_table_index_and_slices(env, shape):
             for kind in ("enc", "pub"):
                 got = ck.lhe_lookup(ts, tab_b, tab_a=tab_a if kind == "enc" else None, **kw)
                 assert np.array_equal(got, whole[kind]), (kind, differing(got, whole[kind]))
+        finally:
+            ck.set_tree_slice(65536)
+
+
+@pytest.mark.parametrize("cfg", [(0, 3, 4), (0, 10, 1)], ids=lambda c: "tree%d-rot%d-theta%d" % c)
+@pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
+def test_flat_rotation_with_per_sample_table_index(env, shape, cfg):
+    # d_tree = 0 with a per-sample table index: no tree level runs, so sk_lhe_rotate_kernel itself starts sample s from table table_index[s]
+    # (LheRotArgs.src_idx, src_stride = 1024 words, from the uploaded tables directly) -- the one dispatch path of lhe_lookup the cases above
+    # do not enter.  At d_tree = 0 a slice holds tree_slice samples, so set_tree_slice(3) cuts the 11 samples into 3 + 3 + 3 + 2 and the index
+    # slice is uploaded anew for each.
+    p, orc, ck = env(shape)
+    d_tree, d_rot, theta = cfg
+    Cs, tab_a, tab_b, idx, ref = case(p, orc, shape, cfg, n_tables=3)
+    assert tab_b.shape == (3, 1, N) and sorted(set(idx.tolist())) == [0, 1, 2] and len(set(idx[4:9].tolist())) > 1
+    kw = dict(d_tree=d_tree, d_rot=d_rot, theta=theta)
+    with ck.tgsw_set(Cs, d_rot) as ts:
+        whole = {}
+        for kind in ("enc", "pub"):
+            ta = tab_a if kind == "enc" else None
+            u = ck.lhe_lookup_wo_keyswitch(ts, tab_b, tab_a=ta, table_index=idx, **kw)
+            assert u.shape == (COUNT, theta, N + 1)
+            assert np.array_equal(u, ref[kind][0]), (kind, differing(u, ref[kind][0]))
+            whole[kind] = ck.lhe_lookup(ts, tab_b, tab_a=ta, table_index=idx, **kw)
+            assert whole[kind].shape == (COUNT, theta, p.n + 1)
+            assert np.array_equal(whole[kind], ref[kind][1]), (kind, differing(whole[kind], ref[kind][1]))
+            # a window of the set: first != 0, the index array follows the window
+            win = ck.lhe_lookup_wo_keyswitch(ts, tab_b, tab_a=ta, table_index=idx[4:9], first=4, count=5, **kw)
+            assert np.array_equal(win, ref[kind][0][4:9]), (kind, differing(win, ref[kind][0][4:9]))
+            win = ck.lhe_lookup(ts, tab_b, tab_a=ta, table_index=idx[4:9], first=4, count=5, **kw)
+            assert np.array_equal(win, ref[kind][1][4:9]), (kind, differing(win, ref[kind][1][4:9]))
+        try:
+            ck.set_tree_slice(3)
+            for kind in ("enc", "pub"):
+                ta = tab_a if kind == "enc" else None
+                got = ck.lhe_lookup(ts, tab_b, tab_a=ta, table_index=idx, **kw)
+                assert np.array_equal(got, whole[kind]), (kind, differing(got, whole[kind]))
+                u = ck.lhe_lookup_wo_keyswitch(ts, tab_b, tab_a=ta, table_index=idx, **kw)
+                assert np.array_equal(u, ref[kind][0]), (kind, differing(u, ref[kind][0]))
         finally:
             ck.set_tree_slice(65536)
 
