@@ -7,16 +7,15 @@ import pytest
 
 import dag_lut_reference as DR
 import lut_reference as R
+from support import SIGMA, words
 
 pytestmark = pytest.mark.gpu
-
-SIGMA = 2.0**-15   # fresh-ciphertext noise of SK-128
 
 
 def _random_table(rng, N, torus_bits):
     if torus_bits == 64:
         return rng.integers(-2**63, 2**63 - 1, N, dtype=np.int64)
-    return rng.integers(-2**31, 2**31, N).astype(np.int32)
+    return words(rng, N)
 
 
 def random_mixed_dag(rng, n_in, n_rows, gate_ops, N=1024, torus_bits=32, n_tables=3):
@@ -78,7 +77,7 @@ def test_random_mixed_dags_equal_the_level_loop(O):
             for trial in range(trials):
                 cir = random_mixed_dag(rng, 6, 90, ops, torus_bits=torus_bits)
                 assert cir.has_luts()
-                x = rng.integers(-2**31, 2**31, (6, key.words)).astype(np.int32)
+                x = words(rng, 6, key.words)
                 stats = {}
                 got = Cc.evaluate(key, cir, x, stats)
                 ref = Cc.evaluate_levels(key, cir, x)
@@ -110,7 +109,7 @@ def test_full_size_lut_nodes_equal_the_oracle(O, sk128):
     ck = thfhe.CloudKey(thfhe.make_params("SK-128"), K.bk, K.ksk, device=0)
     try:
         c, outs = _small_full_size_dag(rng, 1024, 32)
-        x = rng.integers(-2**31, 2**31, (3, p.n + 1)).astype(np.int32)
+        x = words(rng, 3, p.n + 1)
         got = Cc.evaluate(ck, c, x)
         ref = DR.evaluate(orc, c, x)
         assert np.array_equal(got[outs], ref[outs])
@@ -122,7 +121,7 @@ def test_full_size_lut_nodes_equal_the_oracle(O, sk128):
     mk = thfhe.MKCloudKey(thfhe.make_params(**mp.as_dict()), KM.bk, KM.ksk, device=0)
     try:
         c, outs = _small_full_size_dag(rng, mp.N, 64)
-        x = rng.integers(-2**31, 2**31, (3, mk.words)).astype(np.int32)
+        x = words(rng, 3, mk.words)
         got = Cc.evaluate(mk, c, x)
         ref = DR.evaluate(O.MKOracle(mp, KM.bk, KM.ksk), c, x, multi_key=True)
         assert np.array_equal(got[outs], ref[outs])
@@ -140,7 +139,7 @@ def test_instances_equal_single_runs_with_slices(O):
         for key, ops, torus_bits in ((ck, SK_OPS, 32), (mk, MK_OPS, 64)):
             cir = random_mixed_dag(rng, 5, 60, ops, torus_bits=torus_bits)
             Q = 6
-            x = rng.integers(-2**31, 2**31, (Q, 5, key.words)).astype(np.int32)
+            x = words(rng, Q, 5, key.words)
             single = np.stack([Cc.evaluate(key, cir, x[q]) for q in range(Q)])
             lut_outs = [cir.n_inputs + g for g, row in enumerate(cir.gates) if row[0] == thfhe.LUT_OUT]
             assert lut_outs
@@ -166,7 +165,7 @@ def test_lut_level_on_every_rotation_shape():
         a = c.lut(t[1], [x[0], x[1]], weights=(3, -1), bias=99, theta=1)
         b = c.lut(t[2], [x[1]], weights=(5,), bias=-4, theta=4)
         Q = 2048 + 1100
-        xs = rng.integers(-2**31, 2**31, (Q, 2, ck.words)).astype(np.int32)
+        xs = words(rng, Q, 2, ck.words)
         st = {}
         got = Cc.evaluate_batch(ck, c, xs, a + b, st)
         assert st["launches"] == 2 and st["levels"] == 1 and st["rotations"] == 2 * Q

@@ -8,38 +8,19 @@ import numpy as np
 import pytest
 
 import lut_reference as R
+from support import N, SIGMA, sk128_cloud_key, sk128_pack, words
 
 pytestmark = pytest.mark.gpu
-
-N = 1024
-SIGMA = 2.0**-15      # fresh-ciphertext noise of SK-128
-SIGMA_BK = 2.0**-25   # its ring noise: the packing key
 
 
 @pytest.fixture(scope="module")
 def ck(sk128):
-    import thfhe
-    p, K, orc = sk128
-    c = thfhe.CloudKey(thfhe.make_params("SK-128"), K.bk, K.ksk, device=0)
-    yield c
-    c.close()
+    yield from sk128_cloud_key(sk128)
 
 
 @pytest.fixture(scope="module")
 def pack(sk128):
-    """(PolyContext, packing key): LWE key -> the BOOTSTRAPPING ring key of the same key set."""
-    from thfhe import keygen
-    from thfhe import threshold as T
-    p, K, orc = sk128
-    pk = keygen.gen_pack_key(np.random.default_rng(0x7EE0001), K.lwe_key, K.rlwe_key[0], p.ks_t, p.ks_basebit, SIGMA_BK)
-    pc = T.PolyContext(0)
-    pc.set_pack_key(pk, p.ks_t, p.ks_basebit)
-    yield pc, pk
-    pc.close()
-
-
-def words(rng, shape):
-    return rng.integers(-2**31, 2**31, shape).astype(np.int32)
+    yield from sk128_pack(sk128)
 
 
 def run(ck, pc, cir, x):
@@ -56,8 +37,8 @@ def mixed_circuit(rng):
     from thfhe import circuits as Cc
     c = Cc.Circuit()
     x0, x1, x2, x3 = c.inputs(4)
-    t = dict(tab=words(rng, N), rows=words(rng, (2, N)), base=words(rng, (2, N)), wA=words(rng, (2, 4, 8)), wB=words(rng, (5, 4)),
-             wT=words(rng, (2, 3, 4, 8)), bias=int(rng.integers(-2**31, 2**31)))
+    t = dict(tab=words(rng, N), rows=words(rng, 2, N), base=words(rng, 2, N), wA=words(rng, 2, 4, 8), wB=words(rng, 5, 4),
+             wT=words(rng, 2, 3, 4, 8), bias=int(rng.integers(-2**31, 2**31)))
     b0, b1 = c.mv_base(t["base"][0]), c.mv_base(t["base"][1])
     w = dict(g=c.gate(NAND, x0, x1), l=c.lut(c.table(t["tab"]), [x0], theta=2), t=c.tree(c.tree_rows(t["rows"]), [x1], [x2], 4, theta1=2))
     w["mvA"] = c.mv(b0, t["wA"][0], [x0, x1], weights=(2, -3), bias=t["bias"])
@@ -78,7 +59,7 @@ def test_mixed_dag_equals_the_flat_calls(sk128, ck, pack, instances):
     rng = np.random.default_rng(6100)
     c, t, w = mixed_circuit(rng)
     assert c.has_mv_nodes() and len(c.mv_specs) == 3 and [len(s[6]) for s in c.mv_specs] == [2, 1, 2]
-    x = words(rng, (instances, 4, ck.words))
+    x = words(rng, instances, 4, ck.words)
     got, st = run(ck, pc, c, x)
     col = lambda *ws: [np.ascontiguousarray(got[:, i]) for i in ws]
     # the nodes against their flat calls, directly
@@ -152,11 +133,11 @@ def test_tree_batch_without_the_new_nodes_is_unchanged(sk128, ck, pack):
     x0, x1, x2 = c.inputs(3)
     g = c.gate(NAND, x0, x1)
     l = c.lut(c.table(words(rng, N)), [x0, x2], weights=(1, -2), theta=4)
-    tr = c.tree(c.tree_rows(words(rng, (4, N))), [x1], [x2], 4)
+    tr = c.tree(c.tree_rows(words(rng, 4, N)), [x1], [x2], 4)
     e = c.lut_enc(c.enc_table(words(rng, N), words(rng, N)), [g], theta=2)
     s = c.select([tr], l[0], 4)
     assert c.has_tree_nodes() and not c.has_mv_nodes()
-    x = words(rng, (2, 3, ck.words))
+    x = words(rng, 2, 3, ck.words)
     got, st = run(ck, pc, c, x)
     for q in range(2):
         assert np.array_equal(got[q], Cc.evaluate_levels(ck, c, x[q], pack=pc)), q
@@ -179,7 +160,7 @@ def test_the_gate_list_entries_refuse_the_two_opcodes(O, sk128, ck, op):
     try:
         rng = np.random.default_rng(6400 + op)
         for key in (ck, mk):
-            x = words(rng, (3, key.words))
+            x = words(rng, 3, key.words)
             bad = np.array([[thfhe.NAND, 0, 1, -1], [op, 0, 1, 2 if op == 20 else -1]], np.int32)
             with pytest.raises(thfhe.ThfheError, match="error -1.*opcode not defined"):
                 key.dag_run(x, bad)

@@ -8,38 +8,19 @@ import pytest
 
 import dag_tree_reference as DT
 import lut_reference as R
+from support import N, SIGMA, SIGMA_BK, sk128_cloud_key, sk128_pack, words
 
 pytestmark = pytest.mark.gpu
-
-N = 1024
-SIGMA = 2.0**-15      # fresh-ciphertext noise of SK-128
-SIGMA_BK = 2.0**-25   # its ring noise: the packing key
 
 
 @pytest.fixture(scope="module")
 def ck(sk128):
-    import thfhe
-    p, K, orc = sk128
-    c = thfhe.CloudKey(thfhe.make_params("SK-128"), K.bk, K.ksk, device=0)
-    yield c
-    c.close()
+    yield from sk128_cloud_key(sk128)
 
 
 @pytest.fixture(scope="module")
 def pack(sk128):
-    """(PolyContext, packing key): LWE key -> the BOOTSTRAPPING ring key of the same key set."""
-    from thfhe import keygen
-    from thfhe import threshold as T
-    p, K, orc = sk128
-    pk = keygen.gen_pack_key(np.random.default_rng(0x7EE0001), K.lwe_key, K.rlwe_key[0], p.ks_t, p.ks_basebit, SIGMA_BK)
-    pc = T.PolyContext(0)
-    pc.set_pack_key(pk, p.ks_t, p.ks_basebit)
-    yield pc, pk
-    pc.close()
-
-
-def words(rng, shape):
-    return rng.integers(-2**31, 2**31, shape).astype(np.int32)
+    yield from sk128_pack(sk128)
 
 
 def run(ck, pc, cir, x):
@@ -66,14 +47,14 @@ def test_lut_enc_nodes_alone(sk128, ck, instances):
     rng = np.random.default_rng(100 + instances)
     c = Cc.Circuit()
     x0, x1, x2 = c.inputs(3)
-    ea, eb = words(rng, (2, N)), words(rng, (2, N))
+    ea, eb = words(rng, 2, N), words(rng, 2, N)
     e = [c.enc_table(ea[i], eb[i]) for i in range(2)]
     b1 = int(rng.integers(-2**31, 2**31))
     o1 = c.lut_enc(e[0], [x0, x1], weights=(2, -3), bias=b1, theta=2)
     o2 = c.lut_enc(e[1], [x2], theta=4)
     o3 = c.lut_enc(e[1], [x0, x1, x2], weights=(1, 1, -5), theta=1)
     o4 = c.lut_enc(e[0], [x1], theta=4)
-    x = words(rng, (instances, 3, ck.words))
+    x = words(rng, instances, 3, ck.words)
     got, st = run(ck, None, c, x)                       # no packing context needed
     flat = lambda i, ins, **kw: ck.lut_bootstrap_enc(ea[i:i + 1], eb[i:i + 1], *[x[:, w] for w in ins], **kw)
     assert np.array_equal(got[:, o1], flat(0, [x0, x1], weights=(2, -3), bias=b1, theta=2))
@@ -98,7 +79,7 @@ def test_select_nodes_alone(sk128, ck, pack, instances):
     s2 = c.select([i0, i1], cand[2], 4, weights=(1, 2), bias=bias)
     s3 = c.select([i1], cand[0], 8)
     s4 = c.select([i1], cand[4], 4)                     # s1's group
-    x = words(rng, (instances, 10, ck.words))
+    x = words(rng, instances, 10, ck.words)
     got, st = run(ck, pc, c, x)
 
     def flat(first, p, ins, **kw):
@@ -119,14 +100,14 @@ def test_tree_nodes_alone(sk128, ck, pack, instances):
     rng = np.random.default_rng(120 + instances)
     c = Cc.Circuit()
     x0, x1, x2 = c.inputs(3)
-    rows = words(rng, (10, N))
+    rows = words(rng, 10, N)
     ra, rb, rc8 = c.tree_rows(rows[:2]), c.tree_rows(rows[2:6]), c.tree_rows(rows[6:10])
     b_lo, b_hi = (int(v) for v in rng.integers(-2**31, 2**31, 2))
     t1 = c.tree(ra, [x0], [x1], 4, theta1=2)
     t2 = c.tree(rb, [x0, x2], [x1], 4, lo_weights=(1, -2), lo_bias=b_lo, hi_bias=b_hi)
     t3 = c.tree(rc8, [x2], [x0, x1], 8, hi_weights=(3, 1), theta1=2)
     t4 = c.tree(ra, [x1], [x2], 4, theta1=2)            # t1's group
-    x = words(rng, (instances, 3, ck.words))
+    x = words(rng, instances, 3, ck.words)
     got, st = run(ck, pc, c, x)
     col = lambda ws: tuple(x[:, w] for w in ws)
     assert np.array_equal(got[:, t1], ck.tree_lut_bootstrap(pc, rows[:2], col([x0]), col([x1]), p_hi=4, theta=2))
@@ -148,9 +129,9 @@ def mixed_circuit(rng):
     c = Cc.Circuit()
     x = c.inputs(6)
     tabs = [c.table(words(rng, N)) for _ in range(2)]
-    ea, eb = words(rng, (2, N)), words(rng, (2, N))
+    ea, eb = words(rng, 2, N), words(rng, 2, N)
     e = [c.enc_table(ea[i], eb[i]) for i in range(2)]
-    rows = words(rng, (4 + 2 + 1 + 4, N))
+    rows = words(rng, 4 + 2 + 1 + 4, N)
     r41, r42, r44, r82 = c.tree_rows(rows[:4]), c.tree_rows(rows[4:6]), c.tree_rows(rows[6:7]), c.tree_rows(rows[7:11])
     w = {}
     # level 1
@@ -185,7 +166,7 @@ def test_mixed_circuit_levels_model_and_stats(sk128, ck, pack):
     rng = np.random.default_rng(130)
     c, w = mixed_circuit(rng)
     Q = 3
-    x = words(rng, (Q, 6, ck.words))
+    x = words(rng, Q, 6, ck.words)
     got, st = run(ck, pc, c, x)
     check_against_levels_and_single_runs(ck, pc, c, x, got)
     cen = c.census()
@@ -209,7 +190,7 @@ def test_slices_inside_instances(sk128, ck, pack):
     pc, pk = pack
     rng = np.random.default_rng(140)
     c, w = mixed_circuit(rng)
-    x = words(rng, (5, 6, ck.words))
+    x = words(rng, 5, 6, ck.words)
     whole, st = run(ck, pc, c, x)
     try:
         ck.set_dag_slice(7)
@@ -256,12 +237,12 @@ def test_context_checks(sk128, ck, pack):
     rng = np.random.default_rng(150)
     c = Cc.Circuit()
     x0, x1 = c.inputs(2)
-    t = c.tree(c.tree_rows(words(rng, (4, N))), [x0], [x1], 4)
+    t = c.tree(c.tree_rows(words(rng, 4, N)), [x0], [x1], 4)
     s = Cc.Circuit()
     s.select([s.inputs(3)[2]], 0, 2)
-    x = words(rng, (2, 2, ck.words))
+    x = words(rng, 2, 2, ck.words)
     want, _ = run(ck, pc, c, x)
-    for cir, xin in ((c, x), (s, words(rng, (1, 3, ck.words)))):
+    for cir, xin in ((c, x), (s, words(rng, 1, 3, ck.words))):
         with pytest.raises(thfhe.ThfheError, match="error -1.*null ctx"):
             run(ck, None, cir, xin)
         bare = T.PolyContext(0)
@@ -280,7 +261,7 @@ def test_context_checks(sk128, ck, pack):
     # a plan with only LUT_ENC nodes takes no packing context, and a bare one is not looked at
     e = Cc.Circuit()
     e.lut_enc(e.enc_table(words(rng, N), words(rng, N)), [e.inputs(1)[0]], theta=2)
-    xe = words(rng, (2, 1, ck.words))
+    xe = words(rng, 2, 1, ck.words)
     bare = T.PolyContext(0)
     assert np.array_equal(run(ck, None, e, xe)[0], run(ck, bare, e, xe)[0])
     bare.close()

@@ -13,15 +13,11 @@ import pytest
 import bound_inputs as B
 import lut_reference as R
 import oracle_lib as OL
+from support import KERNELS, words
 
 pytestmark = pytest.mark.gpu
 
-SK_KERNELS = [  # (coop threshold, ring4 threshold, kernel that does the batch of 12 rotations) -- as test_every_blind_rotate_kernel_bit_exact
-    (0, 0, "sk_blind_rotate_ring_kernel<{l}>"),
-    (0, 1024, "sk_blind_rotate_ring_kernel<{l}, 4 waves>"),
-    (1 << 20, 1024, "sk_blind_rotate_coop_kernel<{l}>"),
-    (6, 6, "sk_blind_rotate_ring_kernel<{l}, 4 waves>"),   # split (launch_br): 6 rotations on the four-wave ring + 6 cooperative (12 <= 6 + 6)
-]
+SK_KERNELS = [k[1:] for k in KERNELS]   # (coop threshold, ring4 threshold, kernel that does the batch of 12 rotations)
 
 
 @pytest.mark.parametrize("l, Bgbit, full", [(2, 10, True), (3, 7, True), (3, 10, True), (4, 8, False)],
@@ -266,10 +262,6 @@ def _same_as(got, ref, what):
         assert np.array_equal(got[g], ref), (what, g, np.argwhere(got[g] != ref)[:8].tolist())
 
 
-def _words(rng, *shape):
-    return rng.integers(-2**31, 2**31, size=shape, dtype=np.int64).astype(np.int32)
-
-
 @pytest.mark.parametrize("l, Bgbit", LHE_SHAPES, ids=LHE_IDS)
 def test_lhe_cmux_at_the_bound(O, l, Bgbit):
     # thfhe_lhe_cmux (sk_lhe_cmux_kernel<l, false>, diff_digits_z) with all 2l rows at the extreme digit against extreme key words: first from
@@ -279,7 +271,7 @@ def test_lhe_cmux_at_the_bound(O, l, Bgbit):
     try:
         p, N = E.p, E.p.N
         C, d1, d0 = B.lhe_cmux_case(p)
-        w = _words(np.random.default_rng(0xC0 + l), 2 * N)
+        w = words(np.random.default_rng(0xC0 + l), 2 * N)
         with E.ck.tgsw_set(np.tile(C, (BATCH, 1, 1, 1)), 1) as ts:
             for what, (x1, x0) in (("zero d0", (d1, d0)), ("random d0", (LR._add(w, d1), w))):
                 assert B.lhe_reached(p, C, LR._sub(x1, x0)) == B.bound(2 * l, N, Bgbit)
@@ -303,7 +295,7 @@ def test_lhe_rotate_at_the_bound(O, l, Bgbit):
         p, N = E.p, E.p.N
         bd = B.bound(2 * l, N, Bgbit)
         CK = np.full((2 * l, 2, N), B.extreme_key_word(32), np.int32)
-        rnd = _words(np.random.default_rng(0xD0 + l), 2 * l, 2, N)
+        rnd = words(np.random.default_rng(0xD0 + l), 2 * l, 2, N)
         cases = [  # (name, TGSW samples of the address bits, table shift s, crafted step)
             ("rot1", np.stack([CK]), 512, 0),
             ("rot2-step1", np.stack([np.zeros_like(CK), CK]), 512, 1),

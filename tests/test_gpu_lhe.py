@@ -13,16 +13,9 @@ import numpy as np
 import pytest
 
 import lhe_reference as LR
+from support import N, pmap
 
 pytestmark = pytest.mark.gpu
-
-N = 1024
-
-
-def pmap(fn, items):
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(8) as pool:
-        return list(pool.map(fn, items))
 
 
 class Keys:

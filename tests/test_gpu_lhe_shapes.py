@@ -1,4 +1,4 @@
-"""Leveled table lookup on every parameter shape (pytest -m gpu): the seven shapes of test_gpu_lut_shapes.py -- l = 1 .. 4
+"""Leveled table lookup on every parameter shape (pytest -m gpu): the seven shapes of support.py -- l = 1 .. 4
 and the Bgbit of each -- on sk_lhe_cmux_kernel and sk_lhe_rotate_kernel, every word against the model composed from the CPU oracle's exact
 pieces (lhe_reference.py).
 
@@ -16,51 +16,17 @@ import pytest
 
 import lhe_reference as LR
 import lut_reference as R
+from support import N, SHAPES, differing, pmap, shape_env, shape_id, words
 
 pytestmark = pytest.mark.gpu
 
-N = 1024
-SHAPES = [  # test_gpu_lut_shapes.SHAPES: (n, l, Bgbit, ks_t, ks_basebit)
-    (24, 1, 8, 8, 2), (24, 2, 10, 8, 2), (37, 3, 7, 8, 2), (16, 4, 8, 5, 3), (33, 3, 6, 3, 5), (1, 2, 7, 15, 1), (64, 4, 4, 4, 4),
-]
 CONFIGS = [(0, 1, 1), (1, 0, 1), (2, 3, 4), (6, 2, 1), (0, 10, 1)]
 COUNT = 11
 
 
-def shape_id(s):
-    return "n%d-l%d-Bg%d-ks%dx%d" % s
-
-
-def pmap(fn, items):
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(8) as pool:
-        return list(pool.map(fn, items))
-
-
-def words(rng, *shape):
-    return rng.integers(-2**31, 2**31, size=shape, dtype=np.int64).astype(np.int32)
-
-
-def differing(got, ref):
-    return np.argwhere(got != ref)[:6].tolist()
-
-
 @pytest.fixture(scope="module")
 def env(O):
-    import thfhe
-    made = {}
-
-    def get(shape):
-        if shape not in made:
-            n, l, Bgbit, t, bb = shape
-            kw = dict(n=n, N=N, k=1, l=l, Bgbit=Bgbit, ks_t=t, ks_basebit=bb, torus_bits=32, parties=1)
-            p = O.make_params(**kw)
-            K = O.SKKeys(p, 3000 + 7 * n + l, 2.0**-25, 2.0**-15)
-            made[shape] = (p, O.Oracle(p, K.bk, K.ksk), thfhe.CloudKey(thfhe.make_params(**kw), K.bk, K.ksk, device=0))
-        return made[shape]
-    yield get
-    for v in made.values():
-        v[2].close()
+    yield from shape_env(O)
 
 
 _cache = {}
@@ -88,7 +54,7 @@ def case(p, orc, shape, cfg, n_tables=1):
 
 @pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
 def test_cmux_every_word(env, shape):
-    p, orc, ck = env(shape)
+    p, K, orc, ck = env(shape)
     rng = np.random.default_rng(50 + SHAPES.index(shape))
     d = 3
     Cs = words(rng, COUNT, d, 2 * p.l, 2, N)
@@ -105,7 +71,7 @@ def test_cmux_every_word(env, shape):
 @pytest.mark.parametrize("cfg", CONFIGS, ids=lambda c: "tree%d-rot%d-theta%d" % c)
 @pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
 def test_lookup_every_word(env, shape, cfg):
-    p, orc, ck = env(shape)
+    p, K, orc, ck = env(shape)
     d_tree, d_rot, theta = cfg
     Cs, tab_a, tab_b, idx, ref = case(p, orc, shape, cfg)
     kw = dict(d_tree=d_tree, d_rot=d_rot, theta=theta)
@@ -122,7 +88,7 @@ def test_lookup_every_word(env, shape, cfg):
 
 @pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
 def test_per_sample_table_index_and_slices(env, shape):
-    p, orc, ck = env(shape)
+    p, K, orc, ck = env(shape)
     cfg = (2, 3, 4)
     Cs, tab_a, tab_b, idx, ref = case(p, orc, shape, cfg, n_tables=3)
     assert len(set(idx.tolist())) == 3
@@ -154,7 +120,7 @@ def test_flat_rotation_with_per_sample_table_index(env, shape, cfg):
     # (LheRotArgs.src_idx, src_stride = 1024 words, from the uploaded tables directly) -- the one dispatch path of lhe_lookup the cases above
     # do not enter.  At d_tree = 0 a slice holds tree_slice samples, so set_tree_slice(3) cuts the 11 samples into 3 + 3 + 3 + 2 and the index
     # slice is uploaded anew for each.
-    p, orc, ck = env(shape)
+    p, K, orc, ck = env(shape)
     d_tree, d_rot, theta = cfg
     Cs, tab_a, tab_b, idx, ref = case(p, orc, shape, cfg, n_tables=3)
     assert tab_b.shape == (3, 1, N) and sorted(set(idx.tolist())) == [0, 1, 2] and len(set(idx[4:9].tolist())) > 1
@@ -194,7 +160,7 @@ def exact_words(rng, p, *shape):
 
 @pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
 def test_trivial_samples_on_all_1024_addresses(env, shape):
-    p, orc, ck = env(shape)
+    p, K, orc, ck = env(shape)
     rng = np.random.default_rng(70 + SHAPES.index(shape))
     tab = exact_words(rng, p, 1, N)                              # (0, 10): box = 1, entry e at coefficient e
     addr = rng.permutation(1024)
@@ -209,7 +175,7 @@ def test_trivial_samples_on_all_1024_addresses(env, shape):
 
 @pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
 def test_trivial_samples_on_all_4096_addresses(env, shape):
-    p, orc, ck = env(shape)
+    p, K, orc, ck = env(shape)
     rng = np.random.default_rng(90 + SHAPES.index(shape))
     tab_a, tab_b = exact_words(rng, p, 4, N), exact_words(rng, p, 4, N)   # (2, 10): an encrypted table, so the mask is rotated too
     addr = rng.permutation(4096)

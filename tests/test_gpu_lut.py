@@ -7,29 +7,14 @@ import numpy as np
 import pytest
 
 import lut_reference as R
+from support import SIGMA, dec_int, enc_int, sk128_cloud_key, thresholds, words
 
 pytestmark = pytest.mark.gpu
-
-SIGMA = 2.0**-15   # fresh-ciphertext noise of SK-128
 
 
 @pytest.fixture(scope="module")
 def ck(sk128):
-    import thfhe
-    p, K, orc = sk128
-    c = thfhe.CloudKey(thfhe.make_params("SK-128"), K.bk, K.ksk, device=0)
-    yield c
-    c.close()
-
-
-def enc_int(K, m, p, seed):
-    from thfhe import lut
-    return R.encrypt_words(K, lut.encode(np.asarray(m), p), SIGMA, seed)
-
-
-def dec_int(K, recs, p):
-    from thfhe import lut
-    return lut.decode(K.phases(recs), p)
+    yield from sk128_cloud_key(sk128)
 
 
 def test_constant_test_vector_is_the_gate_bootstrap(sk128, ck):
@@ -65,7 +50,7 @@ def test_bit_exact_against_the_composed_oracle(sk128, ck, theta, n_inputs):
     rng = np.random.default_rng(10 * theta + n_inputs)
     count = 12
     recs, weights, bias = _random_case(K, rng, count, n_inputs, 200 + 10 * theta + n_inputs)
-    tvs = rng.integers(-2**31, 2**31, (3, p.N)).astype(np.int32)
+    tvs = words(rng, 3, p.N)
     idx = rng.integers(0, 3, count).astype(np.int32)
     kw = dict(weights=weights, bias=bias, theta=theta, lut_index=idx)
     u = ck.lut_bootstrap_wo_keyswitch(tvs, *recs, **kw)
@@ -82,20 +67,15 @@ def test_every_blind_rotate_kernel_shape(sk128, ck):
     p, K, orc = sk128
     rng = np.random.default_rng(7)
     recs, weights, bias = _random_case(K, rng, 12, 2, 300)
-    tvs = rng.integers(-2**31, 2**31, (3, p.N)).astype(np.int32)
+    tvs = words(rng, 3, p.N)
     idx = rng.integers(0, 3, 12).astype(np.int32)
     for theta in (1, 4):
         kw = dict(weights=weights, bias=bias, theta=theta, lut_index=idx)
         wo, ks = _reference(orc, recs, weights, bias, tvs, idx, theta, range(12))
-        try:
-            for coop, ring4 in ((0, 0), (0, 1024), (1 << 20, 1024), (5, 6)):
-                ck.set_coop_threshold(coop)
-                ck.set_ring4_threshold(ring4)
+        for coop, ring4 in ((0, 0), (0, 1024), (1 << 20, 1024), (5, 6)):
+            with thresholds(ck, coop, ring4):
                 assert np.array_equal(ck.lut_bootstrap_wo_keyswitch(tvs, *recs, **kw), wo), (theta, coop, ring4)
                 assert np.array_equal(ck.lut_bootstrap(tvs, *recs, **kw), ks), (theta, coop, ring4)
-        finally:
-            ck.set_coop_threshold(768)
-            ck.set_ring4_threshold(1024)
 
 
 @pytest.mark.parametrize("p_msg", [2, 4, 8])

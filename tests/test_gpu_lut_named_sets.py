@@ -11,10 +11,10 @@ import pytest
 
 import lut_reference as R
 import tree_lut_reference as TR
+from support import N, pmap
 
 pytestmark = pytest.mark.gpu
 
-N = 1024
 SETS = ["SK-80", "SK-lib"]
 
 
@@ -51,13 +51,6 @@ def S(O, request):
     s = NamedSet(O, request.param)
     yield s
     s.close()
-
-
-def pmap(fn, items):
-    """independent model samples on Python threads (ctypes and numpy drop the GIL)"""
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(8) as pool:
-        return list(pool.map(fn, items))
 
 
 # ---- the cases: inputs by seed, so that the CPU-only check of the model (the module docstring) can rebuild them ------------------------------

@@ -3,7 +3,7 @@ launch_rotations<kLut> and <kLutEnc> on the eight-wave ring, four-wave ring and 
 model composed from the CPU oracle (lut_reference.py, tree_lut_reference.py).
 
   (1) a sweep of parameter shapes (n <= 64 keeps an oracle rotation at tens of milliseconds): random non-constant tables with a per-sample
-      index, 1 .. 3 weighted inputs and a bias, theta = 1, 2, 4, on the four threshold pairs of test_gpu_exactness_bound.SK_KERNELS;
+      index, 1 .. 3 weighted inputs and a bias, theta = 1, 2, 4, on the four threshold pairs of support.KERNELS;
   (2) every rotation amount: records with an all-zero mask run no CMux, so the output is the extraction of X^{-barb} * table, which numpy
       gives without an oracle rotation -- every multiple of theta in Z_2N, the words next to the 2^32 wrap included, on each kernel shape;
   (3) zero-mask jobs interleaved with ordinary ones in the same workgroups (idle waves keep the ring's lock step).
@@ -15,63 +15,18 @@ import pytest
 import lut_reference as R
 import oracle_lib as OL
 import tree_lut_reference as TR
+from support import KERNELS, N, SHAPES, differing, pmap, shape_env, shape_id, spread_index, thresholds, words
 
 pytestmark = pytest.mark.gpu
 
-N = 1024
-SHAPES = [  # (n, l, Bgbit, ks_t, ks_basebit): l = 1 .. 4, digits up to SK-80's 10 bits, n = 1, n off the mask padding (37, 33), several key-switch shapes
-    (24, 1, 8, 8, 2), (24, 2, 10, 8, 2), (37, 3, 7, 8, 2), (16, 4, 8, 5, 3), (33, 3, 6, 3, 5), (1, 2, 7, 15, 1), (64, 4, 4, 4, 4),
-]
-KERNELS = [  # (id, coop threshold, ring4 threshold, kernel that does most of a batch below 2 048) -- test_gpu_exactness_bound.SK_KERNELS
-    ("ring8", 0, 0, "sk_blind_rotate_ring_kernel<{l}>"),
-    ("ring4", 0, 1024, "sk_blind_rotate_ring_kernel<{l}, 4 waves>"),
-    ("coop", 1 << 20, 1024, "sk_blind_rotate_coop_kernel<{l}>"),
-    ("split", 6, 6, "sk_blind_rotate_ring_kernel<{l}, 4 waves>"),   # launch_br: 6 rotations on the four-wave ring + the rest cooperative
-]
 KINDS = ["plain", "enc"]
 # 11 jobs: the eight-wave ring's second workgroup holds 3, the four-wave ring's third holds 3, the split is 6 (4 + 2) + 5 cooperative
 COUNT = 11
 
 
-def shape_id(s):
-    return "n%d-l%d-Bg%d-ks%dx%d" % s
-
-
-def pmap(fn, items):
-    """independent model jobs on Python threads (ctypes and numpy drop the GIL)"""
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(8) as pool:
-        return list(pool.map(fn, items))
-
-
 @pytest.fixture(scope="module")
 def env(O):
-    """shape -> (params, keys, oracle, CloudKey), built once per shape and closed at the end of the module"""
-    import thfhe
-    made = {}
-
-    def get(shape):
-        if shape not in made:
-            n, l, Bgbit, t, bb = shape
-            kw = dict(n=n, N=N, k=1, l=l, Bgbit=Bgbit, ks_t=t, ks_basebit=bb, torus_bits=32, parties=1)
-            p = O.make_params(**kw)
-            K = O.SKKeys(p, 3000 + 7 * n + l, 2.0**-25, 2.0**-15)
-            made[shape] = (p, K, O.Oracle(p, K.bk, K.ksk), thfhe.CloudKey(thfhe.make_params(**kw), K.bk, K.ksk, device=0))
-        return made[shape]
-    yield get
-    for v in made.values():
-        v[3].close()
-
-
-def words(rng, *shape):
-    return rng.integers(-2**31, 2**31, size=shape, dtype=np.int64).astype(np.int32)
-
-
-def spread_index(rng, count, n_luts):
-    """a per-sample table index that uses every table and differs between the two launches of the split case"""
-    idx = rng.permutation(np.arange(count) % n_luts).astype(np.int32)
-    assert len(set(idx.tolist())) == n_luts
-    return idx
+    yield from shape_env(O)
 
 
 def call(ck, kind, keyswitch, tabs, recs, **kw):
@@ -93,11 +48,6 @@ def model(orc, kind, tabs, recs, weights, bias, idx, theta):
     wo = np.stack(pmap(lambda g: model_wo(orc, kind, tabs, recs, weights, bias, idx, theta, g), range(len(idx))))
     ks = np.stack(pmap(lambda u: orc.keyswitch(u), wo.reshape(-1, N + 1))).reshape(wo.shape[0], theta, -1)
     return wo, ks
-
-
-def differing(got, ref):
-    """(job, output, word) of the first mismatches, for the assertion message"""
-    return np.argwhere(got != ref)[:6].tolist()
 
 
 _sweep_cache = {}
@@ -130,9 +80,7 @@ def sweep_case(orc, shape, kind, theta):
 def test_every_word_on_every_shape(env, shape, kind, kernel):
     p, K, orc, ck = env(shape)
     _, coop, ring4, name = kernel
-    try:
-        ck.set_coop_threshold(coop)
-        ck.set_ring4_threshold(ring4)
+    with thresholds(ck, coop, ring4):
         assert ck.rotation_kernel_name(COUNT) == name.format(l=p.l)
         for theta in (1, 2, 4):
             recs, weights, bias, tabs, idx, wo, ks = sweep_case(orc, shape, kind, theta)
@@ -143,9 +91,6 @@ def test_every_word_on_every_shape(env, shape, kind, kernel):
             got = call(ck, kind, True, tabs, recs, **kw)
             assert got.shape == (COUNT, theta, p.n + 1)
             assert np.array_equal(got, ks), (theta, differing(got, ks))
-    finally:
-        ck.set_coop_threshold(768)
-        ck.set_ring4_threshold(1024)
 
 
 # ---- (2) every rotation amount --------------------------------------------------------------------------------------------------------------
@@ -199,9 +144,7 @@ def test_every_rotation_amount(env, l, theta, kind, kernel):
     tabs = (words(rng, 3, N), words(rng, 3, N))
     idx = rng.integers(0, 3, len(body)).astype(np.int32)
     ref = rotation_only_reference(kind, tabs, idx, bar, theta)
-    try:
-        ck.set_coop_threshold(coop)
-        ck.set_ring4_threshold(ring4)
+    with thresholds(ck, coop, ring4):
         covered = set()
         for first in range(0, len(body), CALL):
             sl = slice(first, min(first + CALL, len(body)))
@@ -212,9 +155,6 @@ def test_every_rotation_amount(env, l, theta, kind, kernel):
             assert bad.size == 0, ("barb, output, word of the first mismatches", [(int(bar[first + g]), int(j), int(q)) for g, j, q in bad[:6]])
             covered |= set((bar[sl] % (2 * N)).tolist())
         assert covered == seen
-    finally:
-        ck.set_coop_threshold(768)
-        ck.set_ring4_threshold(1024)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -262,15 +202,10 @@ def test_zero_mask_jobs_between_ordinary_jobs(env, shape, kind, kernel):
     if key not in _sweep_cache:
         _sweep_cache[key] = model(orc, kind, tabs, [x], weights, bias, idx, theta)
     wo, ks = _sweep_cache[key]
-    try:
-        ck.set_coop_threshold(coop)
-        ck.set_ring4_threshold(ring4)
+    with thresholds(ck, coop, ring4):
         assert ck.rotation_kernel_name(COUNT) == name.format(l=p.l)
         kw = dict(weights=weights, bias=bias, theta=theta, lut_index=idx)
         u = call(ck, kind, False, tabs, [x], **kw)
         assert np.array_equal(u, wo), differing(u, wo)
         got = call(ck, kind, True, tabs, [x], **kw)
         assert np.array_equal(got, ks), differing(got, ks)
-    finally:
-        ck.set_coop_threshold(768)
-        ck.set_ring4_threshold(1024)

@@ -14,10 +14,10 @@ import pytest
 
 import lut_reference as R
 import mv_lut_reference as MV
+from support import N, pmap
 
 pytestmark = pytest.mark.gpu
 
-N = 1024
 SIGMA_BR = {"SK-128": 2.5e-3, "SK-80": 4.3e-3, "SK-lib": 3.2e-3}   # one rotation's noise, measured on the CPU model
 SIGMA_KS = {"SK-128": 2.8e-3, "SK-80": 2.2e-3, "SK-lib": 2.8e-3}
 
@@ -56,13 +56,6 @@ def Snamed(O, request):
     s = KeySet(O, request.param).open()
     yield s
     s.ck.close()
-
-
-def pmap(fn, items):
-    """independent model samples on Python threads (ctypes and numpy drop the GIL)"""
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(8) as pool:
-        return list(pool.map(fn, items))
 
 
 def model(S, recs, weights, bias, tv0, factors, idx, picks):

@@ -1,6 +1,6 @@
 """Multi-value bootstrapping on every kernel shape (pytest -m gpu): launch_rotations<kLutMv> at every decomposition
 length l = 1 .. 4 on the eight-wave ring, four-wave ring and cooperative kernels, every word of every job against the model composed from
-the CPU oracle (mv_lut_reference.py).  The shapes and threshold pairs are those of test_gpu_lut_shapes.py.
+the CPU oracle (mv_lut_reference.py).  The shapes and threshold pairs are those of support.py.
 
   (1) a sweep of parameter shapes: a random-word base vector, random int32 factors in three tables with a per-sample index, 1 .. 3 weighted
       inputs and a bias, at (p, q) = (2, 1), (16, 9), (64, 17), (8, 64): q off the eight waves of the cooperative kernel, q > 8, both limits
@@ -18,83 +18,19 @@ import pytest
 import lut_reference as R
 import mv_lut_reference as MV
 import oracle_lib as OL
+from support import KERNELS, N, SHAPES, differing, pmap, shape_env, shape_id, spread_index, thresholds, words
 
 pytestmark = pytest.mark.gpu
 
-N = 1024
-SHAPES = [  # (n, l, Bgbit, ks_t, ks_basebit), as test_gpu_lut_shapes.SHAPES
-    (24, 1, 8, 8, 2), (24, 2, 10, 8, 2), (37, 3, 7, 8, 2), (16, 4, 8, 5, 3), (33, 3, 6, 3, 5), (1, 2, 7, 15, 1), (64, 4, 4, 4, 4),
-]
-KERNELS = [  # (id, coop threshold, ring4 threshold, kernel that does most of a batch below 2 048), as test_gpu_lut_shapes.KERNELS
-    ("ring8", 0, 0, "sk_blind_rotate_ring_kernel<{l}>"),
-    ("ring4", 0, 1024, "sk_blind_rotate_ring_kernel<{l}, 4 waves>"),
-    ("coop", 1 << 20, 1024, "sk_blind_rotate_coop_kernel<{l}>"),
-    ("split", 6, 6, "sk_blind_rotate_ring_kernel<{l}, 4 waves>"),   # launch_br: 6 rotations on the four-wave ring + the rest cooperative
-]
 PQ = [(2, 1), (16, 9), (64, 17), (8, 64)]
 N_TABLES = 3
 # 11 jobs: the eight-wave ring's second workgroup holds 3, the four-wave ring's third holds 3, the split is 6 (4 + 2) + 5 cooperative
 COUNT = 11
 
 
-def shape_id(s):
-    return "n%d-l%d-Bg%d-ks%dx%d" % s
-
-
-def pmap(fn, items):
-    """independent model jobs on Python threads (ctypes and numpy drop the GIL)"""
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(8) as pool:
-        return list(pool.map(fn, items))
-
-
 @pytest.fixture(scope="module")
 def env(O):
-    """shape -> (params, keys, oracle, CloudKey), built once per shape and closed at the end of the module"""
-    import thfhe
-    made = {}
-
-    def get(shape):
-        if shape not in made:
-            n, l, Bgbit, t, bb = shape
-            kw = dict(n=n, N=N, k=1, l=l, Bgbit=Bgbit, ks_t=t, ks_basebit=bb, torus_bits=32, parties=1)
-            p = O.make_params(**kw)
-            K = O.SKKeys(p, 3000 + 7 * n + l, 2.0**-25, 2.0**-15)
-            made[shape] = (p, K, O.Oracle(p, K.bk, K.ksk), thfhe.CloudKey(thfhe.make_params(**kw), K.bk, K.ksk, device=0))
-        return made[shape]
-    yield get
-    for v in made.values():
-        v[3].close()
-
-
-class thresholds:
-    """the kernel choice of a case, restored on the way out"""
-    def __init__(self, ck, coop, ring4):
-        self.ck, self.coop, self.ring4 = ck, coop, ring4
-
-    def __enter__(self):
-        self.ck.set_coop_threshold(self.coop)
-        self.ck.set_ring4_threshold(self.ring4)
-
-    def __exit__(self, *exc):
-        self.ck.set_coop_threshold(768)
-        self.ck.set_ring4_threshold(1024)
-
-
-def words(rng, *shape):
-    return rng.integers(-2**31, 2**31, size=shape, dtype=np.int64).astype(np.int32)
-
-
-def spread_index(rng, count, n_tables):
-    """a per-sample table index that uses every table and differs between the two launches of the split case"""
-    idx = rng.permutation(np.arange(count) % n_tables).astype(np.int32)
-    assert len(set(idx.tolist())) == n_tables
-    return idx
-
-
-def differing(got, ref):
-    """(job, output, word) of the first mismatches, for the assertion message"""
-    return np.argwhere(got != ref)[:6].tolist()
+    yield from shape_env(O)
 
 
 def outputs_of(orc, accs, factors, idx):

@@ -5,17 +5,14 @@ import numpy as np
 import pytest
 
 from conftest import full_adder
+from support import sk128_cloud_key, thresholds, words
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def gpu128(O, sk128):
-    import thfhe
-    p, K, orc = sk128
-    ck = thfhe.CloudKey(thfhe.make_params("SK-128"), K.bk, K.ksk, device=0)
-    yield ck
-    ck.close()
+    yield from sk128_cloud_key(sk128)
 
 
 def enc(O, K, bits, seed, name="SK-128"):
@@ -64,14 +61,9 @@ def test_every_blind_rotate_kernel_bit_exact(O, sk128, gpu128):
     a = np.array([0, 1, 1, 0, 1, 0, 1, 1, 0, 0, 1, 0]); b = np.array([1, 1, 0, 0, 1, 0, 0, 1, 1, 0, 1, 1])
     ca, cb = enc(O, K, a, 45), enc(O, K, b, 46)
     ref = orc.gates(O.XOR, ca, cb)
-    try:
-        for coop, ring4 in ((0, 0), (0, 1024), (1 << 20, 1024), (5, 6)):     # (5, 6): 6 gates on the four-wave ring + 6 cooperative (12 <= ring4 + 256)
-            gpu128.set_coop_threshold(coop)
-            gpu128.set_ring4_threshold(ring4)
+    for coop, ring4 in ((0, 0), (0, 1024), (1 << 20, 1024), (5, 6)):     # (5, 6): 6 gates on the four-wave ring + 6 cooperative (12 <= ring4 + 256)
+        with thresholds(gpu128, coop, ring4):
             assert np.array_equal(gpu128.gates(thfhe.XOR, ca, cb), ref), (coop, ring4)   # partially filled workgroups in both ring shapes
-    finally:
-        gpu128.set_coop_threshold(768)
-        gpu128.set_ring4_threshold(1024)
 
 
 def test_mux_bit_exact(O, sk128, gpu128):
@@ -182,7 +174,7 @@ def test_full_batch_4096_properties(O, sk128, gpu128):
 
 def _check_keyswitch(O, ck, orc, p, batch, seed):
     rng = np.random.default_rng(seed)
-    u = rng.integers(-2**31, 2**31, (batch, p.N + 1), dtype=np.int64).astype(np.int32)
+    u = words(rng, batch, p.N + 1)
     u[0, :] = 0                      # every digit zero but the rounding offset's carry
     u[min(1, batch - 1), :] = -1     # all digits 3
     u[min(2, batch - 1), :] = 2**31 - 1

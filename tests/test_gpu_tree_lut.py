@@ -9,51 +9,19 @@ import pytest
 import lut_reference as R
 import pack_reference as PR
 import tree_lut_reference as TR
+from support import N, SIGMA, SIGMA_BK, dec_int, enc_int, pmap, sk128_cloud_key, sk128_pack, thresholds, words
 
 pytestmark = pytest.mark.gpu
-
-N = 1024
-SIGMA = 2.0**-15      # fresh-ciphertext noise of SK-128
-SIGMA_BK = 2.0**-25   # its ring noise: encrypted tables and the packing key
 
 
 @pytest.fixture(scope="module")
 def ck(sk128):
-    import thfhe
-    p, K, orc = sk128
-    c = thfhe.CloudKey(thfhe.make_params("SK-128"), K.bk, K.ksk, device=0)
-    yield c
-    c.close()
+    yield from sk128_cloud_key(sk128)
 
 
 @pytest.fixture(scope="module")
 def pack(sk128):
-    """(PolyContext, packing key): LWE key -> the BOOTSTRAPPING ring key of the same key set."""
-    from thfhe import keygen
-    from thfhe import threshold as T
-    p, K, orc = sk128
-    pk = keygen.gen_pack_key(np.random.default_rng(0x7EE0001), K.lwe_key, K.rlwe_key[0], p.ks_t, p.ks_basebit, SIGMA_BK)
-    pc = T.PolyContext(0)
-    pc.set_pack_key(pk, p.ks_t, p.ks_basebit)
-    yield pc, pk
-    pc.close()
-
-
-def pmap(fn, items):
-    """The model is ~0.6 s per SK-128 rotation on one core: independent samples run on Python threads (ctypes and numpy drop the GIL)."""
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(8) as pool:
-        return list(pool.map(fn, items))
-
-
-def enc_int(K, m, p, seed):
-    from thfhe import lut
-    return R.encrypt_words(K, lut.encode(np.asarray(m), p), SIGMA, seed)
-
-
-def dec_int(K, recs, p):
-    from thfhe import lut
-    return lut.decode(K.phases(recs), p)
+    yield from sk128_pack(sk128)
 
 
 def ring_phase_at0(K, u):
@@ -95,28 +63,23 @@ def test_enc_on_every_kernel_shape_with_random_words(sk128, ck):
     rng = np.random.default_rng(77)
     recs = [R.encrypt_words(K, rng.integers(-2**31, 2**31, 12), SIGMA, 1100 + q) for q in range(2)]
     weights, bias = (3, -5), int(rng.integers(-2**31, 2**31))
-    tv_a, tv_b = (rng.integers(-2**31, 2**31, (3, N)).astype(np.int32) for _ in range(2))
+    tv_a, tv_b = (words(rng, 3, N) for _ in range(2))
     idx = rng.integers(0, 3, 12).astype(np.int32)
     for theta in (1, 4):
         kw = dict(weights=weights, bias=bias, theta=theta, lut_index=idx)
         wo = np.stack(pmap(lambda g: TR.lut_enc(orc, [r[g] for r in recs], weights, bias, tv_a[idx[g]], tv_b[idx[g]], theta, keyswitch=False), range(12)))
         ks = np.stack([np.stack([orc.keyswitch(u) for u in s]) for s in wo])
-        try:
-            for coop, ring4 in ((0, 0), (0, 1024), (1 << 20, 1024), (5, 6)):
-                ck.set_coop_threshold(coop)
-                ck.set_ring4_threshold(ring4)
+        for coop, ring4 in ((0, 0), (0, 1024), (1 << 20, 1024), (5, 6)):
+            with thresholds(ck, coop, ring4):
                 assert np.array_equal(ck.lut_bootstrap_enc_wo_keyswitch(tv_a, tv_b, *recs, **kw), wo), (theta, coop, ring4)
                 assert np.array_equal(ck.lut_bootstrap_enc(tv_a, tv_b, *recs, **kw), ks), (theta, coop, ring4)
-        finally:
-            ck.set_coop_threshold(768)
-            ck.set_ring4_threshold(1024)
 
 
 def test_enc_zero_mask_is_the_plaintext_entry(sk128, ck):
     p, K, orc = sk128
     rng = np.random.default_rng(78)
     x = R.encrypt_words(K, rng.integers(-2**31, 2**31, 20), SIGMA, 1200)
-    tvs = rng.integers(-2**31, 2**31, (4, N)).astype(np.int32)
+    tvs = words(rng, 4, N)
     idx = rng.integers(0, 4, 20).astype(np.int32)
     for theta in (1, 2, 4):
         kw = dict(weights=(-3,), bias=99, theta=theta, lut_index=idx)
@@ -150,7 +113,7 @@ def test_pack_boxes_equals_the_model(sk128, pack, p_box, outs):
     p, K, orc = sk128
     pc, pk = pack
     rng = np.random.default_rng(p_box)
-    lwe = rng.integers(-2**31, 2**31, size=(p_box * outs, p.n + 1), dtype=np.int64).astype(np.int32)
+    lwe = words(rng, p_box * outs, p.n + 1)
     lwe[0, :p.n], lwe[-1, :p.n] = -2**31, 2**31 - 1
     a, b = T.PackBoxes(pc, lwe, p_box)
     ra, rb = TR.pack_boxes(lwe, pk, p.ks_t, p.ks_basebit, p_box)
@@ -299,7 +262,7 @@ def test_tree_three_lo_and_three_hi_operands_in_slices(sk128, ck, pack):
     pc, pk = pack
     rng = np.random.default_rng(90)
     count = 10
-    word = lambda *shape: rng.integers(-2**31, 2**31, shape, dtype=np.int64).astype(np.int32)
+    word = lambda *shape: words(rng, *shape)
     tv1 = word(2, 2, N)
     lo, hi = [word(count, p.n + 1) for _ in range(3)], [word(count, p.n + 1) for _ in range(3)]
     tab = rng.integers(0, 2, count).astype(np.int32)

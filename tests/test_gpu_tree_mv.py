@@ -14,52 +14,20 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import lut_reference as R
 import mv_lut_reference as MV
+from support import N, SIGMA_BK, dec_int, enc_int, pmap, sk128_cloud_key, sk128_pack, words
 
 pytestmark = pytest.mark.gpu
-
-N = 1024
-SIGMA = 2.0**-15      # fresh-ciphertext noise of SK-128
-SIGMA_BK = 2.0**-25   # its ring noise: the packing key
 
 
 @pytest.fixture(scope="module")
 def ck(sk128):
-    import thfhe
-    p, K, orc = sk128
-    c = thfhe.CloudKey(thfhe.make_params("SK-128"), K.bk, K.ksk, device=0)
-    yield c
-    c.close()
+    yield from sk128_cloud_key(sk128)
 
 
 @pytest.fixture(scope="module")
 def pack(sk128):
-    """(PolyContext, packing key): LWE key -> the BOOTSTRAPPING ring key of the same key set."""
-    from thfhe import keygen
-    from thfhe import threshold as T
-    p, K, orc = sk128
-    pk = keygen.gen_pack_key(np.random.default_rng(0x7EE0001), K.lwe_key, K.rlwe_key[0], p.ks_t, p.ks_basebit, SIGMA_BK)
-    pc = T.PolyContext(0)
-    pc.set_pack_key(pk, p.ks_t, p.ks_basebit)
-    yield pc, pk
-    pc.close()
-
-
-def pmap(fn, items):
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(8) as pool:
-        return list(pool.map(fn, items))
-
-
-def enc_int(K, m, p, seed):
-    from thfhe import lut
-    return R.encrypt_words(K, lut.encode(np.asarray(m), p), SIGMA, seed)
-
-
-def dec_int(K, recs, p):
-    from thfhe import lut
-    return lut.decode(K.phases(recs), p)
+    yield from sk128_pack(sk128)
 
 
 def compose(ck, pc, tv0, w, lo, hi, w_lo=(1,), b_lo=0, w_hi=(1,), b_hi=0, table_index=None):
@@ -133,7 +101,7 @@ def test_slices_table_index_and_weighted_operands(sk128, ck, pack):
     pc, pk = pack
     rng = np.random.default_rng(4300)
     count = 13
-    word = lambda *shape: rng.integers(-2**31, 2**31, shape, dtype=np.int64).astype(np.int32)
+    word = lambda *shape: words(rng, *shape)
     tv0, w = word(N), word(3, 4, 16)                              # p_hi = 4 candidates of p_lo = 16 taps
     lo, hi = [word(count, p.n + 1) for _ in range(2)], [word(count, p.n + 1) for _ in range(3)]
     tab = rng.integers(0, 3, count).astype(np.int32)

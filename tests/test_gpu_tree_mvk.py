@@ -1,7 +1,7 @@
 """The k-output two-digit tree with a multi-value level 1 on the MI355X (pytest -m gpu): thfhe_tree_lut_bootstrap_mvk
 word for word against the three public calls in a row (thfhe_mv_lut_bootstrap at q = k p_hi -> thfhe_pack_boxes -> thfhe_lut_bootstrap_enc with
 every sample's `hi` operands repeated k times), against thfhe_tree_lut_bootstrap_mv at k = 1, and against the model composed from the CPU oracle
-(tree_mvk_reference.py) on a sample of jobs.  The reduced key shapes and threshold pairs are those of test_gpu_lut_shapes.py.
+(tree_mvk_reference.py) on a sample of jobs.  The reduced key shapes and threshold pairs are those of support.py.
 
 Word-for-word cases use random int32 taps and random-word base vectors and inputs.  The one decrypting case is inside DESIGN 4.13's supported
 set: SK-128, bit-valued tables (p_out = 2) at p_hi = p_lo = 8, |c|_2 <= 3.4.
@@ -13,91 +13,30 @@ import numpy as np
 import pytest
 
 import lut_reference as R
+import support
 import tree_mvk_reference as TK
+from support import KERNELS, N, SIGMA, SIGMA_BK, shape_env, shape_id, sk128_cloud_key, sk128_pack, thresholds, words
 
 pytestmark = pytest.mark.gpu
 
-N = 1024
-SIGMA = 2.0**-15      # fresh-ciphertext noise of SK-128
-SIGMA_BK = 2.0**-25   # its ring noise: the packing key
-SHAPES = [(24, 1, 8, 8, 2), (24, 2, 10, 8, 2), (37, 3, 7, 8, 2), (16, 4, 8, 5, 3)]   # (n, l, Bgbit, ks_t, ks_basebit): test_gpu_lut_shapes.SHAPES at l = 1 .. 4
-KERNELS = [  # (id, coop threshold, ring4 threshold, kernel that does most of a batch below 2 048), as test_gpu_lut_shapes.KERNELS
-    ("ring8", 0, 0, "sk_blind_rotate_ring_kernel<{l}>"),
-    ("ring4", 0, 1024, "sk_blind_rotate_ring_kernel<{l}, 4 waves>"),
-    ("coop", 1 << 20, 1024, "sk_blind_rotate_coop_kernel<{l}>"),
-    ("split", 6, 6, "sk_blind_rotate_ring_kernel<{l}, 4 waves>"),
-]
+SHAPES = support.SHAPES[:4]   # (n, l, Bgbit, ks_t, ks_basebit) at l = 1 .. 4
 CASES = [(2, 2, 1), (4, 8, 3), (8, 8, 4), (2, 64, 32), (64, 2, 1)]   # (p_hi, p_lo, k): smallest and largest q, q = 64 both ways, k = 1, k no power of two
 COUNT = 11
 
 
-def shape_id(s):
-    return "n%d-l%d-Bg%d-ks%dx%d" % s
-
-
-def words(rng, *shape):
-    return rng.integers(-2**31, 2**31, size=shape, dtype=np.int64).astype(np.int32)
-
-
-def make_pack(K, p, seed):
-    from thfhe import keygen
-    from thfhe import threshold as T
-    pk = keygen.gen_pack_key(np.random.default_rng(seed), K.lwe_key, K.rlwe_key[0], p.ks_t, p.ks_basebit, SIGMA_BK)
-    pc = T.PolyContext(0)
-    pc.set_pack_key(pk, p.ks_t, p.ks_basebit)
-    return pc, pk
-
-
 @pytest.fixture(scope="module")
 def ck(sk128):
-    import thfhe
-    p, K, orc = sk128
-    c = thfhe.CloudKey(thfhe.make_params("SK-128"), K.bk, K.ksk, device=0)
-    yield c
-    c.close()
+    yield from sk128_cloud_key(sk128)
 
 
 @pytest.fixture(scope="module")
 def pack(sk128):
-    """(PolyContext, packing key): LWE key -> the BOOTSTRAPPING ring key of the same key set."""
-    p, K, orc = sk128
-    pc, pk = make_pack(K, p, 0x7EE0001)
-    yield pc, pk
-    pc.close()
+    yield from sk128_pack(sk128)
 
 
 @pytest.fixture(scope="module")
 def env(O):
-    """shape -> (params, keys, oracle, CloudKey, PolyContext, packing key), built once per shape"""
-    import thfhe
-    made = {}
-
-    def get(shape):
-        if shape not in made:
-            n, l, Bgbit, t, bb = shape
-            kw = dict(n=n, N=N, k=1, l=l, Bgbit=Bgbit, ks_t=t, ks_basebit=bb, torus_bits=32, parties=1)
-            p = O.make_params(**kw)
-            K = O.SKKeys(p, 3000 + 7 * n + l, 2.0**-25, 2.0**-15)
-            made[shape] = (p, K, O.Oracle(p, K.bk, K.ksk), thfhe.CloudKey(thfhe.make_params(**kw), K.bk, K.ksk, device=0)) + make_pack(K, p, 5000 + n)
-        return made[shape]
-    yield get
-    for v in made.values():
-        v[3].close()
-        v[4].close()
-
-
-class thresholds:
-    """the kernel choice of a case, restored on the way out"""
-    def __init__(self, ck, coop, ring4):
-        self.ck, self.coop, self.ring4 = ck, coop, ring4
-
-    def __enter__(self):
-        self.ck.set_coop_threshold(self.coop)
-        self.ck.set_ring4_threshold(self.ring4)
-
-    def __exit__(self, *exc):
-        self.ck.set_coop_threshold(768)
-        self.ck.set_ring4_threshold(1024)
+    yield from shape_env(O, with_pack=True)
 
 
 def compose(ck, pc, tv0, w, lo, hi, w_lo=(1,), b_lo=0, w_hi=(1,), b_hi=0, table_index=None):

@@ -8,12 +8,9 @@ import pytest
 
 import lhe_reference as LR
 import lut_reference as R
+from support import words
 
 N = 1024
-
-
-def words(rng, *shape):
-    return rng.integers(-2**31, 2**31, size=shape, dtype=np.int64).astype(np.int32)
 
 
 @pytest.fixture(scope="module")

@@ -13,7 +13,7 @@ import lhe_reference as LR
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 1024
 i32p = C.POINTER(C.c_int32)
-SHAPES = [(1, 8), (2, 10), (3, 7), (4, 8), (3, 6), (2, 7), (4, 4)]   # (l, Bgbit) of test_gpu_lut_shapes.SHAPES
+SHAPES = [(1, 8), (2, 10), (3, 7), (4, 8), (3, 6), (2, 7), (4, 4)]   # (l, Bgbit) of support.SHAPES
 
 
 @pytest.fixture(scope="module")

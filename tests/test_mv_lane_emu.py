@@ -10,6 +10,7 @@ import pytest
 
 import lut_reference as R
 import mv_lut_reference as MV
+from support import words
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 1024
@@ -24,10 +25,6 @@ def emu(tmp_path_factory):
     L.mv_emu_init.argtypes = [i32p, C.c_int, i32p]
     L.mv_emu_extract.argtypes = [i32p, i32p, C.c_int, C.c_int, i32p]
     return L
-
-
-def words(rng, *shape):
-    return rng.integers(-2**31, 2**31, size=shape, dtype=np.int64).astype(np.int32)
 
 
 @pytest.mark.parametrize("p", [2, 4, 8, 16, 32, 64])
