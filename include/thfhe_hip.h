@@ -444,6 +444,40 @@ int thfhe_lhe_lookup_wo_keyswitch(thfhe_ctx *ctx, const thfhe_tgsw_set *set, siz
                                   const int32_t *tab_a, const int32_t *tab_b /*[n_tables][2^d_tree][N]*/, int n_tables, const int32_t *table_index,
                                   int32_t *out_N1);
 
+/* ---- layered automata on TGSW-encrypted bits (single key, N = 1024): one CMux per state and input bit, whatever the number of bits.
+ * A deterministic automaton (or a layered decision diagram) of n_states <= 64 states reads n_steps <= 4096 encrypted bits; its final weights are
+ * TLWE samples.  Noise grows as sqrt(steps) sigma_1, so comparisons, equality and threshold tests of wide numbers and pattern matches over some
+ * hundred bits need no bootstrap.
+ *
+ * thfhe_lhe_wfa(_wo_keyswitch): sets: HOST array of n_sets (1 .. 64) sets of ONE context and ONE count (thfhe_tgsw_set_create; each holds at most 16
+ *   bits per sample, the array is what reaches past 16); the samples first .. first+count-1 of every set are read.
+ *   trans: HOST int32[n_steps][n_states][2], entries in 0 .. n_states-1: trans[j][q][b] is the state that q moves to when the bit of step j is b.
+ *   step_bit: HOST int32[n_steps]: step j reads bit (step_bit[j] & 15) of set (step_bit[j] >> 4); any order, any bit more than once.
+ *   fin_b: HOST int32[n_tables][n_states][N], the final weight of every state (thfhe.lut.wfa_finals); fin_a: their masks, or NULL for trivial
+ *   samples (0, fin_b); n_tables n_states <= 262144; table_index: HOST int32[count] or NULL (table 0).  start: HOST int32[n_out], 1 <= n_out <= 64.
+ *   Per sample s, with V_(n_steps)[q] = final weight q of its table, for j = n_steps-1 .. 0:
+ *       V_j[q] = V_(j+1)[t0] + C_(s, step_bit[j]) (.) (V_(j+1)[t1] - V_(j+1)[t0]),   (t0, t1) = trans[j][q]
+ *   -- thfhe_lhe_cmux's d0 + C (.) (d1 - d0), the same decomposition, words and transforms; where t0 == t1 the state is copied: no product, no noise.
+ *   Output (s, o, j) is the extraction of V_0[start[o]] at coefficient j < theta, theta in {1, 2, 4}.  Exact integers, as thfhe_lhe_cmux.
+ *   out: HOST int32[count][n_out][theta][n+1] (key-switched) or int32[count][n_out][theta][N+1] (_wo_keyswitch).
+ *   One kernel launch per step; the batch runs in slices of at most max(1, max_candidates / (2 n_states)) samples (thfhe_set_tree_slice: two layers
+ *   of n_states TLWE samples per sample), at most max(1, max_candidates / (n_out theta)) samples (the output records of a slice) and 65 535 samples.
+ *   THFHE_E_INVALID, in this order: on the host, before any set or context is looked at, null pointers, the limits above, a trans, start or
+ *   table_index entry out of range; then a null set, a step_bit naming a set >= n_sets or a bit >= that set's d, sets of differing count or
+ *   context, samples outside the sets; then a NULL context or a set of another context.  count 0 returns THFHE_OK once those have passed.
+ *
+ * thfhe_set_wfa_chunk: states per workgroup of a step, 1 .. 64, or 0 (the default): the largest number for which the launch still gives every
+ *   compute unit a workgroup.  A workgroup loads the spectra of its sample's bit once for all its states (l <= 3; at l = 4 per state, from the
+ *   lines it has just read).  No output word depends on it. */
+int thfhe_lhe_wfa(thfhe_ctx *ctx, const thfhe_tgsw_set *const *sets, int n_sets, size_t first, size_t count, int n_steps, int n_states,
+                  const int32_t *trans /*[n_steps][n_states][2]*/, const int32_t *step_bit /*[n_steps]*/, const int32_t *fin_a,
+                  const int32_t *fin_b /*[n_tables][n_states][N]*/, int n_tables, const int32_t *table_index, int theta, const int32_t *start /*[n_out]*/,
+                  int n_out, int32_t *out);
+int thfhe_lhe_wfa_wo_keyswitch(thfhe_ctx *ctx, const thfhe_tgsw_set *const *sets, int n_sets, size_t first, size_t count, int n_steps, int n_states,
+                               const int32_t *trans, const int32_t *step_bit, const int32_t *fin_a, const int32_t *fin_b, int n_tables,
+                               const int32_t *table_index, int theta, const int32_t *start, int n_out, int32_t *out_N1);
+int thfhe_set_wfa_chunk(thfhe_ctx *ctx, int g);
+
 /* ---- encrypted-table, select and tree nodes in the gate-DAG executor (single key): thfhe_dag_run_lut_batch with three more node
  * kinds, so that a circuit needing a private table, an oblivious pick or a 6-bit -> 3-bit function does not leave the device-resident wire table.
  * nodes: HOST int32[n_nodes][6] = (opcode, in0, in1, in2, x, y); row g defines wire n_inputs + g.  Gate rows, THFHE_LUT and THFHE_LUT_OUT rows mean

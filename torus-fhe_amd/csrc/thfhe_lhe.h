@@ -2,6 +2,8 @@
 // thfhe_tgsw_set_create, thfhe_lhe_cmux and thfhe_lhe_lookup(_wo_keyswitch).  Included by thfhe_sk.hip INSIDE its second anonymous namespace, after
 // thfhe_ctx, the cooperative blind-rotate kernel (whose barriers and phases it reuses) and enqueue_keyswitch.
 //
+// Also the layered automata of DESIGN 4.16, thfhe_lhe_wfa(_wo_keyswitch): sk_lhe_wfa_step_kernel and its host side, further down.
+//
 // Data flow.  The blind-rotate kernels share ONE key stream among all jobs and give every job its own rotation amounts.  Here every job has its OWN
 // TGSW spectra (the address bits of its sample, 2l x 32 KiB per bit) and the rotation amounts are public: X^(2N - box 2^i) for address bit i.  Nothing
 // is shared between workgroups, so both kernels are the cooperative kernel's shape -- one job per 512-thread workgroup, accumulator and the 2l digit
@@ -197,6 +199,98 @@ __global__ __launch_bounds__(512, 2) void sk_lhe_cmux_kernel(LheCmuxArgs a) {
     }
 }
 
+// ---- layered automata on TGSW-encrypted bits: thfhe_lhe_wfa(_wo_keyswitch) ---------------------------------------------------------
+constexpr int kWfaMaxSets = 64, kWfaMaxSteps = 4096, kWfaMaxStates = 64, kWfaMaxOut = 64;
+
+// arguments of sk_lhe_wfa_step_kernel, grid (ceil(n_states / chunk), samples): one step of the automaton for every state of the workgroup's chunk,
+//   layer_j(s, q) = src(s, t0) + C_(s,bit) (.) (src(s, t1) - src(s, t0)),  (t0, t1) = trans[q],   a copy of src(s, t0) where t0 == t1.
+// src is layer j+1, or the finals at the last step: state t of sample s at word index(s) * src_sample + t * src_state of src_a (masks; PUB: not read,
+// zero) and src_b (bodies), index(s) = src_idx[s] or s.  dst is layer j, [samples][n_states][mask | body] of N words each, never the buffer of src:
+// a state of layer j+1 is read by every state that moves to it.
+struct LheWfaArgs {
+    const cplx *spec;   // spectra of the step's set, at the first sample of the launch
+    const cplx *tw;
+    const int32_t *src_a, *src_b;
+    int32_t *dst;
+    const int32_t *src_idx;   // [samples] or null
+    const int32_t *trans;     // the step's [n_states][2], validated on the host
+    size_t src_sample, src_state;
+    int d, bit, Bgbit, n_states, chunk;
+};
+
+// The workgroup keeps the spectra of its sample's TGSW sample of the step in registers and walks its chunk of states: per CMux only the two
+// TLWE operands (16 KiB) come from memory, the 2l x 32 KiB of spectra once per workgroup.  The transitions are public, so the copy branch is
+// wave-uniform and skips the barriers of the CMux as a whole workgroup.
+template <int L, bool PUB>
+__global__ __launch_bounds__(512, 2) void sk_lhe_wfa_step_kernel(LheWfaArgs a) {
+    constexpr int ROWS = 2 * L;
+    __shared__ __attribute__((aligned(4096))) int32_t sAcc[2048];
+    __shared__ int32_t sD1[2048];
+    __shared__ cplx sSpec[ROWS][512];
+    __shared__ cplx sX[8][kXbufSlots];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
+    const LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
+    const size_t s = blockIdx.y;
+    const int q0 = blockIdx.x * a.chunk, q1 = q0 + a.chunk < a.n_states ? q0 + a.chunk : a.n_states;   // the last chunk may be ragged
+    const size_t in = (a.src_idx ? (size_t)a.src_idx[s] : s) * a.src_sample;
+    int32_t *const dst = a.dst + s * a.n_states * 2048;
+    // l <= 3 (HOLD): the wave's chunks of the spectra stay in registers for all the states of the chunk.  l = 4: the four rows (128 registers) do not
+    // fit next to the inverse transform, so this instantiation does not share them: every CMux requests its rows itself, as sk_lhe_cmux_kernel
+    // does, and they are dead after its multiply.  After the chunk's first state these requests hit the lines the workgroup has just read.
+    constexpr bool HOLD = L <= 3;
+    const cplx *const key = a.spec + (s * a.d + a.bit) * ((size_t)ROWS * 2048);
+    cplx B[L][8];
+    if constexpr (HOLD) lhe_load_spectra<L, PUB>(lane, wave, B, key);
+#pragma unroll 1
+    for (int q = q0; q < q1; q++) {
+        // The lane index and the lane's roots behind an empty asm: what the transforms derive from them (the swizzled LDS slot maps, the powers
+        // of the roots: 80 registers) is rebuilt inside the state.  Hoisted out of the loop it would sit next to the spectra and spill at l = 3 too.
+        const int ln = opaque_lane(lane);
+        W64 w = w64;
+        LaneRoots r = roots;
+        asm volatile("" : "+v"(w.w1.re), "+v"(w.w1.im), "+v"(r.b.re), "+v"(r.b.im), "+v"(r.s.re), "+v"(r.s.im));
+        const int t0 = __builtin_amdgcn_readfirstlane(a.trans[2 * q]), t1 = __builtin_amdgcn_readfirstlane(a.trans[2 * q + 1]);
+        const size_t i0 = in + t0 * a.src_state, i1 = in + t1 * a.src_state;
+        int32_t *const o = dst + (size_t)q * 2048;
+        if (t0 == t1) {   // both bit values lead to one state: no product, no noise
+            for (int x = threadIdx.x; x < 1024; x += 512) {
+                o[x] = PUB ? 0 : a.src_a[i0 + x];
+                o[1024 + x] = a.src_b[i0 + x];
+            }
+            continue;
+        }
+        for (int x = threadIdx.x; x < 1024; x += 512) {   // the slots this thread read out at the end of the previous state
+            sAcc[x] = PUB ? 0 : a.src_a[i0 + x];
+            sD1[x] = PUB ? 0 : a.src_a[i1 + x];
+            sAcc[1024 + x] = a.src_b[i0 + x];
+            sD1[1024 + x] = a.src_b[i1 + x];
+        }
+        if constexpr (!HOLD) lhe_load_spectra<L, false>(ln, wave, B, key);   // PUB too: rows left unloaded in half the waves made the compiler carry B round the loop
+        wg_barrier();
+        lhe_cmux_step<L, false, PUB, false>(ln, wave, sAcc, sD1, sSpec, sX, B, nullptr, nullptr, 0, a.Bgbit, r, w);
+        for (int x = threadIdx.x; x < 1024; x += 512) {
+            o[x] = sAcc[x];
+            o[1024 + x] = sAcc[1024 + x];
+        }
+    }
+}
+
+// the outputs of the automaton: record (s, o, j) is the extraction at coefficient j of state start[o] of layer 0; grid (n_out theta, samples), one wave
+struct LheWfaOutArgs {
+    const int32_t *layer;   // [samples][n_states][mask | body]
+    const int32_t *start;   // [n_out], validated on the host
+    int32_t *out;           // [samples][n_out][theta][N+1]
+    int n_states, n_out, theta;
+};
+__global__ __launch_bounds__(64) void sk_lhe_wfa_extract_kernel(LheWfaOutArgs a) {
+    const int lane = threadIdx.x, o = blockIdx.x / a.theta, j = blockIdx.x % a.theta;
+    const size_t s = blockIdx.y;
+    const int32_t *const v = a.layer + (s * a.n_states + a.start[o]) * 2048;
+    extract_at16(lane, v, v + 1024, j, a.out + ((s * a.n_out + o) * a.theta + j) * 1025);
+}
+
 template <int L>
 void launch_lhe_cmux_l(const LheCmuxArgs &a, size_t pairs, size_t samples, bool pub, hipStream_t s) {
     const dim3 grid((unsigned)pairs, (unsigned)samples);
@@ -221,6 +315,24 @@ int launch_lhe_rotate(thfhe_ctx *c, const LheRotArgs &a, size_t jobs) {
     case 2: hipLaunchKernelGGL(sk_lhe_rotate_kernel<2>, grid, block, 0, c->stream, a); break;
     case 3: hipLaunchKernelGGL(sk_lhe_rotate_kernel<3>, grid, block, 0, c->stream, a); break;
     case 4: hipLaunchKernelGGL(sk_lhe_rotate_kernel<4>, grid, block, 0, c->stream, a); break;
+    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
+    }
+    THFHE_HIP(hipGetLastError());
+    return THFHE_OK;
+}
+template <int L>
+void launch_lhe_wfa_l(const LheWfaArgs &a, size_t chunks, size_t samples, bool pub, hipStream_t s) {
+    const dim3 grid((unsigned)chunks, (unsigned)samples);
+    if (pub) hipLaunchKernelGGL((sk_lhe_wfa_step_kernel<L, true>), grid, dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((sk_lhe_wfa_step_kernel<L, false>), grid, dim3(512), 0, s, a);
+}
+int launch_lhe_wfa(thfhe_ctx *c, const LheWfaArgs &a, size_t samples, bool pub) {
+    const size_t chunks = ((size_t)a.n_states + a.chunk - 1) / a.chunk;
+    switch (c->p.l) {
+    case 1: launch_lhe_wfa_l<1>(a, chunks, samples, pub, c->stream); break;
+    case 2: launch_lhe_wfa_l<2>(a, chunks, samples, pub, c->stream); break;
+    case 3: launch_lhe_wfa_l<3>(a, chunks, samples, pub, c->stream); break;
+    case 4: launch_lhe_wfa_l<4>(a, chunks, samples, pub, c->stream); break;
     default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
     }
     THFHE_HIP(hipGetLastError());
@@ -359,6 +471,110 @@ int lhe_lookup(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t cou
             c->ev_valid = true;
         }
         THFHE_HIP(hipMemcpyAsync(out + s0 * theta * rec, res, S * theta * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
+}
+
+// states per workgroup of a step on S samples: the forced value (thfhe_set_wfa_chunk), else the largest for which ceil(n_states / G) S workgroups
+// still give every compute unit one -- all the states of a sample once S reaches the number of compute units
+int wfa_chunk_for(const thfhe_ctx *c, int n_states, size_t S, int cus) {
+    if (c->wfa_chunk) return std::min(c->wfa_chunk, n_states);
+    for (int g = n_states; g > 1; g--)
+        if ((size_t)((n_states + g - 1) / g) * S >= (size_t)cus) return g;
+    return 1;
+}
+
+// thfhe_lhe_wfa (keyswitch) / thfhe_lhe_wfa_wo_keyswitch: out = count x n_out x theta records of n+1 (resp. N+1) words.  One launch per step on the
+// context's stream: step j reads layer j+1 (the finals at j = n_steps-1) and writes layer j, the layers alternating between d_lhe_a and d_lhe_b,
+// layer j in buffer j & 1, so layer 0 -- the one the outputs are extracted from -- is always in d_lhe_a.
+int lhe_wfa(thfhe_ctx *c, const thfhe_tgsw_set *const *sets, int n_sets, size_t first, size_t count, int n_steps, int n_states, const int32_t *trans,
+            const int32_t *step_bit, const int32_t *fin_a, const int32_t *fin_b, int n_tables, const int32_t *table_index, int theta, const int32_t *start,
+            int n_out, int32_t *out, bool keyswitch) {
+    // host checks, before any set or context is looked at
+    if (!sets || !trans || !step_bit || !fin_b || !start || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (n_sets < 1 || n_sets > kWfaMaxSets) return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: n_sets must be 1 .. 64");
+    if (n_steps < 1 || n_steps > kWfaMaxSteps) return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: n_steps must be 1 .. 4096");
+    if (n_states < 1 || n_states > kWfaMaxStates) return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: n_states must be 1 .. 64");
+    if (n_out < 1 || n_out > kWfaMaxOut) return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: n_out must be 1 .. 64");
+    if (theta != 1 && theta != 2 && theta != 4) return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: theta must be 1, 2 or 4");
+    if (n_tables < 1 || (long)n_tables * n_states > kMaxEncLuts) return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: n_tables n_states must be 1 .. 262144");
+    const size_t n_trans = (size_t)n_steps * n_states * 2;
+    for (size_t i = 0; i < n_trans; i++)
+        if (trans[i] < 0 || trans[i] >= n_states) return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: trans entry out of range (0 .. n_states-1)");
+    for (int o = 0; o < n_out; o++)
+        if (start[o] < 0 || start[o] >= n_states) return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: start entry out of range (0 .. n_states-1)");
+    THFHE_TRY(tree_validate_index(table_index, n_tables, count));
+    // the sets
+    for (int i = 0; i < n_sets; i++)
+        if (!sets[i]) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
+    for (int j = 0; j < n_steps; j++)
+        if (step_bit[j] < 0 || (step_bit[j] >> 4) >= n_sets || (step_bit[j] & 15) >= sets[step_bit[j] >> 4]->d)
+            return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: step_bit must name bit 0 .. d-1 of set 0 .. n_sets-1 (16 set + bit)");
+    for (int i = 1; i < n_sets; i++)
+        if (sets[i]->count != sets[0]->count || sets[i]->ctx != sets[0]->ctx)
+            return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: the sets must have one count and one context");
+    THFHE_TRY(lhe_validate_range(sets[0], first, count));
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (c != sets[0]->ctx) return thfhe_fail(THFHE_E_INVALID, "lhe: the set belongs to another context");
+    if (count == 0) return THFHE_OK;
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    int cus = 0;
+    THFHE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    // a slice: two layers of n_states TLWE samples per sample within the tree workspace's bound, at most tree_slice output records, one grid.y
+    const size_t recs = (size_t)n_out * theta;
+    const size_t S_max = std::min({count, (size_t)65535, std::max<size_t>(1, c->tree_slice / (2 * (size_t)n_states)), std::max<size_t>(1, c->tree_slice / recs)});
+    const size_t words = c->p.n + 1, rec = keyswitch ? words : 1025, fin_bytes = (size_t)n_tables * n_states * 4096;
+    const size_t layer_words = (size_t)n_states * 2048, tab_bytes = (n_trans + n_out) * sizeof(int32_t);
+    int rc = c->d_tv.grow(fin_bytes);
+    if (!rc && fin_a) rc = c->d_tva.grow(fin_bytes);
+    if (!rc) rc = c->d_lhe_a.grow(S_max * layer_words * sizeof(int32_t));
+    if (!rc) rc = c->d_lhe_b.grow(S_max * layer_words * sizeof(int32_t));
+    if (!rc) rc = c->d_wfa_tab.grow(tab_bytes);
+    if (!rc) rc = c->d_u.grow(S_max * recs * 1025 * sizeof(int32_t));
+    if (!rc && keyswitch) rc = c->stage.grow(S_max * recs * words);
+    if (!rc && table_index) rc = c->d_lut_idx.grow(S_max * sizeof(int32_t));
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), fin_b, fin_bytes, hipMemcpyHostToDevice, st));
+    if (fin_a) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int32_t>(), fin_a, fin_bytes, hipMemcpyHostToDevice, st));
+    int32_t *const d_trans = c->d_wfa_tab.as<int32_t>(), *const d_start = d_trans + n_trans;
+    THFHE_HIP(hipMemcpyAsync(d_trans, trans, n_trans * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    THFHE_HIP(hipMemcpyAsync(d_start, start, n_out * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    int32_t *const layer[2] = {c->d_lhe_a.as<int32_t>(), c->d_lhe_b.as<int32_t>()};
+    int32_t *const res = keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>();
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0);
+        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[0], st));
+        const int chunk = wfa_chunk_for(c, n_states, S, cus);
+        for (int j = n_steps - 1; j >= 0; j--) {
+            const thfhe_tgsw_set *set = sets[step_bit[j] >> 4];
+            LheWfaArgs a{set->spec.as<cplx>() + (first + s0) * lhe_sample_slots(c, set->d), c->d_tw.as<cplx>(), nullptr, nullptr, layer[j & 1], nullptr,
+                         d_trans + (size_t)j * n_states * 2, 0, 0, set->d, step_bit[j] & 15, c->p.Bgbit, n_states, chunk};
+            const bool last = j == n_steps - 1;   // the first launch: it reads the finals, of the sample's table if there is an index
+            if (last) {
+                a.src_a = fin_a ? c->d_tva.as<int32_t>() : nullptr, a.src_b = c->d_tv.as<int32_t>();
+                a.src_idx = table_index ? c->d_lut_idx.as<int32_t>() : nullptr;
+                a.src_sample = table_index ? (size_t)n_states * 1024 : 0, a.src_state = 1024;
+            } else {
+                a.src_a = layer[(j + 1) & 1], a.src_b = a.src_a + 1024;
+                a.src_sample = layer_words, a.src_state = 2048;
+            }
+            THFHE_TRY(launch_lhe_wfa(c, a, S, last && !fin_a));
+        }
+        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[1], st));
+        const LheWfaOutArgs x{layer[0], d_start, c->d_u.as<int32_t>(), n_states, n_out, theta};
+        hipLaunchKernelGGL(sk_lhe_wfa_extract_kernel, dim3((unsigned)recs, (unsigned)S), dim3(64), 0, st, x);
+        THFHE_HIP(hipGetLastError());
+        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[2], st));
+        if (keyswitch) THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), S * recs, 1, false));
+        if (c->profiling && s0 == 0) {
+            THFHE_HIP(hipEventRecord(c->ev[3], st));
+            c->ev_valid = true;
+        }
+        THFHE_HIP(hipMemcpyAsync(out + s0 * recs * rec, res, S * recs * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     THFHE_HIP(hipStreamSynchronize(st));
     return THFHE_OK;

@@ -511,6 +511,9 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     DevBuf d_dag_mv_tv0, d_dag_mv_w;
     // leveled lookup (thfhe_lhe_cmux, thfhe_lhe_lookup): the CMux tree's workspace (masks, bodies) and the flat CMux's four operands
     DevBuf d_lhe_a, d_lhe_b, d_lhe_in[4];
+    // layered automata (thfhe_lhe_wfa): the two layers alternate between d_lhe_a and d_lhe_b; the transition table and the start states
+    DevBuf d_wfa_tab;
+    int wfa_chunk = 0;   // states per workgroup of sk_lhe_wfa_step_kernel, 0: chosen per slice (wfa_chunk_for)
     size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate); also the output records (samples x q) per slice of thfhe_mv_lut_bootstrap
     // staging for the host-buffer API
     Stage stage;
@@ -1397,6 +1400,26 @@ int thfhe_lhe_lookup(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size
 int thfhe_lhe_lookup_wo_keyswitch(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta,
                                   const int32_t *tab_a, const int32_t *tab_b, int n_tables, const int32_t *table_index, int32_t *out_N1) {
     return lhe_lookup(c, set, first, count, d_tree, d_rot, theta, tab_a, tab_b, n_tables, table_index, out_N1, false);
+}
+
+int thfhe_set_wfa_chunk(thfhe_ctx *c, int g) {
+    if (!c || g < 0 || g > kWfaMaxStates) return thfhe_fail(THFHE_E_INVALID, "wfa chunk must be 0 (automatic) or 1 .. 64 states");
+    std::lock_guard<std::mutex> lg(c->mu);
+    c->wfa_chunk = g;
+    return THFHE_OK;
+}
+
+int thfhe_lhe_wfa(thfhe_ctx *c, const thfhe_tgsw_set *const *sets, int n_sets, size_t first, size_t count, int n_steps, int n_states, const int32_t *trans,
+                  const int32_t *step_bit, const int32_t *fin_a, const int32_t *fin_b, int n_tables, const int32_t *table_index, int theta,
+                  const int32_t *start, int n_out, int32_t *out) {
+    return lhe_wfa(c, sets, n_sets, first, count, n_steps, n_states, trans, step_bit, fin_a, fin_b, n_tables, table_index, theta, start, n_out, out, true);
+}
+
+int thfhe_lhe_wfa_wo_keyswitch(thfhe_ctx *c, const thfhe_tgsw_set *const *sets, int n_sets, size_t first, size_t count, int n_steps, int n_states,
+                               const int32_t *trans, const int32_t *step_bit, const int32_t *fin_a, const int32_t *fin_b, int n_tables,
+                               const int32_t *table_index, int theta, const int32_t *start, int n_out, int32_t *out_N1) {
+    return lhe_wfa(c, sets, n_sets, first, count, n_steps, n_states, trans, step_bit, fin_a, fin_b, n_tables, table_index, theta, start, n_out, out_N1,
+                   false);
 }
 
 }  // extern "C"

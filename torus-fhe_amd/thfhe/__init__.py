@@ -206,6 +206,11 @@ SIGNATURES = {
     "thfhe_lhe_cmux": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_lhe_lookup": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p]),
     "thfhe_lhe_lookup_wo_keyswitch": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p]),
+    "thfhe_lhe_wfa": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, _i32p, C.c_int,
+                                _i32p, C.c_int, _i32p]),
+    "thfhe_lhe_wfa_wo_keyswitch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, _i32p,
+                                             C.c_int, _i32p, C.c_int, _i32p]),
+    "thfhe_set_wfa_chunk": (C.c_int, [_vp, C.c_int]),
     "thfhe_dev_alloc": (_vp, [_vp, C.c_size_t]),
     "thfhe_dev_free": (None, [_vp, _vp]),
     "thfhe_copy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
@@ -806,6 +811,59 @@ class CloudKey(_EvalKey):
         _check(fn(self.h, tset.h, first, count, int(d_tree), int(d_rot), int(theta), _p32(tab_a), _p32(tab_b), tab_b.size // (leaves * N), _p32(idx),
                   _p32(out)))
         return out
+
+    # -- layered automata on TGSW-encrypted bits (thfhe_lhe_wfa) ------------------------------------------------------------------
+    def lhe_wfa(self, sets, trans, step_bit, fin_b, start, *, theta=1, fin_a=None, table_index=None, first=0, count=None):
+        """Evaluate a layered automaton on samples first .. first+count-1 of `sets` (a list of TgswSet of this key with one count; step j reads
+        bit step_bit[j] & 15 of set step_bit[j] >> 4): trans int32[n_steps][n_states][2], fin_b int32[n_tables][n_states][N] the final weights
+        (thfhe.lut.wfa_finals; fin_a: their masks, None: trivial samples), start int32[n_out].  One CMux per state and step (a copy where both
+        transitions agree).  Returns key-switched records int32[count, n_out, theta, n+1]."""
+        return self._lhe_wfa(sets, trans, step_bit, fin_b, start, theta, fin_a, table_index, first, count, True)
+
+    def lhe_wfa_wo_keyswitch(self, sets, trans, step_bit, fin_b, start, *, theta=1, fin_a=None, table_index=None, first=0, count=None):
+        """lhe_wfa without the key switch: int32[count, n_out, theta, N+1] records under the ring key."""
+        return self._lhe_wfa(sets, trans, step_bit, fin_b, start, theta, fin_a, table_index, first, count, False)
+
+    def _lhe_wfa(self, sets, trans, step_bit, fin_b, start, theta, fin_a, table_index, first, count, keyswitch):
+        N = self.params.N
+        sets = list(sets)
+        if not sets:
+            raise ValueError("sets: expected at least one TgswSet")
+        trans = np.ascontiguousarray(trans, np.int32)
+        if trans.ndim != 3 or trans.shape[2] != 2 or trans.size == 0:
+            raise ValueError("trans: expected int32[n_steps][n_states][2]")
+        n_steps, n_states = trans.shape[:2]
+        step_bit = np.ascontiguousarray(step_bit, np.int32).reshape(-1)
+        if step_bit.shape[0] != n_steps:
+            raise ValueError(f"step_bit holds {step_bit.shape[0]} entries for {n_steps} steps")
+        fin_b = np.ascontiguousarray(fin_b, np.int32)
+        if fin_b.size == 0 or fin_b.size % (n_states * N):
+            raise ValueError(f"fin_b: expected int32[n_tables][{n_states}][{N}]")
+        if fin_a is not None:
+            fin_a = np.ascontiguousarray(fin_a, np.int32)
+            if fin_a.size != fin_b.size:
+                raise ValueError("fin_a and fin_b differ in size")
+        start = np.ascontiguousarray(start, np.int32).reshape(-1)
+        first = int(first)
+        count = sets[0].count - first if count is None else int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        idx = None
+        if table_index is not None:
+            idx = np.ascontiguousarray(table_index, np.int32).reshape(-1)
+            if idx.shape[0] != count:
+                raise ValueError(f"table_index holds {idx.shape[0]} entries for {count} samples")
+        hs = (_vp * len(sets))(*[t.h for t in sets])
+        th = int(theta) if theta in (1, 2, 4) else 1
+        out = np.empty((count, max(start.shape[0], 1), th, self.words if keyswitch else N + 1), np.int32)
+        fn = lib().thfhe_lhe_wfa if keyswitch else lib().thfhe_lhe_wfa_wo_keyswitch
+        _check(fn(self.h, hs, len(sets), first, count, n_steps, n_states, _p32(trans), _p32(step_bit), _p32(fin_a), _p32(fin_b),
+                  fin_b.size // (n_states * N), _p32(idx), int(theta), _p32(start), start.shape[0], _p32(out)))
+        return out
+
+    def set_wfa_chunk(self, g):
+        """States per workgroup of a step of lhe_wfa, 1 .. 64; 0: automatic.  No output word depends on it."""
+        _check(lib().thfhe_set_wfa_chunk(self.h, int(g)))
 
     def set_tree_slice(self, max_candidates):
         """Level-1 candidates (samples x p_hi, x k for tree_lut_bootstrap_mvk) per slice of tree_lut_bootstrap(_mv, _mvk): bounds its workspace (8 KiB of packing scratch per candidate);

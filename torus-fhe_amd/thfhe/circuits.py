@@ -725,6 +725,112 @@ def lhe_sbox(ck, tset, table, p_out=8):
     return np.stack(outs, axis=1)
 
 
+# ---- layered automata for thfhe_lhe_wfa ------------------------------------------------------------------------------------------
+# An automaton is (trans int32[n_steps][n_states][2], step_bit int32[n_steps], finals int[1][n_states], start int32[n_out]): step j reads bit
+# step_bit[j] & 15 of TGSW set step_bit[j] >> 4 and moves state q to trans[j][q][bit]; the output is finals[:, state after the last step].  Sets hold
+# at most 16 bits, so the operands are dealt over sets in 16-bit chunks (wfa_pair_bits, wfa_text_bits).
+
+def wfa_pair_bits(a, b, width):
+    """The bits of two `width`-bit operands per sample in the layout of wfa_less_than / wfa_equal: chunk c (bits 16c .. 16c+15) of a is set 2c,
+    of b set 2c+1 -> a list of int32[count][bits of the chunk], low bit first (each goes through SecretKeySet.tgsw_encrypt to CloudKey.tgsw_set)."""
+    a, b = np.asarray(a, np.int64).reshape(-1), np.asarray(b, np.int64).reshape(-1)
+    if not 1 <= width <= 62 or a.shape != b.shape or np.any((a < 0) | (a >> width != 0) | (b < 0) | (b >> width != 0)):
+        raise ValueError(f"expected two arrays of one length with values in [0, 2^{width}), 1 <= width <= 62")
+    sets = []
+    for lo in range(0, width, 16):
+        d = min(16, width - lo)
+        for v in (a, b):
+            sets.append((((v >> lo)[:, None] >> np.arange(d)[None, :]) & 1).astype(np.int32))
+    return sets
+
+
+def wfa_text_bits(bits):
+    """The bits int[count][n] of a text in the layout of wfa_match: bit i is bit i % 16 of set i // 16 -> a list of int32[count][<= 16]."""
+    t = np.asarray(bits, np.int32)
+    t = t[None] if t.ndim == 1 else t
+    return [np.ascontiguousarray(t[:, lo:lo + 16]) for lo in range(0, t.shape[1], 16)]
+
+
+def _wfa_pair_steps(width):
+    bit = lambda operand, i: 16 * (2 * (i // 16) + operand) + i % 16
+    return np.array([bit(j & 1, j >> 1) for j in range(2 * width)], np.int32)
+
+
+def wfa_less_than(width):
+    """a < b for two `width`-bit numbers (wfa_pair_bits), low bit first: 2 width steps, 4 states.  Even steps read a_i in state lt (0 / 1) and
+    move to 2 lt + a_i; odd steps read b_i: lt' = 1 if a_i < b_i, 0 if a_i > b_i, else lt -- half of the odd steps' states are copies.
+    finals: 1 in state 1."""
+    if not 1 <= width <= 62:
+        raise ValueError("1 <= width <= 62")
+    even = [[0, 1], [2, 3], [2, 2], [3, 3]]              # states 2, 3 are not reached at an even step
+    odd = [[0, 1], [0, 0], [1, 1], [0, 1]]               # (lt, a_i) = (0, 0), (0, 1), (1, 0), (1, 1)
+    trans = np.array([even, odd] * width, np.int32)
+    return trans, _wfa_pair_steps(width), np.array([[0, 1, 0, 0]]), np.array([0], np.int32)
+
+
+def wfa_equal(width):
+    """a == b for two `width`-bit numbers (wfa_pair_bits): 2 width steps, 4 states -- 0 equal so far, 1 different (absorbing: copies), 2 + a_i
+    after an even step.  finals: 1 in state 0."""
+    if not 1 <= width <= 62:
+        raise ValueError("1 <= width <= 62")
+    even = [[2, 3], [1, 1], [2, 2], [3, 3]]
+    odd = [[0, 0], [1, 1], [0, 1], [1, 0]]
+    trans = np.array([even, odd] * width, np.int32)
+    return trans, _wfa_pair_steps(width), np.array([[1, 0, 0, 0]]), np.array([0], np.int32)
+
+
+def wfa_match(pattern_bits, text_bits=None):
+    """Does the public bit pattern occur in an encrypted text of text_bits bits (wfa_text_bits; default: the pattern's length, i.e. equality with
+    the pattern)?  The Knuth-Morris-Pratt automaton: state q = length of the longest prefix of the pattern that ends here, state m = found
+    (absorbing); m + 1 <= 64 states, one step per text bit.  finals: 1 in state m."""
+    pat = [int(v) for v in np.asarray(pattern_bits).reshape(-1)]
+    m = len(pat)
+    n = m if text_bits is None else int(text_bits)
+    if not 1 <= m <= 63 or any(v not in (0, 1) for v in pat) or not m <= n <= 4096:
+        raise ValueError("expected 1 .. 63 pattern bits in {0, 1} and len(pattern) <= text_bits <= 4096")
+    delta = np.zeros((m + 1, 2), np.int32)
+    for q in range(m):
+        for b in (0, 1):
+            seen = pat[:q] + [b]
+            k = min(m, q + 1)
+            while k and seen[len(seen) - k:] != pat[:k]:
+                k -= 1
+            delta[q, b] = k
+    delta[m] = m
+    trans = np.repeat(delta[None], n, axis=0)
+    step_bit = np.array([16 * (i // 16) + i % 16 for i in range(n)], np.int32)
+    fin = np.zeros((1, m + 1), np.int64)
+    fin[0, m] = 1
+    return trans, step_bit, fin, np.array([0], np.int32)
+
+
+def wfa_run_plain(automaton, bits):
+    """The automaton on plain bits: bits is the list of sets (int[count][d] each, as wfa_pair_bits / wfa_text_bits return them) -> int[count][n_out]
+    [theta], finals[:, state] of the state each start state ends in."""
+    trans, step_bit, finals, start = automaton
+    trans, finals = np.asarray(trans), np.asarray(finals)
+    sets = [np.asarray(b).reshape(len(b), -1) for b in bits]
+    count = sets[0].shape[0]
+    state = np.tile(np.asarray(start, np.int64)[None], (count, 1))
+    for j, sb in enumerate(np.asarray(step_bit)):
+        b = sets[sb >> 4][:, sb & 15]
+        state = trans[j][state, b[:, None]]
+    return np.moveaxis(finals[:, state], 0, -1)
+
+
+def wfa_noise_steps(automaton, bits):
+    """Non-copy steps on the path of every (sample, output): the CMuxes whose noise the output carries -> int[count][n_out]."""
+    trans, step_bit, finals, start = automaton
+    trans = np.asarray(trans)
+    sets = [np.asarray(b).reshape(len(b), -1) for b in bits]
+    state = np.tile(np.asarray(start, np.int64)[None], (sets[0].shape[0], 1))
+    steps = np.zeros_like(state)
+    for j, sb in enumerate(np.asarray(step_bit)):
+        steps += trans[j][state, 0] != trans[j][state, 1]
+        state = trans[j][state, sets[sb >> 4][:, sb & 15][:, None]]
+    return steps
+
+
 def _tables(ck, cir):
     return np.stack([np.asarray(t, ck._tv_dtype).reshape(ck.params.N) for t in cir.tables])
 

@@ -188,6 +188,24 @@ def lhe_address_bits(addresses, d):
     return ((a[:, None] >> np.arange(d)[None, :]) & 1).astype(np.int32).reshape(-1)
 
 
+def wfa_finals(values, theta=1, encode=None, N=1024):
+    """Final weights of a layered automaton (thfhe_lhe_wfa): int32[n_states][N] from theta integer tables over the states
+    (values[j][q] = f_j(q); with theta = 1 one table will do).  State q becomes the polynomial with f_j(q) at coefficient j < theta and zero
+    elsewhere, so output j of the automaton carries f_j of the state it ends in.  encode: integers -> Torus32 words (e.g. lambda v:
+    lut.encode(v, 8)); None: the values are the words."""
+    if theta not in (1, 2, 4):
+        raise ValueError("theta must be 1, 2 or 4")
+    F = np.asarray(values, np.int64)
+    if F.ndim == 1 and theta == 1:
+        F = F[None]
+    if F.ndim != 2 or F.shape[0] != theta or F.shape[1] < 1:
+        raise ValueError(f"expected {theta} tables over the states, got shape {F.shape}")
+    words = np.asarray(encode(F), np.int64) if encode is not None else F
+    fin = np.zeros((F.shape[1], N), np.int64)
+    fin[:, :theta] = words.T
+    return _to_i32(fin)
+
+
 def encrypt_table(rlwe_key, tv, sigma, rng):
     """The client side of an encrypted table (thfhe_lut_bootstrap_enc): a fresh TLWE sample (tv_a, tv_b) of the test vector(s) tv int32[..., N]
     under the bootstrapping ring key: tv_a uniform, tv_b = tv_a (*) z + tv + e, e Gaussian of standard deviation sigma; exact product."""
