@@ -478,6 +478,40 @@ int thfhe_lhe_wfa_wo_keyswitch(thfhe_ctx *ctx, const thfhe_tgsw_set *const *sets
                                const int32_t *table_index, int theta, const int32_t *start, int n_out, int32_t *out_N1);
 int thfhe_set_wfa_chunk(thfhe_ctx *ctx, int g);
 
+/* ---- leveled scatter: demux trees that write at TGSW-encrypted addresses (single key, N = 1024): the other half of the leveled
+ * memory.  thfhe_lhe_lookup reads a table at an encrypted address; thfhe_lhe_scatter adds values into tables at encrypted addresses (scatter-add,
+ * histograms, one-hot encodings) and returns the tables as TLWE samples in the layout thfhe_lhe_lookup reads (tab_a non-NULL), so a write and a read
+ * compose with nothing in between.  A TGSW sample is used once; nothing is bootstrapped.
+ *
+ * thfhe_lhe_demux: for the samples s = 0 .. count-1 of the set, out1[s] = C_(s,bit) (.) x[s] -- thfhe_lhe_cmux with d0 = 0 and d1 = x, the same
+ *   decomposition, words and transforms -- and out0[s] = x[s] - out1[s] word-wise mod 2^32: out1 carries x where the bit is 1, out0 where it is 0, the
+ *   other child encrypts zero.  x_a, x_b, out0_a, out0_b, out1_a, out1_b: HOST int32[count][N]; x_a NULL: the trivial samples (0, x_b).
+ *
+ * thfhe_lhe_scatter: samples first .. first+count-1 of the set; d_tree + d_rot must equal the set's d, 0 <= d_tree <= 6, 0 <= d_rot <= 10,
+ *   box = N >> d_rot.  val_b: HOST int32[n_vals][N], val_a: the masks, or NULL for trivial samples (0, val_b); 1 <= n_vals <= 2^24.  Sample s writes the
+ *   value val_index[s] (HOST int32[count]); with val_index NULL it writes value s when n_vals == count and value 0 when n_vals == 1 (any other n_vals is
+ *   invalid).  table_index: HOST int32[count] or NULL (table 0); n_tables 2^d_tree <= 262144.  Per sample, with v its value:
+ *     1. ACC = v; for i = 0 .. d_rot-1  ACC += C_(s,i) (.) (X^(box 2^i) ACC - ACC) -- the mirror of the lookup's X^(2N - box 2^i); the largest shift is
+ *        N - box, so nothing wraps;
+ *     2. a demux tree, top down over bits d-1 .. d_rot: the node at depth k splits on bit d-1-k, child 1 = C (.) x, child 0 = x - child 1
+ *        (thfhe_lhe_demux); leaf P = sum_t bit_(d_rot+t) 2^t carries ACC, the other 2^d_tree - 1 leaves encrypt zero;
+ *     3. leaf P is added into polynomial P of the sample's table, word-wise mod 2^32, masks and bodies.  Tables start from zero.
+ *   With f_j at coefficient j < box of v, the table ends with f_j at coefficient (addr mod 2^d_rot) box + j of polynomial addr >> d_rot, the layout of
+ *   thfhe.lut.lhe_table.  What v means is not looked at: coefficients >= box spill into the neighbouring entries, unchecked.
+ *   tab_a, tab_b: OUT, HOST int32[n_tables][2^d_tree][N].  Exact integers, as thfhe_lhe_cmux; sums of integers do not depend on their order.
+ *   d_rot + 2^d_tree - 1 external products per sample; every leaf carries the d products of its path.  The batch runs in slices of at most
+ *   max(1, max_candidates / 2^d_tree) samples (thfhe_set_tree_slice; the workspace is 2^d_tree TLWE samples per sample) and 65 535 samples; the tables
+ *   stay on the device across the slices and come down once.
+ *
+ * THFHE_E_INVALID, in the order of thfhe_lhe_lookup: on the host, before the set or the context is looked at, null pointers, the ranges above and
+ * every val_index and table_index entry; then samples outside the set (and d_tree + d_rot against its d); then a NULL context or a set of another
+ * context.  count 0 returns THFHE_OK once those have passed, with the tables zeroed. */
+int thfhe_lhe_demux(thfhe_ctx *ctx, const thfhe_tgsw_set *set, int bit, const int32_t *x_a, const int32_t *x_b /*[count][N]*/, int32_t *out0_a,
+                    int32_t *out0_b, int32_t *out1_a, int32_t *out1_b /*[count][N]*/, size_t count);
+int thfhe_lhe_scatter(thfhe_ctx *ctx, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, const int32_t *val_a,
+                      const int32_t *val_b /*[n_vals][N]*/, int n_vals, const int32_t *val_index /*[count]*/, int n_tables,
+                      const int32_t *table_index /*[count]*/, int32_t *tab_a, int32_t *tab_b /*[n_tables][2^d_tree][N]*/);
+
 /* ---- encrypted-table, select and tree nodes in the gate-DAG executor (single key): thfhe_dag_run_lut_batch with three more node
  * kinds, so that a circuit needing a private table, an oblivious pick or a 6-bit -> 3-bit function does not leave the device-resident wire table.
  * nodes: HOST int32[n_nodes][6] = (opcode, in0, in1, in2, x, y); row g defines wire n_inputs + g.  Gate rows, THFHE_LUT and THFHE_LUT_OUT rows mean

@@ -2,7 +2,8 @@
 // thfhe_tgsw_set_create, thfhe_lhe_cmux and thfhe_lhe_lookup(_wo_keyswitch).  Included by thfhe_sk.hip INSIDE its second anonymous namespace, after
 // thfhe_ctx, the cooperative blind-rotate kernel (whose barriers and phases it reuses) and enqueue_keyswitch.
 //
-// Also the layered automata of DESIGN 4.16, thfhe_lhe_wfa(_wo_keyswitch): sk_lhe_wfa_step_kernel and its host side, further down.
+// Also the layered automata of DESIGN 4.16, thfhe_lhe_wfa(_wo_keyswitch): sk_lhe_wfa_step_kernel and its host side, further down; and the leveled
+// scatter of DESIGN 4.17, thfhe_lhe_demux and thfhe_lhe_scatter: sk_lhe_demux_kernel, sk_lhe_scatter_rotate_kernel, sk_lhe_scatter_sum_kernel, at the end.
 //
 // Data flow.  The blind-rotate kernels share ONE key stream among all jobs and give every job its own rotation amounts.  Here every job has its OWN
 // TGSW spectra (the address bits of its sample, 2l x 32 KiB per bit) and the rotation amounts are public: X^(2N - box 2^i) for address bit i.  Nothing
@@ -576,6 +577,271 @@ int lhe_wfa(thfhe_ctx *c, const thfhe_tgsw_set *const *sets, int n_sets, size_t 
         }
         THFHE_HIP(hipMemcpyAsync(out + s0 * recs * rec, res, S * recs * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
+    THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
+}
+
+// ---- leveled scatter: demux trees that write at TGSW-encrypted addresses: thfhe_lhe_demux, thfhe_lhe_scatter --------------------------
+constexpr int kScatterMaxVals = 1 << 24;
+
+// arguments of sk_lhe_demux_kernel, grid (nodes, samples): child 1 of node (s, q) = C_(s,bit) (.) x(s, q), child 0 = x(s, q) - child 1.  Word offsets:
+// x at index(s) * in_sample + q * in_node, index(s) = in_idx[s] or s; both children at s * out_sample + q * out_node of their own pointers.  A child
+// may be written over x: the node is in LDS before the first store.  PUB: x_a is not read (zero).
+struct LheDemuxArgs {
+    const cplx *spec;   // spectra of the set, at the first sample of the launch
+    const cplx *tw;
+    const int32_t *x_a, *x_b;
+    int32_t *out0_a, *out0_b, *out1_a, *out1_b;
+    const int32_t *in_idx;   // [samples] or null
+    size_t in_sample, in_node, out_sample, out_node;
+    int d, bit, Bgbit;
+};
+
+// One external product, two outputs: sk_lhe_cmux_kernel with d0 = 0 and d1 = x, which then also stores x - product.
+template <int L, bool PUB>
+__global__ __launch_bounds__(512, 2) void sk_lhe_demux_kernel(LheDemuxArgs a) {
+    constexpr int ROWS = 2 * L;
+    __shared__ __attribute__((aligned(4096))) int32_t sAcc[2048];
+    __shared__ int32_t sD1[2048];
+    __shared__ cplx sSpec[ROWS][512];
+    __shared__ cplx sX[8][kXbufSlots];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
+    const LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
+    const size_t s = blockIdx.y, node = blockIdx.x;
+    const size_t in = (a.in_idx ? (size_t)a.in_idx[s] : s) * a.in_sample + node * a.in_node;
+    cplx B[L][8];
+    lhe_load_spectra<L, PUB>(lane, wave, B, a.spec + (s * a.d + a.bit) * ((size_t)ROWS * 2048));
+    for (int q = threadIdx.x; q < 1024; q += 512) {
+        sAcc[q] = 0;
+        sAcc[1024 + q] = 0;
+        sD1[q] = PUB ? 0 : a.x_a[in + q];
+        sD1[1024 + q] = a.x_b[in + q];
+    }
+    wg_barrier();   // x is read: from here on its slot may be written
+    lhe_cmux_step<L, false, PUB, false>(lane, wave, sAcc, sD1, sSpec, sX, B, nullptr, nullptr, 0, a.Bgbit, roots, w64);
+    const size_t o = s * a.out_sample + node * a.out_node;
+    for (int q = threadIdx.x; q < 1024; q += 512) {
+        const uint32_t pa = (uint32_t)sAcc[q], pb = (uint32_t)sAcc[1024 + q];
+        a.out1_a[o + q] = (int32_t)pa;
+        a.out1_b[o + q] = (int32_t)pb;
+        a.out0_a[o + q] = (int32_t)((uint32_t)sD1[q] - pa);
+        a.out0_b[o + q] = (int32_t)((uint32_t)sD1[1024 + q] - pb);
+    }
+}
+
+// arguments of sk_lhe_scatter_rotate_kernel: sk_lhe_rotate_kernel's start (LheRotArgs: src_a, src_b, src_idx, src_stride), the POSITIVE rotations
+// ACC += C_(s,i) (.) (X^(box 2^i) ACC - ACC) for i = 0 .. d_rot-1, and the whole accumulator (mask | body) to out + job * out_stride
+struct LheScatterRotArgs {
+    const cplx *spec;
+    const cplx *tw;
+    const int32_t *src_a, *src_b;
+    const int32_t *src_idx;
+    size_t src_stride;
+    int32_t *out;
+    size_t out_stride;   // words between the accumulators of consecutive jobs
+    int d, d_rot, box, Bgbit;
+};
+
+// sk_lhe_rotate_kernel's loop, mirrored: the value moves UP to coefficient (addr mod 2^d_rot) box, where the lookup moves an entry down to 0.  The
+// largest total shift is N - box, so nothing wraps.  Nothing is extracted: the accumulator is the root of the sample's demux tree.
+template <int L>
+__global__ __launch_bounds__(512, 2) void sk_lhe_scatter_rotate_kernel(LheScatterRotArgs a) {
+    constexpr int ROWS = 2 * L;
+    __shared__ __attribute__((aligned(4096))) int32_t sAcc[2048];
+    __shared__ cplx sSpec[ROWS][512];
+    __shared__ cplx sX[8][kXbufSlots];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
+    const LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
+    const size_t job = blockIdx.x;
+    const size_t bit_stride = (size_t)ROWS * 2048;
+    const cplx *key = a.spec + job * a.d * bit_stride;
+    if (wave == 0) {
+        const size_t t = (a.src_idx ? (size_t)a.src_idx[job] : job) * a.src_stride;
+        if (a.src_a) acc_init_tlwe16(lane, sAcc, sAcc + 1024, 0, a.src_a + t, a.src_b + t);
+        else acc_init_tv16(lane, sAcc, sAcc + 1024, 0, a.src_b + t);
+    }
+    cplx B[L][8];
+    lhe_load_spectra<L, false>(lane, wave, B, key);   // d_rot >= 1: the host does not launch this kernel otherwise
+    wg_barrier();
+    for (int i = 0; i < a.d_rot; i++) {
+        const int a2n = a.box << i;   // <= N / 2
+        const int inl = i + 1 < a.d_rot ? i + 1 : i;
+        lhe_cmux_step<L, true, false, true>(lane, wave, sAcc, nullptr, sSpec, sX, B, key + i * bit_stride, key + inl * bit_stride, a2n, a.Bgbit, roots, w64);
+    }
+    int32_t *const o = a.out + job * a.out_stride;
+    for (int q = threadIdx.x; q < 2048; q += 512) o[q] = sAcc[q];
+}
+
+// arguments of sk_lhe_scatter_sum_kernel, grid (leaves, samples): leaf P of sample s is added into polynomial P of table tab_idx[s] (null: table 0)
+struct LheScatterSumArgs {
+    const int32_t *leaves;    // [samples][n_leaves][mask | body]
+    const int32_t *tab_idx;   // [samples] or null, validated on the host
+    int32_t *tab;             // masks [n_tables][n_leaves][N], then the bodies tab_half words further
+    size_t tab_half;
+    int n_leaves;
+};
+// Samples of one table meet on the same words, so the sum is made of atomic adds in global memory; integer sums mod 2^32 do not depend on their order.
+__global__ __launch_bounds__(256) void sk_lhe_scatter_sum_kernel(LheScatterSumArgs a) {
+    const size_t s = blockIdx.y, P = blockIdx.x;
+    const int32_t *const v = a.leaves + (s * a.n_leaves + P) * 2048;
+    const size_t t = a.tab_idx ? (size_t)a.tab_idx[s] : 0;
+    unsigned int *const dst = reinterpret_cast<unsigned int *>(a.tab) + (t * a.n_leaves + P) * 1024;
+    for (int q = threadIdx.x; q < 1024; q += 256) {
+        atomicAdd(dst + q, (unsigned int)v[q]);
+        atomicAdd(dst + a.tab_half + q, (unsigned int)v[1024 + q]);
+    }
+}
+
+template <int L>
+void launch_lhe_demux_l(const LheDemuxArgs &a, size_t nodes, size_t samples, bool pub, hipStream_t s) {
+    const dim3 grid((unsigned)nodes, (unsigned)samples);
+    if (pub) hipLaunchKernelGGL((sk_lhe_demux_kernel<L, true>), grid, dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((sk_lhe_demux_kernel<L, false>), grid, dim3(512), 0, s, a);
+}
+int launch_lhe_demux(thfhe_ctx *c, const LheDemuxArgs &a, size_t nodes, size_t samples, bool pub) {
+    switch (c->p.l) {
+    case 1: launch_lhe_demux_l<1>(a, nodes, samples, pub, c->stream); break;
+    case 2: launch_lhe_demux_l<2>(a, nodes, samples, pub, c->stream); break;
+    case 3: launch_lhe_demux_l<3>(a, nodes, samples, pub, c->stream); break;
+    case 4: launch_lhe_demux_l<4>(a, nodes, samples, pub, c->stream); break;
+    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
+    }
+    THFHE_HIP(hipGetLastError());
+    return THFHE_OK;
+}
+int launch_lhe_scatter_rotate(thfhe_ctx *c, const LheScatterRotArgs &a, size_t jobs) {
+    const dim3 grid((unsigned)jobs), block(512);
+    switch (c->p.l) {
+    case 1: hipLaunchKernelGGL(sk_lhe_scatter_rotate_kernel<1>, grid, block, 0, c->stream, a); break;
+    case 2: hipLaunchKernelGGL(sk_lhe_scatter_rotate_kernel<2>, grid, block, 0, c->stream, a); break;
+    case 3: hipLaunchKernelGGL(sk_lhe_scatter_rotate_kernel<3>, grid, block, 0, c->stream, a); break;
+    case 4: hipLaunchKernelGGL(sk_lhe_scatter_rotate_kernel<4>, grid, block, 0, c->stream, a); break;
+    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
+    }
+    THFHE_HIP(hipGetLastError());
+    return THFHE_OK;
+}
+
+// thfhe_lhe_demux: the flat form of one node per sample.  x goes up into d_lhe_a / d_lhe_b, the children come down from d_lhe_in[0 .. 3].
+int lhe_demux(thfhe_ctx *c, const thfhe_tgsw_set *set, int bit, const int32_t *x_a, const int32_t *x_b, int32_t *out0_a, int32_t *out0_b, int32_t *out1_a,
+              int32_t *out1_b, size_t count) {
+    if (!x_b || !out0_a || !out0_b || !out1_a || !out1_b) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (bit < 0 || bit >= kLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "lhe_demux: bit must be 0 .. d-1");
+    if (!set) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
+    if (bit >= set->d) return thfhe_fail(THFHE_E_INVALID, "lhe_demux: bit must be 0 .. d-1");
+    THFHE_TRY(lhe_validate_range(set, 0, count));
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (c != set->ctx) return thfhe_fail(THFHE_E_INVALID, "lhe: the set belongs to another context");
+    if (count == 0) return THFHE_OK;
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const size_t S_max = std::min<size_t>(count, 32768), bytes = S_max * 4096;
+    for (DevBuf &b : c->d_lhe_in) THFHE_TRY(b.grow(bytes));
+    if (x_a) THFHE_TRY(c->d_lhe_a.grow(bytes));
+    THFHE_TRY(c->d_lhe_b.grow(bytes));
+    int32_t *const dst[4] = {out0_a, out0_b, out1_a, out1_b};
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0);
+        if (x_a) THFHE_HIP(hipMemcpyAsync(c->d_lhe_a.as<int32_t>(), x_a + s0 * 1024, S * 4096, hipMemcpyHostToDevice, c->stream));
+        THFHE_HIP(hipMemcpyAsync(c->d_lhe_b.as<int32_t>(), x_b + s0 * 1024, S * 4096, hipMemcpyHostToDevice, c->stream));
+        LheDemuxArgs a{set->spec.as<cplx>() + s0 * lhe_sample_slots(c, set->d), c->d_tw.as<cplx>(), x_a ? c->d_lhe_a.as<int32_t>() : nullptr,
+                       c->d_lhe_b.as<int32_t>(), c->d_lhe_in[0].as<int32_t>(), c->d_lhe_in[1].as<int32_t>(), c->d_lhe_in[2].as<int32_t>(),
+                       c->d_lhe_in[3].as<int32_t>(), nullptr, 1024, 0, 1024, 0, set->d, bit, c->p.Bgbit};
+        THFHE_TRY(launch_lhe_demux(c, a, 1, S, !x_a));
+        for (int q = 0; q < 4; q++) THFHE_HIP(hipMemcpyAsync(dst[q] + s0 * 1024, c->d_lhe_in[q].as<int32_t>(), S * 4096, hipMemcpyDeviceToHost, c->stream));
+    }
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    return THFHE_OK;
+}
+
+// thfhe_lhe_scatter: per slice of at most tree_slice / 2^d_tree samples (the workspace: 2^d_tree TLWE samples of 8 KiB per sample) the rotations into
+// slot 0 of every sample, the demux tree in place -- the node at depth k, prefix q, lies in slot q 2^(d_tree-k), keeps child 0 there and writes child 1
+// 2^(d_tree-k-1) slots further, so leaf P ends in slot P -- and the sum of the leaves into the tables, which stay on the device until the last slice.
+int lhe_scatter(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, const int32_t *val_a, const int32_t *val_b,
+                int n_vals, const int32_t *val_index, int n_tables, const int32_t *table_index, int32_t *tab_a, int32_t *tab_b) {
+    // host checks, before the set or the context is looked at
+    if (!val_b || !tab_a || !tab_b) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (d_tree < 0 || d_tree > kLheMaxTree) return thfhe_fail(THFHE_E_INVALID, "lhe_scatter: d_tree must be 0 .. 6");
+    if (d_rot < 0 || d_rot > kLheMaxRot) return thfhe_fail(THFHE_E_INVALID, "lhe_scatter: d_rot must be 0 .. 10");
+    if (n_tables < 1 || ((long)n_tables << d_tree) > kMaxEncLuts) return thfhe_fail(THFHE_E_INVALID, "lhe_scatter: n_tables 2^d_tree must be 1 .. 262144");
+    if (n_vals < 1 || n_vals > kScatterMaxVals) return thfhe_fail(THFHE_E_INVALID, "lhe_scatter: n_vals must be 1 .. 2^24");
+    if (count > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "count too large");
+    if (val_index) {
+        for (size_t g = 0; g < count; g++)
+            if (val_index[g] < 0 || val_index[g] >= n_vals) return thfhe_fail(THFHE_E_INVALID, "val_index out of range (0 .. n_vals-1)");
+    } else if (n_vals != 1 && (size_t)n_vals != count) {
+        return thfhe_fail(THFHE_E_INVALID, "lhe_scatter: without val_index n_vals must be 1 or count");
+    }
+    THFHE_TRY(tree_validate_index(table_index, n_tables, count));
+    if (!set) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
+    if (d_tree + d_rot != set->d) return thfhe_fail(THFHE_E_INVALID, "lhe_scatter: d_tree + d_rot must equal the set's d");
+    THFHE_TRY(lhe_validate_range(set, first, count));
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (c != set->ctx) return thfhe_fail(THFHE_E_INVALID, "lhe: the set belongs to another context");
+    const size_t leaves = (size_t)1 << d_tree, tab_words = (size_t)n_tables * leaves * 1024;
+    if (count == 0) {   // nothing is written anywhere: the tables are their starting value
+        std::fill_n(tab_a, tab_words, 0);
+        std::fill_n(tab_b, tab_words, 0);
+        return THFHE_OK;
+    }
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const size_t S_max = std::min({count, (size_t)65535, std::max<size_t>(1, c->tree_slice / leaves)});
+    const bool per_slice = !val_index && n_vals > 1;   // value s belongs to sample s: a slice's values go up with the slice
+    const size_t val_bytes = (per_slice ? S_max : (size_t)n_vals) * 4096;
+    int rc = c->d_sc_tab.grow(2 * tab_words * sizeof(int32_t));
+    if (!rc) rc = c->d_lhe_a.grow(S_max * leaves * 2048 * sizeof(int32_t));
+    if (!rc) rc = c->d_tv.grow(val_bytes);
+    if (!rc && val_a) rc = c->d_tva.grow(val_bytes);
+    if (!rc && (val_index || table_index)) rc = c->d_sc_idx.grow(2 * S_max * sizeof(int32_t));
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    int32_t *const tab = c->d_sc_tab.as<int32_t>(), *const w = c->d_lhe_a.as<int32_t>();
+    int32_t *const d_vidx = c->d_sc_idx.as<int32_t>(), *const d_tidx = d_vidx + S_max;
+    const int32_t *const v_a = val_a ? c->d_tva.as<int32_t>() : nullptr, *const v_b = c->d_tv.as<int32_t>();
+    THFHE_HIP(hipMemsetAsync(tab, 0, 2 * tab_words * sizeof(int32_t), st));
+    if (!per_slice) {
+        THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), val_b, val_bytes, hipMemcpyHostToDevice, st));
+        if (val_a) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int32_t>(), val_a, val_bytes, hipMemcpyHostToDevice, st));
+    }
+    const size_t val_stride = n_vals > 1 ? 1024 : 0, ws = leaves * 2048;   // ws: words of workspace per sample
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0);
+        const cplx *spec = set->spec.as<cplx>() + (first + s0) * lhe_sample_slots(c, set->d);
+        if (per_slice) {
+            THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), val_b + s0 * 1024, S * 4096, hipMemcpyHostToDevice, st));
+            if (val_a) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int32_t>(), val_a + s0 * 1024, S * 4096, hipMemcpyHostToDevice, st));
+        }
+        if (val_index) THFHE_HIP(hipMemcpyAsync(d_vidx, val_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (table_index) THFHE_HIP(hipMemcpyAsync(d_tidx, table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[0], st));
+        if (d_rot > 0) {
+            LheScatterRotArgs r{spec, c->d_tw.as<cplx>(), v_a, v_b, val_index ? d_vidx : nullptr, val_stride, w, ws, set->d, d_rot, 1024 >> d_rot, c->p.Bgbit};
+            THFHE_TRY(launch_lhe_scatter_rotate(c, r, S));
+        }
+        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[1], st));
+        for (int k = 0; k < d_tree; k++) {
+            const size_t node = ws >> k, half = node / 2;   // words between the nodes of depth k; child 1 lies half a node further
+            LheDemuxArgs a{spec, c->d_tw.as<cplx>(), w, w + 1024, w, w + 1024, w + half, w + half + 1024, nullptr, ws, node, ws, node, set->d, set->d - 1 - k, c->p.Bgbit};
+            const bool from_values = k == 0 && d_rot == 0;   // no rotation ran: the root is the value itself, and a trivial value has a zero mask
+            if (from_values) a.x_a = v_a, a.x_b = v_b, a.in_idx = val_index ? d_vidx : nullptr, a.in_sample = val_stride, a.in_node = 0;
+            THFHE_TRY(launch_lhe_demux(c, a, (size_t)1 << k, S, from_values && !val_a));
+        }
+        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[2], st));
+        const LheScatterSumArgs x{w, table_index ? d_tidx : nullptr, tab, tab_words, (int)leaves};
+        hipLaunchKernelGGL(sk_lhe_scatter_sum_kernel, dim3((unsigned)leaves, (unsigned)S), dim3(256), 0, st, x);
+        THFHE_HIP(hipGetLastError());
+        if (c->profiling && s0 == 0) {
+            THFHE_HIP(hipEventRecord(c->ev[3], st));
+            c->ev_valid = true;
+        }
+    }
+    THFHE_HIP(hipMemcpyAsync(tab_a, tab, tab_words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    THFHE_HIP(hipMemcpyAsync(tab_b, tab + tab_words, tab_words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     THFHE_HIP(hipStreamSynchronize(st));
     return THFHE_OK;
 }

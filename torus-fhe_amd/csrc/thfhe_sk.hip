@@ -513,6 +513,9 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     DevBuf d_lhe_a, d_lhe_b, d_lhe_in[4];
     // layered automata (thfhe_lhe_wfa): the two layers alternate between d_lhe_a and d_lhe_b; the transition table and the start states
     DevBuf d_wfa_tab;
+    // leveled scatter (thfhe_lhe_demux, thfhe_lhe_scatter): the demux trees run in d_lhe_a ([sample][leaf][mask | body]); the tables
+    // being summed ([masks | bodies][n_tables][2^d_tree][N]) and a slice's value and table indices ([2][samples])
+    DevBuf d_sc_tab, d_sc_idx;
     int wfa_chunk = 0;   // states per workgroup of sk_lhe_wfa_step_kernel, 0: chosen per slice (wfa_chunk_for)
     size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate); also the output records (samples x q) per slice of thfhe_mv_lut_bootstrap
     // staging for the host-buffer API
@@ -1420,6 +1423,17 @@ int thfhe_lhe_wfa_wo_keyswitch(thfhe_ctx *c, const thfhe_tgsw_set *const *sets, 
                                const int32_t *table_index, int theta, const int32_t *start, int n_out, int32_t *out_N1) {
     return lhe_wfa(c, sets, n_sets, first, count, n_steps, n_states, trans, step_bit, fin_a, fin_b, n_tables, table_index, theta, start, n_out, out_N1,
                    false);
+}
+
+int thfhe_lhe_demux(thfhe_ctx *c, const thfhe_tgsw_set *set, int bit, const int32_t *x_a, const int32_t *x_b, int32_t *out0_a, int32_t *out0_b,
+                    int32_t *out1_a, int32_t *out1_b, size_t count) {
+    return lhe_demux(c, set, bit, x_a, x_b, out0_a, out0_b, out1_a, out1_b, count);
+}
+
+int thfhe_lhe_scatter(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, const int32_t *val_a,
+                      const int32_t *val_b, int n_vals, const int32_t *val_index, int n_tables, const int32_t *table_index, int32_t *tab_a,
+                      int32_t *tab_b) {
+    return lhe_scatter(c, set, first, count, d_tree, d_rot, val_a, val_b, n_vals, val_index, n_tables, table_index, tab_a, tab_b);
 }
 
 }  // extern "C"

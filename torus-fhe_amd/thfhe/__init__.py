@@ -206,6 +206,8 @@ SIGNATURES = {
     "thfhe_lhe_cmux": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_lhe_lookup": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p]),
     "thfhe_lhe_lookup_wo_keyswitch": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i32p]),
+    "thfhe_lhe_demux": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_lhe_scatter": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _i32p, C.c_int, _i32p, _i32p, _i32p]),
     "thfhe_lhe_wfa": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, _i32p, C.c_int,
                                 _i32p, C.c_int, _i32p]),
     "thfhe_lhe_wfa_wo_keyswitch": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, _i32p,
@@ -860,6 +862,54 @@ class CloudKey(_EvalKey):
         _check(fn(self.h, hs, len(sets), first, count, n_steps, n_states, _p32(trans), _p32(step_bit), _p32(fin_a), _p32(fin_b),
                   fin_b.size // (n_states * N), _p32(idx), int(theta), _p32(start), start.shape[0], _p32(out)))
         return out
+
+    # -- leveled scatter: demux trees that write at TGSW-encrypted addresses (thfhe_lhe_demux, thfhe_lhe_scatter) -----------------
+    def lhe_demux(self, tset, bit, x_b, x_a=None):
+        """(out0_a, out0_b, out1_a, out1_b) int32[count][N]: sample s gets out1 = C_(s,bit) (.) x[s] and out0 = x[s] - out1 -- x in out1 where its
+        address bit `bit` is 1, in out0 where it is 0, an encryption of zero in the other.  x_a None: the trivial samples (0, x_b)."""
+        N = self.params.N
+        x_b = np.ascontiguousarray(x_b, np.int32).reshape(-1, N)
+        if x_a is not None:
+            x_a = np.ascontiguousarray(x_a, np.int32).reshape(-1, N)
+            _same_count(x_a, x_b)
+        outs = [np.empty_like(x_b) for _ in range(4)]
+        _check(lib().thfhe_lhe_demux(self.h, tset.h, int(bit), _p32(x_a), _p32(x_b), *[_p32(v) for v in outs], x_b.shape[0]))
+        return tuple(outs)
+
+    def lhe_scatter(self, tset, val_b, *, d_tree, d_rot, val_a=None, val_index=None, n_tables=1, table_index=None, first=0, count=None):
+        """Leveled scatter of samples first .. first+count-1 of the set (default: all from `first`): sample s adds its value -- val_b
+        int32[n_vals][N] (thfhe.lut.lhe_value; val_a: the masks, None: trivial samples), value val_index[s], or value s when n_vals == count, or the
+        one value when n_vals == 1 -- into entry `address of s` of table table_index[s] (None: table 0) of n_tables tables that start from zero:
+        d_rot + 2^d_tree - 1 external products per sample.  Returns (tab_a, tab_b) int32[n_tables][2^d_tree][N], TLWE samples in the layout of
+        thfhe.lut.lhe_table: lhe_lookup(tset2, tab_b, tab_a=tab_a, ...) reads them."""
+        N = self.params.N
+        if not 0 <= int(d_tree) <= 6:
+            raise ValueError("d_tree must be 0 .. 6")
+        if int(n_tables) < 1:
+            raise ValueError("n_tables must be at least 1")
+        val_b = np.ascontiguousarray(val_b, np.int32)
+        if val_b.size == 0 or val_b.size % N:
+            raise ValueError(f"val_b: expected int32[n_vals][{N}]")
+        if val_a is not None:
+            val_a = np.ascontiguousarray(val_a, np.int32)
+            if val_a.size != val_b.size:
+                raise ValueError("val_a and val_b differ in size")
+        first = int(first)
+        count = tset.count - first if count is None else int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        idx = []
+        for name, v in (("val_index", val_index), ("table_index", table_index)):
+            if v is not None:
+                v = np.ascontiguousarray(v, np.int32).reshape(-1)
+                if v.shape[0] != count:
+                    raise ValueError(f"{name} holds {v.shape[0]} entries for {count} samples")
+            idx.append(v)
+        tab_a = np.empty((int(n_tables), 1 << int(d_tree), N), np.int32)
+        tab_b = np.empty_like(tab_a)
+        _check(lib().thfhe_lhe_scatter(self.h, tset.h, first, count, int(d_tree), int(d_rot), _p32(val_a), _p32(val_b), val_b.size // N, _p32(idx[0]),
+                                       int(n_tables), _p32(idx[1]), _p32(tab_a), _p32(tab_b)))
+        return tab_a, tab_b
 
     def set_wfa_chunk(self, g):
         """States per workgroup of a step of lhe_wfa, 1 .. 64; 0: automatic.  No output word depends on it."""

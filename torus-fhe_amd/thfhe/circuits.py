@@ -725,6 +725,38 @@ def lhe_sbox(ck, tset, table, p_out=8):
     return np.stack(outs, axis=1)
 
 
+def lhe_histogram(ck, tset, p_out, d_tree, d_rot):
+    """A histogram of encrypted addresses by leveled scatter (thfhe_lhe_scatter): every sample of `tset` adds the trivial value
+    2^32 / (2 p_out) -- the message 1 at modulus p_out (thfhe.lut.encode) -- at its address, so entry e of the returned table (tab_a, tab_b)
+    int32[1][2^d_tree][N] encrypts the number of samples whose address is e: decrypt with lut.decode(lut.lhe_table_entries(phases, d_tree, d_rot), p_out).
+    Counts must stay below p_out, and the noise of an entry grows with the number of samples, hit or not (DESIGN 4.17 tabulates it)."""
+    from . import lut
+    one = lut.lhe_value([1], encode=lambda v: lut.encode(v, p_out), N=ck.params.N)
+    return ck.lhe_scatter(tset, one, d_tree=d_tree, d_rot=d_rot)
+
+
+def lhe_scatter_plain(addresses, values, d_tree, d_rot, val_index=None, n_tables=1, table_index=None, N=1024):
+    """The plain model of thfhe_lhe_scatter: int32[n_tables][2^d_tree][N], the table polynomials after sample s has added X^((a mod 2^d_rot) box)
+    times its value polynomial -- values int[n_vals][N] words, value val_index[s], or value s when n_vals == len(addresses), or the one value --
+    into polynomial a >> d_rot of table table_index[s] (None: table 0), a = addresses[s], box = N >> d_rot; sums mod 2^32."""
+    addr = np.asarray(addresses, np.int64).reshape(-1)
+    vals = np.asarray(values, np.int64).reshape(-1, N)
+    if not (0 <= d_tree <= 6 and 0 <= d_rot <= 10) or np.any((addr < 0) | (addr >= 1 << (d_tree + d_rot))):
+        raise ValueError("d_tree must be 0 .. 6, d_rot 0 .. 10 and the addresses in [0, 2^(d_tree + d_rot))")
+    if val_index is None:
+        if vals.shape[0] not in (1, addr.shape[0]):
+            raise ValueError("without val_index there must be one value or one per address")
+        val_index = np.arange(addr.shape[0]) if vals.shape[0] > 1 else np.zeros(addr.shape[0], np.int64)
+    table_index = np.zeros(addr.shape[0], np.int64) if table_index is None else np.asarray(table_index, np.int64).reshape(-1)
+    box = N >> d_rot
+    tab = np.zeros((n_tables, 1 << d_tree, N), np.int64)
+    for a, vi, ti in zip(addr, np.asarray(val_index, np.int64).reshape(-1), table_index):
+        shift = int(a & ((1 << d_rot) - 1)) * box
+        v = vals[vi]
+        tab[ti, a >> d_rot] += np.concatenate([-v[N - shift:], v[:N - shift]])   # X^shift v mod X^N + 1
+    return (tab & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
 # ---- layered automata for thfhe_lhe_wfa (DESIGN 4.16) ------------------------------------------------------------------------------------------
 # An automaton is (trans int32[n_steps][n_states][2], step_bit int32[n_steps], finals int[1][n_states], start int32[n_out]): step j reads bit
 # step_bit[j] & 15 of TGSW set step_bit[j] >> 4 and moves state q to trans[j][q][bit]; the output is finals[:, state after the last step].  Sets hold

@@ -179,6 +179,31 @@ def lhe_table(functions, d_tree, d_rot, theta=1, encode=None, N=1024):
     return _to_i32(tab)
 
 
+def lhe_value(values, encode=None, N=1024):
+    """Value polynomial(s) of a leveled scatter (thfhe_lhe_scatter): values int[k] -> int32[N] with f_j = values[j] at coefficient j
+    and zero elsewhere; int[n_vals][k] -> int32[n_vals][N].  Written at address e with box = N >> d_rot >= k, f_j lands where entry e of function j
+    sits in lhe_table's layout; k > box spills into the neighbouring entries.  encode: integers -> Torus32 words; None: the values are the words."""
+    F = np.asarray(values, np.int64)
+    if F.ndim == 0:
+        F = F[None]
+    if F.ndim > 2 or F.shape[-1] < 1 or F.shape[-1] > N:
+        raise ValueError(f"expected int[k] or int[n_vals][k] with 1 <= k <= {N}, got shape {F.shape}")
+    words = np.asarray(encode(F), np.int64) if encode is not None else F
+    val = np.zeros(F.shape[:-1] + (N,), np.int64)
+    val[..., :F.shape[-1]] = words
+    return _to_i32(val)
+
+
+def lhe_table_entries(polys, d_tree, d_rot, theta=1, N=1024):
+    """The inverse of lhe_table's layout: from words int[2^d_tree][N] (e.g. the phases of a scattered table) the entries int[theta][2^(d_tree + d_rot)],
+    entry e of function j read at coefficient (e mod 2^d_rot) * box + j of polynomial e >> d_rot."""
+    if not (0 <= d_tree <= 6 and 0 <= d_rot <= 10) or theta < 1 or theta > (N >> d_rot):
+        raise ValueError("d_tree must be 0 .. 6, d_rot 0 .. 10 and 1 <= theta <= box = N >> d_rot")
+    P = np.asarray(polys).reshape(1 << d_tree, N)
+    e = np.arange(1 << (d_tree + d_rot))
+    return np.stack([P[e >> d_rot, (e & ((1 << d_rot) - 1)) * (N >> d_rot) + j] for j in range(theta)])
+
+
 def lhe_address_bits(addresses, d):
     """Bits of the addresses, low bit first, sample-major: int32[len(addresses) * d], bit i of address s at s d + i -- the order
     SecretKeySet.tgsw_encrypt -> CloudKey.tgsw_set expects."""
