@@ -63,7 +63,10 @@ enum thfhe_gate {
     THFHE_SELECT = 17,  /* gate-DAG node: oblivious pick among p consecutive earlier wires (thfhe_dag_run_tree_batch only) */
     THFHE_TREE = 18,    /* gate-DAG node: two-digit tree PBS (thfhe_dag_run_tree_batch, thfhe_dag_run_mv_batch) */
     THFHE_MV = 19,      /* gate-DAG node: multi-value bootstrap, q outputs of one rotation (thfhe_dag_run_mv_batch only) */
-    THFHE_TREE_MV = 20  /* gate-DAG node: two-digit tree with a multi-value level 1 and k outputs (thfhe_dag_run_mv_batch only) */
+    THFHE_TREE_MV = 20, /* gate-DAG node: two-digit tree with a multi-value level 1 and k outputs (thfhe_dag_run_mv_batch, thfhe_dag_run_lhe_batch) */
+    THFHE_LHE_LOOKUP = 21,  /* gate-DAG node: leveled lookup of a table of the run at a TGSW-encrypted address (thfhe_dag_run_lhe_batch only) */
+    THFHE_LHE_GATHER = 22,  /* gate-DAG node: leveled pick among 2^d computed wires at a TGSW-encrypted index (thfhe_dag_run_lhe_batch only) */
+    THFHE_LHE_WFA = 23      /* gate-DAG node: layered automaton on TGSW-encrypted bits (thfhe_dag_run_lhe_batch only) */
 };
 
 enum thfhe_error {
@@ -586,6 +589,76 @@ int thfhe_dag_run_mv_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const int32
                            const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs,
                            const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, size_t instances,
                            const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats);
+
+/* ---- leveled nodes in the gate-DAG executor (single key): thfhe_dag_run_mv_batch with three more node kinds that read the client's
+ * TGSW-encrypted bits, so that a leveled lookup, a leveled pick among COMPUTED wires and a layered automaton run between gates on the device-resident
+ * wire table.  Every argument before `lhe` means what it means in thfhe_dag_run_mv_batch; with lhe = NULL the call is that call.  Instance q of the
+ * run reads sample q of every set.  New rows (operand fields -1):
+ *   (THFHE_LHE_LOOKUP, -1, -1, -1, lk, row0), followed by theta - 1 THFHE_LUT_OUT rows: wire head + j of instance q is the record
+ *       thfhe_lhe_lookup(ctx, sets[lks[lk].set], q, 1, d_tree, d_rot, theta, tab_a + row0 N, tab_b + row0 N, 1, NULL) returns at [0][j], word for
+ *       word; it reads rows row0 .. row0 + 2^d_tree - 1 of the run's table polynomials.
+ *   (THFHE_LHE_GATHER, -1, -1, -1, lk, first): one output, lks[lk].theta = 1, 1 <= d_rot <= 9 (the range of p of thfhe_pack_boxes), d_tree <= 6.  The
+ *       candidates are the 2^d (d = d_tree + d_rot) consecutive EARLIER wires first .. first + 2^d - 1, candidate e = wire first + e.  The wire equals
+ *       thfhe_pack_boxes(ctx_pack, candidate records, 2^d, p = 2^d_rot) -> 2^d_tree TLWE samples -> thfhe_lhe_lookup(.., d_tree, d_rot, 1, those
+ *       samples as tab_a / tab_b, 1, NULL), word for word: the box packer's output is a theta = 1 leveled table.
+ *   (THFHE_LHE_WFA, -1, -1, -1, wfa, fin_row0), followed by n_out theta - 1 THFHE_LUT_OUT rows: wire head + o theta + j of instance q is
+ *       thfhe_lhe_wfa(ctx, sets + set0, n_sets, q, 1, n_steps, n_states, trans, step_bit, fin_a + fin_row0 N, fin_b + fin_row0 N, 1, NULL, theta,
+ *       start, n_out) at [0][o][j]; it reads n_states rows from fin_row0.  trans (int32[n_steps][n_states][2]), step_bit (int32[n_steps]) and start
+ *       (int32[n_out]) lie in the pool wfa_words at the spec's offsets.
+ * Scheduling: every new node costs one level; a GATHER's depth counts its candidates, LOOKUP and WFA nodes have no wire operands and sit on the
+ *   first level.  A level's leveled nodes run as one launch group per distinct lks[] / wfas[] index, after the other groups, on the gate context's
+ *   stream with no host synchronisation between levels.  The leveled kernels address the TGSW sample by the job number, so a group runs the flat
+ *   entry's launch chain once per node with count = the instances of the slice.  Slices: at most thfhe_set_dag_slice instances; LOOKUP and WFA
+ *   groups also follow the flat entries' thfhe_set_tree_slice rules, a GATHER slice holds at most thfhe_set_tree_slice / 2^d jobs.
+ * stats: a leveled node counts no rotation.  stats[1] counts launch GROUPS, one per group of a level: a leveled group of cnt nodes issues cnt launch
+ *   chains per slice (each d_tree CMux launches, a rotation, a key switch and a scatter; a GATHER also its gather and packing), so the kernel
+ *   launches of a leveled group are not that figure.
+ * thfhe_dag_last_group_ms: with profiling on (thfhe_set_profiling), *ms = the device time of the LAST SELECT / TREE / MV / TREE_MV / leveled group
+ *   of the context's last thfhe_dag_run_lut_batch / _tree_batch / _mv_batch / _lhe_batch, first launch to last scatter: a pair of events of its own
+ *   on the gate context's stream, no copy inside, which gate levels and the stages' events do not touch; thfhe_last_timings is not changed by it.
+ *   THFHE_E_INVALID when profiling is off or that run had no such group.
+ * Checks, on the host before any device work and before either context or any set is looked at (THFHE_E_INVALID): those of thfhe_dag_run_mv_batch; a
+ *   spec the flat entry would refuse; lk, wfa, row0 + 2^d_tree or fin_row0 + n_states out of range; pool offsets past n_wfa_words; a wrong number of
+ *   LUT_OUT rows; operand fields that are not -1; GATHER candidates that are not all earlier wires; GATHER with theta != 1 or d_rot outside 1 .. 9; a
+ *   family that is NULL while a row refers to it.  Then: null sets, a set of another context, a set count below `instances`, d_tree + d_rot against
+ *   the set's d, step_bit against the spec's sets.  The context checks of thfhe_tree_lut_bootstrap apply when the plan holds a SELECT, TREE, TREE_MV
+ *   or GATHER node; ctx_pack may be NULL otherwise.  Every other thfhe_dag_* and thfhe_mk_dag_* entry rejects the three opcodes. */
+typedef struct thfhe_dag_lhe_spec {
+    int32_t set;      /* index into sets[] */
+    int32_t d_tree;   /* 0 .. 6 */
+    int32_t d_rot;    /* LOOKUP: 0 .. 10; GATHER: 1 .. 9 */
+    int32_t theta;    /* LOOKUP: 1, 2 or 4, at most N >> d_rot; GATHER: 1 */
+} thfhe_dag_lhe_spec;
+
+typedef struct thfhe_dag_wfa_spec {
+    int32_t n_steps, n_states, theta, n_out;
+    int32_t set0, n_sets;   /* the automaton's sets are sets[set0 .. set0 + n_sets - 1]; step_bit = 16 set + bit names set0 + set */
+    int32_t trans_off;      /* int32[n_steps][n_states][2] in wfa_words */
+    int32_t step_off;       /* int32[n_steps] in wfa_words */
+    int32_t start_off;      /* int32[n_out] in wfa_words */
+} thfhe_dag_wfa_spec;
+
+typedef struct thfhe_dag_lhe_families {
+    const thfhe_tgsw_set *const *sets;   /* HOST array of 1 .. 64 sets of the gate context, each of at least `instances` samples */
+    int32_t n_sets;
+    const thfhe_dag_lhe_spec *lks;       /* at most 1024, or NULL, 0 */
+    int32_t n_lks;
+    const int32_t *tab_a, *tab_b;        /* HOST int32[n_tab_rows][N]; tab_a NULL: public tables.  Uploaded once, shared by all instances */
+    int32_t n_tab_rows;
+    const thfhe_dag_wfa_spec *wfas;      /* at most 1024, or NULL, 0 */
+    int32_t n_wfas;
+    const int32_t *wfa_words;            /* HOST int32[n_wfa_words] */
+    size_t n_wfa_words;
+    const int32_t *fin_a, *fin_b;        /* HOST int32[n_fin_rows][N] final weights; fin_a NULL: public */
+    int32_t n_fin_rows;
+} thfhe_dag_lhe_families;
+
+int thfhe_dag_run_lhe_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                            const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
+                            const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs,
+                            const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, const thfhe_dag_lhe_families *lhe,
+                            size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats);
+int thfhe_dag_last_group_ms(thfhe_ctx *ctx, float *ms);
 
 /* ---- multi-key KEY GENERATION arithmetic on the device --------------------------------------------------------------
  * Exact multiply-accumulate of small-coefficient polynomials with torus polynomials, the only non-trivial arithmetic of

@@ -5,6 +5,8 @@
 // into consecutive wires.
 // Encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch, DESIGN 4.12, single key): three more node kinds, planned here, run by the engine.
 // Multi-value nodes (thfhe_dag_run_mv_batch, DESIGN 4.14, single key): MV and TREE_MV rows, planned here next to them.
+// Leveled nodes (thfhe_dag_run_lhe_batch, DESIGN 4.18, single key): LHE_LOOKUP, LHE_GATHER and LHE_WFA rows on the client's TGSW sets, planned here;
+// dag_lhe_gather_kernel stages a GATHER node's candidates for the box packing.
 #ifndef THFHE_DAG_H
 #define THFHE_DAG_H
 
@@ -78,13 +80,23 @@ __global__ __launch_bounds__(256) void dag_select_gather_kernel(const int32_t *_
         dst[(size_t)r * words + i] = wires[((size_t)q * n_wires + t_first[g] + k) * words + i];
     }
 }
-
+// Candidate gather of one LHE_GATHER node over a slice of instances: candidate r = j P + k is wire first_wire + k of instance q0 + j -> dst[r], the
+// [jobs P][words] buffer the box packing reads.  The P candidates of a job are consecutive wires, so a job is one contiguous copy of P records.
+__global__ __launch_bounds__(256) void dag_lhe_gather_kernel(const int32_t *__restrict__ wires, int32_t *__restrict__ dst, long q0, long total, size_t n_wires,
+                                                             int words, int first_wire, int P) {
+    const long j = blockIdx.y;
+    const size_t len = (size_t)P * words;
+    if (j >= total) return;
+    const int32_t *const src = wires + ((size_t)(q0 + j) * n_wires + first_wire) * words;
+    int32_t *const out = dst + (size_t)j * len;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (size_t)gridDim.x * 256) out[i] = src[i];
+}
 
 // One launch group of the schedule: `count` gates of one class whose operands are all available.
 struct DagBatch {
     int32_t depth, sub, cls;  // cls: engine-defined gate class; 2 = NOT / COPY (no bootstrap); 4 / 5 / 6 = LUT nodes of theta 1 / 2 / 4
     size_t off, count;        // index table slice: [ops | in0 | in1 | in2 | out], LUT classes + [spec | lut], `count` entries each, at tab[off]
-    int32_t tree = -1;        // SELECT / TREE groups: the trees[] entry the whole group shares; MV / TREE_MV groups: the mvs[] entry
+    int32_t tree = -1;        // SELECT / TREE groups: the trees[] entry the whole group shares; MV / TREE_MV groups: the mvs[] entry; leveled groups: lks[] / wfas[]
 };
 constexpr int kDagLutOut = 7;                // LUT_OUT row: no launch, its wire is written by its head's scatter
 inline int dag_lut_class(int theta) { return theta == 1 ? 4 : (theta == 2 ? 5 : 6); }
@@ -95,6 +107,9 @@ constexpr int kDagEnc = 8, kDagSelect = 11, kDagTree = 12;
 inline int dag_enc_theta(int cls) { return cls == 8 ? 1 : (cls == 9 ? 2 : 4); }
 // thfhe_dag_run_mv_batch: MV groups = 13, TREE_MV groups = 14 ([mv | t]), one group per mvs[] entry
 constexpr int kDagMv = 13, kDagTreeMv = 14;
+// thfhe_dag_run_lhe_batch: LHE_LOOKUP groups = 15 ([lk | row0]), LHE_GATHER groups = 16 ([lk | first]), one group per lks[] entry; LHE_WFA groups = 17
+// ([wfa | fin_row0]), one group per wfas[] entry
+constexpr int kDagLheLookup = 15, kDagLheGather = 16, kDagLheWfa = 17;
 
 // The LUT side of a run (thfhe_dag_run_lut_batch): node rows of 6 words, the run's specs and its table count.
 struct DagLuts {
@@ -110,6 +125,8 @@ struct DagLuts {
     const thfhe_mv_spec *mvs = nullptr;
     int n_mvs = 0, n_bases = 0;
     size_t n_factor_words = 0;
+    // thfhe_dag_run_lhe_batch only: the leveled families (host pointers; a family the run does not have is null / 0)
+    const thfhe_dag_lhe_families *lhe = nullptr;
 };
 
 // the rules a multi-value rotation adds to lut_spec_check's: theta 1, p taps, q outputs, the table count (thfhe_mv_lut_bootstrap)
@@ -148,6 +165,41 @@ inline int dag_mv_spec_check(const DagLuts &L, const thfhe_mv_spec &m, bool tree
     return THFHE_OK;
 }
 
+// One lks[] entry as a LOOKUP row (gather = false) or a GATHER row uses it: the rules of thfhe_lhe_lookup that need no set, then the node kind's own.
+inline int dag_lhe_spec_check(const thfhe_dag_lhe_families &F, const thfhe_dag_lhe_spec &k, bool gather) {
+    if (k.d_tree < 0 || k.d_tree > 6) return thfhe_fail(THFHE_E_INVALID, "leveled node: d_tree must be 0 .. 6");
+    if (k.d_rot < 0 || k.d_rot > 10) return thfhe_fail(THFHE_E_INVALID, "leveled node: d_rot must be 0 .. 10");
+    if (k.theta != 1 && k.theta != 2 && k.theta != 4) return thfhe_fail(THFHE_E_INVALID, "leveled node: theta must be 1, 2 or 4");
+    if (k.theta > (1024 >> k.d_rot)) return thfhe_fail(THFHE_E_INVALID, "leveled node: theta must not exceed box = N >> d_rot");
+    if (gather && k.theta != 1) return thfhe_fail(THFHE_E_INVALID, "LHE_GATHER node: the spec's theta must be 1 (a packed box holds one value)");
+    if (gather && (k.d_rot < 1 || k.d_rot > 9)) return thfhe_fail(THFHE_E_INVALID, "LHE_GATHER node: d_rot must be 1 .. 9 (the box packing's p = 2^d_rot)");
+    if (!F.sets || F.n_sets < 1) return thfhe_fail(THFHE_E_INVALID, "leveled node: no tgsw sets given (null family)");
+    if (k.set < 0 || k.set >= F.n_sets) return thfhe_fail(THFHE_E_INVALID, "leveled node: the spec's set is out of range (0 .. n_sets-1)");
+    return THFHE_OK;
+}
+// One wfas[] entry: the rules of thfhe_lhe_wfa that need no set, its sets within sets[], its three slices of the word pool and their entries.
+inline int dag_wfa_spec_check(const thfhe_dag_lhe_families &F, const thfhe_dag_wfa_spec &a) {
+    if (a.n_sets < 1 || a.n_sets > 64) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: the spec's n_sets must be 1 .. 64");
+    if (a.n_steps < 1 || a.n_steps > 4096) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: n_steps must be 1 .. 4096");
+    if (a.n_states < 1 || a.n_states > 64) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: n_states must be 1 .. 64");
+    if (a.n_out < 1 || a.n_out > 64) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: n_out must be 1 .. 64");
+    if (a.theta != 1 && a.theta != 2 && a.theta != 4) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: theta must be 1, 2 or 4");
+    if (!F.sets || F.n_sets < 1) return thfhe_fail(THFHE_E_INVALID, "leveled node: no tgsw sets given (null family)");
+    if (a.set0 < 0 || (long)a.set0 + a.n_sets > F.n_sets) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: set0 + n_sets out of range (0 .. n_sets)");
+    if (!F.wfa_words) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: no word pool given (null family)");
+    const size_t n_trans = (size_t)a.n_steps * a.n_states * 2;
+    if (a.trans_off < 0 || (size_t)a.trans_off + n_trans > F.n_wfa_words || a.step_off < 0 || (size_t)a.step_off + a.n_steps > F.n_wfa_words ||
+        a.start_off < 0 || (size_t)a.start_off + a.n_out > F.n_wfa_words)
+        return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: a pool offset runs past n_wfa_words");
+    for (size_t i = 0; i < n_trans; i++)
+        if (F.wfa_words[a.trans_off + i] < 0 || F.wfa_words[a.trans_off + i] >= a.n_states)
+            return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: trans entry out of range (0 .. n_states-1)");
+    for (int o = 0; o < a.n_out; o++)
+        if (F.wfa_words[a.start_off + o] < 0 || F.wfa_words[a.start_off + o] >= a.n_states)
+            return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: start entry out of range (0 .. n_states-1)");
+    return THFHE_OK;
+}
+
 struct DagPlan {
     std::vector<DagBatch> batches;
     std::vector<int32_t> tab;
@@ -161,7 +213,12 @@ struct DagPlan {
     }
     bool has_tree_groups() const {
         for (const auto &b : batches)
-            if (b.cls == kDagSelect || b.cls == kDagTree || b.cls == kDagTreeMv) return true;
+            if (b.cls == kDagSelect || b.cls == kDagTree || b.cls == kDagTreeMv || b.cls == kDagLheGather) return true;
+        return false;
+    }
+    bool has_lhe_groups() const {
+        for (const auto &b : batches)
+            if (b.cls >= kDagLheLookup) return true;
         return false;
     }
 };
@@ -175,6 +232,9 @@ struct DagPlan {
 // rows add one level above their operands (a SELECT's candidates included) and form one group per trees[] entry, emitted after the other classes.
 // luts->mv (thfhe_dag_run_mv_batch): THFHE_MV and THFHE_TREE_MV rows (mv, t) add one level and form one group per mvs[] entry, emitted after those;
 // q - 1 (MV) or k - 1 (TREE_MV) LUT_OUT rows follow the head.
+// luts->lhe (thfhe_dag_run_lhe_batch): LHE_LOOKUP, LHE_GATHER and LHE_WFA rows (no wire operands; lk / wfa, row0 / first / fin_row0) add one level --
+// a GATHER above its candidates, the two others on the first -- and form one group per lks[] / wfas[] entry, emitted after those; theta - 1 (LOOKUP) or
+// n_out theta - 1 (WFA) LUT_OUT rows follow the head.
 template <typename Classify>
 int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify classify, DagPlan &plan, const DagLuts *luts = nullptr) {
     const size_t n_wires = n_inputs + n_gates, stride = luts ? 6 : 4;
@@ -184,6 +244,8 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
     std::vector<char> tree_lo_ok(ext ? (size_t)luts->n_trees : 0, 0);   // trees[] entries whose `lo` half a TREE row has had checked
     const bool mvx = ext && luts->mv;
     std::vector<char> mv_ok(mvx ? (size_t)luts->n_mvs : 0, 0);          // mvs[] entries checked as an MV (bit 0) / a TREE_MV (bit 1) row uses them
+    const thfhe_dag_lhe_families *const lhe = mvx ? luts->lhe : nullptr;
+    std::vector<char> lk_ok(lhe && lhe->lks ? (size_t)lhe->n_lks : 0, 0), wfa_ok(lhe && lhe->wfas ? (size_t)lhe->n_wfas : 0, 0);   // as mv_ok: LOOKUP bit 0, GATHER bit 1
     int32_t max_depth = 0;
     int32_t head = -1, pending = 0;   // the LUT node whose LUT_OUT rows are still due, and how many
     for (size_t g = 0; g < n_gates; g++) {
@@ -260,6 +322,43 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
                                                                : "MV node: operands do not match lo.n_inputs (unused ones are -1)");
             k = is_tree ? kDagTreeMv : kDagMv;
             head = w, pending = (is_tree ? m.k : m.q) - 1;
+        } else if (lhe && (op == THFHE_LHE_LOOKUP || op == THFHE_LHE_GATHER)) {
+            const bool gather = op == THFHE_LHE_GATHER;
+            if (row[1] != -1 || row[2] != -1 || row[3] != -1) return thfhe_fail(THFHE_E_INVALID, "leveled node: the operand fields must be -1");
+            if (!lhe->lks) return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP / LHE_GATHER node: no lookup specs given (null family)");
+            if (row[4] < 0 || row[4] >= lhe->n_lks) return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP / LHE_GATHER node: lk out of range (0 .. n_lks-1)");
+            const thfhe_dag_lhe_spec &ls = lhe->lks[row[4]];
+            if (!(lk_ok[row[4]] & (gather ? 2 : 1))) {
+                THFHE_TRY(dag_lhe_spec_check(*lhe, ls, gather));
+                lk_ok[row[4]] |= gather ? 2 : 1;
+            }
+            if (gather) {
+                cand_first = row[5], cand_count = (int32_t)1 << (ls.d_tree + ls.d_rot);
+                if (cand_first < 0 || (long)cand_first + cand_count > (long)w)
+                    return thfhe_fail(THFHE_E_INVALID, "LHE_GATHER node: candidate is not an earlier wire (first .. first + 2^d - 1 must all be defined above)");
+            } else {
+                if (!lhe->tab_b || lhe->n_tab_rows < 1) return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP node: no table rows given (null family)");
+                if (row[5] < 0 || (long)row[5] + (1L << ls.d_tree) > lhe->n_tab_rows)
+                    return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP node: row0 + 2^d_tree out of range (0 .. n_tab_rows)");
+                head = w, pending = ls.theta - 1;
+            }
+            nin = 0;
+            k = gather ? kDagLheGather : kDagLheLookup;
+        } else if (lhe && op == THFHE_LHE_WFA) {
+            if (row[1] != -1 || row[2] != -1 || row[3] != -1) return thfhe_fail(THFHE_E_INVALID, "leveled node: the operand fields must be -1");
+            if (!lhe->wfas) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: no automaton specs given (null family)");
+            if (row[4] < 0 || row[4] >= lhe->n_wfas) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: wfa out of range (0 .. n_wfas-1)");
+            const thfhe_dag_wfa_spec &a = lhe->wfas[row[4]];
+            if (!wfa_ok[row[4]]) {
+                THFHE_TRY(dag_wfa_spec_check(*lhe, a));
+                wfa_ok[row[4]] = 1;
+            }
+            if (!lhe->fin_b || lhe->n_fin_rows < 1) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: no final weights given (null family)");
+            if (row[5] < 0 || (long)row[5] + a.n_states > lhe->n_fin_rows)
+                return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: fin_row0 + n_states out of range (0 .. n_fin_rows)");
+            head = w, pending = a.n_out * a.theta - 1;
+            nin = 0;
+            k = kDagLheWfa;
         } else {
             k = classify(op);
             if (k < 0) return thfhe_fail(THFHE_E_INVALID, "gate opcode not defined for this engine");
@@ -285,6 +384,8 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
     std::vector<std::vector<std::vector<int32_t>>> boot(max_depth + 1, std::vector<std::vector<int32_t>>(kDagSelect)), lin(max_depth + 1);
     std::vector<std::map<int32_t, std::vector<int32_t>>> sel(ext ? max_depth + 1 : 0), tre(ext ? max_depth + 1 : 0);   // per level, by trees[] index
     std::vector<std::map<int32_t, std::vector<int32_t>>> mvn(mvx ? max_depth + 1 : 0), tmv(mvx ? max_depth + 1 : 0);   // per level, by mvs[] index
+    std::vector<std::map<int32_t, std::vector<int32_t>>> lhg[3];   // LOOKUP / GATHER / WFA nodes per level, by lks[] / wfas[] index
+    for (auto &v : lhg) v.resize(lhe ? max_depth + 1 : 0);
     for (size_t g = 0; g < n_gates; g++) {
         const int32_t w = (int32_t)(n_inputs + g);
         if (cls[g] == kDagLutOut) continue;
@@ -292,6 +393,8 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
             (cls[g] == kDagTree ? tre : sel)[depth[w]][gates[stride * g + 4]].push_back((int32_t)g);
         } else if (cls[g] == kDagMv || cls[g] == kDagTreeMv) {
             (cls[g] == kDagTreeMv ? tmv : mvn)[depth[w]][gates[stride * g + 4]].push_back((int32_t)g);
+        } else if (cls[g] >= kDagLheLookup) {
+            lhg[cls[g] - kDagLheLookup][depth[w]][gates[stride * g + 4]].push_back((int32_t)g);
         } else if (cls[g] == 2) {
             auto &L = lin[depth[w]];
             if ((int)L.size() < sub[w]) L.resize(sub[w]);
@@ -312,7 +415,7 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
             }
         plan.batches.push_back(b);
         if (G.size() > plan.max_width) plan.max_width = G.size();
-        size_t rot = k == 2 ? 0 : (k == 1 ? 2 * G.size() : G.size());
+        size_t rot = k == 2 || k >= kDagLheLookup ? 0 : (k == 1 ? 2 * G.size() : G.size());   // a leveled node counts no blind rotation
         if (k == kDagTree) rot = G.size() * (size_t)(luts->trees[tree].p_hi / luts->trees[tree].lo.theta + 1);   // R level-1 rotations + the selection
         if (k == kDagTreeMv) rot = G.size() * (size_t)(1 + luts->mvs[tree].k);   // one multi-value rotation + k selections
         if (rot > plan.max_rot) plan.max_rot = rot;
@@ -330,6 +433,9 @@ int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify cla
             for (const auto &kv : mvn[d]) emit(d, 0, kDagMv, kv.second, kv.first);
             for (const auto &kv : tmv[d]) emit(d, 0, kDagTreeMv, kv.second, kv.first);
         }
+        if (lhe)
+            for (int q = 0; q < 3; q++)
+                for (const auto &kv : lhg[q][d]) emit(d, 0, kDagLheLookup + q, kv.second, kv.first);
         for (size_t q = 0; q < lin[d].size(); q++) emit(d, (int32_t)q + 1, 2, lin[d][q]);
     }
     return THFHE_OK;
@@ -369,7 +475,7 @@ template <typename Classify>
 int dag_tree_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs, int n_specs, const int32_t *tv,
                   int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc, const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1,
                   int n_tv1_rows, const int32_t *out_wires, size_t n_out, const int32_t *outputs, Classify classify, DagPlan &plan,
-                  const DagMvFamilies *mv = nullptr) {
+                  const DagMvFamilies *mv = nullptr, const thfhe_dag_lhe_families *lhe = nullptr) {
     if ((!inputs && n_inputs) || (!nodes && n_nodes) || (!outputs && n_nodes) || (!out_wires && n_out)) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if ((!specs && n_specs) || (!tv && n_luts) || ((!enc_a || !enc_b) && n_enc) || (!trees && n_trees) || (!tv1 && n_tv1_rows))
         return thfhe_fail(THFHE_E_INVALID, "null argument: a table family with a count but no pointer");
@@ -386,6 +492,20 @@ int dag_tree_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, 
         if (mv->n_factor_words > ((size_t)1 << 28) || (mv->factors && mv->n_factor_words < 1))
             return thfhe_fail(THFHE_E_INVALID, "n_factor_words must be 1 .. 2^28 (0 with mv_factors = NULL)");
     }
+    if (lhe) {
+        if ((!lhe->sets && lhe->n_sets) || (!lhe->lks && lhe->n_lks) || (!lhe->tab_b && (lhe->n_tab_rows || lhe->tab_a)) || (!lhe->wfas && lhe->n_wfas) ||
+            (!lhe->wfa_words && lhe->n_wfa_words) || (!lhe->fin_b && (lhe->n_fin_rows || lhe->fin_a)))
+            return thfhe_fail(THFHE_E_INVALID, "null argument: a leveled family with a count but no pointer");
+        if (lhe->n_sets < 0 || lhe->n_sets > 64 || (lhe->sets && lhe->n_sets < 1)) return thfhe_fail(THFHE_E_INVALID, "lhe: n_sets must be 1 .. 64 (0 with sets = NULL)");
+        if (lhe->n_lks < 0 || lhe->n_lks > 1024 || (lhe->lks && lhe->n_lks < 1)) return thfhe_fail(THFHE_E_INVALID, "lhe: n_lks must be 1 .. 1024 (0 with lks = NULL)");
+        if (lhe->n_wfas < 0 || lhe->n_wfas > 1024 || (lhe->wfas && lhe->n_wfas < 1)) return thfhe_fail(THFHE_E_INVALID, "lhe: n_wfas must be 1 .. 1024 (0 with wfas = NULL)");
+        if (lhe->n_tab_rows < 0 || lhe->n_tab_rows > (1 << 18) || (lhe->tab_b && lhe->n_tab_rows < 1))
+            return thfhe_fail(THFHE_E_INVALID, "lhe: n_tab_rows must be 1 .. 262144 (0 with tab_b = NULL)");
+        if (lhe->n_fin_rows < 0 || lhe->n_fin_rows > (1 << 18) || (lhe->fin_b && lhe->n_fin_rows < 1))
+            return thfhe_fail(THFHE_E_INVALID, "lhe: n_fin_rows must be 1 .. 262144 (0 with fin_b = NULL)");
+        if (lhe->n_wfa_words > ((size_t)1 << 28) || (lhe->wfa_words && lhe->n_wfa_words < 1))
+            return thfhe_fail(THFHE_E_INVALID, "lhe: n_wfa_words must be 1 .. 2^28 (0 with wfa_words = NULL)");
+    }
     for (int s = 0; s < n_specs; s++)
         THFHE_TRY(lut_spec_check(specs[s]));
     for (int t = 0; t < n_trees; t++) {
@@ -401,6 +521,7 @@ int dag_tree_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, 
     if (mv) {
         luts.mv = true, luts.mvs = mv->mvs, luts.n_mvs = mv->mvs ? mv->n_mvs : 0, luts.n_bases = mv->tv0 ? mv->n_bases : 0;
         luts.n_factor_words = mv->factors ? mv->n_factor_words : 0;
+        luts.lhe = lhe;
     }
     return dag_plan(nodes, n_inputs, n_nodes, classify, plan, &luts);
 }
@@ -434,6 +555,7 @@ struct DagExtGroup {
     const int32_t *t0, *t1, *t2, *t_out, *t_y;
     long all, cnt;
     size_t n_wires;
+    size_t off = 0;   // the group's index columns in plan.tab, for an engine that walks the nodes on the host (the leveled groups)
 };
 
 // Device-resident executor.  Level by level, each class of a level as slices of at most `slice_cap` gates over ALL instances: gather ->
@@ -489,7 +611,7 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
         }
         if (cls >= kDagSelect) {
             if constexpr (!std::is_same_v<RunExt, std::nullptr_t>)
-                rc = run_ext(DagExtGroup{cls, plan.batches[b].tree, d_wires, t0, t1, t2, t_out, t_out + 2 * cnt, all, cnt, n_wires});
+                rc = run_ext(DagExtGroup{cls, plan.batches[b].tree, d_wires, t0, t1, t2, t_out, t_out + 2 * cnt, all, cnt, n_wires, plan.batches[b].off});
             continue;
         }
         if (cls >= 4) {   // LUT groups, and LUT_ENC groups over the run's encrypted tables

@@ -403,6 +403,44 @@ int lhe_cmux(thfhe_ctx *c, const thfhe_tgsw_set *set, int bit, const int32_t *d1
     return THFHE_OK;
 }
 
+// The launch chain of a leveled lookup over S samples, on device pointers only (thfhe_lhe_lookup's slices and the LOOKUP / GATHER groups of the gate
+// DAG): the CMux tree, the rotations, and with ks_out the key switch of the S theta records into it (else they stay in d_u).  spec: the
+// spectra at the first sample.  Sample s reads the 2^d_tree table polynomials at (t_a, t_b) + index(s) * tab_stride words, index(s) = idx[s] or s
+// (t_a null: a public table).  The caller has sized d_lhe_a / d_lhe_b (S 2^(d_tree-1) polynomials each), d_u and ks_out.  prof: record the
+// profiling events.
+int enqueue_lhe_lookup(thfhe_ctx *c, const cplx *spec, int d, size_t S, int d_tree, int d_rot, int theta, const int32_t *t_a, const int32_t *t_b,
+                       const int32_t *idx, size_t tab_stride, int32_t *ks_out, bool prof) {
+    hipStream_t st = c->stream;
+    const size_t leaves = (size_t)1 << d_tree, ws = d_tree ? leaves / 2 : 0;   // TLWE samples of tree workspace per sample
+    int32_t *const w_a = c->d_lhe_a.as<int32_t>(), *const w_b = c->d_lhe_b.as<int32_t>();
+    if (prof) THFHE_HIP(hipEventRecord(c->ev[0], st));
+    // the tree: level t pairs neighbours on bit d_rot + t; level 0 reads the table, the later levels run in place on the workspace -- the result
+    // of pair p of level t lies at slot p 2^t of the sample, the slot of its own d0, which no other workgroup of the launch touches
+    for (int t = 0; t < d_tree; t++) {
+        LheCmuxArgs a{spec, c->d_tw.as<cplx>(), nullptr, nullptr, nullptr, nullptr, w_a, w_b, nullptr, 0, 0, ws * 1024, 0, d, d_rot + t, c->p.Bgbit};
+        if (t == 0) {
+            a.d0_a = t_a, a.d0_b = t_b, a.d1_a = t_a ? t_a + 1024 : nullptr, a.d1_b = t_b + 1024;
+            a.in_idx = idx, a.in_sample = tab_stride, a.in_pair = 2048, a.out_pair = 1024;
+        } else {
+            const size_t step = (size_t)1024 << t;   // words between the d0 slots of neighbouring pairs
+            a.d0_a = w_a, a.d0_b = w_b, a.d1_a = w_a + step / 2, a.d1_b = w_b + step / 2;
+            a.in_sample = ws * 1024, a.in_pair = step, a.out_pair = step;
+        }
+        THFHE_TRY(launch_lhe_cmux(c, a, leaves >> (t + 1), S, t == 0 && !t_a));
+    }
+    if (prof) THFHE_HIP(hipEventRecord(c->ev[1], st));
+    LheRotArgs r{spec, c->d_tw.as<cplx>(), d_tree ? w_a : t_a, d_tree ? w_b : t_b, d_tree ? nullptr : idx, d_tree ? ws * 1024 : tab_stride,
+                 c->d_u.as<int32_t>(), d, d_rot, 1024 >> d_rot, theta, c->p.Bgbit};
+    THFHE_TRY(launch_lhe_rotate(c, r, S));
+    if (prof) THFHE_HIP(hipEventRecord(c->ev[2], st));
+    if (ks_out) THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), ks_out, S * theta, 1, false));
+    if (prof) {
+        THFHE_HIP(hipEventRecord(c->ev[3], st));
+        c->ev_valid = true;
+    }
+    return THFHE_OK;
+}
+
 // thfhe_lhe_lookup (keyswitch) / thfhe_lhe_lookup_wo_keyswitch: out = count x theta records of n+1 (resp. N+1) words, in slices of at most
 // tree_slice / 2^(d_tree-1) samples (the tree workspace: 2^(d_tree-1) TLWE samples of 8 KiB per sample)
 int lhe_lookup(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta, const int32_t *tab_a,
@@ -439,41 +477,24 @@ int lhe_lookup(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t cou
     if (tab_a) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int32_t>(), tab_a, tab_bytes, hipMemcpyHostToDevice, st));
     const int32_t *const t_a = tab_a ? c->d_tva.as<int32_t>() : nullptr, *const t_b = c->d_tv.as<int32_t>();
     const int32_t *const idx = table_index ? c->d_lut_idx.as<int32_t>() : nullptr;
-    int32_t *const w_a = c->d_lhe_a.as<int32_t>(), *const w_b = c->d_lhe_b.as<int32_t>();
     int32_t *const res = keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>();
     const size_t tab_stride = table_index ? leaves * 1024 : 0;   // without an index every sample reads table 0
     for (size_t s0 = 0; s0 < count; s0 += S_max) {
         const size_t S = std::min(S_max, count - s0);
         const cplx *spec = set->spec.as<cplx>() + (first + s0) * lhe_sample_slots(c, set->d);
         if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        // the tree: level t pairs neighbours on bit d_rot + t; level 0 reads the table, the later levels run in place on the workspace -- the result
-        // of pair p of level t lies at slot p 2^t of the sample, the slot of its own d0, which no other workgroup of the launch touches
-        for (int t = 0; t < d_tree; t++) {
-            LheCmuxArgs a{spec, c->d_tw.as<cplx>(), nullptr, nullptr, nullptr, nullptr, w_a, w_b, nullptr, 0, 0, ws * 1024, 0, set->d, d_rot + t, c->p.Bgbit};
-            if (t == 0) {
-                a.d0_a = t_a, a.d0_b = t_b, a.d1_a = t_a ? t_a + 1024 : nullptr, a.d1_b = t_b + 1024;
-                a.in_idx = idx, a.in_sample = tab_stride, a.in_pair = 2048, a.out_pair = 1024;
-            } else {
-                const size_t step = (size_t)1024 << t;   // words between the d0 slots of neighbouring pairs
-                a.d0_a = w_a, a.d0_b = w_b, a.d1_a = w_a + step / 2, a.d1_b = w_b + step / 2;
-                a.in_sample = ws * 1024, a.in_pair = step, a.out_pair = step;
-            }
-            THFHE_TRY(launch_lhe_cmux(c, a, leaves >> (t + 1), S, t == 0 && !tab_a));
-        }
-        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[1], st));
-        LheRotArgs r{spec, c->d_tw.as<cplx>(), d_tree ? w_a : t_a, d_tree ? w_b : t_b, d_tree ? nullptr : idx, d_tree ? ws * 1024 : (table_index ? 1024 : 0),
-                     c->d_u.as<int32_t>(), set->d, d_rot, 1024 >> d_rot, theta, c->p.Bgbit};
-        THFHE_TRY(launch_lhe_rotate(c, r, S));
-        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[2], st));
-        if (keyswitch) THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), S * theta, 1, false));
-        if (c->profiling && s0 == 0) {
-            THFHE_HIP(hipEventRecord(c->ev[3], st));
-            c->ev_valid = true;
-        }
+        THFHE_TRY(enqueue_lhe_lookup(c, spec, set->d, S, d_tree, d_rot, theta, t_a, t_b, idx, tab_stride, keyswitch ? c->stage.out_ptr() : nullptr,
+                                     c->profiling && s0 == 0));
         THFHE_HIP(hipMemcpyAsync(out + s0 * theta * rec, res, S * theta * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
+}
+
+// compute units of the context's device, asked once per context
+int ctx_cus(thfhe_ctx *c, int *cus) {
+    if (!c->cus) THFHE_HIP(hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    *cus = c->cus;
     return THFHE_OK;
 }
 
@@ -484,6 +505,46 @@ int wfa_chunk_for(const thfhe_ctx *c, int n_states, size_t S, int cus) {
     for (int g = n_states; g > 1; g--)
         if ((size_t)((n_states + g - 1) / g) * S >= (size_t)cus) return g;
     return 1;
+}
+
+// The launch chain of a layered automaton over S samples, on device pointers only (thfhe_lhe_wfa's slices and the WFA groups of the gate DAG, DESIGN
+// 4.18): one launch per step, the extraction, and with ks_out the key switch of the S n_out theta records into it (else they stay in d_u).  Samples
+// first .. first + S - 1 of the sets; step_bit is the HOST array; d_trans / d_start: the transitions and start states on the device; sample s reads
+// its n_states finals at (f_a, f_b) + index(s) * fin_stride words, index(s) = idx[s] or s (f_a null: public).  The caller has sized d_lhe_a / d_lhe_b
+// (S layers each), d_u and ks_out.
+int enqueue_lhe_wfa(thfhe_ctx *c, const thfhe_tgsw_set *const *sets, size_t first, size_t S, int n_steps, int n_states, const int32_t *step_bit,
+                    const int32_t *d_trans, const int32_t *d_start, const int32_t *f_a, const int32_t *f_b, const int32_t *idx, size_t fin_stride, int theta,
+                    int n_out, int cus, int32_t *ks_out, bool prof) {
+    hipStream_t st = c->stream;
+    const size_t recs = (size_t)n_out * theta, layer_words = (size_t)n_states * 2048;
+    int32_t *const layer[2] = {c->d_lhe_a.as<int32_t>(), c->d_lhe_b.as<int32_t>()};
+    if (prof) THFHE_HIP(hipEventRecord(c->ev[0], st));
+    const int chunk = wfa_chunk_for(c, n_states, S, cus);
+    for (int j = n_steps - 1; j >= 0; j--) {
+        const thfhe_tgsw_set *set = sets[step_bit[j] >> 4];
+        LheWfaArgs a{set->spec.as<cplx>() + first * lhe_sample_slots(c, set->d), c->d_tw.as<cplx>(), nullptr, nullptr, layer[j & 1], nullptr,
+                     d_trans + (size_t)j * n_states * 2, 0, 0, set->d, step_bit[j] & 15, c->p.Bgbit, n_states, chunk};
+        const bool last = j == n_steps - 1;   // the first launch: it reads the finals, of the sample's table if there is an index
+        if (last) {
+            a.src_a = f_a, a.src_b = f_b, a.src_idx = idx;
+            a.src_sample = fin_stride, a.src_state = 1024;
+        } else {
+            a.src_a = layer[(j + 1) & 1], a.src_b = a.src_a + 1024;
+            a.src_sample = layer_words, a.src_state = 2048;
+        }
+        THFHE_TRY(launch_lhe_wfa(c, a, S, last && !f_a));
+    }
+    if (prof) THFHE_HIP(hipEventRecord(c->ev[1], st));
+    const LheWfaOutArgs x{layer[0], d_start, c->d_u.as<int32_t>(), n_states, n_out, theta};
+    hipLaunchKernelGGL(sk_lhe_wfa_extract_kernel, dim3((unsigned)recs, (unsigned)S), dim3(64), 0, st, x);
+    THFHE_HIP(hipGetLastError());
+    if (prof) THFHE_HIP(hipEventRecord(c->ev[2], st));
+    if (ks_out) THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), ks_out, S * recs, 1, false));
+    if (prof) {
+        THFHE_HIP(hipEventRecord(c->ev[3], st));
+        c->ev_valid = true;
+    }
+    return THFHE_OK;
 }
 
 // thfhe_lhe_wfa (keyswitch) / thfhe_lhe_wfa_wo_keyswitch: out = count x n_out x theta records of n+1 (resp. N+1) words.  One launch per step on the
@@ -522,7 +583,7 @@ int lhe_wfa(thfhe_ctx *c, const thfhe_tgsw_set *const *sets, int n_sets, size_t 
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
     int cus = 0;
-    THFHE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    THFHE_TRY(ctx_cus(c, &cus));
     // a slice: two layers of n_states TLWE samples per sample within the tree workspace's bound, at most tree_slice output records, one grid.y
     const size_t recs = (size_t)n_out * theta;
     const size_t S_max = std::min({count, (size_t)65535, std::max<size_t>(1, c->tree_slice / (2 * (size_t)n_states)), std::max<size_t>(1, c->tree_slice / recs)});
@@ -543,38 +604,13 @@ int lhe_wfa(thfhe_ctx *c, const thfhe_tgsw_set *const *sets, int n_sets, size_t 
     int32_t *const d_trans = c->d_wfa_tab.as<int32_t>(), *const d_start = d_trans + n_trans;
     THFHE_HIP(hipMemcpyAsync(d_trans, trans, n_trans * sizeof(int32_t), hipMemcpyHostToDevice, st));
     THFHE_HIP(hipMemcpyAsync(d_start, start, n_out * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    int32_t *const layer[2] = {c->d_lhe_a.as<int32_t>(), c->d_lhe_b.as<int32_t>()};
     int32_t *const res = keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>();
     for (size_t s0 = 0; s0 < count; s0 += S_max) {
         const size_t S = std::min(S_max, count - s0);
         if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        const int chunk = wfa_chunk_for(c, n_states, S, cus);
-        for (int j = n_steps - 1; j >= 0; j--) {
-            const thfhe_tgsw_set *set = sets[step_bit[j] >> 4];
-            LheWfaArgs a{set->spec.as<cplx>() + (first + s0) * lhe_sample_slots(c, set->d), c->d_tw.as<cplx>(), nullptr, nullptr, layer[j & 1], nullptr,
-                         d_trans + (size_t)j * n_states * 2, 0, 0, set->d, step_bit[j] & 15, c->p.Bgbit, n_states, chunk};
-            const bool last = j == n_steps - 1;   // the first launch: it reads the finals, of the sample's table if there is an index
-            if (last) {
-                a.src_a = fin_a ? c->d_tva.as<int32_t>() : nullptr, a.src_b = c->d_tv.as<int32_t>();
-                a.src_idx = table_index ? c->d_lut_idx.as<int32_t>() : nullptr;
-                a.src_sample = table_index ? (size_t)n_states * 1024 : 0, a.src_state = 1024;
-            } else {
-                a.src_a = layer[(j + 1) & 1], a.src_b = a.src_a + 1024;
-                a.src_sample = layer_words, a.src_state = 2048;
-            }
-            THFHE_TRY(launch_lhe_wfa(c, a, S, last && !fin_a));
-        }
-        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[1], st));
-        const LheWfaOutArgs x{layer[0], d_start, c->d_u.as<int32_t>(), n_states, n_out, theta};
-        hipLaunchKernelGGL(sk_lhe_wfa_extract_kernel, dim3((unsigned)recs, (unsigned)S), dim3(64), 0, st, x);
-        THFHE_HIP(hipGetLastError());
-        if (c->profiling && s0 == 0) THFHE_HIP(hipEventRecord(c->ev[2], st));
-        if (keyswitch) THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), S * recs, 1, false));
-        if (c->profiling && s0 == 0) {
-            THFHE_HIP(hipEventRecord(c->ev[3], st));
-            c->ev_valid = true;
-        }
+        THFHE_TRY(enqueue_lhe_wfa(c, sets, first + s0, S, n_steps, n_states, step_bit, d_trans, d_start, fin_a ? c->d_tva.as<int32_t>() : nullptr,
+                                  c->d_tv.as<int32_t>(), table_index ? c->d_lut_idx.as<int32_t>() : nullptr, table_index ? (size_t)n_states * 1024 : 0, theta,
+                                  n_out, cus, keyswitch ? c->stage.out_ptr() : nullptr, c->profiling && s0 == 0));
         THFHE_HIP(hipMemcpyAsync(out + s0 * recs * rec, res, S * recs * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     THFHE_HIP(hipStreamSynchronize(st));

@@ -509,6 +509,8 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     DevBuf d_dag_enc_a, d_dag_enc_b, d_dag_tv1;
     // multi-value nodes of the gate DAG (thfhe_dag_run_mv_batch): the run's base vectors and the factor array of all its specs
     DevBuf d_dag_mv_tv0, d_dag_mv_w;
+    // leveled nodes of the gate DAG (thfhe_dag_run_lhe_batch): the run's table polynomials and final weights (masks, bodies) and the automata's word pool
+    DevBuf d_dag_lhe_tab_a, d_dag_lhe_tab_b, d_dag_lhe_fin_a, d_dag_lhe_fin_b, d_dag_lhe_words;
     // leveled lookup (thfhe_lhe_cmux, thfhe_lhe_lookup): the CMux tree's workspace (masks, bodies) and the flat CMux's four operands
     DevBuf d_lhe_a, d_lhe_b, d_lhe_in[4];
     // layered automata (thfhe_lhe_wfa): the two layers alternate between d_lhe_a and d_lhe_b; the transition table and the start states
@@ -516,6 +518,7 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     // leveled scatter (thfhe_lhe_demux, thfhe_lhe_scatter): the demux trees run in d_lhe_a ([sample][leaf][mask | body]); the tables
     // being summed ([masks | bodies][n_tables][2^d_tree][N]) and a slice's value and table indices ([2][samples])
     DevBuf d_sc_tab, d_sc_idx;
+    int cus = 0;         // compute units of the device, asked once (ctx_cus)
     int wfa_chunk = 0;   // states per workgroup of sk_lhe_wfa_step_kernel, 0: chosen per slice (wfa_chunk_for)
     size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate); also the output records (samples x q) per slice of thfhe_mv_lut_bootstrap
     // staging for the host-buffer API
@@ -523,6 +526,14 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     // gate-DAG executor: wire table and index tables (grow-only, reused by every thfhe_dag_run on this context)
     DagBuffers dag;
     size_t dag_slice = 28672;  // gates per launch of a DAG level: 14 x 2048 (a MUX slice is 57 344 rotations); it sizes the staging arrays, not the prologue's grid: the runtime runs grid.y > 65 535 (66 636 rotations in one call, tests/test_gpu_large_batch.py)
+    // thfhe_dag_last_group_ms: events of their own around a run's last SELECT / TREE / MV / TREE_MV / leveled group (made by the first profiled group);
+    // ev[] stays what the stages record, so thfhe_last_timings answers as it did
+    hipEvent_t grp_ev[2] = {nullptr, nullptr};
+    bool grp_valid = false;
+    ~thfhe_ctx() {
+        for (hipEvent_t e : grp_ev)
+            if (e) (void)hipEventDestroy(e);
+    }
 };
 
 // Device-resident TGSW samples of thfhe_tgsw_set_create: the spectra of count x d address bits, laid out like the bootstrapping key's with
@@ -809,14 +820,21 @@ struct SkDagTables {
     int n_bases = 0;
     const int32_t *mv_factors = nullptr;
     size_t n_factor_words = 0;
+    // thfhe_dag_run_lhe_batch: the leveled families
+    const thfhe_dag_lhe_families *lhe = nullptr;
 };
+
+// the leveled groups of a run (thfhe_dag_lhe.h, after the leveled kernels)
+int sk_dag_lhe_check_sets(const thfhe_ctx *c, const DagPlan &plan, const thfhe_dag_lhe_families &F, size_t instances);
+int sk_dag_lhe_reserve(thfhe_ctx *c, const DagPlan &plan, const thfhe_dag_lhe_families &F, size_t instances, size_t &w_cand);
+int sk_dag_lhe_group(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const thfhe_dag_lhe_families &F, const DagExtGroup &g, size_t instances);
 
 // The device side of thfhe_dag_run_lut_batch and thfhe_dag_run_tree_batch, both contexts locked by the caller (pc: null in a run without SELECT /
 // TREE groups).  Gate classes run as in thfhe_dag_run_batch.  A LUT group is one PBS stage on the wire table over the run's plaintext tables
 // (DESIGN 4.9), a LUT_ENC group the same over its encrypted tables.  A SELECT group gathers its candidates into the buffer the box packing reads
 // and runs the tree chain from there; a TREE group runs the whole chain with both prologues reading the wire table.  An MV group is
 // one multi-value PBS stage on the wire table, its q records per node scattered into consecutive wires; a TREE_MV group the k-table chain with both
-// prologues on the wire table.  Everything is enqueued on the gate context's stream.
+// prologues on the wire table.  A leveled group is sk_dag_lhe_group's.  Everything is enqueued on the gate context's stream.
 int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const SkDagTables &T, const int32_t *inputs, size_t n_inputs, size_t n_nodes,
                     size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs) {
     const int words = c->p.n + 1;
@@ -828,7 +846,7 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
     auto mv_slice_of = [&](int mv, size_t all) { return std::min({all, dag_slice, std::max<size_t>(1, tree_slice / ((size_t)T.mvs[mv].k * T.mvs[mv].q))}); };
     size_t w_cand = 0;
     for (const DagBatch &b : plan.batches) {
-        if (b.cls < kDagSelect) continue;
+        if (b.cls < kDagSelect || b.cls >= kDagLheLookup) continue;
         if (b.cls == kDagMv || b.cls == kDagTreeMv) {   // every buffer the group's slices use, the staging output included, before dag_execute takes pointers
             const thfhe_mv_spec &m = T.mvs[b.tree];
             const size_t S = mv_slice_of(b.tree, b.count * instances), k = (size_t)m.k, q = (size_t)m.q;
@@ -848,6 +866,7 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
         THFHE_TRY(tree_workspace(c, S, p, b.cls == kDagTree ? p / theta_lo : 1, theta_lo));
         w_cand = std::max(w_cand, S * p);
     }
+    if (T.lhe) THFHE_TRY(sk_dag_lhe_reserve(c, plan, *T.lhe, instances, w_cand));
     if (w_cand) {
         THFHE_TRY(pack_boxes_reserve(pc, w_cand));
         THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle; from here on its buffers are used on `st`
@@ -867,6 +886,56 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
     THFHE_TRY(upload(c->d_dag_mv_tv0, T.mv_tv0, (size_t)T.n_bases * 1024 * sizeof(int32_t)));
     THFHE_TRY(upload(c->d_dag_mv_w, T.mv_factors, T.n_factor_words * sizeof(int32_t)));
     const unsigned wb = (unsigned)((words + 255) / 256);
+    // one SELECT / TREE / MV / TREE_MV / leveled group of a level
+    auto ext_group = [&](const DagExtGroup &g) -> int {
+        auto no_seam = [](int) { return (int)THFHE_OK; };
+        if (g.cls >= kDagLheLookup) return sk_dag_lhe_group(c, pc, plan, *T.lhe, g, instances);
+        if (g.cls == kDagMv || g.cls == kDagTreeMv) {   // t_y = each node's table
+            const thfhe_mv_spec m = T.mvs[g.tree];
+            const bool is_tree = g.cls == kDagTreeMv;
+            const int outs = is_tree ? m.k : m.q, hi0 = m.lo.n_inputs;
+            const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};
+            const int32_t *const tv0 = c->d_dag_mv_tv0.as<int32_t>() + (size_t)m.base * 1024;
+            const MvArgs mv{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p};
+            const long slice = (long)mv_slice_of(g.tree, (size_t)g.all);
+            for (long first = 0; first < g.all; first += slice) {
+                const long S = std::min(slice, g.all - first);
+                const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
+                if (is_tree) {
+                    const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
+                    THFHE_TRY(enqueue_tree_chain(c, pc, lo, tv0, m.k * m.q, hi, (size_t)S, m.q, c->stage.out_ptr(), no_seam, &mv, (size_t)m.k));
+                } else {
+                    THFHE_TRY(enqueue_pbs(c, lo, (size_t)S, tv0, nullptr, m.q, nullptr, c->stage.out_ptr(), false, &mv));
+                }
+                hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(S * outs), wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires,
+                                   first, S, g.cnt, g.n_wires, words, outs);
+                THFHE_HIP(hipGetLastError());
+            }
+            return (int)THFHE_OK;
+        }
+        const thfhe_tree_spec ts = T.trees[g.tree];
+        const int p = ts.p_hi, hi0 = g.cls == kDagTree ? ts.lo.n_inputs : 0;
+        const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the index operands of a TREE node follow its lo.n_inputs level-1 operands
+        const long slice = (long)slice_of(g.tree, (size_t)g.all);
+        for (long first = 0; first < g.all; first += slice) {
+            const long S = std::min(slice, g.all - first);
+            const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
+            if (g.cls == kDagTree) {   // t_y = row0
+                const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {ts.lo}, g.t_y, first, g.cnt, g.n_wires, p / ts.lo.theta};
+                THFHE_TRY(enqueue_tree_chain(c, pc, lo, c->d_dag_tv1.as<int32_t>(), ts.lo.theta, hi, (size_t)S, p, c->stage.out_ptr(), no_seam));
+            } else {                   // SELECT: t_y = first candidate wire
+                const unsigned gy = (unsigned)std::min<long>(S * p, 65535);
+                hipLaunchKernelGGL(dag_select_gather_kernel, dim3(wb, gy), dim3(256), 0, st, (const int32_t *)g.wires, g.t_y, c->d_tree_lwe.as<int32_t>(), first, S,
+                                   g.cnt, g.n_wires, words, p);
+                THFHE_TRY(enqueue_tree_chain(c, pc, nullptr, nullptr, 1, hi, (size_t)S, p, c->stage.out_ptr(), no_seam));
+            }
+            hipLaunchKernelGGL(dag_scatter_kernel, dim3((unsigned)S, wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires, first, S, g.cnt,
+                               g.n_wires, words);
+            THFHE_HIP(hipGetLastError());
+        }
+        return (int)THFHE_OK;
+    };
+    c->grp_valid = false;
     return dag_execute(
         plan, c->dag, st, words, n_inputs, n_nodes, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) { return sk_dag_ensure(c, max_gates, plan.max_theta, in, out); },
@@ -875,52 +944,18 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
             return enqueue_pbs(c, s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, (s.enc ? c->d_dag_enc_b : c->d_tv).as<int32_t>(),
                                s.enc ? c->d_dag_enc_a.as<int32_t>() : nullptr, theta, nullptr, c->stage.out_ptr());
         },
-        [&](const DagExtGroup &g) {
-            auto no_seam = [](int) { return (int)THFHE_OK; };
-            if (g.cls == kDagMv || g.cls == kDagTreeMv) {   // t_y = each node's table
-                const thfhe_mv_spec m = T.mvs[g.tree];
-                const bool is_tree = g.cls == kDagTreeMv;
-                const int outs = is_tree ? m.k : m.q, hi0 = m.lo.n_inputs;
-                const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};
-                const int32_t *const tv0 = c->d_dag_mv_tv0.as<int32_t>() + (size_t)m.base * 1024;
-                const MvArgs mv{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p};
-                const long slice = (long)mv_slice_of(g.tree, (size_t)g.all);
-                for (long first = 0; first < g.all; first += slice) {
-                    const long S = std::min(slice, g.all - first);
-                    const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
-                    if (is_tree) {
-                        const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
-                        THFHE_TRY(enqueue_tree_chain(c, pc, lo, tv0, m.k * m.q, hi, (size_t)S, m.q, c->stage.out_ptr(), no_seam, &mv, (size_t)m.k));
-                    } else {
-                        THFHE_TRY(enqueue_pbs(c, lo, (size_t)S, tv0, nullptr, m.q, nullptr, c->stage.out_ptr(), false, &mv));
-                    }
-                    hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(S * outs), wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires,
-                                       first, S, g.cnt, g.n_wires, words, outs);
-                    THFHE_HIP(hipGetLastError());
-                }
-                return (int)THFHE_OK;
-            }
-            const thfhe_tree_spec ts = T.trees[g.tree];
-            const int p = ts.p_hi, hi0 = g.cls == kDagTree ? ts.lo.n_inputs : 0;
-            const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the index operands of a TREE node follow its lo.n_inputs level-1 operands
-            const long slice = (long)slice_of(g.tree, (size_t)g.all);
-            for (long first = 0; first < g.all; first += slice) {
-                const long S = std::min(slice, g.all - first);
-                const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
-                if (g.cls == kDagTree) {   // t_y = row0
-                    const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {ts.lo}, g.t_y, first, g.cnt, g.n_wires, p / ts.lo.theta};
-                    THFHE_TRY(enqueue_tree_chain(c, pc, lo, c->d_dag_tv1.as<int32_t>(), ts.lo.theta, hi, (size_t)S, p, c->stage.out_ptr(), no_seam));
-                } else {                   // SELECT: t_y = first candidate wire
-                    const unsigned gy = (unsigned)std::min<long>(S * p, 65535);
-                    hipLaunchKernelGGL(dag_select_gather_kernel, dim3(wb, gy), dim3(256), 0, st, (const int32_t *)g.wires, g.t_y, c->d_tree_lwe.as<int32_t>(), first, S,
-                                       g.cnt, g.n_wires, words, p);
-                    THFHE_TRY(enqueue_tree_chain(c, pc, nullptr, nullptr, 1, hi, (size_t)S, p, c->stage.out_ptr(), no_seam));
-                }
-                hipLaunchKernelGGL(dag_scatter_kernel, dim3((unsigned)S, wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires, first, S, g.cnt,
-                                   g.n_wires, words);
-                THFHE_HIP(hipGetLastError());
-            }
-            return (int)THFHE_OK;
+        [&](const DagExtGroup &g) -> int {
+            // profiling (thfhe_set_profiling): a pair of events of the group's own around it, first launch to last scatter, for thfhe_dag_last_group_ms;
+            // a later group of the run records over them, a gate level or a stage's ev[] does not touch them
+            if (!c->profiling) return ext_group(g);
+            for (hipEvent_t &e : c->grp_ev)
+                if (!e) THFHE_HIP(hipEventCreate(&e));
+            c->grp_valid = false;
+            THFHE_HIP(hipEventRecord(c->grp_ev[0], st));
+            THFHE_TRY(ext_group(g));
+            THFHE_HIP(hipEventRecord(c->grp_ev[1], st));
+            c->grp_valid = true;
+            return THFHE_OK;
         });
 }
 
@@ -1055,13 +1090,15 @@ int mv_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv0,
 int sk_dag_run_ext_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
                          const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
                          const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const DagMvFamilies *mv, size_t instances,
-                         const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
+                         const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats, const thfhe_dag_lhe_families *lhe = nullptr) {
     DagPlan plan;
     int rc = dag_tree_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, out_wires, n_out,
-                           outputs, sk_dag_classify, plan, mv);
+                           outputs, sk_dag_classify, plan, mv, lhe);
     if (rc) return rc;
     if (stats) plan.fill_stats(stats);   // the plan's figures need no device
     const bool packs = plan.has_tree_groups();
+    if (lhe && !plan.has_lhe_groups()) lhe = nullptr;
+    if (lhe) THFHE_TRY(sk_dag_lhe_check_sets(c, plan, *lhe, instances));   // the sets, then the context
     if (!c || (packs && !pc)) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     if (packs && pack_ctx_device(pc) != c->device)
         return thfhe_fail(THFHE_E_INVALID, "tree: the gate context and the packing context must be on the same device");
@@ -1077,10 +1114,12 @@ int sk_dag_run_ext_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs
     if (instances > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "too many instances");
     SkDagTables T{specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, tv1, n_tv1_rows};
     if (mv) T.mvs = mv->mvs, T.mv_tv0 = mv->tv0, T.n_bases = mv->tv0 ? mv->n_bases : 0, T.mv_factors = mv->factors, T.n_factor_words = mv->factors ? mv->n_factor_words : 0;
+    T.lhe = lhe;
     return sk_dag_run_luts(c, packs ? pc : nullptr, plan, T, inputs, n_inputs, n_nodes, instances, out_wires, n_out, outputs);
 }
 
 #include "thfhe_lhe.h"
+#include "thfhe_dag_lhe.h"
 
 }  // namespace
 
@@ -1161,8 +1200,21 @@ int thfhe_set_ring4_threshold(thfhe_ctx *c, int max_jobs) {
     c->ring4_max_jobs = max_jobs;
     return THFHE_OK;
 }
-int thfhe_set_profiling(thfhe_ctx *c, int enabled) { return ctx_set_profiling(c, enabled); }
+int thfhe_set_profiling(thfhe_ctx *c, int enabled) {
+    THFHE_TRY(ctx_set_profiling(c, enabled));
+    std::lock_guard<std::mutex> g(c->mu);
+    c->grp_valid = false;
+    return THFHE_OK;
+}
 int thfhe_last_timings(thfhe_ctx *c, float ms[4]) { return ctx_last_timings(c, ms); }
+int thfhe_dag_last_group_ms(thfhe_ctx *c, float *ms) {
+    if (!c || !ms) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->profiling || !c->grp_valid) return thfhe_fail(THFHE_E_INVALID, "no profiled group recorded");
+    THFHE_HIP(hipEventSynchronize(c->grp_ev[1]));
+    THFHE_HIP(hipEventElapsedTime(ms, c->grp_ev[0], c->grp_ev[1]));
+    return THFHE_OK;
+}
 
 int thfhe_gates_dev(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1, const int32_t *d2, int32_t *dout, size_t count) {
     if (!c || !d0 || !dout) return thfhe_fail(THFHE_E_INVALID, "null argument");
@@ -1241,6 +1293,17 @@ int thfhe_dag_run_mv_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inpu
     const DagMvFamilies mv{mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words};
     return sk_dag_run_ext_batch(c, pc, inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, &mv,
                                 instances, out_wires, n_out, outputs, stats);
+}
+
+// the same with the leveled families; without them (lhe NULL) it is thfhe_dag_run_mv_batch.
+int thfhe_dag_run_lhe_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                            const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
+                            const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs,
+                            const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, const thfhe_dag_lhe_families *lhe,
+                            size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
+    const DagMvFamilies mv{mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words};
+    return sk_dag_run_ext_batch(c, pc, inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, &mv,
+                                instances, out_wires, n_out, outputs, stats, lhe);
 }
 
 int thfhe_set_dag_slice(thfhe_ctx *c, size_t max_gates) { return ctx_set_dag_slice(c, max_gates); }

@@ -197,6 +197,9 @@ function dag_run_batch(ck::HipCloudKey, inputs::Array{Int32,3}, gates::Matrix{In
     out
 end
 
+# thfhe_dag_run_lhe_batch (leveled nodes on TGSW-encrypted bits, include/thfhe_hip.h): the raw binding, arguments as the C prototype
+dag_run_lhe_batch_raw(a...) = ccall((:thfhe_dag_run_lhe_batch, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Csize_t, Ptr{Int32}, Csize_t, Ptr{Cvoid}, Cint, Ptr{Int32}, Cint, Ptr{Int32}, Ptr{Int32}, Cint, Ptr{Cvoid}, Cint, Ptr{Int32}, Cint, Ptr{Cvoid}, Cint, Ptr{Int32}, Cint, Ptr{Int32}, Csize_t, Ptr{Cvoid}, Csize_t, Ptr{Int32}, Csize_t, Ptr{Int32}, Ptr{Int64}), a...)
+
 # ---- after the gate path: TLweFromLwe / PartialDecrypt / finalDecrypt (src/libthfhe.cpp:270-348) ---------------------------
 mutable struct HipPolyContext
     h::Ptr{Cvoid}

@@ -18,7 +18,8 @@ LIB_PATH = os.environ.get("THFHE_HIP_LIB", os.path.join(os.path.dirname(_HERE), 
 NAND, OR, AND, XOR, XNOR, NOR, ANDNY, ANDYN, ORNY, ORYN, MUX, NOT, COPY, AND3 = range(14)
 LUT, LUT_OUT = 14, 15   # gate-DAG LUT node and its outputs j > 0 (dag_run_lut_batch, dag_run_tree_batch)
 LUT_ENC, SELECT, TREE = 16, 17, 18   # gate-DAG encrypted-table, select and tree nodes (CloudKey.dag_run_tree_batch, dag_run_mv_batch)
-MV, TREE_MV = 19, 20                 # gate-DAG multi-value and k-output multi-value tree nodes (CloudKey.dag_run_mv_batch only)
+MV, TREE_MV = 19, 20                 # gate-DAG multi-value and k-output multi-value tree nodes (CloudKey.dag_run_mv_batch, dag_run_lhe_batch)
+LHE_LOOKUP, LHE_GATHER, LHE_WFA = 21, 22, 23   # gate-DAG leveled nodes on TGSW-encrypted bits (CloudKey.dag_run_lhe_batch only)
 
 MU8 = 1 << 29     # encode_message(1, 8), Torus32      (numeric-functions.jl:86-89)
 MU8_64 = 1 << 61  # encode_message64(1, 8), Torus64    (numeric-functions.jl:92-95)
@@ -150,6 +151,24 @@ class MvSpec(C.Structure):
     _fields_ = [("lo", LutSpec), ("hi", LutSpec)] + [(f, C.c_int32) for f in ("p", "q", "k", "base", "factors_off", "n_tables")]
 
 
+class DagLheSpec(C.Structure):
+    """thfhe_dag_lhe_spec (include/thfhe_hip.h): the set and shape (d_tree, d_rot, theta) of the LHE_LOOKUP / LHE_GATHER nodes of one launch group."""
+    _fields_ = [(f, C.c_int32) for f in ("set", "d_tree", "d_rot", "theta")]
+
+
+class DagWfaSpec(C.Structure):
+    """thfhe_dag_wfa_spec (include/thfhe_hip.h): the shape, sets and word-pool slices of the LHE_WFA nodes of one launch group."""
+    _fields_ = [(f, C.c_int32) for f in ("n_steps", "n_states", "theta", "n_out", "set0", "n_sets", "trans_off", "step_off", "start_off")]
+
+
+class DagLheFamilies(C.Structure):
+    """thfhe_dag_lhe_families (include/thfhe_hip.h)."""
+    _fields_ = [("sets", C.POINTER(C.c_void_p)), ("n_sets", C.c_int32), ("lks", C.POINTER(DagLheSpec)), ("n_lks", C.c_int32),
+                ("tab_a", C.POINTER(C.c_int32)), ("tab_b", C.POINTER(C.c_int32)), ("n_tab_rows", C.c_int32),
+                ("wfas", C.POINTER(DagWfaSpec)), ("n_wfas", C.c_int32), ("wfa_words", C.POINTER(C.c_int32)), ("n_wfa_words", C.c_size_t),
+                ("fin_a", C.POINTER(C.c_int32)), ("fin_b", C.POINTER(C.c_int32)), ("n_fin_rows", C.c_int32)]
+
+
 def _lut_spec(s):
     """LutSpec from a (n_inputs, (w0, w1, w2), bias, theta) tuple (or a LutSpec)."""
     if isinstance(s, LutSpec):
@@ -184,6 +203,10 @@ SIGNATURES = {
     "thfhe_dag_run_mv_batch": (C.c_int, [_vp, _vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, _i32p, _i32p, C.c_int,
                                          C.POINTER(TreeSpec), C.c_int, _i32p, C.c_int, C.POINTER(MvSpec), C.c_int, _i32p, C.c_int, _i32p, C.c_size_t,
                                          C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
+    "thfhe_dag_run_lhe_batch": (C.c_int, [_vp, _vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, _i32p, _i32p, C.c_int,
+                                          C.POINTER(TreeSpec), C.c_int, _i32p, C.c_int, C.POINTER(MvSpec), C.c_int, _i32p, C.c_int, _i32p, C.c_size_t,
+                                          C.POINTER(DagLheFamilies), C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
+    "thfhe_dag_last_group_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "thfhe_bootstrap": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_keyswitch": (C.c_int, [_vp, _i32p, _i32p, C.c_size_t]),
@@ -728,6 +751,39 @@ class CloudKey(_EvalKey):
         fac = None if mv_factors is None else np.ascontiguousarray(mv_factors, np.int32).reshape(-1)
         families = (mv, len(mvs), _p32(tv0), 0 if tv0 is None else tv0.shape[0], _p32(fac), 0 if fac is None else fac.shape[0])
         return self._dag_run_ext(lib().thfhe_dag_run_mv_batch, families, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack)
+
+    def dag_run_lhe_batch(self, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, mvs=(), mv_tv0=None, mv_factors=None,
+                          tgsw_sets=(), lks=(), tab_b=None, tab_a=None, wfas=(), wfa_words=None, fin_b=None, fin_a=None, out_wires=None, pack=None):
+        """dag_run_mv_batch with leveled nodes on TGSW-encrypted bits (thfhe_dag_run_lhe_batch).  tgsw_sets: the TgswSets of this key,
+        instance q reads sample q of each; lks: DagLheSpec or (set, d_tree, d_rot, theta) tuples; tab_b / tab_a: int32[rows][N] table polynomials
+        (tab_a None: public); wfas: DagWfaSpec or (n_steps, n_states, theta, n_out, set0, n_sets, trans_off, step_off, start_off) tuples; wfa_words:
+        int32[words], their pool; fin_b / fin_a: int32[rows][N] final weights; pack: needed when an LHE_GATHER node is present.  Without any leveled
+        family the call is dag_run_mv_batch."""
+        N = self.params.N
+        none = (1, (0, 0, 0), 0, 1)
+        mv = (MvSpec * len(mvs))(*[m if isinstance(m, MvSpec) else MvSpec(_lut_spec(m[0]), _lut_spec(m[1] or none), *[int(v) for v in m[2:]]) for m in mvs]) if len(mvs) else None
+        tv0 = None if mv_tv0 is None else np.ascontiguousarray(mv_tv0, np.int32).reshape(-1, N)
+        fac = None if mv_factors is None else np.ascontiguousarray(mv_factors, np.int32).reshape(-1)
+        tab = lambda a: None if a is None else np.ascontiguousarray(a, np.int32).reshape(-1, N)
+        rows = lambda a: 0 if a is None else a.shape[0]
+        tab_a, tab_b, fin_a, fin_b = tab(tab_a), tab(tab_b), tab(fin_a), tab(fin_b)
+        if (tab_a is not None and (tab_b is None or tab_a.shape != tab_b.shape)) or (fin_a is not None and (fin_b is None or fin_a.shape != fin_b.shape)):
+            raise ValueError("tab_a / fin_a need tab_b / fin_b of the same shape")
+        words = None if wfa_words is None else np.ascontiguousarray(wfa_words, np.int32).reshape(-1)
+        hs = (_vp * len(tgsw_sets))(*[t.h for t in tgsw_sets]) if len(tgsw_sets) else None
+        lk = (DagLheSpec * len(lks))(*[k if isinstance(k, DagLheSpec) else DagLheSpec(*[int(v) for v in k]) for k in lks]) if len(lks) else None
+        wf = (DagWfaSpec * len(wfas))(*[a if isinstance(a, DagWfaSpec) else DagWfaSpec(*[int(v) for v in a]) for a in wfas]) if len(wfas) else None
+        fam = DagLheFamilies(hs, len(tgsw_sets), lk, len(lks), _p32(tab_a), _p32(tab_b), rows(tab_b), wf, len(wfas), _p32(words),
+                             0 if words is None else words.shape[0], _p32(fin_a), _p32(fin_b), rows(fin_b))
+        leveled = len(tgsw_sets) or len(lks) or len(wfas) or tab_b is not None or fin_b is not None or words is not None
+        families = (mv, len(mvs), _p32(tv0), rows(tv0), _p32(fac), 0 if fac is None else fac.shape[0], C.byref(fam) if leveled else None)
+        return self._dag_run_ext(lib().thfhe_dag_run_lhe_batch, families, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack)
+
+    def dag_last_group_ms(self):
+        """Device time of the last SELECT / TREE / MV / TREE_MV / leveled group of the last dag_run_*_batch with set_profiling(True) (thfhe_dag_last_group_ms)."""
+        ms = C.c_float()
+        _check(lib().thfhe_dag_last_group_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def dag_run_tree_batch(self, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, out_wires=None, pack=None):
         """dag_run_lut_batch with encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch, DESIGN 4.12).  nodes: int32[n_nodes][6];

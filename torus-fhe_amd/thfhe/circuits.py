@@ -20,12 +20,19 @@ thfhe_dag_run_tree_batch with the packing context (`pack`); tree_mul_digits mult
 Multi-value nodes (Circuit.mv / tree_mv; single key): q functions of one digit from one rotation on q consecutive wires, and k functions
 of two digits in 1 + k rotations on k consecutive wires, each one level.  Circuits that hold them run on thfhe_dag_run_mv_batch; sbox_digits looks a
 6-bit -> 4-bit table up in one TREE_MV node.
+
+Leveled nodes (Circuit.lhe_lookup / lhe_gather / lhe_wfa; single key): a table lookup, a pick among 2^d computed wires and a layered
+automaton on the client's TGSW-encrypted bits (`tgsw_sets`: instance q reads sample q of every set), each one level and no blind rotation.  Circuits
+that hold them run on thfhe_dag_run_lhe_batch; lhe_array_read reads an array of computed wires at the client's index, wfa_mux_max takes the larger
+of two numbers with one automaton and `width` MUX gates.
 """
 import time
 
 import numpy as np
 
-from . import AND, COPY, LUT, LUT_ENC, LUT_OUT, MUX, MV, NOT, OR, SELECT, TREE, TREE_MV, XOR, _wrap32
+from . import AND, COPY, LHE_GATHER, LHE_LOOKUP, LHE_WFA, LUT, LUT_ENC, LUT_OUT, MUX, MV, NOT, OR, SELECT, TREE, TREE_MV, XOR, _wrap32
+
+_LHE_OPS = (LHE_LOOKUP, LHE_GATHER, LHE_WFA)
 
 
 class Circuit:
@@ -45,6 +52,11 @@ class Circuit:
         self.mv_bases = []    # base vectors int32[N] of the MV / TREE_MV nodes
         self.mv_specs = []    # [lo spec, hi spec or None, p, q, k, base id, [factor tables int32[k][q][p]]] of the MV / TREE_MV launch groups
         self.mv_rows = {}     # gate index of an MV / TREE_MV node -> (mv id, table t of that spec)
+        self.lhe_tab = []     # table polynomials of the LHE_LOOKUP nodes: (body int32[N], mask or None, plaintext polynomial or None), rows of lhe_table
+        self.lhe_fin = []     # final weights of the LHE_WFA nodes, the same triples, rows of lhe_finals
+        self.lhe_specs = []   # (set, d_tree, d_rot, theta) of the LHE_LOOKUP / LHE_GATHER launch groups, deduplicated
+        self.wfa_specs = []   # (trans, step_bit, start, theta, set0, n_sets) of the LHE_WFA launch groups
+        self.lhe_rows = {}    # gate index of a leveled node -> (lk, row0) / (lk, first) / (wfa, fin_row0)
         self._ids = {}
 
     def inputs(self, count):
@@ -53,7 +65,7 @@ class Circuit:
         self.n_inputs += count
         return ids
 
-    def gate(self, op, a, b=-1, c=-1):
+    def gate(self, op, a=-1, b=-1, c=-1):
         self.gates.append((op, a, b, c))
         return self.n_inputs + len(self.gates) - 1
 
@@ -241,6 +253,109 @@ class Circuit:
         hi = (len(hi_inputs), tuple(_wrap32(v) for v in list(hi_weights) + [0] * (3 - len(hi_weights))), _wrap32(hi_bias), 1)
         return self._mv_row(TREE_MV, lo, hi, base, w, lo_inputs + hi_inputs)
 
+    def _lhe_rows(self, store, rows_b, rows_a, plain, what):
+        b = np.ascontiguousarray(rows_b, np.int32)
+        b = b[None] if b.ndim == 1 else b
+        if b.ndim != 2 or b.shape[0] < 1:
+            raise ValueError(f"{what}: expected int32[rows][N]")
+        a = None if rows_a is None else np.ascontiguousarray(rows_a, np.int32).reshape(b.shape)
+        pl = None if plain is None else np.ascontiguousarray(plain, np.int32).reshape(b.shape)
+        if a is None and pl is None:
+            pl = b   # a public polynomial is its own plaintext
+        row0 = len(store)
+        store.extend((b[i], None if a is None else a[i], None if pl is None else pl[i]) for i in range(b.shape[0]))
+        return row0
+
+    def lhe_table(self, rows_b, rows_a=None, plain=None):
+        """Register table polynomials int32[rows][N] of the LHE_LOOKUP nodes (thfhe.lut.lhe_table: 2^d_tree per table; rows_a: the masks of an
+        encrypted table, None: public); returns row0, the index of the first.  plain: the plaintext polynomials of an encrypted table, for simulate."""
+        return self._lhe_rows(self.lhe_tab, rows_b, rows_a, plain, "lhe_table")
+
+    def lhe_finals(self, rows_b, rows_a=None, plain=None):
+        """Register the n_states final weights int32[n_states][N] of an automaton (thfhe.lut.wfa_finals); returns fin_row0.  As lhe_table."""
+        return self._lhe_rows(self.lhe_fin, rows_b, rows_a, plain, "lhe_finals")
+
+    def _lk_id(self, set_id, d_tree, d_rot, theta):
+        key = ("lk", int(set_id), int(d_tree), int(d_rot), int(theta))
+        if set_id < 0 or not 0 <= d_tree <= 6 or not 0 <= d_rot <= 10 or theta not in (1, 2, 4) or theta > (1024 >> d_rot):
+            raise ValueError("leveled node: set_id >= 0, d_tree 0 .. 6, d_rot 0 .. 10, theta 1, 2 or 4 and at most N >> d_rot")
+        if key not in self._ids:
+            self._ids[key] = len(self.lhe_specs)
+            self.lhe_specs.append(key[1:])
+        return self._ids[key]
+
+    def lhe_lookup(self, set_id, row0, d_tree, d_rot, theta=1):
+        """An LHE_LOOKUP node: the table of 2^d_tree polynomials from row0 (lhe_table) read at the address the instance's sample of TGSW set `set_id`
+        encrypts (d_tree + d_rot bits, low bits rotate, high bits pick the polynomial): theta consecutive coefficients from addr_lo N / 2^d_rot.  One
+        level, no rotation key.  Returns the theta output wire ids (consecutive)."""
+        lk = self._lk_id(set_id, d_tree, d_rot, theta)
+        if row0 < 0 or row0 + (1 << d_tree) > len(self.lhe_tab):
+            raise ValueError("row0 + 2^d_tree exceeds the registered table polynomials (lhe_table)")
+        head = self.gate(LHE_LOOKUP)
+        self.lhe_rows[len(self.gates) - 1] = (lk, int(row0))
+        return [head] + [self.gate(LUT_OUT, head) for _ in range(theta - 1)]
+
+    def lhe_gather(self, set_id, first, d_tree, d_rot):
+        """An LHE_GATHER node: the wire among first .. first + 2^d - 1 (d = d_tree + d_rot, all defined above) at the index the instance's sample of
+        TGSW set `set_id` encrypts: box packing of the candidates into 2^d_tree samples and d CMuxes.  1 <= d_rot <= 9.  One level, one output wire."""
+        if not 1 <= d_rot <= 9:
+            raise ValueError("lhe_gather: d_rot must be 1 .. 9")
+        lk = self._lk_id(set_id, d_tree, d_rot, 1)
+        if first < 0 or first + (1 << (d_tree + d_rot)) > self.n_wires():
+            raise ValueError("the candidates first .. first + 2^d - 1 must be wires defined above the node")
+        w = self.gate(LHE_GATHER)
+        self.lhe_rows[len(self.gates) - 1] = (lk, int(first))
+        return w
+
+    def lhe_wfa(self, automaton, set_ids, finals_row0, theta=1):
+        """An LHE_WFA node: the layered automaton (trans, step_bit, finals, start) -- what wfa_less_than and friends return -- on the consecutive TGSW
+        sets set_ids (step_bit = 16 set + bit counts within them), its final weights the n_states rows from finals_row0 (lhe_finals).  One level.
+        Returns the n_out theta output wire ids (consecutive, output-major)."""
+        trans, step_bit, _, start = automaton
+        trans = np.ascontiguousarray(trans, np.int32)
+        step_bit, start = np.ascontiguousarray(step_bit, np.int32).reshape(-1), np.ascontiguousarray(start, np.int32).reshape(-1)
+        set_ids = [int(v) for v in set_ids]
+        if trans.ndim != 3 or trans.shape[2] != 2 or step_bit.shape[0] != trans.shape[0] or not start.shape[0]:
+            raise ValueError("automaton: expected (trans int32[n_steps][n_states][2], step_bit int32[n_steps], finals, start int32[n_out])")
+        if not set_ids or set_ids[0] < 0 or set_ids != list(range(set_ids[0], set_ids[0] + len(set_ids))):
+            raise ValueError("lhe_wfa: set_ids must be consecutive set ids")
+        if theta not in (1, 2, 4):
+            raise ValueError("theta must be 1, 2 or 4")
+        if finals_row0 < 0 or finals_row0 + trans.shape[1] > len(self.lhe_fin):
+            raise ValueError("finals_row0 + n_states exceeds the registered final weights (lhe_finals)")
+        key = ("wfa", trans.shape, trans.tobytes(), step_bit.tobytes(), start.tobytes(), int(theta), set_ids[0], len(set_ids))
+        if key not in self._ids:
+            self._ids[key] = len(self.wfa_specs)
+            self.wfa_specs.append((trans, step_bit, start, int(theta), set_ids[0], len(set_ids)))
+        head = self.gate(LHE_WFA)
+        self.lhe_rows[len(self.gates) - 1] = (self._ids[key], int(finals_row0))
+        return [head] + [self.gate(LUT_OUT, head) for _ in range(start.shape[0] * theta - 1)]
+
+    def has_lhe_nodes(self):
+        """Whether the circuit holds an LHE_LOOKUP, LHE_GATHER or LHE_WFA node (it then runs on thfhe_dag_run_lhe_batch)."""
+        return bool(self.lhe_rows)
+
+    def n_lhe_sets(self):
+        """TGSW sets the leveled nodes name: one more than the largest set id."""
+        return max([k[0] + 1 for k in self.lhe_specs] + [a[4] + a[5] for a in self.wfa_specs] + [0])
+
+    def lhe_families(self):
+        """The leveled keyword arguments of CloudKey.dag_run_lhe_batch but the sets: lks, tab_b, tab_a, wfas, wfa_words, fin_b, fin_a.  A family with
+        any encrypted row carries zero masks for its public rows."""
+        def rows(store):
+            if not store:
+                return None, None
+            enc = any(r[1] is not None for r in store)
+            return np.stack([r[0] for r in store]), (np.stack([np.zeros_like(r[0]) if r[1] is None else r[1] for r in store]) if enc else None)
+        wfas, words, off = [], [], 0
+        for trans, step_bit, start, theta, set0, n_sets in self.wfa_specs:
+            wfas.append((trans.shape[0], trans.shape[1], theta, start.shape[0], set0, n_sets, off, off + trans.size, off + trans.size + step_bit.size))
+            words += [trans.reshape(-1), step_bit, start]
+            off += trans.size + step_bit.size + start.size
+        tab_b, tab_a = rows(self.lhe_tab)
+        fin_b, fin_a = rows(self.lhe_fin)
+        return dict(lks=list(self.lhe_specs), tab_b=tab_b, tab_a=tab_a, wfas=wfas, wfa_words=np.concatenate(words) if words else None, fin_b=fin_b, fin_a=fin_a)
+
     def has_mv_nodes(self):
         """Whether the circuit holds an MV or TREE_MV node (it then runs on thfhe_dag_run_mv_batch)."""
         return bool(self.mv_rows)
@@ -264,8 +379,9 @@ class Circuit:
 
     def nodes(self):
         """int32[n_gates][6] = (op, in0, in1, in2, spec, lut): the rows of thfhe_dag_run_lut_batch (spec = lut = -1 on gate rows); LUT_ENC, SELECT and
-        TREE rows (thfhe_dag_run_tree_batch) carry (spec, etab), (tree, first), (tree, row0); MV and TREE_MV rows (thfhe_dag_run_mv_batch) (mv, t)."""
-        rows = [tuple(g) + (self.lut_rows.get(i) or self.ext_rows.get(i) or self.mv_rows.get(i, (-1, -1))) for i, g in enumerate(self.gates)]
+        TREE rows (thfhe_dag_run_tree_batch) carry (spec, etab), (tree, first), (tree, row0); MV and TREE_MV rows (thfhe_dag_run_mv_batch) (mv, t);
+        LHE_LOOKUP, LHE_GATHER and LHE_WFA rows (thfhe_dag_run_lhe_batch) (lk, row0), (lk, first), (wfa, fin_row0)."""
+        rows = [tuple(g) + (self.lut_rows.get(i) or self.ext_rows.get(i) or self.mv_rows.get(i) or self.lhe_rows.get(i, (-1, -1))) for i, g in enumerate(self.gates)]
         return np.array(rows, np.int32).reshape(-1, 6)
 
     def n_wires(self):
@@ -280,10 +396,13 @@ class Circuit:
             if op == LUT_OUT:
                 d = depth[a]
             else:
-                d = max(depth[w] for w in (a, b, c) if w >= 0)
+                d = max([depth[w] for w in (a, b, c) if w >= 0] + [0])   # a leveled node has no wire operands
                 if op == SELECT:   # its candidates count too
                     ti, first = self.ext_rows[gi]
                     d = max(d, depth[first:first + self.tree_specs[ti][2]].max())
+                if op == LHE_GATHER:
+                    lk, first = self.lhe_rows[gi]
+                    d = max(d, depth[first:first + (1 << (self.lhe_specs[lk][1] + self.lhe_specs[lk][2]))].max())
                 if op not in (NOT, COPY):
                     d += 1
             depth[self.n_inputs + gi] = d
@@ -293,7 +412,7 @@ class Circuit:
 
     def census(self):
         ops = [g[0] for g in self.gates]
-        boot = sum(1 for o in ops if o not in (NOT, COPY, LUT_OUT))
+        boot = sum(1 for o in ops if o not in (NOT, COPY, LUT_OUT) + _LHE_OPS)   # a leveled node takes no blind rotation
         c = dict(gates=len(ops), bootstrapped=boot, mux=ops.count(MUX), rotations=boot + ops.count(MUX),
                  depth=len([l for l in self.levels() if self.gates[l[0]][0] not in (NOT, COPY)]))
         if self.lut_rows:
@@ -304,6 +423,8 @@ class Circuit:
         if self.mv_rows:    # a TREE_MV node: one multi-value rotation + k selection rotations
             extra = sum(self.mv_specs[self.mv_rows[i][0]][4] for i, o in enumerate(ops) if o == TREE_MV)
             c.update(rotations=c["rotations"] + extra, mvs=ops.count(MV), tree_mvs=ops.count(TREE_MV))
+        if self.lhe_rows:
+            c.update(lhe_lookups=ops.count(LHE_LOOKUP), lhe_gathers=ops.count(LHE_GATHER), lhe_wfas=ops.count(LHE_WFA))
         return c
 
 
@@ -863,6 +984,41 @@ def wfa_noise_steps(automaton, bits):
     return steps
 
 
+# ---- leveled nodes among gates ---------------------------------------------------------------------------------------------------
+def lhe_array_read(cir, wires, set_id, d_tree, d_rot):
+    """Read an array of computed wires at the client's index: wires[addr] for the address the instance's sample of TGSW set `set_id` encrypts
+    (d_tree + d_rot bits, len(wires) = 2^(d_tree + d_rot)).  A GATHER takes consecutive wires, so wires that are not consecutive are copied
+    first (COPY costs no bootstrap).  Returns the output wire."""
+    wires = [int(w) for w in wires]
+    if len(wires) != 1 << (d_tree + d_rot):
+        raise ValueError("lhe_array_read: expected 2^(d_tree + d_rot) wires")
+    if wires != list(range(wires[0], wires[0] + len(wires))):
+        wires = [cir.gate(COPY, w) for w in wires]
+    return cir.lhe_gather(set_id, wires[0], d_tree, d_rot)
+
+
+def wfa_mux_max(cir, a_wires, b_wires, set_ids, width, N=1024):
+    """max(a, b) of two `width`-bit numbers the circuit holds as gate bits (MSB first) and the client also sent as TGSW bits (wfa_pair_bits over the
+    consecutive sets set_ids): a < b comes from the leveled automaton wfa_less_than with no bootstrap -- its final weights are the gate bits
+    +-1/8 as trivial samples, 1/8 in the accepting state -- and drives `width` bootstrapped MUX gates over the LWE bits.  Returns the wires of the
+    maximum, MSB first."""
+    a_wires, b_wires = list(a_wires), list(b_wires)
+    if len(a_wires) != width or len(b_wires) != width:
+        raise ValueError("wfa_mux_max: expected `width` wires per number")
+    aut = wfa_less_than(width)
+    fin = np.zeros((aut[0].shape[1], N), np.int32)
+    fin[:, 0] = np.where(np.asarray(aut[2])[0] == 1, 1 << 29, -(1 << 29))
+    lt = cir.lhe_wfa(aut, set_ids, cir.lhe_finals(fin))[0]
+    return [cir.gate(MUX, lt, b, a) for a, b in zip(a_wires, b_wires)]
+
+
+def _lhe_plain_bits(lhe_bits, set_id, instance):
+    if lhe_bits is None or set_id >= len(lhe_bits):
+        raise ValueError("simulate: the circuit holds leveled nodes; lhe_bits must give the plain bits of every set")
+    b = np.asarray(lhe_bits[set_id], np.int64)
+    return b[instance] if b.ndim == 2 else b
+
+
 def _tables(ck, cir):
     return np.stack([np.asarray(t, ck._tv_dtype).reshape(ck.params.N) for t in cir.tables])
 
@@ -893,7 +1049,7 @@ def _mv_test_vector(tv0, taps):
     return ((acc + (1 << 31)) % (1 << 32)) - (1 << 31)
 
 
-def _simulate_words(cir, input_words):
+def _simulate_words(cir, input_words, lhe_bits=None, instance=0):
     """simulate for circuits with LUT-type nodes: noiseless Torus32 phase words in (thfhe.lut.encode of the digits; +-2^29 for gate bits), the
     noiseless phase word of every wire out (thfhe.lut.decode gives the digits)."""
     from . import lut
@@ -939,6 +1095,30 @@ def _simulate_words(cir, input_words):
             else:
                 y = lin(hi, ops[lo[0]:lo[0] + hi[0]])
                 v[o:o + k] = [wrap(_rotate_noiseless(y, lut.test_vector(lut._to_i32(np.array(cands, np.int64)), q, N=N), 1)[0]) for cands in outs]
+        elif op in (LHE_LOOKUP, LHE_GATHER):
+            lk, y = cir.lhe_rows[gi]
+            set_id, d_tree, d_rot, theta = cir.lhe_specs[lk]
+            bits = _lhe_plain_bits(lhe_bits, set_id, instance)[:d_tree + d_rot]
+            addr = int(sum(int(bit) << i for i, bit in enumerate(bits)))
+            if op == LHE_GATHER:
+                v[o] = v[y + addr]
+            else:
+                poly = cir.lhe_tab[y + (addr >> d_rot)][2]
+                if poly is None:
+                    raise ValueError("simulate: the encrypted table polynomial was registered without its plaintext")
+                at = (addr & ((1 << d_rot) - 1)) * (len(poly) >> d_rot)
+                v[o:o + theta] = poly[at:at + theta]
+        elif op == LHE_WFA:
+            wi, y = cir.lhe_rows[gi]
+            trans, step_bit, start, theta, set0, n_sets = cir.wfa_specs[wi]
+            state = np.array(start, np.int64)
+            for j, sb in enumerate(step_bit):
+                state = trans[j][state, int(_lhe_plain_bits(lhe_bits, set0 + (sb >> 4), instance)[sb & 15])]
+            for k, q in enumerate(state):
+                poly = cir.lhe_fin[y + int(q)][2]
+                if poly is None:
+                    raise ValueError("simulate: the encrypted final weight was registered without its plaintext")
+                v[o + k * theta:o + (k + 1) * theta] = poly[:theta]
         elif op == NOT:
             v[o] = wrap(-int(v[a]))
         elif op == COPY:
@@ -949,13 +1129,14 @@ def _simulate_words(cir, input_words):
     return lut._to_i32(v)
 
 
-def simulate(cir, input_bits):
-    """Plaintext evaluation of the DAG (wiring check): bool[n_inputs] -> bool[n_wires].  Circuits with LUT, LUT_ENC, SELECT or TREE nodes work on
-    integer digits in their torus encoding: int32[n_inputs] noiseless phase words (thfhe.lut.encode(digit, p); +-2^29 for gate bits) -> the
-    noiseless phase word int32[n_wires] of every wire, which thfhe.lut.decode turns into digits."""
+def simulate(cir, input_bits, lhe_bits=None, instance=0):
+    """Plaintext evaluation of the DAG (wiring check): bool[n_inputs] -> bool[n_wires].  Circuits with LUT, LUT_ENC, SELECT, TREE, multi-value or
+    leveled nodes work on integer digits in their torus encoding: int32[n_inputs] noiseless phase words (thfhe.lut.encode(digit, p); +-2^29 for gate
+    bits) -> the noiseless phase word int32[n_wires] of every wire, which thfhe.lut.decode turns into digits.  lhe_bits (circuits with leveled
+    nodes): the plain bits of every TGSW set, low bit first -- int[d] per set, or int[instances][d] of which row `instance` is read."""
     from . import ANDNY, ANDYN, NAND, NOR, ORNY, ORYN, XNOR
-    if cir.lut_rows or cir.ext_rows or cir.mv_rows:
-        return _simulate_words(cir, input_bits)
+    if cir.lut_rows or cir.ext_rows or cir.mv_rows or cir.lhe_rows:
+        return _simulate_words(cir, input_bits, lhe_bits, instance)
     v = np.zeros(cir.n_wires(), bool)
     v[:cir.n_inputs] = np.asarray(input_bits, bool)
     f = {NAND: lambda a, b: not (a and b), OR: lambda a, b: a or b, AND: lambda a, b: a and b, XOR: lambda a, b: a != b,
@@ -997,25 +1178,30 @@ def simulate_mk(cir, input_bits):
 
 
 # ---- evaluator --------------------------------------------------------------------------------------------------------
-def _run_tree_batch(ck, cir, x, sel, pack):
+def _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets=None):
     enc = cir.enc_tables
     args = (x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None, np.stack([e[0] for e in enc]) if enc else None,
             np.stack([e[1] for e in enc]) if enc else None, cir.tree_specs, np.stack(cir.tv1) if cir.tv1 else None)
+    if cir.has_lhe_nodes():
+        if tgsw_sets is None or len(tgsw_sets) < cir.n_lhe_sets():
+            raise ValueError("the circuit holds leveled nodes: tgsw_sets must give the %d TgswSets they name" % cir.n_lhe_sets())
+        return ck.dag_run_lhe_batch(*args, *cir.mv_families(), tgsw_sets=list(tgsw_sets), **cir.lhe_families(), out_wires=sel, pack=pack)
     if cir.has_mv_nodes():
         return ck.dag_run_mv_batch(*args, *cir.mv_families(), sel, pack)
     return ck.dag_run_tree_batch(*args, sel, pack)
 
 
-def evaluate(ck, cir, input_records, stats=None, pack=None):
+def evaluate(ck, cir, input_records, stats=None, pack=None, tgsw_sets=None):
     """Run the DAG on the engine.  input_records: int32[n_inputs][n+1].  Returns int32[n_wires][n+1].
     Single-key contexts use the native scheduler / executor (thfhe_dag_run: wires stay in HBM, no host round trip per level);
     multi-key contexts go level by level through thfhe_mk_gates_mixed (evaluate_levels).  Circuits with LUT nodes run on
     thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch, circuits with encrypted-table, select or tree nodes on thfhe_dag_run_tree_batch
-    (pack: the threshold.PolyContext holding the packing key)."""
-    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes():
+    (pack: the threshold.PolyContext holding the packing key), circuits with leveled nodes on thfhe_dag_run_lhe_batch (tgsw_sets: the TgswSets they
+    name; sample 0 is read)."""
+    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes():
         x = np.ascontiguousarray(input_records, np.int32).reshape(1, cir.n_inputs, ck.words)
-        if cir.has_tree_nodes() or cir.has_mv_nodes():
-            out, st = _run_tree_batch(ck, cir, x, None, pack)
+        if cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes():
+            out, st = _run_tree_batch(ck, cir, x, None, pack, tgsw_sets)
         else:
             out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir))
         if stats is not None:
@@ -1029,19 +1215,20 @@ def evaluate(ck, cir, input_records, stats=None, pack=None):
     return evaluate_levels(ck, cir, input_records, stats)
 
 
-def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None, pack=None):
+def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None, pack=None, tgsw_sets=None):
     """`instances` evaluations of one DAG side by side.  input_records: int32[instances][n_inputs][words]; out_wires: wire ids to return
     (None: every wire).  Returns int32[instances][len(out_wires) or n_wires][words].  Contexts with the native executor use
     thfhe_dag_run_batch / thfhe_mk_dag_run_batch (wire tables stay in HBM), circuits with LUT nodes thfhe_dag_run_lut_batch /
     thfhe_mk_dag_run_lut_batch, circuits with encrypted-table, select or tree nodes thfhe_dag_run_tree_batch (pack: the threshold.PolyContext
-    holding the packing key); others are driven level by level from the host, a level's call holding the gates of all instances."""
+    holding the packing key), circuits with leveled nodes thfhe_dag_run_lhe_batch (tgsw_sets: the TgswSets they name, instance q reads sample q);
+    others are driven level by level from the host, a level's call holding the gates of all instances."""
     x = np.ascontiguousarray(input_records, np.int32)
     Q, n_in, words = x.shape
     assert n_in == cir.n_inputs
-    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or hasattr(ck, "dag_run_batch"):
+    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or hasattr(ck, "dag_run_batch"):
         sel = None if out_wires is None else np.asarray(out_wires, np.int32)
-        if cir.has_tree_nodes() or cir.has_mv_nodes():
-            out, st = _run_tree_batch(ck, cir, x, sel, pack)
+        if cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes():
+            out, st = _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets)
         elif cir.has_luts():
             out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir), sel)
         else:
@@ -1137,11 +1324,42 @@ def _levels_mv(ck, cir, level, vals, pack):
     return len(by)
 
 
-def evaluate_levels(ck, cir, input_records, stats=None, pack=None):
+def _levels_lhe(ck, cir, level, vals, pack, tgsw_sets, instance):
+    """The leveled nodes of one level through the public flat calls on sample `instance` of the sets (lhe_lookup; PackBoxes + lhe_lookup; lhe_wfa),
+    one call per node; returns the number of calls."""
+    from .threshold import PackBoxes
+    gates, base, calls = cir.gates, cir.n_inputs, 0
+    fam = cir.lhe_families()
+    for g in level:
+        op = gates[g][0]
+        if op not in _LHE_OPS:
+            continue
+        x, y = cir.lhe_rows[g]
+        calls += 1
+        if op == LHE_WFA:
+            trans, step_bit, start, theta, set0, n_sets = cir.wfa_specs[x]
+            n = trans.shape[1]
+            r = ck.lhe_wfa(list(tgsw_sets[set0:set0 + n_sets]), trans, step_bit, fam["fin_b"][y:y + n], start, theta=theta,
+                           fin_a=None if fam["fin_a"] is None else fam["fin_a"][y:y + n], first=instance, count=1)
+            vals[base + g:base + g + start.shape[0] * theta] = r[0].reshape(-1, r.shape[-1])
+            continue
+        set_id, d_tree, d_rot, theta = cir.lhe_specs[x]
+        if op == LHE_GATHER:
+            tab_a, tab_b = PackBoxes(pack, vals[y:y + (1 << (d_tree + d_rot))], 1 << d_rot)
+        else:
+            tab_b = fam["tab_b"][y:y + (1 << d_tree)]
+            tab_a = None if fam["tab_a"] is None else fam["tab_a"][y:y + (1 << d_tree)]
+        r = ck.lhe_lookup(tgsw_sets[set_id], tab_b, d_tree=d_tree, d_rot=d_rot, theta=theta, tab_a=tab_a, first=instance, count=1)
+        vals[base + g:base + g + theta] = r[0]
+    return calls
+
+
+def evaluate_levels(ck, cir, input_records, stats=None, pack=None, tgsw_sets=None, instance=0):
     """The same schedule driven from the host: one host-buffer call per level (works for single-key and multi-key contexts).  LUT nodes go
     through ck.lut_bootstrap, one call per (theta, spec) of a level: the yardstick of the native LUT-node executor.  LUT_ENC, SELECT and TREE nodes
     go through lut_bootstrap_enc, PackBoxes + lut_bootstrap_enc and tree_lut_bootstrap (pack: the packing context): the yardstick of
-    thfhe_dag_run_tree_batch.  MV and TREE_MV nodes go through mv_lut_bootstrap and tree_lut_bootstrap_mvk: the yardstick of thfhe_dag_run_mv_batch."""
+    thfhe_dag_run_tree_batch.  MV and TREE_MV nodes go through mv_lut_bootstrap and tree_lut_bootstrap_mvk: the yardstick of thfhe_dag_run_mv_batch.
+    Leveled nodes go through lhe_lookup, PackBoxes + lhe_lookup and lhe_wfa on sample `instance` of tgsw_sets: the yardstick of thfhe_dag_run_lhe_batch."""
     from . import AND3 as _AND3
     words = ck.words
     vals = np.zeros((cir.n_wires(), words), np.int32)
@@ -1175,7 +1393,9 @@ def evaluate_levels(ck, cir, input_records, stats=None, pack=None):
             launches += _levels_ext(ck, cir, level, vals, pack)
         if cir.mv_rows:
             launches += _levels_mv(ck, cir, level, vals, pack)
-        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT, LUT_ENC, SELECT, TREE, MV, TREE_MV)]
+        if cir.lhe_rows:
+            launches += _levels_lhe(ck, cir, level, vals, pack, tgsw_sets, instance)
+        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT, LUT_ENC, SELECT, TREE, MV, TREE_MV) + _LHE_OPS]
         mux = [g for g in level if gates[g][0] == MUX]
         and3 = [g for g in level if gates[g][0] == _AND3]   # 3-gen three-input AND: its own gate class (thfhe_mk_gates)
         if and3:
