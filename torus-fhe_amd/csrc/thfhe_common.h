@@ -216,6 +216,26 @@ __device__ __forceinline__ void wave_fft_inv_q(int lane, cplx (&z)[8], cplx *xb,
     wave_transpose_hi3(z);
     invq_seg3(z, r);
 }
+// variant "f": the exchanges of "q", every inter-pass twiddle folded into the butterflies of the following pass (thfhe_lane.h)
+__device__ __forceinline__ void wave_fft_fwd_f(int lane, cplx (&z)[8], cplx *xb, const LaneRootsF &r) {
+    fwdf_seg1(z);
+    wave_transpose_hi3(z);
+    wave_sync();
+    fwdf_seg2_st(lane, z, xb, r);
+    wave_sync();
+    fwdf_seg3(lane, z, xb, r);
+}
+template <bool LEAN>   // LEAN: the two roots are made opaque (in place) per transform, so that their powers are neither shared between transforms nor hoisted
+__device__ __forceinline__ void wave_fft_inv_f(int lane, cplx (&z)[8], cplx *xb, W64 &w, LaneRoots &r, const cplx (&bc)[4]) {
+    if (LEAN) opaque_in_place(w.w1), opaque_in_place(r.s);
+    wave_sync();
+    invf_seg1(lane, z, xb);
+    wave_sync();
+    inv_seg2_ld(lane, z, xb);
+    invf_seg2(z, w);
+    wave_transpose_hi3(z);
+    invf_seg3(z, r, bc);
+}
 // variant "qs" (multi-key kernels, whose LDS has no room for padded buffers): first transpose in registers, pass-1 twiddles from the
 // per-lane roots, second transpose through the XOR-swizzled 512-slot buffer -- one LDS crossing and no T1 table reads per transform
 template <class Roots>

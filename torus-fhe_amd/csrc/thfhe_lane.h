@@ -21,9 +21,10 @@
 // bootstrapping-key spectra.  Spectra never leave this register order, so no permutation pass exists.
 //
 // Exactness.  Torus32 key coefficients are split into two balanced 16-bit limbs; digits are
-// |d| <= 2^(Bgbit-1).  Each limb product sum is an integer of magnitude < 2^37 computed in FP64 with
-// worst-case rounding error < 2^-7, so rounding to nearest recovers it exactly
-// and lo + (hi << 16) mod 2^32 equals the reference's exact product (tgsw_extern_mul_wo_FFT,
+// |d| <= 2^(Bgbit-1).  Each limb product sum is an integer of magnitude M <= rows N 2^(Bgbit-1) 2^15 < 2^37 computed
+// in FP64 with worst-case rounding error < 2^12 u M, u = 2^-53 (derived there for the
+// folded form "f" below: 2^-7.4 for SK-128, 2^-4.4 at the largest shape the engine admits), so rounding to nearest
+// recovers it exactly and lo + (hi << 16) mod 2^32 equals the reference's exact product (tgsw_extern_mul_wo_FFT,
 // 3-gen-mk-tfhe/src/tgsw.jl:152-156).
 #ifndef THFHE_LANE_H
 #define THFHE_LANE_H
@@ -97,7 +98,7 @@ THFHE_FN int xs_d(int j0, int lane) { return (lane >> 3) * 72 + (lane & 7) * 9 +
 
 // ---- forward transform, three segments -------------------------------------------------------------
 // This table form (padded buffer, T1 and T2 read from tables) runs in no product kernel: tests/emu/lane_emu.cpp keeps it as the
-// reference that the "s", "r", "q" and N = 2048 forms below are checked against.
+// reference that the "s", "r", "q" and N = 2048 forms below are checked against ("f": tests/emu/fold_emu.cpp).
 // z[m] on entry: folded coefficients (p[lane + 64 m], p[lane + 64 m + 512])
 THFHE_FN void fwd_seg1(int lane, cplx (&z)[8], cplx *xbuf, const cplx *T1) {
 #pragma unroll
@@ -352,6 +353,13 @@ THFHE_FN cplx opaque_cplx(cplx v) {
 #endif
     return v;
 }
+// The same fence on the variable itself: its value becomes loop-carried in the registers it already occupies (no copy, nothing derived from it
+// is hoisted out of the loop).
+THFHE_FN void opaque_in_place(cplx &v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(v.re), "+v"(v.im));
+#endif
+}
 THFHE_FN void fwdq_seg1(cplx (&z)[8], const LaneTw &t) {
 #pragma unroll
     for (int m = 1; m < 8; m++) z[m] = cmul(z[m], cplx{THFHE_C_RE(m), THFHE_C_IM(m)});
@@ -373,6 +381,119 @@ THFHE_FN void invq_seg3(cplx (&z)[8], const LaneTw &t) {
     dft8<-1>(z);
 #pragma unroll
     for (int m = 1; m < 8; m++) z[m] = cmul_conj(z[m], cplx{THFHE_C_RE(m), THFHE_C_IM(m)});
+}
+
+// ---- variant "f" (eight- and four-wave ring kernel): the exchanges of "q", every inter-pass twiddle FOLDED into the butterflies of the
+// pass that follows it.  A radix-2 butterfly with a twiddle on its second input,
+//     x = a + W b   (two dependent FMAs per component),      a - W b = 2 a - x   (one FMA per component),
+// is 6 FP64 instructions; the separate product (2 mul + 2 fma) followed by the add / sub pair is 8.  Every twiddle set of the transform is
+// the powers W^m of ONE root over the register index m, and a DFT8 whose inputs carry W^m needs only four constants:
+//     stage 1 (m, m + 4):  u_m = y_m + W^4 y_(m+4),  v_m = y_m - W^4 y_(m+4)                 pending W^m on u, (W w8)^m on v   (m < 4)
+//     stage 2 (m, m + 2):  u_m +- W^2 u_(m+2),       v_m +- (i W^2) v_(m+2)                  (i = the quarter turn of the direction S)
+//     stage 3 (0, 1):      roots W, i W on the two u pairs, W w8, i W w8 on the two v pairs  (i W: components swapped, one sign)
+// so 12 folded butterflies = 72 FP64 instructions replace 52 (dft8) + 28 (seven products), and W^2, W^4, W w8 are rebuilt from W in 12.
+// Where the twiddles sit (header comment's notation; lane and register index of each pass as in "q"):
+//   forward   pass 1 over j2: root w32 = C[1] (wave-uniform, compile-time constants; W^4 = C[4] = (R, R) keeps its short form)
+//             pass 2 over j1 (lane = j0 + 8 k0): T1[k0][j0 + 8 j1] = b' s'^j1,  s' = zeta^(8 (4 k0 + 1)): root s'; the common factor
+//                    b' = zeta^(j0 (4 k0 + 1)) rides through the (linear) pass
+//             pass 3 over j0 (lane = k1 + 8 k0): pending b' = (zeta^(4 k0 + 1))^j0 times T2[k1][j0] = (w64^k1)^j0: root w'' = w64^k1 zeta^(4 k0 + 1)
+//   inverse   pass over k2: plain dft8;  pass over k1 (lane = j0 + 8 k0): root conj(w64^j0);  pass over k0 (lane = j0 + 8 j1): root conj(s),
+//             s = zeta^(4 lane);  the untwist conj(b C[m]) = conj(zeta^(lane + 64 m)) is an output-side factor and stays a product.
+// Spectra keep the register order (and, up to rounding, the values) of every other form.
+THFHE_FN void bfly_tw(cplx &a, cplx &b, cplx W) {   // (a, b) <- (a + W b, a - W b)
+    const cplx x{__builtin_fma(-W.im, b.im, __builtin_fma(W.re, b.re, a.re)), __builtin_fma(W.im, b.re, __builtin_fma(W.re, b.im, a.im))};
+    b = cplx{__builtin_fma(2.0, a.re, -x.re), __builtin_fma(2.0, a.im, -x.im)};
+    a = x;
+}
+THFHE_FN void bfly_c4(cplx &a, cplx &b) {   // W = C[4] = (R, R): W b = R (b.re - b.im, b.re + b.im), both outputs rounded once
+    constexpr double R = 0.70710678118654752440;
+    const double t = b.re - b.im, u = b.re + b.im;
+    b = cplx{__builtin_fma(-R, t, a.re), __builtin_fma(-R, u, a.im)};
+    a = cplx{__builtin_fma(R, t, a.re), __builtin_fma(R, u, a.im)};
+}
+struct RootPow {  // W, W^2, W^4 and W w8 (w8 = exp(S 2 pi i / 8)) of one root
+    cplx w1, w2, w4, w1o;
+};
+THFHE_FN cplx csqr(cplx a) { return cplx{__builtin_fma(a.re, a.re, -(a.im * a.im)), (a.re + a.re) * a.im}; }
+template <int S>
+THFHE_FN RootPow root_powers(cplx w) {
+    constexpr double R = 0.70710678118654752440;
+    RootPow p;
+    p.w1 = w;
+    p.w2 = csqr(w);
+    p.w4 = csqr(p.w2);
+    p.w1o = S > 0 ? cplx{R * (w.re - w.im), R * (w.re + w.im)} : cplx{R * (w.re + w.im), R * (w.im - w.re)};
+    return p;
+}
+// stages 2 and 3 and the reordering, shared by the per-lane and the uniform form
+template <int S>
+THFHE_FN void dft8_tw_tail(cplx (&y)[8], cplx w1, cplx w2, cplx w1o) {
+    bfly_tw(y[0], y[2], w2);
+    bfly_tw(y[1], y[3], w2);
+    bfly_tw(y[4], y[6], mul_si<S>(w2));
+    bfly_tw(y[5], y[7], mul_si<S>(w2));
+    bfly_tw(y[0], y[1], w1);            // -> X0, X4
+    bfly_tw(y[2], y[3], mul_si<S>(w1));   // -> X2, X6
+    bfly_tw(y[4], y[5], w1o);           // -> X1, X5
+    bfly_tw(y[6], y[7], mul_si<S>(w1o));  // -> X3, X7
+    const cplx x4 = y[1], x2 = y[2], x6 = y[3], x1 = y[4], x5 = y[5], x3 = y[6];
+    y[1] = x1;
+    y[2] = x2;
+    y[3] = x3;
+    y[4] = x4;
+    y[5] = x5;
+    y[6] = x6;
+}
+// y[k] <- sum_m y[m] W^m exp(S 2 pi i m k / 8), natural order in and out; p = root_powers<S>(W)
+template <int S>
+THFHE_FN void dft8_tw(cplx (&y)[8], const RootPow &p) {
+#pragma unroll
+    for (int m = 0; m < 4; m++) bfly_tw(y[m], y[m + 4], p.w4);
+    dft8_tw_tail<S>(y, p.w1, p.w2, p.w1o);
+}
+// the same with the wave-uniform root W = w32 = C[1] (the twist of pass 1, forward): W^2 = C[2], W^4 = C[4], W w8 = C[5]
+THFHE_FN void dft8_tw_c32(cplx (&y)[8]) {
+#pragma unroll
+    for (int m = 0; m < 4; m++) bfly_c4(y[m], y[m + 4]);
+    dft8_tw_tail<+1>(y, cplx{THFHE_C_RE(1), THFHE_C_IM(1)}, cplx{THFHE_C_RE(2), THFHE_C_IM(2)}, cplx{THFHE_C_RE(5), THFHE_C_IM(5)});
+}
+struct LaneRootsF {  // forward roots of "f": s = zeta^(8 (4 (lane >> 3) + 1)), w = w64^(lane & 7) zeta^(4 (lane >> 3) + 1)
+    cplx s, w;
+};
+THFHE_FN void fwdf_seg1(cplx (&z)[8]) { dft8_tw_c32(z); }
+THFHE_FN void fwdf_seg2_st(int lane, cplx (&z)[8], cplx *xbuf, const LaneRootsF &r) {
+    dft8_tw<+1>(z, root_powers<+1>(r.s));
+#pragma unroll
+    for (int k1 = 0; k1 < 8; k1++) xbuf[xs_c(k1, lane)] = z[k1];
+}
+THFHE_FN void fwdf_seg3(int lane, cplx (&z)[8], const cplx *xbuf, const LaneRootsF &r) {
+    fwd_seg3_ld(lane, z, xbuf);
+    dft8_tw<+1>(z, root_powers<+1>(r.w));
+}
+// inverse of "f", from the roots of "q" (w64, b, s).  The untwist constants b C[m] = zeta^(lane + 64 m), m < 4, are built once per CMux for its four
+// inverse transforms (outputs m + 4 take conj(C[4]) = R (1 - i) first: four instructions, no constant); the powers of the two conjugate roots are
+// rebuilt in every transform (12 FP64 instructions each): sharing them as well costs 12 registers per root, and the eight-wave kernel then spills
+// (measured: 6 spilled registers cost more than the 72 instructions saved).
+THFHE_FN cplx cconj(cplx a) { return cplx{a.re, -a.im}; }
+THFHE_FN void make_untwist_f(cplx b, cplx (&bc)[4]) {
+    bc[0] = b;
+#pragma unroll
+    for (int m = 1; m < 4; m++) bc[m] = cmul(b, cplx{THFHE_C_RE(m), THFHE_C_IM(m)});
+}
+THFHE_FN void invf_seg1(int lane, cplx (&z)[8], cplx *xbuf) {
+    dft8<-1>(z);
+#pragma unroll
+    for (int j0 = 0; j0 < 8; j0++) xbuf[xs_d(j0, lane)] = z[j0];
+}
+THFHE_FN void invf_seg2(cplx (&z)[8], const W64 &w) { dft8_tw<-1>(z, root_powers<-1>(cconj(w.w1))); }   // after inv_seg2_ld: pass over k1, root conj(w64^j0)
+THFHE_FN void invf_seg3(cplx (&z)[8], const LaneRoots &r, const cplx (&bc)[4]) {                        // after the lane exchange: pass over k0, root conj(s)
+    constexpr double R = 0.70710678118654752440;
+    dft8_tw<-1>(z, root_powers<-1>(cconj(r.s)));
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        z[m] = cmul_conj(z[m], bc[m]);
+        z[m + 4] = cmul_conj(cplx{R * (z[m + 4].re + z[m + 4].im), R * (z[m + 4].im - z[m + 4].re)}, bc[m]);
+    }
 }
 
 // ---- integer helpers ---------------------------------------------------------------------------------
@@ -1058,7 +1179,8 @@ struct TwRing1k {
     static constexpr int T1 = 0;       // [512] T1[k0*64 + lane]
     static constexpr int T2 = 512;     // [64]  T2[k1*8 + j0]; the W64 root of a lane is T2[1*8 + (lane & 7)]
     static constexpr int ROOTS = 576;  // [128] per-lane roots of variant "r"
-    static constexpr int SIZE = 704;
+    static constexpr int ROOTSF = 704; // [128] per-lane forward roots of variant "f"
+    static constexpr int SIZE = 832;
 };
 // N = 2048 and N = 4096
 struct TwRing2k {
@@ -1107,6 +1229,17 @@ inline void make_lane_roots_1024(cplx *roots /*128*/) {
         roots[2 * lane + 1] = cplx{(double)cosl(b), (double)sinl(b)};
     }
 }
+// per-lane forward roots of variant "f" (LaneRootsF): roots[2*lane] = zeta^(8 (4 k0 + 1)), roots[2*lane + 1] = zeta^(32 k1 + 4 k0 + 1) = w64^k1 zeta^(4 k0 + 1),
+// k0 = lane >> 3, k1 = lane & 7
+inline void make_lane_roots_f_1024(cplx *roots /*128*/) {
+    const long double PI = 3.14159265358979323846264338327950288L;
+    for (int lane = 0; lane < 64; lane++) {
+        const int k0 = lane >> 3, k1 = lane & 7;
+        long double a = PI * (long double)(8 * (4 * k0 + 1)) / 1024.0L, b = PI * (long double)(32 * k1 + 4 * k0 + 1) / 1024.0L;
+        roots[2 * lane] = cplx{(double)cosl(a), (double)sinl(a)};
+        roots[2 * lane + 1] = cplx{(double)cosl(b), (double)sinl(b)};
+    }
+}
 // N = 2048, "qs" form: the common ratio s[lane] = exp(i pi 8 lane / 2048) of the pass-1 twiddles (b_T = T1_T[0][lane] comes from the tables)
 inline void make_lane_ratio_2048(cplx *s /*64*/) {
     const long double PI = 3.14159265358979323846264338327950288L;
@@ -1140,6 +1273,7 @@ inline std::vector<cplx> make_twiddle_table(int N) {
         std::vector<cplx> tw(TwRing1k::SIZE);
         make_twiddles_1024(tw.data() + TwRing1k::T1, tw.data() + TwRing1k::T2);
         make_lane_roots_1024(tw.data() + TwRing1k::ROOTS);
+        make_lane_roots_f_1024(tw.data() + TwRing1k::ROOTSF);
         return tw;
     }
     std::vector<cplx> tw(TwRing2k::SIZE);

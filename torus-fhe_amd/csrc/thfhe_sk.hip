@@ -149,6 +149,15 @@ constexpr int kGate = 0, kLut = 1, kLutEnc = 2, kLutMv = 3;
 //     some of them; every reload was followed by s_waitcnt vmcnt(0), which also waits for the ring DMAs issued just before the
 //     transform.  Keeping only the even products and forming the odd ones in place (16 more FP64 instructions per transform) removes
 //     those reloads from the transforms.
+// Fourth pass (29.7 -> 28.7 ms): the kernel's time is its FP64 instruction stream (an FP64 wave instruction holds the SIMD's vector pipe for 4 cycles),
+// and a third of that stream was twiddle work.  Transforms of variant "f" (thfhe_lane.h): every inter-pass twiddle sits on the input side of the pass
+// that follows it and is folded into that pass's radix-2 butterflies (a + W b as two dependent FMAs per component, a - W b = 2 a - x as one), a
+// twiddled DFT8 = 72 FP64 instructions against 52 + 28, from four constants per root instead of seven.  Forward: the twist C[m] rides in pass 1
+// (wave-uniform constants), pass 2 and pass 3 take one per-lane root each (TwRing1k::ROOTSF); inverse: the two conjugate roots of "q", the untwist
+// stays a product.  Per CMux and wave 3 582 -> 3 356 FP64 instructions (forward transform 275 -> 240), still 256 VGPRs and no scratch: the roots are
+// made opaque IN PLACE per transform (no register copies), only the four untwist constants are shared by a CMux's inverse transforms.  Sharing one
+// or both roots' powers as well (3 320 / 3 284 instructions) spilled 6 / 15 registers around the inverse phase and measured 0.45 ms SLOWER than this
+// form (profiles/r06_fold_static_counts.md).
 // ------------------------------------------------------------------------------------------------------
 #ifndef THFHE_RING_NF
 #define THFHE_RING_NF 16
@@ -165,7 +174,9 @@ constexpr int kGate = 0, kLut = 1, kLutEnc = 2, kLutMv = 3;
 // LUT = kLut, kLutEnc: programmable bootstrap, the accumulator starts from a test vector (kLutEnc: from a TLWE sample, mask included) and theta
 // coefficients are extracted; kLutMv: multi-value bootstrap, the kLut start on one base vector and a.theta = q outputs, each a
 // p-tap combination of extractions (extract_mv16); the CMux loop is the same code.
-template <int L, int V = 1, int W = 8, int LUT = kGate>
+// V = transform form (bits): 1 = first transpose in registers ("q"; 0 = through the LDS, "r"), 2 = inverse through the LDS all the same,
+// 4 = twiddles folded into the butterflies ("f", with the exchanges of "q": the product form); 0, 1 and 3 remain for A/B runs.
+template <int L, int V = 5, int W = 8, int LUT = kGate>
 __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_kernel(BRArgs a) {
     __shared__ __attribute__((aligned(4096))) int32_t sAcc[W][2048];   // rotated_digits_z ORs byte offsets into the polynomial base
     __shared__ cplx sX[W][kXbufSlots];
@@ -177,6 +188,10 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
     const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
     const LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
     const LaneTw tw = make_lane_tw(roots);
+    // the roots of the "f" path are variables: opaque_in_place makes them loop-carried in the registers they already occupy
+    LaneRootsF rootsf{a.tw[TwRing1k::ROOTSF + 2 * lane], a.tw[TwRing1k::ROOTSF + 2 * lane + 1]};
+    W64 w64f = w64;
+    LaneRoots rootsi = roots;
     const long job = (long)blockIdx.x * W + wave;
     const bool has_job = job < a.jobs;
     int32_t *acc = sAcc[wave];
@@ -240,7 +255,11 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
                 // they are not hoisted out of the CMux loop): 12 fewer registers live across the loop than with the even products kept (LaneTw), the
                 // compiler then parks nothing in scratch (44 -> 0 B per lane: no reload in front of a row's digits waits for the ring DMAs any more) --
                 // 30.21 -> 29.97 ms per 4096 gates.  The four-wave shape (registers to spare) keeps LaneTw: 9.67 against 9.80 ms per 1024 gates.
-                if (!(V & 1)) wave_fft_fwd_r(lane, z, xb, roots, w64);
+                // "f": the two forward roots likewise opaque per transform: their powers (12 FP64 instructions each) are rebuilt, not kept across the loop
+                if (V & 4) {
+                    if (THFHE_RING_LEAN_ROOTS && W == 8) opaque_in_place(rootsf.s), opaque_in_place(rootsf.w);
+                    wave_fft_fwd_f(lane, z, xb, rootsf);
+                } else if (!(V & 1)) wave_fft_fwd_r(lane, z, xb, roots, w64);
                 else if (THFHE_RING_LEAN_ROOTS && W == 8) wave_fft_fwd_q(lane, z, xb, LaneRoots{opaque_cplx(roots.b), opaque_cplx(roots.s)}, w64);
                 else wave_fft_fwd_q(lane, z, xb, tw, w64);
             }
@@ -290,9 +309,19 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
         }
         if (active) {
             wave_sync();
+            // "f": the untwist constants b C[m] are built once per CMux for the four inverse transforms, from a root made opaque here so that they
+            // are not kept across the multiply phase
+            cplx bc[4];
+            if (V & 4) {
+                if (THFHE_RING_LEAN_ROOTS && W == 8) opaque_in_place(rootsi.b);
+                make_untwist_f(rootsi.b, bc);
+            }
 #pragma unroll
             for (int c = 0; c < 2; c++) {
-                if ((V & 1) && !(V & 2)) {
+                if (V & 4) {
+                    wave_fft_inv_f<THFHE_RING_LEAN_ROOTS && W == 8>(lane, S[c][0], xb, w64f, rootsi, bc);
+                    wave_fft_inv_f<THFHE_RING_LEAN_ROOTS && W == 8>(lane, S[c][1], xb, w64f, rootsi, bc);
+                } else if ((V & 1) && !(V & 2)) {
                     if (THFHE_RING_LEAN_ROOTS && W == 8) {
                         wave_fft_inv_q(lane, S[c][0], xb, LaneRoots{opaque_cplx(roots.b), opaque_cplx(roots.s)}, w64);
                         wave_fft_inv_q(lane, S[c][1], xb, LaneRoots{opaque_cplx(roots.b), opaque_cplx(roots.s)}, w64);
@@ -569,17 +598,18 @@ void launch_coop(const BRArgs &a, hipStream_t s) {
 }
 template <int L, int LUT>
 void launch_ring4(const BRArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 1, 4, LUT>), dim3((unsigned)((a.jobs + 3) / 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 5, 4, LUT>), dim3((unsigned)((a.jobs + 3) / 4)), dim3(256), 0, s, a);
 }
 template <int L, int LUT>
 void launch_ring8(const BRArgs &a, hipStream_t s) {
     const dim3 grid((unsigned)((a.jobs + 7) / 8)), block(512);
-#ifdef THFHE_VARIANTS  // developer A/B builds only: 8 = first transpose through the LDS (variant "r")
+#ifdef THFHE_VARIANTS  // developer A/B builds only: 8 = first transpose through the LDS (variant "r"), 1 = "q" (separate twiddle products, the form before "f")
     static const int variant = std::getenv("THFHE_RING_VARIANT") ? std::atoi(std::getenv("THFHE_RING_VARIANT")) : 0;
     if (!LUT && variant == 8) { hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 0>), grid, block, 0, s, a); return; }
+    if (!LUT && variant == 1) { hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 1>), grid, block, 0, s, a); return; }
     if (!LUT && variant == 3) { hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 3>), grid, block, 0, s, a); return; }   // forward in registers, inverse through the LDS
 #endif
-    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 1, 8, LUT>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 5, 8, LUT>), grid, block, 0, s, a);
 }
 
 // Kernel choice for a batch of rotations.  Measured on one MI355X (256 CUs, SK-128; profiles/r04_time_batch.txt): a round of the
