@@ -442,3 +442,82 @@ def lut_enc_reached(p, bk, mu):
     """Exact peak limb sum of step 0 of lut_enc_case, largest over the two output columns."""
     rows = step_digit_rows(np.full((2, p.N), mu, np.int32), p.N, 32, p.l, p.Bgbit)
     return max(peak_limb_sum([(d, bk[0, r, c]) for r, _, d in rows], 32) for c in range(2))
+
+
+# ---- multi-value bootstrap (the kLutMv instantiations of the blind rotations; DESIGN.md section 4.13) -------------------------------------------
+# kLutMv starts like kLut, with the accumulator (0, X^{-barb} tv0): tv0 = mu everywhere, one input of weight 1 and bias 0 make the rotation of
+# sk_case(p, bk, full) the gate's, so sk_reached(...) is the limb sum of its crafted step too.  What differs is the epilogue: output j is the
+# integer combination of the extractions at the p tap coefficients N - box/2 - k box.
+def sk_acc_after(orc, p, x, mu):
+    """The accumulator after the last CMux of the crafted single-key bootstrap (the oracle's schoolbook steps), int32[2N] = (mask, body)."""
+    return sk_acc_before(orc, p, x, mu, p.n).reshape(-1)
+
+
+def mv_factors(rng, n_tables, q, pt):
+    """Factor tables int32[n_tables][q][pt] for the bound cases: output 0 of table t is the single unit tap at k = (pt - 1 - t) mod pt, so its
+    record is minus one plain extraction and shows every bit of the accumulator's mask (an even tap would hide bit 0 behind the product); the
+    other outputs are random int32 taps."""
+    w = rng.integers(-2**31, 2**31, size=(n_tables, q, pt), dtype=np.int64).astype(np.int32)
+    for t in range(n_tables):
+        w[t, 0] = 0
+        w[t, 0, (pt - 1 - t) % pt] = 1
+    return w
+
+
+def mv_tap_positions(N, pt):
+    """the body coefficients an output record of a pt-tap factor table reads"""
+    box = N // pt
+    return [N - box // 2 - k * box for k in range(pt)]
+
+
+# ---- layered automata (sk_lhe_wfa_step_kernel<L, PUB>; DESIGN.md section 4.16) ------------------------------------------------------------------
+def wfa_case(p, n_states, rng=None):
+    """One step of an automaton whose every non-copy state is the CMux of lhe_cmux_case: returns (C int32[2l][2][N], fin int32[n_states][2N],
+    trans int32[n_states][2]).  The finals hold d0 in the even states and d1 = d0 + digit_word in the odd ones; trans[q] = (2 floor(q/2),
+    2 floor(q/2) + 1) except for the last state, a copy of itself.  rng None: d0 = 0; else every pair (and the copy state) gets random words w of
+    its own, (d1, d0) = (w + T, w): the same digits out of non-zero operands, and states that differ from each other.  fin[:, :N] are the masks
+    (fin_a), fin[:, N:] the bodies; the public variant passes the bodies alone and reaches the l-row sum."""
+    C, d1, _ = lhe_cmux_case(p)
+    fin = np.zeros((n_states, 2 * p.N), np.int32)
+    for q in range(0, n_states, 2):
+        if rng is not None:
+            fin[q] = rng.integers(-2**31, 2**31, size=2 * p.N, dtype=np.int64).astype(np.int32)
+        if q + 1 < n_states:
+            fin[q + 1] = _i32(fin[q].astype(np.int64) + d1)
+    trans = np.array([[q & ~1, q | 1] for q in range(n_states)], np.int32)
+    trans[n_states - 1] = n_states - 1
+    return C, fin, trans
+
+
+def wfa_copies(n_states):
+    """a step whose every state is a copy of itself: the layer it writes holds the layer (or the finals) it read"""
+    return np.repeat(np.arange(n_states, dtype=np.int32)[:, None], 2, axis=1)
+
+
+# the automata of tests/test_gpu_wfa_bound.py (and of the CPU checks of the same cases in tests/test_bound_inputs.py): 5 states, the step bits name
+# bit 0 (every word extreme_key_word) and bit 1 (random words) of one set
+WFA_STATES = 5
+WFA_FOLLOW = np.array([[0, 1], [1, 2], [2, 3], [3, 4], [4, 0]], np.int32)   # every state of the layer below is the d0 of one CMux, so its low bits reach an output
+
+
+def wfa_bound_automata(p):
+    """name -> (trans int32[n_steps][5][2], step_bit): the crafted step alone on the finals; the crafted step as the non-final layer above a step
+    of copies (it reads the layer buffer); the crafted step on the finals, then a step on the random bit that reads what it wrote."""
+    tr = wfa_case(p, WFA_STATES)[2]
+    return {
+        "one-step": (tr[None], [0]),
+        "reads-a-layer": (np.stack([tr, wfa_copies(WFA_STATES)]), [0, 0]),
+        "then-random": (np.stack([WFA_FOLLOW, tr]), [1, 0]),
+    }
+
+
+def wfa_bound_finals(p, kind, variant, seed):
+    """(fin_a or None, fin_b) int32[5][N] of a variant: kind "enc" / "pub" (bodies alone), variant "zero d0" / "random d0"."""
+    fin = wfa_case(p, WFA_STATES, None if variant == "zero d0" else np.random.default_rng(seed))[1]
+    return (fin[:, :p.N] if kind == "enc" else None), fin[:, p.N:]
+
+
+def wfa_bound_bits(p):
+    """the TGSW samples int32[2][2l][2][N] of the two bits those automata read"""
+    rnd = np.random.default_rng(0xE0 + 16 * p.l + p.Bgbit).integers(-2**31, 2**31, size=(2 * p.l, 2, p.N), dtype=np.int64).astype(np.int32)
+    return np.stack([lhe_cmux_case(p)[0], rnd])

@@ -204,3 +204,146 @@ def test_encrypted_table_recipe_reaches_the_bound_at_step_0(O, l, Bgbit):
     # the oracle's schoolbook path agrees on the crafted step: the accumulator (mu, mu) through CMux 0 at bara = N
     acc = np.full((2, p.N), mu, np.int32)
     assert np.array_equal(orc.mux_rotate(0, p.N, acc), orc.mux_rotate(0, p.N, acc, schoolbook=True))
+
+
+# ---- multi-value bootstrap at the bound (the crafting facts test_gpu_mv_bound.py relies on) -----------------------------------------------------
+# (l, Bgbit, full) of test_gpu_mv_bound.py: the shapes of test_single_key_at_the_bound, and l = 1 for the <1, ...> instantiations
+MV_SHAPES = [(1, 8, True), (2, 10, True), (3, 7, True), (3, 10, True), (4, 8, False)]
+MV_IDS = ["l1-Bg8", "SK-80", "SK-128", "l3-Bg10", "l4-Bg8-half"]
+MV_PQ = [(2, 1), (64, 9), (8, 64)]       # (taps, outputs): the smallest; the most taps, q off the eight waves; the most outputs
+MV_TABLES = 2
+
+
+def _mv_case(O, l, Bgbit, full):
+    """(params, keys, crafted key, record, mu, crafted step, oracle) of one multi-value bound case"""
+    p = O.make_params("SK-128", n=4, l=l, Bgbit=Bgbit)
+    K = O.SKKeys(p, 0xB0 + l, 2.0**-25, 2.0**-15)
+    bk, x, mu, step = B.sk_case(p, K.bk, full)
+    return p, K, bk, x, mu, step, O.Oracle(p, bk, K.ksk)
+
+
+@pytest.mark.parametrize("l, Bgbit, full", MV_SHAPES, ids=MV_IDS)
+def test_multi_value_recipe_reaches_the_bound(O, l, Bgbit, full):
+    import lut_reference as R
+    import mv_lut_reference as MV
+    p, K, bk, x, mu, step, orc = _mv_case(O, l, Bgbit, full)
+    assert B.sk_reached(orc, p, bk, x, mu, step) == B.bound(2 * l, p.N, Bgbit) // (1 if full else 2)
+    # one input of weight 1 and bias 0: the prologue leaves the record alone, barb = 0, and tv0 = mu everywhere is the gate's accumulator
+    xs = R.prologue([x], (1,), 0)
+    assert np.array_equal(xs, x) and O.lib().oracle_modswitch(int(x[p.n]), p.N) == 0
+    acc = MV.rotate(orc, xs, np.full(p.N, mu, np.int32))
+    assert np.array_equal(acc, B.sk_acc_after(orc, p, x, mu))              # the model's rotation (NTT) = the oracle's schoolbook steps
+    assert np.array_equal(R.extract_at(acc, 0, p.N), orc.bootstrap_wo_keyswitch(x, mu))   # ... = the accumulator of the oracle's own bootstrap
+
+
+@pytest.mark.parametrize("l, Bgbit, full", MV_SHAPES, ids=MV_IDS)
+def test_multi_value_records_see_one_lsb(O, l, Bgbit, full):
+    """What the compared records of test_gpu_mv_bound.py expose of the accumulator: the mask column, all N coefficients (the peak at N - 1 is
+    observed there), through the unit-tap output 0 of every factor table -- bit 0 of any mask coefficient moves exactly one word of it by one --
+    and of the body the coefficients at the tap positions N - box/2 - k box only."""
+    import mv_lut_reference as MV
+    p, K, bk, x, mu, step, orc = _mv_case(O, l, Bgbit, full)
+    N = p.N
+    acc = B.sk_acc_after(orc, p, x, mu)
+    for pt, q in MV_PQ:
+        w = B.mv_factors(np.random.default_rng(0xF0 + pt), MV_TABLES, q, pt)
+        taps = B.mv_tap_positions(N, pt)
+        for t in range(MV_TABLES):
+            assert np.count_nonzero(w[t, 0]) == 1 and w[t, 0].sum() == 1
+            ref = MV.combine(acc, w[t], N)
+            assert ref.shape == (q, N + 1)
+            for c in (N - 1, 0, 517):                   # mask coefficients: the peak and two others
+                bad = acc.copy()
+                bad[c] ^= 1
+                got = MV.combine(bad, w[t], N)
+                delta = got[0].astype(np.int64) - ref[0]
+                assert np.count_nonzero(delta) == 1 and abs(int(delta[np.flatnonzero(delta)[0]])) == 1, (pt, q, t, c)
+                assert not delta[N]
+            used = np.flatnonzero(np.any(w[t] != 0, axis=0))
+            for c in (taps[used[0]], taps[used[-1]]):   # body coefficients a (non-zero) tap reads
+                bad = acc.copy()
+                bad[N + c] ^= 1
+                assert not np.array_equal(MV.combine(bad, w[t], N), ref), (pt, q, t, c)
+            bad = acc.copy()                            # ... and one no tap reads: not exposed
+            assert N - 1 not in taps
+            bad[N + N - 1] ^= 1
+            assert np.array_equal(MV.combine(bad, w[t], N), ref)
+
+
+# ---- layered automata at the bound (the crafting facts test_gpu_wfa_bound.py relies on) ---------------------------------------------------------
+WFA_KINDS = [(kind, variant) for kind in ("enc", "pub") for variant in ("zero d0", "random d0")]
+
+
+def _wfa_diff(fa, fb, t0, t1):
+    """d1 - d0 of a transition, int32[2N]; fa None: zero masks"""
+    import lhe_reference as LR
+    N = fb.shape[1]
+    z = np.zeros(N, np.int32)
+    return LR._sub(np.concatenate([z if fa is None else fa[t1], fb[t1]]), np.concatenate([z if fa is None else fa[t0], fb[t0]]))
+
+
+@pytest.mark.parametrize("l, Bgbit", LHE_SHAPES)
+def test_automaton_recipe_reaches_the_bound(O, l, Bgbit):
+    import lhe_reference as LR
+    import wfa_reference as WR
+    p = _lhe_params(O, l, Bgbit)
+    N, T = p.N, B.wrap(B.digit_word(32, l, Bgbit), 32)
+    for n_states in (5, 4, 1):
+        C, fin, trans = B.wfa_case(p, n_states)
+        assert np.all(C == B.extreme_key_word(32)) and fin.shape == (n_states, 2 * N)
+        assert trans.tolist() == [[q & ~1, q | 1] for q in range(n_states - 1)] + [[n_states - 1] * 2]
+        assert not fin[0::2].any() and np.all(fin[1::2] == T)
+    C, _, trans = B.wfa_case(p, B.WFA_STATES)
+    for kind, variant in WFA_KINDS:
+        fa, fb = B.wfa_bound_finals(p, kind, variant, 0xA0 + l)
+        if variant == "random d0":      # every pair has words of its own: a state read at another state's index shows
+            assert len({fb[q].tobytes() for q in range(B.WFA_STATES)}) == B.WFA_STATES
+        rows = 2 * l if kind == "enc" else l
+        V = WR.layer0(p, [C[None]], trans[None], [0], fa, fb)
+        z = np.zeros(N, np.int32)
+        state = lambda q: np.concatenate([z if fa is None else fa[q], fb[q]])
+        for q, (t0, t1) in enumerate(trans.tolist()):
+            if t0 == t1:
+                assert q == B.WFA_STATES - 1 and np.array_equal(V[q], state(t0))
+                continue
+            diff = _wfa_diff(fa, fb, t0, t1)
+            assert np.all(diff[N:] == T) and np.all(diff[:N] == (T if kind == "enc" else 0))
+            assert B.lhe_reached(p, C, diff) == B.bound(rows, N, Bgbit), (kind, variant, q)
+            assert np.array_equal(V[q], LR.cmux(p, C, state(t1), state(t0))), (kind, variant, q)
+
+
+@pytest.mark.parametrize("l, Bgbit", LHE_SHAPES)
+def test_automaton_records_see_one_lsb(O, l, Bgbit):
+    """What the compared records of test_gpu_wfa_bound.py (theta = 4, start = every state) expose of a layer-0 state: the mask column, all N
+    coefficients (the peak at N - 1 is observed there), and of the body the theta extracted coefficients 0 .. 3 only.  In the automaton whose
+    crafted step is followed by a random step, every state the crafted step wrote is the d0 of one CMux of the step above, so bit 0 of its words
+    is added into an output undecomposed."""
+    import lut_reference as R
+    import wfa_reference as WR
+    p = _lhe_params(O, l, Bgbit)
+    N, S, theta = p.N, B.WFA_STATES, 4
+    Cs = B.wfa_bound_bits(p)
+    records = lambda V: np.stack([np.stack([R.extract_at(V[q], j, N) for j in range(theta)]) for q in range(S)])
+    for name, (trans, step_bit) in B.wfa_bound_automata(p).items():
+        for kind, variant in WFA_KINDS:
+            fa, fb = B.wfa_bound_finals(p, kind, variant, 0xA0 + l)
+            V = WR.layer0(p, [Cs], trans, step_bit, fa, fb)
+            ref = records(V)
+            for q in range(S):
+                for c, seen in ((N - 1, True), (300, True), (N + 0, True), (N + theta - 1, True), (N + theta, False), (2 * N - 1, False)):
+                    bad = [v.copy() for v in V]
+                    bad[q][c] ^= 1
+                    got = records(bad)
+                    assert np.array_equal(got, ref) != seen, (name, kind, variant, q, c)
+                    assert np.array_equal(np.delete(got, q, axis=0), np.delete(ref, q, axis=0))
+            if name != "then-random":
+                continue
+            # one LSB in the layer the crafted step wrote, before the random step reads it
+            V1 = WR.layer0(p, [Cs], trans[1:], step_bit[1:], fa, fb)
+            assert np.array_equal(ref, records(WR.layer0(p, [Cs], trans[:1], step_bit[:1], np.stack(V1)[:, :N], np.stack(V1)[:, N:])))
+            for q in (0, 3):
+                for c in (N - 1, 300):
+                    bad = np.stack(V1)
+                    bad[q, c] ^= 1
+                    got = records(WR.layer0(p, [Cs], trans[:1], step_bit[:1], bad[:, :N], bad[:, N:]))
+                    assert not np.array_equal(got, ref), (kind, variant, q, c)
