@@ -1,21 +1,29 @@
 // thfhe_dag.h -- the gate-DAG front end shared by the single-key and the 3-gen multi-key engines:
 // an ASAP levelising scheduler for the reference's circuits (src/KNN_medical_data.cpp:127-489, J/3gen_mk_gates.jl:183-362), and the
-// gather / scatter kernels of the device-resident executor.  LUT nodes (thfhe_dag_run_lut_batch): programmable bootstraps among the
-// gates, fed by the shared prologue reading their operands from the wire table (LutWireSrc, thfhe_lut_prologue.h), their theta outputs scattered
-// into consecutive wires.
-// Encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch, DESIGN 4.12, single key): three more node kinds, planned here, run by the engine.
-// Multi-value nodes (thfhe_dag_run_mv_batch, DESIGN 4.14, single key): MV and TREE_MV rows, planned here next to them.
-// Leveled nodes (thfhe_dag_run_lhe_batch, DESIGN 4.18, single key): LHE_LOOKUP, LHE_GATHER and LHE_WFA rows on the client's TGSW sets, planned here;
-// dag_lhe_gather_kernel stages a GATHER node's candidates for the box packing.
+// gather / scatter kernels of the device-resident executor.
+// The host side of an entry is three records and two functions.  DagCall: the inputs, the node rows, the wires to return.  DagFamilies: every table
+// family a run can bring, with the generations of node kinds the entry admits (DagGen).  DagPlan: the schedule, launch groups of one DagClass each.
+// dag_families_check: the checks that need no row; dag_plan: one row checker per node kind (DagRowChecks), then the levels and their groups.
+//   kDagGenLut   LUT nodes (thfhe_dag_run_lut_batch, thfhe_mk_dag_run_lut_batch): programmable bootstraps among the gates, fed by the shared
+//                prologue reading their operands from the wire table (LutWireSrc, thfhe_lut_prologue.h), their theta outputs scattered into consecutive wires
+//   kDagGenTree  encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch; single key)
+//   kDagGenMv    multi-value nodes (thfhe_dag_run_mv_batch; single key): MV and TREE_MV rows
+//   kDagGenLhe   leveled nodes (thfhe_dag_run_lhe_batch; single key): LHE_LOOKUP, LHE_GATHER and LHE_WFA rows on the client's TGSW sets;
+//                dag_lhe_gather_kernel stages a GATHER node's candidates for the box packing
+// The kinds from kDagGenTree on are planned here and run by the engine (thfhe_sk.hip: sk_dag_run_luts).
 #ifndef THFHE_DAG_H
 #define THFHE_DAG_H
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <map>
+#include <set>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/thfhe_hip.h"
@@ -92,41 +100,81 @@ __global__ __launch_bounds__(256) void dag_lhe_gather_kernel(const int32_t *__re
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (size_t)gridDim.x * 256) out[i] = src[i];
 }
 
+// The launch classes of the schedule.  0 .. 3 are the engine's gate classes, what its classify(op) returns.
+enum DagClass : int32_t {
+    kDagGate2 = 0,       // two-input bootstrapped gates, per-gate opcodes in one launch
+    kDagMux = 1,         // MUX: two rotations per gate
+    kDagLinear = 2,      // NOT / COPY: no bootstrap
+    kDagGate3 = 3,       // three-input bootstrapped gates
+    kDagLut1 = 4, kDagLut2 = 5, kDagLut4 = 6,     // LUT nodes of theta 1 / 2 / 4, index columns + [spec | lut]
+    kDagLutOut = 7,      // LUT_OUT row: no launch, its wire is written by its head's scatter
+    kDagEnc1 = 8, kDagEnc2 = 9, kDagEnc4 = 10,    // LUT_ENC nodes of theta 1 / 2 / 4: [spec | etab]
+    // the grouped kinds: one launch group per entry of the family and level
+    kDagSelect = 11,     // [tree | first], per trees[] entry
+    kDagTree = 12,       // [tree | row0]
+    kDagMv = 13,         // [mv | t], per mvs[] entry
+    kDagTreeMv = 14,
+    kDagLheLookup = 15,  // [lk | row0], per lks[] entry
+    kDagLheGather = 16,  // [lk | first]
+    kDagLheWfa = 17,     // [wfa | fin_row0], per wfas[] entry
+};
+// theta of a LUT / LUT_ENC class, 0 for every other class
+inline int dag_class_theta(int cls) {
+    switch (cls) {
+    case kDagLut1: case kDagEnc1: return 1;
+    case kDagLut2: case kDagEnc2: return 2;
+    case kDagLut4: case kDagEnc4: return 4;
+    default: return 0;
+    }
+}
+inline int dag_lut_class(int theta, bool enc) { return theta == 1 ? (enc ? kDagEnc1 : kDagLut1) : (theta == 2 ? (enc ? kDagEnc2 : kDagLut2) : (enc ? kDagEnc4 : kDagLut4)); }
+
 // One launch group of the schedule: `count` gates of one class whose operands are all available.
 struct DagBatch {
-    int32_t depth, sub, cls;  // cls: engine-defined gate class; 2 = NOT / COPY (no bootstrap); 4 / 5 / 6 = LUT nodes of theta 1 / 2 / 4
-    size_t off, count;        // index table slice: [ops | in0 | in1 | in2 | out], LUT classes + [spec | lut], `count` entries each, at tab[off]
-    int32_t tree = -1;        // SELECT / TREE groups: the trees[] entry the whole group shares; MV / TREE_MV groups: the mvs[] entry; leveled groups: lks[] / wfas[]
+    int32_t depth, sub, cls;  // cls: a DagClass
+    size_t off, count;        // index table slice: [ops | in0 | in1 | in2 | out], classes from kDagLut1 on + [spec | lut], `count` entries each, at tab[off]
+    int32_t tree = -1;        // the grouped kinds: the trees[] / mvs[] / lks[] / wfas[] entry the whole group shares
 };
-constexpr int kDagLutOut = 7;                // LUT_OUT row: no launch, its wire is written by its head's scatter
-inline int dag_lut_class(int theta) { return theta == 1 ? 4 : (theta == 2 ? 5 : 6); }
-inline int dag_lut_theta(int cls) { return cls == 4 ? 1 : (cls == 5 ? 2 : 4); }
-// thfhe_dag_run_tree_batch: LUT_ENC nodes of theta 1 / 2 / 4 = 8 / 9 / 10 (index columns as the LUT classes: [spec | etab]); SELECT groups = 11
-// ([tree | first]), TREE groups = 12 ([tree | row0]), one group per trees[] entry
-constexpr int kDagEnc = 8, kDagSelect = 11, kDagTree = 12;
-inline int dag_enc_theta(int cls) { return cls == 8 ? 1 : (cls == 9 ? 2 : 4); }
-// thfhe_dag_run_mv_batch: MV groups = 13, TREE_MV groups = 14 ([mv | t]), one group per mvs[] entry
-constexpr int kDagMv = 13, kDagTreeMv = 14;
-// thfhe_dag_run_lhe_batch: LHE_LOOKUP groups = 15 ([lk | row0]), LHE_GATHER groups = 16 ([lk | first]), one group per lks[] entry; LHE_WFA groups = 17
-// ([wfa | fin_row0]), one group per wfas[] entry
-constexpr int kDagLheLookup = 15, kDagLheGather = 16, kDagLheWfa = 17;
 
-// The LUT side of a run (thfhe_dag_run_lut_batch): node rows of 6 words, the run's specs and its table count.
-struct DagLuts {
-    const thfhe_lut_spec *specs;
-    int n_specs, n_luts;
-    // thfhe_dag_run_tree_batch only (ext): the encrypted-table count, the tree specs and the level-1 row count
-    bool ext = false;
+// The arguments every thfhe_dag_run_*_batch entry has: the inputs, the node rows, the wires to return.
+struct DagCall {
+    const int32_t *inputs;      // int32[instances][n_inputs][words]
+    size_t n_inputs;
+    const int32_t *nodes;       // int32[n_nodes][4 or 6]
+    size_t n_nodes;
+    const int32_t *out_wires;   // wire ids to return (n_out of them) or null = every node's wire
+    size_t n_out;
+    int32_t *outputs;           // int32[instances][n_out or n_nodes][words]
+};
+
+// The generations of node kinds an entry admits.  An opcode of a generation the entry does not have is a gate opcode the engine does not define.
+enum DagGen : unsigned {
+    kDagGenLut = 1,    // six-column rows; THFHE_LUT and THFHE_LUT_OUT (thfhe_dag_run_lut_batch, thfhe_mk_dag_run_lut_batch)
+    kDagGenTree = 2,   // THFHE_LUT_ENC, THFHE_SELECT, THFHE_TREE; every family may be absent (thfhe_dag_run_tree_batch)
+    kDagGenMv = 4,     // THFHE_MV, THFHE_TREE_MV (thfhe_dag_run_mv_batch)
+    kDagGenLhe = 8,    // THFHE_LHE_LOOKUP, THFHE_LHE_GATHER, THFHE_LHE_WFA (thfhe_dag_run_lhe_batch with its families)
+};
+// Everything a run can bring besides its DagCall: the table families (host pointers) with their counts.  An entry fills the families it has and the
+// generations it admits; none (gens = 0) is a run of four-column gate rows.  After dag_families_check a family without a pointer has count 0.
+struct DagFamilies {
+    unsigned gens = 0;   // DagGen bits; the members below in the order of the entries' arguments
+    const thfhe_lut_spec *specs = nullptr;
+    int n_specs = 0;
+    const void *tv = nullptr;                           // [n_luts][N] test vectors of the ring's torus: int32 single key, int64 multi key
+    int n_luts = 0;
+    const int32_t *enc_a = nullptr, *enc_b = nullptr;   // [n_enc][N] encrypted tables: masks, bodies
     int n_enc = 0;
     const thfhe_tree_spec *trees = nullptr;
-    int n_trees = 0, n_tv1_rows = 0;
-    // thfhe_dag_run_mv_batch only (mv): the multi-value specs, the base-vector count and the words of the factor array
-    bool mv = false;
+    int n_trees = 0;
+    const int32_t *tv1 = nullptr;                       // [n_tv1_rows][N] level-1 rows
+    int n_tv1_rows = 0;
     const thfhe_mv_spec *mvs = nullptr;
-    int n_mvs = 0, n_bases = 0;
+    int n_mvs = 0;
+    const int32_t *mv_tv0 = nullptr;                    // [n_bases][N] base vectors
+    int n_bases = 0;
+    const int32_t *mv_factors = nullptr;                // the taps of every mvs[] entry
     size_t n_factor_words = 0;
-    // thfhe_dag_run_lhe_batch only: the leveled families (host pointers; a family the run does not have is null / 0)
-    const thfhe_dag_lhe_families *lhe = nullptr;
+    const thfhe_dag_lhe_families *lhe = nullptr;        // the leveled families, with kDagGenLhe
 };
 
 // the rules a multi-value rotation adds to lut_spec_check's: theta 1, p taps, q outputs, the table count (thfhe_mv_lut_bootstrap)
@@ -146,7 +194,7 @@ inline int mvk_validate(int p_hi, int k) {
     return THFHE_OK;
 }
 // One mvs[] entry as an MV row (tree = false) or a TREE_MV row uses it: the flat entries' rules, then its base row and its slice of the factor array.
-inline int dag_mv_spec_check(const DagLuts &L, const thfhe_mv_spec &m, bool tree) {
+inline int dag_mv_spec_check(const DagFamilies &F, const thfhe_mv_spec &m, bool tree) {
     THFHE_TRY(lut_spec_check(m.lo));
     if (tree) {
         THFHE_TRY(lut_spec_check(m.hi));
@@ -157,10 +205,10 @@ inline int dag_mv_spec_check(const DagLuts &L, const thfhe_mv_spec &m, bool tree
         if (m.k != 1) return thfhe_fail(THFHE_E_INVALID, "MV node: the spec's k must be 1");
         THFHE_TRY(mv_validate(m.lo, m.p, m.q, m.n_tables));
     }
-    if (L.n_bases < 1) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: no base vectors given (null table family)");
-    if (m.base < 0 || m.base >= L.n_bases) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: base out of range (0 .. n_bases-1)");
-    if (L.n_factor_words < 1) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: no factors given (null table family)");
-    if (m.factors_off < 0 || (size_t)m.factors_off + (size_t)m.n_tables * m.k * m.q * m.p > L.n_factor_words)
+    if (F.n_bases < 1) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: no base vectors given (null table family)");
+    if (m.base < 0 || m.base >= F.n_bases) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: base out of range (0 .. n_bases-1)");
+    if (F.n_factor_words < 1) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: no factors given (null table family)");
+    if (m.factors_off < 0 || (size_t)m.factors_off + (size_t)m.n_tables * m.k * m.q * m.p > F.n_factor_words)
         return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: factors_off + n_tables k q p out of range (0 .. n_factor_words)");
     return THFHE_OK;
 }
@@ -200,6 +248,204 @@ inline int dag_wfa_spec_check(const thfhe_dag_lhe_families &F, const thfhe_dag_w
     return THFHE_OK;
 }
 
+// One family of a run: whether its pointer is given, its count, and the range of the count when it is.
+struct DagFamilyRule {
+    bool have;
+    long long n, min, max;
+    const char *range_msg;
+};
+// The families of one generation: a count without its pointer first, whichever family has it, then every count against its range in order.
+inline int dag_family_rules(std::initializer_list<DagFamilyRule> rules, const char *null_msg) {
+    for (const DagFamilyRule &r : rules)
+        if (!r.have && r.n) return thfhe_fail(THFHE_E_INVALID, null_msg);
+    for (const DagFamilyRule &r : rules)
+        if (r.have && (r.n < r.min || r.n > r.max)) return thfhe_fail(THFHE_E_INVALID, r.range_msg);
+    return THFHE_OK;
+}
+// The host checks of a six-column entry that need no row, before any device work and before a context is looked at: the call's pointers; per
+// generation of families a count without its pointer, then the counts (a family without a pointer has count 0 from here on); every spec (the rules
+// of lut_validate) and every tree spec's `hi` half and p_hi (the rules of thfhe_tree_lut_bootstrap; the `lo` half, and an mvs[] / lks[] / wfas[]
+// entry, when a row uses it); the output wire ids.  The LUT entries (no kDagGenTree) require specs and tv; from thfhe_dag_run_tree_batch on every
+// family may be absent.
+inline int dag_families_check(const DagCall &A, const DagFamilies &F) {
+    const bool strict = !(F.gens & kDagGenTree);
+    if ((!A.inputs && A.n_inputs) || (!A.nodes && A.n_nodes) || (!A.outputs && A.n_nodes) || (!A.out_wires && A.n_out) || (strict && (!F.specs || !F.tv)))
+        return thfhe_fail(THFHE_E_INVALID, "null argument");
+    const char *const null_msg = "null argument: a table family with a count but no pointer";
+    THFHE_TRY(dag_family_rules({{F.specs != nullptr, F.n_specs, 1, 1024, strict ? "n_specs must be 1 .. 1024" : "n_specs must be 1 .. 1024 (0 with specs = NULL)"},
+                                {F.tv != nullptr, F.n_luts, 1, 1024, strict ? "n_luts must be 1 .. 1024" : "n_luts must be 1 .. 1024 (0 with tv = NULL)"},
+                                {F.enc_a && F.enc_b, F.n_enc, 0, 1 << 18, "n_enc must be 1 .. 262144 (0 with enc_a = enc_b = NULL)"},
+                                {F.trees != nullptr, F.n_trees, 1, 1024, "n_trees must be 1 .. 1024 (0 with trees = NULL)"},
+                                {F.tv1 != nullptr, F.n_tv1_rows, 1, 1 << 18, "n_tv1_rows must be 1 .. 262144 (0 with tv1 = NULL)"}},
+                               null_msg));
+    THFHE_TRY(dag_family_rules({{F.mvs != nullptr, F.n_mvs, 1, 1024, "n_mvs must be 1 .. 1024 (0 with mvs = NULL)"},
+                                {F.mv_tv0 != nullptr, F.n_bases, 1, 1024, "n_bases must be 1 .. 1024 (0 with mv_tv0 = NULL)"},
+                                {F.mv_factors != nullptr, (long long)F.n_factor_words, 1, 1 << 28, "n_factor_words must be 1 .. 2^28 (0 with mv_factors = NULL)"}},
+                               null_msg));
+    if (const thfhe_dag_lhe_families *const L = F.lhe) {
+        const char *const lhe_null_msg = "null argument: a leveled family with a count but no pointer";
+        if ((!L->tab_b && L->tab_a) || (!L->fin_b && L->fin_a)) return thfhe_fail(THFHE_E_INVALID, lhe_null_msg);   // masks without bodies
+        THFHE_TRY(dag_family_rules({{L->sets != nullptr, L->n_sets, 1, 64, "lhe: n_sets must be 1 .. 64 (0 with sets = NULL)"},
+                                    {L->lks != nullptr, L->n_lks, 1, 1024, "lhe: n_lks must be 1 .. 1024 (0 with lks = NULL)"},
+                                    {L->wfas != nullptr, L->n_wfas, 1, 1024, "lhe: n_wfas must be 1 .. 1024 (0 with wfas = NULL)"},
+                                    {L->tab_b != nullptr, L->n_tab_rows, 1, 1 << 18, "lhe: n_tab_rows must be 1 .. 262144 (0 with tab_b = NULL)"},
+                                    {L->fin_b != nullptr, L->n_fin_rows, 1, 1 << 18, "lhe: n_fin_rows must be 1 .. 262144 (0 with fin_b = NULL)"},
+                                    {L->wfa_words != nullptr, (long long)L->n_wfa_words, 1, 1 << 28, "lhe: n_wfa_words must be 1 .. 2^28 (0 with wfa_words = NULL)"}},
+                                   lhe_null_msg));
+    }
+    for (int s = 0; s < F.n_specs; s++)
+        THFHE_TRY(lut_spec_check(F.specs[s]));
+    for (int t = 0; t < F.n_trees; t++) {
+        THFHE_TRY(lut_spec_check(F.trees[t].hi));
+        if (F.trees[t].hi.theta != 1) return thfhe_fail(THFHE_E_INVALID, "tree: spec_hi theta must be 1 (the packed table holds one function)");
+        const int p_hi = F.trees[t].p_hi;
+        if (p_hi < 2 || p_hi > 512 || (p_hi & (p_hi - 1))) return thfhe_fail(THFHE_E_INVALID, "tree: p_hi must be a power of two in 2 .. N/2");
+    }
+    for (size_t s = 0; s < A.n_out; s++)
+        if (A.out_wires[s] < 0 || (size_t)A.out_wires[s] >= A.n_inputs + A.n_nodes) return thfhe_fail(THFHE_E_INVALID, "output wire id out of range");
+    return THFHE_OK;
+}
+
+// What a row checker makes of its row.
+struct DagRow {
+    int cls = kDagLutOut;
+    int32_t entry = -1;                       // the grouped kinds: the family entry the row's group shares (row field 4)
+    int nin = 0;                              // wire operands, row fields 1 .. nin
+    int32_t cand_first = 0, cand_count = 0;   // SELECT / GATHER: the candidate wires; they count for the depth as operands do
+    int outs = 0;                             // LUT_OUT rows due after the row
+};
+
+// The row checks of a run, one checker per node kind; each fills the DagRow of a row it accepts.
+struct DagRowChecks {
+    const DagFamilies &F;
+    std::set<std::pair<int, int32_t>> checked;   // (class, entry): the family entries that have had the checks a kind makes once per entry
+
+    bool first_use(int cls, int32_t entry) { return checked.insert({cls, entry}).second; }
+    static int operands_match(const int32_t *row, int nin, const char *msg) {
+        for (int q = 0; q < 3; q++)
+            if ((q < nin) != (row[1 + q] != -1)) return thfhe_fail(THFHE_E_INVALID, msg);
+        return THFHE_OK;
+    }
+    static int no_operands(const int32_t *row) {
+        if (row[1] != -1 || row[2] != -1 || row[3] != -1) return thfhe_fail(THFHE_E_INVALID, "leveled node: the operand fields must be -1");
+        return THFHE_OK;
+    }
+    static int candidates(DagRow &r, int32_t first, int32_t count, int32_t w, const char *msg) {
+        if (first < 0 || (long)first + count > (long)w) return thfhe_fail(THFHE_E_INVALID, msg);
+        r.cand_first = first, r.cand_count = count;
+        return THFHE_OK;
+    }
+
+    template <typename Classify>
+    int gate(const int32_t *row, Classify classify, DagRow &r) const {
+        r.cls = classify(row[0]);
+        if (r.cls < 0) return thfhe_fail(THFHE_E_INVALID, "gate opcode not defined for this engine");
+        if (F.gens && (row[4] != -1 || row[5] != -1)) return thfhe_fail(THFHE_E_INVALID, "gate row: spec and lut must be -1");
+        r.nin = r.cls == kDagLinear ? 1 : (r.cls == kDagGate2 ? 2 : 3);
+        return THFHE_OK;
+    }
+    // (LUT_OUT, head, -1, -1, -1, -1): one of the `pending` rows due after the node of wire `head`
+    static int lut_out(const int32_t *row, int32_t head, int pending) {
+        if (pending == 0) return thfhe_fail(THFHE_E_INVALID, "LUT_OUT row without a LUT node before it (extra or misplaced LUT_OUT row)");
+        if (row[1] != head) return thfhe_fail(THFHE_E_INVALID, "LUT_OUT row names the wrong head (it must name its LUT node's wire)");
+        if (row[2] != -1 || row[3] != -1 || row[4] != -1 || row[5] != -1) return thfhe_fail(THFHE_E_INVALID, "LUT_OUT row: fields after the head must be -1");
+        return THFHE_OK;
+    }
+    // (LUT | LUT_ENC, operands, spec, lut | etab)
+    int lut(const int32_t *row, bool enc, DagRow &r) const {
+        if (!F.specs || (!enc && F.n_luts == 0))
+            return thfhe_fail(THFHE_E_INVALID, enc ? "LUT_ENC node: no specs given (null table family)" : "LUT node: no specs or no tables given (null table family)");
+        if (enc && F.n_enc < 1) return thfhe_fail(THFHE_E_INVALID, "LUT_ENC node: n_enc must be 1 .. 262144 (null table family)");
+        if (row[4] < 0 || row[4] >= F.n_specs) return thfhe_fail(THFHE_E_INVALID, "LUT node: spec index out of range (0 .. n_specs-1)");
+        if (!enc && (row[5] < 0 || row[5] >= F.n_luts)) return thfhe_fail(THFHE_E_INVALID, "LUT node: table index out of range (0 .. n_luts-1)");
+        if (enc && (row[5] < 0 || row[5] >= F.n_enc)) return thfhe_fail(THFHE_E_INVALID, "LUT_ENC node: etab out of range (0 .. n_enc-1)");
+        const thfhe_lut_spec &sp = F.specs[row[4]];
+        THFHE_TRY(operands_match(row, sp.n_inputs, "LUT node: operands do not match the spec's n_inputs (unused ones are -1)"));
+        r.cls = dag_lut_class(sp.theta, enc), r.nin = sp.n_inputs, r.outs = sp.theta - 1;
+        return THFHE_OK;
+    }
+    // (SELECT, index operands, tree, first candidate wire) / (TREE, lo then hi operands, tree, row0); w: the row's own wire
+    int tree(const int32_t *row, int32_t w, bool is_tree, DagRow &r) {
+        if (!F.trees) return thfhe_fail(THFHE_E_INVALID, "SELECT / TREE node: no tree specs given (null table family)");
+        if (row[4] < 0 || row[4] >= F.n_trees) return thfhe_fail(THFHE_E_INVALID, "SELECT / TREE node: tree index out of range (0 .. n_trees-1)");
+        const thfhe_tree_spec &ts = F.trees[row[4]];
+        r.cls = is_tree ? kDagTree : kDagSelect, r.entry = row[4], r.nin = ts.hi.n_inputs;
+        if (is_tree) {
+            if (first_use(kDagTree, row[4])) {   // the `lo` half: a SELECT ignores it
+                THFHE_TRY(lut_spec_check(ts.lo));
+                if (ts.p_hi % ts.lo.theta) return thfhe_fail(THFHE_E_INVALID, "tree: spec_lo theta must divide p_hi");
+            }
+            r.nin += ts.lo.n_inputs;
+            if (r.nin > 3) return thfhe_fail(THFHE_E_INVALID, "TREE node: lo and hi operands exceed three");
+            if (F.n_tv1_rows < 1) return thfhe_fail(THFHE_E_INVALID, "TREE node: no level-1 rows given (null table family)");
+            if (row[5] < 0 || (long)row[5] + ts.p_hi / ts.lo.theta > F.n_tv1_rows)
+                return thfhe_fail(THFHE_E_INVALID, "TREE node: row0 + R out of range (0 .. n_tv1_rows)");
+        } else {
+            THFHE_TRY(candidates(r, row[5], ts.p_hi, w, "SELECT node: candidate is not an earlier wire (first .. first + p - 1 must all be defined above)"));
+        }
+        return operands_match(row, r.nin, is_tree ? "TREE node: operands do not match lo.n_inputs + hi.n_inputs (unused ones are -1)"
+                                                  : "SELECT node: operands do not match hi.n_inputs (unused ones are -1)");
+    }
+    // (MV, operands, mv, t) / (TREE_MV, lo then hi operands, mv, t)
+    int mv(const int32_t *row, bool is_tree, DagRow &r) {
+        if (!F.mvs) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: no multi-value specs given (null table family)");
+        if (row[4] < 0 || row[4] >= F.n_mvs) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: mv index out of range (0 .. n_mvs-1)");
+        const thfhe_mv_spec &m = F.mvs[row[4]];
+        r.cls = is_tree ? kDagTreeMv : kDagMv, r.entry = row[4];
+        if (first_use(r.cls, row[4])) THFHE_TRY(dag_mv_spec_check(F, m, is_tree));
+        if (row[5] < 0 || row[5] >= m.n_tables) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: table index out of range (0 .. n_tables-1)");
+        r.nin = m.lo.n_inputs + (is_tree ? m.hi.n_inputs : 0), r.outs = (is_tree ? m.k : m.q) - 1;
+        if (r.nin > 3) return thfhe_fail(THFHE_E_INVALID, "TREE_MV node: lo and hi operands exceed three");
+        return operands_match(row, r.nin, is_tree ? "TREE_MV node: operands do not match lo.n_inputs + hi.n_inputs (unused ones are -1)"
+                                                  : "MV node: operands do not match lo.n_inputs (unused ones are -1)");
+    }
+    // (LHE_LOOKUP, -1, -1, -1, lk, row0) / (LHE_GATHER, -1, -1, -1, lk, first candidate wire)
+    int lookup(const int32_t *row, int32_t w, bool gather, DagRow &r) {
+        const thfhe_dag_lhe_families &L = *F.lhe;
+        THFHE_TRY(no_operands(row));
+        if (!L.lks) return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP / LHE_GATHER node: no lookup specs given (null family)");
+        if (row[4] < 0 || row[4] >= L.n_lks) return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP / LHE_GATHER node: lk out of range (0 .. n_lks-1)");
+        const thfhe_dag_lhe_spec &ls = L.lks[row[4]];
+        r.cls = gather ? kDagLheGather : kDagLheLookup, r.entry = row[4];
+        if (first_use(r.cls, row[4])) THFHE_TRY(dag_lhe_spec_check(L, ls, gather));
+        if (gather)
+            return candidates(r, row[5], (int32_t)1 << (ls.d_tree + ls.d_rot), w,
+                              "LHE_GATHER node: candidate is not an earlier wire (first .. first + 2^d - 1 must all be defined above)");
+        if (!L.tab_b || L.n_tab_rows < 1) return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP node: no table rows given (null family)");
+        if (row[5] < 0 || (long)row[5] + (1L << ls.d_tree) > L.n_tab_rows)
+            return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP node: row0 + 2^d_tree out of range (0 .. n_tab_rows)");
+        r.outs = ls.theta - 1;
+        return THFHE_OK;
+    }
+    // (LHE_WFA, -1, -1, -1, wfa, fin_row0)
+    int wfa(const int32_t *row, DagRow &r) {
+        const thfhe_dag_lhe_families &L = *F.lhe;
+        THFHE_TRY(no_operands(row));
+        if (!L.wfas) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: no automaton specs given (null family)");
+        if (row[4] < 0 || row[4] >= L.n_wfas) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: wfa out of range (0 .. n_wfas-1)");
+        const thfhe_dag_wfa_spec &a = L.wfas[row[4]];
+        r.cls = kDagLheWfa, r.entry = row[4];
+        if (first_use(kDagLheWfa, row[4])) THFHE_TRY(dag_wfa_spec_check(L, a));
+        if (!L.fin_b || L.n_fin_rows < 1) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: no final weights given (null family)");
+        if (row[5] < 0 || (long)row[5] + a.n_states > L.n_fin_rows)
+            return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: fin_row0 + n_states out of range (0 .. n_fin_rows)");
+        r.outs = a.n_out * a.theta - 1;
+        return THFHE_OK;
+    }
+    // a row other than LUT_OUT: the checker of its kind; an opcode of a generation the run does not admit goes to the engine's gates
+    template <typename Classify>
+    int node(const int32_t *row, int32_t w, Classify classify, DagRow &r) {
+        const int32_t op = row[0];
+        if ((F.gens & kDagGenLut) && op == THFHE_LUT) return lut(row, false, r);
+        if ((F.gens & kDagGenTree) && op == THFHE_LUT_ENC) return lut(row, true, r);
+        if ((F.gens & kDagGenTree) && (op == THFHE_SELECT || op == THFHE_TREE)) return tree(row, w, op == THFHE_TREE, r);
+        if ((F.gens & kDagGenMv) && (op == THFHE_MV || op == THFHE_TREE_MV)) return mv(row, op == THFHE_TREE_MV, r);
+        if ((F.gens & kDagGenLhe) && (op == THFHE_LHE_LOOKUP || op == THFHE_LHE_GATHER)) return lookup(row, w, op == THFHE_LHE_GATHER, r);
+        if ((F.gens & kDagGenLhe) && op == THFHE_LHE_WFA) return wfa(row, r);
+        return gate(row, classify, r);
+    }
+};
+
 struct DagPlan {
     std::vector<DagBatch> batches;
     std::vector<int32_t> tab;
@@ -209,7 +455,8 @@ struct DagPlan {
     int32_t max_depth = 0;
     void fill_stats(int64_t *stats) const {
         stats[0] = max_depth, stats[1] = 0, stats[2] = rotations, stats[3] = (int64_t)max_width;
-        for (const auto &b : batches) stats[1] += b.cls == kDagTree || b.cls == kDagTreeMv ? 2 : (b.cls != 2);   // a TREE / TREE_MV group: level-1 and selection launch
+        // a TREE / TREE_MV group: level-1 and selection launch
+        for (const auto &b : batches) stats[1] += b.cls == kDagTree || b.cls == kDagTreeMv ? 2 : (b.cls != kDagLinear);
     }
     bool has_tree_groups() const {
         for (const auto &b : batches)
@@ -223,307 +470,106 @@ struct DagPlan {
     }
 };
 
-// ASAP schedule.  gates: int32[n_gates][4] = (opcode, in0, in1, in2) in topological order; gate g defines wire n_inputs + g.
-// classify(op) -> class id (0 = two-input bootstrapped gate, 1 = MUX, 2 = NOT / COPY, 3 = three-input bootstrapped gate) or -1.
-// Bootstrapped gates add one level; NOT / COPY ride on their operand's level as sub-levels (a NOT may read a NOT of the same depth).
-// luts (thfhe_dag_run_lut_batch): rows of 6 words (opcode, in0, in1, in2, spec, lut); a THFHE_LUT node adds one level like a bootstrapped
-// gate and joins the launch group of its theta; its theta - 1 THFHE_LUT_OUT rows take its depth with sub-level 0 and launch nothing.
-// luts->ext (thfhe_dag_run_tree_batch): THFHE_LUT_ENC rows are LUT rows over the encrypted tables (classes 8 / 9 / 10); THFHE_SELECT and THFHE_TREE
-// rows add one level above their operands (a SELECT's candidates included) and form one group per trees[] entry, emitted after the other classes.
-// luts->mv (thfhe_dag_run_mv_batch): THFHE_MV and THFHE_TREE_MV rows (mv, t) add one level and form one group per mvs[] entry, emitted after those;
-// q - 1 (MV) or k - 1 (TREE_MV) LUT_OUT rows follow the head.
-// luts->lhe (thfhe_dag_run_lhe_batch): LHE_LOOKUP, LHE_GATHER and LHE_WFA rows (no wire operands; lk / wfa, row0 / first / fin_row0) add one level --
-// a GATHER above its candidates, the two others on the first -- and form one group per lks[] / wfas[] entry, emitted after those; theta - 1 (LOOKUP) or
-// n_out theta - 1 (WFA) LUT_OUT rows follow the head.
+// the blind rotations of a launch group of `count` nodes: a MUX takes two, a TREE node its R level-1 rotations and the selection, a TREE_MV node one
+// multi-value rotation and k selections; a linear gate and a leveled node none
+inline size_t dag_group_rotations(const DagFamilies &F, int cls, int32_t entry, size_t count) {
+    if (cls == kDagLinear || cls >= kDagLheLookup) return 0;
+    if (cls == kDagMux) return 2 * count;
+    if (cls == kDagTree) return count * (size_t)(F.trees[entry].p_hi / F.trees[entry].lo.theta + 1);
+    if (cls == kDagTreeMv) return count * (size_t)(1 + F.mvs[entry].k);
+    return count;
+}
+
+// ASAP schedule of A.nodes: int32[n_nodes][4] = (opcode, in0, in1, in2) in topological order, or, with any generation of F, rows of 6 words
+// (opcode, in0, in1, in2, spec, lut); node g defines wire n_inputs + g.  F has passed dag_families_check.
+// classify(op) -> kDagGate2, kDagMux, kDagLinear or kDagGate3, or -1.
+// Every bootstrapped gate and every node adds one level above its operands (a SELECT's and a GATHER's candidates included; LHE_LOOKUP and LHE_WFA
+// nodes have no wire operands and sit on the first); NOT / COPY ride on their operand's level as sub-levels (a NOT may read a NOT of the same
+// depth).  The LUT_OUT rows a head is due -- theta - 1 (LUT, LUT_ENC, LHE_LOOKUP), q - 1 (MV), k - 1 (TREE_MV), n_out theta - 1 (LHE_WFA) -- take
+// its depth with sub-level 0 and launch nothing.
+// Launch groups of a level, in this order: the gate classes kDagGate2, kDagGate3, kDagMux; the LUT classes by theta; the LUT_ENC classes by theta;
+// the grouped kinds by ascending (class, entry), one group per entry; the linear sub-levels.
 template <typename Classify>
-int dag_plan(const int32_t *gates, size_t n_inputs, size_t n_gates, Classify classify, DagPlan &plan, const DagLuts *luts = nullptr) {
-    const size_t n_wires = n_inputs + n_gates, stride = luts ? 6 : 4;
+int dag_plan(const DagCall &A, const DagFamilies &F, Classify classify, DagPlan &plan) {
+    const size_t n_inputs = A.n_inputs, n_gates = A.n_nodes, n_wires = n_inputs + n_gates, stride = F.gens ? 6 : 4;
+    const int32_t *const gates = A.nodes;
     if (n_wires > (size_t)INT32_MAX / 2) return thfhe_fail(THFHE_E_INVALID, "too many wires");
-    std::vector<int32_t> depth(n_wires, 0), sub(n_wires, 0), cls(n_gates, 0);
-    const bool ext = luts && luts->ext;
-    std::vector<char> tree_lo_ok(ext ? (size_t)luts->n_trees : 0, 0);   // trees[] entries whose `lo` half a TREE row has had checked
-    const bool mvx = ext && luts->mv;
-    std::vector<char> mv_ok(mvx ? (size_t)luts->n_mvs : 0, 0);          // mvs[] entries checked as an MV (bit 0) / a TREE_MV (bit 1) row uses them
-    const thfhe_dag_lhe_families *const lhe = mvx ? luts->lhe : nullptr;
-    std::vector<char> lk_ok(lhe && lhe->lks ? (size_t)lhe->n_lks : 0, 0), wfa_ok(lhe && lhe->wfas ? (size_t)lhe->n_wfas : 0, 0);   // as mv_ok: LOOKUP bit 0, GATHER bit 1
+    std::vector<int32_t> depth(n_wires, 0), sub(n_wires, 0);
+    std::vector<DagRow> rows(n_gates);
+    DagRowChecks checks{F, {}};
     int32_t max_depth = 0;
-    int32_t head = -1, pending = 0;   // the LUT node whose LUT_OUT rows are still due, and how many
+    int32_t head = -1, pending = 0;   // the node whose LUT_OUT rows are still due, and how many
     for (size_t g = 0; g < n_gates; g++) {
         const int32_t *row = gates + stride * g;
-        const int32_t op = row[0], w = (int32_t)(n_inputs + g);
-        if (luts && op == THFHE_LUT_OUT) {
-            if (pending == 0) return thfhe_fail(THFHE_E_INVALID, "LUT_OUT row without a LUT node before it (extra or misplaced LUT_OUT row)");
-            if (row[1] != head) return thfhe_fail(THFHE_E_INVALID, "LUT_OUT row names the wrong head (it must name its LUT node's wire)");
-            if (row[2] != -1 || row[3] != -1 || row[4] != -1 || row[5] != -1) return thfhe_fail(THFHE_E_INVALID, "LUT_OUT row: fields after the head must be -1");
+        const int32_t w = (int32_t)(n_inputs + g);
+        DagRow &r = rows[g];
+        if (F.gens && row[0] == THFHE_LUT_OUT) {
+            THFHE_TRY(DagRowChecks::lut_out(row, head, pending));
             pending--;
-            cls[g] = kDagLutOut;
             depth[w] = depth[head], sub[w] = 0;
             continue;
         }
         if (pending) return thfhe_fail(THFHE_E_INVALID, "LUT node: missing LUT_OUT row (theta - 1 of them must follow it)");
-        int k, nin;
-        int32_t cand_first = 0, cand_count = 0;   // SELECT: its candidate wires
-        if (luts && (op == THFHE_LUT || (ext && op == THFHE_LUT_ENC))) {
-            const bool enc = op == THFHE_LUT_ENC;
-            if (ext && (!luts->specs || (!enc && luts->n_luts == 0)))
-                return thfhe_fail(THFHE_E_INVALID, enc ? "LUT_ENC node: no specs given (null table family)" : "LUT node: no specs or no tables given (null table family)");
-            if (enc && luts->n_enc < 1) return thfhe_fail(THFHE_E_INVALID, "LUT_ENC node: n_enc must be 1 .. 262144 (null table family)");
-            if (row[4] < 0 || row[4] >= luts->n_specs) return thfhe_fail(THFHE_E_INVALID, "LUT node: spec index out of range (0 .. n_specs-1)");
-            if (!enc && (row[5] < 0 || row[5] >= luts->n_luts)) return thfhe_fail(THFHE_E_INVALID, "LUT node: table index out of range (0 .. n_luts-1)");
-            if (enc && (row[5] < 0 || row[5] >= luts->n_enc)) return thfhe_fail(THFHE_E_INVALID, "LUT_ENC node: etab out of range (0 .. n_enc-1)");
-            const thfhe_lut_spec &sp = luts->specs[row[4]];
-            nin = sp.n_inputs;
-            for (int q = 0; q < 3; q++)
-                if ((q < nin) != (row[1 + q] != -1)) return thfhe_fail(THFHE_E_INVALID, "LUT node: operands do not match the spec's n_inputs (unused ones are -1)");
-            k = enc ? kDagEnc + (dag_lut_class(sp.theta) - 4) : dag_lut_class(sp.theta);
-            head = w, pending = sp.theta - 1;
-        } else if (ext && (op == THFHE_SELECT || op == THFHE_TREE)) {
-            const bool is_tree = op == THFHE_TREE;
-            if (!luts->trees) return thfhe_fail(THFHE_E_INVALID, "SELECT / TREE node: no tree specs given (null table family)");
-            if (row[4] < 0 || row[4] >= luts->n_trees) return thfhe_fail(THFHE_E_INVALID, "SELECT / TREE node: tree index out of range (0 .. n_trees-1)");
-            const thfhe_tree_spec &ts = luts->trees[row[4]];
-            nin = ts.hi.n_inputs;
-            if (is_tree) {
-                if (!tree_lo_ok[row[4]]) {
-                    THFHE_TRY(lut_spec_check(ts.lo));
-                    if (ts.p_hi % ts.lo.theta) return thfhe_fail(THFHE_E_INVALID, "tree: spec_lo theta must divide p_hi");
-                    tree_lo_ok[row[4]] = 1;
-                }
-                nin += ts.lo.n_inputs;
-                if (nin > 3) return thfhe_fail(THFHE_E_INVALID, "TREE node: lo and hi operands exceed three");
-                if (luts->n_tv1_rows < 1) return thfhe_fail(THFHE_E_INVALID, "TREE node: no level-1 rows given (null table family)");
-                if (row[5] < 0 || (long)row[5] + ts.p_hi / ts.lo.theta > luts->n_tv1_rows)
-                    return thfhe_fail(THFHE_E_INVALID, "TREE node: row0 + R out of range (0 .. n_tv1_rows)");
-            } else {
-                cand_first = row[5], cand_count = ts.p_hi;
-                if (cand_first < 0 || (long)cand_first + cand_count > (long)w)
-                    return thfhe_fail(THFHE_E_INVALID, "SELECT node: candidate is not an earlier wire (first .. first + p - 1 must all be defined above)");
-            }
-            for (int q = 0; q < 3; q++)
-                if ((q < nin) != (row[1 + q] != -1))
-                    return thfhe_fail(THFHE_E_INVALID, is_tree ? "TREE node: operands do not match lo.n_inputs + hi.n_inputs (unused ones are -1)"
-                                                               : "SELECT node: operands do not match hi.n_inputs (unused ones are -1)");
-            k = is_tree ? kDagTree : kDagSelect;
-        } else if (mvx && (op == THFHE_MV || op == THFHE_TREE_MV)) {
-            const bool is_tree = op == THFHE_TREE_MV;
-            if (!luts->mvs) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: no multi-value specs given (null table family)");
-            if (row[4] < 0 || row[4] >= luts->n_mvs) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: mv index out of range (0 .. n_mvs-1)");
-            const thfhe_mv_spec &m = luts->mvs[row[4]];
-            if (!(mv_ok[row[4]] & (is_tree ? 2 : 1))) {
-                THFHE_TRY(dag_mv_spec_check(*luts, m, is_tree));
-                mv_ok[row[4]] |= is_tree ? 2 : 1;
-            }
-            if (row[5] < 0 || row[5] >= m.n_tables) return thfhe_fail(THFHE_E_INVALID, "MV / TREE_MV node: table index out of range (0 .. n_tables-1)");
-            nin = m.lo.n_inputs + (is_tree ? m.hi.n_inputs : 0);
-            if (nin > 3) return thfhe_fail(THFHE_E_INVALID, "TREE_MV node: lo and hi operands exceed three");
-            for (int q = 0; q < 3; q++)
-                if ((q < nin) != (row[1 + q] != -1))
-                    return thfhe_fail(THFHE_E_INVALID, is_tree ? "TREE_MV node: operands do not match lo.n_inputs + hi.n_inputs (unused ones are -1)"
-                                                               : "MV node: operands do not match lo.n_inputs (unused ones are -1)");
-            k = is_tree ? kDagTreeMv : kDagMv;
-            head = w, pending = (is_tree ? m.k : m.q) - 1;
-        } else if (lhe && (op == THFHE_LHE_LOOKUP || op == THFHE_LHE_GATHER)) {
-            const bool gather = op == THFHE_LHE_GATHER;
-            if (row[1] != -1 || row[2] != -1 || row[3] != -1) return thfhe_fail(THFHE_E_INVALID, "leveled node: the operand fields must be -1");
-            if (!lhe->lks) return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP / LHE_GATHER node: no lookup specs given (null family)");
-            if (row[4] < 0 || row[4] >= lhe->n_lks) return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP / LHE_GATHER node: lk out of range (0 .. n_lks-1)");
-            const thfhe_dag_lhe_spec &ls = lhe->lks[row[4]];
-            if (!(lk_ok[row[4]] & (gather ? 2 : 1))) {
-                THFHE_TRY(dag_lhe_spec_check(*lhe, ls, gather));
-                lk_ok[row[4]] |= gather ? 2 : 1;
-            }
-            if (gather) {
-                cand_first = row[5], cand_count = (int32_t)1 << (ls.d_tree + ls.d_rot);
-                if (cand_first < 0 || (long)cand_first + cand_count > (long)w)
-                    return thfhe_fail(THFHE_E_INVALID, "LHE_GATHER node: candidate is not an earlier wire (first .. first + 2^d - 1 must all be defined above)");
-            } else {
-                if (!lhe->tab_b || lhe->n_tab_rows < 1) return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP node: no table rows given (null family)");
-                if (row[5] < 0 || (long)row[5] + (1L << ls.d_tree) > lhe->n_tab_rows)
-                    return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP node: row0 + 2^d_tree out of range (0 .. n_tab_rows)");
-                head = w, pending = ls.theta - 1;
-            }
-            nin = 0;
-            k = gather ? kDagLheGather : kDagLheLookup;
-        } else if (lhe && op == THFHE_LHE_WFA) {
-            if (row[1] != -1 || row[2] != -1 || row[3] != -1) return thfhe_fail(THFHE_E_INVALID, "leveled node: the operand fields must be -1");
-            if (!lhe->wfas) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: no automaton specs given (null family)");
-            if (row[4] < 0 || row[4] >= lhe->n_wfas) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: wfa out of range (0 .. n_wfas-1)");
-            const thfhe_dag_wfa_spec &a = lhe->wfas[row[4]];
-            if (!wfa_ok[row[4]]) {
-                THFHE_TRY(dag_wfa_spec_check(*lhe, a));
-                wfa_ok[row[4]] = 1;
-            }
-            if (!lhe->fin_b || lhe->n_fin_rows < 1) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: no final weights given (null family)");
-            if (row[5] < 0 || (long)row[5] + a.n_states > lhe->n_fin_rows)
-                return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: fin_row0 + n_states out of range (0 .. n_fin_rows)");
-            head = w, pending = a.n_out * a.theta - 1;
-            nin = 0;
-            k = kDagLheWfa;
-        } else {
-            k = classify(op);
-            if (k < 0) return thfhe_fail(THFHE_E_INVALID, "gate opcode not defined for this engine");
-            if (luts && (row[4] != -1 || row[5] != -1)) return thfhe_fail(THFHE_E_INVALID, "gate row: spec and lut must be -1");
-            nin = k == 2 ? 1 : (k == 0 ? 2 : 3);
-        }
-        cls[g] = k;
+        THFHE_TRY(checks.node(row, w, classify, r));
+        head = w, pending = r.outs;
         int32_t d = 0, s = 0;
-        for (int q = 0; q < nin; q++) {
+        auto above = [&](int32_t in) {
+            if (depth[in] > d || (depth[in] == d && sub[in] > s)) d = depth[in], s = sub[in];
+        };
+        for (int q = 0; q < r.nin; q++) {
             const int32_t in = row[1 + q];
             if (in < 0 || in >= w) return thfhe_fail(THFHE_E_INVALID, "gate operand is not an earlier wire (gates must be in topological order)");
-            if (depth[in] > d || (depth[in] == d && sub[in] > s)) d = depth[in], s = sub[in];
+            above(in);
         }
-        for (int32_t in = cand_first; in < cand_first + cand_count; in++)
-            if (depth[in] > d || (depth[in] == d && sub[in] > s)) d = depth[in], s = sub[in];
-        if (k == 2) s += 1; else d += 1, s = 0;
+        for (int32_t in = r.cand_first; in < r.cand_first + r.cand_count; in++) above(in);
+        if (r.cls == kDagLinear) s += 1; else d += 1, s = 0;
         depth[w] = d, sub[w] = s;
         if (d > max_depth) max_depth = d;
     }
     if (pending) return thfhe_fail(THFHE_E_INVALID, "LUT node: missing LUT_OUT row (theta - 1 of them must follow it)");
     plan.max_depth = max_depth;
-    // bucket: (depth, sub, class); bootstrapped classes first (sub 0), then the linear sub-levels in order
-    std::vector<std::vector<std::vector<int32_t>>> boot(max_depth + 1, std::vector<std::vector<int32_t>>(kDagSelect)), lin(max_depth + 1);
-    std::vector<std::map<int32_t, std::vector<int32_t>>> sel(ext ? max_depth + 1 : 0), tre(ext ? max_depth + 1 : 0);   // per level, by trees[] index
-    std::vector<std::map<int32_t, std::vector<int32_t>>> mvn(mvx ? max_depth + 1 : 0), tmv(mvx ? max_depth + 1 : 0);   // per level, by mvs[] index
-    std::vector<std::map<int32_t, std::vector<int32_t>>> lhg[3];   // LOOKUP / GATHER / WFA nodes per level, by lks[] / wfas[] index
-    for (auto &v : lhg) v.resize(lhe ? max_depth + 1 : 0);
+    // per level: the bootstrapped groups by (class, entry) -- entry -1 for the classes that are one group --, and the linear sub-levels in order
+    struct Level {
+        std::map<std::pair<int, int32_t>, std::vector<int32_t>> boot;
+        std::vector<std::vector<int32_t>> lin;
+    };
+    std::vector<Level> levels(max_depth + 1);
     for (size_t g = 0; g < n_gates; g++) {
         const int32_t w = (int32_t)(n_inputs + g);
-        if (cls[g] == kDagLutOut) continue;
-        if (cls[g] == kDagSelect || cls[g] == kDagTree) {
-            (cls[g] == kDagTree ? tre : sel)[depth[w]][gates[stride * g + 4]].push_back((int32_t)g);
-        } else if (cls[g] == kDagMv || cls[g] == kDagTreeMv) {
-            (cls[g] == kDagTreeMv ? tmv : mvn)[depth[w]][gates[stride * g + 4]].push_back((int32_t)g);
-        } else if (cls[g] >= kDagLheLookup) {
-            lhg[cls[g] - kDagLheLookup][depth[w]][gates[stride * g + 4]].push_back((int32_t)g);
-        } else if (cls[g] == 2) {
-            auto &L = lin[depth[w]];
+        if (rows[g].cls == kDagLutOut) continue;
+        if (rows[g].cls == kDagLinear) {
+            auto &L = levels[depth[w]].lin;
             if ((int)L.size() < sub[w]) L.resize(sub[w]);
             L[sub[w] - 1].push_back((int32_t)g);
         } else {
-            boot[depth[w]][cls[g]].push_back((int32_t)g);
+            levels[depth[w]].boot[{rows[g].cls, rows[g].entry}].push_back((int32_t)g);
         }
     }
     plan.tab.reserve(5 * n_gates);
-    auto emit = [&](int32_t d, int32_t s, int32_t k, const std::vector<int32_t> &G, int32_t tree = -1) {
-        if (G.empty()) return;
-        DagBatch b{d, s, k, plan.tab.size(), G.size(), tree};
-        const int cols = k >= 4 ? 7 : 5;   // LUT groups: + spec, lut
-        for (int col = 0; col < cols; col++)
-            for (int32_t g : G) {
-                const int32_t *row = gates + stride * g;   // columns 5, 6 = row fields 4, 5 (spec, lut)
-                plan.tab.push_back(col == 4 ? (int32_t)(n_inputs + g) : (col == 0 ? row[0] : (row[col < 4 ? col : col - 1] < 0 ? 0 : row[col < 4 ? col : col - 1])));
-            }
-        plan.batches.push_back(b);
-        if (G.size() > plan.max_width) plan.max_width = G.size();
-        size_t rot = k == 2 || k >= kDagLheLookup ? 0 : (k == 1 ? 2 * G.size() : G.size());   // a leveled node counts no blind rotation
-        if (k == kDagTree) rot = G.size() * (size_t)(luts->trees[tree].p_hi / luts->trees[tree].lo.theta + 1);   // R level-1 rotations + the selection
-        if (k == kDagTreeMv) rot = G.size() * (size_t)(1 + luts->mvs[tree].k);   // one multi-value rotation + k selections
-        if (rot > plan.max_rot) plan.max_rot = rot;
-        if (k >= 4 && k < kDagSelect && dag_lut_theta(k < kDagEnc ? k : k - 4) > plan.max_theta) plan.max_theta = dag_lut_theta(k < kDagEnc ? k : k - 4);
+    auto emit = [&](int32_t d, int32_t s, int32_t k, const std::vector<int32_t> &G, int32_t entry) {
+        static constexpr int kField[7] = {0, 1, 2, 3, -1, 4, 5};   // [ops | in0 | in1 | in2 | out | spec | lut] from the row's fields; out: the node's wire
+        plan.batches.push_back(DagBatch{d, s, k, plan.tab.size(), G.size(), entry});
+        for (int col = 0; col < (k >= kDagLut1 ? 7 : 5); col++)   // an unused field (-1) reads as 0
+            for (int32_t g : G) plan.tab.push_back(kField[col] < 0 ? (int32_t)(n_inputs + g) : std::max(gates[stride * g + kField[col]], 0));
+        const size_t rot = dag_group_rotations(F, k, entry, G.size());
+        plan.max_width = std::max(plan.max_width, G.size()), plan.max_rot = std::max(plan.max_rot, rot), plan.max_theta = std::max(plan.max_theta, dag_class_theta(k));
         plan.rotations += (int64_t)rot;
     };
     for (int32_t d = 0; d <= max_depth; d++) {
-        for (int32_t k : {0, 3, 1, 4, 5, 6}) emit(d, 0, k, boot[d][k]);
-        if (ext) {
-            for (int32_t k : {8, 9, 10}) emit(d, 0, k, boot[d][k]);
-            for (const auto &kv : sel[d]) emit(d, 0, kDagSelect, kv.second, kv.first);
-            for (const auto &kv : tre[d]) emit(d, 0, kDagTree, kv.second, kv.first);
-        }
-        if (mvx) {
-            for (const auto &kv : mvn[d]) emit(d, 0, kDagMv, kv.second, kv.first);
-            for (const auto &kv : tmv[d]) emit(d, 0, kDagTreeMv, kv.second, kv.first);
-        }
-        if (lhe)
-            for (int q = 0; q < 3; q++)
-                for (const auto &kv : lhg[q][d]) emit(d, 0, kDagLheLookup + q, kv.second, kv.first);
-        for (size_t q = 0; q < lin[d].size(); q++) emit(d, (int32_t)q + 1, 2, lin[d][q]);
+        const auto &boot = levels[d].boot;
+        for (int32_t k : {kDagGate2, kDagGate3, kDagMux, kDagLut1, kDagLut2, kDagLut4, kDagEnc1, kDagEnc2, kDagEnc4})
+            if (const auto it = boot.find({k, -1}); it != boot.end()) emit(d, 0, k, it->second, -1);
+        for (auto it = boot.lower_bound({kDagSelect, INT32_MIN}); it != boot.end(); ++it) emit(d, 0, it->first.first, it->second, it->first.second);
+        for (size_t q = 0; q < levels[d].lin.size(); q++) emit(d, (int32_t)q + 1, kDagLinear, levels[d].lin[q], -1);
     }
     return THFHE_OK;
 }
 
-// Host-side checks and plan of thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch, before any device work and before the context is looked
-// at: null pointers, the spec and table counts, every spec (the rules of lut_validate), the output wire ids, then dag_plan's row checks.
+// The host side of a six-column entry, before any device work and before a context is looked at: the family checks, then the row checks and the plan.
 template <typename Classify>
-int dag_lut_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs, int n_specs, const void *tv,
-                 int n_luts, const int32_t *out_wires, size_t n_out, const int32_t *outputs, Classify classify, DagPlan &plan) {
-    if ((!inputs && n_inputs) || (!nodes && n_nodes) || (!outputs && n_nodes) || (!out_wires && n_out) || !specs || !tv)
-        return thfhe_fail(THFHE_E_INVALID, "null argument");
-    if (n_specs < 1 || n_specs > 1024) return thfhe_fail(THFHE_E_INVALID, "n_specs must be 1 .. 1024");
-    if (n_luts < 1 || n_luts > 1024) return thfhe_fail(THFHE_E_INVALID, "n_luts must be 1 .. 1024");
-    for (int s = 0; s < n_specs; s++)
-        THFHE_TRY(lut_spec_check(specs[s]));
-    for (size_t s = 0; s < n_out; s++)
-        if (out_wires[s] < 0 || (size_t)out_wires[s] >= n_inputs + n_nodes) return thfhe_fail(THFHE_E_INVALID, "output wire id out of range");
-    const DagLuts luts{specs, n_specs, n_luts};
-    return dag_plan(nodes, n_inputs, n_nodes, classify, plan, &luts);
-}
-
-// Host-side checks and plan of thfhe_dag_run_tree_batch, before any device work and before either context is looked at: what
-// dag_lut_plan checks (specs / tv may both be absent), the encrypted-table and level-1 row counts, every tree spec's `hi` half and p_hi (the rules of
-// thfhe_tree_lut_bootstrap; the `lo` half when a TREE row uses the entry), then dag_plan's row checks with the three node kinds.
-// mv (thfhe_dag_run_mv_batch): the multi-value families too -- their counts here, every mvs[] entry when a row uses it (dag_mv_spec_check);
-// null: a run without them, which rejects MV and TREE_MV rows as opcodes it does not define.
-struct DagMvFamilies {
-    const thfhe_mv_spec *mvs;
-    int n_mvs;
-    const int32_t *tv0;
-    int n_bases;
-    const int32_t *factors;
-    size_t n_factor_words;
-};
-template <typename Classify>
-int dag_tree_plan(const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs, int n_specs, const int32_t *tv,
-                  int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc, const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1,
-                  int n_tv1_rows, const int32_t *out_wires, size_t n_out, const int32_t *outputs, Classify classify, DagPlan &plan,
-                  const DagMvFamilies *mv = nullptr, const thfhe_dag_lhe_families *lhe = nullptr) {
-    if ((!inputs && n_inputs) || (!nodes && n_nodes) || (!outputs && n_nodes) || (!out_wires && n_out)) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    if ((!specs && n_specs) || (!tv && n_luts) || ((!enc_a || !enc_b) && n_enc) || (!trees && n_trees) || (!tv1 && n_tv1_rows))
-        return thfhe_fail(THFHE_E_INVALID, "null argument: a table family with a count but no pointer");
-    if (n_specs < 0 || n_specs > 1024 || (specs && n_specs < 1)) return thfhe_fail(THFHE_E_INVALID, "n_specs must be 1 .. 1024 (0 with specs = NULL)");
-    if (n_luts < 0 || n_luts > 1024 || (tv && n_luts < 1)) return thfhe_fail(THFHE_E_INVALID, "n_luts must be 1 .. 1024 (0 with tv = NULL)");
-    if (n_enc < 0 || n_enc > (1 << 18)) return thfhe_fail(THFHE_E_INVALID, "n_enc must be 1 .. 262144 (0 with enc_a = enc_b = NULL)");
-    if (n_trees < 0 || n_trees > 1024 || (trees && n_trees < 1)) return thfhe_fail(THFHE_E_INVALID, "n_trees must be 1 .. 1024 (0 with trees = NULL)");
-    if (n_tv1_rows < 0 || n_tv1_rows > (1 << 18) || (tv1 && n_tv1_rows < 1)) return thfhe_fail(THFHE_E_INVALID, "n_tv1_rows must be 1 .. 262144 (0 with tv1 = NULL)");
-    if (mv) {
-        if ((!mv->mvs && mv->n_mvs) || (!mv->tv0 && mv->n_bases) || (!mv->factors && mv->n_factor_words))
-            return thfhe_fail(THFHE_E_INVALID, "null argument: a table family with a count but no pointer");
-        if (mv->n_mvs < 0 || mv->n_mvs > 1024 || (mv->mvs && mv->n_mvs < 1)) return thfhe_fail(THFHE_E_INVALID, "n_mvs must be 1 .. 1024 (0 with mvs = NULL)");
-        if (mv->n_bases < 0 || mv->n_bases > 1024 || (mv->tv0 && mv->n_bases < 1)) return thfhe_fail(THFHE_E_INVALID, "n_bases must be 1 .. 1024 (0 with mv_tv0 = NULL)");
-        if (mv->n_factor_words > ((size_t)1 << 28) || (mv->factors && mv->n_factor_words < 1))
-            return thfhe_fail(THFHE_E_INVALID, "n_factor_words must be 1 .. 2^28 (0 with mv_factors = NULL)");
-    }
-    if (lhe) {
-        if ((!lhe->sets && lhe->n_sets) || (!lhe->lks && lhe->n_lks) || (!lhe->tab_b && (lhe->n_tab_rows || lhe->tab_a)) || (!lhe->wfas && lhe->n_wfas) ||
-            (!lhe->wfa_words && lhe->n_wfa_words) || (!lhe->fin_b && (lhe->n_fin_rows || lhe->fin_a)))
-            return thfhe_fail(THFHE_E_INVALID, "null argument: a leveled family with a count but no pointer");
-        if (lhe->n_sets < 0 || lhe->n_sets > 64 || (lhe->sets && lhe->n_sets < 1)) return thfhe_fail(THFHE_E_INVALID, "lhe: n_sets must be 1 .. 64 (0 with sets = NULL)");
-        if (lhe->n_lks < 0 || lhe->n_lks > 1024 || (lhe->lks && lhe->n_lks < 1)) return thfhe_fail(THFHE_E_INVALID, "lhe: n_lks must be 1 .. 1024 (0 with lks = NULL)");
-        if (lhe->n_wfas < 0 || lhe->n_wfas > 1024 || (lhe->wfas && lhe->n_wfas < 1)) return thfhe_fail(THFHE_E_INVALID, "lhe: n_wfas must be 1 .. 1024 (0 with wfas = NULL)");
-        if (lhe->n_tab_rows < 0 || lhe->n_tab_rows > (1 << 18) || (lhe->tab_b && lhe->n_tab_rows < 1))
-            return thfhe_fail(THFHE_E_INVALID, "lhe: n_tab_rows must be 1 .. 262144 (0 with tab_b = NULL)");
-        if (lhe->n_fin_rows < 0 || lhe->n_fin_rows > (1 << 18) || (lhe->fin_b && lhe->n_fin_rows < 1))
-            return thfhe_fail(THFHE_E_INVALID, "lhe: n_fin_rows must be 1 .. 262144 (0 with fin_b = NULL)");
-        if (lhe->n_wfa_words > ((size_t)1 << 28) || (lhe->wfa_words && lhe->n_wfa_words < 1))
-            return thfhe_fail(THFHE_E_INVALID, "lhe: n_wfa_words must be 1 .. 2^28 (0 with wfa_words = NULL)");
-    }
-    for (int s = 0; s < n_specs; s++)
-        THFHE_TRY(lut_spec_check(specs[s]));
-    for (int t = 0; t < n_trees; t++) {
-        THFHE_TRY(lut_spec_check(trees[t].hi));
-        if (trees[t].hi.theta != 1) return thfhe_fail(THFHE_E_INVALID, "tree: spec_hi theta must be 1 (the packed table holds one function)");
-        const int p_hi = trees[t].p_hi;
-        if (p_hi < 2 || p_hi > 512 || (p_hi & (p_hi - 1))) return thfhe_fail(THFHE_E_INVALID, "tree: p_hi must be a power of two in 2 .. N/2");
-    }
-    for (size_t s = 0; s < n_out; s++)
-        if (out_wires[s] < 0 || (size_t)out_wires[s] >= n_inputs + n_nodes) return thfhe_fail(THFHE_E_INVALID, "output wire id out of range");
-    DagLuts luts{specs, n_specs, n_luts};
-    luts.ext = true, luts.n_enc = enc_a ? n_enc : 0, luts.trees = trees, luts.n_trees = n_trees, luts.n_tv1_rows = tv1 ? n_tv1_rows : 0;
-    if (mv) {
-        luts.mv = true, luts.mvs = mv->mvs, luts.n_mvs = mv->mvs ? mv->n_mvs : 0, luts.n_bases = mv->tv0 ? mv->n_bases : 0;
-        luts.n_factor_words = mv->factors ? mv->n_factor_words : 0;
-        luts.lhe = lhe;
-    }
-    return dag_plan(nodes, n_inputs, n_nodes, classify, plan, &luts);
+int dag_checked_plan(const DagCall &A, const DagFamilies &F, Classify classify, DagPlan &plan) {
+    THFHE_TRY(dag_families_check(A, F));
+    return dag_plan(A, F, classify, plan);
 }
 
 // Device buffers of the executor (grow-only, owned by the engine's context and reused by every run on it).
@@ -561,19 +607,20 @@ struct DagExtGroup {
 // Device-resident executor.  Level by level, each class of a level as slices of at most `slice_cap` gates over ALL instances: gather ->
 // run(cls, d_ops, n) (the engine's prologue + blind rotations + key switch from its staging arrays stage_in[0..2] into stage_out) ->
 // scatter.  Nothing synchronises with the host between levels.
-//   h_inputs  int32[instances][n_inputs][words]
-//   h_sel     wire ids to return (n_sel of them) or null = every gate wire [n_inputs, n_wires)
-//   h_out     int32[instances][n_sel or n_gates][words]
+//   A.inputs     int32[instances][n_inputs][words]
+//   A.out_wires  wire ids to return (n_out of them) or null = every gate wire [n_inputs, n_wires)
+//   A.outputs    int32[instances][n_out or n_nodes][words]
 // ensure(max_gates_per_slice) sizes the engine's workspace and staging and returns its staging pointers through the out-parameters.
 // LUT and LUT_ENC launch groups: run_lut(theta, DagLutSlice) -> prologue + LUT rotation + key switch of the slice's nodes x theta records into
 // the staging output, then the theta-record scatter into wires out[g] + j.  ensure sizes for plan.max_theta records per node.  SELECT / TREE
 // groups (plans of thfhe_dag_run_tree_batch): run_ext(DagExtGroup) slices, runs and scatters the whole group.  An engine without run_ext
 // rejects all three kinds.
 template <typename Ensure, typename Run, typename RunLut = std::nullptr_t, typename RunExt = std::nullptr_t>
-int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int words, size_t n_inputs, size_t n_gates, size_t instances,
-                const int32_t *h_inputs, const int32_t *h_sel, size_t n_sel, int32_t *h_out, size_t slice_cap, Ensure ensure, Run run,
+int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int words, const DagCall &A, size_t instances, size_t slice_cap, Ensure ensure, Run run,
                 RunLut run_lut = nullptr, RunExt run_ext = nullptr) {
-    const size_t n_wires = n_inputs + n_gates;
+    const size_t n_inputs = A.n_inputs, n_gates = A.n_nodes, n_sel = A.n_out, n_wires = n_inputs + n_gates;
+    const int32_t *const h_inputs = A.inputs, *const h_sel = A.out_wires;
+    int32_t *const h_out = A.outputs;
     if (instances == 0 || n_gates == 0) return THFHE_OK;
     if (n_wires * instances > ((size_t)1 << 40) / (size_t)words) return thfhe_fail(THFHE_E_INVALID, "wire table too large");
     for (size_t s = 0; s < n_sel; s++)
@@ -601,11 +648,11 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
         const long cnt = (long)plan.batches[b].count, all = cnt * (long)instances;
         const int cls = plan.batches[b].cls;
         const int32_t *t_ops = d_tab + plan.batches[b].off, *t0 = t_ops + cnt, *t1 = t0 + cnt, *t2 = t1 + cnt, *t_out = t2 + cnt;
-        if (cls == 2) {
+        if (cls == kDagLinear) {
             hipLaunchKernelGGL(dag_wire_linear_kernel, dim3((unsigned)all, wb), block, 0, stream, d_wires, t0, t_out, t_ops, all, cnt, n_wires, words);
             continue;
         }
-        if (cls >= kDagEnc && std::is_same_v<RunExt, std::nullptr_t>) {
+        if (cls >= kDagEnc1 && std::is_same_v<RunExt, std::nullptr_t>) {
             rc = thfhe_fail(THFHE_E_INVALID, "encrypted-table, select or tree node in a run without them");
             continue;
         }
@@ -614,12 +661,12 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
                 rc = run_ext(DagExtGroup{cls, plan.batches[b].tree, d_wires, t0, t1, t2, t_out, t_out + 2 * cnt, all, cnt, n_wires, plan.batches[b].off});
             continue;
         }
-        if (cls >= 4) {   // LUT groups, and LUT_ENC groups over the run's encrypted tables
+        if (cls >= kDagLut1) {   // LUT groups, and LUT_ENC groups over the run's encrypted tables
             if constexpr (std::is_same_v<RunLut, std::nullptr_t>) {
                 rc = thfhe_fail(THFHE_E_INVALID, "LUT node in a gate-only run");
             } else {
-                const bool enc = cls >= kDagEnc;
-                const int theta = enc ? dag_enc_theta(cls) : dag_lut_theta(cls);
+                const bool enc = cls >= kDagEnc1;
+                const int theta = dag_class_theta(cls);
                 const int32_t *t_spec = t_out + cnt, *t_lut = t_spec + cnt;
                 for (long first = 0; first < all && rc == THFHE_OK; first += (long)slice) {
                     const long n = all - first < (long)slice ? all - first : (long)slice;
@@ -636,7 +683,7 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
             const dim3 grid((unsigned)n, wb);
             hipLaunchKernelGGL(dag_gather_kernel, grid, block, 0, stream, d_wires, t0, stage_in[0], first, n, cnt, n_wires, words, t_ops, d_ops);
             hipLaunchKernelGGL(dag_gather_kernel, grid, block, 0, stream, d_wires, t1, stage_in[1], first, n, cnt, n_wires, words, nullptr, nullptr);
-            if (cls != 0) hipLaunchKernelGGL(dag_gather_kernel, grid, block, 0, stream, d_wires, t2, stage_in[2], first, n, cnt, n_wires, words, nullptr, nullptr);
+            if (cls != kDagGate2) hipLaunchKernelGGL(dag_gather_kernel, grid, block, 0, stream, d_wires, t2, stage_in[2], first, n, cnt, n_wires, words, nullptr, nullptr);
             rc = run(cls, d_ops, (size_t)n);
             if (!rc) hipLaunchKernelGGL(dag_scatter_kernel, grid, block, 0, stream, stage_out, t_out, d_wires, first, n, cnt, n_wires, words);
         }

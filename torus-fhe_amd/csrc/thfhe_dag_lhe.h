@@ -23,7 +23,8 @@ size_t dag_lhe_slice(const thfhe_ctx *c, const thfhe_dag_lhe_families &F, const 
 
 // The checks of thfhe_dag_run_lhe_batch that look at the sets, after the plan's, in the order of the header: null sets, (the null context,) a set of
 // another context, a set count below `instances`, d_tree + d_rot against the set's d, step_bit against the spec's sets.
-int sk_dag_lhe_check_sets(const thfhe_ctx *c, const DagPlan &plan, const thfhe_dag_lhe_families &F, size_t instances) {
+int sk_dag_lhe_check_sets(const thfhe_ctx *c, const DagPlan &plan, const DagFamilies &T, size_t instances) {
+    const thfhe_dag_lhe_families &F = *T.lhe;
     for (int i = 0; i < F.n_sets; i++)
         if (!F.sets[i]) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
@@ -49,7 +50,8 @@ int sk_dag_lhe_check_sets(const thfhe_ctx *c, const DagPlan &plan, const thfhe_d
 
 // Every buffer the leveled groups of the plan use, the staging output included, before dag_execute takes pointers; w_cand: the most candidates one
 // box packing of the run takes.  Then the run's table polynomials, final weights and word pool, once per call.
-int sk_dag_lhe_reserve(thfhe_ctx *c, const DagPlan &plan, const thfhe_dag_lhe_families &F, size_t instances, size_t &w_cand) {
+int sk_dag_lhe_reserve(thfhe_ctx *c, const DagPlan &plan, const DagFamilies &T, size_t instances, size_t &w_cand) {
+    const thfhe_dag_lhe_families &F = *T.lhe;
     const size_t words = c->p.n + 1;
     bool any = false;
     for (const DagBatch &b : plan.batches) {
@@ -79,7 +81,7 @@ int sk_dag_lhe_reserve(thfhe_ctx *c, const DagPlan &plan, const thfhe_dag_lhe_fa
     }
     if (!any) return THFHE_OK;
     auto upload = [&](DevBuf &d, const void *h, size_t bytes) -> int {
-        if (!h || !bytes) return THFHE_OK;
+        if (!h) return THFHE_OK;   // a family the run does not have (its count is 0: dag_families_check), or public tables / weights (no masks)
         THFHE_TRY(d.grow(bytes));
         THFHE_HIP(hipMemcpyAsync(d.as<void>(), h, bytes, hipMemcpyHostToDevice, c->stream));
         return THFHE_OK;
@@ -96,7 +98,8 @@ int sk_dag_lhe_reserve(thfhe_ctx *c, const DagPlan &plan, const thfhe_dag_lhe_fa
 //   GATHER  dag_lhe_gather_kernel stages the slice's 2^d candidates per instance from the wire table, the packing context packs them into 2^d_tree
 //           TLWE samples per instance (boxes of N / 2^d_rot coefficients), and the lookup chain reads instance j's own samples (stride 2^d_tree).
 //   WFA     the chain of thfhe_lhe_wfa on the spec's slices of the word pool and the final weights from fin_row0.
-int sk_dag_lhe_group(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const thfhe_dag_lhe_families &F, const DagExtGroup &g, size_t instances) {
+int sk_dag_lhe_group(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const DagFamilies &T, const DagExtGroup &g, size_t instances) {
+    const thfhe_dag_lhe_families &F = *T.lhe;
     hipStream_t st = c->stream;
     const int words = c->p.n + 1;
     const unsigned wb = (unsigned)((words + 255) / 256);

@@ -1180,7 +1180,10 @@ int mk_gates_dev_locked(thfhe_mk_ctx *c, int op, const int32_t *d0, const int32_
 
 // gate classes of the 3-gen gate DAG (thfhe_dag.h): two-input gates NAND / OR / AND / XOR, MUX, NOT / COPY, AND3
 int mk_dag_classify(int op) {
-    return op == THFHE_NOT || op == THFHE_COPY ? 2 : (op == THFHE_MUX ? 1 : (op == THFHE_AND3 ? 3 : (op == THFHE_NAND || op == THFHE_OR || op == THFHE_AND || op == THFHE_XOR ? 0 : -1)));
+    if (op == THFHE_NOT || op == THFHE_COPY) return kDagLinear;
+    if (op == THFHE_MUX) return kDagMux;
+    if (op == THFHE_AND3) return kDagGate3;
+    return op == THFHE_NAND || op == THFHE_OR || op == THFHE_AND || op == THFHE_XOR ? kDagGate2 : -1;
 }
 
 // one launch of a gate-DAG gate class from the staging arrays into stage.out (dag_execute's run): two-input gates with per-gate opcodes, MUX
@@ -1188,8 +1191,8 @@ int mk_dag_classify(int op) {
 int mk_dag_gate_class(thfhe_mk_ctx *c, int cls, const int32_t *d_ops, size_t n) {
     MKLin L;
     mk_gate_lin(THFHE_NAND, 0, L);
-    if (cls == 0) return mk_enqueue_bootstraps(c, c->stage.in_ptr(0), c->stage.in_ptr(1), nullptr, L, L, 1, n, (int64_t)1 << 61, c->stage.out_ptr(), d_ops);
-    return mk_gates_dev_locked(c, cls == 1 ? THFHE_MUX : THFHE_AND3, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), c->stage.out_ptr(), n);
+    if (cls == kDagGate2) return mk_enqueue_bootstraps(c, c->stage.in_ptr(0), c->stage.in_ptr(1), nullptr, L, L, 1, n, (int64_t)1 << 61, c->stage.out_ptr(), d_ops);
+    return mk_gates_dev_locked(c, cls == kDagMux ? THFHE_MUX : THFHE_AND3, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), c->stage.out_ptr(), n);
 }
 
 // thfhe_mk_lut_bootstrap (keyswitch) / thfhe_mk_lut_bootstrap_wo_keyswitch: out = count x theta records of P n + 1 (resp. N + 1) words
@@ -1327,15 +1330,15 @@ int thfhe_mk_gates(thfhe_mk_ctx *c, int op, const int32_t *in0, const int32_t *i
 int thfhe_mk_dag_run_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *gates, size_t n_gates, size_t instances,
                            const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
     if (!c || (!inputs && n_inputs) || (!gates && n_gates) || (!outputs && n_gates) || (!out_wires && n_out)) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    const DagCall A{inputs, n_inputs, gates, n_gates, out_wires, n_out, outputs};
     DagPlan plan;
-    int rc = dag_plan(gates, n_inputs, n_gates, mk_dag_classify, plan);
-    if (rc) return rc;
+    THFHE_TRY(dag_plan(A, DagFamilies{}, mk_dag_classify, plan));
     if (stats) plan.fill_stats(stats);
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
     const int words = c->words + 1;
     return dag_execute(
-        plan, c->dag, c->stream, words, n_inputs, n_gates, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
+        plan, c->dag, c->stream, words, A, instances, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) {
             int r = mk_ensure_workspace(c, 2 * max_gates);
             if (!r) r = c->stage.grow(max_gates * words);
@@ -1350,8 +1353,9 @@ int thfhe_mk_dag_run_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inpu
 int thfhe_mk_dag_run_lut_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
                                const thfhe_lut_spec *specs, int n_specs, const int64_t *tv, int n_luts, size_t instances, const int32_t *out_wires,
                                size_t n_out, int32_t *outputs, int64_t *stats) {
+    const DagCall A{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs};
     DagPlan plan;
-    int rc = dag_lut_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, out_wires, n_out, outputs, mk_dag_classify, plan);
+    int rc = dag_checked_plan(A, DagFamilies{kDagGenLut, specs, n_specs, tv, n_luts}, mk_dag_classify, plan);
     if (rc) return rc;
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     if (stats) plan.fill_stats(stats);
@@ -1365,7 +1369,7 @@ int thfhe_mk_dag_run_lut_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_
     THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv, (size_t)n_luts * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     THFHE_HIP(hipMemcpyAsync(c->dag.specs.as<thfhe_lut_spec>(), specs, (size_t)n_specs * sizeof(thfhe_lut_spec), hipMemcpyHostToDevice, c->stream));
     return dag_execute(
-        plan, c->dag, c->stream, words, n_inputs, n_nodes, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
+        plan, c->dag, c->stream, words, A, instances, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) {
             int r = mk_ensure_workspace(c, 2 * max_gates);
             if (!r) r = mk_lut_workspace(c, max_gates, theta_max);

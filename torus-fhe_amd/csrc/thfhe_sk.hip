@@ -749,7 +749,7 @@ int gates_dev_locked(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1,
 // one launch of a gate-DAG gate class from the staging arrays into stage.out (thfhe_dag.h, dag_execute's run): two-input gates with per-gate
 // opcodes, or MUX
 int dag_gate_class(thfhe_ctx *c, int cls, const int32_t *d_ops, size_t n) {
-    const bool is_mux = cls == 1;
+    const bool is_mux = cls == kDagMux;
     int r = enqueue_rotations(c, is_mux ? THFHE_MUX : THFHE_NAND, c->stage.in_ptr(0), c->stage.in_ptr(1), is_mux ? c->stage.in_ptr(2) : nullptr, n, is_mux ? 2 : 1, 1 << 29,
                               is_mux ? nullptr : d_ops);
     if (!r) r = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), n, is_mux ? 2 : 1, false);
@@ -819,7 +819,7 @@ int enqueue_tree_chain(thfhe_ctx *c, thfhe_poly_ctx *pc, const Lo &lo, const int
 }
 
 // ---- gate-DAG entry points: what thfhe_dag_run_batch, thfhe_dag_run_lut_batch and thfhe_dag_run_tree_batch share ----
-int sk_dag_classify(int op) { return op == THFHE_NOT || op == THFHE_COPY ? 2 : (op == THFHE_MUX ? 1 : (op >= THFHE_NAND && op <= THFHE_ORYN ? 0 : -1)); }
+int sk_dag_classify(int op) { return op == THFHE_NOT || op == THFHE_COPY ? kDagLinear : (op == THFHE_MUX ? kDagMux : (op >= THFHE_NAND && op <= THFHE_ORYN ? kDagGate2 : -1)); }
 
 // dag_execute's ensure: workspace and staging for slices of max_gates gates; theta_max > 0: a run with LUT groups of up to theta_max records per node
 int sk_dag_ensure(thfhe_ctx *c, size_t max_gates, int theta_max, int32_t **in, int32_t **out) {
@@ -833,40 +833,18 @@ int sk_dag_ensure(thfhe_ctx *c, size_t max_gates, int theta_max, int32_t **in, i
     return r;
 }
 
-// The table families of a LUT / tree run (host pointers, checked by dag_lut_plan / dag_tree_plan; a family the run does not have is null / 0).
-struct SkDagTables {
-    const thfhe_lut_spec *specs;
-    int n_specs;
-    const int32_t *tv;
-    int n_luts;
-    const int32_t *enc_a = nullptr, *enc_b = nullptr;
-    int n_enc = 0;
-    const thfhe_tree_spec *trees = nullptr;
-    const int32_t *tv1 = nullptr;
-    int n_tv1_rows = 0;
-    // thfhe_dag_run_mv_batch: the multi-value specs, base vectors int32[n_bases][N] and the factor array
-    const thfhe_mv_spec *mvs = nullptr;
-    const int32_t *mv_tv0 = nullptr;
-    int n_bases = 0;
-    const int32_t *mv_factors = nullptr;
-    size_t n_factor_words = 0;
-    // thfhe_dag_run_lhe_batch: the leveled families
-    const thfhe_dag_lhe_families *lhe = nullptr;
-};
-
 // the leveled groups of a run (thfhe_dag_lhe.h, after the leveled kernels)
-int sk_dag_lhe_check_sets(const thfhe_ctx *c, const DagPlan &plan, const thfhe_dag_lhe_families &F, size_t instances);
-int sk_dag_lhe_reserve(thfhe_ctx *c, const DagPlan &plan, const thfhe_dag_lhe_families &F, size_t instances, size_t &w_cand);
-int sk_dag_lhe_group(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const thfhe_dag_lhe_families &F, const DagExtGroup &g, size_t instances);
+int sk_dag_lhe_check_sets(const thfhe_ctx *c, const DagPlan &plan, const DagFamilies &T, size_t instances);
+int sk_dag_lhe_reserve(thfhe_ctx *c, const DagPlan &plan, const DagFamilies &T, size_t instances, size_t &w_cand);
+int sk_dag_lhe_group(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const DagFamilies &T, const DagExtGroup &g, size_t instances);
 
-// The device side of thfhe_dag_run_lut_batch and thfhe_dag_run_tree_batch, both contexts locked by the caller (pc: null in a run without SELECT /
-// TREE groups).  Gate classes run as in thfhe_dag_run_batch.  A LUT group is one PBS stage on the wire table over the run's plaintext tables
+// The device side of the six-column entries, both contexts locked by the caller (T: the run's families, checked by dag_families_check; pc: null in a
+// run without SELECT / TREE groups).  Gate classes run as in thfhe_dag_run_batch.  A LUT group is one PBS stage on the wire table over the run's plaintext tables
 // (DESIGN 4.9), a LUT_ENC group the same over its encrypted tables.  A SELECT group gathers its candidates into the buffer the box packing reads
 // and runs the tree chain from there; a TREE group runs the whole chain with both prologues reading the wire table.  An MV group is
 // one multi-value PBS stage on the wire table, its q records per node scattered into consecutive wires; a TREE_MV group the k-table chain with both
 // prologues on the wire table.  A leveled group is sk_dag_lhe_group's.  Everything is enqueued on the gate context's stream.
-int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const SkDagTables &T, const int32_t *inputs, size_t n_inputs, size_t n_nodes,
-                    size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs) {
+int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const DagFamilies &T, const DagCall &A, size_t instances) {
     const int words = c->p.n + 1;
     hipStream_t st = c->stream;
     // a slice of a SELECT / TREE group: at most dag_slice nodes over all instances and at most tree_slice / p_hi of them
@@ -896,7 +874,7 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
         THFHE_TRY(tree_workspace(c, S, p, b.cls == kDagTree ? p / theta_lo : 1, theta_lo));
         w_cand = std::max(w_cand, S * p);
     }
-    if (T.lhe) THFHE_TRY(sk_dag_lhe_reserve(c, plan, *T.lhe, instances, w_cand));
+    if (T.lhe) THFHE_TRY(sk_dag_lhe_reserve(c, plan, T, instances, w_cand));
     if (w_cand) {
         THFHE_TRY(pack_boxes_reserve(pc, w_cand));
         THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle; from here on its buffers are used on `st`
@@ -919,7 +897,7 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
     // one SELECT / TREE / MV / TREE_MV / leveled group of a level
     auto ext_group = [&](const DagExtGroup &g) -> int {
         auto no_seam = [](int) { return (int)THFHE_OK; };
-        if (g.cls >= kDagLheLookup) return sk_dag_lhe_group(c, pc, plan, *T.lhe, g, instances);
+        if (g.cls >= kDagLheLookup) return sk_dag_lhe_group(c, pc, plan, T, g, instances);
         if (g.cls == kDagMv || g.cls == kDagTreeMv) {   // t_y = each node's table
             const thfhe_mv_spec m = T.mvs[g.tree];
             const bool is_tree = g.cls == kDagTreeMv;
@@ -967,7 +945,7 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
     };
     c->grp_valid = false;
     return dag_execute(
-        plan, c->dag, st, words, n_inputs, n_nodes, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
+        plan, c->dag, st, words, A, instances, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) { return sk_dag_ensure(c, max_gates, plan.max_theta, in, out); },
         [&](int cls, const int32_t *d_ops, size_t m) { return dag_gate_class(c, cls, d_ops, m); },
         [&](int theta, const DagLutSlice &s) {
@@ -1114,38 +1092,34 @@ int mv_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv0,
     return THFHE_OK;
 }
 
-// Encrypted-table, select and tree nodes among the gates and LUT nodes, and the multi-value nodes among those (mv null:
-// a run without their families, thfhe_dag_run_tree_batch): the host checks and the two locks here, the run in sk_dag_run_luts.  Both contexts stay
-// locked for the run.
-int sk_dag_run_ext_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
-                         const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
-                         const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const DagMvFamilies *mv, size_t instances,
-                         const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats, const thfhe_dag_lhe_families *lhe = nullptr) {
+// What the six-column entries share (T: the entry's families and the generations of node kinds it admits): the host checks and the plan, the two
+// locks, the run in sk_dag_run_luts.  Both contexts stay locked for the run.  The LUT entry has plaintext tables only, so its plans
+// hold no group that needs the packing context; from thfhe_dag_run_tree_batch on every family may be absent.
+int sk_dag_run(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagCall &A, DagFamilies T, size_t instances, int64_t *stats) {
+    const bool ext = T.gens & kDagGenTree;
     DagPlan plan;
-    int rc = dag_tree_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, out_wires, n_out,
-                           outputs, sk_dag_classify, plan, mv, lhe);
-    if (rc) return rc;
-    if (stats) plan.fill_stats(stats);   // the plan's figures need no device
+    THFHE_TRY(dag_checked_plan(A, T, sk_dag_classify, plan));
+    if (stats && ext) plan.fill_stats(stats);   // the plan's figures need no device
     const bool packs = plan.has_tree_groups();
-    if (lhe && !plan.has_lhe_groups()) lhe = nullptr;
-    if (lhe) THFHE_TRY(sk_dag_lhe_check_sets(c, plan, *lhe, instances));   // the sets, then the context
+    if (T.lhe && !plan.has_lhe_groups()) T.lhe = nullptr;
+    if (T.lhe) THFHE_TRY(sk_dag_lhe_check_sets(c, plan, T, instances));   // the sets, then the context
     if (!c || (packs && !pc)) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (stats && !ext) plan.fill_stats(stats);   // thfhe_dag_run_lut_batch gives them to a caller with a context only
     if (packs && pack_ctx_device(pc) != c->device)
         return thfhe_fail(THFHE_E_INVALID, "tree: the gate context and the packing context must be on the same device");
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
     std::unique_lock<std::mutex> pg;   // always after the gate context's: nothing else takes both
-    if (packs) pg = std::unique_lock<std::mutex>(pack_ctx_mutex(pc));
     if (packs) {
+        pg = std::unique_lock<std::mutex>(pack_ctx_mutex(pc));
         if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
         if (pack_key_n(pc) != c->p.n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
     }
-    if (instances == 0 || n_nodes == 0) return THFHE_OK;
-    if (instances > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "too many instances");
-    SkDagTables T{specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, tv1, n_tv1_rows};
-    if (mv) T.mvs = mv->mvs, T.mv_tv0 = mv->tv0, T.n_bases = mv->tv0 ? mv->n_bases : 0, T.mv_factors = mv->factors, T.n_factor_words = mv->factors ? mv->n_factor_words : 0;
-    T.lhe = lhe;
-    return sk_dag_run_luts(c, packs ? pc : nullptr, plan, T, inputs, n_inputs, n_nodes, instances, out_wires, n_out, outputs);
+    if (ext) {   // the LUT entry uploads its tables for an empty run too, and leaves the instance count to dag_execute
+        if (instances == 0 || A.n_nodes == 0) return THFHE_OK;
+        if (instances > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "too many instances");
+    }
+    return sk_dag_run_luts(c, packs ? pc : nullptr, plan, T, A, instances);
 }
 
 #include "thfhe_lhe.h"
@@ -1280,60 +1254,56 @@ int thfhe_gates_mixed(thfhe_ctx *c, const int32_t *ops, const int32_t *in0, cons
 int thfhe_dag_run_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *gates, size_t n_gates, size_t instances,
                         const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
     if (!c || (!inputs && n_inputs) || (!gates && n_gates) || (!outputs && n_gates) || (!out_wires && n_out)) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    const DagCall A{inputs, n_inputs, gates, n_gates, out_wires, n_out, outputs};
     DagPlan plan;
-    int rc = dag_plan(gates, n_inputs, n_gates, sk_dag_classify, plan);
-    if (rc) return rc;
+    THFHE_TRY(dag_plan(A, DagFamilies{}, sk_dag_classify, plan));
     if (stats) plan.fill_stats(stats);
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
     return dag_execute(
-        plan, c->dag, c->stream, c->p.n + 1, n_inputs, n_gates, instances, inputs, out_wires, n_out, outputs, c->dag_slice,
+        plan, c->dag, c->stream, c->p.n + 1, A, instances, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) { return sk_dag_ensure(c, max_gates, 0, in, out); },
         [&](int cls, const int32_t *d_ops, size_t n) { return dag_gate_class(c, cls, d_ops, n); });
 }
 
-// LUT nodes among the gates: sk_dag_run_luts with plaintext tables only -- no encrypted tables, no trees, no packing context.
+// The six-column entries: each fills the families it has and the generations of node kinds it admits; the rest is sk_dag_run.
+// LUT nodes among the gates: plaintext tables only -- no encrypted tables, no trees, no packing context.
 int thfhe_dag_run_lut_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs,
                             int n_specs, const int32_t *tv, int n_luts, size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs,
                             int64_t *stats) {
-    DagPlan plan;
-    int rc = dag_lut_plan(inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, out_wires, n_out, outputs, sk_dag_classify, plan);
-    if (rc) return rc;
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (stats) plan.fill_stats(stats);
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    return sk_dag_run_luts(c, nullptr, plan, SkDagTables{specs, n_specs, tv, n_luts}, inputs, n_inputs, n_nodes, instances, out_wires, n_out, outputs);
+    const DagFamilies T{kDagGenLut, specs, n_specs, tv, n_luts};
+    return sk_dag_run(c, nullptr, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, T, instances, stats);
 }
 
-// both entries are sk_dag_run_ext_batch, without and with the multi-value families.
+// encrypted-table, select and tree nodes among those.
 int thfhe_dag_run_tree_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
                              const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
                              const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, size_t instances, const int32_t *out_wires,
                              size_t n_out, int32_t *outputs, int64_t *stats) {
-    return sk_dag_run_ext_batch(c, pc, inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, nullptr,
-                                instances, out_wires, n_out, outputs, stats);
+    const DagFamilies T{kDagGenLut | kDagGenTree, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows};
+    return sk_dag_run(c, pc, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, T, instances, stats);
 }
 
+// the multi-value nodes and their families.
 int thfhe_dag_run_mv_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
                            const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
                            const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs,
                            const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, size_t instances, const int32_t *out_wires,
                            size_t n_out, int32_t *outputs, int64_t *stats) {
-    const DagMvFamilies mv{mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words};
-    return sk_dag_run_ext_batch(c, pc, inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, &mv,
-                                instances, out_wires, n_out, outputs, stats);
+    const DagFamilies T{kDagGenLut | kDagGenTree | kDagGenMv, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows,
+                        mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words};
+    return sk_dag_run(c, pc, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, T, instances, stats);
 }
 
-// the same with the leveled families; without them (lhe NULL) it is thfhe_dag_run_mv_batch.
+// the leveled nodes, when their families are given; without them (lhe NULL) the call is thfhe_dag_run_mv_batch.
 int thfhe_dag_run_lhe_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
                             const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
                             const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs,
                             const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, const thfhe_dag_lhe_families *lhe,
                             size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
-    const DagMvFamilies mv{mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words};
-    return sk_dag_run_ext_batch(c, pc, inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, &mv,
-                                instances, out_wires, n_out, outputs, stats, lhe);
+    const DagFamilies T{kDagGenLut | kDagGenTree | kDagGenMv | (lhe ? kDagGenLhe : 0u), specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows,
+                        mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words, lhe};
+    return sk_dag_run(c, pc, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, T, instances, stats);
 }
 
 int thfhe_set_dag_slice(thfhe_ctx *c, size_t max_gates) { return ctx_set_dag_slice(c, max_gates); }

@@ -176,6 +176,16 @@ def _lut_spec(s):
     return LutSpec(int(s[0]), (C.c_int32 * 3)(*[_wrap32(w) for w in (list(s[1]) + [0, 0, 0])[:3]]), _wrap32(s[2]), int(s[3]))
 
 
+
+_NO_SPEC = (1, (0, 0, 0), 0, 1)   # stands for the half of a TreeSpec / MvSpec that its rows do not use
+
+
+def _mv_specs(mvs):
+    """MvSpec array from MvSpec or (lo, hi, p, q, k, base, factors_off, n_tables) tuples (hi may be None: MV only); None without any."""
+    if not len(mvs):
+        return None
+    return (MvSpec * len(mvs))(*[m if isinstance(m, MvSpec) else MvSpec(_lut_spec(m[0]), _lut_spec(m[1] or _NO_SPEC), *[int(v) for v in m[2:]]) for m in mvs])
+
 _lib = None
 
 _i32p = C.POINTER(C.c_int32)
@@ -455,42 +465,37 @@ class _EvalKey(_Handle):
         _check(self._fn("dag_run")(self.h, _p32(wires), x.shape[0], _p32(g), g.shape[0], st.ctypes.data_as(_i64p)))
         return wires, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]), widest_level=int(st[3]))
 
-    def dag_run_batch(self, input_records, gates, out_wires=None):
-        """`instances` evaluations of one gate list side by side (the reference's loop over test records,
-        src/KNN_medical_data.cpp:676-691).  input_records: int32[instances][n_inputs][words]; out_wires: wire ids to return (None = every
-        gate wire).  Returns (int32[instances][len(out_wires) or n_gates][words], stats)."""
+    def _dag_run(self, what, fn, ctxs, input_records, nodes, cols, families, out_wires):
+        """The marshalling every dag_run_*_batch shares: fn(*ctxs, inputs, the node rows of `cols` words, *families(), instances, out_wires, outputs, stats).
+        families: called after the input records and the rows are checked.  Returns (outputs, the stats dictionary)."""
         words = self.words
         x = np.ascontiguousarray(input_records, np.int32)
         if x.ndim != 3 or x.shape[2] != words:
-            raise ValueError("dag_run_batch: input records must be int32[instances][n_inputs][%d]" % words)
-        g = np.ascontiguousarray(gates, np.int32).reshape(-1, 4)
+            raise ValueError("%s: input records must be int32[instances][n_inputs][%d]" % (what, words))
+        g = np.ascontiguousarray(nodes, np.int32).reshape(-1, cols)
+        fam = families()
         q, n_in = x.shape[0], x.shape[1]
         sel = None if out_wires is None else np.ascontiguousarray(out_wires, np.int32).reshape(-1)
         out = np.zeros((q, g.shape[0] if sel is None else sel.shape[0], words), np.int32)
         st = np.zeros(4, np.int64)
-        _check(self._fn("dag_run_batch")(self.h, _p32(x), n_in, _p32(g), g.shape[0], q, _p32(sel), 0 if sel is None else sel.shape[0], _p32(out),
-                                         st.ctypes.data_as(_i64p)))
+        _check(fn(*ctxs, _p32(x), n_in, _p32(g), g.shape[0], *fam, q, _p32(sel), 0 if sel is None else sel.shape[0], _p32(out), st.ctypes.data_as(_i64p)))
         return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
+
+    def dag_run_batch(self, input_records, gates, out_wires=None):
+        """`instances` evaluations of one gate list side by side (the reference's loop over test records,
+        src/KNN_medical_data.cpp:676-691).  input_records: int32[instances][n_inputs][words]; out_wires: wire ids to return (None = every
+        gate wire).  Returns (int32[instances][len(out_wires) or n_gates][words], stats)."""
+        return self._dag_run("dag_run_batch", self._fn("dag_run_batch"), (self.h,), input_records, gates, 4, tuple, out_wires)
 
     def dag_run_lut_batch(self, input_records, nodes, specs, tv, out_wires=None):
         """dag_run_batch with LUT nodes (thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch).  nodes: int32[n_nodes][6] =
         (op, in0, in1, in2, spec, lut); specs: (n_inputs, (w0, w1, w2), bias, theta) tuples or LutSpec; tv: [n_luts][N] test vectors of the
         ring's torus (int32 for CloudKey, int64 for MKCloudKey).  Returns (int32[instances][len(out_wires) or n_nodes][words], stats)."""
-        words = self.words
-        x = np.ascontiguousarray(input_records, np.int32)
-        if x.ndim != 3 or x.shape[2] != words:
-            raise ValueError("dag_run_lut_batch: input records must be int32[instances][n_inputs][%d]" % words)
-        g = np.ascontiguousarray(nodes, np.int32).reshape(-1, 6)
-        sp = (LutSpec * len(specs))(*[_lut_spec(s) for s in specs])
-        tv = np.ascontiguousarray(tv, self._tv_dtype).reshape(-1, self.params.N)
-        q, n_in = x.shape[0], x.shape[1]
-        sel = None if out_wires is None else np.ascontiguousarray(out_wires, np.int32).reshape(-1)
-        out = np.zeros((q, g.shape[0] if sel is None else sel.shape[0], words), np.int32)
-        st = np.zeros(4, np.int64)
-        ptv = tv.ctypes.data_as(_i64p if self._tv_dtype == np.int64 else _i32p)
-        _check(self._fn("dag_run_lut_batch")(self.h, _p32(x), n_in, _p32(g), g.shape[0], sp, len(specs), ptv, tv.shape[0], q, _p32(sel),
-                                             0 if sel is None else sel.shape[0], _p32(out), st.ctypes.data_as(_i64p)))
-        return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
+        def families():
+            sp = (LutSpec * len(specs))(*[_lut_spec(s) for s in specs])
+            t = np.ascontiguousarray(tv, self._tv_dtype).reshape(-1, self.params.N)
+            return sp, len(specs), t.ctypes.data_as(_i64p if self._tv_dtype == np.int64 else _i32p), t.shape[0]
+        return self._dag_run("dag_run_lut_batch", self._fn("dag_run_lut_batch"), (self.h,), input_records, nodes, 6, families, out_wires)
 
     def _bootstrap(self, x, mu):
         x = _rec(x, self.words)
@@ -745,8 +750,7 @@ class CloudKey(_EvalKey):
                          out_wires=None, pack=None):
         """dag_run_tree_batch with multi-value nodes (thfhe_dag_run_mv_batch).  mvs: MvSpec or (lo, hi, p, q, k, base, factors_off, n_tables)
         tuples (hi may be None: MV only); mv_tv0: int32[n_bases][N] base vectors; mv_factors: int32[words], the taps of every spec."""
-        none = (1, (0, 0, 0), 0, 1)
-        mv = (MvSpec * len(mvs))(*[m if isinstance(m, MvSpec) else MvSpec(_lut_spec(m[0]), _lut_spec(m[1] or none), *[int(v) for v in m[2:]]) for m in mvs]) if len(mvs) else None
+        mv = _mv_specs(mvs)
         tv0 = None if mv_tv0 is None else np.ascontiguousarray(mv_tv0, np.int32).reshape(-1, self.params.N)
         fac = None if mv_factors is None else np.ascontiguousarray(mv_factors, np.int32).reshape(-1)
         families = (mv, len(mvs), _p32(tv0), 0 if tv0 is None else tv0.shape[0], _p32(fac), 0 if fac is None else fac.shape[0])
@@ -760,8 +764,7 @@ class CloudKey(_EvalKey):
         int32[words], their pool; fin_b / fin_a: int32[rows][N] final weights; pack: needed when an LHE_GATHER node is present.  Without any leveled
         family the call is dag_run_mv_batch."""
         N = self.params.N
-        none = (1, (0, 0, 0), 0, 1)
-        mv = (MvSpec * len(mvs))(*[m if isinstance(m, MvSpec) else MvSpec(_lut_spec(m[0]), _lut_spec(m[1] or none), *[int(v) for v in m[2:]]) for m in mvs]) if len(mvs) else None
+        mv = _mv_specs(mvs)
         tv0 = None if mv_tv0 is None else np.ascontiguousarray(mv_tv0, np.int32).reshape(-1, N)
         fac = None if mv_factors is None else np.ascontiguousarray(mv_factors, np.int32).reshape(-1)
         tab = lambda a: None if a is None else np.ascontiguousarray(a, np.int32).reshape(-1, N)
@@ -795,28 +798,16 @@ class CloudKey(_EvalKey):
     def _dag_run_ext(self, fn, families, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack):
         """What dag_run_tree_batch and dag_run_mv_batch share: fn(contexts, inputs, nodes, the earlier table families, `families` -- the multi-value
         arguments of thfhe_dag_run_mv_batch, none for thfhe_dag_run_tree_batch --, instances, outputs, stats)."""
-        words, N = self.words, self.params.N
-        x = np.ascontiguousarray(input_records, np.int32)
-        if x.ndim != 3 or x.shape[2] != words:
-            raise ValueError("dag_run_tree_batch / dag_run_mv_batch: input records must be int32[instances][n_inputs][%d]" % words)
-        g = np.ascontiguousarray(nodes, np.int32).reshape(-1, 6)
-        sp = (LutSpec * len(specs))(*[_lut_spec(s) for s in specs]) if len(specs) else None
-        none = (1, (0, 0, 0), 0, 1)
-        tr = (TreeSpec * len(trees))(*[t if isinstance(t, TreeSpec) else TreeSpec(_lut_spec(t[0] or none), _lut_spec(t[1]), int(t[2])) for t in trees]) if len(trees) else None
-        tab = lambda a: None if a is None else np.ascontiguousarray(a, np.int32).reshape(-1, N)
-        tv, enc_a, enc_b, tv1 = tab(tv), tab(enc_a), tab(enc_b), tab(tv1)
-        if (enc_a is None) != (enc_b is None) or (enc_a is not None and enc_a.shape != enc_b.shape):
-            raise ValueError("enc_a and enc_b must both be given, with the same shape")
-        rows = lambda a: 0 if a is None else a.shape[0]
-        q, n_in = x.shape[0], x.shape[1]
-        sel = None if out_wires is None else np.ascontiguousarray(out_wires, np.int32).reshape(-1)
-        out = np.zeros((q, g.shape[0] if sel is None else sel.shape[0], words), np.int32)
-        st = np.zeros(4, np.int64)
-        head = (self.h, None if pack is None else pack.h, _p32(x), n_in, _p32(g), g.shape[0], sp, len(specs), _p32(tv), rows(tv), _p32(enc_a), _p32(enc_b),
-                rows(enc_a), tr, len(trees), _p32(tv1), rows(tv1))
-        tail = (q, _p32(sel), 0 if sel is None else sel.shape[0], _p32(out), st.ctypes.data_as(_i64p))
-        _check(fn(*head, *families, *tail))
-        return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
+        def earlier():
+            sp = (LutSpec * len(specs))(*[_lut_spec(s) for s in specs]) if len(specs) else None
+            tr = (TreeSpec * len(trees))(*[t if isinstance(t, TreeSpec) else TreeSpec(_lut_spec(t[0] or _NO_SPEC), _lut_spec(t[1]), int(t[2])) for t in trees]) if len(trees) else None
+            tab = lambda a: None if a is None else np.ascontiguousarray(a, np.int32).reshape(-1, self.params.N)
+            t, ea, eb, t1 = tab(tv), tab(enc_a), tab(enc_b), tab(tv1)
+            if (ea is None) != (eb is None) or (ea is not None and ea.shape != eb.shape):
+                raise ValueError("enc_a and enc_b must both be given, with the same shape")
+            rows = lambda a: 0 if a is None else a.shape[0]
+            return (sp, len(specs), _p32(t), rows(t), _p32(ea), _p32(eb), rows(ea), tr, len(trees), _p32(t1), rows(t1)) + tuple(families)
+        return self._dag_run("dag_run_tree_batch / dag_run_mv_batch", fn, (self.h, None if pack is None else pack.h), input_records, nodes, 6, earlier, out_wires)
 
     # -- leveled table lookup on TGSW-encrypted address bits (thfhe_tgsw_set_create, thfhe_lhe_cmux, thfhe_lhe_lookup; DESIGN 4.15) ----------
     def tgsw_set(self, samples, d):
