@@ -572,7 +572,8 @@ int thfhe_dag_run_tree_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const int
  *   base or factors_off + n_tables k q p out of range; a spec the flat entries would refuse (theta != 1, p, q, k, k q > 64, n_tables; an MV row on
  *   a spec with k != 1); a wrong number of LUT_OUT rows after a head; operand counts that do not match the specs or exceed three; a family that is
  *   NULL while a row refers to it.  The context checks of thfhe_tree_lut_bootstrap apply when the plan holds a SELECT, TREE or TREE_MV node; ctx_pack
- *   may be NULL otherwise.  Every other thfhe_dag_* and thfhe_mk_dag_* entry rejects the two opcodes. */
+ *   may be NULL otherwise.  Every other thfhe_dag_* and thfhe_mk_dag_* entry rejects the two opcodes, but thfhe_mk_dag_run_mv_batch (below), which
+ *   takes THFHE_MV rows. */
 typedef struct thfhe_mv_spec {
     thfhe_lut_spec lo;      /* the multi-value rotation's inputs, theta 1 */
     thfhe_lut_spec hi;      /* TREE_MV: selection inputs, theta 1; ignored by MV */
@@ -589,6 +590,48 @@ int thfhe_dag_run_mv_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const int32
                            const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs,
                            const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, size_t instances,
                            const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats);
+
+/* ---- multi-value bootstrapping on the 3-gen multi-key engine: the contract of thfhe_mv_lut_bootstrap restated on Torus64, every
+ * parameter family (N = the context's ring degree: 1024, 2048 or 4096).  q <= 64 functions of one encrypted digit from ONE blind rotation.
+ *
+ * thfhe_mk_mv_lut_bootstrap(_wo_keyswitch): spec must have theta 1; prologue, mod-switch, the accumulator start (0, X^{-barb} * tv0), the party-major
+ *   CMux chain and the skip of mask words with bara == 0 are those of thfhe_mk_lut_bootstrap at theta = 1.  tv0: HOST int64[N], any words.
+ *   factors: HOST int32[n_tables][q][p], p a power of two, 2 <= p <= 64, 1 <= q <= 64, 1 <= n_tables <= 1024; table_index: HOST int32[count] or NULL
+ *   (table 0).  With box = N/p, J_k = N - box/2 - k box and E(ACC, J) the UNCONVERTED extraction over int64 (e_i = a_{J-i} for i <= J,
+ *   -a_{N+J-i} for i > J, e_N = body_J; negations mod 2^64), record (s, j) is t64tot32, word by word, of
+ *       - sum_k factors[t][j][k] * E(ACC_s, J_k)   (+ out_bias on the body word),   t = table_index[s],
+ *   all sums mod 2^64, taps sign-extended.  The combination happens in Torus64 BEFORE the one conversion of each word: t64tot32 truncates toward
+ *   zero and is not linear, so converting the p extractions first gives other words.  With tv0 = (u, ..., u), step = 2u, and the factors of
+ *   thfhe.lut.mv_factors, output j carries f_j(m) * step (+ out_bias) on Torus64; the rotation's noise reaches it times the 2-norm of its taps.
+ *   out_bias: one Torus64 word for every output; 0/1 tables at step 2^62 with out_bias = -2^61 leave the rotation in the 3-gen gates' encoding
+ *   +-2^61 (thfhe.lut.mv_bool_factors) with half the taps -- and half the rotation noise -- of +-1 tables at step 2^61.
+ *   out: HOST int32[count][q][P*n+1] after the multi-key key switch of the count q records, or int32[count][q][N+1] (_wo_keyswitch).
+ *   THFHE_E_INVALID on the host, before the context is looked at: the checks of thfhe_mk_lut_bootstrap (tv0 and n_tables in the places of tv and
+ *   n_luts), a null factors, theta != 1, a bad p, q or n_tables, a table_index entry out of range.  count 0 returns THFHE_OK.  The batch runs in
+ *   slices of at most max_records (thfhe_mk_set_mv_slice, default 4 096, 1 .. 2^20) output records and at least one sample: (N + 1) x 4 B of
+ *   workspace per record; only a slice's inputs go up and only its records come down.  thfhe_mk_last_timings: the last slice, prologue | accumulator
+ *   start | rotation + multi-value epilogue | key switch on the boundaries of thfhe_mk_lut_bootstrap.
+ *
+ * thfhe_mk_dag_run_mv_batch: thfhe_mk_dag_run_lut_batch with one more node kind.  New rows: (THFHE_MV, in0, in1, in2, mv, t) followed by q - 1
+ *   THFHE_LUT_OUT rows (q = mvs[mv].q), the rows of thfhe_dag_run_mv_batch with the same meaning: wire head + j is the record
+ *   thfhe_mk_mv_lut_bootstrap(mvs[mv].lo, mv_tv0[base], table t of the spec, p, q, out_bias = mv_out_bias[mv], operands) returns at [0][j], word for
+ *   word.  mvs[mv].k must be 1, .hi is ignored.  mv_tv0: HOST int64[n_bases][N]; mv_factors as in thfhe_dag_run_mv_batch; mv_out_bias: HOST
+ *   int64[n_mvs] or NULL (0 for every spec).  specs / tv may be NULL, 0 when no LUT row needs them; with mvs, mv_tv0 and mv_factors all absent the
+ *   call is thfhe_mk_dag_run_lut_batch.  THFHE_TREE_MV, THFHE_SELECT, THFHE_TREE and the encrypted-table rows are refused as undefined opcodes: there
+ *   is no multi-key packing key switch.  One launch group per distinct mvs[] index and level; slices of at most thfhe_mk_set_dag_slice nodes over all
+ *   instances and at most max_records / q of them.  stats: an MV node counts one rotation and its group one launch.  Checks as
+ *   thfhe_dag_run_mv_batch's for these rows, on the host before the context is looked at. */
+int thfhe_mk_mv_lut_bootstrap(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec, const int64_t *tv0, const int32_t *factors /*[n_tables][q][p]*/, int p,
+                              int q, int n_tables, const int32_t *table_index, int64_t out_bias, const int32_t *in0, const int32_t *in1,
+                              const int32_t *in2, int32_t *out, size_t count);
+int thfhe_mk_mv_lut_bootstrap_wo_keyswitch(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec, const int64_t *tv0, const int32_t *factors /*[n_tables][q][p]*/,
+                                           int p, int q, int n_tables, const int32_t *table_index, int64_t out_bias, const int32_t *in0,
+                                           const int32_t *in1, const int32_t *in2, int32_t *out_N1, size_t count);
+int thfhe_mk_set_mv_slice(thfhe_mk_ctx *ctx, size_t max_records);
+int thfhe_mk_dag_run_mv_batch(thfhe_mk_ctx *ctx, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                              const thfhe_lut_spec *specs, int n_specs, const int64_t *tv, int n_luts, const thfhe_mv_spec *mvs, int n_mvs,
+                              const int64_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, const int64_t *mv_out_bias,
+                              size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats);
 
 /* ---- leveled nodes in the gate-DAG executor (single key): thfhe_dag_run_mv_batch with three more node kinds that read the client's
  * TGSW-encrypted bits, so that a leveled lookup, a leveled pick among COMPUTED wires and a layered automaton run between gates on the device-resident

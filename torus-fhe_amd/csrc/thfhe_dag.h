@@ -7,7 +7,8 @@
 //   kDagGenLut   LUT nodes (thfhe_dag_run_lut_batch, thfhe_mk_dag_run_lut_batch): programmable bootstraps among the gates, fed by the shared
 //                prologue reading their operands from the wire table (LutWireSrc, thfhe_lut_prologue.h), their theta outputs scattered into consecutive wires
 //   kDagGenTree  encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch; single key)
-//   kDagGenMv    multi-value nodes (thfhe_dag_run_mv_batch; single key): MV and TREE_MV rows
+//   kDagGenMv    multi-value nodes (thfhe_dag_run_mv_batch; thfhe_mk_dag_run_mv_batch): MV rows, and TREE_MV rows where the
+//                entry has the tree generation too (single key)
 //   kDagGenLhe   leveled nodes (thfhe_dag_run_lhe_batch; single key): LHE_LOOKUP, LHE_GATHER and LHE_WFA rows on the client's TGSW sets;
 //                dag_lhe_gather_kernel stages a GATHER node's candidates for the box packing
 // The kinds from kDagGenTree on are planned here and run by the engine (thfhe_sk.hip: sk_dag_run_luts).
@@ -151,7 +152,7 @@ struct DagCall {
 enum DagGen : unsigned {
     kDagGenLut = 1,    // six-column rows; THFHE_LUT and THFHE_LUT_OUT (thfhe_dag_run_lut_batch, thfhe_mk_dag_run_lut_batch)
     kDagGenTree = 2,   // THFHE_LUT_ENC, THFHE_SELECT, THFHE_TREE; every family may be absent (thfhe_dag_run_tree_batch)
-    kDagGenMv = 4,     // THFHE_MV, THFHE_TREE_MV (thfhe_dag_run_mv_batch)
+    kDagGenMv = 4,     // THFHE_MV; with kDagGenTree also THFHE_TREE_MV (thfhe_dag_run_mv_batch; thfhe_mk_dag_run_mv_batch has no tree generation)
     kDagGenLhe = 8,    // THFHE_LHE_LOOKUP, THFHE_LHE_GATHER, THFHE_LHE_WFA (thfhe_dag_run_lhe_batch with its families)
 };
 // Everything a run can bring besides its DagCall: the table families (host pointers) with their counts.  An entry fills the families it has and the
@@ -170,7 +171,7 @@ struct DagFamilies {
     int n_tv1_rows = 0;
     const thfhe_mv_spec *mvs = nullptr;
     int n_mvs = 0;
-    const int32_t *mv_tv0 = nullptr;                    // [n_bases][N] base vectors
+    const void *mv_tv0 = nullptr;                       // [n_bases][N] base vectors of the ring's torus, as tv
     int n_bases = 0;
     const int32_t *mv_factors = nullptr;                // the taps of every mvs[] entry
     size_t n_factor_words = 0;
@@ -265,10 +266,10 @@ inline int dag_family_rules(std::initializer_list<DagFamilyRule> rules, const ch
 // The host checks of a six-column entry that need no row, before any device work and before a context is looked at: the call's pointers; per
 // generation of families a count without its pointer, then the counts (a family without a pointer has count 0 from here on); every spec (the rules
 // of lut_validate) and every tree spec's `hi` half and p_hi (the rules of thfhe_tree_lut_bootstrap; the `lo` half, and an mvs[] / lks[] / wfas[]
-// entry, when a row uses it); the output wire ids.  The LUT entries (no kDagGenTree) require specs and tv; from thfhe_dag_run_tree_batch on every
-// family may be absent.
+// entry, when a row uses it); the output wire ids.  The LUT entries (kDagGenLut alone) require specs and tv; from thfhe_dag_run_tree_batch and
+// thfhe_mk_dag_run_mv_batch on every family may be absent.
 inline int dag_families_check(const DagCall &A, const DagFamilies &F) {
-    const bool strict = !(F.gens & kDagGenTree);
+    const bool strict = !(F.gens & (kDagGenTree | kDagGenMv));
     if ((!A.inputs && A.n_inputs) || (!A.nodes && A.n_nodes) || (!A.outputs && A.n_nodes) || (!A.out_wires && A.n_out) || (strict && (!F.specs || !F.tv)))
         return thfhe_fail(THFHE_E_INVALID, "null argument");
     const char *const null_msg = "null argument: a table family with a count but no pointer";
@@ -439,7 +440,7 @@ struct DagRowChecks {
         if ((F.gens & kDagGenLut) && op == THFHE_LUT) return lut(row, false, r);
         if ((F.gens & kDagGenTree) && op == THFHE_LUT_ENC) return lut(row, true, r);
         if ((F.gens & kDagGenTree) && (op == THFHE_SELECT || op == THFHE_TREE)) return tree(row, w, op == THFHE_TREE, r);
-        if ((F.gens & kDagGenMv) && (op == THFHE_MV || op == THFHE_TREE_MV)) return mv(row, op == THFHE_TREE_MV, r);
+        if ((F.gens & kDagGenMv) && (op == THFHE_MV || (op == THFHE_TREE_MV && (F.gens & kDagGenTree)))) return mv(row, op == THFHE_TREE_MV, r);
         if ((F.gens & kDagGenLhe) && (op == THFHE_LHE_LOOKUP || op == THFHE_LHE_GATHER)) return lookup(row, w, op == THFHE_LHE_GATHER, r);
         if ((F.gens & kDagGenLhe) && op == THFHE_LHE_WFA) return wfa(row, r);
         return gate(row, classify, r);

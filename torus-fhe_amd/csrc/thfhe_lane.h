@@ -1170,6 +1170,35 @@ THFHE_FN void extract_64_n(int lane, const int64_t *acc_mask, const int64_t *acc
     }
     if (lane == 0) out[NN] = t64tot32(acc_body[0]);
 }
+// multi-value bootstrap on the 3-gen accumulator: ONE output of mk_extract_mv_kernel (thfhe_mk.hip), extract_mv16 over Torus64 for a
+// 256-thread workgroup.  With box = NN / p and J_k = NN - box/2 - k box the record is, word by word,
+//     t64tot32( - sum_k c[k] * E(ACC, J_k)  [+ out_bias on the body word] ),
+// E the UNCONVERTED extraction in int64 (e_i = a_{J-i} for i <= J, -a_{NN+J-i} above, e_NN = body_J): the sum wraps mod 2^64 and is converted
+// once -- t64tot32 truncates toward zero and is not linear, so converting the p extractions first gives other words.  Thread `tid` owns words
+// tid + 256 m.  acc_mask: the mask polynomial (in LDS); body_taps[k] = body_{J_k}; c: the p taps, sign-extended int32 (WPtr: a uniform_i32_ptr in
+// the kernel, a plain pointer in host code).  An instruction reads ONE tap for all lanes -- lane i of a wave takes word (J_k - i) mod NN, 64
+// consecutive 8-byte words, conflict-free -- and the extraction sign and the leading minus are a select between c and -c, as in extract_mv16.
+template <int NN, typename WPtr>
+THFHE_FN void extract_mv64(int tid, const int64_t *acc_mask, const int64_t *body_taps, WPtr c, int p, int64_t out_bias, int32_t *out) {
+    constexpr int M = NN / 256;
+    const int box = NN / p;
+    uint64_t s[M], sb = (uint64_t)out_bias;
+#pragma unroll
+    for (int m = 0; m < M; m++) s[m] = 0;
+    int J = NN - (box >> 1);
+    for (int k = 0; k < p; k++, J -= box) {
+        const uint64_t ck = (uint64_t)(int64_t)c[k], nck = 0ull - ck;
+#pragma unroll
+        for (int m = 0; m < M; m++) {
+            const int d = J - (tid + 256 * m);
+            s[m] += (uint64_t)acc_mask[d & (NN - 1)] * (d >= 0 ? nck : ck);
+        }
+        sb += (uint64_t)body_taps[k] * nck;
+    }
+#pragma unroll
+    for (int m = 0; m < M; m++) out[tid + 256 * m] = t64tot32((int64_t)s[m]);
+    if (tid == 0) out[NN] = t64tot32((int64_t)sb);
+}
 // spectral key stream for N = 2048: [party*n + i][row r][limb h][output o][half][slot m][lane], 16 KiB per (pi, r, h, o)
 THFHE_FN size_t mk_chunk_index_2k(long pi, int r, int h, int o, int rows) { return mk_chunk_index(pi, r, h, o, rows) * 2; }  // * 512 complex
 

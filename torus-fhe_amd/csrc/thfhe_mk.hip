@@ -19,6 +19,9 @@
 //                             (thfhe_mk_lut_bootstrap): weighted sum + mod-switch to multiples of theta, accumulator X^{-barb} * tv in
 //                             global memory, the rotation kernels above through acc_in / acc_out, extraction of theta coefficients; with the
 //                             prologue reading the wire table they run the LUT nodes of the gate DAG (thfhe_mk_dag_run_lut_batch)
+//   mk_extract_mv_kernel      multi-value bootstrap (thfhe_mk_mv_lut_bootstrap): q outputs of ONE rotation, each the integer combination of p
+//                             extractions of the Torus64 accumulator staged in LDS (extract_mv64, thfhe_lane.h), converted once; with the prologue on the
+//                             wire table the MV nodes of the gate DAG (thfhe_mk_dag_run_mv_batch)
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -897,6 +900,30 @@ __global__ __launch_bounds__(256) void mk_extract_at_kernel(const int64_t *__res
     }
 }
 
+// multi-value epilogue (thfhe_mk_mv_lut_bootstrap): the q outputs of job blockIdx.x from its accumulator in global memory, record
+// (job q + j) of NN + 1 words = extract_mv64 with the taps w[table][j][0 .. p), table = tab_idx[job] (null: table 0).  The mask polynomial is staged
+// once in LDS (8 / 16 / 32 KiB) with the p body words the taps meet; the q outputs then read LDS only.  Taps and table index are wave-uniform loads.
+struct MkMvArgs {
+    const int32_t *w;   // [n_tables][q][p] taps
+    int p, q;
+    int64_t out_bias;   // added to the body word of every output before its conversion
+};
+template <int NN>
+__global__ __launch_bounds__(256) void mk_extract_mv_kernel(const int64_t *__restrict__ acc, MkMvArgs mv, const int32_t *__restrict__ tab_idx, long jobs,
+                                                            int32_t *__restrict__ out) {
+    __shared__ int64_t sMask[NN];
+    __shared__ int64_t sBody[64];
+    const long job = blockIdx.x;
+    if (job >= jobs) return;
+    const int64_t *ap = acc + job * 2 * NN;
+    for (int q = threadIdx.x; q < NN; q += 256) sMask[q] = ap[q];
+    const int box = NN / mv.p;
+    if ((int)threadIdx.x < mv.p) sBody[threadIdx.x] = ap[NN + NN - (box >> 1) - (int)threadIdx.x * box];
+    __syncthreads();
+    const uniform_i32_ptr w = as_uniform(mv.w) + (size_t)(tab_idx ? as_uniform(tab_idx)[job] : 0) * mv.q * mv.p;
+    for (int j = 0; j < mv.q; j++) extract_mv64<NN>((int)threadIdx.x, sMask, sBody, w + j * mv.p, mv.p, mv.out_bias, out + (job * mv.q + j) * (NN + 1));
+}
+
 __global__ __launch_bounds__(256) void mk_linear_kernel(const int32_t *__restrict__ x, const int32_t *__restrict__ y, int32_t *__restrict__ out,
                                                          size_t words, size_t rec, int mode) {
     // mode 0: copy, 1: negate, 2: (0, 1/8) + x + y   (the 3-gen MUX epilogue, J/3gen_mk_gates.jl:144-147)
@@ -937,6 +964,10 @@ struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     Stage stage;
     DagBuffers dag;   // gate-DAG executor tables (thfhe_dag.h)
     size_t dag_slice = 8192;  // gates per launch of a DAG level
+    // multi-value bootstrap (thfhe_mk_mv_lut_bootstrap): the factor tables of a flat call (d_tv holds its base vector); the base vectors
+    // and the factor array of a gate-DAG run (thfhe_mk_dag_run_mv_batch)
+    DevBuf d_mv_w, d_dag_mv_tv0, d_dag_mv_w;
+    size_t mv_slice = 4096;   // output records (samples x q) per slice of a multi-value call: (N + 1) x 4 B of d_u each
 };
 
 namespace {
@@ -993,11 +1024,14 @@ int mk_lut_workspace(thfhe_mk_ctx *c, size_t count, int theta) {
 // the rotation side of a programmable bootstrap of `count` samples whose bara / barb are in the workspace: accumulator start from the
 // sample's table, the rotation of mk_bootstrap_3gen, extraction of theta coefficients into d_u [count][theta][N+1]; then, if d_dst is given,
 // the key switch of the count x theta records into d_dst.  Shared by mk_enqueue_lut and the gate-DAG LUT nodes (thfhe_mk_dag_run_lut_batch).
-int mk_enqueue_lut_rotation(thfhe_mk_ctx *c, int theta, size_t count, const int64_t *d_tv, const int32_t *d_idx, int32_t *d_dst) {
+// mv: every sample rotates the ONE base vector d_tv (theta is 1), d_idx picks its factor table, and the extraction is
+// mk_extract_mv_kernel's mv->q records per sample, d_u [count][q][N+1].
+int mk_enqueue_lut_rotation(thfhe_mk_ctx *c, int theta, size_t count, const int64_t *d_tv, const int32_t *d_idx, int32_t *d_dst, const MkMvArgs *mv = nullptr) {
     const int N = c->p.N;
-    const size_t recs = count * theta;
+    const size_t recs = count * (mv ? mv->q : theta);
     int64_t *acc = c->d_acc.as<int64_t>();
-    hipLaunchKernelGGL(mk_lut_acc_init_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, c->d_barb.as<int32_t>(), d_tv, d_idx, (long)count, N, acc);
+    hipLaunchKernelGGL(mk_lut_acc_init_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, c->d_barb.as<int32_t>(), d_tv, mv ? nullptr : d_idx, (long)count, N,
+                       acc);
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
     // acc_in == acc_out == d_acc: every rotation shape may run in place.  The N = 1024 / 2048 coop and pair kernels copy their job's
     // accumulator(s) into LDS before the first barrier and write them back only after the last CMux, and no workgroup touches another job's
@@ -1007,8 +1041,17 @@ int mk_enqueue_lut_rotation(thfhe_mk_ctx *c, int theta, size_t count, const int6
                c->w_pad, c->p.Bgbit, 0, acc, acc};
     int rc = mk_launch_rotation(c, a);
     if (rc) return rc;
-    hipLaunchKernelGGL(mk_extract_at_kernel, dim3((unsigned)count, (unsigned)theta), dim3(256), 0, c->stream, (const int64_t *)acc, c->d_u.as<int32_t>(),
-                       (long)count, N, theta);
+    if (mv) {
+        const dim3 grid((unsigned)count), block(256);
+        switch (N) {
+        case 1024: hipLaunchKernelGGL(mk_extract_mv_kernel<1024>, grid, block, 0, c->stream, (const int64_t *)acc, *mv, d_idx, (long)count, c->d_u.as<int32_t>()); break;
+        case 2048: hipLaunchKernelGGL(mk_extract_mv_kernel<2048>, grid, block, 0, c->stream, (const int64_t *)acc, *mv, d_idx, (long)count, c->d_u.as<int32_t>()); break;
+        default: hipLaunchKernelGGL(mk_extract_mv_kernel<4096>, grid, block, 0, c->stream, (const int64_t *)acc, *mv, d_idx, (long)count, c->d_u.as<int32_t>()); break;
+        }
+    } else {
+        hipLaunchKernelGGL(mk_extract_at_kernel, dim3((unsigned)count, (unsigned)theta), dim3(256), 0, c->stream, (const int64_t *)acc, c->d_u.as<int32_t>(),
+                           (long)count, N, theta);
+    }
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
     if (d_dst) THFHE_TRY(mk_keyswitch(c, c->d_u.as<int32_t>(), d_dst, recs));
     if (c->profiling) {
@@ -1218,6 +1261,122 @@ int mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *t
     }, keyswitch ? c->stage.out : c->d_u, out, out_bytes);
 }
 
+// thfhe_mk_mv_lut_bootstrap (keyswitch) / thfhe_mk_mv_lut_bootstrap_wo_keyswitch: out = count x q records of P n + 1 (resp. N + 1) words,
+// in slices of at most mv_slice records (at least one sample): only a slice's inputs go up and only its records come down.
+int mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *tv0, const int32_t *factors, int p, int q, int n_tables,
+                        const int32_t *table_index, int64_t out_bias, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count,
+                        bool keyswitch) {
+    if (!factors) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    THFHE_TRY(lut_validate(sp, tv0, n_tables, table_index, in0, in1, in2, out, count));
+    THFHE_TRY(mv_validate(*sp, p, q, n_tables));
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (count == 0) return THFHE_OK;
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const thfhe_lut_spec s = *sp;
+    const size_t words = (size_t)c->words + 1, N = c->p.N, rec = keyswitch ? words : N + 1;
+    const size_t S_max = std::min(count, std::max<size_t>(1, c->mv_slice / q));
+    const size_t w_bytes = (size_t)n_tables * q * p * sizeof(int32_t);
+    int rc = mk_lut_workspace(c, S_max, q);
+    if (!rc) rc = c->stage.grow(keyswitch ? S_max * q * words : S_max * words);   // the key switch writes S x q records into stage.out
+    if (!rc) rc = c->d_tv.grow(N * sizeof(int64_t));
+    if (!rc) rc = c->d_mv_w.grow(w_bytes);
+    if (!rc && table_index) rc = c->d_lut_idx.grow(S_max * sizeof(int32_t));
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv0, N * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
+    const MkMvArgs mv{c->d_mv_w.as<int32_t>(), p, q, out_bias};
+    const int32_t *in[3] = {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr};
+    const int32_t *const res = keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>();
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0);
+        for (int k = 0; k < 3; k++)
+            if (in[k]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(k), in[k] + s0 * words, S * words * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], st));
+        lut_prologue_launch(LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, S, c->words, c->w_pad, c->log2_2n,
+                            c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), nullptr, st);
+        THFHE_TRY(mk_enqueue_lut_rotation(c, 1, S, c->d_tv.as<int64_t>(), table_index ? c->d_lut_idx.as<int32_t>() : nullptr,
+                                          keyswitch ? c->stage.out_ptr() : nullptr, &mv));
+        THFHE_HIP(hipMemcpyAsync(out + s0 * q * rec, res, S * q * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
+}
+
+// The six-column entries of the 3-gen executor (F: the entry's families and the generations it admits): the host checks and the plan before the
+// context is looked at, then the run.  The gate classes run as in thfhe_mk_dag_run_batch; a LUT launch group runs the fused prologue
+// (lut_prologue_kernel on the wire table, over the P n + 1 record words), then mk_enqueue_lut_rotation with the key switch into the staging output
+// (DESIGN 4.9).  An MV group is the same with the multi-value epilogue: one base vector per launch, the table per job, q records per
+// node scattered into consecutive wires, in slices of at most dag_slice nodes and mv_slice / q of them.
+int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const int64_t *mv_out_bias, size_t instances, int64_t *stats) {
+    DagPlan plan;
+    THFHE_TRY(dag_checked_plan(A, F, mk_dag_classify, plan));
+    const bool mv_entry = F.gens & kDagGenMv;
+    if (stats && mv_entry) plan.fill_stats(stats);   // the plan's figures need no device
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (stats && !mv_entry) plan.fill_stats(stats);   // thfhe_mk_dag_run_lut_batch gives them to a caller with a context only
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const int words = c->words + 1, theta_max = plan.max_theta;
+    const size_t N = c->p.N;
+    hipStream_t st = c->stream;
+    auto mv_slice_of = [&](int mv, size_t all) { return std::min({all, c->dag_slice, std::max<size_t>(1, c->mv_slice / (size_t)F.mvs[mv].q)}); };
+    for (const DagBatch &b : plan.batches) {   // every buffer an MV group's slices use, the staging output included, before dag_execute takes pointers
+        if (b.cls != kDagMv) continue;
+        const size_t S = mv_slice_of(b.tree, b.count * instances), q = (size_t)F.mvs[b.tree].q;
+        THFHE_TRY(mk_lut_workspace(c, S, (int)q));
+        THFHE_TRY(c->d_lut_idx.grow(S * sizeof(int32_t)));
+        THFHE_TRY(c->stage.out.grow(S * q * words * sizeof(int32_t)));
+    }
+    auto upload = [&](DevBuf &d, const void *h, size_t bytes) -> int {   // the run's tables and specs, once per call
+        if (!bytes) return THFHE_OK;
+        THFHE_TRY(d.grow(bytes));
+        THFHE_HIP(hipMemcpyAsync(d.as<void>(), h, bytes, hipMemcpyHostToDevice, st));
+        return THFHE_OK;
+    };
+    THFHE_TRY(upload(c->d_tv, F.tv, (size_t)F.n_luts * N * sizeof(int64_t)));
+    THFHE_TRY(upload(c->dag.specs, F.specs, (size_t)F.n_specs * sizeof(thfhe_lut_spec)));
+    THFHE_TRY(upload(c->d_dag_mv_tv0, F.mv_tv0, (size_t)F.n_bases * N * sizeof(int64_t)));
+    THFHE_TRY(upload(c->d_dag_mv_w, F.mv_factors, F.n_factor_words * sizeof(int32_t)));
+    const unsigned wb = (unsigned)((words + 255) / 256);
+    return dag_execute(
+        plan, c->dag, st, words, A, instances, c->dag_slice,
+        [&](size_t max_gates, int32_t **in, int32_t **out) {
+            int r = mk_ensure_workspace(c, 2 * max_gates);
+            if (!r) r = mk_lut_workspace(c, max_gates, theta_max);
+            if (!r) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
+            if (!r) r = c->stage.grow(max_gates * words);
+            if (!r) r = c->stage.out.grow(theta_max * max_gates * words * sizeof(int32_t));   // key switch of nodes x theta records
+            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
+            return r;
+        },
+        [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); },
+        [&](int theta, const DagLutSlice &s) {
+            lut_prologue_launch(s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, c->words, c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(),
+                                c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>(), st);
+            return mk_enqueue_lut_rotation(c, theta, (size_t)s.total, c->d_tv.as<int64_t>(), c->d_lut_idx.as<int32_t>(), c->stage.out_ptr());
+        },
+        [&](const DagExtGroup &g) -> int {   // the plan of this engine holds no other grouped kind; t_y = each node's table
+            if (g.cls != kDagMv) return thfhe_fail(THFHE_E_INVALID, "grouped node kind not defined for the 3-gen engine");
+            const thfhe_mv_spec m = F.mvs[g.tree];
+            const int64_t *const tv0 = c->d_dag_mv_tv0.as<int64_t>() + (size_t)m.base * N;
+            const MkMvArgs mv{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p, m.q, mv_out_bias ? mv_out_bias[g.tree] : 0};
+            const long slice = (long)mv_slice_of(g.tree, (size_t)g.all);
+            for (long first = 0; first < g.all; first += slice) {
+                const long S = std::min(slice, g.all - first);
+                lut_prologue_launch(LutWireSrc<LutSpecByValue, LutIdx::table>{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1}, (size_t)S, c->words,
+                                    c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>(), st);
+                THFHE_TRY(mk_enqueue_lut_rotation(c, 1, (size_t)S, tv0, c->d_lut_idx.as<int32_t>(), c->stage.out_ptr(), &mv));
+                hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(S * m.q), wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires, first,
+                                   S, g.cnt, g.n_wires, words, m.q);
+                THFHE_HIP(hipGetLastError());
+            }
+            return (int)THFHE_OK;
+        });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1348,46 +1507,34 @@ int thfhe_mk_dag_run_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inpu
         [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); });
 }
 
-// LUT nodes among the 3-gen gates: the gate classes run as in thfhe_mk_dag_run_batch; a LUT launch group runs the fused
-// prologue (lut_prologue_kernel on the wire table, over the P n + 1 record words), then mk_enqueue_lut_rotation with the key switch into the staging output.
+// LUT nodes among the 3-gen gates: mk_dag_run with the LUT generation, both families required.
 int thfhe_mk_dag_run_lut_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
                                const thfhe_lut_spec *specs, int n_specs, const int64_t *tv, int n_luts, size_t instances, const int32_t *out_wires,
                                size_t n_out, int32_t *outputs, int64_t *stats) {
-    const DagCall A{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs};
-    DagPlan plan;
-    int rc = dag_checked_plan(A, DagFamilies{kDagGenLut, specs, n_specs, tv, n_luts}, mk_dag_classify, plan);
-    if (rc) return rc;
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (stats) plan.fill_stats(stats);
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    const int words = c->words + 1, theta_max = plan.max_theta;
-    const size_t N = c->p.N;
-    rc = c->d_tv.grow((size_t)n_luts * N * sizeof(int64_t));
-    if (!rc) rc = c->dag.specs.grow((size_t)n_specs * sizeof(thfhe_lut_spec));
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv, (size_t)n_luts * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->dag.specs.as<thfhe_lut_spec>(), specs, (size_t)n_specs * sizeof(thfhe_lut_spec), hipMemcpyHostToDevice, c->stream));
-    return dag_execute(
-        plan, c->dag, c->stream, words, A, instances, c->dag_slice,
-        [&](size_t max_gates, int32_t **in, int32_t **out) {
-            int r = mk_ensure_workspace(c, 2 * max_gates);
-            if (!r) r = mk_lut_workspace(c, max_gates, theta_max);
-            if (!r) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
-            if (!r) r = c->stage.grow(max_gates * words);
-            if (!r) r = c->stage.out.grow(theta_max * max_gates * words * sizeof(int32_t));   // key switch of nodes x theta records
-            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
-            return r;
-        },
-        [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); },
-        [&](int theta, const DagLutSlice &s) {
-            lut_prologue_launch(s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, c->words, c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(),
-                                c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>(), c->stream);
-            return mk_enqueue_lut_rotation(c, theta, (size_t)s.total, c->d_tv.as<int64_t>(), c->d_lut_idx.as<int32_t>(), c->stage.out_ptr());
-        });
+    return mk_dag_run(c, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, DagFamilies{kDagGenLut, specs, n_specs, tv, n_luts}, nullptr,
+                      instances, stats);
+}
+
+// ... and multi-value nodes: MV rows on the run's Torus64 base vectors; without the multi-value families the call is the one above.
+int thfhe_mk_dag_run_mv_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs,
+                              int n_specs, const int64_t *tv, int n_luts, const thfhe_mv_spec *mvs, int n_mvs, const int64_t *mv_tv0, int n_bases,
+                              const int32_t *mv_factors, size_t n_factor_words, const int64_t *mv_out_bias, size_t instances, const int32_t *out_wires,
+                              size_t n_out, int32_t *outputs, int64_t *stats) {
+    if (!mvs && !n_mvs && !mv_tv0 && !n_bases && !mv_factors && !n_factor_words)
+        return thfhe_mk_dag_run_lut_batch(c, inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, instances, out_wires, n_out, outputs, stats);
+    DagFamilies F{kDagGenLut | kDagGenMv, specs, n_specs, tv, n_luts};
+    F.mvs = mvs, F.n_mvs = n_mvs, F.mv_tv0 = mv_tv0, F.n_bases = n_bases, F.mv_factors = mv_factors, F.n_factor_words = n_factor_words;
+    return mk_dag_run(c, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, F, mv_out_bias, instances, stats);
 }
 
 int thfhe_mk_set_dag_slice(thfhe_mk_ctx *c, size_t max_gates) { return ctx_set_dag_slice(c, max_gates); }
+
+int thfhe_mk_set_mv_slice(thfhe_mk_ctx *c, size_t max_records) {
+    if (!c || max_records < 1 || max_records > ((size_t)1 << 20)) return thfhe_fail(THFHE_E_INVALID, "slice must be 1 .. 2^20 records");
+    std::lock_guard<std::mutex> g(c->mu);
+    c->mv_slice = max_records;
+    return THFHE_OK;
+}
 
 int thfhe_mk_dag_run(thfhe_mk_ctx *c, int32_t *wires, size_t n_inputs, const int32_t *gates, size_t n_gates, int64_t *stats) {
     if (!wires) return thfhe_fail(THFHE_E_INVALID, "null argument");
@@ -1491,6 +1638,18 @@ int thfhe_mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const in
 int thfhe_mk_lut_bootstrap_wo_keyswitch(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const int64_t *tv, int n_luts, const int32_t *lut_index,
                                         const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1, size_t count) {
     return mk_lut_bootstrap(c, spec, tv, n_luts, lut_index, in0, in1, in2, out_N1, count, false);
+}
+
+int thfhe_mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const int64_t *tv0, const int32_t *factors, int p, int q, int n_tables,
+                              const int32_t *table_index, int64_t out_bias, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out,
+                              size_t count) {
+    return mk_mv_lut_bootstrap(c, spec, tv0, factors, p, q, n_tables, table_index, out_bias, in0, in1, in2, out, count, true);
+}
+
+int thfhe_mk_mv_lut_bootstrap_wo_keyswitch(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const int64_t *tv0, const int32_t *factors, int p, int q,
+                                           int n_tables, const int32_t *table_index, int64_t out_bias, const int32_t *in0, const int32_t *in1,
+                                           const int32_t *in2, int32_t *out_N1, size_t count) {
+    return mk_mv_lut_bootstrap(c, spec, tv0, factors, p, q, n_tables, table_index, out_bias, in0, in1, in2, out_N1, count, false);
 }
 
 }  // extern "C"

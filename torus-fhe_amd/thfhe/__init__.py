@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("THFHE_HIP_LIB", os.path.join(os.path.dirname(_HERE), 
 NAND, OR, AND, XOR, XNOR, NOR, ANDNY, ANDYN, ORNY, ORYN, MUX, NOT, COPY, AND3 = range(14)
 LUT, LUT_OUT = 14, 15   # gate-DAG LUT node and its outputs j > 0 (dag_run_lut_batch, dag_run_tree_batch)
 LUT_ENC, SELECT, TREE = 16, 17, 18   # gate-DAG encrypted-table, select and tree nodes (CloudKey.dag_run_tree_batch, dag_run_mv_batch)
-MV, TREE_MV = 19, 20                 # gate-DAG multi-value and k-output multi-value tree nodes (CloudKey.dag_run_mv_batch, dag_run_lhe_batch)
+MV, TREE_MV = 19, 20                 # gate-DAG multi-value and k-output multi-value tree nodes (CloudKey.dag_run_mv_batch, dag_run_lhe_batch; MV: MKCloudKey.dag_run_mv_batch)
 LHE_LOOKUP, LHE_GATHER, LHE_WFA = 21, 22, 23   # gate-DAG leveled nodes on TGSW-encrypted bits (CloudKey.dag_run_lhe_batch only)
 
 MU8 = 1 << 29     # encode_message(1, 8), Torus32      (numeric-functions.jl:86-89)
@@ -296,6 +296,13 @@ SIGNATURES = {
     "thfhe_mk_bootstrap": (C.c_int, [_vp, C.c_int64, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_mk_mv_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int64, _i32p, _i32p, _i32p, _i32p,
+                                            C.c_size_t]),
+    "thfhe_mk_mv_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int64, _i32p, _i32p, _i32p,
+                                                         _i32p, C.c_size_t]),
+    "thfhe_mk_set_mv_slice": (C.c_int, [_vp, C.c_size_t]),
+    "thfhe_mk_dag_run_mv_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, C.POINTER(MvSpec), C.c_int,
+                                            _i64p, C.c_int, _i32p, C.c_size_t, _i64p, C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_mk_prologue_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t]),
     "thfhe_mk_set_stream": (C.c_int, [_vp, _vp]),
     "thfhe_mk_set_pair_threshold": (C.c_int, [_vp, C.c_long]),
@@ -363,6 +370,12 @@ def _wrap32(v):
     """An integer taken mod 2^32 as a signed int32 (weights and Torus32 constants)."""
     v = int(v) & 0xFFFFFFFF
     return v - (1 << 32) if v >= 1 << 31 else v
+
+
+def _wrap64(v):
+    """An integer taken mod 2^64 as a signed int64 (Torus64 constants)."""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= 1 << 63 else v
 
 
 def _rec(a, words):
@@ -540,6 +553,16 @@ class _EvalKey(_Handle):
         _check(fn(self.h, C.byref(spec), ptv, tv.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
         return out
 
+    def _lut_args(self, ins, weights, bias, theta, what):
+        given = [v for v in ins if v is not None]
+        if any(v is None for v in ins[:len(given)]) or len(given) != len(weights):
+            raise ValueError(f"{what}: give the inputs in order and one weight per input")
+        recs = [_rec(v, self.words) for v in given]
+        _same_count(*recs)
+        w = list(weights) + [0] * (3 - len(weights))
+        spec = LutSpec(len(recs), (C.c_int32 * 3)(*[_wrap32(v) for v in w]), _wrap32(bias), int(theta))
+        return recs, spec, [_p32(v) for v in recs] + [None] * (3 - len(recs))
+
     # -- device-buffer calls -----------------------------------------------------------------------
     def _alloc(self, n):
         return self._fn("dev_alloc")(self.h, n)
@@ -625,16 +648,6 @@ class CloudKey(_EvalKey):
     def lut_bootstrap_enc_wo_keyswitch(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
         """lut_bootstrap_enc without the key switch: int32[count, theta, N+1] records under the ring key."""
         return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, False)
-
-    def _lut_args(self, ins, weights, bias, theta, what):
-        given = [v for v in ins if v is not None]
-        if any(v is None for v in ins[:len(given)]) or len(given) != len(weights):
-            raise ValueError(f"{what}: give the inputs in order and one weight per input")
-        recs = [_rec(v, self.words) for v in given]
-        _same_count(*recs)
-        w = list(weights) + [0] * (3 - len(weights))
-        spec = LutSpec(len(recs), (C.c_int32 * 3)(*[_wrap32(v) for v in w]), _wrap32(bias), int(theta))
-        return recs, spec, [_p32(v) for v in recs] + [None] * (3 - len(recs))
 
     def _lut_enc(self, tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, keyswitch):
         ins, spec, p = self._lut_args((x, y, z), weights, bias, theta, "lut_bootstrap_enc")
@@ -1070,6 +1083,63 @@ class MKCloudKey(_EvalKey):
         """Batches of <= max_single_jobs rotations run one gate per workgroup; larger ones two gates per workgroup."""
         _check(lib().thfhe_mk_set_pair_threshold(self.h, int(max_single_jobs)))
         self._pair_threshold = int(max_single_jobs)
+
+    # -- multi-value bootstrapping on Torus64 (thfhe_mk_mv_lut_bootstrap, DESIGN 4.19) ---------------------------------------------------
+    def mv_lut_bootstrap(self, factors, x, y=None, z=None, *, tv0, weights=(1,), bias=0, table_index=None, out_bias=0):
+        """q functions of one encrypted digit from ONE multi-key blind rotation: the base vector tv0 int64[N] (thfhe.lut.mv_base(step, N, torus_bits=64))
+        is rotated by x = sum_q weights[q] * (x, y, z)[q] + (0, bias) at theta = 1; output j of sample s combines p extractions of the Torus64
+        accumulator with the taps factors[table_index[s]][j] (thfhe.lut.mv_factors, mv_bool_factors), adds out_bias (a Torus64 word) to the body and
+        converts once.  factors: int32[q][p] or int32[n_tables][q][p].  Returns int32[count, q, P*n+1]."""
+        return self._mv(factors, x, y, z, tv0, weights, bias, table_index, out_bias, True)
+
+    def mv_lut_bootstrap_wo_keyswitch(self, factors, x, y=None, z=None, *, tv0, weights=(1,), bias=0, table_index=None, out_bias=0):
+        """mv_lut_bootstrap without the key switch: int32[count, q, N+1] records under the ring key."""
+        return self._mv(factors, x, y, z, tv0, weights, bias, table_index, out_bias, False)
+
+    def _mv(self, factors, x, y, z, tv0, weights, bias, table_index, out_bias, keyswitch):
+        ins, spec, p = self._lut_args((x, y, z), weights, bias, 1, "mv_lut_bootstrap")
+        count = ins[0].shape[0]
+        w = np.ascontiguousarray(factors, np.int32)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.size == 0:
+            raise ValueError("factors: expected int32[q][p] or int32[n_tables][q][p]")
+        tv0 = np.ascontiguousarray(tv0, np.int64).reshape(-1)
+        if tv0.shape[0] != self.params.N:
+            raise ValueError(f"tv0: expected int64[{self.params.N}]")
+        idx = None
+        if table_index is not None:
+            idx = np.ascontiguousarray(table_index, np.int32).reshape(-1)
+            if idx.shape[0] != count:
+                raise ValueError(f"table_index holds {idx.shape[0]} entries for {count} samples")
+        out = np.empty((count, w.shape[1], self.words if keyswitch else self.params.N + 1), np.int32)
+        fn = lib().thfhe_mk_mv_lut_bootstrap if keyswitch else lib().thfhe_mk_mv_lut_bootstrap_wo_keyswitch
+        _check(fn(self.h, C.byref(spec), tv0.ctypes.data_as(_i64p), _p32(w), w.shape[2], w.shape[1], w.shape[0], _p32(idx), _wrap64(out_bias), p[0], p[1], p[2],
+                  _p32(out), count))
+        return out
+
+    def set_mv_slice(self, max_records):
+        """Output records (samples x q) per slice of mv_lut_bootstrap and of an MV launch group: (N + 1) x 4 B of workspace each; default 4096."""
+        _check(lib().thfhe_mk_set_mv_slice(self.h, int(max_records)))
+
+    def dag_run_mv_batch(self, input_records, nodes, specs=(), tv=None, mvs=(), mv_tv0=None, mv_factors=None, mv_out_bias=None, out_wires=None):
+        """dag_run_lut_batch with multi-value nodes (thfhe_mk_dag_run_mv_batch).  mvs: MvSpec or (lo, hi, p, q, k, base, factors_off,
+        n_tables) tuples (hi None, k 1); mv_tv0: int64[n_bases][N] base vectors; mv_factors: int32[words], the taps of every spec; mv_out_bias: one
+        Torus64 word per spec (None: 0).  specs and tv may be absent."""
+        def families():
+            N = self.params.N
+            sp = (LutSpec * len(specs))(*[_lut_spec(s) for s in specs]) if len(specs) else None
+            t = None if tv is None else np.ascontiguousarray(tv, np.int64).reshape(-1, N)
+            mv = _mv_specs(mvs)
+            tv0 = None if mv_tv0 is None else np.ascontiguousarray(mv_tv0, np.int64).reshape(-1, N)
+            fac = None if mv_factors is None else np.ascontiguousarray(mv_factors, np.int32).reshape(-1)
+            ob = None if mv_out_bias is None else np.array([_wrap64(v) for v in np.ravel(mv_out_bias)], np.int64)
+            if ob is not None and ob.shape[0] != len(mvs):
+                raise ValueError(f"mv_out_bias holds {ob.shape[0]} words for {len(mvs)} specs")
+            p64 = lambda a: None if a is None else a.ctypes.data_as(_i64p)
+            return (sp, len(specs), p64(t), 0 if t is None else t.shape[0], mv, len(mvs), p64(tv0), 0 if tv0 is None else tv0.shape[0], _p32(fac),
+                    0 if fac is None else fac.shape[0], p64(ob))
+        return self._dag_run("dag_run_mv_batch", lib().thfhe_mk_dag_run_mv_batch, (self.h,), input_records, nodes, 6, families, out_wires)
 
     def rotation_kernel_name(self, rotations):
         """The blind-rotation kernel a batch of `rotations` is dispatched to (mk_launch_rotation in thfhe_mk.hip)."""

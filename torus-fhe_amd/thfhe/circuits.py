@@ -52,6 +52,7 @@ class Circuit:
         self.mv_bases = []    # base vectors int32[N] of the MV / TREE_MV nodes
         self.mv_specs = []    # [lo spec, hi spec or None, p, q, k, base id, [factor tables int32[k][q][p]]] of the MV / TREE_MV launch groups
         self.mv_rows = {}     # gate index of an MV / TREE_MV node -> (mv id, table t of that spec)
+        self.mv_out_bias = {} # mv id -> the Torus64 word added to every output of its MV nodes (multi-key engine only; absent: 0)
         self.lhe_tab = []     # table polynomials of the LHE_LOOKUP nodes: (body int32[N], mask or None, plaintext polynomial or None), rows of lhe_table
         self.lhe_fin = []     # final weights of the LHE_WFA nodes, the same triples, rows of lhe_finals
         self.lhe_specs = []   # (set, d_tree, d_rot, theta) of the LHE_LOOKUP / LHE_GATHER launch groups, deduplicated
@@ -193,15 +194,17 @@ class Circuit:
 
     def mv_base(self, tv0):
         """Register the base vector int32[N] of multi-value rotations (thfhe.lut.mv_base, or the first result of tree_mv_factors / tree_mvk_factors);
-        returns its id.  Equal vectors share one id."""
-        tv0 = np.ascontiguousarray(tv0, np.int32).reshape(-1)
-        key = ("mv_base", tv0.tobytes())
+        returns its id.  Equal vectors share one id.  An int64 array is kept as the Torus64 base vector of a circuit for the multi-key engine
+        (thfhe.lut.mv_base(step, N, torus_bits=64))."""
+        tv0 = np.asarray(tv0)
+        tv0 = np.ascontiguousarray(tv0, np.int64 if tv0.dtype == np.int64 else np.int32).reshape(-1)
+        key = ("mv_base", tv0.dtype.str, tv0.tobytes())
         if key not in self._ids:
             self._ids[key] = len(self.mv_bases)
             self.mv_bases.append(tv0)
         return self._ids[key]
 
-    def _mv_row(self, op, lo, hi, base, w, operands):
+    def _mv_row(self, op, lo, hi, base, w, operands, out_bias=0):
         """An MV / TREE_MV row on the factor table w int32[k][q][p]: its launch group's spec (one per distinct prologues, shape and base) and the
         table's index in it; the head wire and its LUT_OUT rows."""
         k, q, p = w.shape
@@ -209,10 +212,12 @@ class Circuit:
             raise ValueError(f"unknown base vector id {base}")
         if p < 2 or p > 64 or p & (p - 1) or k * q > 64:
             raise ValueError("p must be a power of two in 2 .. 64 and the node's rotation has at most 64 outputs")
-        key = ("mv", lo, hi, p, q, k, int(base))
+        key = ("mv", lo, hi, p, q, k, int(base)) + ((int(out_bias),) if out_bias else ())
         if key not in self._ids:
             self._ids[key] = len(self.mv_specs)
             self.mv_specs.append([lo, hi, p, q, k, int(base), []])
+            if out_bias:
+                self.mv_out_bias[self._ids[key]] = int(out_bias)
         mi = self._ids[key]
         tabs = self.mv_specs[mi][6]
         t = next((i for i, x in enumerate(tabs) if np.array_equal(x, w)), len(tabs))
@@ -222,10 +227,11 @@ class Circuit:
         self.mv_rows[len(self.gates) - 1] = (mi, t)
         return [head] + [self.gate(LUT_OUT, head) for _ in range((k if op == TREE_MV else q) - 1)]
 
-    def mv(self, base, factors, inputs, weights=(1,), bias=0):
+    def mv(self, base, factors, inputs, weights=(1,), bias=0, out_bias=0):
         """An MV node: q functions of the digit x = sum_q weights[q] * inputs[q] + (0, bias) from ONE rotation of the base vector `base` (mv_base),
         function j through the taps factors[j] (thfhe.lut.mv_factors: int32[q][p]).  Returns the q output wire ids (consecutive: a SELECT can take
-        them as its candidates)."""
+        them as its candidates).  out_bias: the Torus64 word the multi-key engine adds to every output (thfhe.lut.mv_bool_factors); the single-key
+        engine has none."""
         inputs = list(inputs)
         if not 1 <= len(inputs) <= 3 or len(weights) != len(inputs):
             raise ValueError("an MV node takes 1 to 3 inputs and one weight per input")
@@ -233,7 +239,7 @@ class Circuit:
         if w.ndim != 2:
             raise ValueError("factors: expected int32[q][p]")
         lo = (len(inputs), tuple(_wrap32(v) for v in list(weights) + [0] * (3 - len(weights))), _wrap32(bias), 1)
-        return self._mv_row(MV, lo, None, base, w[None], inputs)
+        return self._mv_row(MV, lo, None, base, w[None], inputs, out_bias)
 
     def tree_mv(self, base, factors, lo_inputs, hi_inputs, lo_weights=None, hi_weights=None, lo_bias=0, hi_bias=0):
         """A TREE_MV node: k functions f_j(hi, lo) of two encrypted digits in 1 + k rotations (one multi-value rotation of the base vector `base` on
@@ -1179,6 +1185,14 @@ def simulate_mk(cir, input_bits):
 
 # ---- evaluator --------------------------------------------------------------------------------------------------------
 def _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets=None):
+    if ck._tv_dtype == np.int64:   # the 3-gen multi-key engine: gates, LUT and MV nodes (thfhe_mk_dag_run_mv_batch)
+        if cir.has_tree_nodes() or cir.has_lhe_nodes() or any(g[0] == TREE_MV for g in cir.gates):
+            raise ValueError("the multi-key engine runs gate, LUT and MV nodes only (no packing key switch, no leveled nodes)")
+        mvs, tv0, fac = cir.mv_families()
+        bias = [cir.mv_out_bias.get(i, 0) for i in range(len(mvs))]
+        return ck.dag_run_mv_batch(x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None, mvs, tv0, fac, bias, sel)
+    if cir.mv_out_bias:
+        raise ValueError("out_bias on an MV node is the multi-key engine's; the single-key thfhe_dag_run_mv_batch has none")
     enc = cir.enc_tables
     args = (x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None, np.stack([e[0] for e in enc]) if enc else None,
             np.stack([e[1] for e in enc]) if enc else None, cir.tree_specs, np.stack(cir.tv1) if cir.tv1 else None)

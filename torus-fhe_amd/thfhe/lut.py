@@ -107,13 +107,17 @@ def tree_test_vectors(f, p_hi, p_lo, p_out, theta=1, N=1024):
                      for r in range(p_hi // theta)])
 
 
-def mv_base(step, N=1024):
+def mv_base(step, N=1024, torus_bits=32):
     """Base vector of a multi-value bootstrap (thfhe_mv_lut_bootstrap): int32[N] = (step/2, ..., step/2).  Times the factor of an integer
     table f (mv_factors) it is test_vector(f * step, p): output j of the rotation carries f_j(m) * step.  step: an even Torus32 word, e.g.
-    2^32 / (2 p_out) for outputs in the padding-bit encoding at modulus p_out."""
+    2^32 / (2 p_out) for outputs in the padding-bit encoding at modulus p_out.  torus_bits=64: int64[N] from an even Torus64 step (the multi-key
+    engine, thfhe_mk_mv_lut_bootstrap)."""
+    _check_bits(torus_bits)
     step = int(step)
     if step % 2:
         raise ValueError("step must be even (the base vector holds step / 2)")
+    if torus_bits == 64:
+        return _to_i64([step // 2] * N)
     return _to_i32(np.full(N, step // 2, np.int64))
 
 
@@ -133,6 +137,19 @@ def mv_factors(int_tables, p):
     if np.any(np.abs(c) >= 1 << 31):
         raise ValueError("factor out of the int32 range")
     return c.astype(np.int32)
+
+
+def mv_bool_factors(bit_tables, p, torus_bits=32, N=1024):
+    """(tv0, factors, out_bias) of q bit tables (bit_tables[j][m] in {0, 1}, m in [0, p)) whose outputs leave the rotation in the gates' encoding
+    +-mu (mu = 2^29, or 2^61 with torus_bits=64): the 0/1 tables at step 2 mu with the bias -mu added after the combination, so that a tap is a
+    difference of bits -- half the taps, and half the rotation noise at the output, of +-1 tables at step mu.  out_bias is the argument of that name of
+    thfhe_mk_mv_lut_bootstrap; the single-key entry has none (add it to the body words)."""
+    _check_bits(torus_bits)
+    f = np.asarray(bit_tables, np.int64)
+    if np.any((f != 0) & (f != 1)):
+        raise ValueError("bit tables hold 0 and 1 only")
+    mu = MU8_64 if torus_bits == 64 else MU8
+    return mv_base(2 * mu, N, torus_bits), mv_factors(f, p), -mu
 
 
 def tree_mv_factors(f, p_hi, p_lo, p_out, N=1024):
