@@ -178,3 +178,25 @@ def test_invalid_calls_are_refused_and_the_context_stays_usable(O, mk2):
         ck.lut_bootstrap(tv, x, theta=3)
     assert ck.lut_bootstrap(tv, x[:0]).shape == (0, 1, p.parties * p.n + 1)
     assert np.array_equal(ck.lut_bootstrap(tv, x)[:, 0], ck.bootstrap(x, 1 << 61))
+
+
+def test_a_profiled_dag_run_leaves_the_flat_calls_timings(O):
+    # A stage of a gate-DAG run records no profiling events: after a profiled run, last_timings() still answers from the four events of the last
+    # flat call and returns the same four floats.
+    import thfhe
+    p, K, ck = _keys(O, "MK2", 43, n=30)
+    try:
+        ck.set_profiling(True)
+        rng = np.random.default_rng(811)
+        x = R.encrypt_words(K, rng.integers(-2**31, 2**31, 3), O.SIGMAS["MK2"]["lwe"], 812)
+        tvs = rng.integers(-2**63, 2**63, (2, p.N), dtype=np.int64)
+        flat = ck.lut_bootstrap(tvs, x, lut_index=[0, 1, 0])
+        before = ck.last_timings()
+        assert all(np.isfinite(v) and v >= 0 for v in before.values())
+        nodes = np.array([[thfhe.LUT, 0, -1, -1, 0, 0], [thfhe.LUT, 1, -1, -1, 0, 1]], np.int32)   # node g: table g on input g
+        out, stats = ck.dag_run_lut_batch(x[None], nodes, [(1, (1, 0, 0), 0, 1)], tvs)
+        assert stats["rotations"] == 2
+        assert ck.last_timings() == before
+        assert np.array_equal(out[0], flat[:2, 0])
+    finally:
+        ck.close()

@@ -11,7 +11,8 @@
 //                entry has the tree generation too (single key)
 //   kDagGenLhe   leveled nodes (thfhe_dag_run_lhe_batch; single key): LHE_LOOKUP, LHE_GATHER and LHE_WFA rows on the client's TGSW sets;
 //                dag_lhe_gather_kernel stages a GATHER node's candidates for the box packing
-// The kinds from kDagGenTree on are planned here and run by the engine (thfhe_sk.hip: sk_dag_run_luts).
+// The kinds from kDagGenTree on are planned here and run by the engine (thfhe_sk.hip: sk_dag_run_luts), a grouped kind in slices through dag_group_slices.
+// dag_gates_run_batch / dag_gates_run are the four-column entries of both engines.
 #ifndef THFHE_DAG_H
 #define THFHE_DAG_H
 
@@ -704,6 +705,51 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
     e = hipStreamSynchronize(stream);
     if (rc == THFHE_OK && e != hipSuccess) rc = thfhe_fail_hip(e, "gate-DAG executor: sync");
     return rc;
+}
+
+// One table family or spec array of a run into its grow-only device buffer, once per call; an absent family (bytes = 0) uploads nothing.
+inline int dag_upload(DevBuf &d, hipStream_t stream, const void *h, size_t bytes) {
+    if (!bytes) return THFHE_OK;
+    THFHE_TRY(d.grow(bytes));
+    THFHE_HIP(hipMemcpyAsync(d.as<void>(), h, bytes, hipMemcpyHostToDevice, stream));
+    return THFHE_OK;
+}
+
+// A grouped launch group in slices of at most `slice` nodes over all instances: body(first, S) enqueues the chain of nodes [first, first + S) of
+// g.all, `outs` records of `words` words per node into stage_out; then record j outs + t of the slice goes to wire t_out[g] + t of its instance.
+template <typename Body>
+int dag_group_slices(const DagExtGroup &g, size_t slice, int outs, const int32_t *stage_out, int words, hipStream_t stream, Body body) {
+    const unsigned wb = (unsigned)((words + 255) / 256);
+    for (long first = 0; first < g.all; first += (long)slice) {
+        const long S = std::min((long)slice, g.all - first);
+        THFHE_TRY(body(first, S));
+        if (outs == 1)
+            hipLaunchKernelGGL(dag_scatter_kernel, dim3((unsigned)S, wb), dim3(256), 0, stream, stage_out, g.t_out, g.wires, first, S, g.cnt, g.n_wires, words);
+        else
+            hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(S * outs), wb), dim3(256), 0, stream, stage_out, g.t_out, g.wires, first, S, g.cnt,
+                               g.n_wires, words, outs);
+        THFHE_HIP(hipGetLastError());
+    }
+    return THFHE_OK;
+}
+
+// thfhe_dag_run_batch / thfhe_mk_dag_run_batch: four-column gate rows only.  classify, ensure and run are dag_plan's and dag_execute's.
+template <typename Ctx, typename Classify, typename Ensure, typename Run>
+int dag_gates_run_batch(Ctx *c, const DagCall &A, size_t instances, int64_t *stats, Classify classify, Ensure ensure, Run run) {
+    if (!c || (!A.inputs && A.n_inputs) || (!A.nodes && A.n_nodes) || (!A.outputs && A.n_nodes) || (!A.out_wires && A.n_out))
+        return thfhe_fail(THFHE_E_INVALID, "null argument");
+    DagPlan plan;
+    THFHE_TRY(dag_plan(A, DagFamilies{}, classify, plan));
+    if (stats) plan.fill_stats(stats);
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    return dag_execute(plan, c->dag, c->stream, c->rec_words(), A, instances, c->dag_slice, ensure, run);
+}
+// thfhe_dag_run / thfhe_mk_dag_run: one instance in place, every gate's wire written after the inputs; run_batch is the engine's entry above
+template <typename Ctx, typename RunBatch>
+int dag_gates_run(Ctx *c, int32_t *wires, size_t n_inputs, const int32_t *gates, size_t n_gates, int64_t *stats, RunBatch run_batch) {
+    if (!wires) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    return run_batch(c, wires, n_inputs, gates, n_gates, 1, nullptr, 0, wires + n_inputs * (size_t)(c ? c->rec_words() : 0), stats);
 }
 
 }  // namespace

@@ -208,6 +208,45 @@ int ctx_staged(Ctx *c, size_t words, const void *const (&src)[3], const size_t (
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }
+// ... and of a call that goes up and down in slices of at most S_max samples (the multi-value bootstraps), the caller having locked the context
+// and sized every buffer for S_max: per slice the operand records in[q] (null sources skipped) into stage.in[q] and, with `index`, the slice's
+// per-sample indices into d_index; run(S, last) enqueued; then the slice's S records of out_words words copied from `res` to their place in
+// `out`.  The stream is drained once, after the last slice.
+template <typename Ctx, typename Run>
+int ctx_sliced(Ctx *c, size_t count, size_t S_max, const int32_t *const (&in)[3], const int32_t *index, int32_t *d_index, Run run, const int32_t *res,
+               int32_t *out, size_t out_words) {
+    const size_t words = c->rec_words();
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = count - s0 < S_max ? count - s0 : S_max;
+        for (int q = 0; q < 3; q++)
+            if (in[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), in[q] + s0 * words, S * words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if (index) THFHE_HIP(hipMemcpyAsync(d_index, index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        THFHE_TRY(run(S, s0 + S == count));
+        THFHE_HIP(hipMemcpyAsync(out + s0 * out_words, res, S * out_words * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    return THFHE_OK;
+}
+
+// thfhe_gates / thfhe_mk_gates: one gate on host buffers; gates(d0, d1, d2, dout, count) is the engine's gates_dev body on the staging arrays
+template <typename Ctx, typename Gates>
+int ctx_gates(Ctx *c, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, Gates gates) {
+    if (!c || !in0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (count == 0) return THFHE_OK;
+    const size_t words = count * c->rec_words(), bytes = words * sizeof(int32_t);
+    return ctx_staged(c, words, {in0, in1, in2}, {bytes, bytes, bytes}, [&] {
+        return gates(c->stage.in_ptr(0), in1 ? c->stage.in_ptr(1) : nullptr, in2 ? c->stage.in_ptr(2) : nullptr, c->stage.out_ptr(), count);
+    }, c->stage.out, out, bytes);
+}
+// thfhe_gates_mixed / thfhe_mk_gates_mixed after the entry's own checks (the opcodes an engine admits differ): two-input gates with per-gate
+// opcodes, which travel in staging buffer 2; run(d0, d1, d_ops, dout) enqueues the engine's bootstraps of the `count` gates
+template <typename Ctx, typename Run>
+int ctx_gates_mixed(Ctx *c, const int32_t *ops, const int32_t *in0, const int32_t *in1, int32_t *out, size_t count, Run run) {
+    const size_t words = count * c->rec_words(), bytes = words * sizeof(int32_t);
+    return ctx_staged(c, words, {in0, in1, ops}, {bytes, bytes, count * sizeof(int32_t)}, [&] {
+        return run(c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), c->stage.out_ptr());
+    }, c->stage.out, out, bytes);
+}
 
 }  // namespace thfhe
 

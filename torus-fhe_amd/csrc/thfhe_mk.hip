@@ -953,7 +953,8 @@ struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     thfhe_params p;
     DevBuf d_bk;
     KsKey ksk;
-    int w_pad = 0, words = 0, log2_2n = 11;
+    int w_pad = 0, words = 0, log2_2n = 11;   // words: the mask words P n of a record
+    int rec_words() const { return words + 1; }
     DevBuf park;                 // batched N = 2048 rotation, two jobs per workgroup: partial spectra between row-part batches (thfhe_rot2k.h)
     long pair_threshold = 256;  // batches of more rotations than this run two gates per workgroup (mk_blind_rotate_pair_kernel)
     bool batched = false;       // N = 2048 with l x digit parts > 3: thfhe_rot2k.h (row parts through the LDS in batches), key table in its layout
@@ -976,7 +977,7 @@ int mk_ensure_workspace(thfhe_mk_ctx *c, size_t jobs) {
     int rc = c->d_bara.grow(jobs * c->w_pad * sizeof(int32_t));
     if (!rc) rc = c->d_barb.grow(jobs * sizeof(int32_t));
     if (!rc) rc = c->d_u.grow(jobs * ((size_t)c->p.N + 1) * sizeof(int32_t));
-    if (!rc) rc = c->d_tmp.grow(jobs * (c->words + 1) * sizeof(int32_t));
+    if (!rc) rc = c->d_tmp.grow(jobs * c->rec_words() * sizeof(int32_t));
     return rc;
 }
 
@@ -996,7 +997,7 @@ int mk_enqueue_bootstraps(thfhe_mk_ctx *c, const int32_t *d0, const int32_t *d1,
                           size_t gates, int64_t mu, int32_t *d_dst, const int32_t *d_ops = nullptr) {
     const size_t jobs = gates * rot;
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
-    dim3 pg((unsigned)((c->words + 1 + 255) / 256), (unsigned)jobs);
+    dim3 pg((unsigned)((c->rec_words() + 255) / 256), (unsigned)jobs);
     hipLaunchKernelGGL(mk_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, L0, L1, d_ops, rot, c->words, c->w_pad, c->log2_2n, (long)jobs, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
     MKBRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, c->p.parties * c->p.n, c->w_pad, c->p.Bgbit, mu};
@@ -1021,57 +1022,51 @@ int mk_lut_workspace(thfhe_mk_ctx *c, size_t count, int theta) {
     return rc;
 }
 
-// the rotation side of a programmable bootstrap of `count` samples whose bara / barb are in the workspace: accumulator start from the
-// sample's table, the rotation of mk_bootstrap_3gen, extraction of theta coefficients into d_u [count][theta][N+1]; then, if d_dst is given,
-// the key switch of the count x theta records into d_dst.  Shared by mk_enqueue_lut and the gate-DAG LUT nodes (thfhe_mk_dag_run_lut_batch).
-// mv: every sample rotates the ONE base vector d_tv (theta is 1), d_idx picks its factor table, and the extraction is
-// mk_extract_mv_kernel's mv->q records per sample, d_u [count][q][N+1].
-int mk_enqueue_lut_rotation(thfhe_mk_ctx *c, int theta, size_t count, const int64_t *d_tv, const int32_t *d_idx, int32_t *d_dst, const MkMvArgs *mv = nullptr) {
+// One PBS stage on the context's stream, the workspace sized by the caller (mk_lut_workspace): the prologue of `jobs` jobs of `src`, the
+// accumulator start from each job's table of d_tv, the rotation of mk_bootstrap_3gen, extraction of theta coefficients into d_u [jobs][theta][N+1];
+// then, with ks_dst, the key switch of the jobs x theta records into it.  A source that writes no table index rotates on d_idx (null: table 0).
+// timed: the profiling events of a flat call (prologue + accumulator start | rotation + extraction | key switch); a gate-DAG run records none.
+// mv: every job rotates the ONE base vector d_tv (theta is 1), the index picks its factor table, and the extraction is
+// mk_extract_mv_kernel's mv->q records per job, d_u [jobs][q][N+1].
+template <typename Src>
+int mk_enqueue_pbs(thfhe_mk_ctx *c, const Src &src, size_t jobs, const int64_t *d_tv, int theta, const int32_t *d_idx, int32_t *ks_dst, bool timed = false,
+                   const MkMvArgs *mv = nullptr) {
     const int N = c->p.N;
-    const size_t recs = count * (mv ? mv->q : theta);
+    const bool ev = timed && c->profiling;
+    int32_t *const idx = c->d_lut_idx.as<int32_t>();
+    if (Src::kIdx != LutIdx::none) d_idx = idx;   // the prologue writes the index the rotation reads
     int64_t *acc = c->d_acc.as<int64_t>();
-    hipLaunchKernelGGL(mk_lut_acc_init_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, c->d_barb.as<int32_t>(), d_tv, mv ? nullptr : d_idx, (long)count, N,
+    if (ev) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
+    lut_prologue_launch(src, jobs, c->words, c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), idx, c->stream);
+    hipLaunchKernelGGL(mk_lut_acc_init_kernel, dim3((unsigned)jobs), dim3(256), 0, c->stream, c->d_barb.as<int32_t>(), d_tv, mv ? nullptr : d_idx, (long)jobs, N,
                        acc);
-    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
+    if (ev) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
     // acc_in == acc_out == d_acc: every rotation shape may run in place.  The N = 1024 / 2048 coop and pair kernels copy their job's
     // accumulator(s) into LDS before the first barrier and write them back only after the last CMux, and no workgroup touches another job's
     // slot; the batched two-level path (c->batched) always rotates the global accumulator in place; the N = 4096 path skips its copy when
     // acc_in is the accumulator it rotates.  barb is not read when acc_in is given: the start above already applied X^{-barb}.
-    MKBRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), nullptr, (long)count, c->p.parties * c->p.n,
+    MKBRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), nullptr, (long)jobs, c->p.parties * c->p.n,
                c->w_pad, c->p.Bgbit, 0, acc, acc};
-    int rc = mk_launch_rotation(c, a);
-    if (rc) return rc;
+    THFHE_TRY(mk_launch_rotation(c, a));
     if (mv) {
-        const dim3 grid((unsigned)count), block(256);
+        const dim3 grid((unsigned)jobs), block(256);
         switch (N) {
-        case 1024: hipLaunchKernelGGL(mk_extract_mv_kernel<1024>, grid, block, 0, c->stream, (const int64_t *)acc, *mv, d_idx, (long)count, c->d_u.as<int32_t>()); break;
-        case 2048: hipLaunchKernelGGL(mk_extract_mv_kernel<2048>, grid, block, 0, c->stream, (const int64_t *)acc, *mv, d_idx, (long)count, c->d_u.as<int32_t>()); break;
-        default: hipLaunchKernelGGL(mk_extract_mv_kernel<4096>, grid, block, 0, c->stream, (const int64_t *)acc, *mv, d_idx, (long)count, c->d_u.as<int32_t>()); break;
+        case 1024: hipLaunchKernelGGL(mk_extract_mv_kernel<1024>, grid, block, 0, c->stream, (const int64_t *)acc, *mv, d_idx, (long)jobs, c->d_u.as<int32_t>()); break;
+        case 2048: hipLaunchKernelGGL(mk_extract_mv_kernel<2048>, grid, block, 0, c->stream, (const int64_t *)acc, *mv, d_idx, (long)jobs, c->d_u.as<int32_t>()); break;
+        default: hipLaunchKernelGGL(mk_extract_mv_kernel<4096>, grid, block, 0, c->stream, (const int64_t *)acc, *mv, d_idx, (long)jobs, c->d_u.as<int32_t>()); break;
         }
     } else {
-        hipLaunchKernelGGL(mk_extract_at_kernel, dim3((unsigned)count, (unsigned)theta), dim3(256), 0, c->stream, (const int64_t *)acc, c->d_u.as<int32_t>(),
-                           (long)count, N, theta);
+        hipLaunchKernelGGL(mk_extract_at_kernel, dim3((unsigned)jobs, (unsigned)theta), dim3(256), 0, c->stream, (const int64_t *)acc, c->d_u.as<int32_t>(),
+                           (long)jobs, N, theta);
     }
-    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
-    if (d_dst) THFHE_TRY(mk_keyswitch(c, c->d_u.as<int32_t>(), d_dst, recs));
-    if (c->profiling) {
+    if (ev) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
+    if (ks_dst) THFHE_TRY(mk_keyswitch(c, c->d_u.as<int32_t>(), ks_dst, jobs * (mv ? mv->q : theta)));
+    if (ev) {
         THFHE_HIP(hipEventRecord(c->ev[3], c->stream));
         c->ev_valid = true;
     }
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
-}
-
-// programmable bootstrap of `count` samples: lut prologue, then mk_enqueue_lut_rotation.  The profiling events sit on the
-// boundaries of mk_enqueue_bootstraps: prologue | rotation + extraction | key switch.
-int mk_enqueue_lut(thfhe_mk_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0, const int32_t *d1, const int32_t *d2, size_t count,
-                   const int64_t *d_tv, const int32_t *d_idx, int32_t *d_dst) {
-    int rc = mk_lut_workspace(c, count, sp.theta);
-    if (rc) return rc;
-    if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
-    lut_prologue_launch(LutFlatSrc<LutIdx::none>{d0, d1, d2, sp, 1, nullptr}, count, c->words, c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(),
-                        c->d_barb.as<int32_t>(), nullptr, c->stream);
-    return mk_enqueue_lut_rotation(c, sp.theta, count, d_tv, d_idx, d_dst);
 }
 
 int mk_launch_rotation(thfhe_mk_ctx *c, const MKBRArgs &a) {
@@ -1193,7 +1188,7 @@ int mk_gates_dev_locked(thfhe_mk_ctx *c, int op, const int32_t *d0, const int32_
     if (count == 0) return THFHE_OK;
     if (count > (size_t)INT32_MAX / 4) return thfhe_fail(THFHE_E_INVALID, "count too large");
     THFHE_HIP(hipSetDevice(c->device));
-    const size_t rec = (size_t)c->words + 1, words = count * rec;
+    const size_t rec = c->rec_words(), words = count * rec;
     const unsigned lb = (unsigned)((words + 255) / 256);
     if (op == THFHE_NOT || op == THFHE_COPY) {
         hipLaunchKernelGGL(mk_linear_kernel, dim3(lb), dim3(256), 0, c->stream, d0, d0, dout, words, rec, op == THFHE_NOT ? 1 : 0);
@@ -1238,6 +1233,18 @@ int mk_dag_gate_class(thfhe_mk_ctx *c, int cls, const int32_t *d_ops, size_t n) 
     return mk_gates_dev_locked(c, cls == kDagMux ? THFHE_MUX : THFHE_AND3, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), c->stage.out_ptr(), n);
 }
 
+// dag_execute's ensure: workspace and staging for slices of max_gates gates; theta_max > 0: a run with LUT groups of up to theta_max records per node
+int mk_dag_ensure(thfhe_mk_ctx *c, size_t max_gates, int theta_max, int32_t **in, int32_t **out) {
+    const size_t words = c->rec_words();
+    int r = mk_ensure_workspace(c, 2 * max_gates);
+    if (!r && theta_max) r = mk_lut_workspace(c, max_gates, theta_max);
+    if (!r && theta_max) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
+    if (!r) r = c->stage.grow(max_gates * words);
+    if (!r && theta_max) r = c->stage.out.grow(theta_max * max_gates * words * sizeof(int32_t));   // key switch of nodes x theta records
+    in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
+    return r;
+}
+
 // thfhe_mk_lut_bootstrap (keyswitch) / thfhe_mk_lut_bootstrap_wo_keyswitch: out = count x theta records of P n + 1 (resp. N + 1) words
 int mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
                      const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch) {
@@ -1246,7 +1253,7 @@ int mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *t
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     if (count == 0) return THFHE_OK;
     const thfhe_lut_spec s = *sp;
-    const size_t rec = (size_t)c->words + 1, in_words = count * rec, outs = count * s.theta, N = c->p.N;
+    const size_t rec = c->rec_words(), in_words = count * rec, outs = count * s.theta, N = c->p.N;
     const size_t in_bytes = in_words * sizeof(int32_t);
     const size_t out_bytes = outs * (keyswitch ? rec : N + 1) * sizeof(int32_t);
     const size_t stage_words = keyswitch ? outs * rec : in_words;   // the key switch writes count x theta records into stage.out
@@ -1256,8 +1263,9 @@ int mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *t
         if (r) return r;
         THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv, (size_t)n_luts * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
         if (lut_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), lut_index, count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        return mk_enqueue_lut(c, s, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), count, c->d_tv.as<int64_t>(),
-                              lut_index ? c->d_lut_idx.as<int32_t>() : nullptr, keyswitch ? c->stage.out_ptr() : nullptr);
+        THFHE_TRY(mk_lut_workspace(c, count, s.theta));
+        return mk_enqueue_pbs(c, LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, count, c->d_tv.as<int64_t>(),
+                              s.theta, lut_index ? c->d_lut_idx.as<int32_t>() : nullptr, keyswitch ? c->stage.out_ptr() : nullptr, true);
     }, keyswitch ? c->stage.out : c->d_u, out, out_bytes);
 }
 
@@ -1274,7 +1282,7 @@ int mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
     const thfhe_lut_spec s = *sp;
-    const size_t words = (size_t)c->words + 1, N = c->p.N, rec = keyswitch ? words : N + 1;
+    const size_t words = c->rec_words(), N = c->p.N;
     const size_t S_max = std::min(count, std::max<size_t>(1, c->mv_slice / q));
     const size_t w_bytes = (size_t)n_tables * q * p * sizeof(int32_t);
     int rc = mk_lut_workspace(c, S_max, q);
@@ -1283,33 +1291,21 @@ int mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t
     if (!rc) rc = c->d_mv_w.grow(w_bytes);
     if (!rc && table_index) rc = c->d_lut_idx.grow(S_max * sizeof(int32_t));
     if (rc) return rc;
-    hipStream_t st = c->stream;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv0, N * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv0, N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, c->stream));
     const MkMvArgs mv{c->d_mv_w.as<int32_t>(), p, q, out_bias};
-    const int32_t *in[3] = {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr};
-    const int32_t *const res = keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>();
-    for (size_t s0 = 0; s0 < count; s0 += S_max) {
-        const size_t S = std::min(S_max, count - s0);
-        for (int k = 0; k < 3; k++)
-            if (in[k]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(k), in[k] + s0 * words, S * words * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        lut_prologue_launch(LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, S, c->words, c->w_pad, c->log2_2n,
-                            c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), nullptr, st);
-        THFHE_TRY(mk_enqueue_lut_rotation(c, 1, S, c->d_tv.as<int64_t>(), table_index ? c->d_lut_idx.as<int32_t>() : nullptr,
-                                          keyswitch ? c->stage.out_ptr() : nullptr, &mv));
-        THFHE_HIP(hipMemcpyAsync(out + s0 * q * rec, res, S * q * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    THFHE_HIP(hipStreamSynchronize(st));
-    return THFHE_OK;
+    int32_t *const d_idx = c->d_lut_idx.as<int32_t>();
+    return ctx_sliced(c, count, S_max, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, table_index, d_idx, [&](size_t S, bool last) {
+        return mk_enqueue_pbs(c, LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, S, c->d_tv.as<int64_t>(), 1,
+                              table_index ? d_idx : nullptr, keyswitch ? c->stage.out_ptr() : nullptr, last, &mv);
+    }, keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>(), out, q * (keyswitch ? words : N + 1));
 }
 
 // The six-column entries of the 3-gen executor (F: the entry's families and the generations it admits): the host checks and the plan before the
-// context is looked at, then the run.  The gate classes run as in thfhe_mk_dag_run_batch; a LUT launch group runs the fused prologue
-// (lut_prologue_kernel on the wire table, over the P n + 1 record words), then mk_enqueue_lut_rotation with the key switch into the staging output
-// (DESIGN 4.9).  An MV group is the same with the multi-value epilogue: one base vector per launch, the table per job, q records per
-// node scattered into consecutive wires, in slices of at most dag_slice nodes and mv_slice / q of them.
+// context is looked at, then the run.  The gate classes run as in thfhe_mk_dag_run_batch; a LUT launch group is one PBS stage on the wire table
+// (lut_prologue_kernel over the P n + 1 record words) with the key switch into the staging output.  An MV group is the
+// same with the multi-value epilogue: one base vector per launch, the table per job, q records per node scattered into consecutive wires, in
+// slices of at most dag_slice nodes and mv_slice / q of them.  No stage of a run records profiling events.
 int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const int64_t *mv_out_bias, size_t instances, int64_t *stats) {
     DagPlan plan;
     THFHE_TRY(dag_checked_plan(A, F, mk_dag_classify, plan));
@@ -1319,7 +1315,7 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
     if (stats && !mv_entry) plan.fill_stats(stats);   // thfhe_mk_dag_run_lut_batch gives them to a caller with a context only
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
-    const int words = c->words + 1, theta_max = plan.max_theta;
+    const int words = c->rec_words();
     const size_t N = c->p.N;
     hipStream_t st = c->stream;
     auto mv_slice_of = [&](int mv, size_t all) { return std::min({all, c->dag_slice, std::max<size_t>(1, c->mv_slice / (size_t)F.mvs[mv].q)}); };
@@ -1330,50 +1326,26 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
         THFHE_TRY(c->d_lut_idx.grow(S * sizeof(int32_t)));
         THFHE_TRY(c->stage.out.grow(S * q * words * sizeof(int32_t)));
     }
-    auto upload = [&](DevBuf &d, const void *h, size_t bytes) -> int {   // the run's tables and specs, once per call
-        if (!bytes) return THFHE_OK;
-        THFHE_TRY(d.grow(bytes));
-        THFHE_HIP(hipMemcpyAsync(d.as<void>(), h, bytes, hipMemcpyHostToDevice, st));
-        return THFHE_OK;
-    };
-    THFHE_TRY(upload(c->d_tv, F.tv, (size_t)F.n_luts * N * sizeof(int64_t)));
-    THFHE_TRY(upload(c->dag.specs, F.specs, (size_t)F.n_specs * sizeof(thfhe_lut_spec)));
-    THFHE_TRY(upload(c->d_dag_mv_tv0, F.mv_tv0, (size_t)F.n_bases * N * sizeof(int64_t)));
-    THFHE_TRY(upload(c->d_dag_mv_w, F.mv_factors, F.n_factor_words * sizeof(int32_t)));
-    const unsigned wb = (unsigned)((words + 255) / 256);
+    THFHE_TRY(dag_upload(c->d_tv, st, F.tv, (size_t)F.n_luts * N * sizeof(int64_t)));
+    THFHE_TRY(dag_upload(c->dag.specs, st, F.specs, (size_t)F.n_specs * sizeof(thfhe_lut_spec)));
+    THFHE_TRY(dag_upload(c->d_dag_mv_tv0, st, F.mv_tv0, (size_t)F.n_bases * N * sizeof(int64_t)));
+    THFHE_TRY(dag_upload(c->d_dag_mv_w, st, F.mv_factors, F.n_factor_words * sizeof(int32_t)));
     return dag_execute(
         plan, c->dag, st, words, A, instances, c->dag_slice,
-        [&](size_t max_gates, int32_t **in, int32_t **out) {
-            int r = mk_ensure_workspace(c, 2 * max_gates);
-            if (!r) r = mk_lut_workspace(c, max_gates, theta_max);
-            if (!r) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
-            if (!r) r = c->stage.grow(max_gates * words);
-            if (!r) r = c->stage.out.grow(theta_max * max_gates * words * sizeof(int32_t));   // key switch of nodes x theta records
-            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
-            return r;
-        },
+        [&](size_t max_gates, int32_t **in, int32_t **out) { return mk_dag_ensure(c, max_gates, plan.max_theta, in, out); },
         [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); },
         [&](int theta, const DagLutSlice &s) {
-            lut_prologue_launch(s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, c->words, c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(),
-                                c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>(), st);
-            return mk_enqueue_lut_rotation(c, theta, (size_t)s.total, c->d_tv.as<int64_t>(), c->d_lut_idx.as<int32_t>(), c->stage.out_ptr());
+            return mk_enqueue_pbs(c, s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, c->d_tv.as<int64_t>(), theta, nullptr, c->stage.out_ptr());
         },
         [&](const DagExtGroup &g) -> int {   // the plan of this engine holds no other grouped kind; t_y = each node's table
             if (g.cls != kDagMv) return thfhe_fail(THFHE_E_INVALID, "grouped node kind not defined for the 3-gen engine");
             const thfhe_mv_spec m = F.mvs[g.tree];
             const int64_t *const tv0 = c->d_dag_mv_tv0.as<int64_t>() + (size_t)m.base * N;
             const MkMvArgs mv{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p, m.q, mv_out_bias ? mv_out_bias[g.tree] : 0};
-            const long slice = (long)mv_slice_of(g.tree, (size_t)g.all);
-            for (long first = 0; first < g.all; first += slice) {
-                const long S = std::min(slice, g.all - first);
-                lut_prologue_launch(LutWireSrc<LutSpecByValue, LutIdx::table>{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1}, (size_t)S, c->words,
-                                    c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_lut_idx.as<int32_t>(), st);
-                THFHE_TRY(mk_enqueue_lut_rotation(c, 1, (size_t)S, tv0, c->d_lut_idx.as<int32_t>(), c->stage.out_ptr(), &mv));
-                hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(S * m.q), wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires, first,
-                                   S, g.cnt, g.n_wires, words, m.q);
-                THFHE_HIP(hipGetLastError());
-            }
-            return (int)THFHE_OK;
+            return dag_group_slices(g, mv_slice_of(g.tree, (size_t)g.all), m.q, c->stage.out_ptr(), words, st, [&](long first, long S) {
+                const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
+                return mk_enqueue_pbs(c, lo, (size_t)S, tv0, 1, nullptr, c->stage.out_ptr(), false, &mv);
+            });
         });
 }
 
@@ -1474,12 +1446,9 @@ int thfhe_mk_gates_dev(thfhe_mk_ctx *c, int op, const int32_t *d0, const int32_t
 }
 
 int thfhe_mk_gates(thfhe_mk_ctx *c, int op, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count) {
-    if (!c || !in0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    if (count == 0) return THFHE_OK;
-    const size_t words = count * ((size_t)c->words + 1), bytes = words * sizeof(int32_t);
-    return ctx_staged(c, words, {in0, in1, in2}, {bytes, bytes, bytes}, [&] {
-        return mk_gates_dev_locked(c, op, c->stage.in_ptr(0), in1 ? c->stage.in_ptr(1) : nullptr, in2 ? c->stage.in_ptr(2) : nullptr, c->stage.out_ptr(), count);
-    }, c->stage.out, out, bytes);
+    return ctx_gates(c, in0, in1, in2, out, count, [&](const int32_t *d0, const int32_t *d1, const int32_t *d2, int32_t *dout, size_t n) {
+        return mk_gates_dev_locked(c, op, d0, d1, d2, dout, n);
+    });
 }
 
 // Gate-DAG evaluation for the 3-gen scheme: the reference's integer circuits (mk_add_3gen ... mk_int_mul_3gen, J/3gen_mk_gates.jl:183-362) as
@@ -1488,22 +1457,9 @@ int thfhe_mk_gates(thfhe_mk_ctx *c, int op, const int32_t *in0, const int32_t *i
 // mk_copy_3gen: no bootstrap).
 int thfhe_mk_dag_run_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *gates, size_t n_gates, size_t instances,
                            const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
-    if (!c || (!inputs && n_inputs) || (!gates && n_gates) || (!outputs && n_gates) || (!out_wires && n_out)) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    const DagCall A{inputs, n_inputs, gates, n_gates, out_wires, n_out, outputs};
-    DagPlan plan;
-    THFHE_TRY(dag_plan(A, DagFamilies{}, mk_dag_classify, plan));
-    if (stats) plan.fill_stats(stats);
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    const int words = c->words + 1;
-    return dag_execute(
-        plan, c->dag, c->stream, words, A, instances, c->dag_slice,
-        [&](size_t max_gates, int32_t **in, int32_t **out) {
-            int r = mk_ensure_workspace(c, 2 * max_gates);
-            if (!r) r = c->stage.grow(max_gates * words);
-            in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
-            return r;
-        },
+    return dag_gates_run_batch(
+        c, DagCall{inputs, n_inputs, gates, n_gates, out_wires, n_out, outputs}, instances, stats, mk_dag_classify,
+        [&](size_t max_gates, int32_t **in, int32_t **out) { return mk_dag_ensure(c, max_gates, 0, in, out); },
         [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); });
 }
 
@@ -1537,8 +1493,7 @@ int thfhe_mk_set_mv_slice(thfhe_mk_ctx *c, size_t max_records) {
 }
 
 int thfhe_mk_dag_run(thfhe_mk_ctx *c, int32_t *wires, size_t n_inputs, const int32_t *gates, size_t n_gates, int64_t *stats) {
-    if (!wires) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    return thfhe_mk_dag_run_batch(c, wires, n_inputs, gates, n_gates, 1, nullptr, 0, wires + n_inputs * (size_t)(c ? c->words + 1 : 0), stats);
+    return dag_gates_run(c, wires, n_inputs, gates, n_gates, stats, thfhe_mk_dag_run_batch);
 }
 
 int thfhe_mk_gates_mixed(thfhe_mk_ctx *c, const int32_t *ops, const int32_t *in0, const int32_t *in1, int32_t *out, size_t count) {
@@ -1547,13 +1502,12 @@ int thfhe_mk_gates_mixed(thfhe_mk_ctx *c, const int32_t *ops, const int32_t *in0
     for (size_t g = 0; g < count; g++)
         if (!(ops[g] == THFHE_NAND || ops[g] == THFHE_OR || ops[g] == THFHE_AND || ops[g] == THFHE_XOR))
             return thfhe_fail(THFHE_E_INVALID, "thfhe_mk_gates_mixed takes the two-input 3-gen gates NAND / OR / AND / XOR only");
-    const size_t words = count * ((size_t)c->words + 1), bytes = words * sizeof(int32_t);
     MKLin L;
     mk_gate_lin(THFHE_NAND, 0, L);
-    return ctx_staged(c, words, {in0, in1, ops}, {bytes, bytes, count * sizeof(int32_t)}, [&] {   // staging buffer 2 holds the opcodes
+    return ctx_gates_mixed(c, ops, in0, in1, out, count, [&](const int32_t *d0, const int32_t *d1, const int32_t *d_ops, int32_t *dout) {
         int rc = mk_ensure_workspace(c, count);
-        return rc ? rc : mk_enqueue_bootstraps(c, c->stage.in_ptr(0), c->stage.in_ptr(1), nullptr, L, L, 1, count, (int64_t)1 << 61, c->stage.out_ptr(), c->stage.in_ptr(2));
-    }, c->stage.out, out, bytes);
+        return rc ? rc : mk_enqueue_bootstraps(c, d0, d1, nullptr, L, L, 1, count, (int64_t)1 << 61, dout, d_ops);
+    });
 }
 
 // ---- party-sharded building blocks (device pointers; see include/thfhe_hip.h and thfhe/party_sharded.py) -------------------
@@ -1621,7 +1575,7 @@ int thfhe_mk_keyswitch_dev(thfhe_mk_ctx *c, const int32_t *d_u, int32_t *d_out, 
 int thfhe_mk_bootstrap(thfhe_mk_ctx *c, int64_t mu, const int32_t *x, int32_t *out, size_t count) {
     if (!c || !x || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    const size_t words = count * ((size_t)c->words + 1), bytes = words * sizeof(int32_t);
+    const size_t words = count * c->rec_words(), bytes = words * sizeof(int32_t);
     MKLin L;
     mk_gate_lin(kOpIdentity, 0, L);
     return ctx_staged(c, words, {x, nullptr, nullptr}, {bytes, 0, 0}, [&] {

@@ -522,6 +522,7 @@ __global__ __launch_bounds__(256) void sk_linear_kernel(const int32_t *__restric
 // ======================================================================================================
 struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     thfhe_params p;
+    int rec_words() const { return p.n + 1; }
     DevBuf d_bk;              // spectral key
     KsKey ksk;                // padded rows (+ the matrix-core planes)
     int coop_max_jobs = 768;    // remainders (batch mod 2048) up to this many rotations use the cooperative (latency) kernel
@@ -731,7 +732,7 @@ int gates_dev_locked(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1,
     if (count > (size_t)INT32_MAX / 4) return thfhe_fail(THFHE_E_INVALID, "count too large");
     THFHE_HIP(hipSetDevice(c->device));
     if (op == THFHE_NOT || op == THFHE_COPY) {
-        const size_t words = count * (c->p.n + 1);
+        const size_t words = count * c->rec_words();
         hipLaunchKernelGGL(sk_linear_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, d0, dout, words,
                            op == THFHE_NOT ? 1 : 0);
         THFHE_HIP(hipGetLastError());
@@ -766,10 +767,10 @@ int lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv, int
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     if (count == 0) return THFHE_OK;
     const thfhe_lut_spec s = *sp;
-    const size_t in_words = count * (c->p.n + 1), outs = count * s.theta;
+    const size_t in_words = count * c->rec_words(), outs = count * s.theta;
     const size_t in_bytes = in_words * sizeof(int32_t);
-    const size_t out_bytes = outs * (keyswitch ? c->p.n + 1 : c->p.N + 1) * sizeof(int32_t);
-    const size_t stage_words = keyswitch ? outs * (c->p.n + 1) : in_words;   // the key switch writes count x theta records into stage.out
+    const size_t out_bytes = outs * (keyswitch ? c->rec_words() : c->p.N + 1) * sizeof(int32_t);
+    const size_t stage_words = keyswitch ? outs * c->rec_words() : in_words;   // the key switch writes count x theta records into stage.out
     return ctx_staged(c, stage_words, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, {in_bytes, in_bytes, in_bytes}, [&] {
         int r = c->d_tv.grow((size_t)n_luts * 1024 * sizeof(int32_t));
         if (!r && enc) r = c->d_tva.grow((size_t)n_luts * 1024 * sizeof(int32_t));
@@ -792,7 +793,7 @@ int tree_workspace(thfhe_ctx *c, size_t S, size_t p, size_t R, size_t theta_lo, 
     int rc = ensure_workspace(c, jobs);
     if (!rc) rc = c->d_u.grow(std::max(S * R * theta_lo, S * k) * 1025 * sizeof(int32_t));
     if (!rc) rc = c->d_lut_idx.grow(jobs * sizeof(int32_t));
-    if (!rc) rc = c->d_tree_lwe.grow(S * k * p * (c->p.n + 1) * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_lwe.grow(S * k * p * c->rec_words() * sizeof(int32_t));
     if (!rc) rc = c->d_tree_a.grow(S * k * 1024 * sizeof(int32_t));
     if (!rc) rc = c->d_tree_b.grow(S * k * 1024 * sizeof(int32_t));
     return rc;
@@ -823,7 +824,7 @@ int sk_dag_classify(int op) { return op == THFHE_NOT || op == THFHE_COPY ? kDagL
 
 // dag_execute's ensure: workspace and staging for slices of max_gates gates; theta_max > 0: a run with LUT groups of up to theta_max records per node
 int sk_dag_ensure(thfhe_ctx *c, size_t max_gates, int theta_max, int32_t **in, int32_t **out) {
-    const size_t words = c->p.n + 1;
+    const size_t words = c->rec_words();
     int r = ensure_workspace(c, 2 * max_gates);
     if (!r && theta_max) r = c->d_u.grow(theta_max * max_gates * 1025 * sizeof(int32_t));
     if (!r && theta_max) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
@@ -845,7 +846,7 @@ int sk_dag_lhe_group(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, cons
 // one multi-value PBS stage on the wire table, its q records per node scattered into consecutive wires; a TREE_MV group the k-table chain with both
 // prologues on the wire table.  A leveled group is sk_dag_lhe_group's.  Everything is enqueued on the gate context's stream.
 int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const DagFamilies &T, const DagCall &A, size_t instances) {
-    const int words = c->p.n + 1;
+    const int words = c->rec_words();
     hipStream_t st = c->stream;
     // a slice of a SELECT / TREE group: at most dag_slice nodes over all instances and at most tree_slice / p_hi of them
     const size_t dag_slice = c->dag_slice, tree_slice = c->tree_slice;
@@ -880,68 +881,46 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
         THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle; from here on its buffers are used on `st`
     }
     // the run's tables and specs, once per call
-    auto upload = [&](DevBuf &d, const void *h, size_t bytes) -> int {
-        if (!bytes) return THFHE_OK;
-        THFHE_TRY(d.grow(bytes));
-        THFHE_HIP(hipMemcpyAsync(d.as<void>(), h, bytes, hipMemcpyHostToDevice, st));
-        return THFHE_OK;
-    };
-    THFHE_TRY(upload(c->d_tv, T.tv, (size_t)T.n_luts * 1024 * sizeof(int32_t)));
-    THFHE_TRY(upload(c->dag.specs, T.specs, (size_t)T.n_specs * sizeof(thfhe_lut_spec)));
-    THFHE_TRY(upload(c->d_dag_enc_a, T.enc_a, (size_t)T.n_enc * 1024 * sizeof(int32_t)));
-    THFHE_TRY(upload(c->d_dag_enc_b, T.enc_b, (size_t)T.n_enc * 1024 * sizeof(int32_t)));
-    THFHE_TRY(upload(c->d_dag_tv1, T.tv1, (size_t)T.n_tv1_rows * 1024 * sizeof(int32_t)));
-    THFHE_TRY(upload(c->d_dag_mv_tv0, T.mv_tv0, (size_t)T.n_bases * 1024 * sizeof(int32_t)));
-    THFHE_TRY(upload(c->d_dag_mv_w, T.mv_factors, T.n_factor_words * sizeof(int32_t)));
-    const unsigned wb = (unsigned)((words + 255) / 256);
+    THFHE_TRY(dag_upload(c->d_tv, st, T.tv, (size_t)T.n_luts * 1024 * sizeof(int32_t)));
+    THFHE_TRY(dag_upload(c->dag.specs, st, T.specs, (size_t)T.n_specs * sizeof(thfhe_lut_spec)));
+    THFHE_TRY(dag_upload(c->d_dag_enc_a, st, T.enc_a, (size_t)T.n_enc * 1024 * sizeof(int32_t)));
+    THFHE_TRY(dag_upload(c->d_dag_enc_b, st, T.enc_b, (size_t)T.n_enc * 1024 * sizeof(int32_t)));
+    THFHE_TRY(dag_upload(c->d_dag_tv1, st, T.tv1, (size_t)T.n_tv1_rows * 1024 * sizeof(int32_t)));
+    THFHE_TRY(dag_upload(c->d_dag_mv_tv0, st, T.mv_tv0, (size_t)T.n_bases * 1024 * sizeof(int32_t)));
+    THFHE_TRY(dag_upload(c->d_dag_mv_w, st, T.mv_factors, T.n_factor_words * sizeof(int32_t)));
     // one SELECT / TREE / MV / TREE_MV / leveled group of a level
     auto ext_group = [&](const DagExtGroup &g) -> int {
         auto no_seam = [](int) { return (int)THFHE_OK; };
+        int32_t *const dst = c->stage.out_ptr();
         if (g.cls >= kDagLheLookup) return sk_dag_lhe_group(c, pc, plan, T, g, instances);
         if (g.cls == kDagMv || g.cls == kDagTreeMv) {   // t_y = each node's table
             const thfhe_mv_spec m = T.mvs[g.tree];
             const bool is_tree = g.cls == kDagTreeMv;
-            const int outs = is_tree ? m.k : m.q, hi0 = m.lo.n_inputs;
+            const int hi0 = m.lo.n_inputs;
             const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};
             const int32_t *const tv0 = c->d_dag_mv_tv0.as<int32_t>() + (size_t)m.base * 1024;
             const MvArgs mv{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p};
-            const long slice = (long)mv_slice_of(g.tree, (size_t)g.all);
-            for (long first = 0; first < g.all; first += slice) {
-                const long S = std::min(slice, g.all - first);
+            return dag_group_slices(g, mv_slice_of(g.tree, (size_t)g.all), is_tree ? m.k : m.q, dst, words, st, [&](long first, long S) {
                 const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
-                if (is_tree) {
-                    const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
-                    THFHE_TRY(enqueue_tree_chain(c, pc, lo, tv0, m.k * m.q, hi, (size_t)S, m.q, c->stage.out_ptr(), no_seam, &mv, (size_t)m.k));
-                } else {
-                    THFHE_TRY(enqueue_pbs(c, lo, (size_t)S, tv0, nullptr, m.q, nullptr, c->stage.out_ptr(), false, &mv));
-                }
-                hipLaunchKernelGGL(dag_scatter_theta_kernel, dim3((unsigned)(S * outs), wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires,
-                                   first, S, g.cnt, g.n_wires, words, outs);
-                THFHE_HIP(hipGetLastError());
-            }
-            return (int)THFHE_OK;
+                if (!is_tree) return enqueue_pbs(c, lo, (size_t)S, tv0, nullptr, m.q, nullptr, dst, false, &mv);
+                const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
+                return enqueue_tree_chain(c, pc, lo, tv0, m.k * m.q, hi, (size_t)S, m.q, dst, no_seam, &mv, (size_t)m.k);
+            });
         }
         const thfhe_tree_spec ts = T.trees[g.tree];
         const int p = ts.p_hi, hi0 = g.cls == kDagTree ? ts.lo.n_inputs : 0;
         const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the index operands of a TREE node follow its lo.n_inputs level-1 operands
-        const long slice = (long)slice_of(g.tree, (size_t)g.all);
-        for (long first = 0; first < g.all; first += slice) {
-            const long S = std::min(slice, g.all - first);
+        return dag_group_slices(g, slice_of(g.tree, (size_t)g.all), 1, dst, words, st, [&](long first, long S) {
             const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
             if (g.cls == kDagTree) {   // t_y = row0
                 const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {ts.lo}, g.t_y, first, g.cnt, g.n_wires, p / ts.lo.theta};
-                THFHE_TRY(enqueue_tree_chain(c, pc, lo, c->d_dag_tv1.as<int32_t>(), ts.lo.theta, hi, (size_t)S, p, c->stage.out_ptr(), no_seam));
-            } else {                   // SELECT: t_y = first candidate wire
-                const unsigned gy = (unsigned)std::min<long>(S * p, 65535);
-                hipLaunchKernelGGL(dag_select_gather_kernel, dim3(wb, gy), dim3(256), 0, st, (const int32_t *)g.wires, g.t_y, c->d_tree_lwe.as<int32_t>(), first, S,
-                                   g.cnt, g.n_wires, words, p);
-                THFHE_TRY(enqueue_tree_chain(c, pc, nullptr, nullptr, 1, hi, (size_t)S, p, c->stage.out_ptr(), no_seam));
+                return enqueue_tree_chain(c, pc, lo, c->d_dag_tv1.as<int32_t>(), ts.lo.theta, hi, (size_t)S, p, dst, no_seam);
             }
-            hipLaunchKernelGGL(dag_scatter_kernel, dim3((unsigned)S, wb), dim3(256), 0, st, (const int32_t *)c->stage.out_ptr(), g.t_out, g.wires, first, S, g.cnt,
-                               g.n_wires, words);
-            THFHE_HIP(hipGetLastError());
-        }
-        return (int)THFHE_OK;
+            // SELECT: t_y = first candidate wire
+            hipLaunchKernelGGL(dag_select_gather_kernel, dim3((unsigned)((words + 255) / 256), (unsigned)std::min<long>(S * p, 65535)), dim3(256), 0, st,
+                               (const int32_t *)g.wires, g.t_y, c->d_tree_lwe.as<int32_t>(), first, S, g.cnt, g.n_wires, words, p);
+            return enqueue_tree_chain(c, pc, nullptr, nullptr, 1, hi, (size_t)S, p, dst, no_seam);
+        });
     };
     c->grp_valid = false;
     return dag_execute(
@@ -1001,7 +980,7 @@ int tree_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec &lo, c
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
     std::lock_guard<std::mutex> pg(pack_ctx_mutex(pc));   // always after the gate context's: nothing else takes both
-    const int n = c->p.n, words = n + 1;
+    const int n = c->p.n, words = c->rec_words();
     if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
     if (pack_key_n(pc) != n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
     if (count == 0) return THFHE_OK;
@@ -1063,7 +1042,7 @@ int mv_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv0,
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
     const thfhe_lut_spec s = *sp;
-    const size_t words = c->p.n + 1, rec = keyswitch ? words : (size_t)c->p.N + 1;
+    const size_t words = c->rec_words();
     const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / q));
     const size_t w_bytes = (size_t)n_tables * q * p * sizeof(int32_t);
     int rc = ensure_workspace(c, S_max);
@@ -1073,23 +1052,14 @@ int mv_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv0,
     if (!rc) rc = c->d_mv_w.grow(w_bytes);
     if (!rc && table_index) rc = c->d_lut_idx.grow(S_max * sizeof(int32_t));
     if (rc) return rc;
-    hipStream_t st = c->stream;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv0, 1024 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv0, 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, c->stream));
     const MvArgs mv{c->d_mv_w.as<int32_t>(), p};
-    const int32_t *in[3] = {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr};
-    int32_t *const res = keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>();
-    for (size_t s0 = 0; s0 < count; s0 += S_max) {
-        const size_t S = std::min(S_max, count - s0);
-        for (int k = 0; k < 3; k++)
-            if (in[k]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(k), in[k] + s0 * words, S * words * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        THFHE_TRY(enqueue_pbs(c, LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, S, c->d_tv.as<int32_t>(),
-                              nullptr, q, table_index ? c->d_lut_idx.as<int32_t>() : nullptr, keyswitch ? c->stage.out_ptr() : nullptr, s0 + S == count, &mv));
-        THFHE_HIP(hipMemcpyAsync(out + s0 * q * rec, res, S * q * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    THFHE_HIP(hipStreamSynchronize(st));
-    return THFHE_OK;
+    int32_t *const d_idx = c->d_lut_idx.as<int32_t>();
+    return ctx_sliced(c, count, S_max, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, table_index, d_idx, [&](size_t S, bool last) {
+        return enqueue_pbs(c, LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, S, c->d_tv.as<int32_t>(), nullptr, q,
+                           table_index ? d_idx : nullptr, keyswitch ? c->stage.out_ptr() : nullptr, last, &mv);
+    }, keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>(), out, q * (keyswitch ? words : (size_t)c->p.N + 1));
 }
 
 // What the six-column entries share (T: the entry's families and the generations of node kinds it admits): the host checks and the plan, the two
@@ -1227,12 +1197,9 @@ int thfhe_gates_dev(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1, 
 }
 
 int thfhe_gates(thfhe_ctx *c, int op, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count) {
-    if (!c || !in0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    if (count == 0) return THFHE_OK;
-    const size_t words = count * (c->p.n + 1), bytes = words * sizeof(int32_t);
-    return ctx_staged(c, words, {in0, in1, in2}, {bytes, bytes, bytes}, [&] {
-        return gates_dev_locked(c, op, c->stage.in_ptr(0), in1 ? c->stage.in_ptr(1) : nullptr, in2 ? c->stage.in_ptr(2) : nullptr, c->stage.out_ptr(), count);
-    }, c->stage.out, out, bytes);
+    return ctx_gates(c, in0, in1, in2, out, count, [&](const int32_t *d0, const int32_t *d1, const int32_t *d2, int32_t *dout, size_t n) {
+        return gates_dev_locked(c, op, d0, d1, d2, dout, n);
+    });
 }
 
 int thfhe_gates_mixed(thfhe_ctx *c, const int32_t *ops, const int32_t *in0, const int32_t *in1, int32_t *out, size_t count) {
@@ -1240,11 +1207,10 @@ int thfhe_gates_mixed(thfhe_ctx *c, const int32_t *ops, const int32_t *in0, cons
     if (count == 0) return THFHE_OK;
     for (size_t g = 0; g < count; g++)
         if (ops[g] < THFHE_NAND || ops[g] > THFHE_ORYN) return thfhe_fail(THFHE_E_INVALID, "thfhe_gates_mixed takes two-input bootstrapped gates only");
-    const size_t words = count * (c->p.n + 1), bytes = words * sizeof(int32_t);
-    return ctx_staged(c, words, {in0, in1, ops}, {bytes, bytes, count * sizeof(int32_t)}, [&] {   // staging buffer 2 holds the opcodes
-        int rc = enqueue_rotations(c, THFHE_NAND, c->stage.in_ptr(0), c->stage.in_ptr(1), nullptr, count, 1, 1 << 29, c->stage.in_ptr(2));
-        return rc ? rc : enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), count, 1, true);
-    }, c->stage.out, out, bytes);
+    return ctx_gates_mixed(c, ops, in0, in1, out, count, [&](const int32_t *d0, const int32_t *d1, const int32_t *d_ops, int32_t *dout) {
+        int rc = enqueue_rotations(c, THFHE_NAND, d0, d1, nullptr, count, 1, 1 << 29, d_ops);
+        return rc ? rc : enqueue_keyswitch(c, c->d_u.as<int32_t>(), dout, count, 1, true);
+    });
 }
 
 // Gate-DAG evaluation: ASAP levelising scheduler (thfhe_dag.h) + device-resident executor.  The reference's
@@ -1253,15 +1219,8 @@ int thfhe_gates_mixed(thfhe_ctx *c, const int32_t *ops, const int32_t *in0, cons
 // the host between levels.
 int thfhe_dag_run_batch(thfhe_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *gates, size_t n_gates, size_t instances,
                         const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
-    if (!c || (!inputs && n_inputs) || (!gates && n_gates) || (!outputs && n_gates) || (!out_wires && n_out)) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    const DagCall A{inputs, n_inputs, gates, n_gates, out_wires, n_out, outputs};
-    DagPlan plan;
-    THFHE_TRY(dag_plan(A, DagFamilies{}, sk_dag_classify, plan));
-    if (stats) plan.fill_stats(stats);
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    return dag_execute(
-        plan, c->dag, c->stream, c->p.n + 1, A, instances, c->dag_slice,
+    return dag_gates_run_batch(
+        c, DagCall{inputs, n_inputs, gates, n_gates, out_wires, n_out, outputs}, instances, stats, sk_dag_classify,
         [&](size_t max_gates, int32_t **in, int32_t **out) { return sk_dag_ensure(c, max_gates, 0, in, out); },
         [&](int cls, const int32_t *d_ops, size_t n) { return dag_gate_class(c, cls, d_ops, n); });
 }
@@ -1309,14 +1268,13 @@ int thfhe_dag_run_lhe_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inp
 int thfhe_set_dag_slice(thfhe_ctx *c, size_t max_gates) { return ctx_set_dag_slice(c, max_gates); }
 
 int thfhe_dag_run(thfhe_ctx *c, int32_t *wires, size_t n_inputs, const int32_t *gates, size_t n_gates, int64_t *stats) {
-    if (!wires) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    return thfhe_dag_run_batch(c, wires, n_inputs, gates, n_gates, 1, nullptr, 0, wires + n_inputs * (size_t)(c ? c->p.n + 1 : 0), stats);
+    return dag_gates_run(c, wires, n_inputs, gates, n_gates, stats, thfhe_dag_run_batch);
 }
 
 int thfhe_bootstrap_wo_keyswitch(thfhe_ctx *c, int32_t mu, const int32_t *x, int32_t *out_N1, size_t count) {
     if (!c || !x || !out_N1) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    const size_t words = count * (c->p.n + 1);
+    const size_t words = count * c->rec_words();
     return ctx_staged(c, words, {x, nullptr, nullptr}, {words * sizeof(int32_t), 0, 0}, [&] {
         return enqueue_rotations(c, kOpIdentity, c->stage.in_ptr(0), c->stage.in_ptr(0), nullptr, count, 1, mu);
     }, c->d_u, out_N1, count * 1025 * sizeof(int32_t));
@@ -1325,7 +1283,7 @@ int thfhe_bootstrap_wo_keyswitch(thfhe_ctx *c, int32_t mu, const int32_t *x, int
 int thfhe_bootstrap(thfhe_ctx *c, int32_t mu, const int32_t *x, int32_t *out, size_t count) {
     if (!c || !x || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
     if (count == 0) return THFHE_OK;
-    const size_t words = count * (c->p.n + 1);
+    const size_t words = count * c->rec_words();
     return ctx_staged(c, words, {x, nullptr, nullptr}, {words * sizeof(int32_t), 0, 0}, [&] {
         int rc = enqueue_rotations(c, kOpIdentity, c->stage.in_ptr(0), c->stage.in_ptr(0), nullptr, count, 1, mu);
         return rc ? rc : enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), count, 1, false);
@@ -1415,12 +1373,12 @@ int thfhe_keyswitch(thfhe_ctx *c, const int32_t *in_N1, int32_t *out, size_t cou
     if (lk.rc) return lk.rc;
     int rc = ensure_workspace(c, count);
     if (rc) return rc;
-    rc = c->stage.grow(count * (c->p.n + 1));
+    rc = c->stage.grow(count * c->rec_words());
     if (rc) return rc;
     THFHE_HIP(hipMemcpyAsync(c->d_u.as<int32_t>(), in_N1, count * 1025 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     rc = enqueue_keyswitch(c, c->d_u.as<int32_t>(), c->stage.out_ptr(), count, 1, false);
     if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(out, c->stage.out_ptr(), count * (c->p.n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    THFHE_HIP(hipMemcpyAsync(out, c->stage.out_ptr(), count * c->rec_words() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }

@@ -392,6 +392,26 @@ def _same_count(x, *others):
             raise ValueError(f"operand batches differ in length: {x.shape[0]} vs {o.shape[0]} records")
 
 
+def _index(name, v, count):
+    """A per-sample index (lut_index, table_index, val_index) as int32[count]; None stays None."""
+    if v is None:
+        return None
+    v = np.ascontiguousarray(v, np.int32).reshape(-1)
+    if v.shape[0] != count:
+        raise ValueError(f"{name} holds {v.shape[0]} entries for {count} samples")
+    return v
+
+
+def _as_tuple(v):
+    """The operands of one tree level, one record array or a tuple of 1 .. 3, as a 3-tuple padded with None."""
+    return tuple(v) + (None,) * (3 - len(v)) if isinstance(v, (tuple, list)) else (v, None, None)
+
+
+def _theta_records(theta):
+    """Records per sample of the output array: theta, or 1 for a theta the library is going to refuse."""
+    return int(theta) if theta in (1, 2, 4) else 1
+
+
 class DeviceBuffer:
     """A device allocation owned by a context (records resident in HBM)."""
 
@@ -507,7 +527,7 @@ class _EvalKey(_Handle):
         def families():
             sp = (LutSpec * len(specs))(*[_lut_spec(s) for s in specs])
             t = np.ascontiguousarray(tv, self._tv_dtype).reshape(-1, self.params.N)
-            return sp, len(specs), t.ctypes.data_as(_i64p if self._tv_dtype == np.int64 else _i32p), t.shape[0]
+            return sp, len(specs), self._ptv(t), t.shape[0]
         return self._dag_run("dag_run_lut_batch", self._fn("dag_run_lut_batch"), (self.h,), input_records, nodes, 6, families, out_wires)
 
     def _bootstrap(self, x, mu):
@@ -530,38 +550,52 @@ class _EvalKey(_Handle):
 
     _tv_dtype = np.int32   # the ring's torus: Torus32 test vectors (MKCloudKey: Torus64)
 
+    def _ptv(self, a):
+        return a.ctypes.data_as(_i64p if self._tv_dtype == np.int64 else _i32p)
+
     def _lut(self, tv, x, y, z, weights, bias, theta, lut_index, keyswitch):
-        given = [v for v in (x, y, z) if v is not None]
-        if any(v is None for v in (x, y, z)[:len(given)]) or len(given) != len(weights):
-            raise ValueError("give the inputs in order (x, then y, then z) and one weight per input")
-        ins = [_rec(v, self.words) for v in given]
-        _same_count(*ins)
+        ins, spec, p = self._lut_args((x, y, z), weights, bias, theta)
         tv = np.ascontiguousarray(tv, self._tv_dtype).reshape(-1, self.params.N)
         count = ins[0].shape[0]
-        idx = None
-        if lut_index is not None:
-            idx = np.ascontiguousarray(lut_index, np.int32).reshape(-1)
-            if idx.shape[0] != count:
-                raise ValueError(f"lut_index holds {idx.shape[0]} entries for {count} samples")
-        w = list(weights) + [0] * (3 - len(weights))
-        spec = LutSpec(len(ins), (C.c_int32 * 3)(*[_wrap32(v) for v in w]), _wrap32(bias), int(theta))
-        words = self.words if keyswitch else self.params.N + 1
-        out = np.empty((count, int(theta) if theta in (1, 2, 4) else 1, words), np.int32)
+        idx = _index("lut_index", lut_index, count)
+        out = np.empty((count, _theta_records(theta), self.words if keyswitch else self.params.N + 1), np.int32)
         fn = self._fn("lut_bootstrap" if keyswitch else "lut_bootstrap_wo_keyswitch")
-        p = [_p32(v) for v in ins] + [None] * (3 - len(ins))
-        ptv = tv.ctypes.data_as(_i64p if self._tv_dtype == np.int64 else _i32p)
-        _check(fn(self.h, C.byref(spec), ptv, tv.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
+        _check(fn(self.h, C.byref(spec), self._ptv(tv), tv.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
         return out
 
-    def _lut_args(self, ins, weights, bias, theta, what):
+    def _lut_args(self, ins, weights, bias, theta, what=None):
+        """(records, LutSpec, the three operand pointers) of the operands `ins` = (x, y, z); what: the call, named in front of the error text."""
         given = [v for v in ins if v is not None]
         if any(v is None for v in ins[:len(given)]) or len(given) != len(weights):
-            raise ValueError(f"{what}: give the inputs in order and one weight per input")
+            raise ValueError(f"{what}: give the inputs in order and one weight per input" if what else
+                             "give the inputs in order (x, then y, then z) and one weight per input")
         recs = [_rec(v, self.words) for v in given]
         _same_count(*recs)
         w = list(weights) + [0] * (3 - len(weights))
         spec = LutSpec(len(recs), (C.c_int32 * 3)(*[_wrap32(v) for v in w]), _wrap32(bias), int(theta))
         return recs, spec, [_p32(v) for v in recs] + [None] * (3 - len(recs))
+
+    # -- multi-value bootstrapping (thfhe_mv_lut_bootstrap / thfhe_mk_mv_lut_bootstrap) -------------------------------------------------------
+    def _mv_tables(self, factors, tv0, table_index, count):
+        w = np.ascontiguousarray(factors, np.int32)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.size == 0:
+            raise ValueError("factors: expected int32[q][p] or int32[n_tables][q][p]")
+        tv0 = np.ascontiguousarray(tv0, self._tv_dtype).reshape(-1)
+        if tv0.shape[0] != self.params.N:
+            raise ValueError(f"tv0: expected {np.dtype(self._tv_dtype).name}[{self.params.N}]")
+        return w, tv0, _index("table_index", table_index, count)
+
+    def _mv(self, factors, x, y, z, tv0, weights, bias, table_index, keyswitch, *extra):
+        """extra: what the engine's entry takes after table_index (MKCloudKey: out_bias)"""
+        ins, spec, p = self._lut_args((x, y, z), weights, bias, 1, "mv_lut_bootstrap")
+        count = ins[0].shape[0]
+        w, tv0, idx = self._mv_tables(factors, tv0, table_index, count)
+        out = np.empty((count, w.shape[1], self.words if keyswitch else self.params.N + 1), np.int32)
+        fn = self._fn("mv_lut_bootstrap" if keyswitch else "mv_lut_bootstrap_wo_keyswitch")
+        _check(fn(self.h, C.byref(spec), self._ptv(tv0), _p32(w), w.shape[2], w.shape[1], w.shape[0], _p32(idx), *extra, p[0], p[1], p[2], _p32(out), count))
+        return out
 
     # -- device-buffer calls -----------------------------------------------------------------------
     def _alloc(self, n):
@@ -657,12 +691,8 @@ class CloudKey(_EvalKey):
         if tv_a.shape != tv_b.shape:
             raise ValueError(f"tv_a and tv_b differ in shape: {tv_a.shape} vs {tv_b.shape}")
         count = ins[0].shape[0]
-        idx = None
-        if lut_index is not None:
-            idx = np.ascontiguousarray(lut_index, np.int32).reshape(-1)
-            if idx.shape[0] != count:
-                raise ValueError(f"lut_index holds {idx.shape[0]} entries for {count} samples")
-        out = np.empty((count, int(theta) if theta in (1, 2, 4) else 1, self.words if keyswitch else N + 1), np.int32)
+        idx = _index("lut_index", lut_index, count)
+        out = np.empty((count, _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
         fn = lib().thfhe_lut_bootstrap_enc if keyswitch else lib().thfhe_lut_bootstrap_enc_wo_keyswitch
         _check(fn(self.h, C.byref(spec), _p32(tv_a), _p32(tv_b), tv_a.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
         return out
@@ -671,20 +701,15 @@ class CloudKey(_EvalKey):
         """Two-digit tree PBS (thfhe_tree_lut_bootstrap): sample s gets f_table[s](hi, lo) as one record int32[count, n+1].  lo, hi: one record
         array or a tuple of 1 .. 3 (weighted by weights_lo / weights_hi); tv1: int32[n_tables][p_hi / theta][N] (thfhe.lut.tree_test_vectors);
         poly_ctx: a threshold.PolyContext holding the packing key from this key set's LWE key to its bootstrapping ring key."""
-        as_tuple = lambda v: tuple(v) + (None,) * (3 - len(v)) if isinstance(v, (tuple, list)) else (v, None, None)
-        lo_r, spec_lo, plo = self._lut_args(as_tuple(lo), weights_lo, bias_lo, theta, "tree_lut_bootstrap (lo)")
-        hi_r, spec_hi, phi = self._lut_args(as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap (hi)")
+        lo_r, spec_lo, plo = self._lut_args(_as_tuple(lo), weights_lo, bias_lo, theta, "tree_lut_bootstrap (lo)")
+        hi_r, spec_hi, phi = self._lut_args(_as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap (hi)")
         _same_count(lo_r[0], hi_r[0])
         count = lo_r[0].shape[0]
         R = int(p_hi) // int(theta) if theta in (1, 2, 4) else 1
         tv1 = np.ascontiguousarray(tv1, np.int32)
         if R < 1 or tv1.size == 0 or tv1.size % (R * self.params.N):
             raise ValueError(f"tv1: expected int32[n_tables][{R}][{self.params.N}]")
-        idx = None
-        if table_index is not None:
-            idx = np.ascontiguousarray(table_index, np.int32).reshape(-1)
-            if idx.shape[0] != count:
-                raise ValueError(f"table_index holds {idx.shape[0]} entries for {count} samples")
+        idx = _index("table_index", table_index, count)
         out = np.empty((count, self.words), np.int32)
         _check(lib().thfhe_tree_lut_bootstrap(self.h, poly_ctx.h, C.byref(spec_lo), C.byref(spec_hi), int(p_hi), _p32(tv1), tv1.size // (R * self.params.N),
                                               _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
@@ -701,37 +726,11 @@ class CloudKey(_EvalKey):
         """mv_lut_bootstrap without the key switch: int32[count, q, N+1] records under the ring key."""
         return self._mv(factors, x, y, z, tv0, weights, bias, table_index, False)
 
-    def _mv_tables(self, factors, tv0, table_index, count):
-        w = np.ascontiguousarray(factors, np.int32)
-        if w.ndim == 2:
-            w = w[None]
-        if w.ndim != 3 or w.size == 0:
-            raise ValueError("factors: expected int32[q][p] or int32[n_tables][q][p]")
-        tv0 = np.ascontiguousarray(tv0, np.int32).reshape(-1)
-        if tv0.shape[0] != self.params.N:
-            raise ValueError(f"tv0: expected int32[{self.params.N}]")
-        idx = None
-        if table_index is not None:
-            idx = np.ascontiguousarray(table_index, np.int32).reshape(-1)
-            if idx.shape[0] != count:
-                raise ValueError(f"table_index holds {idx.shape[0]} entries for {count} samples")
-        return w, tv0, idx
-
-    def _mv(self, factors, x, y, z, tv0, weights, bias, table_index, keyswitch):
-        ins, spec, p = self._lut_args((x, y, z), weights, bias, 1, "mv_lut_bootstrap")
-        count = ins[0].shape[0]
-        w, tv0, idx = self._mv_tables(factors, tv0, table_index, count)
-        out = np.empty((count, w.shape[1], self.words if keyswitch else self.params.N + 1), np.int32)
-        fn = lib().thfhe_mv_lut_bootstrap if keyswitch else lib().thfhe_mv_lut_bootstrap_wo_keyswitch
-        _check(fn(self.h, C.byref(spec), _p32(tv0), _p32(w), w.shape[2], w.shape[1], w.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
-        return out
-
     def tree_lut_bootstrap_mv(self, poly_ctx, factors, lo, hi, *, tv0, weights_lo=(1,), bias_lo=0, weights_hi=(1,), bias_hi=0, table_index=None):
         """tree_lut_bootstrap with level 1 as ONE multi-value rotation per sample (thfhe_tree_lut_bootstrap_mv): 1 + 1 rotations whatever p_hi is.
         tv0, factors int32[p_hi][p_lo] or int32[n_tables][p_hi][p_lo]: thfhe.lut.tree_mv_factors.  int32[count, n+1]."""
-        as_tuple = lambda v: tuple(v) + (None,) * (3 - len(v)) if isinstance(v, (tuple, list)) else (v, None, None)
-        lo_r, spec_lo, plo = self._lut_args(as_tuple(lo), weights_lo, bias_lo, 1, "tree_lut_bootstrap_mv (lo)")
-        hi_r, spec_hi, phi = self._lut_args(as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap_mv (hi)")
+        lo_r, spec_lo, plo = self._lut_args(_as_tuple(lo), weights_lo, bias_lo, 1, "tree_lut_bootstrap_mv (lo)")
+        hi_r, spec_hi, phi = self._lut_args(_as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap_mv (hi)")
         _same_count(lo_r[0], hi_r[0])
         count = lo_r[0].shape[0]
         w, tv0, idx = self._mv_tables(factors, tv0, table_index, count)
@@ -743,9 +742,8 @@ class CloudKey(_EvalKey):
     def tree_lut_bootstrap_mvk(self, poly_ctx, factors, lo, hi, *, tv0, weights_lo=(1,), bias_lo=0, weights_hi=(1,), bias_hi=0, table_index=None):
         """tree_lut_bootstrap_mv with k tables per sample (thfhe_tree_lut_bootstrap_mvk): out[s][j] = f_j(hi_s, lo_s) in 1 + k rotations.
         tv0, factors int32[k][p_hi][p_lo] or int32[n_tables][k][p_hi][p_lo]: thfhe.lut.tree_mvk_factors; k p_hi <= 64.  int32[count, k, n+1]."""
-        as_tuple = lambda v: tuple(v) + (None,) * (3 - len(v)) if isinstance(v, (tuple, list)) else (v, None, None)
-        lo_r, spec_lo, plo = self._lut_args(as_tuple(lo), weights_lo, bias_lo, 1, "tree_lut_bootstrap_mvk (lo)")
-        hi_r, spec_hi, phi = self._lut_args(as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap_mvk (hi)")
+        lo_r, spec_lo, plo = self._lut_args(_as_tuple(lo), weights_lo, bias_lo, 1, "tree_lut_bootstrap_mvk (lo)")
+        hi_r, spec_hi, phi = self._lut_args(_as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap_mvk (hi)")
         _same_count(lo_r[0], hi_r[0])
         count = lo_r[0].shape[0]
         w = np.ascontiguousarray(factors, np.int32)
@@ -863,12 +861,8 @@ class CloudKey(_EvalKey):
         count = tset.count - first if count is None else int(count)
         if first < 0 or count < 0:
             raise ValueError("first and count must not be negative")
-        idx = None
-        if table_index is not None:
-            idx = np.ascontiguousarray(table_index, np.int32).reshape(-1)
-            if idx.shape[0] != count:
-                raise ValueError(f"table_index holds {idx.shape[0]} entries for {count} samples")
-        out = np.empty((count, int(theta) if theta in (1, 2, 4) else 1, self.words if keyswitch else N + 1), np.int32)
+        idx = _index("table_index", table_index, count)
+        out = np.empty((count, _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
         fn = lib().thfhe_lhe_lookup if keyswitch else lib().thfhe_lhe_lookup_wo_keyswitch
         _check(fn(self.h, tset.h, first, count, int(d_tree), int(d_rot), int(theta), _p32(tab_a), _p32(tab_b), tab_b.size // (leaves * N), _p32(idx),
                   _p32(out)))
@@ -910,14 +904,9 @@ class CloudKey(_EvalKey):
         count = sets[0].count - first if count is None else int(count)
         if first < 0 or count < 0:
             raise ValueError("first and count must not be negative")
-        idx = None
-        if table_index is not None:
-            idx = np.ascontiguousarray(table_index, np.int32).reshape(-1)
-            if idx.shape[0] != count:
-                raise ValueError(f"table_index holds {idx.shape[0]} entries for {count} samples")
+        idx = _index("table_index", table_index, count)
         hs = (_vp * len(sets))(*[t.h for t in sets])
-        th = int(theta) if theta in (1, 2, 4) else 1
-        out = np.empty((count, max(start.shape[0], 1), th, self.words if keyswitch else N + 1), np.int32)
+        out = np.empty((count, max(start.shape[0], 1), _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
         fn = lib().thfhe_lhe_wfa if keyswitch else lib().thfhe_lhe_wfa_wo_keyswitch
         _check(fn(self.h, hs, len(sets), first, count, n_steps, n_states, _p32(trans), _p32(step_bit), _p32(fin_a), _p32(fin_b),
                   fin_b.size // (n_states * N), _p32(idx), int(theta), _p32(start), start.shape[0], _p32(out)))
@@ -958,13 +947,7 @@ class CloudKey(_EvalKey):
         count = tset.count - first if count is None else int(count)
         if first < 0 or count < 0:
             raise ValueError("first and count must not be negative")
-        idx = []
-        for name, v in (("val_index", val_index), ("table_index", table_index)):
-            if v is not None:
-                v = np.ascontiguousarray(v, np.int32).reshape(-1)
-                if v.shape[0] != count:
-                    raise ValueError(f"{name} holds {v.shape[0]} entries for {count} samples")
-            idx.append(v)
+        idx = [_index("val_index", val_index, count), _index("table_index", table_index, count)]
         tab_a = np.empty((int(n_tables), 1 << int(d_tree), N), np.int32)
         tab_b = np.empty_like(tab_a)
         _check(lib().thfhe_lhe_scatter(self.h, tset.h, first, count, int(d_tree), int(d_rot), _p32(val_a), _p32(val_b), val_b.size // N, _p32(idx[0]),
@@ -1090,33 +1073,11 @@ class MKCloudKey(_EvalKey):
         is rotated by x = sum_q weights[q] * (x, y, z)[q] + (0, bias) at theta = 1; output j of sample s combines p extractions of the Torus64
         accumulator with the taps factors[table_index[s]][j] (thfhe.lut.mv_factors, mv_bool_factors), adds out_bias (a Torus64 word) to the body and
         converts once.  factors: int32[q][p] or int32[n_tables][q][p].  Returns int32[count, q, P*n+1]."""
-        return self._mv(factors, x, y, z, tv0, weights, bias, table_index, out_bias, True)
+        return self._mv(factors, x, y, z, tv0, weights, bias, table_index, True, _wrap64(out_bias))
 
     def mv_lut_bootstrap_wo_keyswitch(self, factors, x, y=None, z=None, *, tv0, weights=(1,), bias=0, table_index=None, out_bias=0):
         """mv_lut_bootstrap without the key switch: int32[count, q, N+1] records under the ring key."""
-        return self._mv(factors, x, y, z, tv0, weights, bias, table_index, out_bias, False)
-
-    def _mv(self, factors, x, y, z, tv0, weights, bias, table_index, out_bias, keyswitch):
-        ins, spec, p = self._lut_args((x, y, z), weights, bias, 1, "mv_lut_bootstrap")
-        count = ins[0].shape[0]
-        w = np.ascontiguousarray(factors, np.int32)
-        if w.ndim == 2:
-            w = w[None]
-        if w.ndim != 3 or w.size == 0:
-            raise ValueError("factors: expected int32[q][p] or int32[n_tables][q][p]")
-        tv0 = np.ascontiguousarray(tv0, np.int64).reshape(-1)
-        if tv0.shape[0] != self.params.N:
-            raise ValueError(f"tv0: expected int64[{self.params.N}]")
-        idx = None
-        if table_index is not None:
-            idx = np.ascontiguousarray(table_index, np.int32).reshape(-1)
-            if idx.shape[0] != count:
-                raise ValueError(f"table_index holds {idx.shape[0]} entries for {count} samples")
-        out = np.empty((count, w.shape[1], self.words if keyswitch else self.params.N + 1), np.int32)
-        fn = lib().thfhe_mk_mv_lut_bootstrap if keyswitch else lib().thfhe_mk_mv_lut_bootstrap_wo_keyswitch
-        _check(fn(self.h, C.byref(spec), tv0.ctypes.data_as(_i64p), _p32(w), w.shape[2], w.shape[1], w.shape[0], _p32(idx), _wrap64(out_bias), p[0], p[1], p[2],
-                  _p32(out), count))
-        return out
+        return self._mv(factors, x, y, z, tv0, weights, bias, table_index, False, _wrap64(out_bias))
 
     def set_mv_slice(self, max_records):
         """Output records (samples x q) per slice of mv_lut_bootstrap and of an MV launch group: (N + 1) x 4 B of workspace each; default 4096."""
