@@ -617,8 +617,8 @@ int thfhe_dag_run_mv_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const int32
  *   thfhe_mk_mv_lut_bootstrap(mvs[mv].lo, mv_tv0[base], table t of the spec, p, q, out_bias = mv_out_bias[mv], operands) returns at [0][j], word for
  *   word.  mvs[mv].k must be 1, .hi is ignored.  mv_tv0: HOST int64[n_bases][N]; mv_factors as in thfhe_dag_run_mv_batch; mv_out_bias: HOST
  *   int64[n_mvs] or NULL (0 for every spec).  specs / tv may be NULL, 0 when no LUT row needs them; with mvs, mv_tv0 and mv_factors all absent the
- *   call is thfhe_mk_dag_run_lut_batch.  THFHE_TREE_MV, THFHE_SELECT, THFHE_TREE and the encrypted-table rows are refused as undefined opcodes: there
- *   is no multi-key packing key switch.  One launch group per distinct mvs[] index and level; slices of at most thfhe_mk_set_dag_slice nodes over all
+ *   call is thfhe_mk_dag_run_lut_batch.  THFHE_TREE_MV, THFHE_SELECT, THFHE_TREE and the encrypted-table rows are refused as undefined opcodes: the
+ *   flat entries exist, their rows in this executor do not.  One launch group per distinct mvs[] index and level; slices of at most thfhe_mk_set_dag_slice nodes over all
  *   instances and at most max_records / q of them.  stats: an MV node counts one rotation and its group one launch.  Checks as
  *   thfhe_dag_run_mv_batch's for these rows, on the host before the context is looked at. */
 int thfhe_mk_mv_lut_bootstrap(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec, const int64_t *tv0, const int32_t *factors /*[n_tables][q][p]*/, int p,
@@ -632,6 +632,57 @@ int thfhe_mk_dag_run_mv_batch(thfhe_mk_ctx *ctx, const int32_t *inputs, size_t n
                               const thfhe_lut_spec *specs, int n_specs, const int64_t *tv, int n_luts, const thfhe_mv_spec *mvs, int n_mvs,
                               const int64_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, const int64_t *mv_out_bias,
                               size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats);
+
+/* ---- multi-key packing key switch, encrypted tables and the two-digit tree on the 3-gen engine: thfhe_pack_boxes,
+ * thfhe_lut_bootstrap_enc and thfhe_tree_lut_bootstrap restated on Torus64, every parameter family (N = the context's ring degree).  Phases are
+ * beta - alpha (*) Z with Z = sum_q z_q the summed ring key; all arithmetic is integer and wrapping.
+ *
+ * thfhe_mk_pack_key_set: pk HOST int64[D][t][R][2][N], R = 2^basebit - 1 (thfhe.keygen.gen_mk_pack_key).  D = P*n: the key takes the concatenated
+ *   LWE keys (it packs key-switched records and gate outputs); D = N: it takes the coefficients of Z (it packs _wo_keyswitch records; the tree's
+ *   key).  1 <= basebit <= 4, t >= 1, t basebit <= 32 (checked before the context is looked at), D one of the two.  A second call replaces the
+ *   key.  The key stays on the device: D t R 2N x 8 B (N = 1024, D = N, t = 12, basebit = 1: 192 MiB).  THFHE_E_NOMEM if it does not fit (no key is set then).
+ *
+ * thfhe_mk_pack_boxes: p records -> ONE encrypted test vector.  recs: HOST int32[count][D+1] (D = the key's), p a power of two, 2 <= p <= 64, count
+ *   a multiple of p -> tv_a, tv_b HOST int64[count / p][N].  Digits are the LWE key switch's: abar = a + 2^(31 - t basebit) (nothing at t basebit
+ *   = 32; the sum wraps), d_jp = (abar_j >> (32 - (p+1) basebit)) & R, a zero digit contributes nothing.
+ *   T_i = (0, (int64) b_i 2^32 on X^0) - sum_{j, p: d != 0} pk[j][p][d - 1] mod 2^64 on both polynomials;
+ *   output g = U(X) * sum_{i < p} X^(i N/p) T_(g p + i) mod X^N + 1, U(X) = X^(-N/(2p)) (1 + X + ... + X^(N/p - 1)) -- the layout of thfhe_pack_boxes.
+ *   Records with a zero mask give exactly (0, thfhe.lut.test_vector(b 2^32, p, N=N, torus_bits=64)) whatever the key is.  Bit-exact: integer sums.
+ *   THFHE_E_INVALID: null pointers, a bad p, a count that is no multiple of p (on the host, before the context is looked at); no key.  count 0
+ *   returns THFHE_OK.  The batch runs in slices of at most max_candidates records (thfhe_mk_set_tree_slice).
+ *
+ * thfhe_mk_lut_bootstrap_enc(_wo_keyswitch): the contract of thfhe_mk_lut_bootstrap(_wo_keyswitch) with ENCRYPTED tables.  Table t is the RLWE
+ *   sample (tv_a[t], tv_b[t]) under Z whose phase is a test vector (thfhe.lut.encrypt_table(..., torus_bits=64), or an output of thfhe_mk_pack_boxes).
+ *   tv_a, tv_b: HOST int64[n_luts][N], 1 <= n_luts <= 262 144.  Accumulator (X^{-barb} * tv_a[t], X^{-barb} * tv_b[t]), t = lut_index[s], or table 0
+ *   when lut_index is NULL; everything else, the argument checks included, is thfhe_mk_lut_bootstrap's.  tv_a = 0, tv_b = tv gives the words of
+ *   thfhe_mk_lut_bootstrap(tv).
+ *
+ * thfhe_mk_tree_lut_bootstrap: out[s] = f_table[s](hi, lo) for two encrypted digits: level-1 many-LUT rotations on `lo` without a key switch, box
+ *   packing of their [N+1] records with the D = N key, one rotation of the packed table on `hi`, extraction at coefficient 0 and the multi-key key
+ *   switch; three stages per slice on the context's stream, nothing between them visits the host.  spec_lo: 1 .. 3 weighted inputs lo0..2, theta1 in
+ *   {1, 2, 4}.  spec_hi: inputs hi0..2, theta must be 1.  p_hi: a power of two, 2 <= p_hi <= 64, theta1 | p_hi; R = p_hi / theta1.  tv1: HOST
+ *   int64[n_tables][R][N] (thfhe.lut.tree_test_vectors(..., torus_bits=64)); 1 <= n_tables, n_tables R <= 262 144.  table_index: HOST int32[count] or
+ *   NULL (table 0).  lo*, hi*: HOST int32[count][P*n+1]; out: HOST int32[count][P*n+1], which must not alias an input.
+ *   The result equals, word for word, thfhe_mk_lut_bootstrap_wo_keyswitch(spec_lo, tv1 rows, lut_index = table R + r) on every sample's inputs repeated
+ *   R times -> thfhe_mk_pack_boxes(p = p_hi) -> thfhe_mk_lut_bootstrap_enc(spec_hi, table s for sample s).
+ *   THFHE_E_INVALID, before any device work: null pointers, an invalid spec, spec_hi theta != 1, a bad p_hi, theta1 not dividing p_hi, n_tables or a
+ *   table_index entry out of range (on the host, before the context is looked at); then no packing key, a packing key with D != N.
+ *   The batch runs in slices of at most max_candidates / p_hi samples (thfhe_mk_set_tree_slice, default 16 384 candidates, 1 .. 2^18).  Per candidate
+ *   the workspace holds its sum T, 2N x 8 B (16 / 32 / 64 KiB at N = 1024 / 2048 / 4096), its record of (N + 1) x 4 B and, per level-1 rotation, an
+ *   accumulator of 2N x 8 B.  With profiling on, thfhe_mk_last_timings gives ms[0] = level 1, ms[1] = packing, ms[2] = selection of the LAST slice
+ *   and ms[3] = the three together. */
+int thfhe_mk_pack_key_set(thfhe_mk_ctx *ctx, const int64_t *pk, int D, int t, int basebit);
+int thfhe_mk_pack_boxes(thfhe_mk_ctx *ctx, const int32_t *recs /*[count][D+1]*/, size_t count, int p, int64_t *tv_a, int64_t *tv_b /*[count/p][N]*/);
+int thfhe_mk_lut_bootstrap_enc(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec, const int64_t *tv_a, const int64_t *tv_b, int n_luts,
+                               const int32_t *lut_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count);
+int thfhe_mk_lut_bootstrap_enc_wo_keyswitch(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec, const int64_t *tv_a, const int64_t *tv_b, int n_luts,
+                                            const int32_t *lut_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1,
+                                            size_t count);
+int thfhe_mk_tree_lut_bootstrap(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi,
+                                const int64_t *tv1 /*[n_tables][p_hi/theta_lo][N]*/, int n_tables, const int32_t *table_index, const int32_t *lo0,
+                                const int32_t *lo1, const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2,
+                                int32_t *out /*[count][P*n+1]*/, size_t count);
+int thfhe_mk_set_tree_slice(thfhe_mk_ctx *ctx, size_t max_candidates);
 
 /* ---- leveled nodes in the gate-DAG executor (single key): thfhe_dag_run_mv_batch with three more node kinds that read the client's
  * TGSW-encrypted bits, so that a leveled lookup, a leveled pick among COMPUTED wires and a layered automaton run between gates on the device-resident

@@ -22,6 +22,9 @@
 //   mk_extract_mv_kernel      multi-value bootstrap (thfhe_mk_mv_lut_bootstrap): q outputs of ONE rotation, each the integer combination of p
 //                             extractions of the Torus64 accumulator staged in LDS (extract_mv64, thfhe_lane.h), converted once; with the prologue on the
 //                             wire table the MV nodes of the gate DAG (thfhe_mk_dag_run_mv_batch)
+//   mk_pack_rows_kernel / mk_pack_boxes_kernel / mk_lut_acc_init_enc_kernel (thfhe_mk_pack.h)   the multi-key packing key switch, encrypted tables and
+//                             the two-digit tree (thfhe_mk_pack_boxes, thfhe_mk_lut_bootstrap_enc, thfhe_mk_tree_lut_bootstrap): records ->
+//                             Torus64 RLWE sums under Z = sum_q z_q, box packing of p of them, accumulator start on both polynomials
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -35,6 +38,7 @@
 #include "thfhe_dag.h"
 #include "thfhe_lane.h"
 #include "thfhe_mk_shared.h"
+#include "thfhe_mk_pack.h"
 
 using namespace thfhe;
 
@@ -969,6 +973,13 @@ struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     // and the factor array of a gate-DAG run (thfhe_mk_dag_run_mv_batch)
     DevBuf d_mv_w, d_dag_mv_tv0, d_dag_mv_w;
     size_t mv_slice = 4096;   // output records (samples x q) per slice of a multi-value call: (N + 1) x 4 B of d_u each
+    // packing key switch, encrypted tables and the tree
+    DevBuf d_pk;                              // the packing key int64[D][t][R][2][N] (thfhe_mk_pack_key_set)
+    int pk_D = 0, pk_t = 0, pk_basebit = 0;   // its shape; pk_D == 0: no key
+    DevBuf d_tva;                             // encrypted tables: the masks (d_tv holds the bodies)
+    DevBuf d_pin, d_pt;                       // a packing call's records and the per-record sums T int64[records][2][N]
+    DevBuf d_tab_a, d_tab_b, d_tree_tab;      // a tree slice's packed tables (mask, body) and table indices
+    size_t tree_slice = 16384;                // level-1 candidates (samples x p_hi) per slice of a tree or packing call: 2 N x 8 B of d_pt each
 };
 
 namespace {
@@ -1026,11 +1037,12 @@ int mk_lut_workspace(thfhe_mk_ctx *c, size_t count, int theta) {
 // accumulator start from each job's table of d_tv, the rotation of mk_bootstrap_3gen, extraction of theta coefficients into d_u [jobs][theta][N+1];
 // then, with ks_dst, the key switch of the jobs x theta records into it.  A source that writes no table index rotates on d_idx (null: table 0).
 // timed: the profiling events of a flat call (prologue + accumulator start | rotation + extraction | key switch); a gate-DAG run records none.
+// d_tva: the tables are RLWE samples (d_tva, d_tv) under Z; the accumulator starts at (X^{-barb} d_tva[t], X^{-barb} d_tv[t]).
 // mv: every job rotates the ONE base vector d_tv (theta is 1), the index picks its factor table, and the extraction is
 // mk_extract_mv_kernel's mv->q records per job, d_u [jobs][q][N+1].
 template <typename Src>
 int mk_enqueue_pbs(thfhe_mk_ctx *c, const Src &src, size_t jobs, const int64_t *d_tv, int theta, const int32_t *d_idx, int32_t *ks_dst, bool timed = false,
-                   const MkMvArgs *mv = nullptr) {
+                   const MkMvArgs *mv = nullptr, const int64_t *d_tva = nullptr) {
     const int N = c->p.N;
     const bool ev = timed && c->profiling;
     int32_t *const idx = c->d_lut_idx.as<int32_t>();
@@ -1038,8 +1050,12 @@ int mk_enqueue_pbs(thfhe_mk_ctx *c, const Src &src, size_t jobs, const int64_t *
     int64_t *acc = c->d_acc.as<int64_t>();
     if (ev) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
     lut_prologue_launch(src, jobs, c->words, c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), idx, c->stream);
-    hipLaunchKernelGGL(mk_lut_acc_init_kernel, dim3((unsigned)jobs), dim3(256), 0, c->stream, c->d_barb.as<int32_t>(), d_tv, mv ? nullptr : d_idx, (long)jobs, N,
-                       acc);
+    if (d_tva)   // an encrypted table: both polynomials start rotated
+        hipLaunchKernelGGL(mk_lut_acc_init_enc_kernel, dim3((unsigned)jobs), dim3(256), 0, c->stream, c->d_barb.as<int32_t>(), d_tva, d_tv, d_idx, (long)jobs, N,
+                           acc);
+    else
+        hipLaunchKernelGGL(mk_lut_acc_init_kernel, dim3((unsigned)jobs), dim3(256), 0, c->stream, c->d_barb.as<int32_t>(), d_tv, mv ? nullptr : d_idx,
+                           (long)jobs, N, acc);
     if (ev) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
     // acc_in == acc_out == d_acc: every rotation shape may run in place.  The N = 1024 / 2048 coop and pair kernels copy their job's
     // accumulator(s) into LDS before the first barrier and write them back only after the last CMux, and no workgroup touches another job's
@@ -1245,10 +1261,14 @@ int mk_dag_ensure(thfhe_mk_ctx *c, size_t max_gates, int theta_max, int32_t **in
     return r;
 }
 
+constexpr int kMaxEncLuts = 262144;   // tables of one thfhe_mk_lut_bootstrap_enc call, rows of one tree call
+
 // thfhe_mk_lut_bootstrap (keyswitch) / thfhe_mk_lut_bootstrap_wo_keyswitch: out = count x theta records of P n + 1 (resp. N + 1) words
+// enc: thfhe_mk_lut_bootstrap_enc(_wo_keyswitch), the tables are RLWE samples (tv_a, tv) under Z and up to kMaxEncLuts of them
 int mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
-                     const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch) {
-    int rc = lut_validate(sp, tv, n_luts, lut_index, in0, in1, in2, out, count);
+                     const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch, bool enc = false, const int64_t *tv_a = nullptr) {
+    if (enc && !tv_a) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    int rc = lut_validate(sp, tv, n_luts, lut_index, in0, in1, in2, out, count, enc ? kMaxEncLuts : 1024);
     if (rc) return rc;
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     if (count == 0) return THFHE_OK;
@@ -1259,14 +1279,156 @@ int mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *t
     const size_t stage_words = keyswitch ? outs * rec : in_words;   // the key switch writes count x theta records into stage.out
     return ctx_staged(c, stage_words, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, {in_bytes, in_bytes, in_bytes}, [&] {
         int r = c->d_tv.grow((size_t)n_luts * N * sizeof(int64_t));
+        if (!r && enc) r = c->d_tva.grow((size_t)n_luts * N * sizeof(int64_t));
         if (!r && lut_index) r = c->d_lut_idx.grow(count * sizeof(int32_t));
         if (r) return r;
         THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv, (size_t)n_luts * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        if (enc) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int64_t>(), tv_a, (size_t)n_luts * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
         if (lut_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), lut_index, count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         THFHE_TRY(mk_lut_workspace(c, count, s.theta));
         return mk_enqueue_pbs(c, LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, count, c->d_tv.as<int64_t>(),
-                              s.theta, lut_index ? c->d_lut_idx.as<int32_t>() : nullptr, keyswitch ? c->stage.out_ptr() : nullptr, true);
+                              s.theta, lut_index ? c->d_lut_idx.as<int32_t>() : nullptr, keyswitch ? c->stage.out_ptr() : nullptr, true, nullptr,
+                              enc ? c->d_tva.as<int64_t>() : nullptr);
     }, keyswitch ? c->stage.out : c->d_u, out, out_bytes);
+}
+
+// ---- the packing key switch and the two-digit tree ----
+// host checks of a packing call that need no context
+int mk_pack_validate(const int32_t *recs, size_t count, int p, const int64_t *tv_a, const int64_t *tv_b) {
+    if (!recs || !tv_a || !tv_b) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (p < 2 || p > 64 || (p & (p - 1))) return thfhe_fail(THFHE_E_INVALID, "pack: p must be a power of two in 2 .. 64");
+    if (count % (size_t)p) return thfhe_fail(THFHE_E_INVALID, "pack: count must be a multiple of p");
+    if (count > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "count too large");
+    return THFHE_OK;
+}
+
+// grow the scratch of packing `count` records: their sums T
+int mk_pack_reserve(thfhe_mk_ctx *c, size_t count) { return c->d_pt.grow(count * 2 * (size_t)c->p.N * sizeof(int64_t)); }
+
+// thfhe_mk_pack_boxes on device records, enqueued on the context's stream: d_recs int32[count][D + 1] (D = the packing key's), count a multiple of p
+// -> d_a, d_b int64[count / p][N].  The scratch is sized by mk_pack_reserve.
+int mk_pack_enqueue(thfhe_mk_ctx *c, const int32_t *d_recs, size_t count, int p, int64_t *d_a, int64_t *d_b) {
+    const int N = c->p.N;
+    const MkPackArgs a{d_recs, c->d_pk.as<int64_t>(), c->d_pt.as<int64_t>(), (long)count, c->pk_D, c->pk_t, c->pk_basebit, N};
+    hipLaunchKernelGGL(mk_pack_rows_kernel, dim3((unsigned)((count + kMkPackGroup - 1) / kMkPackGroup), (unsigned)(2 * N / kMkPackTile)), dim3(256), 0, c->stream, a);
+    const dim3 grid((unsigned)(count / p), 2), block(1024);
+    const int64_t *T = c->d_pt.as<int64_t>();
+    switch (N) {
+    case 1024: hipLaunchKernelGGL(mk_pack_boxes_kernel<1024>, grid, block, 0, c->stream, T, p, d_a, d_b); break;
+    case 2048: hipLaunchKernelGGL(mk_pack_boxes_kernel<2048>, grid, block, 0, c->stream, T, p, d_a, d_b); break;
+    default: hipLaunchKernelGGL(mk_pack_boxes_kernel<4096>, grid, block, 0, c->stream, T, p, d_a, d_b); break;
+    }
+    THFHE_HIP(hipGetLastError());
+    return THFHE_OK;
+}
+
+// thfhe_mk_pack_boxes: in slices of at most tree_slice records (a multiple of p): only a slice's records go up and its tables come down
+int mk_pack_boxes(thfhe_mk_ctx *c, const int32_t *recs, size_t count, int p, int64_t *tv_a, int64_t *tv_b) {
+    THFHE_TRY(mk_pack_validate(recs, count, p, tv_a, tv_b));
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    if (!c->pk_D) return thfhe_fail(THFHE_E_INVALID, "pack: no packing key set (thfhe_mk_pack_key_set)");
+    if (count == 0) return THFHE_OK;
+    const size_t N = c->p.N, rec = (size_t)c->pk_D + 1;
+    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / p) * p);
+    int rc = mk_pack_reserve(c, S_max);
+    if (!rc) rc = c->d_pin.grow(S_max * rec * sizeof(int32_t));
+    if (!rc) rc = c->d_tab_a.grow(S_max / p * N * sizeof(int64_t));
+    if (!rc) rc = c->d_tab_b.grow(S_max / p * N * sizeof(int64_t));
+    if (rc) return rc;
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0), tab_bytes = S / p * N * sizeof(int64_t);
+        THFHE_HIP(hipMemcpyAsync(c->d_pin.as<int32_t>(), recs + s0 * rec, S * rec * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        THFHE_TRY(mk_pack_enqueue(c, c->d_pin.as<int32_t>(), S, p, c->d_tab_a.as<int64_t>(), c->d_tab_b.as<int64_t>()));
+        THFHE_HIP(hipMemcpyAsync(tv_a + s0 / p * N, c->d_tab_a.as<int64_t>(), tab_bytes, hipMemcpyDeviceToHost, c->stream));
+        THFHE_HIP(hipMemcpyAsync(tv_b + s0 / p * N, c->d_tab_b.as<int64_t>(), tab_bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    return THFHE_OK;
+}
+
+// host checks of a tree call that need no context: pointers, both specs, p_hi, theta_lo | p_hi, the tables and their indices
+int mk_tree_validate(const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, const int64_t *tv1, int n_tables, const int32_t *table_index,
+                     const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2,
+                     const int32_t *out, size_t count) {
+    if (!spec_lo || !spec_hi || !tv1 || !lo0 || !hi0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    THFHE_TRY(lut_spec_check(*spec_lo));
+    THFHE_TRY(lut_spec_check(*spec_hi));
+    if ((spec_lo->n_inputs > 1 && !lo1) || (spec_lo->n_inputs > 2 && !lo2) || (spec_hi->n_inputs > 1 && !hi1) || (spec_hi->n_inputs > 2 && !hi2))
+        return thfhe_fail(THFHE_E_INVALID, "null operand: the spec names more inputs");
+    if (spec_hi->theta != 1) return thfhe_fail(THFHE_E_INVALID, "tree: spec_hi theta must be 1 (the packed table holds one function)");
+    if (p_hi < 2 || p_hi > 64 || (p_hi & (p_hi - 1))) return thfhe_fail(THFHE_E_INVALID, "tree: p_hi must be a power of two in 2 .. 64");
+    if (p_hi % spec_lo->theta) return thfhe_fail(THFHE_E_INVALID, "tree: spec_lo theta must divide p_hi");
+    if (n_tables < 1 || (size_t)n_tables * (p_hi / spec_lo->theta) > (size_t)kMaxEncLuts)
+        return thfhe_fail(THFHE_E_INVALID, "tree: n_tables must be >= 1 and n_tables * p_hi / theta <= 262144");
+    if (count > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "count too large");
+    if (table_index)
+        for (size_t g = 0; g < count; g++)
+            if (table_index[g] < 0 || table_index[g] >= n_tables) return thfhe_fail(THFHE_E_INVALID, "table_index out of range (0 .. n_tables-1)");
+    return THFHE_OK;
+}
+
+// thfhe_mk_tree_lut_bootstrap: per slice of S samples three stages on the context's stream, nothing visiting the host in between --
+//   level 1    S R many-LUT rotations (R = p_hi / theta_lo) of the plaintext rows tv1[table[s]][r] on the `lo` operands, no key switch: the S p_hi
+//              candidates stay in d_u as [N + 1] records under the coefficients of Z, candidate k of sample s at record s p_hi + k
+//   packing    mk_pack_enqueue with p = p_hi and the D = N key: sample s's encrypted table (d_tab_a[s], d_tab_b[s])
+//   selection  one theta = 1 rotation per sample of its own table on the `hi` operands, coefficient 0, mk_keyswitch into the staging output
+// Only a slice's inputs go up and its S records come down; the `hi` operands replace the `lo` ones in the staging arrays once level 1 is enqueued.
+int mk_tree_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec &lo, const thfhe_lut_spec &hi, int p_hi, const int64_t *tv1, int n_tables,
+                      const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0, const int32_t *hi1,
+                      const int32_t *hi2, int32_t *out, size_t count) {
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const size_t N = c->p.N, words = c->rec_words();
+    if (!c->pk_D) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_mk_pack_key_set)");
+    if (c->pk_D != (int)N) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key must take the ring key's coefficients (D = N)");
+    if (count == 0) return THFHE_OK;
+    const int R = p_hi / lo.theta;
+    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / p_hi));
+    const size_t tv_bytes = (size_t)n_tables * R * N * sizeof(int64_t);
+    int rc = c->d_tv.grow(tv_bytes);
+    if (!rc) rc = mk_lut_workspace(c, S_max * R, lo.theta);
+    if (!rc) rc = c->d_lut_idx.grow(S_max * R * sizeof(int32_t));
+    if (!rc) rc = mk_pack_reserve(c, S_max * p_hi);
+    if (!rc) rc = c->d_tab_a.grow(S_max * N * sizeof(int64_t));
+    if (!rc) rc = c->d_tab_b.grow(S_max * N * sizeof(int64_t));
+    if (!rc) rc = c->stage.grow(S_max * words);
+    if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv1, tv_bytes, hipMemcpyHostToDevice, st));
+    const int32_t *lo_in[3] = {lo0, lo.n_inputs > 1 ? lo1 : nullptr, lo.n_inputs > 2 ? lo2 : nullptr};
+    const int32_t *hi_in[3] = {hi0, hi.n_inputs > 1 ? hi1 : nullptr, hi.n_inputs > 2 ? hi2 : nullptr};
+    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0), in_bytes = S * words * sizeof(int32_t);
+        const bool ev = c->profiling && s0 + S == count;   // profiling, on the last slice: level 1 | packing | selection
+        auto upload = [&](const int32_t *const *h) {
+            for (int q = 0; q < 3; q++)
+                if (h[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), h[q] + s0 * words, in_bytes, hipMemcpyHostToDevice, st));
+            return (int)THFHE_OK;
+        };
+        THFHE_TRY(upload(lo_in));
+        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_tree_tab.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (ev) THFHE_HIP(hipEventRecord(c->ev[0], st));
+        THFHE_TRY(mk_enqueue_pbs(c, LutFlatSrc<LutIdx::table>{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr}, S * R, c->d_tv.as<int64_t>(),
+                                 lo.theta, nullptr, nullptr));
+        if (ev) THFHE_HIP(hipEventRecord(c->ev[1], st));
+        THFHE_TRY(mk_pack_enqueue(c, c->d_u.as<int32_t>(), S * p_hi, p_hi, c->d_tab_a.as<int64_t>(), c->d_tab_b.as<int64_t>()));
+        if (ev) THFHE_HIP(hipEventRecord(c->ev[2], st));
+        THFHE_TRY(upload(hi_in));
+        THFHE_TRY(mk_enqueue_pbs(c, LutFlatSrc<LutIdx::job>{in0, in1, in2, hi, 1, nullptr}, S, c->d_tab_b.as<int64_t>(), 1, nullptr, c->stage.out_ptr(), false, nullptr,
+                                 c->d_tab_a.as<int64_t>()));
+        if (ev) {
+            THFHE_HIP(hipEventRecord(c->ev[3], st));
+            c->ev_valid = true;
+        }
+        THFHE_HIP(hipMemcpyAsync(out + s0 * words, c->stage.out_ptr(), in_bytes, hipMemcpyDeviceToHost, st));
+    }
+    THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
 }
 
 // thfhe_mk_mv_lut_bootstrap (keyswitch) / thfhe_mk_mv_lut_bootstrap_wo_keyswitch: out = count x q records of P n + 1 (resp. N + 1) words,
@@ -1592,6 +1754,53 @@ int thfhe_mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const in
 int thfhe_mk_lut_bootstrap_wo_keyswitch(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const int64_t *tv, int n_luts, const int32_t *lut_index,
                                         const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out_N1, size_t count) {
     return mk_lut_bootstrap(c, spec, tv, n_luts, lut_index, in0, in1, in2, out_N1, count, false);
+}
+
+int thfhe_mk_lut_bootstrap_enc(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const int64_t *tv_a, const int64_t *tv_b, int n_luts, const int32_t *lut_index,
+                               const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count) {
+    return mk_lut_bootstrap(c, spec, tv_b, n_luts, lut_index, in0, in1, in2, out, count, true, true, tv_a);
+}
+
+int thfhe_mk_lut_bootstrap_enc_wo_keyswitch(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const int64_t *tv_a, const int64_t *tv_b, int n_luts,
+                                            const int32_t *lut_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out,
+                                            size_t count) {
+    return mk_lut_bootstrap(c, spec, tv_b, n_luts, lut_index, in0, in1, in2, out, count, false, true, tv_a);
+}
+
+int thfhe_mk_pack_key_set(thfhe_mk_ctx *c, const int64_t *pk, int D, int t, int basebit) {
+    if (!pk) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (basebit < 1 || basebit > 4 || t < 1 || t * basebit > 32) return thfhe_fail(THFHE_E_INVALID, "pack key: need 1 <= basebit <= 4, t >= 1, t * basebit <= 32");
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    if (D != c->p.N && D != c->words) return thfhe_fail(THFHE_E_INVALID, "pack key: D must be the ring degree N or the record's P * n mask words");
+    const size_t bytes = (size_t)D * t * ((1u << basebit) - 1) * 2 * c->p.N * sizeof(int64_t);
+    THFHE_HIP(hipStreamSynchronize(c->stream));   // nothing reads the key it replaces
+    c->pk_D = 0;
+    THFHE_TRY(c->d_pk.grow(bytes));
+    THFHE_HIP(hipMemcpyAsync(c->d_pk.as<int64_t>(), pk, bytes, hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    c->pk_D = D, c->pk_t = t, c->pk_basebit = basebit;
+    return THFHE_OK;
+}
+
+int thfhe_mk_pack_boxes(thfhe_mk_ctx *c, const int32_t *recs, size_t count, int p, int64_t *tv_a, int64_t *tv_b) {
+    return mk_pack_boxes(c, recs, count, p, tv_a, tv_b);
+}
+
+int thfhe_mk_tree_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, const int64_t *tv1, int n_tables,
+                                const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
+                                const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
+    // host checks, before the context is looked at
+    THFHE_TRY(mk_tree_validate(spec_lo, spec_hi, p_hi, tv1, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count));
+    return mk_tree_bootstrap(c, *spec_lo, *spec_hi, p_hi, tv1, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
+}
+
+int thfhe_mk_set_tree_slice(thfhe_mk_ctx *c, size_t max_candidates) {
+    if (!c || max_candidates < 1 || max_candidates > ((size_t)1 << 18)) return thfhe_fail(THFHE_E_INVALID, "slice must be 1 .. 2^18 candidates");
+    std::lock_guard<std::mutex> g(c->mu);
+    c->tree_slice = max_candidates;
+    return THFHE_OK;
 }
 
 int thfhe_mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const int64_t *tv0, const int32_t *factors, int p, int q, int n_tables,

@@ -301,6 +301,13 @@ SIGNATURES = {
     "thfhe_mk_mv_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int64, _i32p, _i32p, _i32p,
                                                          _i32p, C.c_size_t]),
     "thfhe_mk_set_mv_slice": (C.c_int, [_vp, C.c_size_t]),
+    "thfhe_mk_pack_key_set": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int]),
+    "thfhe_mk_pack_boxes": (C.c_int, [_vp, _i32p, C.c_size_t, C.c_int, _i64p, _i64p]),
+    "thfhe_mk_lut_bootstrap_enc": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_mk_lut_bootstrap_enc_wo_keyswitch": (C.c_int, [_vp, C.POINTER(LutSpec), _i64p, _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_mk_tree_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
+                                              _i32p, _i32p, C.c_size_t]),
+    "thfhe_mk_set_tree_slice": (C.c_int, [_vp, C.c_size_t]),
     "thfhe_mk_dag_run_mv_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, C.POINTER(MvSpec), C.c_int,
                                             _i64p, C.c_int, _i32p, C.c_size_t, _i64p, C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_mk_prologue_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t]),
@@ -1082,6 +1089,77 @@ class MKCloudKey(_EvalKey):
     def set_mv_slice(self, max_records):
         """Output records (samples x q) per slice of mv_lut_bootstrap and of an MV launch group: (N + 1) x 4 B of workspace each; default 4096."""
         _check(lib().thfhe_mk_set_mv_slice(self.h, int(max_records)))
+
+    # -- packing key switch, encrypted tables and the two-digit tree on Torus64 (DESIGN 4.20) ------------------------------------------------
+    def pack_key_set(self, pk, t, basebit):
+        """Upload the multi-key packing key pk int64[D][t][2^basebit - 1][2][N] (thfhe.keygen.gen_mk_pack_key): D = P*n packs key-switched records and
+        gate outputs, D = N packs _wo_keyswitch records (the tree's key).  A second call replaces the key."""
+        p = self.params
+        R = (1 << int(basebit)) - 1
+        pk = np.ascontiguousarray(pk, np.int64)
+        if pk.ndim != 5 or pk.shape[1:] != (int(t), R, 2, p.N):
+            raise ValueError(f"pk: expected int64[D][{t}][{R}][2][{p.N}], got shape {pk.shape}")
+        _check(lib().thfhe_mk_pack_key_set(self.h, pk.ctypes.data_as(_i64p), pk.shape[0], int(t), int(basebit)))
+        self._pack_D = pk.shape[0]
+
+    def pack_boxes(self, recs, p):
+        """p records -> one encrypted test vector (thfhe_mk_pack_boxes): recs int32[count][D+1] with D the packing key's, count a multiple of p.
+        Returns (tv_a, tv_b) int64[count / p][N]: RLWE samples under the summed ring key, ready for lut_bootstrap_enc."""
+        D = getattr(self, "_pack_D", None)
+        if D is None:
+            raise ValueError("pack_boxes: no packing key set (pack_key_set)")
+        recs = _rec(recs, D + 1)
+        p = int(p)
+        tabs = recs.shape[0] // p if p > 0 else 0
+        tv_a, tv_b = np.empty((tabs, self.params.N), np.int64), np.empty((tabs, self.params.N), np.int64)
+        _check(lib().thfhe_mk_pack_boxes(self.h, _p32(recs), recs.shape[0], p, tv_a.ctypes.data_as(_i64p), tv_b.ctypes.data_as(_i64p)))
+        return tv_a, tv_b
+
+    def lut_bootstrap_enc(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
+        """lut_bootstrap with ENCRYPTED tables: table t is the RLWE sample (tv_a[t], tv_b[t]) int64[N] under the summed ring key
+        (thfhe.lut.encrypt_table(..., torus_bits=64), or pack_boxes' output); up to 262 144 tables.  int32[count, theta, P*n+1]."""
+        return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, True)
+
+    def lut_bootstrap_enc_wo_keyswitch(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
+        """lut_bootstrap_enc without the key switch: int32[count, theta, N+1] records under the coefficients of the summed ring key."""
+        return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, False)
+
+    def _lut_enc(self, tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, keyswitch):
+        ins, spec, p = self._lut_args((x, y, z), weights, bias, theta, "lut_bootstrap_enc")
+        N = self.params.N
+        tv_a = np.ascontiguousarray(tv_a, np.int64).reshape(-1, N)
+        tv_b = np.ascontiguousarray(tv_b, np.int64).reshape(-1, N)
+        if tv_a.shape != tv_b.shape:
+            raise ValueError(f"tv_a and tv_b differ in shape: {tv_a.shape} vs {tv_b.shape}")
+        count = ins[0].shape[0]
+        idx = _index("lut_index", lut_index, count)
+        out = np.empty((count, _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
+        fn = lib().thfhe_mk_lut_bootstrap_enc if keyswitch else lib().thfhe_mk_lut_bootstrap_enc_wo_keyswitch
+        _check(fn(self.h, C.byref(spec), self._ptv(tv_a), self._ptv(tv_b), tv_a.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
+        return out
+
+    def tree_lut_bootstrap(self, tv1, lo, hi, *, p_hi, weights_lo=(1,), bias_lo=0, theta=1, weights_hi=(1,), bias_hi=0, table_index=None):
+        """Two-digit tree PBS (thfhe_mk_tree_lut_bootstrap): sample s gets f_table[s](hi, lo) as one record int32[count, P*n+1].  lo, hi: one record
+        array or a tuple of 1 .. 3 (weighted by weights_lo / weights_hi); tv1: int64[n_tables][p_hi / theta][N]
+        (thfhe.lut.tree_test_vectors(..., torus_bits=64)).  Needs a packing key with D = N (pack_key_set)."""
+        lo_r, spec_lo, plo = self._lut_args(_as_tuple(lo), weights_lo, bias_lo, theta, "tree_lut_bootstrap (lo)")
+        hi_r, spec_hi, phi = self._lut_args(_as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap (hi)")
+        _same_count(lo_r[0], hi_r[0])
+        count = lo_r[0].shape[0]
+        R = int(p_hi) // int(theta) if theta in (1, 2, 4) else 1
+        tv1 = np.ascontiguousarray(tv1, np.int64)
+        if R < 1 or tv1.size == 0 or tv1.size % (R * self.params.N):
+            raise ValueError(f"tv1: expected int64[n_tables][{R}][{self.params.N}]")
+        idx = _index("table_index", table_index, count)
+        out = np.empty((count, self.words), np.int32)
+        _check(lib().thfhe_mk_tree_lut_bootstrap(self.h, C.byref(spec_lo), C.byref(spec_hi), int(p_hi), self._ptv(tv1), tv1.size // (R * self.params.N),
+                                                 _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
+        return out
+
+    def set_tree_slice(self, max_candidates):
+        """Level-1 candidates (samples x p_hi) per slice of tree_lut_bootstrap and records per slice of pack_boxes: 2N x 8 B of workspace each;
+        default 16384."""
+        _check(lib().thfhe_mk_set_tree_slice(self.h, int(max_candidates)))
 
     def dag_run_mv_batch(self, input_records, nodes, specs=(), tv=None, mvs=(), mv_tv0=None, mv_factors=None, mv_out_bias=None, out_wires=None):
         """dag_run_lut_batch with multi-value nodes (thfhe_mk_dag_run_mv_batch).  mvs: MvSpec or (lo, hi, p, q, k, base, factors_off,

@@ -1187,7 +1187,7 @@ def simulate_mk(cir, input_bits):
 def _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets=None):
     if ck._tv_dtype == np.int64:   # the 3-gen multi-key engine: gates, LUT and MV nodes (thfhe_mk_dag_run_mv_batch)
         if cir.has_tree_nodes() or cir.has_lhe_nodes() or any(g[0] == TREE_MV for g in cir.gates):
-            raise ValueError("the multi-key engine runs gate, LUT and MV nodes only (no packing key switch, no leveled nodes)")
+            raise ValueError("the multi-key executor runs gate, LUT and MV nodes only (no tree or encrypted-table rows, no leveled nodes)")
         mvs, tv0, fac = cir.mv_families()
         bias = [cir.mv_out_bias.get(i, 0) for i in range(len(mvs))]
         return ck.dag_run_mv_batch(x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None, mvs, tv0, fac, bias, sel)

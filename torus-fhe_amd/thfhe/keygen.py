@@ -101,6 +101,51 @@ def gen_pack_key(rng, lwe_key, tlwe_key, t, basebit, sigma, chunk=2048):
     return pk.reshape(n, t, R, 2, N)
 
 
+def gen_mk_pack_key(rng, in_key, rlwe_keys, t, basebit, sigma, chunk=1024, device=None):
+    """The multi-key packing key of the 3-gen engine -> int64[D][t][2^basebit - 1][2][N].  in_key, an integer vector of
+    length D, is the concatenated LWE keys lwe_keys.reshape(-1) (D = P n: the key packs key-switched records and gate outputs) or the coefficients
+    of Z = sum_q z_q (D = N: it packs _wo_keyswitch records; the tree's key).  Row (j, p, v - 1) is the RLWE sample (alpha, beta) under Z with alpha
+    uniform and beta = alpha (*) Z + e + v in_key[j] 2^(64 - (p+1) basebit) on the constant coefficient, e Gaussian of standard deviation
+    sigma sqrt(P) on all N coefficients.  That is the row the P parties obtain without any of them knowing Z: for a per-row common reference alpha
+    each publishes alpha (*) z_q + e_q with its own noise of deviation sigma (the message term added by whoever holds in_key[j], or shared
+    additively), and the published polynomials are summed.  Here the sum is drawn in one step.
+    Exact products through polymul_small64, `chunk` rows at a time; device = d routes them through thfhe.PolyMac on MI355X number d, as
+    MKSecretKeySet does.  The random stream is drawn identically either way, so both give the same words."""
+    s = np.asarray(in_key, np.int64).reshape(-1)
+    zq = np.asarray(rlwe_keys, np.int64)
+    zq = zq[None] if zq.ndim == 1 else zq
+    P, N = zq.shape
+    Z = zq.sum(axis=0)
+    D, R = s.shape[0], (1 << basebit) - 1
+    assert t >= 1 and 1 <= basebit and t * basebit <= 32
+    assert (1 << 22) * N * max(int(np.abs(Z).max()), 1) < 1 << 53, "polymul_small64: a limb product sum would leave the exact range of float64"
+    rows = D * t * R
+    pk = np.empty((rows, 2, N), np.int64)
+    j = np.repeat(np.arange(D), t * R)
+    p = np.tile(np.repeat(np.arange(t), R), D)
+    v = np.tile(np.arange(1, R + 1), D * t)
+    msg = (v * s[j]).astype(np.uint64) << (64 - (p + 1) * basebit).astype(np.uint64)   # wraps mod 2^64
+    pm = None
+    if device is not None:
+        from . import PolyMac
+        pm = PolyMac(N, 64, device)
+    for r0 in range(0, rows, chunk):
+        r1 = min(rows, r0 + chunk)
+        m = r1 - r0
+        alpha = rng.integers(-2**63, 2**63, size=(m, N), dtype=np.int64)
+        e = dtot64(rng.standard_normal((m, N)) * (sigma * np.sqrt(P))).view(np.uint64)
+        e[:, 0] += msg[r0:r1]
+        if pm is not None:   # out[i] = e[i] + Z (*) alpha[i]
+            beta = pm.mac(Z[None, :], alpha, [(i, 0, i, 1) for i in range(m)], m, e.view(np.int64)).view(np.uint64)
+        else:
+            beta = polymul_small64(alpha, Z).view(np.uint64) + e
+        pk[r0:r1, 0] = alpha
+        pk[r0:r1, 1] = beta.view(np.int64)
+    if pm is not None:
+        pm.close()
+    return pk.reshape(D, t, R, 2, N)
+
+
 def seed_seq_generate(seeds, count):
     """std::seed_seq(seeds).generate: `count` 32-bit words ([rand.util.seedseq], as libstdc++ implements it)."""
     v = [int(x) & 0xFFFFFFFF for x in seeds]

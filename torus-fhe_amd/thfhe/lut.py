@@ -97,14 +97,16 @@ def bool_outputs(f, p, torus_bits=32):
     return _to_i32(np.array([MU8 if f(m) else -MU8 for m in range(p)], np.int64))
 
 
-def tree_test_vectors(f, p_hi, p_lo, p_out, theta=1, N=1024):
+def tree_test_vectors(f, p_hi, p_lo, p_out, theta=1, N=1024, torus_bits=32):
     """Level-1 test vectors of the two-digit tree (thfhe_tree_lut_bootstrap) for f(hi, lo), taken mod p_out: int32[p_hi / theta][N],
-    row r = test_vector of the theta functions lo -> f(r theta + j, lo), j < theta, at modulus p_lo."""
+    row r = test_vector of the theta functions lo -> f(r theta + j, lo), j < theta, at modulus p_lo.  torus_bits=64: int64 rows of Torus64 words
+    (thfhe_mk_tree_lut_bootstrap)."""
     _check_p(p_hi)
+    _check_bits(torus_bits)
     if theta not in (1, 2, 4) or p_hi % theta:
         raise ValueError("theta must be 1, 2 or 4 and divide p_hi")
-    return np.stack([test_vector([int_outputs(lambda lo, h=r * theta + j: f(h, lo), p_out, p_lo) for j in range(theta)], p_lo, theta, N)
-                     for r in range(p_hi // theta)])
+    return np.stack([test_vector([int_outputs(lambda lo, h=r * theta + j: f(h, lo), p_out, p_lo, torus_bits) for j in range(theta)], p_lo, theta, N,
+                                 torus_bits) for r in range(p_hi // theta)])
 
 
 def mv_base(step, N=1024, torus_bits=32):
@@ -248,10 +250,20 @@ def wfa_finals(values, theta=1, encode=None, N=1024):
     return _to_i32(fin)
 
 
-def encrypt_table(rlwe_key, tv, sigma, rng):
+def encrypt_table(rlwe_key, tv, sigma, rng, torus_bits=32):
     """The client side of an encrypted table (thfhe_lut_bootstrap_enc): a fresh TLWE sample (tv_a, tv_b) of the test vector(s) tv int32[..., N]
-    under the bootstrapping ring key: tv_a uniform, tv_b = tv_a (*) z + tv + e, e Gaussian of standard deviation sigma; exact product."""
-    from .keygen import dtot32, polymul_small32
+    under the bootstrapping ring key: tv_a uniform, tv_b = tv_a (*) z + tv + e, e Gaussian of standard deviation sigma; exact product.
+    torus_bits=64 (thfhe_mk_lut_bootstrap_enc): int64 test vectors and samples, rlwe_key the small ring key the table is under -- on
+    the 3-gen engine the summed key Z = sum_q z_q."""
+    from .keygen import dtot32, dtot64, polymul_small32, polymul_small64
+    _check_bits(torus_bits)
+    if torus_bits == 64:
+        z = np.asarray(rlwe_key, np.int64).reshape(-1)
+        tv = np.ascontiguousarray(tv, np.int64)
+        flat = tv.reshape(-1, z.shape[0])
+        a = rng.integers(-2**63, 2**63, size=flat.shape, dtype=np.int64)
+        b = polymul_small64(a, z).view(np.uint64) + flat.view(np.uint64) + dtot64(rng.standard_normal(flat.shape) * sigma).view(np.uint64)
+        return a.reshape(tv.shape), b.view(np.int64).reshape(tv.shape)
     z = np.asarray(rlwe_key, np.int32).reshape(-1)
     tv = np.ascontiguousarray(tv, np.int32)
     flat = tv.reshape(-1, z.shape[0])
