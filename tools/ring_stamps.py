@@ -35,7 +35,7 @@ NS = 6 if COOP else 4
 st = buf.reshape(nwg, 8, 8)[:, :, :NS].astype(np.float64) / p.n   # cycles per CMux
 names = (["F: rotate+decompose+fwd FFT+publish", "wait at barrier 1", "M: spectra reads + MAC", "hand-off / prefetch issue / I: inverse+atomics",
           "wait at barrier 2", "wait at barrier 3"] if COOP else
-         ["rotate+decompose+fwd FFT (6 rows)", "chunk barriers (30)", "key reads + MAC (24 chunks)", "4 inverse FFT + acc update"])
+         ["rotate+decompose+fwd FFT (6 rows)", "hand-off barriers (3 per row)", "key reads + MAC (24 chunks)", "4 inverse FFT + acc update"])
 print(f"batch {B}: blind rotate {t['blind_rotate_ms']:.3f} ms; s_memtime ticks per CMux per wave (mean over {nwg} workgroups x 8 waves; 100 MHz ticks x clock ratio):")
 tot = st.sum(axis=2).mean()
 for q, nm in enumerate(names):

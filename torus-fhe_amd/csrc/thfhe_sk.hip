@@ -34,6 +34,7 @@
 #include "thfhe_keyswitch.h"
 #include "thfhe_lane.h"
 #include "thfhe_pack.h"
+#include "thfhe_ring_schedule.h"
 
 using namespace thfhe;
 
@@ -123,11 +124,21 @@ constexpr int kGate = 0, kLut = 1, kLutEnc = 2, kLutMv = 3;
 //     8 x (accumulator int32[2][1024] 8 KiB + transpose buffer 9 KiB) | key ring 3 x 8 KiB                  = 163 840 B
 // Each wave owns one job; its accumulator never leaves LDS during the n CMuxes.  The eight waves walk the key index i, the digit
 // rows and the four (column, limb) chunks of a row in lock step.  A chunk is 8 KiB of key spectrum = 8 slices of 1 KiB; wave w brings
-// slice w into the ring with ONE global_load_lds_dwordx4 (LDS-DMA, no registers), so the whole key crosses the CU's vector-memory
-// path once per workgroup instead of once per wave.  Hand-off of chunk q: every wave waits for its own slice (s_waitcnt vmcnt(N),
-// N = younger DMAs in flight), then s_barrier -- after it the chunk is complete AND everybody has finished reading chunk q-1, whose
-// slot is refilled at once with chunk q+2.  Per row: 5 barriers, 4 DMA issues per wave.  A wave whose mod-switched mask word is 0
-// (J/bootstrap.jl:40) or that has no job still streams and synchronises.
+// slice w into its slot with ONE global_load_lds_dwordx4 (LDS-DMA, no registers), so the whole key crosses the CU's vector-memory
+// path once per workgroup instead of once per wave.
+//
+// Hand-off per ROW (thfhe_ring_schedule.h holds the slot schedule; tests/cpp/ring_schedule_test.cpp replays it on the host).  The transpose
+// buffers are touched only inside transforms, and between the first and the last barrier of a row no wave is inside one: the first 8 KiB of
+// transpose buffer 0 are a fourth slot for that time.  With c0 .. c3 the row's chunks (column, limb) = (0,0), (0,1), (1,0), (1,1), and a
+// hand-off = s_waitcnt vmcnt(N) lgkmcnt(0) (own slices landed, N = younger DMAs in flight; own LDS reads returned) + s_barrier:
+//   A  after the forward transform: c0 c1 c2 are complete in ring slots 0 1 2 (issued at X of the row before, or by the prologue) and
+//      everybody is out of the transform -> DMA c3 into the borrowed slot; c0 c1 c2 consumed back to back, no barrier between them
+//   X  c3 is complete, everybody's reads of c0 .. c2 have returned -> DMA the NEXT row's c0 c1 c2 into slots 0 1 2 (they land under the rest
+//      of this row and the next transform; the next row may be the next CMux's); c3 consumed from the borrowed slot
+//   B  everybody's reads of the borrowed slot have returned (c3's second half sits in registers) -> transpose buffer 0 is wave 0's again
+// Per row: 3 barriers, 4 DMA issues per wave (the per-chunk hand-off this replaces: 5 barriers); a wave still issues the key in linear order.
+// A wave whose mod-switched mask word is 0 (J/bootstrap.jl:40) or that has no job still streams and synchronises.  Measured
+// (profiles/r09_handoff_timing.md): what the barriers cost was skew between the two waves of a SIMD, not the multiply phase itself.
 //
 // What the second generation changed comes from an in-kernel cycle trace and the PMC counters of the first (tools/ring_stamps.py,
 // profiles/r02_ring_generations.md): with two waves per SIMD that kernel was bound by exposed LDS round trips and by the LDS
@@ -165,9 +176,6 @@ constexpr int kGate = 0, kLut = 1, kLutEnc = 2, kLutMv = 3;
 #ifndef THFHE_RING_LEAN_ROOTS
 #define THFHE_RING_LEAN_ROOTS 1   // eight-wave shape: pass-1 twiddles rebuilt per transform (no scratch); 0 = even products kept across the loop
 #endif
-#ifndef THFHE_RING_READ_FIRST
-#define THFHE_RING_READ_FIRST 0   // 1 = round 4's experiment (profiles/r04_ring_multiply_phase.md): measured slower, kept for the record
-#endif
 // W = waves (= jobs) per workgroup.  W = 8 is the throughput shape described above.  W = 4 (one wave per SIMD, 92 KiB of LDS, each wave
 // brings TWO slices of a chunk) is the shape for batches that cannot give every CU eight jobs (<= 1024 rotations): a wave alone on its
 // SIMD issues at ~87 % of what a pair reaches together (tools/probes/issue_probe.hip), so four jobs finish much sooner than eight.
@@ -183,6 +191,7 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
     __shared__ cplx sRing[3][512];
     constexpr int ROWS = 2 * L;
     constexpr int DPC = 8 / W;   // ring DMAs per wave and chunk
+    namespace RS = ring_schedule;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
@@ -207,25 +216,26 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
         else acc_init16(lane, acc, acc + 1024, a.barb[job], a.mu);
     }
 
-    const long total_chunks = (long)a.n * ROWS * 4;
+    const long total_chunks = (long)a.n * ROWS * RS::kChunksPerRow;
     const cplx *gsrc = a.bk + wave * (64 * DPC) + lane;
     long q_issue = 0;
-    int slot_issue = 0;
+    // slots 0 .. 2 are the key ring, slot 3 is borrowed from transpose buffer 0 between barriers A and B of a row (thfhe_ring_schedule.h)
+    static_assert(RS::kResidentSlots * RS::kSlotBytes == sizeof(sRing) && RS::kSlotBytes <= sizeof(sX[0]), "ring schedule against the LDS layout");
     const uint32_t ring_base = (uint32_t)(size_t)(__attribute__((address_space(3))) void *)&sRing[0][0] + (uint32_t)wave * (1024u * DPC);
-    auto issue = [&]() {
+    const uint32_t lent_base = (uint32_t)(size_t)(__attribute__((address_space(3))) void *)&sX[0][0] + (uint32_t)wave * (1024u * DPC);
+    auto issue = [&](int slot) {
+        const uint32_t dst = slot == RS::kBorrowedSlot ? lent_base : ring_base + (uint32_t)slot * (uint32_t)RS::kSlotBytes;
 #pragma unroll
-        for (int d = 0; d < DPC; d++) ring_dma(gsrc + 64 * d, ring_base + (uint32_t)slot_issue * 8192u + 1024u * d);
+        for (int d = 0; d < DPC; d++) ring_dma(gsrc + 64 * d, dst + 1024u * d);
         if (q_issue + 1 < total_chunks) {
             gsrc += 512;
             q_issue++;
         }
-        slot_issue = slot_issue == 2 ? 0 : slot_issue + 1;
     };
+    auto slot_ptr = [&](int slot) -> const cplx * { return slot == RS::kBorrowedSlot ? &sX[0][0] : &sRing[slot][0]; };
     __syncthreads();
-    issue();
-    issue();
-    issue();
-    int slot_use = 0;
+#pragma unroll
+    for (int k = 0; k < RS::kPrologueIssues; k++) issue(RS::kPlan[k].slot);
     STAMP_DECL;
 
     for (int i = 0; i < a.n; i++) {
@@ -265,27 +275,13 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
             }
             STAMP(0);
             cplx bA[4], bB[4];
-#pragma unroll
-            for (int c4 = 0; c4 < 4; c4++) {
-                if (c4 == 0) ring_barrier<2 * DPC>(); else ring_barrier<DPC>();
-                STAMP(1);
-                const cplx *B = &sRing[slot_use][0];
-#if THFHE_RING_READ_FIRST
-                // the chunk's first four reads go out the moment the barrier falls (the eight waves' reads of a chunk keep the LDS array busy for
-                // 256 cycles: they, not the arithmetic, are the longest thing between two barriers), then the refill DMA, then the arithmetic
+            // one chunk: its first half is read, the second half of the chunk before multiplied under those reads, its second half read, its first
+            // half multiplied -- the same software pipeline whether or not a barrier stands between two chunks
+            auto consume = [&](int c4) {
+                const cplx *B = slot_ptr(RS::kPlan[c4].slot);
                 if (active) {
 #pragma unroll
                     for (int m = 0; m < 4; m++) bA[m] = B[m * 64 + lane];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (c4 > 0) issue();
-                if (active) {
-#else
-                if (c4 > 0) issue();
-                if (active) {
-#pragma unroll
-                    for (int m = 0; m < 4; m++) bA[m] = B[m * 64 + lane];
-#endif
                     if (c4 > 0) {
 #pragma unroll
                         for (int m = 0; m < 4; m++) cfma(S[(c4 - 1) >> 1][(c4 - 1) & 1][4 + m], z[4 + m], bB[m]);
@@ -295,11 +291,26 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
 #pragma unroll
                     for (int m = 0; m < 4; m++) cfma(S[c4 >> 1][c4 & 1][m], z[m], bA[m]);
                 }
-                slot_use = slot_use == 2 ? 0 : slot_use + 1;
-                STAMP(2);
-            }
-            ring_barrier<2 * DPC>();  // the row's last chunk is read by all (its second half sits in bB): refill its slot before the next transform
-            issue();
+            };
+            // barrier A: c0 c1 c2 have landed and no wave is inside a transform -> c3 into the borrowed slot, c0 c1 c2 consumed back to back
+            ring_barrier<RS::vmcnt_at(RS::kBarA) * DPC>();
+            STAMP(1);
+#pragma unroll
+            for (int k = 0; k < RS::issues_at(RS::kBarA); k++) issue(RS::issue_slot(RS::kBarA, k));
+#pragma unroll
+            for (int c4 = RS::first_consumed(RS::kBarA); c4 < RS::first_consumed(RS::kBarX); c4++) consume(c4);
+            STAMP(2);
+            // barrier X: c3 has landed and everybody's reads of c0 c1 c2 have returned -> the next row's c0 c1 c2 into the ring, c3 consumed
+            ring_barrier<RS::vmcnt_at(RS::kBarX) * DPC>();
+            STAMP(1);
+#pragma unroll
+            for (int k = 0; k < RS::issues_at(RS::kBarX); k++) issue(RS::issue_slot(RS::kBarX, k));
+#pragma unroll
+            for (int c4 = RS::first_consumed(RS::kBarX); c4 < RS::first_consumed(RS::kBarB); c4++) consume(c4);
+            STAMP(2);
+            // barrier B: everybody's reads of the borrowed slot have returned (c3's second half sits in bB) -> transpose buffer 0 is wave 0's again
+            ring_barrier<RS::vmcnt_at(RS::kBarB) * DPC>();
+            static_assert(RS::issues_at(RS::kBarB) == 0 && RS::first_consumed(RS::kBarB) == RS::kChunksPerRow, "nothing is issued or read after barrier B");
             STAMP(1);
             if (active) {
 #pragma unroll
