@@ -103,8 +103,13 @@ __device__ __forceinline__ uniform_i32_ptr as_uniform(const int32_t *p) { return
 // travels in m0 as a register-constrained INPUT ("{m0}"): the compiler itself materialises the value in m0 and knows it is live there,
 // so nothing is clobbered behind its back (round 3 wrote m0 inside the asm and listed it as a clobber, which LLVM calls undefined
 // for a reserved register).  s_nop 0 = the one wait state gfx9 wants between an SALU write of m0 and an LDS-DMA.
-__device__ __forceinline__ void ring_dma(const cplx *gptr_lane, uint32_t lds_byte_off) {
-    asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gptr_lane), "{m0}"(lds_byte_off) : "memory");
+// The address is in the scalar-base form: a wave-uniform 64-bit base in an SGPR pair (the stream position: advanced with scalar adds, no vector
+// instruction per issue) plus the lane's 32-bit byte offset in ONE loop-invariant VGPR.  IMM is the instruction's immediate offset; the hardware adds
+// it to the global address AND to the LDS address, which is what a wave's second slice of a chunk (four-wave shape: + 1 KiB on both sides) wants.
+template <int IMM = 0>
+__device__ __forceinline__ void ring_dma(uint64_t gbase_uniform, uint32_t lane_byte_off, uint32_t lds_byte_off) {
+    static_assert(IMM >= 0 && IMM < 4096, "immediate offset of a global instruction");
+    asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" ::"v"(lane_byte_off), "s"(gbase_uniform), "{m0}"(lds_byte_off), "n"(IMM) : "memory");
 }
 // Hand-off barrier of the ring: this wave's own slice of the chunk has landed (at most VM younger DMAs in flight), every LDS read it issued
 // has returned, then the workgroup barrier.  Two forms: the wait inside an asm (default), or the s_waitcnt BUILTIN -- with the builtin the compiler's
@@ -168,6 +173,11 @@ __device__ __forceinline__ void wave_fft_inv_r(int lane, cplx (&z)[8], cplx *xb,
 //   stage C  lanes with bit 3 clear take z[r] (r even) of lane ^ 8 into z[r + 1], lanes with bit 3 set take z[r + 1] into z[r]
 //            (row_ror:8 DPP moves, bank masks 0x3 / 0xC)
 // The exchange is its own inverse.
+// KEEP64 (the ring kernel's transforms): stage C is a swap, its first move overwrites what the second one reads, so one side is kept -- by the compiler
+// as one v_mov_b32 per dword; with KEEP64 per DOUBLE, behind an empty asm on the 64-bit pair: one v_mov_b64 (gfx950 has no DPP move on a 64-bit
+// register, so the two moves themselves stay per dword).  Same lanes, same values; 64 fewer vector instructions per CMux and wave there.  Not the
+// default: the multi-key rotation kernels, at their register limit, spill with it.
+template <bool KEEP64 = false>
 __device__ __forceinline__ void wave_transpose_hi3(cplx (&z)[8]) {
     uint32_t w[8][4];
 #pragma unroll
@@ -187,11 +197,30 @@ __device__ __forceinline__ void wave_transpose_hi3(cplx (&z)[8]) {
             w[r][d] = q[0];
             w[r + 2][d] = q[1];
         }
+        if constexpr (!KEEP64) {
+#pragma unroll
+            for (int r = 0; r < 8; r += 2) {
+                const uint32_t a = w[r][d], b = w[r + 1][d];
+                w[r + 1][d] = __builtin_amdgcn_update_dpp(b, a, 0x128, 0xF, 0x3, false);
+                w[r][d] = __builtin_amdgcn_update_dpp(a, b, 0x128, 0xF, 0xC, false);
+            }
+        }
+    }
+    if constexpr (KEEP64) {
 #pragma unroll
         for (int r = 0; r < 8; r += 2) {
-            const uint32_t a = w[r][d], b = w[r + 1][d];
-            w[r + 1][d] = __builtin_amdgcn_update_dpp(b, a, 0x128, 0xF, 0x3, false);
-            w[r][d] = __builtin_amdgcn_update_dpp(a, b, 0x128, 0xF, 0xC, false);
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                uint64_t keep = (uint64_t)w[r + 1][2 * k] | (uint64_t)w[r + 1][2 * k + 1] << 32;
+                asm("" : "+v"(keep));
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int d = 2 * k + h;
+                    const uint32_t a = w[r][d], b = w[r + 1][d], kept = (uint32_t)(keep >> (32 * h));
+                    w[r + 1][d] = __builtin_amdgcn_update_dpp(b, a, 0x128, 0xF, 0x3, false);
+                    w[r][d] = __builtin_amdgcn_update_dpp(a, kept, 0x128, 0xF, 0xC, false);
+                }
+            }
         }
     }
 #pragma unroll
@@ -219,7 +248,7 @@ __device__ __forceinline__ void wave_fft_inv_q(int lane, cplx (&z)[8], cplx *xb,
 // variant "f": the exchanges of "q", every inter-pass twiddle folded into the butterflies of the following pass (thfhe_lane.h)
 __device__ __forceinline__ void wave_fft_fwd_f(int lane, cplx (&z)[8], cplx *xb, const LaneRootsF &r) {
     fwdf_seg1(z);
-    wave_transpose_hi3(z);
+    wave_transpose_hi3<true>(z);
     wave_sync();
     fwdf_seg2_st(lane, z, xb, r);
     wave_sync();
@@ -233,7 +262,7 @@ __device__ __forceinline__ void wave_fft_inv_f(int lane, cplx (&z)[8], cplx *xb,
     wave_sync();
     inv_seg2_ld(lane, z, xb);
     invf_seg2(z, w);
-    wave_transpose_hi3(z);
+    wave_transpose_hi3<true>(z);
     invf_seg3(z, r, bc);
 }
 // variant "qs" (multi-key kernels, whose LDS has no room for padded buffers): first transpose in registers, pass-1 twiddles from the

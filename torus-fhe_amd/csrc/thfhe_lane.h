@@ -722,6 +722,15 @@ THFHE_FN void cfma(cplx &s, cplx z, cplx b) {
     s.re = __builtin_fma(-z.im, b.im, s.re);
     s.im = __builtin_fma(z.im, b.re, s.im);
 }
+// The same sum, bit for bit (the product's sign is exact either way), with the negation on the KEY operand.  For the ring kernel: there a spectrum z is
+// multiplied in four places behind barriers, the compiler keeps ONE negated copy of every z.im for all of them (a sign flip and a move per value
+// and row) and can then no longer put the negation on the FMA's source modifier; a key value is read and used once, so its negation stays a modifier.
+THFHE_FN void cfma_negkey(cplx &s, cplx z, cplx b) {
+    s.re = __builtin_fma(z.re, b.re, s.re);
+    s.im = __builtin_fma(z.re, b.im, s.im);
+    s.re = __builtin_fma(z.im, -b.im, s.re);
+    s.im = __builtin_fma(z.im, b.re, s.im);
+}
 // S[m] += z[m] * B[m*64 + lane], one slice at a time with the smallest register footprint: the ring kernels run at the 256-VGPR
 // limit, where this form (18 spilled registers) beats the batched-FMA form below (31+) by 4-20 % (measured)
 THFHE_FN void mac8_lean(int lane, cplx (&S)[8], const cplx (&z)[8], const cplx *B) {

@@ -169,6 +169,10 @@ constexpr int kGate = 0, kLut = 1, kLutEnc = 2, kLutMv = 3;
 // made opaque IN PLACE per transform (no register copies), only the four untwist constants are shared by a CMux's inverse transforms.  Sharing one
 // or both roots' powers as well (3 320 / 3 284 instructions) spilled 6 / 15 registers around the inverse phase and measured 0.45 ms SLOWER than this
 // form (profiles/r06_fold_static_counts.md).
+// Fifth pass (28.26 -> 27.70 ms; profiles/r10_valu_diet.md): the other third of the vector stream, 1 545 -> 1 311 instructions per CMux and wave, the FP64
+// and LDS work untouched.  The key-stream cursor is scalar (below; ring_dma in thfhe_common.h); the kept side of the transposes' half-row swap is one
+// 64-bit move per double (wave_transpose_hi3<KEEP64>); the multiply negates the key operand, not z.im (cfma_negkey in thfhe_lane.h), which is what
+// paid most: the compiler had carried a negated copy of every z.im through the row.
 // ------------------------------------------------------------------------------------------------------
 #ifndef THFHE_RING_NF
 #define THFHE_RING_NF 16
@@ -216,21 +220,23 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
         else acc_init16(lane, acc, acc + 1024, a.barb[job], a.mu);
     }
 
-    const long total_chunks = (long)a.n * ROWS * RS::kChunksPerRow;
-    const cplx *gsrc = a.bk + wave * (64 * DPC) + lane;
-    long q_issue = 0;
+    // The key-stream cursor is wave-uniform and lives in SGPRs: the stream position as a 64-bit base, the count of chunks still ahead of it; the only
+    // per-lane part of a DMA's address is one loop-invariant 32-bit byte offset.  An issue costs the vector pipe nothing but the DMA itself.
+    static_assert(DPC == 1 || DPC == 2, "a wave brings one slice of a chunk, or two 1 KiB apart");
+    const uint32_t lane_off = (uint32_t)(wave * (64 * DPC) + lane) * (uint32_t)sizeof(cplx);
+    uint64_t gbase = (uint64_t)(size_t)a.bk;
+    int chunks_ahead = a.n * ROWS * RS::kChunksPerRow - 1;   // issues past the end of the stream repeat its last chunk
+    asm volatile("" : "+s"(gbase), "+s"(chunks_ahead));
     // slots 0 .. 2 are the key ring, slot 3 is borrowed from transpose buffer 0 between barriers A and B of a row (thfhe_ring_schedule.h)
     static_assert(RS::kResidentSlots * RS::kSlotBytes == sizeof(sRing) && RS::kSlotBytes <= sizeof(sX[0]), "ring schedule against the LDS layout");
     const uint32_t ring_base = (uint32_t)(size_t)(__attribute__((address_space(3))) void *)&sRing[0][0] + (uint32_t)wave * (1024u * DPC);
     const uint32_t lent_base = (uint32_t)(size_t)(__attribute__((address_space(3))) void *)&sX[0][0] + (uint32_t)wave * (1024u * DPC);
     auto issue = [&](int slot) {
         const uint32_t dst = slot == RS::kBorrowedSlot ? lent_base : ring_base + (uint32_t)slot * (uint32_t)RS::kSlotBytes;
-#pragma unroll
-        for (int d = 0; d < DPC; d++) ring_dma(gsrc + 64 * d, dst + 1024u * d);
-        if (q_issue + 1 < total_chunks) {
-            gsrc += 512;
-            q_issue++;
-        }
+        ring_dma(gbase, lane_off, dst);
+        if constexpr (DPC == 2) ring_dma<1024>(gbase, lane_off, dst);   // + 1 KiB in the key and in the slot
+        gbase += chunks_ahead > 0 ? (uint32_t)RS::kSlotBytes : 0u;   // scalar compare, select, add with carry
+        chunks_ahead = chunks_ahead > 0 ? chunks_ahead - 1 : 0;
     };
     auto slot_ptr = [&](int slot) -> const cplx * { return slot == RS::kBorrowedSlot ? &sX[0][0] : &sRing[slot][0]; };
     __syncthreads();
@@ -284,12 +290,12 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
                     for (int m = 0; m < 4; m++) bA[m] = B[m * 64 + lane];
                     if (c4 > 0) {
 #pragma unroll
-                        for (int m = 0; m < 4; m++) cfma(S[(c4 - 1) >> 1][(c4 - 1) & 1][4 + m], z[4 + m], bB[m]);
+                        for (int m = 0; m < 4; m++) cfma_negkey(S[(c4 - 1) >> 1][(c4 - 1) & 1][4 + m], z[4 + m], bB[m]);
                     }
 #pragma unroll
                     for (int m = 0; m < 4; m++) bB[m] = B[(4 + m) * 64 + lane];
 #pragma unroll
-                    for (int m = 0; m < 4; m++) cfma(S[c4 >> 1][c4 & 1][m], z[m], bA[m]);
+                    for (int m = 0; m < 4; m++) cfma_negkey(S[c4 >> 1][c4 & 1][m], z[m], bA[m]);
                 }
             };
             // barrier A: c0 c1 c2 have landed and no wave is inside a transform -> c3 into the borrowed slot, c0 c1 c2 consumed back to back
@@ -314,7 +320,7 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
             STAMP(1);
             if (active) {
 #pragma unroll
-                for (int m = 0; m < 4; m++) cfma(S[1][1][4 + m], z[4 + m], bB[m]);
+                for (int m = 0; m < 4; m++) cfma_negkey(S[1][1][4 + m], z[4 + m], bB[m]);
             }
             STAMP(2);
         }
