@@ -75,6 +75,24 @@ def dec_int(K, recs, p):
     return lut.decode(K.phases(recs), p)
 
 
+def mk_rotate_dev(ck, p, x, mu):
+    """thfhe_mk_rotate_partial_dev on the records x: the raw Torus64 accumulators int64[count][2][N] (barb = 0)."""
+    import oracle_lib as OL
+    import thfhe
+    count, words = x.shape[0], p.parties * p.n
+    bara = np.array([[OL.lib().oracle_modswitch(int(v), p.N) for v in r[:words]] for r in x], np.int32)
+    db, dbb, dacc = thfhe.DeviceBuffer(ck, bara.nbytes), thfhe.DeviceBuffer(ck, 4 * count), thfhe.DeviceBuffer(ck, 16 * count * p.N)
+    try:
+        db.upload(bara)
+        dbb.upload(np.zeros(count, np.int32))
+        thfhe._check(thfhe.lib().thfhe_mk_rotate_partial_dev(ck.h, db.ptr, dbb.ptr, int(mu), None, dacc.ptr, count))
+        ck.sync()
+        return dacc.download((count, 2, p.N), np.int64)
+    finally:
+        for b in (db, dbb, dacc):
+            b.free()
+
+
 # ---- the generators behind the fixtures: `yield from` them in a fixture of the scope the module wants --------------------------------------
 
 def sk128_cloud_key(sk128):

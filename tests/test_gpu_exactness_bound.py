@@ -12,8 +12,7 @@ import pytest
 
 import bound_inputs as B
 import lut_reference as R
-import oracle_lib as OL
-from support import KERNELS, words
+from support import KERNELS, mk_rotate_dev, words
 
 pytestmark = pytest.mark.gpu
 
@@ -67,23 +66,6 @@ MK_CASES = [  # (set, kernels by pair threshold, lowest reached fraction of the 
 ]
 
 
-def _mk_rotate_dev(ck, p, x, mu):
-    """thfhe_mk_rotate_partial_dev on the records x: the raw Torus64 accumulators int64[count][2][N] (barb = 0)."""
-    import thfhe
-    count, words = x.shape[0], p.parties * p.n
-    bara = np.array([[OL.lib().oracle_modswitch(int(v), p.N) for v in r[:words]] for r in x], np.int32)
-    db, dbb, dacc = thfhe.DeviceBuffer(ck, bara.nbytes), thfhe.DeviceBuffer(ck, 4 * count), thfhe.DeviceBuffer(ck, 16 * count * p.N)
-    try:
-        db.upload(bara)
-        dbb.upload(np.zeros(count, np.int32))
-        thfhe._check(thfhe.lib().thfhe_mk_rotate_partial_dev(ck.h, db.ptr, dbb.ptr, int(mu), None, dacc.ptr, count))
-        ck.sync()
-        return dacc.download((count, 2, p.N), np.int64)
-    finally:
-        for b in (db, dbb, dacc):
-            b.free()
-
-
 @pytest.mark.parametrize("name, kernels, frac", MK_CASES, ids=[c[0] for c in MK_CASES])
 def test_multi_key_at_the_bound(O, name, kernels, frac):
     # the 3-gen CMux with mask and body both loaded (party 0's and the last party's crafted step, one record each): every raw 64-bit
@@ -107,7 +89,7 @@ def test_multi_key_at_the_bound(O, name, kernels, frac):
         for thr, kname in kernels.items():
             ck.set_pair_threshold(thr)
             assert ck.rotation_kernel_name(len(x)) == kname
-            got = _mk_rotate_dev(ck, p, x, mu)
+            got = mk_rotate_dev(ck, p, x, mu)
             for k in range(len(x)):
                 assert np.array_equal(got[k], accs[k]), (kname, k, np.argwhere(got[k] != accs[k])[:8])
             assert np.array_equal(ck.bootstrap(x, mu), ref_u), kname
