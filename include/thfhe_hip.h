@@ -515,6 +515,39 @@ int thfhe_lhe_scatter(thfhe_ctx *ctx, const thfhe_tgsw_set *set, size_t first, s
                       const int32_t *val_b /*[n_vals][N]*/, int n_vals, const int32_t *val_index /*[count]*/, int n_tables,
                       const int32_t *table_index /*[count]*/, int32_t *tab_a, int32_t *tab_b /*[n_tables][2^d_tree][N]*/);
 
+/* ---- circuit bootstrapping (single key, N = 1024): LWE gate outputs -> device-resident TGSW samples, so that bits the circuit
+ * computed drive thfhe_lhe_cmux / _lookup / _wfa / _demux / _scatter and the leveled DAG entry.  Level 1 is `ctx` (ring key z, decomposition (l, Bgbit),
+ * LWE key s of dimension n); level 2 is a 3-gen context with parties = 1, THE SAME LWE key s and a ternary ring key z2 of degree D = 2048.
+ *
+ * thfhe_cb_key_set: the private key-switching key pks HOST int32[2][D][t][2][N] (thfhe.keygen.gen_cb_key): row (f, i, p) is a TLWE encryption of zero
+ *   under z with z2[i] 2^(32 - (p+1) basebit) added to coefficient 0 of the body (f = 1) or of the mask (f = 0).  1 <= D <= 2048, t >= 1,
+ *   1 <= basebit <= 8, t basebit <= 32 (THFHE_E_INVALID, checked before the context is looked at).  The key stays on the device twice, as rows and
+ *   as byte planes: 2 x 2 D t 8 KiB (D = 2048, t = 7: 2 x 224 MiB); THFHE_E_NOMEM if that does not fit (no key is set then).  A second call
+ *   replaces the key.
+ *
+ * thfhe_cb_private_keyswitch: stage B alone.  lwe2: HOST int32[count][l][D+1], record (s, j) an LWE sample (a, b) under z2 -> tgsw HOST
+ *   int32[count][2l][2][N]: row j = (b X^0, 0) - sum_(i,p) d_ip K[0][i][p], row l + j = (0, b X^0) - sum_(i,p) d_ip K[1][i][p], d_ip in [-B/2, B/2) the
+ *   balanced base-2^basebit digits of a_i rounded to t basebit bits (sum_p d_ip 2^(32 - (p+1) basebit) = the rounded word mod 2^32).  Exact
+ *   integers.  thfhe_cb_set_batch_threshold: inputs (count l per launch) from which the matrix-core kernel runs instead of the plain one; 0
+ *   restores the default.  No output word depends on it.
+ *
+ * thfhe_circuit_bootstrap: lwe HOST int32[count][d][n+1], gate-encoded records (+-1/8) under s -> *out, a set of `count` samples of d bits for the
+ *   calls of section 4.15 - 4.18, and, with tgsw_words != NULL, its rows HOST int32[count][d][2l][2][N] (the layout of thfhe_tgsw_set_create).
+ *   Per bit and gadget level j < l: the level-2 gate bootstrap with mu_j = 2^(63 - (j+1) Bgbit), extraction of coefficient 0, the engine's Torus64 ->
+ *   Torus32 conversion, + 2^(31 - (j+1) Bgbit) on the body; then the private key switch and the key transform.  Nothing leaves the device between
+ *   the stages; the batch runs in slices of 2048 bits.  1 <= d <= 16, 1 <= count <= 2^24.  THFHE_E_INVALID: null pointers and those ranges (before
+ *   the contexts are looked at), then a null context, no key, contexts on different devices, a level-2 context without parties = 1, n = ctx's n and
+ *   ring degree = the key's D.  THFHE_E_NOMEM (before anything is allocated) if spectra and workspace exceed the free device memory.  With profiling
+ *   on, thfhe_last_timings gives ms[0] = stage A, ms[1] = stage B, ms[2] = transform of the LAST slice.  The library cannot check that the two
+ *   contexts share s or that the key is from z2 to z: with other keys the call succeeds and the set does not decrypt.
+ * thfhe_mk_ctx_info: the parameters and the device of a 3-gen context. */
+int thfhe_cb_key_set(thfhe_ctx *ctx, const int32_t *pks /*[2][D][t][2][N]*/, int D, int t, int basebit);
+int thfhe_cb_private_keyswitch(thfhe_ctx *ctx, const int32_t *lwe2 /*[count][l][D+1]*/, size_t count, int32_t *tgsw /*[count][2l][2][N]*/);
+int thfhe_cb_set_batch_threshold(thfhe_ctx *ctx, long min_inputs);
+int thfhe_circuit_bootstrap(thfhe_ctx *ctx, thfhe_mk_ctx *level2, const int32_t *lwe /*[count][d][n+1]*/, size_t count, int d, int32_t *tgsw_words,
+                            thfhe_tgsw_set **out);
+int thfhe_mk_ctx_info(const thfhe_mk_ctx *ctx, thfhe_params *params, int *device);
+
 /* ---- encrypted-table, select and tree nodes in the gate-DAG executor (single key): thfhe_dag_run_lut_batch with three more node
  * kinds, so that a circuit needing a private table, an oblivious pick or a 6-bit -> 3-bit function does not leave the device-resident wire table.
  * nodes: HOST int32[n_nodes][6] = (opcode, in0, in1, in2, x, y); row g defines wire n_inputs + g.  Gate rows, THFHE_LUT and THFHE_LUT_OUT rows mean

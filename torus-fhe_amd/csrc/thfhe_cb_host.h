@@ -1,0 +1,132 @@
+// thfhe_cb_host.h -- circuit bootstrapping on the single-key context: the bodies of thfhe_cb_key_set,
+// thfhe_cb_private_keyswitch and thfhe_circuit_bootstrap.  Included by thfhe_sk.hip INSIDE its second anonymous namespace, after thfhe_lhe.h
+// (it fills a thfhe_tgsw_set); the key, the kernels and their launcher are in thfhe_cb.h.
+
+int cb_check_shape(int D, int t, int basebit) {
+    if (D < 1 || D > kCbMaxD) return thfhe_fail(THFHE_E_INVALID, "circuit-bootstrap key: D must be 1 .. 2048");
+    if (t < 1 || basebit < 1 || basebit > 8 || t * basebit > 32)
+        return thfhe_fail(THFHE_E_INVALID, "circuit-bootstrap key: need t >= 1, 1 <= basebit <= 8 (a digit is a signed byte) and t basebit <= 32");
+    return THFHE_OK;
+}
+
+int cb_key_set(thfhe_ctx *c, const int32_t *pks, int D, int t, int basebit) {
+    if (!pks) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    THFHE_TRY(cb_check_shape(D, t, basebit));
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    return c->cb.upload(pks, D, t, basebit, c->stream);
+}
+
+// stage B alone on host buffers, in slices of at most 2048 inputs
+int cb_private_keyswitch(thfhe_ctx *c, const int32_t *lwe2, size_t count, int32_t *tgsw) {
+    if (!lwe2 || !tgsw) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (count > ((size_t)1 << 24)) return thfhe_fail(THFHE_E_INVALID, "private key switch: count must be at most 2^24");
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    if (!c->cb.D) return thfhe_fail(THFHE_E_INVALID, "no circuit-bootstrap key (thfhe_cb_key_set)");
+    if (count == 0) return THFHE_OK;
+    const int l = c->p.l, D = c->cb.D;
+    const size_t S_max = std::min<size_t>(count, std::max(1, 2048 / l));
+    const size_t in_words = (size_t)l * (D + 1), out_words = (size_t)2 * l * kCbRow;
+    THFHE_TRY(c->d_cb_lwe2.grow(S_max * in_words * sizeof(int32_t)));
+    THFHE_TRY(c->d_cb_rows.grow(S_max * out_words * sizeof(int32_t)));
+    for (size_t s0 = 0; s0 < count; s0 += S_max) {
+        const size_t S = std::min(S_max, count - s0);
+        THFHE_HIP(hipMemcpyAsync(c->d_cb_lwe2.as<int32_t>(), lwe2 + s0 * in_words, S * in_words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        THFHE_TRY(cb_enqueue(c->cb, c->d_cb_lwe2.as<int32_t>(), (long)(S * l), l, c->d_cb_rows.as<int32_t>(), c->stream));
+        THFHE_HIP(hipMemcpyAsync(tgsw + s0 * out_words, c->d_cb_rows.as<int32_t>(), S * out_words * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    return THFHE_OK;
+}
+
+constexpr size_t kCbSliceBits = 2048;   // bits per slice of thfhe_circuit_bootstrap: 64 MiB of level-2 accumulators, 2l x 16 MiB of rows
+
+// thfhe_circuit_bootstrap after its host checks, the level-2 context enqueueing on c's stream: per slice of bits stage A (one prologue, l rotations
+// with mu_j = 2^(63 - (j+1) Bgbit), extraction, + 2^(31 - (j+1) Bgbit) on the body), stage B (the private key switch) and stage C (the key
+// transform into the set's spectra).  Nothing leaves the device between the stages; `words`, if wanted, gets the rows of stage B.
+int cb_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, thfhe_tgsw_set *set, const int32_t *lwe, int32_t *words) {
+    const int l = c->p.l, n = c->p.n, D = c->cb.D;
+    const size_t polys_per_bit = (size_t)2 * l * 2, bits = set->count * set->d, R_max = std::min(bits, kCbSliceBits);
+    const size_t spec_bytes = bits * polys_per_bit * 1024 * sizeof(cplx);
+    const size_t b_lwe = R_max * (n + 1) * 4, b_bara = R_max * n * 4, b_barb = R_max * 4, b_acc = R_max * 2 * N2 * sizeof(int64_t),
+                 b_x = R_max * (D + 1) * 4, b_lwe2 = b_x * l, b_rows = R_max * polys_per_bit * 4096,
+                 b_dig = std::min<size_t>(R_max * l, kCbMaxLaunchInputs) * c->cb.nstages * kCbStage;
+    size_t free_b = 0, total_b = 0;
+    THFHE_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (spec_bytes + b_lwe + b_bara + b_barb + b_acc + b_x + b_lwe2 + b_rows + b_dig > free_b)
+        return thfhe_fail(THFHE_E_NOMEM, "circuit bootstrap: count d 2l 32 KiB of spectra and the slice workspace exceed the free device memory");
+    THFHE_TRY(c->d_cb_lwe.grow(b_lwe));
+    THFHE_TRY(c->d_cb_bara.grow(b_bara));
+    THFHE_TRY(c->d_cb_barb.grow(b_barb));
+    THFHE_TRY(c->d_cb_acc.grow(b_acc));
+    THFHE_TRY(c->d_cb_x.grow(b_x));
+    THFHE_TRY(c->d_cb_lwe2.grow(b_lwe2));
+    THFHE_TRY(c->d_cb_rows.grow(b_rows));
+    THFHE_TRY(set->spec.grow(spec_bytes));
+    hipStream_t st = c->stream;
+    const bool prof = c->profiling;
+    for (size_t b0 = 0; b0 < bits; b0 += R_max) {
+        const size_t R = std::min(R_max, bits - b0);
+        const bool last = b0 + R == bits;
+        THFHE_HIP(hipMemcpyAsync(c->d_cb_lwe.as<int32_t>(), lwe + b0 * (n + 1), R * (n + 1) * 4, hipMemcpyHostToDevice, st));
+        if (prof && last) THFHE_HIP(hipEventRecord(c->ev[0], st));
+        THFHE_TRY(thfhe_mk_prologue_dev(l2, -1, 0, c->d_cb_lwe.as<int32_t>(), nullptr, nullptr, n + 1, 0, c->d_cb_bara.as<int32_t>(), c->d_cb_barb.as<int32_t>(), R));
+        for (int j = 0; j < l; j++) {
+            const int64_t mu = (int64_t)1 << (63 - (j + 1) * c->p.Bgbit);
+            THFHE_TRY(thfhe_mk_rotate_partial_dev(l2, c->d_cb_bara.as<int32_t>(), c->d_cb_barb.as<int32_t>(), mu, nullptr, c->d_cb_acc.as<int64_t>(), R));
+            THFHE_TRY(thfhe_mk_extract_dev(l2, c->d_cb_acc.as<int64_t>(), c->d_cb_x.as<int32_t>(), R));
+            hipLaunchKernelGGL(cb_place_kernel, dim3((unsigned)((D + 1 + 255) / 256), (unsigned)R), dim3(256), 0, st, c->d_cb_x.as<int32_t>(), D, l, j,
+                               1u << (31 - (j + 1) * c->p.Bgbit), c->d_cb_lwe2.as<int32_t>());
+            THFHE_HIP(hipGetLastError());
+        }
+        if (prof && last) THFHE_HIP(hipEventRecord(c->ev[1], st));
+        THFHE_TRY(cb_enqueue(c->cb, c->d_cb_lwe2.as<int32_t>(), (long)(R * l), l, c->d_cb_rows.as<int32_t>(), st));
+        if (prof && last) THFHE_HIP(hipEventRecord(c->ev[2], st));
+        if (words) THFHE_HIP(hipMemcpyAsync(words + b0 * polys_per_bit * 1024, c->d_cb_rows.as<int32_t>(), R * polys_per_bit * 4096, hipMemcpyDeviceToHost, st));
+        THFHE_TRY((launch_torus_transform<1024, 32>(st, c->d_cb_rows.as<int32_t>(), (long)(R * polys_per_bit), c->d_tw.as<cplx>(),
+                                                    set->spec.as<cplx>() + b0 * polys_per_bit * 1024)));
+        if (prof && last) {
+            THFHE_HIP(hipEventRecord(c->ev[3], st));
+            c->ev_valid = true;
+        }
+    }
+    THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
+}
+
+int circuit_bootstrap(thfhe_ctx *c, thfhe_mk_ctx *l2, const int32_t *lwe, size_t count, int d, int32_t *words, thfhe_tgsw_set **out) {
+    if (!lwe || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    *out = nullptr;
+    if (d < 1 || d > kLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: d must be 1 .. 16");
+    if (count < 1 || count > ((size_t)1 << 24)) return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: count must be 1 .. 2^24");
+    if (!c || !l2) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    thfhe_params p2;
+    int dev2 = -1;
+    THFHE_TRY(thfhe_mk_ctx_info(l2, &p2, &dev2));
+    std::unique_ptr<thfhe_tgsw_set> set(new (std::nothrow) thfhe_tgsw_set);
+    if (!set) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
+    set->ctx = c, set->count = count, set->d = d;
+    int rc;
+    {
+        DevLock lk(*c);
+        if (lk.rc) return lk.rc;
+        if (!c->cb.D) return thfhe_fail(THFHE_E_INVALID, "no circuit-bootstrap key (thfhe_cb_key_set)");
+        if (dev2 != c->device) return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: the two contexts are on different devices");
+        if (p2.parties != 1 || p2.n != c->p.n || p2.N != c->cb.D)
+            return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: the level-2 context needs parties = 1, the gate context's n and the key's D as its ring degree");
+        if ((c->p.l) * c->p.Bgbit > 32) return thfhe_fail(THFHE_E_UNSUPPORTED, "circuit bootstrap: l Bgbit must be at most 32");
+        THFHE_TRY(thfhe_mk_set_stream(l2, c->stream));   // one stream for the three stages
+        rc = cb_fill(c, l2, p2.N, set.get(), lwe, words);
+        const int rc2 = thfhe_mk_set_stream(l2, nullptr);   // drains the stream first
+        if (!rc) rc = rc2;
+    }
+    if (rc) {   // nothing is left behind: the spectra are freed on the context's device
+        (void)hipSetDevice(c->device);
+        return rc;
+    }
+    *out = set.release();
+    return THFHE_OK;
+}

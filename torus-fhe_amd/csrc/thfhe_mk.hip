@@ -1587,6 +1587,12 @@ int thfhe_mk_ctx_create(const thfhe_params *p, const int64_t *bk_coeff, const in
 
 void thfhe_mk_ctx_destroy(thfhe_mk_ctx *c) { ctx_destroy(c); }
 
+int thfhe_mk_ctx_info(const thfhe_mk_ctx *c, thfhe_params *params, int *device) {
+    if (!c || !params || !device) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    *params = c->p, *device = c->device;
+    return THFHE_OK;
+}
+
 void *thfhe_mk_dev_alloc(thfhe_mk_ctx *c, size_t bytes) { return ctx_dev_alloc(c, bytes); }
 void thfhe_mk_dev_free(thfhe_mk_ctx *c, void *p) { ctx_dev_free(c, p); }
 int thfhe_mk_copy_h2d(thfhe_mk_ctx *c, void *dst, const void *src, size_t bytes) { return ctx_copy(c, dst, src, bytes, hipMemcpyHostToDevice); }

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/thfhe_hip.h"
+#include "thfhe_cb.h"
 #include "thfhe_common.h"
 #include "thfhe_dag.h"
 #include "thfhe_devctx.h"
@@ -565,6 +566,10 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     // leveled scatter (thfhe_lhe_demux, thfhe_lhe_scatter): the demux trees run in d_lhe_a ([sample][leaf][mask | body]); the tables
     // being summed ([masks | bodies][n_tables][2^d_tree][N]) and a slice's value and table indices ([2][samples])
     DevBuf d_sc_tab, d_sc_idx;
+    // circuit bootstrapping (thfhe_cb_key_set, thfhe_circuit_bootstrap): the private key-switching key; a slice's gate records, their
+    // level-2 mod-switched words, level-2 accumulators, extracted records of one level, the l records per bit and the TGSW rows
+    CbKey cb;
+    DevBuf d_cb_lwe, d_cb_bara, d_cb_barb, d_cb_acc, d_cb_x, d_cb_lwe2, d_cb_rows;
     int cus = 0;         // compute units of the device, asked once (ctx_cus)
     int wfa_chunk = 0;   // states per workgroup of sk_lhe_wfa_step_kernel, 0: chosen per slice (wfa_chunk_for)
     size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate); also the output records (samples x q) per slice of thfhe_mv_lut_bootstrap
@@ -1111,6 +1116,7 @@ int sk_dag_run(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagCall &A, DagFamilies T
 
 #include "thfhe_lhe.h"
 #include "thfhe_dag_lhe.h"
+#include "thfhe_cb_host.h"
 
 }  // namespace
 
@@ -1472,6 +1478,21 @@ int thfhe_lhe_scatter(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, siz
                       const int32_t *val_b, int n_vals, const int32_t *val_index, int n_tables, const int32_t *table_index, int32_t *tab_a,
                       int32_t *tab_b) {
     return lhe_scatter(c, set, first, count, d_tree, d_rot, val_a, val_b, n_vals, val_index, n_tables, table_index, tab_a, tab_b);
+}
+
+int thfhe_cb_key_set(thfhe_ctx *c, const int32_t *pks, int D, int t, int basebit) { return cb_key_set(c, pks, D, t, basebit); }
+
+int thfhe_cb_private_keyswitch(thfhe_ctx *c, const int32_t *lwe2, size_t count, int32_t *tgsw) { return cb_private_keyswitch(c, lwe2, count, tgsw); }
+
+int thfhe_cb_set_batch_threshold(thfhe_ctx *c, long min_inputs) {
+    if (!c || min_inputs < 0) return thfhe_fail(THFHE_E_INVALID, "batch threshold must be 0 (the default) or a number of inputs");
+    std::lock_guard<std::mutex> lg(c->mu);
+    c->cb.batch_min = min_inputs ? min_inputs : kCbBatchMinInputs;
+    return THFHE_OK;
+}
+
+int thfhe_circuit_bootstrap(thfhe_ctx *c, thfhe_mk_ctx *level2, const int32_t *lwe, size_t count, int d, int32_t *tgsw_words, thfhe_tgsw_set **out) {
+    return circuit_bootstrap(c, level2, lwe, count, d, tgsw_words, out);
 }
 
 }  // extern "C"

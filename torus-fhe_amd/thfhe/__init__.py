@@ -97,6 +97,21 @@ SIGMAS = {
 }
 
 
+# Level-2 sets of circuit bootstrapping: a one-party 3-gen (Torus64) context on the ring of degree 2048 whose LWE key is the gate
+# set's (keygen.MKSecretKeySet(..., lwe_keys=...)); l = 2 with an 18-bit base is the shape of MK256, served by the batched N = 2048 rotation.  A table
+# of its own: PARAM_SETS is what the tests of the named sets iterate over.  The key-switch fields are MK256's and are not used (the level-2 records
+# go to the private key switch).  Made with make_params(**CB_PARAM_SETS[name]).
+CB_PARAM_SETS = {
+    "CB-128": dict(n=630, N=2048, k=1, l=2, Bgbit=18, ks_t=8, ks_basebit=2, torus_bits=64, parties=1),   # level 2 of SK-128
+    "CB-80": dict(n=500, N=2048, k=1, l=2, Bgbit=18, ks_t=8, ks_basebit=2, torus_bits=64, parties=1),    # level 2 of SK-80
+}
+CB_BATCH_MIN_INPUTS = 3   # kCbBatchMinInputs (csrc/thfhe_cb.h): records per launch from which the private key switch runs on the matrix cores
+CB_SIGMAS = {
+    "CB-128": dict(lwe=2.0**-15, bk=2.0**-62.0, ks=2.0**-15),
+    "CB-80": dict(lwe=2.0**-15, bk=2.0**-62.0, ks=2.0**-15),
+}
+
+
 class KmsParams(C.Structure):
     """thfhe_kms_params (include/thfhe_hip.h): the KMS scheme (mk_bootstrap_new) has three gadget families -- gsw (per-party TGSW blind
     rotation of the TLev accumulator), lev (the TLev accumulator), uni (uni-encryption / public keys) -- on a Torus64 ring."""
@@ -287,6 +302,11 @@ SIGNATURES = {
     "thfhe_pm_mac": (C.c_int, [_vp, _i32p, C.c_size_t, _vp, C.c_size_t, _i32p, C.c_size_t, _vp, _vp, C.c_size_t]),
     "thfhe_mk_ctx_create": (C.c_int, [C.POINTER(Params), _i64p, _i32p, C.c_int, C.POINTER(_vp)]),
     "thfhe_mk_ctx_destroy": (None, [_vp]),
+    "thfhe_mk_ctx_info": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(C.c_int)]),
+    "thfhe_cb_key_set": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_int]),
+    "thfhe_cb_private_keyswitch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p]),
+    "thfhe_cb_set_batch_threshold": (C.c_int, [_vp, C.c_long]),
+    "thfhe_circuit_bootstrap": (C.c_int, [_vp, _vp, _i32p, C.c_size_t, C.c_int, _i32p, C.POINTER(_vp)]),
     "thfhe_mk_gates": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_gates_mixed": (C.c_int, [_vp, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_dag_run": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, _i64p]),
@@ -961,6 +981,56 @@ class CloudKey(_EvalKey):
                                        int(n_tables), _p32(idx[1]), _p32(tab_a), _p32(tab_b)))
         return tab_a, tab_b
 
+    # -- circuit bootstrapping: LWE gate outputs -> TGSW address bits (thfhe_cb_key_set, thfhe_circuit_bootstrap) -----------------
+    def cb_key_set(self, level2_cloud_key, pks, t, basebit):
+        """Upload the private key-switching key pks int32[2][D][t][2][N] (thfhe.keygen.gen_cb_key, from the level-2 ring key to this key's ring key)
+        and name the level-2 context: an MKCloudKey of one party on this device whose LWE key is this key's (CB_PARAM_SETS).  It is kept alive for
+        as long as this key.  A second call replaces both."""
+        p = self.params
+        pks = np.ascontiguousarray(pks, np.int32)
+        if pks.ndim != 5 or pks.shape[0] != 2 or pks.shape[2:] != (int(t), 2, p.N):
+            raise ValueError(f"pks: expected int32[2][D][{t}][2][{p.N}], got shape {pks.shape}")
+        _check(lib().thfhe_cb_key_set(self.h, _p32(pks), pks.shape[1], int(t), int(basebit)))
+        self._cb_level2, self._cb_D = level2_cloud_key, pks.shape[1]
+
+    def cb_private_keyswitch(self, lwe2):
+        """Stage B of circuit bootstrapping alone: lwe2 int32[count][l][D+1], LWE samples under the level-2 ring key (record (s, j) of m g_j) ->
+        int32[count][2l][2][N], the TGSW rows of thfhe.keygen.SecretKeySet.tgsw_encrypt's layout."""
+        D = getattr(self, "_cb_D", None)
+        if D is None:
+            raise ThfheError("no circuit-bootstrap key: call cb_key_set first")
+        p = self.params
+        lwe2 = np.ascontiguousarray(lwe2, np.int32)
+        if lwe2.size % (p.l * (D + 1)) or lwe2.shape[-1] != D + 1:
+            raise ValueError(f"lwe2: expected int32[count][{p.l}][{D + 1}], got shape {lwe2.shape}")
+        count = lwe2.size // (p.l * (D + 1))
+        out = np.empty((count, 2 * p.l, 2, p.N), np.int32)
+        _check(lib().thfhe_cb_private_keyswitch(self.h, _p32(lwe2), count, _p32(out)))
+        return out
+
+    def cb_set_batch_threshold(self, min_inputs):
+        """Inputs (records of a launch) from which the private key switch runs on the matrix cores; 0 restores the default.  No word depends on it."""
+        _check(lib().thfhe_cb_set_batch_threshold(self.h, int(min_inputs)))
+
+    def circuit_bootstrap(self, recs, d, return_words=False):
+        """recs int32[count * d][n+1], gate-encoded records under this key's LWE key (sample-major: bit i of sample s is record s d + i) -> a TgswSet
+        of count samples of d bits, device-resident, for lhe_cmux / lhe_lookup / lhe_wfa / lhe_demux / lhe_scatter and the leveled DAG entry.
+        return_words: also the rows int32[count * d][2l][2][N], as (set, words)."""
+        l2 = getattr(self, "_cb_level2", None)
+        if l2 is None:
+            raise ThfheError("no circuit-bootstrap key: call cb_key_set first")
+        p = self.params
+        d = int(d)
+        recs = _rec(recs, self.words)
+        if d < 1 or recs.shape[0] == 0 or recs.shape[0] % d:
+            raise ValueError(f"recs: expected int32[count * d][{self.words}] with d = {d}")
+        count = recs.shape[0] // d
+        words = np.empty((count * d, 2 * p.l, 2, p.N), np.int32) if return_words else None
+        h = _vp()
+        _check(lib().thfhe_circuit_bootstrap(self.h, l2.h, _p32(recs), count, d, _p32(words), C.byref(h)))
+        tset = TgswSet._adopt(self, h, count, d)
+        return (tset, words) if return_words else tset
+
     def set_wfa_chunk(self, g):
         """States per workgroup of a step of lhe_wfa, 1 .. 64; 0: automatic.  No output word depends on it."""
         _check(lib().thfhe_set_wfa_chunk(self.h, int(g)))
@@ -1007,6 +1077,14 @@ class TgswSet(_Handle):
         h = _vp()
         _check(lib().thfhe_tgsw_set_create(ck.h, _p32(a), self.count, d, C.byref(h)))
         self._own(h, lib().thfhe_tgsw_set_destroy)
+
+    @classmethod
+    def _adopt(cls, ck, h, count, d):
+        """A set the library made itself (thfhe_circuit_bootstrap)."""
+        self = cls.__new__(cls)
+        self.ck, self.d, self.count = ck, d, count
+        self._own(h, lib().thfhe_tgsw_set_destroy)
+        return self
 
     def __enter__(self):
         return self

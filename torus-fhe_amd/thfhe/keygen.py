@@ -146,6 +146,48 @@ def gen_mk_pack_key(rng, in_key, rlwe_keys, t, basebit, sigma, chunk=1024, devic
     return pk.reshape(D, t, R, 2, N)
 
 
+def gen_cb_key(rng, rlwe2_key, tlwe_key, t, basebit, sigma, chunk=2048, device=None):
+    """The private key-switching key of circuit bootstrapping -> int32[2][D][t][2][N].  rlwe2_key: the level-2 ring key z2
+    (D small integers: the extracted LWE key of the level-2 rotation); tlwe_key: the level-1 ring key z.  Row (f, i, p) is a TLWE encryption of
+    zero under z -- mask alpha uniform, body alpha (*) z + e, e Gaussian of standard deviation `sigma` -- with z2[i] 2^(32 - (p+1) basebit) added to
+    coefficient 0 of the body (f = 1: the row encrypts the term) or of the mask (f = 0: its phase is -z times the term), the trick of
+    SecretKeySet._tgsw_encrypt.  A digit multiplies a row, so there is one row per (f, i, p), not one per digit value.
+    `sigma` is the caller's: a 32-bit level-1 ring needs about 2^-31 (section 4.21), which no security estimate of the named sets covers.
+    Exact products through polymul_small32, `chunk` rows at a time; device = d routes them through thfhe.PolyMac on MI355X number d.  The random
+    stream is drawn identically either way, so both give the same words."""
+    z2 = np.asarray(rlwe2_key, np.int64).reshape(-1)
+    z = np.asarray(tlwe_key, np.int32)
+    D, N = z2.shape[0], z.shape[0]
+    assert t >= 1 and 1 <= basebit <= 8 and t * basebit <= 32
+    rows = 2 * D * t
+    key = np.empty((rows, 2, N), np.int32)
+    i = np.tile(np.repeat(np.arange(D), t), 2)
+    p = np.tile(np.arange(t), 2 * D)
+    msg = z2[i] << (32 - (p + 1) * basebit)
+    pm = None
+    if device is not None:
+        from . import PolyMac
+        pm = PolyMac(N, 32, device)
+    for r0 in range(0, rows, chunk):
+        r1 = min(rows, r0 + chunk)
+        m = r1 - r0
+        alpha = rng.integers(-2**31, 2**31, size=(m, N), dtype=np.int64).astype(np.int32)
+        e = dtot32(rng.standard_normal((m, N)) * sigma)
+        if pm is not None:   # out[i] = e[i] + z (*) alpha[i]
+            beta = pm.mac(z[None, :], alpha, [(q, 0, q, 1) for q in range(m)], m, e).astype(np.int64)
+        else:
+            beta = polymul_small32(alpha, z).astype(np.int64) + e
+        f = (np.arange(r0, r1) >= D * t)
+        beta[:, 0] += np.where(f, msg[r0:r1], 0)
+        a64 = alpha.astype(np.int64)
+        a64[:, 0] += np.where(f, 0, msg[r0:r1])
+        key[r0:r1, 0] = a64.astype(np.uint32).view(np.int32)
+        key[r0:r1, 1] = beta.astype(np.uint32).view(np.int32)
+    if pm is not None:
+        pm.close()
+    return key.reshape(2, D, t, 2, N)
+
+
 def seed_seq_generate(seeds, count):
     """std::seed_seq(seeds).generate: `count` 32-bit words ([rand.util.seedseq], as libstdc++ implements it)."""
     v = [int(x) & 0xFFFFFFFF for x in seeds]
@@ -274,9 +316,12 @@ def rand_ternary(rng, shape):
 class MKSecretKeySet:
     """3-gen multi-key material following 3-gen-mk-tfhe/multikey_3gen.jl:15-30."""
 
-    def __init__(self, params, seed=0x5EED0001, sigma_lwe=None, sigma_bk=2.0**-30.70, sigma_ks=None, device=None):
+    def __init__(self, params, seed=0x5EED0001, sigma_lwe=None, sigma_bk=2.0**-30.70, sigma_ks=None, device=None, lwe_keys=None):
         """device = None: the ring products run on the host (float64 GEMMs on 22-bit limbs); device = d: on MI355X number d
-        (thfhe.PolyMac / thfhe_pm_mac).  The random stream is drawn identically either way, so both give the same key material bit for bit."""
+        (thfhe.PolyMac / thfhe_pm_mac).  The random stream is drawn identically either way, so both give the same key material bit for bit.
+        lwe_keys: int[P][n], the parties' LWE keys, given instead of drawn -- how the level-2 set of circuit bootstrapping shares the gate set's
+        key.  The keys are drawn all the same and discarded, so the rest of the stream does not depend on the argument; with None
+        every word is what it was."""
         p = self.params = params
         assert p.k == 1 and p.torus_bits == 64
         rng = np.random.default_rng(seed)
@@ -288,7 +333,9 @@ class MKSecretKeySet:
         self.sigma_lwe = sigma_lwe if sigma_lwe is not None else 2.0**-13.52
         sigma_ks = sigma_ks if sigma_ks is not None else self.sigma_lwe
         self.lwe_keys = rng.integers(0, 2, (P, n)).astype(np.int32)          # SecretKey_3gen
-        self.rlwe_keys = rand_ternary(rng, (P, N))                            # RLweKey(rng, params, true)
+        if lwe_keys is not None:
+            self.lwe_keys = np.ascontiguousarray(lwe_keys, np.int32).reshape(P, n)
+        self.rlwe_keys = rand_ternary(rng, (P, N))                           # RLweKey(rng, params, true)
         crp = rng.integers(-2**63, 2**63, size=N, dtype=np.int64)             # CRP_3gen(a_same = true)
         # PublicKey b_q[i] = z_q (*) a + e ; CommonPubKey B[i] = sum_q b_q[i]
         B = np.zeros((l, N), np.uint64)
