@@ -208,10 +208,10 @@ int ctx_staged(Ctx *c, size_t words, const void *const (&src)[3], const size_t (
     THFHE_HIP(hipStreamSynchronize(c->stream));
     return THFHE_OK;
 }
-// ... and of a call that goes up and down in slices of at most S_max samples (the multi-value bootstraps), the caller having locked the context
-// and sized every buffer for S_max: per slice the operand records in[q] (null sources skipped) into stage.in[q] and, with `index`, the slice's
-// per-sample indices into d_index; run(S, last) enqueued; then the slice's S records of out_words words copied from `res` to their place in
-// `out`.  The stream is drained once, after the last slice.
+// ... and of a call that goes up and down in slices of at most S_max samples (the multi-value bootstraps and the trees, thfhe_pbs_host.h), the
+// caller having locked the context and sized every buffer for S_max: per slice the operand records in[q] (null sources skipped) into stage.in[q] and, with `index`, the slice's
+// per-sample indices into d_index; run(s0, S, last) enqueued (s0: the slice's first sample); then the slice's S records of out_words words copied
+// from `res` to their place in `out`.  The stream is drained once, after the last slice.
 template <typename Ctx, typename Run>
 int ctx_sliced(Ctx *c, size_t count, size_t S_max, const int32_t *const (&in)[3], const int32_t *index, int32_t *d_index, Run run, const int32_t *res,
                int32_t *out, size_t out_words) {
@@ -221,7 +221,7 @@ int ctx_sliced(Ctx *c, size_t count, size_t S_max, const int32_t *const (&in)[3]
         for (int q = 0; q < 3; q++)
             if (in[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), in[q] + s0 * words, S * words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         if (index) THFHE_HIP(hipMemcpyAsync(d_index, index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        THFHE_TRY(run(S, s0 + S == count));
+        THFHE_TRY(run(s0, S, s0 + S == count));
         THFHE_HIP(hipMemcpyAsync(out + s0 * out_words, res, S * out_words * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     }
     THFHE_HIP(hipStreamSynchronize(c->stream));

@@ -39,6 +39,7 @@
 #include "thfhe_lane.h"
 #include "thfhe_mk_shared.h"
 #include "thfhe_mk_pack.h"
+#include "thfhe_pbs_host.h"
 
 using namespace thfhe;
 
@@ -984,11 +985,14 @@ struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
 
 namespace {
 
-int mk_ensure_workspace(thfhe_mk_ctx *c, size_t jobs) {
+// workspace of `jobs` rotations: bara / barb, one extracted record each, the MUX halves; theta > 0: of PBS jobs with theta records each, plus
+// their accumulators
+int mk_ensure_workspace(thfhe_mk_ctx *c, size_t jobs, int theta = 0) {
     int rc = c->d_bara.grow(jobs * c->w_pad * sizeof(int32_t));
     if (!rc) rc = c->d_barb.grow(jobs * sizeof(int32_t));
-    if (!rc) rc = c->d_u.grow(jobs * ((size_t)c->p.N + 1) * sizeof(int32_t));
+    if (!rc) rc = c->d_u.grow(jobs * std::max(theta, 1) * ((size_t)c->p.N + 1) * sizeof(int32_t));
     if (!rc) rc = c->d_tmp.grow(jobs * c->rec_words() * sizeof(int32_t));
+    if (!rc && theta) rc = c->d_acc.grow(jobs * 2 * (size_t)c->p.N * sizeof(int64_t));
     return rc;
 }
 
@@ -1025,15 +1029,7 @@ int mk_enqueue_bootstraps(thfhe_mk_ctx *c, const int32_t *d0, const int32_t *d1,
     return THFHE_OK;
 }
 
-// workspace of a programmable bootstrap of `count` samples with theta outputs each: bara / barb, count x theta extracted records, accumulators
-int mk_lut_workspace(thfhe_mk_ctx *c, size_t count, int theta) {
-    int rc = mk_ensure_workspace(c, count);
-    if (!rc) rc = c->d_u.grow(count * theta * ((size_t)c->p.N + 1) * sizeof(int32_t));
-    if (!rc) rc = c->d_acc.grow(count * 2 * (size_t)c->p.N * sizeof(int64_t));
-    return rc;
-}
-
-// One PBS stage on the context's stream, the workspace sized by the caller (mk_lut_workspace): the prologue of `jobs` jobs of `src`, the
+// One PBS stage on the context's stream, the workspace sized by the caller (mk_ensure_workspace with theta): the prologue of `jobs` jobs of `src`, the
 // accumulator start from each job's table of d_tv, the rotation of mk_bootstrap_3gen, extraction of theta coefficients into d_u [jobs][theta][N+1];
 // then, with ks_dst, the key switch of the jobs x theta records into it.  A source that writes no table index rotates on d_idx (null: table 0).
 // timed: the profiling events of a flat call (prologue + accumulator start | rotation + extraction | key switch); a gate-DAG run records none.
@@ -1041,8 +1037,8 @@ int mk_lut_workspace(thfhe_mk_ctx *c, size_t count, int theta) {
 // mv: every job rotates the ONE base vector d_tv (theta is 1), the index picks its factor table, and the extraction is
 // mk_extract_mv_kernel's mv->q records per job, d_u [jobs][q][N+1].
 template <typename Src>
-int mk_enqueue_pbs(thfhe_mk_ctx *c, const Src &src, size_t jobs, const int64_t *d_tv, int theta, const int32_t *d_idx, int32_t *ks_dst, bool timed = false,
-                   const MkMvArgs *mv = nullptr, const int64_t *d_tva = nullptr) {
+int mk_enqueue_pbs(thfhe_mk_ctx *c, const Src &src, size_t jobs, const int64_t *d_tv, const int64_t *d_tva, int theta, const int32_t *d_idx, int32_t *ks_dst,
+                   bool timed = false, const MkMvArgs *mv = nullptr) {
     const int N = c->p.N;
     const bool ev = timed && c->profiling;
     int32_t *const idx = c->d_lut_idx.as<int32_t>();
@@ -1249,47 +1245,17 @@ int mk_dag_gate_class(thfhe_mk_ctx *c, int cls, const int32_t *d_ops, size_t n) 
     return mk_gates_dev_locked(c, cls == kDagMux ? THFHE_MUX : THFHE_AND3, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), c->stage.out_ptr(), n);
 }
 
-// dag_execute's ensure: workspace and staging for slices of max_gates gates; theta_max > 0: a run with LUT groups of up to theta_max records per node
+// dag_execute's ensure (dag_ensure, thfhe_pbs_host.h) on this engine's workspace
 int mk_dag_ensure(thfhe_mk_ctx *c, size_t max_gates, int theta_max, int32_t **in, int32_t **out) {
-    const size_t words = c->rec_words();
-    int r = mk_ensure_workspace(c, 2 * max_gates);
-    if (!r && theta_max) r = mk_lut_workspace(c, max_gates, theta_max);
-    if (!r && theta_max) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
-    if (!r) r = c->stage.grow(max_gates * words);
-    if (!r && theta_max) r = c->stage.out.grow(theta_max * max_gates * words * sizeof(int32_t));   // key switch of nodes x theta records
-    in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
-    return r;
+    return dag_ensure(c, max_gates, theta_max, in, out, [&](size_t jobs, int theta) { return mk_ensure_workspace(c, jobs, theta); });
 }
 
-constexpr int kMaxEncLuts = 262144;   // tables of one thfhe_mk_lut_bootstrap_enc call, rows of one tree call
-
-// thfhe_mk_lut_bootstrap (keyswitch) / thfhe_mk_lut_bootstrap_wo_keyswitch: out = count x theta records of P n + 1 (resp. N + 1) words
-// enc: thfhe_mk_lut_bootstrap_enc(_wo_keyswitch), the tables are RLWE samples (tv_a, tv) under Z and up to kMaxEncLuts of them
+// thfhe_mk_lut_bootstrap(_enc)(_wo_keyswitch): ctx_lut_bootstrap (thfhe_pbs_host.h) on this engine's workspace and PBS stage; the encrypted tables
+// are RLWE samples (tv_a, tv) under Z
 int mk_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
                      const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch, bool enc = false, const int64_t *tv_a = nullptr) {
-    if (enc && !tv_a) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    int rc = lut_validate(sp, tv, n_luts, lut_index, in0, in1, in2, out, count, enc ? kMaxEncLuts : 1024);
-    if (rc) return rc;
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (count == 0) return THFHE_OK;
-    const thfhe_lut_spec s = *sp;
-    const size_t rec = c->rec_words(), in_words = count * rec, outs = count * s.theta, N = c->p.N;
-    const size_t in_bytes = in_words * sizeof(int32_t);
-    const size_t out_bytes = outs * (keyswitch ? rec : N + 1) * sizeof(int32_t);
-    const size_t stage_words = keyswitch ? outs * rec : in_words;   // the key switch writes count x theta records into stage.out
-    return ctx_staged(c, stage_words, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, {in_bytes, in_bytes, in_bytes}, [&] {
-        int r = c->d_tv.grow((size_t)n_luts * N * sizeof(int64_t));
-        if (!r && enc) r = c->d_tva.grow((size_t)n_luts * N * sizeof(int64_t));
-        if (!r && lut_index) r = c->d_lut_idx.grow(count * sizeof(int32_t));
-        if (r) return r;
-        THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv, (size_t)n_luts * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        if (enc) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int64_t>(), tv_a, (size_t)n_luts * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        if (lut_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), lut_index, count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        THFHE_TRY(mk_lut_workspace(c, count, s.theta));
-        return mk_enqueue_pbs(c, LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, count, c->d_tv.as<int64_t>(),
-                              s.theta, lut_index ? c->d_lut_idx.as<int32_t>() : nullptr, keyswitch ? c->stage.out_ptr() : nullptr, true, nullptr,
-                              enc ? c->d_tva.as<int64_t>() : nullptr);
-    }, keyswitch ? c->stage.out : c->d_u, out, out_bytes);
+    return ctx_lut_bootstrap(c, sp, tv, tv_a, enc, n_luts, lut_index, in0, in1, in2, out, count, keyswitch,
+                             [&](size_t jobs, int theta) { return mk_ensure_workspace(c, jobs, theta); }, [&](auto &&...a) { return mk_enqueue_pbs(c, a...); });
 }
 
 // ---- the packing key switch and the two-digit tree ----
@@ -1348,26 +1314,8 @@ int mk_pack_boxes(thfhe_mk_ctx *c, const int32_t *recs, size_t count, int p, int
     return THFHE_OK;
 }
 
-// host checks of a tree call that need no context: pointers, both specs, p_hi, theta_lo | p_hi, the tables and their indices
-int mk_tree_validate(const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, const int64_t *tv1, int n_tables, const int32_t *table_index,
-                     const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2,
-                     const int32_t *out, size_t count) {
-    if (!spec_lo || !spec_hi || !tv1 || !lo0 || !hi0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    THFHE_TRY(lut_spec_check(*spec_lo));
-    THFHE_TRY(lut_spec_check(*spec_hi));
-    if ((spec_lo->n_inputs > 1 && !lo1) || (spec_lo->n_inputs > 2 && !lo2) || (spec_hi->n_inputs > 1 && !hi1) || (spec_hi->n_inputs > 2 && !hi2))
-        return thfhe_fail(THFHE_E_INVALID, "null operand: the spec names more inputs");
-    if (spec_hi->theta != 1) return thfhe_fail(THFHE_E_INVALID, "tree: spec_hi theta must be 1 (the packed table holds one function)");
-    if (p_hi < 2 || p_hi > 64 || (p_hi & (p_hi - 1))) return thfhe_fail(THFHE_E_INVALID, "tree: p_hi must be a power of two in 2 .. 64");
-    if (p_hi % spec_lo->theta) return thfhe_fail(THFHE_E_INVALID, "tree: spec_lo theta must divide p_hi");
-    if (n_tables < 1 || (size_t)n_tables * (p_hi / spec_lo->theta) > (size_t)kMaxEncLuts)
-        return thfhe_fail(THFHE_E_INVALID, "tree: n_tables must be >= 1 and n_tables * p_hi / theta <= 262144");
-    if (count > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "count too large");
-    if (table_index)
-        for (size_t g = 0; g < count; g++)
-            if (table_index[g] < 0 || table_index[g] >= n_tables) return thfhe_fail(THFHE_E_INVALID, "table_index out of range (0 .. n_tables-1)");
-    return THFHE_OK;
-}
+// what tree_validate_rows (thfhe_pbs_host.h) admits here: p_hi up to the 64 records one packing takes
+constexpr TreeRules kMkTreeRules{64, "tree: p_hi must be a power of two in 2 .. 64", "tree: n_tables must be >= 1 and n_tables * p_hi / theta <= 262144"};
 
 // thfhe_mk_tree_lut_bootstrap: per slice of S samples three stages on the context's stream, nothing visiting the host in between --
 //   level 1    S R many-LUT rotations (R = p_hi / theta_lo) of the plaintext rows tv1[table[s]][r] on the `lo` operands, no key switch: the S p_hi
@@ -1389,7 +1337,7 @@ int mk_tree_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec &lo, const thfhe_lut
     const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / p_hi));
     const size_t tv_bytes = (size_t)n_tables * R * N * sizeof(int64_t);
     int rc = c->d_tv.grow(tv_bytes);
-    if (!rc) rc = mk_lut_workspace(c, S_max * R, lo.theta);
+    if (!rc) rc = mk_ensure_workspace(c, S_max * R, lo.theta);
     if (!rc) rc = c->d_lut_idx.grow(S_max * R * sizeof(int32_t));
     if (!rc) rc = mk_pack_reserve(c, S_max * p_hi);
     if (!rc) rc = c->d_tab_a.grow(S_max * N * sizeof(int64_t));
@@ -1399,68 +1347,37 @@ int mk_tree_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec &lo, const thfhe_lut
     if (rc) return rc;
     hipStream_t st = c->stream;
     THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv1, tv_bytes, hipMemcpyHostToDevice, st));
-    const int32_t *lo_in[3] = {lo0, lo.n_inputs > 1 ? lo1 : nullptr, lo.n_inputs > 2 ? lo2 : nullptr};
-    const int32_t *hi_in[3] = {hi0, hi.n_inputs > 1 ? hi1 : nullptr, hi.n_inputs > 2 ? hi2 : nullptr};
     const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);
-    for (size_t s0 = 0; s0 < count; s0 += S_max) {
-        const size_t S = std::min(S_max, count - s0), in_bytes = S * words * sizeof(int32_t);
-        const bool ev = c->profiling && s0 + S == count;   // profiling, on the last slice: level 1 | packing | selection
-        auto upload = [&](const int32_t *const *h) {
-            for (int q = 0; q < 3; q++)
-                if (h[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), h[q] + s0 * words, in_bytes, hipMemcpyHostToDevice, st));
-            return (int)THFHE_OK;
-        };
-        THFHE_TRY(upload(lo_in));
-        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_tree_tab.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const LutFlatSrc<LutIdx::table> lo_src{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr};
+    const LutFlatSrc<LutIdx::job> hi_src{in0, in1, in2, hi, 1, nullptr};
+    return ctx_tree_sliced(c, count, S_max, lo, hi, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, 1, [&](size_t S, bool, bool last, auto upload_hi) {
+        const bool ev = c->profiling && last;   // profiling, on the last slice: level 1 | packing | selection
         if (ev) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        THFHE_TRY(mk_enqueue_pbs(c, LutFlatSrc<LutIdx::table>{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr}, S * R, c->d_tv.as<int64_t>(),
-                                 lo.theta, nullptr, nullptr));
+        THFHE_TRY(mk_enqueue_pbs(c, lo_src, S * R, c->d_tv.as<int64_t>(), nullptr, lo.theta, nullptr, nullptr));
         if (ev) THFHE_HIP(hipEventRecord(c->ev[1], st));
         THFHE_TRY(mk_pack_enqueue(c, c->d_u.as<int32_t>(), S * p_hi, p_hi, c->d_tab_a.as<int64_t>(), c->d_tab_b.as<int64_t>()));
         if (ev) THFHE_HIP(hipEventRecord(c->ev[2], st));
-        THFHE_TRY(upload(hi_in));
-        THFHE_TRY(mk_enqueue_pbs(c, LutFlatSrc<LutIdx::job>{in0, in1, in2, hi, 1, nullptr}, S, c->d_tab_b.as<int64_t>(), 1, nullptr, c->stage.out_ptr(), false, nullptr,
-                                 c->d_tab_a.as<int64_t>()));
+        THFHE_TRY(upload_hi());
+        THFHE_TRY(mk_enqueue_pbs(c, hi_src, S, c->d_tab_b.as<int64_t>(), c->d_tab_a.as<int64_t>(), 1, nullptr, c->stage.out_ptr()));
         if (ev) {
             THFHE_HIP(hipEventRecord(c->ev[3], st));
             c->ev_valid = true;
         }
-        THFHE_HIP(hipMemcpyAsync(out + s0 * words, c->stage.out_ptr(), in_bytes, hipMemcpyDeviceToHost, st));
-    }
-    THFHE_HIP(hipStreamSynchronize(st));
-    return THFHE_OK;
+        return (int)THFHE_OK;
+    });
 }
 
-// thfhe_mk_mv_lut_bootstrap (keyswitch) / thfhe_mk_mv_lut_bootstrap_wo_keyswitch: out = count x q records of P n + 1 (resp. N + 1) words,
-// in slices of at most mv_slice records (at least one sample): only a slice's inputs go up and only its records come down.
+// thfhe_mk_mv_lut_bootstrap(_wo_keyswitch): ctx_mv_lut_bootstrap (thfhe_pbs_host.h) in slices of at most mv_slice records, one stage
+// with the multi-value epilogue per slice
 int mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *tv0, const int32_t *factors, int p, int q, int n_tables,
                         const int32_t *table_index, int64_t out_bias, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count,
                         bool keyswitch) {
-    if (!factors) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    THFHE_TRY(lut_validate(sp, tv0, n_tables, table_index, in0, in1, in2, out, count));
-    THFHE_TRY(mv_validate(*sp, p, q, n_tables));
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (count == 0) return THFHE_OK;
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    const thfhe_lut_spec s = *sp;
-    const size_t words = c->rec_words(), N = c->p.N;
-    const size_t S_max = std::min(count, std::max<size_t>(1, c->mv_slice / q));
-    const size_t w_bytes = (size_t)n_tables * q * p * sizeof(int32_t);
-    int rc = mk_lut_workspace(c, S_max, q);
-    if (!rc) rc = c->stage.grow(keyswitch ? S_max * q * words : S_max * words);   // the key switch writes S x q records into stage.out
-    if (!rc) rc = c->d_tv.grow(N * sizeof(int64_t));
-    if (!rc) rc = c->d_mv_w.grow(w_bytes);
-    if (!rc && table_index) rc = c->d_lut_idx.grow(S_max * sizeof(int32_t));
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv0, N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, c->stream));
-    const MkMvArgs mv{c->d_mv_w.as<int32_t>(), p, q, out_bias};
-    int32_t *const d_idx = c->d_lut_idx.as<int32_t>();
-    return ctx_sliced(c, count, S_max, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, table_index, d_idx, [&](size_t S, bool last) {
-        return mk_enqueue_pbs(c, LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, S, c->d_tv.as<int64_t>(), 1,
-                              table_index ? d_idx : nullptr, keyswitch ? c->stage.out_ptr() : nullptr, last, &mv);
-    }, keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>(), out, q * (keyswitch ? words : N + 1));
+    return ctx_mv_lut_bootstrap(c, sp, tv0, factors, p, q, n_tables, table_index, in0, in1, in2, out, count, keyswitch, &thfhe_mk_ctx::mv_slice,
+                                [&](size_t jobs, int theta) { return mk_ensure_workspace(c, jobs, theta); },
+                                [&](const auto &src, size_t S, const int32_t *d_idx, int32_t *ks_dst, bool last) {
+                                    const MkMvArgs mv{c->d_mv_w.as<int32_t>(), p, q, out_bias};
+                                    return mk_enqueue_pbs(c, src, S, c->d_tv.as<int64_t>(), nullptr, 1, d_idx, ks_dst, last, &mv);
+                                });
 }
 
 // The six-column entries of the 3-gen executor (F: the entry's families and the generations it admits): the host checks and the plan before the
@@ -1484,7 +1401,7 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
     for (const DagBatch &b : plan.batches) {   // every buffer an MV group's slices use, the staging output included, before dag_execute takes pointers
         if (b.cls != kDagMv) continue;
         const size_t S = mv_slice_of(b.tree, b.count * instances), q = (size_t)F.mvs[b.tree].q;
-        THFHE_TRY(mk_lut_workspace(c, S, (int)q));
+        THFHE_TRY(mk_ensure_workspace(c, S, (int)q));
         THFHE_TRY(c->d_lut_idx.grow(S * sizeof(int32_t)));
         THFHE_TRY(c->stage.out.grow(S * q * words * sizeof(int32_t)));
     }
@@ -1497,7 +1414,7 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
         [&](size_t max_gates, int32_t **in, int32_t **out) { return mk_dag_ensure(c, max_gates, plan.max_theta, in, out); },
         [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); },
         [&](int theta, const DagLutSlice &s) {
-            return mk_enqueue_pbs(c, s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, c->d_tv.as<int64_t>(), theta, nullptr, c->stage.out_ptr());
+            return mk_enqueue_pbs(c, s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, c->d_tv.as<int64_t>(), nullptr, theta, nullptr, c->stage.out_ptr());
         },
         [&](const DagExtGroup &g) -> int {   // the plan of this engine holds no other grouped kind; t_y = each node's table
             if (g.cls != kDagMv) return thfhe_fail(THFHE_E_INVALID, "grouped node kind not defined for the 3-gen engine");
@@ -1506,7 +1423,7 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
             const MkMvArgs mv{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p, m.q, mv_out_bias ? mv_out_bias[g.tree] : 0};
             return dag_group_slices(g, mv_slice_of(g.tree, (size_t)g.all), m.q, c->stage.out_ptr(), words, st, [&](long first, long S) {
                 const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
-                return mk_enqueue_pbs(c, lo, (size_t)S, tv0, 1, nullptr, c->stage.out_ptr(), false, &mv);
+                return mk_enqueue_pbs(c, lo, (size_t)S, tv0, nullptr, 1, nullptr, c->stage.out_ptr(), false, &mv);
             });
         });
 }
@@ -1798,7 +1715,7 @@ int thfhe_mk_tree_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *spec_lo, 
                                 const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
                                 const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
     // host checks, before the context is looked at
-    THFHE_TRY(mk_tree_validate(spec_lo, spec_hi, p_hi, tv1, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count));
+    THFHE_TRY(tree_validate_rows(kMkTreeRules, spec_lo, spec_hi, p_hi, tv1, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count));
     return mk_tree_bootstrap(c, *spec_lo, *spec_hi, p_hi, tv1, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
 }
 

@@ -35,6 +35,7 @@
 #include "thfhe_keyswitch.h"
 #include "thfhe_lane.h"
 #include "thfhe_pack.h"
+#include "thfhe_pbs_host.h"
 #include "thfhe_ring_schedule.h"
 
 using namespace thfhe;
@@ -599,12 +600,11 @@ struct THFHE_INTERNAL thfhe_tgsw_set {
 
 namespace {
 
-constexpr int kMaxEncLuts = 1 << 18;   // encrypted tables per call (2 GiB of TLWE samples): every sample may bring its own
-
-int ensure_workspace(thfhe_ctx *c, size_t jobs) {
+// workspace of `jobs` rotations: bara / barb and one extracted record each; theta > 0: of PBS jobs with theta records each
+int ensure_workspace(thfhe_ctx *c, size_t jobs, int theta = 0) {
     int rc = c->d_bara.grow(jobs * c->n_pad * sizeof(int32_t));
     if (!rc) rc = c->d_barb.grow(jobs * sizeof(int32_t));
-    if (!rc) rc = c->d_u.grow(jobs * 1025 * sizeof(int32_t));
+    if (!rc) rc = c->d_u.grow(jobs * std::max(theta, 1) * ((size_t)c->p.N + 1) * sizeof(int32_t));
     return rc;
 }
 
@@ -739,16 +739,6 @@ int enqueue_pbs(thfhe_ctx *c, const Src &src, size_t jobs, const int32_t *tv, co
     return ks_dst ? enqueue_keyswitch(c, c->d_u.as<int32_t>(), ks_dst, jobs * theta, 1, timed) : THFHE_OK;
 }
 
-// programmable bootstrap of `count` samples from contiguous operand arrays: count x theta records of N+1 words into c->d_u and, with ks_dst,
-// key-switched into it; d_tva: the masks of encrypted tables (d_tv their bodies), or null: plaintext tables
-int enqueue_lut_rotations(thfhe_ctx *c, const thfhe_lut_spec &sp, const int32_t *d0, const int32_t *d1, const int32_t *d2, size_t count,
-                          const int32_t *d_tv, const int32_t *d_idx, const int32_t *d_tva, int32_t *ks_dst) {
-    int rc = ensure_workspace(c, count);
-    if (!rc) rc = c->d_u.grow(count * sp.theta * 1025 * sizeof(int32_t));
-    if (rc) return rc;
-    return enqueue_pbs(c, LutFlatSrc<LutIdx::none>{d0, d1, d2, sp, 1, nullptr}, count, d_tv, d_tva, sp.theta, d_idx, ks_dst, true);
-}
-
 int gates_dev_locked(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1, const int32_t *d2, int32_t *dout, size_t count) {
     if (count == 0) return THFHE_OK;
     if (count > (size_t)INT32_MAX / 4) return thfhe_fail(THFHE_E_INVALID, "count too large");
@@ -779,45 +769,24 @@ int dag_gate_class(thfhe_ctx *c, int cls, const int32_t *d_ops, size_t n) {
     return r;
 }
 
-// thfhe_lut_bootstrap (keyswitch) / thfhe_lut_bootstrap_wo_keyswitch: out = count x theta records of n+1 (resp. N+1) words.
-// enc: thfhe_lut_bootstrap_enc(_wo_keyswitch), the tables are TLWE samples (tv_a, tv) and up to kMaxEncLuts of them
+// thfhe_lut_bootstrap(_enc)(_wo_keyswitch): ctx_lut_bootstrap (thfhe_pbs_host.h) on this engine's workspace and PBS stage
 int lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv, int n_luts, const int32_t *lut_index, const int32_t *in0,
                   const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch, bool enc = false, const int32_t *tv_a = nullptr) {
-    if (enc && !tv_a) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    int rc = lut_validate(sp, tv, n_luts, lut_index, in0, in1, in2, out, count, enc ? kMaxEncLuts : 1024);
-    if (rc) return rc;
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (count == 0) return THFHE_OK;
-    const thfhe_lut_spec s = *sp;
-    const size_t in_words = count * c->rec_words(), outs = count * s.theta;
-    const size_t in_bytes = in_words * sizeof(int32_t);
-    const size_t out_bytes = outs * (keyswitch ? c->rec_words() : c->p.N + 1) * sizeof(int32_t);
-    const size_t stage_words = keyswitch ? outs * c->rec_words() : in_words;   // the key switch writes count x theta records into stage.out
-    return ctx_staged(c, stage_words, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, {in_bytes, in_bytes, in_bytes}, [&] {
-        int r = c->d_tv.grow((size_t)n_luts * 1024 * sizeof(int32_t));
-        if (!r && enc) r = c->d_tva.grow((size_t)n_luts * 1024 * sizeof(int32_t));
-        if (!r && lut_index) r = c->d_lut_idx.grow(count * sizeof(int32_t));
-        if (r) return r;
-        THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        if (enc) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int32_t>(), tv_a, (size_t)n_luts * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        if (lut_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), lut_index, count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        return enqueue_lut_rotations(c, s, c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), count, c->d_tv.as<int32_t>(),
-                                     lut_index ? c->d_lut_idx.as<int32_t>() : nullptr, enc ? c->d_tva.as<int32_t>() : nullptr,
-                                     keyswitch ? c->stage.out_ptr() : nullptr);
-    }, keyswitch ? c->stage.out : c->d_u, out, out_bytes);
+    return ctx_lut_bootstrap(c, sp, tv, tv_a, enc, n_luts, lut_index, in0, in1, in2, out, count, keyswitch,
+                             [&](size_t jobs, int theta) { return ensure_workspace(c, jobs, theta); }, [&](auto &&...a) { return enqueue_pbs(c, a...); });
 }
 
 // Grow-only workspace of one tree chain over S samples / nodes: S R level-1 jobs of theta_lo records each (a SELECT group, whose candidates are
 // gathered: R = theta_lo = 1, the selection rotation alone), their S k p candidates, S k packed tables and selection jobs (k tables per sample,
 // R = 1, theta_lo = k p).
 int tree_workspace(thfhe_ctx *c, size_t S, size_t p, size_t R, size_t theta_lo, size_t k = 1) {
-    const size_t jobs = S * std::max(R, k);
+    const size_t jobs = S * std::max(R, k), N = c->p.N;
     int rc = ensure_workspace(c, jobs);
-    if (!rc) rc = c->d_u.grow(std::max(S * R * theta_lo, S * k) * 1025 * sizeof(int32_t));
+    if (!rc) rc = c->d_u.grow(std::max(S * R * theta_lo, S * k) * (N + 1) * sizeof(int32_t));
     if (!rc) rc = c->d_lut_idx.grow(jobs * sizeof(int32_t));
     if (!rc) rc = c->d_tree_lwe.grow(S * k * p * c->rec_words() * sizeof(int32_t));
-    if (!rc) rc = c->d_tree_a.grow(S * k * 1024 * sizeof(int32_t));
-    if (!rc) rc = c->d_tree_b.grow(S * k * 1024 * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_a.grow(S * k * N * sizeof(int32_t));
+    if (!rc) rc = c->d_tree_b.grow(S * k * N * sizeof(int32_t));
     return rc;
 }
 
@@ -844,16 +813,9 @@ int enqueue_tree_chain(thfhe_ctx *c, thfhe_poly_ctx *pc, const Lo &lo, const int
 // ---- gate-DAG entry points: what thfhe_dag_run_batch, thfhe_dag_run_lut_batch and thfhe_dag_run_tree_batch share ----
 int sk_dag_classify(int op) { return op == THFHE_NOT || op == THFHE_COPY ? kDagLinear : (op == THFHE_MUX ? kDagMux : (op >= THFHE_NAND && op <= THFHE_ORYN ? kDagGate2 : -1)); }
 
-// dag_execute's ensure: workspace and staging for slices of max_gates gates; theta_max > 0: a run with LUT groups of up to theta_max records per node
+// dag_execute's ensure (dag_ensure, thfhe_pbs_host.h) on this engine's workspace
 int sk_dag_ensure(thfhe_ctx *c, size_t max_gates, int theta_max, int32_t **in, int32_t **out) {
-    const size_t words = c->rec_words();
-    int r = ensure_workspace(c, 2 * max_gates);
-    if (!r && theta_max) r = c->d_u.grow(theta_max * max_gates * 1025 * sizeof(int32_t));
-    if (!r && theta_max) r = c->d_lut_idx.grow(max_gates * sizeof(int32_t));
-    if (!r) r = c->stage.grow(max_gates * words);
-    if (!r && theta_max) r = c->stage.out.grow(theta_max * max_gates * words * sizeof(int32_t));   // key switch of nodes x theta records
-    in[0] = c->stage.in_ptr(0), in[1] = c->stage.in_ptr(1), in[2] = c->stage.in_ptr(2), *out = c->stage.out_ptr();
-    return r;
+    return dag_ensure(c, max_gates, theta_max, in, out, [&](size_t jobs, int theta) { return ensure_workspace(c, jobs, theta); });
 }
 
 // the leveled groups of a run (thfhe_dag_lhe.h, after the leveled kernels)
@@ -885,8 +847,7 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
                 THFHE_TRY(tree_workspace(c, S, q, 1, k * q, k));
                 w_cand = std::max(w_cand, S * k * q);
             } else {
-                THFHE_TRY(ensure_workspace(c, S));
-                THFHE_TRY(c->d_u.grow(S * q * 1025 * sizeof(int32_t)));
+                THFHE_TRY(ensure_workspace(c, S, (int)q));
                 THFHE_TRY(c->d_lut_idx.grow(S * sizeof(int32_t)));
             }
             THFHE_TRY(c->stage.out.grow(S * (b.cls == kDagTreeMv ? k : q) * words * sizeof(int32_t)));
@@ -969,25 +930,8 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
 }
 
 // ---- what thfhe_tree_lut_bootstrap and thfhe_tree_lut_bootstrap_mv share ----
-// host checks of a tree call that need no context: pointers, both specs, p_hi
-int tree_validate(const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, const int32_t *tv, const int32_t *lo0, const int32_t *lo1,
-                  const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, const int32_t *out) {
-    if (!spec_lo || !spec_hi || !tv || !lo0 || !hi0 || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    THFHE_TRY(lut_spec_check(*spec_lo));
-    THFHE_TRY(lut_spec_check(*spec_hi));
-    if ((spec_lo->n_inputs > 1 && !lo1) || (spec_lo->n_inputs > 2 && !lo2) || (spec_hi->n_inputs > 1 && !hi1) || (spec_hi->n_inputs > 2 && !hi2))
-        return thfhe_fail(THFHE_E_INVALID, "null operand: the spec names more inputs");
-    if (spec_hi->theta != 1) return thfhe_fail(THFHE_E_INVALID, "tree: spec_hi theta must be 1 (the packed table holds one function)");
-    if (p_hi < 2 || p_hi > 512 || (p_hi & (p_hi - 1))) return thfhe_fail(THFHE_E_INVALID, "tree: p_hi must be a power of two in 2 .. N/2");
-    return THFHE_OK;
-}
-int tree_validate_index(const int32_t *table_index, int n_tables, size_t count) {
-    if (count > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "count too large");
-    if (table_index)
-        for (size_t g = 0; g < count; g++)
-            if (table_index[g] < 0 || table_index[g] >= n_tables) return thfhe_fail(THFHE_E_INVALID, "table_index out of range (0 .. n_tables-1)");
-    return THFHE_OK;
-}
+// what tree_validate (thfhe_pbs_host.h) admits here: p_hi up to N / 2
+constexpr TreeRules kTreeRules{512, "tree: p_hi must be a power of two in 2 .. N/2", "tree: n_tables must be 1 .. 262144 / (p_hi / theta)"};
 
 // Two-digit tree PBS: per slice of S samples one enqueue_tree_chain on contiguous operands -- level 1 on the rows
 // tv[table[s]][r] (tv_rows rows of N words in all) and the `lo` operands, the selection on the `hi` operands.  Only the inputs of a slice go up and its
@@ -1008,7 +952,7 @@ int tree_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec &lo, c
     if (count == 0) return THFHE_OK;
     const int theta1 = factors ? k * p_hi : lo.theta, R = k * p_hi / theta1;   // level-1 records per rotation, rotations per sample
     const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / ((size_t)k * p_hi)));
-    const size_t tv_bytes = tv_rows * 1024 * sizeof(int32_t), w_bytes = factors ? (size_t)mv_tables * k * p_hi * mv_p * sizeof(int32_t) : 0;
+    const size_t tv_bytes = tv_rows * c->p.N * sizeof(int32_t), w_bytes = factors ? (size_t)mv_tables * k * p_hi * mv_p * sizeof(int32_t) : 0;
     int rc = c->d_tv.grow(tv_bytes);
     if (!rc && factors) rc = c->d_mv_w.grow(w_bytes);
     if (!rc) rc = tree_workspace(c, S_max, p_hi, R, theta1, k);
@@ -1020,68 +964,35 @@ int tree_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec &lo, c
     THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, tv_bytes, hipMemcpyHostToDevice, st));
     if (factors) THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
     const MvArgs mv{c->d_mv_w.as<int32_t>(), mv_p};
-    const int32_t *lo_in[3] = {lo0, lo.n_inputs > 1 ? lo1 : nullptr, lo.n_inputs > 2 ? lo2 : nullptr};
-    const int32_t *hi_in[3] = {hi0, hi.n_inputs > 1 ? hi1 : nullptr, hi.n_inputs > 2 ? hi2 : nullptr};
     const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);   // `lo`, then `hi` operands of the slice
-    for (size_t s0 = 0; s0 < count; s0 += S_max) {
-        const size_t S = std::min(S_max, count - s0), in_bytes = S * words * sizeof(int32_t);
-        const bool first = s0 == 0, last = s0 + S == count;
-        auto upload = [&](const int32_t *const *h) {
-            for (int q = 0; q < 3; q++)
-                if (h[q]) THFHE_HIP(hipMemcpyAsync(c->stage.in_ptr(q), h[q] + s0 * words, in_bytes, hipMemcpyHostToDevice, st));
-            return (int)THFHE_OK;
-        };
-        THFHE_TRY(upload(lo_in));
-        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_tree_tab.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const LutFlatSrc<LutIdx::table> lo_src{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr};
+    const LutFlatSrc<LutIdx::job> hi_src{in0, in1, in2, hi, k, nullptr};
+    return ctx_tree_sliced(c, count, S_max, lo, hi, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, (size_t)k, [&](size_t S, bool first, bool last, auto upload_hi) {
+        // profiling: ev[0] on the first slice; level 1 | packing | selection on the last
         if (c->profiling && first) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        // profiling, on the last slice: level 1 | packing | selection.  The `hi` operands replace the `lo` ones in the staging arrays once level 1 is enqueued.
         auto seam = [&](int stage) {
             if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[stage], st));
-            return stage == 2 ? upload(hi_in) : (int)THFHE_OK;
+            return stage == 2 ? upload_hi() : (int)THFHE_OK;
         };
-        THFHE_TRY(enqueue_tree_chain(c, pc, LutFlatSrc<LutIdx::table>{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr},
-                                     c->d_tv.as<int32_t>(), theta1, LutFlatSrc<LutIdx::job>{in0, in1, in2, hi, k, nullptr}, S, p_hi, c->stage.out_ptr(), seam,
-                                     factors ? &mv : nullptr, (size_t)k));
+        THFHE_TRY(enqueue_tree_chain(c, pc, lo_src, c->d_tv.as<int32_t>(), theta1, hi_src, S, p_hi, c->stage.out_ptr(), seam, factors ? &mv : nullptr, (size_t)k));
         if (c->profiling && last) {
             THFHE_HIP(hipEventRecord(c->ev[3], st));
             c->ev_valid = true;
         }
-        THFHE_HIP(hipMemcpyAsync(out + s0 * k * words, c->stage.out_ptr(), in_bytes * k, hipMemcpyDeviceToHost, st));
-    }
-    THFHE_HIP(hipStreamSynchronize(st));
-    return THFHE_OK;
+        return (int)THFHE_OK;
+    });
 }
 
-// thfhe_mv_lut_bootstrap (keyswitch) / thfhe_mv_lut_bootstrap_wo_keyswitch: out = count x q records of n+1 (resp. N+1) words, in slices
-// of at most tree_slice records: only a slice's inputs go up and its records come down.
+// thfhe_mv_lut_bootstrap(_wo_keyswitch): ctx_mv_lut_bootstrap (thfhe_pbs_host.h) in slices of at most tree_slice records, one kLutMv
+// stage of theta = q records per slice
 int mv_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv0, const int32_t *factors, int p, int q, int n_tables,
                      const int32_t *table_index, const int32_t *in0, const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch) {
-    if (!factors) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    THFHE_TRY(lut_validate(sp, tv0, n_tables, table_index, in0, in1, in2, out, count));
-    THFHE_TRY(mv_validate(*sp, p, q, n_tables));
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (count == 0) return THFHE_OK;
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    const thfhe_lut_spec s = *sp;
-    const size_t words = c->rec_words();
-    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / q));
-    const size_t w_bytes = (size_t)n_tables * q * p * sizeof(int32_t);
-    int rc = ensure_workspace(c, S_max);
-    if (!rc) rc = c->d_u.grow(S_max * q * 1025 * sizeof(int32_t));
-    if (!rc) rc = c->stage.grow(keyswitch ? S_max * q * words : S_max * words);   // the key switch writes S x q records into stage.out
-    if (!rc) rc = c->d_tv.grow(1024 * sizeof(int32_t));
-    if (!rc) rc = c->d_mv_w.grow(w_bytes);
-    if (!rc && table_index) rc = c->d_lut_idx.grow(S_max * sizeof(int32_t));
-    if (rc) return rc;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv0, 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, c->stream));
-    const MvArgs mv{c->d_mv_w.as<int32_t>(), p};
-    int32_t *const d_idx = c->d_lut_idx.as<int32_t>();
-    return ctx_sliced(c, count, S_max, {in0, s.n_inputs > 1 ? in1 : nullptr, s.n_inputs > 2 ? in2 : nullptr}, table_index, d_idx, [&](size_t S, bool last) {
-        return enqueue_pbs(c, LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, S, c->d_tv.as<int32_t>(), nullptr, q,
-                           table_index ? d_idx : nullptr, keyswitch ? c->stage.out_ptr() : nullptr, last, &mv);
-    }, keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>(), out, q * (keyswitch ? words : (size_t)c->p.N + 1));
+    return ctx_mv_lut_bootstrap(c, sp, tv0, factors, p, q, n_tables, table_index, in0, in1, in2, out, count, keyswitch, &thfhe_ctx::tree_slice,
+                                [&](size_t jobs, int theta) { return ensure_workspace(c, jobs, theta); },
+                                [&](const auto &src, size_t S, const int32_t *d_idx, int32_t *ks_dst, bool last) {
+                                    const MvArgs mv{c->d_mv_w.as<int32_t>(), p};
+                                    return enqueue_pbs(c, src, S, c->d_tv.as<int32_t>(), nullptr, q, d_idx, ks_dst, last, &mv);
+                                });
 }
 
 // What the six-column entries share (T: the entry's families and the generations of node kinds it admits): the host checks and the plan, the two
@@ -1345,12 +1256,8 @@ int thfhe_tree_lut_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_s
                              int n_tables, const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
                              const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
     // host checks, before either context is looked at
-    THFHE_TRY(tree_validate(spec_lo, spec_hi, p_hi, tv1, lo0, lo1, lo2, hi0, hi1, hi2, out));
-    if (p_hi % spec_lo->theta) return thfhe_fail(THFHE_E_INVALID, "tree: spec_lo theta must divide p_hi");
-    const int R = p_hi / spec_lo->theta;
-    if (n_tables < 1 || (long)n_tables * R > kMaxEncLuts) return thfhe_fail(THFHE_E_INVALID, "tree: n_tables must be 1 .. 262144 / (p_hi / theta)");
-    THFHE_TRY(tree_validate_index(table_index, n_tables, count));
-    return tree_bootstrap(c, pc, *spec_lo, *spec_hi, p_hi, tv1, (size_t)n_tables * R, nullptr, 0, 0, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
+    THFHE_TRY(tree_validate_rows(kTreeRules, spec_lo, spec_hi, p_hi, tv1, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count));
+    return tree_bootstrap(c, pc, *spec_lo, *spec_hi, p_hi, tv1, (size_t)n_tables * (p_hi / spec_lo->theta), nullptr, 0, 0, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
 }
 
 int thfhe_mv_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *spec, const int32_t *tv0, const int32_t *factors, int p, int q, int n_tables,
@@ -1369,7 +1276,7 @@ int thfhe_tree_lut_bootstrap_mv(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lu
                                 const int32_t *lo1, const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out,
                                 size_t count) {
     // host checks, before either context is looked at
-    THFHE_TRY(tree_validate(spec_lo, spec_hi, p_hi, tv0, lo0, lo1, lo2, hi0, hi1, hi2, out));
+    THFHE_TRY(tree_validate(kTreeRules, spec_lo, spec_hi, p_hi, tv0, lo0, lo1, lo2, hi0, hi1, hi2, out));
     if (!factors) return thfhe_fail(THFHE_E_INVALID, "null argument");
     THFHE_TRY(mv_validate(*spec_lo, p_lo, p_hi, n_tables));
     THFHE_TRY(tree_validate_index(table_index, n_tables, count));
@@ -1381,7 +1288,7 @@ int thfhe_tree_lut_bootstrap_mvk(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_l
                                  const int32_t *lo1, const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out,
                                  size_t count) {
     // host checks, before either context is looked at: those of thfhe_tree_lut_bootstrap_mv, then k and k p_hi
-    THFHE_TRY(tree_validate(spec_lo, spec_hi, p_hi, tv0, lo0, lo1, lo2, hi0, hi1, hi2, out));
+    THFHE_TRY(tree_validate(kTreeRules, spec_lo, spec_hi, p_hi, tv0, lo0, lo1, lo2, hi0, hi1, hi2, out));
     if (!factors) return thfhe_fail(THFHE_E_INVALID, "null argument");
     THFHE_TRY(mv_validate(*spec_lo, p_lo, p_hi, n_tables));
     THFHE_TRY(tree_validate_index(table_index, n_tables, count));

@@ -602,6 +602,48 @@ class _EvalKey(_Handle):
         spec = LutSpec(len(recs), (C.c_int32 * 3)(*[_wrap32(v) for v in w]), _wrap32(bias), int(theta))
         return recs, spec, [_p32(v) for v in recs] + [None] * (3 - len(recs))
 
+    # -- encrypted tables and the two-digit tree (thfhe_lut_bootstrap_enc / thfhe_mk_lut_bootstrap_enc) -----------------------
+    def lut_bootstrap_enc(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
+        """lut_bootstrap with ENCRYPTED tables: table t is the ring sample (tv_a[t], tv_b[t]) of [N] words each; up to 262 144 tables, so every
+        sample may bring its own.  CloudKey: int32 TLWE samples under the bootstrapping ring key (thfhe.lut.encrypt_table, or PackBoxes' output),
+        returns int32[count, theta, n+1].  MKCloudKey: int64 RLWE samples under the summed ring key (thfhe.lut.encrypt_table(..., torus_bits=64),
+        or pack_boxes' output), returns int32[count, theta, P*n+1]."""
+        return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, True)
+
+    def lut_bootstrap_enc_wo_keyswitch(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
+        """lut_bootstrap_enc without the key switch: int32[count, theta, N+1] records under the (MKCloudKey: coefficients of the summed) ring key."""
+        return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, False)
+
+    def _lut_enc(self, tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, keyswitch):
+        ins, spec, p = self._lut_args((x, y, z), weights, bias, theta, "lut_bootstrap_enc")
+        N = self.params.N
+        tv_a = np.ascontiguousarray(tv_a, self._tv_dtype).reshape(-1, N)
+        tv_b = np.ascontiguousarray(tv_b, self._tv_dtype).reshape(-1, N)
+        if tv_a.shape != tv_b.shape:
+            raise ValueError(f"tv_a and tv_b differ in shape: {tv_a.shape} vs {tv_b.shape}")
+        count = ins[0].shape[0]
+        idx = _index("lut_index", lut_index, count)
+        out = np.empty((count, _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
+        fn = self._fn("lut_bootstrap_enc" if keyswitch else "lut_bootstrap_enc_wo_keyswitch")
+        _check(fn(self.h, C.byref(spec), self._ptv(tv_a), self._ptv(tv_b), tv_a.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
+        return out
+
+    def _tree(self, ctxs, tv1, lo, hi, p_hi, weights_lo, bias_lo, theta, weights_hi, bias_hi, table_index):
+        """The marshalling both tree_lut_bootstrap methods share; ctxs: the contexts the engine's entry takes (CloudKey: its own and the packing context)."""
+        lo_r, spec_lo, plo = self._lut_args(_as_tuple(lo), weights_lo, bias_lo, theta, "tree_lut_bootstrap (lo)")
+        hi_r, spec_hi, phi = self._lut_args(_as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap (hi)")
+        _same_count(lo_r[0], hi_r[0])
+        count = lo_r[0].shape[0]
+        R = int(p_hi) // int(theta) if theta in (1, 2, 4) else 1
+        tv1 = np.ascontiguousarray(tv1, self._tv_dtype)
+        if R < 1 or tv1.size == 0 or tv1.size % (R * self.params.N):
+            raise ValueError(f"tv1: expected {np.dtype(self._tv_dtype).name}[n_tables][{R}][{self.params.N}]")
+        idx = _index("table_index", table_index, count)
+        out = np.empty((count, self.words), np.int32)
+        _check(self._fn("tree_lut_bootstrap")(*ctxs, C.byref(spec_lo), C.byref(spec_hi), int(p_hi), self._ptv(tv1), tv1.size // (R * self.params.N),
+                                              _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
+        return out
+
     # -- multi-value bootstrapping (thfhe_mv_lut_bootstrap / thfhe_mk_mv_lut_bootstrap) -------------------------------------------------------
     def _mv_tables(self, factors, tv0, table_index, count):
         w = np.ascontiguousarray(factors, np.int32)
@@ -700,47 +742,12 @@ class CloudKey(_EvalKey):
         _check(lib().thfhe_keyswitch(self.h, _p32(u), _p32(out), u.shape[0]))
         return out
 
-    # -- encrypted tables and the two-digit tree (thfhe_lut_bootstrap_enc, thfhe_tree_lut_bootstrap) ------------------------
-    def lut_bootstrap_enc(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
-        """lut_bootstrap with ENCRYPTED tables: table t is the TLWE sample (tv_a[t], tv_b[t]) under the bootstrapping ring key
-        (thfhe.lut.encrypt_table, or PackBoxes' output); up to 262 144 tables, so every sample may bring its own.  int32[count, theta, n+1]."""
-        return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, True)
-
-    def lut_bootstrap_enc_wo_keyswitch(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
-        """lut_bootstrap_enc without the key switch: int32[count, theta, N+1] records under the ring key."""
-        return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, False)
-
-    def _lut_enc(self, tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, keyswitch):
-        ins, spec, p = self._lut_args((x, y, z), weights, bias, theta, "lut_bootstrap_enc")
-        N = self.params.N
-        tv_a = np.ascontiguousarray(tv_a, np.int32).reshape(-1, N)
-        tv_b = np.ascontiguousarray(tv_b, np.int32).reshape(-1, N)
-        if tv_a.shape != tv_b.shape:
-            raise ValueError(f"tv_a and tv_b differ in shape: {tv_a.shape} vs {tv_b.shape}")
-        count = ins[0].shape[0]
-        idx = _index("lut_index", lut_index, count)
-        out = np.empty((count, _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
-        fn = lib().thfhe_lut_bootstrap_enc if keyswitch else lib().thfhe_lut_bootstrap_enc_wo_keyswitch
-        _check(fn(self.h, C.byref(spec), _p32(tv_a), _p32(tv_b), tv_a.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
-        return out
-
+    # -- the two-digit tree (thfhe_tree_lut_bootstrap); lut_bootstrap_enc takes int32 TLWE tables here ----------------------------
     def tree_lut_bootstrap(self, poly_ctx, tv1, lo, hi, *, p_hi, weights_lo=(1,), bias_lo=0, theta=1, weights_hi=(1,), bias_hi=0, table_index=None):
         """Two-digit tree PBS (thfhe_tree_lut_bootstrap): sample s gets f_table[s](hi, lo) as one record int32[count, n+1].  lo, hi: one record
         array or a tuple of 1 .. 3 (weighted by weights_lo / weights_hi); tv1: int32[n_tables][p_hi / theta][N] (thfhe.lut.tree_test_vectors);
         poly_ctx: a threshold.PolyContext holding the packing key from this key set's LWE key to its bootstrapping ring key."""
-        lo_r, spec_lo, plo = self._lut_args(_as_tuple(lo), weights_lo, bias_lo, theta, "tree_lut_bootstrap (lo)")
-        hi_r, spec_hi, phi = self._lut_args(_as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap (hi)")
-        _same_count(lo_r[0], hi_r[0])
-        count = lo_r[0].shape[0]
-        R = int(p_hi) // int(theta) if theta in (1, 2, 4) else 1
-        tv1 = np.ascontiguousarray(tv1, np.int32)
-        if R < 1 or tv1.size == 0 or tv1.size % (R * self.params.N):
-            raise ValueError(f"tv1: expected int32[n_tables][{R}][{self.params.N}]")
-        idx = _index("table_index", table_index, count)
-        out = np.empty((count, self.words), np.int32)
-        _check(lib().thfhe_tree_lut_bootstrap(self.h, poly_ctx.h, C.byref(spec_lo), C.byref(spec_hi), int(p_hi), _p32(tv1), tv1.size // (R * self.params.N),
-                                              _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
-        return out
+        return self._tree((self.h, poly_ctx.h), tv1, lo, hi, p_hi, weights_lo, bias_lo, theta, weights_hi, bias_hi, table_index)
 
     # -- multi-value bootstrapping with factored test vectors (thfhe_mv_lut_bootstrap, thfhe_tree_lut_bootstrap_mv; DESIGN 4.13) ---------
     def mv_lut_bootstrap(self, factors, x, y=None, z=None, *, tv0, weights=(1,), bias=0, table_index=None):
@@ -1193,46 +1200,11 @@ class MKCloudKey(_EvalKey):
         _check(lib().thfhe_mk_pack_boxes(self.h, _p32(recs), recs.shape[0], p, tv_a.ctypes.data_as(_i64p), tv_b.ctypes.data_as(_i64p)))
         return tv_a, tv_b
 
-    def lut_bootstrap_enc(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
-        """lut_bootstrap with ENCRYPTED tables: table t is the RLWE sample (tv_a[t], tv_b[t]) int64[N] under the summed ring key
-        (thfhe.lut.encrypt_table(..., torus_bits=64), or pack_boxes' output); up to 262 144 tables.  int32[count, theta, P*n+1]."""
-        return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, True)
-
-    def lut_bootstrap_enc_wo_keyswitch(self, tv_a, tv_b, x, y=None, z=None, *, weights=(1,), bias=0, theta=1, lut_index=None):
-        """lut_bootstrap_enc without the key switch: int32[count, theta, N+1] records under the coefficients of the summed ring key."""
-        return self._lut_enc(tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, False)
-
-    def _lut_enc(self, tv_a, tv_b, x, y, z, weights, bias, theta, lut_index, keyswitch):
-        ins, spec, p = self._lut_args((x, y, z), weights, bias, theta, "lut_bootstrap_enc")
-        N = self.params.N
-        tv_a = np.ascontiguousarray(tv_a, np.int64).reshape(-1, N)
-        tv_b = np.ascontiguousarray(tv_b, np.int64).reshape(-1, N)
-        if tv_a.shape != tv_b.shape:
-            raise ValueError(f"tv_a and tv_b differ in shape: {tv_a.shape} vs {tv_b.shape}")
-        count = ins[0].shape[0]
-        idx = _index("lut_index", lut_index, count)
-        out = np.empty((count, _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
-        fn = lib().thfhe_mk_lut_bootstrap_enc if keyswitch else lib().thfhe_mk_lut_bootstrap_enc_wo_keyswitch
-        _check(fn(self.h, C.byref(spec), self._ptv(tv_a), self._ptv(tv_b), tv_a.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
-        return out
-
     def tree_lut_bootstrap(self, tv1, lo, hi, *, p_hi, weights_lo=(1,), bias_lo=0, theta=1, weights_hi=(1,), bias_hi=0, table_index=None):
         """Two-digit tree PBS (thfhe_mk_tree_lut_bootstrap): sample s gets f_table[s](hi, lo) as one record int32[count, P*n+1].  lo, hi: one record
         array or a tuple of 1 .. 3 (weighted by weights_lo / weights_hi); tv1: int64[n_tables][p_hi / theta][N]
-        (thfhe.lut.tree_test_vectors(..., torus_bits=64)).  Needs a packing key with D = N (pack_key_set)."""
-        lo_r, spec_lo, plo = self._lut_args(_as_tuple(lo), weights_lo, bias_lo, theta, "tree_lut_bootstrap (lo)")
-        hi_r, spec_hi, phi = self._lut_args(_as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap (hi)")
-        _same_count(lo_r[0], hi_r[0])
-        count = lo_r[0].shape[0]
-        R = int(p_hi) // int(theta) if theta in (1, 2, 4) else 1
-        tv1 = np.ascontiguousarray(tv1, np.int64)
-        if R < 1 or tv1.size == 0 or tv1.size % (R * self.params.N):
-            raise ValueError(f"tv1: expected int64[n_tables][{R}][{self.params.N}]")
-        idx = _index("table_index", table_index, count)
-        out = np.empty((count, self.words), np.int32)
-        _check(lib().thfhe_mk_tree_lut_bootstrap(self.h, C.byref(spec_lo), C.byref(spec_hi), int(p_hi), self._ptv(tv1), tv1.size // (R * self.params.N),
-                                                 _p32(idx), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
-        return out
+        (thfhe.lut.tree_test_vectors(..., torus_bits=64)).  Needs a packing key with D = N (pack_key_set).  lut_bootstrap_enc takes int64 RLWE tables."""
+        return self._tree((self.h,), tv1, lo, hi, p_hi, weights_lo, bias_lo, theta, weights_hi, bias_hi, table_index)
 
     def set_tree_slice(self, max_candidates):
         """Level-1 candidates (samples x p_hi) per slice of tree_lut_bootstrap and records per slice of pack_boxes: 2N x 8 B of workspace each;
