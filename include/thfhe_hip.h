@@ -193,6 +193,11 @@ int thfhe_sync(thfhe_ctx *ctx);
  * on the eight-wave kernel.  Every shape computes the same words. */
 int thfhe_set_coop_threshold(thfhe_ctx *ctx, int max_jobs);
 int thfhe_set_ring4_threshold(thfhe_ctx *ctx, int max_jobs);
+/* The name of the blind-rotation kernel that a batch of `rotations` runs on under the context's thresholds, as a C string in buf (for
+ * profiles and coverage checks; where a batch is cut in pieces, the kernel of its first and largest).  The answer comes from the rule the
+ * launcher itself follows (csrc/thfhe_launch_plan.h); no device work.  A buffer shorter than the name is THFHE_E_INVALID; 64 bytes hold
+ * every name.  thfhe_mk_ / thfhe_kms_ / thfhe_ccs_rotation_kernel_name answer for the other engines. */
+int thfhe_rotation_kernel_name(const thfhe_ctx *ctx, size_t rotations, char *buf, int len);
 
 /* Per-kernel device timing: when enabled, every *_dev call brackets each kernel with HIP events on the
  * context's stream.  After thfhe_sync, thfhe_last_timings returns milliseconds of the most recent call:
@@ -215,6 +220,7 @@ int thfhe_mk_gates_mixed(thfhe_mk_ctx *ctx, const int32_t *ops, const int32_t *i
 /* Batches of at most `max_single_jobs` rotations run one gate per workgroup (latency), larger ones two gates per workgroup sharing
  * every key chunk (throughput; l <= 3 on the ring of degree 1024, every set on the ring of degree 2048).  Default 256 = one workgroup per CU of an MI355X. */
 int thfhe_mk_set_pair_threshold(thfhe_mk_ctx *ctx, long max_single_jobs);
+int thfhe_mk_rotation_kernel_name(const thfhe_mk_ctx *ctx, size_t rotations, char *buf, int len);   /* see thfhe_rotation_kernel_name */
 /* Gate-DAG evaluation for the 3-gen scheme (same contract as thfhe_dag_run; records of P*n+1 words): the reference's multi-key integer
  * circuits mk_add_3gen ... mk_int_mul_3gen (J/3gen_mk_gates.jl:183-362).  Opcodes: NAND / OR / AND / XOR, AND3, MUX, NOT, COPY. */
 int thfhe_mk_dag_run(thfhe_mk_ctx *ctx, int32_t *wires, size_t n_inputs, const int32_t *gates, size_t n_gates, int64_t *stats);
@@ -286,6 +292,8 @@ int thfhe_ccs_ctx_create(const thfhe_params *params, const int32_t *bk, const in
 void thfhe_ccs_ctx_destroy(thfhe_ccs_ctx *ctx);
 int thfhe_ccs_gates(thfhe_ccs_ctx *ctx, int op, const int32_t *in0, const int32_t *in1, int32_t *out, size_t count);
 int thfhe_ccs_bootstrap(thfhe_ccs_ctx *ctx, int32_t mu, const int32_t *x, int32_t *out, size_t count);
+/* the context's blind-rotation kernel (more than 8 parties or 8 levels take the wide one); see thfhe_rotation_kernel_name */
+int thfhe_ccs_rotation_kernel_name(const thfhe_ccs_ctx *ctx, char *buf, int len);
 
 /* ---- LWE -> TLWE conversion and threshold partial / final decryption: the step after the gate path in the reference's C++
  * applications.  k = 1, N = 1024; all pointers are HOST arrays.
@@ -857,6 +865,7 @@ int thfhe_kms_set_stream(thfhe_kms_ctx *ctx, void *hip_stream);
 /* Launches of at most `max_single_jobs` TLev / RLWE rotations run one job per workgroup, larger ones two jobs per workgroup that share
  * every key chunk (kms_tlev_rotate_pair_kernel).  Default 256 = one workgroup per CU of an MI355X. */
 int thfhe_kms_set_pair_threshold(thfhe_kms_ctx *ctx, long max_single_jobs);
+int thfhe_kms_rotation_kernel_name(const thfhe_kms_ctx *ctx, size_t rotations, char *buf, int len);   /* see thfhe_rotation_kernel_name */
 
 #ifdef __cplusplus
 }

@@ -122,6 +122,21 @@ def test_new_entry_points_validate_arguments_without_a_device():
             threshold.PolyContext(0)
 
 
+def test_rotation_kernel_name_calls_refuse_null_arguments():
+    # thfhe_*_rotation_kernel_name: a null context or a null buffer is THFHE_E_INVALID with a message, before anything is read
+    import thfhe
+    L = thfhe.lib()
+    buf = C.create_string_buffer(64)
+    fake = C.c_void_p(8)   # never dereferenced: the buffer check comes with the context check
+    for name in ("thfhe_rotation_kernel_name", "thfhe_mk_rotation_kernel_name", "thfhe_kms_rotation_kernel_name", "thfhe_ccs_rotation_kernel_name"):
+        fn = getattr(L, name)
+        jobs = () if name == "thfhe_ccs_rotation_kernel_name" else (5,)
+        for ctx, b in ((None, buf), (fake, None)):
+            assert fn(ctx, *jobs, b, 64) == -1, name
+            assert b"null" in L.thfhe_last_error(), (name, L.thfhe_last_error())
+        assert buf.value == b""
+
+
 def test_multi_rank_processes_load_torch_before_the_engine():
     """Runtime-order rule: torch bundles its own HIP runtime, and loading libthfhe_hip.so first hides the GPU
     from torch.  thfhe.lib() therefore imports torch itself in a multi-rank job (WORLD_SIZE > 1) -- and does not in a single process."""

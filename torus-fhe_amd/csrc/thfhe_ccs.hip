@@ -28,13 +28,14 @@
 #include "thfhe_common.h"
 #include "thfhe_devctx.h"
 #include "thfhe_lane.h"
+#include "thfhe_launch_plan.h"
 #include "thfhe_mk_shared.h"
 
 using namespace thfhe;
 
 namespace {
 
-constexpr int kCcsMaxParties = 8;
+using launch_plan::kCcsMaxParties;
 
 #include "thfhe_transform.h"
 
@@ -388,7 +389,7 @@ int thfhe_ccs_ctx_create(const thfhe_params *p, const int32_t *bk, const int32_t
     if (!c) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
     THFHE_TRY(c->open(device, false));
     c->p = *p;
-    c->wide = p->parties > kCcsMaxParties || p->l > 8;   // the 16-party shape: ccs_blind_rotate_wide_kernel
+    c->wide = launch_plan::ccs_wide(p->parties, p->l);   // the 16-party shape: ccs_blind_rotate_wide_kernel
     c->words = p->parties * p->n;
     c->w_pad = (c->words + 3) & ~3;
     THFHE_TRY(c->upload_twiddles(1024));
@@ -416,6 +417,11 @@ int thfhe_ccs_gates(thfhe_ccs_ctx *c, int op, const int32_t *in0, const int32_t 
     if (!(op == THFHE_NAND || op == THFHE_OR || op == THFHE_AND || op == THFHE_XOR) || !mk_gate_lin(op, 0, L))
         return thfhe_fail(THFHE_E_INVALID, "thfhe_ccs_gates takes NAND (the reference's mk_gate_nand) / AND / OR / XOR");
     return ccs_run(c, L, in0, in1, 1 << 29, out, count);
+}
+
+int thfhe_ccs_rotation_kernel_name(const thfhe_ccs_ctx *c, char *buf, int len) {
+    if (!c || !buf) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    return kernel_name_result(len, launch_plan::ccs_kernel_name(c->wide, buf, len > 0 ? (size_t)len : 0));
 }
 
 int thfhe_ccs_bootstrap(thfhe_ccs_ctx *c, int32_t mu, const int32_t *x, int32_t *out, size_t count) {

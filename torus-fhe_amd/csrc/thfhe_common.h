@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/thfhe_hip.h"
 #include "thfhe_lane.h"
 
@@ -49,6 +51,23 @@ inline int lut_spec_check(const thfhe_lut_spec &sp) {
         hipError_t thfhe_e_ = (expr);                                      \
         if (thfhe_e_ != hipSuccess) return ::thfhe::thfhe_fail_hip(thfhe_e_, #expr); \
     } while (0)
+
+// A runtime template argument: calls f(std::integral_constant<int, v>{}) for v in 1 .. Max, so that f can launch kernel<v>; kernel<1> ..
+// kernel<Max> are instantiated and no other.  Any other v fails with `unsupported`.
+template <int Max, int V = 1, class F>
+int with_static_int(int v, const char *unsupported, F &&f) {
+    if constexpr (V > Max) return thfhe_fail(THFHE_E_UNSUPPORTED, unsupported);
+    else if (v == V) {
+        f(std::integral_constant<int, V>{});
+        return THFHE_OK;
+    } else return with_static_int<Max, V + 1>(v, unsupported, f);
+}
+constexpr const char *kBadL = "decomposition length l must be 1..4";
+
+// the end of a thfhe_*_rotation_kernel_name call: `need` is what the name writer of thfhe_launch_plan.h returned (the name's length)
+inline int kernel_name_result(int len, int need) {
+    return need < len ? THFHE_OK : thfhe_fail(THFHE_E_INVALID, "buffer too short for the kernel name");
+}
 
 #if defined(__HIPCC__)
 #ifdef THFHE_STAMPS

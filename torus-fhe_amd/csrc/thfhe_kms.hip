@@ -29,6 +29,7 @@
 #include "thfhe_common.h"
 #include "thfhe_devctx.h"
 #include "thfhe_lane.h"
+#include "thfhe_launch_plan.h"
 #include "thfhe_mk_shared.h"
 
 using namespace thfhe;
@@ -638,6 +639,12 @@ int thfhe_kms_set_pair_threshold(thfhe_kms_ctx *c, long max_single_jobs) {
     std::lock_guard<std::mutex> g(c->mu);
     c->pair_threshold = max_single_jobs;
     return THFHE_OK;
+}
+
+int thfhe_kms_rotation_kernel_name(const thfhe_kms_ctx *c, size_t rotations, char *buf, int len) {
+    if (!c || !buf) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(const_cast<thfhe_kms_ctx *>(c)->mu);   // the threshold is set under it
+    return kernel_name_result(len, launch_plan::kms_kernel_name((long)rotations, c->pair_threshold, buf, len > 0 ? (size_t)len : 0));
 }
 
 }  // extern "C"

@@ -299,25 +299,13 @@ void launch_lhe_cmux_l(const LheCmuxArgs &a, size_t pairs, size_t samples, bool 
     else hipLaunchKernelGGL((sk_lhe_cmux_kernel<L, false>), grid, dim3(512), 0, s, a);
 }
 int launch_lhe_cmux(thfhe_ctx *c, const LheCmuxArgs &a, size_t pairs, size_t samples, bool pub) {
-    switch (c->p.l) {
-    case 1: launch_lhe_cmux_l<1>(a, pairs, samples, pub, c->stream); break;
-    case 2: launch_lhe_cmux_l<2>(a, pairs, samples, pub, c->stream); break;
-    case 3: launch_lhe_cmux_l<3>(a, pairs, samples, pub, c->stream); break;
-    case 4: launch_lhe_cmux_l<4>(a, pairs, samples, pub, c->stream); break;
-    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
-    }
+    THFHE_TRY(with_static_int<4>(c->p.l, kBadL, [&](auto l) { launch_lhe_cmux_l<decltype(l)::value>(a, pairs, samples, pub, c->stream); }));
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
 int launch_lhe_rotate(thfhe_ctx *c, const LheRotArgs &a, size_t jobs) {
     const dim3 grid((unsigned)jobs), block(512);
-    switch (c->p.l) {
-    case 1: hipLaunchKernelGGL(sk_lhe_rotate_kernel<1>, grid, block, 0, c->stream, a); break;
-    case 2: hipLaunchKernelGGL(sk_lhe_rotate_kernel<2>, grid, block, 0, c->stream, a); break;
-    case 3: hipLaunchKernelGGL(sk_lhe_rotate_kernel<3>, grid, block, 0, c->stream, a); break;
-    case 4: hipLaunchKernelGGL(sk_lhe_rotate_kernel<4>, grid, block, 0, c->stream, a); break;
-    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
-    }
+    THFHE_TRY(with_static_int<4>(c->p.l, kBadL, [&](auto l) { hipLaunchKernelGGL(sk_lhe_rotate_kernel<decltype(l)::value>, grid, block, 0, c->stream, a); }));
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
@@ -329,13 +317,7 @@ void launch_lhe_wfa_l(const LheWfaArgs &a, size_t chunks, size_t samples, bool p
 }
 int launch_lhe_wfa(thfhe_ctx *c, const LheWfaArgs &a, size_t samples, bool pub) {
     const size_t chunks = ((size_t)a.n_states + a.chunk - 1) / a.chunk;
-    switch (c->p.l) {
-    case 1: launch_lhe_wfa_l<1>(a, chunks, samples, pub, c->stream); break;
-    case 2: launch_lhe_wfa_l<2>(a, chunks, samples, pub, c->stream); break;
-    case 3: launch_lhe_wfa_l<3>(a, chunks, samples, pub, c->stream); break;
-    case 4: launch_lhe_wfa_l<4>(a, chunks, samples, pub, c->stream); break;
-    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
-    }
+    THFHE_TRY(with_static_int<4>(c->p.l, kBadL, [&](auto l) { launch_lhe_wfa_l<decltype(l)::value>(a, chunks, samples, pub, c->stream); }));
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
@@ -739,25 +721,13 @@ void launch_lhe_demux_l(const LheDemuxArgs &a, size_t nodes, size_t samples, boo
     else hipLaunchKernelGGL((sk_lhe_demux_kernel<L, false>), grid, dim3(512), 0, s, a);
 }
 int launch_lhe_demux(thfhe_ctx *c, const LheDemuxArgs &a, size_t nodes, size_t samples, bool pub) {
-    switch (c->p.l) {
-    case 1: launch_lhe_demux_l<1>(a, nodes, samples, pub, c->stream); break;
-    case 2: launch_lhe_demux_l<2>(a, nodes, samples, pub, c->stream); break;
-    case 3: launch_lhe_demux_l<3>(a, nodes, samples, pub, c->stream); break;
-    case 4: launch_lhe_demux_l<4>(a, nodes, samples, pub, c->stream); break;
-    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
-    }
+    THFHE_TRY(with_static_int<4>(c->p.l, kBadL, [&](auto l) { launch_lhe_demux_l<decltype(l)::value>(a, nodes, samples, pub, c->stream); }));
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
 int launch_lhe_scatter_rotate(thfhe_ctx *c, const LheScatterRotArgs &a, size_t jobs) {
     const dim3 grid((unsigned)jobs), block(512);
-    switch (c->p.l) {
-    case 1: hipLaunchKernelGGL(sk_lhe_scatter_rotate_kernel<1>, grid, block, 0, c->stream, a); break;
-    case 2: hipLaunchKernelGGL(sk_lhe_scatter_rotate_kernel<2>, grid, block, 0, c->stream, a); break;
-    case 3: hipLaunchKernelGGL(sk_lhe_scatter_rotate_kernel<3>, grid, block, 0, c->stream, a); break;
-    case 4: hipLaunchKernelGGL(sk_lhe_scatter_rotate_kernel<4>, grid, block, 0, c->stream, a); break;
-    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
-    }
+    THFHE_TRY(with_static_int<4>(c->p.l, kBadL, [&](auto l) { hipLaunchKernelGGL(sk_lhe_scatter_rotate_kernel<decltype(l)::value>, grid, block, 0, c->stream, a); }));
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }

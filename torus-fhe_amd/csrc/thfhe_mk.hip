@@ -37,6 +37,7 @@
 #include "thfhe_common.h"
 #include "thfhe_dag.h"
 #include "thfhe_lane.h"
+#include "thfhe_launch_plan.h"
 #include "thfhe_mk_shared.h"
 #include "thfhe_mk_pack.h"
 #include "thfhe_pbs_host.h"
@@ -1082,8 +1083,10 @@ int mk_enqueue_pbs(thfhe_mk_ctx *c, const Src &src, size_t jobs, const int64_t *
 }
 
 int mk_launch_rotation(thfhe_mk_ctx *c, const MKBRArgs &a) {
+    using namespace launch_plan;
     const dim3 grid((unsigned)a.jobs), block(512);
-    if (c->p.N == 4096) {
+    const MkChoice ch = mk_rotation_choice(c->p.N, c->p.l, c->parts, c->batched, a.jobs, c->pair_threshold);   // thfhe_launch_plan.h
+    if (ch.family == kR4k) {
         // ring of degree 4096: accumulators in global memory, rotated in place by r4k_rotate_kernel (thfhe_rot4k.h)
         int64_t *acc = a.acc_out;
         if (!acc) {
@@ -1103,7 +1106,7 @@ int mk_launch_rotation(thfhe_mk_ctx *c, const MKBRArgs &a) {
         THFHE_HIP(hipGetLastError());
         return THFHE_OK;
     }
-    if (c->batched) {
+    if (ch.family == kRot2kSingle || ch.family == kRot2kPair) {   // rot2k_launch takes the one of the two
         // accumulators in global memory: start (unless the caller hands one in), rotate by all P n key bits in place, then extract (unless the caller wants
         // the accumulator itself)
         int64_t *acc = a.acc_out;
@@ -1121,47 +1124,20 @@ int mk_launch_rotation(thfhe_mk_ctx *c, const MKBRArgs &a) {
         THFHE_HIP(hipGetLastError());
         return THFHE_OK;
     }
-    if (c->p.N == 2048) {
-        MKBRArgs b = a;
-        b.parts = c->parts;
-        b.pw = c->pw;
-        if (a.jobs > c->pair_threshold) {   // more gates than CUs: two gates per workgroup share every key chunk
-            const dim3 pgrid((unsigned)((a.jobs + 1) / 2));
-            switch (c->p.l * c->parts) {
-            case 1: hipLaunchKernelGGL(mk_blind_rotate_pair2k_kernel<1>, pgrid, block, 0, c->stream, b); break;
-            case 2: hipLaunchKernelGGL(mk_blind_rotate_pair2k_kernel<2>, pgrid, block, 0, c->stream, b); break;
-            case 3: hipLaunchKernelGGL(mk_blind_rotate_pair2k_kernel<3>, pgrid, block, 0, c->stream, b); break;
-            default: return thfhe_fail(THFHE_E_UNSUPPORTED, "N = 2048 needs l x digit parts <= 3");
-            }
-            THFHE_HIP(hipGetLastError());
-            return THFHE_OK;
-        }
-        switch (c->p.l * c->parts) {
-        case 1: hipLaunchKernelGGL(mk_blind_rotate_coop2k_kernel<1>, grid, block, 0, c->stream, b); break;
-        case 2: hipLaunchKernelGGL(mk_blind_rotate_coop2k_kernel<2>, grid, block, 0, c->stream, b); break;
-        case 3: hipLaunchKernelGGL(mk_blind_rotate_coop2k_kernel<3>, grid, block, 0, c->stream, b); break;
-        default: return thfhe_fail(THFHE_E_UNSUPPORTED, "N = 2048 needs l x digit parts <= 3");
-        }
-        THFHE_HIP(hipGetLastError());
-        return THFHE_OK;
+    // the one-pass kernels: two gates per workgroup share every key chunk (more gates than CUs, also the party-sharded pieces), else one
+    const dim3 pgrid((unsigned)((a.jobs + 1) / 2));
+    MKBRArgs b = a;   // N = 2048: with the digit parts
+    b.parts = c->parts;
+    b.pw = c->pw;
+    constexpr const char *kBadLE = "N = 2048 needs l x digit parts <= 3";
+    int rc;
+    switch (ch.family) {
+    case kPair2k: rc = with_static_int<3>(ch.LE, kBadLE, [&](auto le) { hipLaunchKernelGGL(mk_blind_rotate_pair2k_kernel<decltype(le)::value>, pgrid, block, 0, c->stream, b); }); break;
+    case kCoop2k: rc = with_static_int<3>(ch.LE, kBadLE, [&](auto le) { hipLaunchKernelGGL(mk_blind_rotate_coop2k_kernel<decltype(le)::value>, grid, block, 0, c->stream, b); }); break;
+    case kMkPair: rc = with_static_int<3>(ch.LE, kBadL, [&](auto l) { hipLaunchKernelGGL(mk_blind_rotate_pair_kernel<decltype(l)::value>, pgrid, block, 0, c->stream, a); }); break;
+    default: rc = with_static_int<4>(ch.LE, kBadL, [&](auto l) { hipLaunchKernelGGL(mk_blind_rotate_coop_kernel<decltype(l)::value>, grid, block, 0, c->stream, a); }); break;
     }
-    if (c->p.l <= 3 && a.jobs > c->pair_threshold) {  // throughput path: two gates per workgroup (also for the party-sharded pieces)
-        const dim3 pgrid((unsigned)((a.jobs + 1) / 2));
-        switch (c->p.l) {
-        case 1: hipLaunchKernelGGL(mk_blind_rotate_pair_kernel<1>, pgrid, block, 0, c->stream, a); break;
-        case 2: hipLaunchKernelGGL(mk_blind_rotate_pair_kernel<2>, pgrid, block, 0, c->stream, a); break;
-        default: hipLaunchKernelGGL(mk_blind_rotate_pair_kernel<3>, pgrid, block, 0, c->stream, a); break;
-        }
-        THFHE_HIP(hipGetLastError());
-        return THFHE_OK;
-    }
-    switch (c->p.l) {
-    case 1: hipLaunchKernelGGL(mk_blind_rotate_coop_kernel<1>, grid, block, 0, c->stream, a); break;
-    case 2: hipLaunchKernelGGL(mk_blind_rotate_coop_kernel<2>, grid, block, 0, c->stream, a); break;
-    case 3: hipLaunchKernelGGL(mk_blind_rotate_coop_kernel<3>, grid, block, 0, c->stream, a); break;
-    case 4: hipLaunchKernelGGL(mk_blind_rotate_coop_kernel<4>, grid, block, 0, c->stream, a); break;
-    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
-    }
+    if (rc) return rc;
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
@@ -1439,13 +1415,8 @@ int thfhe_mk_ctx_create(const thfhe_params *p, const int64_t *bk_coeff, const in
     if ((p->N != 1024 && p->N != 2048 && p->N != 4096) || p->k != 1) return thfhe_fail(THFHE_E_UNSUPPORTED, "only N = 1024 / 2048 / 4096, k = 1 is implemented");
     if (p->N == 2048 && p->l > 3) return thfhe_fail(THFHE_E_UNSUPPORTED, "N = 2048 needs decomposition length l <= 3");
     if (p->parties < 1 || p->parties > 512) return thfhe_fail(THFHE_E_UNSUPPORTED, "need 1 <= parties <= 512");
-    // digits beyond 10 bit are cut into balanced parts of <= 9 bit (N = 2048 only: the sets that use a wide base live on that ring,
-    // J/mk_api.jl:214-298); |sum| <= 2 l parts N 2^(pw-1) 2^15 <= 2^36.6 stays inside the N = 2048 exactness bound
-    const int parts = p->Bgbit > 10 ? (p->Bgbit + 8) / 9 : 1;
-    const int pw = parts > 1 ? (p->Bgbit + parts - 1) / parts : 0;
-    // l x parts <= 3: the one-pass N = 2048 kernel; more row parts (the 256-party set: l = 2, Bgbit = 18 -> 2 x 2 parts) go through the batched
-    // rotation of thfhe_rot2k.h, which knows one- and two-part digits.  Exactness: 2 l parts N 2^(part bits - 1) 2^15 <= 2^37 (section 4.3).
-    const bool batched = p->N == 2048 && p->l * parts > 3;
+    // the digit parts and the batched N = 2048 path: launch_plan::mk_digit_parts (thfhe_launch_plan.h)
+    const auto [parts, pw, batched] = launch_plan::mk_digit_parts(p->N, p->l, p->Bgbit);
     const bool ring4k = p->N == 4096;   // thfhe_rot4k.h: at most six row parts, digits from the top 32 bits; |sum| <= 6 x 4096 x 2^8 x 2^15 = 2^37.6 (one level more than N = 2048)
     if (ring4k && (p->l < 1 || 2 * p->l * parts > 6 || p->l * p->Bgbit > 32 || (double)(2 * p->l * parts) * 4096.0 * (double)(1 << ((parts > 1 ? pw : p->Bgbit) - 1)) * 32768.0 > 274877906944.0))
         return thfhe_fail(THFHE_E_UNSUPPORTED, "N = 4096 needs l x ceil(Bgbit / 9) <= 3, l*Bgbit <= 32 and the FP64 exactness bound 2 l parts N 2^(part bits - 1) 2^15 <= 2^38");
@@ -1632,6 +1603,11 @@ int thfhe_mk_set_pair_threshold(thfhe_mk_ctx *c, long max_single_jobs) {
     std::lock_guard<std::mutex> g(c->mu);
     c->pair_threshold = max_single_jobs;
     return THFHE_OK;
+}
+int thfhe_mk_rotation_kernel_name(const thfhe_mk_ctx *c, size_t rotations, char *buf, int len) {
+    if (!c || !buf) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(const_cast<thfhe_mk_ctx *>(c)->mu);   // the threshold is set under it
+    return kernel_name_result(len, launch_plan::mk_kernel_name(c->p.N, c->p.l, c->parts, c->batched, (long)rotations, c->pair_threshold, buf, len > 0 ? (size_t)len : 0));
 }
 int thfhe_mk_set_stream(thfhe_mk_ctx *c, void *hip_stream) {
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");

@@ -454,9 +454,9 @@ __global__ __launch_bounds__(512, 2) void kms_tlev_rotate_pair_kernel(KmsBRArgs 
 }
 
 // launch: one job per workgroup up to `pair_threshold` jobs (one per CU), two above; the park buffer (128 KiB per workgroup) is only
-// needed when the row parts do not fit one batch
+// needed when the row parts do not fit one batch.  The rule is launch_plan::rot2k_pair (thfhe_launch_plan.h, included by the translation unit).
 inline int rot2k_launch(const KmsBRArgs &a, hipStream_t stream, long pair_threshold, DevBuf &park) {
-    if (a.jobs > pair_threshold) {
+    if (launch_plan::rot2k_pair(a.jobs, pair_threshold)) {
         const size_t wgs = ((size_t)a.jobs + 1) / 2, park_bytes = wgs * 8 * 2 * 512 * sizeof(cplx);
         const bool need_park = 2 * a.lg * a.parts > 6;
         if (need_park && park_bytes > park.bytes()) {

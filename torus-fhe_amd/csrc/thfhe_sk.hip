@@ -34,6 +34,7 @@
 #include "thfhe_devctx.h"
 #include "thfhe_keyswitch.h"
 #include "thfhe_lane.h"
+#include "thfhe_launch_plan.h"
 #include "thfhe_pack.h"
 #include "thfhe_pbs_host.h"
 #include "thfhe_ring_schedule.h"
@@ -635,13 +636,9 @@ void launch_ring8(const BRArgs &a, hipStream_t s) {
     hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 5, 8, LUT>), grid, block, 0, s, a);
 }
 
-// Kernel choice for a batch of rotations.  Measured on one MI355X (256 CUs, SK-128; profiles/r04_time_batch.txt): a round of the
-// eight-wave ring kernel takes 14.9 ms whether its workgroups hold 1 025 or 2 048 jobs between them, a round of the four-wave shape
-// 9.8 ms for up to 1 024 jobs, the cooperative kernel 3.0 ms per 256 jobs.  So a batch is cut into whole rounds of 2 048 jobs on the
-// eight-wave kernel plus a remainder r on the cheapest shape: cooperative up to coop_max (default 768: 8.6 ms), four-wave ring up to
-// ring4_max (1 024), four-wave ring + one cooperative round up to ring4_max + 256 (12.9 ms), else one more eight-wave round.
-// (3 072 rotations: 30.1 ms as one launch of 384 eight-wave workgroups, 24.8 ms as 2 048 + 1 024.)  The pieces are independent jobs
-// on disjoint slices of the same arrays, launched back to back on the context's stream.
+// The rotations of a batch, piece by piece of launch_plan::sk_rotation_plan (thfhe_launch_plan.h: whole rounds on the eight-wave ring kernel,
+// the remainder on the cheapest shape).  The pieces are independent jobs on disjoint slices of the same arrays, launched back to back on
+// the context's stream.
 template <int L, int LUT>
 void launch_br(const BRArgs &a, hipStream_t s, int coop_max, int ring4_max) {
     auto piece = [&](long first, long count) {
@@ -651,30 +648,20 @@ void launch_br(const BRArgs &a, hipStream_t s, int coop_max, int ring4_max) {
         if (LUT && b.lut_idx) b.lut_idx += first;
         return b;
     };
-    constexpr long kRound = 2048;   // 256 CUs x 8 jobs
-    const long full = (coop_max > 0 || ring4_max > 0) ? a.jobs / kRound * kRound : a.jobs;   // both thresholds 0: everything on the eight-wave kernel
-    if (full > 0) launch_ring8<L, LUT>(piece(0, full), s);
-    const long r = a.jobs - full;
-    if (r == 0) return;
-    if (r <= coop_max) launch_coop<L, LUT>(piece(full, r), s);
-    else if (r <= ring4_max) launch_ring4<L, LUT>(piece(full, r), s);
-    else if (ring4_max > 0 && coop_max > 0 && r <= ring4_max + (coop_max < 256 ? coop_max : 256)) {
-        launch_ring4<L, LUT>(piece(full, ring4_max), s);
-        launch_coop<L, LUT>(piece(full + ring4_max, r - ring4_max), s);
-    } else launch_ring8<L, LUT>(piece(full, r), s);
+    launch_plan::SkPiece pc[launch_plan::kMaxPieces];
+    const int n = launch_plan::sk_rotation_plan(a.jobs, coop_max, ring4_max, pc);
+    for (int i = 0; i < n; i++) {
+        const BRArgs b = piece(pc[i].first, pc[i].count);
+        if (pc[i].shape == launch_plan::kRing8) launch_ring8<L, LUT>(b, s);
+        else if (pc[i].shape == launch_plan::kCoop) launch_coop<L, LUT>(b, s);
+        else launch_ring4<L, LUT>(b, s);
+    }
 }
 
 // the blind rotations of `a` on the kernel shapes of launch_br, for the context's decomposition length
 template <int LUT>
 int launch_rotations(thfhe_ctx *c, const BRArgs &a) {
-    switch (c->p.l) {
-    case 1: launch_br<1, LUT>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
-    case 2: launch_br<2, LUT>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
-    case 3: launch_br<3, LUT>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
-    case 4: launch_br<4, LUT>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); break;
-    default: return thfhe_fail(THFHE_E_UNSUPPORTED, "decomposition length l must be 1..4");
-    }
-    return THFHE_OK;
+    return with_static_int<4>(c->p.l, kBadL, [&](auto l) { launch_br<decltype(l)::value, LUT>(a, c->stream, c->coop_max_jobs, c->ring4_max_jobs); });
 }
 
 // rotations (prologue + blind rotate) of `jobs` = gates * rot_per_gate jobs into c->d_u
@@ -1107,6 +1094,11 @@ int thfhe_set_ring4_threshold(thfhe_ctx *c, int max_jobs) {
     std::lock_guard<std::mutex> g(c->mu);
     c->ring4_max_jobs = max_jobs;
     return THFHE_OK;
+}
+int thfhe_rotation_kernel_name(const thfhe_ctx *c, size_t rotations, char *buf, int len) {
+    if (!c || !buf) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(const_cast<thfhe_ctx *>(c)->mu);   // the thresholds are set under it
+    return kernel_name_result(len, launch_plan::sk_kernel_name(c->p.l, (long)rotations, c->coop_max_jobs, c->ring4_max_jobs, buf, len > 0 ? (size_t)len : 0));
 }
 int thfhe_set_profiling(thfhe_ctx *c, int enabled) {
     THFHE_TRY(ctx_set_profiling(c, enabled));

@@ -270,6 +270,10 @@ SIGNATURES = {
     "thfhe_sync": (C.c_int, [_vp]),
     "thfhe_set_coop_threshold": (C.c_int, [_vp, C.c_int]),
     "thfhe_set_ring4_threshold": (C.c_int, [_vp, C.c_int]),
+    "thfhe_rotation_kernel_name": (C.c_int, [_vp, C.c_size_t, C.c_char_p, C.c_int]),
+    "thfhe_mk_rotation_kernel_name": (C.c_int, [_vp, C.c_size_t, C.c_char_p, C.c_int]),
+    "thfhe_kms_rotation_kernel_name": (C.c_int, [_vp, C.c_size_t, C.c_char_p, C.c_int]),
+    "thfhe_ccs_rotation_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "thfhe_set_profiling": (C.c_int, [_vp, C.c_int]),
     "thfhe_last_timings": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "thfhe_ccs_ctx_create": (C.c_int, [C.POINTER(Params), _i32p, _i32p, _i32p, _i32p, C.c_int, C.POINTER(_vp)]),
@@ -485,6 +489,12 @@ class _Handle:
             self.close()
         except Exception:  # interpreter teardown
             pass
+
+    def _kernel_name(self, fn, *args):
+        """The answer of one of the library's thfhe_*_rotation_kernel_name calls for this context (the rule is csrc/thfhe_launch_plan.h's)."""
+        buf = C.create_string_buffer(64)
+        _check(fn(self.h, *args, buf, len(buf)))
+        return buf.value.decode()
 
 
 class _EvalKey(_Handle):
@@ -1050,23 +1060,14 @@ class CloudKey(_EvalKey):
     def set_ring4_threshold(self, max_jobs):
         """Remainders (batch mod 2048) above the cooperative threshold and <= max_jobs rotations use the four-wave ring kernel; 0 disables it."""
         _check(lib().thfhe_set_ring4_threshold(self.h, int(max_jobs)))
-        self._ring4_threshold = int(max_jobs)
 
     def set_coop_threshold(self, max_jobs):
         """Remainders (batch mod 2048) of <= max_jobs rotations use the cooperative latency kernel; 0 disables it."""
         _check(lib().thfhe_set_coop_threshold(self.h, int(max_jobs)))
-        self._coop_threshold = int(max_jobs)
 
     def rotation_kernel_name(self, rotations):
-        """The blind-rotation kernel that does most of a batch of `rotations` (thfhe_sk.hip launch_br; for profiles and bench.py)."""
-        l = self.params.l
-        coop, ring4 = getattr(self, "_coop_threshold", 768), getattr(self, "_ring4_threshold", 1024)
-        r = rotations % 2048 if (coop or ring4) else 0
-        if rotations >= 2048 or r == 0:
-            return f"sk_blind_rotate_ring_kernel<{l}>"
-        if r <= coop:
-            return f"sk_blind_rotate_coop_kernel<{l}>"
-        return f"sk_blind_rotate_ring_kernel<{l}, 4 waves>" if r <= ring4 + min(coop, 256) and ring4 else f"sk_blind_rotate_ring_kernel<{l}>"
+        """The blind-rotation kernel that does most of a batch of `rotations`, as the library's launcher decides it (for profiles and bench.py)."""
+        return self._kernel_name(lib().thfhe_rotation_kernel_name, int(rotations))
 
 
 # ---- the reference's single-key gate API (gates.jl:15-177), batched over the leading axis -------------
@@ -1157,7 +1158,6 @@ class MKCloudKey(_EvalKey):
     def set_pair_threshold(self, max_single_jobs):
         """Batches of <= max_single_jobs rotations run one gate per workgroup; larger ones two gates per workgroup."""
         _check(lib().thfhe_mk_set_pair_threshold(self.h, int(max_single_jobs)))
-        self._pair_threshold = int(max_single_jobs)
 
     # -- multi-value bootstrapping on Torus64 (thfhe_mk_mv_lut_bootstrap, DESIGN 4.19) ---------------------------------------------------
     def mv_lut_bootstrap(self, factors, x, y=None, z=None, *, tv0, weights=(1,), bias=0, table_index=None, out_bias=0):
@@ -1231,18 +1231,8 @@ class MKCloudKey(_EvalKey):
         return self._dag_run("dag_run_mv_batch", lib().thfhe_mk_dag_run_mv_batch, (self.h,), input_records, nodes, 6, families, out_wires)
 
     def rotation_kernel_name(self, rotations):
-        """The blind-rotation kernel a batch of `rotations` is dispatched to (mk_launch_rotation in thfhe_mk.hip)."""
-        p = self.params
-        if p.N == 4096:
-            return "r4k_rotate_kernel"
-        if p.N == 2048:
-            le = p.l * (((p.Bgbit + 8) // 9) if p.Bgbit > 10 else 1)
-            pair = rotations > getattr(self, "_pair_threshold", 256)
-            if le > 3:
-                return "kms_tlev_rotate_pair_kernel" if pair else "kms_tlev_rotate_kernel"
-            return f"mk_blind_rotate_{'pair2k' if pair else 'coop2k'}_kernel<{le}>"
-        pair = p.l <= 3 and rotations > getattr(self, "_pair_threshold", 256)
-        return f"mk_blind_rotate_{'pair' if pair else 'coop'}_kernel<{p.l}>"
+        """The blind-rotation kernel a batch of `rotations` is dispatched to, as mk_launch_rotation in thfhe_mk.hip decides it."""
+        return self._kernel_name(lib().thfhe_mk_rotation_kernel_name, int(rotations))
 
 
 class PolyMac(_Handle):
@@ -1296,7 +1286,7 @@ class CCSCloudKey(_Handle):
 
     def rotation_kernel_name(self):
         """The blind-rotation kernel of this context (thfhe_ccs_ctx_create: more than 8 parties or 8 levels take the wide kernel)."""
-        return "ccs_blind_rotate_wide_kernel" if self.params.parties > 8 or self.params.l > 8 else "ccs_blind_rotate_kernel"
+        return self._kernel_name(lib().thfhe_ccs_rotation_kernel_name)
 
 
 def mk_gate_nand(ck, x, y): return ck.gates(NAND, x, y)          # mk_gates.jl:7-13 (CCS scheme)

@@ -57,11 +57,10 @@ class KMSCloudKey(_Handle):
     def set_pair_threshold(self, max_single_jobs):
         """Launches of <= max_single_jobs rotations run one job per workgroup; larger ones two jobs per workgroup (shared key chunks)."""
         _check(lib().thfhe_kms_set_pair_threshold(self.h, int(max_single_jobs)))
-        self._pair_threshold = int(max_single_jobs)
 
     def rotation_kernel_name(self, rotations):
-        """The kernel a launch of `rotations` RLWE rotations runs on (rot2k_launch; a TLev rotation of g gates is g * l_lev of them)."""
-        return "kms_tlev_rotate_pair_kernel" if rotations > getattr(self, "_pair_threshold", 256) else "kms_tlev_rotate_kernel"
+        """The kernel a launch of `rotations` RLWE rotations runs on, as rot2k_launch decides it (a TLev rotation of g gates is g * l_lev of them)."""
+        return self._kernel_name(lib().thfhe_kms_rotation_kernel_name, int(rotations))
 
     # ---- the pieces (same decomposition as the reference) --------------------------------------------------------------------------
     def tlev_rotate(self, party, bara):
