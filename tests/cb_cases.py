@@ -97,6 +97,30 @@ def case(O, name, device=None):
     return c
 
 
+def drawn(case, bits, seed, pool=None):
+    """(recs, idx): a batch of `bits` records drawn from the first `pool` records of the case (default: all of them), idx = rng.integers(0, pool,
+    bits) on a fixed seed.  Every stage is a deterministic function of one record, so the model of the batch is case["rows"][idx].  The draw is
+    random, not periodic: an offset wrong by a multiple of the pool size cannot hide."""
+    pool = len(case["recs"]) if pool is None else int(pool)
+    assert 1 <= pool <= len(case["recs"])
+    idx = np.random.default_rng(seed).integers(0, pool, int(bits))
+    return np.ascontiguousarray(case["recs"][idx]), idx
+
+
+# The batch boundaries that tests/test_gpu_cb_slices.py is sized by: name -> (value, file under torus-fhe_amd/csrc, the defining line as a regular
+# expression whose one group is the value).  tests/test_cb_host.py reads the files and asserts the values, so that a changed constant fails there
+# and does not silently move the GPU cases off the boundaries.
+BOUNDARIES = {
+    "bit slice": (2048, "thfhe_cb_host.h", r"constexpr size_t kCbSliceBits = (\d+);"),                    # bits per slice of cb_fill
+    "inputs per launch": (4096, "thfhe_cb.h", r"constexpr long kCbMaxLaunchInputs = (\d+);"),             # cb_enqueue: launches of 4096 // l * l inputs
+    "stage-B host slice": (2048, "thfhe_cb_host.h", r"S_max = std::min<size_t>\(count, std::max\(1, (\d+) / l\)\);"),   # cb_private_keyswitch: 2048 // l samples
+    "input tile": (256, "thfhe_cb.h", r"\(int\)\(\(G \+ 255\) / (\d+)\), 1\};"),                          # CbmArgs.gtiles: inputs per workgroup of the matrix-core kernel
+    "pair threshold": (256, "thfhe_mk.hip", r"long pair_threshold = (\d+);"),                             # level-2 rotations per launch above which two jobs share a workgroup
+}
+SLICE_BITS, LAUNCH_INPUTS, HOST_SLICE_INPUTS, TILE_INPUTS, PAIR_THRESHOLD = (BOUNDARIES[k][0] for k in (
+    "bit slice", "inputs per launch", "stage-B host slice", "input tile", "pair threshold"))
+
+
 def row_noise(S, rows, bits):
     """std of phase - message over all coefficients of all rows (torus units)"""
     return float(CB.row_errors(S.K, rows, bits, S.tp.l, S.tp.Bgbit).std()) / 2.0**32

@@ -180,6 +180,48 @@ def test_mk_key_set_without_lwe_keys_is_unchanged(name, over, digest):
     assert np.array_equal(K2.decrypt(x), [False, True, True, False])
 
 
+# ---- the boundaries of tests/test_gpu_cb_slices.py ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", list(CC.BOUNDARIES))
+def test_batch_boundaries_are_what_the_sources_say(name):
+    """the slice, launch, tile and threshold constants the GPU slice tests are sized by, read from the text of the sources: a changed constant fails
+    here instead of moving those cases off their boundaries unnoticed"""
+    import os
+    import re
+    value, fname, pattern = CC.BOUNDARIES[name]
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "torus-fhe_amd", "csrc", fname)) as f:
+        found = re.findall(pattern, f.read())
+    assert len(found) == 1, (name, fname, "the defining line was expected exactly once", found)
+    assert int(found[0]) == value, (name, fname, int(found[0]), value)
+
+
+def test_boundary_table_names_every_boundary_once():
+    assert sorted(CC.BOUNDARIES) == ["bit slice", "input tile", "inputs per launch", "pair threshold", "stage-B host slice"]
+    assert (CC.SLICE_BITS, CC.LAUNCH_INPUTS, CC.HOST_SLICE_INPUTS, CC.TILE_INPUTS, CC.PAIR_THRESHOLD) == (2048, 4096, 2048, 256, 256)
+
+
+@pytest.mark.parametrize("name", ["SK-128", "SK-80"])
+def test_pool_rows_are_pairwise_distinct(O, name):
+    # a draw from the pool can only show a misplaced bit if no two records of the pool have the same rows
+    rows = CC.case(O, name)["rows"]
+    flat = rows.reshape(rows.shape[0], -1)
+    assert len({r.tobytes() for r in flat}) == rows.shape[0] == (48 if name == "SK-128" else 24)
+
+
+def test_drawn_batch_has_the_drawn_rows_as_its_model(O):
+    S, c = CC.keys(O, "SK-128"), CC.case(O, "SK-128")
+    recs, idx = CC.drawn(c, 100, 0xD7A3)
+    assert recs.shape == (100, S.tp.n + 1) and idx.shape == (100,) and idx.min() >= 0 and idx.max() < 48
+    assert np.array_equal(recs, c["recs"][idx])
+    assert len(set(idx.tolist())) > 24 and not np.array_equal(idx, np.arange(100) % 48)       # a random draw, not a period of the pool
+    again = CC.drawn(c, 100, 0xD7A3)
+    assert np.array_equal(again[0], recs) and np.array_equal(again[1], idx)                      # a fixed seed
+    assert not np.array_equal(CC.drawn(c, 100, 0xD7A4)[1], idx)
+    assert CC.drawn(c, 100, 0xD7A3, pool=24)[1].max() < 24
+    rows = CB.circuit_bootstrap(S.orc2, S.pks, recs, S.tp.l, S.tp.Bgbit, CC.T, CC.BASEBIT)
+    assert np.array_equal(rows, c["rows"][idx])
+
+
 def test_cb_param_sets_stay_out_of_the_named_sets():
     import thfhe
     assert not set(thfhe.CB_PARAM_SETS) & set(thfhe.PARAM_SETS)
