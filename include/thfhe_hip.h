@@ -548,12 +548,36 @@ int thfhe_lhe_scatter(thfhe_ctx *ctx, const thfhe_tgsw_set *set, size_t first, s
  *   ring degree = the key's D.  THFHE_E_NOMEM (before anything is allocated) if spectra and workspace exceed the free device memory.  With profiling
  *   on, thfhe_last_timings gives ms[0] = stage A, ms[1] = stage B, ms[2] = transform of the LAST slice.  The library cannot check that the two
  *   contexts share s or that the key is from z2 to z: with other keys the call succeeds and the set does not decrypt.
+ * thfhe_circuit_bootstrap_mode: thfhe_circuit_bootstrap with stage A chosen by `mode`; THFHE_CB_PER_LEVEL is thfhe_circuit_bootstrap, word for word.
+ *   THFHE_CB_ONE_ROTATION takes the l records of a bit from ONE level-2 rotation (many-LUT with the l constants mu_j as the functions): with
+ *   theta = the smallest power of two >= l, the record's n + 1 words are mod-switched to multiples of theta, bar = modswitch_{2D/theta}(word) theta
+ *   (the prologue of thfhe_mk_lut_bootstrap with one input, weight 1, bias 0); the accumulator starts at (0, X^{-barb} tv), tv[q] = mu_(q mod theta)
+ *   for q mod theta < l and 0 otherwise; the CMux chain is the gate bootstrap's; record (bit, j) is the extraction at coefficient j (mask word i
+ *   t64tot32(a_{j-i}) for i <= j, t64tot32(-a_{D+j-i}) above, negated mod 2^64 first) with 2^(31 - (j+1) Bgbit) added to the body.  barb is a
+ *   multiple of theta and j < theta, so coefficient j is +-mu_j with the sign of coefficient 0.  Stages B and C are the same.  The mode gives OTHER
+ *   words than the default (another mod-switch) with the same rotation noise; its price is a theta times coarser mod-switch of the INPUT, which the
+ *   gate encoding +-1/8 absorbs (DESIGN 4.21 has the margins) -- an input with a smaller box is the caller's risk.  THFHE_E_INVALID for an unknown
+ *   mode, with the null pointers, before the contexts are looked at; THFHE_E_UNSUPPORTED for l > 4 (the engines' theta stops at 4).  The security
+ *   caveat of the default mode (sigma_pks near 2^-31) is unchanged.
+ * thfhe_cb_stage_a: stage A alone on host buffers, the counterpart of thfhe_cb_private_keyswitch: lwe HOST int32[count][n+1] -> lwe2_out HOST
+ *   int32[count][l][D+1], in either mode, in the slices and on the lent stream of thfhe_circuit_bootstrap.  count <= 2^24; count 0 returns THFHE_OK
+ *   once the checks have passed.
+ * thfhe_mk_lut_rotate_dev (3-gen engine, DEVICE pointers, on the context's stream): d_recs int32[count][P*n+1] -> the theta-rounded prologue of the
+ *   records themselves, the accumulator start (0, X^{-barb} d_tv) from the ONE table d_tv int64[N], and the rotation in place in d_acc
+ *   int64[count][2][N].  The caller extracts.  theta is 1, 2 or 4; arguments are checked before the context is looked at.
  * thfhe_mk_ctx_info: the parameters and the device of a 3-gen context. */
+enum { THFHE_CB_PER_LEVEL = 0, THFHE_CB_ONE_ROTATION = 1 };
 int thfhe_cb_key_set(thfhe_ctx *ctx, const int32_t *pks /*[2][D][t][2][N]*/, int D, int t, int basebit);
 int thfhe_cb_private_keyswitch(thfhe_ctx *ctx, const int32_t *lwe2 /*[count][l][D+1]*/, size_t count, int32_t *tgsw /*[count][2l][2][N]*/);
 int thfhe_cb_set_batch_threshold(thfhe_ctx *ctx, long min_inputs);
 int thfhe_circuit_bootstrap(thfhe_ctx *ctx, thfhe_mk_ctx *level2, const int32_t *lwe /*[count][d][n+1]*/, size_t count, int d, int32_t *tgsw_words,
                             thfhe_tgsw_set **out);
+int thfhe_circuit_bootstrap_mode(thfhe_ctx *ctx, thfhe_mk_ctx *level2, const int32_t *lwe /*[count][d][n+1]*/, size_t count, int d, int mode,
+                                 int32_t *tgsw_words, thfhe_tgsw_set **out);
+int thfhe_cb_stage_a(thfhe_ctx *ctx, thfhe_mk_ctx *level2, const int32_t *lwe /*[count][n+1]*/, size_t count, int mode,
+                     int32_t *lwe2_out /*[count][l][D+1]*/);
+int thfhe_mk_lut_rotate_dev(thfhe_mk_ctx *ctx, const int32_t *d_recs /*[count][P*n+1]*/, int theta, const int64_t *d_tv /*[N]*/,
+                            int64_t *d_acc /*[count][2][N]*/, size_t count);
 int thfhe_mk_ctx_info(const thfhe_mk_ctx *ctx, thfhe_params *params, int *device);
 
 /* ---- encrypted-table, select and tree nodes in the gate-DAG executor (single key): thfhe_dag_run_lut_batch with three more node

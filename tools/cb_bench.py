@@ -12,7 +12,13 @@ The events are those of the call's LAST slice (2 048 bits), whose size is report
 figures behind the threshold kCbBatchMinInputs.  Each workload is warmed up, then the kernels alternate for --reps rounds; medians are kept.
 The records are fresh encryptions, not gate outputs: timing does not depend on the words.  Writes one JSON line to --out and prints it.
 
-usage: python tools/cb_bench.py [--reps 5] [--device 0] [--bits 256,4096] [--sweep 1,2,4,8,16,64] [--out profiles/cb_bench.json]
+--mode both times the default stage A (l level-2 rotations per bit) against the one-rotation mode (THFHE_CB_ONE_ROTATION) instead: the two modes
+alternate for --reps rounds in this one process, stage B on the library's own choice of kernel, and every workload reports per mode stage A / B /
+transform ms (device events, last slice), bits per second (wall), and the ratios per-level / one-rotation.  --mode one-rotation runs the workloads
+above in that mode.
+
+usage: python tools/cb_bench.py [--reps 5] [--device 0] [--bits 256,4096] [--sweep 1,2,4,8,16,64] [--mode per-level|one-rotation|both]
+                                [--out profiles/cb_bench.json]
 """
 import argparse
 import json
@@ -40,6 +46,7 @@ def main():
     ap.add_argument("--bits", default="256,4096")
     ap.add_argument("--sweep", default="1,2,4,8,16,64")
     ap.add_argument("--d", type=int, default=16)
+    ap.add_argument("--mode", choices=("per-level", "one-rotation", "both"), default="per-level")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cb_bench.json"))
     args = ap.parse_args()
     bits = [int(b) for b in args.bits.split(",")]
@@ -58,11 +65,11 @@ def main():
     recs = K.encrypt(np.random.default_rng(4).integers(0, 2, max(bits + sweep)), 5)
     row_bytes = 2 * D * T * 8192
 
-    def run(nbits, thr):
+    def run(nbits, thr, one_rotation=args.mode == "one-rotation"):
         d = args.d if nbits % args.d == 0 else 1
         ck.cb_set_batch_threshold(thr)
         t = time.perf_counter()
-        ck.circuit_bootstrap(recs[:nbits], d).close()
+        ck.circuit_bootstrap(recs[:nbits], d, one_rotation=one_rotation).close()
         wall = time.perf_counter() - t
         ms = ck.last_timings()
         return wall, ms["prologue_ms"], ms["blind_rotate_ms"], ms["keyswitch_ms"]
@@ -83,6 +90,34 @@ def main():
                     stage_a_ms=med[MFMA][1], transform_ms=med[MFMA][3],
                     stage_b_ms={"plain": med[PLAIN][2], "mfma": med[MFMA][2]},
                     key_bytes_per_s={"plain": key_bytes[PLAIN] / (med[PLAIN][2] * 1e-3), "mfma": key_bytes[MFMA] / (med[MFMA][2] * 1e-3)})
+
+    def measure_modes(nbits):
+        modes = {"per_level": False, "one_rotation": True}
+        for one in modes.values():
+            run(nbits, 0, one)                    # warm-up of both modes
+        got = {m: [] for m in modes}
+        for _ in range(args.reps):                # alternating rounds
+            for m, one in modes.items():
+                got[m].append(run(nbits, 0, one))
+        med = {m: [statistics.median(v[q] for v in got[m]) for q in range(4)] for m in got}
+        out = dict(bits=nbits, last_slice_bits=nbits % SLICE_BITS or min(nbits, SLICE_BITS))
+        for m in modes:
+            out[m] = dict(bits_per_s=nbits / med[m][0], stage_a_ms=med[m][1], stage_b_ms=med[m][2], transform_ms=med[m][3])
+        out["stage_a_ratio"] = med["per_level"][1] / med["one_rotation"][1]
+        out["bits_per_s_ratio"] = med["per_level"][0] / med["one_rotation"][0]
+        return out
+
+    if args.mode == "both":
+        res = dict(tool="cb_bench", mode="both", set="SK-128 + CB-128", l=p.l, theta=4 if p.l > 2 else p.l, t=T, basebit=BASEBIT, D=D, reps=args.reps,
+                   rotation_kernel={str(b): ck2.rotation_kernel_name(min(b, SLICE_BITS)) for b in bits}, workloads=[measure_modes(b) for b in bits])
+        line = json.dumps(res)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+        print(line)
+        ck.close()
+        ck2.close()
+        return
 
     res = dict(tool="cb_bench", set="SK-128 + CB-128", t=T, basebit=BASEBIT, D=D, key_MiB=row_bytes / 2**20, keygen_s=keygen_s, reps=args.reps,
                workloads=[measure(b) for b in bits],

@@ -11,6 +11,11 @@ Measured: sigma_A over `--coeffs` extracted coefficients of each of the 8 level-
 extraction through the oracle's Torus64 -> Torus32 conversion) against +-mu_0; sigma_row over the 8 x 2 x 1024 coefficients of the rows T_0, T_1
 of those 8 records at level 0, with a key at sigma_pks = 2^-31 and (t, basebit) = (7, 4).
 
+Input margin of stage A: the gate-encoded input sits at +-1/8, so stage A decides its bit while the input's phase error stays inside the half-box
+1/8.  Two terms, as DESIGN 4.8: the mod-switch rounding sigma_ms = theta / (2 D) / sqrt(12) sqrt(n / 2 + 1) (theta = 1 in the default mode; the
+smallest power of two >= l in one-rotation mode) and the gate output's key-switch noise from SIGMAS,
+sigma_ks^2 = N t sigma_ks,row^2 + (N / 2) 2^(-2 t basebit) / 12 (binary ring key).  The project's threshold for "supported" is 6 sigma.
+
 usage: python tools/cb_noise.py [--rotations 8] [--coeffs 64] [--set SK-128] [--no-measure]
 """
 import argparse
@@ -58,6 +63,21 @@ def predictions():
             print("| 2^%d | (%d, %d) | %d | %.2e | %.2e | %.2e | %s | %.2e | %.2e |" % (
                 round(math.log2(spk)), t, b, 2 * D2 * t * 8192 >> 20, cols[0][0], cols[0][1], cols[0][2], "yes" if cols[0][2] < QUARTER else "no",
                 cols[1][1], cols[1][2]))
+
+
+def input_margins():
+    """half-box 1/8 over the input's phase error at stage A's mod-switch, per set and mode"""
+    print("| set | l | theta | sigma_ks (gate output) | sigma_ms, one rotation | margin, one rotation | sigma_ms, per level | margin, per level (theta = 1) |")
+    print("|---|---|---|---|---|---|---|---|")
+    for sk, cb in (("SK-128", "CB-128"), ("SK-80", "CB-80")):
+        p, s = thfhe.PARAM_SETS[sk], thfhe.SIGMAS[sk]
+        D = thfhe.CB_PARAM_SETS[cb]["N"]
+        theta = 1 if p["l"] == 1 else (2 if p["l"] == 2 else 4)
+        sks = math.sqrt(p["N"] * p["ks_t"] * s["ks"] ** 2 + p["N"] / 2 * 4.0 ** (-p["ks_t"] * p["ks_basebit"]) / 12)
+        ms = lambda th: th / (2 * D) / math.sqrt(12) * math.sqrt(p["n"] / 2 + 1)
+        margin = lambda th: 0.125 / math.hypot(sks, ms(th))
+        print("| %s / %s | %d | %d | %.2e | %.2e | %.1f sigma | %.2e | %.1f sigma |" % (sk, cb, p["l"], theta, sks, ms(theta), margin(theta), ms(1), margin(1)))
+    print("threshold for \"supported\": 6 sigma.  One-rotation mode assumes gate-encoded inputs (+-1/8): an input with a smaller box is the caller's risk.")
 
 
 def measure(name, rotations, coeffs, seed=0x5EED0C50):
@@ -109,6 +129,9 @@ if __name__ == "__main__":
     ap.add_argument("--no-measure", action="store_true")
     a = ap.parse_args()
     predictions()
+    print()
+    input_margins()
+    print()
     if not a.no_measure:
         O.lib()
         measure(a.set, a.rotations, a.coeffs)

@@ -17,6 +17,7 @@
 //   cb_pks_mfma_kernel    out = e(b) - sum_plane (A B_plane) << 8 plane: the exact int8 GEMM of sk_keyswitch_mfma_kernel with a digit-valued A.
 //                         256 inputs x 32 words per workgroup, so a key byte leaves memory once per 256 inputs.
 //                         |C_plane| <= D t 2^(basebit-1) 128 <= 2^27 (D = 2048, t = 4, basebit = 8) < 2^31.
+//   cb_extract_levels_kernel   stage A in one-rotation mode: the l records of a bit from ONE accumulator, its mask polynomial staged in LDS
 //
 // Integer sums commute: kernel, split and summation order cannot change a word.
 #ifndef THFHE_CB_H
@@ -30,6 +31,7 @@
 #include "thfhe_common.h"
 #include "thfhe_devctx.h"
 #include "thfhe_keyswitch.h"
+#include "thfhe_lane.h"
 
 namespace {
 using namespace thfhe;
@@ -139,6 +141,30 @@ __global__ __launch_bounds__(256) void cb_place_kernel(const int32_t *__restrict
     uint32_t v = (uint32_t)x[(size_t)r * (D + 1) + q];
     if (q == D) v += add;
     lwe2[((size_t)r * l + level) * (D + 1) + q] = (int32_t)v;
+}
+
+// Stage A in one-rotation mode ("one rotation per bit"): grid = bits, one workgroup per bit.  acc int64[bits][2][D] holds the rotated
+// accumulators of a test vector with mu_j at every coefficient q = j mod theta; record (bit, j), j < l, of lwe2[bits][l][D + 1] is
+// mk_extract_at_kernel's extraction at coefficient j -- a'_i = t64tot32(a_{j-i}) for i <= j, t64tot32(-a_{D+j-i}) for i > j, negated mod 2^64
+// before the conversion -- with `2^(31 - (j+1) Bgbit)` added to the body.  The mask polynomial is read once, 16 bytes per lane, into LDS (8 D
+// bytes); the l records read it from there: lane i of a wave takes word (j - i) mod D, 64 consecutive 8-byte words in descending order, one bank
+// row per half wave, conflict-free.  A record starts (bit l + j)(D + 1) words into lwe2, which is 4-byte aligned and no more: the stores are one
+// dword per lane, 64 consecutive dwords per wave.  D is a power of two, 512 <= D <= kCbMaxD (cb_extract_levels checks it).
+__global__ __launch_bounds__(256) void cb_extract_levels_kernel(const int64_t *__restrict__ acc, int D, int l, int Bgbit, int32_t *__restrict__ lwe2) {
+    __shared__ __attribute__((aligned(16))) int64_t sMask[kCbMaxD];
+    const long bit = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int64_t *ap = acc + (size_t)bit * 2 * D;
+    for (int q = 2 * tid; q < D; q += 512) *reinterpret_cast<longlong2 *>(sMask + q) = *reinterpret_cast<const longlong2 *>(ap + q);
+    __syncthreads();
+    for (int j = 0; j < l; j++) {
+        uint32_t *o = reinterpret_cast<uint32_t *>(lwe2) + ((size_t)bit * l + j) * ((size_t)D + 1);
+        for (int q = tid; q < D; q += 256) {
+            const int64_t v = sMask[(j - q) & (D - 1)];
+            o[q] = (uint32_t)t64tot32(q > j ? (int64_t)(0ull - (uint64_t)v) : v);
+        }
+        if (tid == 0) o[D] = (uint32_t)t64tot32(ap[D + j]) + (1u << (31 - (j + 1) * Bgbit));
+    }
 }
 
 // Planes: [word tile wt < 128][stage st][chunk c < 4][plane < 4][lane][4 dwords]: a 1 KiB B fragment per (wt, st, c, plane).  Byte v of dword q of

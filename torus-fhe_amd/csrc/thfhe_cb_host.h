@@ -1,6 +1,6 @@
 // thfhe_cb_host.h -- circuit bootstrapping on the single-key context: the bodies of thfhe_cb_key_set,
-// thfhe_cb_private_keyswitch and thfhe_circuit_bootstrap.  Included by thfhe_sk.hip INSIDE its second anonymous namespace, after thfhe_lhe.h
-// (it fills a thfhe_tgsw_set); the key, the kernels and their launcher are in thfhe_cb.h.
+// thfhe_cb_private_keyswitch, thfhe_cb_stage_a and thfhe_circuit_bootstrap(_mode).  Included by thfhe_sk.hip INSIDE its second anonymous
+// namespace, after thfhe_lhe.h (it fills a thfhe_tgsw_set); the key, the kernels and their launcher are in thfhe_cb.h.
 
 int cb_check_shape(int D, int t, int basebit) {
     if (D < 1 || D > kCbMaxD) return thfhe_fail(THFHE_E_INVALID, "circuit-bootstrap key: D must be 1 .. 2048");
@@ -44,26 +44,109 @@ int cb_private_keyswitch(thfhe_ctx *c, const int32_t *lwe2, size_t count, int32_
 
 constexpr size_t kCbSliceBits = 2048;   // bits per slice of thfhe_circuit_bootstrap: 64 MiB of level-2 accumulators, 2l x 16 MiB of rows
 
-// thfhe_circuit_bootstrap after its host checks, the level-2 context enqueueing on c's stream: per slice of bits stage A (one prologue, l rotations
-// with mu_j = 2^(63 - (j+1) Bgbit), extraction, + 2^(31 - (j+1) Bgbit) on the body), stage B (the private key switch) and stage C (the key
-// transform into the set's spectra).  Nothing leaves the device between the stages; `words`, if wanted, gets the rows of stage B.
-int cb_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, thfhe_tgsw_set *set, const int32_t *lwe, int32_t *words) {
+int cb_check_mode(int mode) {
+    if (mode != THFHE_CB_PER_LEVEL && mode != THFHE_CB_ONE_ROTATION)
+        return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: mode must be THFHE_CB_PER_LEVEL or THFHE_CB_ONE_ROTATION");
+    return THFHE_OK;
+}
+
+// theta of the one-rotation mode: the smallest power of two >= l (l <= 4: the engines' theta stops there)
+int cb_theta(int l) { return l <= 1 ? 1 : (l == 2 ? 2 : 4); }
+
+// the checks of the two contexts that stage A makes, under c's lock: p2 / dev2 are thfhe_mk_ctx_info's answer about the level-2 context
+int cb_check_pair(const thfhe_ctx *c, const thfhe_params &p2, int dev2, int mode) {
+    if (!c->cb.D) return thfhe_fail(THFHE_E_INVALID, "no circuit-bootstrap key (thfhe_cb_key_set)");
+    if (dev2 != c->device) return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: the two contexts are on different devices");
+    if (p2.parties != 1 || p2.n != c->p.n || p2.N != c->cb.D)
+        return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: the level-2 context needs parties = 1, the gate context's n and the key's D as its ring degree");
+    if ((c->p.l) * c->p.Bgbit > 32) return thfhe_fail(THFHE_E_UNSUPPORTED, "circuit bootstrap: l Bgbit must be at most 32");
+    if (mode == THFHE_CB_ONE_ROTATION && c->p.l > 4)
+        return thfhe_fail(THFHE_E_UNSUPPORTED, "circuit bootstrap, one rotation per bit: l must be at most 4 (theta is 1, 2 or 4)");
+    return THFHE_OK;
+}
+
+// The buffers of stage A for slices of R_max bits, and in one-rotation mode the call's test vector tv[q] = mu_(q mod theta) for q mod theta < l, else 0
+// (built here, once per call, into the context's grow-only d_cb_tv).  One-rotation mode needs neither the mod-switched words (the level-2 context
+// keeps them in its own workspace) nor the one-level hop d_cb_x.
+int cb_stage_a_prepare(thfhe_ctx *c, int mode, size_t R_max, int N2) {
+    const int l = c->p.l, n = c->p.n, D = c->cb.D;
+    THFHE_TRY(c->d_cb_lwe.grow(R_max * (n + 1) * 4));
+    THFHE_TRY(c->d_cb_acc.grow(R_max * 2 * N2 * sizeof(int64_t)));
+    THFHE_TRY(c->d_cb_lwe2.grow(R_max * l * (D + 1) * 4));
+    if (mode == THFHE_CB_PER_LEVEL) {
+        THFHE_TRY(c->d_cb_bara.grow(R_max * n * 4));
+        THFHE_TRY(c->d_cb_barb.grow(R_max * 4));
+        THFHE_TRY(c->d_cb_x.grow(R_max * (D + 1) * 4));
+        return THFHE_OK;
+    }
+    THFHE_TRY(c->d_cb_tv.grow((size_t)N2 * sizeof(int64_t)));
+    std::vector<int64_t> tv((size_t)N2, 0);
+    const int theta = cb_theta(l);
+    for (int q = 0; q < N2; q++)
+        if (q % theta < l) tv[q] = (int64_t)1 << (63 - (q % theta + 1) * c->p.Bgbit);
+    THFHE_HIP(hipMemcpyAsync(c->d_cb_tv.as<int64_t>(), tv.data(), tv.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    THFHE_HIP(hipStreamSynchronize(c->stream));   // tv goes out of scope
+    return THFHE_OK;
+}
+
+// Stage A of R bits on c's stream, which the level-2 context has been lent: d_cb_lwe [R][n + 1] -> d_cb_lwe2 [R][l][D + 1].
+//   per level:     one prologue, l rotations with mu_j = 2^(63 - (j+1) Bgbit), extraction of coefficient 0, + 2^(31 - (j+1) Bgbit) on the body
+//   one rotation:  the theta-rounded prologue, the start from d_cb_tv and ONE rotation (thfhe_mk_lut_rotate_dev), then cb_extract_levels_kernel:
+//                  coefficients 0 .. l-1 with the same body offsets
+int cb_stage_a_enqueue(thfhe_ctx *c, thfhe_mk_ctx *l2, int mode, size_t R) {
+    const int l = c->p.l, n = c->p.n, D = c->cb.D;
+    hipStream_t st = c->stream;
+    if (mode == THFHE_CB_ONE_ROTATION) {
+        if (D < 512 || (D & (D - 1))) return thfhe_fail(THFHE_E_UNSUPPORTED, "circuit bootstrap, one rotation per bit: D must be a power of two >= 512");
+        THFHE_TRY(thfhe_mk_lut_rotate_dev(l2, c->d_cb_lwe.as<int32_t>(), cb_theta(l), c->d_cb_tv.as<int64_t>(), c->d_cb_acc.as<int64_t>(), R));
+        hipLaunchKernelGGL(cb_extract_levels_kernel, dim3((unsigned)R), dim3(256), 0, st, c->d_cb_acc.as<int64_t>(), D, l, c->p.Bgbit, c->d_cb_lwe2.as<int32_t>());
+        THFHE_HIP(hipGetLastError());
+        return THFHE_OK;
+    }
+    THFHE_TRY(thfhe_mk_prologue_dev(l2, -1, 0, c->d_cb_lwe.as<int32_t>(), nullptr, nullptr, n + 1, 0, c->d_cb_bara.as<int32_t>(), c->d_cb_barb.as<int32_t>(), R));
+    for (int j = 0; j < l; j++) {
+        const int64_t mu = (int64_t)1 << (63 - (j + 1) * c->p.Bgbit);
+        THFHE_TRY(thfhe_mk_rotate_partial_dev(l2, c->d_cb_bara.as<int32_t>(), c->d_cb_barb.as<int32_t>(), mu, nullptr, c->d_cb_acc.as<int64_t>(), R));
+        THFHE_TRY(thfhe_mk_extract_dev(l2, c->d_cb_acc.as<int64_t>(), c->d_cb_x.as<int32_t>(), R));
+        hipLaunchKernelGGL(cb_place_kernel, dim3((unsigned)((D + 1 + 255) / 256), (unsigned)R), dim3(256), 0, st, c->d_cb_x.as<int32_t>(), D, l, j,
+                           1u << (31 - (j + 1) * c->p.Bgbit), c->d_cb_lwe2.as<int32_t>());
+        THFHE_HIP(hipGetLastError());
+    }
+    return THFHE_OK;
+}
+
+// thfhe_cb_stage_a after its host checks: slices of kCbSliceBits records up, stage A, the l records per bit down
+int cb_stage_a_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, int mode, const int32_t *lwe, size_t count, int32_t *lwe2) {
+    const int l = c->p.l, n = c->p.n, D = c->cb.D;
+    const size_t R_max = std::min(count, kCbSliceBits), out_words = (size_t)l * (D + 1);
+    THFHE_TRY(cb_stage_a_prepare(c, mode, R_max, N2));
+    hipStream_t st = c->stream;
+    for (size_t b0 = 0; b0 < count; b0 += R_max) {
+        const size_t R = std::min(R_max, count - b0);
+        THFHE_HIP(hipMemcpyAsync(c->d_cb_lwe.as<int32_t>(), lwe + b0 * (n + 1), R * (n + 1) * 4, hipMemcpyHostToDevice, st));
+        THFHE_TRY(cb_stage_a_enqueue(c, l2, mode, R));
+        THFHE_HIP(hipMemcpyAsync(lwe2 + b0 * out_words, c->d_cb_lwe2.as<int32_t>(), R * out_words * 4, hipMemcpyDeviceToHost, st));
+    }
+    THFHE_HIP(hipStreamSynchronize(st));
+    return THFHE_OK;
+}
+
+// thfhe_circuit_bootstrap_mode after its host checks, the level-2 context enqueueing on c's stream: per slice of bits stage A (cb_stage_a_enqueue),
+// stage B (the private key switch) and stage C (the key transform into the set's spectra).  Nothing leaves the device between the stages;
+// `words`, if wanted, gets the rows of stage B.
+int cb_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, thfhe_tgsw_set *set, const int32_t *lwe, int32_t *words, int mode) {
     const int l = c->p.l, n = c->p.n, D = c->cb.D;
     const size_t polys_per_bit = (size_t)2 * l * 2, bits = set->count * set->d, R_max = std::min(bits, kCbSliceBits);
     const size_t spec_bytes = bits * polys_per_bit * 1024 * sizeof(cplx);
+    // one-rotation mode has no one-level hop: b_x drops out (its mod-switched words, b_bara and b_barb, are in the level-2 context's workspace)
     const size_t b_lwe = R_max * (n + 1) * 4, b_bara = R_max * n * 4, b_barb = R_max * 4, b_acc = R_max * 2 * N2 * sizeof(int64_t),
-                 b_x = R_max * (D + 1) * 4, b_lwe2 = b_x * l, b_rows = R_max * polys_per_bit * 4096,
+                 b_x = mode == THFHE_CB_PER_LEVEL ? R_max * (D + 1) * 4 : 0, b_lwe2 = R_max * (D + 1) * 4 * l, b_rows = R_max * polys_per_bit * 4096,
                  b_dig = std::min<size_t>(R_max * l, kCbMaxLaunchInputs) * c->cb.nstages * kCbStage;
     size_t free_b = 0, total_b = 0;
     THFHE_HIP(hipMemGetInfo(&free_b, &total_b));
     if (spec_bytes + b_lwe + b_bara + b_barb + b_acc + b_x + b_lwe2 + b_rows + b_dig > free_b)
         return thfhe_fail(THFHE_E_NOMEM, "circuit bootstrap: count d 2l 32 KiB of spectra and the slice workspace exceed the free device memory");
-    THFHE_TRY(c->d_cb_lwe.grow(b_lwe));
-    THFHE_TRY(c->d_cb_bara.grow(b_bara));
-    THFHE_TRY(c->d_cb_barb.grow(b_barb));
-    THFHE_TRY(c->d_cb_acc.grow(b_acc));
-    THFHE_TRY(c->d_cb_x.grow(b_x));
-    THFHE_TRY(c->d_cb_lwe2.grow(b_lwe2));
+    THFHE_TRY(cb_stage_a_prepare(c, mode, R_max, N2));
     THFHE_TRY(c->d_cb_rows.grow(b_rows));
     THFHE_TRY(set->spec.grow(spec_bytes));
     hipStream_t st = c->stream;
@@ -73,15 +156,7 @@ int cb_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, thfhe_tgsw_set *set, const i
         const bool last = b0 + R == bits;
         THFHE_HIP(hipMemcpyAsync(c->d_cb_lwe.as<int32_t>(), lwe + b0 * (n + 1), R * (n + 1) * 4, hipMemcpyHostToDevice, st));
         if (prof && last) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        THFHE_TRY(thfhe_mk_prologue_dev(l2, -1, 0, c->d_cb_lwe.as<int32_t>(), nullptr, nullptr, n + 1, 0, c->d_cb_bara.as<int32_t>(), c->d_cb_barb.as<int32_t>(), R));
-        for (int j = 0; j < l; j++) {
-            const int64_t mu = (int64_t)1 << (63 - (j + 1) * c->p.Bgbit);
-            THFHE_TRY(thfhe_mk_rotate_partial_dev(l2, c->d_cb_bara.as<int32_t>(), c->d_cb_barb.as<int32_t>(), mu, nullptr, c->d_cb_acc.as<int64_t>(), R));
-            THFHE_TRY(thfhe_mk_extract_dev(l2, c->d_cb_acc.as<int64_t>(), c->d_cb_x.as<int32_t>(), R));
-            hipLaunchKernelGGL(cb_place_kernel, dim3((unsigned)((D + 1 + 255) / 256), (unsigned)R), dim3(256), 0, st, c->d_cb_x.as<int32_t>(), D, l, j,
-                               1u << (31 - (j + 1) * c->p.Bgbit), c->d_cb_lwe2.as<int32_t>());
-            THFHE_HIP(hipGetLastError());
-        }
+        THFHE_TRY(cb_stage_a_enqueue(c, l2, mode, R));
         if (prof && last) THFHE_HIP(hipEventRecord(c->ev[1], st));
         THFHE_TRY(cb_enqueue(c->cb, c->d_cb_lwe2.as<int32_t>(), (long)(R * l), l, c->d_cb_rows.as<int32_t>(), st));
         if (prof && last) THFHE_HIP(hipEventRecord(c->ev[2], st));
@@ -97,32 +172,41 @@ int cb_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, thfhe_tgsw_set *set, const i
     return THFHE_OK;
 }
 
-int circuit_bootstrap(thfhe_ctx *c, thfhe_mk_ctx *l2, const int32_t *lwe, size_t count, int d, int32_t *words, thfhe_tgsw_set **out) {
-    if (!lwe || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    *out = nullptr;
-    if (d < 1 || d > kLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: d must be 1 .. 16");
-    if (count < 1 || count > ((size_t)1 << 24)) return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: count must be 1 .. 2^24");
-    if (!c || !l2) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+// `run` under c's lock with c's stream lent to the level-2 context (one stream for all stages), handed back whatever `run` returns
+template <typename Run>
+int cb_with_level2(thfhe_ctx *c, thfhe_mk_ctx *l2, int mode, Run &&run) {
     thfhe_params p2;
     int dev2 = -1;
     THFHE_TRY(thfhe_mk_ctx_info(l2, &p2, &dev2));
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    THFHE_TRY(cb_check_pair(c, p2, dev2, mode));
+    THFHE_TRY(thfhe_mk_set_stream(l2, c->stream));
+    int rc = run(p2.N);
+    const int rc2 = thfhe_mk_set_stream(l2, nullptr);   // drains the stream first
+    return rc ? rc : rc2;
+}
+
+// stage A alone on host buffers: the counterpart of cb_private_keyswitch
+int cb_stage_a(thfhe_ctx *c, thfhe_mk_ctx *l2, const int32_t *lwe, size_t count, int mode, int32_t *lwe2) {
+    if (!lwe || !lwe2) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    THFHE_TRY(cb_check_mode(mode));
+    if (count > ((size_t)1 << 24)) return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap, stage A: count must be at most 2^24");
+    if (!c || !l2) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    return cb_with_level2(c, l2, mode, [&](int N2) { return count ? cb_stage_a_fill(c, l2, N2, mode, lwe, count, lwe2) : THFHE_OK; });
+}
+
+int circuit_bootstrap(thfhe_ctx *c, thfhe_mk_ctx *l2, const int32_t *lwe, size_t count, int d, int mode, int32_t *words, thfhe_tgsw_set **out) {
+    if (!lwe || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    *out = nullptr;
+    THFHE_TRY(cb_check_mode(mode));
+    if (d < 1 || d > kLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: d must be 1 .. 16");
+    if (count < 1 || count > ((size_t)1 << 24)) return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: count must be 1 .. 2^24");
+    if (!c || !l2) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     std::unique_ptr<thfhe_tgsw_set> set(new (std::nothrow) thfhe_tgsw_set);
     if (!set) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
     set->ctx = c, set->count = count, set->d = d;
-    int rc;
-    {
-        DevLock lk(*c);
-        if (lk.rc) return lk.rc;
-        if (!c->cb.D) return thfhe_fail(THFHE_E_INVALID, "no circuit-bootstrap key (thfhe_cb_key_set)");
-        if (dev2 != c->device) return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: the two contexts are on different devices");
-        if (p2.parties != 1 || p2.n != c->p.n || p2.N != c->cb.D)
-            return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: the level-2 context needs parties = 1, the gate context's n and the key's D as its ring degree");
-        if ((c->p.l) * c->p.Bgbit > 32) return thfhe_fail(THFHE_E_UNSUPPORTED, "circuit bootstrap: l Bgbit must be at most 32");
-        THFHE_TRY(thfhe_mk_set_stream(l2, c->stream));   // one stream for the three stages
-        rc = cb_fill(c, l2, p2.N, set.get(), lwe, words);
-        const int rc2 = thfhe_mk_set_stream(l2, nullptr);   // drains the stream first
-        if (!rc) rc = rc2;
-    }
+    const int rc = cb_with_level2(c, l2, mode, [&](int N2) { return cb_fill(c, l2, N2, set.get(), lwe, words, mode); });
     if (rc) {   // nothing is left behind: the spectra are freed on the context's device
         (void)hipSetDevice(c->device);
         return rc;

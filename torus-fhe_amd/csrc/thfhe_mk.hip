@@ -1576,6 +1576,28 @@ int thfhe_mk_rotate_partial_dev(thfhe_mk_ctx *c, const int32_t *d_bara, const in
     MKBRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), d_bara, d_barb, nullptr, (long)count, c->p.parties * c->p.n, c->words, c->p.Bgbit, mu, d_acc_in, d_acc_out};
     return mk_launch_rotation(c, a);
 }
+// the front of mk_enqueue_pbs on the caller's accumulators: the theta-rounded prologue of the records themselves (one input, weight 1, bias 0),
+// the start X^{-barb} d_tv from the ONE table, the rotation in place.  The caller extracts.
+int thfhe_mk_lut_rotate_dev(thfhe_mk_ctx *c, const int32_t *d_recs, int theta, const int64_t *d_tv, int64_t *d_acc, size_t count) {
+    if (!d_recs || !d_tv || !d_acc) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    if (theta != 1 && theta != 2 && theta != 4) return thfhe_fail(THFHE_E_INVALID, "theta must be 1, 2 or 4");
+    if (count > ((size_t)1 << 24)) return thfhe_fail(THFHE_E_INVALID, "count must be at most 2^24");
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (count == 0) return THFHE_OK;
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    THFHE_TRY(mk_ensure_workspace(c, count));
+    thfhe_lut_spec sp{};
+    sp.n_inputs = 1, sp.weights[0] = 1, sp.theta = theta;
+    const LutFlatSrc<LutIdx::none> src{d_recs, d_recs, d_recs, sp, 1, nullptr};
+    lut_prologue_launch(src, count, c->words, c->w_pad, c->log2_2n, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), nullptr, c->stream);
+    hipLaunchKernelGGL(mk_lut_acc_init_kernel, dim3((unsigned)count), dim3(256), 0, c->stream, c->d_barb.as<int32_t>(), d_tv, nullptr, (long)count, c->p.N,
+                       d_acc);
+    THFHE_HIP(hipGetLastError());
+    MKBRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), nullptr, (long)count, c->p.parties * c->p.n,
+               c->w_pad, c->p.Bgbit, 0, d_acc, d_acc};
+    return mk_launch_rotation(c, a);
+}
 int thfhe_mk_prologue_dev(thfhe_mk_ctx *c, int op, int which, const int32_t *d0, const int32_t *d1, const int32_t *d2, int rec_words,
                           int first_word, int32_t *d_bara, int32_t *d_barb, size_t count) {
     if (!c || !d0 || !d_bara || !d_barb) return thfhe_fail(THFHE_E_INVALID, "null argument");

@@ -569,9 +569,10 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     // being summed ([masks | bodies][n_tables][2^d_tree][N]) and a slice's value and table indices ([2][samples])
     DevBuf d_sc_tab, d_sc_idx;
     // circuit bootstrapping (thfhe_cb_key_set, thfhe_circuit_bootstrap): the private key-switching key; a slice's gate records, their
-    // level-2 mod-switched words, level-2 accumulators, extracted records of one level, the l records per bit and the TGSW rows
+    // level-2 mod-switched words, level-2 accumulators, extracted records of one level, the l records per bit and the TGSW rows; the Torus64 test
+    // vector of the one-rotation mode
     CbKey cb;
-    DevBuf d_cb_lwe, d_cb_bara, d_cb_barb, d_cb_acc, d_cb_x, d_cb_lwe2, d_cb_rows;
+    DevBuf d_cb_lwe, d_cb_bara, d_cb_barb, d_cb_acc, d_cb_x, d_cb_lwe2, d_cb_rows, d_cb_tv;
     int cus = 0;         // compute units of the device, asked once (ctx_cus)
     int wfa_chunk = 0;   // states per workgroup of sk_lhe_wfa_step_kernel, 0: chosen per slice (wfa_chunk_for)
     size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate); also the output records (samples x q) per slice of thfhe_mv_lut_bootstrap
@@ -1391,7 +1392,16 @@ int thfhe_cb_set_batch_threshold(thfhe_ctx *c, long min_inputs) {
 }
 
 int thfhe_circuit_bootstrap(thfhe_ctx *c, thfhe_mk_ctx *level2, const int32_t *lwe, size_t count, int d, int32_t *tgsw_words, thfhe_tgsw_set **out) {
-    return circuit_bootstrap(c, level2, lwe, count, d, tgsw_words, out);
+    return circuit_bootstrap(c, level2, lwe, count, d, THFHE_CB_PER_LEVEL, tgsw_words, out);
+}
+
+int thfhe_circuit_bootstrap_mode(thfhe_ctx *c, thfhe_mk_ctx *level2, const int32_t *lwe, size_t count, int d, int mode, int32_t *tgsw_words,
+                                 thfhe_tgsw_set **out) {
+    return circuit_bootstrap(c, level2, lwe, count, d, mode, tgsw_words, out);
+}
+
+int thfhe_cb_stage_a(thfhe_ctx *c, thfhe_mk_ctx *level2, const int32_t *lwe, size_t count, int mode, int32_t *lwe2_out) {
+    return cb_stage_a(c, level2, lwe, count, mode, lwe2_out);
 }
 
 }  // extern "C"

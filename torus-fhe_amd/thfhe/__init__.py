@@ -106,6 +106,7 @@ CB_PARAM_SETS = {
     "CB-80": dict(n=500, N=2048, k=1, l=2, Bgbit=18, ks_t=8, ks_basebit=2, torus_bits=64, parties=1),    # level 2 of SK-80
 }
 CB_BATCH_MIN_INPUTS = 3   # kCbBatchMinInputs (csrc/thfhe_cb.h): records per launch from which the private key switch runs on the matrix cores
+CB_PER_LEVEL, CB_ONE_ROTATION = 0, 1   # stage A of circuit bootstrapping: l level-2 rotations per bit, or one (include/thfhe_hip.h)
 CB_SIGMAS = {
     "CB-128": dict(lwe=2.0**-15, bk=2.0**-62.0, ks=2.0**-15),
     "CB-80": dict(lwe=2.0**-15, bk=2.0**-62.0, ks=2.0**-15),
@@ -311,6 +312,8 @@ SIGNATURES = {
     "thfhe_cb_private_keyswitch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p]),
     "thfhe_cb_set_batch_threshold": (C.c_int, [_vp, C.c_long]),
     "thfhe_circuit_bootstrap": (C.c_int, [_vp, _vp, _i32p, C.c_size_t, C.c_int, _i32p, C.POINTER(_vp)]),
+    "thfhe_circuit_bootstrap_mode": (C.c_int, [_vp, _vp, _i32p, C.c_size_t, C.c_int, C.c_int, _i32p, C.POINTER(_vp)]),
+    "thfhe_cb_stage_a": (C.c_int, [_vp, _vp, _i32p, C.c_size_t, C.c_int, _i32p]),
     "thfhe_mk_gates": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_gates_mixed": (C.c_int, [_vp, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_dag_run": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, _i64p]),
@@ -339,6 +342,7 @@ SIGNATURES = {
     "thfhe_mk_set_pair_threshold": (C.c_int, [_vp, C.c_long]),
     "thfhe_mk_rotate_partial_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_size_t]),
     "thfhe_mk_extract_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "thfhe_mk_lut_rotate_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_size_t]),
     "thfhe_mk_keyswitch_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     "thfhe_mk_dev_alloc": (_vp, [_vp, C.c_size_t]),
     "thfhe_mk_dev_free": (None, [_vp, _vp]),
@@ -1029,10 +1033,12 @@ class CloudKey(_EvalKey):
         """Inputs (records of a launch) from which the private key switch runs on the matrix cores; 0 restores the default.  No word depends on it."""
         _check(lib().thfhe_cb_set_batch_threshold(self.h, int(min_inputs)))
 
-    def circuit_bootstrap(self, recs, d, return_words=False):
+    def circuit_bootstrap(self, recs, d, return_words=False, one_rotation=False):
         """recs int32[count * d][n+1], gate-encoded records under this key's LWE key (sample-major: bit i of sample s is record s d + i) -> a TgswSet
         of count samples of d bits, device-resident, for lhe_cmux / lhe_lookup / lhe_wfa / lhe_demux / lhe_scatter and the leveled DAG entry.
-        return_words: also the rows int32[count * d][2l][2][N], as (set, words)."""
+        return_words: also the rows int32[count * d][2l][2][N], as (set, words).
+        one_rotation: the l records of a bit from ONE level-2 rotation instead of l (THFHE_CB_ONE_ROTATION): other words, the same rotation noise,
+        a theta = 2 or 4 times coarser mod-switch of the input -- for gate-encoded inputs (+-1/8) only."""
         l2 = getattr(self, "_cb_level2", None)
         if l2 is None:
             raise ThfheError("no circuit-bootstrap key: call cb_key_set first")
@@ -1044,9 +1050,23 @@ class CloudKey(_EvalKey):
         count = recs.shape[0] // d
         words = np.empty((count * d, 2 * p.l, 2, p.N), np.int32) if return_words else None
         h = _vp()
-        _check(lib().thfhe_circuit_bootstrap(self.h, l2.h, _p32(recs), count, d, _p32(words), C.byref(h)))
+        if one_rotation:
+            _check(lib().thfhe_circuit_bootstrap_mode(self.h, l2.h, _p32(recs), count, d, CB_ONE_ROTATION, _p32(words), C.byref(h)))
+        else:
+            _check(lib().thfhe_circuit_bootstrap(self.h, l2.h, _p32(recs), count, d, _p32(words), C.byref(h)))
         tset = TgswSet._adopt(self, h, count, d)
         return (tset, words) if return_words else tset
+
+    def cb_stage_a(self, recs, one_rotation=False):
+        """Stage A of circuit bootstrapping alone: recs int32[count][n+1], gate-encoded records -> int32[count][l][D+1], record (s, j) an LWE sample
+        of m g_j under the level-2 ring key: the input of cb_private_keyswitch.  one_rotation as in circuit_bootstrap."""
+        l2, D = getattr(self, "_cb_level2", None), getattr(self, "_cb_D", None)
+        if l2 is None:
+            raise ThfheError("no circuit-bootstrap key: call cb_key_set first")
+        recs = _rec(recs, self.words)
+        out = np.empty((recs.shape[0], self.params.l, D + 1), np.int32)
+        _check(lib().thfhe_cb_stage_a(self.h, l2.h, _p32(recs), recs.shape[0], CB_ONE_ROTATION if one_rotation else CB_PER_LEVEL, _p32(out)))
+        return out
 
     def set_wfa_chunk(self, g):
         """States per workgroup of a step of lhe_wfa, 1 .. 64; 0: automatic.  No output word depends on it."""

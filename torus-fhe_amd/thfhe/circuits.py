@@ -852,18 +852,19 @@ def lhe_sbox(ck, tset, table, p_out=8):
     return np.stack(outs, axis=1)
 
 
-def cb_lookup(ck, a_recs, b_recs, table, p_out=8):
+def cb_lookup(ck, a_recs, b_recs, table, p_out=8, one_rotation=False):
     """A table read at an address the circuit computed (circuit bootstrapping): a_recs, b_recs int32[count * d][n+1] hold the gate-encoded
     bits of two d-bit numbers per sample (sample-major, low bit first; d = log2(len(table)), 1 <= d <= 10), the address is a XOR b -- d XOR gates
     per sample --, CloudKey.circuit_bootstrap turns the gate outputs into TGSW address bits and lhe_lookup reads `table` (integers in [0, p_out)) with
-    d CMuxes.  `ck` holds a circuit-bootstrap key (cb_key_set).  Returns int32[count, n+1]: the entry at modulus p_out (thfhe.lut.encode)."""
+    d CMuxes.  `ck` holds a circuit-bootstrap key (cb_key_set).  one_rotation: CloudKey.circuit_bootstrap's (the XOR outputs are gate-encoded, as
+    it needs).  Returns int32[count, n+1]: the entry at modulus p_out (thfhe.lut.encode)."""
     from . import lut
     t = np.asarray(table, np.int64).reshape(-1)
     d = t.shape[0].bit_length() - 1
     if not 1 <= d <= 10 or t.shape[0] != 1 << d or np.any((t < 0) | (t >= p_out)):
         raise ValueError("table: expected 2^d integers in [0, p_out), 1 <= d <= 10")
     addr = ck.gates(XOR, a_recs, b_recs)
-    with ck.circuit_bootstrap(addr, d) as tset:
+    with ck.circuit_bootstrap(addr, d, one_rotation=one_rotation) as tset:
         return ck.lhe_lookup(tset, lut.lhe_table(t, 0, d, encode=lambda v: lut.encode(v, p_out)), d_tree=0, d_rot=d)[:, 0]
 
 
