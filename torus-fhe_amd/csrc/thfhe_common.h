@@ -131,23 +131,12 @@ __device__ __forceinline__ void ring_dma(uint64_t gbase_uniform, uint32_t lane_b
     asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" ::"v"(lane_byte_off), "s"(gbase_uniform), "{m0}"(lds_byte_off), "n"(IMM) : "memory");
 }
 // Hand-off barrier of the ring: this wave's own slice of the chunk has landed (at most VM younger DMAs in flight), every LDS read it issued
-// has returned, then the workgroup barrier.  Two forms: the wait inside an asm (default), or the s_waitcnt BUILTIN -- with the builtin the compiler's
-// wait-count pass knows that nothing is pending on lgkmcnt after the barrier and counts the waits of reads issued right after it exactly (with the asm
-// it puts a conservative lgkmcnt(0) in front of the first multiply after the barrier; harmless in the default order, where no read is pending there).
-// gfx9 encoding of s_waitcnt: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14.
-#ifndef THFHE_RING_ASM_BARRIER
-#define THFHE_RING_ASM_BARRIER 1   // the builtin form times the same (profiles/r04_ring_multiply_phase.md); the asm form is the one every round measured
-#endif
+// has returned, then the workgroup barrier.  The wait sits inside the asm: the compiler's wait-count pass then puts a conservative lgkmcnt(0) in front
+// of the first multiply after the barrier, harmless in this order, where no read is pending there.  The form with the s_waitcnt and s_barrier builtins
+// times the same (profiles/r04_ring_multiply_phase.md); the asm form is the one every round measured.
 template <int VM>
 __device__ __forceinline__ void ring_barrier() {
-#if THFHE_RING_ASM_BARRIER
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM) : "memory");
-#else
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt((VM & 15) | (7 << 4) | (0 << 8) | ((VM >> 4) << 14));
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-#endif
 }
 __device__ __forceinline__ void wave_fft_fwd_s(int lane, cplx (&z)[8], cplx *xb, const cplx *T1, const W64 &w) {
     wave_sync();
@@ -167,26 +156,7 @@ __device__ __forceinline__ void wave_fft_inv_s(int lane, cplx (&z)[8], cplx *xb,
     wave_sync();
     invs_seg3(lane, z, xb, T1);
 }
-// variant "r": padded buffer, pass-1 twiddles from per-lane roots (thfhe_lane.h)
-__device__ __forceinline__ void wave_fft_fwd_r(int lane, cplx (&z)[8], cplx *xb, const LaneRoots &r, const W64 &w) {
-    wave_sync();
-    fwdr_seg1(lane, z, xb, r);
-    wave_sync();
-    fwd_seg2_ld(lane, z, xb);
-    fwdr_seg2_st(lane, z, xb, w);
-    wave_sync();
-    fwd_seg3(lane, z, xb);
-}
-__device__ __forceinline__ void wave_fft_inv_r(int lane, cplx (&z)[8], cplx *xb, const LaneRoots &r, const W64 &w) {
-    wave_sync();
-    invr_seg1(lane, z, xb, w);
-    wave_sync();
-    inv_seg2_ld(lane, z, xb);
-    inv_seg2_st(lane, z, xb);
-    wave_sync();
-    invr_seg3(lane, z, xb, r);
-}
-// variant "q": first transpose in registers.  Exchange of the register index (bits 2,1,0) with lane bits (5,4,3):
+// variant "q" (padded buffer, pass-1 twiddles from per-lane roots: thfhe_lane.h): first transpose in registers.  Exchange of the register index (bits 2,1,0) with lane bits (5,4,3):
 //   stage A  z[r] (r < 4) of the upper half-wave <-> z[r + 4] of the lower half-wave      v_permlane32_swap
 //   stage B  z[r] (bit 1 clear) of the odd 16-lane rows <-> z[r + 2] of the even rows      v_permlane16_swap
 //   stage C  lanes with bit 3 clear take z[r] (r even) of lane ^ 8 into z[r + 1], lanes with bit 3 set take z[r + 1] into z[r]
@@ -245,24 +215,15 @@ __device__ __forceinline__ void wave_transpose_hi3(cplx (&z)[8]) {
 #pragma unroll
     for (int r = 0; r < 8; r++) __builtin_memcpy(&z[r], w[r], 16);
 }
-template <class Roots>
-__device__ __forceinline__ void wave_fft_fwd_q(int lane, cplx (&z)[8], cplx *xb, const Roots &r, const W64 &w) {
+// forward "q"; the inverse (invr_seg1 | inv_seg2_ld, dft8<-1> | wave_transpose_hi3, invq_seg3) is written out where it is used, with key requests
+// between its stages (sk_blind_rotate_coop_kernel, thfhe_lhe.h)
+__device__ __forceinline__ void wave_fft_fwd_q(int lane, cplx (&z)[8], cplx *xb, const LaneRoots &r, const W64 &w) {
     fwdq_seg1(z, r);
     wave_transpose_hi3(z);
     wave_sync();
     fwdr_seg2_st(lane, z, xb, w);
     wave_sync();
     fwd_seg3(lane, z, xb);
-}
-template <class Roots>
-__device__ __forceinline__ void wave_fft_inv_q(int lane, cplx (&z)[8], cplx *xb, const Roots &r, const W64 &w) {
-    wave_sync();
-    invr_seg1(lane, z, xb, w);
-    wave_sync();
-    inv_seg2_ld(lane, z, xb);
-    dft8<-1>(z);
-    wave_transpose_hi3(z);
-    invq_seg3(z, r);
 }
 // variant "f": the exchanges of "q", every inter-pass twiddle folded into the butterflies of the following pass (thfhe_lane.h)
 __device__ __forceinline__ void wave_fft_fwd_f(int lane, cplx (&z)[8], cplx *xb, const LaneRootsF &r) {
@@ -286,8 +247,7 @@ __device__ __forceinline__ void wave_fft_inv_f(int lane, cplx (&z)[8], cplx *xb,
 }
 // variant "qs" (multi-key kernels, whose LDS has no room for padded buffers): first transpose in registers, pass-1 twiddles from the
 // per-lane roots, second transpose through the XOR-swizzled 512-slot buffer -- one LDS crossing and no T1 table reads per transform
-template <class Roots>
-__device__ __forceinline__ void wave_fft_fwd_qs(int lane, cplx (&z)[8], cplx *xb, const Roots &r, const W64 &w) {
+__device__ __forceinline__ void wave_fft_fwd_qs(int lane, cplx (&z)[8], cplx *xb, const LaneRoots &r, const W64 &w) {
     fwdq_seg1(z, r);
     wave_transpose_hi3(z);
     wave_sync();
@@ -295,8 +255,7 @@ __device__ __forceinline__ void wave_fft_fwd_qs(int lane, cplx (&z)[8], cplx *xb
     wave_sync();
     fwds_seg3(lane, z, xb);
 }
-template <class Roots>
-__device__ __forceinline__ void wave_fft_inv_qs(int lane, cplx (&z)[8], cplx *xb, const Roots &r, const W64 &w) {
+__device__ __forceinline__ void wave_fft_inv_qs(int lane, cplx (&z)[8], cplx *xb, const LaneRoots &r, const W64 &w) {
     wave_sync();
     invs_seg1(lane, z, xb, w);
     wave_sync();

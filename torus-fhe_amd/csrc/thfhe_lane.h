@@ -97,8 +97,9 @@ THFHE_FN int xs_c(int k1, int lane) { return (lane >> 3) * 72 + k1 * 9 + (lane &
 THFHE_FN int xs_d(int j0, int lane) { return (lane >> 3) * 72 + (lane & 7) * 9 + j0; }      // lane = k1 + 8 k0
 
 // ---- forward transform, three segments -------------------------------------------------------------
-// This table form (padded buffer, T1 and T2 read from tables) runs in no product kernel: tests/emu/lane_emu.cpp keeps it as the
-// reference that the "s", "r", "q" and N = 2048 forms below are checked against ("f": tests/emu/fold_emu.cpp).
+// This table form (padded buffer, T1 and T2 read from tables) runs whole in no product kernel (its fwd_seg3 and inv_seg2_ld are halves of
+// "q" and "f" below): tests/emu/lane_emu.cpp keeps it as the reference that the "s", "r", "q" and N = 2048 forms below are checked
+// against ("f": tests/emu/fold_emu.cpp).
 // z[m] on entry: folded coefficients (p[lane + 64 m], p[lane + 64 m + 512])
 THFHE_FN void fwd_seg1(int lane, cplx (&z)[8], cplx *xbuf, const cplx *T1) {
 #pragma unroll
@@ -144,17 +145,6 @@ THFHE_FN void inv_seg2_st(int lane, cplx (&z)[8], cplx *xbuf) {
 #pragma unroll
     for (int j1 = 0; j1 < 8; j1++) xbuf[xs_b(j1, lane)] = z[j1];
 }
-THFHE_FN void inv_seg3_ld(int lane, cplx (&z)[8], const cplx *xbuf) {
-#pragma unroll
-    for (int k0 = 0; k0 < 8; k0++) z[k0] = xbuf[xs_a(k0, lane)];
-}
-THFHE_FN void inv_seg3_fin(int lane, cplx (&z)[8], const cplx *T1) {
-#pragma unroll
-    for (int k0 = 0; k0 < 8; k0++) z[k0] = cmul_conj(z[k0], T1[k0 * 64 + lane]);
-    dft8<-1>(z);
-#pragma unroll
-    for (int m = 1; m < 8; m++) z[m] = cmul_conj(z[m], cplx{THFHE_C_RE(m), THFHE_C_IM(m)});
-}
 THFHE_FN void inv_seg3(int lane, cplx (&z)[8], const cplx *xbuf, const cplx *T1) {
 #pragma unroll
     for (int k0 = 0; k0 < 8; k0++) z[k0] = cmul_conj(xbuf[xs_a(k0, lane)], T1[k0 * 64 + lane]);
@@ -165,7 +155,9 @@ THFHE_FN void inv_seg3(int lane, cplx (&z)[8], const cplx *xbuf, const cplx *T1)
 
 // ---- variant with an unpadded, XOR-swizzled 512-slot transpose buffer and pass-2 twiddles as powers of one per-lane
 // root w = exp(2 pi i (lane & 7) / 64) (w, w^2, w^4 held in registers; w^3, w^5, w^6, w^7 by one product each).
-// Used by the LDS-ring kernel, whose 160 KiB LDS budget has no room for padding or for the T2 table.
+// Variant "s", for kernels whose LDS has no room for padding or for the T2 table.  It runs whole (pass-1 twiddles from a T1 table) in the
+// key transform (thfhe_transform.h), the polynomial kernels (thfhe_pm_kernels.h), thfhe_threshold.hip, thfhe_ccs.hip and the multi-key
+// cooperative kernel; its second transpose also serves the "qs" and twisted forms of the multi-key rotation kernels.
 //   transpose 1: column (j1*8 + j0) of row k0 is XORed with 8*(k0 & 1);
 //   transpose 2: column (k1*8 + (j0 ^ k1)) of row k0 is XORed with 8*((k0 >> 1) & 1)          
 THFHE_FN int ys_a(int k0, int lane) { return k0 * 64 + (lane ^ ((k0 & 1) << 3)); }
@@ -236,11 +228,13 @@ THFHE_FN void invs_seg3(int lane, cplx (&z)[8], const cplx *xbuf, const cplx *T1
     for (int m = 1; m < 8; m++) z[m] = cmul_conj(z[m], cplx{THFHE_C_RE(m), THFHE_C_IM(m)});
 }
 
-// ---- variant "r" (second-generation LDS-ring kernel): padded 576-slot buffer (three LDS address registers per wave instead of
-// the 25 the XOR maps need) and pass-1 twiddles rebuilt from two per-lane roots instead of read from the 8 KiB T1 table:
+// ---- variant "r": padded 576-slot buffer (three LDS address registers per wave instead of the 25 the XOR maps need) and pass-1
+// twiddles rebuilt from two per-lane roots instead of read from the 8 KiB T1 table:
 //     T1[k0][lane] = zeta^(lane (4 k0 + 1)) = b * s^k0,    b = zeta^lane,  s = zeta^(4 lane)
 // (one square and seven products per transform, two interleaved chains of depth 4; the table reads were a dependent LDS round trip
 // in front of every transpose store, the products are FP64 work the SIMD has room for).  Same spectra order as the other variants.
+// No kernel runs "r" whole any more.  fwdr_seg2_st and invr_seg1 are the LDS halves of "q"; fwdr_seg1 and invr_seg3 (both transposes
+// through the LDS) stay as the host-checked baseline that "q" and "f" are compared against (tests/emu/lane_emu.cpp, fold_emu.cpp).
 struct LaneRoots {
     cplx b, s;
 };
@@ -297,7 +291,8 @@ THFHE_FN void invr_seg3(int lane, cplx (&z)[8], const cplx *xbuf, const LaneRoot
 // registers between its lanes with v_permlane32_swap (lane bit 5), v_permlane16_swap (bit 4) and a row_ror:8 DPP move (bit 3) --
 // 80 32-bit VALU instructions per transpose in place of 8 ds_write_b128 + 8 ds_read_b128 (136 cycles of the CU's one LDS pipe, the
 // busiest unit of the first-generation kernel).  The lane functions below are the per-lane halves; the exchange itself is
-// wave_transpose_hi3 (thfhe_common.h on the device, lanes_transpose_hi3 in the emulator).
+// wave_transpose_hi3 (thfhe_common.h on the device, lanes_transpose_hi3 in the emulator).  Runs in the single-key cooperative kernel and
+// the leveled kernels (thfhe_lhe.h); with the XOR-swizzled buffer of "s" for the second transpose ("qs") in the multi-key rotation kernels.
 THFHE_FN void fwdq_seg1(cplx (&z)[8], const LaneRoots &r) {
 #pragma unroll
     for (int m = 1; m < 8; m++) z[m] = cmul(z[m], cplx{THFHE_C_RE(m), THFHE_C_IM(m)});
@@ -331,22 +326,8 @@ THFHE_FN void invq_seg3(cplx (&z)[8], const LaneRoots &r) {
     for (int m = 1; m < 8; m++) z[m] = cmul_conj(z[m], cplx{THFHE_C_RE(m), THFHE_C_IM(m)});
 }
 
-// Register-lean form of the "q" pass-1 twiddles for kernels at the VGPR limit (LDS-ring kernel): the compiler hoists the eight products
-// b s^k0 of fwdq_seg1 out of the CMux loop (32 VGPRs) and then spills some of them; here only the even ones e_j = b s^(2j) live across
-// the loop (16 VGPRs + s), the odd ones e_j s are formed in place (four more complex products per transform).  `s` is passed through an
-// empty asm so that these products are not hoisted as well.
-struct LaneTw {
-    cplx e[4], s;
-};
-THFHE_FN LaneTw make_lane_tw(const LaneRoots &r) {
-    LaneTw t;
-    const cplx s2 = cmul(r.s, r.s);
-    t.e[0] = r.b;
-#pragma unroll
-    for (int j = 1; j < 4; j++) t.e[j] = cmul(t.e[j - 1], s2);
-    t.s = r.s;
-    return t;
-}
+// Kernels at the VGPR limit: the compiler hoists the eight products b s^k0 of fwdq_seg1 / invq_seg3 out of a CMux loop (32 VGPRs) and then
+// spills some of them.  Roots passed through an empty asm are rebuilt per transform instead (the multi-key rotation kernels).
 THFHE_FN cplx opaque_cplx(cplx v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(v.re), "+v"(v.im));
@@ -359,28 +340,6 @@ THFHE_FN void opaque_in_place(cplx &v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(v.re), "+v"(v.im));
 #endif
-}
-THFHE_FN void fwdq_seg1(cplx (&z)[8], const LaneTw &t) {
-#pragma unroll
-    for (int m = 1; m < 8; m++) z[m] = cmul(z[m], cplx{THFHE_C_RE(m), THFHE_C_IM(m)});
-    dft8<+1>(z);
-    const cplx s = opaque_cplx(t.s);
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        z[2 * j] = cmul(z[2 * j], t.e[j]);
-        z[2 * j + 1] = cmul(z[2 * j + 1], cmul(t.e[j], s));
-    }
-}
-THFHE_FN void invq_seg3(cplx (&z)[8], const LaneTw &t) {
-    const cplx s = opaque_cplx(t.s);
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        z[2 * j] = cmul_conj(z[2 * j], t.e[j]);
-        z[2 * j + 1] = cmul_conj(z[2 * j + 1], cmul(t.e[j], s));
-    }
-    dft8<-1>(z);
-#pragma unroll
-    for (int m = 1; m < 8; m++) z[m] = cmul_conj(z[m], cplx{THFHE_C_RE(m), THFHE_C_IM(m)});
 }
 
 // ---- variant "f" (eight- and four-wave ring kernel): the exchanges of "q", every inter-pass twiddle FOLDED into the butterflies of the
@@ -730,16 +689,6 @@ THFHE_FN void cfma_negkey(cplx &s, cplx z, cplx b) {
     s.im = __builtin_fma(z.re, b.im, s.im);
     s.re = __builtin_fma(z.im, -b.im, s.re);
     s.im = __builtin_fma(z.im, b.re, s.im);
-}
-// S[m] += z[m] * B[m*64 + lane], one slice at a time with the smallest register footprint: the ring kernels run at the 256-VGPR
-// limit, where this form (18 spilled registers) beats the batched-FMA form below (31+) by 4-20 % (measured)
-THFHE_FN void mac8_lean(int lane, cplx (&S)[8], const cplx (&z)[8], const cplx *B) {
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-        cplx b = B[m * 64 + lane];
-        S[m].re += z[m].re * b.re - z[m].im * b.im;
-        S[m].im += z[m].re * b.im + z[m].im * b.re;
-    }
 }
 // S[m] += z[m] * B[m*64 + lane]; DEPTH key slices are requested ahead of the multiplies (kernels with registers to spare)
 template <int DEPTH = 8>

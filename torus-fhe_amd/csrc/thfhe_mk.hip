@@ -184,34 +184,17 @@ __global__ __launch_bounds__(512, 2) void mk_blind_rotate_coop_kernel(MKBRArgs a
 // spectra of two gates, so each key byte serves two CMuxes; the 2 x 2l forward transforms of a step keep all eight waves busy in
 // phase 1 (l = 2: one each), and the transpose scratch aliases the spectrum area (a third barrier frees it for the inverses), which is
 // what lets two accumulators and two sets of spectra fit: acc 32 + spectra 2 x 2l x 8 KiB (l = 3: 128 KiB).  Transforms are variant "qs"
-// (first transpose in registers, pass-1 twiddles from per-lane roots: no T1 table, one LDS crossing per transform); measured on MI355X the
-// three ways of holding the pass-1 twiddles give MK2 39.5 k (hoisted by the compiler, 88 B/lane scratch) / 45.8 k (LaneTw, 48 B) /
-// 52.2 k gates/s (rebuilt per transform, 8 B): with four key rows carried across the loop the registers are worth more than 28 FP64
-// instructions per transform.
+// (first transpose in registers, pass-1 twiddles from per-lane roots: no T1 table, one LDS crossing per transform).  The eight pass-1 products
+// b s^k are rebuilt in every transform from the two roots, passed through an empty asm (8 VGPRs across the CMux loop): measured on MI355X, MK2 runs
+// 39.5 k gates/s when the compiler may hoist all eight out of the loop (32 VGPRs, 88 B/lane scratch), 45.8 k with only the even ones kept
+// (20 VGPRs, 48 B) and 52.2 k rebuilt (8 B): with four key rows carried across the loop the registers are worth more than 28 FP64 instructions
+// per transform.
 // ------------------------------------------------------------------------------------------------------
 // mk_pin: memory operations do not move across this point (keeps the paced key requests where they are written)
 __device__ __forceinline__ void mk_pin2() { asm volatile("" ::: "memory"); }
 // inverse transform of one partial spectrum with the requests for two key rows of the NEXT step between its stages
-#ifndef THFHE_MK_LEAN_ROOTS
-#define THFHE_MK_LEAN_ROOTS 2
-#endif
-// pass-1 twiddles of the "qs" transforms: 0 = the compiler may hoist all eight products b s^k out of the CMux loop (32 VGPRs),
-// 1 = only the even ones live across the loop (LaneTw, 20 VGPRs), 2 = everything is rebuilt per transform from the two roots (8 VGPRs)
-#if THFHE_MK_LEAN_ROOTS == 1
-typedef LaneTw MK_ROOTS;
-__device__ __forceinline__ MK_ROOTS mk_make_roots(const LaneRoots &r) { return make_lane_tw(r); }
-__device__ __forceinline__ const MK_ROOTS &mk_use_roots(const MK_ROOTS &r) { return r; }
-#elif THFHE_MK_LEAN_ROOTS == 2
-typedef LaneRoots MK_ROOTS;
-__device__ __forceinline__ MK_ROOTS mk_make_roots(const LaneRoots &r) { return r; }
-__device__ __forceinline__ MK_ROOTS mk_use_roots(const MK_ROOTS &r) { return LaneRoots{opaque_cplx(r.b), opaque_cplx(r.s)}; }
-#else
-typedef LaneRoots MK_ROOTS;
-__device__ __forceinline__ MK_ROOTS mk_make_roots(const LaneRoots &r) { return r; }
-__device__ __forceinline__ const MK_ROOTS &mk_use_roots(const MK_ROOTS &r) { return r; }
-#endif
 template <bool PF0, bool PF1>
-__device__ __forceinline__ void inv_s_prefetch(int lane, cplx (&S)[8], cplx *xb, const MK_ROOTS &roots, const W64 &w, cplx (&b0)[8], const cplx *src0, cplx (&b1)[8],
+__device__ __forceinline__ void inv_s_prefetch(int lane, cplx (&S)[8], cplx *xb, const LaneRoots &roots, const W64 &w, cplx (&b0)[8], const cplx *src0, cplx (&b1)[8],
                                                const cplx *src1) {   // wave_fft_inv_qs with the requests in between
     wave_sync();
     invs_seg1(lane, S, xb, w);
@@ -225,7 +208,7 @@ __device__ __forceinline__ void inv_s_prefetch(int lane, cplx (&S)[8], cplx *xb,
     if (PF1) load8(lane, b1, src1);
     mk_pin2();
     wave_transpose_hi3(S);
-    invq_seg3(S, mk_use_roots(roots));
+    invq_seg3(S, LaneRoots{opaque_cplx(roots.b), opaque_cplx(roots.s)});
 }
 template <int L>
 __global__ __launch_bounds__(512, 2) void mk_blind_rotate_pair_kernel(MKBRArgs a) {
@@ -238,8 +221,7 @@ __global__ __launch_bounds__(512, 2) void mk_blind_rotate_pair_kernel(MKBRArgs a
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
-    const LaneRoots roots0{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
-    const MK_ROOTS roots = mk_make_roots(roots0);
+    const LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
     const long job0 = 2 * (long)blockIdx.x;
     const bool has1 = job0 + 1 < a.jobs;
     const int32_t *bara0 = a.bara + job0 * a.w_pad;
@@ -286,7 +268,7 @@ __global__ __launch_bounds__(512, 2) void mk_blind_rotate_pair_kernel(MKBRArgs a
                     load_rotated16_hi(lane, sAcc[g] + (r / L) * 1024, ai & 2047, offset, t);
                     digits_to_z(t, (r % L) + 1, Bgbit, z);
                     cplx *slot = sSpec + f * 512;  // transposes run inside the task's own, not yet published, spectrum slot
-                    wave_fft_fwd_qs(opaque_lane(lane), z, slot, mk_use_roots(roots), w64);
+                    wave_fft_fwd_qs(opaque_lane(lane), z, slot, LaneRoots{opaque_cplx(roots.b), opaque_cplx(roots.s)}, w64);
                     wave_sync();
 #pragma unroll
                     for (int m = 0; m < 8; m++) slot[m * 64 + lane] = z[m];

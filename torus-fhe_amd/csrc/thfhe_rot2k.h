@@ -282,18 +282,7 @@ __device__ __forceinline__ void r2k_finish(int ln, int lane, int h, cplx (&S0)[8
 }
 
 // S += spectrum slot * key chunk, the slot read in two halves (16 registers of digit spectrum alive instead of 32)
-#ifndef R2K_KMS_HALVES
-#define R2K_KMS_HALVES 1
-#endif
-template <int HALVES = 1>
 __device__ __forceinline__ void r2k_mac_slot(cplx (&S)[8], const cplx *slot, int lane, const cplx (&b)[8]) {
-    if (!HALVES) {
-        cplx z[8];
-#pragma unroll
-        for (int m = 0; m < 8; m++) z[m] = slot[m * 64 + lane];
-        mac8r(S, z, b);
-        return;
-    }
 #pragma unroll
     for (int m0 = 0; m0 < 8; m0 += 4) {
         cplx z[4];
@@ -386,8 +375,8 @@ __global__ __launch_bounds__(512, 2) void kms_tlev_rotate_pair_kernel(KmsBRArgs 
 #pragma unroll
             for (int q = 0; q < BATCH; q++) {
                 if (q < nb) {
-                    if (ai0 != 0) r2k_mac_slot<R2K_KMS_HALVES>(S0a, sSpec + q * 512, lane, B[q % PRE]);
-                    if (ai1 != 0) r2k_mac_slot<R2K_KMS_HALVES>(S0b, sSpec + (BATCH + q) * 512, lane, B[q % PRE]);
+                    if (ai0 != 0) r2k_mac_slot(S0a, sSpec + q * 512, lane, B[q % PRE]);
+                    if (ai1 != 0) r2k_mac_slot(S0b, sSpec + (BATCH + q) * 512, lane, B[q % PRE]);
                     kms_pin();
                     if (q + PRE < nb) load8(gl, B[q % PRE], chunk(i, b0 + q + PRE, 0));
                     kms_pin();
@@ -418,8 +407,8 @@ __global__ __launch_bounds__(512, 2) void kms_tlev_rotate_pair_kernel(KmsBRArgs 
 #pragma unroll
             for (int q = 0; q < BATCH; q++) {
                 if (q < nb) {
-                    if (ai0 != 0) r2k_mac_slot<R2K_KMS_HALVES>(S1a, sSpec + q * 512, lane, B[q % PRE]);
-                    if (ai1 != 0) r2k_mac_slot<R2K_KMS_HALVES>(S1b, sSpec + (BATCH + q) * 512, lane, B[q % PRE]);
+                    if (ai0 != 0) r2k_mac_slot(S1a, sSpec + q * 512, lane, B[q % PRE]);
+                    if (ai1 != 0) r2k_mac_slot(S1b, sSpec + (BATCH + q) * 512, lane, B[q % PRE]);
                     kms_pin();
                     if (q + PRE < nb) load8(gl, B[q % PRE], chunk(i, b0 + q + PRE, 1));
                     kms_pin();

@@ -10,9 +10,6 @@
 // nothing is scheduled across this point: without it the multiply-accumulates of a row sink below the requests for the next row's key chunk and the
 // registers of both rows, the spectrum points and the partial sums are live at once
 #define R4K_FENCE() do { kms_pin(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#ifndef R4K_EARLY_KEY
-#define R4K_EARLY_KEY 0
-#endif
 
 struct R4KArgs {
     const cplx *bk;       // key spectra [step][row part][output o][limb h][quarter][512]
@@ -117,12 +114,6 @@ __global__ __launch_bounds__(512, 2) void r4k_rotate_kernel(R4KArgs a, cplx *__r
             // ---- forward quarter transforms into the slots; first key chunks requested
             cplx B[PRE][8];
             const int gl = opaque_lane(lane);
-#if R4K_EARLY_KEY
-            kms_pin();
-            load8(gl, B[0], chunk(i, 0, 2 * P));
-            load8(gl, B[1], chunk(i, 0, 2 * P + 1));
-            kms_pin();
-#endif
             {
                 const int ln = opaque_lane(lane);
                 const W64 w64{a.tw[TwRing2k::T2 + 1 * 8 + (ln & 7)]};
@@ -141,9 +132,6 @@ __global__ __launch_bounds__(512, 2) void r4k_rotate_kernel(R4KArgs a, cplx *__r
                 if (t0) transform(q0, q0 * ROWP + rp0, y0);
                 if (t1) transform(q1, q1 * ROWP + rp1, y1);
             }
-#if R4K_EARLY_KEY
-            lds_barrier<8 * PRE>();   // spectra published
-#else
             // the first key rows are requested AFTER the transforms: held across them (64 VGPRs next to two tasks' points and twiddles) they were
             // spilled as soon as they arrived
             kms_pin();
@@ -151,7 +139,6 @@ __global__ __launch_bounds__(512, 2) void r4k_rotate_kernel(R4KArgs a, cplx *__r
             load8(gl, B[1], chunk(i, 0, 2 * P + 1));
             kms_pin();
             lds_barrier<8 * PRE>();   // spectra published
-#endif
             // ---- multiply: row part q, quarters 2P (chunk in B[0]) and 2P + 1 (B[1])
 #pragma unroll
             for (int t = 0; t < 2; t++)
@@ -162,11 +149,11 @@ __global__ __launch_bounds__(512, 2) void r4k_rotate_kernel(R4KArgs a, cplx *__r
 #pragma unroll 1
             for (int q = 0; q < RP; q++) {
                 const int qn = q + 1 < RP ? q + 1 : q;
-                r2k_mac_slot<1>(S[0], sSpec + q * 512, lane, B[0]);
+                r2k_mac_slot(S[0], sSpec + q * 512, lane, B[0]);
                 R4K_FENCE();
                 load8(gl, B[0], chunk(i, qn, 2 * P));
                 R4K_FENCE();
-                r2k_mac_slot<1>(S[1], sSpec + (ROWP + q) * 512, lane, B[1]);
+                r2k_mac_slot(S[1], sSpec + (ROWP + q) * 512, lane, B[1]);
                 R4K_FENCE();
                 load8(gl, B[1], chunk(i, qn, 2 * P + 1));
                 R4K_FENCE();

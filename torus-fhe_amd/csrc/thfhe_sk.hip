@@ -12,7 +12,8 @@
 //                             The blind-rotate kernels' LUT instantiations start from a test vector and extract theta coefficients
 //   sk_blind_rotate_ring_kernel / sk_blind_rotate_coop_kernel   blind_rotate_and_extract (J/bootstrap.jl:38-65): accumulator in
 //                             LDS for all n CMuxes; throughput (8 gates per workgroup, key through an LDS-DMA ring) and latency
-//                             (one workgroup per gate) variants
+//                             (one workgroup per gate) kernels; each is built in one form only, the forms that were measured against
+//                             them and lost are written up in profiles/r03_ring_variants.md and r04_ring_multiply_phase.md
 //   ks_plain_kernel / ks_staged_kernel / sk_keyswitch_mfma_kernel   keyswitch (J/keyswitch.jl:45-80) (+ the MUX combine of J/gates.jl:172-176),
 //   (thfhe_keyswitch.h, shared with the multi-key engines): one gate per workgroup (small batches); from 192 gates on the rows of a few
 //                             (i, j) staged in LDS for 32 gates, the digit selecting an address; from 512 gates on an int8 GEMM on the matrix cores
@@ -20,7 +21,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -143,55 +143,40 @@ constexpr int kGate = 0, kLut = 1, kLutEnc = 2, kLutMv = 3;
 // A wave whose mod-switched mask word is 0 (J/bootstrap.jl:40) or that has no job still streams and synchronises.  Measured
 // (profiles/r09_handoff_timing.md): what the barriers cost was skew between the two waves of a SIMD, not the multiply phase itself.
 //
-// What the second generation changed comes from an in-kernel cycle trace and the PMC counters of the first (tools/ring_stamps.py,
-// profiles/r02_ring_generations.md): with two waves per SIMD that kernel was bound by exposed LDS round trips and by the LDS
-// instruction pipe (69 % busy, bursts in lock step), with the VALU 55 % busy.  So:
-//   * the FIRST transpose of every transform (register index <-> lane bits 3..5) stays in registers: v_permlane32_swap,
-//     v_permlane16_swap and row_ror:8 DPP moves (wave_transpose_hi3) instead of 8 ds_write_b128 + 8 ds_read_b128;
-//   * pass-1 twiddles are rebuilt from two per-lane roots (thfhe_lane.h, variant "q") instead of read from a T1 table in LDS: the
-//     table reads sat between the butterflies and the transpose of every transform;
-//   * the second transpose uses the padded 576-slot buffer (the 8 KiB of the T1 table pay for the padding): its slot maps are
-//     base + immediate, 2 LDS address registers per wave instead of 16 for the XOR-swizzled maps;
-//   * the multiply-accumulate is software-pipelined over half chunks: the four ring reads of one half are in flight under the
-//     16 FMAs of the half before (the first generation read one slice, used it, read the next: 8 serial round trips per chunk),
-//     and S += z * b is four FMAs (the mul + fma + add form cost 384 more FP64 instructions per CMux);
-// LDS pipe instructions per launch 1.74e9 -> 1.38e9, LDS pipe busy 69 % -> 46 %, VALU busy 55 % -> 75 %, 34.8 -> 33.3 ms per 4096 gates.
-// Third pass (33.3 -> 29.9 ms):
-//   * rotate + decompose in one step on byte offsets (thfhe_lane.h: rotated_word / mixed_digits_z), the index / sign / subtraction
-//     work once per accumulator polynomial (fields kept across its l levels), a level = one v_bfe_i32 + one conversion per coefficient;
-//   * register-lean pass-1 twiddles (LaneTw): the compiler hoists loop-invariant twiddle products out of the CMux loop and then spills
-//     some of them; every reload was followed by s_waitcnt vmcnt(0), which also waits for the ring DMAs issued just before the
-//     transform.  Keeping only the even products and forming the odd ones in place (16 more FP64 instructions per transform) removes
-//     those reloads from the transforms.
-// Fourth pass (29.7 -> 28.7 ms): the kernel's time is its FP64 instruction stream (an FP64 wave instruction holds the SIMD's vector pipe for 4 cycles),
-// and a third of that stream was twiddle work.  Transforms of variant "f" (thfhe_lane.h): every inter-pass twiddle sits on the input side of the pass
-// that follows it and is folded into that pass's radix-2 butterflies (a + W b as two dependent FMAs per component, a - W b = 2 a - x as one), a
-// twiddled DFT8 = 72 FP64 instructions against 52 + 28, from four constants per root instead of seven.  Forward: the twist C[m] rides in pass 1
-// (wave-uniform constants), pass 2 and pass 3 take one per-lane root each (TwRing1k::ROOTSF); inverse: the two conjugate roots of "q", the untwist
-// stays a product.  Per CMux and wave 3 582 -> 3 356 FP64 instructions (forward transform 275 -> 240), still 256 VGPRs and no scratch: the roots are
-// made opaque IN PLACE per transform (no register copies), only the four untwist constants are shared by a CMux's inverse transforms.  Sharing one
-// or both roots' powers as well (3 320 / 3 284 instructions) spilled 6 / 15 registers around the inverse phase and measured 0.45 ms SLOWER than this
-// form (profiles/r06_fold_static_counts.md).
-// Fifth pass (28.26 -> 27.70 ms; profiles/r10_valu_diet.md): the other third of the vector stream, 1 545 -> 1 311 instructions per CMux and wave, the FP64
-// and LDS work untouched.  The key-stream cursor is scalar (below; ring_dma in thfhe_common.h); the kept side of the transposes' half-row swap is one
-// 64-bit move per double (wave_transpose_hi3<KEEP64>); the multiply negates the key operand, not z.im (cfma_negkey in thfhe_lane.h), which is what
-// paid most: the compiler had carried a negated copy of every z.im through the row.
+// What the kernel does about its bounds.  An in-kernel cycle trace and the PMC counters of the first generation (tools/ring_stamps.py,
+// profiles/r02_ring_generations.md) showed it, at two waves per SIMD, bound by exposed LDS round trips and by the LDS instruction pipe (69 % busy,
+// bursts in lock step) with the VALU 55 % busy; since then the time is the FP64 instruction stream (an FP64 wave instruction holds the SIMD's
+// vector pipe for 4 cycles).  Per 4096 gates 34.8 -> 33.3 -> 29.9 -> 28.7 -> 27.70 ms; the forms that were tried and lost are in
+// profiles/r03_ring_variants.md and r04_ring_multiply_phase.md.
+//   * the FIRST transpose of every transform (register index <-> lane bits 3..5) stays in registers: v_permlane32_swap, v_permlane16_swap and
+//     row_ror:8 DPP moves (wave_transpose_hi3) instead of 8 ds_write_b128 + 8 ds_read_b128; the kept side of its half-row swap is one 64-bit move
+//     per double (wave_transpose_hi3<KEEP64>);
+//   * the second transpose uses the padded 576-slot buffer (there is no T1 table in the LDS, its 8 KiB pay for the padding): its slot maps are
+//     base + immediate, 2 LDS address registers per wave instead of 16 for XOR-swizzled maps;
+//   * no twiddle is read from a table: the transforms are variant "f" (thfhe_lane.h).  Every inter-pass twiddle sits on the input side of the pass
+//     that follows it and is folded into that pass's radix-2 butterflies (a + W b as two dependent FMAs per component, a - W b = 2 a - x as one), a
+//     twiddled DFT8 = 72 FP64 instructions from four constants per root.  Forward: the twist C[m] rides in pass 1 (wave-uniform constants), pass 2
+//     and pass 3 take one per-lane root each (TwRing1k::ROOTSF); inverse: the two conjugate per-lane roots of TwRing1k::ROOTS, the untwist stays a
+//     product.  Per CMux and wave 3 356 FP64 instructions (forward transform 240), no scratch within the 256 VGPRs of two waves per SIMD: the roots are made opaque IN PLACE per
+//     transform (no register copies), so their powers are rebuilt and not kept across the CMux loop; only the four untwist constants are shared by a
+//     CMux's inverse transforms.  Sharing one or both roots' powers as well (3 320 / 3 284 instructions) spilled 6 / 15 registers around the inverse
+//     phase and measured 0.45 ms SLOWER than this form (profiles/r06_fold_static_counts.md);
+//   * rotate + decompose in one step on byte offsets (thfhe_lane.h: rotated_word / mixed_digits_z), the index / sign / subtraction work once per
+//     accumulator polynomial (fields kept across its l levels), a level = one v_bfe_i32 + one conversion per coefficient;
+//   * the multiply-accumulate is software-pipelined over half chunks: the four ring reads of one half are in flight under the 16 FMAs of the half
+//     before, S += z * b is four FMAs, and the multiply negates the key operand, not z.im (cfma_negkey in thfhe_lane.h): the compiler had carried a
+//     negated copy of every z.im through the row;
+//   * the key-stream cursor is scalar (below; ring_dma in thfhe_common.h).
+// The scalar cursor, KEEP64 and cfma_negkey took the other (non-FP64) third of the vector stream from 1 545 to 1 311 instructions per CMux and wave
+// (28.26 -> 27.70 ms; profiles/r10_valu_diet.md).
 // ------------------------------------------------------------------------------------------------------
-#ifndef THFHE_RING_NF
-#define THFHE_RING_NF 16
-#endif
-#ifndef THFHE_RING_LEAN_ROOTS
-#define THFHE_RING_LEAN_ROOTS 1   // eight-wave shape: pass-1 twiddles rebuilt per transform (no scratch); 0 = even products kept across the loop
-#endif
 // W = waves (= jobs) per workgroup.  W = 8 is the throughput shape described above.  W = 4 (one wave per SIMD, 92 KiB of LDS, each wave
 // brings TWO slices of a chunk) is the shape for batches that cannot give every CU eight jobs (<= 1024 rotations): a wave alone on its
 // SIMD issues at ~87 % of what a pair reaches together (tools/probes/issue_probe.hip), so four jobs finish much sooner than eight.
 // LUT = kLut, kLutEnc: programmable bootstrap, the accumulator starts from a test vector (kLutEnc: from a TLWE sample, mask included) and theta
 // coefficients are extracted; kLutMv: multi-value bootstrap, the kLut start on one base vector and a.theta = q outputs, each a
 // p-tap combination of extractions (extract_mv16); the CMux loop is the same code.
-// V = transform form (bits): 1 = first transpose in registers ("q"; 0 = through the LDS, "r"), 2 = inverse through the LDS all the same,
-// 4 = twiddles folded into the butterflies ("f", with the exchanges of "q": the product form); 0, 1 and 3 remain for A/B runs.
-template <int L, int V = 5, int W = 8, int LUT = kGate>
+template <int L, int W = 8, int LUT = kGate>
 __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_kernel(BRArgs a) {
     __shared__ __attribute__((aligned(4096))) int32_t sAcc[W][2048];   // rotated_digits_z ORs byte offsets into the polynomial base
     __shared__ cplx sX[W][kXbufSlots];
@@ -201,13 +186,10 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
     namespace RS = ring_schedule;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    const W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};
-    const LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
-    const LaneTw tw = make_lane_tw(roots);
-    // the roots of the "f" path are variables: opaque_in_place makes them loop-carried in the registers they already occupy
-    LaneRootsF rootsf{a.tw[TwRing1k::ROOTSF + 2 * lane], a.tw[TwRing1k::ROOTSF + 2 * lane + 1]};
-    W64 w64f = w64;
-    LaneRoots rootsi = roots;
+    // the roots are variables: opaque_in_place makes them loop-carried in the registers they already occupy
+    W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};                                               // inverse transforms
+    LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
+    LaneRootsF rootsf{a.tw[TwRing1k::ROOTSF + 2 * lane], a.tw[TwRing1k::ROOTSF + 2 * lane + 1]};   // forward transforms
     const long job = (long)blockIdx.x * W + wave;
     const bool has_job = job < a.jobs;
     int32_t *acc = sAcc[wave];
@@ -258,7 +240,7 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
             for (int h = 0; h < 2; h++)
 #pragma unroll
                 for (int m = 0; m < 8; m++) S[c][h][m] = cplx{0.0, 0.0};
-        constexpr int NF = THFHE_RING_NF;   // rotated fields kept across the levels of a polynomial (register budget)
+        constexpr int NF = 16;   // rotated fields kept across the levels of a polynomial (register budget)
         uint32_t fld[NF];
 #pragma unroll
         for (int r = 0; r < ROWS; r++) {
@@ -270,17 +252,13 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
                 if (r % L == 0) rotated_fields_keep<NF, W == 4>(lane, acc + (r / L) * 1024, a2n_r, L, Bgbit, fld);
                 asm volatile("" : "+s"(a2n_r));
                 mixed_digits_z<NF>(lane, acc + (r / L) * 1024, a2n_r, (r % L) + 1, L, Bgbit, fld, z);
-                // pass-1 twiddles: the eight-wave shape rebuilds all eight products b s^k per transform from the two per-lane roots (made opaque so that
-                // they are not hoisted out of the CMux loop): 12 fewer registers live across the loop than with the even products kept (LaneTw), the
-                // compiler then parks nothing in scratch (44 -> 0 B per lane: no reload in front of a row's digits waits for the ring DMAs any more) --
-                // 30.21 -> 29.97 ms per 4096 gates.  The four-wave shape (registers to spare) keeps LaneTw: 9.67 against 9.80 ms per 1024 gates.
-                // "f": the two forward roots likewise opaque per transform: their powers (12 FP64 instructions each) are rebuilt, not kept across the loop
-                if (V & 4) {
-                    if (THFHE_RING_LEAN_ROOTS && W == 8) opaque_in_place(rootsf.s), opaque_in_place(rootsf.w);
-                    wave_fft_fwd_f(lane, z, xb, rootsf);
-                } else if (!(V & 1)) wave_fft_fwd_r(lane, z, xb, roots, w64);
-                else if (THFHE_RING_LEAN_ROOTS && W == 8) wave_fft_fwd_q(lane, z, xb, LaneRoots{opaque_cplx(roots.b), opaque_cplx(roots.s)}, w64);
-                else wave_fft_fwd_q(lane, z, xb, tw, w64);
+                // eight-wave shape: the two forward roots are made opaque per transform, so their powers (12 FP64 instructions each) are rebuilt and
+                // not hoisted out of the CMux loop.  With nothing derived from the roots live across the loop the compiler parks nothing in scratch: no
+                // reload in front of a row's digits waits for the ring DMAs (s_waitcnt vmcnt(0) follows every reload).  Rebuilding instead of keeping
+                // measured 30.21 -> 29.97 ms per 4096 gates, 44 -> 0 B of scratch per lane, when it was introduced (on the transforms before these;
+                // DESIGN 4.1, profiles/r04_summary.md).  The four-wave shape has registers to spare and lets the compiler keep what it likes.
+                if (W == 8) opaque_in_place(rootsf.s), opaque_in_place(rootsf.w);
+                wave_fft_fwd_f(lane, z, xb, rootsf);
             }
             STAMP(0);
             cplx bA[4], bB[4];
@@ -329,30 +307,15 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
         }
         if (active) {
             wave_sync();
-            // "f": the untwist constants b C[m] are built once per CMux for the four inverse transforms, from a root made opaque here so that they
-            // are not kept across the multiply phase
+            // the untwist constants b C[m] are built once per CMux for the four inverse transforms, from a root made opaque here so that they are not
+            // kept across the multiply phase
             cplx bc[4];
-            if (V & 4) {
-                if (THFHE_RING_LEAN_ROOTS && W == 8) opaque_in_place(rootsi.b);
-                make_untwist_f(rootsi.b, bc);
-            }
+            if (W == 8) opaque_in_place(roots.b);
+            make_untwist_f(roots.b, bc);
 #pragma unroll
             for (int c = 0; c < 2; c++) {
-                if (V & 4) {
-                    wave_fft_inv_f<THFHE_RING_LEAN_ROOTS && W == 8>(lane, S[c][0], xb, w64f, rootsi, bc);
-                    wave_fft_inv_f<THFHE_RING_LEAN_ROOTS && W == 8>(lane, S[c][1], xb, w64f, rootsi, bc);
-                } else if ((V & 1) && !(V & 2)) {
-                    if (THFHE_RING_LEAN_ROOTS && W == 8) {
-                        wave_fft_inv_q(lane, S[c][0], xb, LaneRoots{opaque_cplx(roots.b), opaque_cplx(roots.s)}, w64);
-                        wave_fft_inv_q(lane, S[c][1], xb, LaneRoots{opaque_cplx(roots.b), opaque_cplx(roots.s)}, w64);
-                    } else {
-                        wave_fft_inv_q(lane, S[c][0], xb, tw, w64);
-                        wave_fft_inv_q(lane, S[c][1], xb, tw, w64);
-                    }
-                } else {
-                    wave_fft_inv_r(lane, S[c][0], xb, roots, w64);
-                    wave_fft_inv_r(lane, S[c][1], xb, roots, w64);
-                }
+                wave_fft_inv_f<W == 8>(lane, S[c][0], xb, w64, roots, bc);
+                wave_fft_inv_f<W == 8>(lane, S[c][1], xb, w64, roots, bc);
                 acc_update16(lane, acc + c * 1024, S[c][0], S[c][1]);
             }
             wave_sync();
@@ -391,12 +354,12 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
 // spread out, 2.4x what that kernel reached.  Here the chunks of step i+1 are requested during step i, once the registers that
 // held step i's chunks are dead: the idle waves of half 1 right after the hand-off, the transforming waves one row's worth at a
 // time between the stages of their inverse transform (compiler fences pin the places) -- nobody's transform waits on the queue.
-// Transforms are variant "r" (padded buffer, pass-1 twiddles from per-lane roots): LDS = acc 8 + spectra 2l x 8 + 8 x 9 KiB.
+// Transforms are variant "q" (first transpose in registers, padded buffer, pass-1 twiddles from per-lane roots): LDS = acc 8 + spectra 2l x 8 + 8 x 9 KiB.
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ void pin() { asm volatile("" ::: "memory"); }  // memory operations do not move across this point
 
-template <int L, int PACE = 1, int LUT = kGate>
+template <int L, int LUT = kGate>
 __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) {
     constexpr int ROWS = 2 * L;
     __shared__ __attribute__((aligned(4096))) int32_t sAcc[2048];
@@ -475,7 +438,7 @@ __global__ __launch_bounds__(512, 2) void sk_blind_rotate_coop_kernel(BRArgs a) 
                 for (int m = 0; m < 8; m++) {
                     B[r][m] = src[m * 64 + lane];
                     pin();
-                    __builtin_amdgcn_s_sleep(PACE);   // paced: these waves have the whole inverse phase; a flooded queue stalls the partners' loads
+                    __builtin_amdgcn_s_sleep(1);   // paced: these waves have the whole inverse phase; a flooded queue stalls the partners' loads
                 }
             }
         } else {
@@ -610,31 +573,18 @@ int ensure_workspace(thfhe_ctx *c, size_t jobs, int theta = 0) {
     return rc;
 }
 
-// One launch of `a.jobs` rotations on one kernel shape.  LUT: kGate, or a programmable-bootstrap instantiation (the developer variants are gate-only).
+// One launch of `a.jobs` rotations on one kernel shape.  LUT: kGate, or a programmable-bootstrap instantiation.
 template <int L, int LUT>
 void launch_coop(const BRArgs &a, hipStream_t s) {
-#ifdef THFHE_VARIANTS
-    static const int pace = std::getenv("THFHE_COOP_PACE") ? std::atoi(std::getenv("THFHE_COOP_PACE")) : 1;
-    if (!LUT && pace == 0) { hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 0>), dim3((unsigned)a.jobs), dim3(512), 0, s, a); return; }
-    if (!LUT && pace == 2) { hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 2>), dim3((unsigned)a.jobs), dim3(512), 0, s, a); return; }
-    if (!LUT && pace == 4) { hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 4>), dim3((unsigned)a.jobs), dim3(512), 0, s, a); return; }
-#endif
-    hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, 1, LUT>), dim3((unsigned)a.jobs), dim3(512), 0, s, a);
+    hipLaunchKernelGGL((sk_blind_rotate_coop_kernel<L, LUT>), dim3((unsigned)a.jobs), dim3(512), 0, s, a);
 }
 template <int L, int LUT>
 void launch_ring4(const BRArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 5, 4, LUT>), dim3((unsigned)((a.jobs + 3) / 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 4, LUT>), dim3((unsigned)((a.jobs + 3) / 4)), dim3(256), 0, s, a);
 }
 template <int L, int LUT>
 void launch_ring8(const BRArgs &a, hipStream_t s) {
-    const dim3 grid((unsigned)((a.jobs + 7) / 8)), block(512);
-#ifdef THFHE_VARIANTS  // developer A/B builds only: 8 = first transpose through the LDS (variant "r"), 1 = "q" (separate twiddle products, the form before "f")
-    static const int variant = std::getenv("THFHE_RING_VARIANT") ? std::atoi(std::getenv("THFHE_RING_VARIANT")) : 0;
-    if (!LUT && variant == 8) { hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 0>), grid, block, 0, s, a); return; }
-    if (!LUT && variant == 1) { hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 1>), grid, block, 0, s, a); return; }
-    if (!LUT && variant == 3) { hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 3>), grid, block, 0, s, a); return; }   // forward in registers, inverse through the LDS
-#endif
-    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 5, 8, LUT>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((sk_blind_rotate_ring_kernel<L, 8, LUT>), dim3((unsigned)((a.jobs + 7) / 8)), dim3(512), 0, s, a);
 }
 
 // The rotations of a batch, piece by piece of launch_plan::sk_rotation_plan (thfhe_launch_plan.h: whole rounds on the eight-wave ring kernel,
