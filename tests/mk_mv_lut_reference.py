@@ -6,17 +6,11 @@ import numpy as np
 
 import mk_lut_reference as R
 import oracle_lib as O
+from conv_edges import t64tot32   # the vectorised conversion lives with its edge words; MV.t64tot32 stays this module's name for it
 
 
 def _u64(v):
     return np.ascontiguousarray(v, np.int64).view(np.uint64)
-
-
-def t64tot32(d):
-    """oracle_t64tot32 on an array: trunc(Float64(d) / 2^32) toward zero, the one double that reaches 2^31 wrapped to INT32_MIN
-    (test_mk_mv_lut_host.py holds it against the oracle's word by word)."""
-    v = np.trunc(np.asarray(d, np.int64).astype(np.float64) / 4294967296.0)
-    return np.where(v >= 2147483648.0, -2147483648.0, v).astype(np.int64).astype(np.int32)
 
 
 def extract_raw(acc, J, N):
@@ -35,16 +29,17 @@ def tap_positions(p, N):
     return [N - box // 2 - k * box for k in range(p)]
 
 
-def combine64(acc, taps, p, N, out_bias=0):
+def combine64(acc, taps, p, N, out_bias=0, convert=t64tot32):
     """Every output of one accumulator int64[2N]: record j = t64tot32, word by word, of - sum_k taps[j][k] * E(acc, J_k) (+ out_bias on the body
-    word), all mod 2^64, taps sign-extended -> int32[q][N+1]."""
+    word), all mod 2^64, taps sign-extended -> int32[q][N+1].  convert: what is applied to the int64 sums instead of t64tot32 (the edge tests pass
+    the identity and a wrong conversion)."""
     taps = np.asarray(taps, np.int64).reshape(-1, p)
     E = np.stack([extract_raw(acc, J, N) for J in tap_positions(p, N)])
     s = np.zeros((taps.shape[0], N + 1), np.uint64)
     for k in range(p):   # uint64 products and sums wrap mod 2^64
         s -= _u64(taps[:, k])[:, None] * E[k][None, :]
     s[:, N] += _u64(R.to_i64([out_bias]))[0]
-    return t64tot32(s.view(np.int64))
+    return convert(s.view(np.int64))
 
 
 def convert_then_combine(acc, taps, p, N, out_bias=0):
