@@ -66,7 +66,9 @@ enum thfhe_gate {
     THFHE_TREE_MV = 20, /* gate-DAG node: two-digit tree with a multi-value level 1 and k outputs (thfhe_dag_run_mv_batch, thfhe_dag_run_lhe_batch) */
     THFHE_LHE_LOOKUP = 21,  /* gate-DAG node: leveled lookup of a table of the run at a TGSW-encrypted address (thfhe_dag_run_lhe_batch only) */
     THFHE_LHE_GATHER = 22,  /* gate-DAG node: leveled pick among 2^d computed wires at a TGSW-encrypted index (thfhe_dag_run_lhe_batch only) */
-    THFHE_LHE_WFA = 23      /* gate-DAG node: layered automaton on TGSW-encrypted bits (thfhe_dag_run_lhe_batch only) */
+    THFHE_LHE_WFA = 23,     /* gate-DAG node: layered automaton on TGSW-encrypted bits (thfhe_dag_run_lhe_batch only) */
+    THFHE_CB = 24           /* gate-DAG node: wires -> a computed TGSW set by circuit bootstrapping (thfhe_dag_run_cb_batch only); in
+                               THFHE_CB_ONE_ROTATION mode the operand wires must be gate-encoded (+-1/8): the caller's responsibility */
 };
 
 enum thfhe_error {
@@ -818,6 +820,56 @@ int thfhe_dag_run_lhe_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const int3
                             const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, const thfhe_dag_lhe_families *lhe,
                             size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats);
 int thfhe_dag_last_group_ms(thfhe_ctx *ctx, float *ms);
+
+/* ---- circuit-bootstrap nodes in the gate-DAG executor (single key): thfhe_dag_run_lhe_batch with one more node kind, which turns
+ * d wires of the run into the d TGSW bits of a COMPUTED set that later leveled rows read, so that an index computed by gates is converted, used by a
+ * LOOKUP / GATHER / WFA node and its result fed back into gates in ONE run on the device-resident wire table.  Every argument before `cb` means what
+ * it means in thfhe_dag_run_lhe_batch; with cb = NULL the call is that call (level2 may then be NULL; stats[4] = 0).
+ *   Row: (THFHE_CB, -1, -1, -1, cbset, -1), exactly one per computed set.  Its operands are the d wires cb_wires[wire_off .. wire_off + d - 1] of
+ *       sets[cbset]: earlier wires (inputs too), not necessarily consecutive; they count for the depth as a GATHER's candidates do, the node costs one
+ *       level, and its own wire is a word-for-word copy of the wire of bit 0.
+ *   Reading: in lks[].set and in a WFA spec's set0 .. set0 + n_sets - 1 an index >= lhe->n_sets names computed set index - lhe->n_sets (lhe->sets may
+ *       be NULL with count 0 when every set is computed; a WFA spec may mix the two kinds).  A leveled row that reads a computed set comes after the
+ *       set's THFHE_CB row and sits at least one level above it.
+ *   Contract: computed set c of a run equals, word for word, what thfhe_circuit_bootstrap_mode(ctx, level2, the operand wires' records as
+ *       int32[instances][d][n+1], instances, d, mode, words[c], &set) makes, its rows (cb->words) included; every leveled wire that reads it equals the
+ *       flat thfhe_lhe_lookup / thfhe_pack_boxes + thfhe_lhe_lookup / thfhe_lhe_wfa on that set.  THFHE_CB_ONE_ROTATION keeps its caveat: it assumes
+ *       gate-encoded (+-1/8) operands.  The security caveat of the private key-switching key's noise is unchanged.
+ *   Scheduling: all CB nodes of a level form ONE launch group, run before the level's leveled groups as one batch in slices of
+ *       S = min(instances, thfhe_set_dag_slice, 2048 / sum of d) instances: a gather of the operand wires, stage A on S sum-d bits, stage B, one key
+ *       transform per node into its set's spectra.  The run lends the gate context's stream to level2 and hands it back whatever happens.
+ *   Ownership: the computed sets belong to ctx, grow only, are reused by the next run, and are freed by thfhe_dag_cb_release and with the context.
+ *       Before any device work the spectra (instances d 2l 32 KiB per set) not yet held and the slice workspace are checked against the free device
+ *       memory: THFHE_E_NOMEM with nothing run.
+ *   stats[0..3]: as thfhe_dag_run_lhe_batch; a CB node adds a level, one launch group per level that has CB nodes and no level-1 rotation.
+ *       stats[4]: level-2 rotations per instance, sum of d in one-rotation mode (a plan figure), sum of d x l per level (written once ctx is known;
+ *       0 when the call is refused before).  thfhe_dag_last_group_ms also answers for a CB group.
+ *   Checks, on the host before either context or any set is looked at (THFHE_E_INVALID): those of thfhe_dag_run_lhe_batch; an unknown mode; n_sets
+ *       outside 1 .. 64 or client + computed sets above 64; d outside 1 .. 16; wire_off + d past the pool; a pool wire that is not earlier than the
+ *       CB row; cbset out of range; a set with no CB row or with two; a leveled row that reads a computed set before its CB row; operand fields or
+ *       field 5 not -1; d_tree + d_rot != the computed set's d.  Then the null level2, then the checks of thfhe_circuit_bootstrap on the two contexts.
+ *   Every other thfhe_dag_* and thfhe_mk_dag_* entry rejects THFHE_CB. */
+typedef struct thfhe_dag_cb_spec {
+    int32_t d;          /* 1 .. 16 */
+    int32_t wire_off;   /* bit i of sample q = wire cb_wires[wire_off + i] of instance q */
+} thfhe_dag_cb_spec;
+
+typedef struct thfhe_dag_cb_families {
+    const thfhe_dag_cb_spec *sets;   /* computed sets, 1 .. 64; client sets + computed sets <= 64 */
+    int32_t n_sets;
+    const int32_t *cb_wires;         /* HOST pool of wire ids */
+    size_t n_cb_wires;
+    int32_t mode;                    /* THFHE_CB_PER_LEVEL | THFHE_CB_ONE_ROTATION */
+    int32_t *const *words;           /* NULL, or per computed set NULL or HOST int32[instances][d][2l][2][N]: the rows of stage B */
+} thfhe_dag_cb_families;
+
+int thfhe_dag_run_cb_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, thfhe_mk_ctx *level2, const int32_t *inputs, size_t n_inputs, const int32_t *nodes,
+                           size_t n_nodes, const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a,
+                           const int32_t *enc_b, int n_enc, const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows,
+                           const thfhe_mv_spec *mvs, int n_mvs, const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words,
+                           const thfhe_dag_lhe_families *lhe, const thfhe_dag_cb_families *cb, size_t instances, const int32_t *out_wires, size_t n_out,
+                           int32_t *outputs, int64_t *stats /*[5]*/);
+int thfhe_dag_cb_release(thfhe_ctx *ctx);
 
 /* ---- multi-key KEY GENERATION arithmetic on the device --------------------------------------------------------------
  * Exact multiply-accumulate of small-coefficient polynomials with torus polynomials, the only non-trivial arithmetic of

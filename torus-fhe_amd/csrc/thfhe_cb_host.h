@@ -131,13 +131,11 @@ int cb_stage_a_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, int mode, const int3
     return THFHE_OK;
 }
 
-// thfhe_circuit_bootstrap_mode after its host checks, the level-2 context enqueueing on c's stream: per slice of bits stage A (cb_stage_a_enqueue),
-// stage B (the private key switch) and stage C (the key transform into the set's spectra).  Nothing leaves the device between the stages;
-// `words`, if wanted, gets the rows of stage B.
-int cb_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, thfhe_tgsw_set *set, const int32_t *lwe, int32_t *words, int mode) {
+// Before any device work of a call: the spectra it has to allocate (spec_bytes) and the workspace of slices of R_max bits against the free device
+// memory, THFHE_E_NOMEM with nothing run; then the buffers of the three stages.
+int cb_reserve(thfhe_ctx *c, int mode, size_t R_max, int N2, size_t spec_bytes) {
     const int l = c->p.l, n = c->p.n, D = c->cb.D;
-    const size_t polys_per_bit = (size_t)2 * l * 2, bits = set->count * set->d, R_max = std::min(bits, kCbSliceBits);
-    const size_t spec_bytes = bits * polys_per_bit * 1024 * sizeof(cplx);
+    const size_t polys_per_bit = (size_t)2 * l * 2;
     // one-rotation mode has no one-level hop: b_x drops out (its mod-switched words, b_bara and b_barb, are in the level-2 context's workspace)
     const size_t b_lwe = R_max * (n + 1) * 4, b_bara = R_max * n * 4, b_barb = R_max * 4, b_acc = R_max * 2 * N2 * sizeof(int64_t),
                  b_x = mode == THFHE_CB_PER_LEVEL ? R_max * (D + 1) * 4 : 0, b_lwe2 = R_max * (D + 1) * 4 * l, b_rows = R_max * polys_per_bit * 4096,
@@ -147,7 +145,49 @@ int cb_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, thfhe_tgsw_set *set, const i
     if (spec_bytes + b_lwe + b_bara + b_barb + b_acc + b_x + b_lwe2 + b_rows + b_dig > free_b)
         return thfhe_fail(THFHE_E_NOMEM, "circuit bootstrap: count d 2l 32 KiB of spectra and the slice workspace exceed the free device memory");
     THFHE_TRY(cb_stage_a_prepare(c, mode, R_max, N2));
-    THFHE_TRY(c->d_cb_rows.grow(b_rows));
+    return c->d_cb_rows.grow(b_rows);
+}
+
+// One part of a slice's TGSW rows on its way out: the rows of bits [bit0, bit0 + bits) of the slice go to `words` on the host, if wanted, and as
+// spectra to `spec`.
+struct CbSliceOut {
+    size_t bit0, bits;
+    cplx *spec;
+    int32_t *words;
+};
+// The device part of one slice of R bits whose gate records are in d_cb_lwe: stage A (cb_stage_a_enqueue), stage B (the private key switch) and
+// stage C (the key transform of every part of `outs` into its spectra), all on c's stream.  prof: the stages' events around them.  cb_fill has one
+// part per slice; a CB group of the gate DAG (thfhe_dag_cb.h) one per node.
+int cb_slice_enqueue(thfhe_ctx *c, thfhe_mk_ctx *l2, int mode, size_t R, const CbSliceOut *outs, size_t n_outs, bool prof) {
+    const int l = c->p.l;
+    const size_t polys_per_bit = (size_t)2 * l * 2;
+    hipStream_t st = c->stream;
+    if (prof) THFHE_HIP(hipEventRecord(c->ev[0], st));
+    THFHE_TRY(cb_stage_a_enqueue(c, l2, mode, R));
+    if (prof) THFHE_HIP(hipEventRecord(c->ev[1], st));
+    THFHE_TRY(cb_enqueue(c->cb, c->d_cb_lwe2.as<int32_t>(), (long)(R * l), l, c->d_cb_rows.as<int32_t>(), st));
+    if (prof) THFHE_HIP(hipEventRecord(c->ev[2], st));
+    for (size_t k = 0; k < n_outs; k++) {
+        const CbSliceOut &o = outs[k];
+        const int32_t *const rows = c->d_cb_rows.as<int32_t>() + o.bit0 * polys_per_bit * 1024;
+        if (o.words) THFHE_HIP(hipMemcpyAsync(o.words, rows, o.bits * polys_per_bit * 4096, hipMemcpyDeviceToHost, st));
+        THFHE_TRY((launch_torus_transform<1024, 32>(st, rows, (long)(o.bits * polys_per_bit), c->d_tw.as<cplx>(), o.spec)));
+    }
+    if (prof) {
+        THFHE_HIP(hipEventRecord(c->ev[3], st));
+        c->ev_valid = true;
+    }
+    return THFHE_OK;
+}
+
+// thfhe_circuit_bootstrap_mode after its host checks, the level-2 context enqueueing on c's stream: per slice of bits stage A (cb_stage_a_enqueue),
+// stage B (the private key switch) and stage C (the key transform into the set's spectra).  Nothing leaves the device between the stages;
+// `words`, if wanted, gets the rows of stage B.
+int cb_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, thfhe_tgsw_set *set, const int32_t *lwe, int32_t *words, int mode) {
+    const int l = c->p.l, n = c->p.n;
+    const size_t polys_per_bit = (size_t)2 * l * 2, bits = set->count * set->d, R_max = std::min(bits, kCbSliceBits);
+    const size_t spec_bytes = bits * polys_per_bit * 1024 * sizeof(cplx);
+    THFHE_TRY(cb_reserve(c, mode, R_max, N2, spec_bytes));
     THFHE_TRY(set->spec.grow(spec_bytes));
     hipStream_t st = c->stream;
     const bool prof = c->profiling;
@@ -155,35 +195,34 @@ int cb_fill(thfhe_ctx *c, thfhe_mk_ctx *l2, int N2, thfhe_tgsw_set *set, const i
         const size_t R = std::min(R_max, bits - b0);
         const bool last = b0 + R == bits;
         THFHE_HIP(hipMemcpyAsync(c->d_cb_lwe.as<int32_t>(), lwe + b0 * (n + 1), R * (n + 1) * 4, hipMemcpyHostToDevice, st));
-        if (prof && last) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        THFHE_TRY(cb_stage_a_enqueue(c, l2, mode, R));
-        if (prof && last) THFHE_HIP(hipEventRecord(c->ev[1], st));
-        THFHE_TRY(cb_enqueue(c->cb, c->d_cb_lwe2.as<int32_t>(), (long)(R * l), l, c->d_cb_rows.as<int32_t>(), st));
-        if (prof && last) THFHE_HIP(hipEventRecord(c->ev[2], st));
-        if (words) THFHE_HIP(hipMemcpyAsync(words + b0 * polys_per_bit * 1024, c->d_cb_rows.as<int32_t>(), R * polys_per_bit * 4096, hipMemcpyDeviceToHost, st));
-        THFHE_TRY((launch_torus_transform<1024, 32>(st, c->d_cb_rows.as<int32_t>(), (long)(R * polys_per_bit), c->d_tw.as<cplx>(),
-                                                    set->spec.as<cplx>() + b0 * polys_per_bit * 1024)));
-        if (prof && last) {
-            THFHE_HIP(hipEventRecord(c->ev[3], st));
-            c->ev_valid = true;
-        }
+        const CbSliceOut out{0, R, set->spec.as<cplx>() + b0 * polys_per_bit * 1024, words ? words + b0 * polys_per_bit * 1024 : nullptr};
+        THFHE_TRY(cb_slice_enqueue(c, l2, mode, R, &out, 1, prof && last));
     }
     THFHE_HIP(hipStreamSynchronize(st));
     return THFHE_OK;
 }
 
-// `run` under c's lock with c's stream lent to the level-2 context (one stream for all stages), handed back whatever `run` returns
-template <typename Run>
-int cb_with_level2(thfhe_ctx *c, thfhe_mk_ctx *l2, int mode, Run &&run) {
+// Under c's lock: the checks of the two contexts, then c's stream lent to the level-2 context (one stream for all stages); *N2: its ring degree.
+// cb_level2_end hands the stream back, and is due whatever ran in between.
+int cb_level2_begin(thfhe_ctx *c, thfhe_mk_ctx *l2, int mode, int *N2) {
     thfhe_params p2;
     int dev2 = -1;
     THFHE_TRY(thfhe_mk_ctx_info(l2, &p2, &dev2));
+    THFHE_TRY(cb_check_pair(c, p2, dev2, mode));
+    *N2 = p2.N;
+    return thfhe_mk_set_stream(l2, c->stream);
+}
+int cb_level2_end(thfhe_mk_ctx *l2) { return thfhe_mk_set_stream(l2, nullptr); }   // drains the stream first
+
+// `run` under c's lock between the two, the stream handed back whatever `run` returns
+template <typename Run>
+int cb_with_level2(thfhe_ctx *c, thfhe_mk_ctx *l2, int mode, Run &&run) {
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
-    THFHE_TRY(cb_check_pair(c, p2, dev2, mode));
-    THFHE_TRY(thfhe_mk_set_stream(l2, c->stream));
-    int rc = run(p2.N);
-    const int rc2 = thfhe_mk_set_stream(l2, nullptr);   // drains the stream first
+    int N2 = 0;
+    THFHE_TRY(cb_level2_begin(c, l2, mode, &N2));
+    int rc = run(N2);
+    const int rc2 = cb_level2_end(l2);
     return rc ? rc : rc2;
 }
 

@@ -11,6 +11,8 @@
 //                entry has the tree generation too (single key)
 //   kDagGenLhe   leveled nodes (thfhe_dag_run_lhe_batch; single key): LHE_LOOKUP, LHE_GATHER and LHE_WFA rows on the client's TGSW sets;
 //                dag_lhe_gather_kernel stages a GATHER node's candidates for the box packing
+//   kDagGenCb    circuit-bootstrap nodes (thfhe_dag_run_cb_batch; single key): CB rows, whose operands are a LIST of wires (a slice of the
+//                run's wire pool) and whose result is a computed TGSW set that later leveled rows read (the group and its gather kernel: thfhe_dag_cb.h)
 // The kinds from kDagGenTree on are planned here and run by the engine (thfhe_sk.hip: sk_dag_run_luts), a grouped kind in slices through dag_group_slices.
 // dag_gates_run_batch / dag_gates_run are the four-column entries of both engines.
 #ifndef THFHE_DAG_H
@@ -119,7 +121,9 @@ enum DagClass : int32_t {
     kDagLheLookup = 15,  // [lk | row0], per lks[] entry
     kDagLheGather = 16,  // [lk | first]
     kDagLheWfa = 17,     // [wfa | fin_row0], per wfas[] entry
+    kDagCb = 18,         // [cbset | -], ONE group per level (entry -1), before the level's leveled groups; then int32[count][4] = (base, off, d, out wire)
 };
+inline bool dag_class_leveled(int cls) { return cls >= kDagLheLookup && cls <= kDagLheWfa; }
 // theta of a LUT / LUT_ENC class, 0 for every other class
 inline int dag_class_theta(int cls) {
     switch (cls) {
@@ -136,6 +140,7 @@ struct DagBatch {
     int32_t depth, sub, cls;  // cls: a DagClass
     size_t off, count;        // index table slice: [ops | in0 | in1 | in2 | out], classes from kDagLut1 on + [spec | lut], `count` entries each, at tab[off]
     int32_t tree = -1;        // the grouped kinds: the trees[] / mvs[] / lks[] / wfas[] entry the whole group shares
+    size_t ext = 0, bits = 0; // a CB group: its node table int32[count][4] at tab[ext], and the d of its nodes together
 };
 
 // The arguments every thfhe_dag_run_*_batch entry has: the inputs, the node rows, the wires to return.
@@ -155,6 +160,7 @@ enum DagGen : unsigned {
     kDagGenTree = 2,   // THFHE_LUT_ENC, THFHE_SELECT, THFHE_TREE; every family may be absent (thfhe_dag_run_tree_batch)
     kDagGenMv = 4,     // THFHE_MV; with kDagGenTree also THFHE_TREE_MV (thfhe_dag_run_mv_batch; thfhe_mk_dag_run_mv_batch has no tree generation)
     kDagGenLhe = 8,    // THFHE_LHE_LOOKUP, THFHE_LHE_GATHER, THFHE_LHE_WFA (thfhe_dag_run_lhe_batch with its families)
+    kDagGenCb = 16,    // THFHE_CB (thfhe_dag_run_cb_batch with its family)
 };
 // Everything a run can bring besides its DagCall: the table families (host pointers) with their counts.  An entry fills the families it has and the
 // generations it admits; none (gens = 0) is a run of four-column gate rows.  After dag_families_check a family without a pointer has count 0.
@@ -177,6 +183,11 @@ struct DagFamilies {
     const int32_t *mv_factors = nullptr;                // the taps of every mvs[] entry
     size_t n_factor_words = 0;
     const thfhe_dag_lhe_families *lhe = nullptr;        // the leveled families, with kDagGenLhe
+    const thfhe_dag_cb_families *cb = nullptr;          // the computed sets, with kDagGenCb
+    int n_client_sets() const { return lhe ? lhe->n_sets : 0; }
+    int n_computed_sets() const { return cb ? cb->n_sets : 0; }
+    // d of set `s` of the run when the host knows it: a computed set's; -1 for a client set
+    int computed_d(int s) const { return s >= n_client_sets() ? cb->sets[s - n_client_sets()].d : -1; }
 };
 
 // the rules a multi-value rotation adds to lut_spec_check's: theta 1, p taps, q outputs, the table count (thfhe_mv_lut_bootstrap)
@@ -216,26 +227,26 @@ inline int dag_mv_spec_check(const DagFamilies &F, const thfhe_mv_spec &m, bool 
 }
 
 // One lks[] entry as a LOOKUP row (gather = false) or a GATHER row uses it: the rules of thfhe_lhe_lookup that need no set, then the node kind's own.
-inline int dag_lhe_spec_check(const thfhe_dag_lhe_families &F, const thfhe_dag_lhe_spec &k, bool gather) {
+inline int dag_lhe_spec_check(const thfhe_dag_lhe_families &F, const thfhe_dag_lhe_spec &k, bool gather, int n_computed = 0) {
     if (k.d_tree < 0 || k.d_tree > 6) return thfhe_fail(THFHE_E_INVALID, "leveled node: d_tree must be 0 .. 6");
     if (k.d_rot < 0 || k.d_rot > 10) return thfhe_fail(THFHE_E_INVALID, "leveled node: d_rot must be 0 .. 10");
     if (k.theta != 1 && k.theta != 2 && k.theta != 4) return thfhe_fail(THFHE_E_INVALID, "leveled node: theta must be 1, 2 or 4");
     if (k.theta > (1024 >> k.d_rot)) return thfhe_fail(THFHE_E_INVALID, "leveled node: theta must not exceed box = N >> d_rot");
     if (gather && k.theta != 1) return thfhe_fail(THFHE_E_INVALID, "LHE_GATHER node: the spec's theta must be 1 (a packed box holds one value)");
     if (gather && (k.d_rot < 1 || k.d_rot > 9)) return thfhe_fail(THFHE_E_INVALID, "LHE_GATHER node: d_rot must be 1 .. 9 (the box packing's p = 2^d_rot)");
-    if (!F.sets || F.n_sets < 1) return thfhe_fail(THFHE_E_INVALID, "leveled node: no tgsw sets given (null family)");
-    if (k.set < 0 || k.set >= F.n_sets) return thfhe_fail(THFHE_E_INVALID, "leveled node: the spec's set is out of range (0 .. n_sets-1)");
+    if (F.n_sets + n_computed < 1) return thfhe_fail(THFHE_E_INVALID, "leveled node: no tgsw sets given (null family)");
+    if (k.set < 0 || k.set >= F.n_sets + n_computed) return thfhe_fail(THFHE_E_INVALID, "leveled node: the spec's set is out of range (0 .. n_sets-1)");
     return THFHE_OK;
 }
 // One wfas[] entry: the rules of thfhe_lhe_wfa that need no set, its sets within sets[], its three slices of the word pool and their entries.
-inline int dag_wfa_spec_check(const thfhe_dag_lhe_families &F, const thfhe_dag_wfa_spec &a) {
+inline int dag_wfa_spec_check(const thfhe_dag_lhe_families &F, const thfhe_dag_wfa_spec &a, int n_computed = 0) {
     if (a.n_sets < 1 || a.n_sets > 64) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: the spec's n_sets must be 1 .. 64");
     if (a.n_steps < 1 || a.n_steps > 4096) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: n_steps must be 1 .. 4096");
     if (a.n_states < 1 || a.n_states > 64) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: n_states must be 1 .. 64");
     if (a.n_out < 1 || a.n_out > 64) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: n_out must be 1 .. 64");
     if (a.theta != 1 && a.theta != 2 && a.theta != 4) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: theta must be 1, 2 or 4");
-    if (!F.sets || F.n_sets < 1) return thfhe_fail(THFHE_E_INVALID, "leveled node: no tgsw sets given (null family)");
-    if (a.set0 < 0 || (long)a.set0 + a.n_sets > F.n_sets) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: set0 + n_sets out of range (0 .. n_sets)");
+    if (F.n_sets + n_computed < 1) return thfhe_fail(THFHE_E_INVALID, "leveled node: no tgsw sets given (null family)");
+    if (a.set0 < 0 || (long)a.set0 + a.n_sets > F.n_sets + n_computed) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: set0 + n_sets out of range (0 .. n_sets)");
     if (!F.wfa_words) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: no word pool given (null family)");
     const size_t n_trans = (size_t)a.n_steps * a.n_states * 2;
     if (a.trans_off < 0 || (size_t)a.trans_off + n_trans > F.n_wfa_words || a.step_off < 0 || (size_t)a.step_off + a.n_steps > F.n_wfa_words ||
@@ -295,6 +306,18 @@ inline int dag_families_check(const DagCall &A, const DagFamilies &F) {
                                     {L->wfa_words != nullptr, (long long)L->n_wfa_words, 1, 1 << 28, "lhe: n_wfa_words must be 1 .. 2^28 (0 with wfa_words = NULL)"}},
                                    lhe_null_msg));
     }
+    if (const thfhe_dag_cb_families *const B = F.cb) {
+        if (B->mode != THFHE_CB_PER_LEVEL && B->mode != THFHE_CB_ONE_ROTATION)
+            return thfhe_fail(THFHE_E_INVALID, "circuit bootstrap: mode must be THFHE_CB_PER_LEVEL or THFHE_CB_ONE_ROTATION");
+        if (!B->sets || B->n_sets < 1 || B->n_sets > 64) return thfhe_fail(THFHE_E_INVALID, "cb: n_sets must be 1 .. 64");
+        if (F.n_client_sets() + B->n_sets > 64) return thfhe_fail(THFHE_E_INVALID, "cb: client sets + computed sets must be at most 64");
+        if (!B->cb_wires && B->n_cb_wires) return thfhe_fail(THFHE_E_INVALID, "null argument: a wire pool with a count but no pointer");
+        for (int s = 0; s < B->n_sets; s++) {
+            if (B->sets[s].d < 1 || B->sets[s].d > 16) return thfhe_fail(THFHE_E_INVALID, "cb: d must be 1 .. 16");
+            if (B->sets[s].wire_off < 0 || (size_t)B->sets[s].wire_off + B->sets[s].d > B->n_cb_wires)
+                return thfhe_fail(THFHE_E_INVALID, "cb: wire_off + d runs past the wire pool");
+        }
+    }
     for (int s = 0; s < F.n_specs; s++)
         THFHE_TRY(lut_spec_check(F.specs[s]));
     for (int t = 0; t < F.n_trees; t++) {
@@ -315,6 +338,9 @@ struct DagRow {
     int nin = 0;                              // wire operands, row fields 1 .. nin
     int32_t cand_first = 0, cand_count = 0;   // SELECT / GATHER: the candidate wires; they count for the depth as operands do
     int outs = 0;                             // LUT_OUT rows due after the row
+    const int32_t *list = nullptr;            // CB: the operand list, list_count pool wires; they count for the depth as candidates do
+    int32_t list_count = 0;
+    int32_t set_first = 0, set_count = 0;     // leveled rows: the sets of the run the row reads; a computed one gives the row its depth.  CB: the set it defines
 };
 
 // The row checks of a run, one checker per node kind; each fills the DagRow of a row it accepts.
@@ -409,7 +435,12 @@ struct DagRowChecks {
         if (row[4] < 0 || row[4] >= L.n_lks) return thfhe_fail(THFHE_E_INVALID, "LHE_LOOKUP / LHE_GATHER node: lk out of range (0 .. n_lks-1)");
         const thfhe_dag_lhe_spec &ls = L.lks[row[4]];
         r.cls = gather ? kDagLheGather : kDagLheLookup, r.entry = row[4];
-        if (first_use(r.cls, row[4])) THFHE_TRY(dag_lhe_spec_check(L, ls, gather));
+        if (first_use(r.cls, row[4])) {
+            THFHE_TRY(dag_lhe_spec_check(L, ls, gather, F.n_computed_sets()));
+            if (F.computed_d(ls.set) >= 0 && ls.d_tree + ls.d_rot != F.computed_d(ls.set))
+                return thfhe_fail(THFHE_E_INVALID, "leveled node: d_tree + d_rot must equal the set's d");
+        }
+        r.set_first = ls.set, r.set_count = 1;
         if (gather)
             return candidates(r, row[5], (int32_t)1 << (ls.d_tree + ls.d_rot), w,
                               "LHE_GATHER node: candidate is not an earlier wire (first .. first + 2^d - 1 must all be defined above)");
@@ -427,11 +458,23 @@ struct DagRowChecks {
         if (row[4] < 0 || row[4] >= L.n_wfas) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: wfa out of range (0 .. n_wfas-1)");
         const thfhe_dag_wfa_spec &a = L.wfas[row[4]];
         r.cls = kDagLheWfa, r.entry = row[4];
-        if (first_use(kDagLheWfa, row[4])) THFHE_TRY(dag_wfa_spec_check(L, a));
+        if (first_use(kDagLheWfa, row[4])) THFHE_TRY(dag_wfa_spec_check(L, a, F.n_computed_sets()));
+        r.set_first = a.set0, r.set_count = a.n_sets;
         if (!L.fin_b || L.n_fin_rows < 1) return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: no final weights given (null family)");
         if (row[5] < 0 || (long)row[5] + a.n_states > L.n_fin_rows)
             return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: fin_row0 + n_states out of range (0 .. n_fin_rows)");
         r.outs = a.n_out * a.theta - 1;
+        return THFHE_OK;
+    }
+    // (CB, -1, -1, -1, cbset, -1); w: the row's own wire
+    int cb(const int32_t *row, int32_t w, DagRow &r) const {
+        const thfhe_dag_cb_families &B = *F.cb;
+        if (row[1] != -1 || row[2] != -1 || row[3] != -1 || row[5] != -1) return thfhe_fail(THFHE_E_INVALID, "CB node: the operand fields and field 5 must be -1");
+        if (row[4] < 0 || row[4] >= B.n_sets) return thfhe_fail(THFHE_E_INVALID, "CB node: cbset out of range (0 .. n_sets-1)");
+        const thfhe_dag_cb_spec &cs = B.sets[row[4]];
+        r.cls = kDagCb, r.list = B.cb_wires + cs.wire_off, r.list_count = cs.d, r.set_first = row[4], r.set_count = 1;
+        for (int i = 0; i < cs.d; i++)
+            if (r.list[i] < 0 || r.list[i] >= w) return thfhe_fail(THFHE_E_INVALID, "CB node: a pool wire is not an earlier wire");
         return THFHE_OK;
     }
     // a row other than LUT_OUT: the checker of its kind; an opcode of a generation the run does not admit goes to the engine's gates
@@ -444,6 +487,7 @@ struct DagRowChecks {
         if ((F.gens & kDagGenMv) && (op == THFHE_MV || (op == THFHE_TREE_MV && (F.gens & kDagGenTree)))) return mv(row, op == THFHE_TREE_MV, r);
         if ((F.gens & kDagGenLhe) && (op == THFHE_LHE_LOOKUP || op == THFHE_LHE_GATHER)) return lookup(row, w, op == THFHE_LHE_GATHER, r);
         if ((F.gens & kDagGenLhe) && op == THFHE_LHE_WFA) return wfa(row, r);
+        if ((F.gens & kDagGenCb) && op == THFHE_CB) return cb(row, w, r);
         return gate(row, classify, r);
     }
 };
@@ -455,6 +499,9 @@ struct DagPlan {
     int max_theta = 1;   // most records per node of any launch group (LUT groups: theta); sizes staging and workspace
     int64_t rotations = 0;
     int32_t max_depth = 0;
+    size_t cb_pool = 0;          // plans with CB groups: the run's wire pool in tab, after the groups
+    size_t cb_bits = 0;          // the d of every CB node of the run: its level-2 rotations per instance in one-rotation mode, 1 / l of them per level
+    size_t cb_max_bits = 0;      // ... of the widest CB group
     void fill_stats(int64_t *stats) const {
         stats[0] = max_depth, stats[1] = 0, stats[2] = rotations, stats[3] = (int64_t)max_width;
         // a TREE / TREE_MV group: level-1 and selection launch
@@ -467,15 +514,16 @@ struct DagPlan {
     }
     bool has_lhe_groups() const {
         for (const auto &b : batches)
-            if (b.cls >= kDagLheLookup) return true;
+            if (dag_class_leveled(b.cls)) return true;
         return false;
     }
+    bool has_cb_groups() const { return cb_max_bits != 0; }
 };
 
 // the blind rotations of a launch group of `count` nodes: a MUX takes two, a TREE node its R level-1 rotations and the selection, a TREE_MV node one
 // multi-value rotation and k selections; a linear gate and a leveled node none
 inline size_t dag_group_rotations(const DagFamilies &F, int cls, int32_t entry, size_t count) {
-    if (cls == kDagLinear || cls >= kDagLheLookup) return 0;
+    if (cls == kDagLinear || cls >= kDagLheLookup) return 0;   // a CB node: level-2 rotations only (DagPlan::cb_bits)
     if (cls == kDagMux) return 2 * count;
     if (cls == kDagTree) return count * (size_t)(F.trees[entry].p_hi / F.trees[entry].lo.theta + 1);
     if (cls == kDagTreeMv) return count * (size_t)(1 + F.mvs[entry].k);
@@ -501,6 +549,8 @@ int dag_plan(const DagCall &A, const DagFamilies &F, Classify classify, DagPlan 
     DagRowChecks checks{F, {}};
     int32_t max_depth = 0;
     int32_t head = -1, pending = 0;   // the node whose LUT_OUT rows are still due, and how many
+    const int n_client = F.n_client_sets();
+    std::vector<int32_t> set_depth((size_t)F.n_computed_sets(), -1);   // the depth a computed set is defined at, -1 before its CB row
     for (size_t g = 0; g < n_gates; g++) {
         const int32_t *row = gates + stride * g;
         const int32_t w = (int32_t)(n_inputs + g);
@@ -524,11 +574,23 @@ int dag_plan(const DagCall &A, const DagFamilies &F, Classify classify, DagPlan 
             above(in);
         }
         for (int32_t in = r.cand_first; in < r.cand_first + r.cand_count; in++) above(in);
+        for (int32_t i = 0; i < r.list_count; i++) above(r.list[i]);
+        if (r.cls != kDagCb)   // a leveled row inherits the depth of the computed sets it reads
+            for (int32_t t = std::max(r.set_first, n_client); t < r.set_first + r.set_count; t++) {
+                if (set_depth[t - n_client] < 0) return thfhe_fail(THFHE_E_INVALID, "leveled node: it reads a computed set before the set's CB row");
+                if (set_depth[t - n_client] >= d) d = set_depth[t - n_client], s = 0;
+            }
         if (r.cls == kDagLinear) s += 1; else d += 1, s = 0;
+        if (r.cls == kDagCb) {
+            if (set_depth[r.set_first] >= 0) return thfhe_fail(THFHE_E_INVALID, "CB node: the set has a CB row already (exactly one per computed set)");
+            set_depth[r.set_first] = d;
+        }
         depth[w] = d, sub[w] = s;
         if (d > max_depth) max_depth = d;
     }
     if (pending) return thfhe_fail(THFHE_E_INVALID, "LUT node: missing LUT_OUT row (theta - 1 of them must follow it)");
+    for (int32_t sd : set_depth)
+        if (sd < 0) return thfhe_fail(THFHE_E_INVALID, "cb: a computed set has no CB row (exactly one per computed set)");
     plan.max_depth = max_depth;
     // per level: the bootstrapped groups by (class, entry) -- entry -1 for the classes that are one group --, and the linear sub-levels in order
     struct Level {
@@ -561,8 +623,33 @@ int dag_plan(const DagCall &A, const DagFamilies &F, Classify classify, DagPlan 
         const auto &boot = levels[d].boot;
         for (int32_t k : {kDagGate2, kDagGate3, kDagMux, kDagLut1, kDagLut2, kDagLut4, kDagEnc1, kDagEnc2, kDagEnc4})
             if (const auto it = boot.find({k, -1}); it != boot.end()) emit(d, 0, k, it->second, -1);
-        for (auto it = boot.lower_bound({kDagSelect, INT32_MIN}); it != boot.end(); ++it) emit(d, 0, it->first.first, it->second, it->first.second);
+        // the level's CB nodes: one group, its node table after its columns
+        auto emit_cb = [&]() {
+            const auto it = boot.find({kDagCb, -1});
+            if (it == boot.end()) return;
+            emit(d, 0, kDagCb, it->second, -1);
+            plan.batches.back().ext = plan.tab.size();
+            int32_t base = 0;
+            for (int32_t g : it->second) {
+                const thfhe_dag_cb_spec &cs = F.cb->sets[gates[stride * g + 4]];
+                for (int32_t v : {base, cs.wire_off, cs.d, (int32_t)(n_inputs + g)}) plan.tab.push_back(v);
+                base += cs.d;
+            }
+            plan.batches.back().bits = (size_t)base;
+            plan.cb_bits += (size_t)base, plan.cb_max_bits = std::max(plan.cb_max_bits, (size_t)base);
+        };
+        bool cb_done = false;
+        for (auto it = boot.lower_bound({kDagSelect, INT32_MIN}); it != boot.end(); ++it) {
+            if (it->first.first == kDagCb) continue;
+            if (it->first.first >= kDagLheLookup && !cb_done) emit_cb(), cb_done = true;
+            emit(d, 0, it->first.first, it->second, it->first.second);
+        }
+        if (!cb_done) emit_cb();
         for (size_t q = 0; q < levels[d].lin.size(); q++) emit(d, (int32_t)q + 1, kDagLinear, levels[d].lin[q], -1);
+    }
+    if (plan.cb_max_bits) {
+        plan.cb_pool = plan.tab.size();
+        plan.tab.insert(plan.tab.end(), F.cb->cb_wires, F.cb->cb_wires + F.cb->n_cb_wires);
     }
     return THFHE_OK;
 }
@@ -604,6 +691,8 @@ struct DagExtGroup {
     long all, cnt;
     size_t n_wires;
     size_t off = 0;   // the group's index columns in plan.tab, for an engine that walks the nodes on the host (the leveled groups)
+    const int32_t *tab = nullptr;   // the device's copy of plan.tab
+    size_t ext = 0;                 // a CB group: its node table at tab[ext] (DagBatch::ext)
 };
 
 // Device-resident executor.  Level by level, each class of a level as slices of at most `slice_cap` gates over ALL instances: gather ->
@@ -660,7 +749,8 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
         }
         if (cls >= kDagSelect) {
             if constexpr (!std::is_same_v<RunExt, std::nullptr_t>)
-                rc = run_ext(DagExtGroup{cls, plan.batches[b].tree, d_wires, t0, t1, t2, t_out, t_out + 2 * cnt, all, cnt, n_wires, plan.batches[b].off});
+                rc = run_ext(DagExtGroup{cls, plan.batches[b].tree, d_wires, t0, t1, t2, t_out, t_out + 2 * cnt, all, cnt, n_wires, plan.batches[b].off, d_tab,
+                                             plan.batches[b].ext});
             continue;
         }
         if (cls >= kDagLut1) {   // LUT groups, and LUT_ENC groups over the run's encrypted tables

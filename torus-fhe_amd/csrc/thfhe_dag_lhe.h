@@ -1,5 +1,5 @@
 // thfhe_dag_lhe.h -- the leveled nodes of the gate-DAG executor (thfhe_dag_run_lhe_batch; single key): LHE_LOOKUP, LHE_GATHER and
-// LHE_WFA groups on the client's TGSW sets.  Included by thfhe_sk.hip INSIDE its second anonymous namespace after thfhe_lhe.h, whose launch chains
+// LHE_WFA groups on the client's TGSW sets and, in thfhe_dag_run_cb_batch, on the sets the run computed (looked up through sk_dag_sets).  Included by thfhe_sk.hip INSIDE its second anonymous namespace after thfhe_lhe.h, whose launch chains
 // (enqueue_lhe_lookup, enqueue_lhe_wfa) the groups run on device pointers; sk_dag_run_luts calls the three functions below through forward declarations.
 //
 // The leveled kernels take the TGSW sample of a job from the job's number (spec + job d 2l 32 KiB), so a chain runs over consecutive instances of ONE
@@ -7,6 +7,11 @@
 // node's wires by dag_scatter_theta_kernel (one node per launch: cnt = 1, the index column advanced to the node).
 #ifndef THFHE_DAG_LHE_H
 #define THFHE_DAG_LHE_H
+
+// d of set i of the run: a computed set's from its spec (thfhe_dag_run_cb_batch; an index past the client's sets), a client set's own
+int sk_dag_set_d(const DagFamilies &T, int i) { return T.computed_d(i) >= 0 ? T.computed_d(i) : T.lhe->sets[i]->d; }
+// the sets of the run from set i on: the client's array, or, in a run with computed sets, the context's list of both kinds (sk_dag_cb_reserve)
+const thfhe_tgsw_set *const *sk_dag_sets(const thfhe_ctx *c, const DagFamilies &T, int i) { return (T.cb ? c->dag_sets.data() : T.lhe->sets) + i; }
 
 // instances per chain of a group: the flat entries' thfhe_set_tree_slice rules, at most thfhe_set_dag_slice, one grid.y
 size_t dag_lhe_slice(const thfhe_ctx *c, const thfhe_dag_lhe_families &F, const DagBatch &b, size_t instances) {
@@ -25,6 +30,16 @@ size_t dag_lhe_slice(const thfhe_ctx *c, const thfhe_dag_lhe_families &F, const 
 // another context, a set count below `instances`, d_tree + d_rot against the set's d, step_bit against the spec's sets.
 int sk_dag_lhe_check_sets(const thfhe_ctx *c, const DagPlan &plan, const DagFamilies &T, size_t instances) {
     const thfhe_dag_lhe_families &F = *T.lhe;
+    if (T.cb)   // a computed set's d is known on the host: the step bits that name one, before any set or context is looked at
+        for (const DagBatch &b : plan.batches) {
+            if (b.cls != kDagLheWfa) continue;
+            const thfhe_dag_wfa_spec &a = F.wfas[b.tree];
+            for (int j = 0; j < a.n_steps; j++) {
+                const int32_t sb = F.wfa_words[a.step_off + j];
+                if (sb >= 0 && (sb >> 4) < a.n_sets && T.computed_d(a.set0 + (sb >> 4)) >= 0 && (sb & 15) >= T.computed_d(a.set0 + (sb >> 4)))
+                    return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: step_bit must name bit 0 .. d-1 of set 0 .. n_sets-1 of the spec (16 set + bit)");
+            }
+        }
     for (int i = 0; i < F.n_sets; i++)
         if (!F.sets[i]) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
@@ -33,16 +48,16 @@ int sk_dag_lhe_check_sets(const thfhe_ctx *c, const DagPlan &plan, const DagFami
     for (int i = 0; i < F.n_sets; i++)
         if (F.sets[i]->count < instances) return thfhe_fail(THFHE_E_INVALID, "lhe: a set holds fewer samples than the run has instances");
     for (const DagBatch &b : plan.batches) {
-        if (b.cls < kDagLheLookup) continue;
+        if (!dag_class_leveled(b.cls)) continue;
         if (b.cls == kDagLheWfa) {
             const thfhe_dag_wfa_spec &a = F.wfas[b.tree];
             const int32_t *const step_bit = F.wfa_words + a.step_off;
             for (int j = 0; j < a.n_steps; j++)
-                if (step_bit[j] < 0 || (step_bit[j] >> 4) >= a.n_sets || (step_bit[j] & 15) >= F.sets[a.set0 + (step_bit[j] >> 4)]->d)
+                if (step_bit[j] < 0 || (step_bit[j] >> 4) >= a.n_sets || (step_bit[j] & 15) >= sk_dag_set_d(T, a.set0 + (step_bit[j] >> 4)))
                     return thfhe_fail(THFHE_E_INVALID, "LHE_WFA node: step_bit must name bit 0 .. d-1 of set 0 .. n_sets-1 of the spec (16 set + bit)");
         } else {
             const thfhe_dag_lhe_spec &k = F.lks[b.tree];
-            if (k.d_tree + k.d_rot != F.sets[k.set]->d) return thfhe_fail(THFHE_E_INVALID, "leveled node: d_tree + d_rot must equal the set's d");
+            if (k.d_tree + k.d_rot != sk_dag_set_d(T, k.set)) return thfhe_fail(THFHE_E_INVALID, "leveled node: d_tree + d_rot must equal the set's d");
         }
     }
     return THFHE_OK;
@@ -55,7 +70,7 @@ int sk_dag_lhe_reserve(thfhe_ctx *c, const DagPlan &plan, const DagFamilies &T, 
     const size_t words = c->p.n + 1;
     bool any = false;
     for (const DagBatch &b : plan.batches) {
-        if (b.cls < kDagLheLookup) continue;
+        if (!dag_class_leveled(b.cls)) continue;
         any = true;
         const size_t S = dag_lhe_slice(c, F, b, instances);
         size_t recs, ws;   // records and TLWE samples of workspace (per buffer) per instance
@@ -120,12 +135,12 @@ int sk_dag_lhe_group(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, cons
                 const int32_t *const d_words = c->d_dag_lhe_words.as<int32_t>();
                 const size_t fin = (size_t)h_y[node] * 1024;
                 recs = a.n_out * a.theta;
-                THFHE_TRY(enqueue_lhe_wfa(c, F.sets + a.set0, q0, S, a.n_steps, a.n_states, F.wfa_words + a.step_off, d_words + a.trans_off, d_words + a.start_off,
+                THFHE_TRY(enqueue_lhe_wfa(c, sk_dag_sets(c, T, a.set0), q0, S, a.n_steps, a.n_states, F.wfa_words + a.step_off, d_words + a.trans_off, d_words + a.start_off,
                                           F.fin_a ? c->d_dag_lhe_fin_a.as<int32_t>() + fin : nullptr, c->d_dag_lhe_fin_b.as<int32_t>() + fin, nullptr, 0, a.theta,
                                           a.n_out, cus, ks_out, false));
             } else {
                 const thfhe_dag_lhe_spec &k = F.lks[g.tree];
-                const thfhe_tgsw_set *const set = F.sets[k.set];
+                const thfhe_tgsw_set *const set = *sk_dag_sets(c, T, k.set);
                 const cplx *const spec = set->spec.as<cplx>() + q0 * lhe_sample_slots(c, set->d);
                 recs = k.theta;
                 if (g.cls == kDagLheGather) {

@@ -503,6 +503,16 @@ __global__ __launch_bounds__(256) void sk_linear_kernel(const int32_t *__restric
 // ======================================================================================================
 // host side
 // ======================================================================================================
+// Device-resident TGSW samples of thfhe_tgsw_set_create: the spectra of count x d address bits, laid out like the bootstrapping key's with
+// (sample d + bit) in the place of the key index.  Belongs to the context that made it and is destroyed before it; the computed sets of the gate DAG
+// (thfhe_dag_run_cb_batch) are the context's own.
+struct THFHE_INTERNAL thfhe_tgsw_set {
+    thfhe_ctx *ctx = nullptr;
+    DevBuf spec;
+    size_t count = 0;
+    int d = 0;
+};
+
 struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     thfhe_params p;
     int rec_words() const { return p.n + 1; }
@@ -535,6 +545,10 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     // level-2 mod-switched words, level-2 accumulators, extracted records of one level, the l records per bit and the TGSW rows; the Torus64 test
     // vector of the one-rotation mode
     CbKey cb;
+    // circuit-bootstrap nodes of the gate DAG (thfhe_dag_run_cb_batch): the computed sets (grow-only spectra, reused by the next run,
+    // freed by thfhe_dag_cb_release), and the sets of the current run in the order its rows name them, the client's then the computed ones
+    std::vector<std::unique_ptr<thfhe_tgsw_set>> cb_sets;
+    std::vector<const thfhe_tgsw_set *> dag_sets;
     DevBuf d_cb_lwe, d_cb_bara, d_cb_barb, d_cb_acc, d_cb_x, d_cb_lwe2, d_cb_rows, d_cb_tv;
     int cus = 0;         // compute units of the device, asked once (ctx_cus)
     int wfa_chunk = 0;   // states per workgroup of sk_lhe_wfa_step_kernel, 0: chosen per slice (wfa_chunk_for)
@@ -552,15 +566,6 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
         for (hipEvent_t e : grp_ev)
             if (e) (void)hipEventDestroy(e);
     }
-};
-
-// Device-resident TGSW samples of thfhe_tgsw_set_create: the spectra of count x d address bits, laid out like the bootstrapping key's with
-// (sample d + bit) in the place of the key index.  Belongs to the context that made it and is destroyed before it.
-struct THFHE_INTERNAL thfhe_tgsw_set {
-    thfhe_ctx *ctx = nullptr;
-    DevBuf spec;
-    size_t count = 0;
-    int d = 0;
 };
 
 namespace {
@@ -756,6 +761,16 @@ int sk_dag_ensure(thfhe_ctx *c, size_t max_gates, int theta_max, int32_t **in, i
     return dag_ensure(c, max_gates, theta_max, in, out, [&](size_t jobs, int theta) { return ensure_workspace(c, jobs, theta); });
 }
 
+// The level-2 side of a run whose plan holds CB groups (thfhe_dag_cb.h): the context the gate context's stream is lent to, and its ring degree.
+struct DagCbRun {
+    thfhe_mk_ctx *l2 = nullptr;
+    int N2 = 0;
+};
+int sk_dag_cb_reserve(thfhe_ctx *c, const DagPlan &plan, const DagFamilies &T, const DagCbRun &cbr, size_t instances);
+int sk_dag_cb_group(thfhe_ctx *c, const DagCbRun &cbr, const DagPlan &plan, const DagFamilies &T, const DagExtGroup &g, size_t instances);
+int cb_level2_begin(thfhe_ctx *c, thfhe_mk_ctx *l2, int mode, int *N2);
+int cb_level2_end(thfhe_mk_ctx *l2);
+
 // the leveled groups of a run (thfhe_dag_lhe.h, after the leveled kernels)
 int sk_dag_lhe_check_sets(const thfhe_ctx *c, const DagPlan &plan, const DagFamilies &T, size_t instances);
 int sk_dag_lhe_reserve(thfhe_ctx *c, const DagPlan &plan, const DagFamilies &T, size_t instances, size_t &w_cand);
@@ -767,9 +782,10 @@ int sk_dag_lhe_group(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, cons
 // and runs the tree chain from there; a TREE group runs the whole chain with both prologues reading the wire table.  An MV group is
 // one multi-value PBS stage on the wire table, its q records per node scattered into consecutive wires; a TREE_MV group the k-table chain with both
 // prologues on the wire table.  A leveled group is sk_dag_lhe_group's.  Everything is enqueued on the gate context's stream.
-int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const DagFamilies &T, const DagCall &A, size_t instances) {
+int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const DagFamilies &T, const DagCall &A, size_t instances, const DagCbRun &cbr = {}) {
     const int words = c->rec_words();
     hipStream_t st = c->stream;
+    if (cbr.l2) THFHE_TRY(sk_dag_cb_reserve(c, plan, T, cbr, instances));   // first: it refuses a run that does not fit (THFHE_E_NOMEM) with nothing done
     // a slice of a SELECT / TREE group: at most dag_slice nodes over all instances and at most tree_slice / p_hi of them
     const size_t dag_slice = c->dag_slice, tree_slice = c->tree_slice;
     auto slice_of = [&](int tree, size_t all) { return std::min({all, dag_slice, std::max<size_t>(1, tree_slice / (size_t)T.trees[tree].p_hi)}); };
@@ -813,6 +829,7 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
     auto ext_group = [&](const DagExtGroup &g) -> int {
         auto no_seam = [](int) { return (int)THFHE_OK; };
         int32_t *const dst = c->stage.out_ptr();
+        if (g.cls == kDagCb) return sk_dag_cb_group(c, cbr, plan, T, g, instances);
         if (g.cls >= kDagLheLookup) return sk_dag_lhe_group(c, pc, plan, T, g, instances);
         if (g.cls == kDagMv || g.cls == kDagTreeMv) {   // t_y = each node's table
             const thfhe_mv_spec m = T.mvs[g.tree];
@@ -934,17 +951,21 @@ int mv_lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv0,
 }
 
 // What the six-column entries share (T: the entry's families and the generations of node kinds it admits): the host checks and the plan, the two
-// locks, the run in sk_dag_run_luts.  Both contexts stay locked for the run.  The LUT entry has plaintext tables only, so its plans
+// locks, the run in sk_dag_run_luts (a plan with CB groups: between cb_level2_begin and cb_level2_end, the level-2 context enqueueing on the gate
+// context's stream; stats is then int64[5]).  Both contexts stay locked for the run.  The LUT entry has plaintext tables only, so its plans
 // hold no group that needs the packing context; from thfhe_dag_run_tree_batch on every family may be absent.
-int sk_dag_run(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagCall &A, DagFamilies T, size_t instances, int64_t *stats) {
+int sk_dag_run(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagCall &A, DagFamilies T, size_t instances, int64_t *stats, thfhe_mk_ctx *l2 = nullptr) {
     const bool ext = T.gens & kDagGenTree;
     DagPlan plan;
     THFHE_TRY(dag_checked_plan(A, T, sk_dag_classify, plan));
     if (stats && ext) plan.fill_stats(stats);   // the plan's figures need no device
-    const bool packs = plan.has_tree_groups();
+    const bool packs = plan.has_tree_groups(), cbs = plan.has_cb_groups();
+    if (stats && T.cb) stats[4] = T.cb->mode == THFHE_CB_ONE_ROTATION ? (int64_t)plan.cb_bits : 0;
     if (T.lhe && !plan.has_lhe_groups()) T.lhe = nullptr;
     if (T.lhe) THFHE_TRY(sk_dag_lhe_check_sets(c, plan, T, instances));   // the sets, then the context
     if (!c || (packs && !pc)) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (cbs && !l2) return thfhe_fail(THFHE_E_INVALID, "null ctx: the plan holds CB nodes, which need the level-2 context");
+    if (stats && cbs && T.cb->mode == THFHE_CB_PER_LEVEL) stats[4] = (int64_t)plan.cb_bits * c->p.l;
     if (stats && !ext) plan.fill_stats(stats);   // thfhe_dag_run_lut_batch gives them to a caller with a context only
     if (packs && pack_ctx_device(pc) != c->device)
         return thfhe_fail(THFHE_E_INVALID, "tree: the gate context and the packing context must be on the same device");
@@ -960,12 +981,18 @@ int sk_dag_run(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagCall &A, DagFamilies T
         if (instances == 0 || A.n_nodes == 0) return THFHE_OK;
         if (instances > (size_t)INT32_MAX / 16) return thfhe_fail(THFHE_E_INVALID, "too many instances");
     }
-    return sk_dag_run_luts(c, packs ? pc : nullptr, plan, T, A, instances);
+    if (!cbs) return sk_dag_run_luts(c, packs ? pc : nullptr, plan, T, A, instances);
+    DagCbRun cbr{l2, 0};
+    THFHE_TRY(cb_level2_begin(c, l2, T.cb->mode, &cbr.N2));
+    const int rc = sk_dag_run_luts(c, packs ? pc : nullptr, plan, T, A, instances, cbr);
+    const int rc2 = cb_level2_end(l2);   // drains the stream first
+    return rc ? rc : rc2;
 }
 
 #include "thfhe_lhe.h"
 #include "thfhe_dag_lhe.h"
 #include "thfhe_cb_host.h"
+#include "thfhe_dag_cb.h"
 
 }  // namespace
 
@@ -1140,6 +1167,28 @@ int thfhe_dag_run_lhe_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, const int32_t *inp
     const DagFamilies T{kDagGenLut | kDagGenTree | kDagGenMv | (lhe ? kDagGenLhe : 0u), specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows,
                         mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words, lhe};
     return sk_dag_run(c, pc, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, T, instances, stats);
+}
+
+// the circuit-bootstrap nodes, when their family is given; without it (cb NULL) the call is thfhe_dag_run_lhe_batch.
+int thfhe_dag_run_cb_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, thfhe_mk_ctx *level2, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                           const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
+                           const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs,
+                           const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, const thfhe_dag_lhe_families *lhe,
+                           const thfhe_dag_cb_families *cb, size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
+    if (stats) stats[4] = 0;
+    const DagFamilies T{kDagGenLut | kDagGenTree | kDagGenMv | (lhe ? kDagGenLhe : 0u) | (cb ? kDagGenCb : 0u), specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees,
+                        n_trees, tv1, n_tv1_rows, mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words, lhe, cb};
+    return sk_dag_run(c, pc, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, T, instances, stats, level2);
+}
+
+int thfhe_dag_cb_release(thfhe_ctx *c) {
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    THFHE_HIP(hipStreamSynchronize(c->stream));
+    c->cb_sets.clear();
+    c->dag_sets.clear();
+    return THFHE_OK;
 }
 
 int thfhe_set_dag_slice(thfhe_ctx *c, size_t max_gates) { return ctx_set_dag_slice(c, max_gates); }

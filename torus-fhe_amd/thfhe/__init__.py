@@ -20,6 +20,7 @@ LUT, LUT_OUT = 14, 15   # gate-DAG LUT node and its outputs j > 0 (dag_run_lut_b
 LUT_ENC, SELECT, TREE = 16, 17, 18   # gate-DAG encrypted-table, select and tree nodes (CloudKey.dag_run_tree_batch, dag_run_mv_batch)
 MV, TREE_MV = 19, 20                 # gate-DAG multi-value and k-output multi-value tree nodes (CloudKey.dag_run_mv_batch, dag_run_lhe_batch; MV: MKCloudKey.dag_run_mv_batch)
 LHE_LOOKUP, LHE_GATHER, LHE_WFA = 21, 22, 23   # gate-DAG leveled nodes on TGSW-encrypted bits (CloudKey.dag_run_lhe_batch only)
+CB = 24                                        # gate-DAG node: wires -> a computed TGSW set by circuit bootstrapping (CloudKey.dag_run_cb_batch only)
 
 MU8 = 1 << 29     # encode_message(1, 8), Torus32      (numeric-functions.jl:86-89)
 MU8_64 = 1 << 61  # encode_message64(1, 8), Torus64    (numeric-functions.jl:92-95)
@@ -185,6 +186,17 @@ class DagLheFamilies(C.Structure):
                 ("fin_a", C.POINTER(C.c_int32)), ("fin_b", C.POINTER(C.c_int32)), ("n_fin_rows", C.c_int32)]
 
 
+class DagCbSpec(C.Structure):
+    """thfhe_dag_cb_spec (include/thfhe_hip.h): the bits of one computed set and its slice of the wire pool."""
+    _fields_ = [("d", C.c_int32), ("wire_off", C.c_int32)]
+
+
+class DagCbFamilies(C.Structure):
+    """thfhe_dag_cb_families (include/thfhe_hip.h)."""
+    _fields_ = [("sets", C.POINTER(DagCbSpec)), ("n_sets", C.c_int32), ("cb_wires", C.POINTER(C.c_int32)), ("n_cb_wires", C.c_size_t),
+                ("mode", C.c_int32), ("words", C.POINTER(C.POINTER(C.c_int32)))]
+
+
 def _lut_spec(s):
     """LutSpec from a (n_inputs, (w0, w1, w2), bias, theta) tuple (or a LutSpec)."""
     if isinstance(s, LutSpec):
@@ -233,6 +245,10 @@ SIGNATURES = {
                                           C.POINTER(TreeSpec), C.c_int, _i32p, C.c_int, C.POINTER(MvSpec), C.c_int, _i32p, C.c_int, _i32p, C.c_size_t,
                                           C.POINTER(DagLheFamilies), C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_dag_last_group_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
+    "thfhe_dag_run_cb_batch": (C.c_int, [_vp, _vp, _vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, _i32p, _i32p, C.c_int,
+                                         C.POINTER(TreeSpec), C.c_int, _i32p, C.c_int, C.POINTER(MvSpec), C.c_int, _i32p, C.c_int, _i32p, C.c_size_t,
+                                         C.POINTER(DagLheFamilies), C.POINTER(DagCbFamilies), C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
+    "thfhe_dag_cb_release": (C.c_int, [_vp]),
     "thfhe_bootstrap": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_keyswitch": (C.c_int, [_vp, _i32p, _i32p, C.c_size_t]),
@@ -539,7 +555,7 @@ class _EvalKey(_Handle):
         _check(self._fn("dag_run")(self.h, _p32(wires), x.shape[0], _p32(g), g.shape[0], st.ctypes.data_as(_i64p)))
         return wires, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]), widest_level=int(st[3]))
 
-    def _dag_run(self, what, fn, ctxs, input_records, nodes, cols, families, out_wires):
+    def _dag_run(self, what, fn, ctxs, input_records, nodes, cols, families, out_wires, n_stats=4):
         """The marshalling every dag_run_*_batch shares: fn(*ctxs, inputs, the node rows of `cols` words, *families(), instances, out_wires, outputs, stats).
         families: called after the input records and the rows are checked.  Returns (outputs, the stats dictionary)."""
         words = self.words
@@ -551,9 +567,12 @@ class _EvalKey(_Handle):
         q, n_in = x.shape[0], x.shape[1]
         sel = None if out_wires is None else np.ascontiguousarray(out_wires, np.int32).reshape(-1)
         out = np.zeros((q, g.shape[0] if sel is None else sel.shape[0], words), np.int32)
-        st = np.zeros(4, np.int64)
+        st = np.zeros(n_stats, np.int64)
         _check(fn(*ctxs, _p32(x), n_in, _p32(g), g.shape[0], *fam, q, _p32(sel), 0 if sel is None else sel.shape[0], _p32(out), st.ctypes.data_as(_i64p)))
-        return out, dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
+        stats = dict(levels=int(st[0]), launches=int(st[1]), rotations=int(st[2]) * q, widest_level=int(st[3]) * q, instances=q)
+        if n_stats > 4:   # thfhe_dag_run_cb_batch: the level-2 rotations of the CB nodes
+            stats["level2_rotations"] = int(st[4]) * q
+        return out, stats
 
     def dag_run_batch(self, input_records, gates, out_wires=None):
         """`instances` evaluations of one gate list side by side (the reference's loop over test records,
@@ -822,6 +841,13 @@ class CloudKey(_EvalKey):
         (tab_a None: public); wfas: DagWfaSpec or (n_steps, n_states, theta, n_out, set0, n_sets, trans_off, step_off, start_off) tuples; wfa_words:
         int32[words], their pool; fin_b / fin_a: int32[rows][N] final weights; pack: needed when an LHE_GATHER node is present.  Without any leveled
         family the call is dag_run_mv_batch."""
+        return self._dag_run_leveled(None, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, mvs, mv_tv0, mv_factors, tgsw_sets, lks, tab_b, tab_a, wfas,
+                                     wfa_words, fin_b, fin_a, out_wires, pack)
+
+    def _dag_run_leveled(self, cb, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, mvs=(), mv_tv0=None, mv_factors=None,
+                         tgsw_sets=(), lks=(), tab_b=None, tab_a=None, wfas=(), wfa_words=None, fin_b=None, fin_a=None, out_wires=None, pack=None):
+        """What dag_run_lhe_batch (cb = None) and dag_run_cb_batch share: the leveled families.  cb = (the level-2 key or None, a pointer to the
+        DagCbFamilies or None): the run goes through thfhe_dag_run_cb_batch with the level-2 context after the other two and a fifth statistic."""
         N = self.params.N
         mv = _mv_specs(mvs)
         tv0 = None if mv_tv0 is None else np.ascontiguousarray(mv_tv0, np.int32).reshape(-1, N)
@@ -839,7 +865,35 @@ class CloudKey(_EvalKey):
                              0 if words is None else words.shape[0], _p32(fin_a), _p32(fin_b), rows(fin_b))
         leveled = len(tgsw_sets) or len(lks) or len(wfas) or tab_b is not None or fin_b is not None or words is not None
         families = (mv, len(mvs), _p32(tv0), rows(tv0), _p32(fac), 0 if fac is None else fac.shape[0], C.byref(fam) if leveled else None)
-        return self._dag_run_ext(lib().thfhe_dag_run_lhe_batch, families, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack)
+        if cb is None:
+            return self._dag_run_ext(lib().thfhe_dag_run_lhe_batch, families, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack)
+        level2, cb_fam = cb
+        return self._dag_run_ext(lib().thfhe_dag_run_cb_batch, families + (cb_fam,), input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack,
+                                 more_ctxs=(None if level2 is None else level2.h,), n_stats=5)
+
+    def dag_run_cb_batch(self, input_records, nodes, cb_sets=(), cb_wires=(), one_rotation=False, return_words=False, level2=None, **kw):
+        """dag_run_lhe_batch with circuit-bootstrap nodes (thfhe_dag_run_cb_batch): a CB row turns d wires of the run into the TGSW bits
+        of a computed set, which leveled rows read under set index len(tgsw_sets) + c.  cb_sets: (d, wire_off) tuples or DagCbSpec, one per computed
+        set; cb_wires: the pool of wire ids they slice; one_rotation: stage A from one level-2 rotation per bit (gate-encoded operands only);
+        return_words: also the rows of every computed set, a list of int32[instances][d][2l][2][N], as (outputs, stats, words); level2: the level-2
+        MKCloudKey (default: the one cb_key_set named); the other arguments are dag_run_lhe_batch's.  Without cb_sets the call is dag_run_lhe_batch
+        through the new entry.  stats gains level2_rotations."""
+        p = self.params
+        l2 = level2 if level2 is not None else getattr(self, "_cb_level2", None)
+        if not len(cb_sets):
+            return self._dag_run_leveled((l2, None), input_records, nodes, **kw)
+        q = np.asarray(input_records).shape[0]
+        cs = (DagCbSpec * len(cb_sets))(*[s if isinstance(s, DagCbSpec) else DagCbSpec(int(s[0]), int(s[1])) for s in cb_sets])
+        pool = np.ascontiguousarray(cb_wires, np.int32).reshape(-1)
+        words = [np.zeros((q, s.d, 2 * p.l, 2, p.N), np.int32) for s in cs] if return_words else None
+        wp = (C.POINTER(C.c_int32) * len(cs))(*[_p32(w) for w in words]) if return_words else None
+        fam = DagCbFamilies(cs, len(cs), _p32(pool), pool.shape[0], CB_ONE_ROTATION if one_rotation else CB_PER_LEVEL, wp)
+        out, st = self._dag_run_leveled((l2, C.byref(fam)), input_records, nodes, **kw)
+        return (out, st, words) if return_words else (out, st)
+
+    def dag_cb_release(self):
+        """Free the computed sets the CB nodes of earlier dag_run_cb_batch calls left on this key (thfhe_dag_cb_release); the next run allocates again."""
+        _check(lib().thfhe_dag_cb_release(self.h))
 
     def dag_last_group_ms(self):
         """Device time of the last SELECT / TREE / MV / TREE_MV / leveled group of the last dag_run_*_batch with set_profiling(True) (thfhe_dag_last_group_ms)."""
@@ -854,7 +908,7 @@ class CloudKey(_EvalKey):
         (needed when a SELECT or TREE node is present).  Returns (int32[instances][len(out_wires) or n_nodes][words], stats)."""
         return self._dag_run_ext(lib().thfhe_dag_run_tree_batch, (), input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack)
 
-    def _dag_run_ext(self, fn, families, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack):
+    def _dag_run_ext(self, fn, families, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack, more_ctxs=(), n_stats=4):
         """What dag_run_tree_batch and dag_run_mv_batch share: fn(contexts, inputs, nodes, the earlier table families, `families` -- the multi-value
         arguments of thfhe_dag_run_mv_batch, none for thfhe_dag_run_tree_batch --, instances, outputs, stats)."""
         def earlier():
@@ -866,7 +920,8 @@ class CloudKey(_EvalKey):
                 raise ValueError("enc_a and enc_b must both be given, with the same shape")
             rows = lambda a: 0 if a is None else a.shape[0]
             return (sp, len(specs), _p32(t), rows(t), _p32(ea), _p32(eb), rows(ea), tr, len(trees), _p32(t1), rows(t1)) + tuple(families)
-        return self._dag_run("dag_run_tree_batch / dag_run_mv_batch", fn, (self.h, None if pack is None else pack.h), input_records, nodes, 6, earlier, out_wires)
+        ctxs = (self.h, None if pack is None else pack.h) + tuple(more_ctxs)   # thfhe_dag_run_cb_batch: the level-2 context after the two
+        return self._dag_run("dag_run_tree_batch / dag_run_mv_batch", fn, ctxs, input_records, nodes, 6, earlier, out_wires, n_stats)
 
     # -- leveled table lookup on TGSW-encrypted address bits (thfhe_tgsw_set_create, thfhe_lhe_cmux, thfhe_lhe_lookup) ----------
     def tgsw_set(self, samples, d):

@@ -25,14 +25,20 @@ Leveled nodes (Circuit.lhe_lookup / lhe_gather / lhe_wfa; single ke
 automaton on the client's TGSW-encrypted bits (`tgsw_sets`: instance q reads sample q of every set), each one level and no blind rotation.  Circuits
 that hold them run on thfhe_dag_run_lhe_batch; lhe_array_read reads an array of computed wires at the client's index, wfa_mux_max takes the larger
 of two numbers with one automaton and `width` MUX gates.
+
+Circuit-bootstrap nodes (Circuit.cb_set; single key): d wires of the circuit become the d TGSW bits of a COMPUTED set, whose id the
+leveled nodes accept in place of a client set id, one level and d l (or d) level-2 rotations.  Circuits that hold them run on thfhe_dag_run_cb_batch
+(`level2`: the level-2 key, default the one CloudKey.cb_key_set named); cb_lookup_dag reads a table at an address the circuit computed, cb_array_read
+an array of computed wires at a computed index, cb_mux_max takes the larger of two numbers the circuit holds as gate bits only.
 """
 import time
 
 import numpy as np
 
-from . import AND, COPY, LHE_GATHER, LHE_LOOKUP, LHE_WFA, LUT, LUT_ENC, LUT_OUT, MUX, MV, NOT, OR, SELECT, TREE, TREE_MV, XOR, _wrap32
+from . import AND, CB, COPY, LHE_GATHER, LHE_LOOKUP, LHE_WFA, LUT, LUT_ENC, LUT_OUT, MUX, MV, NOT, OR, SELECT, TREE, TREE_MV, XOR, _wrap32
 
 _LHE_OPS = (LHE_LOOKUP, LHE_GATHER, LHE_WFA)
+CB_SET_BASE = 1 << 16   # Circuit.cb_set returns CB_SET_BASE + c for computed set c; ids below it are the client's sets
 
 
 class Circuit:
@@ -58,6 +64,8 @@ class Circuit:
         self.lhe_specs = []   # (set, d_tree, d_rot, theta) of the LHE_LOOKUP / LHE_GATHER launch groups, deduplicated
         self.wfa_specs = []   # (trans, step_bit, start, theta, set0, n_sets) of the LHE_WFA launch groups
         self.lhe_rows = {}    # gate index of a leveled node -> (lk, row0) / (lk, first) / (wfa, fin_row0)
+        self.cb_specs = []    # the operand wires (bit 0 first) of every computed set, in the order of cb_set
+        self.cb_rows = {}     # gate index of a CB node -> (computed set, -1)
         self._ids = {}
 
     def inputs(self, count):
@@ -295,6 +303,8 @@ class Circuit:
         encrypts (d_tree + d_rot bits, low bits rotate, high bits pick the polynomial): theta consecutive coefficients from addr_lo N / 2^d_rot.  One
         level, no rotation key.  Returns the theta output wire ids (consecutive)."""
         lk = self._lk_id(set_id, d_tree, d_rot, theta)
+        if self._set_d(set_id) not in (None, d_tree + d_rot):
+            raise ValueError("d_tree + d_rot must equal the computed set's d")
         if row0 < 0 or row0 + (1 << d_tree) > len(self.lhe_tab):
             raise ValueError("row0 + 2^d_tree exceeds the registered table polynomials (lhe_table)")
         head = self.gate(LHE_LOOKUP)
@@ -307,6 +317,8 @@ class Circuit:
         if not 1 <= d_rot <= 9:
             raise ValueError("lhe_gather: d_rot must be 1 .. 9")
         lk = self._lk_id(set_id, d_tree, d_rot, 1)
+        if self._set_d(set_id) not in (None, d_tree + d_rot):
+            raise ValueError("d_tree + d_rot must equal the computed set's d")
         if first < 0 or first + (1 << (d_tree + d_rot)) > self.n_wires():
             raise ValueError("the candidates first .. first + 2^d - 1 must be wires defined above the node")
         w = self.gate(LHE_GATHER)
@@ -325,6 +337,8 @@ class Circuit:
             raise ValueError("automaton: expected (trans int32[n_steps][n_states][2], step_bit int32[n_steps], finals, start int32[n_out])")
         if not set_ids or set_ids[0] < 0 or set_ids != list(range(set_ids[0], set_ids[0] + len(set_ids))):
             raise ValueError("lhe_wfa: set_ids must be consecutive set ids")
+        if set_ids[0] < CB_SET_BASE <= set_ids[-1] or (set_ids[0] >= CB_SET_BASE and self._set_d(set_ids[-1]) is None):
+            raise ValueError("lhe_wfa: set_ids must be all client sets or all computed sets (the C entry alone mixes the two)")
         if theta not in (1, 2, 4):
             raise ValueError("theta must be 1, 2 or 4")
         if finals_row0 < 0 or finals_row0 + trans.shape[1] > len(self.lhe_fin):
@@ -337,13 +351,49 @@ class Circuit:
         self.lhe_rows[len(self.gates) - 1] = (self._ids[key], int(finals_row0))
         return [head] + [self.gate(LUT_OUT, head) for _ in range(start.shape[0] * theta - 1)]
 
+    def cb_set(self, wires):
+        """A CB node: circuit bootstrapping of the 1 .. 16 wires `wires` (bit 0 first; inputs too, not necessarily consecutive; gate-encoded in
+        one-rotation mode) into the TGSW bits of a computed set.  One level.  Returns the set id that lhe_lookup / lhe_gather / lhe_wfa accept in
+        place of a client set id; the node's own wire (a copy of bit 0's) is n_wires() - 1 right after the call."""
+        wires = [int(w) for w in wires]
+        if not 1 <= len(wires) <= 16 or any(w < 0 or w >= self.n_wires() for w in wires):
+            raise ValueError("cb_set: expected 1 .. 16 wires defined above the node")
+        self.gate(CB)
+        self.cb_rows[len(self.gates) - 1] = (len(self.cb_specs), -1)
+        self.cb_specs.append(wires)
+        return CB_SET_BASE + len(self.cb_specs) - 1
+
+    def has_cb_nodes(self):
+        """Whether the circuit holds a CB node (it then runs on thfhe_dag_run_cb_batch)."""
+        return bool(self.cb_rows)
+
+    def cb_families(self):
+        """The cb_sets and cb_wires keyword arguments of CloudKey.dag_run_cb_batch: (d, wire_off) per computed set and the pool of their wires."""
+        sets, pool = [], []
+        for wires in self.cb_specs:
+            sets.append((len(wires), len(pool)))
+            pool += wires
+        return dict(cb_sets=sets, cb_wires=np.array(pool, np.int32))
+
+    def _set_index(self, set_id):
+        """The index the entry knows set `set_id` by: the client's sets first, then the computed ones."""
+        return set_id if set_id < CB_SET_BASE else self.n_lhe_sets() + set_id - CB_SET_BASE
+
+    def _set_d(self, set_id):
+        """d of a computed set, None for a client set (the circuit does not know it)."""
+        if set_id < CB_SET_BASE:
+            return None
+        if set_id - CB_SET_BASE >= len(self.cb_specs):
+            raise ValueError("set id: no such computed set (cb_set)")
+        return len(self.cb_specs[set_id - CB_SET_BASE])
+
     def has_lhe_nodes(self):
         """Whether the circuit holds an LHE_LOOKUP, LHE_GATHER or LHE_WFA node (it then runs on thfhe_dag_run_lhe_batch)."""
         return bool(self.lhe_rows)
 
     def n_lhe_sets(self):
         """TGSW sets the leveled nodes name: one more than the largest set id."""
-        return max([k[0] + 1 for k in self.lhe_specs] + [a[4] + a[5] for a in self.wfa_specs] + [0])
+        return max([k[0] + 1 for k in self.lhe_specs if k[0] < CB_SET_BASE] + [a[4] + a[5] for a in self.wfa_specs if a[4] < CB_SET_BASE] + [0])
 
     def lhe_families(self):
         """The leveled keyword arguments of CloudKey.dag_run_lhe_batch but the sets: lks, tab_b, tab_a, wfas, wfa_words, fin_b, fin_a.  A family with
@@ -355,12 +405,12 @@ class Circuit:
             return np.stack([r[0] for r in store]), (np.stack([np.zeros_like(r[0]) if r[1] is None else r[1] for r in store]) if enc else None)
         wfas, words, off = [], [], 0
         for trans, step_bit, start, theta, set0, n_sets in self.wfa_specs:
-            wfas.append((trans.shape[0], trans.shape[1], theta, start.shape[0], set0, n_sets, off, off + trans.size, off + trans.size + step_bit.size))
+            wfas.append((trans.shape[0], trans.shape[1], theta, start.shape[0], self._set_index(set0), n_sets, off, off + trans.size, off + trans.size + step_bit.size))
             words += [trans.reshape(-1), step_bit, start]
             off += trans.size + step_bit.size + start.size
         tab_b, tab_a = rows(self.lhe_tab)
         fin_b, fin_a = rows(self.lhe_fin)
-        return dict(lks=list(self.lhe_specs), tab_b=tab_b, tab_a=tab_a, wfas=wfas, wfa_words=np.concatenate(words) if words else None, fin_b=fin_b, fin_a=fin_a)
+        return dict(lks=[(self._set_index(k[0]),) + k[1:] for k in self.lhe_specs], tab_b=tab_b, tab_a=tab_a, wfas=wfas, wfa_words=np.concatenate(words) if words else None, fin_b=fin_b, fin_a=fin_a)
 
     def has_mv_nodes(self):
         """Whether the circuit holds an MV or TREE_MV node (it then runs on thfhe_dag_run_mv_batch)."""
@@ -386,8 +436,10 @@ class Circuit:
     def nodes(self):
         """int32[n_gates][6] = (op, in0, in1, in2, spec, lut): the rows of thfhe_dag_run_lut_batch (spec = lut = -1 on gate rows); LUT_ENC, SELECT and
         TREE rows (thfhe_dag_run_tree_batch) carry (spec, etab), (tree, first), (tree, row0); MV and TREE_MV rows (thfhe_dag_run_mv_batch) (mv, t);
-        LHE_LOOKUP, LHE_GATHER and LHE_WFA rows (thfhe_dag_run_lhe_batch) (lk, row0), (lk, first), (wfa, fin_row0)."""
-        rows = [tuple(g) + (self.lut_rows.get(i) or self.ext_rows.get(i) or self.mv_rows.get(i) or self.lhe_rows.get(i, (-1, -1))) for i, g in enumerate(self.gates)]
+        LHE_LOOKUP, LHE_GATHER and LHE_WFA rows (thfhe_dag_run_lhe_batch) (lk, row0), (lk, first), (wfa, fin_row0); CB rows (thfhe_dag_run_cb_batch)
+        (cbset, -1)."""
+        rows = [tuple(g) + (self.lut_rows.get(i) or self.ext_rows.get(i) or self.mv_rows.get(i) or self.cb_rows.get(i) or self.lhe_rows.get(i, (-1, -1)))
+                for i, g in enumerate(self.gates)]
         return np.array(rows, np.int32).reshape(-1, 6)
 
     def n_wires(self):
@@ -398,6 +450,8 @@ class Circuit:
         level; its LUT_OUT rows join its level."""
         depth = np.zeros(self.n_wires(), np.int64)
         lv = {}
+        set_depth = {}   # computed set -> the depth of its CB node: a leveled node that reads it sits above
+        reads = lambda ids: max([set_depth[s] for s in ids if s >= CB_SET_BASE] + [0])
         for gi, (op, a, b, c) in enumerate(self.gates):
             if op == LUT_OUT:
                 d = depth[a]
@@ -409,6 +463,14 @@ class Circuit:
                 if op == LHE_GATHER:
                     lk, first = self.lhe_rows[gi]
                     d = max(d, depth[first:first + (1 << (self.lhe_specs[lk][1] + self.lhe_specs[lk][2]))].max())
+                if op in (LHE_LOOKUP, LHE_GATHER):
+                    d = max(d, reads([self.lhe_specs[self.lhe_rows[gi][0]][0]]))
+                if op == LHE_WFA:
+                    spec = self.wfa_specs[self.lhe_rows[gi][0]]
+                    d = max(d, reads(range(spec[4], spec[4] + spec[5])))
+                if op == CB:
+                    d = max(depth[w] for w in self.cb_specs[self.cb_rows[gi][0]])
+                    set_depth[CB_SET_BASE + self.cb_rows[gi][0]] = d + 1
                 if op not in (NOT, COPY):
                     d += 1
             depth[self.n_inputs + gi] = d
@@ -418,7 +480,7 @@ class Circuit:
 
     def census(self):
         ops = [g[0] for g in self.gates]
-        boot = sum(1 for o in ops if o not in (NOT, COPY, LUT_OUT) + _LHE_OPS)   # a leveled node takes no blind rotation
+        boot = sum(1 for o in ops if o not in (NOT, COPY, LUT_OUT, CB) + _LHE_OPS)   # a leveled node takes no blind rotation, a CB node level-2 ones
         c = dict(gates=len(ops), bootstrapped=boot, mux=ops.count(MUX), rotations=boot + ops.count(MUX),
                  depth=len([l for l in self.levels() if self.gates[l[0]][0] not in (NOT, COPY)]))
         if self.lut_rows:
@@ -431,6 +493,8 @@ class Circuit:
             c.update(rotations=c["rotations"] + extra, mvs=ops.count(MV), tree_mvs=ops.count(TREE_MV))
         if self.lhe_rows:
             c.update(lhe_lookups=ops.count(LHE_LOOKUP), lhe_gathers=ops.count(LHE_GATHER), lhe_wfas=ops.count(LHE_WFA))
+        if self.cb_rows:
+            c.update(cbs=ops.count(CB), cb_bits=sum(len(w) for w in self.cb_specs))
         return c
 
 
@@ -1039,7 +1103,55 @@ def wfa_mux_max(cir, a_wires, b_wires, set_ids, width, N=1024):
     return [cir.gate(MUX, lt, b, a) for a, b in zip(a_wires, b_wires)]
 
 
-def _lhe_plain_bits(lhe_bits, set_id, instance):
+# ---- circuit-bootstrap nodes among gates -------------------------------------------------------------------------------------------
+def cb_lookup_dag(cir, a_wires, b_wires, table, p_out=8, d_tree=0, encode=None):
+    """cb_lookup as one circuit: a_wires, b_wires hold the gate bits of two d-bit numbers (low bit first; d = log2(len(table))), the address is
+    a XOR b -- d XOR gates --, a CB node turns the XOR outputs into TGSW bits and an LHE_LOOKUP node at (d_tree, d - d_tree) reads `table`
+    (integers in [0, p_out); encode: integers -> Torus32 words, default thfhe.lut.encode at modulus p_out).  Returns the output wire; the plain twin
+    is cb_lookup_plain."""
+    from . import lut
+    t = np.asarray(table, np.int64).reshape(-1)
+    d = t.shape[0].bit_length() - 1
+    a_wires, b_wires = list(a_wires), list(b_wires)
+    if not 1 <= d <= 16 or t.shape[0] != 1 << d or len(a_wires) != d or len(b_wires) != d or not 0 <= d_tree <= min(d, 6) or d - d_tree > 10:
+        raise ValueError("table: expected 2^d entries, d wires per operand, 0 <= d_tree <= 6 and d - d_tree <= 10")
+    addr = [cir.gate(XOR, a, b) for a, b in zip(a_wires, b_wires)]
+    tset = cir.cb_set(addr)
+    row0 = cir.lhe_table(lut.lhe_table(t, d_tree, d - d_tree, encode=encode or (lambda v: lut.encode(v, p_out))))
+    return cir.lhe_lookup(tset, row0, d_tree, d - d_tree)[0]
+
+
+def cb_array_read(cir, wires, index_wires, d_tree, d_rot):
+    """lhe_array_read at an index the circuit computed: wires[index] for the index whose gate bits are index_wires (low bit first,
+    d_tree + d_rot of them, len(wires) = 2^(d_tree + d_rot)); a CB node makes the TGSW bits.  Returns the output wire."""
+    index_wires = list(index_wires)
+    if len(index_wires) != d_tree + d_rot:
+        raise ValueError("cb_array_read: expected d_tree + d_rot index wires")
+    wires = [int(w) for w in wires]
+    if wires != list(range(wires[0], wires[0] + len(wires))):   # before the CB node, so that it shares their level
+        wires = [cir.gate(COPY, w) for w in wires]
+    return lhe_array_read(cir, wires, cir.cb_set(index_wires), d_tree, d_rot)
+
+
+def cb_mux_max(cir, a_wires, b_wires, width, N=1024):
+    """wfa_mux_max without the client's TGSW copy of the operands: max(a, b) of two `width`-bit numbers the circuit holds as gate bits (MSB first,
+    width <= 8): ONE CB node makes a computed set of 2 width bits (a's low bit first, then b's), the automaton wfa_less_than reads it and drives
+    `width` MUX gates.  Returns the wires of the maximum, MSB first."""
+    a_wires, b_wires = list(a_wires), list(b_wires)
+    if not 1 <= width <= 8 or len(a_wires) != width or len(b_wires) != width:
+        raise ValueError("cb_mux_max: expected `width` <= 8 wires per number")
+    tset = cir.cb_set(a_wires[::-1] + b_wires[::-1])
+    trans, _, finals, start = wfa_less_than(width)
+    step_bit = np.array([(j & 1) * width + (j >> 1) for j in range(2 * width)], np.int32)   # a_i, b_i, low bit first, all in the one set
+    fin = np.zeros((trans.shape[1], N), np.int32)
+    fin[:, 0] = np.where(np.asarray(finals)[0] == 1, 1 << 29, -(1 << 29))
+    lt = cir.lhe_wfa((trans, step_bit, finals, start), [tset], cir.lhe_finals(fin))[0]
+    return [cir.gate(MUX, lt, b, a) for a, b in zip(a_wires, b_wires)]
+
+
+def _lhe_plain_bits(lhe_bits, set_id, instance, computed=None):
+    if set_id >= CB_SET_BASE:   # a computed set: the bits simulate derived from the wires
+        return computed[set_id - CB_SET_BASE]
     if lhe_bits is None or set_id >= len(lhe_bits):
         raise ValueError("simulate: the circuit holds leveled nodes; lhe_bits must give the plain bits of every set")
     b = np.asarray(lhe_bits[set_id], np.int64)
@@ -1086,9 +1198,15 @@ def _simulate_words(cir, input_words, lhe_bits=None, instance=0):
     wrap = lambda t: ((int(t) + (1 << 31)) % (1 << 32)) - (1 << 31)
     lin = lambda spec, ws: wrap(sum(int(w) * int(v[i]) for w, i in zip(spec[1], ws)) + spec[2])
     gates_only = Circuit()
+    computed = {}   # computed set -> its plain bits, from the gate-encoded wires
     for gi, (op, a, b, c) in enumerate(cir.gates):
         o = cir.n_inputs + gi
         if op == LUT_OUT:
+            continue
+        if op == CB:
+            wires = cir.cb_specs[cir.cb_rows[gi][0]]
+            computed[cir.cb_rows[gi][0]] = np.array([int(v[w] > 0) for w in wires], np.int64)
+            v[o] = v[wires[0]]
             continue
         if op in (LUT, LUT_ENC):
             si, ti = cir.lut_rows[gi] if op == LUT else cir.ext_rows[gi]
@@ -1125,7 +1243,7 @@ def _simulate_words(cir, input_words, lhe_bits=None, instance=0):
         elif op in (LHE_LOOKUP, LHE_GATHER):
             lk, y = cir.lhe_rows[gi]
             set_id, d_tree, d_rot, theta = cir.lhe_specs[lk]
-            bits = _lhe_plain_bits(lhe_bits, set_id, instance)[:d_tree + d_rot]
+            bits = _lhe_plain_bits(lhe_bits, set_id, instance, computed)[:d_tree + d_rot]
             addr = int(sum(int(bit) << i for i, bit in enumerate(bits)))
             if op == LHE_GATHER:
                 v[o] = v[y + addr]
@@ -1140,7 +1258,7 @@ def _simulate_words(cir, input_words, lhe_bits=None, instance=0):
             trans, step_bit, start, theta, set0, n_sets = cir.wfa_specs[wi]
             state = np.array(start, np.int64)
             for j, sb in enumerate(step_bit):
-                state = trans[j][state, int(_lhe_plain_bits(lhe_bits, set0 + (sb >> 4), instance)[sb & 15])]
+                state = trans[j][state, int(_lhe_plain_bits(lhe_bits, set0 + (sb >> 4), instance, computed)[sb & 15])]
             for k, q in enumerate(state):
                 poly = cir.lhe_fin[y + int(q)][2]
                 if poly is None:
@@ -1160,9 +1278,10 @@ def simulate(cir, input_bits, lhe_bits=None, instance=0):
     """Plaintext evaluation of the DAG (wiring check): bool[n_inputs] -> bool[n_wires].  Circuits with LUT, LUT_ENC, SELECT, TREE, multi-value or
     leveled nodes work on integer digits in their torus encoding: int32[n_inputs] noiseless phase words (thfhe.lut.encode(digit, p); +-2^29 for gate
     bits) -> the noiseless phase word int32[n_wires] of every wire, which thfhe.lut.decode turns into digits.  lhe_bits (circuits with leveled
-    nodes): the plain bits of every TGSW set, low bit first -- int[d] per set, or int[instances][d] of which row `instance` is read."""
+    nodes): the plain bits of every CLIENT TGSW set, low bit first -- int[d] per set, or int[instances][d] of which row `instance` is read; a computed
+    set's bits (Circuit.cb_set) come from its wires, a positive phase word reading as 1."""
     from . import ANDNY, ANDYN, NAND, NOR, ORNY, ORYN, XNOR
-    if cir.lut_rows or cir.ext_rows or cir.mv_rows or cir.lhe_rows:
+    if cir.lut_rows or cir.ext_rows or cir.mv_rows or cir.lhe_rows or cir.cb_rows:
         return _simulate_words(cir, input_bits, lhe_bits, instance)
     v = np.zeros(cir.n_wires(), bool)
     v[:cir.n_inputs] = np.asarray(input_bits, bool)
@@ -1205,9 +1324,9 @@ def simulate_mk(cir, input_bits):
 
 
 # ---- evaluator --------------------------------------------------------------------------------------------------------
-def _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets=None):
+def _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets=None, level2=None, one_rotation=False):
     if ck._tv_dtype == np.int64:   # the 3-gen multi-key engine: gates, LUT and MV nodes (thfhe_mk_dag_run_mv_batch)
-        if cir.has_tree_nodes() or cir.has_lhe_nodes() or any(g[0] == TREE_MV for g in cir.gates):
+        if cir.has_tree_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes() or any(g[0] == TREE_MV for g in cir.gates):
             raise ValueError("the multi-key executor runs gate, LUT and MV nodes only (no tree or encrypted-table rows, no leveled nodes)")
         mvs, tv0, fac = cir.mv_families()
         bias = [cir.mv_out_bias.get(i, 0) for i in range(len(mvs))]
@@ -1217,6 +1336,12 @@ def _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets=None):
     enc = cir.enc_tables
     args = (x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None, np.stack([e[0] for e in enc]) if enc else None,
             np.stack([e[1] for e in enc]) if enc else None, cir.tree_specs, np.stack(cir.tv1) if cir.tv1 else None)
+    if cir.has_cb_nodes():
+        if len(tgsw_sets or ()) < cir.n_lhe_sets():
+            raise ValueError("the circuit holds leveled nodes: tgsw_sets must give the %d TgswSets they name" % cir.n_lhe_sets())
+        names = ("specs", "tv", "enc_a", "enc_b", "trees", "tv1", "mvs", "mv_tv0", "mv_factors")
+        return ck.dag_run_cb_batch(x, cir.nodes(), **cir.cb_families(), one_rotation=one_rotation, level2=level2, **dict(zip(names, args[2:] + tuple(cir.mv_families()))),
+                                   tgsw_sets=list(tgsw_sets or ())[:cir.n_lhe_sets()], **cir.lhe_families(), out_wires=sel, pack=pack)
     if cir.has_lhe_nodes():
         if tgsw_sets is None or len(tgsw_sets) < cir.n_lhe_sets():
             raise ValueError("the circuit holds leveled nodes: tgsw_sets must give the %d TgswSets they name" % cir.n_lhe_sets())
@@ -1226,17 +1351,18 @@ def _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets=None):
     return ck.dag_run_tree_batch(*args, sel, pack)
 
 
-def evaluate(ck, cir, input_records, stats=None, pack=None, tgsw_sets=None):
+def evaluate(ck, cir, input_records, stats=None, pack=None, tgsw_sets=None, level2=None, one_rotation=False):
     """Run the DAG on the engine.  input_records: int32[n_inputs][n+1].  Returns int32[n_wires][n+1].
     Single-key contexts use the native scheduler / executor (thfhe_dag_run: wires stay in HBM, no host round trip per level);
     multi-key contexts go level by level through thfhe_mk_gates_mixed (evaluate_levels).  Circuits with LUT nodes run on
     thfhe_dag_run_lut_batch / thfhe_mk_dag_run_lut_batch, circuits with encrypted-table, select or tree nodes on thfhe_dag_run_tree_batch
     (pack: the threshold.PolyContext holding the packing key), circuits with leveled nodes on thfhe_dag_run_lhe_batch (tgsw_sets: the TgswSets they
-    name; sample 0 is read)."""
-    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes():
+    name; sample 0 is read), circuits with CB nodes on thfhe_dag_run_cb_batch (level2: the level-2 key, default the one cb_key_set named; one_rotation:
+    CloudKey.circuit_bootstrap's)."""
+    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes():
         x = np.ascontiguousarray(input_records, np.int32).reshape(1, cir.n_inputs, ck.words)
-        if cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes():
-            out, st = _run_tree_batch(ck, cir, x, None, pack, tgsw_sets)
+        if cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes():
+            out, st = _run_tree_batch(ck, cir, x, None, pack, tgsw_sets, level2, one_rotation)
         else:
             out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir))
         if stats is not None:
@@ -1250,20 +1376,21 @@ def evaluate(ck, cir, input_records, stats=None, pack=None, tgsw_sets=None):
     return evaluate_levels(ck, cir, input_records, stats)
 
 
-def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None, pack=None, tgsw_sets=None):
+def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None, pack=None, tgsw_sets=None, level2=None, one_rotation=False):
     """`instances` evaluations of one DAG side by side.  input_records: int32[instances][n_inputs][words]; out_wires: wire ids to return
     (None: every wire).  Returns int32[instances][len(out_wires) or n_wires][words].  Contexts with the native executor use
     thfhe_dag_run_batch / thfhe_mk_dag_run_batch (wire tables stay in HBM), circuits with LUT nodes thfhe_dag_run_lut_batch /
     thfhe_mk_dag_run_lut_batch, circuits with encrypted-table, select or tree nodes thfhe_dag_run_tree_batch (pack: the threshold.PolyContext
     holding the packing key), circuits with leveled nodes thfhe_dag_run_lhe_batch (tgsw_sets: the TgswSets they name, instance q reads sample q);
-    others are driven level by level from the host, a level's call holding the gates of all instances."""
+    circuits with CB nodes thfhe_dag_run_cb_batch (level2, one_rotation: as evaluate); others are driven level by level from the host, a level's call
+    holding the gates of all instances."""
     x = np.ascontiguousarray(input_records, np.int32)
     Q, n_in, words = x.shape
     assert n_in == cir.n_inputs
-    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or hasattr(ck, "dag_run_batch"):
+    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes() or hasattr(ck, "dag_run_batch"):
         sel = None if out_wires is None else np.asarray(out_wires, np.int32)
-        if cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes():
-            out, st = _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets)
+        if cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes():
+            out, st = _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets, level2, one_rotation)
         elif cir.has_luts():
             out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir), sel)
         else:
@@ -1359,12 +1486,13 @@ def _levels_mv(ck, cir, level, vals, pack):
     return len(by)
 
 
-def _levels_lhe(ck, cir, level, vals, pack, tgsw_sets, instance):
+def _levels_lhe(ck, cir, level, vals, pack, tgsw_sets, instance, computed=None):
     """The leveled nodes of one level through the public flat calls on sample `instance` of the sets (lhe_lookup; PackBoxes + lhe_lookup; lhe_wfa),
-    one call per node; returns the number of calls."""
+    one call per node; returns the number of calls.  computed: the one-sample TgswSets circuit_bootstrap made of the CB nodes above (sample 0 is read)."""
     from .threshold import PackBoxes
     gates, base, calls = cir.gates, cir.n_inputs, 0
     fam = cir.lhe_families()
+    pick = lambda s: (computed[s - CB_SET_BASE], 0) if s >= CB_SET_BASE else (tgsw_sets[s], instance)
     for g in level:
         op = gates[g][0]
         if op not in _LHE_OPS:
@@ -1374,8 +1502,8 @@ def _levels_lhe(ck, cir, level, vals, pack, tgsw_sets, instance):
         if op == LHE_WFA:
             trans, step_bit, start, theta, set0, n_sets = cir.wfa_specs[x]
             n = trans.shape[1]
-            r = ck.lhe_wfa(list(tgsw_sets[set0:set0 + n_sets]), trans, step_bit, fam["fin_b"][y:y + n], start, theta=theta,
-                           fin_a=None if fam["fin_a"] is None else fam["fin_a"][y:y + n], first=instance, count=1)
+            r = ck.lhe_wfa([pick(s)[0] for s in range(set0, set0 + n_sets)], trans, step_bit, fam["fin_b"][y:y + n], start, theta=theta,
+                           fin_a=None if fam["fin_a"] is None else fam["fin_a"][y:y + n], first=pick(set0)[1], count=1)
             vals[base + g:base + g + start.shape[0] * theta] = r[0].reshape(-1, r.shape[-1])
             continue
         set_id, d_tree, d_rot, theta = cir.lhe_specs[x]
@@ -1384,24 +1512,38 @@ def _levels_lhe(ck, cir, level, vals, pack, tgsw_sets, instance):
         else:
             tab_b = fam["tab_b"][y:y + (1 << d_tree)]
             tab_a = None if fam["tab_a"] is None else fam["tab_a"][y:y + (1 << d_tree)]
-        r = ck.lhe_lookup(tgsw_sets[set_id], tab_b, d_tree=d_tree, d_rot=d_rot, theta=theta, tab_a=tab_a, first=instance, count=1)
+        r = ck.lhe_lookup(pick(set_id)[0], tab_b, d_tree=d_tree, d_rot=d_rot, theta=theta, tab_a=tab_a, first=pick(set_id)[1], count=1)
         vals[base + g:base + g + theta] = r[0]
     return calls
 
 
-def evaluate_levels(ck, cir, input_records, stats=None, pack=None, tgsw_sets=None, instance=0):
+def evaluate_levels(ck, cir, input_records, stats=None, pack=None, tgsw_sets=None, instance=0, level2=None, one_rotation=False):
     """The same schedule driven from the host: one host-buffer call per level (works for single-key and multi-key contexts).  LUT nodes go
     through ck.lut_bootstrap, one call per (theta, spec) of a level: the yardstick of the native LUT-node executor.  LUT_ENC, SELECT and TREE nodes
     go through lut_bootstrap_enc, PackBoxes + lut_bootstrap_enc and tree_lut_bootstrap (pack: the packing context): the yardstick of
     thfhe_dag_run_tree_batch.  MV and TREE_MV nodes go through mv_lut_bootstrap and tree_lut_bootstrap_mvk: the yardstick of thfhe_dag_run_mv_batch.
-    Leveled nodes go through lhe_lookup, PackBoxes + lhe_lookup and lhe_wfa on sample `instance` of tgsw_sets: the yardstick of thfhe_dag_run_lhe_batch."""
-    from . import AND3 as _AND3
+    Leveled nodes go through lhe_lookup, PackBoxes + lhe_lookup and lhe_wfa on sample `instance` of tgsw_sets: the yardstick of thfhe_dag_run_lhe_batch.
+    A CB node goes through circuit_bootstrap of its wires' records (one sample; one_rotation: its mode; level2 is the key's own, cb_key_set's), the
+    leveled nodes that read it through the flat calls on that set: the yardstick of thfhe_dag_run_cb_batch."""
     words = ck.words
     vals = np.zeros((cir.n_wires(), words), np.int32)
     vals[:cir.n_inputs] = np.asarray(input_records, np.int32).reshape(cir.n_inputs, words)
-    gates = cir.gates
-    base = cir.n_inputs
-    launches = 0
+    computed = {}  # computed set -> the one-sample TgswSet circuit_bootstrap made of it
+    try:
+        launches = _evaluate_levels(ck, cir, vals, pack, tgsw_sets, instance, one_rotation, computed)
+    finally:
+        for t in computed.values():
+            t.close()
+    if stats is not None:
+        stats.update(cir.census(), launches=launches)
+    return vals
+
+
+def _evaluate_levels(ck, cir, vals, pack, tgsw_sets, instance, one_rotation, computed):
+    """evaluate_levels' walk over the levels, into vals; the TgswSets it makes of CB nodes go into `computed`, which the caller closes.  Returns the
+    number of host-buffer calls."""
+    from . import AND3 as _AND3
+    gates, base, launches = cir.gates, cir.n_inputs, 0
     for level in cir.levels():
         op0 = gates[level[0]][0]
         if op0 in (NOT, COPY):
@@ -1429,8 +1571,14 @@ def evaluate_levels(ck, cir, input_records, stats=None, pack=None, tgsw_sets=Non
         if cir.mv_rows:
             launches += _levels_mv(ck, cir, level, vals, pack)
         if cir.lhe_rows:
-            launches += _levels_lhe(ck, cir, level, vals, pack, tgsw_sets, instance)
-        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT, LUT_ENC, SELECT, TREE, MV, TREE_MV) + _LHE_OPS]
+            launches += _levels_lhe(ck, cir, level, vals, pack, tgsw_sets, instance, computed)
+        for g in level:
+            if gates[g][0] == CB:
+                wires = cir.cb_specs[cir.cb_rows[g][0]]
+                computed[cir.cb_rows[g][0]] = ck.circuit_bootstrap(vals[wires], len(wires), one_rotation=one_rotation)
+                vals[base + g] = vals[wires[0]]
+                launches += 1
+        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT, LUT_ENC, SELECT, TREE, MV, TREE_MV, CB) + _LHE_OPS]
         mux = [g for g in level if gates[g][0] == MUX]
         and3 = [g for g in level if gates[g][0] == _AND3]   # 3-gen three-input AND: its own gate class (thfhe_mk_gates)
         if and3:
@@ -1449,6 +1597,4 @@ def evaluate_levels(ck, cir, input_records, stats=None, pack=None, tgsw_sets=Non
             c = vals[[gates[g][3] for g in mux]]
             vals[base + np.array(mux)] = ck.gates(MUX, a, b, c)
             launches += 1
-    if stats is not None:
-        stats.update(cir.census(), launches=launches)
-    return vals
+    return launches
