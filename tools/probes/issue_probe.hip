@@ -8,7 +8,7 @@
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 
-enum Role { NONE = 0, F64_IND, F64_DEP, I32_IND, MIX_IND, DPP_IND, F64_DEP2, F64_DEP4 };
+enum Role { NONE = 0, F64_IND, F64_DEP, I32_IND, MIX_IND, DPP_IND, F64_DEP2, F64_DEP4, SWAP32_IND, SWAP16_IND };
 
 template <int ROLE>
 __device__ __forceinline__ void body(double (&a)[8], unsigned (&u)[8], double c, int iters) {
@@ -23,6 +23,9 @@ __device__ __forceinline__ void body(double (&a)[8], unsigned (&u)[8], double c,
                 if (ROLE == F64_DEP4) asm volatile("v_fma_f64 %0, %0, %1, %0" : "+v"(a[q & 3]) : "v"(c));
                 if (ROLE == I32_IND) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(u[q]) : "v"(u[(q + 1) & 7]));
                 if (ROLE == DPP_IND) asm volatile("v_mov_b32_dpp %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf" : "+v"(u[q]));
+                // lane swaps on four independent register pairs (the two swap stages of wave_transpose_hi3 / wave_transpose_x3)
+                if (ROLE == SWAP32_IND) asm volatile("v_permlane32_swap_b32 %0, %1" : "+v"(u[2 * (q & 3)]), "+v"(u[2 * (q & 3) + 1]));
+                if (ROLE == SWAP16_IND) asm volatile("v_permlane16_swap_b32 %0, %1" : "+v"(u[2 * (q & 3)]), "+v"(u[2 * (q & 3) + 1]));
                 if (ROLE == MIX_IND) {
                     if (q & 1) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(u[q]) : "v"(u[(q + 1) & 7]));
                     else asm volatile("v_fma_f64 %0, %0, %1, %0" : "+v"(a[q]) : "v"(c));
@@ -80,6 +83,8 @@ int main() {
     run<I32_IND, NONE>("one wave/SIMD: int32 independent", 0);
     run<DPP_IND, NONE>("one wave/SIMD: dpp mov", 0);
     run<MIX_IND, NONE>("one wave/SIMD: fp64 / int32 alternating", 0);
+    run<SWAP32_IND, NONE>("one wave/SIMD: v_permlane32_swap", 0);
+    run<SWAP16_IND, NONE>("one wave/SIMD: v_permlane16_swap", 0);
     run<F64_IND, F64_IND>("two waves/SIMD: fp64 | fp64", 1);
     run<F64_IND, I32_IND>("two waves/SIMD: fp64 | int32", 1);
     run<I32_IND, I32_IND>("two waves/SIMD: int32 | int32", 1);
@@ -87,5 +92,9 @@ int main() {
     run<F64_DEP, F64_DEP>("two waves/SIMD: fp64 dep | fp64 dep", 1);
     run<F64_IND, DPP_IND>("two waves/SIMD: fp64 | dpp", 1);
     run<F64_DEP, I32_IND>("two waves/SIMD: fp64 dep | int32", 1);
+    run<F64_IND, SWAP32_IND>("two waves/SIMD: fp64 | v_permlane32_swap", 1);
+    run<F64_IND, SWAP16_IND>("two waves/SIMD: fp64 | v_permlane16_swap", 1);
+    run<SWAP32_IND, SWAP32_IND>("two waves/SIMD: swap32 | swap32", 1);
+    run<DPP_IND, DPP_IND>("two waves/SIMD: dpp | dpp", 1);
     return 0;
 }

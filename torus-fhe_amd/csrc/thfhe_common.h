@@ -225,25 +225,80 @@ __device__ __forceinline__ void wave_fft_fwd_q(int lane, cplx (&z)[8], cplx *xb,
     wave_sync();
     fwd_seg3(lane, z, xb);
 }
-// variant "f": the exchanges of "q", every inter-pass twiddle folded into the butterflies of the following pass (thfhe_lane.h)
-__device__ __forceinline__ void wave_fft_fwd_f(int lane, cplx (&z)[8], cplx *xb, const LaneRootsF &r) {
+// variant "x" (the ring kernel; thfhe_lane.h): the exchange of register bits (2, 1, 0) with lane bits (3, 5, 4).  Its own inverse.  The two swap
+// stages are the expensive ones: a lane swap holds the vector pipe about twice as long as a DPP move (tools/probes/issue_probe.hip: 9.25 against
+// 5.0 cycles per instruction for a wave alone, 13.0 against 8.9 beside an FP64 wave), and there is one per dword pair either way.
+//   lane bit 3 <-> register bit 2   FLIPPED: one unmasked row_ror:8 move per dword of registers 4 .. 7 (16 instructions; the lanes with bit 3 set
+//                                   hold the pairs (r, r + 4) the other way round, before and after); else the two masked moves and the kept copy
+//                                   of wave_transpose_hi3<true> on the pairs (r, r + 4) (32 moves + one 64-bit copy per double)
+//   lane bit 5 <-> register bit 1   v_permlane32_swap
+//   lane bit 4 <-> register bit 0   v_permlane16_swap
+template <bool FLIPPED>
+__device__ __forceinline__ void wave_transpose_x3(cplx (&z)[8]) {
+    uint32_t w[8][4];
+#pragma unroll
+    for (int r = 0; r < 8; r++) __builtin_memcpy(w[r], &z[r], 16);
+    if constexpr (FLIPPED) {
+#pragma unroll
+        for (int r = 4; r < 8; r++)
+#pragma unroll
+            for (int d = 0; d < 4; d++) w[r][d] = __builtin_amdgcn_update_dpp(w[r][d], w[r][d], 0x128, 0xF, 0xF, false);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                uint64_t keep = (uint64_t)w[r + 4][2 * k] | (uint64_t)w[r + 4][2 * k + 1] << 32;
+                asm("" : "+v"(keep));
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int d = 2 * k + h;
+                    const uint32_t a = w[r][d], b = w[r + 4][d], kept = (uint32_t)(keep >> (32 * h));
+                    w[r + 4][d] = __builtin_amdgcn_update_dpp(b, a, 0x128, 0xF, 0x3, false);
+                    w[r][d] = __builtin_amdgcn_update_dpp(a, kept, 0x128, 0xF, 0xC, false);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            if (r & 2) continue;
+            auto q = __builtin_amdgcn_permlane32_swap(w[r][d], w[r + 2][d], false, false);
+            w[r][d] = q[0];
+            w[r + 2][d] = q[1];
+        }
+#pragma unroll
+        for (int r = 0; r < 8; r += 2) {
+            auto q = __builtin_amdgcn_permlane16_swap(w[r][d], w[r + 1][d], false, false);
+            w[r][d] = q[0];
+            w[r + 1][d] = q[1];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 8; r++) __builtin_memcpy(&z[r], w[r], 16);
+}
+// r = the forward roots of lane_nu(lane); spectra come out at lane nu, register k2
+__device__ __forceinline__ void wave_fft_fwd_x(int lane, cplx (&z)[8], cplx *xb, const LaneRootsF &r) {
     fwdf_seg1(z);
-    wave_transpose_hi3<true>(z);
+    wave_transpose_x3<false>(z);
     wave_sync();
-    fwdf_seg2_st(lane, z, xb, r);
+    fwdx_seg2_st(lane, z, xb, r);
     wave_sync();
     fwdf_seg3(lane, z, xb, r);
 }
-template <bool LEAN>   // LEAN: the two roots are made opaque (in place) per transform, so that their powers are neither shared between transforms nor hoisted
-__device__ __forceinline__ void wave_fft_inv_f(int lane, cplx (&z)[8], cplx *xb, W64 &w, LaneRoots &r, const cplx (&bc)[4]) {
+// w = lane_w64_x, r = lane_roots_x, bc = make_untwist_x(r.b, flip); outputs: the coefficients nu + 64 m of lane nu = lane_nu(lane)
+template <bool LEAN>
+__device__ __forceinline__ void wave_fft_inv_x(int lane, cplx (&z)[8], cplx *xb, W64 &w, LaneRoots &r, uint32_t flip, const cplx (&bc)[4]) {
     if (LEAN) opaque_in_place(w.w1), opaque_in_place(r.s);
     wave_sync();
     invf_seg1(lane, z, xb);
     wave_sync();
     inv_seg2_ld(lane, z, xb);
     invf_seg2(z, w);
-    wave_transpose_hi3<true>(z);
-    invf_seg3(z, r, bc);
+    wave_transpose_x3<true>(z);
+    invx_seg3(z, r, flip, bc);
 }
 // variant "qs" (multi-key kernels, whose LDS has no room for padded buffers): first transpose in registers, pass-1 twiddles from the
 // per-lane roots, second transpose through the XOR-swizzled 512-slot buffer -- one LDS crossing and no T1 table reads per transform

@@ -342,7 +342,8 @@ THFHE_FN void opaque_in_place(cplx &v) {
 #endif
 }
 
-// ---- variant "f" (eight- and four-wave ring kernel): the exchanges of "q", every inter-pass twiddle FOLDED into the butterflies of the
+// ---- variant "f" (the passes of the eight- and four-wave ring kernel, which runs them around the exchange of variant "x" below; whole, with the
+// exchange of "q", in tests/emu/fold_emu.cpp): the exchanges of "q", every inter-pass twiddle FOLDED into the butterflies of the
 // pass that follows it.  A radix-2 butterfly with a twiddle on its second input,
 //     x = a + W b   (two dependent FMAs per component),      a - W b = 2 a - x   (one FMA per component),
 // is 6 FP64 instructions; the separate product (2 mul + 2 fma) followed by the add / sub pair is 8.  Every twiddle set of the transform is
@@ -448,6 +449,69 @@ THFHE_FN void invf_seg2(cplx (&z)[8], const W64 &w) { dft8_tw<-1>(z, root_powers
 THFHE_FN void invf_seg3(cplx (&z)[8], const LaneRoots &r, const cplx (&bc)[4]) {                        // after the lane exchange: pass over k0, root conj(s)
     constexpr double R = 0.70710678118654752440;
     dft8_tw<-1>(z, root_powers<-1>(cconj(r.s)));
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        z[m] = cmul_conj(z[m], bc[m]);
+        z[m + 4] = cmul_conj(cplx{R * (z[m + 4].re + z[m + 4].im), R * (z[m + 4].im - z[m + 4].re)}, bc[m]);
+    }
+}
+
+// ---- variant "x" (the ring kernel): the transforms of "f" around a lane exchange whose lane-bit-3 stage pairs the registers (r, r + 4) -- the
+// pairs that the LAST radix-2 stage of a pass writes and the FIRST stage of the next pass reads (wave_transpose_x3 in thfhe_common.h).
+// Lane map.  The exchange swaps register bits (2, 1, 0) with lane bits (3, 5, 4), so on the spectrum side (and on the inverse's coefficient side) a
+// lane's upper index is  hi = (lane bit 3) << 2 | lane bits 5..4, and the lane stands for the natural position nu = (lane & 7) + 8 hi: roots, key
+// reads (B[m * 64 + nu]: still one 256-byte row per ds_read_b128 lane group) and acc_update16 take nu, the private transpose buffer takes the lane.
+// The key spectra and their order in memory are those of every other form.
+// Inverse: the stage is ONE unmasked row_ror:8 move per dword of registers 4 .. 7.  That is an exchange when the lanes with bit 3 set name the pairs
+// (r, r + 4) the other way round (physical r holds logical r ^ 4), before and after.
+//   before  the pass over k1 writes its outputs shifted by four, X_(k + 4) into register k, when its root is NEGATED: (-W)^m = W^m w8^(4 m).  The
+//           root conj(w64^j0) is a loaded per-lane constant; those lanes load its negative (lane_w64_x).  Its powers W^2, W^4 do not see the sign,
+//           W w8 carries it; no instruction is added and every butterfly rounds as before, with the two outputs of a last-stage pair exchanged.
+//   after   the pass over k0 finds y_(m + 4) where y_m should be.  With conj(W^4) in place of W^4 its first stage gives
+//               y_(m+4) + conj(W^4) y_m = conj(W^4) u_m,      y_(m+4) - conj(W^4) y_m = -conj(W^4) v_m        (|W| = 1)
+//           and the u / v halves become the even / odd outputs: X'_j = conj(W^4) (-1)^j X_j, W = conj(s), s = zeta^(4 nu).  The untwist is a product
+//           with per-lane constants anyway: those lanes build it from b s^4 = zeta^(17 nu) (= T1[4][nu], exact from the table) and negate the odd
+//           ones (make_untwist_x).  Cost per transform: one XOR on the sign of Im W^4.
+// Forward: the same pairing with the masked moves of "q" (natural names on every lane).  The unmasked stage is NOT taken there: the pass after the
+// exchange would leave the factor conj(s'^4) = rho^(-32) (rho the spectrum point's root) on the spectra of half the lanes; a folded pass cannot
+// absorb a scalar, the key must not carry it, and taking it out in the inverse's first stage costs three complex products per inverse transform.
+THFHE_FN int lane_nu(int lane) { return (lane & 7) | ((lane & 8) << 2) | ((lane & 0x30) >> 1); }
+THFHE_FN uint32_t lane_flip_x(int lane) { return (lane & 8) ? 0x80000000u : 0u; }   // XORed into the high word of a double: its sign on the lanes with bit 3 set
+THFHE_FN double flip_sign(double v, uint32_t flip) {
+    uint64_t b;
+    __builtin_memcpy(&b, &v, 8);
+    b ^= (uint64_t)flip << 32;
+    __builtin_memcpy(&v, &b, 8);
+    return v;
+}
+THFHE_FN W64 lane_w64_x(cplx w64_j0, uint32_t flip) { return W64{cplx{flip_sign(w64_j0.re, flip), flip_sign(w64_j0.im, flip)}}; }
+// per-lane constants of the inverse: b = zeta^nu (lanes with bit 3 set: zeta^(17 nu)), s = zeta^(4 nu); tw = the TwRing1k table
+template <typename WPtr>
+THFHE_FN LaneRoots lane_roots_x(const WPtr tw, int t1_base, int roots_base, int lane) {
+    const int nu = lane_nu(lane);
+    return LaneRoots{(lane & 8) ? tw[t1_base + 4 * 64 + nu] : tw[roots_base + 2 * nu], tw[roots_base + 2 * nu + 1]};
+}
+THFHE_FN void make_untwist_x(cplx b, uint32_t flip, cplx (&bc)[4]) {
+    make_untwist_f(b, bc);
+    bc[1] = cplx{flip_sign(bc[1].re, flip), flip_sign(bc[1].im, flip)};
+    bc[3] = cplx{flip_sign(bc[3].re, flip), flip_sign(bc[3].im, flip)};
+}
+// register j1 of the pass after the forward exchange sits in physical register (j1 bit 0) << 2 | (j1 bit 2) << 1 | (j1 bit 1): the exchange
+// leaves lane bits (3, 5, 4) of the natural coefficient lanes, i.e. j1 bits (0, 2, 1), in register bits (2, 1, 0)
+THFHE_FN constexpr int fwdx_phys(int j1) { return ((j1 & 1) << 2) | ((j1 >> 2) & 1) << 1 | ((j1 >> 1) & 1); }
+THFHE_FN void fwdx_seg2_st(int lane, cplx (&z)[8], cplx *xbuf, const LaneRootsF &r) {
+    cplx y[8];
+#pragma unroll
+    for (int j1 = 0; j1 < 8; j1++) y[j1] = z[fwdx_phys(j1)];
+    dft8_tw<+1>(y, root_powers<+1>(r.s));
+#pragma unroll
+    for (int k1 = 0; k1 < 8; k1++) xbuf[xs_c(k1, lane)] = y[k1];
+}
+THFHE_FN void invx_seg3(cplx (&z)[8], const LaneRoots &r, uint32_t flip, const cplx (&bc)[4]) {   // bc from make_untwist_x
+    constexpr double R = 0.70710678118654752440;
+    RootPow p = root_powers<-1>(cconj(r.s));
+    p.w4.im = flip_sign(p.w4.im, flip);
+    dft8_tw<-1>(z, p);
 #pragma unroll
     for (int m = 0; m < 4; m++) {
         z[m] = cmul_conj(z[m], bc[m]);

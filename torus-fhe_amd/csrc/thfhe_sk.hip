@@ -149,8 +149,14 @@ constexpr int kGate = 0, kLut = 1, kLutEnc = 2, kLutMv = 3;
 // vector pipe for 4 cycles).  Per 4096 gates 34.8 -> 33.3 -> 29.9 -> 28.7 -> 27.70 ms; the forms that were tried and lost are in
 // profiles/r03_ring_variants.md and r04_ring_multiply_phase.md.
 //   * the FIRST transpose of every transform (register index <-> lane bits 3..5) stays in registers: v_permlane32_swap, v_permlane16_swap and
-//     row_ror:8 DPP moves (wave_transpose_hi3) instead of 8 ds_write_b128 + 8 ds_read_b128; the kept side of its half-row swap is one 64-bit move
-//     per double (wave_transpose_hi3<KEEP64>);
+//     row_ror:8 DPP moves instead of 8 ds_write_b128 + 8 ds_read_b128.  It is the exchange of variant "x" (wave_transpose_x3; thfhe_lane.h): lane
+//     bit 3 trades with register bit 2, the pairs (r, r + 4) that a pass writes last and reads first.  In the inverse transforms that stage is 16
+//     unmasked moves: the lanes with bit 3 set name those pairs the other way round, which a negated per-lane root produces and conj(W^4), a
+//     signed and rescaled untwist constant consume -- 24 instructions fewer per transform than two masked moves and a kept 64-bit copy per
+//     double, which the forward transforms keep (a folded pass cannot absorb the scalar the flipped names would leave on the spectra).  A lane
+//     therefore stands for the natural position nu = lane_nu(lane) from the forward exchange on: key reads, roots and acc_update16 take nu; the
+//     key's order in memory and in the ring is untouched.  1 311 -> 1 223 other vector instructions per CMux and wave, 252 -> 248 VGPRs,
+//     27.74 -> 27.33 ms per 4096 gates (profiles/r11_exchange.md);
 //   * the second transpose uses the padded 576-slot buffer (there is no T1 table in the LDS, its 8 KiB pay for the padding): its slot maps are
 //     base + immediate, 2 LDS address registers per wave instead of 16 for XOR-swizzled maps;
 //   * no twiddle is read from a table: the transforms are variant "f" (thfhe_lane.h).  Every inter-pass twiddle sits on the input side of the pass
@@ -187,9 +193,12 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     // the roots are variables: opaque_in_place makes them loop-carried in the registers they already occupy
-    W64 w64{a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)]};                                               // inverse transforms
-    LaneRoots roots{a.tw[TwRing1k::ROOTS + 2 * lane], a.tw[TwRing1k::ROOTS + 2 * lane + 1]};
-    LaneRootsF rootsf{a.tw[TwRing1k::ROOTSF + 2 * lane], a.tw[TwRing1k::ROOTSF + 2 * lane + 1]};   // forward transforms
+    // variant "x" (thfhe_lane.h): past the forward exchange the lane stands for the natural position nu; the lanes with bit 3 set carry the flipped names
+    const int nu = lane_nu(lane);
+    const uint32_t flip = lane_flip_x(lane);
+    W64 w64 = lane_w64_x(a.tw[TwRing1k::T2 + 1 * 8 + (lane & 7)], flip);                        // inverse transforms
+    LaneRoots roots = lane_roots_x(a.tw, TwRing1k::T1, TwRing1k::ROOTS, lane);
+    LaneRootsF rootsf{a.tw[TwRing1k::ROOTSF + 2 * nu], a.tw[TwRing1k::ROOTSF + 2 * nu + 1]};   // forward transforms
     const long job = (long)blockIdx.x * W + wave;
     const bool has_job = job < a.jobs;
     int32_t *acc = sAcc[wave];
@@ -258,7 +267,7 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
                 // measured 30.21 -> 29.97 ms per 4096 gates, 44 -> 0 B of scratch per lane, when it was introduced (on the transforms before these;
                 // DESIGN 4.1, profiles/r04_summary.md).  The four-wave shape has registers to spare and lets the compiler keep what it likes.
                 if (W == 8) opaque_in_place(rootsf.s), opaque_in_place(rootsf.w);
-                wave_fft_fwd_f(lane, z, xb, rootsf);
+                wave_fft_fwd_x(lane, z, xb, rootsf);
             }
             STAMP(0);
             cplx bA[4], bB[4];
@@ -268,13 +277,13 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
                 const cplx *B = slot_ptr(RS::kPlan[c4].slot);
                 if (active) {
 #pragma unroll
-                    for (int m = 0; m < 4; m++) bA[m] = B[m * 64 + lane];
+                    for (int m = 0; m < 4; m++) bA[m] = B[m * 64 + nu];
                     if (c4 > 0) {
 #pragma unroll
                         for (int m = 0; m < 4; m++) cfma_negkey(S[(c4 - 1) >> 1][(c4 - 1) & 1][4 + m], z[4 + m], bB[m]);
                     }
 #pragma unroll
-                    for (int m = 0; m < 4; m++) bB[m] = B[(4 + m) * 64 + lane];
+                    for (int m = 0; m < 4; m++) bB[m] = B[(4 + m) * 64 + nu];
 #pragma unroll
                     for (int m = 0; m < 4; m++) cfma_negkey(S[c4 >> 1][c4 & 1][m], z[m], bA[m]);
                 }
@@ -311,12 +320,12 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
             // kept across the multiply phase
             cplx bc[4];
             if (W == 8) opaque_in_place(roots.b);
-            make_untwist_f(roots.b, bc);
+            make_untwist_x(roots.b, flip, bc);
 #pragma unroll
             for (int c = 0; c < 2; c++) {
-                wave_fft_inv_f<W == 8>(lane, S[c][0], xb, w64, roots, bc);
-                wave_fft_inv_f<W == 8>(lane, S[c][1], xb, w64, roots, bc);
-                acc_update16(lane, acc + c * 1024, S[c][0], S[c][1]);
+                wave_fft_inv_x<W == 8>(lane, S[c][0], xb, w64, roots, flip, bc);
+                wave_fft_inv_x<W == 8>(lane, S[c][1], xb, w64, roots, flip, bc);
+                acc_update16(nu, acc + c * 1024, S[c][0], S[c][1]);
             }
             wave_sync();
         }
