@@ -751,6 +751,50 @@ int thfhe_mk_tree_lut_bootstrap(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec_lo
                                 int32_t *out /*[count][P*n+1]*/, size_t count);
 int thfhe_mk_set_tree_slice(thfhe_mk_ctx *ctx, size_t max_candidates);
 
+/* ---- multi-value two-digit trees on the 3-gen engine: thfhe_tree_lut_bootstrap_mvk restated on Torus64, every parameter family.
+ *
+ * thfhe_mk_tree_lut_bootstrap_mvk: out[s][j] = f_{t,j}(hi_s, lo_s), j < k, t = table_index[s], in 1 + k rotations per sample.  Three stages per slice
+ *   on the context's stream, nothing between them visits the host: ONE multi-value rotation on `lo` with q = k p_hi outputs (output j p_hi + h is
+ *   candidate h of table j; out_bias, a Torus64 word, is added to every body word before its conversion), no key switch; the box packing of the
+ *   [N+1] records with p = p_hi and the D = N key (table (s, j) is packed sample s k + j); k theta = 1 rotations per sample on `hi`, extraction at
+ *   coefficient 0 and the multi-key key switch.  Both specs theta = 1; p_lo, p_hi powers of two in 2 .. 64; 1 <= k, k p_hi <= 64; tv0 HOST int64[N]
+ *   (thfhe.lut.tree_mvk_factors(..., torus_bits=64)); factors HOST int32[n_tables][k][p_hi][p_lo], 1 <= n_tables <= 1024; table_index HOST
+ *   int32[count] or NULL; lo*, hi* HOST int32[count][P*n+1]; out HOST int32[count][k][P*n+1], which must not alias an input.
+ *   The result equals, word for word, thfhe_mk_mv_lut_bootstrap_wo_keyswitch(spec_lo, tv0, factors, p = p_lo, q = k p_hi, ..., out_bias) ->
+ *   thfhe_mk_pack_boxes(p = p_hi) -> thfhe_mk_lut_bootstrap_enc(spec_hi) with each sample's `hi` operands repeated k times and lut_index = 0 ..
+ *   count k - 1.  THFHE_E_INVALID, on the host before the context is looked at: null pointers, an invalid spec, a theta != 1, a bad p_lo, p_hi, k or
+ *   n_tables, a table_index entry out of range, out aliasing an input; then no packing key, a packing key with D != N.  count 0 returns THFHE_OK
+ *   after those.  Slices of max(1, max_candidates / (k p_hi)) samples (thfhe_mk_set_tree_slice); per slice one level-1 accumulator per sample, per
+ *   candidate its record and its sum, S k tables.  With profiling on, thfhe_mk_last_timings gives ms[0] = level 1 with its epilogue, ms[1] =
+ *   packing, ms[2] = selection of the LAST slice and ms[3] = the three together.
+ *
+ * thfhe_mk_set_pack_wide_threshold: packing calls of at least min_records records (per slice; thfhe_mk_pack_boxes and both trees) run
+ *   mk_pack_rows_wide_kernel, which fetches a key row once per 32 records; smaller ones the direct mk_pack_rows_kernel.  0 = never; default 4096, the
+ *   smallest measured size from which the wide kernel is the faster on every measured key.  Both kernels give the same words.  thfhe_mk_pack_kernel_name: the rows kernel a packing of `count` records runs, see thfhe_rotation_kernel_name. */
+int thfhe_mk_tree_lut_bootstrap_mvk(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, int p_lo, int k,
+                                    const int64_t *tv0 /*[N]*/, const int32_t *factors /*[n_tables][k][p_hi][p_lo]*/, int n_tables,
+                                    const int32_t *table_index, int64_t out_bias, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2,
+                                    const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out /*[count][k][P*n+1]*/, size_t count);
+/* thfhe_mk_dag_run_tree_batch: thfhe_mk_dag_run_mv_batch plus three node kinds, the rows meaning what they mean in
+ *   thfhe_dag_run_tree_batch / thfhe_dag_run_mv_batch, restated on Torus64.  (THFHE_LUT_ENC, in0, in1, in2, spec, etab) + theta - 1 LUT_OUT rows:
+ *   thfhe_mk_lut_bootstrap_enc(specs[spec], enc_a[etab], enc_b[etab]); enc_a, enc_b HOST int64[n_enc][N], shared by all instances and uploaded
+ *   once.  (THFHE_TREE, op0, op1, op2, tree, row0): thfhe_mk_tree_lut_bootstrap on tv1[row0 .. row0 + R - 1], tv1 HOST int64[n_tv1_rows][N], p_hi <= 64.
+ *   (THFHE_TREE_MV, op0, op1, op2, mv, t) + k - 1 LUT_OUT rows: thfhe_mk_tree_lut_bootstrap_mvk with mv_out_bias[mv]; wire head + j is its record
+ *   [0][j].  THFHE_SELECT is refused with a message of its own (its candidates would need the D = P*n packing key next to the trees' D = N key,
+ *   and a context holds one).  One level per node; LUT_ENC groups per theta, TREE groups per trees[] index, TREE_MV groups per mvs[] index; both
+ *   prologues read the wire table.  Slices: thfhe_mk_set_dag_slice nodes over all instances and at most max_candidates / p_hi (TREE), max_candidates
+ *   / (k p_hi) (TREE_MV) of them (thfhe_mk_set_tree_slice).  stats (written before the context is looked at): a TREE node counts R + 1 rotations, a
+ *   TREE_MV node 1 + k, each group two launches; a LUT_ENC node one rotation, its group one launch.  Checks before any device work: those of the
+ *   single-key entries for these rows; then, only when the plan holds a TREE or TREE_MV group, a packing key with D = N.  Every other
+ *   thfhe_mk_dag_* entry keeps refusing these opcodes. */
+int thfhe_mk_dag_run_tree_batch(thfhe_mk_ctx *ctx, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                                const thfhe_lut_spec *specs, int n_specs, const int64_t *tv, int n_luts, const int64_t *enc_a, const int64_t *enc_b,
+                                int n_enc, const thfhe_tree_spec *trees, int n_trees, const int64_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs,
+                                int n_mvs, const int64_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words,
+                                const int64_t *mv_out_bias, size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats);
+int thfhe_mk_set_pack_wide_threshold(thfhe_mk_ctx *ctx, size_t min_records);
+int thfhe_mk_pack_kernel_name(const thfhe_mk_ctx *ctx, size_t count, char *buf, int len);
+
 /* ---- leveled nodes in the gate-DAG executor (single key): thfhe_dag_run_mv_batch with three more node kinds that read the client's
  * TGSW-encrypted bits, so that a leveled lookup, a leveled pick among COMPUTED wires and a layered automaton run between gates on the device-resident
  * wire table.  Every argument before `lhe` means what it means in thfhe_dag_run_mv_batch; with lhe = NULL the call is that call.  Instance q of the

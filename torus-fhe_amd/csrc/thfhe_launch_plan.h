@@ -101,6 +101,11 @@ inline int mk_kernel_name(int N, int l, int parts, bool batched, long jobs, long
     default: return std::snprintf(buf, len, "mk_blind_rotate_coop_kernel<%d>", ch.LE);
     }
 }
+// the packing-rows kernel of `records` records (mk_pack_enqueue, thfhe_mk.hip): the wide one from wide_threshold records on, 0 = never
+inline bool mk_pack_wide(size_t records, size_t wide_threshold) { return wide_threshold != 0 && records >= wide_threshold; }
+inline int mk_pack_kernel_name(size_t records, size_t wide_threshold, char *buf, size_t len) {
+    return std::snprintf(buf, len, "%s", mk_pack_wide(records, wide_threshold) ? "mk_pack_rows_wide_kernel" : "mk_pack_rows_kernel");
+}
 inline int ccs_kernel_name(bool wide, char *buf, size_t len) {   // wide: ccs_wide of the context's parameters
     return std::snprintf(buf, len, "%s", wide ? "ccs_blind_rotate_wide_kernel" : "ccs_blind_rotate_kernel");
 }

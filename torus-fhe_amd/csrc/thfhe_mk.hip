@@ -25,6 +25,8 @@
 //   mk_pack_rows_kernel / mk_pack_boxes_kernel / mk_lut_acc_init_enc_kernel (thfhe_mk_pack.h)   the multi-key packing key switch, encrypted tables and
 //                             the two-digit tree (thfhe_mk_pack_boxes, thfhe_mk_lut_bootstrap_enc, thfhe_mk_tree_lut_bootstrap): records ->
 //                             Torus64 RLWE sums under Z = sum_q z_q, box packing of p of them, accumulator start on both polynomials
+//   mk_pack_rows_wide_kernel (thfhe_mk_pack.h)   the row sums of large packings, a key row fetched once per 32 records; with
+//                             mk_extract_mv_kernel as level 1 the multi-value tree thfhe_mk_tree_lut_bootstrap_mvk: 1 + k rotations for k functions
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -964,6 +966,8 @@ struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     DevBuf d_pin, d_pt;                       // a packing call's records and the per-record sums T int64[records][2][N]
     DevBuf d_tab_a, d_tab_b, d_tree_tab;      // a tree slice's packed tables (mask, body) and table indices
     size_t tree_slice = 16384;                // level-1 candidates (samples x p_hi) per slice of a tree or packing call: 2 N x 8 B of d_pt each
+    DevBuf d_dag_enc_a, d_dag_enc_b, d_dag_tv1;   // a gate-DAG run's encrypted tables and level-1 rows (thfhe_mk_dag_run_tree_batch)
+    size_t pack_wide_threshold = kMkPackWideDefault;   // record counts from here on pack with mk_pack_rows_wide_kernel; 0: never
 };
 
 namespace {
@@ -1234,7 +1238,10 @@ int mk_pack_reserve(thfhe_mk_ctx *c, size_t count) { return c->d_pt.grow(count *
 int mk_pack_enqueue(thfhe_mk_ctx *c, const int32_t *d_recs, size_t count, int p, int64_t *d_a, int64_t *d_b) {
     const int N = c->p.N;
     const MkPackArgs a{d_recs, c->d_pk.as<int64_t>(), c->d_pt.as<int64_t>(), (long)count, c->pk_D, c->pk_t, c->pk_basebit, N};
-    hipLaunchKernelGGL(mk_pack_rows_kernel, dim3((unsigned)((count + kMkPackGroup - 1) / kMkPackGroup), (unsigned)(2 * N / kMkPackTile)), dim3(256), 0, c->stream, a);
+    if (launch_plan::mk_pack_wide(count, c->pack_wide_threshold))   // the one place the two rows kernels are chosen between
+        hipLaunchKernelGGL(mk_pack_rows_wide_kernel, dim3((unsigned)((count + kMkPackWideGroup - 1) / kMkPackWideGroup), (unsigned)(2 * N / kMkPackWideTile)), dim3(256), 0, c->stream, a);
+    else
+        hipLaunchKernelGGL(mk_pack_rows_kernel, dim3((unsigned)((count + kMkPackGroup - 1) / kMkPackGroup), (unsigned)(2 * N / kMkPackTile)), dim3(256), 0, c->stream, a);
     const dim3 grid((unsigned)(count / p), 2), block(1024);
     const int64_t *T = c->d_pt.as<int64_t>();
     switch (N) {
@@ -1325,6 +1332,60 @@ int mk_tree_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec &lo, const thfhe_lut
     });
 }
 
+// thfhe_mk_tree_lut_bootstrap_mvk: the tree with level 1 as ONE multi-value rotation per sample and k tables per sample --
+//   level 1    S rotations of the base vector tv0 on the `lo` operands with mk_extract_mv_kernel's q = k p_hi outputs (taps of table[s], out_bias on
+//              the body), no key switch: output j p_hi + h, candidate h of table j, at record s q + j p_hi + h of d_u
+//   packing    mk_pack_enqueue with p = p_hi and the D = N key: table (s, j) is packed sample s k + j
+//   selection  S k theta = 1 rotations, job s k + j on sample s's `hi` operands and its own table, coefficient 0, mk_keyswitch into the staging output
+// One level-1 accumulator per sample; per candidate its record and its sum; S k tables.  The arguments have passed the entry's host checks.
+int mk_tree_mvk_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec &lo, const thfhe_lut_spec &hi, int p_hi, int p_lo, int k, const int64_t *tv0,
+                          const int32_t *factors, int n_tables, const int32_t *table_index, int64_t out_bias, const int32_t *lo0, const int32_t *lo1,
+                          const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const size_t N = c->p.N, words = c->rec_words();
+    if (!c->pk_D) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_mk_pack_key_set)");
+    if (c->pk_D != (int)N) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key must take the ring key's coefficients (D = N)");
+    if (count == 0) return THFHE_OK;
+    const size_t K = (size_t)k, q = K * p_hi;
+    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / q));
+    const size_t w_bytes = (size_t)n_tables * q * p_lo * sizeof(int32_t);
+    int rc = c->d_tv.grow(N * sizeof(int64_t));
+    if (!rc) rc = c->d_mv_w.grow(w_bytes);
+    if (!rc) rc = mk_ensure_workspace(c, S_max, (int)q);   // level 1: S accumulators, S q records
+    if (!rc) rc = mk_ensure_workspace(c, S_max * K, 1);    // selection: S k rotations
+    if (!rc) rc = c->d_lut_idx.grow(S_max * K * sizeof(int32_t));
+    if (!rc) rc = mk_pack_reserve(c, S_max * q);
+    if (!rc) rc = c->d_tab_a.grow(S_max * K * N * sizeof(int64_t));
+    if (!rc) rc = c->d_tab_b.grow(S_max * K * N * sizeof(int64_t));
+    if (!rc) rc = c->stage.grow(S_max * K * words);
+    if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv0, N * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
+    const MkMvArgs mv{c->d_mv_w.as<int32_t>(), p_lo, (int)q, out_bias};
+    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);
+    const LutFlatSrc<LutIdx::table> lo_src{in0, in1, in2, lo, 1, table_index ? c->d_tree_tab.as<int32_t>() : nullptr};
+    const LutFlatSrc<LutIdx::job> hi_src{in0, in1, in2, hi, k, nullptr};
+    return ctx_tree_sliced(c, count, S_max, lo, hi, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, K, [&](size_t S, bool, bool last, auto upload_hi) {
+        const bool ev = c->profiling && last;   // profiling, on the last slice: level 1 with its epilogue | packing | selection
+        if (ev) THFHE_HIP(hipEventRecord(c->ev[0], st));
+        THFHE_TRY(mk_enqueue_pbs(c, lo_src, S, c->d_tv.as<int64_t>(), nullptr, 1, nullptr, nullptr, false, &mv));
+        if (ev) THFHE_HIP(hipEventRecord(c->ev[1], st));
+        THFHE_TRY(mk_pack_enqueue(c, c->d_u.as<int32_t>(), S * q, p_hi, c->d_tab_a.as<int64_t>(), c->d_tab_b.as<int64_t>()));
+        if (ev) THFHE_HIP(hipEventRecord(c->ev[2], st));
+        THFHE_TRY(upload_hi());
+        THFHE_TRY(mk_enqueue_pbs(c, hi_src, S * K, c->d_tab_b.as<int64_t>(), c->d_tab_a.as<int64_t>(), 1, nullptr, c->stage.out_ptr()));
+        if (ev) {
+            THFHE_HIP(hipEventRecord(c->ev[3], st));
+            c->ev_valid = true;
+        }
+        return (int)THFHE_OK;
+    });
+}
+
 // thfhe_mk_mv_lut_bootstrap(_wo_keyswitch): ctx_mv_lut_bootstrap (thfhe_pbs_host.h) in slices of at most mv_slice records, one stage
 // with the multi-value epilogue per slice
 int mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t *tv0, const int32_t *factors, int p, int q, int n_tables,
@@ -1345,7 +1406,14 @@ int mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t
 // slices of at most dag_slice nodes and mv_slice / q of them.  No stage of a run records profiling events.
 int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const int64_t *mv_out_bias, size_t instances, int64_t *stats) {
     DagPlan plan;
+    if ((F.gens & kDagGenTree) && A.nodes)   // before the plan: a SELECT row has a refusal of its own on this engine
+        for (size_t g = 0; g < A.n_nodes; g++)
+            if (A.nodes[6 * g] == THFHE_SELECT)
+                return thfhe_fail(THFHE_E_INVALID, "SELECT node: not run on the 3-gen engine -- its candidates are key-switched P n-word records and need the "
+                                                   "D = P n packing key, trees the D = N key, and a context holds one key");
     THFHE_TRY(dag_checked_plan(A, F, mk_dag_classify, plan));
+    for (const DagBatch &b : plan.batches)   // the flat tree's rule: one packing takes at most 64 records
+        if (b.cls == kDagTree && F.trees[b.tree].p_hi > kMkTreeRules.p_hi_max) return thfhe_fail(THFHE_E_INVALID, kMkTreeRules.p_hi_text);
     const bool mv_entry = F.gens & kDagGenMv;
     if (stats && mv_entry) plan.fill_stats(stats);   // the plan's figures need no device
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
@@ -1355,8 +1423,28 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
     const int words = c->rec_words();
     const size_t N = c->p.N;
     hipStream_t st = c->stream;
+    if (plan.has_tree_groups()) {   // TREE / TREE_MV groups pack [N + 1] records: the D = N key (SELECT rows never reach a plan of this engine)
+        if (!c->pk_D) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_mk_pack_key_set)");
+        if (c->pk_D != (int)N) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key must take the ring key's coefficients (D = N)");
+    }
     auto mv_slice_of = [&](int mv, size_t all) { return std::min({all, c->dag_slice, std::max<size_t>(1, c->mv_slice / (size_t)F.mvs[mv].q)}); };
-    for (const DagBatch &b : plan.batches) {   // every buffer an MV group's slices use, the staging output included, before dag_execute takes pointers
+    // a slice of a TREE group: at most dag_slice nodes over all instances and tree_slice / p_hi of them; of a TREE_MV group: tree_slice / (k p_hi)
+    auto tree_slice_of = [&](size_t cand, size_t all) { return std::min({all, c->dag_slice, std::max<size_t>(1, c->tree_slice / cand)}); };
+    for (const DagBatch &b : plan.batches) {   // every buffer a grouped kind's slices use, the staging output included, before dag_execute takes pointers
+        if (b.cls == kDagTree || b.cls == kDagTreeMv) {
+            const bool is_mv = b.cls == kDagTreeMv;
+            const size_t k = is_mv ? (size_t)F.mvs[b.tree].k : 1, p = is_mv ? (size_t)F.mvs[b.tree].q : (size_t)F.trees[b.tree].p_hi;
+            const int theta = is_mv ? (int)(k * p) : F.trees[b.tree].lo.theta;
+            const size_t S = tree_slice_of(k * p, b.count * instances), rot1 = is_mv ? S : S * (p / theta);
+            THFHE_TRY(mk_ensure_workspace(c, rot1, theta));   // level 1: its rotations, S k p records
+            THFHE_TRY(mk_ensure_workspace(c, S * k, 1));      // selection
+            THFHE_TRY(c->d_lut_idx.grow(std::max(rot1, S * k) * sizeof(int32_t)));
+            THFHE_TRY(mk_pack_reserve(c, S * k * p));
+            THFHE_TRY(c->d_tab_a.grow(S * k * N * sizeof(int64_t)));
+            THFHE_TRY(c->d_tab_b.grow(S * k * N * sizeof(int64_t)));
+            THFHE_TRY(c->stage.out.grow(S * k * words * sizeof(int32_t)));
+            continue;
+        }
         if (b.cls != kDagMv) continue;
         const size_t S = mv_slice_of(b.tree, b.count * instances), q = (size_t)F.mvs[b.tree].q;
         THFHE_TRY(mk_ensure_workspace(c, S, (int)q));
@@ -1367,16 +1455,46 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
     THFHE_TRY(dag_upload(c->dag.specs, st, F.specs, (size_t)F.n_specs * sizeof(thfhe_lut_spec)));
     THFHE_TRY(dag_upload(c->d_dag_mv_tv0, st, F.mv_tv0, (size_t)F.n_bases * N * sizeof(int64_t)));
     THFHE_TRY(dag_upload(c->d_dag_mv_w, st, F.mv_factors, F.n_factor_words * sizeof(int32_t)));
+    THFHE_TRY(dag_upload(c->d_dag_enc_a, st, F.enc_a, (size_t)F.n_enc * N * sizeof(int64_t)));   // the tree generation's families are int64 here
+    THFHE_TRY(dag_upload(c->d_dag_enc_b, st, F.enc_b, (size_t)F.n_enc * N * sizeof(int64_t)));
+    THFHE_TRY(dag_upload(c->d_dag_tv1, st, F.tv1, (size_t)F.n_tv1_rows * N * sizeof(int64_t)));
     return dag_execute(
         plan, c->dag, st, words, A, instances, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) { return mk_dag_ensure(c, max_gates, plan.max_theta, in, out); },
         [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); },
         [&](int theta, const DagLutSlice &s) {
-            return mk_enqueue_pbs(c, s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, c->d_tv.as<int64_t>(), nullptr, theta, nullptr, c->stage.out_ptr());
+            return mk_enqueue_pbs(c, s.src(c->dag.specs.as<thfhe_lut_spec>()), (size_t)s.total, (s.enc ? c->d_dag_enc_b : c->d_tv).as<int64_t>(),
+                                  s.enc ? c->d_dag_enc_a.as<int64_t>() : nullptr, theta, nullptr, c->stage.out_ptr());
         },
-        [&](const DagExtGroup &g) -> int {   // the plan of this engine holds no other grouped kind; t_y = each node's table
-            if (g.cls != kDagMv) return thfhe_fail(THFHE_E_INVALID, "grouped node kind not defined for the 3-gen engine");
-            const thfhe_mv_spec m = F.mvs[g.tree];
+        [&](const DagExtGroup &g) -> int {
+            int32_t *const dst = c->stage.out_ptr();
+            int64_t *const tab_a = c->d_tab_a.as<int64_t>(), *const tab_b = c->d_tab_b.as<int64_t>();
+            const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the `hi` operands of a TREE / TREE_MV node follow its lo.n_inputs level-1 operands
+            if (g.cls == kDagTree) {   // mk_tree_bootstrap's chain with both prologues on the wire table; t_y = row0
+                const thfhe_tree_spec ts = F.trees[g.tree];
+                const int p = ts.p_hi, R = p / ts.lo.theta, hi0 = ts.lo.n_inputs;
+                return dag_group_slices(g, tree_slice_of((size_t)p, (size_t)g.all), 1, dst, words, st, [&](long first, long S) {
+                    const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {ts.lo}, g.t_y, first, g.cnt, g.n_wires, R};
+                    const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
+                    THFHE_TRY(mk_enqueue_pbs(c, lo, (size_t)S * R, c->d_dag_tv1.as<int64_t>(), nullptr, ts.lo.theta, nullptr, nullptr));
+                    THFHE_TRY(mk_pack_enqueue(c, c->d_u.as<int32_t>(), (size_t)S * p, p, tab_a, tab_b));
+                    return mk_enqueue_pbs(c, hi, (size_t)S, tab_b, tab_a, 1, nullptr, dst);
+                });
+            }
+            if (g.cls != kDagMv && g.cls != kDagTreeMv) return thfhe_fail(THFHE_E_INVALID, "grouped node kind not defined for the 3-gen engine");
+            const thfhe_mv_spec m = F.mvs[g.tree];   // t_y = each node's table
+            if (g.cls == kDagTreeMv) {   // mk_tree_mvk_bootstrap's chain on the wire table: record [first + s][j] goes to wire head + j
+                const int64_t *const base = c->d_dag_mv_tv0.as<int64_t>() + (size_t)m.base * N;
+                const MkMvArgs mvk{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p, m.k * m.q, mv_out_bias ? mv_out_bias[g.tree] : 0};
+                const int hi0 = m.lo.n_inputs;
+                return dag_group_slices(g, tree_slice_of((size_t)m.k * m.q, (size_t)g.all), m.k, dst, words, st, [&](long first, long S) {
+                    const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
+                    const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
+                    THFHE_TRY(mk_enqueue_pbs(c, lo, (size_t)S, base, nullptr, 1, nullptr, nullptr, false, &mvk));
+                    THFHE_TRY(mk_pack_enqueue(c, c->d_u.as<int32_t>(), (size_t)S * m.k * m.q, m.q, tab_a, tab_b));
+                    return mk_enqueue_pbs(c, hi, (size_t)S * m.k, tab_b, tab_a, 1, nullptr, dst);
+                });
+            }
             const int64_t *const tv0 = c->d_dag_mv_tv0.as<int64_t>() + (size_t)m.base * N;
             const MkMvArgs mv{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p, m.q, mv_out_bias ? mv_out_bias[g.tree] : 0};
             return dag_group_slices(g, mv_slice_of(g.tree, (size_t)g.all), m.q, c->stage.out_ptr(), words, st, [&](long first, long S) {
@@ -1517,6 +1635,20 @@ int thfhe_mk_dag_run_mv_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_i
     if (!mvs && !n_mvs && !mv_tv0 && !n_bases && !mv_factors && !n_factor_words)
         return thfhe_mk_dag_run_lut_batch(c, inputs, n_inputs, nodes, n_nodes, specs, n_specs, tv, n_luts, instances, out_wires, n_out, outputs, stats);
     DagFamilies F{kDagGenLut | kDagGenMv, specs, n_specs, tv, n_luts};
+    F.mvs = mvs, F.n_mvs = n_mvs, F.mv_tv0 = mv_tv0, F.n_bases = n_bases, F.mv_factors = mv_factors, F.n_factor_words = n_factor_words;
+    return mk_dag_run(c, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, F, mv_out_bias, instances, stats);
+}
+
+// ... and encrypted-table, tree and multi-value tree nodes: LUT_ENC rows on the run's RLWE tables, TREE rows on its int64 level-1
+// rows, TREE_MV rows on the multi-value families; SELECT rows are refused.  The tree generation's families travel as int64 behind DagFamilies'
+// int32 pointers (host pointers: null checks and the upload only).
+int thfhe_mk_dag_run_tree_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs,
+                                int n_specs, const int64_t *tv, int n_luts, const int64_t *enc_a, const int64_t *enc_b, int n_enc, const thfhe_tree_spec *trees,
+                                int n_trees, const int64_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs, const int64_t *mv_tv0, int n_bases,
+                                const int32_t *mv_factors, size_t n_factor_words, const int64_t *mv_out_bias, size_t instances, const int32_t *out_wires,
+                                size_t n_out, int32_t *outputs, int64_t *stats) {
+    DagFamilies F{kDagGenLut | kDagGenTree | kDagGenMv, specs, n_specs, tv, n_luts, reinterpret_cast<const int32_t *>(enc_a), reinterpret_cast<const int32_t *>(enc_b),
+                  n_enc, trees, n_trees, reinterpret_cast<const int32_t *>(tv1), n_tv1_rows};
     F.mvs = mvs, F.n_mvs = n_mvs, F.mv_tv0 = mv_tv0, F.n_bases = n_bases, F.mv_factors = mv_factors, F.n_factor_words = n_factor_words;
     return mk_dag_run(c, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, F, mv_out_bias, instances, stats);
 }
@@ -1697,6 +1829,36 @@ int thfhe_mk_tree_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *spec_lo, 
     // host checks, before the context is looked at
     THFHE_TRY(tree_validate_rows(kMkTreeRules, spec_lo, spec_hi, p_hi, tv1, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count));
     return mk_tree_bootstrap(c, *spec_lo, *spec_hi, p_hi, tv1, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
+}
+
+int thfhe_mk_tree_lut_bootstrap_mvk(thfhe_mk_ctx *c, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, int p_lo, int k, const int64_t *tv0,
+                                    const int32_t *factors, int n_tables, const int32_t *table_index, int64_t out_bias, const int32_t *lo0,
+                                    const int32_t *lo1, const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out,
+                                    size_t count) {
+    // host checks, before the context is looked at: those of thfhe_tree_lut_bootstrap_mvk
+    THFHE_TRY(tree_validate(kMkTreeRules, spec_lo, spec_hi, p_hi, tv0, lo0, lo1, lo2, hi0, hi1, hi2, out));
+    if (!factors) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    THFHE_TRY(mv_validate(*spec_lo, p_lo, p_hi, n_tables));
+    THFHE_TRY(tree_validate_index(table_index, n_tables, count));
+    THFHE_TRY(mvk_validate(p_hi, k));
+    const int32_t *const ins[6] = {lo0, spec_lo->n_inputs > 1 ? lo1 : nullptr, spec_lo->n_inputs > 2 ? lo2 : nullptr, hi0, spec_hi->n_inputs > 1 ? hi1 : nullptr,
+                                   spec_hi->n_inputs > 2 ? hi2 : nullptr};
+    for (const int32_t *in : ins)
+        if (in == out) return thfhe_fail(THFHE_E_INVALID, "tree: out must not alias an input");
+    return mk_tree_mvk_bootstrap(c, *spec_lo, *spec_hi, p_hi, p_lo, k, tv0, factors, n_tables, table_index, out_bias, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
+}
+
+int thfhe_mk_set_pack_wide_threshold(thfhe_mk_ctx *c, size_t min_records) {
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    std::lock_guard<std::mutex> g(c->mu);
+    c->pack_wide_threshold = min_records;
+    return THFHE_OK;
+}
+
+int thfhe_mk_pack_kernel_name(const thfhe_mk_ctx *c, size_t count, char *buf, int len) {
+    if (!c || !buf) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(const_cast<thfhe_mk_ctx *>(c)->mu);   // the threshold is set under it
+    return kernel_name_result(len, launch_plan::mk_pack_kernel_name(count, c->pack_wide_threshold, buf, len > 0 ? (size_t)len : 0));
 }
 
 int thfhe_mk_set_tree_slice(thfhe_mk_ctx *c, size_t max_candidates) {

@@ -4,6 +4,7 @@
 // The pure digit and index arithmetic (mkp_*) is host-callable: tests/emu/mk_pack_emu.cpp replays it against the numpy model without a GPU.
 //   mk_pack_rows_kernel       T_i = (0, b_i 2^32 on X^0) - sum_{j, p: d != 0} PK[j][p][d - 1] mod 2^64, both polynomials: the hot path, a stream of
 //                             64-bit integer adds over key rows of 2N words
+//   mk_pack_rows_wide_kernel  the same sums for large batches: 32 records per workgroup, a key row tile fetched once per digit value
 //   mk_pack_boxes_kernel<NN>  output g = U(X) sum_{i < p} X^(i N/p) T_(g p + i): the Torus64 twin of pack_boxes_kernel (thfhe_threshold.hip)
 #ifndef THFHE_MK_PACK_H
 #define THFHE_MK_PACK_H
@@ -38,8 +39,17 @@ THFHE_FN uint64_t mkp_window(const uint64_t *pre, uint64_t tot, int c, int B, in
     return mkp_ext_prefix(pre, tot, c + B / 2, N) - mkp_ext_prefix(pre, tot, c - B / 2, N);
 }
 
+// whether digit p of a rounded word has the value v (1 .. 2^basebit - 1): one record's bit of the membership mask mk_pack_rows_wide_kernel builds
+// for (j, p, v) over its record group -- bit g of the mask is mkp_digit_is of record g's word j
+THFHE_FN bool mkp_digit_is(uint32_t abar, int p, int basebit, int v) { return mkp_digit(abar, p, basebit) == v; }
+
 constexpr int kMkPackGroup = 4;     // records per workgroup of mk_pack_rows_kernel: their partial sums live in registers
 constexpr int kMkPackTile = 512;    // int64 words of the 2N-word row a workgroup owns: 256 lanes x 16 B
+constexpr int kMkPackWideGroup = 32;   // records per workgroup of mk_pack_rows_wide_kernel: one bit each of a 32-bit membership mask
+constexpr int kMkPackWideTile = 256;   // int64 words of the row a wide workgroup owns: 256 lanes x 8 B, so that 32 sums fit the register file
+// records from which mk_pack_enqueue takes the wide kernel (thfhe_mk_set_pack_wide_threshold): the smallest size at which its median lay below the
+// direct kernel's minimum on every measured key (tools/mk_pack_bench.py, profiles/mk_pack_wide_bench.json)
+constexpr size_t kMkPackWideDefault = 4096;
 
 }  // namespace thfhe
 
@@ -99,6 +109,57 @@ __global__ __launch_bounds__(256) void mk_pack_rows_kernel(MkPackArgs a) {
         if (g >= ng) break;
         if (col == a.N) s0[g] += (unsigned long long)(int64_t)a.recs[(size_t)(g0 + g) * rec + a.D] << 32;   // (0, b 2^32 on X^0)
         *reinterpret_cast<ulonglong2 *>(a.T + (size_t)(g0 + g) * row + col) = ulonglong2{s0[g], s1[g]};
+    }
+}
+
+// The same sums with the key row fetched once per workgroup: grid = (ceil(count / 32), 2N / 256), workgroup (x, y) owns words
+// [256 y, 256 y + 256) of the sums of records [32 x, 32 x + 32), one 8-byte word per lane and 32 partial sums in registers.  It walks (j, p, v), v the
+// digit VALUE 1 .. R: lane L holds the rounded word j of record L mod 32 (LDS, [j][record] with a padded row: conflict-free both ways), a ballot
+// of mkp_digit_is over the wave is the wave-uniform membership mask of v, and row tile (j, p, v - 1) is loaded once when the mask is not empty and
+// subtracted from exactly the sums whose bit is set (a scalar all-ones / zero word ANDed into the tile: no divergence).  Records past the batch's end
+// enter as zero words, whose digits are all zero.  No atomics, no two workgroups write one word; the sums are the direct kernel's word for word.
+__global__ __launch_bounds__(256) void mk_pack_rows_wide_kernel(MkPackArgs a) {
+    constexpr int G = kMkPackWideGroup;
+    __shared__ uint32_t sA[256][G + 1];
+    const int tid = threadIdx.x, lg = tid & (G - 1);
+    const long g0 = (long)blockIdx.x * G;   // < count: the grid covers the records exactly
+    const int ng = (int)(a.count - g0 < G ? a.count - g0 : G);
+    const int col = (int)blockIdx.y * kMkPackWideTile + tid;   // < 2N: the grid covers the row exactly
+    const size_t row = 2 * (size_t)a.N, rec = (size_t)a.D + 1;
+    const int R = (1 << a.basebit) - 1;
+    unsigned long long s[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) s[g] = 0;
+    for (int j0 = 0; j0 < a.D; j0 += 256) {
+        const int jn = a.D - j0 < 256 ? a.D - j0 : 256;
+        __syncthreads();   // the words of the chunk before are consumed
+#pragma unroll 4
+        for (int g = 0; g < G; g++) sA[tid][g] = mkp_round_word(g < ng && tid < jn ? a.recs[(size_t)(g0 + g) * rec + j0 + tid] : 0, a.t, a.basebit);
+        __syncthreads();
+        for (int jj = 0; jj < jn; jj++) {
+            const int64_t *rows = a.pk + (size_t)(j0 + jj) * a.t * R * row + col;
+            const uint32_t w = sA[jj][lg];
+            for (int p = 0; p < a.t; p++) {
+                for (int v = 1; v <= R; v++) {
+                    const uint32_t m = (uint32_t)__ballot(mkp_digit_is(w, p, a.basebit, v));   // lanes 32 .. 63 repeat lanes 0 .. 31
+                    if (m == 0) continue;
+                    const unsigned long long x = *reinterpret_cast<const unsigned long long *>(rows + ((size_t)p * R + (v - 1)) * row);
+#pragma unroll
+                    for (int g = 0; g < G; g++) {
+                        const uint32_t sel = 0u - ((m >> g) & 1u);
+                        s[g] -= x & (((unsigned long long)sel << 32) | sel);
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        if (g < ng) {
+            unsigned long long v = s[g];
+            if (col == a.N) v += (unsigned long long)(int64_t)a.recs[(size_t)(g0 + g) * rec + a.D] << 32;   // (0, b 2^32 on X^0)
+            a.T[(size_t)(g0 + g) * row + col] = (int64_t)v;
+        }
     }
 }
 

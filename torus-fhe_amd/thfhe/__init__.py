@@ -351,8 +351,15 @@ SIGNATURES = {
     "thfhe_mk_tree_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
                                               _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_set_tree_slice": (C.c_int, [_vp, C.c_size_t]),
+    "thfhe_mk_tree_lut_bootstrap_mvk": (C.c_int, [_vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, C.c_int, C.c_int, _i64p, _i32p, C.c_int, _i32p, C.c_int64,
+                                                  _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_mk_set_pack_wide_threshold": (C.c_int, [_vp, C.c_size_t]),
+    "thfhe_mk_pack_kernel_name": (C.c_int, [_vp, C.c_size_t, C.c_char_p, C.c_int]),
     "thfhe_mk_dag_run_mv_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, C.POINTER(MvSpec), C.c_int,
                                             _i64p, C.c_int, _i32p, C.c_size_t, _i64p, C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
+    "thfhe_mk_dag_run_tree_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, _i64p, _i64p, C.c_int,
+                                              C.POINTER(TreeSpec), C.c_int, _i64p, C.c_int, C.POINTER(MvSpec), C.c_int, _i64p, C.c_int, _i32p, C.c_size_t, _i64p,
+                                              C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_mk_prologue_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t]),
     "thfhe_mk_set_stream": (C.c_int, [_vp, _vp]),
     "thfhe_mk_set_pair_threshold": (C.c_int, [_vp, C.c_long]),
@@ -1286,6 +1293,46 @@ class MKCloudKey(_EvalKey):
         default 16384."""
         _check(lib().thfhe_mk_set_tree_slice(self.h, int(max_candidates)))
 
+    # -- multi-value two-digit trees on Torus64 (thfhe_mk_tree_lut_bootstrap_mvk, DESIGN 4.23) -----------------------------------------------
+    def tree_lut_bootstrap_mvk(self, factors, lo, hi, *, tv0, weights_lo=(1,), bias_lo=0, weights_hi=(1,), bias_hi=0, table_index=None, out_bias=0):
+        """k functions of two encrypted digits in 1 + k rotations: out[s][j] = f_j(hi_s, lo_s) from ONE multi-value level-1 rotation on `lo`, the packing
+        of its k p_hi candidates and k selections on `hi`.  tv0 int64[N], factors int32[k][p_hi][p_lo] or int32[n_tables][k][p_hi][p_lo]
+        (thfhe.lut.tree_mvk_factors(..., torus_bits=64), tree_mvk_bool_factors); k p_hi <= 64; out_bias: a Torus64 word added to every candidate's body.
+        Needs a packing key with D = N (pack_key_set).  Returns int32[count, k, P*n+1]."""
+        lo_r, spec_lo, plo = self._lut_args(_as_tuple(lo), weights_lo, bias_lo, 1, "tree_lut_bootstrap_mvk (lo)")
+        hi_r, spec_hi, phi = self._lut_args(_as_tuple(hi), weights_hi, bias_hi, 1, "tree_lut_bootstrap_mvk (hi)")
+        _same_count(lo_r[0], hi_r[0])
+        count = lo_r[0].shape[0]
+        w = np.ascontiguousarray(factors, np.int32)
+        if w.ndim == 3:
+            w = w[None]
+        if w.ndim != 4 or w.size == 0:
+            raise ValueError("factors: expected int32[k][p_hi][p_lo] or int32[n_tables][k][p_hi][p_lo]")
+        _, tv0, idx = self._mv_tables(w[0], tv0, table_index, count)
+        out = np.empty((count, w.shape[1], self.words), np.int32)
+        _check(lib().thfhe_mk_tree_lut_bootstrap_mvk(self.h, C.byref(spec_lo), C.byref(spec_hi), w.shape[2], w.shape[3], w.shape[1], self._ptv(tv0), _p32(w),
+                                                     w.shape[0], _p32(idx), _wrap64(out_bias), plo[0], plo[1], plo[2], phi[0], phi[1], phi[2], _p32(out), count))
+        return out
+
+    def tree_lut_bootstrap_mv(self, factors, lo, hi, *, tv0, weights_lo=(1,), bias_lo=0, weights_hi=(1,), bias_hi=0, table_index=None, out_bias=0):
+        """tree_lut_bootstrap_mvk with k = 1: 1 + 1 rotations whatever p_hi is.  factors int32[p_hi][p_lo] or int32[n_tables][p_hi][p_lo]
+        (thfhe.lut.tree_mv_factors(..., torus_bits=64)).  Returns int32[count, P*n+1]."""
+        w = np.ascontiguousarray(factors, np.int32)
+        if w.ndim not in (2, 3) or w.size == 0:
+            raise ValueError("factors: expected int32[p_hi][p_lo] or int32[n_tables][p_hi][p_lo]")
+        w = w[None, None] if w.ndim == 2 else w[:, None]
+        return self.tree_lut_bootstrap_mvk(w, lo, hi, tv0=tv0, weights_lo=weights_lo, bias_lo=bias_lo, weights_hi=weights_hi, bias_hi=bias_hi,
+                                           table_index=table_index, out_bias=out_bias)[:, 0]
+
+    def set_pack_wide_threshold(self, min_records):
+        """Packing calls of at least min_records records (per slice) run mk_pack_rows_wide_kernel, smaller ones mk_pack_rows_kernel; 0 = never the
+        wide one.  Both give the same words."""
+        _check(lib().thfhe_mk_set_pack_wide_threshold(self.h, int(min_records)))
+
+    def pack_kernel_name(self, count):
+        """The packing-rows kernel a packing of `count` records is dispatched to, as mk_pack_enqueue in thfhe_mk.hip decides it."""
+        return self._kernel_name(lib().thfhe_mk_pack_kernel_name, int(count))
+
     def dag_run_mv_batch(self, input_records, nodes, specs=(), tv=None, mvs=(), mv_tv0=None, mv_factors=None, mv_out_bias=None, out_wires=None):
         """dag_run_lut_batch with multi-value nodes (thfhe_mk_dag_run_mv_batch).  mvs: MvSpec or (lo, hi, p, q, k, base, factors_off,
         n_tables) tuples (hi None, k 1); mv_tv0: int64[n_bases][N] base vectors; mv_factors: int32[words], the taps of every spec; mv_out_bias: one
@@ -1304,6 +1351,30 @@ class MKCloudKey(_EvalKey):
             return (sp, len(specs), p64(t), 0 if t is None else t.shape[0], mv, len(mvs), p64(tv0), 0 if tv0 is None else tv0.shape[0], _p32(fac),
                     0 if fac is None else fac.shape[0], p64(ob))
         return self._dag_run("dag_run_mv_batch", lib().thfhe_mk_dag_run_mv_batch, (self.h,), input_records, nodes, 6, families, out_wires)
+
+    def dag_run_tree_batch(self, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, mvs=(), mv_tv0=None, mv_factors=None,
+                           mv_out_bias=None, out_wires=None):
+        """dag_run_mv_batch with encrypted-table, tree and multi-value tree nodes (thfhe_mk_dag_run_tree_batch).  enc_a, enc_b:
+        int64[n_enc][N] RLWE tables; trees: TreeSpec or (lo, hi, p_hi) tuples; tv1: int64[rows][N] level-1 rows; mvs entries may carry hi and k
+        (TREE_MV).  TREE and TREE_MV rows need a packing key with D = N (pack_key_set); SELECT rows are refused."""
+        def families():
+            N = self.params.N
+            p64 = lambda a: None if a is None else a.ctypes.data_as(_i64p)
+            a64 = lambda a: None if a is None else np.ascontiguousarray(a, np.int64).reshape(-1, N)
+            sp = (LutSpec * len(specs))(*[_lut_spec(s) for s in specs]) if len(specs) else None
+            t, ea, eb, rows, tv0 = a64(tv), a64(enc_a), a64(enc_b), a64(tv1), a64(mv_tv0)
+            if (ea is None) != (eb is None) or (ea is not None and ea.shape != eb.shape):
+                raise ValueError("enc_a and enc_b: give both, int64[n_enc][N]")
+            tr = (TreeSpec * len(trees))(*[t if isinstance(t, TreeSpec) else TreeSpec(_lut_spec(t[0] or _NO_SPEC), _lut_spec(t[1]), int(t[2])) for t in trees]) if len(trees) else None
+            mv = _mv_specs(mvs)
+            fac = None if mv_factors is None else np.ascontiguousarray(mv_factors, np.int32).reshape(-1)
+            ob = None if mv_out_bias is None else np.array([_wrap64(v) for v in np.ravel(mv_out_bias)], np.int64)
+            if ob is not None and ob.shape[0] != len(mvs):
+                raise ValueError(f"mv_out_bias holds {ob.shape[0]} words for {len(mvs)} specs")
+            n = lambda a: 0 if a is None else a.shape[0]
+            return (sp, len(specs), p64(t), n(t), p64(ea), p64(eb), n(ea), tr, len(trees), p64(rows), n(rows), mv, len(mvs), p64(tv0), n(tv0), _p32(fac),
+                    n(fac), p64(ob))
+        return self._dag_run("dag_run_tree_batch", lib().thfhe_mk_dag_run_tree_batch, (self.h,), input_records, nodes, 6, families, out_wires)
 
     def rotation_kernel_name(self, rotations):
         """The blind-rotation kernel a batch of `rotations` is dispatched to, as mk_launch_rotation in thfhe_mk.hip decides it."""

@@ -21,6 +21,9 @@ Multi-value nodes (Circuit.mv / tree_mv; single key): q functions o
 of two digits in 1 + k rotations on k consecutive wires, each one level.  Circuits that hold them run on thfhe_dag_run_mv_batch; sbox_digits looks a
 6-bit -> 4-bit table up in one TREE_MV node.
 
+On the 3-gen multi-key engine LUT_ENC, TREE and TREE_MV nodes on Torus64 tables (int64 enc_table / tree_rows / mv_base, tree_mv's
+out_bias) run on thfhe_mk_dag_run_tree_batch with the context's own D = N packing key; SELECT and the leveled nodes stay single-key.
+
 Leveled nodes (Circuit.lhe_lookup / lhe_gather / lhe_wfa; single key): a table lookup, a pick among 2^d computed wires and a layered
 automaton on the client's TGSW-encrypted bits (`tgsw_sets`: instance q reads sample q of every set), each one level and no blind rotation.  Circuits
 that hold them run on thfhe_dag_run_lhe_batch; lhe_array_read reads an array of computed wires at the client's index, wfa_mux_max takes the larger
@@ -126,14 +129,16 @@ class Circuit:
 
     def enc_table(self, tv_a, tv_b, plain=None):
         """Register an encrypted table: the TLWE sample (tv_a, tv_b) int32[N] under the bootstrapping ring key (thfhe.lut.encrypt_table, or
-        PackBoxes' output); returns its id.  Equal samples share one id.  plain: its plaintext test vector, carried for simulate only."""
-        a, b = np.ascontiguousarray(tv_a, np.int32).reshape(-1), np.ascontiguousarray(tv_b, np.int32).reshape(-1)
+        PackBoxes' output); returns its id.  Equal samples share one id.  plain: its plaintext test vector, carried for simulate only.  int64 arrays
+        are kept as the Torus64 RLWE sample of a circuit for the 3-gen multi-key engine (thfhe.lut.encrypt_table(..., torus_bits=64))."""
+        dt = np.int64 if np.asarray(tv_b).dtype == np.int64 else np.int32
+        a, b = np.ascontiguousarray(tv_a, dt).reshape(-1), np.ascontiguousarray(tv_b, dt).reshape(-1)
         if a.shape != b.shape:
             raise ValueError("tv_a and tv_b differ in shape")
         key = ("enc", a.tobytes(), b.tobytes())
         if key not in self._ids:
             self._ids[key] = len(self.enc_tables)
-            self.enc_tables.append((a, b, None if plain is None else np.ascontiguousarray(plain, np.int32).reshape(-1)))
+            self.enc_tables.append((a, b, None if plain is None else np.ascontiguousarray(plain, dt).reshape(-1)))
         return self._ids[key]
 
     def lut_enc(self, etab, inputs, weights=(1,), bias=0, theta=1):
@@ -152,11 +157,13 @@ class Circuit:
 
     def tree_rows(self, rows):
         """Register the R level-1 rows int32[R][N] of a tree function (thfhe.lut.tree_test_vectors); returns row0, the index of the first.  Equal row
-        blocks share one row0."""
-        rows = np.ascontiguousarray(rows, np.int32)
+        blocks share one row0.  int64 rows (thfhe.lut.tree_test_vectors(..., torus_bits=64)) are kept as the Torus64 rows of a circuit for the 3-gen
+        multi-key engine."""
+        rows = np.asarray(rows)
+        rows = np.ascontiguousarray(rows, np.int64 if rows.dtype == np.int64 else np.int32)
         if rows.ndim != 2 or rows.shape[0] < 1:
             raise ValueError("tree_rows: expected int32[R][N]")
-        key = ("tv1", rows.shape, rows.tobytes())
+        key = ("tv1", rows.dtype.str, rows.shape, rows.tobytes())
         if key not in self._ids:
             self._ids[key] = len(self.tv1)
             self.tv1.extend(rows)
@@ -249,10 +256,12 @@ class Circuit:
         lo = (len(inputs), tuple(_wrap32(v) for v in list(weights) + [0] * (3 - len(weights))), _wrap32(bias), 1)
         return self._mv_row(MV, lo, None, base, w[None], inputs, out_bias)
 
-    def tree_mv(self, base, factors, lo_inputs, hi_inputs, lo_weights=None, hi_weights=None, lo_bias=0, hi_bias=0):
+    def tree_mv(self, base, factors, lo_inputs, hi_inputs, lo_weights=None, hi_weights=None, lo_bias=0, hi_bias=0, out_bias=0):
         """A TREE_MV node: k functions f_j(hi, lo) of two encrypted digits in 1 + k rotations (one multi-value rotation of the base vector `base` on
         the `lo` digit with k p_hi outputs, box packing, k selection rotations on the `hi` digit), one level.  factors: int32[k][p_hi][p_lo]
-        (thfhe.lut.tree_mvk_factors).  lo_inputs and hi_inputs number at most three together.  Returns the k output wire ids (consecutive)."""
+        (thfhe.lut.tree_mvk_factors).  lo_inputs and hi_inputs number at most three together.  Returns the k output wire ids (consecutive).
+        out_bias: the Torus64 word the multi-key engine adds to every level-1 candidate (thfhe.lut.tree_mvk_bool_factors, on a Torus64 base); the
+        single-key engine has none."""
         lo_inputs, hi_inputs = list(lo_inputs), list(hi_inputs)
         lo_weights = (1,) * len(lo_inputs) if lo_weights is None else tuple(lo_weights)
         hi_weights = (1,) * len(hi_inputs) if hi_weights is None else tuple(hi_weights)
@@ -265,7 +274,7 @@ class Circuit:
             raise ValueError("factors: expected int32[k][p_hi][p_lo], p_hi a power of two")
         lo = (len(lo_inputs), tuple(_wrap32(v) for v in list(lo_weights) + [0] * (3 - len(lo_weights))), _wrap32(lo_bias), 1)
         hi = (len(hi_inputs), tuple(_wrap32(v) for v in list(hi_weights) + [0] * (3 - len(hi_weights))), _wrap32(hi_bias), 1)
-        return self._mv_row(TREE_MV, lo, hi, base, w, lo_inputs + hi_inputs)
+        return self._mv_row(TREE_MV, lo, hi, base, w, lo_inputs + hi_inputs, out_bias)
 
     def _lhe_rows(self, store, rows_b, rows_a, plain, what):
         b = np.ascontiguousarray(rows_b, np.int32)
@@ -879,24 +888,25 @@ def to_gate_bit(cir, w, table_id=None, N=1024, torus_bits=32):
     return cir.lut(table_id, [w])[0]
 
 
-def tree_mul_digits(cir, a, b, N=1024):
+def tree_mul_digits(cir, a, b, N=1024, torus_bits=32):
     """The product of two 3-bit digits (p = 8 wires a, b) as its low and high 3-bit digits: two TREE nodes with p_hi = p_lo = p_out = 8 and
-    theta1 = 2 (4 + 1 rotations each; a shape of DESIGN 4.11's supported set), a on the level-1 digit, b on the selection digit.  Returns (low, high)."""
+    theta1 = 2 (4 + 1 rotations each; a shape of DESIGN 4.11's supported set), a on the level-1 digit, b on the selection digit.  Returns (low, high).
+    torus_bits=64 with the context's N: int64 rows for the 3-gen multi-key engine."""
     from . import lut
-    lo_rows = cir.tree_rows(lut.tree_test_vectors(lambda h, l: (h * l) % 8, 8, 8, 8, theta=2, N=N))
-    hi_rows = cir.tree_rows(lut.tree_test_vectors(lambda h, l: (h * l) // 8, 8, 8, 8, theta=2, N=N))
+    lo_rows = cir.tree_rows(lut.tree_test_vectors(lambda h, l: (h * l) % 8, 8, 8, 8, theta=2, N=N, torus_bits=torus_bits))
+    hi_rows = cir.tree_rows(lut.tree_test_vectors(lambda h, l: (h * l) // 8, 8, 8, 8, theta=2, N=N, torus_bits=torus_bits))
     return cir.tree(lo_rows, [a], [b], 8, theta1=2), cir.tree(hi_rows, [a], [b], 8, theta1=2)
 
 
-def sbox_digits(cir, hi, lo, table, N=1024):
+def sbox_digits(cir, hi, lo, table, N=1024, torus_bits=32):
     """A 64-entry table of 4-bit values (a DES S-box: table[8 hi + lo]) on two p = 8 digit wires, as its four bits LSB-first in the p_out = 2 encoding
     of thfhe.lut: ONE TREE_MV node with k = 4, p_hi = p_lo = 8 (1 + 4 rotations; bit-valued outputs, the shape DESIGN 4.13's noise table supports on
-    the named parameter sets).  Returns the four bit wires."""
+    the named parameter sets).  Returns the four bit wires.  torus_bits=64 with the context's N: the Torus64 base vector of the 3-gen multi-key engine."""
     from . import lut
     table = [int(v) for v in table]
     if len(table) != 64 or any(not 0 <= v < 16 for v in table):
         raise ValueError("sbox_digits: expected 64 values in 0 .. 15")
-    tv0, w = lut.tree_mvk_factors([lambda h, l, j=j: (table[8 * h + l] >> j) & 1 for j in range(4)], 8, 8, 2, N=N)
+    tv0, w = lut.tree_mvk_factors([lambda h, l, j=j: (table[8 * h + l] >> j) & 1 for j in range(4)], 8, 8, 2, N=N, torus_bits=torus_bits)
     return cir.tree_mv(cir.mv_base(tv0), w, [lo], [hi])
 
 
@@ -1325,11 +1335,19 @@ def simulate_mk(cir, input_bits):
 
 # ---- evaluator --------------------------------------------------------------------------------------------------------
 def _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets=None, level2=None, one_rotation=False):
-    if ck._tv_dtype == np.int64:   # the 3-gen multi-key engine: gates, LUT and MV nodes (thfhe_mk_dag_run_mv_batch)
-        if cir.has_tree_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes() or any(g[0] == TREE_MV for g in cir.gates):
-            raise ValueError("the multi-key executor runs gate, LUT and MV nodes only (no tree or encrypted-table rows, no leveled nodes)")
+    if ck._tv_dtype == np.int64:   # the 3-gen multi-key engine: thfhe_mk_dag_run_mv_batch, with tree rows thfhe_mk_dag_run_tree_batch
+        if cir.has_lhe_nodes() or cir.has_cb_nodes():
+            raise ValueError("the multi-key executor runs gate, LUT, MV, LUT_ENC, TREE and TREE_MV nodes only (no leveled nodes)")
+        if any(g[0] == SELECT for g in cir.gates):
+            raise ValueError("the multi-key executor runs no SELECT node: its candidates are key-switched records and need the D = P n packing key, "
+                             "trees the D = N key, and a context holds one key")
         mvs, tv0, fac = cir.mv_families()
         bias = [cir.mv_out_bias.get(i, 0) for i in range(len(mvs))]
+        if cir.has_tree_nodes() or any(g[0] == TREE_MV for g in cir.gates):
+            enc = cir.enc_tables
+            return ck.dag_run_tree_batch(x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None, np.stack([e[0] for e in enc]) if enc else None,
+                                         np.stack([e[1] for e in enc]) if enc else None, cir.tree_specs, np.stack(cir.tv1) if cir.tv1 else None, mvs, tv0,
+                                         fac, bias, sel)
         return ck.dag_run_mv_batch(x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None, mvs, tv0, fac, bias, sel)
     if cir.mv_out_bias:
         raise ValueError("out_bias on an MV node is the multi-key engine's; the single-key thfhe_dag_run_mv_batch has none")
@@ -1430,6 +1448,7 @@ def _levels_ext(ck, cir, level, vals, pack):
     the number of calls' groups."""
     from .threshold import PackBoxes
     gates, base, groups = cir.gates, cir.n_inputs, 0
+    mk = ck._tv_dtype == np.int64   # the 3-gen engine: the context holds the packing key, and it runs no SELECT
     by = {}
     for g in level:
         if gates[g][0] in (LUT_ENC, SELECT, TREE):
@@ -1447,6 +1466,8 @@ def _levels_ext(ck, cir, level, vals, pack):
                 vals[out + j] = r[:, j]
             continue
         lo, hi, p = cir.tree_specs[x]
+        if op == SELECT and mk:
+            raise ValueError("the multi-key engine runs no SELECT node")
         if op == SELECT:
             cands = vals[np.concatenate([cir.ext_rows[g][1] + np.arange(p) for g in G])]
             a, b = PackBoxes(pack, cands, p)
@@ -1458,7 +1479,7 @@ def _levels_ext(ck, cir, level, vals, pack):
             tv1 = np.stack([np.stack(cir.tv1[r:r + R]) for r in row0s])
             lo_in = tuple(vals[[gates[g][1 + q] for g in G]] for q in range(lo[0]))
             hi_in = tuple(vals[[gates[g][1 + lo[0] + q] for g in G]] for q in range(hi[0]))
-            vals[out] = ck.tree_lut_bootstrap(pack, tv1, lo_in, hi_in, p_hi=p, weights_lo=lo[1][:lo[0]], bias_lo=lo[2], theta=lo[3], weights_hi=hi[1][:hi[0]],
+            vals[out] = ck.tree_lut_bootstrap(*(() if mk else (pack,)), tv1, lo_in, hi_in, p_hi=p, weights_lo=lo[1][:lo[0]], bias_lo=lo[2], theta=lo[3], weights_hi=hi[1][:hi[0]],
                                               bias_hi=hi[2], table_index=[row0s.index(cir.ext_rows[g][1]) for g in G])
     return groups
 
@@ -1467,6 +1488,7 @@ def _levels_mv(ck, cir, level, vals, pack):
     """The MV and TREE_MV nodes of one level through the public flat calls (mv_lut_bootstrap, tree_lut_bootstrap_mvk), one call per spec; returns
     the number of calls."""
     gates, base, by = cir.gates, cir.n_inputs, {}
+    mk = ck._tv_dtype == np.int64   # the 3-gen engine: out_bias, and the context holds the packing key
     for g in level:
         if gates[g][0] in (MV, TREE_MV):
             by.setdefault((gates[g][0], cir.mv_rows[g][0]), []).append(g)
@@ -1475,12 +1497,13 @@ def _levels_mv(ck, cir, level, vals, pack):
         out = base + np.array(G)
         idx = [cir.mv_rows[g][1] for g in G]
         lo_in = tuple(vals[[gates[g][1 + i] for g in G]] for i in range(lo[0]))
+        extra = dict(out_bias=cir.mv_out_bias.get(mi, 0)) if mk else {}
         if op == MV:
-            r = ck.mv_lut_bootstrap(np.stack([t[0] for t in tabs]), *lo_in, tv0=cir.mv_bases[b], weights=lo[1][:lo[0]], bias=lo[2], table_index=idx)
+            r = ck.mv_lut_bootstrap(np.stack([t[0] for t in tabs]), *lo_in, tv0=cir.mv_bases[b], weights=lo[1][:lo[0]], bias=lo[2], table_index=idx, **extra)
         else:
             hi_in = tuple(vals[[gates[g][1 + lo[0] + i] for g in G]] for i in range(hi[0]))
-            r = ck.tree_lut_bootstrap_mvk(pack, np.stack(tabs), lo_in, hi_in, tv0=cir.mv_bases[b], weights_lo=lo[1][:lo[0]], bias_lo=lo[2],
-                                          weights_hi=hi[1][:hi[0]], bias_hi=hi[2], table_index=idx)
+            r = ck.tree_lut_bootstrap_mvk(*(() if mk else (pack,)), np.stack(tabs), lo_in, hi_in, tv0=cir.mv_bases[b], weights_lo=lo[1][:lo[0]], bias_lo=lo[2],
+                                          weights_hi=hi[1][:hi[0]], bias_hi=hi[2], table_index=idx, **extra)
         for j in range(r.shape[1]):
             vals[out + j] = r[:, j]
     return len(by)

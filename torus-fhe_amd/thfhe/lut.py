@@ -154,24 +154,40 @@ def mv_bool_factors(bit_tables, p, torus_bits=32, N=1024):
     return mv_base(2 * mu, N, torus_bits), mv_factors(f, p), -mu
 
 
-def tree_mv_factors(f, p_hi, p_lo, p_out, N=1024):
+def tree_mv_factors(f, p_hi, p_lo, p_out, N=1024, torus_bits=32):
     """(tv0, factors) of thfhe_tree_lut_bootstrap_mv for f(hi, lo), taken mod p_out: the base vector at step 2^32 / (2 p_out) and int32[p_hi][p_lo],
-    row h = the factor of lo -> f(h, lo).  Candidate h of the one level-1 rotation then carries encode(f(h, lo), p_out)."""
+    row h = the factor of lo -> f(h, lo).  Candidate h of the one level-1 rotation then carries encode(f(h, lo), p_out).  torus_bits=64: the int64
+    base vector at step 2^64 / (2 p_out) (thfhe_mk_tree_lut_bootstrap_mvk); the factors are the same integers."""
     _check_p(p_hi)
     _check_p(p_out)
+    _check_bits(torus_bits)
     tab = [[int(f(h, lo)) % p_out for lo in range(p_lo)] for h in range(p_hi)]
-    return mv_base((1 << 32) // (2 * p_out), N), mv_factors(tab, p_lo)
+    return mv_base((1 << torus_bits) // (2 * p_out), N, torus_bits), mv_factors(tab, p_lo)
 
 
-def tree_mvk_factors(fs, p_hi, p_lo, p_out=2, N=1024):
+def tree_mvk_factors(fs, p_hi, p_lo, p_out=2, N=1024, torus_bits=32):
     """(tv0, factors) of thfhe_tree_lut_bootstrap_mvk for the k functions fs[j](hi, lo), taken mod p_out: one base vector and
     int32[k][p_hi][p_lo], block j = tree_mv_factors(fs[j]).  Output j p_hi + h of the one level-1 rotation is candidate h of function j.  p_out = 2
-    (bit-valued outputs) is what the named parameter sets carry through the two rotations; k p_hi <= 64."""
+    (bit-valued outputs) is what the named parameter sets carry through the two rotations; k p_hi <= 64.  torus_bits=64: the int64 base vector of
+    thfhe_mk_tree_lut_bootstrap_mvk."""
     fs = list(fs)
     if not fs or len(fs) * p_hi > 64:
         raise ValueError("1 <= k and k * p_hi <= 64 (the outputs of one multi-value rotation)")
-    parts = [tree_mv_factors(f, p_hi, p_lo, p_out, N) for f in fs]
+    parts = [tree_mv_factors(f, p_hi, p_lo, p_out, N, torus_bits) for f in fs]
     return parts[0][0], np.stack([w for _, w in parts])
+
+
+def tree_mvk_bool_factors(fs, p_hi, p_lo, N=1024, torus_bits=32):
+    """(tv0, factors, out_bias) of a multi-value tree whose k bit functions fs[j](hi, lo) in {0, 1} leave the tree in the gates' encoding +-mu: the
+    0/1 tables of mv_bool_factors (a tap is a difference of bits: half the taps of +-1 tables) as int32[k][p_hi][p_lo], and the bias -mu that
+    thfhe_mk_tree_lut_bootstrap_mvk adds to every level-1 candidate (its out_bias), so that the packed tables hold +-mu."""
+    fs = list(fs)
+    _check_p(p_hi)
+    if not fs or len(fs) * p_hi > 64:
+        raise ValueError("1 <= k and k * p_hi <= 64 (the outputs of one multi-value rotation)")
+    tabs = [[[int(f(h, lo)) for lo in range(p_lo)] for h in range(p_hi)] for f in fs]
+    tv0, w, bias = mv_bool_factors(np.asarray(tabs, np.int64).reshape(len(fs) * p_hi, p_lo), p_lo, torus_bits, N)
+    return tv0, w.reshape(len(fs), p_hi, p_lo), bias
 
 
 def lhe_table(functions, d_tree, d_rot, theta=1, encode=None, N=1024):
