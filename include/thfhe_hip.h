@@ -751,6 +751,48 @@ int thfhe_mk_tree_lut_bootstrap(thfhe_mk_ctx *ctx, const thfhe_lut_spec *spec_lo
                                 int32_t *out /*[count][P*n+1]*/, size_t count);
 int thfhe_mk_set_tree_slice(thfhe_mk_ctx *ctx, size_t max_candidates);
 
+/* ---- encrypted dense layers: an integer matrix times a vector of LWE records, fused into the programmable bootstrap.
+ *
+ * A PBS prologue combines at most three records; a dense layer combines K.  rec = the words of a record of the context (n + 1 single key,
+ * P n + 1 on the 3-gen engine), word rec - 1 the body.  For sample s < count, output m < M, word i < rec:
+ *     x[s][m][i] = ( sum_{k<K} W[m][k] * in[s][k][i]  +  (i == rec - 1 ? bias[m] : 0) )  mod 2^32
+ * Exact integer arithmetic, independent of the order of summation.  With the padding-bit encoding of the PBS every reachable sum of
+ * messages sum_k W[m][k] m_k + bias must stay inside [0, p): that is the caller's duty (thfhe.circuits.dense_bias).
+ * W: HOST int32[M][K], any int32 values (the products wrap); one matrix serves all samples of a call.  bias: HOST int32[M] Torus32
+ * words, or NULL (zero).  in: HOST int32[count][K][rec].  1 <= M, K <= 65536.
+ *
+ * thfhe_lwe_linear:            out = HOST int32[count][M][rec] = x.
+ * thfhe_linear_lut_bootstrap:  out = HOST int32[count][M][theta][rec]: every x[s][m] bootstrapped on table tv[lut_index[m]] (table 0 with a
+ *   NULL lut_index), theta in {1, 2, 4} records each.  lut_index: HOST int32[M], the table of OUTPUT m, the same for every sample.  Word for
+ *   word the result of thfhe_lwe_linear followed by thfhe_lut_bootstrap(spec = {1, {1}, 0, theta}, tv, n_luts, lut_index'[s M + m] =
+ *   lut_index[m], in0 = x); x stays on the device and nothing visits the host between the two stages.
+ * thfhe_linear_lut_bootstrap_wo_keyswitch: the same without the key switch, out = HOST int32[count][M][theta][N+1].
+ * thfhe_mk_*: the same on a 3-gen context, tv HOST int64[n_luts][N] as in thfhe_mk_lut_bootstrap.
+ * thfhe_set_linear_slice / thfhe_mk_set_linear_slice: the most PBS jobs (sample x output) of one slice, 1 .. 2^20, default 4096.  A call runs
+ *   in slices of whole samples, at least one sample each (a sample with M above the cap runs alone): only a slice's inputs go up and only its
+ *   records come down.  The result does not depend on the setting.
+ * thfhe_linear_last_timings / thfhe_mk_linear_last_timings: with profiling on (thfhe_set_profiling), ms[3] = {input upload, linear kernel, upload
+ *   start .. end of the key switch} of the last slice of the last dense-layer call, by device events; a call without a key switch ends ms[2] at
+ *   the kernel's end.  thfhe_last_timings keeps answering for the PBS stages of that slice.  THFHE_E_INVALID before any profiled call.
+ * thfhe_linear_tile: the kernel's output tile and reduction tile (tests place their edges there).
+ * Checks, on the host before a context or a device is touched (THFHE_E_INVALID): null W, in, out (or tv), M or K outside 1 .. 65536, theta
+ * not in {1, 2, 4}, n_luts outside 1 .. 1024, a lut_index entry outside 0 .. n_luts-1.  count 0 returns THFHE_OK.  in and out must not overlap. */
+int thfhe_lwe_linear(thfhe_ctx *ctx, const int32_t *W, const int32_t *bias, int M, int K, const int32_t *in, int32_t *out, size_t count);
+int thfhe_linear_lut_bootstrap(thfhe_ctx *ctx, const int32_t *W, const int32_t *bias, int M, int K, int theta, const int32_t *tv, int n_luts,
+                               const int32_t *lut_index, const int32_t *in, int32_t *out, size_t count);
+int thfhe_linear_lut_bootstrap_wo_keyswitch(thfhe_ctx *ctx, const int32_t *W, const int32_t *bias, int M, int K, int theta, const int32_t *tv,
+                                            int n_luts, const int32_t *lut_index, const int32_t *in, int32_t *out_N1, size_t count);
+int thfhe_set_linear_slice(thfhe_ctx *ctx, size_t jobs);
+int thfhe_linear_last_timings(thfhe_ctx *ctx, float ms[3]);
+int thfhe_linear_tile(int *tile_m, int *tile_k);
+int thfhe_mk_lwe_linear(thfhe_mk_ctx *ctx, const int32_t *W, const int32_t *bias, int M, int K, const int32_t *in, int32_t *out, size_t count);
+int thfhe_mk_linear_lut_bootstrap(thfhe_mk_ctx *ctx, const int32_t *W, const int32_t *bias, int M, int K, int theta, const int64_t *tv, int n_luts,
+                                  const int32_t *lut_index, const int32_t *in, int32_t *out, size_t count);
+int thfhe_mk_linear_lut_bootstrap_wo_keyswitch(thfhe_mk_ctx *ctx, const int32_t *W, const int32_t *bias, int M, int K, int theta, const int64_t *tv,
+                                               int n_luts, const int32_t *lut_index, const int32_t *in, int32_t *out_N1, size_t count);
+int thfhe_mk_set_linear_slice(thfhe_mk_ctx *ctx, size_t jobs);
+int thfhe_mk_linear_last_timings(thfhe_mk_ctx *ctx, float ms[3]);
+
 /* ---- multi-value two-digit trees on the 3-gen engine: thfhe_tree_lut_bootstrap_mvk restated on Torus64, every parameter family.
  *
  * thfhe_mk_tree_lut_bootstrap_mvk: out[s][j] = f_{t,j}(hi_s, lo_s), j < k, t = table_index[s], in 1 + k rotations per sample.  Three stages per slice

@@ -27,6 +27,8 @@
 //                             Torus64 RLWE sums under Z = sum_q z_q, box packing of p of them, accumulator start on both polynomials
 //   mk_pack_rows_wide_kernel (thfhe_mk_pack.h)   the row sums of large packings, a key row fetched once per 32 records; with
 //                             mk_extract_mv_kernel as level 1 the multi-value tree thfhe_mk_tree_lut_bootstrap_mvk: 1 + k rotations for k functions
+//   lwe_linear_kernel (thfhe_linear.h, shared with thfhe_sk.hip)   dense layer (thfhe_mk_lwe_linear, thfhe_mk_linear_lut_bootstrap): integer
+//                             matrix x vector of P n + 1-word records mod 2^32, the sums staying on the device for the PBS of the same call
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -953,6 +955,7 @@ struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     DevBuf d_bara, d_barb, d_u, d_tmp;
     DevBuf d_tv, d_lut_idx;     // programmable bootstrap: Torus64 test-vector table and per-sample table index (grow-only)
     Stage stage;
+    LinBufs lin;      // dense layer (thfhe_mk_lwe_linear, thfhe_mk_linear_lut_bootstrap)
     DagBuffers dag;   // gate-DAG executor tables (thfhe_dag.h)
     size_t dag_slice = 8192;  // gates per launch of a DAG level
     // multi-value bootstrap (thfhe_mk_mv_lut_bootstrap): the factor tables of a flat call (d_tv holds its base vector); the base vectors
@@ -1210,6 +1213,13 @@ int mk_dag_gate_class(thfhe_mk_ctx *c, int cls, const int32_t *d_ops, size_t n) 
 // dag_execute's ensure (dag_ensure, thfhe_pbs_host.h) on this engine's workspace
 int mk_dag_ensure(thfhe_mk_ctx *c, size_t max_gates, int theta_max, int32_t **in, int32_t **out) {
     return dag_ensure(c, max_gates, theta_max, in, out, [&](size_t jobs, int theta) { return mk_ensure_workspace(c, jobs, theta); });
+}
+
+// thfhe_mk_lwe_linear / thfhe_mk_linear_lut_bootstrap(_wo_keyswitch): ctx_linear (thfhe_pbs_host.h) on this engine's workspace and PBS stage
+int mk_linear(thfhe_mk_ctx *c, const int32_t *W, const int32_t *bias, int M, int K, bool fused, int theta, const int64_t *tv, int n_luts,
+              const int32_t *lut_index, const int32_t *in, int32_t *out, size_t count, bool keyswitch) {
+    return ctx_linear(c, W, bias, M, K, fused, theta, tv, n_luts, lut_index, in, out, count, keyswitch,
+                      [&](size_t jobs, int th) { return mk_ensure_workspace(c, jobs, th); }, [&](auto &&...a) { return mk_enqueue_pbs(c, a...); });
 }
 
 // thfhe_mk_lut_bootstrap(_enc)(_wo_keyswitch): ctx_lut_bootstrap (thfhe_pbs_host.h) on this engine's workspace and PBS stage; the encrypted tables
@@ -1860,6 +1870,24 @@ int thfhe_mk_pack_kernel_name(const thfhe_mk_ctx *c, size_t count, char *buf, in
     std::lock_guard<std::mutex> g(const_cast<thfhe_mk_ctx *>(c)->mu);   // the threshold is set under it
     return kernel_name_result(len, launch_plan::mk_pack_kernel_name(count, c->pack_wide_threshold, buf, len > 0 ? (size_t)len : 0));
 }
+
+int thfhe_mk_lwe_linear(thfhe_mk_ctx *c, const int32_t *W, const int32_t *bias, int M, int K, const int32_t *in, int32_t *out, size_t count) {
+    return mk_linear(c, W, bias, M, K, false, 1, nullptr, 1, nullptr, in, out, count, false);
+}
+
+int thfhe_mk_linear_lut_bootstrap(thfhe_mk_ctx *c, const int32_t *W, const int32_t *bias, int M, int K, int theta, const int64_t *tv, int n_luts,
+                                  const int32_t *lut_index, const int32_t *in, int32_t *out, size_t count) {
+    return mk_linear(c, W, bias, M, K, true, theta, tv, n_luts, lut_index, in, out, count, true);
+}
+
+int thfhe_mk_linear_lut_bootstrap_wo_keyswitch(thfhe_mk_ctx *c, const int32_t *W, const int32_t *bias, int M, int K, int theta, const int64_t *tv, int n_luts,
+                                               const int32_t *lut_index, const int32_t *in, int32_t *out_N1, size_t count) {
+    return mk_linear(c, W, bias, M, K, true, theta, tv, n_luts, lut_index, in, out_N1, count, false);
+}
+
+int thfhe_mk_set_linear_slice(thfhe_mk_ctx *c, size_t jobs) { return ctx_set_linear_slice(c, jobs); }
+
+int thfhe_mk_linear_last_timings(thfhe_mk_ctx *c, float ms[3]) { return ctx_linear_last_timings(c, ms); }
 
 int thfhe_mk_set_tree_slice(thfhe_mk_ctx *c, size_t max_candidates) {
     if (!c || max_candidates < 1 || max_candidates > ((size_t)1 << 18)) return thfhe_fail(THFHE_E_INVALID, "slice must be 1 .. 2^18 candidates");

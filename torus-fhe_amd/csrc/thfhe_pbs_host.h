@@ -7,9 +7,11 @@
 #define THFHE_PBS_HOST_H
 
 #include <algorithm>
+#include <vector>
 
 #include "thfhe_dag.h"
 #include "thfhe_devctx.h"
+#include "thfhe_linear.h"
 #include "thfhe_lut_prologue.h"
 
 namespace {
@@ -79,6 +81,62 @@ int ctx_mv_lut_bootstrap(Ctx *c, const thfhe_lut_spec *sp, const T *tv0, const i
         return pbs(LutFlatSrc<LutIdx::none>{c->stage.in_ptr(0), c->stage.in_ptr(1), c->stage.in_ptr(2), s, 1, nullptr}, S, table_index ? d_idx : nullptr,
                    keyswitch ? c->stage.out_ptr() : nullptr, last);
     }, keyswitch ? c->stage.out_ptr() : c->d_u.template as<int32_t>(), out, q * (keyswitch ? words : N + 1));
+}
+
+// thfhe_lwe_linear, thfhe_linear_lut_bootstrap(_wo_keyswitch) and their thfhe_mk_ forms: x = W in + bias per sample, and (fused) the PBS
+// of every x[s][m] on table lut_index[m], theta records each.  In slices of whole samples (linear_plan, at most c->lin.slice jobs): only a slice's
+// K input records per sample go up, lwe_linear_kernel writes its S M sums into c->lin.x, the engine's PBS stage reads them there as a flat
+// one-input source (weight 1, bias 0: the instantiation of the flat LUT call), and only the slice's records come down (ctx_sliced).  The table
+// indices repeat with period M and a slice starts at a whole sample, so one expanded array serves every slice.  fused false: out = x, and tv,
+// theta (1), n_luts, lut_index, keyswitch, grow and pbs are not looked at.
+template <typename Ctx, typename T, typename Grow, typename Pbs>
+int ctx_linear(Ctx *c, const int32_t *W, const int32_t *bias, int M, int K, bool fused, int theta, const T *tv, int n_luts, const int32_t *lut_index,
+               const int32_t *in, int32_t *out, size_t count, bool keyswitch, Grow grow, Pbs pbs) {
+    THFHE_TRY(linear_validate(W, M, K, in, out, count, fused, tv, theta, n_luts, lut_index));
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    if (count == 0) return THFHE_OK;
+    DevLock lk(*c);
+    if (lk.rc) return lk.rc;
+    const size_t rec = c->rec_words(), N = c->p.N, out_rec = fused && !keyswitch ? N + 1 : rec;
+    const size_t S_max = linear_plan::samples_per_slice(count, (size_t)M, c->lin.slice), jobs_max = S_max * M;
+    const size_t w_bytes = (size_t)M * K * sizeof(int32_t), tv_bytes = (size_t)n_luts * N * sizeof(T);
+    int rc = c->lin.w.grow(w_bytes);
+    if (!rc && bias) rc = c->lin.bias.grow(M * sizeof(int32_t));
+    if (!rc) rc = c->lin.in.grow(S_max * K * rec * sizeof(int32_t));
+    if (!rc) rc = c->lin.x.grow(jobs_max * rec * sizeof(int32_t));
+    if (!rc && fused) rc = grow(jobs_max, theta);
+    if (!rc && fused) rc = c->d_tv.grow(tv_bytes);
+    if (!rc && fused && keyswitch) rc = c->stage.out.grow(jobs_max * theta * rec * sizeof(int32_t));
+    if (!rc && fused && lut_index) rc = c->d_lut_idx.grow(jobs_max * sizeof(int32_t));
+    if (rc) return rc;
+    int32_t *const d_in = c->lin.in.template as<int32_t>(), *const d_x = c->lin.x.template as<int32_t>();
+    int32_t *const d_w = c->lin.w.template as<int32_t>(), *const d_bias = bias ? c->lin.bias.template as<int32_t>() : nullptr;
+    int32_t *const d_idx = fused && lut_index ? c->d_lut_idx.template as<int32_t>() : nullptr;
+    THFHE_HIP(hipMemcpyAsync(d_w, W, w_bytes, hipMemcpyHostToDevice, c->stream));
+    if (bias) THFHE_HIP(hipMemcpyAsync(d_bias, bias, M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    std::vector<int32_t> idx;   // lives until ctx_sliced has drained the stream
+    if (fused) THFHE_HIP(hipMemcpyAsync(c->d_tv.template as<T>(), tv, tv_bytes, hipMemcpyHostToDevice, c->stream));
+    if (d_idx) {
+        idx.resize(jobs_max);
+        for (size_t j = 0; j < jobs_max; j++) idx[j] = lut_index[j % M];
+        THFHE_HIP(hipMemcpyAsync(d_idx, idx.data(), jobs_max * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    const int32_t *const res = !fused ? d_x : keyswitch ? c->stage.out_ptr() : c->d_u.template as<int32_t>();
+    return ctx_sliced(c, count, S_max, {nullptr, nullptr, nullptr}, nullptr, nullptr, [&](size_t s0, size_t S, bool last) {
+        const linear_plan::Slice sl = linear_plan::slice_at(s0 / S_max, count, S_max, M, K, theta, rec, out_rec);
+        const bool ev = last && c->profiling;   // thfhe_linear_last_timings: the last slice's upload and kernel
+        if (ev) THFHE_TRY(c->lin.events());
+        if (ev) THFHE_HIP(hipEventRecord(c->lin.ev[0], c->stream));
+        THFHE_HIP(hipMemcpyAsync(d_in, in + sl.in_off, S * K * rec * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if (ev) THFHE_HIP(hipEventRecord(c->lin.ev[1], c->stream));
+        lwe_linear_launch(d_in, d_w, d_bias, d_x, S, M, K, (int)rec, c->stream);
+        if (ev) THFHE_HIP(hipEventRecord(c->lin.ev[2], c->stream));
+        if (ev) c->lin.ev_valid = true, c->lin.ev_whole = fused && keyswitch;
+        THFHE_HIP(hipGetLastError());
+        if (!fused) return (int)THFHE_OK;
+        return pbs(LutFlatSrc<LutIdx::none>{d_x, d_x, d_x, thfhe_lut_spec{1, {1, 0, 0}, 0, theta}, 1, nullptr}, sl.jobs, c->d_tv.template as<T>(), (const T *)nullptr,
+                   theta, d_idx, keyswitch ? c->stage.out_ptr() : nullptr, last);
+    }, res, out, (size_t)M * theta * out_rec);
 }
 
 // ---- the two-digit tree ----

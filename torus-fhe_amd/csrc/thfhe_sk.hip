@@ -18,6 +18,9 @@
 //   (thfhe_keyswitch.h, shared with the multi-key engines): one gate per workgroup (small batches); from 192 gates on the rows of a few
 //                             (i, j) staged in LDS for 32 gates, the digit selecting an address; from 512 gates on an int8 GEMM on the matrix cores
 //   sk_linear_kernel          NOT / COPY (J/gates.jl:76-79)
+//   lwe_linear_kernel         dense layer (thfhe_lwe_linear, thfhe_linear_lut_bootstrap): integer matrix x LWE vector mod 2^32, the sums
+//   (thfhe_linear.h, shared   staying on the device for the PBS of the same call
+//   with thfhe_mk.hip)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -564,6 +567,7 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     size_t tree_slice = 65536;   // level-1 candidates (samples x p_hi) per slice: bounds the workspace (8 KiB of T_i scratch per candidate); also the output records (samples x q) per slice of thfhe_mv_lut_bootstrap
     // staging for the host-buffer API
     Stage stage;
+    LinBufs lin;   // dense layer (thfhe_lwe_linear, thfhe_linear_lut_bootstrap)
     // gate-DAG executor: wire table and index tables (grow-only, reused by every thfhe_dag_run on this context)
     DagBuffers dag;
     size_t dag_slice = 28672;  // gates per launch of a DAG level: 14 x 2048 (a MUX slice is 57 344 rotations); it sizes the staging arrays, not the prologue's grid: the runtime runs grid.y > 65 535 (66 636 rotations in one call, tests/test_gpu_large_batch.py)
@@ -726,6 +730,13 @@ int lut_bootstrap(thfhe_ctx *c, const thfhe_lut_spec *sp, const int32_t *tv, int
                   const int32_t *in1, const int32_t *in2, int32_t *out, size_t count, bool keyswitch, bool enc = false, const int32_t *tv_a = nullptr) {
     return ctx_lut_bootstrap(c, sp, tv, tv_a, enc, n_luts, lut_index, in0, in1, in2, out, count, keyswitch,
                              [&](size_t jobs, int theta) { return ensure_workspace(c, jobs, theta); }, [&](auto &&...a) { return enqueue_pbs(c, a...); });
+}
+
+// thfhe_lwe_linear / thfhe_linear_lut_bootstrap(_wo_keyswitch): ctx_linear (thfhe_pbs_host.h) on this engine's workspace and PBS stage
+int linear(thfhe_ctx *c, const int32_t *W, const int32_t *bias, int M, int K, bool fused, int theta, const int32_t *tv, int n_luts, const int32_t *lut_index,
+           const int32_t *in, int32_t *out, size_t count, bool keyswitch) {
+    return ctx_linear(c, W, bias, M, K, fused, theta, tv, n_luts, lut_index, in, out, count, keyswitch,
+                      [&](size_t jobs, int th) { return ensure_workspace(c, jobs, th); }, [&](auto &&...a) { return enqueue_pbs(c, a...); });
 }
 
 // Grow-only workspace of one tree chain over S samples / nodes: S R level-1 jobs of theta_lo records each (a SELECT group, whose candidates are
@@ -1245,6 +1256,26 @@ int thfhe_lut_bootstrap_enc_wo_keyswitch(thfhe_ctx *c, const thfhe_lut_spec *spe
                                          size_t count) {
     return lut_bootstrap(c, spec, tv_b, n_luts, lut_index, in0, in1, in2, out_N1, count, false, true, tv_a);
 }
+
+int thfhe_lwe_linear(thfhe_ctx *c, const int32_t *W, const int32_t *bias, int M, int K, const int32_t *in, int32_t *out, size_t count) {
+    return linear(c, W, bias, M, K, false, 1, nullptr, 1, nullptr, in, out, count, false);
+}
+
+int thfhe_linear_lut_bootstrap(thfhe_ctx *c, const int32_t *W, const int32_t *bias, int M, int K, int theta, const int32_t *tv, int n_luts,
+                               const int32_t *lut_index, const int32_t *in, int32_t *out, size_t count) {
+    return linear(c, W, bias, M, K, true, theta, tv, n_luts, lut_index, in, out, count, true);
+}
+
+int thfhe_linear_lut_bootstrap_wo_keyswitch(thfhe_ctx *c, const int32_t *W, const int32_t *bias, int M, int K, int theta, const int32_t *tv, int n_luts,
+                                            const int32_t *lut_index, const int32_t *in, int32_t *out_N1, size_t count) {
+    return linear(c, W, bias, M, K, true, theta, tv, n_luts, lut_index, in, out_N1, count, false);
+}
+
+int thfhe_set_linear_slice(thfhe_ctx *c, size_t jobs) { return ctx_set_linear_slice(c, jobs); }
+
+int thfhe_linear_last_timings(thfhe_ctx *c, float ms[3]) { return ctx_linear_last_timings(c, ms); }
+
+int thfhe_linear_tile(int *tile_m, int *tile_k) { return linear_tile(tile_m, tile_k); }
 
 int thfhe_set_tree_slice(thfhe_ctx *c, size_t max_candidates) {
     if (!c || max_candidates < 1 || max_candidates > ((size_t)1 << 20)) return thfhe_fail(THFHE_E_INVALID, "slice must be 1 .. 2^20 candidates");

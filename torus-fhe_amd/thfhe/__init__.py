@@ -351,6 +351,17 @@ SIGNATURES = {
     "thfhe_mk_tree_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
                                               _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_set_tree_slice": (C.c_int, [_vp, C.c_size_t]),
+    "thfhe_lwe_linear": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, _i32p, _i32p, C.c_size_t]),
+    "thfhe_linear_lut_bootstrap": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_linear_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_set_linear_slice": (C.c_int, [_vp, C.c_size_t]),
+    "thfhe_linear_last_timings": (C.c_int, [_vp, C.POINTER(C.c_float)]),
+    "thfhe_linear_tile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "thfhe_mk_lwe_linear": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, _i32p, _i32p, C.c_size_t]),
+    "thfhe_mk_linear_lut_bootstrap": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i64p, C.c_int, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_mk_linear_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i64p, C.c_int, _i32p, _i32p, _i32p, C.c_size_t]),
+    "thfhe_mk_set_linear_slice": (C.c_int, [_vp, C.c_size_t]),
+    "thfhe_mk_linear_last_timings": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "thfhe_mk_tree_lut_bootstrap_mvk": (C.c_int, [_vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, C.c_int, C.c_int, _i64p, _i32p, C.c_int, _i32p, C.c_int64,
                                                   _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_set_pack_wide_threshold": (C.c_int, [_vp, C.c_size_t]),
@@ -705,6 +716,71 @@ class _EvalKey(_Handle):
         fn = self._fn("mv_lut_bootstrap" if keyswitch else "mv_lut_bootstrap_wo_keyswitch")
         _check(fn(self.h, C.byref(spec), self._ptv(tv0), _p32(w), w.shape[2], w.shape[1], w.shape[0], _p32(idx), *extra, p[0], p[1], p[2], _p32(out), count))
         return out
+
+    # -- encrypted dense layers (thfhe_lwe_linear, thfhe_linear_lut_bootstrap and their thfhe_mk_ forms) --------------------------
+    def lwe_linear(self, W, x, bias=None):
+        """An integer matrix times a vector of records, word-wise mod 2^32: out[s][m] = sum_k W[m][k] * x[s][k] + (0, bias[m]).
+        W: int32[M][K] (any int32 values, the products wrap); x: int32[count][K][words]; bias: M Torus32 words or None.
+        Returns int32[count, M, words]."""
+        W, x, b = self._linear_args(W, x, bias)
+        out = np.empty((x.shape[0], W.shape[0], self.words), np.int32)
+        _check(self._fn("lwe_linear")(self.h, _p32(W), _p32(b), W.shape[0], W.shape[1], _p32(x), _p32(out), x.shape[0]))
+        return out
+
+    def linear_lut_bootstrap(self, tv, W, x, bias=None, theta=1, lut_index=None):
+        """A dense layer and its activation in one call: lwe_linear(W, x, bias), then output m of every sample bootstrapped on table
+        tv[lut_index[m]] (table 0 without an index), theta records each; the sums never leave the device.  Word for word what lwe_linear followed by
+        lut_bootstrap(tv, sums, theta=theta) returns.  tv: [n_luts][N] test vectors of the ring's torus; lut_index: M entries, one per OUTPUT.
+        Every reachable sum of messages must stay in [0, p) of the tables' encoding (thfhe.circuits.dense_bias).  Returns int32[count, M, theta, words]."""
+        return self._linear_lut(tv, W, x, bias, theta, lut_index, True)
+
+    def linear_lut_bootstrap_wo_keyswitch(self, tv, W, x, bias=None, theta=1, lut_index=None):
+        """linear_lut_bootstrap without the key switch: int32[count, M, theta, N+1] records under the ring key."""
+        return self._linear_lut(tv, W, x, bias, theta, lut_index, False)
+
+    def _linear_args(self, W, x, bias):
+        W = np.ascontiguousarray(W, np.int32)
+        x = np.ascontiguousarray(x, np.int32)
+        if W.ndim != 2 or W.size == 0:
+            raise ValueError("W: expected int32[M][K]")
+        if x.ndim == 2:
+            x = x[None]
+        if x.ndim != 3 or x.shape[1] != W.shape[1] or x.shape[2] != self.words:
+            raise ValueError(f"x: expected int32[count][{W.shape[1]}][{self.words}], got shape {x.shape}")
+        b = None
+        if bias is not None:
+            b = np.array([_wrap32(v) for v in np.asarray(bias).reshape(-1)], np.int32)
+            if b.shape[0] != W.shape[0]:
+                raise ValueError(f"bias holds {b.shape[0]} entries for {W.shape[0]} outputs")
+        return W, x, b
+
+    def _linear_lut(self, tv, W, x, bias, theta, lut_index, keyswitch):
+        W, x, b = self._linear_args(W, x, bias)
+        tv = np.ascontiguousarray(tv, self._tv_dtype).reshape(-1, self.params.N)
+        idx = _index("lut_index", lut_index, W.shape[0])
+        out = np.empty((x.shape[0], W.shape[0], _theta_records(theta), self.words if keyswitch else self.params.N + 1), np.int32)
+        fn = self._fn("linear_lut_bootstrap" if keyswitch else "linear_lut_bootstrap_wo_keyswitch")
+        _check(fn(self.h, _p32(W), _p32(b), W.shape[0], W.shape[1], int(theta), self._ptv(tv), tv.shape[0], _p32(idx), _p32(x), _p32(out), x.shape[0]))
+        return out
+
+    def set_linear_slice(self, jobs):
+        """The most PBS jobs (samples x outputs) of one slice of a dense-layer call; a slice holds whole samples, at least one.  The result does not
+        depend on it."""
+        _check(self._fn("set_linear_slice")(self.h, int(jobs)))
+
+    def linear_last_timings(self):
+        """Device-event times of the last slice of the last dense-layer call made with profiling on: the input upload, lwe_linear_kernel, and upload
+        start .. end of the key switch (the kernel's end for a call without one)."""
+        ms = (C.c_float * 3)()
+        _check(self._fn("linear_last_timings")(self.h, ms))
+        return dict(upload_ms=ms[0], linear_ms=ms[1], total_ms=ms[2])
+
+    @staticmethod
+    def linear_tile():
+        """(tile_m, tile_k): the outputs and the reduction steps lwe_linear_kernel handles per pass (where a test places its edges)."""
+        tm, tk = C.c_int(), C.c_int()
+        _check(lib().thfhe_linear_tile(C.byref(tm), C.byref(tk)))
+        return tm.value, tk.value
 
     # -- device-buffer calls -----------------------------------------------------------------------
     def _alloc(self, n):

@@ -1621,3 +1621,57 @@ def _evaluate_levels(ck, cir, vals, pack, tgsw_sets, instance, one_rotation, com
             vals[base + np.array(mux)] = ck.gates(MUX, a, b, c)
             launches += 1
     return launches
+
+
+# ---- encrypted dense layers (CloudKey.lwe_linear / linear_lut_bootstrap): the plaintext side -------------------------------------------
+def dense_plain(W, bias_msgs, m, p):
+    """The plaintext twin of a dense layer on messages: (m @ W^T + bias_msgs) mod 2p for messages m int[count][K] (or int[K]) in the padding-bit
+    encoding of modulus p.  bias_msgs: M integer message offsets (dense_bias_messages) or None.  A value in p .. 2p-1 has left the valid half of
+    the torus: the table that follows would read it negated."""
+    W = np.asarray(W, np.int64)
+    m = np.asarray(m, np.int64)
+    s = m @ W.T
+    if bias_msgs is not None:
+        s = s + np.asarray(bias_msgs, np.int64)
+    return s % (2 * p)
+
+
+def dense_bias_messages(W, p, lo=0, m_max=None):
+    """The integer message offset of every output that moves its smallest reachable sum to message `lo`, the inputs being messages in 0 .. m_max
+    (default p - 1): lo - sum_k min(0, W[m][k]) m_max.  Raises ValueError if an output's reachable sums then do not fit in [0, p): such a
+    layer needs a larger p, smaller weights or fewer inputs."""
+    W = np.asarray(W, np.int64)
+    m_max = p - 1 if m_max is None else int(m_max)
+    low = np.minimum(W, 0).sum(axis=1) * m_max
+    high = np.maximum(W, 0).sum(axis=1) * m_max
+    off = lo - low
+    if lo < 0 or np.any(high + off >= p):
+        raise ValueError(f"dense layer: reachable sums span up to {int((high - low).max()) + 1} messages from lo = {lo}, the encoding holds {p}")
+    return off
+
+
+def dense_bias(W, p, lo=0, m_max=None):
+    """dense_bias_messages as the Torus32 bias words (int32[M]) linear_lut_bootstrap takes.  The padding-bit encoding needs EVERY reachable
+    sum_k W[m][k] m_k + bias inside [0, p); the library adds words mod 2^32 and cannot see a sum that left the range -- keeping it inside is
+    the caller's duty, and this function refuses a layer whose range cannot fit."""
+    off = dense_bias_messages(W, p, lo, m_max)
+    return ((off * ((1 << 32) // (2 * p))) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def conv2d_weights(kernel, in_shape, stride=1):
+    """The dense W of a valid 2-D convolution (cross-correlation, as neural networks use the word), so that a convolution layer is the same call:
+    out[f][y][x] = sum_{i,j} kernel[f][i][j] in[y stride + i][x stride + j].  kernel: int[kh][kw] or int[F][kh][kw]; in_shape = (H, Wd); inputs
+    flattened row-major (K = H Wd), outputs row-major per filter (M = F oh ow, oh = (H - kh) // stride + 1).  Returns int32[M][K]."""
+    k = np.asarray(kernel, np.int64)
+    if k.ndim == 2:
+        k = k[None]
+    H, Wd = in_shape
+    F, kh, kw = k.shape
+    if stride < 1 or kh > H or kw > Wd:
+        raise ValueError("conv2d_weights: the kernel must fit the input and stride must be >= 1")
+    oh, ow = (H - kh) // stride + 1, (Wd - kw) // stride + 1
+    out = np.zeros((F, oh, ow, H, Wd), np.int64)
+    for y in range(oh):
+        for x in range(ow):
+            out[:, y, x, y * stride:y * stride + kh, x * stride:x * stride + kw] = k
+    return out.reshape(F * oh * ow, H * Wd).astype(np.int32)
