@@ -228,38 +228,20 @@ __device__ __forceinline__ void wave_fft_fwd_q(int lane, cplx (&z)[8], cplx *xb,
 // variant "x" (the ring kernel; thfhe_lane.h): the exchange of register bits (2, 1, 0) with lane bits (3, 5, 4).  Its own inverse.  The two swap
 // stages are the expensive ones: a lane swap holds the vector pipe about twice as long as a DPP move (tools/probes/issue_probe.hip: 9.25 against
 // 5.0 cycles per instruction for a wave alone, 13.0 against 8.9 beside an FP64 wave), and there is one per dword pair either way.
-//   lane bit 3 <-> register bit 2   FLIPPED: one unmasked row_ror:8 move per dword of registers 4 .. 7 (16 instructions; the lanes with bit 3 set
-//                                   hold the pairs (r, r + 4) the other way round, before and after); else the two masked moves and the kept copy
-//                                   of wave_transpose_hi3<true> on the pairs (r, r + 4) (32 moves + one 64-bit copy per double)
+//   lane bit 3 <-> register bit 2   one unmasked row_ror:8 move per dword of registers 4 .. 7 (16 instructions): an exchange because the lanes with
+//                                   bit 3 set hold the pairs (r, r + 4) the other way round, before and after (variants "x" and "p" in
+//                                   thfhe_lane.h say who produces and who consumes the flipped names).  With natural names on every lane the stage
+//                                   is two masked moves and a kept 64-bit copy per double, 40 instructions (tests/emu/exchange_emu.cpp keeps it)
 //   lane bit 5 <-> register bit 1   v_permlane32_swap
 //   lane bit 4 <-> register bit 0   v_permlane16_swap
-template <bool FLIPPED>
 __device__ __forceinline__ void wave_transpose_x3(cplx (&z)[8]) {
     uint32_t w[8][4];
 #pragma unroll
     for (int r = 0; r < 8; r++) __builtin_memcpy(w[r], &z[r], 16);
-    if constexpr (FLIPPED) {
 #pragma unroll
-        for (int r = 4; r < 8; r++)
+    for (int r = 4; r < 8; r++)
 #pragma unroll
-            for (int d = 0; d < 4; d++) w[r][d] = __builtin_amdgcn_update_dpp(w[r][d], w[r][d], 0x128, 0xF, 0xF, false);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                uint64_t keep = (uint64_t)w[r + 4][2 * k] | (uint64_t)w[r + 4][2 * k + 1] << 32;
-                asm("" : "+v"(keep));
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const int d = 2 * k + h;
-                    const uint32_t a = w[r][d], b = w[r + 4][d], kept = (uint32_t)(keep >> (32 * h));
-                    w[r + 4][d] = __builtin_amdgcn_update_dpp(b, a, 0x128, 0xF, 0x3, false);
-                    w[r][d] = __builtin_amdgcn_update_dpp(a, kept, 0x128, 0xF, 0xC, false);
-                }
-            }
-        }
-    }
+        for (int d = 0; d < 4; d++) w[r][d] = __builtin_amdgcn_update_dpp(w[r][d], w[r][d], 0x128, 0xF, 0xF, false);
 #pragma unroll
     for (int d = 0; d < 4; d++) {
 #pragma unroll
@@ -279,12 +261,14 @@ __device__ __forceinline__ void wave_transpose_x3(cplx (&z)[8]) {
 #pragma unroll
     for (int r = 0; r < 8; r++) __builtin_memcpy(&z[r], w[r], 16);
 }
-// r = the forward roots of lane_nu(lane); spectra come out at lane nu, register k2
-__device__ __forceinline__ void wave_fft_fwd_x(int lane, cplx (&z)[8], cplx *xb, const LaneRootsF &r) {
-    fwdf_seg1(z);
-    wave_transpose_x3<false>(z);
+// Forward of the ring kernel: variant "p" (thfhe_lane.h), the unmasked exchange.  z = the coefficients nu + 64 m of nu = lane_nu(lane), r = the forward
+// roots of nu, flip = lane_flip_x(lane); spectra come out at lane nu, register k2 -- times rho^(-32) on the lanes with bit 3 set, which the PHASED key
+// copy (thfhe_ctx::d_bk_ring) undoes in the product.  Not for a kernel that multiplies with the plain key.
+__device__ __forceinline__ void wave_fft_fwd_x(int lane, cplx (&z)[8], cplx *xb, const LaneRootsF &r, uint32_t flip) {
+    fwdp_seg1(z, flip);
+    wave_transpose_x3(z);
     wave_sync();
-    fwdx_seg2_st(lane, z, xb, r);
+    fwdp_seg2_st(lane, z, xb, r, flip);
     wave_sync();
     fwdf_seg3(lane, z, xb, r);
 }
@@ -297,8 +281,8 @@ __device__ __forceinline__ void wave_fft_inv_x(int lane, cplx (&z)[8], cplx *xb,
     wave_sync();
     inv_seg2_ld(lane, z, xb);
     invf_seg2(z, w);
-    wave_transpose_x3<true>(z);
-    invx_seg3(z, r, flip, bc);
+    wave_transpose_x3(z);
+    invx_seg3_ring(z, r, flip, bc);
 }
 // variant "qs" (multi-key kernels, whose LDS has no room for padded buffers): first transpose in registers, pass-1 twiddles from the
 // per-lane roots, second transpose through the XOR-swizzled 512-slot buffer -- one LDS crossing and no T1 table reads per transform

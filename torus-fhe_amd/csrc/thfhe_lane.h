@@ -472,9 +472,9 @@ THFHE_FN void invf_seg3(cplx (&z)[8], const LaneRoots &r, const cplx (&bc)[4]) {
 //           and the u / v halves become the even / odd outputs: X'_j = conj(W^4) (-1)^j X_j, W = conj(s), s = zeta^(4 nu).  The untwist is a product
 //           with per-lane constants anyway: those lanes build it from b s^4 = zeta^(17 nu) (= T1[4][nu], exact from the table) and negate the odd
 //           ones (make_untwist_x).  Cost per transform: one XOR on the sign of Im W^4.
-// Forward: the same pairing with the masked moves of "q" (natural names on every lane).  The unmasked stage is NOT taken there: the pass after the
-// exchange would leave the factor conj(s'^4) = rho^(-32) (rho the spectrum point's root) on the spectra of half the lanes; a folded pass cannot
-// absorb a scalar, the key must not carry it, and taking it out in the inverse's first stage costs three complex products per inverse transform.
+// Forward of "x": the same pairing with the masked moves of "q" (natural names on every lane, natural coefficient lanes on entry: fwdx_seg2_st).  No
+// kernel runs it any more -- the ring kernel's forward is variant "p" below, the unmasked stage over a phased key copy -- it stays as the form with the
+// PLAIN key that the host replays check "p" against word for word (tests/emu/exchange_emu.cpp, fwd_exchange_emu.cpp).
 THFHE_FN int lane_nu(int lane) { return (lane & 7) | ((lane & 8) << 2) | ((lane & 0x30) >> 1); }
 THFHE_FN uint32_t lane_flip_x(int lane) { return (lane & 8) ? 0x80000000u : 0u; }   // XORed into the high word of a double: its sign on the lanes with bit 3 set
 THFHE_FN double flip_sign(double v, uint32_t flip) {
@@ -518,6 +518,56 @@ THFHE_FN void invx_seg3(cplx (&z)[8], const LaneRoots &r, uint32_t flip, const c
         z[m + 4] = cmul_conj(cplx{R * (z[m + 4].re + z[m + 4].im), R * (z[m + 4].im - z[m + 4].re)}, bc[m]);
     }
 }
+
+// The ring kernel's form of invx_seg3: the outputs m + 4 come out WITHOUT the scale R of conj(C[4]) = R (1 - i), i.e. as (true value) / R; the ring
+// kernel's accumulator update (acc_update16_ring below) multiplies by R inside its rounding add.  Two multiplies fewer per output m + 4.
+THFHE_FN void invx_seg3_ring(cplx (&z)[8], const LaneRoots &r, uint32_t flip, const cplx (&bc)[4]) {   // bc from make_untwist_x
+    RootPow p = root_powers<-1>(cconj(r.s));
+    p.w4.im = flip_sign(p.w4.im, flip);
+    dft8_tw<-1>(z, p);
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        z[m] = cmul_conj(z[m], bc[m]);
+        z[m + 4] = cmul_conj(cplx{z[m + 4].re + z[m + 4].im, z[m + 4].im - z[m + 4].re}, bc[m]);
+    }
+}
+
+// ---- variant "p" (the ring kernel's FORWARD transforms): the passes of "x" around the UNMASKED lane-bit-3 stage, over a pre-rotated ("phased") copy
+// of the key.  The lane holds the coefficients nu + 64 m of its natural position nu = lane_nu(lane) from the start (the digits are read at nu), so lane
+// bits (3, 5, 4) are j1 bits (2, 1, 0) before the exchange and k0 bits (2, 1, 0) after it, and the registers hold k0 before and j1 after in natural
+// order.  The lanes with bit 3 set name the pairs (r, r + 4) the other way round, before and after, as in the inverse of "x":
+//   before  pass 1 writes X_(k0 + 4) into register k0 when its root w32 = C[1] is negated.  Only the last stage's constants W, W w8 see the sign
+//           (W^2, W^4 do not).  The root is wave-uniform, so the sign costs something here: -W is a per-lane signed constant pair (loop-invariant,
+//           four registers), -W w8 a sign on the second inputs of its two butterflies (four XORs).  All four constants signed and kept: no
+//           instruction, eight registers, and the eight-wave kernel then spills with the fused rounding below; all by XORs: eight instructions;
+//   after   pass 2 finds y_(m + 4) where y_m should be.  With conj(W^4) in its first stage (one XOR, W = s' = zeta^(8 (4 k0 + 1)))
+//               y_(m+4) + conj(W^4) y_m = conj(W^4) u_m,      y_(m+4) - conj(W^4) y_m = -conj(W^4) v_m
+//           its outputs are X'_k1 = conj(s'^4) (-1)^k1 X_k1.  Pass 3 is linear, and with rho = zeta^(4 k + 1), k = k0 + 8 k1 + 64 k2, the spectrum
+//           point's root:  rho^32 = zeta^(32 (4 k0 + 1)) (-1)^k1 = s'^4 (-1)^k1.  Those lanes (k0 >= 4: bit 5 of nu) end with rho^(-32) P(rho), the
+//           spectrum of X^(-32) p.
+// A folded pass has no product that could take the scalar out, and none is needed: every digit spectrum is multiplied by the key exactly once, so the
+// key copy that this form reads carries rho^(+32) at exactly those points -- the spectrum of X^(32) b(X), an exact negacyclic rotation of the integer
+// limb polynomial (limb_pair_rot32; made by the key transform itself, thfhe_transform.h).  The products, the inverse and the accumulator see what they
+// saw.  5 sign XORs per transform replace 24 of the 40 instructions of the masked stage.
+THFHE_FN cplx flip_sign(cplx v, uint32_t flip) { return cplx{flip_sign(v.re, flip), flip_sign(v.im, flip)}; }
+THFHE_FN void fwdp_seg1(cplx (&z)[8], uint32_t flip) {
+#pragma unroll
+    for (int m = 0; m < 4; m++) bfly_c4(z[m], z[m + 4]);
+    // -W: as a signed constant (loop-invariant: two register pairs, no instruction) for the pairs that take W; for the pairs that take W w8 as a sign on
+    // their second inputs, y5 and y7, set one stage early (the stage between is linear in the two): four XORs, and no second pair of constants
+    z[5] = flip_sign(z[5], flip);
+    z[7] = flip_sign(z[7], flip);
+    dft8_tw_tail<+1>(z, flip_sign(cplx{THFHE_C_RE(1), THFHE_C_IM(1)}, flip), cplx{THFHE_C_RE(2), THFHE_C_IM(2)}, cplx{THFHE_C_RE(5), THFHE_C_IM(5)});
+}
+THFHE_FN void fwdp_seg2_st(int lane, cplx (&z)[8], cplx *xbuf, const LaneRootsF &r, uint32_t flip) {
+    RootPow p = root_powers<+1>(r.s);
+    p.w4.im = flip_sign(p.w4.im, flip);
+    dft8_tw<+1>(z, p);
+#pragma unroll
+    for (int k1 = 0; k1 < 8; k1++) xbuf[xs_c(k1, lane)] = z[k1];
+}
+constexpr int kKeyPhase = 32;   // the ring key copy holds the spectrum of X^kKeyPhase b at the points whose natural position has bit 5 set
+THFHE_FN bool key_point_phased(int nu) { return (nu & 32) != 0; }
 
 // ---- integer helpers ---------------------------------------------------------------------------------
 // coefficient q of X^a * p - p for p in LDS, a in [0, 2N)          (mul_by_monomial, J/rlwe.jl:130-131)
@@ -786,6 +836,27 @@ THFHE_FN void acc_update16(int lane, int32_t *acc_poly, const cplx (&zlo)[8], co
         acc_poly[q + 512] = (int32_t)((uint32_t)acc_poly[q + 512] + vi);
     }
 }
+// The ring kernel's update, after invx_seg3_ring.
+//   * Outputs m + 4 arrive as x / R (R = 1/sqrt 2): the scale rides in the rounding add, round(R x) = low word of fma(R, x, 1.5 * 2^52).  The fma
+//     rounds the exact R^ x + 1.5 * 2^52 once, to the nearest integer; the two-step form rounded R^ (re + im) first (one more relative u on the
+//     value) and then the sum.  The distance of the value from the integer limb sum is therefore that of the two-step form less that rounding's
+//     share, never more, and the rounded integer is the same whenever the bound holds.
+THFHE_FN uint32_t round_scaled_lo32(double x) {   // round(x / sqrt 2) as a wrapping 32-bit integer, |x| < 2^51
+    double y = __builtin_fma(0.70710678118654752440, x, 6755399441055744.0);
+    uint64_t b;
+    __builtin_memcpy(&b, &y, 8);
+    return (uint32_t)b;
+}
+THFHE_FN void acc_update16_ring(int lane, int32_t *acc_poly, const cplx (&zlo)[8], const cplx (&zhi)[8]) {
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+        const int q = lane + 64 * m;
+        const uint32_t vr = m < 4 ? round_lo32(zlo[m].re) + (round_lo32(zhi[m].re) << 16) : round_scaled_lo32(zlo[m].re) + (round_scaled_lo32(zhi[m].re) << 16);
+        const uint32_t vi = m < 4 ? round_lo32(zlo[m].im) + (round_lo32(zhi[m].im) << 16) : round_scaled_lo32(zlo[m].im) + (round_scaled_lo32(zhi[m].im) << 16);
+        acc_poly[q] = (int32_t)((uint32_t)acc_poly[q] + vr);
+        acc_poly[q + 512] = (int32_t)((uint32_t)acc_poly[q + 512] + vi);
+    }
+}
 // initial accumulator: acc = (0, X^{-barb} * (mu, ..., mu))            (J/bootstrap.jl:60-62,84)
 THFHE_FN void acc_init16(int lane, int32_t *acc_mask, int32_t *acc_body, int barb, int32_t mu) {
 #pragma unroll
@@ -933,6 +1004,19 @@ THFHE_FN cplx limb_pair(const void *poly, int q0, int q1, int h) {
         split_limbs64(p[q1], b);
         return cplx{a[h], b[h]};
     }
+}
+// limb h of the coefficients q0, q1 of X^rot b (Torus32, N = 1024, 0 <= rot < N): the balanced limb of the word the rotation brings there, negated
+// where it wraps -- the phased key copy of variant "p".  The rotation acts on the LIMB polynomial, after the split, so the phased and the plain points
+// of one spectrum belong to the same integer polynomial and |limb| <= 2^15 holds.  Splitting the rotated WORD instead gives another (lo, hi) pair
+// wherever a negated word has lo = -2^15 (-(-2^15 + 2^16 h) splits into (-2^15, 1 - h), not (2^15, -h)): the two halves of the spectrum would then
+// belong to different limb polynomials and the per-limb sums come out wrong.
+THFHE_FN cplx limb_pair_rot32(const int32_t *p, int q0, int q1, int h, int rot) {
+    const int e0 = (q0 - rot) & 2047, e1 = (q1 - rot) & 2047;
+    double l0, h0, l1, h1;
+    split_limbs32(p[e0 & 1023], l0, h0);
+    split_limbs32(p[e1 & 1023], l1, h1);
+    const double a = h == 0 ? l0 : h0, b = h == 0 ? l1 : h1;
+    return cplx{(e0 & 1024) ? -a : a, (e1 & 1024) ? -b : b};
 }
 // the limb inputs of a Torus64 key polynomial as the key transform reads them: all four limbs of a degree-1024 polynomial, limb h of a
 // degree-2048 one

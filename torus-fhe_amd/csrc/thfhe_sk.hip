@@ -100,7 +100,8 @@ THFHE_STAMP_STORAGE
 
 // arguments of the blind-rotate kernels
 struct BRArgs {
-    const cplx *bk;        // spectral key
+    const cplx *bk;        // spectral key (the cooperative kernel)
+    const cplx *bk_ring;   // its phased copy (thfhe_ctx::d_bk_ring): what the ring kernels stream
     const cplx *tw;        // T1[512] ++ T2[64]
     const int32_t *bara;   // [jobs][n_pad]
     const int32_t *barb;   // [jobs]
@@ -156,10 +157,17 @@ constexpr int kGate = 0, kLut = 1, kLutEnc = 2, kLutMv = 3;
 //     bit 3 trades with register bit 2, the pairs (r, r + 4) that a pass writes last and reads first.  In the inverse transforms that stage is 16
 //     unmasked moves: the lanes with bit 3 set name those pairs the other way round, which a negated per-lane root produces and conj(W^4), a
 //     signed and rescaled untwist constant consume -- 24 instructions fewer per transform than two masked moves and a kept 64-bit copy per
-//     double, which the forward transforms keep (a folded pass cannot absorb the scalar the flipped names would leave on the spectra).  A lane
-//     therefore stands for the natural position nu = lane_nu(lane) from the forward exchange on: key reads, roots and acc_update16 take nu; the
-//     key's order in memory and in the ring is untouched.  1 311 -> 1 223 other vector instructions per CMux and wave, 252 -> 248 VGPRs,
-//     27.74 -> 27.33 ms per 4096 gates (profiles/r11_exchange.md);
+//     double.  1 311 -> 1 223 other vector instructions per CMux and wave, 27.74 -> 27.33 ms per 4096 gates (profiles/r11_exchange.md).  The
+//     FORWARD transforms take the same 16 moves (variant "p"): the flipped names come from a negated pass-1 root (one signed constant pair and
+//     four sign XORs) and are consumed by conj(W^4) in pass 2's first stage (one XOR), which leaves rho^(-32) on the spectra of the lanes with
+//     bit 3 set.  No folded pass can take that scalar out; the KEY does: this kernel streams a.bk_ring, a second spectral array of the context
+//     that holds the spectrum of X^32 b at exactly those points (bit 5 of nu) and the plain value elsewhere -- an exact negacyclic rotation of
+//     the integer limb polynomials, made by the key transform at context creation (thfhe_transform.h: MapPhased).  Every product is what it
+//     was; the inverse and the accumulator see no difference; the cooperative kernel keeps the plain array.  A lane stands for the natural
+//     position nu = lane_nu(lane) throughout: digit reads, key reads, roots and the accumulator update take nu; the key's order in memory and
+//     in the ring is untouched.  1 223 -> 1 109 other vector instructions (profiles/r12_phased_key.md);
+//   * the inverse's outputs m + 4 leave their scale R = 1/sqrt 2 (of conj(C[4])) to the rounding add of the accumulator update: one
+//     fma(R, x, 1.5 * 2^52) per component instead of a multiply and an add (invx_seg3_ring / acc_update16_ring): 3 356 -> 3 324 FP64 instructions;
 //   * the second transpose uses the padded 576-slot buffer (there is no T1 table in the LDS, its 8 KiB pay for the padding): its slot maps are
 //     base + immediate, 2 LDS address registers per wave instead of 16 for XOR-swizzled maps;
 //   * no twiddle is read from a table: the transforms are variant "f" (thfhe_lane.h).  Every inter-pass twiddle sits on the input side of the pass
@@ -221,7 +229,7 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
     // per-lane part of a DMA's address is one loop-invariant 32-bit byte offset.  An issue costs the vector pipe nothing but the DMA itself.
     static_assert(DPC == 1 || DPC == 2, "a wave brings one slice of a chunk, or two 1 KiB apart");
     const uint32_t lane_off = (uint32_t)(wave * (64 * DPC) + lane) * (uint32_t)sizeof(cplx);
-    uint64_t gbase = (uint64_t)(size_t)a.bk;
+    uint64_t gbase = (uint64_t)(size_t)a.bk_ring;
     int chunks_ahead = a.n * ROWS * RS::kChunksPerRow - 1;   // issues past the end of the stream repeat its last chunk
     asm volatile("" : "+s"(gbase), "+s"(chunks_ahead));
     // slots 0 .. 2 are the key ring, slot 3 is borrowed from transpose buffer 0 between barriers A and B of a row (thfhe_ring_schedule.h)
@@ -261,16 +269,16 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
                 // index / sign / subtraction once per accumulator polynomial, then one signed bit-field extract + one conversion per level
                 int a2n_r = a2n;
                 asm volatile("" : "+s"(a2n_r));  // opaque per row: the rotated LDS addresses are recomputed, not kept alive
-                if (r % L == 0) rotated_fields_keep<NF, W == 4>(lane, acc + (r / L) * 1024, a2n_r, L, Bgbit, fld);
+                if (r % L == 0) rotated_fields_keep<NF, W == 4>(nu, acc + (r / L) * 1024, a2n_r, L, Bgbit, fld);
                 asm volatile("" : "+s"(a2n_r));
-                mixed_digits_z<NF>(lane, acc + (r / L) * 1024, a2n_r, (r % L) + 1, L, Bgbit, fld, z);
+                mixed_digits_z<NF>(nu, acc + (r / L) * 1024, a2n_r, (r % L) + 1, L, Bgbit, fld, z);
                 // eight-wave shape: the two forward roots are made opaque per transform, so their powers (12 FP64 instructions each) are rebuilt and
                 // not hoisted out of the CMux loop.  With nothing derived from the roots live across the loop the compiler parks nothing in scratch: no
                 // reload in front of a row's digits waits for the ring DMAs (s_waitcnt vmcnt(0) follows every reload).  Rebuilding instead of keeping
                 // measured 30.21 -> 29.97 ms per 4096 gates, 44 -> 0 B of scratch per lane, when it was introduced (on the transforms before these;
                 // DESIGN 4.1, profiles/r04_summary.md).  The four-wave shape has registers to spare and lets the compiler keep what it likes.
                 if (W == 8) opaque_in_place(rootsf.s), opaque_in_place(rootsf.w);
-                wave_fft_fwd_x(lane, z, xb, rootsf);
+                wave_fft_fwd_x(lane, z, xb, rootsf, flip);
             }
             STAMP(0);
             cplx bA[4], bB[4];
@@ -328,7 +336,7 @@ __global__ __launch_bounds__(64 * W, W == 8 ? 2 : 1) void sk_blind_rotate_ring_k
             for (int c = 0; c < 2; c++) {
                 wave_fft_inv_x<W == 8>(lane, S[c][0], xb, w64, roots, flip, bc);
                 wave_fft_inv_x<W == 8>(lane, S[c][1], xb, w64, roots, flip, bc);
-                acc_update16(nu, acc + c * 1024, S[c][0], S[c][1]);
+                acc_update16_ring(nu, acc + c * 1024, S[c][0], S[c][1]);
             }
             wave_sync();
         }
@@ -529,6 +537,7 @@ struct THFHE_INTERNAL thfhe_ctx : DevCtx {
     thfhe_params p;
     int rec_words() const { return p.n + 1; }
     DevBuf d_bk;              // spectral key
+    DevBuf d_bk_ring;         // the same size again: its phased copy for the ring kernels (variant "p" in thfhe_lane.h), X^32 b at the points with bit 5 of nu set
     KsKey ksk;                // padded rows (+ the matrix-core planes)
     int coop_max_jobs = 768;    // remainders (batch mod 2048) up to this many rotations use the cooperative (latency) kernel
     int ring4_max_jobs = 1024;  // ... above it and up to this many, the four-wave ring kernel (launch_br)
@@ -645,7 +654,7 @@ int enqueue_rotations(thfhe_ctx *c, int op, const int32_t *d0, const int32_t *d1
     hipLaunchKernelGGL(sk_prologue_kernel, pg, dim3(256), 0, c->stream, d0, d1, d2, op, d_ops, rot_per_gate, n, c->n_pad,
                        ilog2(2 * c->p.N), (long)jobs, c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>());
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
-    BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, n, c->n_pad, c->p.Bgbit, mu};
+    BRArgs a{c->d_bk.as<cplx>(), c->d_bk_ring.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, n, c->n_pad, c->p.Bgbit, mu};
     rc = launch_rotations<kGate>(c, a);
     if (rc) return rc;
     if (c->profiling) THFHE_HIP(hipEventRecord(c->ev[2], c->stream));
@@ -684,7 +693,7 @@ int enqueue_pbs(thfhe_ctx *c, const Src &src, size_t jobs, const int32_t *tv, co
     if (ev) THFHE_HIP(hipEventRecord(c->ev[0], c->stream));
     lut_prologue_launch(src, jobs, n, c->n_pad, ilog2(2 * c->p.N), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), idx, c->stream);
     if (ev) THFHE_HIP(hipEventRecord(c->ev[1], c->stream));
-    BRArgs a{c->d_bk.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, n, c->n_pad, c->p.Bgbit,
+    BRArgs a{c->d_bk.as<cplx>(), c->d_bk_ring.as<cplx>(), c->d_tw.as<cplx>(), c->d_bara.as<int32_t>(), c->d_barb.as<int32_t>(), c->d_u.as<int32_t>(), (long)jobs, n, c->n_pad, c->p.Bgbit,
              0, tv, Src::kIdx == LutIdx::none ? d_idx : idx, theta, tv_a};
     if (mv) {
         a.mv_w = mv->w, a.mv_p = mv->p, a.mv_box = c->p.N / mv->p;
@@ -1052,6 +1061,8 @@ int thfhe_ctx_create(const thfhe_params *p, const int32_t *bk_coeff, const int32
     THFHE_HIP(hipMemcpyAsync(coeff.as<int32_t>(), bk_coeff, (size_t)npolys * 1024 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     THFHE_TRY(c->d_bk.grow((size_t)npolys * 1024 * sizeof(cplx)));
     THFHE_TRY((launch_torus_transform<1024, 32>(c->stream, coeff.as<int32_t>(), npolys, c->d_tw.as<cplx>(), c->d_bk.as<cplx>())));
+    THFHE_TRY(c->d_bk_ring.grow((size_t)npolys * 1024 * sizeof(cplx)));
+    THFHE_TRY((launch_torus_transform<1024, 32, MapPhased>(c->stream, coeff.as<int32_t>(), npolys, c->d_tw.as<cplx>(), c->d_bk_ring.as<cplx>())));
     THFHE_TRY(c->ksk.upload(ksk, 1, p->N, p->n, p->ks_t, p->ks_basebit, true, c->stream));   // (synchronises: the transform is done too)
     *out = c.release();
     return THFHE_OK;

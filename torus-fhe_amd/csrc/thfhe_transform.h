@@ -10,6 +10,17 @@ struct MapIdentity {
     __device__ size_t dst(long p, int h, int limbs) const { return (size_t)p * limbs + h; }
 };
 
+// The phased copy of a Torus32, N = 1024 key (variant "p" in thfhe_lane.h; the single-key ring kernels stream it): the layout of MapIdentity; at the
+// points whose natural position nu has bit 5 set the value is the spectrum of X^kKeyPhase b_h, the limb polynomial rotated AFTER the split
+// (limb_pair_rot32), everywhere else the plain value.  Both come out of the same transform, so the copy costs a second transform per limb.
+struct MapPhased : MapIdentity {
+    static constexpr bool kPhased = true;
+};
+template <class Map, class = void>
+struct map_is_phased : std::false_type {};
+template <class Map>
+struct map_is_phased<Map, std::void_t<decltype(Map::kPhased)>> : std::true_type {};
+
 // torus polynomials [NN] of TB-bit words -> balanced 16-bit limb spectra, scaled by 1/(NN/2), one wave per (polynomial, limb): limb h of
 // polynomial map.src(p) goes to spec + map.dst(p, h, limbs) * NN/2, i.e. [poly][limb][halves or quarters][512] with MapIdentity.
 //   NN = 1024: the "s" form; NN = 2048: radix-2 split + two twisted halves (T1 tables in LDS); NN = 4096: radix-4 split + four twisted
@@ -43,6 +54,17 @@ __global__ __launch_bounds__(256) void torus_transform_kernel(const void *__rest
 #pragma unroll
         for (int m = 0; m < 8; m++) z[m] = limb_pair<TB>(poly, lane + 64 * m, lane + 64 * m + 512, h);
         wave_fft_fwd_s(lane, z, sX[wave], sT1[0], w64);
+        if constexpr (map_is_phased<Map>::value) {
+            static_assert(TB == 32, "the phased copy is the single-key ring kernels'");
+            cplx y[8];
+#pragma unroll
+            for (int m = 0; m < 8; m++) y[m] = limb_pair_rot32(reinterpret_cast<const int32_t *>(poly), lane + 64 * m, lane + 64 * m + 512, h, kKeyPhase);
+            wave_fft_fwd_s(lane, y, sX[wave], sT1[0], w64);
+            if (key_point_phased(lane)) {   // spectra come out at their natural positions: lane = nu
+#pragma unroll
+                for (int m = 0; m < 8; m++) z[m] = y[m];
+            }
+        }
 #pragma unroll
         for (int m = 0; m < 8; m++) dst[m * 64 + lane] = cplx{z[m].re * (1.0 / 512), z[m].im * (1.0 / 512)};
     } else if constexpr (NN == 2048) {
