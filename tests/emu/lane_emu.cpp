@@ -277,6 +277,11 @@ int emu_rotated_digits_crosscheck(const int32_t *acc /*[1024]*/, int a2n, int l,
             rotated_fields_keep<16>(lane, acc, a2n, l, Bgbit, f12);
             mixed_digits_z<16>(lane, acc, a2n, p, l, Bgbit, f12, z1);
             for (int m = 0; m < 8; m++) bad += (z0[m].re != z1[m].re) + (z0[m].im != z1[m].im);
+            uint32_t fb[16];           // BATCH form (the four-wave ring shape: reads first, arithmetic after): the same fields, the same digits
+            rotated_fields_keep<16, true>(lane, acc, a2n, l, Bgbit, fb);
+            for (int j = 0; j < 16; j++) bad += fb[j] != f12[j];
+            mixed_digits_z<16>(lane, acc, a2n, p, l, Bgbit, fb, z1);
+            for (int m = 0; m < 8; m++) bad += (z0[m].re != z1[m].re) + (z0[m].im != z1[m].im);
         }
     }
     return bad;

@@ -127,13 +127,22 @@ def test_roots_variant_exact_with_margin(E, O, case, fn):
 
 
 def test_fused_rotated_digits_match_reference_form(E):
-    # rotated_digits_z (one signed bit-field extract per digit, sign by xor/subtract) == load_rotated16 + digits_to_z on random and
-    # extreme accumulators, every rotation class (0, < N, = N, > N, 2N - 1) and the three gadget shapes in use
+    # rotated_digits_z (one signed bit-field extract per digit, sign by xor/subtract), the two-step forms (some / all fields kept) and the BATCH form of
+    # the four-wave ring shape == load_rotated16 + digits_to_z on random and extreme accumulators, EVERY rotation amount 0 .. 2N - 1 and the gadget
+    # shapes in use; then on the polynomials of tests/decomp_edges.py, whose difference meets every digit edge at every amount
+    import decomp_edges as D
     rng = np.random.default_rng(33)
+    check = lambda acc, a2n, l, bg: E.emu_rotated_digits_crosscheck(acc.ctypes.data_as(C.POINTER(C.c_int32)), a2n, l, bg)
     for acc in (rng.integers(-2**31, 2**31, 1024).astype(np.int32), np.full(1024, -2**31, np.int32), np.full(1024, 2**31 - 1, np.int32)):
-        for a2n in (0, 1, 63, 64, 1023, 1024, 1025, 2047, int(rng.integers(0, 2048))):
+        for a2n in range(2048):
             for l, bg in ((3, 7), (2, 10), (4, 8), (1, 4)):
-                assert E.emu_rotated_digits_crosscheck(acc.ctypes.data_as(C.POINTER(C.c_int32)), a2n, l, bg) == 0, (a2n, l, bg)
+                assert check(acc, a2n, l, bg) == 0, (a2n, l, bg)
+    for l, bg in ((1, 8), (2, 10), (3, 7), (4, 8)):
+        for k, pair in enumerate(D.edge_tables(32, 1024, l, bg)):
+            for j, acc in enumerate(pair):
+                acc = np.ascontiguousarray(acc, np.int32)
+                for a2n in range(2048):
+                    assert check(acc, a2n, l, bg) == 0, (a2n, l, bg, "table", k, "polynomial", j)
 
 
 def test_mk_cmux_and_extract_bit_exact(E, O):
