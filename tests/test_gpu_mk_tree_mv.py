@@ -16,6 +16,8 @@ import mk_lut_reference as R
 import mk_pack_reference as MP
 import mk_tree_mv_reference as TM
 from support import differing, pmap
+from test_gpu_mk_dag_tree import BASEBIT, T_PK
+from test_gpu_mk_tree import _flat as _flat_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -155,6 +157,69 @@ def test_refused_calls_leave_the_context_usable(O):
         assert np.array_equal(got, _flat(ck, tv0, w[None], x, x, (1,), 0, (1,), 0, np.zeros(2, np.int32), 0))
     finally:
         ck.close()
+
+
+def test_tree_workspace_in_every_call_order(O):
+    """The tree calls share one grow-only workspace rule: a rows tree (R = 4 rotations per sample, one sample per slice), a k = 2 multi-value tree
+    and a gate-DAG run with a TREE and a TREE_MV group, on fresh contexts in three orders -- a call sized after a smaller one gives the words it
+    gives first, and the flat trees the words of the flat calls they stand for."""
+    import thfhe
+    from thfhe import circuits as CIR, lut
+    p = O.make_params("MK2", n=30)
+    s = O.SIGMAS["MK2"]
+    K = O.MKKeys(p, 53, s["bk"], s["ks"])
+    rng = np.random.default_rng(0x5EED0071)
+    pk = rng.integers(-2**63, 2**63, (p.N, T_PK, (1 << BASEBIT) - 1, 2, p.N), dtype=np.int64)
+    lo = R.encrypt_words(K, rng.integers(-2**31, 2**31, 3), s["lwe"], 71)
+    hi = R.encrypt_words(K, rng.integers(-2**31, 2**31, 3), s["lwe"], 72)
+    wlo, blo, whi, bhi = (3,), 1234567, (-5,), -7654321
+    # (a) the rows tree: p_hi = 8, theta_lo = 2, two tables
+    tabs = rng.integers(0, 4, (2, 8, 4))
+    tv1 = np.stack([lut.tree_test_vectors(lambda h, l, T=T: T[h, l], 8, 4, 4, 2, p.N, torus_bits=64) for T in tabs])
+    idx_a = np.array([0, 1, 1], np.int32)
+    # (b) the multi-value tree: p_hi = 4, p_lo = 2, k = 2, two tables
+    bits = rng.integers(0, 2, (2, 2, 4, 2))
+    parts = [lut.tree_mvk_factors([lambda h, l, T=T: T[h, l] for T in tab], 4, 2, 2, N=p.N, torus_bits=64) for tab in bits]
+    tv0, w = parts[0][0], np.stack([f for _, f in parts])
+    idx_b, ob = np.array([1, 0, 1], np.int32), int(rng.integers(-2**63, 2**63))
+    # (c) a TREE node (p_hi = 4, theta_lo = 2) feeding a TREE_MV node (k = 2), two instances; random tables: only words are compared
+    cir = CIR.Circuit()
+    a, b = cir.inputs(2)
+    t = cir.tree(cir.tree_rows(rng.integers(-2**63, 2**63, (2, p.N), dtype=np.int64)), [a], [b], 4, lo_weights=wlo, hi_weights=whi, lo_bias=blo, hi_bias=bhi,
+                 theta1=2)
+    cir.tree_mv(cir.mv_base(rng.integers(-2**63, 2**63, p.N, dtype=np.int64)), rng.integers(-3, 4, (2, 4, 4)).astype(np.int32), [t], [b], lo_weights=wlo,
+                hi_weights=whi, lo_bias=blo, hi_bias=bhi, out_bias=ob)
+    x = np.stack([lo[:2], hi[:2]])   # [instance][wire][words]
+
+    def call_a(ck):
+        ck.set_tree_slice(8)   # one sample per slice
+        try:
+            return ck.tree_lut_bootstrap(tv1, lo, hi, p_hi=8, weights_lo=wlo, bias_lo=blo, theta=2, weights_hi=whi, bias_hi=bhi, table_index=idx_a)
+        finally:
+            ck.set_tree_slice(16384)
+
+    def call_b(ck):
+        return ck.tree_lut_bootstrap_mvk(w, lo, hi, tv0=tv0, weights_lo=wlo, bias_lo=blo, weights_hi=whi, bias_hi=bhi, table_index=idx_b, out_bias=ob)
+
+    calls = dict(a=call_a, b=call_b, c=lambda ck: CIR.evaluate_batch(ck, cir, x))
+    first = None
+    for order in ("abc", "cba", "bca"):
+        ck = thfhe.MKCloudKey(thfhe.make_params(**p.as_dict()), K.bk, K.ksk, device=0)
+        try:
+            ck.pack_key_set(pk, T_PK, BASEBIT)
+            ck.set_profiling(False)
+            got = {name: calls[name](ck) for name in order}
+            if first is None:
+                first = got
+                assert got["a"].shape == (3, p.parties * p.n + 1) and got["b"].shape == (3, 2, p.parties * p.n + 1) and got["c"].shape[:2] == (2, 5)
+                flat = _flat_rows(ck, tv1, lo, hi, 8, 2, wlo, blo, whi, bhi, idx_a)
+                assert np.array_equal(got["a"], flat), ("a", differing(got["a"], flat))
+                flat = _flat(ck, tv0, w, lo, hi, wlo, blo, whi, bhi, idx_b, ob)
+                assert np.array_equal(got["b"], flat), ("b", differing(got["b"], flat))
+            for name in order:
+                assert np.array_equal(got[name], first[name]), (order, name, differing(got[name], first[name]))
+        finally:
+            ck.close()
 
 
 @pytest.fixture(scope="module")

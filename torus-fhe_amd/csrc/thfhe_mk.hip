@@ -1292,102 +1292,86 @@ int mk_pack_boxes(thfhe_mk_ctx *c, const int32_t *recs, size_t count, int p, int
 // what tree_validate_rows (thfhe_pbs_host.h) admits here: p_hi up to the 64 records one packing takes
 constexpr TreeRules kMkTreeRules{64, "tree: p_hi must be a power of two in 2 .. 64", "tree: n_tables must be >= 1 and n_tables * p_hi / theta <= 262144"};
 
-// thfhe_mk_tree_lut_bootstrap: per slice of S samples three stages on the context's stream, nothing visiting the host in between --
-//   level 1    S R many-LUT rotations (R = p_hi / theta_lo) of the plaintext rows tv1[table[s]][r] on the `lo` operands, no key switch: the S p_hi
-//              candidates stay in d_u as [N + 1] records under the coefficients of Z, candidate k of sample s at record s p_hi + k
-//   packing    mk_pack_enqueue with p = p_hi and the D = N key: sample s's encrypted table (d_tab_a[s], d_tab_b[s])
-//   selection  one theta = 1 rotation per sample of its own table on the `hi` operands, coefficient 0, mk_keyswitch into the staging output
-// Only a slice's inputs go up and its S records come down; the `hi` operands replace the `lo` ones in the staging arrays once level 1 is enqueued.
-int mk_tree_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec &lo, const thfhe_lut_spec &hi, int p_hi, const int64_t *tv1, int n_tables,
-                      const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0, const int32_t *hi1,
-                      const int32_t *hi2, int32_t *out, size_t count) {
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    const size_t N = c->p.N, words = c->rec_words();
+// the packing key of a tree: set, and taking the [N + 1] records level 1 leaves in d_u
+int mk_tree_key_check(const thfhe_mk_ctx *c, size_t N) {
     if (!c->pk_D) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_mk_pack_key_set)");
     if (c->pk_D != (int)N) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key must take the ring key's coefficients (D = N)");
-    if (count == 0) return THFHE_OK;
-    const int R = p_hi / lo.theta;
-    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / p_hi));
-    const size_t tv_bytes = (size_t)n_tables * R * N * sizeof(int64_t);
-    int rc = c->d_tv.grow(tv_bytes);
-    if (!rc) rc = mk_ensure_workspace(c, S_max * R, lo.theta);
-    if (!rc) rc = c->d_lut_idx.grow(S_max * R * sizeof(int32_t));
-    if (!rc) rc = mk_pack_reserve(c, S_max * p_hi);
-    if (!rc) rc = c->d_tab_a.grow(S_max * N * sizeof(int64_t));
-    if (!rc) rc = c->d_tab_b.grow(S_max * N * sizeof(int64_t));
-    if (!rc) rc = c->stage.grow(S_max * words);
-    if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv1, tv_bytes, hipMemcpyHostToDevice, st));
-    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);
-    const LutFlatSrc<LutIdx::table> lo_src{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr};
-    const LutFlatSrc<LutIdx::job> hi_src{in0, in1, in2, hi, 1, nullptr};
-    return ctx_tree_sliced(c, count, S_max, lo, hi, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, 1, [&](size_t S, bool, bool last, auto upload_hi) {
-        const bool ev = c->profiling && last;   // profiling, on the last slice: level 1 | packing | selection
-        if (ev) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        THFHE_TRY(mk_enqueue_pbs(c, lo_src, S * R, c->d_tv.as<int64_t>(), nullptr, lo.theta, nullptr, nullptr));
-        if (ev) THFHE_HIP(hipEventRecord(c->ev[1], st));
-        THFHE_TRY(mk_pack_enqueue(c, c->d_u.as<int32_t>(), S * p_hi, p_hi, c->d_tab_a.as<int64_t>(), c->d_tab_b.as<int64_t>()));
-        if (ev) THFHE_HIP(hipEventRecord(c->ev[2], st));
-        THFHE_TRY(upload_hi());
-        THFHE_TRY(mk_enqueue_pbs(c, hi_src, S, c->d_tab_b.as<int64_t>(), c->d_tab_a.as<int64_t>(), 1, nullptr, c->stage.out_ptr()));
-        if (ev) {
-            THFHE_HIP(hipEventRecord(c->ev[3], st));
-            c->ev_valid = true;
-        }
-        return (int)THFHE_OK;
-    });
+    return THFHE_OK;
 }
 
-// thfhe_mk_tree_lut_bootstrap_mvk: the tree with level 1 as ONE multi-value rotation per sample and k tables per sample --
-//   level 1    S rotations of the base vector tv0 on the `lo` operands with mk_extract_mv_kernel's q = k p_hi outputs (taps of table[s], out_bias on
-//              the body), no key switch: output j p_hi + h, candidate h of table j, at record s q + j p_hi + h of d_u
-//   packing    mk_pack_enqueue with p = p_hi and the D = N key: table (s, j) is packed sample s k + j
-//   selection  S k theta = 1 rotations, job s k + j on sample s's `hi` operands and its own table, coefficient 0, mk_keyswitch into the staging output
-// One level-1 accumulator per sample; per candidate its record and its sum; S k tables.  The arguments have passed the entry's host checks.
-int mk_tree_mvk_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec &lo, const thfhe_lut_spec &hi, int p_hi, int p_lo, int k, const int64_t *tv0,
-                          const int32_t *factors, int n_tables, const int32_t *table_index, int64_t out_bias, const int32_t *lo0, const int32_t *lo1,
-                          const int32_t *lo2, const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
+// Grow-only workspace of one tree chain over S samples / nodes: S R level-1 rotations of theta_lo records each (their accumulators, the S k p
+// candidates in d_u), S k selection rotations, an index per job of the larger stage, the packing sums of the S k p candidates and the S k packed
+// tables (k tables per sample, DESIGN 4.23: R = 1, theta_lo = k p).  With k = 1 the second grow and the max are redundant -- S <= S R, one record
+// per job <= theta_lo -- and the sizes are those of the first.
+int mk_tree_workspace(thfhe_mk_ctx *c, size_t S, size_t p, size_t R, size_t theta_lo, size_t k = 1) {
+    const size_t N = c->p.N;
+    int rc = mk_ensure_workspace(c, S * R, (int)theta_lo);
+    if (!rc) rc = mk_ensure_workspace(c, S * k, 1);
+    if (!rc) rc = c->d_lut_idx.grow(std::max(S * R, S * k) * sizeof(int32_t));
+    if (!rc) rc = mk_pack_reserve(c, S * k * p);
+    if (!rc) rc = c->d_tab_a.grow(S * k * N * sizeof(int64_t));
+    if (!rc) rc = c->d_tab_b.grow(S * k * N * sizeof(int64_t));
+    return rc;
+}
+
+// One tree chain over S samples / nodes on the context's stream, the workspace sized by mk_tree_workspace, nothing visiting the host
+// in between.  Level 1: S (p / theta_lo) many-LUT rotations of the plaintext rows d_tv1 on the `lo` source, no key switch -- the S p candidates stay
+// in d_u as [N + 1] records under the coefficients of Z, candidate h of sample s at record s p + h, the order the rotations write them in.  Then
+// mk_pack_enqueue with the D = N key packs them in place into S encrypted tables (d_tab_a[s], d_tab_b[s]), and the selection: sample s rotates its
+// own table on the `hi` source, theta = 1, coefficient 0, mk_keyswitch into d_out.  seam(1) / seam(2) run after level 1 and after the packing: what
+// the caller has to put on the stream there.  mv: level 1 is ONE multi-value rotation per sample of the base vector d_tv1 with
+// mk_extract_mv_kernel's theta_lo = k p outputs (taps of the job's table, out_bias on the body) -- output j p + h is candidate h of table j, at
+// record s k p + j p + h, so the packed table of (s, j) is sample s k + j, and selection job s k + j rotates it on sample s's `hi` operands (the
+// `hi` source repeats every sample k times and numbers its jobs): S k records into d_out.
+template <typename Lo, typename Hi, typename Seam>
+int mk_enqueue_tree_chain(thfhe_mk_ctx *c, const Lo &lo, const int64_t *d_tv1, int theta_lo, const Hi &hi, size_t S, int p, int32_t *d_out, Seam seam,
+                          const MkMvArgs *mv = nullptr, size_t k = 1) {
+    int64_t *const tab_a = c->d_tab_a.as<int64_t>(), *const tab_b = c->d_tab_b.as<int64_t>();
+    THFHE_TRY(mk_enqueue_pbs(c, lo, mv ? S : S * (p / theta_lo), d_tv1, nullptr, mv ? 1 : theta_lo, nullptr, nullptr, false, mv));
+    THFHE_TRY(seam(1));
+    THFHE_TRY(mk_pack_enqueue(c, c->d_u.as<int32_t>(), S * k * p, p, tab_a, tab_b));
+    THFHE_TRY(seam(2));
+    return mk_enqueue_pbs(c, hi, S * k, tab_b, tab_a, 1, nullptr, d_out);
+}
+
+// thfhe_mk_tree_lut_bootstrap: per slice of S samples one mk_enqueue_tree_chain on contiguous operands -- level 1 on the rows
+// tv[table[s]][r] (tv_rows rows of N words in all) and the `lo` operands, the selection on the `hi` operands.  Only a slice's inputs go up and its
+// records come down; the `hi` operands replace the `lo` ones in the staging arrays once the packing is enqueued.  factors
+// (thfhe_mk_tree_lut_bootstrap_mvk): level 1 is one multi-value rotation per sample of the base vector tv with k tables per sample,
+// factors int32[n_tables][k][p_hi][p_lo], out int32[count][k][P n + 1].  The arguments have passed the entry's host checks.
+int mk_tree_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec &lo, const thfhe_lut_spec &hi, int p_hi, const int64_t *tv, size_t tv_rows, const int32_t *factors,
+                      int p_lo, int n_tables, const int32_t *table_index, int64_t out_bias, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2,
+                      const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count, int k = 1) {
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
-    const size_t N = c->p.N, words = c->rec_words();
-    if (!c->pk_D) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_mk_pack_key_set)");
-    if (c->pk_D != (int)N) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key must take the ring key's coefficients (D = N)");
+    const size_t N = c->p.N, words = c->rec_words(), K = (size_t)k;
+    THFHE_TRY(mk_tree_key_check(c, N));
     if (count == 0) return THFHE_OK;
-    const size_t K = (size_t)k, q = K * p_hi;
-    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / q));
-    const size_t w_bytes = (size_t)n_tables * q * p_lo * sizeof(int32_t);
-    int rc = c->d_tv.grow(N * sizeof(int64_t));
-    if (!rc) rc = c->d_mv_w.grow(w_bytes);
-    if (!rc) rc = mk_ensure_workspace(c, S_max, (int)q);   // level 1: S accumulators, S q records
-    if (!rc) rc = mk_ensure_workspace(c, S_max * K, 1);    // selection: S k rotations
-    if (!rc) rc = c->d_lut_idx.grow(S_max * K * sizeof(int32_t));
-    if (!rc) rc = mk_pack_reserve(c, S_max * q);
-    if (!rc) rc = c->d_tab_a.grow(S_max * K * N * sizeof(int64_t));
-    if (!rc) rc = c->d_tab_b.grow(S_max * K * N * sizeof(int64_t));
+    const int theta1 = factors ? k * p_hi : lo.theta, R = k * p_hi / theta1;   // level-1 records per rotation, rotations per sample
+    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / (K * p_hi)));
+    const size_t tv_bytes = tv_rows * N * sizeof(int64_t), w_bytes = factors ? (size_t)n_tables * K * p_hi * p_lo * sizeof(int32_t) : 0;
+    int rc = c->d_tv.grow(tv_bytes);
+    if (!rc && factors) rc = c->d_mv_w.grow(w_bytes);
+    if (!rc) rc = mk_tree_workspace(c, S_max, p_hi, R, theta1, K);
     if (!rc) rc = c->stage.grow(S_max * K * words);
     if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
     if (rc) return rc;
     hipStream_t st = c->stream;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv0, N * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
-    const MkMvArgs mv{c->d_mv_w.as<int32_t>(), p_lo, (int)q, out_bias};
-    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);
-    const LutFlatSrc<LutIdx::table> lo_src{in0, in1, in2, lo, 1, table_index ? c->d_tree_tab.as<int32_t>() : nullptr};
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv, tv_bytes, hipMemcpyHostToDevice, st));
+    if (factors) THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
+    const MkMvArgs mv{c->d_mv_w.as<int32_t>(), p_lo, k * p_hi, out_bias};
+    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);   // `lo`, then `hi` operands of the slice
+    const LutFlatSrc<LutIdx::table> lo_src{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr};
     const LutFlatSrc<LutIdx::job> hi_src{in0, in1, in2, hi, k, nullptr};
     return ctx_tree_sliced(c, count, S_max, lo, hi, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, K, [&](size_t S, bool, bool last, auto upload_hi) {
-        const bool ev = c->profiling && last;   // profiling, on the last slice: level 1 with its epilogue | packing | selection
+        const bool ev = c->profiling && last;   // profiling, all on the last slice: level 1 (with its epilogue) | packing | selection
         if (ev) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        THFHE_TRY(mk_enqueue_pbs(c, lo_src, S, c->d_tv.as<int64_t>(), nullptr, 1, nullptr, nullptr, false, &mv));
-        if (ev) THFHE_HIP(hipEventRecord(c->ev[1], st));
-        THFHE_TRY(mk_pack_enqueue(c, c->d_u.as<int32_t>(), S * q, p_hi, c->d_tab_a.as<int64_t>(), c->d_tab_b.as<int64_t>()));
-        if (ev) THFHE_HIP(hipEventRecord(c->ev[2], st));
-        THFHE_TRY(upload_hi());
-        THFHE_TRY(mk_enqueue_pbs(c, hi_src, S * K, c->d_tab_b.as<int64_t>(), c->d_tab_a.as<int64_t>(), 1, nullptr, c->stage.out_ptr()));
+        auto seam = [&](int stage) {
+            if (ev) THFHE_HIP(hipEventRecord(c->ev[stage], st));
+            return stage == 2 ? upload_hi() : (int)THFHE_OK;
+        };
+        THFHE_TRY(mk_enqueue_tree_chain(c, lo_src, c->d_tv.as<int64_t>(), theta1, hi_src, S, p_hi, c->stage.out_ptr(), seam, factors ? &mv : nullptr, K));
         if (ev) {
             THFHE_HIP(hipEventRecord(c->ev[3], st));
             c->ev_valid = true;
@@ -1433,10 +1417,8 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
     const int words = c->rec_words();
     const size_t N = c->p.N;
     hipStream_t st = c->stream;
-    if (plan.has_tree_groups()) {   // TREE / TREE_MV groups pack [N + 1] records: the D = N key (SELECT rows never reach a plan of this engine)
-        if (!c->pk_D) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_mk_pack_key_set)");
-        if (c->pk_D != (int)N) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key must take the ring key's coefficients (D = N)");
-    }
+    // TREE / TREE_MV groups pack [N + 1] records: the D = N key (SELECT rows never reach a plan of this engine)
+    if (plan.has_tree_groups()) THFHE_TRY(mk_tree_key_check(c, N));
     auto mv_slice_of = [&](int mv, size_t all) { return std::min({all, c->dag_slice, std::max<size_t>(1, c->mv_slice / (size_t)F.mvs[mv].q)}); };
     // a slice of a TREE group: at most dag_slice nodes over all instances and tree_slice / p_hi of them; of a TREE_MV group: tree_slice / (k p_hi)
     auto tree_slice_of = [&](size_t cand, size_t all) { return std::min({all, c->dag_slice, std::max<size_t>(1, c->tree_slice / cand)}); };
@@ -1444,14 +1426,8 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
         if (b.cls == kDagTree || b.cls == kDagTreeMv) {
             const bool is_mv = b.cls == kDagTreeMv;
             const size_t k = is_mv ? (size_t)F.mvs[b.tree].k : 1, p = is_mv ? (size_t)F.mvs[b.tree].q : (size_t)F.trees[b.tree].p_hi;
-            const int theta = is_mv ? (int)(k * p) : F.trees[b.tree].lo.theta;
-            const size_t S = tree_slice_of(k * p, b.count * instances), rot1 = is_mv ? S : S * (p / theta);
-            THFHE_TRY(mk_ensure_workspace(c, rot1, theta));   // level 1: its rotations, S k p records
-            THFHE_TRY(mk_ensure_workspace(c, S * k, 1));      // selection
-            THFHE_TRY(c->d_lut_idx.grow(std::max(rot1, S * k) * sizeof(int32_t)));
-            THFHE_TRY(mk_pack_reserve(c, S * k * p));
-            THFHE_TRY(c->d_tab_a.grow(S * k * N * sizeof(int64_t)));
-            THFHE_TRY(c->d_tab_b.grow(S * k * N * sizeof(int64_t)));
+            const size_t theta_lo = is_mv ? k * p : (size_t)F.trees[b.tree].lo.theta, S = tree_slice_of(k * p, b.count * instances);
+            THFHE_TRY(mk_tree_workspace(c, S, p, k * p / theta_lo, theta_lo, k));
             THFHE_TRY(c->stage.out.grow(S * k * words * sizeof(int32_t)));
             continue;
         }
@@ -1478,31 +1454,27 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
         },
         [&](const DagExtGroup &g) -> int {
             int32_t *const dst = c->stage.out_ptr();
-            int64_t *const tab_a = c->d_tab_a.as<int64_t>(), *const tab_b = c->d_tab_b.as<int64_t>();
+            auto no_seam = [](int) { return (int)THFHE_OK; };
             const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the `hi` operands of a TREE / TREE_MV node follow its lo.n_inputs level-1 operands
-            if (g.cls == kDagTree) {   // mk_tree_bootstrap's chain with both prologues on the wire table; t_y = row0
+            if (g.cls == kDagTree) {   // the flat tree's chain with both prologues on the wire table; t_y = row0
                 const thfhe_tree_spec ts = F.trees[g.tree];
-                const int p = ts.p_hi, R = p / ts.lo.theta, hi0 = ts.lo.n_inputs;
+                const int p = ts.p_hi, hi0 = ts.lo.n_inputs;
                 return dag_group_slices(g, tree_slice_of((size_t)p, (size_t)g.all), 1, dst, words, st, [&](long first, long S) {
-                    const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {ts.lo}, g.t_y, first, g.cnt, g.n_wires, R};
+                    const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {ts.lo}, g.t_y, first, g.cnt, g.n_wires, p / ts.lo.theta};
                     const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
-                    THFHE_TRY(mk_enqueue_pbs(c, lo, (size_t)S * R, c->d_dag_tv1.as<int64_t>(), nullptr, ts.lo.theta, nullptr, nullptr));
-                    THFHE_TRY(mk_pack_enqueue(c, c->d_u.as<int32_t>(), (size_t)S * p, p, tab_a, tab_b));
-                    return mk_enqueue_pbs(c, hi, (size_t)S, tab_b, tab_a, 1, nullptr, dst);
+                    return mk_enqueue_tree_chain(c, lo, c->d_dag_tv1.as<int64_t>(), ts.lo.theta, hi, (size_t)S, p, dst, no_seam);
                 });
             }
             if (g.cls != kDagMv && g.cls != kDagTreeMv) return thfhe_fail(THFHE_E_INVALID, "grouped node kind not defined for the 3-gen engine");
             const thfhe_mv_spec m = F.mvs[g.tree];   // t_y = each node's table
-            if (g.cls == kDagTreeMv) {   // mk_tree_mvk_bootstrap's chain on the wire table: record [first + s][j] goes to wire head + j
+            if (g.cls == kDagTreeMv) {   // the k-table chain on the wire table: record [first + s][j] goes to wire head + j
                 const int64_t *const base = c->d_dag_mv_tv0.as<int64_t>() + (size_t)m.base * N;
                 const MkMvArgs mvk{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p, m.k * m.q, mv_out_bias ? mv_out_bias[g.tree] : 0};
                 const int hi0 = m.lo.n_inputs;
                 return dag_group_slices(g, tree_slice_of((size_t)m.k * m.q, (size_t)g.all), m.k, dst, words, st, [&](long first, long S) {
                     const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
                     const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
-                    THFHE_TRY(mk_enqueue_pbs(c, lo, (size_t)S, base, nullptr, 1, nullptr, nullptr, false, &mvk));
-                    THFHE_TRY(mk_pack_enqueue(c, c->d_u.as<int32_t>(), (size_t)S * m.k * m.q, m.q, tab_a, tab_b));
-                    return mk_enqueue_pbs(c, hi, (size_t)S * m.k, tab_b, tab_a, 1, nullptr, dst);
+                    return mk_enqueue_tree_chain(c, lo, base, m.k * m.q, hi, (size_t)S, m.q, dst, no_seam, &mvk, (size_t)m.k);
                 });
             }
             const int64_t *const tv0 = c->d_dag_mv_tv0.as<int64_t>() + (size_t)m.base * N;
@@ -1838,7 +1810,8 @@ int thfhe_mk_tree_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *spec_lo, 
                                 const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count) {
     // host checks, before the context is looked at
     THFHE_TRY(tree_validate_rows(kMkTreeRules, spec_lo, spec_hi, p_hi, tv1, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count));
-    return mk_tree_bootstrap(c, *spec_lo, *spec_hi, p_hi, tv1, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
+    return mk_tree_bootstrap(c, *spec_lo, *spec_hi, p_hi, tv1, (size_t)n_tables * (p_hi / spec_lo->theta), nullptr, 0, 0, table_index, 0, lo0, lo1, lo2, hi0, hi1,
+                             hi2, out, count);
 }
 
 int thfhe_mk_tree_lut_bootstrap_mvk(thfhe_mk_ctx *c, const thfhe_lut_spec *spec_lo, const thfhe_lut_spec *spec_hi, int p_hi, int p_lo, int k, const int64_t *tv0,
@@ -1855,7 +1828,7 @@ int thfhe_mk_tree_lut_bootstrap_mvk(thfhe_mk_ctx *c, const thfhe_lut_spec *spec_
                                    spec_hi->n_inputs > 2 ? hi2 : nullptr};
     for (const int32_t *in : ins)
         if (in == out) return thfhe_fail(THFHE_E_INVALID, "tree: out must not alias an input");
-    return mk_tree_mvk_bootstrap(c, *spec_lo, *spec_hi, p_hi, p_lo, k, tv0, factors, n_tables, table_index, out_bias, lo0, lo1, lo2, hi0, hi1, hi2, out, count);
+    return mk_tree_bootstrap(c, *spec_lo, *spec_hi, p_hi, tv0, 1, factors, p_lo, n_tables, table_index, out_bias, lo0, lo1, lo2, hi0, hi1, hi2, out, count, k);
 }
 
 int thfhe_mk_set_pack_wide_threshold(thfhe_mk_ctx *c, size_t min_records) {
