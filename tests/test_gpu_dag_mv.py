@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import lut_reference as R
-from support import N, SIGMA, sk128_cloud_key, sk128_pack, words
+from support import N, SIGMA, differing, sk128_cloud_key, sk128_pack, words
 
 pytestmark = pytest.mark.gpu
 
@@ -146,6 +146,114 @@ def test_tree_batch_without_the_new_nodes_is_unchanged(sk128, ck, pack):
                                    np.stack(c.tv1), pack=pc)
     assert np.array_equal(out, got[:, 3:]) and st2 == {k: st[k] for k in st2}
     assert s == c.n_wires() - 1 and e[1] == s - 1
+
+
+@pytest.fixture(scope="module")
+def small(O):
+    """SK-128 at n = 16 and a packing key of random words (only words are compared); open_small: a fresh CloudKey and packing context on them"""
+    p = O.make_params("SK-128", n=16)
+    s = O.SIGMAS["SK-128"]
+    K = O.SKKeys(p, 0x5EED0016, s["bk"], s["ks"])
+    return p, K, words(np.random.default_rng(6500), p.n, p.ks_t, (1 << p.ks_basebit) - 1, 2, N)
+
+
+def open_small(small):
+    import thfhe
+    from thfhe import threshold as T
+    p, K, pk = small
+    key = thfhe.CloudKey(thfhe.make_params(**p.as_dict()), K.bk, K.ksk, device=0)
+    pc = T.PolyContext(0)
+    pc.set_pack_key(pk, p.ks_t, p.ks_basebit)
+    return key, pc
+
+
+def test_tree_workspace_in_every_call_order(O, small):
+    """The tree calls, the flat multi-value call and the grouped kinds of a DAG run size one set of grow-only buffers: a rows tree (R = 4 rotations
+    per sample, one sample per slice), a k = 2 multi-value tree, a q = 3 multi-value call and a DAG run with a SELECT, a TREE feeding a TREE_MV and an
+    MV group, on fresh contexts in three orders -- a call sized after a smaller one gives the words it gives first (the DAG run first: the packing
+    reserve of a context nothing has sized), and the flat calls the words of the public calls they stand for."""
+    import mv_lut_reference as MV
+    from test_gpu_tree_lut import compose as rows_compose
+    from test_gpu_tree_mvk import compose as mvk_compose
+    from thfhe import circuits as Cc
+    p, K, pk = small
+    orc = O.Oracle(p, K.bk, K.ksk)
+    rng = np.random.default_rng(6501)
+    lo, hi = words(rng, 3, p.n + 1), words(rng, 3, p.n + 1)
+    wlo, blo, whi, bhi = (3,), 1234567, (-5,), -7654321
+    tv1, idx_a = words(rng, 2, 4, N), np.array([0, 1, 1], np.int32)                       # (a) p_hi = 8, theta = 2, two tables
+    tv0, w, idx_b = words(rng, N), words(rng, 2, 2, 4, 2), np.array([1, 0, 1], np.int32)   # (b) p_hi = 4, p_lo = 2, k = 2, two tables
+    w3 = words(rng, 3, 4)                                                                  # (c) p = 4, q = 3
+    cir = Cc.Circuit()                                                                     # (d)
+    a, b = cir.inputs(2)
+    m = cir.mv(cir.mv_base(words(rng, N)), words(rng, 4, 4), [a], weights=wlo, bias=blo)
+    cir.select([b], m[0], 4, weights=whi, bias=bhi)
+    t = cir.tree(cir.tree_rows(words(rng, 2, N)), [a], [b], 4, lo_weights=wlo, hi_weights=whi, lo_bias=blo, hi_bias=bhi, theta1=2)
+    cir.tree_mv(cir.mv_base(words(rng, N)), words(rng, 2, 4, 4), [t], [b], lo_weights=wlo, hi_weights=whi, lo_bias=blo, hi_bias=bhi)
+    x = np.stack([lo[:2], hi[:2]])   # [instance][wire][words]
+
+    def call_a(key, pc):
+        key.set_tree_slice(8)   # one sample per slice
+        try:
+            return key.tree_lut_bootstrap(pc, tv1, lo, hi, p_hi=8, weights_lo=wlo, bias_lo=blo, theta=2, weights_hi=whi, bias_hi=bhi, table_index=idx_a)
+        finally:
+            key.set_tree_slice(65536)
+
+    calls = dict(a=call_a,
+                 b=lambda key, pc: key.tree_lut_bootstrap_mvk(pc, w, lo, hi, tv0=tv0, weights_lo=wlo, bias_lo=blo, weights_hi=whi, bias_hi=bhi, table_index=idx_b),
+                 c=lambda key, pc: key.mv_lut_bootstrap(w3, lo, tv0=tv0, weights=wlo, bias=blo),
+                 d=lambda key, pc: Cc.evaluate_batch(key, cir, x, pack=pc))
+    first = None
+    for order in ("abcd", "dcba", "bdac"):
+        key, pc = open_small(small)
+        try:
+            got = {name: calls[name](key, pc) for name in order}
+            if first is None:
+                first = got
+                assert got["a"].shape == (3, p.n + 1) and got["b"].shape == (3, 2, p.n + 1) and got["c"].shape == (3, 3, p.n + 1)
+                assert got["d"].shape == (2, cir.n_wires(), p.n + 1) and cir.n_wires() == 2 + 4 + 1 + 1 + 2
+                flat = rows_compose(key, pc, tv1, [lo], [hi], 8, 2, wlo, blo, whi, bhi, idx_a)
+                assert np.array_equal(got["a"], flat), ("a", differing(got["a"], flat))
+                flat = mvk_compose(key, pc, tv0, w, [lo], [hi], wlo, blo, whi, bhi, idx_b)
+                assert np.array_equal(got["b"], flat), ("b", differing(got["b"], flat))
+                flat = np.stack([MV.mv_lut(orc, [lo[g]], wlo, blo, tv0, w3) for g in range(3)])
+                assert np.array_equal(got["c"], flat), ("c", differing(got["c"], flat))
+            for name in order:
+                assert np.array_equal(got[name], first[name]), (order, name, differing(got[name], first[name]))
+        finally:
+            key.close()
+            pc.close()
+
+
+def test_mv_and_tree_mv_groups_slice_by_their_own_rule(small):
+    """An MV group of 5 nodes and a TREE_MV group (k = 2, q = 4) of 3 nodes, two instances: the words of the unsliced run with tree_slice = k q (one
+    TREE_MV node and, q = 4, two MV nodes per slice) and with two nodes per slice of either group."""
+    from thfhe import circuits as Cc
+    p, K, pk = small
+    rng = np.random.default_rng(6502)
+    cir = Cc.Circuit()
+    ins = cir.inputs(3)
+    b0, wm, wt = cir.mv_base(words(rng, N)), words(rng, 2, 4, 4), words(rng, 2, 2, 4, 4)
+    for j in range(5):
+        cir.mv(b0, wm[j % 2], [ins[j % 3]], weights=(3,), bias=1234567)
+    for j in range(3):
+        cir.tree_mv(b0, wt[j % 2], [ins[j]], [ins[(j + 1) % 3]], hi_weights=(-5,))
+    x = words(rng, 2, 3, p.n + 1)
+    key, pc = open_small(small)
+    try:
+        st = {}
+        ref = Cc.evaluate_batch(key, cir, x, stats=st, pack=pc)
+        assert (st["levels"], st["launches"], st["rotations"]) == (1, 3, (5 + 3 * 3) * 2)   # launch groups: MV, the level 1 and the selections of TREE_MV
+        for setter, value, default in ((key.set_tree_slice, 8, 65536), (key.set_dag_slice, 2, 28672)):
+            setter(value)
+            try:
+                got = Cc.evaluate_batch(key, cir, x, pack=pc)
+            finally:
+                setter(default)
+            assert np.array_equal(got, ref), (setter.__name__, differing(got, ref))
+    finally:
+        key.close()
+        pc.close()
 
 
 @pytest.mark.parametrize("op", [19, 20], ids=["MV", "TREE_MV"])

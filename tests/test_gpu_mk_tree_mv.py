@@ -222,6 +222,44 @@ def test_tree_workspace_in_every_call_order(O):
             ck.close()
 
 
+def test_mv_and_tree_mv_groups_slice_by_their_own_member(O):
+    """An MV group (q = 4) of 5 nodes and a TREE_MV group (k = 2, q = 4) of 3 nodes, two instances, in one gate-DAG run: the words of the unsliced
+    run with mv_slice = q (one MV node per slice, the TREE_MV group whole), with tree_slice = k q (one TREE_MV node per slice, the MV group whole)
+    and with dag_slice = 2 (two nodes per slice of either group)."""
+    import thfhe
+    from thfhe import circuits as CIR
+    p = O.make_params("MK2", n=30)
+    s = O.SIGMAS["MK2"]
+    K = O.MKKeys(p, 59, s["bk"], s["ks"])
+    rng = np.random.default_rng(0x5EED0072)
+    pk = rng.integers(-2**63, 2**63, (p.N, T_PK, (1 << BASEBIT) - 1, 2, p.N), dtype=np.int64)
+    cir = CIR.Circuit()
+    ins = cir.inputs(3)
+    b0 = cir.mv_base(rng.integers(-2**63, 2**63, p.N, dtype=np.int64))
+    wm, wt = rng.integers(-2**31, 2**31, (2, 4, 4)).astype(np.int32), rng.integers(-3, 4, (2, 2, 4, 4)).astype(np.int32)
+    ob = int(rng.integers(-2**63, 2**63))
+    for j in range(5):
+        cir.mv(b0, wm[j % 2], [ins[j % 3]], weights=(3,), bias=1234567, out_bias=ob)
+    for j in range(3):
+        cir.tree_mv(b0, wt[j % 2], [ins[j]], [ins[(j + 1) % 3]], hi_weights=(-5,), out_bias=ob)
+    x = np.stack([R.encrypt_words(K, rng.integers(-2**31, 2**31, 3), s["lwe"], 90 + i) for i in range(2)])   # [instance][wire][words]
+    ck = thfhe.MKCloudKey(thfhe.make_params(**p.as_dict()), K.bk, K.ksk, device=0)
+    try:
+        ck.pack_key_set(pk, T_PK, BASEBIT)
+        st = {}
+        ref = CIR.evaluate_batch(ck, cir, x, stats=st)
+        assert (st["levels"], st["launches"], st["rotations"]) == (1, 3, (5 + 3 * 3) * 2)   # launch groups: MV, the level 1 and the selections of TREE_MV
+        for setter, value, default in ((ck.set_mv_slice, 4, 4096), (ck.set_tree_slice, 8, 16384), (ck.set_dag_slice, 2, 8192)):
+            setter(value)
+            try:
+                got = CIR.evaluate_batch(ck, cir, x)
+            finally:
+                setter(default)
+            assert np.array_equal(got, ref), (setter.__name__, differing(got, ref))
+    finally:
+        ck.close()
+
+
 @pytest.fixture(scope="module")
 def mk4_full(O):
     """Full-size MK4 with the oracle's keys and a packing key from Z to Z of 12 one-bit digits (12 288 rows, 192 MiB), its ring products on the device."""

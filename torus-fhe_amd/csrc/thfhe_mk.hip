@@ -1334,50 +1334,25 @@ int mk_enqueue_tree_chain(thfhe_mk_ctx *c, const Lo &lo, const int64_t *d_tv1, i
     return mk_enqueue_pbs(c, hi, S * k, tab_b, tab_a, 1, nullptr, d_out);
 }
 
-// thfhe_mk_tree_lut_bootstrap: per slice of S samples one mk_enqueue_tree_chain on contiguous operands -- level 1 on the rows
-// tv[table[s]][r] (tv_rows rows of N words in all) and the `lo` operands, the selection on the `hi` operands.  Only a slice's inputs go up and its
-// records come down; the `hi` operands replace the `lo` ones in the staging arrays once the packing is enqueued.  factors
-// (thfhe_mk_tree_lut_bootstrap_mvk): level 1 is one multi-value rotation per sample of the base vector tv with k tables per sample,
-// factors int32[n_tables][k][p_hi][p_lo], out int32[count][k][P n + 1].  The arguments have passed the entry's host checks.
+// mk_enqueue_tree_chain into stage.out as the shared call bodies (thfhe_pbs_host.h) call it; w, mv_p: the taps of a multi-value level 1 (null: rows)
+auto mk_tree_chain_of(thfhe_mk_ctx *c, int64_t out_bias) {
+    return [=](const auto &lo, const int64_t *d_tv1, int theta_lo, const auto &hi, size_t S, int p, auto seam, const int32_t *w, int mv_p, size_t k) {
+        const MkMvArgs mv{w, mv_p, (int)k * p, out_bias};
+        return mk_enqueue_tree_chain(c, lo, d_tv1, theta_lo, hi, S, p, c->stage.out_ptr(), seam, w ? &mv : nullptr, k);
+    };
+}
+
+// thfhe_mk_tree_lut_bootstrap(_mvk): the lock and the packing key's check, then ctx_tree_bootstrap (thfhe_pbs_host.h) on this
+// engine's tree workspace and chain, every profiling event on the call's last slice.  The arguments have passed the entry's host checks.
 int mk_tree_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec &lo, const thfhe_lut_spec &hi, int p_hi, const int64_t *tv, size_t tv_rows, const int32_t *factors,
                       int p_lo, int n_tables, const int32_t *table_index, int64_t out_bias, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2,
                       const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count, int k = 1) {
     if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
-    const size_t N = c->p.N, words = c->rec_words(), K = (size_t)k;
-    THFHE_TRY(mk_tree_key_check(c, N));
-    if (count == 0) return THFHE_OK;
-    const int theta1 = factors ? k * p_hi : lo.theta, R = k * p_hi / theta1;   // level-1 records per rotation, rotations per sample
-    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / (K * p_hi)));
-    const size_t tv_bytes = tv_rows * N * sizeof(int64_t), w_bytes = factors ? (size_t)n_tables * K * p_hi * p_lo * sizeof(int32_t) : 0;
-    int rc = c->d_tv.grow(tv_bytes);
-    if (!rc && factors) rc = c->d_mv_w.grow(w_bytes);
-    if (!rc) rc = mk_tree_workspace(c, S_max, p_hi, R, theta1, K);
-    if (!rc) rc = c->stage.grow(S_max * K * words);
-    if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tv, tv_bytes, hipMemcpyHostToDevice, st));
-    if (factors) THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
-    const MkMvArgs mv{c->d_mv_w.as<int32_t>(), p_lo, k * p_hi, out_bias};
-    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);   // `lo`, then `hi` operands of the slice
-    const LutFlatSrc<LutIdx::table> lo_src{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr};
-    const LutFlatSrc<LutIdx::job> hi_src{in0, in1, in2, hi, k, nullptr};
-    return ctx_tree_sliced(c, count, S_max, lo, hi, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, K, [&](size_t S, bool, bool last, auto upload_hi) {
-        const bool ev = c->profiling && last;   // profiling, all on the last slice: level 1 (with its epilogue) | packing | selection
-        if (ev) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        auto seam = [&](int stage) {
-            if (ev) THFHE_HIP(hipEventRecord(c->ev[stage], st));
-            return stage == 2 ? upload_hi() : (int)THFHE_OK;
-        };
-        THFHE_TRY(mk_enqueue_tree_chain(c, lo_src, c->d_tv.as<int64_t>(), theta1, hi_src, S, p_hi, c->stage.out_ptr(), seam, factors ? &mv : nullptr, K));
-        if (ev) {
-            THFHE_HIP(hipEventRecord(c->ev[3], st));
-            c->ev_valid = true;
-        }
-        return (int)THFHE_OK;
-    });
+    THFHE_TRY(mk_tree_key_check(c, c->p.N));
+    return ctx_tree_bootstrap(c, lo, hi, p_hi, tv, tv_rows, factors, p_lo, n_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count, k, false,
+                              [&](auto... a) { return mk_tree_workspace(c, a...); }, mk_tree_chain_of(c, out_bias));
 }
 
 // thfhe_mk_mv_lut_bootstrap(_wo_keyswitch): ctx_mv_lut_bootstrap (thfhe_pbs_host.h) in slices of at most mv_slice records, one stage
@@ -1395,9 +1370,9 @@ int mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t
 
 // The six-column entries of the 3-gen executor (F: the entry's families and the generations it admits): the host checks and the plan before the
 // context is looked at, then the run.  The gate classes run as in thfhe_mk_dag_run_batch; a LUT launch group is one PBS stage on the wire table
-// (lut_prologue_kernel over the P n + 1 record words) with the key switch into the staging output.  An MV group is the
-// same with the multi-value epilogue: one base vector per launch, the table per job, q records per node scattered into consecutive wires, in
-// slices of at most dag_slice nodes and mv_slice / q of them.  No stage of a run records profiling events.
+// (lut_prologue_kernel over the P n + 1 record words) with the key switch into the staging output.  TREE, TREE_MV and MV groups
+//  are dag_run_group's (thfhe_pbs_host.h) on this engine's chain and its stage with the multi-value epilogue, MV groups in
+// slices by mv_slice.  No stage of a run records profiling events.
 int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const int64_t *mv_out_bias, size_t instances, int64_t *stats) {
     DagPlan plan;
     if ((F.gens & kDagGenTree) && A.nodes)   // before the plan: a SELECT row has a refusal of its own on this engine
@@ -1414,38 +1389,14 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
     if (stats && !mv_entry) plan.fill_stats(stats);   // thfhe_mk_dag_run_lut_batch gives them to a caller with a context only
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
-    const int words = c->rec_words();
-    const size_t N = c->p.N;
-    hipStream_t st = c->stream;
     // TREE / TREE_MV groups pack [N + 1] records: the D = N key (SELECT rows never reach a plan of this engine)
-    if (plan.has_tree_groups()) THFHE_TRY(mk_tree_key_check(c, N));
-    auto mv_slice_of = [&](int mv, size_t all) { return std::min({all, c->dag_slice, std::max<size_t>(1, c->mv_slice / (size_t)F.mvs[mv].q)}); };
-    // a slice of a TREE group: at most dag_slice nodes over all instances and tree_slice / p_hi of them; of a TREE_MV group: tree_slice / (k p_hi)
-    auto tree_slice_of = [&](size_t cand, size_t all) { return std::min({all, c->dag_slice, std::max<size_t>(1, c->tree_slice / cand)}); };
-    for (const DagBatch &b : plan.batches) {   // every buffer a grouped kind's slices use, the staging output included, before dag_execute takes pointers
-        if (b.cls == kDagTree || b.cls == kDagTreeMv) {
-            const bool is_mv = b.cls == kDagTreeMv;
-            const size_t k = is_mv ? (size_t)F.mvs[b.tree].k : 1, p = is_mv ? (size_t)F.mvs[b.tree].q : (size_t)F.trees[b.tree].p_hi;
-            const size_t theta_lo = is_mv ? k * p : (size_t)F.trees[b.tree].lo.theta, S = tree_slice_of(k * p, b.count * instances);
-            THFHE_TRY(mk_tree_workspace(c, S, p, k * p / theta_lo, theta_lo, k));
-            THFHE_TRY(c->stage.out.grow(S * k * words * sizeof(int32_t)));
-            continue;
-        }
-        if (b.cls != kDagMv) continue;
-        const size_t S = mv_slice_of(b.tree, b.count * instances), q = (size_t)F.mvs[b.tree].q;
-        THFHE_TRY(mk_ensure_workspace(c, S, (int)q));
-        THFHE_TRY(c->d_lut_idx.grow(S * sizeof(int32_t)));
-        THFHE_TRY(c->stage.out.grow(S * q * words * sizeof(int32_t)));
-    }
-    THFHE_TRY(dag_upload(c->d_tv, st, F.tv, (size_t)F.n_luts * N * sizeof(int64_t)));
-    THFHE_TRY(dag_upload(c->dag.specs, st, F.specs, (size_t)F.n_specs * sizeof(thfhe_lut_spec)));
-    THFHE_TRY(dag_upload(c->d_dag_mv_tv0, st, F.mv_tv0, (size_t)F.n_bases * N * sizeof(int64_t)));
-    THFHE_TRY(dag_upload(c->d_dag_mv_w, st, F.mv_factors, F.n_factor_words * sizeof(int32_t)));
-    THFHE_TRY(dag_upload(c->d_dag_enc_a, st, F.enc_a, (size_t)F.n_enc * N * sizeof(int64_t)));   // the tree generation's families are int64 here
-    THFHE_TRY(dag_upload(c->d_dag_enc_b, st, F.enc_b, (size_t)F.n_enc * N * sizeof(int64_t)));
-    THFHE_TRY(dag_upload(c->d_dag_tv1, st, F.tv1, (size_t)F.n_tv1_rows * N * sizeof(int64_t)));
+    if (plan.has_tree_groups()) THFHE_TRY(mk_tree_key_check(c, c->p.N));
+    size_t w_cand = 0;   // not needed: mk_tree_workspace reserves its own packing
+    THFHE_TRY(dag_reserve_groups(c, plan, F, instances, &thfhe_mk_ctx::mv_slice, w_cand, [&](auto... a) { return mk_tree_workspace(c, a...); },
+                                 [&](size_t jobs, int theta) { return mk_ensure_workspace(c, jobs, theta); }));
+    THFHE_TRY(dag_upload_families<int64_t>(c, c->stream, F));
     return dag_execute(
-        plan, c->dag, st, words, A, instances, c->dag_slice,
+        plan, c->dag, c->stream, c->rec_words(), A, instances, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) { return mk_dag_ensure(c, max_gates, plan.max_theta, in, out); },
         [&](int cls, const int32_t *d_ops, size_t n) { return mk_dag_gate_class(c, cls, d_ops, n); },
         [&](int theta, const DagLutSlice &s) {
@@ -1453,35 +1404,11 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
                                   s.enc ? c->d_dag_enc_a.as<int64_t>() : nullptr, theta, nullptr, c->stage.out_ptr());
         },
         [&](const DagExtGroup &g) -> int {
-            int32_t *const dst = c->stage.out_ptr();
-            auto no_seam = [](int) { return (int)THFHE_OK; };
-            const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the `hi` operands of a TREE / TREE_MV node follow its lo.n_inputs level-1 operands
-            if (g.cls == kDagTree) {   // the flat tree's chain with both prologues on the wire table; t_y = row0
-                const thfhe_tree_spec ts = F.trees[g.tree];
-                const int p = ts.p_hi, hi0 = ts.lo.n_inputs;
-                return dag_group_slices(g, tree_slice_of((size_t)p, (size_t)g.all), 1, dst, words, st, [&](long first, long S) {
-                    const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {ts.lo}, g.t_y, first, g.cnt, g.n_wires, p / ts.lo.theta};
-                    const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
-                    return mk_enqueue_tree_chain(c, lo, c->d_dag_tv1.as<int64_t>(), ts.lo.theta, hi, (size_t)S, p, dst, no_seam);
-                });
-            }
-            if (g.cls != kDagMv && g.cls != kDagTreeMv) return thfhe_fail(THFHE_E_INVALID, "grouped node kind not defined for the 3-gen engine");
-            const thfhe_mv_spec m = F.mvs[g.tree];   // t_y = each node's table
-            if (g.cls == kDagTreeMv) {   // the k-table chain on the wire table: record [first + s][j] goes to wire head + j
-                const int64_t *const base = c->d_dag_mv_tv0.as<int64_t>() + (size_t)m.base * N;
-                const MkMvArgs mvk{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p, m.k * m.q, mv_out_bias ? mv_out_bias[g.tree] : 0};
-                const int hi0 = m.lo.n_inputs;
-                return dag_group_slices(g, tree_slice_of((size_t)m.k * m.q, (size_t)g.all), m.k, dst, words, st, [&](long first, long S) {
-                    const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
-                    const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
-                    return mk_enqueue_tree_chain(c, lo, base, m.k * m.q, hi, (size_t)S, m.q, dst, no_seam, &mvk, (size_t)m.k);
-                });
-            }
-            const int64_t *const tv0 = c->d_dag_mv_tv0.as<int64_t>() + (size_t)m.base * N;
-            const MkMvArgs mv{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p, m.q, mv_out_bias ? mv_out_bias[g.tree] : 0};
-            return dag_group_slices(g, mv_slice_of(g.tree, (size_t)g.all), m.q, c->stage.out_ptr(), words, st, [&](long first, long S) {
-                const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
-                return mk_enqueue_pbs(c, lo, (size_t)S, tv0, nullptr, 1, nullptr, c->stage.out_ptr(), false, &mv);
+            if (g.cls != kDagTree && g.cls != kDagMv && g.cls != kDagTreeMv) return thfhe_fail(THFHE_E_INVALID, "grouped node kind not defined for the 3-gen engine");
+            const int64_t bias = mv_out_bias && g.cls != kDagTree ? mv_out_bias[g.tree] : 0;
+            return dag_run_group<int64_t>(c, F, g, &thfhe_mk_ctx::mv_slice, mk_tree_chain_of(c, bias), [&](const auto &lo, size_t S, const int64_t *tv0, const int32_t *w, int mv_p, int q) {
+                const MkMvArgs mv{w, mv_p, q, bias};
+                return mk_enqueue_pbs(c, lo, S, tv0, nullptr, 1, nullptr, c->stage.out_ptr(), false, &mv);
             });
         });
 }

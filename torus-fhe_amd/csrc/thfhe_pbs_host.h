@@ -1,8 +1,10 @@
 // thfhe_pbs_host.h -- the programmable-bootstrap call bodies the single-key (thfhe_sk.hip) and 3-gen multi-key (thfhe_mk.hip) engines have in
-// common: the flat LUT / encrypted-LUT call, the flat multi-value call, the host checks and the slice loop of a tree call, and dag_execute's
-// ensure.  Function templates over the engine's context, like ctx_staged (thfhe_devctx.h); what differs per engine -- its workspace, its PBS
-// stage, its tree chain -- comes in as a callable.  The table word (Torus32 / Torus64) follows the table pointer; the ring degree is c->p.N.
-// Host code only: no kernels.
+// common: the flat LUT / encrypted-LUT call, the flat multi-value call, the host checks, the body and the slice loop of a flat tree call,
+// dag_execute's ensure, and the grouped TREE / TREE_MV / MV part of a gate-DAG run (table uploads, slice rule, reserve loop, group body).
+// Function templates over the engine's context, like ctx_staged (thfhe_devctx.h); what differs per engine -- its workspace rules, its PBS
+// stage, its tree chain with its multi-value record -- comes in as a callable.  The engine keeps its locks, key checks, refusals, SELECT /
+// leveled / CB groups and profiling wrapper.  The table word (Torus32 / Torus64) follows the table pointer or is named (dag_upload_families<T>,
+// dag_run_group<T>); the ring degree is c->p.N.  Host code only: no kernels.
 #ifndef THFHE_PBS_HOST_H
 #define THFHE_PBS_HOST_H
 
@@ -193,6 +195,130 @@ int ctx_tree_sliced(Ctx *c, size_t count, size_t S_max, const thfhe_lut_spec &lo
             return (int)THFHE_OK;
         });
     }, c->stage.out_ptr(), out, k * words);
+}
+
+// The flat tree call (thfhe_tree_lut_bootstrap(_mv)(k) and their thfhe_mk_ forms), the engine having locked the context and checked its packing key:
+// per slice of S samples one chain on contiguous operands -- level 1 on the rows tv[table[s]][r] (tv_rows rows of N words in all) and the `lo`
+// operands, the selection on the `hi` operands.  Only a slice's inputs go up and its records come down.  factors: level 1 is one
+// multi-value rotation per sample of the base vector tv with the k p_hi factors of p_lo taps of table[s], int32[n_tables][k][p_hi][p_lo]; k tables
+// per sample, out int32[count][k][rec_words()].  ws(S, p, R, theta_lo, k): the engine's tree workspace rule;
+// chain(lo, d_tv1, theta_lo, hi, S, p, seam, w, mv_p, k): its tree chain into stage.out, w the taps of a multi-value level 1 (null: rows).
+// Profiling: level 1 | packing | selection of the last slice in ev[1..3]; ev[0] on the call's first slice (ev0_first) or on its last.
+template <typename Ctx, typename T, typename Ws, typename Chain>
+int ctx_tree_bootstrap(Ctx *c, const thfhe_lut_spec &lo, const thfhe_lut_spec &hi, int p_hi, const T *tv, size_t tv_rows, const int32_t *factors, int p_lo,
+                       int n_tables, const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2, const int32_t *hi0,
+                       const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count, int k, bool ev0_first, Ws ws, Chain chain) {
+    if (count == 0) return THFHE_OK;
+    const size_t words = c->rec_words(), K = (size_t)k;
+    const int theta1 = factors ? k * p_hi : lo.theta, R = k * p_hi / theta1;   // level-1 records per rotation, rotations per sample
+    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / (K * p_hi)));
+    const size_t tv_bytes = tv_rows * c->p.N * sizeof(T), w_bytes = factors ? (size_t)n_tables * K * p_hi * p_lo * sizeof(int32_t) : 0;
+    int rc = c->d_tv.grow(tv_bytes);
+    if (!rc && factors) rc = c->d_mv_w.grow(w_bytes);
+    if (!rc) rc = ws(S_max, (size_t)p_hi, (size_t)R, (size_t)theta1, K);
+    if (!rc) rc = c->stage.grow(S_max * K * words);
+    if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    THFHE_HIP(hipMemcpyAsync(c->d_tv.template as<T>(), tv, tv_bytes, hipMemcpyHostToDevice, st));
+    if (factors) THFHE_HIP(hipMemcpyAsync(c->d_mv_w.template as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
+    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);   // `lo`, then `hi` operands of the slice
+    const LutFlatSrc<LutIdx::table> lo_src{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.template as<int32_t>() : nullptr};
+    const LutFlatSrc<LutIdx::job> hi_src{in0, in1, in2, hi, k, nullptr};
+    return ctx_tree_sliced(c, count, S_max, lo, hi, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, K, [&](size_t S, bool first, bool last, auto upload_hi) {
+        const bool ev = c->profiling && last;
+        if (c->profiling && (ev0_first ? first : last)) THFHE_HIP(hipEventRecord(c->ev[0], st));
+        auto seam = [&](int stage) {
+            if (ev) THFHE_HIP(hipEventRecord(c->ev[stage], st));
+            return stage == 2 ? upload_hi() : (int)THFHE_OK;
+        };
+        THFHE_TRY(chain(lo_src, c->d_tv.template as<T>(), theta1, hi_src, S, p_hi, seam, factors ? c->d_mv_w.template as<int32_t>() : nullptr, p_lo, K));
+        if (ev) {
+            THFHE_HIP(hipEventRecord(c->ev[3], st));
+            c->ev_valid = true;
+        }
+        return (int)THFHE_OK;
+    });
+}
+
+// ---- the grouped TREE / TREE_MV / MV kinds of a gate-DAG run ----
+// The run's tables and specs into their grow-only device buffers, once per call (T: the table word; F.enc_a / enc_b / tv1 are words of T too).
+template <typename T, typename Ctx>
+int dag_upload_families(Ctx *c, hipStream_t st, const DagFamilies &F) {
+    const size_t row = c->p.N * sizeof(T);
+    THFHE_TRY(dag_upload(c->d_tv, st, F.tv, F.n_luts * row));
+    THFHE_TRY(dag_upload(c->dag.specs, st, F.specs, (size_t)F.n_specs * sizeof(thfhe_lut_spec)));
+    THFHE_TRY(dag_upload(c->d_dag_enc_a, st, F.enc_a, F.n_enc * row));
+    THFHE_TRY(dag_upload(c->d_dag_enc_b, st, F.enc_b, F.n_enc * row));
+    THFHE_TRY(dag_upload(c->d_dag_tv1, st, F.tv1, F.n_tv1_rows * row));
+    THFHE_TRY(dag_upload(c->d_dag_mv_tv0, st, F.mv_tv0, F.n_bases * row));
+    return dag_upload(c->d_dag_mv_w, st, F.mv_factors, F.n_factor_words * sizeof(int32_t));
+}
+
+// A slice of a grouped kind's `all` nodes over all instances: at most dag_slice of them, and the flat calls' workspace rules -- tree_slice / p_hi
+// nodes of a SELECT / TREE group, tree_slice / (k q) of a TREE_MV group, c->*mv_slice / q of an MV group.
+template <typename Ctx>
+size_t dag_group_slice(const Ctx *c, const DagFamilies &F, int cls, int entry, size_t all, size_t Ctx::*mv_slice) {
+    const bool mv = cls == kDagMv || cls == kDagTreeMv;
+    const size_t per = cls == kDagMv ? c->*mv_slice / (size_t)F.mvs[entry].q : c->tree_slice / (mv ? (size_t)F.mvs[entry].k * F.mvs[entry].q : (size_t)F.trees[entry].p_hi);
+    return std::min({all, c->dag_slice, std::max<size_t>(1, per)});
+}
+
+// Every buffer the slices of the plan's TREE / TREE_MV / MV groups use, the staging output included, before dag_execute takes pointers.
+// tree_ws(S, p, R, theta_lo, k) / pbs_ws(jobs, theta): the engine's workspace rules; w_cand: raised to the most candidates (S k p) a slice packs.
+template <typename Ctx, typename TreeWs, typename PbsWs>
+int dag_reserve_groups(Ctx *c, const DagPlan &plan, const DagFamilies &F, size_t instances, size_t Ctx::*mv_slice, size_t &w_cand, TreeWs tree_ws, PbsWs pbs_ws) {
+    for (const DagBatch &b : plan.batches) {
+        if (b.cls != kDagTree && b.cls != kDagTreeMv && b.cls != kDagMv) continue;
+        const size_t S = dag_group_slice(c, F, b.cls, b.tree, b.count * instances, mv_slice);
+        size_t outs = 1;
+        if (b.cls == kDagMv) {
+            outs = (size_t)F.mvs[b.tree].q;
+            THFHE_TRY(pbs_ws(S, (int)outs));
+            THFHE_TRY(c->d_lut_idx.grow(S * sizeof(int32_t)));
+        } else {
+            const bool mv = b.cls == kDagTreeMv;
+            const size_t k = mv ? (size_t)F.mvs[b.tree].k : 1, p = mv ? (size_t)F.mvs[b.tree].q : (size_t)F.trees[b.tree].p_hi;
+            const size_t theta_lo = mv ? k * p : (size_t)F.trees[b.tree].lo.theta;
+            THFHE_TRY(tree_ws(S, p, k * p / theta_lo, theta_lo, k));
+            w_cand = std::max(w_cand, S * k * p), outs = k;
+        }
+        THFHE_TRY(c->stage.out.grow(S * outs * c->rec_words() * sizeof(int32_t)));
+    }
+    return THFHE_OK;
+}
+
+// One TREE / TREE_MV / MV group of a level, in slices (dag_group_slice) with every prologue reading the wire table.  A TREE group runs the flat
+// tree's chain on the run's level-1 rows (t_y = row0), the index operands of a node following its lo.n_inputs level-1 operands.  An MV group is one
+// multi-value PBS stage on its base vector (t_y = each node's table), its q records per node scattered into consecutive wires; a TREE_MV group the
+// k-table chain, record [first + s][j] going to wire head + j.  chain: as ctx_tree_bootstrap's; mv_pbs(lo, S, tv0, w, mv_p, q): the engine's
+// multi-value PBS stage of S nodes into stage.out.
+template <typename T, typename Ctx, typename Chain, typename MvPbs>
+int dag_run_group(Ctx *c, const DagFamilies &F, const DagExtGroup &g, size_t Ctx::*mv_slice, Chain chain, MvPbs mv_pbs) {
+    const int words = c->rec_words();
+    const size_t slice = dag_group_slice(c, F, g.cls, g.tree, (size_t)g.all, mv_slice);
+    auto no_seam = [](int) { return (int)THFHE_OK; };
+    const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};
+    if (g.cls == kDagTree) {
+        const thfhe_tree_spec ts = F.trees[g.tree];
+        const int p = ts.p_hi, hi0 = ts.lo.n_inputs;
+        return dag_group_slices(g, slice, 1, c->stage.out_ptr(), words, c->stream, [&](long first, long S) {
+            const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {ts.lo}, g.t_y, first, g.cnt, g.n_wires, p / ts.lo.theta};
+            const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
+            return chain(lo, c->d_dag_tv1.template as<T>(), ts.lo.theta, hi, (size_t)S, p, no_seam, (const int32_t *)nullptr, 0, (size_t)1);
+        });
+    }
+    const thfhe_mv_spec m = F.mvs[g.tree];
+    const bool is_tree = g.cls == kDagTreeMv;
+    const int hi0 = m.lo.n_inputs;
+    const T *const tv0 = c->d_dag_mv_tv0.template as<T>() + (size_t)m.base * c->p.N;
+    const int32_t *const w = c->d_dag_mv_w.template as<int32_t>() + m.factors_off;
+    return dag_group_slices(g, slice, is_tree ? m.k : m.q, c->stage.out_ptr(), words, c->stream, [&](long first, long S) {
+        const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
+        if (!is_tree) return mv_pbs(lo, (size_t)S, tv0, w, m.p, m.q);
+        const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
+        return chain(lo, tv0, m.k * m.q, hi, (size_t)S, m.q, no_seam, w, m.p, (size_t)m.k);
+    });
 }
 
 // dag_execute's ensure: workspace and staging for slices of max_gates gates; theta_max > 0: a run with LUT groups of up to theta_max records per

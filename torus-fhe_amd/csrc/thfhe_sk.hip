@@ -782,6 +782,14 @@ int enqueue_tree_chain(thfhe_ctx *c, thfhe_poly_ctx *pc, const Lo &lo, const int
     return enqueue_pbs(c, hi, S * k, tab_b, tab_a, 1, nullptr, d_out);
 }
 
+// enqueue_tree_chain into stage.out as the shared call bodies (thfhe_pbs_host.h) call it; w, mv_p: the taps of a multi-value level 1 (null: rows)
+auto tree_chain_of(thfhe_ctx *c, thfhe_poly_ctx *pc) {
+    return [=](const auto &lo, const int32_t *d_tv1, int theta_lo, const auto &hi, size_t S, int p, auto seam, const int32_t *w, int mv_p, size_t k) {
+        const MvArgs mv{w, mv_p};
+        return enqueue_tree_chain(c, pc, lo, d_tv1, theta_lo, hi, S, p, c->stage.out_ptr(), seam, w ? &mv : nullptr, k);
+    };
+}
+
 // ---- gate-DAG entry points: what thfhe_dag_run_batch, thfhe_dag_run_lut_batch and thfhe_dag_run_tree_batch share ----
 int sk_dag_classify(int op) { return op == THFHE_NOT || op == THFHE_COPY ? kDagLinear : (op == THFHE_MUX ? kDagMux : (op >= THFHE_NAND && op <= THFHE_ORYN ? kDagGate2 : -1)); }
 
@@ -807,38 +815,20 @@ int sk_dag_lhe_group(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, cons
 
 // The device side of the six-column entries, both contexts locked by the caller (T: the run's families, checked by dag_families_check; pc: null in a
 // run without SELECT / TREE groups).  Gate classes run as in thfhe_dag_run_batch.  A LUT group is one PBS stage on the wire table over the run's plaintext tables
-// (DESIGN 4.9), a LUT_ENC group the same over its encrypted tables.  A SELECT group gathers its candidates into the buffer the box packing reads
-// and runs the tree chain from there; a TREE group runs the whole chain with both prologues reading the wire table.  An MV group is
-// one multi-value PBS stage on the wire table, its q records per node scattered into consecutive wires; a TREE_MV group the k-table chain with both
-// prologues on the wire table.  A leveled group is sk_dag_lhe_group's.  Everything is enqueued on the gate context's stream.
+// (DESIGN 4.9), a LUT_ENC group the same over its encrypted tables.  TREE, TREE_MV and MV groups are dag_run_group's (thfhe_pbs_host.h) on this
+// engine's chain and PBS stage, sized by dag_reserve_groups.  A SELECT group gathers its candidates into the buffer the box packing reads and runs
+// the tree chain from there.  A leveled group is sk_dag_lhe_group's.  Everything is enqueued on the gate context's stream.
 int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const DagFamilies &T, const DagCall &A, size_t instances, const DagCbRun &cbr = {}) {
     const int words = c->rec_words();
     hipStream_t st = c->stream;
     if (cbr.l2) THFHE_TRY(sk_dag_cb_reserve(c, plan, T, cbr, instances));   // first: it refuses a run that does not fit (THFHE_E_NOMEM) with nothing done
-    // a slice of a SELECT / TREE group: at most dag_slice nodes over all instances and at most tree_slice / p_hi of them
-    const size_t dag_slice = c->dag_slice, tree_slice = c->tree_slice;
-    auto slice_of = [&](int tree, size_t all) { return std::min({all, dag_slice, std::max<size_t>(1, tree_slice / (size_t)T.trees[tree].p_hi)}); };
-    // ... of an MV / TREE_MV group: at most tree_slice / q, resp. tree_slice / (k q) nodes -- the flat calls' workspace rules
-    auto mv_slice_of = [&](int mv, size_t all) { return std::min({all, dag_slice, std::max<size_t>(1, tree_slice / ((size_t)T.mvs[mv].k * T.mvs[mv].q))}); };
-    size_t w_cand = 0;
-    for (const DagBatch &b : plan.batches) {
-        if (b.cls < kDagSelect || b.cls >= kDagLheLookup) continue;
-        if (b.cls == kDagMv || b.cls == kDagTreeMv) {   // every buffer the group's slices use, the staging output included, before dag_execute takes pointers
-            const thfhe_mv_spec &m = T.mvs[b.tree];
-            const size_t S = mv_slice_of(b.tree, b.count * instances), k = (size_t)m.k, q = (size_t)m.q;
-            if (b.cls == kDagTreeMv) {
-                THFHE_TRY(tree_workspace(c, S, q, 1, k * q, k));
-                w_cand = std::max(w_cand, S * k * q);
-            } else {
-                THFHE_TRY(ensure_workspace(c, S, (int)q));
-                THFHE_TRY(c->d_lut_idx.grow(S * sizeof(int32_t)));
-            }
-            THFHE_TRY(c->stage.out.grow(S * (b.cls == kDagTreeMv ? k : q) * words * sizeof(int32_t)));
-            continue;
-        }
-        const thfhe_tree_spec &ts = T.trees[b.tree];
-        const size_t S = slice_of(b.tree, b.count * instances), p = (size_t)ts.p_hi, theta_lo = b.cls == kDagTree ? (size_t)ts.lo.theta : 1;
-        THFHE_TRY(tree_workspace(c, S, p, b.cls == kDagTree ? p / theta_lo : 1, theta_lo));
+    size_t w_cand = 0;   // the most candidates one packing takes
+    THFHE_TRY(dag_reserve_groups(c, plan, T, instances, &thfhe_ctx::tree_slice, w_cand, [&](auto... a) { return tree_workspace(c, a...); },
+                                 [&](size_t jobs, int theta) { return ensure_workspace(c, jobs, theta); }));
+    for (const DagBatch &b : plan.batches) {   // a SELECT group's candidates are gathered: the selection rotation alone
+        if (b.cls != kDagSelect) continue;
+        const size_t p = (size_t)T.trees[b.tree].p_hi, S = dag_group_slice(c, T, b.cls, b.tree, b.count * instances, &thfhe_ctx::tree_slice);
+        THFHE_TRY(tree_workspace(c, S, p, 1, 1));
         w_cand = std::max(w_cand, S * p);
     }
     if (T.lhe) THFHE_TRY(sk_dag_lhe_reserve(c, plan, T, instances, w_cand));
@@ -846,47 +836,24 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
         THFHE_TRY(pack_boxes_reserve(pc, w_cand));
         THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle; from here on its buffers are used on `st`
     }
-    // the run's tables and specs, once per call
-    THFHE_TRY(dag_upload(c->d_tv, st, T.tv, (size_t)T.n_luts * 1024 * sizeof(int32_t)));
-    THFHE_TRY(dag_upload(c->dag.specs, st, T.specs, (size_t)T.n_specs * sizeof(thfhe_lut_spec)));
-    THFHE_TRY(dag_upload(c->d_dag_enc_a, st, T.enc_a, (size_t)T.n_enc * 1024 * sizeof(int32_t)));
-    THFHE_TRY(dag_upload(c->d_dag_enc_b, st, T.enc_b, (size_t)T.n_enc * 1024 * sizeof(int32_t)));
-    THFHE_TRY(dag_upload(c->d_dag_tv1, st, T.tv1, (size_t)T.n_tv1_rows * 1024 * sizeof(int32_t)));
-    THFHE_TRY(dag_upload(c->d_dag_mv_tv0, st, T.mv_tv0, (size_t)T.n_bases * 1024 * sizeof(int32_t)));
-    THFHE_TRY(dag_upload(c->d_dag_mv_w, st, T.mv_factors, T.n_factor_words * sizeof(int32_t)));
+    THFHE_TRY(dag_upload_families<int32_t>(c, st, T));
     // one SELECT / TREE / MV / TREE_MV / leveled group of a level
     auto ext_group = [&](const DagExtGroup &g) -> int {
-        auto no_seam = [](int) { return (int)THFHE_OK; };
         int32_t *const dst = c->stage.out_ptr();
         if (g.cls == kDagCb) return sk_dag_cb_group(c, cbr, plan, T, g, instances);
         if (g.cls >= kDagLheLookup) return sk_dag_lhe_group(c, pc, plan, T, g, instances);
-        if (g.cls == kDagMv || g.cls == kDagTreeMv) {   // t_y = each node's table
-            const thfhe_mv_spec m = T.mvs[g.tree];
-            const bool is_tree = g.cls == kDagTreeMv;
-            const int hi0 = m.lo.n_inputs;
-            const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};
-            const int32_t *const tv0 = c->d_dag_mv_tv0.as<int32_t>() + (size_t)m.base * 1024;
-            const MvArgs mv{c->d_dag_mv_w.as<int32_t>() + m.factors_off, m.p};
-            return dag_group_slices(g, mv_slice_of(g.tree, (size_t)g.all), is_tree ? m.k : m.q, dst, words, st, [&](long first, long S) {
-                const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {m.lo}, g.t_y, first, g.cnt, g.n_wires, 1};
-                if (!is_tree) return enqueue_pbs(c, lo, (size_t)S, tv0, nullptr, m.q, nullptr, dst, false, &mv);
-                const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
-                return enqueue_tree_chain(c, pc, lo, tv0, m.k * m.q, hi, (size_t)S, m.q, dst, no_seam, &mv, (size_t)m.k);
+        if (g.cls != kDagSelect)
+            return dag_run_group<int32_t>(c, T, g, &thfhe_ctx::tree_slice, tree_chain_of(c, pc), [&](const auto &lo, size_t S, const int32_t *tv0, const int32_t *w, int mv_p, int q) {
+                const MvArgs mv{w, mv_p};
+                return enqueue_pbs(c, lo, S, tv0, nullptr, q, nullptr, dst, false, &mv);
             });
-        }
-        const thfhe_tree_spec ts = T.trees[g.tree];
-        const int p = ts.p_hi, hi0 = g.cls == kDagTree ? ts.lo.n_inputs : 0;
-        const int32_t *col[5] = {g.t0, g.t1, g.t2, g.t2, g.t2};   // the index operands of a TREE node follow its lo.n_inputs level-1 operands
-        return dag_group_slices(g, slice_of(g.tree, (size_t)g.all), 1, dst, words, st, [&](long first, long S) {
-            const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
-            if (g.cls == kDagTree) {   // t_y = row0
-                const LutWireSrc<LutSpecByValue, LutIdx::table> lo{g.wires, g.t0, g.t1, g.t2, {ts.lo}, g.t_y, first, g.cnt, g.n_wires, p / ts.lo.theta};
-                return enqueue_tree_chain(c, pc, lo, c->d_dag_tv1.as<int32_t>(), ts.lo.theta, hi, (size_t)S, p, dst, no_seam);
-            }
-            // SELECT: t_y = first candidate wire
+        const thfhe_tree_spec ts = T.trees[g.tree];   // t_y = first candidate wire
+        const int p = ts.p_hi;
+        return dag_group_slices(g, dag_group_slice(c, T, g.cls, g.tree, (size_t)g.all, &thfhe_ctx::tree_slice), 1, dst, words, st, [&](long first, long S) {
+            const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, g.t0, g.t1, g.t2, {ts.hi}, nullptr, first, g.cnt, g.n_wires, 1};
             hipLaunchKernelGGL(dag_select_gather_kernel, dim3((unsigned)((words + 255) / 256), (unsigned)std::min<long>(S * p, 65535)), dim3(256), 0, st,
                                (const int32_t *)g.wires, g.t_y, c->d_tree_lwe.as<int32_t>(), first, S, g.cnt, g.n_wires, words, p);
-            return enqueue_tree_chain(c, pc, nullptr, nullptr, 1, hi, (size_t)S, p, dst, no_seam);
+            return enqueue_tree_chain(c, pc, nullptr, nullptr, 1, hi, (size_t)S, p, dst, [](int) { return (int)THFHE_OK; });
         });
     };
     c->grp_valid = false;
@@ -917,11 +884,8 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
 // what tree_validate (thfhe_pbs_host.h) admits here: p_hi up to N / 2
 constexpr TreeRules kTreeRules{512, "tree: p_hi must be a power of two in 2 .. N/2", "tree: n_tables must be 1 .. 262144 / (p_hi / theta)"};
 
-// Two-digit tree PBS: per slice of S samples one enqueue_tree_chain on contiguous operands -- level 1 on the rows
-// tv[table[s]][r] (tv_rows rows of N words in all) and the `lo` operands, the selection on the `hi` operands.  Only the inputs of a slice go up and its
-// S results come down.  factors: level 1 is one multi-value rotation per sample of the base vector tv with the p_hi factors of mv_p taps
-// of table[s], int32[mv_tables][p_hi][mv_p].  k (with factors only): k tables per sample from the one rotation, factors
-// int32[mv_tables][k][p_hi][mv_p], out int32[count][k][n+1].  The arguments have passed the entry's host checks.
+// Two-digit tree PBS: both locks and the packing key's checks, then ctx_tree_bootstrap (thfhe_pbs_host.h) on this engine's
+// tree workspace and chain, ev[0] on the call's first slice.  The arguments have passed the entry's host checks.
 int tree_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec &lo, const thfhe_lut_spec &hi, int p_hi, const int32_t *tv, size_t tv_rows,
                    const int32_t *factors, int mv_p, int mv_tables, const int32_t *table_index, const int32_t *lo0, const int32_t *lo1, const int32_t *lo2,
                    const int32_t *hi0, const int32_t *hi1, const int32_t *hi2, int32_t *out, size_t count, int k = 1) {
@@ -930,41 +894,11 @@ int tree_bootstrap(thfhe_ctx *c, thfhe_poly_ctx *pc, const thfhe_lut_spec &lo, c
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
     std::lock_guard<std::mutex> pg(pack_ctx_mutex(pc));   // always after the gate context's: nothing else takes both
-    const int n = c->p.n, words = c->rec_words();
     if (!pack_key_n(pc)) return thfhe_fail(THFHE_E_INVALID, "tree: no packing key set (thfhe_pack_key_set)");
-    if (pack_key_n(pc) != n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
-    if (count == 0) return THFHE_OK;
-    const int theta1 = factors ? k * p_hi : lo.theta, R = k * p_hi / theta1;   // level-1 records per rotation, rotations per sample
-    const size_t S_max = std::min(count, std::max<size_t>(1, c->tree_slice / ((size_t)k * p_hi)));
-    const size_t tv_bytes = tv_rows * c->p.N * sizeof(int32_t), w_bytes = factors ? (size_t)mv_tables * k * p_hi * mv_p * sizeof(int32_t) : 0;
-    int rc = c->d_tv.grow(tv_bytes);
-    if (!rc && factors) rc = c->d_mv_w.grow(w_bytes);
-    if (!rc) rc = tree_workspace(c, S_max, p_hi, R, theta1, k);
-    if (!rc) rc = c->stage.grow(S_max * k * words);
-    if (!rc && table_index) rc = c->d_tree_tab.grow(S_max * sizeof(int32_t));
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle (its calls drain it); from here on its buffers are used on `st`
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tv, tv_bytes, hipMemcpyHostToDevice, st));
-    if (factors) THFHE_HIP(hipMemcpyAsync(c->d_mv_w.as<int32_t>(), factors, w_bytes, hipMemcpyHostToDevice, st));
-    const MvArgs mv{c->d_mv_w.as<int32_t>(), mv_p};
-    const int32_t *const in0 = c->stage.in_ptr(0), *const in1 = c->stage.in_ptr(1), *const in2 = c->stage.in_ptr(2);   // `lo`, then `hi` operands of the slice
-    const LutFlatSrc<LutIdx::table> lo_src{in0, in1, in2, lo, R, table_index ? c->d_tree_tab.as<int32_t>() : nullptr};
-    const LutFlatSrc<LutIdx::job> hi_src{in0, in1, in2, hi, k, nullptr};
-    return ctx_tree_sliced(c, count, S_max, lo, hi, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, (size_t)k, [&](size_t S, bool first, bool last, auto upload_hi) {
-        // profiling: ev[0] on the first slice; level 1 | packing | selection on the last
-        if (c->profiling && first) THFHE_HIP(hipEventRecord(c->ev[0], st));
-        auto seam = [&](int stage) {
-            if (c->profiling && last) THFHE_HIP(hipEventRecord(c->ev[stage], st));
-            return stage == 2 ? upload_hi() : (int)THFHE_OK;
-        };
-        THFHE_TRY(enqueue_tree_chain(c, pc, lo_src, c->d_tv.as<int32_t>(), theta1, hi_src, S, p_hi, c->stage.out_ptr(), seam, factors ? &mv : nullptr, (size_t)k));
-        if (c->profiling && last) {
-            THFHE_HIP(hipEventRecord(c->ev[3], st));
-            c->ev_valid = true;
-        }
-        return (int)THFHE_OK;
-    });
+    if (pack_key_n(pc) != c->p.n) return thfhe_fail(THFHE_E_INVALID, "tree: the packing key's LWE dimension differs from the gate context's n");
+    if (count) THFHE_HIP(hipStreamSynchronize(pack_ctx_stream(pc)));   // the packing context's own stream is idle (its calls drain it); from here on its buffers are used on c->stream
+    return ctx_tree_bootstrap(c, lo, hi, p_hi, tv, tv_rows, factors, mv_p, mv_tables, table_index, lo0, lo1, lo2, hi0, hi1, hi2, out, count, k, true,
+                              [&](auto... a) { return tree_workspace(c, a...); }, tree_chain_of(c, pc));
 }
 
 // thfhe_mv_lut_bootstrap(_wo_keyswitch): ctx_mv_lut_bootstrap (thfhe_pbs_host.h) in slices of at most tree_slice records, one kLutMv
