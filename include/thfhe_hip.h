@@ -67,8 +67,10 @@ enum thfhe_gate {
     THFHE_LHE_LOOKUP = 21,  /* gate-DAG node: leveled lookup of a table of the run at a TGSW-encrypted address (thfhe_dag_run_lhe_batch only) */
     THFHE_LHE_GATHER = 22,  /* gate-DAG node: leveled pick among 2^d computed wires at a TGSW-encrypted index (thfhe_dag_run_lhe_batch only) */
     THFHE_LHE_WFA = 23,     /* gate-DAG node: layered automaton on TGSW-encrypted bits (thfhe_dag_run_lhe_batch only) */
-    THFHE_CB = 24           /* gate-DAG node: wires -> a computed TGSW set by circuit bootstrapping (thfhe_dag_run_cb_batch only); in
+    THFHE_CB = 24,          /* gate-DAG node: wires -> a computed TGSW set by circuit bootstrapping (thfhe_dag_run_cb_batch only); in
                                THFHE_CB_ONE_ROTATION mode the operand wires must be gate-encoded (+-1/8): the caller's responsibility */
+    THFHE_DENSE = 25        /* gate-DAG node: an encrypted dense layer, M theta outputs from K operand wires (thfhe_dag_run_dense_batch,
+                               thfhe_mk_dag_run_dense_batch only) */
 };
 
 enum thfhe_error {
@@ -906,6 +908,12 @@ int thfhe_dag_run_lhe_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, const int3
                             const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, const thfhe_dag_lhe_families *lhe,
                             size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats);
 int thfhe_dag_last_group_ms(thfhe_ctx *ctx, float *ms);
+/* thfhe_dag_last_stage_ms: with profiling on, ms = the device-event times of the three stages of the context's last six-column run
+ *   (thfhe_dag_run_lut_batch ... thfhe_dag_run_dense_batch): {the uploads -- input records into the wire table, the plan's index table, the output
+ *   wire list --, the levels (every launch group and scatter), the output gather and the download}, events on the gate context's stream.  The host
+ *   work before them (checks, plan, workspace, the table families' upload) is the call's wall clock less their sum.  THFHE_E_INVALID when profiling
+ *   is off or no such run was made since it went on. */
+int thfhe_dag_last_stage_ms(thfhe_ctx *ctx, float ms[3]);
 
 /* ---- circuit-bootstrap nodes in the gate-DAG executor (single key): thfhe_dag_run_lhe_batch with one more node kind, which turns
  * d wires of the run into the d TGSW bits of a COMPUTED set that later leveled rows read, so that an index computed by gates is converted, used by a
@@ -956,6 +964,60 @@ int thfhe_dag_run_cb_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, thfhe_mk_ct
                            const thfhe_dag_lhe_families *lhe, const thfhe_dag_cb_families *cb, size_t instances, const int32_t *out_wires, size_t n_out,
                            int32_t *outputs, int64_t *stats /*[5]*/);
 int thfhe_dag_cb_release(thfhe_ctx *ctx);
+
+/* ---- dense-layer nodes in the gate-DAG executor (both engines): thfhe_dag_run_cb_batch / thfhe_mk_dag_run_tree_batch with one more
+ * node kind, an encrypted dense layer (thfhe_linear_lut_bootstrap) whose K operands are wires of the run and whose M theta records go
+ * back into wires, so that a quantised network and the gates, tables and lookups around it are ONE run on the device-resident wire table.  Every
+ * argument before `dense` means what it means in the entry named; with dense = NULL the call is that call (stats stays [5] / [4]).
+ *   Row: (THFHE_DENSE, wire_off, -1, -1, layer, -1), followed by exactly M theta - 1 THFHE_LUT_OUT rows that name its head.  Its operands are the K
+ *       wires wires[wire_off .. wire_off + K - 1] of the pool: earlier wires (inputs too), in any order, repeats allowed; they count for the depth as
+ *       a CB row's list does, and the node costs one level.  Several rows may name one layers[] entry with different wire_off (a convolution window
+ *       at several positions, one comparator on several operand sets).
+ *   Contract: wire head + m theta + t of instance q is record [0][m][t] of thfhe_linear_lut_bootstrap(ctx, W, bias, M, K, theta, tv, n_luts,
+ *       lut_index, in = the K operand wires' records of instance q, out, 1) -- thfhe_mk_linear_lut_bootstrap on the 3-gen engine, int64 tables and
+ *       records of P n + 1 words --, key switch included, word for word.  W = words[w_off ..], bias = words[bias_off ..] (or none), lut_index =
+ *       words[lut_off ..] (or table 0 for every output); tv is the run's table family.  The noise rule is the flat call's: the
+ *       library cannot see a sum that left [0, p).
+ *   Scheduling: the DENSE rows of a level that share a layers[] entry form one launch group; LUT_OUT wires sit on the head's level.  A group runs in
+ *       slices of S whole samples (a sample = one node of one instance), S = min(nodes x instances, thfhe_set_dag_slice, max(1,
+ *       thfhe_set_linear_slice / M)): the dense kernel reads the operand records in place from the wire table into S M sums, the engine's PBS stage
+ *       and key switch run on those, and the S M theta records are scattered into the wires.  A slice may begin and end inside an instance.
+ *   stats: a DENSE node counts M rotations and one level, its group one launch.
+ *   Checks, on the host before any context is looked at (THFHE_E_INVALID): those of the underlying entry; a family count without its pointer;
+ *       n_layers outside 1 .. 1024, n_words outside 1 .. 2^28; M or K outside 1 .. 65 536, theta not 1, 2 or 4; w_off + M K, bias_off + M or
+ *       lut_off + M past n_words; a lut_off entry outside 0 .. n_luts - 1 (once per entry a row uses); layer out of range; wire_off + K past the wire
+ *       pool; a pool wire that is not earlier than the row; operand fields 2, 3 or field 5 not -1; a missing, extra or misplaced LUT_OUT run; a
+ *       DENSE row with no tv.
+ *   Every other thfhe_dag_* and thfhe_mk_dag_* entry rejects THFHE_DENSE. */
+typedef struct thfhe_dag_dense_spec {
+    int32_t M, K;       /* outputs and operands of the layer, 1 .. 65 536 each (the limits of thfhe_lwe_linear) */
+    int32_t theta;      /* 1, 2 or 4 records per output */
+    int32_t w_off;      /* W = words[w_off .. w_off + M K), int32[M][K] row-major, any int32 values */
+    int32_t bias_off;   /* bias = words[bias_off .. + M) Torus32 words, or -1: none */
+    int32_t lut_off;    /* table of output m = tv[words[lut_off + m]], or -1: tv[0] for every output */
+} thfhe_dag_dense_spec;
+
+typedef struct thfhe_dag_dense_families {
+    const thfhe_dag_dense_spec *layers;   /* 1 .. 1024 */
+    int32_t n_layers;
+    const int32_t *words;                 /* HOST pool: weights, biases, table indices; 1 .. 2^28 words */
+    size_t n_words;
+    const int32_t *wires;                 /* HOST pool of operand wire ids */
+    size_t n_wires;
+} thfhe_dag_dense_families;
+
+int thfhe_dag_run_dense_batch(thfhe_ctx *ctx, thfhe_poly_ctx *ctx_pack, thfhe_mk_ctx *level2, const int32_t *inputs, size_t n_inputs, const int32_t *nodes,
+                              size_t n_nodes, const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a,
+                              const int32_t *enc_b, int n_enc, const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows,
+                              const thfhe_mv_spec *mvs, int n_mvs, const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words,
+                              const thfhe_dag_lhe_families *lhe, const thfhe_dag_cb_families *cb, const thfhe_dag_dense_families *dense, size_t instances,
+                              const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats /*[5]*/);
+int thfhe_mk_dag_run_dense_batch(thfhe_mk_ctx *ctx, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                                 const thfhe_lut_spec *specs, int n_specs, const int64_t *tv, int n_luts, const int64_t *enc_a, const int64_t *enc_b,
+                                 int n_enc, const thfhe_tree_spec *trees, int n_trees, const int64_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs,
+                                 int n_mvs, const int64_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words,
+                                 const int64_t *mv_out_bias, const thfhe_dag_dense_families *dense, size_t instances, const int32_t *out_wires,
+                                 size_t n_out, int32_t *outputs, int64_t *stats);
 
 /* ---- multi-key KEY GENERATION arithmetic on the device --------------------------------------------------------------
  * Exact multiply-accumulate of small-coefficient polynomials with torus polynomials, the only non-trivial arithmetic of

@@ -13,6 +13,9 @@
 //                dag_lhe_gather_kernel stages a GATHER node's candidates for the box packing
 //   kDagGenCb    circuit-bootstrap nodes (thfhe_dag_run_cb_batch; single key): CB rows, whose operands are a LIST of wires (a slice of the
 //                run's wire pool) and whose result is a computed TGSW set that later leveled rows read (the group and its gather kernel: thfhe_dag_cb.h)
+//   kDagGenDense dense-layer nodes (thfhe_dag_run_dense_batch, thfhe_mk_dag_run_dense_batch): DENSE rows, whose operands are a LIST of K
+//                wires (a slice of the family's wire pool) and whose M theta records go to consecutive wires (the group: dag_run_dense_group,
+//                thfhe_pbs_host.h; its kernel reads the wire table in place: LinWireSrc, thfhe_linear.h)
 // The kinds from kDagGenTree on are planned here and run by the engine (thfhe_sk.hip: sk_dag_run_luts), a grouped kind in slices through dag_group_slices.
 // dag_gates_run_batch / dag_gates_run are the four-column entries of both engines.
 #ifndef THFHE_DAG_H
@@ -122,6 +125,7 @@ enum DagClass : int32_t {
     kDagLheGather = 16,  // [lk | first]
     kDagLheWfa = 17,     // [wfa | fin_row0], per wfas[] entry
     kDagCb = 18,         // [cbset | -], ONE group per level (entry -1), before the level's leveled groups; then int32[count][4] = (base, off, d, out wire)
+    kDagDense = 19,      // [layer | -], per layers[] entry; the in0 column holds each node's wire_off, the out column its head wire
 };
 inline bool dag_class_leveled(int cls) { return cls >= kDagLheLookup && cls <= kDagLheWfa; }
 // theta of a LUT / LUT_ENC class, 0 for every other class
@@ -161,6 +165,7 @@ enum DagGen : unsigned {
     kDagGenMv = 4,     // THFHE_MV; with kDagGenTree also THFHE_TREE_MV (thfhe_dag_run_mv_batch; thfhe_mk_dag_run_mv_batch has no tree generation)
     kDagGenLhe = 8,    // THFHE_LHE_LOOKUP, THFHE_LHE_GATHER, THFHE_LHE_WFA (thfhe_dag_run_lhe_batch with its families)
     kDagGenCb = 16,    // THFHE_CB (thfhe_dag_run_cb_batch with its family)
+    kDagGenDense = 32, // THFHE_DENSE (thfhe_dag_run_dense_batch, thfhe_mk_dag_run_dense_batch with their family)
 };
 // Everything a run can bring besides its DagCall: the table families (host pointers) with their counts.  An entry fills the families it has and the
 // generations it admits; none (gens = 0) is a run of four-column gate rows.  After dag_families_check a family without a pointer has count 0.
@@ -184,6 +189,7 @@ struct DagFamilies {
     size_t n_factor_words = 0;
     const thfhe_dag_lhe_families *lhe = nullptr;        // the leveled families, with kDagGenLhe
     const thfhe_dag_cb_families *cb = nullptr;          // the computed sets, with kDagGenCb
+    const thfhe_dag_dense_families *dense = nullptr;    // the dense layers, with kDagGenDense
     int n_client_sets() const { return lhe ? lhe->n_sets : 0; }
     int n_computed_sets() const { return cb ? cb->n_sets : 0; }
     // d of set `s` of the run when the host knows it: a computed set's; -1 for a client set
@@ -261,6 +267,16 @@ inline int dag_wfa_spec_check(const thfhe_dag_lhe_families &F, const thfhe_dag_w
     return THFHE_OK;
 }
 
+// One layers[] entry: the limits of thfhe_lwe_linear and of theta, and its three slices of the word pool.
+inline int dag_dense_spec_check(const thfhe_dag_dense_families &D, const thfhe_dag_dense_spec &l) {
+    if (l.M < 1 || l.M > 65536 || l.K < 1 || l.K > 65536) return thfhe_fail(THFHE_E_INVALID, "dense: M and K must be 1 .. 65536");
+    if (l.theta != 1 && l.theta != 2 && l.theta != 4) return thfhe_fail(THFHE_E_INVALID, "dense: theta must be 1, 2 or 4");
+    if (l.w_off < 0 || (size_t)l.w_off + (size_t)l.M * l.K > D.n_words) return thfhe_fail(THFHE_E_INVALID, "dense: w_off + M K runs past n_words");
+    if (l.bias_off < -1 || (l.bias_off >= 0 && (size_t)l.bias_off + l.M > D.n_words)) return thfhe_fail(THFHE_E_INVALID, "dense: bias_off + M runs past n_words");
+    if (l.lut_off < -1 || (l.lut_off >= 0 && (size_t)l.lut_off + l.M > D.n_words)) return thfhe_fail(THFHE_E_INVALID, "dense: lut_off + M runs past n_words");
+    return THFHE_OK;
+}
+
 // One family of a run: whether its pointer is given, its count, and the range of the count when it is.
 struct DagFamilyRule {
     bool have;
@@ -317,6 +333,15 @@ inline int dag_families_check(const DagCall &A, const DagFamilies &F) {
             if (B->sets[s].wire_off < 0 || (size_t)B->sets[s].wire_off + B->sets[s].d > B->n_cb_wires)
                 return thfhe_fail(THFHE_E_INVALID, "cb: wire_off + d runs past the wire pool");
         }
+    }
+    if (const thfhe_dag_dense_families *const D = F.dense) {
+        THFHE_TRY(dag_family_rules({{D->layers != nullptr, D->n_layers, 1, 1024, "dense: n_layers must be 1 .. 1024"},
+                                    {D->words != nullptr, (long long)D->n_words, 1, 1 << 28, "dense: n_words must be 1 .. 2^28"},
+                                    {D->wires != nullptr, (long long)D->n_wires, 0, INT32_MAX, "dense: n_wires out of range"}},
+                                   "null argument: a dense family with a count but no pointer"));
+        if (!D->layers) return thfhe_fail(THFHE_E_INVALID, "dense: n_layers must be 1 .. 1024");
+        if (!D->words) return thfhe_fail(THFHE_E_INVALID, "dense: n_words must be 1 .. 2^28");
+        for (int t = 0; t < D->n_layers; t++) THFHE_TRY(dag_dense_spec_check(*D, D->layers[t]));
     }
     for (int s = 0; s < F.n_specs; s++)
         THFHE_TRY(lut_spec_check(F.specs[s]));
@@ -477,6 +502,23 @@ struct DagRowChecks {
             if (r.list[i] < 0 || r.list[i] >= w) return thfhe_fail(THFHE_E_INVALID, "CB node: a pool wire is not an earlier wire");
         return THFHE_OK;
     }
+    // (DENSE, wire_off, -1, -1, layer, -1); w: the row's own wire
+    int dense(const int32_t *row, int32_t w, DagRow &r) {
+        const thfhe_dag_dense_families &D = *F.dense;
+        if (row[2] != -1 || row[3] != -1 || row[5] != -1) return thfhe_fail(THFHE_E_INVALID, "DENSE node: operand fields 2, 3 and field 5 must be -1");
+        if (row[4] < 0 || row[4] >= D.n_layers) return thfhe_fail(THFHE_E_INVALID, "DENSE node: layer out of range (0 .. n_layers-1)");
+        const thfhe_dag_dense_spec &l = D.layers[row[4]];
+        if (!F.tv || F.n_luts < 1) return thfhe_fail(THFHE_E_INVALID, "DENSE node: no tables given (null table family)");
+        if (first_use(kDagDense, row[4]) && l.lut_off >= 0)
+            for (int m = 0; m < l.M; m++)
+                if (D.words[l.lut_off + m] < 0 || D.words[l.lut_off + m] >= F.n_luts)
+                    return thfhe_fail(THFHE_E_INVALID, "DENSE node: a lut_off entry is out of range (0 .. n_luts-1)");
+        if (row[1] < 0 || (size_t)row[1] + (size_t)l.K > D.n_wires) return thfhe_fail(THFHE_E_INVALID, "DENSE node: wire_off + K runs past the wire pool");
+        r.cls = kDagDense, r.entry = row[4], r.list = D.wires + row[1], r.list_count = l.K, r.outs = l.M * l.theta - 1;
+        for (int i = 0; i < l.K; i++)
+            if (r.list[i] < 0 || r.list[i] >= w) return thfhe_fail(THFHE_E_INVALID, "DENSE node: a pool wire is not an earlier wire");
+        return THFHE_OK;
+    }
     // a row other than LUT_OUT: the checker of its kind; an opcode of a generation the run does not admit goes to the engine's gates
     template <typename Classify>
     int node(const int32_t *row, int32_t w, Classify classify, DagRow &r) {
@@ -488,6 +530,7 @@ struct DagRowChecks {
         if ((F.gens & kDagGenLhe) && (op == THFHE_LHE_LOOKUP || op == THFHE_LHE_GATHER)) return lookup(row, w, op == THFHE_LHE_GATHER, r);
         if ((F.gens & kDagGenLhe) && op == THFHE_LHE_WFA) return wfa(row, r);
         if ((F.gens & kDagGenCb) && op == THFHE_CB) return cb(row, w, r);
+        if ((F.gens & kDagGenDense) && op == THFHE_DENSE) return dense(row, w, r);
         return gate(row, classify, r);
     }
 };
@@ -523,6 +566,7 @@ struct DagPlan {
 // the blind rotations of a launch group of `count` nodes: a MUX takes two, a TREE node its R level-1 rotations and the selection, a TREE_MV node one
 // multi-value rotation and k selections; a linear gate and a leveled node none
 inline size_t dag_group_rotations(const DagFamilies &F, int cls, int32_t entry, size_t count) {
+    if (cls == kDagDense) return count * (size_t)F.dense->layers[entry].M;   // one rotation per output
     if (cls == kDagLinear || cls >= kDagLheLookup) return 0;   // a CB node: level-2 rotations only (DagPlan::cb_bits)
     if (cls == kDagMux) return 2 * count;
     if (cls == kDagTree) return count * (size_t)(F.trees[entry].p_hi / F.trees[entry].lo.theta + 1);
@@ -535,7 +579,7 @@ inline size_t dag_group_rotations(const DagFamilies &F, int cls, int32_t entry, 
 // classify(op) -> kDagGate2, kDagMux, kDagLinear or kDagGate3, or -1.
 // Every bootstrapped gate and every node adds one level above its operands (a SELECT's and a GATHER's candidates included; LHE_LOOKUP and LHE_WFA
 // nodes have no wire operands and sit on the first); NOT / COPY ride on their operand's level as sub-levels (a NOT may read a NOT of the same
-// depth).  The LUT_OUT rows a head is due -- theta - 1 (LUT, LUT_ENC, LHE_LOOKUP), q - 1 (MV), k - 1 (TREE_MV), n_out theta - 1 (LHE_WFA) -- take
+// depth).  The LUT_OUT rows a head is due -- theta - 1 (LUT, LUT_ENC, LHE_LOOKUP), q - 1 (MV), k - 1 (TREE_MV), n_out theta - 1 (LHE_WFA), M theta - 1 (DENSE) -- take
 // its depth with sub-level 0 and launch nothing.
 // Launch groups of a level, in this order: the gate classes kDagGate2, kDagGate3, kDagMux; the LUT classes by theta; the LUT_ENC classes by theta;
 // the grouped kinds by ascending (class, entry), one group per entry; the linear sub-levels.
@@ -665,6 +709,27 @@ int dag_checked_plan(const DagCall &A, const DagFamilies &F, Classify classify, 
 struct DagBuffers {
     DevBuf wires, tab, ops, pack;
     DevBuf specs;   // thfhe_lut_spec[n_specs] of a LUT run
+    // stage events of a run (thfhe_dag_last_stage_ms): the engine sets `timed` from its profiling switch before dag_execute, which then records
+    // before the input upload | after the uploads (inputs, index table, output wire list) | after the last level | after the output gather and
+    // the download are enqueued
+    bool timed = false, st_valid = false;
+    hipEvent_t st_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DagBuffers() = default;
+    DagBuffers(const DagBuffers &) = delete;
+    DagBuffers &operator=(const DagBuffers &) = delete;
+    ~DagBuffers() {
+        for (hipEvent_t e : st_ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    // event k of a timed run on `stream`; an untimed run records nothing
+    hipError_t stamp(int k, hipStream_t stream) {
+        if (!timed) return hipSuccess;
+        if (!st_ev[k]) {
+            const hipError_t e = hipEventCreate(&st_ev[k]);
+            if (e != hipSuccess) return e;
+        }
+        return hipEventRecord(st_ev[k], stream);
+    }
 };
 
 // The slice of a LUT or LUT_ENC launch group that DagExecute hands to the engine: wire table, the group's index columns, jobs
@@ -728,10 +793,12 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
     if (rc) return rc;
     int32_t *const d_wires = B.wires.as<int32_t>(), *const d_tab = B.tab.as<int32_t>(), *const d_sel = d_tab + plan.tab.size();
     int32_t *const d_ops = B.ops.as<int32_t>(), *const d_pack = B.pack.as<int32_t>();
-    hipError_t e = hipSuccess;
-    if (n_inputs) e = hipMemcpy2DAsync(d_wires, n_wires * rec, h_inputs, n_inputs * rec, n_inputs * rec, instances, hipMemcpyHostToDevice, stream);
+    B.st_valid = false;
+    hipError_t e = B.stamp(0, stream);
+    if (e == hipSuccess && n_inputs) e = hipMemcpy2DAsync(d_wires, n_wires * rec, h_inputs, n_inputs * rec, n_inputs * rec, instances, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_tab, plan.tab.data(), plan.tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && n_sel) e = hipMemcpyAsync(d_sel, h_sel, n_sel * sizeof(int32_t), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = B.stamp(1, stream);
     rc = e == hipSuccess ? THFHE_OK : thfhe_fail_hip(e, "gate-DAG executor: upload");
     const unsigned wb = (unsigned)((words + 255) / 256);
     const dim3 block(256);
@@ -782,6 +849,7 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
     }
     if (rc == THFHE_OK) {
         e = hipGetLastError();
+        if (e == hipSuccess) e = B.stamp(2, stream);
         if (e == hipSuccess && h_sel && n_sel) {
             const long all = (long)(n_sel * instances);
             hipLaunchKernelGGL(dag_gather_kernel, dim3((unsigned)all, wb), block, 0, stream, d_wires, d_sel, d_pack, 0L, all, (long)n_sel, n_wires, words, nullptr, nullptr);
@@ -790,10 +858,12 @@ int dag_execute(const DagPlan &plan, DagBuffers &B, hipStream_t stream, int word
         } else if (e == hipSuccess && !h_sel) {
             e = hipMemcpy2DAsync(h_out, n_gates * rec, d_wires + n_inputs * (size_t)words, n_wires * rec, n_gates * rec, instances, hipMemcpyDeviceToHost, stream);
         }
+        if (e == hipSuccess) e = B.stamp(3, stream);
         if (e != hipSuccess) rc = thfhe_fail_hip(e, "gate-DAG executor");
     }
     e = hipStreamSynchronize(stream);
     if (rc == THFHE_OK && e != hipSuccess) rc = thfhe_fail_hip(e, "gate-DAG executor: sync");
+    B.st_valid = B.timed && rc == THFHE_OK;
     return rc;
 }
 

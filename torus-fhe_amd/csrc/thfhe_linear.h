@@ -22,14 +22,40 @@ constexpr int kLinTileK = 16;   // weights of one output staged in the LDS at a 
 constexpr int kLinMaxDim = 65536;
 static_assert(kLinTileM * kLinTileK == 256, "the weight tile is loaded one word per thread");
 
+// Where the K operand records of a sample live.  LinFlatSrc: the contiguous [S][K][rec] array of a flat call, operand k of sample s = record
+// s K + k.  LinWireSrc (DENSE launch groups of the gate DAG, thfhe_dag.h): sample j of the slice is node g of instance q (first + j = q cnt + g);
+// its operand k is the record of wire pool[t_off[g] + k] in instance q's [n_wires][rec] table, read in place.
+struct LinFlatSrc {
+    static constexpr bool kWire = false;
+    const int32_t *in;
+    __device__ const int32_t *sample(long s, int K, int rec) const { return in + (size_t)s * K * rec; }
+    __device__ const int32_t *ids(long) const { return nullptr; }
+};
+struct LinWireSrc {
+    static constexpr bool kWire = true;
+    const int32_t *wires, *pool, *t_off;
+    long first, cnt;
+    size_t n_wires;
+    __device__ const int32_t *sample(long s, int, int rec) const { return wires + (size_t)((first + s) / cnt) * n_wires * rec; }
+    __device__ const int32_t *ids(long s) const { return pool + t_off[(first + s) % cnt]; }
+};
+
 // x[s][m][i] = sum_k W[m][k] in[s][k][i] (+ bias[m] on the body word i = rec - 1) mod 2^32, for the S samples of a slice.
-// in: [S][K][rec], W: [M][K], bias: [M] or null, x: [S][M][rec].  A workgroup owns kLinTileM outputs x 256 consecutive words of one sample:
-// each lane keeps kLinTileM accumulators and reads its word of every input record once (rows of 1 KiB, coalesced); the weights of the tile go
-// through the LDS kLinTileK columns at a time and are read back wave-uniformly.  grid.x: the 256-word blocks of a record; grid.y strides over the
-// S x ceil(M / kLinTileM) tiles (lwe_linear_launch caps it at 65 535).  Lanes past the record's end stay for the barriers and touch no memory.
-__global__ __launch_bounds__(256) void lwe_linear_kernel(const int32_t *__restrict__ in, const int32_t *__restrict__ W, const int32_t *__restrict__ bias,
+// in: the K records per sample of `src`, W: [M][K], bias: [M] or null, x: [S][M][rec].  A workgroup owns kLinTileM outputs x 256 consecutive words
+// of one sample: each lane keeps kLinTileM accumulators and reads its word of every input record once (rows of 1 KiB, coalesced); the weights of the
+// tile go through the LDS kLinTileK columns at a time and are read back wave-uniformly.  A wire source stages the kLinTileK wire ids of the k-tile
+// next to the weights, between the same two barriers, so the record reads of a tile take their row from the LDS and none waits on an index load
+// from memory.  grid.x: the 256-word blocks of a record; grid.y strides over the S x ceil(M / kLinTileM) tiles (lwe_linear_launch caps it at
+// 65 535).  Lanes past the record's end stay for the barriers and touch no memory.
+template <typename Src>
+__global__ __launch_bounds__(256) void lwe_linear_kernel(Src src, const int32_t *__restrict__ W, const int32_t *__restrict__ bias,
                                                          int32_t *__restrict__ x, long S, int M, int K, int rec) {
     __shared__ uint32_t w[kLinTileK][kLinTileM];
+    int32_t *wid = nullptr;
+    if constexpr (Src::kWire) {
+        __shared__ int32_t wire_ids[kLinTileK];
+        wid = wire_ids;
+    }
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool live = i < rec;
     const int wk = threadIdx.x % kLinTileK, wm = threadIdx.x / kLinTileK;   // the weight this thread stages: consecutive threads, consecutive k
@@ -38,19 +64,24 @@ __global__ __launch_bounds__(256) void lwe_linear_kernel(const int32_t *__restri
     for (long t = blockIdx.y; t < tiles; t += gridDim.y) {
         const long s = t / m_tiles;
         const int m0 = (int)(t - s * m_tiles) * kLinTileM;
-        const int32_t *col = in + (size_t)s * K * rec + i;
+        const int32_t *col = src.sample(s, K, rec) + i;
+        const int32_t *ids = src.ids(s);
         uint32_t acc[kLinTileM];
 #pragma unroll
         for (int m = 0; m < kLinTileM; m++) acc[m] = 0;
         for (int k0 = 0; k0 < K; k0 += kLinTileK) {
             __syncthreads();   // the previous tile's weights have been read
             w[wk][wm] = (m0 + wm < M && k0 + wk < K) ? (uint32_t)W[(size_t)(m0 + wm) * K + k0 + wk] : 0u;
+            if constexpr (Src::kWire)
+                if (wm == 0) wid[wk] = k0 + wk < K ? ids[k0 + wk] : 0;
             __syncthreads();
             const int kn = K - k0 < kLinTileK ? K - k0 : kLinTileK;
             if (live) {
 #pragma unroll 4
                 for (int k = 0; k < kn; k++) {
-                    const uint32_t v = (uint32_t)col[(size_t)(k0 + k) * rec];
+                    uint32_t v;
+                    if constexpr (Src::kWire) v = (uint32_t)col[(size_t)wid[k] * rec];
+                    else v = (uint32_t)col[(size_t)(k0 + k) * rec];
 #pragma unroll
                     for (int m = 0; m < kLinTileM; m++) acc[m] += w[k][m] * v;
                 }
@@ -69,16 +100,23 @@ __global__ __launch_bounds__(256) void lwe_linear_kernel(const int32_t *__restri
     }
 }
 
-inline void lwe_linear_launch(const int32_t *in, const int32_t *W, const int32_t *bias, int32_t *x, size_t S, int M, int K, int rec, hipStream_t stream) {
+template <typename Src>
+void lwe_linear_launch(const Src &src, const int32_t *W, const int32_t *bias, int32_t *x, size_t S, int M, int K, int rec, hipStream_t stream) {
     const size_t tiles = S * (size_t)((M + kLinTileM - 1) / kLinTileM);
     const dim3 grid((unsigned)((rec + 255) / 256), (unsigned)(tiles < 65535 ? tiles : 65535));
-    hipLaunchKernelGGL(lwe_linear_kernel, grid, dim3(256), 0, stream, in, W, bias, x, (long)S, M, K, rec);
+    hipLaunchKernelGGL(lwe_linear_kernel<Src>, grid, dim3(256), 0, stream, src, W, bias, x, (long)S, M, K, rec);
+}
+
+// idx[j] = lut[j mod M] for the jobs of one slice of a DENSE launch group: the table of every output, in the job order of the PBS stage
+__global__ __launch_bounds__(256) void dense_lut_idx_kernel(const int32_t *__restrict__ lut, int32_t *__restrict__ idx, long jobs, int M) {
+    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < jobs; j += (long)gridDim.x * 256) idx[j] = lut[j % M];
 }
 
 // What a context keeps for the dense layer (grow-only): the weights and the bias, a slice's input records and its sums x, and the most PBS jobs
 // (samples x outputs) of one slice (thfhe_set_linear_slice).
 struct LinBufs {
     DevBuf w, bias, in, x;
+    DevBuf dag_words, dag_wires;   // a gate-DAG run's dense families (thfhe_dag_run_dense_batch): the word pool and the operand wire ids
     size_t slice = 4096;
     // profiling (thfhe_linear_last_timings): events around the last slice's input upload and kernel, made by the first profiled call
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};

@@ -29,6 +29,7 @@
 //                             mk_extract_mv_kernel as level 1 the multi-value tree thfhe_mk_tree_lut_bootstrap_mvk: 1 + k rotations for k functions
 //   lwe_linear_kernel (thfhe_linear.h, shared with thfhe_sk.hip)   dense layer (thfhe_mk_lwe_linear, thfhe_mk_linear_lut_bootstrap): integer
 //                             matrix x vector of P n + 1-word records mod 2^32, the sums staying on the device for the PBS of the same call
+//                             ; on the wire-table source the DENSE nodes of the gate DAG (thfhe_mk_dag_run_dense_batch)
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -1372,7 +1373,7 @@ int mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *sp, const int64_t
 // context is looked at, then the run.  The gate classes run as in thfhe_mk_dag_run_batch; a LUT launch group is one PBS stage on the wire table
 // (lut_prologue_kernel over the P n + 1 record words) with the key switch into the staging output.  TREE, TREE_MV and MV groups
 //  are dag_run_group's (thfhe_pbs_host.h) on this engine's chain and its stage with the multi-value epilogue, MV groups in
-// slices by mv_slice.  No stage of a run records profiling events.
+// slices by mv_slice; DENSE groups are dag_run_dense_group's on this engine's PBS stage.  Only the PBS stage of a DENSE group's last slice records profiling events.
 int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const int64_t *mv_out_bias, size_t instances, int64_t *stats) {
     DagPlan plan;
     if ((F.gens & kDagGenTree) && A.nodes)   // before the plan: a SELECT row has a refusal of its own on this engine
@@ -1404,6 +1405,7 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
                                   s.enc ? c->d_dag_enc_a.as<int64_t>() : nullptr, theta, nullptr, c->stage.out_ptr());
         },
         [&](const DagExtGroup &g) -> int {
+            if (g.cls == kDagDense) return dag_run_dense_group<int64_t>(c, F, g, &thfhe_mk_ctx::mv_slice, [&](auto &&...a) { return mk_enqueue_pbs(c, a...); });
             if (g.cls != kDagTree && g.cls != kDagMv && g.cls != kDagTreeMv) return thfhe_fail(THFHE_E_INVALID, "grouped node kind not defined for the 3-gen engine");
             const int64_t bias = mv_out_bias && g.cls != kDagTree ? mv_out_bias[g.tree] : 0;
             return dag_run_group<int64_t>(c, F, g, &thfhe_mk_ctx::mv_slice, mk_tree_chain_of(c, bias), [&](const auto &lo, size_t S, const int64_t *tv0, const int32_t *w, int mv_p, int q) {
@@ -1559,6 +1561,18 @@ int thfhe_mk_dag_run_tree_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n
     DagFamilies F{kDagGenLut | kDagGenTree | kDagGenMv, specs, n_specs, tv, n_luts, reinterpret_cast<const int32_t *>(enc_a), reinterpret_cast<const int32_t *>(enc_b),
                   n_enc, trees, n_trees, reinterpret_cast<const int32_t *>(tv1), n_tv1_rows};
     F.mvs = mvs, F.n_mvs = n_mvs, F.mv_tv0 = mv_tv0, F.n_bases = n_bases, F.mv_factors = mv_factors, F.n_factor_words = n_factor_words;
+    return mk_dag_run(c, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, F, mv_out_bias, instances, stats);
+}
+
+// ... and dense-layer nodes: DENSE rows on the run's Torus64 tables; without the family (dense NULL) the call is the one above.
+int thfhe_mk_dag_run_dense_batch(thfhe_mk_ctx *c, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes, const thfhe_lut_spec *specs,
+                                 int n_specs, const int64_t *tv, int n_luts, const int64_t *enc_a, const int64_t *enc_b, int n_enc, const thfhe_tree_spec *trees,
+                                 int n_trees, const int64_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs, const int64_t *mv_tv0, int n_bases,
+                                 const int32_t *mv_factors, size_t n_factor_words, const int64_t *mv_out_bias, const thfhe_dag_dense_families *dense,
+                                 size_t instances, const int32_t *out_wires, size_t n_out, int32_t *outputs, int64_t *stats) {
+    DagFamilies F{kDagGenLut | kDagGenTree | kDagGenMv | (dense ? kDagGenDense : 0u), specs, n_specs, tv, n_luts, reinterpret_cast<const int32_t *>(enc_a),
+                  reinterpret_cast<const int32_t *>(enc_b), n_enc, trees, n_trees, reinterpret_cast<const int32_t *>(tv1), n_tv1_rows};
+    F.mvs = mvs, F.n_mvs = n_mvs, F.mv_tv0 = mv_tv0, F.n_bases = n_bases, F.mv_factors = mv_factors, F.n_factor_words = n_factor_words, F.dense = dense;
     return mk_dag_run(c, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, F, mv_out_bias, instances, stats);
 }
 

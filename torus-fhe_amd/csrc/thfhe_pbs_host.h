@@ -1,6 +1,6 @@
 // thfhe_pbs_host.h -- the programmable-bootstrap call bodies the single-key (thfhe_sk.hip) and 3-gen multi-key (thfhe_mk.hip) engines have in
 // common: the flat LUT / encrypted-LUT call, the flat multi-value call, the host checks, the body and the slice loop of a flat tree call,
-// dag_execute's ensure, and the grouped TREE / TREE_MV / MV part of a gate-DAG run (table uploads, slice rule, reserve loop, group body).
+// dag_execute's ensure, and the grouped TREE / TREE_MV / MV / DENSE part of a gate-DAG run (table uploads, slice rule, reserve loop, group bodies).
 // Function templates over the engine's context, like ctx_staged (thfhe_devctx.h); what differs per engine -- its workspace rules, its PBS
 // stage, its tree chain with its multi-value record -- comes in as a callable.  The engine keeps its locks, key checks, refusals, SELECT /
 // leveled / CB groups and profiling wrapper.  The table word (Torus32 / Torus64) follows the table pointer or is named (dag_upload_families<T>,
@@ -131,7 +131,7 @@ int ctx_linear(Ctx *c, const int32_t *W, const int32_t *bias, int M, int K, bool
         if (ev) THFHE_HIP(hipEventRecord(c->lin.ev[0], c->stream));
         THFHE_HIP(hipMemcpyAsync(d_in, in + sl.in_off, S * K * rec * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         if (ev) THFHE_HIP(hipEventRecord(c->lin.ev[1], c->stream));
-        lwe_linear_launch(d_in, d_w, d_bias, d_x, S, M, K, (int)rec, c->stream);
+        lwe_linear_launch(LinFlatSrc{d_in}, d_w, d_bias, d_x, S, M, K, (int)rec, c->stream);
         if (ev) THFHE_HIP(hipEventRecord(c->lin.ev[2], c->stream));
         if (ev) c->lin.ev_valid = true, c->lin.ev_whole = fused && keyswitch;
         THFHE_HIP(hipGetLastError());
@@ -252,26 +252,41 @@ int dag_upload_families(Ctx *c, hipStream_t st, const DagFamilies &F) {
     THFHE_TRY(dag_upload(c->d_dag_enc_b, st, F.enc_b, F.n_enc * row));
     THFHE_TRY(dag_upload(c->d_dag_tv1, st, F.tv1, F.n_tv1_rows * row));
     THFHE_TRY(dag_upload(c->d_dag_mv_tv0, st, F.mv_tv0, F.n_bases * row));
+    if (F.dense) {   // the dense layers' word pool and operand wire ids
+        THFHE_TRY(dag_upload(c->lin.dag_words, st, F.dense->words, F.dense->n_words * sizeof(int32_t)));
+        THFHE_TRY(dag_upload(c->lin.dag_wires, st, F.dense->wires, F.dense->n_wires * sizeof(int32_t)));
+    }
     return dag_upload(c->d_dag_mv_w, st, F.mv_factors, F.n_factor_words * sizeof(int32_t));
 }
 
 // A slice of a grouped kind's `all` nodes over all instances: at most dag_slice of them, and the flat calls' workspace rules -- tree_slice / p_hi
-// nodes of a SELECT / TREE group, tree_slice / (k q) of a TREE_MV group, c->*mv_slice / q of an MV group.
+// nodes of a SELECT / TREE group, tree_slice / (k q) of a TREE_MV group, c->*mv_slice / q of an MV group, lin.slice / M samples of a DENSE group
+// (a sample = one node of one instance: M PBS jobs, thfhe_set_linear_slice's cap).
 template <typename Ctx>
 size_t dag_group_slice(const Ctx *c, const DagFamilies &F, int cls, int entry, size_t all, size_t Ctx::*mv_slice) {
+    if (cls == kDagDense) return std::min({all, c->dag_slice, std::max<size_t>(1, c->lin.slice / (size_t)F.dense->layers[entry].M)});
     const bool mv = cls == kDagMv || cls == kDagTreeMv;
     const size_t per = cls == kDagMv ? c->*mv_slice / (size_t)F.mvs[entry].q : c->tree_slice / (mv ? (size_t)F.mvs[entry].k * F.mvs[entry].q : (size_t)F.trees[entry].p_hi);
     return std::min({all, c->dag_slice, std::max<size_t>(1, per)});
 }
 
-// Every buffer the slices of the plan's TREE / TREE_MV / MV groups use, the staging output included, before dag_execute takes pointers.
+// Every buffer the slices of the plan's TREE / TREE_MV / MV / DENSE groups use, the staging output included, before dag_execute takes pointers.
 // tree_ws(S, p, R, theta_lo, k) / pbs_ws(jobs, theta): the engine's workspace rules; w_cand: raised to the most candidates (S k p) a slice packs.
 template <typename Ctx, typename TreeWs, typename PbsWs>
 int dag_reserve_groups(Ctx *c, const DagPlan &plan, const DagFamilies &F, size_t instances, size_t Ctx::*mv_slice, size_t &w_cand, TreeWs tree_ws, PbsWs pbs_ws) {
     for (const DagBatch &b : plan.batches) {
-        if (b.cls != kDagTree && b.cls != kDagTreeMv && b.cls != kDagMv) continue;
+        if (b.cls != kDagTree && b.cls != kDagTreeMv && b.cls != kDagMv && b.cls != kDagDense) continue;
         const size_t S = dag_group_slice(c, F, b.cls, b.tree, b.count * instances, mv_slice);
         size_t outs = 1;
+        if (b.cls == kDagDense) {   // S samples: S M sums in lin.x, as many PBS jobs of theta records, their table indices
+            const thfhe_dag_dense_spec &l = F.dense->layers[b.tree];
+            const size_t jobs = S * (size_t)l.M;
+            THFHE_TRY(c->lin.x.grow(jobs * c->rec_words() * sizeof(int32_t)));
+            THFHE_TRY(pbs_ws(jobs, l.theta));
+            THFHE_TRY(c->d_lut_idx.grow(jobs * sizeof(int32_t)));
+            THFHE_TRY(c->stage.out.grow(jobs * l.theta * c->rec_words() * sizeof(int32_t)));
+            continue;
+        }
         if (b.cls == kDagMv) {
             outs = (size_t)F.mvs[b.tree].q;
             THFHE_TRY(pbs_ws(S, (int)outs));
@@ -318,6 +333,41 @@ int dag_run_group(Ctx *c, const DagFamilies &F, const DagExtGroup &g, size_t Ctx
         if (!is_tree) return mv_pbs(lo, (size_t)S, tv0, w, m.p, m.q);
         const LutWireSrc<LutSpecByValue, LutIdx::job> hi{g.wires, col[hi0], col[hi0 + 1], col[hi0 + 2], {m.hi}, nullptr, first, g.cnt, g.n_wires, m.k};
         return chain(lo, tv0, m.k * m.q, hi, (size_t)S, m.q, no_seam, w, m.p, (size_t)m.k);
+    });
+}
+
+// One DENSE group of a level, in slices of whole samples (dag_group_slice): lwe_linear_kernel reads the K operand records of every
+// sample in place from the wire table (LinWireSrc: the group's wire_off column into the run's wire pool) and writes the slice's S M sums into
+// lin.x; the engine's PBS stage reads them there as the flat call does (weight 1, bias 0, the table of job j = lut[j mod M], built once per group:
+// a slice starts at a whole sample) and key-switches into stage.out; record [j][m][t] of the slice goes to wire head + m theta + t.
+// pbs(src, jobs, d_tv, d_tva, theta, d_idx, ks_dst, timed): the engine's enqueue_pbs.  Profiling: the events of thfhe_linear_last_timings around the
+// last slice's kernel (no upload: ev[0] = ev[1]), and the PBS stage of the group's last slice is a timed one (thfhe_last_timings).
+template <typename T, typename Ctx, typename Pbs>
+int dag_run_dense_group(Ctx *c, const DagFamilies &F, const DagExtGroup &g, size_t Ctx::*mv_slice, Pbs pbs) {
+    const thfhe_dag_dense_spec l = F.dense->layers[g.tree];
+    const int rec = c->rec_words();
+    const size_t slice = dag_group_slice(c, F, g.cls, g.tree, (size_t)g.all, mv_slice);
+    const int32_t *const words = c->lin.dag_words.template as<int32_t>(), *const pool = c->lin.dag_wires.template as<int32_t>();
+    const int32_t *const bias = l.bias_off >= 0 ? words + l.bias_off : nullptr;
+    int32_t *const d_x = c->lin.x.template as<int32_t>();
+    int32_t *d_idx = nullptr;
+    if (l.lut_off >= 0) {
+        d_idx = c->d_lut_idx.template as<int32_t>();
+        const long jobs = (long)slice * l.M;
+        hipLaunchKernelGGL(dense_lut_idx_kernel, dim3((unsigned)std::min<long>((jobs + 255) / 256, 1024)), dim3(256), 0, c->stream, words + l.lut_off, d_idx, jobs, l.M);
+        THFHE_HIP(hipGetLastError());
+    }
+    return dag_group_slices(g, slice, l.M * l.theta, c->stage.out_ptr(), rec, c->stream, [&](long first, long S) {
+        const bool ev = c->profiling;
+        if (ev) THFHE_TRY(c->lin.events());
+        if (ev) THFHE_HIP(hipEventRecord(c->lin.ev[0], c->stream));
+        if (ev) THFHE_HIP(hipEventRecord(c->lin.ev[1], c->stream));
+        lwe_linear_launch(LinWireSrc{g.wires, pool, g.t0, first, g.cnt, g.n_wires}, words + l.w_off, bias, d_x, (size_t)S, l.M, l.K, rec, c->stream);
+        if (ev) THFHE_HIP(hipEventRecord(c->lin.ev[2], c->stream));
+        if (ev) c->lin.ev_valid = true, c->lin.ev_whole = false;
+        THFHE_HIP(hipGetLastError());
+        return pbs(LutFlatSrc<LutIdx::none>{d_x, d_x, d_x, thfhe_lut_spec{1, {1, 0, 0}, 0, l.theta}, 1, nullptr}, (size_t)S * l.M, c->d_tv.template as<T>(), (const T *)nullptr,
+                   l.theta, (const int32_t *)d_idx, c->stage.out_ptr(), first + S >= g.all);
     });
 }
 

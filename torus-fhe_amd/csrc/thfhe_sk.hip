@@ -21,6 +21,8 @@
 //   lwe_linear_kernel         dense layer (thfhe_lwe_linear, thfhe_linear_lut_bootstrap): integer matrix x LWE vector mod 2^32, the sums
 //   (thfhe_linear.h, shared   staying on the device for the PBS of the same call
 //   with thfhe_mk.hip)
+//                             ; on the wire-table source (LinWireSrc) the DENSE nodes of the gate DAG (thfhe_dag_run_dense_batch),
+//                             with dense_lut_idx_kernel for a group's per-job table indices
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -817,7 +819,8 @@ int sk_dag_lhe_group(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, cons
 // run without SELECT / TREE groups).  Gate classes run as in thfhe_dag_run_batch.  A LUT group is one PBS stage on the wire table over the run's plaintext tables
 // (DESIGN 4.9), a LUT_ENC group the same over its encrypted tables.  TREE, TREE_MV and MV groups are dag_run_group's (thfhe_pbs_host.h) on this
 // engine's chain and PBS stage, sized by dag_reserve_groups.  A SELECT group gathers its candidates into the buffer the box packing reads and runs
-// the tree chain from there.  A leveled group is sk_dag_lhe_group's.  Everything is enqueued on the gate context's stream.
+// the tree chain from there.  A leveled group is sk_dag_lhe_group's, a DENSE group dag_run_dense_group's on this
+// engine's PBS stage.  Everything is enqueued on the gate context's stream.
 int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const DagFamilies &T, const DagCall &A, size_t instances, const DagCbRun &cbr = {}) {
     const int words = c->rec_words();
     hipStream_t st = c->stream;
@@ -840,6 +843,7 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
     // one SELECT / TREE / MV / TREE_MV / leveled group of a level
     auto ext_group = [&](const DagExtGroup &g) -> int {
         int32_t *const dst = c->stage.out_ptr();
+        if (g.cls == kDagDense) return dag_run_dense_group<int32_t>(c, T, g, &thfhe_ctx::tree_slice, [&](auto &&...a) { return enqueue_pbs(c, a...); });
         if (g.cls == kDagCb) return sk_dag_cb_group(c, cbr, plan, T, g, instances);
         if (g.cls >= kDagLheLookup) return sk_dag_lhe_group(c, pc, plan, T, g, instances);
         if (g.cls != kDagSelect)
@@ -857,6 +861,7 @@ int sk_dag_run_luts(thfhe_ctx *c, thfhe_poly_ctx *pc, const DagPlan &plan, const
         });
     };
     c->grp_valid = false;
+    c->dag.timed = c->profiling;   // thfhe_dag_last_stage_ms
     return dag_execute(
         plan, c->dag, st, words, A, instances, c->dag_slice,
         [&](size_t max_gates, int32_t **in, int32_t **out) { return sk_dag_ensure(c, max_gates, plan.max_theta, in, out); },
@@ -1047,6 +1052,7 @@ int thfhe_set_profiling(thfhe_ctx *c, int enabled) {
     THFHE_TRY(ctx_set_profiling(c, enabled));
     std::lock_guard<std::mutex> g(c->mu);
     c->grp_valid = false;
+    c->dag.st_valid = false;
     return THFHE_OK;
 }
 int thfhe_last_timings(thfhe_ctx *c, float ms[4]) { return ctx_last_timings(c, ms); }
@@ -1056,6 +1062,15 @@ int thfhe_dag_last_group_ms(thfhe_ctx *c, float *ms) {
     if (!c->profiling || !c->grp_valid) return thfhe_fail(THFHE_E_INVALID, "no profiled group recorded");
     THFHE_HIP(hipEventSynchronize(c->grp_ev[1]));
     THFHE_HIP(hipEventElapsedTime(ms, c->grp_ev[0], c->grp_ev[1]));
+    return THFHE_OK;
+}
+// ms = {uploads, the levels, output gather + download} of the last six-column run made with profiling on (DagBuffers::st_ev)
+int thfhe_dag_last_stage_ms(thfhe_ctx *c, float ms[3]) {
+    if (!c || !ms) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->profiling || !c->dag.st_valid) return thfhe_fail(THFHE_E_INVALID, "no profiled run recorded");
+    THFHE_HIP(hipEventSynchronize(c->dag.st_ev[3]));
+    for (int k = 0; k < 3; k++) THFHE_HIP(hipEventElapsedTime(&ms[k], c->dag.st_ev[k], c->dag.st_ev[k + 1]));
     return THFHE_OK;
 }
 
@@ -1143,6 +1158,19 @@ int thfhe_dag_run_cb_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, thfhe_mk_ctx *level
     if (stats) stats[4] = 0;
     const DagFamilies T{kDagGenLut | kDagGenTree | kDagGenMv | (lhe ? kDagGenLhe : 0u) | (cb ? kDagGenCb : 0u), specs, n_specs, tv, n_luts, enc_a, enc_b, n_enc, trees,
                         n_trees, tv1, n_tv1_rows, mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words, lhe, cb};
+    return sk_dag_run(c, pc, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, T, instances, stats, level2);
+}
+
+// the dense-layer nodes, when their family is given; without it (dense NULL) the call is thfhe_dag_run_cb_batch.
+int thfhe_dag_run_dense_batch(thfhe_ctx *c, thfhe_poly_ctx *pc, thfhe_mk_ctx *level2, const int32_t *inputs, size_t n_inputs, const int32_t *nodes, size_t n_nodes,
+                              const thfhe_lut_spec *specs, int n_specs, const int32_t *tv, int n_luts, const int32_t *enc_a, const int32_t *enc_b, int n_enc,
+                              const thfhe_tree_spec *trees, int n_trees, const int32_t *tv1, int n_tv1_rows, const thfhe_mv_spec *mvs, int n_mvs,
+                              const int32_t *mv_tv0, int n_bases, const int32_t *mv_factors, size_t n_factor_words, const thfhe_dag_lhe_families *lhe,
+                              const thfhe_dag_cb_families *cb, const thfhe_dag_dense_families *dense, size_t instances, const int32_t *out_wires, size_t n_out,
+                              int32_t *outputs, int64_t *stats) {
+    if (stats) stats[4] = 0;
+    const DagFamilies T{kDagGenLut | kDagGenTree | kDagGenMv | (lhe ? kDagGenLhe : 0u) | (cb ? kDagGenCb : 0u) | (dense ? kDagGenDense : 0u), specs, n_specs, tv, n_luts,
+                        enc_a, enc_b, n_enc, trees, n_trees, tv1, n_tv1_rows, mvs, n_mvs, mv_tv0, n_bases, mv_factors, n_factor_words, lhe, cb, dense};
     return sk_dag_run(c, pc, DagCall{inputs, n_inputs, nodes, n_nodes, out_wires, n_out, outputs}, T, instances, stats, level2);
 }
 

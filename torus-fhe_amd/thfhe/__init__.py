@@ -21,6 +21,7 @@ LUT_ENC, SELECT, TREE = 16, 17, 18   # gate-DAG encrypted-table, select and tree
 MV, TREE_MV = 19, 20                 # gate-DAG multi-value and k-output multi-value tree nodes (CloudKey.dag_run_mv_batch, dag_run_lhe_batch; MV: MKCloudKey.dag_run_mv_batch)
 LHE_LOOKUP, LHE_GATHER, LHE_WFA = 21, 22, 23   # gate-DAG leveled nodes on TGSW-encrypted bits (CloudKey.dag_run_lhe_batch only)
 CB = 24                                        # gate-DAG node: wires -> a computed TGSW set by circuit bootstrapping (CloudKey.dag_run_cb_batch only)
+DENSE = 25                                     # gate-DAG node: an encrypted dense layer on K operand wires (CloudKey / MKCloudKey.dag_run_dense_batch only)
 
 MU8 = 1 << 29     # encode_message(1, 8), Torus32      (numeric-functions.jl:86-89)
 MU8_64 = 1 << 61  # encode_message64(1, 8), Torus64    (numeric-functions.jl:92-95)
@@ -197,6 +198,29 @@ class DagCbFamilies(C.Structure):
                 ("mode", C.c_int32), ("words", C.POINTER(C.POINTER(C.c_int32)))]
 
 
+class DagDenseSpec(C.Structure):
+    """thfhe_dag_dense_spec (include/thfhe_hip.h): the shape of one dense layer and its slices of the word pool (bias_off / lut_off -1: none)."""
+    _fields_ = [(f, C.c_int32) for f in ("M", "K", "theta", "w_off", "bias_off", "lut_off")]
+
+
+class DagDenseFamilies(C.Structure):
+    """thfhe_dag_dense_families (include/thfhe_hip.h)."""
+    _fields_ = [("layers", C.POINTER(DagDenseSpec)), ("n_layers", C.c_int32), ("words", C.POINTER(C.c_int32)), ("n_words", C.c_size_t),
+                ("wires", C.POINTER(C.c_int32)), ("n_wires", C.c_size_t)]
+
+
+def _dense_families(layers, words, wires):
+    """(DagDenseFamilies or None, the arrays it points into) from DagDenseSpec or (M, K, theta, w_off, bias_off, lut_off) tuples, the word pool and
+    the pool of operand wire ids; None without any of the three."""
+    if not len(layers) and words is None and wires is None:
+        return None, ()
+    ls = (DagDenseSpec * len(layers))(*[l if isinstance(l, DagDenseSpec) else DagDenseSpec(*[int(v) for v in l]) for l in layers]) if len(layers) else None
+    w = None if words is None else np.ascontiguousarray(words, np.int32).reshape(-1)
+    pool = None if wires is None else np.ascontiguousarray(wires, np.int32).reshape(-1)
+    fam = DagDenseFamilies(ls, len(layers), _p32(w), 0 if w is None else w.shape[0], _p32(pool), 0 if pool is None else pool.shape[0])
+    return fam, (ls, w, pool)
+
+
 def _lut_spec(s):
     """LutSpec from a (n_inputs, (w0, w1, w2), bias, theta) tuple (or a LutSpec)."""
     if isinstance(s, LutSpec):
@@ -245,9 +269,14 @@ SIGNATURES = {
                                           C.POINTER(TreeSpec), C.c_int, _i32p, C.c_int, C.POINTER(MvSpec), C.c_int, _i32p, C.c_int, _i32p, C.c_size_t,
                                           C.POINTER(DagLheFamilies), C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_dag_last_group_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
+    "thfhe_dag_last_stage_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "thfhe_dag_run_cb_batch": (C.c_int, [_vp, _vp, _vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, _i32p, _i32p, C.c_int,
                                          C.POINTER(TreeSpec), C.c_int, _i32p, C.c_int, C.POINTER(MvSpec), C.c_int, _i32p, C.c_int, _i32p, C.c_size_t,
                                          C.POINTER(DagLheFamilies), C.POINTER(DagCbFamilies), C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
+    "thfhe_dag_run_dense_batch": (C.c_int, [_vp, _vp, _vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i32p, C.c_int, _i32p, _i32p, C.c_int,
+                                            C.POINTER(TreeSpec), C.c_int, _i32p, C.c_int, C.POINTER(MvSpec), C.c_int, _i32p, C.c_int, _i32p, C.c_size_t,
+                                            C.POINTER(DagLheFamilies), C.POINTER(DagCbFamilies), C.POINTER(DagDenseFamilies), C.c_size_t, _i32p, C.c_size_t, _i32p,
+                                            _i64p]),
     "thfhe_dag_cb_release": (C.c_int, [_vp]),
     "thfhe_bootstrap": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
     "thfhe_bootstrap_wo_keyswitch": (C.c_int, [_vp, C.c_int32, _i32p, _i32p, C.c_size_t]),
@@ -371,6 +400,9 @@ SIGNATURES = {
     "thfhe_mk_dag_run_tree_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, _i64p, _i64p, C.c_int,
                                               C.POINTER(TreeSpec), C.c_int, _i64p, C.c_int, C.POINTER(MvSpec), C.c_int, _i64p, C.c_int, _i32p, C.c_size_t, _i64p,
                                               C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
+    "thfhe_mk_dag_run_dense_batch": (C.c_int, [_vp, _i32p, C.c_size_t, _i32p, C.c_size_t, C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, _i64p, _i64p, C.c_int,
+                                               C.POINTER(TreeSpec), C.c_int, _i64p, C.c_int, C.POINTER(MvSpec), C.c_int, _i64p, C.c_int, _i32p, C.c_size_t, _i64p,
+                                               C.POINTER(DagDenseFamilies), C.c_size_t, _i32p, C.c_size_t, _i32p, _i64p]),
     "thfhe_mk_prologue_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t]),
     "thfhe_mk_set_stream": (C.c_int, [_vp, _vp]),
     "thfhe_mk_set_pair_threshold": (C.c_int, [_vp, C.c_long]),
@@ -928,9 +960,10 @@ class CloudKey(_EvalKey):
                                      wfa_words, fin_b, fin_a, out_wires, pack)
 
     def _dag_run_leveled(self, cb, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, mvs=(), mv_tv0=None, mv_factors=None,
-                         tgsw_sets=(), lks=(), tab_b=None, tab_a=None, wfas=(), wfa_words=None, fin_b=None, fin_a=None, out_wires=None, pack=None):
+                         tgsw_sets=(), lks=(), tab_b=None, tab_a=None, wfas=(), wfa_words=None, fin_b=None, fin_a=None, out_wires=None, pack=None, dense=None):
         """What dag_run_lhe_batch (cb = None) and dag_run_cb_batch share: the leveled families.  cb = (the level-2 key or None, a pointer to the
-        DagCbFamilies or None): the run goes through thfhe_dag_run_cb_batch with the level-2 context after the other two and a fifth statistic."""
+        DagCbFamilies or None): the run goes through thfhe_dag_run_cb_batch with the level-2 context after the other two and a fifth statistic.
+        dense = (a pointer to the DagDenseFamilies or None,): the run goes through thfhe_dag_run_dense_batch, the pointer after cb's."""
         N = self.params.N
         mv = _mv_specs(mvs)
         tv0 = None if mv_tv0 is None else np.ascontiguousarray(mv_tv0, np.int32).reshape(-1, N)
@@ -951,6 +984,9 @@ class CloudKey(_EvalKey):
         if cb is None:
             return self._dag_run_ext(lib().thfhe_dag_run_lhe_batch, families, input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack)
         level2, cb_fam = cb
+        if dense is not None:
+            return self._dag_run_ext(lib().thfhe_dag_run_dense_batch, families + (cb_fam, dense[0]), input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires,
+                                     pack, more_ctxs=(None if level2 is None else level2.h,), n_stats=5)
         return self._dag_run_ext(lib().thfhe_dag_run_cb_batch, families + (cb_fam,), input_records, nodes, specs, tv, enc_a, enc_b, trees, tv1, out_wires, pack,
                                  more_ctxs=(None if level2 is None else level2.h,), n_stats=5)
 
@@ -974,6 +1010,15 @@ class CloudKey(_EvalKey):
         out, st = self._dag_run_leveled((l2, C.byref(fam)), input_records, nodes, **kw)
         return (out, st, words) if return_words else (out, st)
 
+    def dag_run_dense_batch(self, input_records, nodes, dense_layers=(), dense_words=None, dense_wires=None, **kw):
+        """dag_run_cb_batch with dense-layer nodes (thfhe_dag_run_dense_batch): a DENSE row (DENSE, wire_off, -1, -1, layer, -1) and its
+        M theta - 1 LUT_OUT rows are linear_lut_bootstrap of layer `layer` on the K wires dense_wires[wire_off .. wire_off + K), the M theta records
+        on consecutive wires.  dense_layers: DagDenseSpec or (M, K, theta, w_off, bias_off, lut_off) tuples into dense_words (int32: weights, bias
+        words, table indices; an offset of -1: none); tv (keyword) holds the tables.  The other arguments are dag_run_cb_batch's.  Without the three
+        the call is dag_run_cb_batch through the new entry."""
+        fam, keep = _dense_families(dense_layers, dense_words, dense_wires)
+        return self.dag_run_cb_batch(input_records, nodes, dense=(None if fam is None else C.byref(fam),), **kw)
+
     def dag_cb_release(self):
         """Free the computed sets the CB nodes of earlier dag_run_cb_batch calls left on this key (thfhe_dag_cb_release); the next run allocates again."""
         _check(lib().thfhe_dag_cb_release(self.h))
@@ -983,6 +1028,13 @@ class CloudKey(_EvalKey):
         ms = C.c_float()
         _check(lib().thfhe_dag_last_group_ms(self.h, C.byref(ms)))
         return ms.value
+
+    def dag_last_stage_ms(self):
+        """Device-event times of the stages of the last dag_run_lut_batch ... dag_run_dense_batch made with set_profiling(True)
+        (thfhe_dag_last_stage_ms): the uploads (inputs, index table, output wire list), the levels, the output gather and download."""
+        ms = (C.c_float * 3)()
+        _check(lib().thfhe_dag_last_stage_ms(self.h, ms))
+        return dict(upload_ms=ms[0], levels_ms=ms[1], download_ms=ms[2])
 
     def dag_run_tree_batch(self, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, out_wires=None, pack=None):
         """dag_run_lut_batch with encrypted-table, select and tree nodes (thfhe_dag_run_tree_batch, DESIGN 4.12).  nodes: int32[n_nodes][6];
@@ -1428,8 +1480,14 @@ class MKCloudKey(_EvalKey):
                     0 if fac is None else fac.shape[0], p64(ob))
         return self._dag_run("dag_run_mv_batch", lib().thfhe_mk_dag_run_mv_batch, (self.h,), input_records, nodes, 6, families, out_wires)
 
+    def dag_run_dense_batch(self, input_records, nodes, dense_layers=(), dense_words=None, dense_wires=None, **kw):
+        """dag_run_tree_batch with dense-layer nodes (thfhe_mk_dag_run_dense_batch): CloudKey.dag_run_dense_batch on int64 tables and
+        records of P n + 1 words.  Without the three dense arguments the call is dag_run_tree_batch through the new entry."""
+        fam, keep = _dense_families(dense_layers, dense_words, dense_wires)
+        return self.dag_run_tree_batch(input_records, nodes, _dense=(None if fam is None else C.byref(fam),), **kw)
+
     def dag_run_tree_batch(self, input_records, nodes, specs=(), tv=None, enc_a=None, enc_b=None, trees=(), tv1=None, mvs=(), mv_tv0=None, mv_factors=None,
-                           mv_out_bias=None, out_wires=None):
+                           mv_out_bias=None, out_wires=None, _dense=None):
         """dag_run_mv_batch with encrypted-table, tree and multi-value tree nodes (thfhe_mk_dag_run_tree_batch).  enc_a, enc_b:
         int64[n_enc][N] RLWE tables; trees: TreeSpec or (lo, hi, p_hi) tuples; tv1: int64[rows][N] level-1 rows; mvs entries may carry hi and k
         (TREE_MV).  TREE and TREE_MV rows need a packing key with D = N (pack_key_set); SELECT rows are refused."""
@@ -1449,8 +1507,9 @@ class MKCloudKey(_EvalKey):
                 raise ValueError(f"mv_out_bias holds {ob.shape[0]} words for {len(mvs)} specs")
             n = lambda a: 0 if a is None else a.shape[0]
             return (sp, len(specs), p64(t), n(t), p64(ea), p64(eb), n(ea), tr, len(trees), p64(rows), n(rows), mv, len(mvs), p64(tv0), n(tv0), _p32(fac),
-                    n(fac), p64(ob))
-        return self._dag_run("dag_run_tree_batch", lib().thfhe_mk_dag_run_tree_batch, (self.h,), input_records, nodes, 6, families, out_wires)
+                    n(fac), p64(ob)) + (() if _dense is None else (_dense[0],))
+        fn = lib().thfhe_mk_dag_run_tree_batch if _dense is None else lib().thfhe_mk_dag_run_dense_batch
+        return self._dag_run("dag_run_tree_batch", fn, (self.h,), input_records, nodes, 6, families, out_wires)
 
     def rotation_kernel_name(self, rotations):
         """The blind-rotation kernel a batch of `rotations` is dispatched to, as mk_launch_rotation in thfhe_mk.hip decides it."""

@@ -33,12 +33,16 @@ Circuit-bootstrap nodes (Circuit.cb_set; single key): d wires of th
 leveled nodes accept in place of a client set id, one level and d l (or d) level-2 rotations.  Circuits that hold them run on thfhe_dag_run_cb_batch
 (`level2`: the level-2 key, default the one CloudKey.cb_key_set named); cb_lookup_dag reads a table at an address the circuit computed, cb_array_read
 an array of computed wires at a computed index, cb_mux_max takes the larger of two numbers the circuit holds as gate bits only.
+
+Dense-layer nodes (Circuit.dense_layer / dense; both engines): an encrypted dense layer (CloudKey.linear_lut_bootstrap)
+whose K operands are wires and whose M theta records come back as wires, one level and M rotations.  Circuits that hold them run on
+thfhe_dag_run_dense_batch / thfhe_mk_dag_run_dense_batch; dense_network chains layers, dense_argmax puts a LUT and gate tail on the last one.
 """
 import time
 
 import numpy as np
 
-from . import AND, CB, COPY, LHE_GATHER, LHE_LOOKUP, LHE_WFA, LUT, LUT_ENC, LUT_OUT, MUX, MV, NOT, OR, SELECT, TREE, TREE_MV, XOR, _wrap32
+from . import AND, CB, COPY, DENSE, LHE_GATHER, LHE_LOOKUP, LHE_WFA, LUT, LUT_ENC, LUT_OUT, MUX, MV, NOT, OR, SELECT, TREE, TREE_MV, XOR, _wrap32
 
 _LHE_OPS = (LHE_LOOKUP, LHE_GATHER, LHE_WFA)
 CB_SET_BASE = 1 << 16   # Circuit.cb_set returns CB_SET_BASE + c for computed set c; ids below it are the client's sets
@@ -69,6 +73,9 @@ class Circuit:
         self.lhe_rows = {}    # gate index of a leveled node -> (lk, row0) / (lk, first) / (wfa, fin_row0)
         self.cb_specs = []    # the operand wires (bit 0 first) of every computed set, in the order of cb_set
         self.cb_rows = {}     # gate index of a CB node -> (computed set, -1)
+        self.dense_specs = [] # (W int32[M][K], bias int32[M] or None, table ids int32[M] or None, theta) of the DENSE launch groups, deduplicated
+        self.dense_wires = [] # the pool of operand wire ids of the DENSE nodes; a node's gate tuple is (DENSE, wire_off, -1, -1)
+        self.dense_rows = {}  # gate index of a DENSE node -> (layer, -1)
         self._ids = {}
 
     def inputs(self, count):
@@ -372,6 +379,66 @@ class Circuit:
         self.cb_specs.append(wires)
         return CB_SET_BASE + len(self.cb_specs) - 1
 
+    def dense_layer(self, W, bias=None, table_ids=None, theta=1):
+        """Register a dense layer: W int[M][K] (any int32 values), bias M Torus32 words or None, table_ids the table (Circuit.table) of every output or
+        None (table 0 for all), theta records per output.  Returns its layer id; equal layers share one id."""
+        W = np.ascontiguousarray(np.asarray(W, np.int64), np.int64)
+        if W.ndim != 2 or W.size == 0 or max(W.shape) > 65536:
+            raise ValueError("dense_layer: W must be int[M][K] with 1 <= M, K <= 65536")
+        if theta not in (1, 2, 4):
+            raise ValueError("theta must be 1, 2 or 4")
+        W = (W & 0xFFFFFFFF).astype(np.uint32).view(np.int32)   # any integer, taken mod 2^32 as _wrap32 does
+        b = None if bias is None else np.array([_wrap32(v) for v in np.asarray(bias).reshape(-1)], np.int32)
+        t = None if table_ids is None else np.ascontiguousarray(table_ids, np.int32).reshape(-1)
+        if (b is not None and b.shape[0] != W.shape[0]) or (t is not None and t.shape[0] != W.shape[0]):
+            raise ValueError("dense_layer: bias and table_ids hold one entry per output")
+        if t is not None and (t.min() < 0 or t.max() >= len(self.tables)):
+            raise ValueError("dense_layer: unknown table id")
+        key = ("dense", W.shape, W.tobytes(), None if b is None else b.tobytes(), None if t is None else t.tobytes(), int(theta))
+        if key not in self._ids:
+            self._ids[key] = len(self.dense_specs)
+            self.dense_specs.append((W, b, t, int(theta)))
+        return self._ids[key]
+
+    def dense(self, layer, inputs):
+        """A DENSE node: layer `layer` (dense_layer) on the K wires `inputs` (any earlier wires, in any order, repeats allowed).  One level, M
+        rotations.  Returns M lists of theta wire ids (consecutive: the node's row, then M theta - 1 LUT_OUT rows)."""
+        if not 0 <= layer < len(self.dense_specs):
+            raise ValueError(f"unknown dense layer {layer}")
+        W, _, _, theta = self.dense_specs[layer]
+        inputs = [int(w) for w in inputs]
+        if len(inputs) != W.shape[1] or any(w < 0 or w >= self.n_wires() for w in inputs):
+            raise ValueError(f"dense: expected {W.shape[1]} wires defined above the node")
+        head = self.gate(DENSE, len(self.dense_wires))
+        self.dense_rows[len(self.gates) - 1] = (int(layer), -1)
+        self.dense_wires += inputs
+        for _ in range(W.shape[0] * theta - 1):
+            self.gate(LUT_OUT, head)
+        return [[head + m * theta + t for t in range(theta)] for m in range(W.shape[0])]
+
+    def has_dense_nodes(self):
+        """Whether the circuit holds a DENSE node (it then runs on thfhe_dag_run_dense_batch / thfhe_mk_dag_run_dense_batch)."""
+        return bool(self.dense_rows)
+
+    def dense_families(self):
+        """The dense_layers, dense_words and dense_wires keyword arguments of dag_run_dense_batch: (M, K, theta, w_off, bias_off, lut_off) per layer,
+        the pool of their weights, bias words and table ids laid end to end, and the pool of operand wires."""
+        layers, words, off = [], [], 0
+        for W, b, t, theta in self.dense_specs:
+            w_off, off = off, off + W.size
+            b_off = -1 if b is None else off
+            off += 0 if b is None else b.size
+            t_off = -1 if t is None else off
+            off += 0 if t is None else t.size
+            layers.append((W.shape[0], W.shape[1], theta, w_off, b_off, t_off))
+            words += [W.reshape(-1)] + [a for a in (b, t) if a is not None]
+        return dict(dense_layers=layers, dense_words=np.concatenate(words) if words else None, dense_wires=np.array(self.dense_wires, np.int32))
+
+    def _dense_operands(self, gi):
+        """the operand wires of the DENSE node at gate index gi"""
+        off = self.gates[gi][1]
+        return self.dense_wires[off:off + self.dense_specs[self.dense_rows[gi][0]][0].shape[1]]
+
     def has_cb_nodes(self):
         """Whether the circuit holds a CB node (it then runs on thfhe_dag_run_cb_batch)."""
         return bool(self.cb_rows)
@@ -446,8 +513,8 @@ class Circuit:
         """int32[n_gates][6] = (op, in0, in1, in2, spec, lut): the rows of thfhe_dag_run_lut_batch (spec = lut = -1 on gate rows); LUT_ENC, SELECT and
         TREE rows (thfhe_dag_run_tree_batch) carry (spec, etab), (tree, first), (tree, row0); MV and TREE_MV rows (thfhe_dag_run_mv_batch) (mv, t);
         LHE_LOOKUP, LHE_GATHER and LHE_WFA rows (thfhe_dag_run_lhe_batch) (lk, row0), (lk, first), (wfa, fin_row0); CB rows (thfhe_dag_run_cb_batch)
-        (cbset, -1)."""
-        rows = [tuple(g) + (self.lut_rows.get(i) or self.ext_rows.get(i) or self.mv_rows.get(i) or self.cb_rows.get(i) or self.lhe_rows.get(i, (-1, -1)))
+        (cbset, -1); DENSE rows (thfhe_dag_run_dense_batch) hold wire_off in the first operand field and carry (layer, -1)."""
+        rows = [tuple(g) + (self.lut_rows.get(i) or self.ext_rows.get(i) or self.mv_rows.get(i) or self.cb_rows.get(i) or self.dense_rows.get(i) or self.lhe_rows.get(i, (-1, -1)))
                 for i, g in enumerate(self.gates)]
         return np.array(rows, np.int32).reshape(-1, 6)
 
@@ -465,7 +532,8 @@ class Circuit:
             if op == LUT_OUT:
                 d = depth[a]
             else:
-                d = max([depth[w] for w in (a, b, c) if w >= 0] + [0])   # a leveled node has no wire operands
+                ops = self._dense_operands(gi) if op == DENSE else (a, b, c)   # a DENSE node's first field is its slice of the wire pool
+                d = max([depth[w] for w in ops if w >= 0] + [0])   # a leveled node has no wire operands
                 if op == SELECT:   # its candidates count too
                     ti, first = self.ext_rows[gi]
                     d = max(d, depth[first:first + self.tree_specs[ti][2]].max())
@@ -504,6 +572,9 @@ class Circuit:
             c.update(lhe_lookups=ops.count(LHE_LOOKUP), lhe_gathers=ops.count(LHE_GATHER), lhe_wfas=ops.count(LHE_WFA))
         if self.cb_rows:
             c.update(cbs=ops.count(CB), cb_bits=sum(len(w) for w in self.cb_specs))
+        if self.dense_rows:   # a DENSE node: one rotation per output
+            extra = sum(self.dense_specs[l][0].shape[0] - 1 for l, _ in self.dense_rows.values())
+            c.update(rotations=c["rotations"] + extra, denses=ops.count(DENSE))
         return c
 
 
@@ -1185,6 +1256,14 @@ def _rotate_noiseless(x, tv, theta):
     return out
 
 
+def _tv32(tv):
+    """a test vector as Torus32 words: an int64 table of the 3-gen engine rounded to its top 32 bits, what the key-switched record carries"""
+    tv = np.asarray(tv)
+    if tv.dtype != np.int64:
+        return tv
+    return (((tv.astype(object) + (1 << 31)) >> 32) % (1 << 32)).astype(np.int64)
+
+
 def _mv_test_vector(tv0, taps):
     """tv0 * F mod (X^N + 1, 2^32) for the factor F = sum_k taps[k] X^(box/2 + k box), box = N / p: the test vector a multi-value output equals a
     plain rotation of (thfhe_mv_lut_bootstrap)."""
@@ -1217,6 +1296,14 @@ def _simulate_words(cir, input_words, lhe_bits=None, instance=0):
             wires = cir.cb_specs[cir.cb_rows[gi][0]]
             computed[cir.cb_rows[gi][0]] = np.array([int(v[w] > 0) for w in wires], np.int64)
             v[o] = v[wires[0]]
+            continue
+        if op == DENSE:   # x_m = sum_k W[m][k] v_k + bias[m] (dense_plain on the messages), then output m's table
+            W, bias, tids, theta = cir.dense_specs[cir.dense_rows[gi][0]]
+            ws = cir._dense_operands(gi)
+            for m in range(W.shape[0]):
+                x = wrap(sum(int(W[m, k]) * int(v[w]) for k, w in enumerate(ws)) + (0 if bias is None else int(bias[m])))
+                outs = _rotate_noiseless(x, _tv32(cir.tables[0 if tids is None else tids[m]]), theta)
+                v[o + m * theta:o + (m + 1) * theta] = [wrap(t) for t in outs]
             continue
         if op in (LUT, LUT_ENC):
             si, ti = cir.lut_rows[gi] if op == LUT else cir.ext_rows[gi]
@@ -1291,7 +1378,7 @@ def simulate(cir, input_bits, lhe_bits=None, instance=0):
     nodes): the plain bits of every CLIENT TGSW set, low bit first -- int[d] per set, or int[instances][d] of which row `instance` is read; a computed
     set's bits (Circuit.cb_set) come from its wires, a positive phase word reading as 1."""
     from . import ANDNY, ANDYN, NAND, NOR, ORNY, ORYN, XNOR
-    if cir.lut_rows or cir.ext_rows or cir.mv_rows or cir.lhe_rows or cir.cb_rows:
+    if cir.lut_rows or cir.ext_rows or cir.mv_rows or cir.lhe_rows or cir.cb_rows or cir.dense_rows:
         return _simulate_words(cir, input_bits, lhe_bits, instance)
     v = np.zeros(cir.n_wires(), bool)
     v[:cir.n_inputs] = np.asarray(input_bits, bool)
@@ -1319,6 +1406,10 @@ def simulate_mk(cir, input_bits):
     -1/4 + x + y + z.  Three false operands give the phase -5/8 = +3/8 (mod 1), so the reference's gate answers TRUE there -- it is a
     correct AND only when at least one operand is true.  The simulation mirrors the gate, not the name."""
     from . import AND3
+    if cir.dense_rows:   # phase words, as simulate: the DENSE nodes through dense_plain's arithmetic on the tables' top 32 bits
+        if any(g[0] == AND3 for g in cir.gates):
+            raise ValueError("simulate_mk: a circuit with DENSE nodes is simulated on phase words, which has no AND3")
+        return _simulate_words(cir, input_bits)
     v = np.zeros(cir.n_wires(), bool)
     v[:cir.n_inputs] = np.asarray(input_bits, bool)
     for gi, (op, a, b, c) in enumerate(cir.gates):
@@ -1343,6 +1434,12 @@ def _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets=None, level2=None, one_rota
                              "trees the D = N key, and a context holds one key")
         mvs, tv0, fac = cir.mv_families()
         bias = [cir.mv_out_bias.get(i, 0) for i in range(len(mvs))]
+        if cir.has_dense_nodes():
+            enc = cir.enc_tables
+            return ck.dag_run_dense_batch(x, cir.nodes(), **cir.dense_families(), specs=cir.specs, tv=_tables(ck, cir) if cir.tables else None,
+                                          enc_a=np.stack([e[0] for e in enc]) if enc else None, enc_b=np.stack([e[1] for e in enc]) if enc else None,
+                                          trees=cir.tree_specs, tv1=np.stack(cir.tv1) if cir.tv1 else None, mvs=mvs, mv_tv0=tv0, mv_factors=fac,
+                                          mv_out_bias=bias if mvs else None, out_wires=sel)
         if cir.has_tree_nodes() or any(g[0] == TREE_MV for g in cir.gates):
             enc = cir.enc_tables
             return ck.dag_run_tree_batch(x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None, np.stack([e[0] for e in enc]) if enc else None,
@@ -1354,12 +1451,16 @@ def _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets=None, level2=None, one_rota
     enc = cir.enc_tables
     args = (x, cir.nodes(), cir.specs, _tables(ck, cir) if cir.tables else None, np.stack([e[0] for e in enc]) if enc else None,
             np.stack([e[1] for e in enc]) if enc else None, cir.tree_specs, np.stack(cir.tv1) if cir.tv1 else None)
-    if cir.has_cb_nodes():
+    if cir.has_cb_nodes() or cir.has_dense_nodes():
         if len(tgsw_sets or ()) < cir.n_lhe_sets():
             raise ValueError("the circuit holds leveled nodes: tgsw_sets must give the %d TgswSets they name" % cir.n_lhe_sets())
         names = ("specs", "tv", "enc_a", "enc_b", "trees", "tv1", "mvs", "mv_tv0", "mv_factors")
-        return ck.dag_run_cb_batch(x, cir.nodes(), **cir.cb_families(), one_rotation=one_rotation, level2=level2, **dict(zip(names, args[2:] + tuple(cir.mv_families()))),
-                                   tgsw_sets=list(tgsw_sets or ())[:cir.n_lhe_sets()], **cir.lhe_families(), out_wires=sel, pack=pack)
+        kw = dict(zip(names, args[2:] + tuple(cir.mv_families())), tgsw_sets=list(tgsw_sets or ())[:cir.n_lhe_sets()], **cir.lhe_families(), out_wires=sel, pack=pack)
+        if cir.has_cb_nodes():
+            kw.update(cir.cb_families(), one_rotation=one_rotation, level2=level2)
+        if cir.has_dense_nodes():
+            return ck.dag_run_dense_batch(x, cir.nodes(), **cir.dense_families(), **kw)
+        return ck.dag_run_cb_batch(x, cir.nodes(), **kw)
     if cir.has_lhe_nodes():
         if tgsw_sets is None or len(tgsw_sets) < cir.n_lhe_sets():
             raise ValueError("the circuit holds leveled nodes: tgsw_sets must give the %d TgswSets they name" % cir.n_lhe_sets())
@@ -1377,9 +1478,9 @@ def evaluate(ck, cir, input_records, stats=None, pack=None, tgsw_sets=None, leve
     (pack: the threshold.PolyContext holding the packing key), circuits with leveled nodes on thfhe_dag_run_lhe_batch (tgsw_sets: the TgswSets they
     name; sample 0 is read), circuits with CB nodes on thfhe_dag_run_cb_batch (level2: the level-2 key, default the one cb_key_set named; one_rotation:
     CloudKey.circuit_bootstrap's)."""
-    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes():
+    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes() or cir.has_dense_nodes():
         x = np.ascontiguousarray(input_records, np.int32).reshape(1, cir.n_inputs, ck.words)
-        if cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes():
+        if cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes() or cir.has_dense_nodes():
             out, st = _run_tree_batch(ck, cir, x, None, pack, tgsw_sets, level2, one_rotation)
         else:
             out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir))
@@ -1405,9 +1506,9 @@ def evaluate_batch(ck, cir, input_records, out_wires=None, stats=None, pack=None
     x = np.ascontiguousarray(input_records, np.int32)
     Q, n_in, words = x.shape
     assert n_in == cir.n_inputs
-    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes() or hasattr(ck, "dag_run_batch"):
+    if cir.has_luts() or cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes() or cir.has_dense_nodes() or hasattr(ck, "dag_run_batch"):
         sel = None if out_wires is None else np.asarray(out_wires, np.int32)
-        if cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes():
+        if cir.has_tree_nodes() or cir.has_mv_nodes() or cir.has_lhe_nodes() or cir.has_cb_nodes() or cir.has_dense_nodes():
             out, st = _run_tree_batch(ck, cir, x, sel, pack, tgsw_sets, level2, one_rotation)
         elif cir.has_luts():
             out, st = ck.dag_run_lut_batch(x, cir.nodes(), cir.specs, _tables(ck, cir), sel)
@@ -1540,6 +1641,22 @@ def _levels_lhe(ck, cir, level, vals, pack, tgsw_sets, instance, computed=None):
     return calls
 
 
+def _levels_dense(ck, cir, level, vals):
+    """The DENSE nodes of one level through the public flat call (linear_lut_bootstrap), one call per layer with its nodes as the samples; returns
+    the number of calls."""
+    gates, base, by = cir.gates, cir.n_inputs, {}
+    for g in level:
+        if gates[g][0] == DENSE:
+            by.setdefault(cir.dense_rows[g][0], []).append(g)
+    for layer, G in sorted(by.items()):
+        W, bias, tids, theta = cir.dense_specs[layer]
+        x = np.stack([vals[cir._dense_operands(g)] for g in G])
+        r = ck.linear_lut_bootstrap(_tables(ck, cir), W, x, bias, theta=theta, lut_index=tids)
+        for j, g in enumerate(G):
+            vals[base + g:base + g + W.shape[0] * theta] = r[j].reshape(-1, r.shape[-1])
+    return len(by)
+
+
 def evaluate_levels(ck, cir, input_records, stats=None, pack=None, tgsw_sets=None, instance=0, level2=None, one_rotation=False):
     """The same schedule driven from the host: one host-buffer call per level (works for single-key and multi-key contexts).  LUT nodes go
     through ck.lut_bootstrap, one call per (theta, spec) of a level: the yardstick of the native LUT-node executor.  LUT_ENC, SELECT and TREE nodes
@@ -1595,13 +1712,15 @@ def _evaluate_levels(ck, cir, vals, pack, tgsw_sets, instance, one_rotation, com
             launches += _levels_mv(ck, cir, level, vals, pack)
         if cir.lhe_rows:
             launches += _levels_lhe(ck, cir, level, vals, pack, tgsw_sets, instance, computed)
+        if cir.dense_rows:
+            launches += _levels_dense(ck, cir, level, vals)
         for g in level:
             if gates[g][0] == CB:
                 wires = cir.cb_specs[cir.cb_rows[g][0]]
                 computed[cir.cb_rows[g][0]] = ck.circuit_bootstrap(vals[wires], len(wires), one_rotation=one_rotation)
                 vals[base + g] = vals[wires[0]]
                 launches += 1
-        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT, LUT_ENC, SELECT, TREE, MV, TREE_MV, CB) + _LHE_OPS]
+        two = [g for g in level if gates[g][0] not in (MUX, _AND3, LUT, LUT_OUT, LUT_ENC, SELECT, TREE, MV, TREE_MV, CB, DENSE) + _LHE_OPS]
         mux = [g for g in level if gates[g][0] == MUX]
         and3 = [g for g in level if gates[g][0] == _AND3]   # 3-gen three-input AND: its own gate class (thfhe_mk_gates)
         if and3:
@@ -1675,3 +1794,53 @@ def conv2d_weights(kernel, in_shape, stride=1):
         for x in range(ow):
             out[:, y, x, y * stride:y * stride + kh, x * stride:x * stride + kw] = k
     return out.reshape(F * oh * ow, H * Wd).astype(np.int32)
+
+
+# ---- dense layers as nodes of a circuit (Circuit.dense_layer / dense) ---------------------------------------------------------------------
+def dense_network(cir, inputs, layers):
+    """Chain dense layers: `layers` holds layer ids (Circuit.dense_layer) or (W, bias, table_ids) triples registered here with theta = 1; the M
+    outputs of a layer are the operands of the next.  Returns the output wires of every layer, the last list being the network's outputs."""
+    outs, x = [], list(inputs)
+    for l in layers:
+        if not isinstance(l, (int, np.integer)):
+            l = cir.dense_layer(*l)
+        if cir.dense_specs[l][3] != 1:
+            raise ValueError("dense_network: a chained layer has theta = 1")
+        x = [o[0] for o in cir.dense(l, x)]
+        outs.append(x)
+    return outs
+
+
+def dense_argmax(cir, scores, p, N=1024, torus_bits=32):
+    """One-hot argmax of the score wires (messages 0 .. p/2 - 1 in the padding-bit encoding of modulus p): a LUT node per pair i < j on
+    s_i - s_j + p/2 (inside [1, p - 1], table `>= p/2` in the gates' encoding), whose NOT is the reverse comparison, and an AND chain per score:
+    winner i beats every later score or ties it, and beats every earlier one strictly, so exactly one gate bit is set -- the lowest index among
+    the maxima.  Two levels and len(scores) (len(scores) - 1) / 2 rotations for the comparisons, then the AND chains.  Returns the winner wires."""
+    from . import lut
+    n = len(scores)
+    if n < 2:
+        raise ValueError("dense_argmax: at least two scores")
+    ge = cir.table(lut.test_vector(lut.bool_outputs(lambda s: s >= p // 2, p, torus_bits=torus_bits), p, N=N, torus_bits=torus_bits))
+    half = int(lut.encode(p // 2, p))
+    beats = {}
+    for i in range(n):
+        for j in range(i + 1, n):
+            beats[i, j] = cir.lut(ge, [scores[i], scores[j]], weights=(1, -1), bias=half)[0]   # s_i >= s_j
+            beats[j, i] = cir.gate(NOT, beats[i, j])                                             # s_j > s_i
+    winners = []
+    for i in range(n):
+        terms = [beats[i, j] for j in range(n) if j != i]
+        w = terms[0]
+        for t in terms[1:]:
+            w = cir.gate(AND, w, t)
+        winners.append(w)
+    return winners
+
+
+def dense_argmax_plain(scores):
+    """The plain twin of dense_argmax: the one-hot vector of the lowest index among the maxima."""
+    s = np.asarray(scores, np.int64)
+    out = np.zeros(s.shape, np.int64)
+    idx = s.argmax(axis=-1)
+    np.put_along_axis(out, np.expand_dims(idx, -1), 1, axis=-1)
+    return out
