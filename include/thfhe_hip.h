@@ -839,6 +839,45 @@ int thfhe_mk_dag_run_tree_batch(thfhe_mk_ctx *ctx, const int32_t *inputs, size_t
 int thfhe_mk_set_pack_wide_threshold(thfhe_mk_ctx *ctx, size_t min_records);
 int thfhe_mk_pack_kernel_name(const thfhe_mk_ctx *ctx, size_t count, char *buf, int len);
 
+/* ---- leveled CMux and table lookup on the 64-bit ring of degree 2048: thfhe_tgsw_set_create / thfhe_lhe_cmux / thfhe_lhe_lookup on a
+ * one-party 3-gen context, whose external product is the ordinary TGSW (.) TLWE product.  Supported contexts have parties = 1, N = 2048 and run
+ * the batched rotation (l x digit parts > 3: the CB sets, l = 2, Bgbit = 18); on any other thfhe_mk_tgsw_set_create returns THFHE_E_UNSUPPORTED and
+ * says which condition failed.  Ring samples are (mask a, body b) of Torus64 polynomials, phase b - a (*) z under the context's ring key.
+ *
+ * thfhe_mk_tgsw_set_create: tgsw: HOST int64[count][d][4][l][N], the layout of a one-party bootstrapping key with n = d
+ *   (thfhe.keygen.MKSecretKeySet.tgsw_encrypt): bit i of sample s is part_1 .. part_4 of a TGswSample_3gen, the gadget value
+ *   bit * 2^(64 - (level+1) Bgbit) on coefficient 0 of part_1 and part_3.  The samples are uploaded one at a time, transformed on the device and kept as
+ *   spectra in the batched path's key layout, count d (2 l parts) 128 KiB (1 MiB per bit on the CB sets); that size is checked against the free
+ *   device memory before anything is allocated (THFHE_E_NOMEM), and a failed create leaves nothing behind.  1 <= d <= 16, 1 <= count <= 2^24.  The
+ *   set belongs to ctx: destroy it before the context.  thfhe_mk_tgsw_set_destroy(NULL) is a no-op.
+ *
+ * thfhe_mk_lhe_cmux: out[s] = d0[s] + C_(s,bit) (.) (d1[s] - d0[s]) for the samples s = 0 .. count-1 of the set.  d1_a, d1_b, d0_a, d0_b, out_a,
+ *   out_b: HOST int64[count][N].  Exact integers: every word equals the 64-bit decomposition (v = D + offset; digit = ((v >> shift) & mask) - Bg/2,
+ *   cut into balanced parts, as the rotation kernels do) and product.
+ *
+ * thfhe_mk_lhe_lookup(_wo_keyswitch): the contract of thfhe_lhe_lookup on this ring: samples first .. first+count-1 of the set, d_tree + d_rot = d,
+ *   0 <= d_tree <= 6, 0 <= d_rot <= 11, box = N >> d_rot, theta in {1, 2, 4} and theta <= box.  tab_b: HOST int64[n_tables][2^d_tree][N]; tab_a: the
+ *   masks, or NULL for a public table; n_tables 2^d_tree <= 262144; table_index: HOST int32[count] or NULL (table 0).  Entry e of function j sits at
+ *   coefficient e * box + j of polynomial e >> d_rot (thfhe.lut.lhe_table with N = 2048, torus_bits = 64).  Per sample: the CMux tree, level t pairing
+ *   neighbours on bit d_rot + t; then for i = 0 .. d_rot-1  ACC += C_(s,i) (.) (X^(2N - box 2^i) ACC - ACC); then coefficients 0 .. theta-1 extracted and
+ *   converted to Torus32 as the engine's programmable bootstrap does; then, for the key-switched entry, the context's key switch.
+ *   out: HOST int32[count][theta][n+1] or int32[count][theta][N+1] (_wo_keyswitch).  Slices of at most max_candidates / 2^(d_tree-1) samples
+ *   (thfhe_mk_set_tree_slice; the tree workspace is 2^(d_tree-1) accumulators of 32 KiB per sample) and 65 535 samples.
+ *
+ * All checks run on the host before the context is looked at (THFHE_E_INVALID), in the order of thfhe_lhe_lookup: null pointers, the ranges above, a
+ * table_index entry out of range, samples outside the set; then a NULL context or a set of another context.  count 0 returns THFHE_OK once those
+ * have passed. */
+typedef struct thfhe_mk_tgsw_set thfhe_mk_tgsw_set;
+int thfhe_mk_tgsw_set_create(thfhe_mk_ctx *ctx, const int64_t *tgsw /*[count][d][4][l][N]*/, size_t count, int d, thfhe_mk_tgsw_set **out);
+void thfhe_mk_tgsw_set_destroy(thfhe_mk_tgsw_set *set);
+int thfhe_mk_lhe_cmux(thfhe_mk_ctx *ctx, const thfhe_mk_tgsw_set *set, int bit, const int64_t *d1_a, const int64_t *d1_b, const int64_t *d0_a,
+                      const int64_t *d0_b /*[count][N]*/, int64_t *out_a, int64_t *out_b, size_t count);
+int thfhe_mk_lhe_lookup(thfhe_mk_ctx *ctx, const thfhe_mk_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta,
+                        const int64_t *tab_a, const int64_t *tab_b /*[n_tables][2^d_tree][N]*/, int n_tables, const int32_t *table_index, int32_t *out);
+int thfhe_mk_lhe_lookup_wo_keyswitch(thfhe_mk_ctx *ctx, const thfhe_mk_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta,
+                                     const int64_t *tab_a, const int64_t *tab_b /*[n_tables][2^d_tree][N]*/, int n_tables, const int32_t *table_index,
+                                     int32_t *out_N1);
+
 /* ---- leveled nodes in the gate-DAG executor (single key): thfhe_dag_run_mv_batch with three more node kinds that read the client's
  * TGSW-encrypted bits, so that a leveled lookup, a leveled pick among COMPUTED wires and a layered automaton run between gates on the device-resident
  * wire table.  Every argument before `lhe` means what it means in thfhe_dag_run_mv_batch; with lhe = NULL the call is that call.  Instance q of the

@@ -30,6 +30,8 @@
 //   lwe_linear_kernel (thfhe_linear.h, shared with thfhe_sk.hip)   dense layer (thfhe_mk_lwe_linear, thfhe_mk_linear_lut_bootstrap): integer
 //                             matrix x vector of P n + 1-word records mod 2^32, the sums staying on the device for the PBS of the same call
 //                             ; on the wire-table source the DENSE nodes of the gate DAG (thfhe_mk_dag_run_dense_batch)
+//   mk_lhe_cmux2k_kernel / mk_lhe_rotate2k_kernel (thfhe_mk_lhe.h)   leveled CMux and table lookup on TGSW samples the caller brings (thfhe_mk_lhe_cmux,
+//                             thfhe_mk_lhe_lookup): the batched N = 2048 step with a key base per job, on d1 - ACC or on public rotation amounts
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -942,6 +944,17 @@ __global__ __launch_bounds__(256) void mk_mux_combine_kernel(const int32_t *__re
 
 }  // namespace
 
+struct thfhe_mk_ctx;
+// Device-resident TGSW samples of thfhe_mk_tgsw_set_create: the spectra of count x d address bits in the layout of the batched
+// path's key table, (sample d + bit) in the place of the key index.  Belongs to the context that made it and is destroyed before it.  Whoever
+// fills `spec` -- the upload of thfhe_mk_lhe.h today, a device-side producer later -- writes that layout in place.
+struct THFHE_INTERNAL thfhe_mk_tgsw_set {
+    thfhe_mk_ctx *ctx = nullptr;
+    DevBuf spec;
+    size_t count = 0;
+    int d = 0;
+};
+
 struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     thfhe_params p;
     DevBuf d_bk;
@@ -972,6 +985,8 @@ struct THFHE_INTERNAL thfhe_mk_ctx : DevCtx {
     size_t tree_slice = 16384;                // level-1 candidates (samples x p_hi) per slice of a tree or packing call: 2 N x 8 B of d_pt each
     DevBuf d_dag_enc_a, d_dag_enc_b, d_dag_tv1;   // a gate-DAG run's encrypted tables and level-1 rows (thfhe_mk_dag_run_tree_batch)
     size_t pack_wide_threshold = kMkPackWideDefault;   // record counts from here on pack with mk_pack_rows_wide_kernel; 0: never
+    // leveled lookup on this ring (thfhe_mk_lhe_cmux, thfhe_mk_lhe_lookup): the CMux tree's workspace (masks, bodies) and the flat CMux's four operands
+    DevBuf d_lhe_a, d_lhe_b, d_lhe_in[4];
 };
 
 namespace {
@@ -1415,6 +1430,9 @@ int mk_dag_run(thfhe_mk_ctx *c, const DagCall &A, const DagFamilies &F, const in
         });
 }
 
+// leveled CMux and table lookup on the ring of degree 2048
+#include "thfhe_mk_lhe.h"
+
 }  // namespace
 
 extern "C" {
@@ -1808,6 +1826,49 @@ int thfhe_mk_set_tree_slice(thfhe_mk_ctx *c, size_t max_candidates) {
     std::lock_guard<std::mutex> g(c->mu);
     c->tree_slice = max_candidates;
     return THFHE_OK;
+}
+
+int thfhe_mk_tgsw_set_create(thfhe_mk_ctx *c, const int64_t *tgsw, size_t count, int d, thfhe_mk_tgsw_set **out) {
+    if (!tgsw || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
+    *out = nullptr;
+    if (d < 1 || d > kMkLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "mk tgsw set: d must be 1 .. 16");
+    if (count < 1 || count > ((size_t)1 << 24)) return thfhe_fail(THFHE_E_INVALID, "mk tgsw set: count must be 1 .. 2^24");
+    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
+    std::unique_ptr<thfhe_mk_tgsw_set> set(new (std::nothrow) thfhe_mk_tgsw_set);
+    if (!set) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
+    set->ctx = c, set->count = count, set->d = d;
+    const int rc = mk_tgsw_set_fill(c, set.get(), tgsw);
+    if (rc) {   // nothing is left behind: the spectra are freed on the context's device
+        (void)hipSetDevice(c->device);
+        return rc;
+    }
+    *out = set.release();
+    return THFHE_OK;
+}
+
+void thfhe_mk_tgsw_set_destroy(thfhe_mk_tgsw_set *set) {
+    if (!set) return;
+    {
+        std::lock_guard<std::mutex> g(set->ctx->mu);   // a call still running on another thread finishes first
+        (void)hipSetDevice(set->ctx->device);
+        (void)hipStreamSynchronize(set->ctx->stream);
+    }
+    delete set;
+}
+
+int thfhe_mk_lhe_cmux(thfhe_mk_ctx *c, const thfhe_mk_tgsw_set *set, int bit, const int64_t *d1_a, const int64_t *d1_b, const int64_t *d0_a,
+                      const int64_t *d0_b, int64_t *out_a, int64_t *out_b, size_t count) {
+    return mk_lhe_cmux(c, set, bit, d1_a, d1_b, d0_a, d0_b, out_a, out_b, count);
+}
+
+int thfhe_mk_lhe_lookup(thfhe_mk_ctx *c, const thfhe_mk_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta, const int64_t *tab_a,
+                        const int64_t *tab_b, int n_tables, const int32_t *table_index, int32_t *out) {
+    return mk_lhe_lookup(c, set, first, count, d_tree, d_rot, theta, tab_a, tab_b, n_tables, table_index, out, true);
+}
+
+int thfhe_mk_lhe_lookup_wo_keyswitch(thfhe_mk_ctx *c, const thfhe_mk_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta,
+                                     const int64_t *tab_a, const int64_t *tab_b, int n_tables, const int32_t *table_index, int32_t *out_N1) {
+    return mk_lhe_lookup(c, set, first, count, d_tree, d_rot, theta, tab_a, tab_b, n_tables, table_index, out_N1, false);
 }
 
 int thfhe_mk_mv_lut_bootstrap(thfhe_mk_ctx *c, const thfhe_lut_spec *spec, const int64_t *tv0, const int32_t *factors, int p, int q, int n_tables,

@@ -380,6 +380,11 @@ SIGNATURES = {
     "thfhe_mk_tree_lut_bootstrap": (C.c_int, [_vp, C.POINTER(LutSpec), C.POINTER(LutSpec), C.c_int, _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
                                               _i32p, _i32p, C.c_size_t]),
     "thfhe_mk_set_tree_slice": (C.c_int, [_vp, C.c_size_t]),
+    "thfhe_mk_tgsw_set_create": (C.c_int, [_vp, _i64p, C.c_size_t, C.c_int, C.POINTER(_vp)]),
+    "thfhe_mk_tgsw_set_destroy": (None, [_vp]),
+    "thfhe_mk_lhe_cmux": (C.c_int, [_vp, _vp, C.c_int, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, C.c_size_t]),
+    "thfhe_mk_lhe_lookup": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _i64p, _i64p, C.c_int, _i32p, _i32p]),
+    "thfhe_mk_lhe_lookup_wo_keyswitch": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _i64p, _i64p, C.c_int, _i32p, _i32p]),
     "thfhe_lwe_linear": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, _i32p, _i32p, C.c_size_t]),
     "thfhe_linear_lut_bootstrap": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, _i32p, _i32p, _i32p, C.c_size_t]),
     "thfhe_linear_lut_bootstrap_wo_keyswitch": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, _i32p, _i32p, _i32p, C.c_size_t]),
@@ -1511,9 +1516,81 @@ class MKCloudKey(_EvalKey):
         fn = lib().thfhe_mk_dag_run_tree_batch if _dense is None else lib().thfhe_mk_dag_run_dense_batch
         return self._dag_run("dag_run_tree_batch", fn, (self.h,), input_records, nodes, 6, families, out_wires)
 
+    # -- leveled CMux and table lookup on the ring of degree 2048 (thfhe_mk_tgsw_set_create, thfhe_mk_lhe_cmux, thfhe_mk_lhe_lookup) --
+    def tgsw_set(self, samples, d):
+        """Device-resident address bits: samples int64[count * d][4][l][N] (MKSecretKeySet.tgsw_encrypt of the bits, sample-major: bit i of sample s
+        is row s d + i), kept as spectra, 1 MiB per bit on the CB sets.  Returns an MKTgswSet: close() it (or use `with`) before this key is closed.
+        One-party contexts on the batched N = 2048 path only (CB_PARAM_SETS)."""
+        return MKTgswSet(self, samples, d)
+
+    def lhe_cmux(self, tset, bit, d1_a, d1_b, d0_a, d0_b):
+        """(out_a, out_b) int64[count][N]: sample s gets d0[s] + C_(s,bit) (.) (d1[s] - d0[s]) -- d1 where its address bit `bit` is 1, else d0."""
+        N = self.params.N
+        arrs = [np.ascontiguousarray(v, np.int64).reshape(-1, N) for v in (d1_a, d1_b, d0_a, d0_b)]
+        _same_count(*arrs)
+        out_a, out_b = np.empty_like(arrs[0]), np.empty_like(arrs[0])
+        p64 = lambda v: v.ctypes.data_as(_i64p)
+        _check(lib().thfhe_mk_lhe_cmux(self.h, tset.h, int(bit), *[p64(v) for v in arrs], p64(out_a), p64(out_b), arrs[0].shape[0]))
+        return out_a, out_b
+
+    def lhe_lookup(self, tset, tab_b, *, d_tree, d_rot, theta=1, tab_a=None, table_index=None, first=0, count=None):
+        """Leveled lookup of samples first .. first+count-1 of the set (default: all from `first`) in the table tab_b int64[n_tables][2^d_tree][N]
+        (thfhe.lut.lhe_table with N = 2048, torus_bits = 64; tab_a: the masks of an encrypted table, None: public): d_tree + d_rot CMuxes, theta
+        functions per sample.  Returns key-switched records int32[count, theta, n+1]."""
+        return self._lhe_lookup(tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, True)
+
+    def lhe_lookup_wo_keyswitch(self, tset, tab_b, *, d_tree, d_rot, theta=1, tab_a=None, table_index=None, first=0, count=None):
+        """lhe_lookup without the key switch: int32[count, theta, N+1] records under the ring key."""
+        return self._lhe_lookup(tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, False)
+
+    def _lhe_lookup(self, tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, keyswitch):
+        N = self.params.N
+        if not 0 <= int(d_tree) <= 6:
+            raise ValueError("d_tree must be 0 .. 6")
+        leaves = 1 << int(d_tree)
+        tab_b = np.ascontiguousarray(tab_b, np.int64)
+        if tab_b.size == 0 or tab_b.size % (leaves * N):
+            raise ValueError(f"tab_b: expected int64[n_tables][{leaves}][{N}]")
+        if tab_a is not None:
+            tab_a = np.ascontiguousarray(tab_a, np.int64)
+            if tab_a.size != tab_b.size:
+                raise ValueError("tab_a and tab_b differ in size")
+        first = int(first)
+        count = tset.count - first if count is None else int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        idx = _index("table_index", table_index, count)
+        out = np.empty((count, _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
+        fn = lib().thfhe_mk_lhe_lookup if keyswitch else lib().thfhe_mk_lhe_lookup_wo_keyswitch
+        _check(fn(self.h, tset.h, first, count, int(d_tree), int(d_rot), int(theta), None if tab_a is None else tab_a.ctypes.data_as(_i64p),
+                  tab_b.ctypes.data_as(_i64p), tab_b.size // (leaves * N), _p32(idx), _p32(out)))
+        return out
+
     def rotation_kernel_name(self, rotations):
         """The blind-rotation kernel a batch of `rotations` is dispatched to, as mk_launch_rotation in thfhe_mk.hip decides it."""
         return self._kernel_name(lib().thfhe_mk_rotation_kernel_name, int(rotations))
+
+
+class MKTgswSet(_Handle):
+    """TGSW samples resident on an MKCloudKey's device (thfhe_mk_tgsw_set_create): the address bits of `count` samples, d bits each."""
+
+    def __init__(self, ck, samples, d):
+        p = ck.params
+        d = int(d)
+        a = np.ascontiguousarray(samples, np.int64)
+        per_bit = 4 * p.l * p.N
+        if d < 1 or a.size == 0 or a.size % (per_bit * d):
+            raise ValueError(f"samples: expected int64[count * d][4][{p.l}][{p.N}] with d = {d}")
+        self.ck, self.d, self.count = ck, d, a.size // (per_bit * d)   # the key is kept alive for as long as the set
+        h = _vp()
+        _check(lib().thfhe_mk_tgsw_set_create(ck.h, a.ctypes.data_as(_i64p), self.count, d, C.byref(h)))
+        self._own(h, lib().thfhe_mk_tgsw_set_destroy)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class PolyMac(_Handle):

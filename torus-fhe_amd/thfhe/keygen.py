@@ -345,43 +345,95 @@ class MKSecretKeySet:
             za = za_all[q] if pm is not None else polymul_small64(crp[None, :], self.rlwe_keys[q])[0].view(np.uint64)
             B += za[None, :] + dtot64(rng.standard_normal((l, N)) * sigma_bk).view(np.uint64)
         # tgsw_encrypt_3gen for every key bit
+        self.sigma_bk, self._crp, self._B = sigma_bk, crp, B
         bk = np.empty((P, n, 4, l, N), np.uint64)
-        g = [np.uint64(64 - (lv + 1) * p.Bgbit) for lv in range(l)]
+        m = self.lwe_keys.reshape(-1).astype(np.uint64)
         for lv in range(l):
-            r1 = rand_ternary(rng, (P * n, N))
-            r2 = rand_ternary(rng, (P * n, N))
-            e = [dtot64(rng.standard_normal((P * n, N)) * sigma_bk).view(np.uint64) for _ in range(4)]
-            m = self.lwe_keys.reshape(-1).astype(np.uint64)
-            if pm is not None:
-                # tgsw_encrypt_3gen on the device: outputs (bit, part), small operands [r1 rows, r2 rows], torus operands [B_lv, A];
-                # the noise and the message m g on coefficient 0 of part_1 / part_3 travel as the addend
-                K = P * n
-                add = np.stack(e, axis=1).copy()                      # [K][4][N]
-                add[:, 0, 0] += m << g[lv]
-                add[:, 2, 0] += m << g[lv]
-                sm = np.concatenate([r1, r2]).astype(np.int32)
-                terms = np.empty((K, 4, 4), np.int32)
-                kk = np.arange(K)
-                for part, (which, tor) in enumerate(((0, 0), (1, 0), (1, 1), (0, 1))):   # P1 = r1 B, P2 = r2 B, P3 = r2 A, P4 = r1 A
-                    terms[:, part] = np.stack([kk * 4 + part, which * K + kk, np.full(K, tor), np.ones(K, np.int64)], axis=1)
-                res = pm.mac(sm, np.stack([B[lv], crp.view(np.uint64)]), terms.reshape(-1, 4), 4 * K, add.reshape(-1, N)).view(np.uint64).reshape(K, 4, N)
-                P1, P2, P3, P4 = (res[:, q] for q in range(4))
-            else:
-                MB = negacyclic_matrix_u64(B[lv])
-                MA = negacyclic_matrix_u64(crp.view(np.uint64))
-                P1 = small_times_torus64(r1, MB) + e[0]
-                P2 = small_times_torus64(r2, MB) + e[1]
-                P3 = small_times_torus64(r2, MA) + e[2]
-                P4 = small_times_torus64(r1, MA) + e[3]
-                P1[:, 0] += m << g[lv]
-                P3[:, 0] += m << g[lv]
-            for part, arr in enumerate((P1, P2, P3, P4)):
+            for part, arr in enumerate(self._tgsw_level(rng, m, lv, pm)):
                 bk[:, :, part, lv, :] = arr.reshape(P, n, N)
         self.bk = bk.view(np.int64)
         if pm is not None:
             pm.close()
         self.ksk = np.stack([gen_keyswitch_key(rng, self.rlwe_keys[q], self.lwe_keys[q], p.ks_t, p.ks_basebit, sigma_ks)
                              for q in range(P)])
+
+    def _tgsw_level(self, rng, m, lv, pm=None):
+        """Level lv of tgsw_encrypt_3gen (tgsw_3gen.jl:41-95) of the messages m uint64[K] on the generator `rng`, under the set's public material
+        (the common random polynomial and the common public key B): (P1, P2, P3, P4) uint64[K][N], P1 = r1 B + e + m g, P2 = r2 B + e, P3 = r2 A + e
+        + m g, P4 = r1 A + e.  The row maker of the bootstrapping key: __init__ draws through it, in the order r1, r2, e[0..3] per level."""
+        p = self.params
+        K, N = m.shape[0], p.N
+        g = np.uint64(64 - (lv + 1) * p.Bgbit)
+        B, crp = self._B, self._crp
+        r1 = rand_ternary(rng, (K, N))
+        r2 = rand_ternary(rng, (K, N))
+        e = [dtot64(rng.standard_normal((K, N)) * self.sigma_bk).view(np.uint64) for _ in range(4)]
+        if pm is not None:
+            # tgsw_encrypt_3gen on the device: outputs (bit, part), small operands [r1 rows, r2 rows], torus operands [B_lv, A];
+            # the noise and the message m g on coefficient 0 of part_1 / part_3 travel as the addend
+            add = np.stack(e, axis=1).copy()                      # [K][4][N]
+            add[:, 0, 0] += m << g
+            add[:, 2, 0] += m << g
+            sm = np.concatenate([r1, r2]).astype(np.int32)
+            terms = np.empty((K, 4, 4), np.int32)
+            kk = np.arange(K)
+            for part, (which, tor) in enumerate(((0, 0), (1, 0), (1, 1), (0, 1))):   # P1 = r1 B, P2 = r2 B, P3 = r2 A, P4 = r1 A
+                terms[:, part] = np.stack([kk * 4 + part, which * K + kk, np.full(K, tor), np.ones(K, np.int64)], axis=1)
+            res = pm.mac(sm, np.stack([B[lv], crp.view(np.uint64)]), terms.reshape(-1, 4), 4 * K, add.reshape(-1, N)).view(np.uint64).reshape(K, 4, N)
+            return tuple(res[:, q] for q in range(4))
+        MB = negacyclic_matrix_u64(B[lv])
+        MA = negacyclic_matrix_u64(crp.view(np.uint64))
+        P1 = small_times_torus64(r1, MB) + e[0]
+        P2 = small_times_torus64(r2, MB) + e[1]
+        P3 = small_times_torus64(r2, MA) + e[2]
+        P4 = small_times_torus64(r1, MA) + e[3]
+        P1[:, 0] += m << g
+        P3[:, 0] += m << g
+        return P1, P2, P3, P4
+
+    def _one_party(self, what):
+        if self.params.parties != 1:
+            raise ValueError(f"{what}: defined for parties = 1 (the one-party 3-gen product is the ordinary TGSW (.) TLWE product)")
+
+    def tgsw_encrypt(self, bits, seed=0x5EED0003):
+        """TGSW samples of `bits` under the ring key, the bootstrapping key's own row maker under the set's own public material ->
+        int64[len(bits)][4][l][N] (parts in mk_part_index order): what MKCloudKey.tgsw_set takes as the address bits of a leveled lookup on this
+        ring, sample-major -- bit i of sample s is row s d + i.  parties = 1 only."""
+        self._one_party("tgsw_encrypt")
+        p = self.params
+        rng = np.random.default_rng(seed)
+        m = np.asarray(bits, np.int64).reshape(-1).astype(np.uint64)
+        out = np.empty((m.shape[0], 4, p.l, p.N), np.uint64)
+        for lv in range(p.l):
+            for part, arr in enumerate(self._tgsw_level(rng, m, lv)):
+                out[:, part, lv, :] = arr
+        return out.view(np.int64)
+
+    def ring_encrypt(self, msg, sigma=None, seed=0x5EED0004):
+        """TLWE samples of the Torus64 polynomials msg int64[..., N] under the ring key: (a, b) with a uniform, b = a (*) z + msg + e, e Gaussian of
+        standard deviation sigma (default: the key's sigma_bk).  The encrypted tables of MKCloudKey.lhe_lookup.  parties = 1 only."""
+        self._one_party("ring_encrypt")
+        N = self.params.N
+        rng = np.random.default_rng(seed)
+        msg = np.ascontiguousarray(msg, np.int64)
+        a = rng.integers(-2**63, 2**63, size=msg.shape, dtype=np.int64)
+        e = dtot64(rng.standard_normal(msg.shape) * (self.sigma_bk if sigma is None else sigma))
+        az = polymul_small64(a.reshape(-1, N), self.rlwe_keys[0]).reshape(msg.shape)
+        return a, (az.view(np.uint64) + msg.view(np.uint64) + e.view(np.uint64)).view(np.int64)
+
+    def tlwe_phase(self, a, b):
+        """b - a (*) z of TLWE samples under the ring key (masks a, bodies b: int64[..., N]) as wrapping int64.  parties = 1 only."""
+        self._one_party("tlwe_phase")
+        a = np.ascontiguousarray(a, np.int64)
+        az = polymul_small64(a.reshape(-1, self.params.N), self.rlwe_keys[0]).reshape(a.shape)
+        return (np.ascontiguousarray(b, np.int64).view(np.uint64) - az.view(np.uint64)).view(np.int64)
+
+    def ring_phase(self, recs):
+        """Phase of LWE(N) records (the _wo_keyswitch outputs, Torus32 words) under the extracted ring key, as wrapping int32.  parties = 1 only."""
+        self._one_party("ring_phase")
+        recs = np.asarray(recs, np.int32).reshape(-1, self.params.N + 1).astype(np.int64)
+        ph = recs[:, -1] - (recs[:, :-1] * self.rlwe_keys[0].astype(np.int64)).sum(axis=1)
+        return ph.astype(np.uint32).view(np.int32)
 
     def encrypt(self, bits, seed=0x5EED0002):
         """mk_encrypt_3gen, mk_api.jl:519-536 -> int32[len(bits)][P*n+1]."""

@@ -190,13 +190,17 @@ def tree_mvk_bool_factors(fs, p_hi, p_lo, N=1024, torus_bits=32):
     return tv0, w.reshape(len(fs), p_hi, p_lo), bias
 
 
-def lhe_table(functions, d_tree, d_rot, theta=1, encode=None, N=1024):
+def lhe_table(functions, d_tree, d_rot, theta=1, encode=None, N=1024, torus_bits=32):
     """Table polynomials of a leveled lookup (thfhe_lhe_lookup): int32[2^d_tree][N] from theta integer tables of 2^(d_tree + d_rot)
     entries (functions[j][e] = f_j(e); with theta = 1 one table will do).  Entry e of function j sits at coefficient (e mod 2^d_rot) * box + j of
     polynomial e >> d_rot, box = N >> d_rot -- the many-LUT layout without the half-box offset: the address is exact, not a noisy phase.  The other
-    coefficients of a box are zero.  encode: integers -> Torus32 words (e.g. lambda v: lut.encode(v, 8)); None: the entries are the words."""
-    if not (0 <= d_tree <= 6 and 0 <= d_rot <= 10):
-        raise ValueError("d_tree must be 0 .. 6 and d_rot 0 .. 10")
+    coefficients of a box are zero.  encode: integers -> Torus32 words (e.g. lambda v: lut.encode(v, 8)); None: the entries are the words.
+    N = 2048, torus_bits = 64 (thfhe_mk_lhe_lookup): int64[2^d_tree][2048] of Torus64 words, d_rot up to 11."""
+    if torus_bits not in (32, 64):
+        raise ValueError("torus_bits must be 32 or 64")
+    max_rot = N.bit_length() - 1
+    if not (0 <= d_tree <= 6 and 0 <= d_rot <= max_rot):
+        raise ValueError(f"d_tree must be 0 .. 6 and d_rot 0 .. {max_rot}")
     box = N >> d_rot
     if theta not in (1, 2, 4) or theta > box:
         raise ValueError("theta must be 1, 2 or 4 and at most box = N >> d_rot")
@@ -211,7 +215,7 @@ def lhe_table(functions, d_tree, d_rot, theta=1, encode=None, N=1024):
     e = np.arange(entries)
     for j in range(theta):
         tab[e >> d_rot, (e & ((1 << d_rot) - 1)) * box + j] = words[j]
-    return _to_i32(tab)
+    return tab if torus_bits == 64 else _to_i32(tab)
 
 
 def lhe_value(values, encode=None, N=1024):
