@@ -1,6 +1,7 @@
-// thfhe_lhe.h -- leveled table lookup on TGSW-encrypted address bits (single key, N = 1024, k = 1): kernels and host side of
-// thfhe_tgsw_set_create, thfhe_lhe_cmux and thfhe_lhe_lookup(_wo_keyswitch).  Included by thfhe_sk.hip INSIDE its second anonymous namespace, after
-// thfhe_ctx, the cooperative blind-rotate kernel (whose barriers and phases it reuses) and enqueue_keyswitch.
+// thfhe_lhe.h -- leveled table lookup on TGSW-encrypted address bits (single key, N = 1024, k = 1): kernels, launchers, the set's
+// fill and this engine's adaptors over the call bodies of thfhe_lhe_host.h for thfhe_tgsw_set_create, thfhe_lhe_cmux and
+// thfhe_lhe_lookup(_wo_keyswitch).  Included by thfhe_sk.hip INSIDE its second anonymous namespace, after thfhe_ctx, the cooperative blind-rotate
+// kernel (whose barriers and phases it reuses) and enqueue_keyswitch.
 //
 // Also the layered automata of DESIGN 4.16, thfhe_lhe_wfa(_wo_keyswitch): sk_lhe_wfa_step_kernel and its host side, further down; and the leveled
 // scatter of DESIGN 4.17, thfhe_lhe_demux and thfhe_lhe_scatter: sk_lhe_demux_kernel, sk_lhe_scatter_rotate_kernel, sk_lhe_scatter_sum_kernel, at the end.
@@ -12,7 +13,7 @@
 #ifndef THFHE_LHE_H
 #define THFHE_LHE_H
 
-constexpr int kLheMaxBits = 16, kLheMaxTree = 6, kLheMaxRot = 10;
+constexpr int kLheMaxRot = 10;   // log2 N; kLheMaxBits and kLheMaxTree are thfhe_lhe_host.h's
 
 // One CMux ACC += C (.) D in the cooperative kernel's F / M / I phases (sk_blind_rotate_coop_kernel), C's chunks of this wave's role in B.
 //   ROT:  D = X^a2n ACC - ACC (rotated_digits_z);  else D = d1 - ACC, d1 in sD1 (diff_digits_z).
@@ -348,129 +349,59 @@ int tgsw_set_fill(thfhe_ctx *c, thfhe_tgsw_set *set, const int32_t *tgsw) {
     return THFHE_OK;
 }
 
-// host checks shared by thfhe_lhe_cmux and thfhe_lhe_lookup once the set is known to be non-null
-int lhe_validate_range(const thfhe_tgsw_set *set, size_t first, size_t count) {
-    if (first > set->count || count > set->count - first) return thfhe_fail(THFHE_E_INVALID, "lhe: samples first .. first+count-1 are not all in the set");
-    return THFHE_OK;
+// what the shared leveled bodies (thfhe_lhe_host.h) admit on this engine: N = 1024, up to 32 768 samples per launch of the flat CMux
+constexpr LheRules<thfhe_ctx> kLheRules{
+    1024, kLheMaxRot, 32768, lhe_sample_slots,   // N, d_rot_max, cmux_slice, sample_slots
+    "tgsw set: d must be 1 .. 16",                                  // set_d_text
+    "tgsw set: count must be 1 .. 2^24",                            // set_count_text
+    "lhe: samples first .. first+count-1 are not all in the set",   // range_text
+    "lhe: the set belongs to another context",                      // ctx_text
+    "lhe_cmux: bit must be 0 .. d-1",                               // bit_text
+    "lhe_lookup: d_tree must be 0 .. 6",                            // d_tree_text
+    "lhe_lookup: d_rot must be 0 .. 10",                            // d_rot_text
+    "lhe_lookup: theta must be 1, 2 or 4",                          // theta_text
+    "lhe_lookup: theta must not exceed box = N >> d_rot",           // box_text
+    "lhe_lookup: n_tables 2^d_tree must be 1 .. 262144",            // n_tables_text
+    "lhe_lookup: d_tree + d_rot must equal the set's d"};           // d_sum_text
+
+// a CMux launch of the shared bodies on sk_lhe_cmux_kernel, over a set of d bits
+int lhe_cmux_level(thfhe_ctx *c, int d, const LheCmuxIo<int32_t> &io, size_t pairs, size_t S) {
+    const LheCmuxArgs a{io.spec, c->d_tw.as<cplx>(), io.d0_a, io.d0_b, io.d1_a, io.d1_b, io.out_a, io.out_b, io.in_idx,
+                        io.in_sample, io.in_pair, io.out_sample, io.out_pair, d, io.bit, c->p.Bgbit};
+    return launch_lhe_cmux(c, a, pairs, S, io.pub);
 }
 
+// thfhe_lhe_cmux: ctx_lhe_cmux (thfhe_lhe_host.h) on this engine's launch
 int lhe_cmux(thfhe_ctx *c, const thfhe_tgsw_set *set, int bit, const int32_t *d1_a, const int32_t *d1_b, const int32_t *d0_a, const int32_t *d0_b,
              int32_t *out_a, int32_t *out_b, size_t count) {
-    if (!d1_a || !d1_b || !d0_a || !d0_b || !out_a || !out_b) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    if (bit < 0 || bit >= kLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "lhe_cmux: bit must be 0 .. d-1");
-    if (!set) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
-    if (bit >= set->d) return thfhe_fail(THFHE_E_INVALID, "lhe_cmux: bit must be 0 .. d-1");
-    THFHE_TRY(lhe_validate_range(set, 0, count));
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (c != set->ctx) return thfhe_fail(THFHE_E_INVALID, "lhe: the set belongs to another context");
-    if (count == 0) return THFHE_OK;
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    const size_t S_max = std::min<size_t>(count, 32768), bytes = S_max * 4096;
-    for (DevBuf &b : c->d_lhe_in) THFHE_TRY(b.grow(bytes));
-    THFHE_TRY(c->d_lhe_a.grow(bytes));
-    THFHE_TRY(c->d_lhe_b.grow(bytes));
-    const int32_t *src[4] = {d0_a, d0_b, d1_a, d1_b};
-    for (size_t s0 = 0; s0 < count; s0 += S_max) {
-        const size_t S = std::min(S_max, count - s0);
-        for (int q = 0; q < 4; q++) THFHE_HIP(hipMemcpyAsync(c->d_lhe_in[q].as<int32_t>(), src[q] + s0 * 1024, S * 4096, hipMemcpyHostToDevice, c->stream));
-        LheCmuxArgs a{set->spec.as<cplx>() + s0 * lhe_sample_slots(c, set->d), c->d_tw.as<cplx>(), c->d_lhe_in[0].as<int32_t>(), c->d_lhe_in[1].as<int32_t>(),
-                      c->d_lhe_in[2].as<int32_t>(), c->d_lhe_in[3].as<int32_t>(), c->d_lhe_a.as<int32_t>(), c->d_lhe_b.as<int32_t>(), nullptr,
-                      1024, 0, 1024, 0, set->d, bit, c->p.Bgbit};
-        THFHE_TRY(launch_lhe_cmux(c, a, 1, S, false));
-        THFHE_HIP(hipMemcpyAsync(out_a + s0 * 1024, c->d_lhe_a.as<int32_t>(), S * 4096, hipMemcpyDeviceToHost, c->stream));
-        THFHE_HIP(hipMemcpyAsync(out_b + s0 * 1024, c->d_lhe_b.as<int32_t>(), S * 4096, hipMemcpyDeviceToHost, c->stream));
-    }
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
+    return ctx_lhe_cmux(c, set, bit, d1_a, d1_b, d0_a, d0_b, out_a, out_b, count, kLheRules,
+                        [&](const LheCmuxIo<int32_t> &io, size_t S) { return lhe_cmux_level(c, set->d, io, 1, S); });
 }
 
-// The launch chain of a leveled lookup over S samples, on device pointers only (thfhe_lhe_lookup's slices and the LOOKUP / GATHER groups of the gate
-// DAG): the CMux tree, the rotations, and with ks_out the key switch of the S theta records into it (else they stay in d_u).  spec: the
-// spectra at the first sample.  Sample s reads the 2^d_tree table polynomials at (t_a, t_b) + index(s) * tab_stride words, index(s) = idx[s] or s
-// (t_a null: a public table).  The caller has sized d_lhe_a / d_lhe_b (S 2^(d_tree-1) polynomials each), d_u and ks_out.  prof: record the
-// profiling events.
+// The launch chain of a leveled lookup over S samples (thfhe_lhe_lookup's slices and the LOOKUP / GATHER groups of the gate DAG):
+// ctx_enqueue_lhe_lookup (thfhe_lhe_host.h) on sk_lhe_cmux_kernel, sk_lhe_rotate_kernel -- one launch, which extracts its theta records into d_u
+// itself -- and the context's key switch.  d: the bits of the set the spectra belong to.
 int enqueue_lhe_lookup(thfhe_ctx *c, const cplx *spec, int d, size_t S, int d_tree, int d_rot, int theta, const int32_t *t_a, const int32_t *t_b,
                        const int32_t *idx, size_t tab_stride, int32_t *ks_out, bool prof) {
-    hipStream_t st = c->stream;
-    const size_t leaves = (size_t)1 << d_tree, ws = d_tree ? leaves / 2 : 0;   // TLWE samples of tree workspace per sample
-    int32_t *const w_a = c->d_lhe_a.as<int32_t>(), *const w_b = c->d_lhe_b.as<int32_t>();
-    if (prof) THFHE_HIP(hipEventRecord(c->ev[0], st));
-    // the tree: level t pairs neighbours on bit d_rot + t; level 0 reads the table, the later levels run in place on the workspace -- the result
-    // of pair p of level t lies at slot p 2^t of the sample, the slot of its own d0, which no other workgroup of the launch touches
-    for (int t = 0; t < d_tree; t++) {
-        LheCmuxArgs a{spec, c->d_tw.as<cplx>(), nullptr, nullptr, nullptr, nullptr, w_a, w_b, nullptr, 0, 0, ws * 1024, 0, d, d_rot + t, c->p.Bgbit};
-        if (t == 0) {
-            a.d0_a = t_a, a.d0_b = t_b, a.d1_a = t_a ? t_a + 1024 : nullptr, a.d1_b = t_b + 1024;
-            a.in_idx = idx, a.in_sample = tab_stride, a.in_pair = 2048, a.out_pair = 1024;
-        } else {
-            const size_t step = (size_t)1024 << t;   // words between the d0 slots of neighbouring pairs
-            a.d0_a = w_a, a.d0_b = w_b, a.d1_a = w_a + step / 2, a.d1_b = w_b + step / 2;
-            a.in_sample = ws * 1024, a.in_pair = step, a.out_pair = step;
-        }
-        THFHE_TRY(launch_lhe_cmux(c, a, leaves >> (t + 1), S, t == 0 && !t_a));
-    }
-    if (prof) THFHE_HIP(hipEventRecord(c->ev[1], st));
-    LheRotArgs r{spec, c->d_tw.as<cplx>(), d_tree ? w_a : t_a, d_tree ? w_b : t_b, d_tree ? nullptr : idx, d_tree ? ws * 1024 : tab_stride,
-                 c->d_u.as<int32_t>(), d, d_rot, 1024 >> d_rot, theta, c->p.Bgbit};
-    THFHE_TRY(launch_lhe_rotate(c, r, S));
-    if (prof) THFHE_HIP(hipEventRecord(c->ev[2], st));
-    if (ks_out) THFHE_TRY(enqueue_keyswitch(c, c->d_u.as<int32_t>(), ks_out, S * theta, 1, false));
-    if (prof) {
-        THFHE_HIP(hipEventRecord(c->ev[3], st));
-        c->ev_valid = true;
-    }
-    return THFHE_OK;
+    return ctx_enqueue_lhe_lookup(
+        c, spec, S, d_tree, d_rot, theta, t_a, t_b, idx, tab_stride, ks_out, prof, kLheRules,
+        [&](const LheCmuxIo<int32_t> &io, size_t pairs) { return lhe_cmux_level(c, d, io, pairs, S); },
+        [&](const int32_t *src_a, const int32_t *src_b, const int32_t *src_idx, size_t src_stride) {
+            const LheRotArgs r{spec, c->d_tw.as<cplx>(), src_a, src_b, src_idx, src_stride, c->d_u.as<int32_t>(), d, d_rot, 1024 >> d_rot, theta, c->p.Bgbit};
+            return launch_lhe_rotate(c, r, S);
+        },
+        [&](int32_t *out, size_t records) { return enqueue_keyswitch(c, c->d_u.as<int32_t>(), out, records, 1, false); });
 }
 
-// thfhe_lhe_lookup (keyswitch) / thfhe_lhe_lookup_wo_keyswitch: out = count x theta records of n+1 (resp. N+1) words, in slices of at most
-// tree_slice / 2^(d_tree-1) samples (the tree workspace: 2^(d_tree-1) TLWE samples of 8 KiB per sample)
+// thfhe_lhe_lookup (keyswitch) / thfhe_lhe_lookup_wo_keyswitch: ctx_lhe_lookup (thfhe_lhe_host.h) on this engine's chain; the tree workspace is
+// 2^(d_tree-1) TLWE samples of 8 KiB per sample
 int lhe_lookup(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta, const int32_t *tab_a,
                const int32_t *tab_b, int n_tables, const int32_t *table_index, int32_t *out, bool keyswitch) {
-    // host checks, before the context is looked at
-    if (!tab_b || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    if (d_tree < 0 || d_tree > kLheMaxTree) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: d_tree must be 0 .. 6");
-    if (d_rot < 0 || d_rot > kLheMaxRot) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: d_rot must be 0 .. 10");
-    if (theta != 1 && theta != 2 && theta != 4) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: theta must be 1, 2 or 4");
-    if (theta > (1024 >> d_rot)) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: theta must not exceed box = N >> d_rot");
-    if (n_tables < 1 || ((long)n_tables << d_tree) > kMaxEncLuts) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: n_tables 2^d_tree must be 1 .. 262144");
-    THFHE_TRY(tree_validate_index(table_index, n_tables, count));
-    if (!set) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
-    if (d_tree + d_rot != set->d) return thfhe_fail(THFHE_E_INVALID, "lhe_lookup: d_tree + d_rot must equal the set's d");
-    THFHE_TRY(lhe_validate_range(set, first, count));
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (c != set->ctx) return thfhe_fail(THFHE_E_INVALID, "lhe: the set belongs to another context");
-    if (count == 0) return THFHE_OK;
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    const size_t leaves = (size_t)1 << d_tree, ws = d_tree ? leaves / 2 : 0;   // TLWE samples of tree workspace per sample
-    const size_t S_max = std::min({count, (size_t)65535, std::max<size_t>(1, c->tree_slice / std::max<size_t>(ws, 1))});
-    const size_t words = c->p.n + 1, rec = keyswitch ? words : 1025, tab_bytes = (size_t)n_tables * leaves * 4096;
-    int rc = c->d_tv.grow(tab_bytes);
-    if (!rc && tab_a) rc = c->d_tva.grow(tab_bytes);
-    if (!rc && ws) rc = c->d_lhe_a.grow(S_max * ws * 4096);
-    if (!rc && ws) rc = c->d_lhe_b.grow(S_max * ws * 4096);
-    if (!rc) rc = c->d_u.grow(S_max * theta * 1025 * sizeof(int32_t));
-    if (!rc && keyswitch) rc = c->stage.grow(S_max * theta * words);
-    if (!rc && table_index) rc = c->d_lut_idx.grow(S_max * sizeof(int32_t));
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int32_t>(), tab_b, tab_bytes, hipMemcpyHostToDevice, st));
-    if (tab_a) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int32_t>(), tab_a, tab_bytes, hipMemcpyHostToDevice, st));
-    const int32_t *const t_a = tab_a ? c->d_tva.as<int32_t>() : nullptr, *const t_b = c->d_tv.as<int32_t>();
-    const int32_t *const idx = table_index ? c->d_lut_idx.as<int32_t>() : nullptr;
-    int32_t *const res = keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>();
-    const size_t tab_stride = table_index ? leaves * 1024 : 0;   // without an index every sample reads table 0
-    for (size_t s0 = 0; s0 < count; s0 += S_max) {
-        const size_t S = std::min(S_max, count - s0);
-        const cplx *spec = set->spec.as<cplx>() + (first + s0) * lhe_sample_slots(c, set->d);
-        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        THFHE_TRY(enqueue_lhe_lookup(c, spec, set->d, S, d_tree, d_rot, theta, t_a, t_b, idx, tab_stride, keyswitch ? c->stage.out_ptr() : nullptr,
-                                     c->profiling && s0 == 0));
-        THFHE_HIP(hipMemcpyAsync(out + s0 * theta * rec, res, S * theta * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    THFHE_HIP(hipStreamSynchronize(st));
-    return THFHE_OK;
+    return ctx_lhe_lookup(c, set, first, count, d_tree, d_rot, theta, tab_a, tab_b, n_tables, table_index, out, keyswitch, kLheRules,
+                          [](size_t) { return (int)THFHE_OK; },
+                          [&](const cplx *spec, size_t S, const int32_t *t_a, const int32_t *t_b, const int32_t *idx, size_t tab_stride, int32_t *ks_out, bool prof) {
+                              return enqueue_lhe_lookup(c, spec, set->d, S, d_tree, d_rot, theta, t_a, t_b, idx, tab_stride, ks_out, prof);
+                          });
 }
 
 // compute units of the context's device, asked once per context
@@ -558,9 +489,8 @@ int lhe_wfa(thfhe_ctx *c, const thfhe_tgsw_set *const *sets, int n_sets, size_t 
     for (int i = 1; i < n_sets; i++)
         if (sets[i]->count != sets[0]->count || sets[i]->ctx != sets[0]->ctx)
             return thfhe_fail(THFHE_E_INVALID, "lhe_wfa: the sets must have one count and one context");
-    THFHE_TRY(lhe_validate_range(sets[0], first, count));
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (c != sets[0]->ctx) return thfhe_fail(THFHE_E_INVALID, "lhe: the set belongs to another context");
+    THFHE_TRY(ctx_lhe_validate_range(sets[0], first, count, kLheRules.range_text));
+    THFHE_TRY(ctx_lhe_validate_ctx(c, sets[0], kLheRules.ctx_text));
     if (count == 0) return THFHE_OK;
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
@@ -739,9 +669,8 @@ int lhe_demux(thfhe_ctx *c, const thfhe_tgsw_set *set, int bit, const int32_t *x
     if (bit < 0 || bit >= kLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "lhe_demux: bit must be 0 .. d-1");
     if (!set) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
     if (bit >= set->d) return thfhe_fail(THFHE_E_INVALID, "lhe_demux: bit must be 0 .. d-1");
-    THFHE_TRY(lhe_validate_range(set, 0, count));
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (c != set->ctx) return thfhe_fail(THFHE_E_INVALID, "lhe: the set belongs to another context");
+    THFHE_TRY(ctx_lhe_validate_range(set, 0, count, kLheRules.range_text));
+    THFHE_TRY(ctx_lhe_validate_ctx(c, set, kLheRules.ctx_text));
     if (count == 0) return THFHE_OK;
     DevLock lk(*c);
     if (lk.rc) return lk.rc;
@@ -785,9 +714,8 @@ int lhe_scatter(thfhe_ctx *c, const thfhe_tgsw_set *set, size_t first, size_t co
     THFHE_TRY(tree_validate_index(table_index, n_tables, count));
     if (!set) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
     if (d_tree + d_rot != set->d) return thfhe_fail(THFHE_E_INVALID, "lhe_scatter: d_tree + d_rot must equal the set's d");
-    THFHE_TRY(lhe_validate_range(set, first, count));
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (c != set->ctx) return thfhe_fail(THFHE_E_INVALID, "lhe: the set belongs to another context");
+    THFHE_TRY(ctx_lhe_validate_range(set, first, count, kLheRules.range_text));
+    THFHE_TRY(ctx_lhe_validate_ctx(c, set, kLheRules.ctx_text));
     const size_t leaves = (size_t)1 << d_tree, tab_words = (size_t)n_tables * leaves * 1024;
     if (count == 0) {   // nothing is written anywhere: the tables are their starting value
         std::fill_n(tab_a, tab_words, 0);

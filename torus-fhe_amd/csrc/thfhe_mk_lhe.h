@@ -1,5 +1,6 @@
-// thfhe_mk_lhe.h -- leveled CMux and table lookup on the Torus64 ring of degree 2048: kernels, launch chain and host bodies of
-// thfhe_mk_tgsw_set_create, thfhe_mk_lhe_cmux and thfhe_mk_lhe_lookup(_wo_keyswitch).  Included by thfhe_mk.hip INSIDE its second anonymous
+// thfhe_mk_lhe.h -- leveled CMux and table lookup on the Torus64 ring of degree 2048: kernels, launcher, the set's fill and this
+// engine's adaptors over the call bodies of thfhe_lhe_host.h for thfhe_mk_tgsw_set_create, thfhe_mk_lhe_cmux and
+// thfhe_mk_lhe_lookup(_wo_keyswitch).  Included by thfhe_mk.hip INSIDE its second anonymous
 // namespace, after thfhe_mk_ctx and mk_keyswitch: the contexts are the one-party sets on the batched rotation path (thfhe_rot2k.h), whose external
 // product is the ordinary TGSW (.) TLWE product (J/tgsw_3gen.jl:102-113).  A set keeps the spectra of count x d TGSW samples in the layout of that
 // path's key table with (sample d + bit) in the place of the key index, so a job's key chunks are chunk(step, rp, half) of kms_tlev_rotate_kernel
@@ -8,8 +9,7 @@
 // the table-free twisted halves of the one-pass kernels (wave_fft_*_tq_two): no T1 table in the LDS, 128 KiB per workgroup.
 #pragma once
 
-constexpr int kMkLheMaxBits = 16, kMkLheMaxTree = 6, kMkLheMaxRot = 11;
-constexpr int kMkLheN = 2048;
+constexpr int kMkLheN = 2048, kMkLheMaxRot = 11;   // ring degree and its log2
 
 struct MkLheDigits {
     int lg, bg, parts, lo_bits;
@@ -223,139 +223,69 @@ int mk_tgsw_set_fill(thfhe_mk_ctx *c, thfhe_mk_tgsw_set *set, const int64_t *tgs
     return stage_party_keys<2048>(*c, set->spec, (int)set->count, d, 2 * l, c->parts, c->pw, src);   // a slice per sample
 }
 
-int mk_lhe_validate_range(const thfhe_mk_tgsw_set *set, size_t first, size_t count) {
-    if (first > set->count || count > set->count - first) return thfhe_fail(THFHE_E_INVALID, "mk lhe: samples first .. first+count-1 are not all in the set");
-    return THFHE_OK;
-}
-
 int mk_launch_lhe_cmux(thfhe_mk_ctx *c, const MkLheCmuxArgs &a, size_t pairs, size_t samples) {
     hipLaunchKernelGGL(mk_lhe_cmux2k_kernel, dim3((unsigned)pairs, (unsigned)samples), dim3(512), 0, c->stream, a);
     THFHE_HIP(hipGetLastError());
     return THFHE_OK;
 }
 
+// what the shared leveled bodies (thfhe_lhe_host.h) admit on this engine: N = 2048, up to 4 096 samples per launch of the flat CMux
+constexpr LheRules<thfhe_mk_ctx> kMkLheRules{
+    kMkLheN, kMkLheMaxRot, 4096, mk_lhe_sample_slots,   // N, d_rot_max, cmux_slice, sample_slots
+    "mk tgsw set: d must be 1 .. 16",                                  // set_d_text
+    "mk tgsw set: count must be 1 .. 2^24",                            // set_count_text
+    "mk lhe: samples first .. first+count-1 are not all in the set",   // range_text
+    "mk lhe: the set belongs to another context",                      // ctx_text
+    "mk lhe_cmux: bit must be 0 .. d-1",                               // bit_text
+    "mk lhe_lookup: d_tree must be 0 .. 6",                            // d_tree_text
+    "mk lhe_lookup: d_rot must be 0 .. 11",                            // d_rot_text
+    "mk lhe_lookup: theta must be 1, 2 or 4",                          // theta_text
+    "mk lhe_lookup: theta must not exceed box = N >> d_rot",           // box_text
+    "mk lhe_lookup: n_tables 2^d_tree must be 1 .. 262144",            // n_tables_text
+    "mk lhe_lookup: d_tree + d_rot must equal the set's d"};           // d_sum_text
+
+// a CMux launch of the shared bodies on mk_lhe_cmux2k_kernel, over a set of d bits; io.pub is not looked at: a null mask already means a
+// trivial sample here
+int mk_lhe_cmux_level(thfhe_mk_ctx *c, int d, const LheCmuxIo<int64_t> &io, size_t pairs, size_t S) {
+    const MkLheCmuxArgs a{io.spec, c->d_tw.as<cplx>(), io.d0_a, io.d0_b, io.d1_a, io.d1_b, io.out_a, io.out_b, io.in_idx,
+                          io.in_sample, io.in_pair, io.out_sample, io.out_pair, mk_lhe_bit_slots(c), d, io.bit, mk_lhe_digits(c)};
+    return mk_launch_lhe_cmux(c, a, pairs, S);
+}
+
+// thfhe_mk_lhe_cmux: ctx_lhe_cmux (thfhe_lhe_host.h) on this engine's launch
 int mk_lhe_cmux(thfhe_mk_ctx *c, const thfhe_mk_tgsw_set *set, int bit, const int64_t *d1_a, const int64_t *d1_b, const int64_t *d0_a, const int64_t *d0_b,
                 int64_t *out_a, int64_t *out_b, size_t count) {
-    if (!d1_a || !d1_b || !d0_a || !d0_b || !out_a || !out_b) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    if (bit < 0 || bit >= kMkLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "mk lhe_cmux: bit must be 0 .. d-1");
-    if (!set) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
-    if (bit >= set->d) return thfhe_fail(THFHE_E_INVALID, "mk lhe_cmux: bit must be 0 .. d-1");
-    THFHE_TRY(mk_lhe_validate_range(set, 0, count));
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (c != set->ctx) return thfhe_fail(THFHE_E_INVALID, "mk lhe: the set belongs to another context");
-    if (count == 0) return THFHE_OK;
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    constexpr size_t kPoly = kMkLheN * sizeof(int64_t);
-    const size_t S_max = std::min<size_t>(count, 4096), bytes = S_max * kPoly;
-    for (DevBuf &b : c->d_lhe_in) THFHE_TRY(b.grow(bytes));
-    THFHE_TRY(c->d_lhe_a.grow(bytes));
-    THFHE_TRY(c->d_lhe_b.grow(bytes));
-    const int64_t *src[4] = {d0_a, d0_b, d1_a, d1_b};
-    for (size_t s0 = 0; s0 < count; s0 += S_max) {
-        const size_t S = std::min(S_max, count - s0);
-        for (int q = 0; q < 4; q++) THFHE_HIP(hipMemcpyAsync(c->d_lhe_in[q].as<int64_t>(), src[q] + s0 * kMkLheN, S * kPoly, hipMemcpyHostToDevice, c->stream));
-        MkLheCmuxArgs a{set->spec.as<cplx>() + s0 * mk_lhe_sample_slots(c, set->d), c->d_tw.as<cplx>(), c->d_lhe_in[0].as<int64_t>(), c->d_lhe_in[1].as<int64_t>(),
-                        c->d_lhe_in[2].as<int64_t>(), c->d_lhe_in[3].as<int64_t>(), c->d_lhe_a.as<int64_t>(), c->d_lhe_b.as<int64_t>(), nullptr,
-                        kMkLheN, 0, kMkLheN, 0, mk_lhe_bit_slots(c), set->d, bit, mk_lhe_digits(c)};
-        THFHE_TRY(mk_launch_lhe_cmux(c, a, 1, S));
-        THFHE_HIP(hipMemcpyAsync(out_a + s0 * kMkLheN, c->d_lhe_a.as<int64_t>(), S * kPoly, hipMemcpyDeviceToHost, c->stream));
-        THFHE_HIP(hipMemcpyAsync(out_b + s0 * kMkLheN, c->d_lhe_b.as<int64_t>(), S * kPoly, hipMemcpyDeviceToHost, c->stream));
-    }
-    THFHE_HIP(hipStreamSynchronize(c->stream));
-    return THFHE_OK;
+    return ctx_lhe_cmux(c, set, bit, d1_a, d1_b, d0_a, d0_b, out_a, out_b, count, kMkLheRules,
+                        [&](const LheCmuxIo<int64_t> &io, size_t S) { return mk_lhe_cmux_level(c, set->d, io, 1, S); });
 }
 
-// The launch chain of a leveled lookup over S samples, on device pointers only: the CMux tree, the rotation chain, the extraction of theta
-// coefficients into d_u and, with ks_out, the context's key switch of the S theta records into it.  spec: the spectra at the first sample.  Sample s
-// reads the 2^d_tree table polynomials at (t_a, t_b) + index(s) * tab_stride words, index(s) = idx[s] or s (t_a null: a public table).  The caller
-// has sized d_lhe_a / d_lhe_b (S 2^(d_tree-1) polynomials each), d_acc, d_u and ks_out.  prof: record the profiling events.
+// The launch chain of a leveled lookup over S samples: ctx_enqueue_lhe_lookup (thfhe_lhe_host.h) on mk_lhe_cmux2k_kernel, the rotation chain
+// into d_acc with the extraction of theta coefficients into d_u, and the context's key switch.  d: the bits of the set the spectra belong to.
+// The caller has sized d_acc too.
 int mk_enqueue_lhe_lookup(thfhe_mk_ctx *c, const cplx *spec, int d, size_t S, int d_tree, int d_rot, int theta, const int64_t *t_a, const int64_t *t_b,
                           const int32_t *idx, size_t tab_stride, int32_t *ks_out, bool prof) {
-    hipStream_t st = c->stream;
-    const size_t leaves = (size_t)1 << d_tree, ws = d_tree ? leaves / 2 : 0;   // TLWE samples of tree workspace per sample
-    int64_t *const w_a = c->d_lhe_a.as<int64_t>(), *const w_b = c->d_lhe_b.as<int64_t>();
-    if (prof) THFHE_HIP(hipEventRecord(c->ev[0], st));
-    // the tree: level t pairs neighbours on bit d_rot + t; level 0 reads the table, the later levels run in place on the workspace -- the result
-    // of pair p of level t lies at slot p 2^t of the sample, the slot of its own d0, which no other workgroup of the launch touches
-    for (int t = 0; t < d_tree; t++) {
-        MkLheCmuxArgs a{spec, c->d_tw.as<cplx>(), nullptr, nullptr, nullptr, nullptr, w_a, w_b, nullptr, 0, 0, ws * kMkLheN, 0, mk_lhe_bit_slots(c), d, d_rot + t,
-                        mk_lhe_digits(c)};
-        if (t == 0) {
-            a.d0_a = t_a, a.d0_b = t_b, a.d1_a = t_a ? t_a + kMkLheN : nullptr, a.d1_b = t_b + kMkLheN;
-            a.in_idx = idx, a.in_sample = tab_stride, a.in_pair = 2 * kMkLheN, a.out_pair = kMkLheN;
-        } else {
-            const size_t step = (size_t)kMkLheN << t;   // words between the d0 slots of neighbouring pairs
-            a.d0_a = w_a, a.d0_b = w_b, a.d1_a = w_a + step / 2, a.d1_b = w_b + step / 2;
-            a.in_sample = ws * kMkLheN, a.in_pair = step, a.out_pair = step;
-        }
-        THFHE_TRY(mk_launch_lhe_cmux(c, a, leaves >> (t + 1), S));
-    }
-    if (prof) THFHE_HIP(hipEventRecord(c->ev[1], st));
-    int64_t *const acc = c->d_acc.as<int64_t>();
-    MkLheRotArgs r{spec, c->d_tw.as<cplx>(), d_tree ? w_a : t_a, d_tree ? w_b : t_b, d_tree ? nullptr : idx, d_tree ? ws * kMkLheN : tab_stride, acc,
-                   mk_lhe_bit_slots(c), d, d_rot, kMkLheN >> d_rot, mk_lhe_digits(c)};
-    hipLaunchKernelGGL(mk_lhe_rotate2k_kernel, dim3((unsigned)S), dim3(512), 0, st, r);
-    hipLaunchKernelGGL(mk_extract_at_kernel, dim3((unsigned)S, (unsigned)theta), dim3(256), 0, st, (const int64_t *)acc, c->d_u.as<int32_t>(), (long)S, kMkLheN,
-                       theta);
-    THFHE_HIP(hipGetLastError());
-    if (prof) THFHE_HIP(hipEventRecord(c->ev[2], st));
-    if (ks_out) THFHE_TRY(mk_keyswitch(c, c->d_u.as<int32_t>(), ks_out, S * theta));
-    if (prof) {
-        THFHE_HIP(hipEventRecord(c->ev[3], st));
-        c->ev_valid = true;
-    }
-    return THFHE_OK;
+    return ctx_enqueue_lhe_lookup(
+        c, spec, S, d_tree, d_rot, theta, t_a, t_b, idx, tab_stride, ks_out, prof, kMkLheRules,
+        [&](const LheCmuxIo<int64_t> &io, size_t pairs) { return mk_lhe_cmux_level(c, d, io, pairs, S); },
+        [&](const int64_t *src_a, const int64_t *src_b, const int32_t *src_idx, size_t src_stride) {
+            int64_t *const acc = c->d_acc.as<int64_t>();
+            const MkLheRotArgs r{spec, c->d_tw.as<cplx>(), src_a, src_b, src_idx, src_stride, acc, mk_lhe_bit_slots(c), d, d_rot, kMkLheN >> d_rot, mk_lhe_digits(c)};
+            hipLaunchKernelGGL(mk_lhe_rotate2k_kernel, dim3((unsigned)S), dim3(512), 0, c->stream, r);
+            hipLaunchKernelGGL(mk_extract_at_kernel, dim3((unsigned)S, (unsigned)theta), dim3(256), 0, c->stream, (const int64_t *)acc, c->d_u.as<int32_t>(), (long)S,
+                               kMkLheN, theta);
+            THFHE_HIP(hipGetLastError());
+            return (int)THFHE_OK;
+        },
+        [&](int32_t *out, size_t records) { return mk_keyswitch(c, c->d_u.as<int32_t>(), out, records); });
 }
 
-// thfhe_mk_lhe_lookup (keyswitch) / thfhe_mk_lhe_lookup_wo_keyswitch: out = count x theta records of n+1 (resp. N+1) words, in slices of at most
-// tree_slice / 2^(d_tree-1) samples (the tree workspace: 2^(d_tree-1) accumulators of 32 KiB per sample) and 65 535 samples
+// thfhe_mk_lhe_lookup (keyswitch) / thfhe_mk_lhe_lookup_wo_keyswitch: ctx_lhe_lookup (thfhe_lhe_host.h) on this engine's chain and its
+// accumulators; the tree workspace is 2^(d_tree-1) accumulators of 32 KiB per sample
 int mk_lhe_lookup(thfhe_mk_ctx *c, const thfhe_mk_tgsw_set *set, size_t first, size_t count, int d_tree, int d_rot, int theta, const int64_t *tab_a,
                   const int64_t *tab_b, int n_tables, const int32_t *table_index, int32_t *out, bool keyswitch) {
-    // host checks, before the context is looked at, in the order of thfhe_lhe_lookup
-    if (!tab_b || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    if (d_tree < 0 || d_tree > kMkLheMaxTree) return thfhe_fail(THFHE_E_INVALID, "mk lhe_lookup: d_tree must be 0 .. 6");
-    if (d_rot < 0 || d_rot > kMkLheMaxRot) return thfhe_fail(THFHE_E_INVALID, "mk lhe_lookup: d_rot must be 0 .. 11");
-    if (theta != 1 && theta != 2 && theta != 4) return thfhe_fail(THFHE_E_INVALID, "mk lhe_lookup: theta must be 1, 2 or 4");
-    if (theta > (kMkLheN >> d_rot)) return thfhe_fail(THFHE_E_INVALID, "mk lhe_lookup: theta must not exceed box = N >> d_rot");
-    if (n_tables < 1 || ((long)n_tables << d_tree) > kMaxEncLuts) return thfhe_fail(THFHE_E_INVALID, "mk lhe_lookup: n_tables 2^d_tree must be 1 .. 262144");
-    THFHE_TRY(tree_validate_index(table_index, n_tables, count));
-    if (!set) return thfhe_fail(THFHE_E_INVALID, "null tgsw set");
-    if (d_tree + d_rot != set->d) return thfhe_fail(THFHE_E_INVALID, "mk lhe_lookup: d_tree + d_rot must equal the set's d");
-    THFHE_TRY(mk_lhe_validate_range(set, first, count));
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    if (c != set->ctx) return thfhe_fail(THFHE_E_INVALID, "mk lhe: the set belongs to another context");
-    if (count == 0) return THFHE_OK;
-    DevLock lk(*c);
-    if (lk.rc) return lk.rc;
-    constexpr size_t kPoly = kMkLheN * sizeof(int64_t);
-    const size_t leaves = (size_t)1 << d_tree, ws = d_tree ? leaves / 2 : 0;   // TLWE samples of tree workspace per sample
-    const size_t S_max = std::min({count, (size_t)65535, std::max<size_t>(1, c->tree_slice / std::max<size_t>(ws, 1))});
-    const size_t words = c->rec_words(), rec = keyswitch ? words : kMkLheN + 1, tab_bytes = (size_t)n_tables * leaves * kPoly;
-    int rc = c->d_tv.grow(tab_bytes);
-    if (!rc && tab_a) rc = c->d_tva.grow(tab_bytes);
-    if (!rc && ws) rc = c->d_lhe_a.grow(S_max * ws * kPoly);
-    if (!rc && ws) rc = c->d_lhe_b.grow(S_max * ws * kPoly);
-    if (!rc) rc = c->d_acc.grow(S_max * 2 * kPoly);
-    if (!rc) rc = c->d_u.grow(S_max * theta * (kMkLheN + 1) * sizeof(int32_t));
-    if (!rc && keyswitch) rc = c->stage.grow(S_max * theta * words);
-    if (!rc && table_index) rc = c->d_lut_idx.grow(S_max * sizeof(int32_t));
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    THFHE_HIP(hipMemcpyAsync(c->d_tv.as<int64_t>(), tab_b, tab_bytes, hipMemcpyHostToDevice, st));
-    if (tab_a) THFHE_HIP(hipMemcpyAsync(c->d_tva.as<int64_t>(), tab_a, tab_bytes, hipMemcpyHostToDevice, st));
-    const int64_t *const t_a = tab_a ? c->d_tva.as<int64_t>() : nullptr, *const t_b = c->d_tv.as<int64_t>();
-    const int32_t *const idx = table_index ? c->d_lut_idx.as<int32_t>() : nullptr;
-    int32_t *const res = keyswitch ? c->stage.out_ptr() : c->d_u.as<int32_t>();
-    const size_t tab_stride = table_index ? leaves * kMkLheN : 0;   // without an index every sample reads table 0
-    for (size_t s0 = 0; s0 < count; s0 += S_max) {
-        const size_t S = std::min(S_max, count - s0);
-        const cplx *spec = set->spec.as<cplx>() + (first + s0) * mk_lhe_sample_slots(c, set->d);
-        if (table_index) THFHE_HIP(hipMemcpyAsync(c->d_lut_idx.as<int32_t>(), table_index + s0, S * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        THFHE_TRY(mk_enqueue_lhe_lookup(c, spec, set->d, S, d_tree, d_rot, theta, t_a, t_b, idx, tab_stride, keyswitch ? c->stage.out_ptr() : nullptr,
-                                        c->profiling && s0 == 0));
-        THFHE_HIP(hipMemcpyAsync(out + s0 * theta * rec, res, S * theta * rec * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    THFHE_HIP(hipStreamSynchronize(st));
-    return THFHE_OK;
+    return ctx_lhe_lookup(c, set, first, count, d_tree, d_rot, theta, tab_a, tab_b, n_tables, table_index, out, keyswitch, kMkLheRules,
+                          [&](size_t S_max) { return c->d_acc.grow(S_max * 2 * kMkLheN * sizeof(int64_t)); },
+                          [&](const cplx *spec, size_t S, const int64_t *t_a, const int64_t *t_b, const int32_t *idx, size_t tab_stride, int32_t *ks_out, bool prof) {
+                              return mk_enqueue_lhe_lookup(c, spec, set->d, S, d_tree, d_rot, theta, t_a, t_b, idx, tab_stride, ks_out, prof);
+                          });
 }

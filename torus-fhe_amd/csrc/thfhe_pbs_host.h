@@ -1,6 +1,7 @@
 // thfhe_pbs_host.h -- the programmable-bootstrap call bodies the single-key (thfhe_sk.hip) and 3-gen multi-key (thfhe_mk.hip) engines have in
 // common: the flat LUT / encrypted-LUT call, the flat multi-value call, the host checks, the body and the slice loop of a flat tree call,
-// dag_execute's ensure, and the grouped TREE / TREE_MV / MV / DENSE part of a gate-DAG run (table uploads, slice rule, reserve loop, group bodies).
+// dag_execute's ensure, and the grouped TREE / TREE_MV / MV / DENSE part of a gate-DAG run (table uploads, slice rule, reserve loop, group bodies);
+// the leveled call bodies (TGSW sets, CMux, lookup) are thfhe_lhe_host.h's.
 // Function templates over the engine's context, like ctx_staged (thfhe_devctx.h); what differs per engine -- its workspace rules, its PBS
 // stage, its tree chain with its multi-value record -- comes in as a callable.  The engine keeps its locks, key checks, refusals, SELECT /
 // leveled / CB groups and profiling wrapper.  The table word (Torus32 / Torus64) follows the table pointer or is named (dag_upload_families<T>,

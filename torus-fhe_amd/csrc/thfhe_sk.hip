@@ -42,6 +42,7 @@
 #include "thfhe_launch_plan.h"
 #include "thfhe_pack.h"
 #include "thfhe_pbs_host.h"
+#include "thfhe_lhe_host.h"   // builds on thfhe_pbs_host.h
 #include "thfhe_ring_schedule.h"
 
 using namespace thfhe;
@@ -1319,32 +1320,10 @@ int thfhe_keyswitch(thfhe_ctx *c, const int32_t *in_N1, int32_t *out, size_t cou
 }
 
 int thfhe_tgsw_set_create(thfhe_ctx *c, const int32_t *tgsw, size_t count, int d, thfhe_tgsw_set **out) {
-    if (!tgsw || !out) return thfhe_fail(THFHE_E_INVALID, "null argument");
-    *out = nullptr;
-    if (d < 1 || d > kLheMaxBits) return thfhe_fail(THFHE_E_INVALID, "tgsw set: d must be 1 .. 16");
-    if (count < 1 || count > ((size_t)1 << 24)) return thfhe_fail(THFHE_E_INVALID, "tgsw set: count must be 1 .. 2^24");
-    if (!c) return thfhe_fail(THFHE_E_INVALID, "null ctx");
-    std::unique_ptr<thfhe_tgsw_set> set(new (std::nothrow) thfhe_tgsw_set);
-    if (!set) return thfhe_fail(THFHE_E_NOMEM, "out of host memory");
-    set->ctx = c, set->count = count, set->d = d;
-    const int rc = tgsw_set_fill(c, set.get(), tgsw);
-    if (rc) {   // nothing is left behind: the spectra are freed on the context's device
-        (void)hipSetDevice(c->device);
-        return rc;
-    }
-    *out = set.release();
-    return THFHE_OK;
+    return ctx_tgsw_set_create(c, tgsw, count, d, out, kLheRules, tgsw_set_fill);
 }
 
-void thfhe_tgsw_set_destroy(thfhe_tgsw_set *set) {
-    if (!set) return;
-    {
-        std::lock_guard<std::mutex> g(set->ctx->mu);   // a call still running on another thread finishes first
-        (void)hipSetDevice(set->ctx->device);
-        (void)hipStreamSynchronize(set->ctx->stream);
-    }
-    delete set;
-}
+void thfhe_tgsw_set_destroy(thfhe_tgsw_set *set) { ctx_tgsw_set_destroy(set); }
 
 int thfhe_lhe_cmux(thfhe_ctx *c, const thfhe_tgsw_set *set, int bit, const int32_t *d1_a, const int32_t *d1_b, const int32_t *d0_a, const int32_t *d0_b,
                    int32_t *out_a, int32_t *out_b, size_t count) {

@@ -572,6 +572,52 @@ class _Handle:
         return buf.value.decode()
 
 
+class _TgswSetBase(_Handle):
+    """What TgswSet and MKTgswSet share: the address bits of `count` samples, d bits each, resident on the device of the key `ck` in the key's
+    ring word.  A subclass names the layout of the samples: _layout(params) = (words per bit, the shape text of the refusal)."""
+
+    def __init__(self, ck, samples, d):
+        d = int(d)
+        a = np.ascontiguousarray(samples, ck._tv_dtype)
+        per_bit, shape = self._layout(ck.params)
+        if d < 1 or a.size == 0 or a.size % (per_bit * d):
+            raise ValueError(f"samples: expected {shape} with d = {d}")
+        self.ck, self.d, self.count = ck, d, a.size // (per_bit * d)   # the key is kept alive for as long as the set
+        h = _vp()
+        _check(ck._fn("tgsw_set_create")(ck.h, ck._ptv(a), self.count, d, C.byref(h)))
+        self._own(h, ck._fn("tgsw_set_destroy"))
+
+    @classmethod
+    def _adopt(cls, ck, h, count, d):
+        """A set the library made itself (thfhe_circuit_bootstrap)."""
+        self = cls.__new__(cls)
+        self.ck, self.d, self.count = ck, d, count
+        self._own(h, ck._fn("tgsw_set_destroy"))
+        return self
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class TgswSet(_TgswSetBase):
+    """TGSW samples resident on a CloudKey's device (thfhe_tgsw_set_create): the address bits of `count` samples, d bits each."""
+
+    @staticmethod
+    def _layout(p):
+        return 2 * p.l * 2 * p.N, f"int32[count * d][{2 * p.l}][2][{p.N}]"
+
+
+class MKTgswSet(_TgswSetBase):
+    """TGSW samples resident on an MKCloudKey's device (thfhe_mk_tgsw_set_create, DESIGN 4.26): the address bits of `count` samples, d bits each."""
+
+    @staticmethod
+    def _layout(p):
+        return 4 * p.l * p.N, f"int64[count * d][4][{p.l}][{p.N}]"
+
+
 class _EvalKey(_Handle):
     """What CloudKey and MKCloudKey share: the same calls under the C symbol prefix `_prefix` (thfhe_ / thfhe_mk_)."""
 
@@ -676,6 +722,54 @@ class _EvalKey(_Handle):
         out = np.empty((count, _theta_records(theta), self.words if keyswitch else self.params.N + 1), np.int32)
         fn = self._fn("lut_bootstrap" if keyswitch else "lut_bootstrap_wo_keyswitch")
         _check(fn(self.h, C.byref(spec), self._ptv(tv), tv.shape[0], _p32(idx), p[0], p[1], p[2], _p32(out), count))
+        return out
+
+    # -- leveled CMux and table lookup on TGSW-encrypted address bits (tgsw_set_create, lhe_cmux, lhe_lookup), in the ring's word:
+    #    int32 and N = 1024 on a CloudKey, int64 and N = 2048 on an MKCloudKey -------------------------------------------------------------------
+    _tgsw_set_class = None   # TgswSet / MKTgswSet
+
+    def tgsw_set(self, samples, d):
+        """Device-resident address bits of the samples, kept as spectra; each key class states its layout and sizes."""
+        return self._tgsw_set_class(self, samples, d)
+
+    def lhe_cmux(self, tset, bit, d1_a, d1_b, d0_a, d0_b):
+        """(out_a, out_b) [count][N] in the ring's word: sample s gets d0[s] + C_(s,bit) (.) (d1[s] - d0[s])."""
+        N = self.params.N
+        arrs = [np.ascontiguousarray(v, self._tv_dtype).reshape(-1, N) for v in (d1_a, d1_b, d0_a, d0_b)]
+        _same_count(*arrs)
+        out_a, out_b = np.empty_like(arrs[0]), np.empty_like(arrs[0])
+        _check(self._fn("lhe_cmux")(self.h, tset.h, int(bit), *[self._ptv(v) for v in arrs], self._ptv(out_a), self._ptv(out_b), arrs[0].shape[0]))
+        return out_a, out_b
+
+    def lhe_lookup(self, tset, tab_b, *, d_tree, d_rot, theta=1, tab_a=None, table_index=None, first=0, count=None):
+        """Leveled lookup in the table tab_b [n_tables][2^d_tree][N] in the ring's word; returns key-switched records int32[count, theta, n+1]."""
+        return self._lhe_lookup(tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, True)
+
+    def lhe_lookup_wo_keyswitch(self, tset, tab_b, *, d_tree, d_rot, theta=1, tab_a=None, table_index=None, first=0, count=None):
+        """lhe_lookup without the key switch: int32[count, theta, N+1] records under the ring key."""
+        return self._lhe_lookup(tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, False)
+
+    def _lhe_lookup(self, tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, keyswitch):
+        N = self.params.N
+        if not 0 <= int(d_tree) <= 6:
+            raise ValueError("d_tree must be 0 .. 6")
+        leaves = 1 << int(d_tree)
+        tab_b = np.ascontiguousarray(tab_b, self._tv_dtype)
+        if tab_b.size == 0 or tab_b.size % (leaves * N):
+            raise ValueError(f"tab_b: expected {np.dtype(self._tv_dtype).name}[n_tables][{leaves}][{N}]")
+        if tab_a is not None:
+            tab_a = np.ascontiguousarray(tab_a, self._tv_dtype)
+            if tab_a.size != tab_b.size:
+                raise ValueError("tab_a and tab_b differ in size")
+        first = int(first)
+        count = tset.count - first if count is None else int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        idx = _index("table_index", table_index, count)
+        out = np.empty((count, _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
+        fn = self._fn("lhe_lookup" if keyswitch else "lhe_lookup_wo_keyswitch")
+        _check(fn(self.h, tset.h, first, count, int(d_tree), int(d_rot), int(theta), None if tab_a is None else self._ptv(tab_a), self._ptv(tab_b),
+                  tab_b.size // (leaves * N), _p32(idx), _p32(out)))
         return out
 
     def _lut_args(self, ins, weights, bias, theta, what=None):
@@ -865,6 +959,7 @@ class CloudKey(_EvalKey):
     """
 
     _prefix = "thfhe_"
+    _tgsw_set_class = TgswSet
 
     def __init__(self, params, bk_coeff, ksk, device=0):
         self.params = params
@@ -1063,53 +1158,22 @@ class CloudKey(_EvalKey):
         ctxs = (self.h, None if pack is None else pack.h) + tuple(more_ctxs)   # thfhe_dag_run_cb_batch: the level-2 context after the two
         return self._dag_run("dag_run_tree_batch / dag_run_mv_batch", fn, ctxs, input_records, nodes, 6, earlier, out_wires, n_stats)
 
-    # -- leveled table lookup on TGSW-encrypted address bits (thfhe_tgsw_set_create, thfhe_lhe_cmux, thfhe_lhe_lookup) ----------
+    # -- leveled table lookup on TGSW-encrypted address bits (thfhe_tgsw_set_create, thfhe_lhe_cmux, thfhe_lhe_lookup): the bodies are
+    #    _EvalKey's, the wording about this ring's layout and sizes is kept here ----------------------------------------------------------------
     def tgsw_set(self, samples, d):
         """Device-resident address bits: samples int32[count * d][2l][2][N] (SecretKeySet.tgsw_encrypt of the bits, sample-major: bit i of sample s
         is row s d + i), kept as spectra, count d 2l 32 KiB.  Returns a TgswSet: close() it (or use `with`) before this key is closed."""
-        return TgswSet(self, samples, d)
+        return super().tgsw_set(samples, d)
 
     def lhe_cmux(self, tset, bit, d1_a, d1_b, d0_a, d0_b):
         """(out_a, out_b) int32[count][N]: sample s gets d0[s] + C_(s,bit) (.) (d1[s] - d0[s]) -- d1 where its address bit `bit` is 1, else d0."""
-        N = self.params.N
-        arrs = [np.ascontiguousarray(v, np.int32).reshape(-1, N) for v in (d1_a, d1_b, d0_a, d0_b)]
-        _same_count(*arrs)
-        out_a, out_b = np.empty_like(arrs[0]), np.empty_like(arrs[0])
-        _check(lib().thfhe_lhe_cmux(self.h, tset.h, int(bit), *[_p32(v) for v in arrs], _p32(out_a), _p32(out_b), arrs[0].shape[0]))
-        return out_a, out_b
+        return super().lhe_cmux(tset, bit, d1_a, d1_b, d0_a, d0_b)
 
     def lhe_lookup(self, tset, tab_b, *, d_tree, d_rot, theta=1, tab_a=None, table_index=None, first=0, count=None):
         """Leveled lookup of samples first .. first+count-1 of the set (default: all from `first`) in the table tab_b int32[n_tables][2^d_tree][N]
         (thfhe.lut.lhe_table; tab_a: the masks of an encrypted table, None: public): d_tree + d_rot CMuxes, theta functions per sample.
         Returns key-switched records int32[count, theta, n+1]."""
         return self._lhe_lookup(tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, True)
-
-    def lhe_lookup_wo_keyswitch(self, tset, tab_b, *, d_tree, d_rot, theta=1, tab_a=None, table_index=None, first=0, count=None):
-        """lhe_lookup without the key switch: int32[count, theta, N+1] records under the ring key."""
-        return self._lhe_lookup(tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, False)
-
-    def _lhe_lookup(self, tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, keyswitch):
-        N = self.params.N
-        if not 0 <= int(d_tree) <= 6:
-            raise ValueError("d_tree must be 0 .. 6")
-        leaves = 1 << int(d_tree)
-        tab_b = np.ascontiguousarray(tab_b, np.int32)
-        if tab_b.size == 0 or tab_b.size % (leaves * N):
-            raise ValueError(f"tab_b: expected int32[n_tables][{leaves}][{N}]")
-        if tab_a is not None:
-            tab_a = np.ascontiguousarray(tab_a, np.int32)
-            if tab_a.size != tab_b.size:
-                raise ValueError("tab_a and tab_b differ in size")
-        first = int(first)
-        count = tset.count - first if count is None else int(count)
-        if first < 0 or count < 0:
-            raise ValueError("first and count must not be negative")
-        idx = _index("table_index", table_index, count)
-        out = np.empty((count, _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
-        fn = lib().thfhe_lhe_lookup if keyswitch else lib().thfhe_lhe_lookup_wo_keyswitch
-        _check(fn(self.h, tset.h, first, count, int(d_tree), int(d_rot), int(theta), _p32(tab_a), _p32(tab_b), tab_b.size // (leaves * N), _p32(idx),
-                  _p32(out)))
-        return out
 
     # -- layered automata on TGSW-encrypted bits (thfhe_lhe_wfa; DESIGN 4.16) ------------------------------------------------------------------
     def lhe_wfa(self, sets, trans, step_bit, fin_b, start, *, theta=1, fin_a=None, table_index=None, first=0, count=None):
@@ -1286,36 +1350,6 @@ class CloudKey(_EvalKey):
 
 
 # ---- the reference's single-key gate API (gates.jl:15-177), batched over the leading axis -------------
-class TgswSet(_Handle):
-    """TGSW samples resident on a CloudKey's device (thfhe_tgsw_set_create): the address bits of `count` samples, d bits each."""
-
-    def __init__(self, ck, samples, d):
-        p = ck.params
-        d = int(d)
-        a = np.ascontiguousarray(samples, np.int32)
-        per_bit = 2 * p.l * 2 * p.N
-        if d < 1 or a.size == 0 or a.size % (per_bit * d):
-            raise ValueError(f"samples: expected int32[count * d][{2 * p.l}][2][{p.N}] with d = {d}")
-        self.ck, self.d, self.count = ck, d, a.size // (per_bit * d)   # the key is kept alive for as long as the set
-        h = _vp()
-        _check(lib().thfhe_tgsw_set_create(ck.h, _p32(a), self.count, d, C.byref(h)))
-        self._own(h, lib().thfhe_tgsw_set_destroy)
-
-    @classmethod
-    def _adopt(cls, ck, h, count, d):
-        """A set the library made itself (thfhe_circuit_bootstrap)."""
-        self = cls.__new__(cls)
-        self.ck, self.d, self.count = ck, d, count
-        self._own(h, lib().thfhe_tgsw_set_destroy)
-        return self
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
 def gate_nand(ck, x, y): return ck.gates(NAND, x, y)
 def gate_or(ck, x, y): return ck.gates(OR, x, y)
 def gate_and(ck, x, y): return ck.gates(AND, x, y)
@@ -1353,6 +1387,7 @@ class MKCloudKey(_EvalKey):
 
     _prefix = "thfhe_mk_"
     _tv_dtype = np.int64   # the 3-gen accumulator is Torus64
+    _tgsw_set_class = MKTgswSet
 
     def __init__(self, params, bk_coeff, ksk, device=0):
         self.params = p = params
@@ -1516,22 +1551,17 @@ class MKCloudKey(_EvalKey):
         fn = lib().thfhe_mk_dag_run_tree_batch if _dense is None else lib().thfhe_mk_dag_run_dense_batch
         return self._dag_run("dag_run_tree_batch", fn, (self.h,), input_records, nodes, 6, families, out_wires)
 
-    # -- leveled CMux and table lookup on the ring of degree 2048 (thfhe_mk_tgsw_set_create, thfhe_mk_lhe_cmux, thfhe_mk_lhe_lookup) --
+    # -- leveled CMux and table lookup on the ring of degree 2048 (thfhe_mk_tgsw_set_create, thfhe_mk_lhe_cmux, thfhe_mk_lhe_lookup):
+    #    the bodies are _EvalKey's, the wording about this ring's layout and sizes is kept here ---------------------------------------------------
     def tgsw_set(self, samples, d):
         """Device-resident address bits: samples int64[count * d][4][l][N] (MKSecretKeySet.tgsw_encrypt of the bits, sample-major: bit i of sample s
         is row s d + i), kept as spectra, 1 MiB per bit on the CB sets.  Returns an MKTgswSet: close() it (or use `with`) before this key is closed.
         One-party contexts on the batched N = 2048 path only (CB_PARAM_SETS)."""
-        return MKTgswSet(self, samples, d)
+        return super().tgsw_set(samples, d)
 
     def lhe_cmux(self, tset, bit, d1_a, d1_b, d0_a, d0_b):
         """(out_a, out_b) int64[count][N]: sample s gets d0[s] + C_(s,bit) (.) (d1[s] - d0[s]) -- d1 where its address bit `bit` is 1, else d0."""
-        N = self.params.N
-        arrs = [np.ascontiguousarray(v, np.int64).reshape(-1, N) for v in (d1_a, d1_b, d0_a, d0_b)]
-        _same_count(*arrs)
-        out_a, out_b = np.empty_like(arrs[0]), np.empty_like(arrs[0])
-        p64 = lambda v: v.ctypes.data_as(_i64p)
-        _check(lib().thfhe_mk_lhe_cmux(self.h, tset.h, int(bit), *[p64(v) for v in arrs], p64(out_a), p64(out_b), arrs[0].shape[0]))
-        return out_a, out_b
+        return super().lhe_cmux(tset, bit, d1_a, d1_b, d0_a, d0_b)
 
     def lhe_lookup(self, tset, tab_b, *, d_tree, d_rot, theta=1, tab_a=None, table_index=None, first=0, count=None):
         """Leveled lookup of samples first .. first+count-1 of the set (default: all from `first`) in the table tab_b int64[n_tables][2^d_tree][N]
@@ -1539,58 +1569,9 @@ class MKCloudKey(_EvalKey):
         functions per sample.  Returns key-switched records int32[count, theta, n+1]."""
         return self._lhe_lookup(tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, True)
 
-    def lhe_lookup_wo_keyswitch(self, tset, tab_b, *, d_tree, d_rot, theta=1, tab_a=None, table_index=None, first=0, count=None):
-        """lhe_lookup without the key switch: int32[count, theta, N+1] records under the ring key."""
-        return self._lhe_lookup(tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, False)
-
-    def _lhe_lookup(self, tset, tab_b, d_tree, d_rot, theta, tab_a, table_index, first, count, keyswitch):
-        N = self.params.N
-        if not 0 <= int(d_tree) <= 6:
-            raise ValueError("d_tree must be 0 .. 6")
-        leaves = 1 << int(d_tree)
-        tab_b = np.ascontiguousarray(tab_b, np.int64)
-        if tab_b.size == 0 or tab_b.size % (leaves * N):
-            raise ValueError(f"tab_b: expected int64[n_tables][{leaves}][{N}]")
-        if tab_a is not None:
-            tab_a = np.ascontiguousarray(tab_a, np.int64)
-            if tab_a.size != tab_b.size:
-                raise ValueError("tab_a and tab_b differ in size")
-        first = int(first)
-        count = tset.count - first if count is None else int(count)
-        if first < 0 or count < 0:
-            raise ValueError("first and count must not be negative")
-        idx = _index("table_index", table_index, count)
-        out = np.empty((count, _theta_records(theta), self.words if keyswitch else N + 1), np.int32)
-        fn = lib().thfhe_mk_lhe_lookup if keyswitch else lib().thfhe_mk_lhe_lookup_wo_keyswitch
-        _check(fn(self.h, tset.h, first, count, int(d_tree), int(d_rot), int(theta), None if tab_a is None else tab_a.ctypes.data_as(_i64p),
-                  tab_b.ctypes.data_as(_i64p), tab_b.size // (leaves * N), _p32(idx), _p32(out)))
-        return out
-
     def rotation_kernel_name(self, rotations):
         """The blind-rotation kernel a batch of `rotations` is dispatched to, as mk_launch_rotation in thfhe_mk.hip decides it."""
         return self._kernel_name(lib().thfhe_mk_rotation_kernel_name, int(rotations))
-
-
-class MKTgswSet(_Handle):
-    """TGSW samples resident on an MKCloudKey's device (thfhe_mk_tgsw_set_create, DESIGN 4.26): the address bits of `count` samples, d bits each."""
-
-    def __init__(self, ck, samples, d):
-        p = ck.params
-        d = int(d)
-        a = np.ascontiguousarray(samples, np.int64)
-        per_bit = 4 * p.l * p.N
-        if d < 1 or a.size == 0 or a.size % (per_bit * d):
-            raise ValueError(f"samples: expected int64[count * d][4][{p.l}][{p.N}] with d = {d}")
-        self.ck, self.d, self.count = ck, d, a.size // (per_bit * d)   # the key is kept alive for as long as the set
-        h = _vp()
-        _check(lib().thfhe_mk_tgsw_set_create(ck.h, a.ctypes.data_as(_i64p), self.count, d, C.byref(h)))
-        self._own(h, lib().thfhe_mk_tgsw_set_destroy)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 class PolyMac(_Handle):
